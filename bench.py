@@ -9,6 +9,8 @@ when N > 1) of the M1 12-level Wave-U-Net at BASELINE.json configs[1]: fp32, bat
   `python bench.py --gpus N` re-executes itself under torch.distributed.run on 127.0.0.1 (one rank per GPU;
   on a box with fewer GPUs than ranks the ranks share devices and the exchange runs over gloo).
   --dry-run stops after process-group initialisation and the tuning-table broadcast (works without a GPU).
+  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs), so that two builds
+  can be compared output for output.
 
 One "step" = one `sess.run([separator_solver, ...])` of /root/reference/Training.py:105:
 get_output, MSE loss, full backward, TF-Adam update.  Rank 0 prints ONE JSON line.
@@ -256,6 +258,34 @@ def cpu_baseline(cfg_over, params, mix, targets, names, gpu, budget_s=45.0):
     return base, parity
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # array data of --dump-outputs: under 64 MB in all with the .npy headers
+
+
+def dump_outputs(out_dir, sep, loss):
+    """--dump-outputs: what a caller of the timed step receives from its last run, as out_dir/<name>.npy (float32) --
+    `loss` (0-dim), `output_<source>` ([B, Tout, C] each, source_names order), `gradients` (the flat gradient arena
+    of that step) and `parameters` (the flat arena after its Adam update).  Smallest first, an array larger than its
+    share of what is left of DUMP_BUDGET_BYTES is replaced by a fixed sample, `<name>_sample`: the values at sorted
+    flat positions drawn without replacement by numpy's default_rng(0), the same number for every sampled array, so
+    equal-sized arrays share positions."""
+    outs = sep._outs[sep._last_key]
+    arrays = [("loss", loss.detach().cpu().numpy())]
+    arrays += [("output_" + n, outs[i].cpu().numpy()) for i, n in enumerate(sep.source_names)]
+    arrays += [("gradients", sep.grads.cpu().numpy()), ("parameters", sep.params.cpu().numpy())]
+    arrays = sorted(((n, np.asarray(a, dtype=np.float32)) for n, a in arrays), key=lambda na: na[1].nbytes)
+    os.makedirs(out_dir, exist_ok=True)
+    left, whole = DUMP_BUDGET_BYTES, 0
+    while whole < len(arrays) and arrays[whole][1].nbytes <= left // (len(arrays) - whole):
+        left -= arrays[whole][1].nbytes
+        whole += 1
+    for k, (name, a) in enumerate(arrays):
+        if k >= whole:
+            n = left // (len(arrays) - whole) // a.itemsize
+            a, name = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        log("dump: %s %s" % (name, a.shape))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -278,7 +308,13 @@ def main():
                     help="model_config override (JSON value), e.g. --set num_layers=4 --set num_initial_filters=8")
     ap.add_argument("--dry-run", action="store_true",
                     help="stop after process-group initialisation + tuning-table broadcast (launcher check; runs without a GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, <= 64 MB in all); the timed "
+                         "steps then start from the initial parameters and optimizer state, so the files depend on the "
+                         "arguments alone")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("--dump-outputs needs --steps >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(relaunch_under_torchrun(args.gpus))
@@ -353,6 +389,12 @@ def main():
                 "slices": [(off, int(np.prod(shp))) for _, off, shp in tr.sep._active.tensors],
                 "params": [(n, v.detach().cpu().numpy().copy()) for n, v in tr.sep.variables().items()]}
 
+    # --dump-outputs: the number of settle steps below follows the wall clock, so the state the timed steps start from would
+    # differ from run to run; it is reset to this snapshot before the timed region instead
+    initial = None
+    if args.dump_outputs:
+        initial = (tr.sep.params.clone(), tr.sep.adam_m.clone(), tr.sep.adam_v.clone(), tr.sep.global_step)
+
     t_w = time.perf_counter()
     for _ in range(args.warmup):
         loss = step()
@@ -372,6 +414,10 @@ def main():
             loss = step()
         torch.cuda.synchronize()
     log("warm-up done (%d steps + %d settle steps)" % (args.warmup, settle_steps))
+    if initial is not None:
+        tr.sep.params.copy_(initial[0]); tr.sep.adam_m.copy_(initial[1]); tr.sep.adam_v.copy_(initial[2])
+        tr.sep.global_step = initial[3]
+        del initial
     barrier()
     torch.cuda.synchronize()
     # one HIP event per step on the stream the step is launched on (torch's current stream = the stream handed to
@@ -397,6 +443,8 @@ def main():
         elapsed = float(t.item())
     loss_val = float(loss.item())
     log("timed region: %d steps in %.3f s (%.2f ms/step)" % (args.steps, elapsed, 1e3 * elapsed / args.steps))
+    if args.dump_outputs and tr.rank == 0:
+        dump_outputs(args.dump_outputs, tr.sep, loss)      # before the diagnostic / roofline steps below move the state on
 
     step_ms = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)])
     info = tr.sep.plan_info()
