@@ -21,7 +21,7 @@ bfloat16 conversion at exactly the points where the HIP plan stores a tensor in 
 so that the HIP path can be compared with it at fp32-accumulation error plus rare one-ulp bf16 flips (an fp32 sum that
 lands within 1e-7 of a rounding boundary) instead of at the rounding noise of the mode itself.  With `quantize=False`
 every rounding is the identity and the result must equal the float64 oracle exactly (tests/test_bf16_emul.py) -- that
-pins the hand-placed adjoints; the rounding points themselves are a restatement of wave-u-net_amd/csrc (wun_plan.hip:
+pins the hand-placed adjoints; the rounding points themselves are a restatement of wave-u-net_amd/csrc (wun_step.hip:
 wun_forward / wun_loss_backward_ex, wun_bf16.hip epilogue), cited inline.
 
     loss, grads, inter = train_step(cfg, params, mix, targets)                  # chained
@@ -191,7 +191,7 @@ def train_step(cfg, params, mix_btc, targets, quantize=True, forced=None):
         return value
 
     def wq(w, cin):
-        # conv_dispatch (wun_plan.hip): fewer than 8 input channels = the audio-input conv, a direct fp32 conv;
+        # conv_dispatch (wun_dispatch.hip): fewer than 8 input channels = the audio-input conv, a direct fp32 conv;
         # everything else reads the packed bf16 weight image
         return q.a(w) if cin >= 8 else w
 

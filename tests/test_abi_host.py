@@ -251,3 +251,67 @@ def test_bf16_mode_units_carry_no_packed_fp32_instructions():
     r = subprocess.run(["bash", os.path.join(ROOT, "tools", "pk_check.sh")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "wun_narrow.o" in r.stdout and " 0 packed fp32 VALU instructions" in r.stdout
+
+
+# ---- tuning-table headers: the plan's switch snapshot decides which header it accepts ----
+def _import_rc(lib, plan, text):
+    return lib.wun_plan_tune_import(plan.handle, text.encode())
+
+
+@pytest.mark.parametrize("name, batch, frames, table", [
+    ("m1_context", 16, 147443, "round6_tune_table.txt"),
+    ("baseline", 16, 16384, "round6_tune_table_baseline.txt"),
+])
+def test_pinned_tuning_tables_import(name, batch, frames, table, lib, monkeypatch):
+    for k in ("WUN_NO_DEDUP", "WUN_EARLY_WINDOW", "WUN_ODD_FUSE_MIN", "WUN_NO_ODD_ALIGN"):
+        monkeypatch.delenv(k, raising=False)
+    plan = UnetAudioSeparator(wun.get_config(name))._plan(batch, frames)
+    text = open(os.path.join(ROOT, "profiles", table)).read()
+    assert _import_rc(lib, plan, text) == 0, lib.wun_last_error().decode()
+
+
+# the small context config of tests/test_gpu_dedup.py, B = 2 (a dedup plan), under each environment that test uses
+_SMALL_CTX = dict(num_layers=5, num_initial_filters=8, num_frames=301, merge_filter_size=3, filter_size=5, input_filter_size=5)
+_SMALL_HEAD = ("wun-tune 2 order=r6a variants=67 B=2 Tin=637 L=5 F=8 K=5,3,1 ups=0 out=0 ctx=1 S=2 C=1 act=0 dt=0 "
+               "arena=46748 cf=0 cb=0 wg=0")     # + the switch tokens, then a zero-entry table: "\nend\n"
+_SWITCHES = ("WUN_NO_DEDUP", "WUN_EARLY_WINDOW", "WUN_ODD_FUSE_MIN", "WUN_NO_ODD_ALIGN")
+
+
+@pytest.mark.parametrize("env, tokens", [
+    ({}, ""),
+    ({"WUN_NO_DEDUP": "1"}, " dedup=0"),
+    ({"WUN_EARLY_WINDOW": "deep"}, " ew=deep"),
+    ({"WUN_EARLY_WINDOW": "0"}, " ew=0"),
+    ({"WUN_ODD_FUSE_MIN": "256"}, " oddfuse=256"),
+    ({"WUN_ODD_FUSE_MIN": "1"}, " oddfuse=1"),
+    ({"WUN_EARLY_WINDOW": "0", "WUN_ODD_FUSE_MIN": "1"}, " ew=0 oddfuse=1"),
+    ({"WUN_NO_ODD_ALIGN": "1"}, " oddalign=0"),
+    ({"WUN_NO_ODD_ALIGN": "1", "WUN_ODD_FUSE_MIN": "1", "WUN_EARLY_WINDOW": "0"}, " ew=0 oddfuse=1 oddalign=0"),
+    # any other value runs the deep-levels order in the backward pass: the header must say so
+    ({"WUN_EARLY_WINDOW": "1"}, " ew=deep"),
+])
+def test_tuning_header_follows_the_switches(env, tokens, lib, monkeypatch):
+    for k in _SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cfg = wun.get_config("m1_context", **_SMALL_CTX)
+    sep = UnetAudioSeparator(cfg)
+    i, _ = sep.get_padding(np.array([2, cfg["num_frames"], 0]))
+    plan = sep._plan(2, int(i[1]))
+    assert _import_rc(lib, plan, _SMALL_HEAD + tokens + "\nend\n") == 0, lib.wun_last_error().decode()
+    if tokens:
+        assert _import_rc(lib, plan, _SMALL_HEAD + "\nend\n") == -1
+
+
+def test_tuning_header_is_fixed_at_plan_creation(lib, monkeypatch):
+    for k in _SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    cfg = wun.get_config("m1_context", **_SMALL_CTX)
+    sep = UnetAudioSeparator(cfg)
+    i, _ = sep.get_padding(np.array([2, cfg["num_frames"], 0]))
+    plan = sep._plan(2, int(i[1]))
+    monkeypatch.setenv("WUN_EARLY_WINDOW", "0")
+    monkeypatch.setenv("WUN_NO_ODD_ALIGN", "1")
+    assert _import_rc(lib, plan, _SMALL_HEAD + "\nend\n") == 0, lib.wun_last_error().decode()
+    assert _import_rc(lib, plan, _SMALL_HEAD + " ew=0 oddalign=0\nend\n") == -1

@@ -1,4 +1,4 @@
-"""The plan's cross-stream events carry no system-scope fence by default (wun_plan.hip event_flags()).
+"""The plan's cross-stream events carry no system-scope fence by default (wun_dispatch.hip event_flags()).
 Consumers that are NOT kernels follow on the caller's stream: a device-to-host copy of the gradient arena right after
 `wun_loss_backward`, and the host-staged all-reduce of the non-overlapped reducer.  This file runs both in every
 fence mode (default = none, WUN_EVENT_SCOPE=system, =device) and requires the same bytes from all three."""

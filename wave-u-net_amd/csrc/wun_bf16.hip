@@ -581,7 +581,7 @@ int conv_bf16_list_candidates(const ConvArgs& a, ConvChoice* out, int maxn) {
 }
 
 // a.W must point at the packed bf16 image of the layer's weights (pack_bf16_kernel), a.wb_c8p / a.wb_npad set
-hipError_t launch_conv_bf16(const ConvArgs& a_in, hipStream_t s) {
+hipError_t launch_conv_bf16(const ConvArgs& a_in, hipStream_t s, const WunSwitches& sw) {
     ConvArgs a = a_in;
     if (!a.xbf || !conv_bf16_supported(a) || a.wb_c8p <= 0 || a.wb_npad <= 0 || !al16(a.W)) return hipErrorInvalidValue;
     if (!al16(a.src0) || (a.src1 != nullptr && !al16(a.src1))) return hipErrorInvalidValue;      // dword pairs at even row elements
@@ -621,7 +621,7 @@ hipError_t launch_conv_bf16(const ConvArgs& a_in, hipStream_t s) {
                       bf16_lds(a, 64 * mt, bestnw * 16, 1) > 160 * 1024)) mt >>= 1;
     // A workgroup runs its phases (fetch, MFMA, store) back to back, so the CU needs a second resident workgroup to
     // overlap them: take the tallest tile whose LDS footprint still lets two workgroups share a CU
-    static const int lds_cap = getenv("WUN_BF16_LDS_CAP") ? atoi(getenv("WUN_BF16_LDS_CAP")) : 80;
+    const int lds_cap = sw.bf16_lds_cap;
     {
         int m2 = mt;
         while (m2 > 1 && bf16_lds(a, 64 * m2, bestnw * 16, bf16_pick_nck(a, 64 * m2, bestnw * 16, bf16_xit(m2))) >

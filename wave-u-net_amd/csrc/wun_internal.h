@@ -1,5 +1,5 @@
-// Internal: kernel argument blocks + launcher prototypes shared by wun_kernels.hip
-// (device code) and wun_plan.hip (host plan / C ABI).  gfx950 only.
+// Internal: kernel argument blocks + launcher prototypes shared by the device units (wun_kernels.hip, ...) and the
+// host units (wun_plan.hip and the files of wun_plan_impl.h: plan, dispatch, step, tuner, C ABI).  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,6 +8,49 @@
 namespace wun {
 
 enum { LOADER_DIRECT = 0, LOADER_DEINT = 1 };
+
+// Every environment switch the library reads (debugging / experiment switches; the defaults are the shipped schedule),
+// parsed in ONE place: wun_switches_from_env (wun_plan.hip).  wun_plan_create stores a snapshot in the plan and every
+// later decision for that plan reads it; the single-operator entry points take a fresh snapshot per call; the launchers
+// below receive it as a parameter.
+enum WunEarlyWindow { EW_DEFAULT, EW_OFF, EW_DEEP, EW_ALL };     // (EW_DEFAULT: all levels on dedup plans, else deep)
+enum WunEventScope { EV_DEFAULT, EV_SYSTEM, EV_DEVICE };
+enum WunSidePrio { PRIO_DEFAULT, PRIO_LOW, PRIO_HIGH, PRIO_NORMAL };
+struct WunSwitches {
+    // ---- schedule ----
+    bool no_dedup = false;              // WUN_NO_DEDUP (set): rounds 1 - 5's down-level launch sequence on context plans
+    WunEarlyWindow early_window = EW_DEFAULT;   // WUN_EARLY_WINDOW: first char '0' = off, 'a' = all, any other = deep
+    bool odd_fuse_set = false;          // WUN_ODD_FUSE_MIN (set): fuse floor of the odd-window input gradients ...
+    int odd_fuse_min = 64;              // ... atoi of its value (default 64)
+    bool no_odd_align = false;          // WUN_NO_ODD_ALIGN (set): odd-window launches keep their odd start (no shifted filter)
+    bool no_fuse_ups = false;           // WUN_NO_FUSE_UPS (set): separate (adjoint) upsampling kernels, never the fused epilogue
+    bool bf16_head_serial = false;      // WUN_BF16_HEAD_SERIAL (set): bf16 mode, LDS-staged narrow launch on the caller's stream
+    // ---- streams ----
+    bool single_stream = false;         // WUN_SINGLE_STREAM (set): everything on the caller's stream
+    WunSidePrio side_prio = PRIO_DEFAULT;   // WUN_SIDE_PRIO: first char 'l' = lowest, 'h' = highest, anything else = 0
+    WunEventScope event_scope = EV_DEFAULT;  // WUN_EVENT_SCOPE: first char 's' = system fence, 'd' = device release
+    // ---- kernel selection ----
+    bool no_win = false;                // WUN_NO_WIN (set): no register-window weight-gradient kernel
+    bool no_narrow = false;             // WUN_NO_NARROW (set): MFMA weight gradients for the output head / audio-input conv
+    bool no_narrow_down0 = false;       // WUN_NO_NARROW_DOWN0 (set): ... for the audio-input conv only
+    bool no_narrow_stream = false;      // WUN_NO_NARROW_STREAM: atoi != 0 -- LDS-staged narrow kernel, never the streaming form
+    int narrow_splits = 0;              // WUN_NARROW_SPLITS: split cap of the narrow kernels, max(1, atoi) (0 = unset)
+    bool no_dma = false;                // WUN_NO_DMA (set): register staging for every conv tile (no DMA instantiation)
+    bool no_k3 = false;                 // WUN_NO_K3: atoi != 0 -- no in-workgroup split-K conv tiles
+    int win_tk = 64;                    // WUN_WIN_TK: register-window positions per unit, only 16 / 32 / 64 / 128 accepted
+    int bf16_lds_cap = 80;              // WUN_BF16_LDS_CAP: KiB of LDS a bf16 conv tile may take (atoi, default 80)
+    // ---- tuner ----
+    int tune_rounds = 4;                // WUN_TUNE_ROUNDS: round-robin timing rounds per launch position, max(1, atoi)
+    bool tune_log = false;              // WUN_TUNE_LOG (set): one stderr line per tuned launch position
+    std::string tune_alts;              // WUN_TUNE_ALTS: file the near-best candidates are appended to (empty = off)
+    int tune_alts_max = 6;              // WUN_TUNE_ALTS_MAX: candidates per position, atoi (<= 0 gives 6)
+    float tune_alts_tol = 1.15f;        // WUN_TUNE_ALTS_TOL: "near" = within this factor of the best, atof (<= 1 gives 1.15)
+    // ---- diagnostics ----
+    bool dump_layout = false;           // WUN_DUMP_LAYOUT (set): workspace map on stderr at plan creation
+    bool profile_detail = false;        // WUN_PROFILE_DETAIL (set): per-launch list in the profile JSON (read at wun_profile_begin)
+    bool win_occ = false;               // WUN_WIN_OCC (set): occupancy line on stderr per register-window launch
+};
+WunSwitches wun_switches_from_env();
 
 // Epilogue flag bits
 enum { F_LRELU = 1, F_ACCUM = 2, F_VEC4 = 4, F_PHASE2 = 8 };
@@ -120,12 +163,12 @@ WgradGeom wgrad_geom(const WgradArgs& a);
 // register-window weight gradient (wun_wgrad_win.hip; WgradArgs.win): aligned 16-byte operand reads, DMA staging,
 // split partials in the final layout
 bool wgrad_win_supported(const WgradArgs& a);
-long long wgrad_win_partial_floats(const WgradArgs& a);
-int wgrad_win_units(const WgradArgs& a);
-int wgrad_win_tiles(const WgradArgs& a);
-hipError_t launch_wgrad_win(const WgradArgs& a, hipStream_t s);
+long long wgrad_win_partial_floats(const WgradArgs& a, const WunSwitches& sw);
+int wgrad_win_units(const WgradArgs& a, const WunSwitches& sw);
+int wgrad_win_tiles(const WgradArgs& a, const WunSwitches& sw);
+hipError_t launch_wgrad_win(const WgradArgs& a, hipStream_t s, const WunSwitches& sw);
 hipError_t launch_wgrad_win_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
-                                   hipStream_t s);
+                                   hipStream_t s, const WunSwitches& sw);
 // bf16 speed mode (wun_wgrad_bf16.hip): own tiling -- MFMA rows = 16 input channels of one tap; a workgroup holds
 // 4*MTW slots = NCB channel blocks x KW taps + the bias slot
 struct WgradBfGeom { int MTW, NW, NCB, nCB, nMG, nNG, TK, XW4, XROWS, ZPe; size_t lds; };
@@ -241,22 +284,22 @@ template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, long long i, 
 }
 
 // ---- launchers (wun_kernels.hip) ---------------------------------------------------
-size_t conv_lds_bytes(const ConvArgs& a, int variant);
+size_t conv_lds_bytes(const ConvArgs& a, int variant, const WunSwitches& sw);
 int  conv_pick_variant(const ConvArgs& a);
-hipError_t launch_conv(const ConvArgs& a, float* part, long long part_cap, hipStream_t s);
+hipError_t launch_conv(const ConvArgs& a, float* part, long long part_cap, hipStream_t s, const WunSwitches& sw);
 double conv_flops(const ConvArgs& a);        // useful FLOPs (2*MACs) of the launch
 long long conv_natural_wgs_phase2(const ConvArgs& a);
-int conv_list_candidates(const ConvArgs& a, long long part_cap, ConvChoice* out, int maxn);
-bool conv_choice_ok(const ConvArgs& a, long long part_cap, int variant, int ksplit);
+int conv_list_candidates(const ConvArgs& a, long long part_cap, ConvChoice* out, int maxn, const WunSwitches& sw);
+bool conv_choice_ok(const ConvArgs& a, long long part_cap, int variant, int ksplit, const WunSwitches& sw);
 int conv_num_variants();
-int wgrad_max_units(const WgradArgs& a);
+int wgrad_max_units(const WgradArgs& a, const WunSwitches& sw);
 
-int  wgrad_pick_nsplit(const WgradArgs& a);
-hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s);
+int  wgrad_pick_nsplit(const WgradArgs& a, const WunSwitches& sw);
+hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s, const WunSwitches& sw);
 void wgrad_resolved_geom(const WgradArgs& a, int& mtw, int& nw);
-long long wgrad_partial_floats(const WgradArgs& a);
+long long wgrad_partial_floats(const WgradArgs& a, const WunSwitches& sw);
 hipError_t launch_wgrad_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
-                               hipStream_t s);
+                               hipStream_t s, const WunSwitches& sw);
 hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s);
 hipError_t launch_upsample_bwd(const UpsampleBwdArgs& a, hipStream_t s);
 hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s);               // dw of the learned interpolation weights
@@ -272,18 +315,18 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n
                        float b1, float b2, float eps, float gscale, hipStream_t s);
 hipError_t launch_fill(float* p, long long n, float val, hipStream_t s);
 hipError_t launch_mfma_probe(const float* a, const float* b, float* d, hipStream_t s);
-void prof_begin();
+void prof_begin(bool detail);                 // detail: per-launch list in the JSON (WUN_PROFILE_DETAIL)
 std::string prof_end();
 void prof_scope_begin(const char* name, double flops, hipStream_t s, const char* tag, double bytes = 0.0);   // HIP-event bracket of the next launch (bytes: algorithmic HBM bytes of a bandwidth-bound launch)
 void prof_scope_end(hipStream_t s);
 
 // ---- narrow weight gradients (wun_narrow.hip) ----
 bool narrow_wgrad_supported(const NarrowWgradArgs& a);
-bool narrow_wgrad_uses_lds(const NarrowWgradArgs& a);      // the LDS-staged kernel (else the streaming form)
+bool narrow_wgrad_uses_lds(const NarrowWgradArgs& a, const WunSwitches& sw);      // the LDS-staged kernel (else the streaming form)
 int narrow_wgrad_units(const NarrowWgradArgs& a);
-int narrow_wgrad_pick_nsplit(const NarrowWgradArgs& a);
+int narrow_wgrad_pick_nsplit(const NarrowWgradArgs& a, const WunSwitches& sw);
 long long narrow_wgrad_partial_floats(const NarrowWgradArgs& a);
-hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s);
+hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitches& sw);
 hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* partial, int nsplit, float* grads,
                                       const long long* woff, const long long* boff, hipStream_t s);
 
@@ -297,7 +340,7 @@ static inline int bf16_image_groups(int C) {
     return best;
 }
 bool conv_bf16_supported(const ConvArgs& a);
-hipError_t launch_conv_bf16(const ConvArgs& a, hipStream_t s);
+hipError_t launch_conv_bf16(const ConvArgs& a, hipStream_t s, const WunSwitches& sw);
 bool first_conv_supported(const ConvArgs& a);
 hipError_t launch_first_conv(const ConvArgs& a, hipStream_t s);                 // audio-input conv of the bf16 mode
 hipError_t launch_cast_rows_bf16(const float* src, void* dst, long long rows, int T, long long spitch, long long dpitch, hipStream_t s);

@@ -49,10 +49,12 @@ __host__ __device__ static inline int fit_pitch(int width, int mod32) {
 struct ProfSlot { std::string name; std::string tag; double flops; double bytes; hipEvent_t e0, e1, c0, c1; };
 static std::vector<ProfSlot> g_prof;
 static bool g_prof_on = false;
+static bool g_prof_detail = false;   // per-launch list in the JSON (WUN_PROFILE_DETAIL, read at wun_profile_begin)
 static std::mutex g_prof_mu;
 
-void prof_begin() {
+void prof_begin(bool detail) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
+    g_prof_detail = detail;
     for (auto& sl : g_prof) { (void)hipEventDestroy(sl.e0); (void)hipEventDestroy(sl.e1); (void)hipEventDestroy(sl.c0); (void)hipEventDestroy(sl.c1); }
     g_prof.clear();
     g_prof_on = true;
@@ -116,7 +118,7 @@ std::string prof_end() {
         if (hipEventElapsedTime(&cms, sl.c0, sl.c1) == hipSuccess) empty_ms.push_back(cms);
         if (hipEventElapsedTime(&ms, sl.e0, sl.e1) == hipSuccess) {
             Agg& a = agg[sl.name]; a.n += 1; a.ms += ms; a.flops += sl.flops; a.bytes += sl.bytes;
-            if (getenv("WUN_PROFILE_DETAIL") != nullptr) {
+            if (g_prof_detail) {
                 char buf[512];
                 snprintf(buf, sizeof(buf), "%s{\"name\": \"%s\", \"tag\": \"%s\", \"ms\": %.6f, \"flops\": %.6e}",
                          detail.empty() ? "" : ", ", sl.name.c_str(), sl.tag.c_str(), ms, sl.flops);
@@ -1178,10 +1180,10 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 // may this launch use the DMA-staging instantiation (XVEC) of tile `variant`?
 static int conv_dma_pitch(int width) { return fit_pitch((width + 3) & ~3, 16); }
-static bool conv_xvec_ok(const ConvArgs& a, int variant) {
+static bool conv_xvec_ok(const ConvArgs& a, int variant, const WunSwitches& sw) {
     const ConvVariant& cv = kConvVariants[variant];
     const int Ctot = a.C0 + a.C1;
-    if (cv.fold || cv.CK != 8 || getenv("WUN_NO_DMA") != nullptr) return false;
+    if (cv.fold || cv.CK != 8 || sw.no_dma) return false;
     // (a stride-2 variant -- contiguous window, the four k lanes = four consecutive taps -- was built and measured in
     //  round 3: its chunk loop is 14 % faster but the step 1 % slower; not in the tree)
     if (a.loader != LOADER_DIRECT) return false;
@@ -1194,13 +1196,13 @@ static bool conv_xvec_ok(const ConvArgs& a, int variant) {
     return true;
 }
 
-static void conv_geom(const ConvArgs& a, int variant, int& TT, int& NT, int& J, int& XP, int& WP) {
+static void conv_geom(const ConvArgs& a, int variant, const WunSwitches& sw, int& TT, int& NT, int& J, int& XP, int& WP) {
     const ConvVariant& v = kConvVariants[variant];
     TT = v.WT * v.MT * 16;
     NT = v.WN * v.NW * 16;
     J = conv_J(a);
     XP = fit_pitch(v.fold ? WUN_FOLD_XCAP(TT) : TT + J - 1, 16);
-    if (conv_xvec_ok(a, variant)) XP = conv_dma_pitch(TT + J - 1 + 3);       // whole 16-byte granules incl. the sub-vector shift
+    if (conv_xvec_ok(a, variant, sw)) XP = conv_dma_pitch(TT + J - 1 + 3);       // whole 16-byte granules incl. the sub-vector shift
     WP = fit_pitch(NT, 16);
 }
 
@@ -1211,16 +1213,16 @@ static inline long long conv_mtiles(const ConvArgs& a, int variant, int TT, int&
     return (a.Tout + TT - 1) / TT;
 }
 
-size_t conv_lds_bytes(const ConvArgs& a, int variant) {
+size_t conv_lds_bytes(const ConvArgs& a, int variant, const WunSwitches& sw) {
     if (is_k3(variant)) {
         const int bv = conv_tile_variant(variant);
-        const size_t stage = WUN_KG * conv_lds_bytes(a, bv);
+        const size_t stage = WUN_KG * conv_lds_bytes(a, bv, sw);
         const size_t red = (size_t)(WUN_KG - 1) * kConvVariants[bv].MT * kConvVariants[bv].NW * 256 * 16;   // accumulator hand-over
         return stage > red ? stage : red;
     }
     if (variant >= WUN_FIRST_RETIRED_VARIANT) return (size_t)1 << 30;             // retired index range: never launched
     int TT, NT, J, XP, WP;
-    conv_geom(a, variant, TT, NT, J, XP, WP);
+    conv_geom(a, variant, sw, TT, NT, J, XP, WP);
     const int CK = kConvVariants[variant].CK;
     return 2 * sizeof(float) * ((size_t)CK * XP + (size_t)J * CK * WP);     // double buffered
 }
@@ -1232,9 +1234,9 @@ double conv_flops(const ConvArgs& a) {
 }
 
 // split-K decision: (ksplit, chunks per split) from shapes only (deterministic)
-void conv_splitk(const ConvArgs& a, int variant, long long part_cap_floats, int& ksplit, int& cps) {
+void conv_splitk(const ConvArgs& a, int variant, const WunSwitches& sw, long long part_cap_floats, int& ksplit, int& cps) {
     int TT, NT, J, XP, WP;
-    conv_geom(a, variant, TT, NT, J, XP, WP);
+    conv_geom(a, variant, sw, TT, NT, J, XP, WP);
     const int CK = kConvVariants[variant].CK;
     const int CKC = a.loader == LOADER_DEINT ? CK / 2 : CK;
     const int nchunks = (a.C0 + a.C1 + CKC - 1) / CKC;
@@ -1253,14 +1255,14 @@ void conv_splitk(const ConvArgs& a, int variant, long long part_cap_floats, int&
 }
 
 template <int MT, int NW, int WT, int WN, int CK, bool VECW, bool FOLD = false, bool XVEC = false, int KG = 1>
-static hipError_t conv_launch_t(ConvArgs a, int variant, float* part, long long part_cap, hipStream_t s) {
+static hipError_t conv_launch_t(ConvArgs a, int variant, float* part, long long part_cap, hipStream_t s, const WunSwitches& sw) {
     int TT, NT, J, XP, WP;
-    conv_geom(a, variant, TT, NT, J, XP, WP);
+    conv_geom(a, variant, sw, TT, NT, J, XP, WP);
     const bool phase2 = (a.flags & F_PHASE2) != 0;
     int bfac;
     const int nTT = (int)conv_mtiles(a, variant, TT, bfac);
     const int nNT = phase2 ? (a.N + NT / 2 - 1) / (NT / 2) : (a.N + NT - 1) / NT;
-    size_t lds = conv_lds_bytes(a, variant);
+    size_t lds = conv_lds_bytes(a, variant, sw);
     if (KG > 1) {
         const size_t red = (size_t)(KG - 1) * MT * NW * 256 * 16;
         lds = KG * lds > red ? KG * lds : red;
@@ -1276,7 +1278,7 @@ static hipError_t conv_launch_t(ConvArgs a, int variant, float* part, long long 
     }
     const size_t lds_launch = lds;
     int ksplit, cps;
-    conv_splitk(a, variant, (part != nullptr && !phase2) ? part_cap : 0, ksplit, cps);
+    conv_splitk(a, variant, sw, (part != nullptr && !phase2) ? part_cap : 0, ksplit, cps);
     if (a.force_ksplit > 0 && !phase2) {                         // autotuned choice
         const int CKC = a.loader == LOADER_DEINT ? CK / 2 : CK;
         const int nchunks = (a.C0 + a.C1 + CKC - 1) / CKC;
@@ -1333,20 +1335,19 @@ static hipError_t conv_launch_t(ConvArgs a, int variant, float* part, long long 
 // rule set behind the autotuner's candidate list, the test hook's forced choices and imported
 // tuning tables: a choice that fails here is never launched (a stale table cannot push a split
 // past the partial scratch or select a tile the loader does not support).
-bool conv_choice_ok(const ConvArgs& a, long long part_cap, int v, int ks) {
+bool conv_choice_ok(const ConvArgs& a, long long part_cap, int v, int ks, const WunSwitches& sw) {
     const int nvar = (int)(sizeof(kConvVariants) / sizeof(kConvVariants[0]));
     if (is_k3(v)) {
         // the tile's own rules, whole chunks for every group of every split, the three staging regions inside the CU's LDS
         const int bv = conv_tile_variant(v);
-        static const bool off = getenv("WUN_NO_K3") != nullptr && atoi(getenv("WUN_NO_K3")) != 0;
-        if (off || (a.flags & F_PHASE2) || ks < 1 || !conv_choice_ok(a, part_cap, bv, 1)) return false;
+        if (sw.no_k3 || (a.flags & F_PHASE2) || ks < 1 || !conv_choice_ok(a, part_cap, bv, 1, sw)) return false;
         const ConvVariant& cv = kConvVariants[bv];
         const int CKC = a.loader == LOADER_DEINT ? cv.CK / 2 : cv.CK;
         const int Ctot = a.C0 + a.C1;
         if (Ctot % CKC) return false;
         const int nchunks = Ctot / CKC;
         if (nchunks % (WUN_KG * ks) != 0) return false;
-        if (conv_lds_bytes(a, v) > 160 * 1024) return false;
+        if (conv_lds_bytes(a, v, sw) > 160 * 1024) return false;
         const int TT = cv.WT * cv.MT * 16, NT = cv.WN * cv.NW * 16;
         int bfac;
         const long long natural = conv_mtiles(a, bv, TT, bfac) * ((a.N + NT - 1) / NT) * bfac;
@@ -1370,7 +1371,7 @@ bool conv_choice_ok(const ConvArgs& a, long long part_cap, int v, int ks) {
     if (cv.fold && (long long)TT >= 2ll * a.B * a.Tout) return false;
     const int padded = ((a.N + NT - 1) / NT) * NT;
     if (padded * 3 > a.N * 4 + 48) return false;                      // > ~33 % padded columns
-    if (conv_lds_bytes(a, v) > 150 * 1024) return false;
+    if (conv_lds_bytes(a, v, sw) > 150 * 1024) return false;
     if (ks == 1) return true;
     const int CKC = a.loader == LOADER_DEINT ? cv.CK / 2 : cv.CK;
     const int nchunks = (Ctot + CKC - 1) / CKC;
@@ -1381,13 +1382,13 @@ bool conv_choice_ok(const ConvArgs& a, long long part_cap, int v, int ks) {
 }
 
 // Candidate (tile variant, split-K) choices for the autotuner.  Returns the number written.
-int conv_list_candidates(const ConvArgs& a, long long part_cap, ConvChoice* out, int maxn) {
+int conv_list_candidates(const ConvArgs& a, long long part_cap, ConvChoice* out, int maxn, const WunSwitches& sw) {
     int n = 0;
     const int nvar = conv_num_variants();
     static const int ks_menu[] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48};
     for (int v = 0; v < nvar && n < maxn; ++v)
         for (unsigned i = 0; i < sizeof(ks_menu) / sizeof(ks_menu[0]) && n < maxn; ++i) {
-            if (!conv_choice_ok(a, part_cap, v, ks_menu[i])) {
+            if (!conv_choice_ok(a, part_cap, v, ks_menu[i], sw)) {
                 if (is_k3(v) && ks_menu[i] < 8) continue;            // (divisibility: a larger split may fit again)
                 break;                                               // larger splits fail the same bounds
             }
@@ -1403,7 +1404,7 @@ int conv_num_variants() { return first_k3_variant() + kNumK3; }
 
 int conv_last_fused_ups() { return t_last_fused_ups; }
 
-hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hipStream_t s) {
+hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hipStream_t s, const WunSwitches& sw) {
     ConvArgs a = a_in;
     t_last_fused_ups = 0;
     // the fused upsampled copy is written by the split-K epilogue of plain forward launches only
@@ -1438,15 +1439,15 @@ hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hi
     int v = (a.flags & F_PHASE2) ? conv_pick_variant_phase2(a) : conv_pick_variant(a);
     if (a.force_variant > 0 && vecw) {
         v = a.force_variant - 1;
-        if (!conv_choice_ok(a, part != nullptr ? part_cap : 0, v, a.force_ksplit > 0 ? a.force_ksplit : 1)) return hipErrorInvalidValue;
+        if (!conv_choice_ok(a, part != nullptr ? part_cap : 0, v, a.force_ksplit > 0 ? a.force_ksplit : 1, sw)) return hipErrorInvalidValue;
     }
     if (is_k3(v)) {
         const int bv = conv_tile_variant(v);
-        const bool xv3 = conv_xvec_ok(a, bv);
+        const bool xv3 = conv_xvec_ok(a, bv, sw);
 #define WUN_K3(i, MT, NW, WT, WN) case i: \
-        if (xv3) return conv_launch_t<MT, NW, WT, WN, 8, true, false, true, WUN_KG>(a, bv, part, part_cap, s); \
-        return conv_launch_t<MT, NW, WT, WN, 8, true, false, false, WUN_KG>(a, bv, part, part_cap, s);
-#define WUN_K3F(i, MT, NW, WT, WN) case i: return conv_launch_t<MT, NW, WT, WN, 8, true, true, false, WUN_KG>(a, bv, part, part_cap, s);
+        if (xv3) return conv_launch_t<MT, NW, WT, WN, 8, true, false, true, WUN_KG>(a, bv, part, part_cap, s, sw); \
+        return conv_launch_t<MT, NW, WT, WN, 8, true, false, false, WUN_KG>(a, bv, part, part_cap, s, sw);
+#define WUN_K3F(i, MT, NW, WT, WN) case i: return conv_launch_t<MT, NW, WT, WN, 8, true, true, false, WUN_KG>(a, bv, part, part_cap, s, sw);
         switch (bv) {
             WUN_K3(8, 1, 2, 4, 1) WUN_K3(9, 1, 3, 4, 1) WUN_K3(10, 1, 2, 2, 2) WUN_K3(11, 1, 3, 2, 2)
             WUN_K3(4, 2, 2, 4, 1) WUN_K3(5, 2, 3, 4, 1)
@@ -1465,18 +1466,18 @@ hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hi
         if (Ctot <= 4) v = a.Tout > 64 ? 13 : 14;
         else v = a.Tout <= 16 ? 12 : (a.Tout <= 64 ? 9 : 1);
         switch (v) {
-            case 1: return conv_launch_t<4, 3, 4, 1, 8, false>(a, v, part, part_cap, s);
-            case 9: return conv_launch_t<1, 3, 4, 1, 8, false>(a, v, part, part_cap, s);
-            case 12: return conv_launch_t<1, 2, 1, 4, 8, false>(a, v, part, part_cap, s);
-            case 13: return conv_launch_t<4, 2, 4, 1, 4, false>(a, v, part, part_cap, s);
-            default: return conv_launch_t<1, 2, 4, 1, 4, false>(a, v, part, part_cap, s);
+            case 1: return conv_launch_t<4, 3, 4, 1, 8, false>(a, v, part, part_cap, s, sw);
+            case 9: return conv_launch_t<1, 3, 4, 1, 8, false>(a, v, part, part_cap, s, sw);
+            case 12: return conv_launch_t<1, 2, 1, 4, 8, false>(a, v, part, part_cap, s, sw);
+            case 13: return conv_launch_t<4, 2, 4, 1, 4, false>(a, v, part, part_cap, s, sw);
+            default: return conv_launch_t<1, 2, 4, 1, 4, false>(a, v, part, part_cap, s, sw);
         }
     }
-    const bool xv = conv_xvec_ok(a, v);
+    const bool xv = conv_xvec_ok(a, v, sw);
 #define WUN_CV(i, MT, NW, WT, WN, CK) case i: \
-        if (xv) return conv_launch_t<MT, NW, WT, WN, CK, true, false, true>(a, v, part, part_cap, s); \
-        return conv_launch_t<MT, NW, WT, WN, CK, true>(a, v, part, part_cap, s);
-#define WUN_CV4(i, MT, NW, WT, WN, CK) case i: return conv_launch_t<MT, NW, WT, WN, CK, true>(a, v, part, part_cap, s);
+        if (xv) return conv_launch_t<MT, NW, WT, WN, CK, true, false, true>(a, v, part, part_cap, s, sw); \
+        return conv_launch_t<MT, NW, WT, WN, CK, true>(a, v, part, part_cap, s, sw);
+#define WUN_CV4(i, MT, NW, WT, WN, CK) case i: return conv_launch_t<MT, NW, WT, WN, CK, true>(a, v, part, part_cap, s, sw);
     switch (v) {
         WUN_CV(0, 4, 2, 4, 1, 8) WUN_CV(1, 4, 3, 4, 1, 8) WUN_CV(2, 4, 4, 4, 1, 8) WUN_CV(3, 4, 5, 4, 1, 8)
         WUN_CV(4, 2, 2, 4, 1, 8) WUN_CV(5, 2, 3, 4, 1, 8) WUN_CV(6, 2, 4, 4, 1, 8) WUN_CV(7, 2, 5, 4, 1, 8)
@@ -1491,7 +1492,7 @@ hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hi
         WUN_CV(24, 6, 2, 4, 1, 8) WUN_CV(25, 6, 3, 4, 1, 8)
         WUN_CV4(26, 4, 3, 4, 1, 4) WUN_CV4(27, 2, 3, 4, 1, 4) WUN_CV4(28, 3, 3, 4, 1, 4) WUN_CV4(29, 2, 2, 4, 1, 4)
         WUN_CV4(30, 3, 2, 4, 1, 4) WUN_CV4(31, 4, 5, 4, 1, 4) WUN_CV4(32, 3, 5, 4, 1, 4) WUN_CV4(33, 2, 5, 4, 1, 4)
-#define WUN_CF(i, MT, NW, WT, WN, CK) case i: return conv_launch_t<MT, NW, WT, WN, CK, true, true>(a, v, part, part_cap, s);
+#define WUN_CF(i, MT, NW, WT, WN, CK) case i: return conv_launch_t<MT, NW, WT, WN, CK, true, true>(a, v, part, part_cap, s, sw);
         WUN_CF(34, 1, 2, 4, 1, 8) WUN_CF(35, 1, 3, 4, 1, 8) WUN_CF(36, 2, 2, 4, 1, 8) WUN_CF(37, 2, 3, 4, 1, 8)
         WUN_CF(38, 2, 3, 2, 2, 8) WUN_CF(39, 4, 3, 2, 2, 8) WUN_CF(40, 2, 2, 2, 2, 8) WUN_CF(41, 4, 2, 2, 2, 8)
 #undef WUN_CF
@@ -1909,15 +1910,15 @@ WgradGeom wgrad_geom(const WgradArgs& a) {
 }
 
 // (bf16 speed mode: the same questions answered for the bf16 kernel's own tiling)
-int wgrad_max_units(const WgradArgs& a) {
-    if (a.win) return wgrad_win_units(a);
+int wgrad_max_units(const WgradArgs& a, const WunSwitches& sw) {
+    if (a.win) return wgrad_win_units(a, sw);
     const int TK = a.bf16 ? wgrad_bf16_geom(a).TK : wgrad_geom(a).TK;
     return a.B * ((a.Tq + TK - 1) / TK);
 }
 
-int wgrad_pick_nsplit(const WgradArgs& a) {
+int wgrad_pick_nsplit(const WgradArgs& a, const WunSwitches& sw) {
     if (a.win) {
-        const long long units = wgrad_win_units(a), per = wgrad_win_tiles(a);
+        const long long units = wgrad_win_units(a, sw), per = wgrad_win_tiles(a, sw);
         long long ns = (1024 + per - 1) / per;
         if (ns > units) ns = units;
         if (units >= 8 && ns > units / 2) ns = units / 2;
@@ -1968,9 +1969,9 @@ static hipError_t wgrad_launch_t(WgradArgs a, const WgradGeom& g, hipStream_t s)
     return hipGetLastError();
 }
 
-hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s) {
+hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s, const WunSwitches& sw) {
     if (a.bf16) return launch_wgrad_bf16(a, s);
-    if (a.win) return launch_wgrad_win(a, s);
+    if (a.win) return launch_wgrad_win(a, s, sw);
     // canonical layout required (the plan's buffers are; the single-op entry points repack)
     if ((a.pitch0 & 3) || (a.bs0 & 3) || (reinterpret_cast<uintptr_t>(a.src0) & 15) || a.pitch0 < 4) return hipErrorInvalidValue;
     if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || a.pitch1 < 4)) return hipErrorInvalidValue;
@@ -1996,8 +1997,8 @@ void wgrad_resolved_geom(const WgradArgs& a, int& mtw, int& nw) {
 }
 
 // floats one split of this weight gradient occupies in the tile-major partial buffer
-long long wgrad_partial_floats(const WgradArgs& a) {
-    if (a.win) return wgrad_win_partial_floats(a);
+long long wgrad_partial_floats(const WgradArgs& a, const WunSwitches& sw) {
+    if (a.win) return wgrad_win_partial_floats(a, sw);
     if (a.bf16) { const WgradBfGeom b = wgrad_bf16_geom(a); return (long long)b.nMG * b.nNG * (4 * b.MTW * 16) * (b.NW * 16); }
     const WgradGeom g = wgrad_geom(a);
     return (long long)g.nMG * g.nNG * (4 * g.MTW * 16) * (g.NW * 16);
@@ -2005,9 +2006,9 @@ long long wgrad_partial_floats(const WgradArgs& a) {
 
 // partial: `nsplit` consecutive splits written by launch_wgrad calls that share `a`'s tile geometry
 hipError_t launch_wgrad_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
-                               hipStream_t s) {
+                               hipStream_t s, const WunSwitches& sw) {
     if (a.bf16) return launch_wgrad_bf16_reduce(a, partial, nsplit, out_w, out_b, s);
-    if (a.win) return launch_wgrad_win_reduce(a, partial, nsplit, out_w, out_b, s);
+    if (a.win) return launch_wgrad_win_reduce(a, partial, nsplit, out_w, out_b, s, sw);
     const WgradGeom g = wgrad_geom(a);
     WgradReduceArgs r;
     r.partial = partial; r.out_w = out_w; r.out_b = out_b;

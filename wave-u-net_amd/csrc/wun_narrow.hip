@@ -304,12 +304,11 @@ __global__ __launch_bounds__(64 * (24 / NPW)) void narrow_stream_kernel(NarrowWg
 #define WUN_NS_PF false  /* two register sets (loads of the next unit during the FMAs) */
 #endif
 // shapes the streaming form serves: one input channel, all rows on four waves of NPW = 6, taps <= 15
-static bool narrow_stream_ok(const NarrowWgradArgs& a) {
-    static const bool off = getenv("WUN_NO_NARROW_STREAM") != nullptr && atoi(getenv("WUN_NO_NARROW_STREAM")) != 0;
+static bool narrow_stream_ok(const NarrowWgradArgs& a, const WunSwitches& sw) {
     // (the kernel reads src0 only, in 256-position units)
     static_assert(WUN_NW_TQ == 256, "narrow_stream_kernel walks units of 4 positions x 64 lanes");
     // one or two input channels (the reference's mono / stereo audio), up to 48 dz rows (two launches of 24)
-    return !off && (a.C0 == 1 || a.C0 == 2) && a.C1 == 0 && a.N <= 48 && a.KW >= 4 && a.KW <= 15;
+    return !sw.no_narrow_stream && (a.C0 == 1 || a.C0 == 2) && a.C1 == 0 && a.N <= 48 && a.KW >= 4 && a.KW <= 15;
 }
 
 // out element (k, ci, n = s*Nper + c) -> source s: weights [K][Ctot][Nper] at woff[s], bias at boff[s].
@@ -338,8 +337,8 @@ __global__ __launch_bounds__(256) void narrow_wgrad_reduce_kernel(const float* p
     else grads[boff[src] + c] = red[0];
 }
 
-// (the plan keeps the LDS-staged form off the CUs the bf16 weight gradient is using: wun_plan.hip, run_narrow_wgrad)
-bool narrow_wgrad_uses_lds(const NarrowWgradArgs& a) { return !narrow_stream_ok(a); }
+// (the plan keeps the LDS-staged form off the CUs the bf16 weight gradient is using: wun_dispatch.hip, run_narrow_wgrad)
+bool narrow_wgrad_uses_lds(const NarrowWgradArgs& a, const WunSwitches& sw) { return !narrow_stream_ok(a, sw); }
 
 bool narrow_wgrad_supported(const NarrowWgradArgs& a) {
     const int Ctot = a.C0 + a.C1;
@@ -367,23 +366,23 @@ int narrow_wgrad_units(const NarrowWgradArgs& a) { return a.B * ((a.Tq + WUN_NW_
 
 long long narrow_wgrad_partial_floats(const NarrowWgradArgs& a) { return (long long)(a.KW * (a.C0 + a.C1) + 1) * a.N; }
 
-int narrow_wgrad_pick_nsplit(const NarrowWgradArgs& a) {
+int narrow_wgrad_pick_nsplit(const NarrowWgradArgs& a, const WunSwitches& sw) {
     const int units = narrow_wgrad_units(a);
     // ~4 workgroups per CU, each streaming >= 1 unit; the streaming form pays a 64-lane reduction of every accumulator
     // per workgroup: one workgroup per CU, >= 4 units each (measured 256 / 512 / 1024: 36.8 / 44.6 / 51.3 us)
-    int cap = narrow_stream_ok(a) ? 256 : 1024;
-    if (const char* e = getenv("WUN_NARROW_SPLITS")) cap = atoi(e);
+    int cap = narrow_stream_ok(a, sw) ? 256 : 1024;
+    if (sw.narrow_splits > 0) cap = sw.narrow_splits;
     int ns = units < cap ? units : cap;
     return ns < 1 ? 1 : ns;
 }
 
 // a.nsplit / a.split_base / a.partial set by the caller
-hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s) {
+hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitches& sw) {
     if (!narrow_wgrad_supported(a)) return hipErrorInvalidValue;
     a.nQT = (a.Tq + WUN_NW_TQ - 1) / WUN_NW_TQ;
     const int units = a.B * a.nQT;
     a.units_per_split = (units + a.nsplit - 1) / a.nsplit;
-    if (narrow_stream_ok(a)) {
+    if (narrow_stream_ok(a, sw)) {
         char tag[160];
         snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d stride=%d B=%d nsplit=%d stream", a.C0, a.N, a.Tq, a.KW, a.stride, a.B, a.nsplit);
         prof_scope_begin("narrow_wgrad_kernel", 2.0 * a.KW * (double)a.C0 * a.N * (double)a.Tq * a.B, s, tag,

@@ -1,0 +1,410 @@
+// Host side of libwun.so: the single-operator entry points (wun_op_*) the tests and tools call, their test hooks and
+// the MFMA lane-layout probes.
+#include "wun_plan_impl.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+namespace wun {
+hipError_t launch_make_wt_one(const float* src, float* dst, WtDesc d, hipStream_t s);
+}
+
+// ---------------------------------------------------------------------------------------
+// single operators
+// ---------------------------------------------------------------------------------------
+// the single-operator entry points use a lazily allocated split-K scratch of their own
+static const long long kOpScratchFloats = 8ll << 20;
+static int g_op_variant = -1, g_op_ksplit = 0;          // wun_op_force_conv_variant (test hook)
+static int g_op_wg_mtw = 0, g_op_wg_nw = 0, g_op_wg_nsplit = 0;   // wun_op_force_wgrad_variant (test hook)
+static int g_op_wg_bf16 = 0;                                       // wun_op_set_wgrad_bf16 (test hook)
+static int g_op_wg_narrow = 0;                                     // wun_op_set_wgrad_narrow (test hook)
+static int g_op_wg_win = 0;                                        // wun_op_set_wgrad_win (test hook)
+static float* g_op_copy0 = nullptr; static float* g_op_copy1 = nullptr;   // wun_op_set_conv_copies (test hook)
+static int g_op_copy_t0 = 0, g_op_copy_t1 = 0, g_op_copy_exp = 0, g_op_copy_lo = 0, g_op_copy_len = 0, g_op_acc_lo = 0, g_op_acc_len = 0;
+static float* op_scratch() {
+    static float* buf = nullptr;
+    if (!buf && hipMalloc((void**)&buf, kOpScratchFloats * sizeof(float)) != hipSuccess) {
+        buf = nullptr;
+        (void)hipGetLastError();
+    }
+    return buf;
+}
+
+// The bf16 kernels read bf16 rows (the plan's activations are born bf16); the single-operator entry points receive fp32
+// tensors and convert them first -- rounding to nearest even, exactly what "operands rounded to bf16" means -- into a
+// process-wide temporary (slot 0 / 1) that grows on demand.  Rows are re-pitched to 16 bytes.
+static void* op_bf16_tmp(int slot, size_t bytes) {
+    static void* buf[2] = {nullptr, nullptr};
+    static size_t cap[2] = {0, 0};
+    if (bytes > cap[slot]) {
+        (void)hipDeviceSynchronize();
+        if (buf[slot]) (void)hipFree(buf[slot]);
+        buf[slot] = nullptr; cap[slot] = 0;
+        const size_t want = bytes + (bytes >> 2) + 4096;
+        if (hipMalloc(&buf[slot], want) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+        cap[slot] = want;
+    }
+    return buf[slot];
+}
+static inline int pad8(int t) { return (t + 7) / 8 * 8; }
+// fp32 [rows][spitch] (T valid) -> bf16 [rows][pad8(T)] in temporary `slot`; returns the bf16 base or null
+static const float* op_to_bf16(int slot, const float* src, long long rows, int T, long long spitch, hipStream_t s) {
+    void* dst = op_bf16_tmp(slot, (size_t)rows * pad8(T) * 2 + 64);
+    if (!dst) return nullptr;
+    if (launch_cast_rows_bf16(src, dst, rows, T, spitch, pad8(T), s) != hipSuccess) return nullptr;
+    return reinterpret_cast<const float*>(dst);
+}
+
+static hipError_t op_launch_conv(ConvArgs a, hipStream_t s) {
+    if (g_op_variant >= 0) { a.force_variant = g_op_variant + 1; a.force_ksplit = (a.flags & F_PHASE2) ? 0 : g_op_ksplit; }
+    return launch_conv(a, op_scratch(), kOpScratchFloats, s, wun_switches_from_env());
+}
+
+static void op_src(ConvArgs& a, const float* x, int C, int T) {
+    const int pitch = T;
+    a.src0 = x; a.bs0 = (long long)C * pitch; a.pitch0 = pitch; a.off0 = 0; a.C0 = C;
+}
+
+extern "C" int wun_op_conv1d(const float* x, const float* w, const float* bias, float* y, int batch, int cin,
+                             int cout, int k, int t_in, int t_out, int stride, int pad_left, int lrelu,
+                             void* stream) {
+    if (!x || !w || !y) return fail(WUN_ERR_INVALID, "null argument");
+    if (stride != 1 && stride != 2) return fail(WUN_ERR_UNSUPPORTED, "stride must be 1 or 2");
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = batch; a.ostride = 1;
+    op_src(a, x, cin, t_in);
+    a.loader = stride == 2 ? LOADER_DEINT : LOADER_DIRECT;
+    a.Tin = t_in; a.shift = pad_left; a.W = w; a.bias = bias; a.KW = k; a.N = a.N0 = cout; a.Tout = t_out;
+    a.flags = lrelu ? F_LRELU : 0;
+    a.dst0 = y; a.obs0 = (long long)cout * t_out; a.opitch0 = t_out;
+    HIP_TRY(op_launch_conv(a, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+static inline int pad4(int t) { return (t + 3) / 4 * 4; }
+
+static WgradArgs op_wgrad_args(const float* x, const float* dz, int batch, int cin, int cout, int k, int t_in,
+                               int t_out, int stride, int pad_left, int xp, int zp) {
+    WgradArgs w;
+    memset(&w, 0, sizeof(w));
+    w.B = batch; w.loader = stride == 2 ? LOADER_DEINT : LOADER_DIRECT;
+    w.src0 = x; w.bs0 = (long long)cin * xp; w.pitch0 = xp; w.C0 = cin;
+    w.Tin = t_in; w.shift = pad_left; w.KW = k;
+    w.dz = dz; w.dzbs = (long long)cout * zp; w.dzpitch = zp; w.N = cout; w.Tq = t_out;
+    return w;
+}
+
+// split partials of one loader kind under the current (possibly forced) geometry / split count
+static long long op_wgrad_part_floats(int batch, int cin, int cout, int k, int t_out, int loader, const WunSwitches& sw) {
+    WgradArgs a = wgrad_shape_only(batch, cin, 0, k, loader, cout, t_out);
+    a.bf16 = (g_op_wg_bf16 && wgrad_bf16_supported(a)) ? 1 : 0;
+    a.win = (g_op_wg_win && !a.bf16) ? 1 : 0;
+    if (a.win && !wgrad_win_supported(a)) a.win = 0;
+    if (g_op_wg_mtw > 0) { a.force_mtw = g_op_wg_mtw; a.force_nw = g_op_wg_nw; }
+    long long ns = wgrad_pick_nsplit(a, sw);
+    if (g_op_wg_nsplit > 0) ns = std::min(g_op_wg_nsplit, wgrad_max_units(a, sw));
+    if (g_op_wg_nsplit < 0 && a.win) ns = std::min(std::max(1, -g_op_wg_nsplit / wgrad_win_tiles(a, sw)), wgrad_max_units(a, sw));
+    return ns * wgrad_partial_floats(a, sw);
+}
+
+extern "C" int64_t wun_op_conv1d_wgrad_scratch(int batch, int cin, int cout, int k, int t_out) {
+    const WunSwitches sw = wun_switches_from_env();
+    // split partials (worst case over both loaders) + repacked copies of x (t_in <= 2*t_out + k) and dz
+    long long part = std::max(op_wgrad_part_floats(batch, cin, cout, k, t_out, LOADER_DIRECT, sw),
+                              op_wgrad_part_floats(batch, cin, cout, k, t_out, LOADER_DEINT, sw));
+    if (g_op_wg_narrow) {
+        // wun_op_set_wgrad_narrow(1): the direct-reduction kernels keep one (k * cin + 1) * cout vector per split
+        NarrowWgradArgs nw;
+        memset(&nw, 0, sizeof(nw));
+        nw.C0 = cin; nw.KW = k; nw.N = nw.Nper = cout; nw.Tq = t_out; nw.B = batch;
+        for (int stride = 1; stride <= 2; ++stride) {
+            nw.stride = stride;
+            part = std::max(part, (long long)narrow_wgrad_pick_nsplit(nw, sw) * narrow_wgrad_partial_floats(nw));
+        }
+    }
+    const long long tin_max = 2ll * t_out + k + 8;
+    return part + (long long)batch * cin * pad4((int)tin_max) + (long long)batch * cout * pad4(t_out) + 512;
+}
+
+extern "C" int wun_op_conv1d_wgrad(const float* x, const float* dz, float* dw, float* db, float* scratch,
+                                   int batch, int cin, int cout, int k, int t_in, int t_out, int stride,
+                                   int pad_left, void* stream) {
+    if (!x || !dz || !dw || !db || !scratch) return fail(WUN_ERR_INVALID, "null argument");
+    if (stride != 1 && stride != 2) return fail(WUN_ERR_UNSUPPORTED, "stride must be 1 or 2");
+    if (t_in > 2ll * t_out + k + 8) return fail(WUN_ERR_INVALID, "t_in larger than the conv can consume");
+    hipStream_t s = (hipStream_t)stream;
+    const WunSwitches sw = wun_switches_from_env();
+    // repack x / dz into the canonical 4-padded row layout the kernels use
+    const int xp = pad4(t_in), zp = pad4(t_out);
+    float* xs = scratch;                                   // 64-float aligned by construction below
+    xs = (float*)(((uintptr_t)xs + 255) & ~(uintptr_t)255);
+    float* zs = xs + (long long)batch * cin * xp;
+    float* part = zs + (long long)batch * cout * zp;
+    HIP_TRY(hipMemcpy2DAsync(xs, (size_t)xp * 4, x, (size_t)t_in * 4, (size_t)t_in * 4, (size_t)batch * cin,
+                             hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpy2DAsync(zs, (size_t)zp * 4, dz, (size_t)t_out * 4, (size_t)t_out * 4, (size_t)batch * cout,
+                             hipMemcpyDeviceToDevice, s));
+    if (g_op_wg_narrow) {
+        // the direct-reduction kernels of wun_narrow.hip (what the plan runs for the audio-input conv and the head)
+        NarrowWgradArgs nw;
+        memset(&nw, 0, sizeof(nw));
+        nw.src0 = xs; nw.bs0 = (long long)cin * xp; nw.pitch0 = xp; nw.off0 = 0; nw.C0 = cin;
+        nw.Tin = t_in; nw.shift = pad_left; nw.KW = k; nw.stride = stride;
+        nw.dz = zs; nw.zss = 0; nw.dzbs = (long long)cout * zp; nw.dzpitch = zp;
+        nw.N = nw.Nper = cout; nw.Tq = t_out; nw.B = batch;
+        if (!narrow_wgrad_supported(nw)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the narrow weight-gradient kernels");
+        nw.nsplit = narrow_wgrad_pick_nsplit(nw, sw);
+        part = (float*)(((uintptr_t)part + 255) & ~(uintptr_t)255);
+        nw.partial = part; nw.split_base = 0;
+        HIP_TRY(launch_narrow_wgrad(nw, s, sw));
+        const long long woff[4] = {0, 0, 0, 0}, boff[4] = {(long long)(db - dw), 0, 0, 0};
+        HIP_TRY(launch_narrow_wgrad_reduce(nw, part, nw.nsplit, dw, woff, boff, s));
+        return WUN_OK;
+    }
+    WgradArgs w = op_wgrad_args(xs, zs, batch, cin, cout, k, t_in, t_out, stride, pad_left, xp, zp);
+    if (g_op_wg_bf16 && !wgrad_bf16_supported(w)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the bf16 weight-gradient kernel");
+    w.bf16 = g_op_wg_bf16;
+    w.win = (g_op_wg_win && !w.bf16) ? 1 : 0;
+    if (w.win && !wgrad_win_supported(w)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the register-window weight-gradient kernel");
+    if (g_op_wg_mtw > 0) {
+        w.force_mtw = g_op_wg_mtw; w.force_nw = g_op_wg_nw;
+        int m, n;
+        wgrad_resolved_geom(w, m, n);
+        if (m != g_op_wg_mtw || n != g_op_wg_nw)
+            return fail(WUN_ERR_UNSUPPORTED, "forced weight-gradient tile geometry is not available for this shape");
+    }
+    w.nsplit = wgrad_pick_nsplit(w, sw);
+    if (g_op_wg_nsplit > 0) {
+        w.nsplit = std::min(g_op_wg_nsplit, wgrad_max_units(w, sw));
+    }
+    if (g_op_wg_nsplit < 0 && w.win)       // (window kernel: a negative count is a target grid size)
+        w.nsplit = std::min(std::max(1, -g_op_wg_nsplit / wgrad_win_tiles(w, sw)), wgrad_max_units(w, sw));
+    part = (float*)(((uintptr_t)part + 255) & ~(uintptr_t)255);
+    w.out = part; w.direct = 0; w.split_base = 0;      // always through the split reduction (dw and db are separate buffers)
+    if (w.bf16) {
+        // the bf16 kernel reads bf16 rows: convert the repacked copies of x and dz
+        w.src0 = op_to_bf16(0, xs, (long long)batch * cin, t_in, xp, s);
+        w.dz = op_to_bf16(1, zs, (long long)batch * cout, t_out, zp, s);
+        if (!w.src0 || !w.dz) return fail(WUN_ERR_NOMEM, "bf16 temporary");
+        w.pitch0 = pad8(t_in); w.bs0 = (long long)cin * w.pitch0;
+        w.dzpitch = pad8(t_out); w.dzbs = (long long)cout * w.dzpitch;
+        w.sbf = 1;
+    }
+    HIP_TRY(launch_wgrad(w, s, sw));
+    HIP_TRY(launch_wgrad_reduce(w, part, w.nsplit, dw, db, s, sw));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_conv1d_dgrad(const float* dz, const float* w, float* dx, float* wt_scratch, int batch,
+                                   int cin, int cout, int k, int t_in, int t_out, int stride, int pad_left,
+                                   void* stream) {
+    if (!dz || !w || !dx || !wt_scratch) return fail(WUN_ERR_INVALID, "null argument");
+    if (stride != 1 && stride != 2) return fail(WUN_ERR_UNSUPPORTED, "stride must be 1 or 2");
+    hipStream_t s = (hipStream_t)stream;
+    if (stride == 1) {
+        WtDesc d; d.src_off = 0; d.dst_off = 0; d.J = k; d.C = cin; d.N = cout; d.k_last = k - 1; d.k_step = 1; d.mode = 0;
+        HIP_TRY(launch_make_wt_one(w, wt_scratch, d, s));
+        ConvArgs a;
+        memset(&a, 0, sizeof(a));
+        a.B = batch; a.ostride = 1;
+        op_src(a, dz, cout, t_out);
+        a.Tin = t_out; a.shift = k - 1 - pad_left; a.W = wt_scratch; a.KW = k; a.N = a.N0 = cin; a.Tout = t_in;
+        a.dst0 = dx; a.obs0 = (long long)cin * t_in; a.opitch0 = t_in;
+        HIP_TRY(op_launch_conv(a, s));
+    } else {
+        if (pad_left != 0) return fail(WUN_ERR_UNSUPPORTED, "stride-2 dgrad supports pad_left == 0 only");
+        const int J0 = (k + 1) / 2;
+        ConvArgs f;
+        memset(&f, 0, sizeof(f));
+        f.B = batch; f.ostride = 1;
+        op_src(f, dz, cout, t_out);
+        f.Tin = t_out; f.KW = J0; f.kw_full = k; f.shift = J0 - 1; f.W = wt_scratch; f.N = f.N0 = cin;
+        f.Tout = (t_in + 1) / 2; f.Tlim = t_in; f.flags = F_PHASE2;
+        f.dst0 = dx; f.obs0 = (long long)cin * t_in; f.opitch0 = t_in;
+        if ((cin & 3) == 0 && conv_natural_wgs_phase2(f) >= 64) {
+            WtDesc d; d.src_off = 0; d.dst_off = 0; d.J = J0; d.C = cin; d.N = cout; d.k_last = 2 * (J0 - 1);
+            d.k_step = k; d.mode = 1;
+            HIP_TRY(launch_make_wt_one(w, wt_scratch, d, s));
+            HIP_TRY(op_launch_conv(f, s));
+            return WUN_OK;
+        }
+        for (int ph = 0; ph < 2; ++ph) {
+            const int Jp = (k - ph + 1) / 2;
+            float* wt = wt_scratch + (long long)ph * k * cin * cout;
+            WtDesc d; d.src_off = 0; d.dst_off = 0; d.J = Jp; d.C = cin; d.N = cout;
+            d.k_last = 2 * (Jp - 1) + ph; d.k_step = 2; d.mode = 0;
+            if (Jp > 0) HIP_TRY(launch_make_wt_one(w, wt, d, s));
+            ConvArgs a;
+            memset(&a, 0, sizeof(a));
+            a.B = batch; a.ostride = 2;
+            op_src(a, dz, cout, t_out);
+            a.Tin = t_out; a.KW = Jp; a.shift = Jp - 1; a.W = wt; a.N = a.N0 = cin; a.Tout = (t_in - ph + 1) / 2;
+            a.dst0 = dx; a.obs0 = (long long)cin * t_in; a.opitch0 = t_in; a.ooff0 = ph;
+            HIP_TRY(op_launch_conv(a, s));
+        }
+    }
+    return WUN_OK;
+}
+
+extern "C" int wun_op_force_conv_variant(int variant, int ksplit) {
+    g_op_variant = variant; g_op_ksplit = ksplit;
+    return WUN_OK;
+}
+
+extern "C" int wun_op_num_conv_variants(void) { return conv_num_variants(); }
+
+extern "C" int wun_op_set_wgrad_bf16(int on) { g_op_wg_bf16 = on ? 1 : 0; return WUN_OK; }
+extern "C" int wun_op_set_wgrad_win(int on) { g_op_wg_win = on ? 1 : 0; return WUN_OK; }
+extern "C" int wun_op_set_wgrad_narrow(int on) { g_op_wg_narrow = on ? 1 : 0; return WUN_OK; }
+
+extern "C" int wun_op_force_wgrad_variant(int mtw, int nw, int nsplit) {
+    g_op_wg_mtw = mtw; g_op_wg_nw = nw; g_op_wg_nsplit = nsplit;
+    return WUN_OK;
+}
+
+// General form of the conv launch the plan uses: virtual channel-concat of two sources (crop_and_concat,
+// Utils.py:11-24), accumulate into the destination, LeakyReLU-derivative mask, output stride / offset.
+extern "C" int wun_op_conv1d_ex(const float* x0, int c0, const float* x1, int c1, const float* w, const float* bias,
+                                float* y, const float* mask, int batch, int cout, int k, int t_in, int t_out,
+                                int t_y, int stride, int pad_left, int lrelu, int accumulate, int ostride, int ooff,
+                                void* stream) {
+    if (!x0 || !w || !y) return fail(WUN_ERR_INVALID, "null argument");
+    if (stride != 1 && stride != 2) return fail(WUN_ERR_UNSUPPORTED, "stride must be 1 or 2");
+    if (c0 < 1 || c1 < 0 || (c1 > 0 && !x1)) return fail(WUN_ERR_INVALID, "bad source channels");
+    if (ostride < 1 || ooff < 0 || (long long)(t_out - 1) * ostride + ooff >= t_y) return fail(WUN_ERR_INVALID, "output does not fit t_y");
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = batch; a.ostride = ostride;
+    a.src0 = x0; a.bs0 = (long long)c0 * t_in; a.pitch0 = t_in; a.C0 = c0;
+    if (c1 > 0) { a.src1 = x1; a.bs1 = (long long)c1 * t_in; a.pitch1 = t_in; a.C1 = c1; }
+    a.loader = stride == 2 ? LOADER_DEINT : LOADER_DIRECT;
+    a.Tin = t_in; a.shift = pad_left; a.W = w; a.bias = bias; a.KW = k; a.N = a.N0 = cout; a.Tout = t_out;
+    a.flags = (lrelu ? F_LRELU : 0) | (accumulate ? F_ACCUM : 0);
+    a.dst0 = y; a.obs0 = (long long)cout * t_y; a.opitch0 = t_y; a.ooff0 = ooff; a.msk0 = mask;
+    if (g_op_copy0 != nullptr) {
+        a.dec = g_op_copy0; a.decpitch = g_op_copy_t0; a.decbs = (long long)cout * g_op_copy_t0;
+        a.dec_exp = g_op_copy_exp; a.dec_lo = g_op_copy_lo; a.dec_len = (unsigned)g_op_copy_len;
+    }
+    if (g_op_copy1 != nullptr) { a.dec1 = g_op_copy1; a.dec1pitch = g_op_copy_t1; a.dec1bs = (long long)cout * g_op_copy_t1; }
+    if (accumulate && g_op_acc_len > 0) { a.acc_lo = g_op_acc_lo; a.acc_len = (unsigned)g_op_acc_len; }
+    HIP_TRY(op_launch_conv(a, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_set_conv_copies(float* copy0, int t0, int expand, int exp_lo, int exp_len, float* copy1, int t1,
+                                      int acc_lo, int acc_len) {
+    if ((copy0 && t0 < 1) || (copy1 && t1 < 1) || exp_len < 0 || acc_len < 0) return fail(WUN_ERR_INVALID, "bad copy geometry");
+    g_op_copy0 = copy0; g_op_copy_t0 = t0; g_op_copy_exp = expand ? 1 : 0; g_op_copy_lo = exp_lo; g_op_copy_len = exp_len;
+    g_op_copy1 = copy1; g_op_copy_t1 = t1; g_op_acc_lo = acc_lo; g_op_acc_len = acc_len;
+    return WUN_OK;
+}
+
+// bf16-MFMA conv as a single operator: packs w (fp32 [K][Cin][Cout]) into the bf16 image in `scratch`
+// (>= wun_op_conv1d_bf16_scratch floats), then runs the bf16 kernel.  Same semantics as wun_op_conv1d.
+extern "C" int64_t wun_op_conv1d_bf16_scratch(int cin, int cout, int k) {
+    return (int64_t)k * bf16_image_groups(cin) * ((cout + 63) / 64 * 64) * 4 + 64;
+}
+
+extern "C" int wun_op_conv1d_bf16(const float* x, const float* w, const float* bias, float* y, float* scratch,
+                                  int batch, int cin, int cout, int k, int t_in, int t_out, int stride, int pad_left,
+                                  int lrelu, void* stream) {
+    if (!x || !w || !y || !scratch) return fail(WUN_ERR_INVALID, "null argument");
+    if (stride != 1 && stride != 2) return fail(WUN_ERR_UNSUPPORTED, "stride must be 1 or 2");
+    hipStream_t s = (hipStream_t)stream;
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = batch; a.ostride = 1;
+    op_src(a, x, cin, t_in);
+    a.loader = stride == 2 ? LOADER_DEINT : LOADER_DIRECT;
+    a.Tin = t_in; a.shift = pad_left; a.bias = bias; a.KW = k; a.N = a.N0 = cout; a.Tout = t_out;
+    a.flags = lrelu ? F_LRELU : 0;
+    a.dst0 = y; a.obs0 = (long long)cout * t_out; a.opitch0 = t_out;
+    // the kernel reads bf16 rows: convert x (fp32 output, obf = 0, keeps the comparison with float64 sharp)
+    a.src0 = op_to_bf16(0, x, (long long)batch * cin, t_in, t_in, s);
+    if (!a.src0) return fail(WUN_ERR_NOMEM, "bf16 temporary");
+    a.pitch0 = pad8(t_in); a.bs0 = (long long)cin * a.pitch0; a.xbf = 1; a.obf = 0;
+    if (!conv_bf16_supported(a)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the bf16 kernel (cin < 8 or k > 15)");
+    float* img = (float*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+    PackDesc d;
+    d.src_off = 0; d.src_in_ws = 0; d.dst_off = 0; d.KW = k; d.C = cin; d.N = cout;
+    d.C8p = bf16_image_groups(cin); d.Npad = (cout + 63) / 64 * 64;
+    PackDesc* dd = nullptr;
+    HIP_TRY(hipMalloc((void**)&dd, sizeof(PackDesc)));
+    hipError_t e = hipMemcpyAsync(dd, &d, sizeof(d), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_pack_bf16(w, img, dd, 1, (long long)k * d.C8p * d.Npad, s);
+    a.W = img; a.wb_c8p = d.C8p; a.wb_npad = d.Npad;
+    if (e == hipSuccess) e = launch_conv_bf16(a, s, wun_switches_from_env());
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dd);
+    HIP_TRY(e);
+    return WUN_OK;
+}
+
+// Input gradient of the bf16 speed mode as a single operator (wun_op_conv1d_dgrad semantics): stride 1 = the
+// bf16 conv on tap-flipped / transposed weights, stride 2 = the fused two-phase transposed conv (a lane owns 8
+// consecutive outputs).  scratch: >= wun_op_conv1d_dgrad_bf16_scratch floats.  Synchronises the stream.
+extern "C" int64_t wun_op_conv1d_dgrad_bf16_scratch(int cin, int cout, int k) {
+    const int64_t wt = 2ll * (k + 1) * cin * cout + 64;                                       // transposed fp32 copy
+    const int64_t img = (int64_t)(k + 1) * bf16_image_groups(cout) * ((2 * cin + 32 + 63) / 64 * 64) * 4 + 64;
+    return wt + img + 128;
+}
+
+extern "C" int wun_op_conv1d_dgrad_bf16(const float* dz, const float* w, float* dx, float* scratch, int batch, int cin,
+                                        int cout, int k, int t_in, int t_out, int stride, int pad_left, void* stream) {
+    if (!dz || !w || !dx || !scratch) return fail(WUN_ERR_INVALID, "null argument");
+    if (stride != 1 && stride != 2) return fail(WUN_ERR_UNSUPPORTED, "stride must be 1 or 2");
+    if (stride == 2 && (pad_left != 0 || (cin & 3) != 0)) return fail(WUN_ERR_UNSUPPORTED, "stride-2: pad_left 0 and cin % 4 == 0 only");
+    hipStream_t s = (hipStream_t)stream;
+    float* wt = (float*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+    float* img = (float*)(((uintptr_t)(wt + 2ll * (k + 1) * cin * cout) + 255) & ~(uintptr_t)255);
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = batch; a.ostride = 1;
+    op_src(a, dz, cout, t_out);
+    a.Tin = t_out; a.N = a.N0 = cin;
+    a.dst0 = dx; a.obs0 = (long long)cin * t_in; a.opitch0 = t_in;
+    WtDesc d; d.src_off = 0; d.dst_off = 0; d.C = cin; d.N = cout;
+    PackDesc pd; pd.src_off = 0; pd.src_in_ws = 0; pd.dst_off = 0; pd.C = cout;
+    if (stride == 1) {
+        d.J = k; d.k_last = k - 1; d.k_step = 1; d.mode = 0;
+        a.shift = k - 1 - pad_left; a.KW = k; a.Tout = t_in;
+        pd.KW = k; pd.N = cin; pd.Npad = (cin + 63) / 64 * 64;
+    } else {
+        const int J0 = (k + 1) / 2;
+        d.J = J0; d.k_last = 2 * (J0 - 1); d.k_step = k; d.mode = 1;
+        a.KW = J0; a.kw_full = k; a.shift = J0 - 1; a.Tout = (t_in + 1) / 2; a.Tlim = t_in; a.flags = F_PHASE2;
+        pd.KW = J0; pd.N = 2 * cin; pd.Npad = (2 * cin + 32 + 63) / 64 * 64;
+    }
+    pd.C8p = bf16_image_groups(cout);
+    a.src0 = op_to_bf16(0, dz, (long long)batch * cout, t_out, t_out, s);
+    if (!a.src0) return fail(WUN_ERR_NOMEM, "bf16 temporary");
+    a.pitch0 = pad8(t_out); a.bs0 = (long long)cout * a.pitch0; a.xbf = 1; a.obf = 0;
+    if (!conv_bf16_supported(a)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the bf16 kernel");
+    HIP_TRY(launch_make_wt_one(w, wt, d, s));
+    PackDesc* dd = nullptr;
+    HIP_TRY(hipMalloc((void**)&dd, sizeof(PackDesc)));
+    hipError_t e = hipMemcpyAsync(dd, &pd, sizeof(pd), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_pack_bf16(wt, img, dd, 1, (long long)pd.KW * pd.C8p * pd.Npad, s);
+    a.W = img; a.wb_c8p = pd.C8p; a.wb_npad = pd.Npad;
+    if (e == hipSuccess) e = launch_conv_bf16(a, s, wun_switches_from_env());
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dd);
+    HIP_TRY(e);
+    return WUN_OK;
+}
+
+/* Lane layout probe of v_mfma_f32_16x16x32_bf16: d[16][16] = bf16(a[16][32]) * bf16(b[32][16]). */
+extern "C" int wun_op_mfma_bf16_probe(const float* a, const float* b, float* d, void* stream) {
+    if (!a || !b || !d) return fail(WUN_ERR_INVALID, "null argument");
+    HIP_TRY(launch_mfma_bf16_probe(a, b, d, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_mfma_probe(const float* a, const float* b, float* d, void* stream) {
+    if (!a || !b || !d) return fail(WUN_ERR_INVALID, "null argument");
+    HIP_TRY(launch_mfma_probe(a, b, d, (hipStream_t)stream));
+    return WUN_OK;
+}

@@ -579,7 +579,7 @@ struct WinGeom { int K15, NW, S; WinParams p; size_t lds; int threads; };
 // tile choice: K = 15 -> 8 channels x {taps k, k + 8}, three row tiles (24 channels) per workgroup; K = 5 -> 16 channels,
 // four row tiles.  Column tiles per wave: the count in {3, 4, 5} (K = 15) / {2 .. 6} (K = 5) that pads N least, ties to
 // the smaller (<= 24 accumulator tiles fit 3 waves per SIMD).  force_mtw / force_nw override (autotuner, test hook).
-static WinGeom wgrad_win_geom(const WgradArgs& a) {
+static WinGeom wgrad_win_geom(const WgradArgs& a, const WunSwitches& sw) {
     WinGeom g;
     const int Ctot = a.C0 + a.C1;
     g.S = a.loader == LOADER_DEINT ? 2 : 1;
@@ -615,8 +615,7 @@ static WinGeom wgrad_win_geom(const WgradArgs& a) {
     int wgs = wps / p.CGW;
     if (wgs < 1) wgs = 1;
     const size_t lds_cap = (size_t)(160 * 1024) / (size_t)wgs;
-    int tk = 64;
-    if (const char* e = getenv("WUN_WIN_TK")) { const int v = atoi(e); if (v == 16 || v == 32 || v == 64 || v == 128) tk = v; }
+    int tk = sw.win_tk;
     while (tk > 16 && tk / 2 >= a.Tq) tk /= 2;
     for (;;) {
         p.TK = tk;
@@ -639,12 +638,12 @@ static WinGeom wgrad_win_geom(const WgradArgs& a) {
     return g;
 }
 
-long long wgrad_win_partial_floats(const WgradArgs& a) { return wgrad_win_geom(a).p.pstride; }
-int wgrad_win_units(const WgradArgs& a) { const WinGeom g = wgrad_win_geom(a); return a.B * ((a.Tq + g.p.TK - 1) / g.p.TK); }
-int wgrad_win_tiles(const WgradArgs& a) { const WinGeom g = wgrad_win_geom(a); return g.p.nMG * g.p.nNG; }
+long long wgrad_win_partial_floats(const WgradArgs& a, const WunSwitches& sw) { return wgrad_win_geom(a, sw).p.pstride; }
+int wgrad_win_units(const WgradArgs& a, const WunSwitches& sw) { const WinGeom g = wgrad_win_geom(a, sw); return a.B * ((a.Tq + g.p.TK - 1) / g.p.TK); }
+int wgrad_win_tiles(const WgradArgs& a, const WunSwitches& sw) { const WinGeom g = wgrad_win_geom(a, sw); return g.p.nMG * g.p.nNG; }
 
 template <bool K15, int NW, int S>
-static hipError_t win_launch_t(WgradArgs a, const WinGeom& g, hipStream_t s) {
+static hipError_t win_launch_t(WgradArgs a, const WinGeom& g, hipStream_t s, bool occ_log) {
     a.nQT = (a.Tq + g.p.TK - 1) / g.p.TK;
     const long long units = (long long)a.B * a.nQT;
     a.units_per_split = (int)((units + a.nsplit - 1) / a.nsplit);
@@ -660,25 +659,25 @@ static hipError_t win_launch_t(WgradArgs a, const WinGeom& g, hipStream_t s) {
     snprintf(nm, sizeof(nm), "wgrad_win_kernel<%d, %d, %d>", K15 ? 15 : 5, NW, S);
     char tag[200];
     int occ = -1;
-    if (getenv("WUN_WIN_OCC")) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, g.threads, g.lds);
+    if (occ_log) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, g.threads, g.lds);
     snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nsplit=%d grid=%lld w=%dx%d tk=%d lds=%zu occ=%d", a.C0 + a.C1, a.N, a.Tq,
              a.KW, a.loader, a.B, a.nsplit, grid, 4, g.p.CGW, g.p.TK, g.lds, occ);
-    if (getenv("WUN_WIN_OCC")) fprintf(stderr, "[win] %s %s\n", nm, tag);
+    if (occ_log) fprintf(stderr, "[win] %s %s\n", nm, tag);
     prof_scope_begin(nm, 2.0 * a.KW * (double)(a.C0 + a.C1) * a.N * (double)a.Tq * a.B, s, tag);
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(g.threads), g.lds, s, a, g.p);
     prof_scope_end(s);
     return hipGetLastError();
 }
 
-hipError_t launch_wgrad_win(const WgradArgs& a, hipStream_t s) {
+hipError_t launch_wgrad_win(const WgradArgs& a, hipStream_t s, const WunSwitches& sw) {
     if (!wgrad_win_supported(a)) return hipErrorInvalidValue;
-    const WinGeom g = wgrad_win_geom(a);
+    const WinGeom g = wgrad_win_geom(a, sw);
     if (g.lds > 160 * 1024) return hipErrorInvalidValue;
     {
         const long long xs = g.p.zoff / 4, zs = (g.p.bufFloats - g.p.zoff) / 4;
         if (xs > (long long)WUN_WIN_XIT * g.threads || zs > (long long)WUN_WIN_ZIT * g.threads) return hipErrorInvalidValue;
     }
-#define WUN_WIN(k15, nw, ss) if (g.K15 == k15 && g.NW == nw && g.S == ss) return win_launch_t<k15 != 0, nw, ss>(a, g, s);
+#define WUN_WIN(k15, nw, ss) if (g.K15 == k15 && g.NW == nw && g.S == ss) return win_launch_t<k15 != 0, nw, ss>(a, g, s, sw.win_occ);
     WUN_WIN(1, 1, 1) WUN_WIN(1, 2, 1) WUN_WIN(1, 3, 1) WUN_WIN(1, 4, 1) WUN_WIN(1, 5, 1)
     WUN_WIN(1, 1, 2) WUN_WIN(1, 2, 2) WUN_WIN(1, 3, 2) WUN_WIN(1, 4, 2) WUN_WIN(1, 5, 2)
     WUN_WIN(0, 1, 1) WUN_WIN(0, 2, 1) WUN_WIN(0, 3, 1) WUN_WIN(0, 4, 1) WUN_WIN(0, 5, 1) WUN_WIN(0, 6, 1)
@@ -687,8 +686,8 @@ hipError_t launch_wgrad_win(const WgradArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_wgrad_win_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
-                                   hipStream_t s) {
-    const WinGeom g = wgrad_win_geom(a);
+                                   hipStream_t s, const WunSwitches& sw) {
+    const WinGeom g = wgrad_win_geom(a, sw);
     const long long nw = (long long)a.KW * (a.C0 + a.C1) * a.N, n = nw + a.N;
     const long long n4 = (n + 3) / 4;
     char tag[96];
