@@ -208,6 +208,25 @@ int wun_loss_backward_ex(const wun_plan* plan, const float* params, const float*
                          float* grads, float* loss, void* stream,
                          const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets);
 
+/* Backward pass of get_output from an arbitrary upstream gradient -- what tf.gradients gives the reference for any loss
+ * built on get_output's outputs (Training.py:50-63 picks MSE or a spectral L1; a caller may use any), with respect to the
+ * variables and, optionally, the input mix.  Must follow wun_forward(training = 1) on the same workspace / outputs.
+ *   outputs   : device, [S, B, Tout, C]  what wun_forward wrote (read for the tanh derivative)
+ *   d_outputs : device, [S, B, Tout, C]  dL/d outputs
+ *   grads     : device, arena_floats.  Parameter gradients are OVERWRITTEN exactly as wun_loss_backward writes them (same
+ *               tensors, same offsets; padding floats are left as they are)
+ *   d_mix     : device, [B, Tin, C] or NULL.  dL/d mix_btc, overwritten (0 at samples the network never reads); NULL = not
+ *               computed, no extra launch.  One more launch (mix_grad_kernel) on `stream` near the end of the pass.
+ * With d_outputs = 2 / (S B Tout C) * (outputs - targets) the parameter gradients are those of wun_loss_backward.
+ * WUN_ERR_INVALID for a null plan / params / workspace / outputs / d_outputs / grads or bad buckets, before any GPU work;
+ * WUN_ERR_UNSUPPORTED (with a message) for a d_mix the plan's shapes cannot serve.  mix_btc is not read (may be NULL).
+ * wun_backward_ex: the data-parallel bucket hooks of wun_loss_backward_ex. */
+int wun_backward(const wun_plan* plan, const float* params, const float* mix_btc, float* workspace,
+                 const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream);
+int wun_backward_ex(const wun_plan* plan, const float* params, const float* mix_btc, float* workspace,
+                    const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
+                    const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets);
+
 /* Optional autotuning pass (no reference counterpart): runs one forward + loss/backward on the
  * given buffers while timing, for every conv / weight-gradient launch of the step, the candidate
  * tile shapes and split factors, and caches the fastest per launch in the plan.  The contents of

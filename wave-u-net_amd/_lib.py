@@ -44,6 +44,8 @@ _SIGS = {
     "wun_forward": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P]),
     "wun_loss_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "wun_loss_backward_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.c_int32]),
+    "wun_backward": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "wun_backward_ex": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.c_int32]),
     "wun_plan_tune": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "wun_plan_tune_export": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "wun_plan_tune_import": (C.c_int, [_P, C.c_char_p]),

@@ -663,6 +663,25 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(HeadArgs a) {
     if (threadIdx.x == 0) a.loss_partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// dpre from an upstream gradient instead of the MSE (wun_backward): g_s = dout[s] - (difference ? dout[S-1] : 0), times the
+// tanh derivative (1 - y_s^2) -- head_bwd_kernel's arithmetic with gscale * (y - target) replaced by dout
+__global__ __launch_bounds__(256) void head_grad_kernel(HeadArgs a) {
+    const long long total = (long long)a.B * a.Tout;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * 256) {
+        const int t = (int)(idx % a.Tout), b = (int)(idx / a.Tout);
+        for (int c = 0; c < a.C; ++c) {
+            const float glast = a.difference ? a.dout[(((long long)(a.S - 1) * a.B + b) * a.Tout + t) * a.C + c] : 0.f;
+            for (int s = 0; s < a.Sh; ++s) {
+                const long long o = (((long long)s * a.B + b) * a.Tout + t) * a.C + c;
+                float g = a.dout[o] - glast;
+                if (a.tanh_act) { const float y = a.out[o]; g *= (1.f - y * y); }
+                a.dpre[(long long)s * a.dps + (long long)b * a.dpbs + (long long)c * a.dppitch + t] = g;
+            }
+        }
+    }
+}
+
 // dzfeat[b][f][u] = lrelu'(feat) * sum_{k,s,c} W[s][k][C+f][c] * dpre[s][b][c][u - k + padl]
 // one feature-map position (b, u), all F channels
 template <typename FT>
@@ -983,6 +1002,8 @@ int head_bwd_blocks(const HeadArgs& a) {
     return (int)blocks;
 }
 
+static hipError_t launch_head_dfeat(const HeadArgs& a, const long long* hoff, hipStream_t s);
+
 hipError_t launch_head_bwd_off(const HeadArgs& a, const long long* hoff, hipStream_t s) {
     {
         // outputs + targets read, d(pre-activation) written
@@ -991,6 +1012,21 @@ hipError_t launch_head_bwd_off(const HeadArgs& a, const long long* hoff, hipStre
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_head_dfeat(a, hoff, s);
+}
+
+hipError_t launch_head_grad_off(const HeadArgs& a, const long long* hoff, hipStream_t s) {
+    {
+        // upstream gradient (+ outputs for tanh) read, d(pre-activation) written
+        ProfScope ps("head_grad_kernel", 0.0, s, "", 4.0 * (double)a.B * a.Tout * a.C * (a.S + (a.tanh_act ? 2.0 : 1.0) * a.Sh));
+        hipLaunchKernelGGL(head_grad_kernel, dim3((unsigned)head_bwd_blocks(a)), dim3(256), 0, s, a);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_head_dfeat(a, hoff, s);
+}
+
+static hipError_t launch_head_dfeat(const HeadArgs& a, const long long* hoff, hipStream_t s) {
     // (d(pre-activation) read, the feature map read for its LeakyReLU mask, d(feature map) written)
     ProfScope ps("head_dfeat_kernel", 0.0, s, "", (double)a.B * (4.0 * (double)a.Tout * a.Sh * a.C + (a.featbf ? 4.0 : 8.0) * (double)a.Tfeat * a.F));
     const long long total = (long long)a.B * a.Tfeat;

@@ -233,6 +233,24 @@ struct HeadArgs {
     float* loss_partial;                                   // [gridDim.x]
     float gscale;                                          // 2 / (S*B*Tout*C)
     int featbf;                                            // feat and dzfeat hold bf16 elements (fbs / fpitch in elements)
+    const float* dout;                                     // wun_backward: dL/d outputs [S][B][Tout][C] (instead of tgt)
+};
+
+// Gradient of the loss w.r.t. the mix (wun_backward, wun_narrow.hip): dmix[b][t][c] = the transposed conv of down conv 0's
+// d(pre-activation) (up to two parts, each the geometry of one forward launch of that conv:
+//   z[b][n][q] = sum_{k,c} W[k][c][n] * x[b][c][off0 + stride*q + k - shift],  0 <= stride*q + k - shift < Tin)
+// + the head's transposed conv of dpre over the mix-channel rows of every source's output kernel (OutputLayer.py:8,15)
+// + dlast inside the difference crop (OutputLayer.py:20).  Every element written once; 0 where nothing reads the mix.
+struct MixGradPart { const float* dz; long long dzbs; int dzpitch; int Tq, stride, off0, shift, Tin; };
+struct MixGradArgs {
+    MixGradPart part[2]; int nparts;
+    int dzbf;                                              // the parts' dz rows hold bf16 elements (strides in elements)
+    const float* W; int KW, F;                             // down conv 0 kernel [KW][C][F]
+    int C, B, Tin;
+    const float* dpre; long long dps, dpbs; int dppitch;   // head: [Sh][B][C][pitch]
+    const float* Wh; long long hoff[4]; int Sh, Ko, padl, Tfeat, Tout, moff_feat;
+    const float* dlast; int moff_diff;                     // difference output: dL/d out[S-1] [B][Tout][C], or null
+    float* dmix;                                           // [B][Tin][C]
 };
 
 // bf16 mode: one conv's weights, fp32 [KW][C][N] (from the parameter arena or a transposed copy in
@@ -306,6 +324,7 @@ hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s);         
 hipError_t launch_head_fwd_off(const HeadArgs& a, const long long* hoff, hipStream_t s);
 int head_bwd_blocks(const HeadArgs& a);
 hipError_t launch_head_bwd_off(const HeadArgs& a, const long long* hoff, hipStream_t s);
+hipError_t launch_head_grad_off(const HeadArgs& a, const long long* hoff, hipStream_t s);   // dpre from a.dout, then d(feature map)
 hipError_t launch_loss_finish(const float* partial, int n, float scale, float* loss, hipStream_t s);
 hipError_t launch_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pitch,
                              hipStream_t s);
@@ -329,6 +348,8 @@ long long narrow_wgrad_partial_floats(const NarrowWgradArgs& a);
 hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitches& sw);
 hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* partial, int nsplit, float* grads,
                                       const long long* woff, const long long* boff, hipStream_t s);
+size_t mix_grad_lds_bytes(const MixGradArgs& a);
+hipError_t launch_mix_grad(const MixGradArgs& a, hipStream_t s);
 
 // ---- bf16-MFMA speed mode (wun_bf16.hip) ----
 // 8-channel groups of a packed bf16 weight image for C input channels: the conv kernel reads whole stages of

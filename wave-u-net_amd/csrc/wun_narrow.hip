@@ -443,4 +443,109 @@ hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* par
     return hipGetLastError();
 }
 
+// =====================================================================================
+// Gradient w.r.t. the mix (wun_backward with d_mix; MixGradArgs in wun_internal.h).  The audio feeds three places: down conv 0
+// (UnetAudioSeparator.py:98), the output head's input crop (OutputLayer.py:8,15) and the difference output (OutputLayer.py:20).
+// One thread owns one (excerpt, sample) and writes its C channel-last values once: the transposed conv of down conv 0's
+// d(pre-activation) -- lanes walk consecutive samples, so every dz row is read coalesced along t (a stride-2 part: lane pairs
+// read the same element with taps k, k + 1) -- plus the head's transposed conv over the mix-channel rows of every source's
+// kernel, plus the difference term.  Weights in LDS (uniform across the wave: broadcast reads).  Fixed summation order, no
+// atomics: deterministic.  Bound by reading level 0's gradient once (L2 serves the taps' re-reads).
+// =====================================================================================
+template <typename ZT, int CH>
+__global__ __launch_bounds__(256) void mix_grad_kernel(MixGradArgs a) {
+    extern __shared__ float mlds[];
+    const int nw = a.KW * CH * a.F;
+    float* Ws = mlds;                                       // [KW][CH][F]: down conv 0's kernel
+    float* Hs = mlds + nw;                                  // [Sh][Ko][CH (mix channel)][CH (output channel)]
+    for (int i = threadIdx.x; i < nw; i += 256) Ws[i] = a.W[i];
+    const int hb = a.Ko * CH * CH, cin = CH + a.F;
+    for (int i = threadIdx.x; i < a.Sh * hb; i += 256) {
+        const int sh = i / hb, r = i - sh * hb, k = r / (CH * CH);
+        Hs[i] = a.Wh[a.hoff[sh] + (long long)k * cin * CH + (r - k * CH * CH)];   // kernel [Ko][C + F][C], rows ci < C
+    }
+    __syncthreads();
+    const long long total = (long long)a.B * a.Tin;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int t = (int)(idx % a.Tin), b = (int)(idx / a.Tin);
+        float acc[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) acc[c] = 0.f;
+        for (int pi = 0; pi < a.nparts; ++pi) {
+            const MixGradPart& P = a.part[pi];
+            const int r = t - P.off0;
+            if (r < 0 || r >= P.Tin) continue;
+            const ZT* __restrict__ zb = reinterpret_cast<const ZT*>(P.dz) + (long long)b * P.dzbs;
+            const int u0 = r + P.shift, sl = P.stride - 1;      // stride 1 or 2
+            for (int k = u0 & sl; k < a.KW && k <= u0; k += P.stride) {
+                const int q = (u0 - k) >> sl;
+                if (q >= P.Tq) continue;
+                const float* w = Ws + k * CH * a.F;
+                const ZT* zq = zb + q;
+#pragma unroll 4
+                for (int n = 0; n < a.F; ++n) {
+                    const float z = ld1<ZT>(zq, (long long)n * P.dzpitch);
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) acc[c] += w[c * a.F + n] * z;
+                }
+            }
+        }
+        const int tf = t - a.moff_feat;
+        if (tf >= 0 && tf < a.Tfeat) {
+            for (int k = 0; k < a.Ko; ++k) {
+                const int to = tf - k + a.padl;
+                if (to < 0 || to >= a.Tout) continue;
+                for (int sh = 0; sh < a.Sh; ++sh) {
+                    const float* h = Hs + (sh * a.Ko + k) * CH * CH;
+#pragma unroll
+                    for (int c = 0; c < CH; ++c) {
+                        const float g = a.dpre[(long long)sh * a.dps + (long long)b * a.dpbs + (long long)c * a.dppitch + to];
+#pragma unroll
+                        for (int ci = 0; ci < CH; ++ci) acc[ci] += h[ci * CH + c] * g;
+                    }
+                }
+            }
+        }
+        if (a.dlast) {
+            const int td = t - a.moff_diff;
+            if (td >= 0 && td < a.Tout) {
+#pragma unroll
+                for (int c = 0; c < CH; ++c) acc[c] += a.dlast[((long long)b * a.Tout + td) * CH + c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CH; ++c) a.dmix[idx * CH + c] = acc[c];
+    }
+}
+
+size_t mix_grad_lds_bytes(const MixGradArgs& a) {
+    return sizeof(float) * ((size_t)a.KW * a.C * a.F + (size_t)a.Sh * a.Ko * a.C * a.C);
+}
+
+hipError_t launch_mix_grad(const MixGradArgs& a, hipStream_t s) {
+    const size_t lds = mix_grad_lds_bytes(a);
+    if ((a.C != 1 && a.C != 2) || lds > 64 * 1024 || a.nparts < 1 || a.nparts > 2) return hipErrorInvalidValue;
+    const long long total = (long long)a.B * a.Tin;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) return hipSuccess;
+    double zbytes = 0, flops = 0;
+    for (int i = 0; i < a.nparts; ++i) {
+        zbytes += (double)a.B * a.F * a.part[i].Tq * (a.dzbf ? 2.0 : 4.0);
+        flops += 2.0 * a.B * a.part[i].Tq * (double)a.KW * a.C * a.F;
+    }
+    // (level 0's gradient and the head's d(pre-activation) read once, d_mix written once)
+    prof_scope_begin("mix_grad_kernel", flops, s, "",
+                     zbytes + 4.0 * (double)a.B * a.Tout * a.C * (a.Sh + (a.dlast ? 1 : 0)) + 4.0 * (double)total * a.C);
+    if (a.dzbf) {
+        if (a.C == 1) hipLaunchKernelGGL((mix_grad_kernel<bf16_t, 1>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((mix_grad_kernel<bf16_t, 2>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    } else {
+        if (a.C == 1) hipLaunchKernelGGL((mix_grad_kernel<float, 1>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((mix_grad_kernel<float, 2>), dim3((unsigned)blocks), dim3(256), lds, s, a);
+    }
+    prof_scope_end(s);
+    return hipGetLastError();
+}
+
 }  // namespace wun

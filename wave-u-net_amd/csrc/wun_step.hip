@@ -216,16 +216,100 @@ extern "C" int wun_loss_backward(const wun_plan* p, const float* params, const f
     return wun_loss_backward_ex(p, params, mix_btc, ws, outputs, targets, grads, loss, stream, nullptr, nullptr, 0);
 }
 
+static int check_buckets(const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets) {
+    if (nbuckets < 0 || (nbuckets > 0 && (!bucket_starts || !bucket_events))) return fail(WUN_ERR_INVALID, "bad bucket arguments");
+    for (int k = 1; k < nbuckets; ++k)
+        if (bucket_starts[k] >= bucket_starts[k - 1]) return fail(WUN_ERR_INVALID, "bucket_starts must be strictly descending");
+    return WUN_OK;
+}
+
+// The head of the backward pass: "MSE against targets" (wun_loss_backward: head_bwd_kernel + loss_finish) or "upstream gradient"
+// (wun_backward: head_grad_kernel from d_outputs).  Everything after the head's d(pre-activation) is one body.
+struct BackwardHead { const float* targets; float* loss; const float* d_outputs; };
+
+static int backward_body(const wun_plan* p, const float* params, float* ws, const float* outputs, const BackwardHead& head,
+                         float* grads, const MixGradArgs* mix, void* stream, const int64_t* bucket_starts,
+                         void* const* bucket_events, int32_t nbuckets);
+
 extern "C" int wun_loss_backward_ex(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
                                     const float* outputs, const float* targets, float* grads, float* loss,
                                     void* stream, const int64_t* bucket_starts, void* const* bucket_events,
                                     int32_t nbuckets) {
     (void)mix_btc;
-    if (nbuckets < 0 || (nbuckets > 0 && (!bucket_starts || !bucket_events))) return fail(WUN_ERR_INVALID, "bad bucket arguments");
-    for (int k = 1; k < nbuckets; ++k)
-        if (bucket_starts[k] >= bucket_starts[k - 1]) return fail(WUN_ERR_INVALID, "bucket_starts must be strictly descending");
-    BucketSignal sig{bucket_starts, bucket_events, nbuckets, 0};
+    int rc;
+    if ((rc = check_buckets(bucket_starts, bucket_events, nbuckets))) return rc;
     if (!p || !params || !ws || !outputs || !targets || !grads || !loss) return fail(WUN_ERR_INVALID, "null argument");
+    const BackwardHead head{targets, loss, nullptr};
+    return backward_body(p, params, ws, outputs, head, grads, nullptr, stream, bucket_starts, bucket_events, nbuckets);
+}
+
+// d_mix: where the audio's gradient lives after the backward pass -- down conv 0's d(pre-activation) in the launch geometries of
+// its forward pass (the same parts the level-0 weight gradient reads, see the end of backward_body), the head's d(pre-activation)
+// and the difference output's upstream gradient
+static int mix_grad_args(const wun_plan* p, const float* params, float* ws, const float* d_outputs, float* d_mix, MixGradArgs& m) {
+    memset(&m, 0, sizeof(m));
+    const DownShape& d = p->dsh[0];
+    const int Kd = p->cfg.filter_size;
+    auto part = [&](int k, const Buf& z, int Tq, int stride, int off0, int shift, int Tin) {
+        m.part[k].dz = ws + z.off; m.part[k].dzbs = z.bs; m.part[k].dzpitch = z.pitch;
+        m.part[k].Tq = Tq; m.part[k].stride = stride; m.part[k].off0 = off0; m.part[k].shift = shift; m.part[k].Tin = Tin;
+    };
+    const Buf* z1 = nullptr;
+    if (p->same) {
+        part(0, p->dz_skip[0], d.t_conv, 1, 0, (Kd - 1) / 2, d.t_in);
+        m.nparts = 1;
+    } else {
+        part(0, p->dz_dec[0], d.t_dec, 2, 0, 0, d.t_in);
+        m.nparts = 1;
+        if (p->dedup) {
+            // dz_dec[0] holds the even window positions too; the odd ones are compact in dz_odd[0]
+            if (d.n_odd > 0) { part(1, p->dz_odd[0], d.n_odd, 2, d.t_odd0, 0, d.t_in - d.t_odd0); z1 = &p->dz_odd[0]; m.nparts = 2; }
+        } else {
+            // full-rate window conv (bf16 mode): its even positions are computed a second time, both contributions add
+            part(1, p->dz_skip[0], d.tc, 1, d.cs, 0, d.tc + Kd - 1); z1 = &p->dz_skip[0]; m.nparts = 2;
+        }
+    }
+    const Buf& z0 = p->same ? p->dz_skip[0] : p->dz_dec[0];
+    if (z1 && z1->eb != z0.eb) return fail(WUN_ERR_UNSUPPORTED, "d_mix: level-0 gradient parts of different element types");
+    m.dzbf = z0.eb == 2 ? 1 : 0;
+    m.W = params + p->down[0].woff; m.KW = Kd; m.F = p->cfg.num_initial_filters;
+    m.C = p->C; m.B = p->B; m.Tin = p->Tin;
+    const HeadArgs h = head_args(p, params, ws, nullptr, 1);
+    m.dpre = h.dpre; m.dps = h.dps; m.dpbs = h.dpbs; m.dppitch = h.dppitch;
+    m.Wh = params;
+    for (int i = 0; i < p->Sh; ++i) m.hoff[i] = p->head[i].woff;
+    m.Sh = p->Sh; m.Ko = h.Ko; m.padl = h.padl; m.Tfeat = h.Tfeat; m.Tout = h.Tout; m.moff_feat = h.moff_feat;
+    m.dlast = h.difference ? d_outputs + (long long)(p->S - 1) * p->B * p->Tout * p->C : nullptr;
+    m.moff_diff = h.moff_diff;
+    m.dmix = d_mix;
+    if (m.C != 1 && m.C != 2) return fail(WUN_ERR_UNSUPPORTED, "d_mix: only 1 or 2 audio channels are served");
+    if (mix_grad_lds_bytes(m) > 64 * 1024) return fail(WUN_ERR_UNSUPPORTED, "d_mix: down conv 0 / head weights exceed the kernel's 64 KiB of LDS");
+    return WUN_OK;
+}
+
+extern "C" int wun_backward(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                            const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream) {
+    return wun_backward_ex(p, params, mix_btc, ws, outputs, d_outputs, grads, d_mix, stream, nullptr, nullptr, 0);
+}
+
+extern "C" int wun_backward_ex(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                               const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
+                               const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets) {
+    (void)mix_btc;
+    int rc;
+    if ((rc = check_buckets(bucket_starts, bucket_events, nbuckets))) return rc;
+    if (!p || !params || !ws || !outputs || !d_outputs || !grads) return fail(WUN_ERR_INVALID, "null argument");
+    MixGradArgs mix;
+    if (d_mix && (rc = mix_grad_args(p, params, ws, d_outputs, d_mix, mix))) return rc;
+    const BackwardHead head{nullptr, nullptr, d_outputs};
+    return backward_body(p, params, ws, outputs, head, grads, d_mix ? &mix : nullptr, stream, bucket_starts, bucket_events,
+                         nbuckets);
+}
+
+static int backward_body(const wun_plan* p, const float* params, float* ws, const float* outputs, const BackwardHead& head,
+                         float* grads, const MixGradArgs* mix, void* stream, const int64_t* bucket_starts,
+                         void* const* bucket_events, int32_t nbuckets) {
+    BucketSignal sig{bucket_starts, bucket_events, nbuckets, 0};
     if (!p->wt.empty() && !p->dev_wt) return fail(WUN_ERR_HIP, "plan was created without a usable HIP device");
     hipStream_t s = (hipStream_t)stream;
     const int L = p->L, Kd = p->cfg.filter_size, Ku = p->cfg.merge_filter_size, Ko = p->cfg.output_filter_size;
@@ -425,12 +509,17 @@ extern "C" int wun_loss_backward_ex(const wun_plan* p, const float* params, cons
 
     // ---- head: loss, d(pre-activation), d(feature map) ----
     HeadArgs h = head_args(p, params, ws, const_cast<float*>(outputs), 1);
-    h.tgt = targets;
     long long hoff[4] = {0, 0, 0, 0};
     for (int i = 0; i < p->Sh; ++i) hoff[i] = p->head[i].woff;
-    HIP_TRY(launch_head_bwd_off(h, hoff, s));
-    HIP_TRY(launch_loss_finish(h.loss_partial, head_bwd_blocks(h),
-                               1.0f / ((float)p->S * (float)p->B * (float)p->Tout * (float)p->C), loss, s));
+    if (head.d_outputs) {
+        h.dout = head.d_outputs;
+        HIP_TRY(launch_head_grad_off(h, hoff, s));
+    } else {
+        h.tgt = head.targets;
+        HIP_TRY(launch_head_bwd_off(h, hoff, s));
+        HIP_TRY(launch_loss_finish(h.loss_partial, head_bwd_blocks(h),
+                                   1.0f / ((float)p->S * (float)p->B * (float)p->Tout * (float)p->C), head.loss, s));
+    }
     bool head_done = false;
     if (p->head16)
         HIP_TRY(launch_cast_rows_bf16(h.dpre, ws + p->dpre16_off, (long long)p->Sh * p->B * C, p->Tout, h.dppitch, p->dp16_pitch, s));
@@ -673,6 +762,9 @@ extern "C" int wun_loss_backward_ex(const wun_plan* p, const float* params, cons
             }
         }
     }
+    // d_mix: every writer of level 0's d(pre-activation) -- level 1's input gradient, including the early window launches whose
+    // win_ev the caller's stream has waited for -- is complete on `s`.  Not a tuned launch position (no conv_dispatch).
+    if (mix) HIP_TRY(launch_mix_grad(*mix, s));
     if ((rc = flush_wgrads())) return rc;
     if ((rc = stream_dep(p, s3, s))) return rc;
     if ((rc = stream_dep(p, s2, s))) return rc;      // all gradients are complete w.r.t. `stream`

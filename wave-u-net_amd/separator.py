@@ -104,6 +104,7 @@ class UnetAudioSeparator(object):
         self.grads = self.adam_m = self.adam_v = None
         self.global_step = 0
         self._ws = {}
+        self._ws_gen = {}            # (batch, frames) -> forward passes run on that workspace (autograd's stale-workspace guard)
         self._outs = {}
         self._last_mix = None
 
@@ -221,6 +222,7 @@ class UnetAudioSeparator(object):
         _lib.check(self._lib.wun_forward(plan.handle, self.params.data_ptr(), mix.data_ptr(),
                                          ws.data_ptr(), outs.data_ptr(), 1 if training else 0,
                                          self._stream()))
+        self._ws_gen[key] = self._ws_gen.get(key, 0) + 1
         self._active, self._last_mix, self._last_key = plan, mix, key
         self._last_training = bool(training)
         return {name: outs[i] for i, name in enumerate(self.source_names)}
@@ -255,6 +257,48 @@ class UnetAudioSeparator(object):
             self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
             self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb))
         return loss
+
+    def _stacked(self, x, what):
+        """dict source_name -> [B, Tout, C] or [S, B, Tout, C] -> one contiguous float32 [S, B, Tout, C] on the device,
+        checked against the outputs of the last get_output."""
+        dev = self._dev()
+        if isinstance(x, dict):
+            x = torch.stack([torch.as_tensor(x[n]).to(dev, torch.float32) for n in self.source_names])
+        else:
+            x = torch.as_tensor(x).to(dev, torch.float32)
+        x = x.contiguous()
+        outs = self._outs[self._last_key]
+        if tuple(x.shape) != tuple(outs.shape):
+            raise ValueError("%s shape %s != outputs shape %s" % (what, tuple(x.shape), tuple(outs.shape)))
+        return x
+
+    def backward(self, d_outputs, input_grad=False, bucket_starts=None, bucket_events=None):
+        """Backward pass of the last get_output(training=True) from an arbitrary upstream gradient (wun_backward): what
+        tf.gradients gives the reference for any loss built on the outputs.  d_outputs: dL/d outputs, as the targets of
+        loss_and_gradients (dict source_name -> [B, Tout, C] or a stacked [S, B, Tout, C] tensor).  The parameter gradients
+        are written to self.grads (overwritten, as loss_and_gradients does); returns dL/d mix [B, Tin, C] when input_grad,
+        else None.  bucket_starts / bucket_events: as for loss_and_gradients."""
+        if self._active is None or not self._last_training:
+            raise RuntimeError("call get_output(..., training=True) first")
+        dout = self._stacked(d_outputs, "d_outputs")
+        d_mix = torch.empty(tuple(self._last_mix.shape), dtype=torch.float32, device=self._dev()) if input_grad else None
+        self._run_backward(self._ws[self._last_key], self._outs[self._last_key], dout, self.grads, d_mix,
+                           bucket_starts, bucket_events)
+        return d_mix
+
+    def _run_backward(self, ws, outs, dout, grads, d_mix, bucket_starts=None, bucket_events=None):
+        nb = len(bucket_starts) if bucket_starts else 0
+        starts = (C.c_int64 * max(nb, 1))(*([int(x) for x in bucket_starts] if nb else [0]))
+        events = (C.c_void_p * max(nb, 1))(*([int(e.cuda_event) for e in bucket_events] if nb else [0]))
+        _lib.check(self._lib.wun_backward_ex(
+            self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
+            grads.data_ptr(), d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb))
+
+    def module(self):
+        """This separator as a torch.nn.Module (wave_u_net_amd.autograd.WaveUNet): get_output under torch.autograd, the
+        parameter arena as one nn.Parameter sharing storage with self.params."""
+        from .autograd import WaveUNet
+        return WaveUNet(self)
 
     def tune(self, input, targets):
         """Autotune the kernels of this (batch, length) plan on real buffers: one forward +
