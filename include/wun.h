@@ -227,6 +227,31 @@ int wun_backward_ex(const wun_plan* plan, const float* params, const float* mix_
                     const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
                     const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets);
 
+/* Backward pass for a subset of the variables (frozen layers, input-only gradients).  The arguments of wun_backward_ex /
+ * wun_loss_backward_ex plus:
+ *   select   : host, nselect bytes; select[k] != 0 selects tensor k (wun_plan_tensor order).  NULL = every tensor: the call
+ *              is then exactly wun_backward_ex / wun_loss_backward_ex (nselect 0 or num_tensors).
+ *   nselect  : num_tensors when select is given.
+ * The gradient floats of a selected tensor are bit-identical to the full call's on the same inputs; the floats of the other
+ * tensors in `grads` are NOT written.  d_mix and loss, when requested, are bit-identical to the full call's.  Layers in forward
+ * order -- mix, down 0 .. L-1, bottleneck, then interp_j and up j for each j, the head; e = the earliest selected layer, or the
+ * mix when d_mix is requested: no launch before e runs, and a weight-gradient launch runs only for a selected layer
+ * (DESIGN.md 5.5).  Tuned launch positions, accumulation orders and the bucket events are those of the full call (every
+ * event is recorded exactly once; a bucket without a selected tensor when the call reaches it).
+ * A conv's kernel and bias are selected together, and the output layer's convs (every source) together: else
+ * WUN_ERR_UNSUPPORTED.  interp_<j> is selected on its own.  wun_backward_select: grads may be NULL only when no tensor is
+ * selected (input-only gradient: d_mix required).  No tensor selected and no d_mix, a bad nselect, or a NULL grads with a
+ * selection: WUN_ERR_INVALID.  Every argument check runs before any GPU work.  Both compute modes; same workspace. */
+int wun_backward_select(const wun_plan* plan, const float* params, const float* mix_btc, float* workspace,
+                        const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
+                        const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
+                        const uint8_t* select, int64_t nselect);
+int wun_loss_backward_select(const wun_plan* plan, const float* params, const float* mix_btc,
+                             float* workspace, const float* outputs, const float* targets,
+                             float* grads, float* loss, void* stream,
+                             const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
+                             const uint8_t* select, int64_t nselect);
+
 /* Optional autotuning pass (no reference counterpart): runs one forward + loss/backward on the
  * given buffers while timing, for every conv / weight-gradient launch of the step, the candidate
  * tile shapes and split factors, and caches the fastest per launch in the plan.  The contents of
@@ -253,6 +278,14 @@ int wun_plan_tune_import(const wun_plan* plan, const char* text);
 int wun_adam_step(const wun_plan* plan, float* params, const float* grads, float* m, float* v,
                   int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
                   void* stream);
+
+/* wun_adam_step on the selected tensors only (TF's minimize(loss, var_list=...)): params, m and v of a selected tensor are
+ * bit-equal to what wun_adam_step writes; every other float of the three arenas is left as it is.  select / nselect as for
+ * wun_backward_select, except that any subset is accepted (kernel and bias need not agree; nothing selected = no launch).
+ * NULL select = wun_adam_step.  Same lr_t.  No host synchronisation, no allocation. */
+int wun_adam_step_select(const wun_plan* plan, float* params, const float* grads, float* m, float* v,
+                         int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                         void* stream, const uint8_t* select, int64_t nselect);
 
 /* ---- single operators (used by the parity tests and for per-kernel profiling) ---------- */
 

@@ -11,6 +11,16 @@ The separator keeps ONE workspace per (batch, frames): the activations the backw
 the same shape before the first one's backward overwrites them, so that backward raises RuntimeError instead of computing
 wrong gradients (generation counter per workspace).  An in-place change of the arena between forward and backward trips
 torch's own version check (the arena is saved for backward).  Second-order gradients are not supported (once_differentiable).
+
+Frozen variables (fine-tuning part of the network) and input-only gradients (a frozen separator as a front end or a loss term):
+
+    net.freeze([n for n in net.variable_names() if ...])   # e.g. the encoder; unfreeze(names), frozen()
+    net.arena.requires_grad_(False)                         # and a mix that requires grad: only d loss / d mix is computed
+
+The backward pass then runs wun_backward_select: launches no wanted gradient needs are skipped, and the frozen ranges of
+arena.grad are 0, as the padding floats are.  A torch optimizer still steps every float of the one arena Parameter: with
+weight decay (AdamW, Adam(weight_decay=...)) or momentum left over from earlier steps it moves frozen variables too.  The
+separator's own adam_step(variables=...) (wun_adam_step_select) leaves them bit-unchanged.
 """
 import numpy as np
 import torch
@@ -43,9 +53,9 @@ class GetOutput(torch.autograd.Function):
     """outputs [S, B, Tout, C] = get_output(mix [B, Tin, C], training = True) with the parameters in `arena`."""
 
     @staticmethod
-    def forward(ctx, mix, arena, sep):
+    def forward(ctx, mix, arena, sep, mask=None):
         outs, key, gen = _forward(sep, arena, mix, True)
-        ctx.sep, ctx.key, ctx.gen, ctx.mix_shape = sep, key, gen, tuple(mix.shape)
+        ctx.sep, ctx.key, ctx.gen, ctx.mix_shape, ctx.mask = sep, key, gen, tuple(mix.shape), mask
         ctx.save_for_backward(arena, outs)
         return outs
 
@@ -57,14 +67,26 @@ class GetOutput(torch.autograd.Function):
         if sep._ws_gen.get(key) != ctx.gen:
             raise RuntimeError("wave_u_net_amd: another forward pass of shape %s ran on the shared workspace after this "
                                "one; run backward before the next forward of the same shape" % (key,))
-        grads = torch.zeros_like(arena)          # padding floats stay 0 for torch optimizers
+        want_arena = ctx.needs_input_grad[1]
+        # padding floats (and frozen ranges) stay 0 for torch optimizers
+        grads = torch.zeros_like(arena) if want_arena else None
         d_mix = torch.empty(ctx.mix_shape, dtype=torch.float32, device=arena.device) if ctx.needs_input_grad[0] else None
         dout = d_outputs.to(torch.float32).contiguous()
         plan = sep._plans[key]
-        _lib.check(sep._lib.wun_backward(plan.handle, arena.data_ptr(), None, sep._ws[key].data_ptr(), outs.data_ptr(),
-                                         dout.data_ptr(), grads.data_ptr(),
-                                         d_mix.data_ptr() if d_mix is not None else None, sep._stream()))
-        return d_mix, grads, None
+        mask = ctx.mask
+        if not want_arena:
+            mask = np.zeros(len(plan.tensors), dtype=np.uint8)          # input-only gradient
+        if mask is None:
+            _lib.check(sep._lib.wun_backward(plan.handle, arena.data_ptr(), None, sep._ws[key].data_ptr(), outs.data_ptr(),
+                                             dout.data_ptr(), grads.data_ptr(),
+                                             d_mix.data_ptr() if d_mix is not None else None, sep._stream()))
+        elif mask.any() or d_mix is not None:
+            sel, n = sep._mask_arg(mask)
+            _lib.check(sep._lib.wun_backward_select(
+                plan.handle, arena.data_ptr(), None, sep._ws[key].data_ptr(), outs.data_ptr(), dout.data_ptr(),
+                grads.data_ptr() if mask.any() else None, d_mix.data_ptr() if d_mix is not None else None, sep._stream(),
+                None, None, 0, sel, n))
+        return d_mix, grads, None, None
 
 
 class WaveUNet(torch.nn.Module):
@@ -80,6 +102,32 @@ class WaveUNet(torch.nn.Module):
         self.arena = torch.nn.Parameter(sep.params, requires_grad=True)    # shares storage with sep.params
         assert self.arena.data_ptr() == sep.params.data_ptr()
         self.tensors = list(plan.tensors)
+        self._frozen = set()
+
+    def variable_names(self):
+        """The TF variable names, in arena order."""
+        return [name for name, _, _ in self.tensors]
+
+    def _names(self, names):
+        names = [names] if isinstance(names, str) else list(names)
+        known = set(self.variable_names())
+        for n in names:
+            if n not in known:
+                raise KeyError(n)
+        return names
+
+    def freeze(self, names):
+        """Stop computing the gradients of these TF variables (their ranges of arena.grad are 0).  A conv's kernel and bias
+        must be frozen together, and the output layer's convs together: else the backward pass raises NotImplementedError."""
+        self._frozen.update(self._names(names))
+
+    def unfreeze(self, names):
+        for n in self._names(names):
+            self._frozen.discard(n)
+
+    def frozen(self):
+        """The frozen TF variable names, in arena order."""
+        return [n for n in self.variable_names() if n in self._frozen]
 
     def forward(self, mix):
         dev = self.arena.device
@@ -89,7 +137,10 @@ class WaveUNet(torch.nn.Module):
         if not self.training:
             with torch.no_grad():
                 return _forward(self.sep, self.arena, mix, False)[0]
-        return GetOutput.apply(mix, self.arena, self.sep)
+        mask = None
+        if self._frozen:
+            mask = np.array([0 if n in self._frozen else 1 for n in self.variable_names()], dtype=np.uint8)
+        return GetOutput.apply(mix, self.arena, self.sep, mask)
 
     def named_variables(self):
         """tf_name -> view of the arena (the TF variables, UnetAudioSeparator.py)."""

@@ -950,6 +950,38 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n
     return hipGetLastError();
 }
 
+// adam_kernel over the selected runs only: thread-strided over the concatenated runs, the run found by a scan of the (at most
+// WUN_ADAM_RANGES) prefix sums; every float gets adam_kernel's expressions, so a selected float is bit-equal to the full step's
+__global__ void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                   float* __restrict__ v, AdamRanges r, float lr_t, float b1, float b2,
+                                   float eps, float gscale) {
+    const long long total = r.cum[r.n];
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (long long)gridDim.x * blockDim.x) {
+        int k = 0;
+        while (k + 1 < r.n && t >= r.cum[k + 1]) ++k;
+        const long long i = r.off[k] + (t - r.cum[k]);
+        const float gi = g[i] * gscale;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    }
+}
+
+hipError_t launch_adam_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t,
+                              float b1, float b2, float eps, float gscale, hipStream_t s) {
+    const long long n = r.n > 0 ? r.cum[r.n] : 0;
+    if (n <= 0) return hipSuccess;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    ProfScope ps("adam_ranges_kernel", 0.0, s, "", 28.0 * (double)n);
+    hipLaunchKernelGGL(adam_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2,
+                       eps, gscale);
+    return hipGetLastError();
+}
+
 __global__ void fill_kernel(float* p, long long n, float val) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) p[i] = val;

@@ -332,6 +332,12 @@ hipError_t launch_make_wt(const float* params, float* ws, const WtDesc* dev_desc
                           int max_elems, hipStream_t s);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr_t,
                        float b1, float b2, float eps, float gscale, hipStream_t s);
+// TF-Adam over selected runs of the arena (wun_adam_step_select): run k = floats [off[k], off[k] + cum[k+1] - cum[k]),
+// passed by value; the per-element arithmetic of adam_kernel
+#define WUN_ADAM_RANGES 32
+struct AdamRanges { long long off[WUN_ADAM_RANGES]; long long cum[WUN_ADAM_RANGES + 1]; int n; };
+hipError_t launch_adam_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t,
+                              float b1, float b2, float eps, float gscale, hipStream_t s);
 hipError_t launch_fill(float* p, long long n, float val, hipStream_t s);
 hipError_t launch_mfma_probe(const float* a, const float* b, float* d, hipStream_t s);
 void prof_begin(bool detail);                 // detail: per-launch list in the JSON (WUN_PROFILE_DETAIL)

@@ -227,20 +227,88 @@ static int check_buckets(const int64_t* bucket_starts, void* const* bucket_event
 // (wun_backward: head_grad_kernel from d_outputs).  Everything after the head's d(pre-activation) is one body.
 struct BackwardHead { const float* targets; float* loss; const float* d_outputs; };
 
+// Which parts of the backward pass a call runs (wun_*_select).  Layers in the order the forward pass runs them:
+// the mix (0), down level i (1 + i), the bottleneck (L + 1), interp_j (L + 2 + 2j), up level j (L + 3 + 2j), the head (3L + 2).
+// wgrad[k]: layer k's weight-gradient launches run.  first: the earliest layer whose d(pre-activation) is needed -- the
+// input-gradient launches of layer k (which produce the d(pre-activation) of the layers before it) run iff k > first.
+// The full pass: every layer, first = the mix with d_mix, else down level 0 (whose input gradient is d_mix only).
+struct BackwardSelect {
+    std::vector<char> wgrad;
+    int first = 0;
+    int down(int i) const { return 1 + i; }
+    int bott(int L) const { return L + 1; }
+    int interp(int L, int j) const { return L + 2 + 2 * j; }
+    int up(int L, int j) const { return L + 3 + 2 * j; }
+    int head(int L) const { return 3 * L + 2; }
+    bool wg(int k) const { return wgrad[(size_t)k] != 0; }
+    bool ig(int k) const { return k > first; }
+};
+
+// select[k] != 0: tensor k (wun_plan_tensor order) is wanted; NULL = all.  A conv's kernel and bias come from one launch and
+// must agree; so must the output layer's convs (one launch serves every source).  Host work only: fails before any GPU work.
+static int parse_select(const wun_plan* p, const uint8_t* select, int64_t nselect, bool want_mix, BackwardSelect& sel,
+                        bool& any) {
+    const int L = p->L;
+    const int64_t nt = (int64_t)p->tensors.size();
+    sel.wgrad.assign((size_t)(3 * L + 3), 0);
+    if (!select && nselect != 0 && nselect != nt) return fail(WUN_ERR_INVALID, "nselect must be 0 or num_tensors when select is NULL");
+    if (select && nselect != nt) return fail(WUN_ERR_INVALID, "nselect must equal num_tensors");
+    int64_t k = 0;
+    int rc = WUN_OK;
+    auto take = [&]() { return select ? select[k++] != 0 : (++k, true); };
+    auto conv = [&]() {
+        const bool w = take(), b = take();
+        if (w != b && rc == WUN_OK)
+            rc = fail(WUN_ERR_UNSUPPORTED, std::string("select: ") + p->tensors[(size_t)k - 2].name +
+                                           " and its bias must be selected together (one launch computes both)");
+        return w;
+    };
+    for (int i = 0; i < L; ++i) sel.wgrad[(size_t)sel.down(i)] = conv();
+    sel.wgrad[(size_t)sel.bott(L)] = conv();
+    for (int j = 0; j < L; ++j) {
+        if (p->interp[(size_t)j] >= 0) sel.wgrad[(size_t)sel.interp(L, j)] = take();
+        sel.wgrad[(size_t)sel.up(L, j)] = conv();
+    }
+    int nhead = 0;
+    for (int s = 0; s < p->Sh; ++s) nhead += conv() ? 1 : 0;
+    if (rc) return rc;
+    if (nhead != 0 && nhead != p->Sh)
+        return fail(WUN_ERR_UNSUPPORTED, "select: the output layer's convs (every source) must be selected together (one launch computes them)");
+    sel.wgrad[(size_t)sel.head(L)] = nhead > 0;
+    sel.first = -1;
+    for (int l = 0; l <= sel.head(L) && sel.first < 0; ++l)
+        if (sel.wgrad[(size_t)l]) sel.first = l;
+    any = sel.first >= 0;
+    if (want_mix) sel.first = 0;
+    if (sel.first < 0) return fail(WUN_ERR_INVALID, "nothing to compute: no tensor selected and no d_mix");
+    return WUN_OK;
+}
+
 static int backward_body(const wun_plan* p, const float* params, float* ws, const float* outputs, const BackwardHead& head,
                          float* grads, const MixGradArgs* mix, void* stream, const int64_t* bucket_starts,
-                         void* const* bucket_events, int32_t nbuckets);
+                         void* const* bucket_events, int32_t nbuckets, const BackwardSelect& sel);
 
 extern "C" int wun_loss_backward_ex(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
                                     const float* outputs, const float* targets, float* grads, float* loss,
                                     void* stream, const int64_t* bucket_starts, void* const* bucket_events,
                                     int32_t nbuckets) {
+    return wun_loss_backward_select(p, params, mix_btc, ws, outputs, targets, grads, loss, stream, bucket_starts, bucket_events,
+                                    nbuckets, nullptr, 0);
+}
+
+extern "C" int wun_loss_backward_select(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                                        const float* outputs, const float* targets, float* grads, float* loss,
+                                        void* stream, const int64_t* bucket_starts, void* const* bucket_events,
+                                        int32_t nbuckets, const uint8_t* select, int64_t nselect) {
     (void)mix_btc;
     int rc;
     if ((rc = check_buckets(bucket_starts, bucket_events, nbuckets))) return rc;
     if (!p || !params || !ws || !outputs || !targets || !grads || !loss) return fail(WUN_ERR_INVALID, "null argument");
+    BackwardSelect sel;
+    bool any = false;
+    if ((rc = parse_select(p, select, nselect, false, sel, any))) return rc;
     const BackwardHead head{targets, loss, nullptr};
-    return backward_body(p, params, ws, outputs, head, grads, nullptr, stream, bucket_starts, bucket_events, nbuckets);
+    return backward_body(p, params, ws, outputs, head, grads, nullptr, stream, bucket_starts, bucket_events, nbuckets, sel);
 }
 
 // d_mix: where the audio's gradient lives after the backward pass -- down conv 0's d(pre-activation) in the launch geometries of
@@ -295,20 +363,35 @@ extern "C" int wun_backward(const wun_plan* p, const float* params, const float*
 extern "C" int wun_backward_ex(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
                                const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
                                const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets) {
-    (void)mix_btc;
     int rc;
     if ((rc = check_buckets(bucket_starts, bucket_events, nbuckets))) return rc;
     if (!p || !params || !ws || !outputs || !d_outputs || !grads) return fail(WUN_ERR_INVALID, "null argument");
+    return wun_backward_select(p, params, mix_btc, ws, outputs, d_outputs, grads, d_mix, stream, bucket_starts, bucket_events,
+                               nbuckets, nullptr, 0);
+}
+
+extern "C" int wun_backward_select(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                                   const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
+                                   const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
+                                   const uint8_t* select, int64_t nselect) {
+    (void)mix_btc;
+    int rc;
+    if ((rc = check_buckets(bucket_starts, bucket_events, nbuckets))) return rc;
+    if (!p || !params || !ws || !outputs || !d_outputs) return fail(WUN_ERR_INVALID, "null argument");
+    BackwardSelect sel;
+    bool any = false;
+    if ((rc = parse_select(p, select, nselect, d_mix != nullptr, sel, any))) return rc;
+    if (any && !grads) return fail(WUN_ERR_INVALID, "null argument: grads (may be NULL only when no tensor is selected)");
     MixGradArgs mix;
     if (d_mix && (rc = mix_grad_args(p, params, ws, d_outputs, d_mix, mix))) return rc;
     const BackwardHead head{nullptr, nullptr, d_outputs};
     return backward_body(p, params, ws, outputs, head, grads, d_mix ? &mix : nullptr, stream, bucket_starts, bucket_events,
-                         nbuckets);
+                         nbuckets, sel);
 }
 
 static int backward_body(const wun_plan* p, const float* params, float* ws, const float* outputs, const BackwardHead& head,
                          float* grads, const MixGradArgs* mix, void* stream, const int64_t* bucket_starts,
-                         void* const* bucket_events, int32_t nbuckets) {
+                         void* const* bucket_events, int32_t nbuckets, const BackwardSelect& sel) {
     BucketSignal sig{bucket_starts, bucket_events, nbuckets, 0};
     if (!p->wt.empty() && !p->dev_wt) return fail(WUN_ERR_HIP, "plan was created without a usable HIP device");
     hipStream_t s = (hipStream_t)stream;
@@ -325,6 +408,12 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
     hipStream_t s3 = (p->side2 && s2 != s) ? p->side2 : s2;
     int wg_rr = 0;
     auto wstream = [&]() { return (wg_rr++ & 1) ? s3 : s2; };
+    // A launch a selection leaves out (live == false) still takes its launch position, so that every launch that does run
+    // gets the tuned choice of the full pass; a left-out weight gradient also takes its turn of the side streams
+    auto dispatch = [&](bool live, const ConvArgs& a, float* part, long long cap, hipStream_t st) -> hipError_t {
+        if (!live) { ++p->ci; return hipSuccess; }
+        return conv_dispatch(p, a, part, cap, st);
+    };
     // bucket events are recorded on s2 once it has also seen everything queued on s3
     auto ready2 = [&](long long floor) -> int {
         if (s3 != s2 && sig.next < sig.n && sig.starts[sig.next] >= floor) {
@@ -337,7 +426,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
     // streams wait on it.  (Batching several deep levels behind one event -- every event is a barrier packet that holds
     // the dependent chain for ~7 us -- was measured in round 2: 41 -> 26 stalls per step, but the delayed weight gradients
     // lengthen the tail after the last input gradient by more: 9.12 ms per step with one layer per event, 9.19 - 9.23 with 2 - 5.)
-    struct PendingWgrad { WgradArgs w[2]; int n; const ConvLayer* cl; };
+    struct PendingWgrad { WgradArgs w[2]; int n; const ConvLayer* cl; bool live; };
     std::vector<PendingWgrad> pend;
     // Early skip-window input gradients (context mode).  The input gradient of down level i is the transposed stride-2
     // conv of dz_dec[i] over the whole row PLUS the full-rate conv of dz_skip[i] over the crop window.  dz_skip[i] is
@@ -389,7 +478,8 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
         for (auto& e : p->win_ev)
             if (!e) HIP_TRY(hipEventCreateWithFlags(&e, event_flags(p)));
     }
-    std::vector<int> pend_win;
+    struct PendingWin { int i; bool live; };
+    std::vector<PendingWin> pend_win;
     std::vector<UpsampleBwdArgs> pend_interp;
     const long long cpart_half = p->conv_part_floats / 2, cpart_q = p->conv_part_floats / 4;
     auto window_dgrad_args = [&](int i) {
@@ -407,7 +497,8 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
     // dz_odd[i] into [t_odd0, t_odd0 + 2 (n_odd - 1) + Kd) (odd = true).  Both output phases fused in one launch (a lane owns 8
     // consecutive outputs) when the launch fills the chip, else one phase at a time (those launches can use split-K).
     // accum: add to what the row holds inside [acc_lo, acc_lo + acc_len) (acc_len == 0: everywhere), store elsewhere.
-    auto tconv2 = [&](int i, bool odd, bool accum, int acc_lo, unsigned acc_len, hipStream_t st, float* part, long long cap) -> int {
+    auto tconv2 = [&](bool live, int i, bool odd, bool accum, int acc_lo, unsigned acc_len, hipStream_t st, float* part,
+                      long long cap) -> int {
         const DownShape& d = p->dsh[i];
         const ConvLayer& cl = p->down[i];
         const Buf& src = odd ? p->dz_odd[i] : p->dz_dec[i];
@@ -441,7 +532,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
         const int odd_min = p->sw.odd_fuse_min;
         const int tmin = odd ? std::min(256, odd_min) : 256, wmin = odd ? odd_min : 256;
         if ((d.cin & 3) == 0 && (p->bf16 || (f.Tout >= tmin && conv_natural_wgs_phase2(f) >= wmin))) {
-            HIP_TRY(conv_dispatch(p, f, part, cap, st));
+            HIP_TRY(dispatch(live, f, part, cap, st));
             return WUN_OK;
         }
         for (int ph = 0; ph < 2; ++ph) {
@@ -452,13 +543,16 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             set_dst0(a, ws, p->dz_dec[i - 1], out_off + ph, &p->dec[i - 1]);
             a.ostride = 2;
             if (accum) { a.flags |= F_ACCUM; a.acc_lo = acc_lo; a.acc_len = acc_len; }
-            if (a.Tout > 0) HIP_TRY(conv_dispatch(p, a, part, cap, st));
+            if (a.Tout > 0) HIP_TRY(dispatch(live, a, part, cap, st));
         }
         return WUN_OK;
     };
     auto flush_wgrads = [&]() -> int {
         if (pend.empty() && pend_win.empty() && pend_interp.empty()) return WUN_OK;
-        if (s2 != s) {
+        bool work = !pend_interp.empty();
+        for (auto& q : pend) work = work || q.live;
+        for (auto& w : pend_win) work = work || w.live;
+        if (s2 != s && work) {
             hipEvent_t e = p->events[p->ev_next++ % p->events.size()];
             HIP_TRY(hipEventRecord(e, s));
             HIP_TRY(hipStreamWaitEvent(s2, e, 0));
@@ -467,32 +561,36 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
         for (auto& ub : pend_interp) HIP_TRY(launch_interp_grad(ub, wstream()));
         pend_interp.clear();
         for (auto& q : pend) {
-            int rcq = run_wgrad(p, q.w, q.n, *q.cl, ws, grads, s, wstream(), false);
+            int rcq = WUN_OK;
+            if (q.live) rcq = run_wgrad(p, q.w, q.n, *q.cl, ws, grads, s, wstream(), false);
+            else { wstream(); ++p->wi; }
             if (rcq) return rcq;
-            if ((rcq = ready2(q.cl->woff))) return rcq;
+            if ((rcq = ready2(q.cl->woff))) return rcq;        // (a bucket without a selected tensor: signalled here)
         }
         pend.clear();
-        for (int i : pend_win) {
+        for (const PendingWin& pw : pend_win) {
+            const int i = pw.i;
             // own quarter of the split-K scratch per side stream (the chain on `s` uses the first half)
             hipStream_t sw = wstream();
             float* part = ws + p->conv_part_off + cpart_half + ((sw == s3 && s3 != s2) ? cpart_q : 0);
             if (p->dedup) {
                 int elo, elen;
                 e_range(i - 1, elo, elen);
-                int rcw = tconv2(i, true, elen > 0, elo, (unsigned)elen, sw, sw == s ? ws + p->conv_part_off : part, sw == s ? cpart_half : cpart_q);
+                int rcw = tconv2(pw.live, i, true, elen > 0, elo, (unsigned)elen, sw, sw == s ? ws + p->conv_part_off : part,
+                                 sw == s ? cpart_half : cpart_q);
                 if (rcw) return rcw;
             } else {
-                HIP_TRY(conv_dispatch(p, window_dgrad_args(i), sw == s ? ws + p->conv_part_off : part, sw == s ? cpart_half : cpart_q, sw));
+                HIP_TRY(dispatch(pw.live, window_dgrad_args(i), sw == s ? ws + p->conv_part_off : part, sw == s ? cpart_half : cpart_q, sw));
             }
-            if (sw != s) HIP_TRY(hipEventRecord(p->win_ev[(size_t)i], sw));
+            if (sw != s && pw.live) HIP_TRY(hipEventRecord(p->win_ev[(size_t)i], sw));
         }
         pend_win.clear();
         return WUN_OK;
     };
-    auto submit_wgrad = [&](const WgradArgs* w, int n, const ConvLayer& cl) -> int {
+    auto submit_wgrad = [&](const WgradArgs* w, int n, const ConvLayer& cl, bool live) -> int {
         PendingWgrad q;
         for (int k = 0; k < n; ++k) q.w[k] = w[k];
-        q.n = n; q.cl = &cl;
+        q.n = n; q.cl = &cl; q.live = live;
         pend.push_back(q);
         return flush_wgrads();
     };
@@ -521,7 +619,8 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                                    1.0f / ((float)p->S * (float)p->B * (float)p->Tout * (float)p->C), head.loss, s));
     }
     bool head_done = false;
-    if (p->head16)
+    const bool wg_head = sel.wg(sel.head(L));
+    if (p->head16 && wg_head)
         HIP_TRY(launch_cast_rows_bf16(h.dpre, ws + p->dpre16_off, (long long)p->Sh * p->B * C, p->Tout, h.dppitch, p->dp16_pitch, s));
     if (p->Sh > 0 && !p->head16) {
         // every source's output conv in ONE direct-reduction launch (OutputLayer.py:8,15): dz rows = (source, channel)
@@ -536,7 +635,8 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
         if (narrow_wgrad_supported(nw) && (p->bf16 || !p->sw.no_narrow)) {
             long long woff[4] = {0, 0, 0, 0}, boff[4] = {0, 0, 0, 0};
             for (int sh = 0; sh < p->Sh; ++sh) { woff[sh] = p->head[sh].woff; boff[sh] = p->head[sh].boff; }
-            if ((rc = run_narrow_wgrad(p, &nw, 1, woff, boff, ws, grads, s, wstream()))) return rc;
+            hipStream_t sw = wstream();
+            if (wg_head && (rc = run_narrow_wgrad(p, &nw, 1, woff, boff, ws, grads, s, sw))) return rc;
             head_done = true;
         } else if (p->bf16) {
             // bf16 mode: the head's inputs are the fp32 audio and the bf16 feature map -- only the narrow kernels read
@@ -548,12 +648,14 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                 NarrowWgradArgs one = nw;
                 one.dz = h.dpre + (long long)sh * h.dps;
                 const long long woff[4] = {p->head[sh].woff, 0, 0, 0}, boff[4] = {p->head[sh].boff, 0, 0, 0};
-                if ((rc = run_narrow_wgrad(p, &one, 1, woff, boff, ws, grads, s, wstream()))) return rc;
+                hipStream_t sw = wstream();
+                if (wg_head && (rc = run_narrow_wgrad(p, &one, 1, woff, boff, ws, grads, s, sw))) return rc;
             }
             head_done = true;
         }
     }
     for (int sh = 0; sh < p->Sh && !head_done; ++sh) {
+        if (!wg_head) { wstream(); ++p->wi; continue; }
         WgradArgs w = wgrad_base(p);
         wset_src0(w, ws, p->head16 ? p->mix16 : p->mix_ncw, p->in_crop_start, C);
         wset_src1(w, ws, p->upo[L - 1], 0, F);
@@ -580,7 +682,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             wset_dz(w, ws + p->dz_upo[j].off, p->dz_upo[j].bs, p->dz_upo[j].pitch, u.cout, u.t_conv);
             // (interp_j, written on `s` by the previous level's upsample_bwd, sits above up[j] in
             // the arena; the flush makes the side streams wait for everything issued on `s` so far)
-            if ((rc = submit_wgrad(&w, 1, p->up[j]))) return rc;
+            if ((rc = submit_wgrad(&w, 1, p->up[j], sel.wg(sel.up(L, j))))) return rc;
         }
         {
             ConvArgs a = conv_base(p);
@@ -609,9 +711,12 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                 a.ubw_dz = ws + dzprev.off; a.ubw_x = ws + prev.off; a.ubw_bs = prev.bs; a.ubw_pitch = prev.pitch;
                 a.ubw_n = u.t_cur;
             }
-            HIP_TRY(conv_dispatch(p, a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
+            const bool live = sel.ig(sel.up(L, j));
+            HIP_TRY(dispatch(live, a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
             adj_done = a.ubw_dz != nullptr && conv_last_fused_ups() != 0;
-            if (level_early(i)) pend_win.push_back(i);         // dz_skip[i] is final: its window input gradient can start
+            // dz_skip[i] is final: its window input gradient can start
+            if (level_early(i)) pend_win.push_back(PendingWin{i, sel.ig(sel.down(i))});
+            if (!live) continue;                                // (interp_j and everything before it are not needed)
         }
         if (!adj_done) {
             const Buf& prev = (j == 0) ? p->bott_out : p->upo[j - 1];
@@ -622,10 +727,11 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             ub.x = ws + prev.off; ub.xbs = prev.bs; ub.xpitch = prev.pitch; ub.n = u.t_cur;
             ub.dz = ws + dzprev.off;
             ub.w = p->interp[j] >= 0 ? params + p->interp[j] : nullptr;
-            ub.dw = p->interp[j] >= 0 ? grads + p->interp[j] : nullptr;
-            ub.dw_partial = (p->interp[j] >= 0 && !p->interp_partial_off.empty()) ? ws + p->interp_partial_off[(size_t)j] : nullptr;
+            const bool wg_interp = p->interp[j] >= 0 && sel.wg(sel.interp(L, j));
+            ub.dw = wg_interp ? grads + p->interp[j] : nullptr;
+            ub.dw_partial = (wg_interp && !p->interp_partial_off.empty()) ? ws + p->interp_partial_off[(size_t)j] : nullptr;
             ub.C = u.c_cur; ub.B = p->B; ub.context = p->cfg.context; ub.bf = p->bf16 ? 1 : 0;
-            HIP_TRY(launch_upsample_bwd(ub, s));
+            if (sel.ig(sel.interp(L, j))) HIP_TRY(launch_upsample_bwd(ub, s));
             // the interpolation weights' gradient is nobody's input on the chain: with the next flush, on a side stream
             // (interp_<j> lies just below up[j]'s kernel in the arena: complete before the next layer's bucket signal)
             if (ub.dw != nullptr) pend_interp.push_back(ub);
@@ -638,7 +744,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
         wset_src0(w, ws, p->dec[L - 1], 0, p->bott.Cin);
         w.Tin = p->t_b_in; w.shift = padD; w.KW = Kd;
         wset_dz(w, ws + p->dz_bott.off, p->dz_bott.bs, p->dz_bott.pitch, p->c_b, p->t_b);
-        if ((rc = submit_wgrad(&w, 1, p->bott))) return rc;
+        if ((rc = submit_wgrad(&w, 1, p->bott, sel.wg(sel.bott(L))))) return rc;
         ConvArgs a = conv_base(p);
         set_src0(a, ws, p->dz_bott, 0, p->c_b);
         a.Tin = p->t_b; a.shift = Kd - 1 - padD; a.W = ws + p->bott.wt_full; a.KW = Kd;
@@ -655,7 +761,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                 a.flags = F_ACCUM; a.acc_lo = elo; a.acc_len = (unsigned)elen;
             }
         }
-        HIP_TRY(conv_dispatch(p, a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
+        HIP_TRY(dispatch(sel.ig(sel.bott(L)), a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
     }
 
     // ---- down path ----
@@ -694,17 +800,20 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             // (bf16 mode: the narrow kernels are the only ones that read fp32 audio against bf16 gradients)
             if (p->bf16 && !narrow) return fail(WUN_ERR_UNSUPPORTED, "bf16 mode: audio-input conv shape not served by the narrow weight-gradient kernels");
         }
+        const bool wg_down = sel.wg(sel.down(i)), ig_down = sel.ig(sel.down(i));
         if (narrow) {
             if ((rc = flush_wgrads())) return rc;
             const long long woff[4] = {cl.woff, 0, 0, 0}, boff[4] = {cl.boff, 0, 0, 0};
-            if ((rc = run_narrow_wgrad(p, nw, (same || (p->dedup && d.n_odd == 0)) ? 1 : 2, woff, boff, ws, grads, s, wstream()))) return rc;
+            hipStream_t sw = wstream();
+            if (wg_down && (rc = run_narrow_wgrad(p, nw, (same || (p->dedup && d.n_odd == 0)) ? 1 : 2, woff, boff, ws, grads, s, sw)))
+                return rc;
             if ((rc = ready2(cl.woff))) return rc;
         } else if (same) {
             WgradArgs w = wgrad_base(p);
             wset_src0(w, ws, x, 0, d.cin);
             w.Tin = d.t_in; w.shift = padD; w.KW = Kd;
             wset_dz(w, ws + p->dz_skip[i].off, p->dz_skip[i].bs, p->dz_skip[i].pitch, d.cout, d.t_conv);
-            if ((rc = submit_wgrad(&w, 1, cl))) return rc;
+            if ((rc = submit_wgrad(&w, 1, cl, wg_down))) return rc;
             if (i > 0) {
                 ConvArgs a = conv_base(p);
                 set_src0(a, ws, p->dz_skip[i], 0, d.cout);
@@ -712,7 +821,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                 a.N = a.N0 = d.cin; a.Tout = d.t_in;
                 set_dst0(a, ws, p->dz_skip[i - 1], 0, &p->skip[i - 1]);
                 a.ostride = 2; a.flags = F_ACCUM;
-                HIP_TRY(conv_dispatch(p, a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
+                HIP_TRY(dispatch(ig_down, a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
             }
         } else {
             WgradArgs w[2];
@@ -733,7 +842,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                 w[1].Tin = d.tc + Kd - 1; w[1].shift = 0; w[1].KW = Kd;
                 wset_dz(w[1], ws + p->dz_skip[i].off, p->dz_skip[i].bs, p->dz_skip[i].pitch, d.cout, d.tc);
             }
-            if ((rc = submit_wgrad(w, nparts, cl))) return rc;
+            if ((rc = submit_wgrad(w, nparts, cl, wg_down))) return rc;
             if (i > 0) {
                 const bool win_early = level_early(i) && !p->win_ev.empty();
                 int alo = 0, alen = 0;
@@ -741,22 +850,25 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                 if (win_early) {
                     // the window part is already in dz_dec[i-1] (side stream): wait for it, add inside the window (a
                     // launch still sitting in the queue -- win_ev[i] would be last step's record -- is issued now)
-                    if (std::find(pend_win.begin(), pend_win.end(), i) != pend_win.end() && (rc = flush_wgrads())) return rc;
-                    if (s2 != s) HIP_TRY(hipStreamWaitEvent(s, p->win_ev[(size_t)i], 0));
+                    bool queued = false;
+                    for (const PendingWin& pw : pend_win) queued = queued || pw.i == i;
+                    if (ig_down && queued && (rc = flush_wgrads())) return rc;
+                    if (ig_down && s2 != s) HIP_TRY(hipStreamWaitEvent(s, p->win_ev[(size_t)i], 0));
                     w_range(i, alo, alen);
                     acc = true;
                 } else if (p->dedup) {
                     e_range(i - 1, alo, alen);        // the even half of skip window i-1's gradient is already there
                     acc = alen > 0;
                 }
-                if ((rc = tconv2(i, false, acc, alo, (unsigned)alen, s, ws + p->conv_part_off, p->conv_part_floats / 2))) return rc;
+                if ((rc = tconv2(ig_down, i, false, acc, alo, (unsigned)alen, s, ws + p->conv_part_off, p->conv_part_floats / 2))) return rc;
                 if (!win_early) {
                     if (p->dedup) {
-                        if (d.n_odd > 0 && (rc = tconv2(i, true, true, 0, 0u, s, ws + p->conv_part_off, p->conv_part_floats / 2))) return rc;
+                        if (d.n_odd > 0 && (rc = tconv2(ig_down, i, true, true, 0, 0u, s, ws + p->conv_part_off, p->conv_part_floats / 2)))
+                            return rc;
                     } else {
                         ConvArgs a = window_dgrad_args(i);
                         a.flags = F_ACCUM;
-                        HIP_TRY(conv_dispatch(p, a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
+                        HIP_TRY(dispatch(ig_down, a, ws + p->conv_part_off, p->conv_part_floats / 2, s));
                     }
                 }
             }
@@ -772,14 +884,52 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
     return WUN_OK;
 }
 
+// TF-Adam's step size (Training.py:77): lr * sqrt(1 - b2^t) / (1 - b1^t)
+static float adam_lr_t(int64_t step, float lr, float beta1, float beta2) {
+    const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)step)) /
+                        (1.0 - std::pow((double)beta1, (double)step));
+    return (float)lr_t;
+}
+
 extern "C" int wun_adam_step(const wun_plan* p, float* params, const float* grads, float* m, float* v,
                              int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
                              void* stream) {
     if (!p || !params || !grads || !m || !v) return fail(WUN_ERR_INVALID, "null argument");
     if (step < 1) return fail(WUN_ERR_INVALID, "step is 1-based");
-    const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)step)) /
-                        (1.0 - std::pow((double)beta1, (double)step));
-    HIP_TRY(launch_adam(params, grads, m, v, p->arena, (float)lr_t, beta1, beta2, eps, grad_scale, (hipStream_t)stream));
+    HIP_TRY(launch_adam(params, grads, m, v, p->arena, adam_lr_t(step, lr, beta1, beta2), beta1, beta2, eps, grad_scale,
+                        (hipStream_t)stream));
+    return WUN_OK;
+}
+
+// The selected tensors' floats as runs of consecutive arena floats (adjacent tensors merge), WUN_ADAM_RANGES runs per launch.
+extern "C" int wun_adam_step_select(const wun_plan* p, float* params, const float* grads, float* m, float* v,
+                                    int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                                    void* stream, const uint8_t* select, int64_t nselect) {
+    if (!p || !params || !grads || !m || !v) return fail(WUN_ERR_INVALID, "null argument");
+    if (step < 1) return fail(WUN_ERR_INVALID, "step is 1-based");
+    const int64_t nt = (int64_t)p->tensors.size();
+    if (!select) {
+        if (nselect != 0 && nselect != nt) return fail(WUN_ERR_INVALID, "nselect must be 0 or num_tensors when select is NULL");
+        return wun_adam_step(p, params, grads, m, v, step, lr, beta1, beta2, eps, grad_scale, stream);
+    }
+    if (nselect != nt) return fail(WUN_ERR_INVALID, "nselect must equal num_tensors");
+    const float lr_t = adam_lr_t(step, lr, beta1, beta2);
+    hipStream_t s = (hipStream_t)stream;
+    AdamRanges r;
+    memset(&r, 0, sizeof(r));
+    for (int64_t k = 0; k < nt; ++k) {
+        if (!select[k]) continue;
+        const wun_tensor_info& t = p->tensors[(size_t)k];
+        long long n = 1;
+        for (int d = 0; d < t.ndim; ++d) n *= t.shape[d];
+        if (r.n > 0 && r.off[r.n - 1] + (r.cum[r.n] - r.cum[r.n - 1]) == t.offset) { r.cum[r.n] += n; continue; }
+        if (r.n == WUN_ADAM_RANGES) {
+            HIP_TRY(launch_adam_ranges(params, grads, m, v, r, lr_t, beta1, beta2, eps, grad_scale, s));
+            memset(&r, 0, sizeof(r));
+        }
+        r.off[r.n] = t.offset; r.cum[r.n + 1] = r.cum[r.n] + n; ++r.n;
+    }
+    if (r.n > 0) HIP_TRY(launch_adam_ranges(params, grads, m, v, r, lr_t, beta1, beta2, eps, grad_scale, s));
     return WUN_OK;
 }
 

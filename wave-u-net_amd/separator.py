@@ -228,7 +228,27 @@ class UnetAudioSeparator(object):
         return {name: outs[i] for i, name in enumerate(self.source_names)}
 
     # ------------------------------------------------------------------ training step pieces
-    def loss_and_gradients(self, targets, bucket_starts=None, bucket_events=None):
+    def select_mask(self, variables):
+        """TF variable names -> the selection of wun_*_select (include/wun.h): a uint8 array with one byte per tensor in
+        wun_plan_tensor order, or None for `variables=None` (every tensor).  KeyError for an unknown name."""
+        if variables is None:
+            return None
+        if isinstance(variables, str):
+            variables = [variables]
+        plan = self._active if self._active is not None else self._any_plan()
+        index = {name: k for k, (name, _, _) in enumerate(plan.tensors)}
+        mask = np.zeros(len(plan.tensors), dtype=np.uint8)
+        for name in variables:
+            mask[index[name]] = 1                   # KeyError: not a variable of this separator
+        return mask
+
+    @staticmethod
+    def _mask_arg(mask):
+        if mask is None:
+            return None, 0
+        return mask.ctypes.data_as(C.POINTER(C.c_uint8)), int(mask.size)
+
+    def loss_and_gradients(self, targets, bucket_starts=None, bucket_events=None, variables=None):
         """MSE loss averaged over sources (Training.py:50-63) and its gradient w.r.t. every
         separator variable.  targets: dict source_name -> [B, Tout, C] or a stacked
         [S, B, Tout, C] tensor.  Must follow get_output(training=True).  Returns the loss as
@@ -236,7 +256,11 @@ class UnetAudioSeparator(object):
 
         bucket_starts / bucket_events (optional, data parallel): arena offsets in descending
         order and one torch.cuda.Event per bucket; event k is recorded as soon as all gradients
-        at offsets >= bucket_starts[k] are final (see include/wun.h, wun_loss_backward_ex)."""
+        at offsets >= bucket_starts[k] are final (see include/wun.h, wun_loss_backward_ex).
+
+        variables: TF variable names whose gradients are wanted (None = all).  The others' floats in self.grads are not
+        written, and launches no selected gradient needs are skipped (wun_loss_backward_select)."""
+        mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
         dev = self._dev()
@@ -252,10 +276,16 @@ class UnetAudioSeparator(object):
         nb = len(bucket_starts) if bucket_starts else 0
         starts = (C.c_int64 * max(nb, 1))(*([int(x) for x in bucket_starts] if nb else [0]))
         events = (C.c_void_p * max(nb, 1))(*([int(e.cuda_event) for e in bucket_events] if nb else [0]))
-        _lib.check(self._lib.wun_loss_backward_ex(
-            self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
-            self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
-            self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb))
+        if mask is None:
+            _lib.check(self._lib.wun_loss_backward_ex(
+                self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
+                self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
+                self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb))
+        else:
+            _lib.check(self._lib.wun_loss_backward_select(
+                self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
+                self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
+                self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb, *self._mask_arg(mask)))
         return loss
 
     def _stacked(self, x, what):
@@ -272,27 +302,36 @@ class UnetAudioSeparator(object):
             raise ValueError("%s shape %s != outputs shape %s" % (what, tuple(x.shape), tuple(outs.shape)))
         return x
 
-    def backward(self, d_outputs, input_grad=False, bucket_starts=None, bucket_events=None):
+    def backward(self, d_outputs, input_grad=False, bucket_starts=None, bucket_events=None, variables=None):
         """Backward pass of the last get_output(training=True) from an arbitrary upstream gradient (wun_backward): what
         tf.gradients gives the reference for any loss built on the outputs.  d_outputs: dL/d outputs, as the targets of
         loss_and_gradients (dict source_name -> [B, Tout, C] or a stacked [S, B, Tout, C] tensor).  The parameter gradients
         are written to self.grads (overwritten, as loss_and_gradients does); returns dL/d mix [B, Tin, C] when input_grad,
-        else None.  bucket_starts / bucket_events: as for loss_and_gradients."""
+        else None.  bucket_starts / bucket_events: as for loss_and_gradients.  variables: TF variable names whose gradients
+        are wanted (None = all; the others' floats in self.grads are not written); variables=[] with input_grad=True is the
+        input-only gradient (wun_backward_select)."""
+        mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
         dout = self._stacked(d_outputs, "d_outputs")
         d_mix = torch.empty(tuple(self._last_mix.shape), dtype=torch.float32, device=self._dev()) if input_grad else None
         self._run_backward(self._ws[self._last_key], self._outs[self._last_key], dout, self.grads, d_mix,
-                           bucket_starts, bucket_events)
+                           bucket_starts, bucket_events, mask)
         return d_mix
 
-    def _run_backward(self, ws, outs, dout, grads, d_mix, bucket_starts=None, bucket_events=None):
+    def _run_backward(self, ws, outs, dout, grads, d_mix, bucket_starts=None, bucket_events=None, mask=None):
         nb = len(bucket_starts) if bucket_starts else 0
         starts = (C.c_int64 * max(nb, 1))(*([int(x) for x in bucket_starts] if nb else [0]))
         events = (C.c_void_p * max(nb, 1))(*([int(e.cuda_event) for e in bucket_events] if nb else [0]))
-        _lib.check(self._lib.wun_backward_ex(
+        if mask is None:
+            _lib.check(self._lib.wun_backward_ex(
+                self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
+                grads.data_ptr(), d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb))
+            return
+        gp = grads.data_ptr() if (grads is not None and mask.any()) else None     # (input-only: grads is not touched)
+        _lib.check(self._lib.wun_backward_select(
             self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
-            grads.data_ptr(), d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb))
+            gp, d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb, *self._mask_arg(mask)))
 
     def module(self):
         """This separator as a torch.nn.Module (wave_u_net_amd.autograd.WaveUNet): get_output under torch.autograd, the
@@ -328,13 +367,22 @@ class UnetAudioSeparator(object):
         """Reuse choices exported by a plan of the same config / batch / length (ValueError otherwise)."""
         _lib.check(self._lib.wun_plan_tune_import(self._active.handle, text.encode()))
 
-    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
-        """tf.train.AdamOptimizer(learning_rate=lr) update (Training.py:77) + global_step += 1."""
+    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, variables=None):
+        """tf.train.AdamOptimizer(learning_rate=lr) update (Training.py:77) + global_step += 1.  variables: TF variable names
+        to update, as minimize(loss, var_list=...) does (None = all); params, m and v of every other tensor stay as they are
+        (wun_adam_step_select)."""
+        mask = self.select_mask(variables)
         self.global_step += 1
-        _lib.check(self._lib.wun_adam_step(
+        if mask is None:
+            _lib.check(self._lib.wun_adam_step(
+                self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
+                self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
+                grad_scale, self._stream()))
+            return
+        _lib.check(self._lib.wun_adam_step_select(
             self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
             self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
-            grad_scale, self._stream()))
+            grad_scale, self._stream(), *self._mask_arg(mask)))
 
     def activation(self, kind, index=0):
         """(tensor view [B, C, frames], t0, tstep) of a forward activation kept in the workspace of the last
