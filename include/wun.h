@@ -252,6 +252,27 @@ int wun_loss_backward_select(const wun_plan* plan, const float* params, const fl
                              const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
                              const uint8_t* select, int64_t nselect);
 
+/* Gradient accumulation (k micro-batches per optimizer step): the arguments of wun_backward_select /
+ * wun_loss_backward_select, but the parameter gradients are ADDED to `grads` instead of overwriting them.  Let G be what the
+ * matching _select call with the same arguments would write to a gradient float: after the call every float of a selected
+ * tensor holds old + G -- one IEEE fp32 add, round to nearest even (bit-equal to torch's float32 a + b).  All other floats
+ * (unselected tensors, padding floats) are not written.  select = NULL means every tensor.
+ *   d_mix, loss : WRITTEN, not accumulated; bit-equal to the _select call's.
+ * Selection rules, argument checks (all before any GPU work) and bucket events are those of the _select calls; an event fires
+ * once the ACCUMULATED values at offsets >= its start are final.  `grads` is read only after everything the caller queued on
+ * `stream` before the call (the side streams wait on `stream` before they touch it).  Same launches, launch positions, tilings
+ * and split counts as the _select call -- a pinned tuning table applies unchanged and G is bit-identical; only the kernels'
+ * final gradient stores differ.  Both compute modes; same workspace.  Typical use: the first micro-batch calls
+ * wun_loss_backward_ex (overwrite), the others wun_loss_backward_accumulate, the last one with the bucket events. */
+int wun_backward_accumulate(const wun_plan* plan, const float* params, const float* mix_btc, float* workspace,
+                            const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
+                            const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
+                            const uint8_t* select, int64_t nselect);
+int wun_loss_backward_accumulate(const wun_plan* plan, const float* params, const float* mix_btc, float* workspace,
+                                 const float* outputs, const float* targets, float* grads, float* loss, void* stream,
+                                 const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
+                                 const uint8_t* select, int64_t nselect);
+
 /* Optional autotuning pass (no reference counterpart): runs one forward + loss/backward on the
  * given buffers while timing, for every conv / weight-gradient launch of the step, the candidate
  * tile shapes and split factors, and caches the fastest per launch in the plan.  The contents of

@@ -50,6 +50,10 @@ _SIGS = {
                                       C.POINTER(C.c_uint8), C.c_int64]),
     "wun_loss_backward_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
                                            C.c_int32, C.POINTER(C.c_uint8), C.c_int64]),
+    "wun_backward_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                                          C.c_int32, C.POINTER(C.c_uint8), C.c_int64]),
+    "wun_loss_backward_accumulate": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                                               C.c_int32, C.POINTER(C.c_uint8), C.c_int64]),
     "wun_plan_tune": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "wun_plan_tune_export": (C.c_int, [_P, C.c_char_p, C.c_int64]),
     "wun_plan_tune_import": (C.c_int, [_P, C.c_char_p]),

@@ -289,7 +289,7 @@ static bool wgrad_common_geom(WgradArgs* parts, int nparts, int mtw, int nw) {
 }
 
 int run_wgrad(const wun_plan* p, WgradArgs* parts, int nparts, const ConvLayer& cl, float* ws,
-                     float* grads, hipStream_t main, hipStream_t s, bool dep) {
+                     float* grads, hipStream_t main, hipStream_t s, bool dep, bool accum) {
     // everything this weight gradient reads (dz, activations) has been issued on `main`
     // (dep == false: the caller already made `s` wait -- one event for a batch of weight gradients)
     if (dep) {
@@ -326,6 +326,7 @@ int run_wgrad(const wun_plan* p, WgradArgs* parts, int nparts, const ConvLayer& 
         while (!wgrad_common_geom(parts, nparts, m, n) && m > 1) m = m == 6 ? 4 : m / 2;   // (bf16: 8 -> 4)
     }
     for (int i = 0; i < nparts; ++i) parts[i].nsplit = wgrad_pick_nsplit(parts[i], p->sw);
+    for (int i = 0; i < nparts; ++i) parts[i].accum = accum ? 1 : 0;   // (read by the launchers only: direct epilogue, reduction)
 
     auto run = [&](WgradArgs* q) -> hipError_t {
         int total = 0;
@@ -464,7 +465,7 @@ int run_wgrad(const wun_plan* p, WgradArgs* parts, int nparts, const ConvLayer& 
 // Narrow layers (audio-input conv, output head): direct reduction kernel instead of MFMA tiles.  All parts
 // (a down level's decimated + window positions) write consecutive splits of one partial list; one reduction.
 int run_narrow_wgrad(const wun_plan* p, NarrowWgradArgs* parts, int nparts, const long long* woff,
-                            const long long* boff, float* ws, float* grads, hipStream_t main, hipStream_t s) {
+                            const long long* boff, float* ws, float* grads, hipStream_t main, hipStream_t s, bool accum) {
     int rcd = WUN_OK;
     hipStream_t side_of_caller = s;                            // (bucket events of the data-parallel path are recorded there)
     // bf16 mode, history (round 5): built WITH packed fp32 VALU instructions, narrow_wgrad_kernel (the LDS-staged
@@ -499,7 +500,7 @@ int run_narrow_wgrad(const wun_plan* p, NarrowWgradArgs* parts, int nparts, cons
         HIP_TRY(launch_narrow_wgrad(parts[i], s, p->sw));
         done += parts[i].nsplit;
     }
-    HIP_TRY(launch_narrow_wgrad_reduce(parts[0], partial, total, grads, woff, boff, s));
+    HIP_TRY(launch_narrow_wgrad_reduce(parts[0], partial, total, grads, woff, boff, s, accum));
     // (moved to `main`: the side stream the caller named is where it records "gradients complete" -- it follows)
     if (s != side_of_caller && (rcd = stream_dep(p, s, side_of_caller))) return rcd;
     return WUN_OK;

@@ -181,8 +181,9 @@ __global__ void upsample_bwd_kernel(UpsampleBwdArgs a) {
 }
 
 // dw[c] = sigmoid'(w[c]) * sum_{b,i} dy[2i+1] * (x[i] - x[i+1])   (x[n] = 0 in same mode)
-template <typename ET>
-__global__ __launch_bounds__(256) void interp_grad_kernel(UpsampleBwdArgs a) {
+// ACC (interp_grad_acc_kernel): adds to dw instead of storing
+template <typename ET, bool ACC>
+__device__ __forceinline__ void interp_grad_body(const UpsampleBwdArgs& a) {
     __shared__ float red[256];
     const int c = blockIdx.x;
     float s = 0.f;
@@ -201,9 +202,13 @@ __global__ __launch_bounds__(256) void interp_grad_kernel(UpsampleBwdArgs a) {
     }
     if (threadIdx.x == 0) {
         const float sg = sigmoidf_exact(a.w[c]);
-        a.dw[c] = red[0] * sg * (1.f - sg);
+        grad_st<ACC>(&a.dw[c], red[0] * sg * (1.f - sg));
     }
 }
+template <typename ET>
+__global__ __launch_bounds__(256) void interp_grad_kernel(UpsampleBwdArgs a) { interp_grad_body<ET, false>(a); }
+template <typename ET>
+__global__ __launch_bounds__(256) void interp_grad_acc_kernel(UpsampleBwdArgs a) { interp_grad_body<ET, true>(a); }
 
 // Two-stage form of interp_grad_kernel (round 6).  One workgroup per CHANNEL (above) leaves 48 .. 312 workgroups walking
 // B x n/2 strided elements each: 0.58 ms per step on M5 `full` for 12 launches that move 0.3 GB.  Stage 1: one workgroup per
@@ -242,14 +247,17 @@ __global__ __launch_bounds__(256) void interp_grad_rows_kernel(UpsampleBwdArgs a
     if (threadIdx.x == 0) a.dw_partial[(long long)b * a.C + c] = red[0];
 }
 
-__global__ __launch_bounds__(256) void interp_grad_finish_kernel(UpsampleBwdArgs a) {
+template <bool ACC>
+__device__ __forceinline__ void interp_grad_finish_body(const UpsampleBwdArgs& a) {
     const int c = (int)blockIdx.x * 256 + (int)threadIdx.x;
     if (c >= a.C) return;
     float s = 0.f;
     for (int b = 0; b < a.B; ++b) s += a.dw_partial[(long long)b * a.C + c];
     const float sg = sigmoidf_exact(a.w[c]);
-    a.dw[c] = s * sg * (1.f - sg);
+    grad_st<ACC>(&a.dw[c], s * sg * (1.f - sg));
 }
+__global__ __launch_bounds__(256) void interp_grad_finish_kernel(UpsampleBwdArgs a) { interp_grad_finish_body<false>(a); }
+__global__ __launch_bounds__(256) void interp_grad_finish_acc_kernel(UpsampleBwdArgs a) { interp_grad_finish_body<true>(a); }
 
 // Vector form of upsample_bwd_kernel: a lane produces dz[4i .. 4i+3] from dy[8i-1 .. 8i+7] (two 16-byte loads + one
 // scalar) and the mask vector; same arithmetic and summation order per element.
@@ -324,7 +332,7 @@ hipError_t launch_upsample_bwd(const UpsampleBwdArgs& a, hipStream_t s) {
 
 // gradient of the learned interpolation weights of one level (InterpolationLayer.py:19-23): reads d(upsampled tensor) and the
 // level's input, writes dw -- nothing the input-gradient chain waits for, so the plan runs it on a side stream
-hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s) {
+hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s, bool accum) {
     hipError_t e = hipSuccess;
     const bool vecok = (a.ypitch & 3) == 0 && (a.ybs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.dy) & 15) == 0 &&
                        (a.xpitch & 3) == 0 && (a.xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
@@ -335,7 +343,12 @@ hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s) {
             const dim3 grid((unsigned)a.C, (unsigned)a.B);
             if (a.bf) hipLaunchKernelGGL(interp_grad_rows_kernel<bf16_t>, grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL(interp_grad_rows_kernel<float>, grid, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(interp_grad_finish_kernel, dim3((unsigned)((a.C + 255) / 256)), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(accum ? interp_grad_finish_acc_kernel : interp_grad_finish_kernel, dim3((unsigned)((a.C + 255) / 256)),
+                               dim3(256), 0, s, a);
+        } else if (accum) {
+            // (the one-stage form runs for rows that are not 16-byte aligned, without partial scratch, or for B > 65535)
+            if (a.bf) hipLaunchKernelGGL(interp_grad_acc_kernel<bf16_t>, dim3((unsigned)a.C), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL(interp_grad_acc_kernel<float>, dim3((unsigned)a.C), dim3(256), 0, s, a);
         } else {
             if (a.bf) hipLaunchKernelGGL(interp_grad_kernel<bf16_t>, dim3((unsigned)a.C), dim3(256), 0, s, a);
             else hipLaunchKernelGGL(interp_grad_kernel<float>, dim3((unsigned)a.C), dim3(256), 0, s, a);

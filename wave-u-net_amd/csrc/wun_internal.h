@@ -155,6 +155,8 @@ struct WgradArgs {
     int bf16;        // speed mode: operands rounded to bf16 in LDS, v_mfma_f32_16x16x32_bf16 (wun_wgrad_bf16.hip)
     int win;         // exact fp32, register-window form (wun_wgrad_win.hip) instead of the LDS-tiled wgrad_mfma_kernel
     int sbf;         // bf16 kernel: src0 / src1 AND dz point at bf16 elements (pitches / strides / offsets in elements)
+    int accum;       // final stores ADD to what the gradient arena holds (wun_*backward_accumulate): the launchers pick the
+                     // accumulating instantiations (direct epilogue and split reduction); the kernels never read this field
 };
 
 // tile geometry of an exact-fp32 weight-gradient launch
@@ -301,6 +303,19 @@ template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, long long i, 
     *reinterpret_cast<wun_u32x2*>(p + i) = (wun_u32x2){bf_pack2(v[0], v[1]), bf_pack2(v[2], v[3])};
 }
 
+// ---- gradient accumulation (wun_*backward_accumulate) ----
+// Every final gradient float is written once, by one lane: its accumulating form reads the old value and adds the rounded fp32
+// G the overwriting form would store -- one IEEE add, round to nearest even (torch's float32 a + b).  The pragma keeps hipcc
+// from contracting the add with the product that produced G into an FMA (that would change the bits).
+__device__ __forceinline__ float grad_acc_add(float old, float g) {
+#pragma clang fp contract(off)
+    return old + g;
+}
+template <bool ACC> __device__ __forceinline__ void grad_st(float* p, float g) {
+    if constexpr (ACC) *p = grad_acc_add(*p, g);
+    else *p = g;
+}
+
 // ---- launchers (wun_kernels.hip) ---------------------------------------------------
 size_t conv_lds_bytes(const ConvArgs& a, int variant, const WunSwitches& sw);
 int  conv_pick_variant(const ConvArgs& a);
@@ -320,7 +335,7 @@ hipError_t launch_wgrad_reduce(const WgradArgs& a, const float* partial, int nsp
                                hipStream_t s, const WunSwitches& sw);
 hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s);
 hipError_t launch_upsample_bwd(const UpsampleBwdArgs& a, hipStream_t s);
-hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s);               // dw of the learned interpolation weights
+hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s, bool accum = false);   // dw of the learned interpolation weights
 hipError_t launch_head_fwd_off(const HeadArgs& a, const long long* hoff, hipStream_t s);
 int head_bwd_blocks(const HeadArgs& a);
 hipError_t launch_head_bwd_off(const HeadArgs& a, const long long* hoff, hipStream_t s);
@@ -353,7 +368,7 @@ int narrow_wgrad_pick_nsplit(const NarrowWgradArgs& a, const WunSwitches& sw);
 long long narrow_wgrad_partial_floats(const NarrowWgradArgs& a);
 hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitches& sw);
 hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* partial, int nsplit, float* grads,
-                                      const long long* woff, const long long* boff, hipStream_t s);
+                                      const long long* woff, const long long* boff, hipStream_t s, bool accum = false);
 size_t mix_grad_lds_bytes(const MixGradArgs& a);
 hipError_t launch_mix_grad(const MixGradArgs& a, hipStream_t s);
 

@@ -1514,7 +1514,8 @@ hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hi
 // stride-2 convs.  An extra all-ones A row produces the bias gradient.
 #define WUN_WG_XIT 8      // float4 X loads per thread and unit (geometry guarantees it suffices)
 
-template <int MTW, int NW>
+// ACC: the single-split epilogue adds to the gradient arena (wun_*backward_accumulate) instead of storing
+template <int MTW, int NW, bool ACC = false>
 __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WgradArgs a, int nMG, int nNG, int TK,
                                                          int XP, int ZP, int nChMax, int ONESP,
                                                          int XW4) {
@@ -1790,9 +1791,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(WgradArgs a, int nMG
                 const int r = rlo + (wave * MTW + mt) * 16 + lg * 4 + r4;
                 if (r < Mtot) {
                     const int c = r / a.KW, k = r - c * a.KW;
-                    outp[((long long)k * Ctot + c) * a.N + col] = acc[mt][n][r4];
+                    grad_st<ACC>(&outp[((long long)k * Ctot + c) * a.N + col], acc[mt][n][r4]);
                 } else if (r == Mtot) {
-                    outp[(long long)Mtot * a.N + col] = acc[mt][n][r4];
+                    grad_st<ACC>(&outp[(long long)Mtot * a.N + col], acc[mt][n][r4]);
                 }
             }
         }
@@ -1807,7 +1808,8 @@ struct WgradReduceArgs {
     int nsplit, MTW, NW, nMG, nNG, Mtot, KW, Ctot, N;
 };
 
-template <int SL>
+// ACC: adds to the gradient arena (wun_*backward_accumulate) instead of storing
+template <int SL, bool ACC = false>
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradReduceArgs a) {
     __shared__ f32x4 red[SL > 1 ? 256 : 1];
     constexpr int VPB = 256 / SL;                                  // vector slots per block
@@ -1857,9 +1859,9 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradReduceArgs a) {
         const int r = r0 + r4;
         if (r < a.Mtot) {
             const int c = r / a.KW, kk = r - c * a.KW;
-            a.out_w[((long long)kk * a.Ctot + c) * a.N + col] = sum[r4];
+            grad_st<ACC>(&a.out_w[((long long)kk * a.Ctot + c) * a.N + col], sum[r4]);
         } else if (r == a.Mtot) {
-            a.out_b[col] = sum[r4];
+            grad_st<ACC>(&a.out_b[col], sum[r4]);
         }
     }
 }
@@ -1950,16 +1952,18 @@ static hipError_t wgrad_launch_t(WgradArgs a, const WgradGeom& g, hipStream_t s)
     a.nQT = (a.Tq + g.TK - 1) / g.TK;
     const long long units = (long long)a.B * a.nQT;
     a.units_per_split = (int)((units + a.nsplit - 1) / a.nsplit);
-    auto kern = wgrad_mfma_kernel<MTW, NW>;
-    static size_t lds_allowed = 64 * 1024;
-    if (g.lds > lds_allowed) {
+    const bool acc = a.accum && a.direct;           // (split launches write partials: the plain kernel)
+    auto kern = acc ? wgrad_mfma_kernel<MTW, NW, true> : wgrad_mfma_kernel<MTW, NW>;
+    static size_t lds_allowed[2] = {64 * 1024, 64 * 1024};
+    size_t& allowed = lds_allowed[acc ? 1 : 0];
+    if (g.lds > allowed) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
         if (e != hipSuccess) return e;
-        lds_allowed = g.lds;
+        allowed = g.lds;
     }
     const long long grid = (long long)g.nMG * g.nNG * a.nsplit;
     char nm[64];
-    snprintf(nm, sizeof(nm), "wgrad_mfma_kernel<%d, %d>", MTW, NW);
+    snprintf(nm, sizeof(nm), acc ? "wgrad_mfma_acc_kernel<%d, %d>" : "wgrad_mfma_kernel<%d, %d>", MTW, NW);
     char tag[160];
     snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nsplit=%d grid=%lld", a.C0 + a.C1, a.N, a.Tq, a.KW,
              a.loader, a.B, a.nsplit, grid);
@@ -2021,7 +2025,13 @@ hipError_t launch_wgrad_reduce(const WgradArgs& a, const float* partial, int nsp
     const long long blocks = (slots + vpb - 1) / vpb;
     char tag[96];
     snprintf(tag, sizeof(tag), "bytes=%lld nsplit=%d", (long long)((nsplit + 1) * slots * 16), nsplit);
-    ProfScope ps("wgrad_reduce_kernel", 0.0, s, tag, (double)((nsplit + 1) * slots * 16));
+    ProfScope ps(a.accum ? "wgrad_reduce_acc_kernel" : "wgrad_reduce_kernel", 0.0, s, tag, (double)((nsplit + 1) * slots * 16));
+    if (a.accum) {
+        if (sl == 16) hipLaunchKernelGGL((wgrad_reduce_kernel<16, true>), dim3((unsigned)blocks), dim3(256), 0, s, r);
+        else if (sl == 4) hipLaunchKernelGGL((wgrad_reduce_kernel<4, true>), dim3((unsigned)blocks), dim3(256), 0, s, r);
+        else hipLaunchKernelGGL((wgrad_reduce_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, r);
+        return hipGetLastError();
+    }
     if (sl == 16) hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, r);
     else if (sl == 4) hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, r);
     else hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, r);

@@ -314,10 +314,11 @@ static bool narrow_stream_ok(const NarrowWgradArgs& a, const WunSwitches& sw) {
 // out element (k, ci, n = s*Nper + c) -> source s: weights [K][Ctot][Nper] at woff[s], bias at boff[s].
 // One workgroup per output element: 256 threads sum the splits (thread t takes splits t, t+256, ...), then a
 // fixed-order tree through LDS -- deterministic, and ~nsplit/256 dependent loads per thread instead of nsplit.
-__global__ __launch_bounds__(256) void narrow_wgrad_reduce_kernel(const float* partial, int nsplit, int KW, int Ctot, int N,
-                                                                  int Nper, float* grads, long long w0, long long w1,
-                                                                  long long w2, long long w3, long long b0, long long b1,
-                                                                  long long b2, long long b3) {
+// ACC: adds to the gradient arena (narrow_wgrad_reduce_acc_kernel) instead of storing.
+template <bool ACC>
+__device__ __forceinline__ void narrow_wgrad_reduce_body(const float* partial, int nsplit, int KW, int Ctot, int N, int Nper,
+                                                         float* grads, long long w0, long long w1, long long w2, long long w3,
+                                                         long long b0, long long b1, long long b2, long long b3) {
     __shared__ float red[256];
     const long long woff[4] = {w0, w1, w2, w3}, boff[4] = {b0, b1, b2, b3};
     const int P = (KW * Ctot + 1) * N;
@@ -333,8 +334,21 @@ __global__ __launch_bounds__(256) void narrow_wgrad_reduce_kernel(const float* p
     if (threadIdx.x != 0) return;
     const int n = i % N, r = i / N;
     const int src = n / Nper, c = n - src * Nper;
-    if (r < KW * Ctot) grads[woff[src] + (long long)r * Nper + c] = red[0];
-    else grads[boff[src] + c] = red[0];
+    if (r < KW * Ctot) grad_st<ACC>(&grads[woff[src] + (long long)r * Nper + c], red[0]);
+    else grad_st<ACC>(&grads[boff[src] + c], red[0]);
+}
+
+__global__ __launch_bounds__(256) void narrow_wgrad_reduce_kernel(const float* partial, int nsplit, int KW, int Ctot, int N,
+                                                                  int Nper, float* grads, long long w0, long long w1,
+                                                                  long long w2, long long w3, long long b0, long long b1,
+                                                                  long long b2, long long b3) {
+    narrow_wgrad_reduce_body<false>(partial, nsplit, KW, Ctot, N, Nper, grads, w0, w1, w2, w3, b0, b1, b2, b3);
+}
+__global__ __launch_bounds__(256) void narrow_wgrad_reduce_acc_kernel(const float* partial, int nsplit, int KW, int Ctot, int N,
+                                                                      int Nper, float* grads, long long w0, long long w1,
+                                                                      long long w2, long long w3, long long b0, long long b1,
+                                                                      long long b2, long long b3) {
+    narrow_wgrad_reduce_body<true>(partial, nsplit, KW, Ctot, N, Nper, grads, w0, w1, w2, w3, b0, b1, b2, b3);
 }
 
 // (the plan keeps the LDS-staged form off the CUs the bf16 weight gradient is using: wun_dispatch.hip, run_narrow_wgrad)
@@ -436,9 +450,9 @@ hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitch
 }
 
 hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* partial, int nsplit, float* grads,
-                                      const long long* woff, const long long* boff, hipStream_t s) {
+                                      const long long* woff, const long long* boff, hipStream_t s, bool accum) {
     const int P = (int)narrow_wgrad_partial_floats(a);
-    hipLaunchKernelGGL(narrow_wgrad_reduce_kernel, dim3((unsigned)P), dim3(256), 0, s, partial, nsplit, a.KW,
+    hipLaunchKernelGGL(accum ? narrow_wgrad_reduce_acc_kernel : narrow_wgrad_reduce_kernel, dim3((unsigned)P), dim3(256), 0, s, partial, nsplit, a.KW,
                        a.C0 + a.C1, a.N, a.Nper, grads, woff[0], woff[1], woff[2], woff[3], boff[0], boff[1], boff[2], boff[3]);
     return hipGetLastError();
 }

@@ -286,7 +286,7 @@ static int parse_select(const wun_plan* p, const uint8_t* select, int64_t nselec
 
 static int backward_body(const wun_plan* p, const float* params, float* ws, const float* outputs, const BackwardHead& head,
                          float* grads, const MixGradArgs* mix, void* stream, const int64_t* bucket_starts,
-                         void* const* bucket_events, int32_t nbuckets, const BackwardSelect& sel);
+                         void* const* bucket_events, int32_t nbuckets, const BackwardSelect& sel, bool accum);
 
 extern "C" int wun_loss_backward_ex(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
                                     const float* outputs, const float* targets, float* grads, float* loss,
@@ -296,11 +296,10 @@ extern "C" int wun_loss_backward_ex(const wun_plan* p, const float* params, cons
                                     nbuckets, nullptr, 0);
 }
 
-extern "C" int wun_loss_backward_select(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
-                                        const float* outputs, const float* targets, float* grads, float* loss,
-                                        void* stream, const int64_t* bucket_starts, void* const* bucket_events,
-                                        int32_t nbuckets, const uint8_t* select, int64_t nselect) {
-    (void)mix_btc;
+// accum: the final gradient stores add to `grads` (wun_loss_backward_accumulate); everything else is the overwriting call
+static int loss_backward_select(const wun_plan* p, const float* params, float* ws, const float* outputs, const float* targets,
+                                float* grads, float* loss, void* stream, const int64_t* bucket_starts, void* const* bucket_events,
+                                int32_t nbuckets, const uint8_t* select, int64_t nselect, bool accum) {
     int rc;
     if ((rc = check_buckets(bucket_starts, bucket_events, nbuckets))) return rc;
     if (!p || !params || !ws || !outputs || !targets || !grads || !loss) return fail(WUN_ERR_INVALID, "null argument");
@@ -308,7 +307,25 @@ extern "C" int wun_loss_backward_select(const wun_plan* p, const float* params, 
     bool any = false;
     if ((rc = parse_select(p, select, nselect, false, sel, any))) return rc;
     const BackwardHead head{targets, loss, nullptr};
-    return backward_body(p, params, ws, outputs, head, grads, nullptr, stream, bucket_starts, bucket_events, nbuckets, sel);
+    return backward_body(p, params, ws, outputs, head, grads, nullptr, stream, bucket_starts, bucket_events, nbuckets, sel, accum);
+}
+
+extern "C" int wun_loss_backward_select(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                                        const float* outputs, const float* targets, float* grads, float* loss,
+                                        void* stream, const int64_t* bucket_starts, void* const* bucket_events,
+                                        int32_t nbuckets, const uint8_t* select, int64_t nselect) {
+    (void)mix_btc;
+    return loss_backward_select(p, params, ws, outputs, targets, grads, loss, stream, bucket_starts, bucket_events, nbuckets,
+                                select, nselect, false);
+}
+
+extern "C" int wun_loss_backward_accumulate(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                                            const float* outputs, const float* targets, float* grads, float* loss,
+                                            void* stream, const int64_t* bucket_starts, void* const* bucket_events,
+                                            int32_t nbuckets, const uint8_t* select, int64_t nselect) {
+    (void)mix_btc;
+    return loss_backward_select(p, params, ws, outputs, targets, grads, loss, stream, bucket_starts, bucket_events, nbuckets,
+                                select, nselect, true);
 }
 
 // d_mix: where the audio's gradient lives after the backward pass -- down conv 0's d(pre-activation) in the launch geometries of
@@ -370,11 +387,9 @@ extern "C" int wun_backward_ex(const wun_plan* p, const float* params, const flo
                                nbuckets, nullptr, 0);
 }
 
-extern "C" int wun_backward_select(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
-                                   const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
-                                   const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
-                                   const uint8_t* select, int64_t nselect) {
-    (void)mix_btc;
+static int backward_select(const wun_plan* p, const float* params, float* ws, const float* outputs, const float* d_outputs,
+                           float* grads, float* d_mix, void* stream, const int64_t* bucket_starts, void* const* bucket_events,
+                           int32_t nbuckets, const uint8_t* select, int64_t nselect, bool accum) {
     int rc;
     if ((rc = check_buckets(bucket_starts, bucket_events, nbuckets))) return rc;
     if (!p || !params || !ws || !outputs || !d_outputs) return fail(WUN_ERR_INVALID, "null argument");
@@ -386,12 +401,30 @@ extern "C" int wun_backward_select(const wun_plan* p, const float* params, const
     if (d_mix && (rc = mix_grad_args(p, params, ws, d_outputs, d_mix, mix))) return rc;
     const BackwardHead head{nullptr, nullptr, d_outputs};
     return backward_body(p, params, ws, outputs, head, grads, d_mix ? &mix : nullptr, stream, bucket_starts, bucket_events,
-                         nbuckets, sel);
+                         nbuckets, sel, accum);
+}
+
+extern "C" int wun_backward_select(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                                   const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
+                                   const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
+                                   const uint8_t* select, int64_t nselect) {
+    (void)mix_btc;
+    return backward_select(p, params, ws, outputs, d_outputs, grads, d_mix, stream, bucket_starts, bucket_events, nbuckets,
+                           select, nselect, false);
+}
+
+extern "C" int wun_backward_accumulate(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                                       const float* outputs, const float* d_outputs, float* grads, float* d_mix, void* stream,
+                                       const int64_t* bucket_starts, void* const* bucket_events, int32_t nbuckets,
+                                       const uint8_t* select, int64_t nselect) {
+    (void)mix_btc;
+    return backward_select(p, params, ws, outputs, d_outputs, grads, d_mix, stream, bucket_starts, bucket_events, nbuckets,
+                           select, nselect, true);
 }
 
 static int backward_body(const wun_plan* p, const float* params, float* ws, const float* outputs, const BackwardHead& head,
                          float* grads, const MixGradArgs* mix, void* stream, const int64_t* bucket_starts,
-                         void* const* bucket_events, int32_t nbuckets, const BackwardSelect& sel) {
+                         void* const* bucket_events, int32_t nbuckets, const BackwardSelect& sel, bool accum) {
     BucketSignal sig{bucket_starts, bucket_events, nbuckets, 0};
     if (!p->wt.empty() && !p->dev_wt) return fail(WUN_ERR_HIP, "plan was created without a usable HIP device");
     hipStream_t s = (hipStream_t)stream;
@@ -558,11 +591,11 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             HIP_TRY(hipStreamWaitEvent(s2, e, 0));
             if (s3 != s2) HIP_TRY(hipStreamWaitEvent(s3, e, 0));
         }
-        for (auto& ub : pend_interp) HIP_TRY(launch_interp_grad(ub, wstream()));
+        for (auto& ub : pend_interp) HIP_TRY(launch_interp_grad(ub, wstream(), accum));
         pend_interp.clear();
         for (auto& q : pend) {
             int rcq = WUN_OK;
-            if (q.live) rcq = run_wgrad(p, q.w, q.n, *q.cl, ws, grads, s, wstream(), false);
+            if (q.live) rcq = run_wgrad(p, q.w, q.n, *q.cl, ws, grads, s, wstream(), false, accum);
             else { wstream(); ++p->wi; }
             if (rcq) return rcq;
             if ((rcq = ready2(q.cl->woff))) return rcq;        // (a bucket without a selected tensor: signalled here)
@@ -636,7 +669,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             long long woff[4] = {0, 0, 0, 0}, boff[4] = {0, 0, 0, 0};
             for (int sh = 0; sh < p->Sh; ++sh) { woff[sh] = p->head[sh].woff; boff[sh] = p->head[sh].boff; }
             hipStream_t sw = wstream();
-            if (wg_head && (rc = run_narrow_wgrad(p, &nw, 1, woff, boff, ws, grads, s, sw))) return rc;
+            if (wg_head && (rc = run_narrow_wgrad(p, &nw, 1, woff, boff, ws, grads, s, sw, accum))) return rc;
             head_done = true;
         } else if (p->bf16) {
             // bf16 mode: the head's inputs are the fp32 audio and the bf16 feature map -- only the narrow kernels read
@@ -649,7 +682,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
                 one.dz = h.dpre + (long long)sh * h.dps;
                 const long long woff[4] = {p->head[sh].woff, 0, 0, 0}, boff[4] = {p->head[sh].boff, 0, 0, 0};
                 hipStream_t sw = wstream();
-                if (wg_head && (rc = run_narrow_wgrad(p, &one, 1, woff, boff, ws, grads, s, sw))) return rc;
+                if (wg_head && (rc = run_narrow_wgrad(p, &one, 1, woff, boff, ws, grads, s, sw, accum))) return rc;
             }
             head_done = true;
         }
@@ -664,7 +697,7 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             wset_dz(w, ws + p->dpre16_off + ((long long)sh * p->B * C * p->dp16_pitch) / 2, (long long)C * p->dp16_pitch, p->dp16_pitch, C, p->Tout);
         else
             wset_dz(w, h.dpre + (long long)sh * h.dps, h.dpbs, h.dppitch, C, p->Tout);
-        if ((rc = run_wgrad(p, &w, 1, p->head[sh], ws, grads, s, wstream()))) return rc;
+        if ((rc = run_wgrad(p, &w, 1, p->head[sh], ws, grads, s, wstream(), true, accum))) return rc;
     }
     if (p->Sh > 0 && (rc = ready2(p->head[0].woff))) return rc;
 
@@ -805,7 +838,8 @@ static int backward_body(const wun_plan* p, const float* params, float* ws, cons
             if ((rc = flush_wgrads())) return rc;
             const long long woff[4] = {cl.woff, 0, 0, 0}, boff[4] = {cl.boff, 0, 0, 0};
             hipStream_t sw = wstream();
-            if (wg_down && (rc = run_narrow_wgrad(p, nw, (same || (p->dedup && d.n_odd == 0)) ? 1 : 2, woff, boff, ws, grads, s, sw)))
+            if (wg_down && (rc = run_narrow_wgrad(p, nw, (same || (p->dedup && d.n_odd == 0)) ? 1 : 2, woff, boff, ws, grads, s, sw,
+                                                 accum)))
                 return rc;
             if ((rc = ready2(cl.woff))) return rc;
         } else if (same) {

@@ -59,7 +59,8 @@ __device__ __forceinline__ u32x2 wb_tr_read(const unsigned short* p) {
 
 struct WgBfK { int NCB, nCB, nMG, nNG, TK, XW4, XROWS, ZPe; };
 
-template <int MTW, int NW>
+// ACC: the single-split epilogue adds to the gradient arena (wun_*backward_accumulate) instead of storing
+template <int MTW, int NW, bool ACC = false>
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(WgradArgs a, WgBfK g) {
     extern __shared__ __attribute__((aligned(16))) unsigned short wl[];
     constexpr int NG = NW * 16;
@@ -341,14 +342,14 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(WgradArgs a, WgBfK g) {
             const int col = ng * NG + n * 16 + li;
             if (col >= a.N) continue;
             if (kind[mt] == 1) {
-                if (lg == 0) outp[(long long)K * Ctot * a.N + col] = acc[mt][n][0];
+                if (lg == 0) grad_st<ACC>(&outp[(long long)K * Ctot * a.N + col], acc[mt][n][0]);
                 continue;
             }
             const int cbl = slot / K, tap = slot - cbl * K;
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const int c = (cb0 + cbl) * 16 + lg * 4 + r4;
-                if (c < Ctot) outp[((long long)tap * Ctot + c) * a.N + col] = acc[mt][n][r4];
+                if (c < Ctot) grad_st<ACC>(&outp[((long long)tap * Ctot + c) * a.N + col], acc[mt][n][r4]);
             }
         }
     }
@@ -361,7 +362,8 @@ struct WgradBfReduceArgs {
     int nsplit, MTW, NW, NCB, nCB, nMG, nNG, KW, Ctot, N;
 };
 
-template <int SL>
+// ACC: adds to the gradient arena (wun_*backward_accumulate) instead of storing
+template <int SL, bool ACC = false>
 __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(WgradBfReduceArgs a) {
     __shared__ f32x4 red[SL > 1 ? 256 : 1];
     constexpr int VPB = 256 / SL;                                  // vector slots per block
@@ -411,14 +413,14 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(WgradBfReduceArg
     }
     if (!live || col >= a.N) return;
     if (slot == SLOTS - 1) {
-        if (lg == 0) a.out_b[col] = sum[0];
+        if (lg == 0) grad_st<ACC>(&a.out_b[col], sum[0]);
         return;
     }
     const int cbl = slot / a.KW, tap = slot - cbl * a.KW;
 #pragma unroll
     for (int r4 = 0; r4 < 4; ++r4) {
         const int c = (mg * a.NCB + cbl) * 16 + lg * 4 + r4;
-        if (c < a.Ctot) a.out_w[((long long)tap * a.Ctot + c) * a.N + col] = sum[r4];
+        if (c < a.Ctot) grad_st<ACC>(&a.out_w[((long long)tap * a.Ctot + c) * a.N + col], sum[r4]);
     }
 }
 
@@ -482,16 +484,18 @@ static hipError_t wgrad_bf16_launch_t(WgradArgs a, const WgradBfGeom& g, hipStre
     if (g.lds > 160 * 1024 || (size_t)(NW * 16) * g.ZPe > 65535 || g.XW4 >= (1 << 20)) return hipErrorInvalidValue;
     if ((size_t)g.NCB * (a.loader == LOADER_DEINT ? 2 : 1) * g.XROWS * 16 + 80 > 65535) return hipErrorInvalidValue;   // 16-bit LDS destinations
     if ((long long)8 * g.NCB * g.XW4 > (long long)WUN_WGB_XITP * 256) return hipErrorInvalidValue;
-    auto kern = wgrad_bf16_kernel<MTW, NW>;
-    static size_t lds_allowed = 64 * 1024;
-    if (g.lds > lds_allowed) {
+    const bool acc = a.accum && a.direct;           // (split launches write partials: the plain kernel)
+    auto kern = acc ? wgrad_bf16_kernel<MTW, NW, true> : wgrad_bf16_kernel<MTW, NW>;
+    static size_t lds_allowed[2] = {64 * 1024, 64 * 1024};
+    size_t& allowed = lds_allowed[acc ? 1 : 0];
+    if (g.lds > allowed) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
         if (e != hipSuccess) return e;
-        lds_allowed = g.lds;
+        allowed = g.lds;
     }
     const long long grid = (long long)g.nMG * g.nNG * a.nsplit;
     char nm[64], tag[160];
-    snprintf(nm, sizeof(nm), "wgrad_bf16_kernel<%d, %d>", MTW, NW);
+    snprintf(nm, sizeof(nm), acc ? "wgrad_bf16_acc_kernel<%d, %d>" : "wgrad_bf16_kernel<%d, %d>", MTW, NW);
     snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nsplit=%d grid=%lld", a.C0 + a.C1, a.N, a.Tq, a.KW, a.loader, a.B,
              a.nsplit, grid);
     prof_scope_begin(nm, 2.0 * a.KW * (double)(a.C0 + a.C1) * a.N * (double)a.Tq * a.B, s, tag);
@@ -526,6 +530,12 @@ hipError_t launch_wgrad_bf16_reduce(const WgradArgs& a, const float* partial, in
     const int sl = (nsplit >= 64 && slots < (1 << 16)) ? 16 : (nsplit >= 8 && slots < (1 << 18) ? 4 : 1);
     const int vpb = 256 / sl;
     const long long blocks = (slots + vpb - 1) / vpb;
+    if (a.accum) {
+        if (sl == 16) hipLaunchKernelGGL((wgrad_bf16_reduce_kernel<16, true>), dim3((unsigned)blocks), dim3(256), 0, s, r);
+        else if (sl == 4) hipLaunchKernelGGL((wgrad_bf16_reduce_kernel<4, true>), dim3((unsigned)blocks), dim3(256), 0, s, r);
+        else hipLaunchKernelGGL((wgrad_bf16_reduce_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, r);
+        return hipGetLastError();
+    }
     if (sl == 16) hipLaunchKernelGGL(wgrad_bf16_reduce_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, r);
     else if (sl == 4) hipLaunchKernelGGL(wgrad_bf16_reduce_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, r);
     else hipLaunchKernelGGL(wgrad_bf16_reduce_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, r);

@@ -85,7 +85,8 @@ struct WinTaps5 { static constexpr int JR = 1, NK = 5; static constexpr int k(in
 
 // K15 = true: 15-tap scheme (G = 2 tap groups, 8 channels per row tile, 3 row tiles + the tap split above);
 // K15 = false: 5-tap scheme (16 channels per row tile, 4 row tiles).  NA = accumulator tiles per column tile and wave.
-template <bool K15, int NW, int S>
+// ACC: the store adds to the gradient arena (single-split launches of wun_*backward_accumulate only)
+template <bool K15, int NW, int S, bool ACC = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu((K15 ? NW <= 2 : NW <= 4) ? 3 : 2))) void wgrad_win_kernel(WgradArgs a, WinParams p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int G = K15 ? 2 : 1;
@@ -447,7 +448,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu((K15 ? NW <
                     if (n0 + n * 16 + li < a.N && c < Ctot) {
 #pragma unroll
                         for (int kk = 0; kk < NK; ++kk)
-                            if (tg + TP::k(kk) < a.KW) rowp[n * 16 + (long long)TP::k(kk) * tstride] = acc[j * NK + kk][n][r];
+                            if (tg + TP::k(kk) < a.KW) grad_st<ACC>(&rowp[n * 16 + (long long)TP::k(kk) * tstride], acc[j * NK + kk][n][r]);
                     }
                 }
             }
@@ -473,7 +474,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu((K15 ? NW <
                     if (col < a.N) {
                         const f32x4 v = acc[KB][n];
                         const int rr = brow & 3;
-                        outp[boff + col] = rr == 0 ? v[0] : rr == 1 ? v[1] : rr == 2 ? v[2] : v[3];
+                        const float bv = rr == 0 ? v[0] : rr == 1 ? v[1] : rr == 2 ? v[2] : v[3];
+                        grad_st<ACC>(&outp[boff + col], bv);
                     }
                 }
             }
@@ -484,7 +486,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu((K15 ? NW <
 // out[i] = sum over splits of partial[s][i] (i over the final [K][Cin][Cout] + bias block): SL split lanes per element,
 // each summing its splits {sl, sl + SL, ...} in order into one accumulator per residue class mod 4, then a fixed binary
 // tree over the 4 * SL partial sums: deterministic, and the error grows like the tree depth rather than the split count
-template <int SL>
+template <int SL, bool ACC = false>
 __global__ __launch_bounds__(256) void wgrad_win_reduce_kernel(const float* __restrict__ partial, float* __restrict__ out_w,
                                                                float* __restrict__ out_b, long long nw, long long n,
                                                                long long pstride, int nsplit) {
@@ -524,13 +526,20 @@ __global__ __launch_bounds__(256) void wgrad_win_reduce_kernel(const float* __re
     if (v >= n4) return;
     const long long e0 = 4 * v;
     if (e0 + 3 < nw && (reinterpret_cast<uintptr_t>(out_w) & 15) == 0) {
-        reinterpret_cast<f32x4*>(out_w)[v] = sum;
+        f32x4* o = reinterpret_cast<f32x4*>(out_w) + v;
+        if constexpr (ACC) {
+            const f32x4 old = *o;
+            *o = (f32x4){grad_acc_add(old[0], sum[0]), grad_acc_add(old[1], sum[1]), grad_acc_add(old[2], sum[2]),
+                         grad_acc_add(old[3], sum[3])};
+        } else {
+            *o = sum;
+        }
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const long long e = e0 + k;
-            if (e < nw) out_w[e] = sum[k];
-            else if (e < n) out_b[e - nw] = sum[k];
+            if (e < nw) grad_st<ACC>(&out_w[e], sum[k]);
+            else if (e < n) grad_st<ACC>(&out_b[e - nw], sum[k]);
         }
     }
 }
@@ -647,16 +656,19 @@ static hipError_t win_launch_t(WgradArgs a, const WinGeom& g, hipStream_t s, boo
     a.nQT = (a.Tq + g.p.TK - 1) / g.p.TK;
     const long long units = (long long)a.B * a.nQT;
     a.units_per_split = (int)((units + a.nsplit - 1) / a.nsplit);
-    auto kern = wgrad_win_kernel<K15, NW, S>;
-    static size_t lds_allowed = 64 * 1024;
-    if (g.lds > lds_allowed) {
+    // (only a single-split launch stores the final values: a split launch of an accumulating call is the plain kernel)
+    const bool acc = a.accum && a.direct;
+    auto kern = acc ? wgrad_win_kernel<K15, NW, S, true> : wgrad_win_kernel<K15, NW, S>;
+    static size_t lds_allowed[2] = {64 * 1024, 64 * 1024};
+    size_t& allowed = lds_allowed[acc ? 1 : 0];
+    if (g.lds > allowed) {
         hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
         if (e != hipSuccess) return e;
-        lds_allowed = g.lds;
+        allowed = g.lds;
     }
     const long long grid = (long long)g.p.nMG * g.p.nNG * a.nsplit;
     char nm[64];
-    snprintf(nm, sizeof(nm), "wgrad_win_kernel<%d, %d, %d>", K15 ? 15 : 5, NW, S);
+    snprintf(nm, sizeof(nm), acc ? "wgrad_win_acc_kernel<%d, %d, %d>" : "wgrad_win_kernel<%d, %d, %d>", K15 ? 15 : 5, NW, S);
     char tag[200];
     int occ = -1;
     if (occ_log) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, g.threads, g.lds);
@@ -692,11 +704,15 @@ hipError_t launch_wgrad_win_reduce(const WgradArgs& a, const float* partial, int
     const long long n4 = (n + 3) / 4;
     char tag[96];
     snprintf(tag, sizeof(tag), "bytes=%lld nsplit=%d", (long long)(nsplit + 1) * n * 4, nsplit);
-    prof_scope_begin("wgrad_win_reduce_kernel", 0.0, s, tag, (double)(nsplit + 1) * (double)n * 4.0);
+    prof_scope_begin(a.accum ? "wgrad_win_reduce_acc_kernel" : "wgrad_win_reduce_kernel", 0.0, s, tag, (double)(nsplit + 1) * (double)n * 4.0);
     const int sl = nsplit >= 128 ? 16 : (nsplit >= 16 ? 4 : 1);
     const int vpb = 256 / sl;
     const long long blocks = (n4 + vpb - 1) / vpb;
-    if (sl == 16) hipLaunchKernelGGL(wgrad_win_reduce_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, partial, out_w, out_b, nw, n, g.p.pstride, nsplit);
+    if (a.accum) {
+        if (sl == 16) hipLaunchKernelGGL((wgrad_win_reduce_kernel<16, true>), dim3((unsigned)blocks), dim3(256), 0, s, partial, out_w, out_b, nw, n, g.p.pstride, nsplit);
+        else if (sl == 4) hipLaunchKernelGGL((wgrad_win_reduce_kernel<4, true>), dim3((unsigned)blocks), dim3(256), 0, s, partial, out_w, out_b, nw, n, g.p.pstride, nsplit);
+        else hipLaunchKernelGGL((wgrad_win_reduce_kernel<1, true>), dim3((unsigned)blocks), dim3(256), 0, s, partial, out_w, out_b, nw, n, g.p.pstride, nsplit);
+    } else if (sl == 16) hipLaunchKernelGGL(wgrad_win_reduce_kernel<16>, dim3((unsigned)blocks), dim3(256), 0, s, partial, out_w, out_b, nw, n, g.p.pstride, nsplit);
     else if (sl == 4) hipLaunchKernelGGL(wgrad_win_reduce_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, partial, out_w, out_b, nw, n, g.p.pstride, nsplit);
     else hipLaunchKernelGGL(wgrad_win_reduce_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, partial, out_w, out_b, nw, n, g.p.pstride, nsplit);
     prof_scope_end(s);

@@ -248,7 +248,7 @@ class UnetAudioSeparator(object):
             return None, 0
         return mask.ctypes.data_as(C.POINTER(C.c_uint8)), int(mask.size)
 
-    def loss_and_gradients(self, targets, bucket_starts=None, bucket_events=None, variables=None):
+    def loss_and_gradients(self, targets, bucket_starts=None, bucket_events=None, variables=None, accumulate=False):
         """MSE loss averaged over sources (Training.py:50-63) and its gradient w.r.t. every
         separator variable.  targets: dict source_name -> [B, Tout, C] or a stacked
         [S, B, Tout, C] tensor.  Must follow get_output(training=True).  Returns the loss as
@@ -259,7 +259,10 @@ class UnetAudioSeparator(object):
         at offsets >= bucket_starts[k] are final (see include/wun.h, wun_loss_backward_ex).
 
         variables: TF variable names whose gradients are wanted (None = all).  The others' floats in self.grads are not
-        written, and launches no selected gradient needs are skipped (wun_loss_backward_select)."""
+        written, and launches no selected gradient needs are skipped (wun_loss_backward_select).
+
+        accumulate: ADD the gradients to what self.grads holds (wun_loss_backward_accumulate: one fp32 add per float, the
+        loss is still written) -- k micro-batches per optimizer step."""
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
@@ -276,7 +279,12 @@ class UnetAudioSeparator(object):
         nb = len(bucket_starts) if bucket_starts else 0
         starts = (C.c_int64 * max(nb, 1))(*([int(x) for x in bucket_starts] if nb else [0]))
         events = (C.c_void_p * max(nb, 1))(*([int(e.cuda_event) for e in bucket_events] if nb else [0]))
-        if mask is None:
+        if accumulate:
+            _lib.check(self._lib.wun_loss_backward_accumulate(
+                self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
+                self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
+                self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb, *self._mask_arg(mask)))
+        elif mask is None:
             _lib.check(self._lib.wun_loss_backward_ex(
                 self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
                 self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
@@ -302,27 +310,36 @@ class UnetAudioSeparator(object):
             raise ValueError("%s shape %s != outputs shape %s" % (what, tuple(x.shape), tuple(outs.shape)))
         return x
 
-    def backward(self, d_outputs, input_grad=False, bucket_starts=None, bucket_events=None, variables=None):
+    def backward(self, d_outputs, input_grad=False, bucket_starts=None, bucket_events=None, variables=None, accumulate=False):
         """Backward pass of the last get_output(training=True) from an arbitrary upstream gradient (wun_backward): what
         tf.gradients gives the reference for any loss built on the outputs.  d_outputs: dL/d outputs, as the targets of
         loss_and_gradients (dict source_name -> [B, Tout, C] or a stacked [S, B, Tout, C] tensor).  The parameter gradients
         are written to self.grads (overwritten, as loss_and_gradients does); returns dL/d mix [B, Tin, C] when input_grad,
         else None.  bucket_starts / bucket_events: as for loss_and_gradients.  variables: TF variable names whose gradients
         are wanted (None = all; the others' floats in self.grads are not written); variables=[] with input_grad=True is the
-        input-only gradient (wun_backward_select)."""
+        input-only gradient (wun_backward_select).  accumulate: ADD the parameter gradients to self.grads
+        (wun_backward_accumulate); dL/d mix is still written."""
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
         dout = self._stacked(d_outputs, "d_outputs")
         d_mix = torch.empty(tuple(self._last_mix.shape), dtype=torch.float32, device=self._dev()) if input_grad else None
         self._run_backward(self._ws[self._last_key], self._outs[self._last_key], dout, self.grads, d_mix,
-                           bucket_starts, bucket_events, mask)
+                           bucket_starts, bucket_events, mask, accumulate)
         return d_mix
 
-    def _run_backward(self, ws, outs, dout, grads, d_mix, bucket_starts=None, bucket_events=None, mask=None):
+    def _run_backward(self, ws, outs, dout, grads, d_mix, bucket_starts=None, bucket_events=None, mask=None,
+                      accumulate=False):
         nb = len(bucket_starts) if bucket_starts else 0
         starts = (C.c_int64 * max(nb, 1))(*([int(x) for x in bucket_starts] if nb else [0]))
         events = (C.c_void_p * max(nb, 1))(*([int(e.cuda_event) for e in bucket_events] if nb else [0]))
+        if accumulate:
+            gp = grads.data_ptr() if (grads is not None and (mask is None or mask.any())) else None
+            _lib.check(self._lib.wun_backward_accumulate(
+                self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
+                gp, d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb,
+                *self._mask_arg(mask)))
+            return
         if mask is None:
             _lib.check(self._lib.wun_backward_ex(
                 self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),

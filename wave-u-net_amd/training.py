@@ -44,9 +44,14 @@ def synthetic_source(model_config, batch, t_in, t_out, device, seed=1337):
 
 
 class Trainer(object):
-    """One process per GPU.  step() = sess.run([separator_solver, ...]) of Training.py:105."""
+    """One process per GPU.  step() = sess.run([separator_solver, ...]) of Training.py:105.
 
-    def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0):
+    grad_accum_steps = k (or model_config["grad_accum_steps"], default 1): each step runs k micro-batches of batch / k
+    excerpts on a plan built for that size, the first overwriting the gradient arena and the rest adding to it
+    (wun_loss_backward_accumulate), then one all-reduce and one Adam update on the summed gradient scaled by 1 / k.
+    `batch` stays the per-rank batch of one optimizer step."""
+
+    def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0, grad_accum_steps=None):
         self.rank, self.local_rank, self.world = init_distributed()
         # Scheduling hint of the plan (include/wun.h): low-priority side streams only when no collective shares the
         # device -- with a process group initialised (multi-GPU, or bench.py --force-allreduce) they must stay normal.
@@ -60,9 +65,14 @@ class Trainer(object):
         torch.cuda.set_device(self.device)
         self.sep = UnetAudioSeparator(model_config, device=self.device, seed=seed)
         self.batch = batch_size or model_config["batch_size"]
+        k = grad_accum_steps if grad_accum_steps is not None else model_config.get("grad_accum_steps", 1)
+        self.accum = int(k)
+        if self.accum < 1 or self.batch % self.accum:
+            raise ValueError("grad_accum_steps = %r must be >= 1 and divide the batch (%d)" % (k, self.batch))
+        self.micro = self.batch // self.accum
         in_shape, out_shape = self.sep.get_padding(np.array([self.batch, model_config["num_frames"], 0]))
         self.t_in, self.t_out = int(in_shape[1]), int(out_shape[1])
-        plan = self.sep._plan(self.batch, self.t_in)
+        plan = self.sep._plan(self.micro, self.t_in)
         self.sep._active = plan
         self.sep._ensure_variables(plan)
         broadcast_parameters(self.sep.params)
@@ -88,6 +98,8 @@ class Trainer(object):
         if os.environ.get("WUN_NO_TUNE") is not None:
             return
         cache = os.environ.get("WUN_TUNE_CACHE")
+        if self.accum > 1:                                # the plan runs micro-batches: tune on the first one
+            mix, targets = self._micro_batch(mix, targets, 0)
         self.sep.get_output(mix, True)                    # makes this (batch, length) plan the active one
         table, source = None, None
         if self.rank == 0:
@@ -119,7 +131,16 @@ class Trainer(object):
                 self.sep.tune_import(box[0])
         self.tune_table, self.tune_source = box[0], box[1]
 
+    def _micro_batch(self, mix, targets, i):
+        """Micro-batch i of a step's batch: excerpts [i b, (i + 1) b) -- dim 0 of mix, dim 1 of stacked targets."""
+        lo, hi = i * self.micro, (i + 1) * self.micro
+        if isinstance(targets, dict):
+            return mix[lo:hi], {n: t[lo:hi] for n, t in targets.items()}
+        return mix[lo:hi], targets[:, lo:hi]
+
     def step(self, mix, targets):
+        if self.accum > 1:
+            return self._accumulated_step(mix, targets)
         self.sep.get_output(mix, True)
         if self.overlap:
             # bucket events are recorded by the backward pass; the all-reduces wait on them
@@ -131,6 +152,29 @@ class Trainer(object):
             self.reducer.all_reduce(self.sep.grads)
         self.sep.adam_step(self.lr, grad_scale=self.reducer.grad_scale)
         return loss
+
+    def _accumulated_step(self, mix, targets):
+        """k micro-batches, one optimizer step.  Only the last backward pass records the bucket events: an event then means
+        "the SUM is final" and the overlapped all-reduce starts early as in the one-batch step.  Returns the mean of the
+        micro-batch losses (0-dim GPU tensor, no host sync)."""
+        if mix.shape[0] != self.batch:
+            raise ValueError("step takes the whole batch: %d excerpts, got %d" % (self.batch, mix.shape[0]))
+        k = self.accum
+        losses = []
+        for i in range(k):
+            m, t = self._micro_batch(mix, targets, i)
+            self.sep.get_output(m, True)
+            if self.overlap and i == k - 1:
+                losses.append(self.sep.loss_and_gradients(t, *self.reducer.begin(), accumulate=i > 0))
+            else:
+                losses.append(self.sep.loss_and_gradients(t, accumulate=i > 0))
+        if self.overlap:
+            self.reducer.launch(self.sep.grads)
+            self.reducer.finish()
+        else:
+            self.reducer.all_reduce(self.sep.grads)
+        self.sep.adam_step(self.lr, grad_scale=self.reducer.grad_scale / k)
+        return torch.stack(losses).mean()
 
 
 def train(model_config, experiment_id, load_model=None, batch_source=None, log_every=None):
