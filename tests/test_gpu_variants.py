@@ -233,7 +233,9 @@ def test_conv_every_variant_secondary_copies(lib, case, mode):
                           copy0 and whose ODD outputs in copy1 (an up level's input gradient splitting the skip window's
                           gradient by parity): both bit-equal to the main output;
       acc_window          accumulate only inside [lo, lo + len) of the row, store elsewhere (the transposed conv that fills
-                          a gradient row which already holds the even half of the window's gradient)."""
+                          a gradient row which already holds the even half of the window's gradient); also windows of 1-2
+                          elements strictly inside a 16-byte quad of the row (lo % 4 in {1, 2}), which the vector epilogues
+                          must see as well."""
     B, Cin, Cout, K, T, same = case
     rng = np.random.default_rng(abs(hash((case, mode))) % (2 ** 31) + 11)
     x = rng.uniform(-1, 1, (B, Cin, T)).astype(np.float32)
@@ -268,12 +270,15 @@ def test_conv_every_variant_secondary_copies(lib, case, mode):
     else:
         base = rng.uniform(-1, 1, (B, Cout, t_out)).astype(np.float32)
         dbase = _cuda(base)
-        lo, ln = t_out // 3 + 1, max(2, t_out // 3)
+        windows = [(t_out // 3 + 1, max(2, t_out // 3))] + [(4 * (t_out // 8) + r, n) for r in (1, 2) for n in (1, 2)]
+        acc_flag, mask_ptr, lrelu = 1, None, 0
+    runs = []                                                             # (expected row, wun_op_set_conv_copies arguments)
+    for lo, ln in (windows if mode == "acc_window" else []):
         ref = conv.copy()
         ref[:, :, lo:lo + ln] += base[:, :, lo:lo + ln].astype(np.float64)
-        args = (None, 0, 0, 0, 0, None, 0, lo, ln)
-        acc_flag, mask_ptr, lrelu = 1, None, 0
-    scale = max(1.0, np.abs(ref).max())
+        runs.append((ref, (None, 0, 0, 0, 0, None, 0, lo, ln)))
+    if mode != "acc_window":
+        runs.append((ref, args))
 
     def launch():
         if mode == "acc_window":
@@ -293,9 +298,9 @@ def test_conv_every_variant_secondary_copies(lib, case, mode):
     def check(v, ks):
         got = y.cpu().numpy()
         assert np.isfinite(got).all(), (v, ks)
-        err = np.abs(got - ref).max() / scale
+        err = np.abs(got - ref).max() / max(1.0, np.abs(ref).max())
         worst[0] = max(worst[0], err)
-        assert err <= OP_TOL, (v, ks, err)
+        assert err <= OP_TOL, (v, ks, args, err)
         if mode == "expand_stride2":
             g0 = c0.cpu().numpy()
             exp = np.full(g0.shape, POISON, dtype=np.float32)
@@ -309,8 +314,9 @@ def test_conv_every_variant_secondary_copies(lib, case, mode):
             if no:
                 assert np.array_equal(c1.cpu().numpy()[:, :, :no], got[:, :, 1::2]), (v, ks)
 
-    ran = _sweep(lib, "copies_" + mode, launch, check)
-    assert ran >= 2
+    for ref, args in runs:
+        ran = _sweep(lib, "copies_" + mode, launch, check)
+        assert ran >= 2
     record("conv_every_variant_secondary_copies", "%s %s" % (mode, case), worst[0], OP_TOL)
 
 

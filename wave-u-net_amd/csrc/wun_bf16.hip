@@ -21,7 +21,7 @@
 // of stage s+1 stream global -> LDS (global_load_lds) and its input window is fetched into registers
 // (dword loads: two consecutive time steps of one channel), transposed to [time][8 channels] with v_perm_b32 and
 // written to the other LDS buffer afterwards; one barrier per stage.
-#include "wun_internal.h"
+#include "wun_device.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -29,30 +29,7 @@
 
 namespace wun {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// two fp32 -> packed bf16 pair, round-to-nearest-even: one v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){lo, hi}, bf16x2));
-}
-
-__device__ __forceinline__ int xcd_block(int bid, int grid) {
-    const int per = grid >> 3, rem = grid & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-}
-
 #define WUN_BF_KMAX 15         // taps
-
-// F_ACCUM applies to the row positions [lo, lo + len) only (ConvArgs.acc_lo / acc_len)
-__device__ __forceinline__ bool conv_acc_pos(int lo, unsigned len, int pos) { return (unsigned)(pos - lo) < len; }
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
 // X items (PAIRS of 16-byte slots = 8 channels of two consecutive time steps) a thread stages per stage, by tile height
 template <int MT> struct BfXit { static constexpr int v = MT == 4 ? 6 : (MT == 2 ? 4 : 3); };
@@ -103,7 +80,7 @@ __global__ __launch_bounds__(256, (MT == 4 ? 2 : (MT == 2 ? (NW <= 3 ? 3 : 2) : 
     const int lane = tid & 63;
     const int li = lane & 15, lg = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = xcd_block((int)blockIdx.x, (int)gridDim.x);
+    int bid = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x);
     const int nt = bid % nNT;
     const int seg = bid / nNT;
     // fused two-phase transposed stride-2 conv (F_PHASE2): the weight matrix has 2*N columns (phase 0 | phase 1 of the N
@@ -290,7 +267,7 @@ __global__ __launch_bounds__(256, (MT == 4 ? 2 : (MT == 2 ? (NW <= 3 ? 3 : 2) : 
     const long long e_obs0 = a.obs0, e_obs1 = a.obs1, e_decbs = a.decbs;
     const int e_op0 = a.opitch0, e_op1 = a.opitch1, e_oo0 = a.ooff0, e_oo1 = a.ooff1, e_N = a.N, e_N0 = a.N0,
               e_Tout = a.Tout, e_os = a.ostride, e_decp = a.decpitch;
-    const int e_acc_lo = a.acc_lo; const unsigned e_acc_len = a.acc_len;
+    const AccRange e_rng = {a.acc_lo, a.acc_len};
     float e_bv[NW];                                         // this lane's bias values, loaded once (a load inside the
 #pragma unroll                                              // tile loop would wait on vmcnt(0) and drain the input prefetch)
     for (int n = 0; n < NW; ++n) {
@@ -318,36 +295,13 @@ __global__ __launch_bounds__(256, (MT == 4 ? 2 : (MT == 2 ? (NW <= 3 ? 3 : 2) : 
 #pragma unroll
                         for (int r = 0; r < 4; ++r) { v[2 * r] = acc[m][n][r]; v[2 * r + 1] = acc[m][NW / 2 + n][r]; }
                         if (vec && t0 + 7 < e_Tlim) {
-                            const long long idx = rowbase + t0;
-                            if (msk != nullptr) {
-                                const f32x4 m0 = ld4<ET>(msk, idx), m1 = ld4<ET>(msk, idx + 4);
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    v[r] *= (m0[r] > 0.f) ? 1.f : 0.2f;
-                                    v[4 + r] *= (m1[r] > 0.f) ? 1.f : 0.2f;
-                                }
-                            }
-                            if (accum) {
-                                const f32x4 o0 = ld4<ET>(dst, idx), o1 = ld4<ET>(dst, idx + 4);
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    if (conv_acc_pos(e_acc_lo, e_acc_len, e_oo0 + t0 + r)) v[r] += o0[r];
-                                    if (conv_acc_pos(e_acc_lo, e_acc_len, e_oo0 + t0 + 4 + r)) v[4 + r] += o1[r];
-                                }
-                            }
-                            st4<ET>(dst, idx, (f32x4){v[0], v[1], v[2], v[3]});
-                            st4<ET>(dst, idx + 4, (f32x4){v[4], v[5], v[6], v[7]});
+                            f32x4 w[2] = {{v[0], v[1], v[2], v[3]}, {v[4], v[5], v[6], v[7]}};
+                            conv_out_vec<8>(dst, msk, rowbase + t0, accum, e_rng, e_oo0 + t0, w, NoCopy());
                         } else {
 #pragma unroll
-                            for (int r = 0; r < 8; ++r) {
-                                if (t0 + r < e_Tlim) {
-                                    const long long idx = rowbase + t0 + r;
-                                    float x = v[r];
-                                    if (msk != nullptr) x *= (ld1<ET>(msk, idx) > 0.f) ? 1.f : 0.2f;
-                                    if (accum && conv_acc_pos(e_acc_lo, e_acc_len, e_oo0 + t0 + r)) x += ld1<ET>(dst, idx);
-                                    st1<ET>(dst, idx, x);
-                                }
-                            }
+                            for (int r = 0; r < 8; ++r)
+                                if (t0 + r < e_Tlim)
+                                    conv_out1(dst, msk, rowbase + t0 + r, accum && e_rng.at(e_oo0 + t0 + r), v[r], NoCopy());
                         }
                     }
                 }
@@ -370,44 +324,29 @@ __global__ __launch_bounds__(256, (MT == 4 ? 2 : (MT == 2 ? (NW <= 3 ? 3 : 2) : 
             for (int m = 0; m < MT; ++m) {
                 const int q = q0 + wt0 + m * 16 + lg * 4;
                 if (vec && q + 3 < e_Tout) {
-                    f32x4 v = acc[m][n];
+                    f32x4 v[1] = {acc[m][n]};
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        v[r] += bvv;
-                        if (lrelu) v[r] = fmaxf(0.2f * v[r], v[r]);
+                        v[0][r] += bvv;
+                        if (lrelu) v[0][r] = fmaxf(0.2f * v[0][r], v[0][r]);
                     }
-                    const long long idx = rowbase + q;
-                    if (msk != nullptr) {
-                        const f32x4 mk = ld4<ET>(msk, idx);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] *= (mk[r] > 0.f) ? 1.f : 0.2f;
-                    }
-                    if (accum) {
-                        const f32x4 o = ld4<ET>(dst, idx);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r)
-                            if (conv_acc_pos(e_acc_lo, e_acc_len, oo + q + r)) v[r] += o[r];
-                    }
-                    st4<ET>(dst, idx, v);
-                    if (decrow != nullptr) {
+                    conv_out_vec<4>(dst, msk, rowbase + q, accum, e_rng, oo + q, v, [&](const f32x4* x) {
+                        if (decrow == nullptr) return;
                         if constexpr (OB) {
-                            *reinterpret_cast<unsigned*>(decrow + (q >> 1)) = bf_pack2(v[0], v[2]);
+                            *reinterpret_cast<unsigned*>(decrow + (q >> 1)) = bf_pack2(x[0][0], x[0][2]);
                         } else {
-                            decrow[q >> 1] = v[0];
-                            decrow[(q >> 1) + 1] = v[2];
+                            decrow[q >> 1] = x[0][0];
+                            decrow[(q >> 1) + 1] = x[0][2];
                         }
-                    }
+                    });
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (q + r < e_Tout) {
                             float v = acc[m][n][r] + bvv;
                             if (lrelu) v = fmaxf(0.2f * v, v);
-                            const long long idx = rowbase + (long long)(q + r) * e_os;
-                            if (msk != nullptr) v *= (ld1<ET>(msk, idx) > 0.f) ? 1.f : 0.2f;
-                            if (accum && conv_acc_pos(e_acc_lo, e_acc_len, oo + (q + r) * e_os)) v += ld1<ET>(dst, idx);
-                            st1<ET>(dst, idx, v);
-                            if (decrow != nullptr && ((q + r) & 1) == 0) st1<ET>(decrow, (q + r) >> 1, v);
+                            conv_out1(dst, msk, rowbase + (long long)(q + r) * e_os, accum && e_rng.at(oo + (q + r) * e_os), v,
+                                      [&](float x) { if (decrow != nullptr && ((q + r) & 1) == 0) st1<ET>(decrow, (q + r) >> 1, x); });
                         }
                     }
                 }
@@ -463,7 +402,6 @@ bool conv_bf16_supported(const ConvArgs& a) {
     return true;
 }
 
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static inline int bf16_rows(const ConvArgs& a, int TT) {
     return a.loader == LOADER_DEINT ? TT + (a.KW + 1) / 2 : TT + a.KW - 1;
@@ -583,15 +521,10 @@ int conv_bf16_list_candidates(const ConvArgs& a, ConvChoice* out, int maxn) {
 // a.W must point at the packed bf16 image of the layer's weights (pack_bf16_kernel), a.wb_c8p / a.wb_npad set
 hipError_t launch_conv_bf16(const ConvArgs& a_in, hipStream_t s, const WunSwitches& sw) {
     ConvArgs a = a_in;
-    if (!a.xbf || !conv_bf16_supported(a) || a.wb_c8p <= 0 || a.wb_npad <= 0 || !al16(a.W)) return hipErrorInvalidValue;
-    if (!al16(a.src0) || (a.src1 != nullptr && !al16(a.src1))) return hipErrorInvalidValue;      // dword pairs at even row elements
-    if (a.acc_len == 0) { a.acc_lo = 0; a.acc_len = 0x7FFFFFFFu; }                               // F_ACCUM over the whole row (default)
-    bool vec = a.ostride == 1 && al16(a.dst0) && (a.obs0 & 3) == 0 && (a.opitch0 & 3) == 0 && (a.ooff0 & 3) == 0;
-    if (a.dst1 != nullptr) vec = vec && al16(a.dst1) && (a.obs1 & 3) == 0 && (a.opitch1 & 3) == 0 && (a.ooff1 & 3) == 0;
-    if (a.msk0 != nullptr) vec = vec && al16(a.msk0);
-    if (a.msk1 != nullptr) vec = vec && al16(a.msk1);
-    if (a.dec != nullptr) vec = vec && (a.decpitch & 1) == 0 && (a.decbs & 1) == 0 && al16(a.dec);
-    if (vec) a.flags |= F_VEC4;
+    if (!a.xbf || !conv_bf16_supported(a) || a.wb_c8p <= 0 || a.wb_npad <= 0 || !aligned16(a.W)) return hipErrorInvalidValue;
+    if (!aligned16(a.src0) || (a.src1 != nullptr && !aligned16(a.src1))) return hipErrorInvalidValue;      // dword pairs at even row elements
+    conv_output_setup(a);
+    if (a.dec != nullptr && !aligned16(a.dec)) a.flags &= ~F_VEC4;      // (the bf16 copy stores its pairs as dwords)
     // autotuned choice (ConvChoice.variant = kBf16VariantBase + tile code; checked by conv_bf16_choice_ok)
     if (a.force_variant > kBf16VariantBase) {
         const int code = a.force_variant - 1 - kBf16VariantBase;
@@ -732,7 +665,7 @@ __global__ __launch_bounds__(256) void first_conv_kernel(ConvArgs a) {
 bool first_conv_supported(const ConvArgs& a) {
     return a.C1 == 0 && (a.C0 == 1 || a.C0 == 2) && a.KW >= 1 && a.KW <= WUN_BF_KMAX && !a.xbf && a.ostride == 1 &&
            a.dst1 == nullptr && a.msk0 == nullptr && (a.flags & (F_ACCUM | F_PHASE2)) == 0 && a.N0 == a.N && a.B <= 65535 &&
-           (a.opitch0 & 3) == 0 && (a.obs0 & 3) == 0 && (a.ooff0 & 3) == 0 && al16(a.dst0);
+           (a.opitch0 & 3) == 0 && (a.obs0 & 3) == 0 && (a.ooff0 & 3) == 0 && aligned16(a.dst0);
 }
 
 hipError_t launch_first_conv(const ConvArgs& a, hipStream_t s) {
@@ -811,7 +744,7 @@ __global__ __launch_bounds__(256) void pack_bf16_kernel(const float* __restrict_
             const int c = c8 * 8 + e;
             v[e] = (c < d.C && n < d.N) ? src[((long long)k * d.C + c) * d.N + n] : 0.f;
         }
-        u32x4 pk = {pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+        u32x4 pk = {bf_pack2(v[0], v[1]), bf_pack2(v[2], v[3]), bf_pack2(v[4], v[5]), bf_pack2(v[6], v[7])};
         *reinterpret_cast<u32x4*>(dst + i * 8) = pk;
     }
 }
@@ -833,8 +766,8 @@ __global__ void mfma_bf16_probe_kernel(const float* a, const float* b, float* d)
     const int li = lane & 15, lg = lane >> 4;
     float av[8], bv[8];
     for (int e = 0; e < 8; ++e) { av[e] = a[li * 32 + lg * 8 + e]; bv[e] = b[(lg * 8 + e) * 16 + li]; }
-    u32x4 ap = {pack2(av[0], av[1]), pack2(av[2], av[3]), pack2(av[4], av[5]), pack2(av[6], av[7])};
-    u32x4 bp = {pack2(bv[0], bv[1]), pack2(bv[2], bv[3]), pack2(bv[4], bv[5]), pack2(bv[6], bv[7])};
+    u32x4 ap = {bf_pack2(av[0], av[1]), bf_pack2(av[2], av[3]), bf_pack2(av[4], av[5]), bf_pack2(av[6], av[7])};
+    u32x4 bp = {bf_pack2(bv[0], bv[1]), bf_pack2(bv[2], bv[3]), bf_pack2(bv[4], bv[5]), bf_pack2(bv[6], bv[7])};
     f32x4 c = {0.f, 0.f, 0.f, 0.f};
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ap), __builtin_bit_cast(bf16x8, bp), c, 0, 0, 0);
     for (int r = 0; r < 4; ++r) d[(4 * lg + r) * 16 + li] = c[r];

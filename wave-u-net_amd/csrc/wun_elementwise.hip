@@ -7,14 +7,12 @@
 // NO_PK_FP32): in the bf16 mode these kernels run on CUs that bf16 MFMA kernels occupy, where packed fp32 instructions of a
 // neighbouring wave were measured to miscompute.  The exact-fp32 MFMA kernels stay in wun_kernels.hip,
 // built as before (their device code is unchanged by the split: tools/kernel_resources.sh, profiles).
-#include "wun_internal.h"
+#include "wun_device.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace wun {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 // HIP-event bracket of one launch for bench.py's per-kernel figures (the bracket list lives in wun_kernels.hip)

@@ -1,5 +1,6 @@
 // Internal: kernel argument blocks + launcher prototypes shared by the device units (wun_kernels.hip, ...) and the
-// host units (wun_plan.hip and the files of wun_plan_impl.h: plan, dispatch, step, tuner, C ABI).  gfx950 only.
+// host units (wun_plan.hip and the files of wun_plan_impl.h: plan, dispatch, step, tuner, C ABI).  Host declarations only:
+// the device helpers of the kernel units live in wun_device.h.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,7 +109,8 @@ struct ConvArgs {
     // F_ACCUM applies to the row positions pos = ooff + q*ostride with acc_lo <= pos < acc_lo + acc_len only; elsewhere
     // the result is stored.  (A down level's input gradient = transposed stride-2 conv over the whole row + the
     // skip-window conv over the crop window: the window part is computed EARLY on a side stream, the row-wide part
-    // adds it inside the window.)  acc_len == 0 is normalised by launch_conv to "the whole row".
+    // adds it inside the window.)  acc_len == 0 is normalised by conv_output_setup to "the whole row".  Every conv kernel
+    // applies msk, F_ACCUM and the copies through the one epilogue of wun_device.h (conv_out_vec / conv_out1).
     int acc_lo; unsigned acc_len;
     // Fused 2x upsampling of the dst0 output (UnetAudioSeparator.py:109-118, InterpolationLayer.py:19-39): when the launch
     // ends in the split-K epilogue kernel, that kernel also writes ups_y[b][c][0 .. ups_tup) = {y[i], interp(y[i], y[i+1])}
@@ -131,7 +133,10 @@ struct ConvArgs {
 #define WUN_NUM_RETIRED_VARIANTS 14
 // did the last launch_conv() on this thread write the fused upsampled copy?  (only split-K launches do)
 int conv_last_fused_ups();
-__host__ __device__ static inline bool conv_acc_at(const ConvArgs& a, int pos) { return (unsigned)(pos - a.acc_lo) < a.acc_len; }
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// output side of a conv launch, shared by launch_conv and launch_conv_bf16: normalises acc_len == 0 to the whole row and
+// sets F_VEC4 when every destination / mask row allows the 16-byte vector epilogue
+void conv_output_setup(ConvArgs& a);
 
 // Weight/bias gradient launch:  P[split][ (k*C + c)*N + n ] and bias row P[split][KW*C*N + n]
 //   = sum over this split's (b, q-tile) units of in[b][c][q*SI + k - shift] * dz[b][n][q]
@@ -271,50 +276,6 @@ struct WtDesc {      // mode 0: dst[j][n][c] = src[k_last - j*k_step][c][n]
     int J, C, N, k_last, k_step;
     int mode;
 };
-
-// ---- bf16 storage helpers (device): a tensor element type ET is float or bf16_t; values are converted to float on load
-// and rounded to nearest-even (v_cvt_pk_bf16_f32) on store.  ET = float compiles to the plain accesses.
-typedef unsigned short bf16_t;
-typedef float wun_f32x4 __attribute__((ext_vector_type(4)));
-typedef float wun_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned wun_u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 wun_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned bf_pack2(float lo, float hi) {       // two fp32 -> packed bf16 pair (RNE)
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((wun_f32x2){lo, hi}, wun_bf16x2));
-}
-__device__ __forceinline__ float bf_lo(unsigned v) { return __builtin_bit_cast(float, v << 16); }
-__device__ __forceinline__ float bf_hi(unsigned v) { return __builtin_bit_cast(float, v & 0xFFFF0000u); }
-template <typename ET> __device__ __forceinline__ float ld1(const ET* p, long long i);
-template <> __device__ __forceinline__ float ld1<float>(const float* p, long long i) { return p[i]; }
-template <> __device__ __forceinline__ float ld1<bf16_t>(const bf16_t* p, long long i) { return __builtin_bit_cast(float, (unsigned)p[i] << 16); }
-template <typename ET> __device__ __forceinline__ void st1(ET* p, long long i, float v);
-template <> __device__ __forceinline__ void st1<float>(float* p, long long i, float v) { p[i] = v; }
-template <> __device__ __forceinline__ void st1<bf16_t>(bf16_t* p, long long i, float v) { p[i] = (bf16_t)(bf_pack2(v, 0.f) & 0xFFFFu); }
-// four consecutive elements; p + i must be aligned to 4 elements (16 bytes fp32 / 8 bytes bf16)
-template <typename ET> __device__ __forceinline__ wun_f32x4 ld4(const ET* p, long long i);
-template <> __device__ __forceinline__ wun_f32x4 ld4<float>(const float* p, long long i) { return *reinterpret_cast<const wun_f32x4*>(p + i); }
-template <> __device__ __forceinline__ wun_f32x4 ld4<bf16_t>(const bf16_t* p, long long i) {
-    const wun_u32x2 v = *reinterpret_cast<const wun_u32x2*>(p + i);
-    return (wun_f32x4){bf_lo(v[0]), bf_hi(v[0]), bf_lo(v[1]), bf_hi(v[1])};
-}
-template <typename ET> __device__ __forceinline__ void st4(ET* p, long long i, wun_f32x4 v);
-template <> __device__ __forceinline__ void st4<float>(float* p, long long i, wun_f32x4 v) { *reinterpret_cast<wun_f32x4*>(p + i) = v; }
-template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, long long i, wun_f32x4 v) {
-    *reinterpret_cast<wun_u32x2*>(p + i) = (wun_u32x2){bf_pack2(v[0], v[1]), bf_pack2(v[2], v[3])};
-}
-
-// ---- gradient accumulation (wun_*backward_accumulate) ----
-// Every final gradient float is written once, by one lane: its accumulating form reads the old value and adds the rounded fp32
-// G the overwriting form would store -- one IEEE add, round to nearest even (torch's float32 a + b).  The pragma keeps hipcc
-// from contracting the add with the product that produced G into an FMA (that would change the bits).
-__device__ __forceinline__ float grad_acc_add(float old, float g) {
-#pragma clang fp contract(off)
-    return old + g;
-}
-template <bool ACC> __device__ __forceinline__ void grad_st(float* p, float g) {
-    if constexpr (ACC) *p = grad_acc_add(*p, g);
-    else *p = g;
-}
 
 // ---- launchers (wun_kernels.hip) ---------------------------------------------------
 size_t conv_lds_bytes(const ConvArgs& a, int variant, const WunSwitches& sw);

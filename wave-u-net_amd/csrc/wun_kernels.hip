@@ -18,7 +18,7 @@
 //
 // Wavefront = 64 lanes; one 16x16x4 MFMA takes A[i = lane&15][k = lane>>4],
 // B[k = lane>>4][j = lane&15] and returns D[i = 4*(lane>>4)+r][j = lane&15], r = 0..3.
-#include "wun_internal.h"
+#include "wun_device.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -29,8 +29,6 @@
 #include <vector>
 
 namespace wun {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -157,18 +155,7 @@ std::string prof_end() {
 // chunk c run; they are written to LDS after the barrier), weights as 16-byte loads.
 // Low-parallelism launches (deep levels: few time tiles) are split over channel chunks
 // (split-K): raw partial tiles go to a scratch buffer and conv_splitk_epilogue_kernel sums
-// them in a fixed order and applies the epilogue.
-// Workgroups are dealt round-robin to the 8 XCDs (each with its own L2).  Remap the hardware block
-// id so that every XCD works on a CONTIGUOUS range of logical tiles: the tiles that share an input
-// window (the N tiles of one time tile, neighbouring time tiles' halos; for the weight gradient all
-// (row group, column group) tiles of one split) then hit the same L2 instead of fetching the window
-// once per XCD.
-__device__ __forceinline__ int xcd_contiguous_block(int bid, int grid) {
-    const int per = grid >> 3, rem = grid & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-}
-
+// them in a fixed order and applies the epilogue.  Tiles go to the XCDs in contiguous ranges (xcd_contiguous_block).
 #define WUN_JMAX 15
 
 
@@ -232,8 +219,6 @@ __device__ __forceinline__ void conv_copy4(const ConvArgs& a, int b, int n, int 
         row[(q >> 1) + 1] = v[3];
     }
 }
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 // KG > 1 ("in-workgroup split-K", the deep levels): the workgroup is KG groups of 256 threads; group kg runs the whole
 // kernel body on its own LDS region for the channel chunks of sub-split ksg * KG + kg of the SAME output tile, the groups'
 // accumulators are summed through LDS in the fixed order ((g0 + g1) + g2) and group 0 runs the epilogue -- a launch with
@@ -736,6 +721,7 @@ __global__ __launch_bounds__(256 * KG) void conv_mfma_kernel(ConvArgs a, int nTT
         return;
     }
 
+    const AccRange rng = {a.acc_lo, a.acc_len};
     // ---- epilogue of the fused two-phase transposed stride-2 conv: tiles [0, NW/2) hold output
     // phase 0 (t = 2q), tiles [NW/2, NW) phase 1 (t = 2q+1) of the same channels, so a lane
     // owns 8 consecutive output samples ----
@@ -749,39 +735,13 @@ __global__ __launch_bounds__(256 * KG) void conv_mfma_kernel(ConvArgs a, int nTT
                 const int q = q0 + wt0 + m * 16 + lg * 4;
                 const int t0 = 2 * q;
                 if (vec2 && t0 + 7 < a.Tlim) {
-                    const long long idx = rowbase + t0;
-                    if (a.msk0 != nullptr) {
-                        const f32x4 m0 = *reinterpret_cast<const f32x4*>(&a.msk0[idx]);
-                        const f32x4 m1 = *reinterpret_cast<const f32x4*>(&a.msk0[idx + 4]);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            v[r] *= (m0[r] > 0.f) ? 1.f : 0.2f;
-                            v[4 + r] *= (m1[r] > 0.f) ? 1.f : 0.2f;
-                        }
-                    }
-                    const int pos0 = a.ooff0 + t0;
-                    if (accum2 && (conv_acc_at(a, pos0) || conv_acc_at(a, pos0 + 7))) {      // (the window is wider than 8)
-                        const f32x4 o0 = *reinterpret_cast<const f32x4*>(&a.dst0[idx]);
-                        const f32x4 o1 = *reinterpret_cast<const f32x4*>(&a.dst0[idx + 4]);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            if (conv_acc_at(a, pos0 + r)) v[r] += o0[r];
-                            if (conv_acc_at(a, pos0 + 4 + r)) v[4 + r] += o1[r];
-                        }
-                    }
-                    *reinterpret_cast<f32x4*>(&a.dst0[idx]) = (f32x4){v[0], v[1], v[2], v[3]};
-                    *reinterpret_cast<f32x4*>(&a.dst0[idx + 4]) = (f32x4){v[4], v[5], v[6], v[7]};
+                    f32x4 w[2] = {{v[0], v[1], v[2], v[3]}, {v[4], v[5], v[6], v[7]}};
+                    conv_out_vec<8>(a.dst0, a.msk0, rowbase + t0, accum2, rng, a.ooff0 + t0, w, NoCopy());
                 } else {
 #pragma unroll
-                    for (int r = 0; r < 8; ++r) {
-                        if (t0 + r < a.Tlim) {
-                            const long long idx = rowbase + t0 + r;
-                            float x = v[r];
-                            if (a.msk0 != nullptr) x *= (a.msk0[idx] > 0.f) ? 1.f : 0.2f;
-                            if (accum2 && conv_acc_at(a, a.ooff0 + t0 + r)) x += a.dst0[idx];
-                            a.dst0[idx] = x;
-                        }
-                    }
+                    for (int r = 0; r < 8; ++r)
+                        if (t0 + r < a.Tlim)
+                            conv_out1(a.dst0, a.msk0, rowbase + t0 + r, accum2 && rng.at(a.ooff0 + t0 + r), v[r], NoCopy());
                 }
             };
             if constexpr ((NW % 2) == 0) {
@@ -852,6 +812,7 @@ __global__ __launch_bounds__(256 * KG) void conv_mfma_kernel(ConvArgs a, int nTT
             dst = a.dst1; msk = a.msk1;
         }
         const bool copies = (a.dec != nullptr || a.dec1 != nullptr) && ncol < a.N0;
+        const int oo = ncol < a.N0 ? a.ooff0 : a.ooff1;
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             const int q = q0 + wt0 + m * 16 + lg * 4;
@@ -866,47 +827,28 @@ __global__ __launch_bounds__(256 * KG) void conv_mfma_kernel(ConvArgs a, int nTT
                     if (g < a.B) {
                         float v = acc[m][n][r] + bvv;
                         if (lrelu) v = fmaxf(0.2f * v, v);
-                        const long long idx = (long long)g * obs + colbase + (long long)qq * a.ostride;
-                        if (msk != nullptr) v *= (msk[idx] > 0.f) ? 1.f : 0.2f;
-                        if (accum && conv_acc_at(a, (first ? a.ooff0 : a.ooff1) + qq * a.ostride)) v += dst[idx];
-                        dst[idx] = v;
-                        if (copies) conv_copy1(a, g, ncol, qq, v);
+                        conv_out1(dst, msk, (long long)g * obs + colbase + (long long)qq * a.ostride, accum && rng.at(oo + qq * a.ostride), v,
+                                  [&](float x) { if (copies) conv_copy1(a, g, ncol, qq, x); });
                     }
                     if (++qq == a.Tout) { qq = 0; ++g; }
                 }
             } else if (vec && q + 3 < a.Tout) {
-                f32x4 v = acc[m][n];
+                f32x4 v[1] = {acc[m][n]};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    v[r] += bvv;
-                    if (lrelu) v[r] = fmaxf(0.2f * v[r], v[r]);
+                    v[0][r] += bvv;
+                    if (lrelu) v[0][r] = fmaxf(0.2f * v[0][r], v[0][r]);
                 }
-                const long long idx = rowbase + q;
-                if (msk != nullptr) {
-                    const f32x4 mk = *reinterpret_cast<const f32x4*>(&msk[idx]);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] *= (mk[r] > 0.f) ? 1.f : 0.2f;
-                }
-                const int pos0 = (ncol < a.N0 ? a.ooff0 : a.ooff1) + q;                 // vector path: ostride == 1
-                if (accum && (conv_acc_at(a, pos0) || conv_acc_at(a, pos0 + 3))) {
-                    const f32x4 old = *reinterpret_cast<const f32x4*>(&dst[idx]);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (conv_acc_at(a, pos0 + r)) v[r] += old[r];
-                }
-                *reinterpret_cast<f32x4*>(&dst[idx]) = v;
-                if (copies) conv_copy4(a, b, ncol, q, v);
+                conv_out_vec<4>(dst, msk, rowbase + q, accum, rng, oo + q, v,                  // vector path: ostride == 1
+                                [&](const f32x4* x) { if (copies) conv_copy4(a, b, ncol, q, x[0]); });
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     if (q + r < a.Tout) {
                         float v = acc[m][n][r] + bvv;
                         if (lrelu) v = fmaxf(0.2f * v, v);
-                        const long long idx = rowbase + (long long)(q + r) * a.ostride;
-                        if (msk != nullptr) v *= (msk[idx] > 0.f) ? 1.f : 0.2f;
-                        if (accum && conv_acc_at(a, (ncol < a.N0 ? a.ooff0 : a.ooff1) + (q + r) * a.ostride)) v += dst[idx];
-                        dst[idx] = v;
-                        if (copies) conv_copy1(a, b, ncol, q + r, v);
+                        conv_out1(dst, msk, rowbase + (long long)(q + r) * a.ostride, accum && rng.at(oo + (q + r) * a.ostride), v,
+                                  [&](float x) { if (copies) conv_copy1(a, b, ncol, q + r, x); });
                     }
                 }
             }
@@ -925,6 +867,7 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(ConvArgs a, i
     const bool accum = (a.flags & F_ACCUM) != 0;
     const bool vec = (a.flags & F_VEC4) != 0;
     const long long sstride = (long long)a.B * a.N * TP;        // floats between consecutive splits
+    const AccRange rng = {a.acc_lo, a.acc_len};
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
          i += (long long)gridDim.x * blockDim.x) {
         const int q = (int)(i % TP4) * 4;
@@ -941,11 +884,8 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(ConvArgs a, i
         }
         // mask / old values of the vector path are requested before the partials (independent loads)
         const bool vpath = vec && q + 3 < a.Tout;
-        f32x4 mk = {1.f, 1.f, 1.f, 1.f}, old = {0.f, 0.f, 0.f, 0.f};
-        if (vpath && msk != nullptr) mk = *reinterpret_cast<const f32x4*>(&msk[rowbase + q]);
         const int pos0 = (ncol < a.N0 ? a.ooff0 : a.ooff1) + q * a.ostride;
-        const bool acc_v = accum && (conv_acc_at(a, pos0) || conv_acc_at(a, pos0 + 3));       // vector path: ostride == 1
-        if (vpath && acc_v) old = *reinterpret_cast<const f32x4*>(&dst[rowbase + q]);
+        const ConvSide side = conv_out_side(dst, vpath ? msk : nullptr, rowbase + q, vpath && accum, rng, pos0);
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         const float* pp = a.part + bn * TP + q;
         // the loads of a batch are all in flight before the first add (a load + wait per split made this kernel
@@ -974,6 +914,7 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(ConvArgs a, i
             v[r] += bvv;
             if (lrelu) v[r] = fmaxf(0.2f * v[r], v[r]);
         }
+        const bool copies = (a.dec != nullptr || a.dec1 != nullptr) && ncol < a.N0;
         if (a.ubw_dz != nullptr && ncol >= a.N0) {
             // fused adjoint of the 2x linear upsampling (no mask / accumulate on these columns: v = d_up[q .. q+3]).
             // d_up[q-1] belongs to the previous thread: its partials are summed again here in the same order.
@@ -997,30 +938,14 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(ConvArgs a, i
                 }
             }
         } else if (vpath) {
-            const long long idx = rowbase + q;
-            if (msk != nullptr) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] *= (mk[r] > 0.f) ? 1.f : 0.2f;
-            }
-            if (acc_v) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (conv_acc_at(a, pos0 + r)) v[r] += old[r];
-            }
-            *reinterpret_cast<f32x4*>(&dst[idx]) = v;
-            if ((a.dec != nullptr || a.dec1 != nullptr) && ncol < a.N0) conv_copy4(a, b, ncol, q, v);
+            conv_out_vec(dst, msk != nullptr, rowbase + q, rng, pos0, side, &v,                  // vector path: ostride == 1
+                         [&](const f32x4* x) { if (copies) conv_copy4(a, b, ncol, q, x[0]); });
         } else {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (q + r < a.Tout) {
-                    const long long idx = rowbase + (long long)(q + r) * a.ostride;
-                    float x = v[r];
-                    if (msk != nullptr) x *= (msk[idx] > 0.f) ? 1.f : 0.2f;
-                    if (accum && conv_acc_at(a, pos0 + r * a.ostride)) x += dst[idx];
-                    dst[idx] = x;
-                    if ((a.dec != nullptr || a.dec1 != nullptr) && ncol < a.N0) conv_copy1(a, b, ncol, q + r, x);
-                }
-            }
+            for (int r = 0; r < 4; ++r)
+                if (q + r < a.Tout)
+                    conv_out1(dst, msk, rowbase + (long long)(q + r) * a.ostride, accum && rng.at(pos0 + r * a.ostride), v[r],
+                              [&](float x) { if (copies) conv_copy1(a, b, ncol, q + r, x); });
         }
         if (a.ups_y != nullptr && ncol < a.N0 && q < a.Tout) {
             // fused 2x upsampling of this row segment (forward launches: no mask, no accumulate, so v is the stored
@@ -1176,7 +1101,16 @@ long long conv_natural_wgs_phase2(const ConvArgs& a) {
 
 static inline int conv_J(const ConvArgs& a);
 // Vector (16-byte) paths need aligned bases / pitches; everything the plan allocates is.
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+void conv_output_setup(ConvArgs& a) {
+    if (a.acc_len == 0) { a.acc_lo = 0; a.acc_len = 0x7FFFFFFFu; }          // F_ACCUM over the whole row (default)
+    bool vec = a.ostride == 1 && aligned16(a.dst0) && (a.obs0 & 3) == 0 && (a.opitch0 & 3) == 0 && (a.ooff0 & 3) == 0;
+    if (a.dst1 != nullptr)
+        vec = vec && aligned16(a.dst1) && (a.obs1 & 3) == 0 && (a.opitch1 & 3) == 0 && (a.ooff1 & 3) == 0;
+    if (a.msk0 != nullptr) vec = vec && aligned16(a.msk0);
+    if (a.msk1 != nullptr) vec = vec && aligned16(a.msk1);
+    if (a.dec != nullptr) vec = vec && (a.decpitch & 1) == 0 && (a.decbs & 1) == 0;
+    if (vec) a.flags |= F_VEC4;
+}
 
 // may this launch use the DMA-staging instantiation (XVEC) of tile `variant`?
 static int conv_dma_pitch(int width) { return fit_pitch((width + 3) & ~3, 16); }
@@ -1415,7 +1349,7 @@ hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hi
     if (a.ubw_dz != nullptr && (a.dst1 == nullptr || a.msk1 != nullptr || a.ostride != 1 || a.bias != nullptr ||
                                 (a.flags & (F_ACCUM | F_PHASE2 | F_LRELU)) != 0 || a.N0 >= a.N || a.ubw_x == nullptr))
         return hipErrorInvalidValue;
-    if (a.acc_len == 0) { a.acc_lo = 0; a.acc_len = 0x7FFFFFFFu; }          // F_ACCUM over the whole row (default)
+    conv_output_setup(a);
     if (conv_J(a) > WUN_JMAX) return hipErrorInvalidValue;       // rejected at plan creation
     if (a.KW <= 0) {
         // no taps (odd output phase of a transposed stride-2 conv with filter_size 1): the conv is the
@@ -1428,14 +1362,7 @@ hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hi
         return hipGetLastError();
     }
     const bool vecw = (a.N & 3) == 0 && aligned16(a.W);
-    bool vec = a.ostride == 1 && aligned16(a.dst0) && (a.obs0 & 3) == 0 && (a.opitch0 & 3) == 0 && (a.ooff0 & 3) == 0;
-    if (a.dst1 != nullptr)
-        vec = vec && aligned16(a.dst1) && (a.obs1 & 3) == 0 && (a.opitch1 & 3) == 0 && (a.ooff1 & 3) == 0;
-    if (a.msk0 != nullptr) vec = vec && aligned16(a.msk0);
-    if (a.msk1 != nullptr) vec = vec && aligned16(a.msk1);
-    if (a.dec != nullptr) vec = vec && (a.decpitch & 1) == 0 && (a.decbs & 1) == 0;
     if ((a.flags & F_PHASE2) && !(a.ostride == 1 && a.dst1 == nullptr && vecw)) return hipErrorInvalidValue;
-    if (vec) a.flags |= F_VEC4;
     int v = (a.flags & F_PHASE2) ? conv_pick_variant_phase2(a) : conv_pick_variant(a);
     if (a.force_variant > 0 && vecw) {
         v = a.force_variant - 1;

@@ -14,14 +14,12 @@
 // lane groups of a pair are summed through LDS in a fixed order and the workgroup writes one partial
 // vector; narrow_wgrad_reduce_kernel sums the partials in split order (deterministic, no atomics) and
 // scatters to the TF layout [K][Cin][Cout] + bias of each source.
-#include "wun_internal.h"
+#include "wun_device.h"
 
 #include <cstdio>
 #include <cstdlib>
 
 namespace wun {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define WUN_NW_TQ 256            // output positions per unit
 

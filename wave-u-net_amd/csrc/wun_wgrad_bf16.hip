@@ -24,30 +24,13 @@
 // its fp32 arguments first): an item of the input stage is (channel pair, 4 positions) = two 8-byte loads, transposed to
 // four (position, channel pair) dwords with v_perm_b32; a dz item is one 8-byte load written to LDS as it is.  Staging
 // writes are rotated per position group so that the 32-byte rows of 4 neighbouring groups land on different banks.
-#include "wun_internal.h"
+#include "wun_device.h"
 
 #include <cstdio>
 
 namespace wun {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-typedef __bf16 wb_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wb_f32x2 __attribute__((ext_vector_type(2)));
-// two fp32 -> packed bf16 pair, round-to-nearest-even: one v_cvt_pk_bf16_f32
-__device__ __forceinline__ unsigned wb_pack2(float lo, float hi) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector((wb_f32x2){lo, hi}, wb_bf16x2));
-}
-
-__device__ __forceinline__ int wb_xcd_block(int bid, int grid) {
-    const int per = grid >> 3, rem = grid & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
-}
 
 // 4 positions x 16 channels block -> the 4 positions of this lane's channel (see the header)
 __device__ __forceinline__ u32x2 wb_tr_read(const unsigned short* p) {
@@ -79,7 +62,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(WgradArgs a, WgBfK g) {
     const int lane = tid & 63;
     const int li = lane & 15, lg = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = wb_xcd_block((int)blockIdx.x, (int)gridDim.x);
+    int bid = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x);
     const int ng = bid % g.nNG; bid /= g.nNG;
     const int mg = bid % g.nMG;
     const int split = bid / g.nMG;

@@ -24,17 +24,13 @@
 //  * the bias gradient rides in a dead MFMA row (tap 15 of a 15-tap filter / a channel past Cin): its A operand is 1.
 //  * split partials are written in the FINAL layout ([K][Cin][Cout] + bias) and summed by a flat, fixed-order pairwise
 //    reduction; both parts of a down level (decimated + window positions) share it whatever their tiles.
-#include "wun_internal.h"
+#include "wun_device.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
 namespace wun {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_cvoid_t;
 
 // wave-uniform values the compiler cannot prove uniform -> SGPRs (inline-asm "s" operands)
 __device__ __forceinline__ unsigned win_sgpr(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
@@ -52,12 +48,6 @@ __device__ __forceinline__ const float* win_sgpr_ptr(const float* q) {
 //  instructions in this file, none without a fresh M0 write.)
 __device__ __forceinline__ void win_dma16(unsigned m0v, unsigned voff, const float* sbase) {
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" :: "s"(m0v), "v"(voff), "s"(sbase) : "memory");
-}
-
-__device__ __forceinline__ int win_xcd_block(int bid, int grid) {
-    const int per = grid >> 3, rem = grid & 7;
-    const int xcd = bid & 7, idx = bid >> 3;
-    return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
 }
 
 // granules (16 bytes) a thread may stage per unit: X rows x live granules + dz rows x TK/4 over 64 W threads
@@ -101,7 +91,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu((K15 ? NW <
     const int rt = wave & 3, cg = wave >> 2;            // K15: rt == 3 is the wave of taps 4-5 over the three row tiles
     const bool roleB = K15 && rt == 3;
 
-    int bid = win_xcd_block((int)blockIdx.x, (int)gridDim.x);
+    int bid = xcd_contiguous_block((int)blockIdx.x, (int)gridDim.x);
     const int ng = bid % p.nNG; bid /= p.nNG;
     const int mg = bid % p.nMG;
     const int split = bid / p.nMG;
