@@ -308,6 +308,44 @@ int wun_adam_step_select(const wun_plan* plan, float* params, const float* grads
                          int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
                          void* stream, const uint8_t* select, int64_t nselect);
 
+/* ---- global gradient norm, clipping, non-finite step skipping ---------------------------
+ * Floats of the norm workspace (device, caller-owned, 8-byte aligned): [0, num_tensors) the per-tensor norms,
+ * [num_tensors] the global norm, then float64 partial sums (one per chunk of at most 8192 floats of one tensor).
+ * Negative (WUN_ERR_INVALID) for a null plan. */
+int64_t wun_grad_norm_workspace_floats(const wun_plan* plan);
+
+/* Global / per-tensor L2 norms of grad_scale * grads over the selected tensors (tf.clip_by_global_norm's global_norm):
+ *   norm_ws[k]           = |grad_scale| * sqrt(sum of grads^2 over tensor k)  (0 for an unselected tensor)
+ *   norm_ws[num_tensors] = |grad_scale| * sqrt(sum over the selected tensors)
+ * Squares and sums in float64, each norm rounded once to fp32.  No atomics: the result is bitwise reproducible and does
+ * not depend on the grid; a selected tensor's entry is bit-identical whatever else is selected.  Only the selected
+ * tensors' floats are read (padding floats and unselected tensors may hold anything, NaN included).
+ * select / nselect as wun_adam_step_select (any subset; NULL = every tensor).  grads is read in stream order on `stream`
+ * (after a data-parallel all-reduce: once `stream` has waited for it, as for wun_adam_step).  No host synchronisation.
+ * WUN_ERR_INVALID before any GPU work for a null plan / grads / norm_ws, a misaligned norm_ws or a bad nselect. */
+int wun_grad_norm(const wun_plan* plan, const float* grads, float grad_scale, float* norm_ws,
+                  void* stream, const uint8_t* select, int64_t nselect);
+
+#define WUN_CLIP_SKIP_NONFINITE 1
+/* wun_grad_norm into norm_ws, then TF-Adam (wun_adam_step / wun_adam_step_select) on the clipped gradient, the global
+ * norm N read on the device (the host never sees it):
+ *   g := grad_scale * grad;  if (N > clip_norm) g := g * (clip_norm / N);  then wun_adam_step's m, v, theta.
+ * With no clipping (N <= clip_norm, or clip_norm = +INFINITY) params, m and v are BIT-EQUAL to wun_adam_step /
+ * wun_adam_step_select.  tf.clip_by_global_norm scales by clip_norm * min(1/N, 1/clip_norm), which is not exactly 1 when
+ * inactive; the scale here, clip_norm / N, is rounded once and may differ from TF's by 1 ulp when clipping.
+ * flags & WUN_CLIP_SKIP_NONFINITE: when N is not finite (an inf / NaN in a selected gradient), params, m and v are not
+ * written and the device int64 *skipped is incremented by one.  Without that flag skipped may be NULL and a non-finite N
+ * flows into the update as TF's would.
+ * step: the caller's global_step, counted per call as TF counts sess.run -- a skipped step still advances it, so the next
+ * applied update uses lr_t of the caller's step, not that of the number of updates applied (no device step counter).
+ * WUN_ERR_INVALID before any GPU work for a null plan / params / grads / m / v / norm_ws, a misaligned norm_ws,
+ * clip_norm <= 0 or NaN, step < 1, unknown flags, a bad nselect, or a null skipped with WUN_CLIP_SKIP_NONFINITE.
+ * Both compute modes (the arenas are fp32 in both).  No host synchronisation, no allocation. */
+int wun_adam_step_clip(const wun_plan* plan, float* params, const float* grads, float* m, float* v,
+                       int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                       float clip_norm, int32_t flags, float* norm_ws, int64_t* skipped,
+                       void* stream, const uint8_t* select, int64_t nselect);
+
 /* ---- single operators (used by the parity tests and for per-kernel profiling) ---------- */
 
 /* y[b][co][q] = act(bias[co] + sum_{k,ci} w[k][ci][co] * x[b][ci][q*stride + k - pad_left]),

@@ -61,6 +61,10 @@ _SIGS = {
                                 C.c_float, C.c_float, _P]),
     "wun_adam_step_select": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float,
                                        C.c_float, C.c_float, _P, C.POINTER(C.c_uint8), C.c_int64]),
+    "wun_grad_norm_workspace_floats": (C.c_int64, [_P]),
+    "wun_grad_norm": (C.c_int, [_P, _P, C.c_float, _P, _P, C.POINTER(C.c_uint8), C.c_int64]),
+    "wun_adam_step_clip": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                     C.c_float, C.c_int32, _P, _P, _P, C.POINTER(C.c_uint8), C.c_int64]),
     "wun_op_conv1d": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     "wun_op_conv1d_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
     "wun_op_conv1d_wgrad": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
@@ -87,6 +91,7 @@ _SIGS = {
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
+WUN_CLIP_SKIP_NONFINITE = 1      # wun_adam_step_clip flags
 _lib = None
 
 # Process-wide record of the scheduling hint wun_config.exclusive_streams (include/wun.h): plans created with it run

@@ -993,6 +993,162 @@ hipError_t launch_adam_ranges(float* p, const float* g, float* m, float* v, cons
     return hipGetLastError();
 }
 
+// ---- global gradient norm (wun_grad_norm) and the clipped TF-Adam (wun_adam_step_clip) --------------------------------
+// Sums of squares in float64: double(g) * double(g) is exact, so the only rounding is in the float64 adds, whose order is
+// fixed by the chunk table and the block shape alone -- no atomics, bitwise reproducible, independent of the grid size.
+__device__ __forceinline__ double wave_sum_f64(double x) {
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+__device__ __forceinline__ bool norm_selected(const NormSelect& sel, int k) { return (sel.bits[k >> 5] >> (k & 31)) & 1u; }
+
+// one workgroup per chunk (chunks of unselected tensors return at once: their floats are never read); 16-byte loads from the
+// chunk's first 16-byte aligned float, the unaligned head and the tail by single floats
+__global__ __launch_bounds__(256) void grad_norm_kernel(const float* __restrict__ g, const NormChunk* __restrict__ chunks,
+                                                        NormSelect sel, double* __restrict__ partial) {
+    __shared__ double red[4];
+    const NormChunk ch = chunks[blockIdx.x];
+    if (!norm_selected(sel, ch.tensor)) return;
+    const float* x = g + ch.off;
+    const int head = min((int)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) >> 2, ch.len);
+    const int nv = (ch.len - head) >> 2, tail0 = head + 4 * nv;
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    if (t < head) { const double a = x[t]; acc = a * a; }
+    const f32x4* xv = reinterpret_cast<const f32x4*>(x + head);
+#pragma unroll 4
+    for (int i = t; i < nv; i += 256) {
+        const f32x4 q = xv[i];
+        const double a = q[0], b = q[1], c = q[2], d = q[3];
+        acc += ((a * a + b * b) + (c * c + d * d));
+    }
+    if (t < ch.len - tail0) { const double a = x[tail0 + t]; acc += a * a; }
+    acc = wave_sum_f64(acc);
+    if ((t & 63) == 0) red[t >> 6] = acc;
+    __syncthreads();
+    if (t == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// one workgroup of 16 waves: a wave per tensor sums its chunk partials (lane l takes chunks l, l + 64, ... in chunk order,
+// then a fixed butterfly), so a selected tensor's entry does not depend on what else is selected; wave 0 then sums the
+// per-tensor sums the same way.  Each result is |gscale| * sqrt(sum) rounded once to fp32; unselected tensors get 0.
+__global__ __launch_bounds__(1024) void grad_norm_finish_kernel(const double* __restrict__ partial,
+                                                                const int* __restrict__ first, int nt, NormSelect sel,
+                                                                float gscale, float* __restrict__ norms) {
+    __shared__ double tsum[WUN_NORM_MAX_TENSORS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double gs = fabs((double)gscale);
+    for (int k = wave; k < nt; k += 16) {
+        double acc = 0.0;
+        if (norm_selected(sel, k)) {
+            for (int c = first[k] + lane; c < first[k + 1]; c += 64) acc += partial[c];
+            acc = wave_sum_f64(acc);
+        }
+        if (lane == 0) {
+            tsum[k] = acc;
+            norms[k] = (float)(gs * sqrt(acc));
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        double acc = 0.0;
+        for (int k = lane; k < nt; k += 64) acc += tsum[k];
+        acc = wave_sum_f64(acc);
+        if (lane == 0) norms[nt] = (float)(gs * sqrt(acc));
+    }
+}
+
+hipError_t launch_grad_norm(const float* g, const NormChunk* chunks, const int* first, int nchunks, int ntensors,
+                            const NormSelect& sel, long long nfloats, float gscale, float* norms, double* partial,
+                            hipStream_t s) {
+    if (nchunks > 0) {
+        ProfScope ps("grad_norm_kernel", 2.0 * (double)nfloats, s, "", 4.0 * (double)nfloats);     // selected floats read once
+        hipLaunchKernelGGL(grad_norm_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, g, chunks, sel, partial);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    ProfScope ps("grad_norm_finish_kernel", 0.0, s, "", 8.0 * (double)nchunks + 4.0 * (ntensors + 1));
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(1024), 0, s, partial, first, ntensors, sel, gscale, norms);
+    return hipGetLastError();
+}
+
+// adam_kernel's expressions on gi = g * gscale, times clip / N only when N > clip: with no clipping every float is
+// bit-equal to adam_kernel's.  A skipped step returns before any p / m / v access; block 0's first lane counts it.
+__device__ __forceinline__ bool adam_clip_skip(float N, int skip, long long* skipped) {
+    if (!skip || isfinite(N)) return false;
+    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) *skipped = *skipped + 1;
+    return true;
+}
+
+__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, long long n, float lr_t, float b1, float b2, float eps, float gscale,
+                                 const float* __restrict__ gnorm, float clip, int skip, long long* skipped) {
+    const float N = *gnorm;
+    if (adam_clip_skip(N, skip, skipped)) return;
+    const bool clipping = N > clip;
+    const float cs = clip / N;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+         i += (long long)gridDim.x * blockDim.x) {
+        float gi = g[i] * gscale;
+        if (clipping) gi = gi * cs;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    }
+}
+
+hipError_t launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr_t, float b1, float b2,
+                            float eps, float gscale, const float* gnorm, float clip, int skip, long long* skipped,
+                            hipStream_t s) {
+    long long blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    ProfScope ps("adam_clip_kernel", 0.0, s, "", 28.0 * (double)n);
+    hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, gscale,
+                       gnorm, clip, skip, skipped);
+    return hipGetLastError();
+}
+
+__global__ void adam_clip_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                        float* __restrict__ v, AdamRanges r, float lr_t, float b1, float b2, float eps,
+                                        float gscale, const float* __restrict__ gnorm, float clip, int skip,
+                                        long long* skipped) {
+    const float N = *gnorm;
+    if (adam_clip_skip(N, skip, skipped)) return;
+    const bool clipping = N > clip;
+    const float cs = clip / N;
+    const long long total = r.cum[r.n];
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (long long)gridDim.x * blockDim.x) {
+        int k = 0;
+        while (k + 1 < r.n && t >= r.cum[k + 1]) ++k;
+        const long long i = r.off[k] + (t - r.cum[k]);
+        float gi = g[i] * gscale;
+        if (clipping) gi = gi * cs;
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    }
+}
+
+hipError_t launch_adam_clip_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t, float b1,
+                                   float b2, float eps, float gscale, const float* gnorm, float clip, int skip,
+                                   long long* skipped, hipStream_t s) {
+    const long long n = r.n > 0 ? r.cum[r.n] : 0;
+    if (n <= 0) return hipSuccess;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    ProfScope ps("adam_clip_ranges_kernel", 0.0, s, "", 28.0 * (double)n);
+    hipLaunchKernelGGL(adam_clip_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2, eps,
+                       gscale, gnorm, clip, skip, skipped);
+    return hipGetLastError();
+}
+
 __global__ void fill_kernel(float* p, long long n, float val) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) p[i] = val;

@@ -314,6 +314,24 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n
 struct AdamRanges { long long off[WUN_ADAM_RANGES]; long long cum[WUN_ADAM_RANGES + 1]; int n; };
 hipError_t launch_adam_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t,
                               float b1, float b2, float eps, float gscale, hipStream_t s);
+// Gradient norm (wun_grad_norm): the arena cut into chunks of at most WUN_NORM_CHUNK floats that never cross a tensor
+// boundary (plan-owned device table, chunks of tensor k = [first[k], first[k+1])); one float64 sum of squares per chunk,
+// then per tensor and over the selected tensors, in a fixed order (no atomics: bitwise reproducible, grid-independent).
+#define WUN_NORM_CHUNK 8192
+#define WUN_NORM_MAX_TENSORS 256
+struct NormChunk { long long off; int len; int tensor; };
+struct NormSelect { unsigned bits[WUN_NORM_MAX_TENSORS / 32]; };       // by value: bit k = tensor k selected
+hipError_t launch_grad_norm(const float* g, const NormChunk* chunks, const int* first, int nchunks, int ntensors,
+                            const NormSelect& sel, long long nfloats, float gscale, float* norms, double* partial,
+                            hipStream_t s);
+// adam_kernel / adam_ranges_kernel on the gradient clipped by the global norm *gnorm (device): gi *= clip / N when N > clip;
+// skip != 0 and N not finite: nothing written, *skipped += 1 (when non-null) by one lane
+hipError_t launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr_t, float b1, float b2,
+                            float eps, float gscale, const float* gnorm, float clip, int skip, long long* skipped,
+                            hipStream_t s);
+hipError_t launch_adam_clip_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t, float b1,
+                                   float b2, float eps, float gscale, const float* gnorm, float clip, int skip,
+                                   long long* skipped, hipStream_t s);
 hipError_t launch_fill(float* p, long long n, float val, hipStream_t s);
 hipError_t launch_mfma_probe(const float* a, const float* b, float* d, hipStream_t s);
 void prof_begin(bool detail);                 // detail: per-launch list in the JSON (WUN_PROFILE_DETAIL)

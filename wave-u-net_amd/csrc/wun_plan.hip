@@ -487,6 +487,30 @@ extern "C" int wun_plan_create(const wun_config* cfg, int64_t batch, int64_t inp
         if (e == hipSuccess) e = hipMemcpy(p->dev_pack, p->pack.data(), p->pack.size() * sizeof(PackDesc), hipMemcpyHostToDevice);
         if (e != hipSuccess) { p->dev_pack = nullptr; (void)hipGetLastError(); }
     }
+    // wun_grad_norm's chunk table: each tensor cut into WUN_NORM_CHUNK-float chunks in arena order
+    p->norm_first.assign(1, 0);
+    for (size_t k = 0; k < p->tensors.size(); ++k) {
+        const wun_tensor_info& t = p->tensors[k];
+        long long n = 1;
+        for (int d = 0; d < t.ndim; ++d) n *= t.shape[d];
+        for (long long o = 0; o < n; o += WUN_NORM_CHUNK)
+            p->norm_chunks.push_back({t.offset + o, (int)std::min<long long>(WUN_NORM_CHUNK, n - o), (int)k});
+        p->norm_first.push_back((int)p->norm_chunks.size());
+    }
+    if (!p->norm_chunks.empty()) {
+        const size_t cb = p->norm_chunks.size() * sizeof(NormChunk), fb = p->norm_first.size() * sizeof(int);
+        hipError_t e = hipMalloc((void**)&p->dev_norm_chunks, cb + fb);
+        if (e == hipSuccess) e = hipMemcpy(p->dev_norm_chunks, p->norm_chunks.data(), cb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            p->dev_norm_first = reinterpret_cast<int*>(p->dev_norm_chunks + p->norm_chunks.size());
+            e = hipMemcpy(p->dev_norm_first, p->norm_first.data(), fb, hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) {
+            if (p->dev_norm_chunks) (void)hipFree(p->dev_norm_chunks);
+            p->dev_norm_chunks = nullptr; p->dev_norm_first = nullptr;
+            (void)hipGetLastError();
+        }
+    }
     *out = p;
     return WUN_OK;
 }
@@ -495,6 +519,7 @@ extern "C" void wun_plan_destroy(wun_plan* p) {
     if (!p) return;
     if (p->dev_wt) (void)hipFree(p->dev_wt);
     if (p->dev_pack) (void)hipFree(p->dev_pack);
+    if (p->dev_norm_chunks) (void)hipFree(p->dev_norm_chunks);
     for (auto e : p->events) (void)hipEventDestroy(e);
     if (p->tev0) { (void)hipEventDestroy(p->tev0); (void)hipEventDestroy(p->tev1); }
     if (p->wt_ev) (void)hipEventDestroy(p->wt_ev);

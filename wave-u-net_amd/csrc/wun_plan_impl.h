@@ -99,6 +99,11 @@ struct wun_plan {
     int npack_fwd = 0;
     long long pack_max = 0;
     PackDesc* dev_pack = nullptr;
+    // wun_grad_norm: the chunk -> tensor map (host copy and device table: chunks, then num_tensors + 1 first-chunk indices)
+    std::vector<NormChunk> norm_chunks;
+    std::vector<int> norm_first;
+    NormChunk* dev_norm_chunks = nullptr;
+    int* dev_norm_first = nullptr;
     mutable const float* cur_params = nullptr;
     mutable const float* cur_ws = nullptr;
 };

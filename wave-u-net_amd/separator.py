@@ -38,6 +38,20 @@ def _wun_config(cfg):
         1 if cfg.get("exclusive_streams", False) else 0)      # extension key: scheduling hint (wun.h), set by the Trainer
 
 
+def check_clip_norm(clip_norm):
+    """clip_norm of adam_step / Trainer -> the float wun_adam_step_clip takes: None = +inf (no clipping); ValueError unless
+    > 0 (tf.clip_by_global_norm needs a positive clip_norm; NaN is refused)."""
+    if clip_norm is None:
+        return math.inf
+    try:
+        c = float(clip_norm)
+    except (TypeError, ValueError):
+        raise ValueError("clip_norm = %r must be a number > 0" % (clip_norm,))
+    if isinstance(clip_norm, bool) or not c > 0:
+        raise ValueError("clip_norm = %r must be > 0 (None or inf = no clipping)" % (clip_norm,))
+    return c
+
+
 class _Plan(object):
     def __init__(self, lib, wcfg, batch, frames):
         self.lib = lib
@@ -103,6 +117,7 @@ class UnetAudioSeparator(object):
         self.params = None           # flat float32 arena (TF creation order)
         self.grads = self.adam_m = self.adam_v = None
         self.global_step = 0
+        self._norm_ws = self._skipped = None     # wun_grad_norm workspace, skipped-step counter (allocated on first use)
         self._ws = {}
         self._ws_gen = {}            # (batch, frames) -> forward passes run on that workspace (autograd's stale-workspace guard)
         self._outs = {}
@@ -384,11 +399,27 @@ class UnetAudioSeparator(object):
         """Reuse choices exported by a plan of the same config / batch / length (ValueError otherwise)."""
         _lib.check(self._lib.wun_plan_tune_import(self._active.handle, text.encode()))
 
-    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, variables=None):
+    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, variables=None, clip_norm=None,
+                  skip_nonfinite=False):
         """tf.train.AdamOptimizer(learning_rate=lr) update (Training.py:77) + global_step += 1.  variables: TF variable names
         to update, as minimize(loss, var_list=...) does (None = all); params, m and v of every other tensor stay as they are
-        (wun_adam_step_select)."""
+        (wun_adam_step_select).
+
+        clip_norm: tf.clip_by_global_norm(grads, clip_norm) first, the global norm taken over the updated variables' gradients
+        (times grad_scale).  skip_nonfinite: when that norm is not finite, params, m and v are left as they are and
+        skipped_steps grows by one (global_step still advances, as TF's does per sess.run).  With either set the update is
+        wun_adam_step_clip and the global norm is returned (0-dim GPU tensor, no host sync); otherwise None."""
         mask = self.select_mask(variables)
+        if clip_norm is not None or skip_nonfinite:
+            clip = check_clip_norm(clip_norm)
+            ws, skipped = self._norm_buffers()
+            self.global_step += 1
+            _lib.check(self._lib.wun_adam_step_clip(
+                self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
+                self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
+                grad_scale, clip, _lib.WUN_CLIP_SKIP_NONFINITE if skip_nonfinite else 0, ws.data_ptr(),
+                skipped.data_ptr(), self._stream(), *self._mask_arg(mask)))
+            return ws[len(self._active.tensors)].clone()
         self.global_step += 1
         if mask is None:
             _lib.check(self._lib.wun_adam_step(
@@ -400,6 +431,35 @@ class UnetAudioSeparator(object):
             self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
             self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
             grad_scale, self._stream(), *self._mask_arg(mask)))
+
+    def _norm_buffers(self):
+        """(norm workspace, int64 skip counter) of wun_grad_norm / wun_adam_step_clip, allocated on first use."""
+        plan = self._active if self._active is not None else self._any_plan()
+        self._ensure_variables(plan)
+        n = int(self._lib.wun_grad_norm_workspace_floats(plan.handle))
+        if self._norm_ws is None or self._norm_ws.numel() < n:
+            self._norm_ws = torch.empty(n, dtype=torch.float32, device=self._dev())
+        if self._skipped is None:
+            self._skipped = torch.zeros(1, dtype=torch.int64, device=self._dev())
+        return self._norm_ws, self._skipped
+
+    def grad_norm(self, grad_scale=1.0, variables=None):
+        """L2 norms of grad_scale * self.grads (wun_grad_norm): (global norm over `variables` -- tf.clip_by_global_norm's
+        global_norm -- as a 0-dim GPU tensor, per-tensor norms [num_tensors] in variable-table order, 0 for a tensor not in
+        `variables`).  None = every variable.  No host sync."""
+        mask = self.select_mask(variables)
+        ws, _ = self._norm_buffers()
+        plan = self._active if self._active is not None else self._any_plan()
+        nt = len(plan.tensors)
+        _lib.check(self._lib.wun_grad_norm(plan.handle, self.grads.data_ptr(), grad_scale, ws.data_ptr(), self._stream(),
+                                           *self._mask_arg(mask)))
+        out = ws[:nt + 1].clone()
+        return out[nt], out[:nt]
+
+    @property
+    def skipped_steps(self):
+        """Adam steps skipped for a non-finite gradient norm (adam_step(skip_nonfinite=True)); reads the device counter."""
+        return 0 if self._skipped is None else int(self._skipped.item())
 
     def activation(self, kind, index=0):
         """(tensor view [B, C, frames], t0, tstep) of a forward activation kept in the workspace of the last

@@ -18,7 +18,7 @@ import torch.distributed as dist
 
 from .parallel import GradAllReducer, OverlappedGradAllReducer, broadcast_parameters, init_distributed
 from .checkpoint import load_checkpoint, save_checkpoint
-from .separator import UnetAudioSeparator
+from .separator import UnetAudioSeparator, check_clip_norm
 
 
 def synthetic_source(model_config, batch, t_in, t_out, device, seed=1337):
@@ -49,9 +49,15 @@ class Trainer(object):
     grad_accum_steps = k (or model_config["grad_accum_steps"], default 1): each step runs k micro-batches of batch / k
     excerpts on a plan built for that size, the first overwriting the gradient arena and the rest adding to it
     (wun_loss_backward_accumulate), then one all-reduce and one Adam update on the summed gradient scaled by 1 / k.
-    `batch` stays the per-rank batch of one optimizer step."""
+    `batch` stays the per-rank batch of one optimizer step.
 
-    def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0, grad_accum_steps=None):
+    clip_grad_norm / skip_nonfinite (or model_config["clip_grad_norm"] / ["skip_nonfinite_steps"], default off): each Adam
+    update clips by the global norm of the gradient it applies -- after the all-reduce, times the all-reduce's scale / k, so
+    every rank sees the same bits -- and skips the update when that norm is not finite (wun_adam_step_clip).  Off: exactly
+    the old calls."""
+
+    def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0, grad_accum_steps=None,
+                 clip_grad_norm=None, skip_nonfinite=None):
         self.rank, self.local_rank, self.world = init_distributed()
         # Scheduling hint of the plan (include/wun.h): low-priority side streams only when no collective shares the
         # device -- with a process group initialised (multi-GPU, or bench.py --force-allreduce) they must stay normal.
@@ -70,6 +76,8 @@ class Trainer(object):
         if self.accum < 1 or self.batch % self.accum:
             raise ValueError("grad_accum_steps = %r must be >= 1 and divide the batch (%d)" % (k, self.batch))
         self.micro = self.batch // self.accum
+        self.clip_norm, self.skip_nonfinite = clip_settings(model_config, clip_grad_norm, skip_nonfinite)
+        self.grad_norm = None                  # global norm of the last clipped / checked update (0-dim GPU tensor)
         in_shape, out_shape = self.sep.get_padding(np.array([self.batch, model_config["num_frames"], 0]))
         self.t_in, self.t_out = int(in_shape[1]), int(out_shape[1])
         plan = self.sep._plan(self.micro, self.t_in)
@@ -150,8 +158,19 @@ class Trainer(object):
         else:
             loss = self.sep.loss_and_gradients(targets)
             self.reducer.all_reduce(self.sep.grads)
-        self.sep.adam_step(self.lr, grad_scale=self.reducer.grad_scale)
+        self._adam(self.reducer.grad_scale)
         return loss
+
+    @property
+    def clipping(self):
+        return self.clip_norm is not None or self.skip_nonfinite
+
+    def _adam(self, grad_scale):
+        if self.clipping:
+            self.grad_norm = self.sep.adam_step(self.lr, grad_scale=grad_scale, clip_norm=self.clip_norm,
+                                                skip_nonfinite=self.skip_nonfinite)
+        else:
+            self.sep.adam_step(self.lr, grad_scale=grad_scale)
 
     def _accumulated_step(self, mix, targets):
         """k micro-batches, one optimizer step.  Only the last backward pass records the bucket events: an event then means
@@ -173,8 +192,21 @@ class Trainer(object):
             self.reducer.finish()
         else:
             self.reducer.all_reduce(self.sep.grads)
-        self.sep.adam_step(self.lr, grad_scale=self.reducer.grad_scale / k)
+        self._adam(self.reducer.grad_scale / k)
         return torch.stack(losses).mean()
+
+
+def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
+    """(clip_norm or None, skip_nonfinite) of a Trainer: the arguments, else model_config["clip_grad_norm"] /
+    ["skip_nonfinite_steps"].  ValueError for a clip_grad_norm that is not > 0 (NaN included)."""
+    clip = clip_grad_norm if clip_grad_norm is not None else model_config.get("clip_grad_norm")
+    skip = skip_nonfinite if skip_nonfinite is not None else model_config.get("skip_nonfinite_steps", False)
+    if clip is not None:
+        try:
+            clip = check_clip_norm(clip)
+        except ValueError:
+            raise ValueError("clip_grad_norm = %r must be a number > 0" % (clip,))
+    return clip, bool(skip)
 
 
 def train(model_config, experiment_id, load_model=None, batch_source=None, log_every=None):
@@ -213,8 +245,11 @@ def train(model_config, experiment_id, load_model=None, batch_source=None, log_e
         mix, targets = batch_source()
         loss = tr.step(mix, targets)
         if log is not None and (it % log_every == 0 or it == model_config["epoch_it"] - 1):
-            log.write(json.dumps({"global_step": tr.sep.global_step, "sep_loss": float(loss.item()),
-                                  "elapsed_s": time.time() - t0}) + "\n")
+            line = {"global_step": tr.sep.global_step, "sep_loss": float(loss.item()), "elapsed_s": time.time() - t0}
+            if tr.clipping:
+                line["grad_norm"] = float(tr.grad_norm.item())
+                line["skipped_steps"] = tr.sep.skipped_steps
+            log.write(json.dumps(line) + "\n")
             log.flush()
     torch.cuda.synchronize()
     save_path = None
