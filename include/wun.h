@@ -346,6 +346,45 @@ int wun_adam_step_clip(const wun_plan* plan, float* params, const float* grads, 
                        float clip_norm, int32_t flags, float* norm_ws, int64_t* skipped,
                        void* stream, const uint8_t* select, int64_t nselect);
 
+/* ---- sample-rate conversion of the audio boundary ---------------------------------------
+ * Rational polyphase resampler: what the reference does with librosa on the way into and out of Evaluate.predict
+ * (Evaluate.py:59-67,104; Utils.py:94-95), fused with the channel mapping and the context padding around it.
+ *   y[n] = sum_m v[m] * h[n*down - m*up + half],  v = the channel-mapped input, zero outside [0, n_in)
+ * up / down = sr_out / sr_in reduced by their gcd; the result has ceil(n_in * up / down) frames (librosa's and scipy's
+ * rule).  h is the default filter of scipy.signal.resample_poly -- NOT resampy's kaiser_best table that librosa uses:
+ * half = 10 * max(up, down), 2*half + 1 taps, windowed sinc with cutoff 1 / max(up, down) of Nyquist, Kaiser window
+ * beta = 5.0, unit DC gain, times up.  The table the kernel reads is PHASE-MAJOR fp32: K = ceil((2*half + 1) / up) floats per
+ * row, up rows, table[p*K + k] = h[p + k*up] (0 past the last tap); output n uses row (n*down + half) % up.
+ * Audio is float32 [T, C] channel-last.  Every device buffer is the caller's; nothing allocates or synchronises. */
+
+/* up / down after the gcd.  WUN_ERR_INVALID for a null pointer or a rate <= 0; WUN_ERR_UNSUPPORTED when max(up, down)
+ * exceeds 16384 (44 100 -> 8 192 Hz needs 11 025): the table has about 20 * max(up, down) floats. */
+int     wun_resample_ratio(int32_t sr_in, int32_t sr_out, int32_t* up, int32_t* down);
+/* ceil(n_in * up / down), and the floats of the phase-major table; negative wun_status for bad arguments (up, down must be
+ * positive, coprime and within the ceiling). */
+int64_t wun_resample_frames(int64_t n_in, int32_t up, int32_t down);
+int64_t wun_resample_table_floats(int32_t up, int32_t down);
+/* Host: design the filter in float64 (Bessel I0 by its power series) and write the fp32 phase-major table into
+ * table_host[cap].  WUN_ERR_INVALID for a null pointer or cap < wun_resample_table_floats.  up == down == 1 gives the
+ * unit impulse (never read by wun_resample). */
+int     wun_resample_design(int32_t up, int32_t down, float* table_host, int64_t cap);
+/* Device: y[(y_offset + n) * c_out + c] for n < n_out <= wun_resample_frames(n_in, up, down); nothing else of y is
+ * written (a caller that zeroes a longer y gets the context padding of Evaluate.py:121-122 for free; a caller that caps
+ * n_out gets the [:n] of Evaluate.py:64).
+ *   x          : device, [n_in, c_in]
+ *   y          : device, at least [y_offset + n_out, c_out]
+ *   channels   : c_in == c_out (1 or 2): per channel;  c_out == 1, c_in <= 8: the mean of the input channels (sequential
+ *                fp32 sum, one divide: np.mean(axis=1), Evaluate.py:98-99);  c_in == 1, c_out == 2: duplicated
+ *                (Evaluate.py:65-67,101-102)
+ *   table_dev  : device copy of wun_resample_design's table for the same up / down (may be NULL when up == down)
+ * One output frame per lane, taps accumulated by fp32 FMA in one fixed order (k ascending): the result is bitwise
+ * reproducible and does not depend on y_offset, the grid or pointer alignment; no atomics.  up == down is the
+ * channel-mapped copy, exact.  WUN_ERR_INVALID before any GPU work for null pointers, up / down not positive and coprime,
+ * another channel pair, negative lengths or n_out beyond the rule; WUN_ERR_UNSUPPORTED above the ratio ceiling or when
+ * the input window of 256 outputs (255 * down / up + K frames) exceeds 64 KB. */
+int     wun_resample(const float* x, int64_t n_in, int32_t c_in, float* y, int64_t y_offset, int64_t n_out,
+                     int32_t c_out, const float* table_dev, int32_t up, int32_t down, void* stream);
+
 /* ---- single operators (used by the parity tests and for per-kernel profiling) ---------- */
 
 /* y[b][co][q] = act(bias[co] + sum_{k,ci} w[k][ci][co] * x[b][ci][q*stride + k - pad_left]),

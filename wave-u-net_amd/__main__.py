@@ -10,7 +10,8 @@
 
 `with` arguments: `cfg.<named config>` (any of wave_u_net_amd.NAMED_CONFIGS), `model_config.<key>=<value>`
 overrides, and the command's own options as `<name>=<value>`.  data_root holds
-train|valid|test/<track>/<source>.wav|.npy (+ optional mix.wav) at expected_sr.  Multi-GPU:
+train|valid|test/<track>/<source>.wav|.npy (+ optional mix.wav) at expected_sr, or at any rate with the option
+`resample=1` (train, test).  `predict` takes a WAV at any rate and writes the estimates at that rate.  Multi-GPU:
 launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.
 """
 import ast
@@ -61,13 +62,13 @@ def main(argv=None):
             print("Saved model at " + str(path))
         elif opts.get("optimise", True) and "data_root" in opts:
             path, loss = validation.optimise(model_config, experiment_id, data_root=opts["data_root"],
-                                             max_epochs=opts.get("max_epochs"))
+                                             max_epochs=opts.get("max_epochs"), resample=bool(opts.get("resample", False)))
             print("Supervised training finished! Saved model at " + str(path) + ". Performance: " + str(loss))
         else:
             raise SystemExit("train needs data_root=<dir> or synthetic=1")
     elif cmd == "test":
         loss = validation.test(model_config, opts.get("partition", "test"), str(opts.get("experiment_id", "cli")),
-                               opts.get("model_path"), data_root=opts["data_root"])
+                               opts.get("model_path"), data_root=opts["data_root"], resample=bool(opts.get("resample", False)))
         print("Finished testing - Mean MSE: " + str(loss))
     else:
         if "input_path" not in opts:

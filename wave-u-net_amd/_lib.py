@@ -65,6 +65,11 @@ _SIGS = {
     "wun_grad_norm": (C.c_int, [_P, _P, C.c_float, _P, _P, C.POINTER(C.c_uint8), C.c_int64]),
     "wun_adam_step_clip": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_float, C.c_int32, _P, _P, _P, C.POINTER(C.c_uint8), C.c_int64]),
+    "wun_resample_ratio": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "wun_resample_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_resample_table_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "wun_resample_design": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int64]),
+    "wun_resample": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, _P]),
     "wun_op_conv1d": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     "wun_op_conv1d_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
     "wun_op_conv1d_wgrad": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),

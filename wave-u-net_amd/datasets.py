@@ -14,8 +14,8 @@ on the host in numpy.  DeviceSnippetSource is the MI355X-first producer for trai
 track lives in HBM (a full MUSDB train set at 22 kHz mono fp32 is ~4 GB of 288 GB), and a batch
 is one gather + gain + sum + crop on the GPU, so the input side keeps up with a ~10 ms step.
 
-Decoding MUSDB stems / resampling (librosa, musdb, soundfile in the reference, Datasets.py:119-186)
-is out of scope: tracks come from WAV (scipy) or .npy files already at model_config["expected_sr"].
+Decoding MUSDB stems (musdb, soundfile in the reference, Datasets.py:119-186) is out of scope: tracks come from WAV
+(scipy) or .npy files, at model_config["expected_sr"] or -- with resample=True -- at any rate (resample.py).
 """
 import os
 
@@ -25,11 +25,11 @@ import numpy as np
 # --------------------------------------------------------------------------------------
 # tracks
 # --------------------------------------------------------------------------------------
-def load_audio(path, mono=False, expected_sr=None):
-    """[T, C] float32 from a .wav (PCM16/32 or float) or .npy file (Utils.load without resampling)."""
+def read_audio(path):
+    """([T, C] float32, sample rate) of a .wav (PCM16/32 or float) or .npy file; the rate of an .npy is None (unknown)."""
     if path.endswith(".npy"):
         audio = np.load(path).astype(np.float32)
-        sr = expected_sr
+        sr = None
     else:
         from scipy.io import wavfile
         sr, raw = wavfile.read(path)
@@ -43,14 +43,27 @@ def load_audio(path, mono=False, expected_sr=None):
             audio = raw.astype(np.float32)
     if audio.ndim == 1:
         audio = audio[:, None]
-    if expected_sr is not None and sr is not None and int(sr) != int(expected_sr):
-        raise NotImplementedError("resampling is out of scope: %s is at %s Hz, expected %s" % (path, sr, expected_sr))
+    return np.ascontiguousarray(audio, dtype=np.float32), sr
+
+
+def load_audio(path, mono=False, expected_sr=None, resample=False):
+    """[T, C] float32 from a .wav (PCM16/32 or float) or .npy file (Utils.load, Utils.py:97-110).  A file at another rate
+    than expected_sr is refused unless resample=True: then it is downmixed (mono) and resampled to expected_sr as
+    librosa.load does, with resample.py's filter (scipy's Kaiser design on the host, not resampy's)."""
+    audio, sr = read_audio(path)
+    mismatch = expected_sr is not None and sr is not None and int(sr) != int(expected_sr)
+    if mismatch and not resample:
+        raise NotImplementedError("%s is at %s Hz, expected %s: pass resample=True (the `resample=1` option of the "
+                                  "train / test commands) to convert it" % (path, sr, expected_sr))
     if mono and audio.shape[1] > 1:
         audio = audio.mean(axis=1, keepdims=True)
+    if mismatch:
+        from .resample import resample as _resample
+        audio = _resample(audio, sr, expected_sr)
     return np.ascontiguousarray(audio, dtype=np.float32)
 
 
-def make_track(sources, model_config, mix=None):
+def make_track(sources, model_config, mix=None, resample=False):
     """Validated track dict from {source_name: array-or-path}.  Mono tracks are duplicated when
     the model is stereo (Datasets.py:64-66); all signals must have equal shape (:79-84); the mix
     defaults to the sum of the sources."""
@@ -58,7 +71,7 @@ def make_track(sources, model_config, mix=None):
     track = {}
     for key in model_config["source_names"]:
         a = sources[key]
-        a = load_audio(a, mono, model_config.get("expected_sr")) if isinstance(a, str) else np.asarray(a, np.float32)
+        a = load_audio(a, mono, model_config.get("expected_sr"), resample) if isinstance(a, str) else np.asarray(a, np.float32)
         if a.ndim == 1:
             a = a[:, None]
         if mono and a.shape[1] > 1:
@@ -71,7 +84,7 @@ def make_track(sources, model_config, mix=None):
     if mix is None:
         mix = sum(track[k] for k in model_config["source_names"])
     elif isinstance(mix, str):
-        mix = load_audio(mix, mono, model_config.get("expected_sr"))
+        mix = load_audio(mix, mono, model_config.get("expected_sr"), resample)
     mix = np.asarray(mix, np.float32)
     if mix.ndim == 1:
         mix = mix[:, None]
@@ -84,8 +97,9 @@ def make_track(sources, model_config, mix=None):
     return track
 
 
-def load_track_dir(path, model_config):
-    """A directory holding <source_name>.wav|.npy for every source and optionally mix.wav|.npy."""
+def load_track_dir(path, model_config, resample=False):
+    """A directory holding <source_name>.wav|.npy for every source and optionally mix.wav|.npy.  resample: convert files at
+    another rate to expected_sr (load_audio) instead of refusing them."""
     def find(stem):
         for ext in (".wav", ".npy"):
             f = os.path.join(path, stem + ext)
@@ -98,13 +112,13 @@ def load_track_dir(path, model_config):
         if f is None:
             raise FileNotFoundError("%s: no %s.wav/.npy" % (path, key))
         srcs[key] = f
-    return make_track(srcs, model_config, mix=find("mix"))
+    return make_track(srcs, model_config, mix=find("mix"), resample=resample)
 
 
-def load_partition(root, partition, model_config):
+def load_partition(root, partition, model_config, resample=False):
     """root/<partition>/<track>/ directories, sorted by name."""
     base = os.path.join(root, partition)
-    return [load_track_dir(os.path.join(base, d), model_config)
+    return [load_track_dir(os.path.join(base, d), model_config, resample)
             for d in sorted(os.listdir(base)) if os.path.isdir(os.path.join(base, d))]
 
 

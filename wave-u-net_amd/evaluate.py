@@ -6,8 +6,11 @@ inputs (:108-113), symmetric context padding of (input_frames - output_frames)//
 hops of `output_frames` with the LAST hop re-aligned to the end of the track (:125-128), removal of
 the extra padding (:141-143).  MI355X-first difference: hops are evaluated `batch_hops` at a time in
 one get_output call instead of one sess.run per hop (identical results, far fewer launches).
-Resampling (librosa in the reference, :106) is out of scope: the audio must already be at
-model_config["expected_sr"].
+predict_track takes audio that is already at model_config["expected_sr"] and tiles on the host.
+separate_track is the whole of Evaluate.predict (:59-80) for a file at ANY rate, on the device the separator lives on:
+downmix + resampling + context padding in one kernel (resample.py, wun_resample), hop windows gathered and estimates
+scattered on the GPU, resampling back + trim + channel duplication in one kernel per source, one upload and one
+download per track.
 """
 import numpy as np
 import torch
@@ -59,29 +62,94 @@ def predict_track(model_config, separator, mix_audio, mix_sr=None, batch_hops=16
     return preds
 
 
+def _hop_positions(n_frames, output_frames):
+    positions = []
+    for pos in range(0, n_frames, output_frames):                                # Evaluate.py:125-128
+        if pos + output_frames > n_frames:
+            pos = n_frames - output_frames
+        positions.append(pos)
+    return positions
+
+
+def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16):
+    """Evaluate.predict (Evaluate.py:59-80) around predict_track (:82-145) for audio at any sample rate, without the
+    host in the loop.  mix_audio: [n_frames, n_channels] float array or tensor at mix_sr Hz.  Returns {source_name: float32
+    numpy [n_frames, channels]} at mix_sr: channels is the input's count, except that a stereo model on a mono file
+    gives its two channels, as the reference does.
+
+    Everything between the upload of mix_audio and the download of the estimates runs on `separator.device` (a
+    separator without that attribute -- a numpy stand-in -- runs the same steps on CPU tensors).  Same hop positions,
+    chunking and get_output batches as predict_track: at mix_sr == expected_sr the estimates are bit-identical to
+    predict_track's (tiled to the input's channels for a mono model)."""
+    from . import resample as rs
+    device = torch.device(getattr(separator, "device", None) or "cpu")
+    x = mix_audio if torch.is_tensor(mix_audio) else torch.from_numpy(np.ascontiguousarray(np.asarray(mix_audio, dtype=np.float32)))
+    assert x.dim() == 2                                                          # Evaluate.py:97
+    x = x.to(device=device, dtype=torch.float32).contiguous()                    # the one upload
+    n_in, ch = int(x.shape[0]), int(x.shape[1])
+    C = 1 if model_config["mono_downmix"] else max(ch, 2)                        # :98-102
+    up, down = rs.ratio(mix_sr, model_config["expected_sr"])
+    n_res = rs.frames(n_in, up, down)
+
+    in_shape, out_shape = separator.get_padding(np.array([1, model_config["num_frames"], 0]))
+    input_frames, output_frames = int(in_shape[1]), int(out_shape[1])
+    n_frames = max(n_res, input_frames)                                          # :108-113 (short inputs: zeros behind)
+    pad = (input_frames - output_frames) // 2                                    # :121-122
+    padded = torch.zeros((n_frames + 2 * pad, C), dtype=torch.float32, device=device)
+    rs.resample_into(x, padded, pad, n_res, up, down)                            # downmix / duplicate, resample, pad
+
+    names = list(model_config["source_names"])
+    preds = torch.zeros((len(names), n_frames, C), dtype=torch.float32, device=device)   # :117
+    positions = _hop_positions(n_frames, output_frames)
+    for k in range(0, len(positions), batch_hops):
+        chunk = positions[k:k + batch_hops]
+        batch = torch.stack([padded[p:p + input_frames] for p in chunk])         # strided views -> [B, Tin, C]
+        outs = separator.get_output(batch if device.type != "cpu" else batch.numpy(), False)
+        run = 1                                                                  # leading hops at consecutive multiples
+        while run < len(chunk) and chunk[run] == chunk[0] + run * output_frames:
+            run += 1
+        for si, n in enumerate(names):
+            o = outs[n]
+            o = o if torch.is_tensor(o) else torch.from_numpy(np.ascontiguousarray(np.asarray(o, dtype=np.float32)))
+            o = o.to(device)
+            preds[si, chunk[0]:chunk[0] + run * output_frames].view(run, output_frames, C).copy_(o[:run])
+            for bi in range(run, len(chunk)):                                    # the re-aligned last hop, written last
+                preds[si, chunk[bi]:chunk[bi] + output_frames] = o[bi]           # :139
+
+    # back to mix_sr, cut to the input's length, mono estimates duplicated to the input's channels (:64-67)
+    c_out = ch if (C == 1 and ch > 1) else C
+    c_fused = c_out if c_out <= 2 else C
+    n_back = min(rs.frames(n_res, down, up), n_in)
+    out = torch.empty((len(names), n_back, c_fused), dtype=torch.float32, device=device)
+    for si in range(len(names)):
+        rs.resample_into(preds[si, :n_res], out[si], 0, n_back, down, up)        # [:n_res] drops extra_pad (:141-143)
+    if c_fused != c_out:
+        out = out.repeat(1, 1, c_out)
+    host = out.cpu().numpy()                                                     # the one download
+    return {n: host[si] for si, n in enumerate(names)}
+
+
 def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None):
     """Evaluate.produce_source_estimates (Evaluate.py:160-194): separate one mixture file with a
-    checkpoint and write <input file name>_<source>.wav next to it (or into output_path).  WAV/NPY
-    input at expected_sr (no resampling, no MP3 decoding here).  Returns {source: [T, C]}."""
+    checkpoint and write <input file name>_<source>.wav next to it (or into output_path), at the input file's sample rate
+    and length.  WAV/NPY input at any rate (an .npy is taken to be at expected_sr; no MP3 decoding here): the separation runs
+    through separate_track.  Returns {source: [T, C]}."""
     import os
     from scipy.io import wavfile
     from . import datasets
     from .separator import UnetAudioSeparator
-    audio = datasets.load_audio(input_path, mono=False, expected_sr=model_config["expected_sr"])
+    audio, sr = datasets.read_audio(input_path)                    # Utils.load(input_path, sr=None, mono=False), :172
+    if sr is None:
+        sr = model_config["expected_sr"]
     sep = separator if separator is not None else UnetAudioSeparator(model_config)
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
-    preds = predict_track(model_config, sep, audio, model_config["expected_sr"])
-    # Evaluate.predict (:59-80): mono models are evaluated on the downmix; estimates are tiled back to
-    # the input's channel count
-    if model_config["mono_downmix"] and audio.shape[1] > 1:
-        preds = {k: np.tile(v, [1, audio.shape[1]]) for k, v in preds.items()}
+    preds = separate_track(model_config, sep, audio, sr)
     folder, name = os.path.split(input_path)
     if output_path is None:
         output_path = folder
     os.makedirs(output_path or ".", exist_ok=True)
     for source_name, source_audio in preds.items():
-        wavfile.write(os.path.join(output_path, name) + "_" + source_name + ".wav", int(model_config["expected_sr"]),
-                      np.asarray(source_audio, np.float32))
+        wavfile.write(os.path.join(output_path, name) + "_" + source_name + ".wav", int(sr), np.asarray(source_audio, np.float32))
     return preds

@@ -147,6 +147,11 @@ class UnetAudioSeparator(object):
             self._device = torch.device("cuda", torch.cuda.current_device())
         return self._device
 
+    @property
+    def device(self):
+        """The GPU the separator's arenas and workspaces live on (evaluate.separate_track keeps the track there)."""
+        return self._dev()
+
     def variable_table(self, batch=1, frames=None):
         """[(tf_name, offset, shape)] in TF creation order."""
         if frames is None:

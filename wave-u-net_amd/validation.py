@@ -24,16 +24,17 @@ def _load_checkpoint(separator, load_model):
 
 
 def test(model_config, partition, model_folder, load_model, tracks=None, data_root=None, separator=None,
-         return_sums=False):
+         return_sums=False, resample=False):
     """Test.test(model_config, partition, model_folder, load_model) -> mean MSE.  The partition's
     tracks come from `tracks` (list of track dicts) or data_root/<partition>/<track>/.
-    return_sums: (sum of the per-batch losses, number of batches) instead, nothing logged."""
+    return_sums: (sum of the per-batch losses, number of batches) instead, nothing logged.
+    resample: files of data_root at another rate are converted to expected_sr (datasets.load_audio) instead of refused."""
     if model_config["network"] != "unet":
         raise NotImplementedError(model_config["network"])                        # Test.py:14-19
     if tracks is None:
         if data_root is None:
             raise ValueError("test() needs `tracks` or `data_root`")
-        tracks = datasets.load_partition(data_root, partition, model_config)
+        tracks = datasets.load_partition(data_root, partition, model_config, resample)
     sep = separator if separator is not None else UnetAudioSeparator(model_config)
     disc_input_shape = [model_config["batch_size"], model_config["num_frames"], 0]
     in_shape, out_shape = sep.get_padding(np.array(disc_input_shape))            # Test.py:21
@@ -62,14 +63,14 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     return total_loss
 
 
-def optimise(model_config, experiment_id, data=None, data_root=None, max_epochs=None):
+def optimise(model_config, experiment_id, data=None, data_root=None, max_epochs=None, resample=False):
     """Training.optimise -> (best_model_path, test_loss).  `data` = {"train": [...], "valid": [...],
     "test": [...]} track lists (or data_root with those sub-directories).  max_epochs bounds the
-    total number of epochs (the reference has no bound; tests need one)."""
+    total number of epochs (the reference has no bound; tests need one).  resample: as for test()."""
     if data is None:
         if data_root is None:
             raise ValueError("optimise() needs `data` or `data_root`")
-        data = {part: datasets.load_partition(data_root, part, model_config) for part in ("train", "valid", "test")}
+        data = {part: datasets.load_partition(data_root, part, model_config, resample) for part in ("train", "valid", "test")}
     model_config = dict(model_config)
     epoch = 0
     best_loss = 10000
