@@ -21,8 +21,8 @@ bfloat16 conversion at exactly the points where the HIP plan stores a tensor in 
 so that the HIP path can be compared with it at fp32-accumulation error plus rare one-ulp bf16 flips (an fp32 sum that
 lands within 1e-7 of a rounding boundary) instead of at the rounding noise of the mode itself.  With `quantize=False`
 every rounding is the identity and the result must equal the float64 oracle exactly (tests/test_bf16_emul.py) -- that
-pins the hand-placed adjoints; the rounding points themselves are a restatement of wave-u-net_amd/csrc (wun_step.hip:
-wun_forward / wun_loss_backward_ex, wun_bf16.hip epilogue), cited inline.
+pins the hand-placed adjoints; the rounding points themselves are a restatement of wave-u-net_amd/csrc (wun_forward.hip:
+wun_forward, wun_backward.hip: wun_loss_backward_ex, wun_bf16.hip epilogue), cited inline.
 
     loss, grads, inter = train_step(cfg, params, mix, targets)                  # chained
     loss, grads, inter = train_step(cfg, params, mix, targets, forced=gpu_tensors)   # layer by layer (see train_step)

@@ -9,6 +9,7 @@
 // built as before (their device code is unchanged by the split: tools/kernel_resources.sh, profiles).
 #include "wun_device.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
@@ -937,47 +938,52 @@ hipError_t launch_make_wt_one(const float* src, float* dst, WtDesc d, hipStream_
     return hipGetLastError();
 }
 
+// ---- TF-Adam (wun_adam_step, _select, _clip): four thin kernels over ONE update, ONE run lookup, ONE clip prologue --------
+// The kernels differ in which floats they visit (the whole arena / the selected runs) and in what they do to the gradient first
+// (nothing / clip by the global norm); a float's update is the same expressions in the same order in all of them, which is what
+// makes a selected float bit-equal to the full step's and an inactive clip bit-equal to the plain step.
+// The fused multiply-adds of mi and vi (decayed term fused, gradient term rounded first) are written out: left to
+// -ffp-contract, which of a sum's two products is fused is the compiler's choice per call site, and that choice is a rounding.
+__device__ __forceinline__ void adam_update(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long i,
+                                            float gi, float lr_t, float b1, float b2, float eps) {
+    const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
+    const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// position t of the concatenated runs -> arena index: a scan of the (at most WUN_ADAM_RANGES) prefix sums
+__device__ __forceinline__ long long adam_range_index(const AdamRanges& r, long long t) {
+    int k = 0;
+    while (k + 1 < r.n && t >= r.cum[k + 1]) ++k;
+    return r.off[k] + (t - r.cum[k]);
+}
+
+static unsigned adam_grid(long long n) { return (unsigned)std::min(std::max((n + 255) / 256, 1LL), 4096LL); }
+
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long long n, float lr_t, float b1, float b2,
                             float eps, float gscale) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * gscale;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
-    }
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        adam_update(p, m, v, i, g[i] * gscale, lr_t, b1, b2, eps);
 }
 
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr_t,
                        float b1, float b2, float eps, float gscale, hipStream_t s) {
-    long long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
     ProfScope ps("adam_kernel", 0.0, s, "", 28.0 * (double)n);       // p, m, v read + written, g read
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2,
-                       eps, gscale);
+    hipLaunchKernelGGL(adam_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, gscale);
     return hipGetLastError();
 }
 
-// adam_kernel over the selected runs only: thread-strided over the concatenated runs, the run found by a scan of the (at most
-// WUN_ADAM_RANGES) prefix sums; every float gets adam_kernel's expressions, so a selected float is bit-equal to the full step's
+// adam_kernel over the selected runs only: thread-strided over the concatenated runs
 __global__ void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                    float* __restrict__ v, AdamRanges r, float lr_t, float b1, float b2,
                                    float eps, float gscale) {
     const long long total = r.cum[r.n];
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
-         t += (long long)gridDim.x * blockDim.x) {
-        int k = 0;
-        while (k + 1 < r.n && t >= r.cum[k + 1]) ++k;
-        const long long i = r.off[k] + (t - r.cum[k]);
-        const float gi = g[i] * gscale;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const long long i = adam_range_index(r, t);
+        adam_update(p, m, v, i, g[i] * gscale, lr_t, b1, b2, eps);
     }
 }
 
@@ -985,11 +991,8 @@ hipError_t launch_adam_ranges(float* p, const float* g, float* m, float* v, cons
                               float b1, float b2, float eps, float gscale, hipStream_t s) {
     const long long n = r.n > 0 ? r.cum[r.n] : 0;
     if (n <= 0) return hipSuccess;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
     ProfScope ps("adam_ranges_kernel", 0.0, s, "", 28.0 * (double)n);
-    hipLaunchKernelGGL(adam_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2,
-                       eps, gscale);
+    hipLaunchKernelGGL(adam_ranges_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2, eps, gscale);
     return hipGetLastError();
 }
 
@@ -1073,41 +1076,35 @@ hipError_t launch_grad_norm(const float* g, const NormChunk* chunks, const int* 
     return hipGetLastError();
 }
 
-// adam_kernel's expressions on gi = g * gscale, times clip / N only when N > clip: with no clipping every float is
-// bit-equal to adam_kernel's.  A skipped step returns before any p / m / v access; block 0's first lane counts it.
-__device__ __forceinline__ bool adam_clip_skip(float N, int skip, long long* skipped) {
-    if (!skip || isfinite(N)) return false;
+// The clipped kernels: gi = g * gscale, times clip / N only when N > clip -- with no clipping every float is bit-equal to
+// adam_kernel's.  A skipped step (skip != 0, N not finite) returns before any p / m / v access; block 0's first lane counts it.
+struct AdamClip { bool clipping; float cs; };
+// false: the step is skipped
+__device__ __forceinline__ bool adam_clip_prologue(const float* __restrict__ gnorm, float clip, int skip, long long* skipped,
+                                                   AdamClip& c) {
+    const float N = *gnorm;
+    c.clipping = N > clip;
+    c.cs = clip / N;
+    if (!skip || isfinite(N)) return true;
     if (skipped && blockIdx.x == 0 && threadIdx.x == 0) *skipped = *skipped + 1;
-    return true;
+    return false;
 }
+__device__ __forceinline__ float adam_clipped(float gi, const AdamClip& c) { return c.clipping ? gi * c.cs : gi; }
 
 __global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                  float* __restrict__ v, long long n, float lr_t, float b1, float b2, float eps, float gscale,
                                  const float* __restrict__ gnorm, float clip, int skip, long long* skipped) {
-    const float N = *gnorm;
-    if (adam_clip_skip(N, skip, skipped)) return;
-    const bool clipping = N > clip;
-    const float cs = clip / N;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x) {
-        float gi = g[i] * gscale;
-        if (clipping) gi = gi * cs;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
-    }
+    AdamClip c;
+    if (!adam_clip_prologue(gnorm, clip, skip, skipped, c)) return;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        adam_update(p, m, v, i, adam_clipped(g[i] * gscale, c), lr_t, b1, b2, eps);
 }
 
 hipError_t launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr_t, float b1, float b2,
                             float eps, float gscale, const float* gnorm, float clip, int skip, long long* skipped,
                             hipStream_t s) {
-    long long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
     ProfScope ps("adam_clip_kernel", 0.0, s, "", 28.0 * (double)n);
-    hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, gscale,
+    hipLaunchKernelGGL(adam_clip_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, gscale,
                        gnorm, clip, skip, skipped);
     return hipGetLastError();
 }
@@ -1116,23 +1113,12 @@ __global__ void adam_clip_ranges_kernel(float* __restrict__ p, const float* __re
                                         float* __restrict__ v, AdamRanges r, float lr_t, float b1, float b2, float eps,
                                         float gscale, const float* __restrict__ gnorm, float clip, int skip,
                                         long long* skipped) {
-    const float N = *gnorm;
-    if (adam_clip_skip(N, skip, skipped)) return;
-    const bool clipping = N > clip;
-    const float cs = clip / N;
+    AdamClip c;
+    if (!adam_clip_prologue(gnorm, clip, skip, skipped, c)) return;
     const long long total = r.cum[r.n];
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total;
-         t += (long long)gridDim.x * blockDim.x) {
-        int k = 0;
-        while (k + 1 < r.n && t >= r.cum[k + 1]) ++k;
-        const long long i = r.off[k] + (t - r.cum[k]);
-        float gi = g[i] * gscale;
-        if (clipping) gi = gi * cs;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const long long i = adam_range_index(r, t);
+        adam_update(p, m, v, i, adam_clipped(g[i] * gscale, c), lr_t, b1, b2, eps);
     }
 }
 
@@ -1141,10 +1127,8 @@ hipError_t launch_adam_clip_ranges(float* p, const float* g, float* m, float* v,
                                    long long* skipped, hipStream_t s) {
     const long long n = r.n > 0 ? r.cum[r.n] : 0;
     if (n <= 0) return hipSuccess;
-    long long blocks = (n + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
     ProfScope ps("adam_clip_ranges_kernel", 0.0, s, "", 28.0 * (double)n);
-    hipLaunchKernelGGL(adam_clip_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2, eps,
+    hipLaunchKernelGGL(adam_clip_ranges_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2, eps,
                        gscale, gnorm, clip, skip, skipped);
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 // Internal: kernel argument blocks + launcher prototypes shared by the device units (wun_kernels.hip, ...) and the
-// host units (wun_plan.hip and the files of wun_plan_impl.h: plan, dispatch, step, tuner, C ABI).  Host declarations only:
+// host units (wun_plan.hip and the files of wun_plan_impl.h: plan, dispatch, the step's passes, tuner, C ABI).  Host declarations only:
 // the device helpers of the kernel units live in wun_device.h.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,146 @@
+// Host side of libwun.so: the optimizer of the training step -- TF-Adam over the whole arena or a selection of its tensors,
+// the global gradient norm, and the clipped / skipping Adam step built on it.
+#include "wun_plan_impl.h"
+
+#include <cmath>
+#include <cstring>
+
+// TF-Adam's step size (Training.py:77): lr * sqrt(1 - b2^t) / (1 - b1^t)
+static float adam_lr_t(int64_t step, float lr, float beta1, float beta2) {
+    const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)step)) /
+                        (1.0 - std::pow((double)beta1, (double)step));
+    return (float)lr_t;
+}
+
+// what every Adam entry checks first
+static int adam_args(const wun_plan* p, const float* params, const float* grads, const float* m, const float* v, int64_t step) {
+    if (!p || !params || !grads || !m || !v) return fail(WUN_ERR_INVALID, "null argument");
+    if (step < 1) return fail(WUN_ERR_INVALID, "step is 1-based");
+    return WUN_OK;
+}
+
+// The selected tensors' floats as runs of consecutive arena floats (adjacent tensors merge), handed to
+// launch(const AdamRanges&, bool first) -> int in batches of at most WUN_ADAM_RANGES runs; first: the walk's first batch.
+template <class Launch>
+static int for_each_range_batch(const wun_plan* p, const uint8_t* select, Launch launch) {
+    AdamRanges r;
+    memset(&r, 0, sizeof(r));
+    bool first = true;
+    int rc;
+    for (size_t k = 0; k < p->tensors.size(); ++k) {
+        if (!select[k]) continue;
+        const wun_tensor_info& t = p->tensors[k];
+        long long n = 1;
+        for (int d = 0; d < t.ndim; ++d) n *= t.shape[d];
+        if (r.n > 0 && r.off[r.n - 1] + (r.cum[r.n] - r.cum[r.n - 1]) == t.offset) { r.cum[r.n] += n; continue; }
+        if (r.n == WUN_ADAM_RANGES) {
+            if ((rc = launch(r, first))) return rc;
+            first = false;
+            memset(&r, 0, sizeof(r));
+        }
+        r.off[r.n] = t.offset; r.cum[r.n + 1] = r.cum[r.n] + n; ++r.n;
+    }
+    return r.n > 0 ? launch(r, first) : WUN_OK;
+}
+
+extern "C" int wun_adam_step(const wun_plan* p, float* params, const float* grads, float* m, float* v,
+                             int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                             void* stream) {
+    return wun_adam_step_select(p, params, grads, m, v, step, lr, beta1, beta2, eps, grad_scale, stream, nullptr, 0);
+}
+
+extern "C" int wun_adam_step_select(const wun_plan* p, float* params, const float* grads, float* m, float* v,
+                                    int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                                    void* stream, const uint8_t* select, int64_t nselect) {
+    int rc;
+    if ((rc = adam_args(p, params, grads, m, v, step))) return rc;
+    if ((rc = check_nselect(p, select, nselect))) return rc;
+    const float lr_t = adam_lr_t(step, lr, beta1, beta2);
+    hipStream_t s = (hipStream_t)stream;
+    if (!select) {
+        HIP_TRY(launch_adam(params, grads, m, v, p->arena, lr_t, beta1, beta2, eps, grad_scale, s));
+        return WUN_OK;
+    }
+    return for_each_range_batch(p, select, [&](const AdamRanges& r, bool) -> int {
+        HIP_TRY(launch_adam_ranges(params, grads, m, v, r, lr_t, beta1, beta2, eps, grad_scale, s));
+        return WUN_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------------------
+// global gradient norm and the clipped Adam step (tf.clip_by_global_norm + AdamOptimizer)
+// ---------------------------------------------------------------------------------------
+// norm workspace: [0, nt) per-tensor norms, [nt] the global norm, float64 chunk partials from the next even float on
+static long long norm_partial_off(const wun_plan* p) { return ((long long)p->tensors.size() + 2) & ~1LL; }
+
+extern "C" int64_t wun_grad_norm_workspace_floats(const wun_plan* p) {
+    if (!p) return fail(WUN_ERR_INVALID, "null plan");
+    return norm_partial_off(p) + 2 * (long long)p->norm_chunks.size();
+}
+
+// host-side checks of the norm's arguments (no GPU work): the selection as a bit set and its float count
+static int norm_args(const wun_plan* p, const float* grads, const float* norm_ws, const uint8_t* select, int64_t nselect,
+                     NormSelect& sel, long long& nfloats) {
+    if (!grads || !norm_ws) return fail(WUN_ERR_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(norm_ws) & 7) return fail(WUN_ERR_INVALID, "norm_ws must be 8-byte aligned");
+    int rc;
+    if ((rc = check_nselect(p, select, nselect))) return rc;
+    const int64_t nt = (int64_t)p->tensors.size();
+    if (nt > WUN_NORM_MAX_TENSORS) return fail(WUN_ERR_UNSUPPORTED, "wun_grad_norm: more than 256 tensors");
+    memset(&sel, 0, sizeof(sel));
+    nfloats = 0;
+    for (int64_t k = 0; k < nt; ++k) {
+        if (select && !select[k]) continue;
+        sel.bits[k >> 5] |= 1u << (k & 31);
+        for (int c = p->norm_first[(size_t)k]; c < p->norm_first[(size_t)k + 1]; ++c) nfloats += p->norm_chunks[(size_t)c].len;
+    }
+    return WUN_OK;
+}
+
+static int grad_norm_launch(const wun_plan* p, const float* grads, float grad_scale, float* norm_ws, const NormSelect& sel,
+                            long long nfloats, hipStream_t s) {
+    if (!p->dev_norm_chunks) return fail(WUN_ERR_HIP, "plan was created without a usable HIP device");
+    HIP_TRY(launch_grad_norm(grads, p->dev_norm_chunks, p->dev_norm_first, (int)p->norm_chunks.size(), (int)p->tensors.size(),
+                             sel, nfloats, grad_scale, norm_ws, reinterpret_cast<double*>(norm_ws + norm_partial_off(p)), s));
+    return WUN_OK;
+}
+
+extern "C" int wun_grad_norm(const wun_plan* p, const float* grads, float grad_scale, float* norm_ws, void* stream,
+                             const uint8_t* select, int64_t nselect) {
+    if (!p) return fail(WUN_ERR_INVALID, "null plan");
+    NormSelect sel;
+    long long nfloats;
+    int rc;
+    if ((rc = norm_args(p, grads, norm_ws, select, nselect, sel, nfloats))) return rc;
+    return grad_norm_launch(p, grads, grad_scale, norm_ws, sel, nfloats, (hipStream_t)stream);
+}
+
+extern "C" int wun_adam_step_clip(const wun_plan* p, float* params, const float* grads, float* m, float* v,
+                                  int64_t step, float lr, float beta1, float beta2, float eps, float grad_scale,
+                                  float clip_norm, int32_t flags, float* norm_ws, int64_t* skipped,
+                                  void* stream, const uint8_t* select, int64_t nselect) {
+    int rc;
+    if ((rc = adam_args(p, params, grads, m, v, step))) return rc;
+    if (!(clip_norm > 0.f)) return fail(WUN_ERR_INVALID, "clip_norm must be > 0 (+INFINITY = no clipping)");
+    if (flags & ~WUN_CLIP_SKIP_NONFINITE) return fail(WUN_ERR_INVALID, "unknown flags");
+    const int skip = (flags & WUN_CLIP_SKIP_NONFINITE) ? 1 : 0;
+    if (skip && !skipped) return fail(WUN_ERR_INVALID, "skipped is required with WUN_CLIP_SKIP_NONFINITE");
+    NormSelect sel;
+    long long nfloats;
+    if ((rc = norm_args(p, grads, norm_ws, select, nselect, sel, nfloats))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = grad_norm_launch(p, grads, grad_scale, norm_ws, sel, nfloats, s))) return rc;
+    const float lr_t = adam_lr_t(step, lr, beta1, beta2);
+    const float* gnorm = norm_ws + p->tensors.size();
+    long long* cnt = skip ? reinterpret_cast<long long*>(skipped) : nullptr;
+    if (!select) {
+        HIP_TRY(launch_adam_clip(params, grads, m, v, p->arena, lr_t, beta1, beta2, eps, grad_scale, gnorm, clip_norm, skip, cnt, s));
+        return WUN_OK;
+    }
+    // every launch of a skipped step returns at once; only the first one counts it
+    return for_each_range_batch(p, select, [&](const AdamRanges& r, bool first) -> int {
+        HIP_TRY(launch_adam_clip_ranges(params, grads, m, v, r, lr_t, beta1, beta2, eps, grad_scale, gnorm, clip_norm, skip,
+                                        first ? cnt : nullptr, s));
+        return WUN_OK;
+    });
+}

@@ -1,6 +1,7 @@
 // Internal: the plan object (struct wun_plan) and the host helpers its units share -- wun_plan.hip (builder, queries),
-// wun_dispatch.hip (argument blocks, streams, autotuned dispatch), wun_step.hip (forward / backward / Adam),
-// wun_tune.hip (tuner, tuning tables), wun_op.hip (single-operator entry points).  Host code only.
+// wun_dispatch.hip (argument blocks, streams, autotuned dispatch), the training step by pass -- wun_forward.hip (forward),
+// wun_backward.hip (loss + backward), wun_optim.hip (Adam, gradient norm) --, wun_tune.hip (tuner, tuning tables),
+// wun_op.hip (single-operator entry points).  Host code only.
 #pragma once
 #include "../../include/wun.h"
 #include "wun_internal.h"
@@ -108,10 +109,43 @@ struct wun_plan {
     mutable const float* cur_ws = nullptr;
 };
 
+// The forward conv of down level i as its one or two launch geometries over the level's input x ("parts"):
+//   z[q] = sum_k W[k] x[off + stride * q + k - shift]   (0 <= stride * q + k - shift < Tin, q < Tq),
+// and `dz`, where the backward pass keeps that part's d(pre-activation).  'same' plans: the one full-rate conv.  Context plans:
+// part 0 = the stride-2 conv into the decimated stream; part 1 = the rest of the skip window -- dedup plans: its odd positions
+// (a second stride-2 conv over x shifted by t_odd0 samples; none when the window holds no odd position), else the full-rate
+// conv over the whole window (its even positions are computed a second time, both contributions add in the backward pass).
+// The level's weight gradient (MFMA and narrow form), the mix gradient and the forward window conv are all built from this.
+struct DownPart { int off, Tin, shift, stride, loader; const Buf* dz; int Tq; };
+// returns the number of parts that launch; on context plans out[1] is filled even when it does not
+inline int down_parts(const wun_plan* p, int i, DownPart out[2]) {
+    const DownShape& d = p->dsh[i];
+    const int Kd = p->cfg.filter_size;
+    if (p->same) {
+        out[0] = DownPart{0, d.t_in, (Kd - 1) / 2, 1, LOADER_DIRECT, &p->dz_skip[i], d.t_conv};
+        return 1;
+    }
+    out[0] = DownPart{0, d.t_in, 0, 2, LOADER_DEINT, &p->dz_dec[i], d.t_dec};
+    if (p->dedup) {
+        out[1] = DownPart{d.t_odd0, d.t_in - d.t_odd0, 0, 2, LOADER_DEINT, &p->dz_odd[i], d.n_odd};
+        return d.n_odd > 0 ? 2 : 1;
+    }
+    out[1] = DownPart{d.cs, d.tc + Kd - 1, 0, 1, LOADER_DIRECT, &p->dz_skip[i], d.tc};
+    return 2;
+}
+
 // ---- shared host state and helpers ----
 extern thread_local std::string g_err;   // wun_last_error()
 extern bool g_profiling;                 // while wun_profile_* is active everything runs on the caller's stream
 int fail(int code, const std::string& msg);
+
+// select / nselect of the wun_*_select entries: one byte per tensor (wun_plan_tensor order), or NULL = every tensor
+inline int check_nselect(const wun_plan* p, const uint8_t* select, int64_t nselect) {
+    const int64_t nt = (int64_t)p->tensors.size();
+    if (!select && nselect != 0 && nselect != nt) return fail(WUN_ERR_INVALID, "nselect must be 0 or num_tensors when select is NULL");
+    if (select && nselect != nt) return fail(WUN_ERR_INVALID, "nselect must equal num_tensors");
+    return WUN_OK;
+}
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \

@@ -286,35 +286,29 @@ class UnetAudioSeparator(object):
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
-        dev = self._dev()
-        if isinstance(targets, dict):
-            tg = torch.stack([torch.as_tensor(targets[n]).to(dev, torch.float32) for n in self.source_names])
-        else:
-            tg = targets.to(dev, torch.float32)
-        tg = tg.contiguous()
-        outs = self._outs[self._last_key]
-        if tuple(tg.shape) != tuple(outs.shape):
-            raise ValueError("targets shape %s != outputs shape %s" % (tuple(tg.shape), tuple(outs.shape)))
-        loss = torch.empty((), dtype=torch.float32, device=dev)
+        tg = self._stacked(targets, "targets")
+        loss = torch.empty((), dtype=torch.float32, device=self._dev())
+        fn, sel = self._backward_entry("wun_loss_backward", mask, accumulate)
+        _lib.check(fn(self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
+                      self._ws[self._last_key].data_ptr(), self._outs[self._last_key].data_ptr(), tg.data_ptr(),
+                      self.grads.data_ptr(), loss.data_ptr(), self._stream(),
+                      *self._bucket_args(bucket_starts, bucket_events), *sel))
+        return loss
+
+    @staticmethod
+    def _bucket_args(bucket_starts, bucket_events):
+        """(bucket_starts, bucket_events, nbuckets) of the backward entries: int64 arena offsets and event handles (one
+        unused element each when there are no buckets)."""
         nb = len(bucket_starts) if bucket_starts else 0
         starts = (C.c_int64 * max(nb, 1))(*([int(x) for x in bucket_starts] if nb else [0]))
         events = (C.c_void_p * max(nb, 1))(*([int(e.cuda_event) for e in bucket_events] if nb else [0]))
-        if accumulate:
-            _lib.check(self._lib.wun_loss_backward_accumulate(
-                self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
-                self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
-                self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb, *self._mask_arg(mask)))
-        elif mask is None:
-            _lib.check(self._lib.wun_loss_backward_ex(
-                self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
-                self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
-                self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb))
-        else:
-            _lib.check(self._lib.wun_loss_backward_select(
-                self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),
-                self._ws[self._last_key].data_ptr(), outs.data_ptr(), tg.data_ptr(),
-                self.grads.data_ptr(), loss.data_ptr(), self._stream(), starts, events, nb, *self._mask_arg(mask)))
-        return loss
+        return starts, events, nb
+
+    def _backward_entry(self, stem, mask, accumulate):
+        """The C entry point of a backward pass (stem "wun_loss_backward" or "wun_backward") and its trailing selection
+        arguments: <stem>_accumulate when accumulating, <stem>_ex for every variable, else <stem>_select."""
+        suffix = "_accumulate" if accumulate else "_ex" if mask is None else "_select"
+        return getattr(self._lib, stem + suffix), (() if suffix == "_ex" else self._mask_arg(mask))
 
     def _stacked(self, x, what):
         """dict source_name -> [B, Tout, C] or [S, B, Tout, C] -> one contiguous float32 [S, B, Tout, C] on the device,
@@ -350,25 +344,11 @@ class UnetAudioSeparator(object):
 
     def _run_backward(self, ws, outs, dout, grads, d_mix, bucket_starts=None, bucket_events=None, mask=None,
                       accumulate=False):
-        nb = len(bucket_starts) if bucket_starts else 0
-        starts = (C.c_int64 * max(nb, 1))(*([int(x) for x in bucket_starts] if nb else [0]))
-        events = (C.c_void_p * max(nb, 1))(*([int(e.cuda_event) for e in bucket_events] if nb else [0]))
-        if accumulate:
-            gp = grads.data_ptr() if (grads is not None and (mask is None or mask.any())) else None
-            _lib.check(self._lib.wun_backward_accumulate(
-                self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
-                gp, d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb,
-                *self._mask_arg(mask)))
-            return
-        if mask is None:
-            _lib.check(self._lib.wun_backward_ex(
-                self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
-                grads.data_ptr(), d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb))
-            return
-        gp = grads.data_ptr() if (grads is not None and mask.any()) else None     # (input-only: grads is not touched)
-        _lib.check(self._lib.wun_backward_select(
-            self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
-            gp, d_mix.data_ptr() if d_mix is not None else None, self._stream(), starts, events, nb, *self._mask_arg(mask)))
+        fn, sel = self._backward_entry("wun_backward", mask, accumulate)
+        gp = grads.data_ptr() if (grads is not None and (mask is None or mask.any())) else None   # (input-only: not touched)
+        _lib.check(fn(self._active.handle, self.params.data_ptr(), None, ws.data_ptr(), outs.data_ptr(), dout.data_ptr(),
+                      gp, d_mix.data_ptr() if d_mix is not None else None, self._stream(),
+                      *self._bucket_args(bucket_starts, bucket_events), *sel))
 
     def module(self):
         """This separator as a torch.nn.Module (wave_u_net_amd.autograd.WaveUNet): get_output under torch.autograd, the
@@ -382,11 +362,7 @@ class UnetAudioSeparator(object):
         dev = self._dev()
         mix = torch.as_tensor(input).to(device=dev, dtype=torch.float32).contiguous()
         self.get_output(mix, True)                         # allocates plan / workspace / outputs
-        if isinstance(targets, dict):
-            tg = torch.stack([torch.as_tensor(targets[n]).to(dev, torch.float32) for n in self.source_names])
-        else:
-            tg = targets.to(dev, torch.float32)
-        tg = tg.contiguous()
+        tg = self._stacked(targets, "targets")
         loss = torch.empty((), dtype=torch.float32, device=dev)
         _lib.check(self._lib.wun_plan_tune(
             self._active.handle, self.params.data_ptr(), mix.data_ptr(), self._ws[self._last_key].data_ptr(),
