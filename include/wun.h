@@ -385,6 +385,53 @@ int     wun_resample_design(int32_t up, int32_t down, float* table_host, int64_t
 int     wun_resample(const float* x, int64_t n_in, int32_t c_in, float* y, int64_t y_offset, int64_t n_out,
                      int32_t c_out, const float* table_dev, int32_t up, int32_t down, void* stream);
 
+/* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
+ * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
+ * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is
+ * [track_frames, C], the result [S, pred_frames, C], C = num_channels of the plan.  Every buffer is the caller's; nothing
+ * allocates device memory or synchronises, and every argument check runs before any GPU work. */
+
+/* The hop table of Evaluate.py:125-128: hops at 0, Tout, 2 Tout, ... with the last one re-aligned to n_frames - Tout.
+ * Returns the number of hops, ceil(n_frames / output_frames), and writes them to positions[cap] (NULL: count only).
+ * WUN_ERR_INVALID for output_frames < 1, n_frames < output_frames or a cap below the count. */
+int64_t wun_separate_positions(int64_t output_frames, int64_t n_frames, int64_t* positions, int64_t cap);
+
+/* wun_forward, with row b of the mix read from a track: row b < npos is track_tc[positions[b] .. positions[b] + Tin)
+ * (frames), rows npos .. batch - 1 are zeros (a short last chunk needs no second plan).
+ *   track_tc  : device, [track_frames, C]
+ *   positions : HOST, npos window starts in frames (copied into the launch; free to reuse after the call returns)
+ * Everything else as wun_forward.  One gather kernel replaces wun_forward's layout pass and writes the same floats to
+ * the same workspace elements; the rest of the forward is the same launch sequence, so outputs row b is bit-identical to
+ * wun_forward on the materialised [batch, Tin, C] batch.  positions[b] * C need not be 16-byte aligned.
+ * WUN_ERR_INVALID for a null pointer, npos < 1, npos > batch, a window outside [0, track_frames], a track that is not
+ * 4-byte or a workspace that is not 16-byte aligned. */
+int wun_forward_windows(const wun_plan* plan, const float* params, const float* track_tc, int64_t track_frames,
+                        const int64_t* positions, int64_t npos, float* workspace, float* outputs, int training,
+                        void* stream);
+
+/* preds[s][positions[b] + t][c] = outputs[s][b][t][c] for b < npos, hops taken in index order: where windows overlap the
+ * HIGHEST-indexed one wins (Evaluate.py:139 with the re-aligned last hop written last).  Destination-driven: the host cuts
+ * the windows into disjoint runs of frames, one writer per float -- no race, no atomics, deterministic.  Frames no window
+ * covers are not written.
+ *   outputs   : device, [S, batch, Tout, C] (what the forward wrote)
+ *   positions : HOST, npos window starts in frames of preds
+ *   preds     : device, [S, pred_frames, C]
+ * WUN_ERR_INVALID for a null pointer, npos < 1, npos > batch, a window outside [0, pred_frames]. */
+int wun_scatter_windows(const wun_plan* plan, const float* outputs, const int64_t* positions, int64_t npos,
+                        float* preds, int64_t pred_frames, void* stream);
+
+/* The whole loop: hops of wun_separate_positions(Tout, n_frames) in chunks of the plan's batch, each chunk
+ * wun_forward_windows(training = 0) then wun_scatter_windows, all on `stream` (chunk k + 1 reuses workspace and outputs
+ * behind the scatter of chunk k: stream order is the only ordering needed).
+ *   track_tc  : device, [n_frames + 2 pad, C], pad = (Tin - Tout) / 2: the track with `pad` zero frames on both sides
+ *               (Evaluate.py:121-122; wun_resample with y_offset = pad into a zeroed buffer produces exactly this)
+ *   preds     : device, [S, n_frames, C]; every frame is written
+ * WUN_ERR_INVALID for a null pointer, n_frames < Tout (pad short tracks with zeros behind, Evaluate.py:108-113) or an odd
+ * Tin - Tout.  A plan with a longer Tin / Tout (wun_get_padding on a multiple of the hop, or on the whole track) pays the
+ * context Tin - Tout once per hop instead of once per default hop: see DESIGN.md 5.8 for what that changes. */
+int wun_separate_track(const wun_plan* plan, const float* params, const float* track_tc, int64_t n_frames,
+                       float* workspace, float* outputs, float* preds, void* stream);
+
 /* ---- single operators (used by the parity tests and for per-kernel profiling) ---------- */
 
 /* y[b][co][q] = act(bias[co] + sum_{k,ci} w[k][ci][co] * x[b][ci][q*stride + k - pad_left]),

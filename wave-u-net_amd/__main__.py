@@ -11,7 +11,8 @@
 `with` arguments: `cfg.<named config>` (any of wave_u_net_amd.NAMED_CONFIGS), `model_config.<key>=<value>`
 overrides, and the command's own options as `<name>=<value>`.  data_root holds
 train|valid|test/<track>/<source>.wav|.npy (+ optional mix.wav) at expected_sr, or at any rate with the option
-`resample=1` (train, test).  `predict` takes a WAV at any rate and writes the estimates at that rate.  Multi-GPU:
+`resample=1` (train, test).  `predict` takes a WAV at any rate and writes the estimates at that rate;
+`hop_frames=<N|track>` makes its hops N output frames long / one hop over the whole track (default: num_frames).  Multi-GPU:
 launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.
 """
 import ast
@@ -73,7 +74,11 @@ def main(argv=None):
     else:
         if "input_path" not in opts:
             raise SystemExit("predict needs input_path=<mixture.wav>")
-        evaluate.produce_source_estimates(model_config, opts.get("model_path"), opts["input_path"], opts.get("output_path"))
+        hop = opts.get("hop_frames")                               # hop_frames=<N|track>: evaluate.separate_track's option
+        if hop is not None and hop != "track" and (isinstance(hop, bool) or not isinstance(hop, int) or hop < 1):
+            raise SystemExit("hop_frames must be a positive frame count or 'track', got %r" % (hop,))
+        evaluate.produce_source_estimates(model_config, opts.get("model_path"), opts["input_path"], opts.get("output_path"),
+                                          hop_frames=hop)
 
 
 if __name__ == "__main__":

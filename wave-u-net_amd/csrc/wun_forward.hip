@@ -45,11 +45,10 @@ static int forward_up_path(const wun_plan* p, const float* params, float* ws, hi
     return WUN_OK;
 }
 
-// forward: get_output (UnetAudioSeparator.py:85-144)
-extern "C" int wun_forward(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
-                           float* outputs, int training, void* stream) {
-    if (!p || !params || !mix_btc || !ws || !outputs) return fail(WUN_ERR_INVALID, "null argument");
-    hipStream_t s = (hipStream_t)stream;
+// forward: get_output (UnetAudioSeparator.py:85-144).  The mix rows come from mix_btc, or -- win != nullptr, wun_forward_windows --
+// are gathered from a track (wun_track.hip); everything after that first pass is the same launch sequence.
+int forward_pass(const wun_plan* p, const float* params, const float* mix_btc, const MixWindows* win, float* ws,
+                 float* outputs, int training, hipStream_t s) {
     const int L = p->L, Kd = p->cfg.filter_size;
     const bool same = p->same;
     const int padD = same ? (Kd - 1) / 2 : 0;
@@ -77,7 +76,8 @@ extern "C" int wun_forward(const wun_plan* p, const float* params, const float* 
         p->wt_ready = true;
         side_used = true;
     }
-    HIP_TRY(launch_btc_to_ncw(mix_btc, ws + p->mix_ncw.off, p->B, p->Tin, p->C, p->mix_ncw.pitch, s));
+    if (win) HIP_TRY(launch_gather_windows(*win, ws + p->mix_ncw.off, p->B, p->Tin, p->C, p->mix_ncw.pitch, s));
+    else HIP_TRY(launch_btc_to_ncw(mix_btc, ws + p->mix_ncw.off, p->B, p->Tin, p->C, p->mix_ncw.pitch, s));
     if (p->head16 && training)
         HIP_TRY(launch_cast_rows_bf16(ws + p->mix_ncw.off, ws + p->mix16.off, (long long)p->B * p->C, p->Tin, p->mix_ncw.pitch,
                                       p->mix16.pitch, s));
@@ -185,4 +185,10 @@ extern "C" int wun_forward(const wun_plan* p, const float* params, const float* 
     for (int i = 0; i < p->Sh; ++i) hoff[i] = p->head[i].woff;
     HIP_TRY(launch_head_fwd_off(h, hoff, s));
     return WUN_OK;
+}
+
+extern "C" int wun_forward(const wun_plan* p, const float* params, const float* mix_btc, float* ws,
+                           float* outputs, int training, void* stream) {
+    if (!p || !params || !mix_btc || !ws || !outputs) return fail(WUN_ERR_INVALID, "null argument");
+    return forward_pass(p, params, mix_btc, nullptr, ws, outputs, training, (hipStream_t)stream);
 }

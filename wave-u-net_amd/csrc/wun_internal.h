@@ -304,6 +304,18 @@ hipError_t launch_head_grad_off(const HeadArgs& a, const long long* hoff, hipStr
 hipError_t launch_loss_finish(const float* partial, int n, float scale, float* loss, hipStream_t s);
 hipError_t launch_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pitch,
                              hipStream_t s);
+// ---- track windows (wun_track.hip): the mix rows of a forward pass read straight from a [track_frames, C] track, and the
+// estimates of a batch of hops written straight into [S, pred_frames, C] ----
+// Row b < npos of the batch is track[pos[b] .. pos[b] + Tin) (frames; host table, every window checked against the track by
+// the caller); rows >= npos are zeros.
+struct MixWindows { const float* track; const int64_t* pos; int npos; };
+// what launch_btc_to_ncw writes for the materialised batch: the same floats at the same NCW elements (dst 16-byte aligned,
+// pitch a multiple of 4 floats; the floats of a row's last quad beyond T -- row padding nothing reads -- are written as 0)
+hipError_t launch_gather_windows(const MixWindows& w, float* dst, int B, int T, int C, int pitch, hipStream_t s);
+// One run of frames of one hop: preds[s][dst .. dst + len) = outputs[s][row][src .. src + len) for every source s (frames)
+struct ScatterSeg { long long dst; int row, src, len; };
+hipError_t launch_scatter_segments(const float* outputs, float* preds, const ScatterSeg* segs, int nsegs, int S, int B,
+                                   int Tout, int C, long long pred_frames, hipStream_t s);
 hipError_t launch_make_wt(const float* params, float* ws, const WtDesc* dev_descs, int ndesc,
                           int max_elems, hipStream_t s);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr_t,

@@ -161,6 +161,10 @@ inline WgradArgs wgrad_shape_only(int B, int C0, int C1, int KW, int loader, int
     return w;
 }
 
+// wun_forward.hip: the forward pass behind wun_forward (win == nullptr: rows from mix_btc) and wun_forward_windows
+int forward_pass(const wun_plan* p, const float* params, const float* mix_btc, const MixWindows* win, float* ws,
+                 float* outputs, int training, hipStream_t s);
+
 // wun_dispatch.hip
 ConvArgs conv_base(const wun_plan* p);
 void set_src0(ConvArgs& a, const float* ws, const Buf& b, int off, int C);

@@ -8,9 +8,10 @@ the extra padding (:141-143).  MI355X-first difference: hops are evaluated `batc
 one get_output call instead of one sess.run per hop (identical results, far fewer launches).
 predict_track takes audio that is already at model_config["expected_sr"] and tiles on the host.
 separate_track is the whole of Evaluate.predict (:59-80) for a file at ANY rate, on the device the separator lives on:
-downmix + resampling + context padding in one kernel (resample.py, wun_resample), hop windows gathered and estimates
-scattered on the GPU, resampling back + trim + channel duplication in one kernel per source, one upload and one
-download per track.
+downmix + resampling + context padding in one kernel (resample.py, wun_resample), the hop loop in one C call
+(wun_separate_track: windows gathered from the track by the forward's first kernel, estimates scattered by one kernel
+per chunk), resampling back + trim + channel duplication in one kernel per source, one upload and one download per track.
+hop_frames lets a hop be longer than the reference's num_frames, up to the whole track.
 """
 import numpy as np
 import torch
@@ -71,16 +72,66 @@ def _hop_positions(n_frames, output_frames):
     return positions
 
 
-def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16):
+def hop_geometry(model_config, separator, n_res, hop_frames=None):
+    """(input_frames, output_frames) of one hop.  hop_frames None: get_padding of model_config["num_frames"], the
+    reference's hop; an int N: get_padding([1, N, 0]); "track": get_padding of the whole n_res-frame track, one hop.
+    For same-padding models N / the track length is first rounded up to a multiple of 2 ** num_layers."""
+    if hop_frames is None:
+        want = int(model_config["num_frames"])
+    elif hop_frames == "track":
+        want = max(int(n_res), 1)
+    else:
+        want = int(hop_frames)
+        if isinstance(hop_frames, bool) or want < 1:
+            raise ValueError("hop_frames = %r must be a positive frame count, 'track' or None" % (hop_frames,))
+    if hop_frames is not None and not model_config["context"]:
+        m = 2 ** int(model_config["num_layers"])             # same padding: the length must halve num_layers times
+        want = -(-want // m) * m                              # (UnetAudioSeparator.py:121 asserts it)
+    in_shape, out_shape = separator.get_padding(np.array([1, want, 0]))
+    return int(in_shape[1]), int(out_shape[1])
+
+
+def budget_batch_hops(separator, batch_hops, n_hops, input_frames, default_input_frames, workspace_bytes=None):
+    """Hops per forward pass of a long-hop plan: the largest b <= min(batch_hops, n_hops) with
+    b * 4 * workspace_floats(1, input_frames) <= workspace_bytes, at least 1 (one hop cannot be split).  workspace_bytes
+    None: 4 * workspace_floats(batch_hops, default_input_frames), the workspace the default tiling takes at batch_hops.
+    Both figures are wun_plan_query's (separator.workspace_floats); a separator without that method is not limited."""
+    b = max(1, min(int(batch_hops), int(n_hops)))
+    query = getattr(separator, "workspace_floats", None)
+    if query is None:
+        return b
+    if workspace_bytes is None:
+        workspace_bytes = 4 * query(int(batch_hops), default_input_frames)
+    per_hop = 4 * query(1, input_frames)
+    return max(1, min(b, int(workspace_bytes) // per_hop))
+
+
+def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, hop_frames=None, workspace_bytes=None):
     """Evaluate.predict (Evaluate.py:59-80) around predict_track (:82-145) for audio at any sample rate, without the
     host in the loop.  mix_audio: [n_frames, n_channels] float array or tensor at mix_sr Hz.  Returns {source_name: float32
     numpy [n_frames, channels]} at mix_sr: channels is the input's count, except that a stereo model on a mono file
     gives its two channels, as the reference does.
 
-    Everything between the upload of mix_audio and the download of the estimates runs on `separator.device` (a
-    separator without that attribute -- a numpy stand-in -- runs the same steps on CPU tensors).  Same hop positions,
-    chunking and get_output batches as predict_track: at mix_sr == expected_sr the estimates are bit-identical to
-    predict_track's (tiled to the input's channels for a mono model)."""
+    Everything between the upload of mix_audio and the download of the estimates runs on `separator.device`: the hop
+    windows are read from the padded track and the estimates written into the track-long result by the library (one
+    wun_separate_track call when the hops divide into whole chunks, see below) -- no stacked batch, no per-source copies.  (A separator without a device -- a numpy
+    stand-in -- runs the same steps on CPU tensors through get_output.)
+
+    hop_frames=None (default): the reference's hops -- same hop positions, chunking and plans as predict_track: at
+    mix_sr == expected_sr the estimates are bit-identical to predict_track's (tiled to the input's channels for a mono
+    model).  The kernels' split choices depend on a plan's batch, so a last chunk shorter than batch_hops runs on the plan
+    of ITS batch, as predict_track's does (chunk by chunk through wun_forward_windows / wun_scatter_windows, the two
+    halves of wun_separate_track); every other track is the one call.
+
+    hop_frames=N / "track": hops of get_padding([1, N, 0]) output frames / one hop over the whole resampled track.  A
+    context model pays its context (input - output frames) once per hop, so long hops convolve far fewer samples per
+    output sample (M1 + context: 9.0 at the default hop, 1.8 at 10 hops' length).  What comes out is the reference's own
+    output for a config with that num_frames -- the same network on another alignment of the hop grid -- NOT the output
+    of the default tiling: the decimating levels sample other positions, so the two differ as two tilings of the reference
+    differ.  For same-padding models a long hop also moves the zero-padded hop edges (fewer of them, elsewhere).  Short
+    tracks are zero-padded to one hop's OUTPUT (the default pads to its input, Evaluate.py:108-113).  batch_hops is
+    lowered until batch_hops * workspace_floats of the long plan fits workspace_bytes (budget_batch_hops; default: the
+    workspace of the default tiling at batch_hops, from wun_plan_query); a last chunk runs on the same plan with zero rows."""
     from . import resample as rs
     device = torch.device(getattr(separator, "device", None) or "cpu")
     x = mix_audio if torch.is_tensor(mix_audio) else torch.from_numpy(np.ascontiguousarray(np.asarray(mix_audio, dtype=np.float32)))
@@ -91,30 +142,30 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16):
     up, down = rs.ratio(mix_sr, model_config["expected_sr"])
     n_res = rs.frames(n_in, up, down)
 
-    in_shape, out_shape = separator.get_padding(np.array([1, model_config["num_frames"], 0]))
-    input_frames, output_frames = int(in_shape[1]), int(out_shape[1])
-    n_frames = max(n_res, input_frames)                                          # :108-113 (short inputs: zeros behind)
+    input_frames, output_frames = hop_geometry(model_config, separator, n_res, hop_frames)
+    # :108-113 (short inputs: zeros behind)
+    n_frames = max(n_res, input_frames if hop_frames is None else output_frames)
     pad = (input_frames - output_frames) // 2                                    # :121-122
     padded = torch.zeros((n_frames + 2 * pad, C), dtype=torch.float32, device=device)
     rs.resample_into(x, padded, pad, n_res, up, down)                            # downmix / duplicate, resample, pad
 
     names = list(model_config["source_names"])
-    preds = torch.zeros((len(names), n_frames, C), dtype=torch.float32, device=device)   # :117
     positions = _hop_positions(n_frames, output_frames)
-    for k in range(0, len(positions), batch_hops):
-        chunk = positions[k:k + batch_hops]
-        batch = torch.stack([padded[p:p + input_frames] for p in chunk])         # strided views -> [B, Tin, C]
-        outs = separator.get_output(batch if device.type != "cpu" else batch.numpy(), False)
-        run = 1                                                                  # leading hops at consecutive multiples
-        while run < len(chunk) and chunk[run] == chunk[0] + run * output_frames:
-            run += 1
-        for si, n in enumerate(names):
-            o = outs[n]
-            o = o if torch.is_tensor(o) else torch.from_numpy(np.ascontiguousarray(np.asarray(o, dtype=np.float32)))
-            o = o.to(device)
-            preds[si, chunk[0]:chunk[0] + run * output_frames].view(run, output_frames, C).copy_(o[:run])
-            for bi in range(run, len(chunk)):                                    # the re-aligned last hop, written last
-                preds[si, chunk[bi]:chunk[bi] + output_frames] = o[bi]           # :139
+    if hop_frames is not None:
+        batch_hops = budget_batch_hops(separator, batch_hops, len(positions), input_frames,
+                                       hop_geometry(model_config, separator, n_res)[0], workspace_bytes)
+    if device.type != "cpu" and hasattr(separator, "separate_padded"):
+        preds = torch.empty((len(names), n_frames, C), dtype=torch.float32, device=device)   # every frame is written
+        batch = min(batch_hops, len(positions))
+        if hop_frames is not None or len(positions) % batch == 0:
+            separator.separate_padded(padded, n_frames, batch, frames=input_frames, out=preds)
+        else:
+            for k in range(0, len(positions), batch):                            # the last chunk on the plan of its batch
+                chunk = positions[k:k + batch]
+                separator.get_output_windows(padded, chunk, False, frames=input_frames)
+                separator.scatter_windows(chunk, preds, frames=input_frames)
+    else:
+        preds = _separate_cpu(separator, padded, positions, batch_hops, input_frames, output_frames, names, n_frames, C)
 
     # back to mix_sr, cut to the input's length, mono estimates duplicated to the input's channels (:64-67)
     c_out = ch if (C == 1 and ch > 1) else C
@@ -129,11 +180,32 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16):
     return {n: host[si] for si, n in enumerate(names)}
 
 
-def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None):
+def _separate_cpu(separator, padded, positions, batch_hops, input_frames, output_frames, names, n_frames, C):
+    """The hop loop on CPU tensors through separator.get_output (numpy stand-ins)."""
+    device = padded.device
+    preds = torch.zeros((len(names), n_frames, C), dtype=torch.float32, device=device)   # :117
+    for k in range(0, len(positions), batch_hops):
+        chunk = positions[k:k + batch_hops]
+        batch = torch.stack([padded[p:p + input_frames] for p in chunk])         # strided views -> [B, Tin, C]
+        outs = separator.get_output(batch if device.type != "cpu" else batch.numpy(), False)
+        run = 1                                                                  # leading hops at consecutive multiples
+        while run < len(chunk) and chunk[run] == chunk[0] + run * output_frames:
+            run += 1
+        for si, n in enumerate(names):
+            o = outs[n]
+            o = o if torch.is_tensor(o) else torch.from_numpy(np.ascontiguousarray(np.asarray(o, dtype=np.float32)))
+            o = o.to(device)
+            preds[si, chunk[0]:chunk[0] + run * output_frames].view(run, output_frames, C).copy_(o[:run])
+            for bi in range(run, len(chunk)):                                    # the re-aligned last hop, written last
+                preds[si, chunk[bi]:chunk[bi] + output_frames] = o[bi]           # :139
+    return preds
+
+
+def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None, hop_frames=None):
     """Evaluate.produce_source_estimates (Evaluate.py:160-194): separate one mixture file with a
     checkpoint and write <input file name>_<source>.wav next to it (or into output_path), at the input file's sample rate
     and length.  WAV/NPY input at any rate (an .npy is taken to be at expected_sr; no MP3 decoding here): the separation runs
-    through separate_track.  Returns {source: [T, C]}."""
+    through separate_track (hop_frames: its option of that name).  Returns {source: [T, C]}."""
     import os
     from scipy.io import wavfile
     from . import datasets
@@ -145,7 +217,7 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
-    preds = separate_track(model_config, sep, audio, sr)
+    preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames)
     folder, name = os.path.split(input_path)
     if output_path is None:
         output_path = folder

@@ -233,12 +233,7 @@ class UnetAudioSeparator(object):
         plan = self._plan(mix.shape[0], mix.shape[1])
         self._ensure_variables(plan)
         key = (mix.shape[0], mix.shape[1])
-        if key not in self._ws:
-            self._ws[key] = torch.empty(int(plan.info.workspace_floats), dtype=torch.float32, device=dev)
-            self._outs[key] = torch.empty((len(self.source_names), mix.shape[0],
-                                           int(plan.info.output_frames), self.num_channels),
-                                          dtype=torch.float32, device=dev)
-        ws, outs = self._ws[key], self._outs[key]
+        ws, outs = self._buffers(plan, key)
         _lib.check(self._lib.wun_forward(plan.handle, self.params.data_ptr(), mix.data_ptr(),
                                          ws.data_ptr(), outs.data_ptr(), 1 if training else 0,
                                          self._stream()))
@@ -246,6 +241,99 @@ class UnetAudioSeparator(object):
         self._active, self._last_mix, self._last_key = plan, mix, key
         self._last_training = bool(training)
         return {name: outs[i] for i, name in enumerate(self.source_names)}
+
+    # ------------------------------------------------------------------ whole tracks (wun_forward_windows / wun_separate_track)
+    def _buffers(self, plan, key):
+        """(workspace, outputs [S, B, Tout, C]) of the plan `key` = (batch, input frames), allocated on first use."""
+        if key not in self._ws:
+            dev = self._dev()
+            self._ws[key] = torch.empty(int(plan.info.workspace_floats), dtype=torch.float32, device=dev)
+            self._outs[key] = torch.empty((len(self.source_names), key[0], int(plan.info.output_frames), self.num_channels),
+                                          dtype=torch.float32, device=dev)
+        return self._ws[key], self._outs[key]
+
+    def _default_frames(self):
+        return int(self.get_padding([1, self.model_config["num_frames"], 0])[0][1])
+
+    def _track(self, track):
+        if not torch.is_tensor(track):
+            track = torch.as_tensor(np.asarray(track, dtype=np.float32))
+        track = track.to(device=self._dev(), dtype=torch.float32).contiguous()
+        if track.dim() != 2 or track.shape[1] != self.num_channels:
+            raise ValueError("track must be [frames, %d]" % self.num_channels)
+        return track
+
+    @staticmethod
+    def _positions_arg(positions):
+        pos = np.ascontiguousarray(np.asarray(positions, dtype=np.int64).reshape(-1))
+        return pos, pos.ctypes.data_as(C.POINTER(C.c_int64))
+
+    def workspace_floats(self, batch, frames):
+        """wun_plan_info.workspace_floats of the plan for `batch` excerpts of `frames` input frames (wun_plan_query)."""
+        return int(self._plan(batch, frames).info.workspace_floats)
+
+    def get_output_windows(self, track, positions, training=False, frames=None, batch=None):
+        """get_output on the batch whose row b is track[positions[b] : positions[b] + frames], without building that batch
+        (wun_forward_windows: the rows are gathered from the track by the forward's first kernel).  track: [track_frames,
+        num_channels] float32; frames: input frames of a hop (default: get_padding of model_config["num_frames"]); batch:
+        the plan's batch (default len(positions); rows past the positions are zeros).  Returns what get_output returns --
+        bit-identical to get_output on the stacked rows with the same batch.  `training` only selects the forward's own
+        behaviour (True: no AudioClip): there is no materialised mix, so loss_and_gradients / backward refuse to run
+        after this call (RuntimeError) -- use get_output for a training step."""
+        track = self._track(track)
+        pos, pos_p = self._positions_arg(positions)
+        key = (int(batch) if batch is not None else int(pos.size), int(frames) if frames is not None else self._default_frames())
+        plan = self._plan(*key)
+        self._ensure_variables(plan)
+        ws, outs = self._buffers(plan, key)
+        _lib.check(self._lib.wun_forward_windows(plan.handle, self.params.data_ptr(), track.data_ptr(), int(track.shape[0]),
+                                                 pos_p, int(pos.size), ws.data_ptr(), outs.data_ptr(), 1 if training else 0,
+                                                 self._stream()))
+        self._ws_gen[key] = self._ws_gen.get(key, 0) + 1
+        self._active, self._last_key = plan, key
+        self._last_mix, self._last_training = None, False      # (no materialised mix: the backward entries need get_output)
+        return {name: outs[i] for i, name in enumerate(self.source_names)}
+
+    def scatter_windows(self, positions, preds, frames=None, batch=None):
+        """preds[s, positions[b] : positions[b] + Tout] = the estimates of hop b of the last get_output_windows /
+        get_output with the same (batch, frames), hops in index order: where hops overlap the last one wins
+        (wun_scatter_windows).  preds: [S, pred_frames, num_channels] float32 on the device, contiguous."""
+        pos, pos_p = self._positions_arg(positions)
+        key = (int(batch) if batch is not None else int(pos.size), int(frames) if frames is not None else self._default_frames())
+        plan = self._plan(*key)
+        if key not in self._outs:
+            raise RuntimeError("no outputs for batch %d, %d frames: run get_output_windows first" % key)
+        assert preds.is_contiguous() and preds.dtype == torch.float32 and preds.dim() == 3
+        assert preds.shape[0] == len(self.source_names) and preds.shape[2] == self.num_channels
+        _lib.check(self._lib.wun_scatter_windows(plan.handle, self._outs[key].data_ptr(), pos_p, int(pos.size),
+                                                 preds.data_ptr(), int(preds.shape[1]), self._stream()))
+        return preds
+
+    def separate_padded(self, track, n_frames, batch_hops, frames=None, out=None):
+        """The hop loop of Evaluate.predict_track (Evaluate.py:113-143) in one call (wun_separate_track).  track:
+        [n_frames + 2 pad, num_channels], the track with pad = (input - output frames) // 2 zero frames on both sides;
+        batch_hops: hops per forward pass (the plan's batch; a short last chunk runs on the same plan with zero rows);
+        frames: input frames of a hop (default: get_padding of model_config["num_frames"]).  Returns the estimates
+        [S, n_frames, num_channels] on the device (`out` when given).  No host synchronisation."""
+        track = self._track(track)
+        key = (int(batch_hops), int(frames) if frames is not None else self._default_frames())
+        plan = self._plan(*key)
+        self._ensure_variables(plan)
+        ws, outs = self._buffers(plan, key)
+        n_frames = int(n_frames)
+        pad2 = int(plan.info.input_frames - plan.info.output_frames)
+        if track.shape[0] != n_frames + pad2:
+            raise ValueError("track has %d frames, expected n_frames + 2 pad = %d" % (track.shape[0], n_frames + pad2))
+        if out is None:
+            out = torch.empty((len(self.source_names), n_frames, self.num_channels), dtype=torch.float32, device=self._dev())
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (len(self.source_names), n_frames,
+                                                                                             self.num_channels)
+        _lib.check(self._lib.wun_separate_track(plan.handle, self.params.data_ptr(), track.data_ptr(), n_frames,
+                                                ws.data_ptr(), outs.data_ptr(), out.data_ptr(), self._stream()))
+        self._ws_gen[key] = self._ws_gen.get(key, 0) + 1
+        self._active, self._last_key = plan, key
+        self._last_mix, self._last_training = None, False
+        return out
 
     # ------------------------------------------------------------------ training step pieces
     def select_mask(self, variables):
