@@ -385,6 +385,51 @@ int     wun_resample_design(int32_t up, int32_t down, float* table_host, int64_t
 int     wun_resample(const float* x, int64_t n_in, int32_t c_in, float* y, int64_t y_offset, int64_t n_out,
                      int32_t c_out, const float* table_dev, int32_t up, int32_t down, void* stream);
 
+/* ---- BSS Eval v4 scoring: lagged correlations and window energies -----------
+ * The two heavy steps of scoring a separation the way museval's `v4` mode does (Evaluate.py:146-158): the correlations
+ * the track's 512-tap projection filters are solved from, and, per window and source, the projections on those filters
+ * with the eight energies SDR / ISR / SIR / SAR are ratios of.  The solve between the two is the caller's (float64,
+ * any LAPACK; wave_u_net_amd.bsseval does it with torch.linalg).
+ *   refs, ests : device, float32 [S, n, C] channel-last: references and estimates, one sample rate, same source order
+ *   A = S * C reference signals, signal a = j * C + c;  L = filters_len in 1..512;  signals are zero outside [0, n)
+ * Everything is accumulated in float64 in ONE order fixed by the sizes: correlations in chunks of 16384 frames, each an
+ * FMA chain in ascending time, the chunks then added in ascending order; energies in tiles of 256 output frames, each
+ * reduced by one fixed tree, the tiles then added in ascending order (tiles count from the window's start).  No atomics:
+ * the bits do not depend on the grid, the stream, pointer alignment or where a track lies in a buffer.
+ * Every buffer is the caller's; nothing allocates or synchronises, and every argument check runs before any GPU work.
+ * All entries: WUN_ERR_INVALID for a null pointer, S < 1, C not 1 or 2, L outside 1..512 or n < 1. */
+
+/* Host: the window table.  window, hop in frames (museval: int(1.0 * sr) each); nwin = (n - window + hop) / hop windows
+ * [k hop, k hop + window), the LAST one extended to end at n; n < window or window == 0 (no windowing): one window
+ * [0, n).  Returns the count and writes starts[cap] / lengths[cap] (both NULL: count only).  WUN_ERR_INVALID for
+ * n < 1, window < 0, hop < 1 with a window, one table NULL without the other, or a cap below the count. */
+int64_t wun_bss_windows(int64_t n, int64_t window, int64_t hop, int64_t* starts, int64_t* lengths, int64_t cap);
+
+/* float64 elements of `scratch` that serve both entries below: the larger of ceil(n / 16384) * A * 2A * L (correlation
+ * partials) and min(nwin, 64) * S * ceil((max_len + L - 1) / 256) * 8 (energy partials), max_len = the longest window.
+ * Negative wun_status for bad arguments (also nwin < 0 or max_len outside 0..n). */
+int64_t wun_bss_scratch_doubles(int32_t S, int64_t n, int32_t C, int32_t L, int64_t nwin, int64_t max_len);
+
+/* R[a][b][l] = sum_t s_a[t] * s_b[t + l] and D[a][q][l] = sum_t s_a[t] * est_q[t + l] for l in [0, L), every ordered
+ * pair: device float64 [A][A][L] each (q = j * C + c of the estimates).  Negative lags are not stored:
+ * r_ab[-l] = R[b][a][l].  One launch covers R and D (each staged sample feeds up to 4 x 4 pairs) plus one finish launch. */
+int wun_bss_correlations(const float* refs, const float* ests, int32_t S, int64_t n, int32_t C, int32_t L,
+                         double* R, double* D, double* scratch, void* stream);
+
+/* energies[k][j][0..8) for window k < nwin and source j, device float64 [nwin][S][8], over the w + L - 1 output frames of
+ * the window's slices (w = lengths[k]; slices zero-extended):
+ *   0 E(s)  1 E(est)  2 E(est - s)  3 E(P_own - s)  4 E(P_own)  5 E(P_all - P_own)  6 E(P_all)  7 E(est - P_all)
+ *   P_all[u][c] = sum_a sum_l c_all[j][a][l][c] * s_a[start + u - l],  P_own the same over source j's own C signals with
+ *   c_own[j][c'][l][c]; only frames of the WINDOW's slice enter (u - l in [0, w)).  E sums squares over frames and channels.
+ *   c_all : device float64 [S][A][L][C];  c_own : device float64 [S][C][L][C];  both NULL: the filter-free form -- only
+ *           energies 0..2 are computed (3..7 are written as 0), each audio float is read once, L is not used beyond its check
+ *   starts, lengths : HOST, nwin windows in frames (wun_bss_windows; copied into the launches, 64 windows per launch)
+ * WUN_ERR_INVALID also for nwin < 1, a window outside [0, n) or one filter pointer NULL without the other;
+ * WUN_ERR_UNSUPPORTED with filters when A = S * C > 8 (the projection stages A * (255 + L) float64 in LDS). */
+int wun_bss_window_energies(const float* refs, const float* ests, int32_t S, int64_t n, int32_t C, int32_t L,
+                            const double* c_all, const double* c_own, const int64_t* starts, const int64_t* lengths,
+                            int64_t nwin, double* energies, double* scratch, void* stream);
+
 /* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
  * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
  * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is

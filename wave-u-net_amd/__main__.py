@@ -6,14 +6,17 @@
   python -m wave_u_net_amd train   with cfg.m1_context synthetic=1 experiment_id=7
   python -m wave_u_net_amd predict with cfg.full model_path=ckpt.npz input_path=mix.wav output_path=out
   python -m wave_u_net_amd test    with cfg.baseline model_path=ckpt.npz data_root=DATA partition=valid
+  python -m wave_u_net_amd evaluate with cfg.full model_path=ckpt.npz data_root=DATA estimates_path=out partition=test
 (model_path / load_model: a .npz of this package or a TensorFlow V2 checkpoint prefix such as checkpoints/full_44KHz/full_44KHz-236118)
 
 `with` arguments: `cfg.<named config>` (any of wave_u_net_amd.NAMED_CONFIGS), `model_config.<key>=<value>`
 overrides, and the command's own options as `<name>=<value>`.  data_root holds
 train|valid|test/<track>/<source>.wav|.npy (+ optional mix.wav) at expected_sr, or at any rate with the option
 `resample=1` (train, test).  `predict` takes a WAV at any rate and writes the estimates at that rate;
-`hop_frames=<N|track>` makes its hops N output frames long / one hop over the whole track (default: num_frames).  Multi-GPU:
-launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.
+`hop_frames=<N|track>` makes its hops N output frames long / one hop over the whole track (default: num_frames).
+`evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
+1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
+source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.
 """
 import ast
 import os
@@ -22,7 +25,7 @@ import sys
 
 
 def _parse(argv):
-    if len(argv) < 1 or argv[0] not in ("train", "predict", "test"):
+    if len(argv) < 1 or argv[0] not in ("train", "predict", "test", "evaluate"):
         raise SystemExit(__doc__)
     cmd, rest = argv[0], argv[1:]
     if rest and rest[0] == "with":
@@ -71,6 +74,16 @@ def main(argv=None):
         loss = validation.test(model_config, opts.get("partition", "test"), str(opts.get("experiment_id", "cli")),
                                opts.get("model_path"), data_root=opts["data_root"], resample=bool(opts.get("resample", False)))
         print("Finished testing - Mean MSE: " + str(loss))
+    elif cmd == "evaluate":
+        for need in ("data_root", "estimates_path"):
+            if need not in opts:
+                raise SystemExit("evaluate needs %s=<dir>" % need)
+        folder = evaluate.produce_dataset_estimates(model_config, opts.get("model_path"), opts["data_root"],
+                                                    opts["estimates_path"], partition=opts.get("partition", "test"))
+        for metric in ("SDR", "ISR", "SIR", "SAR"):
+            stats = evaluate.compute_mean_metrics(folder, metric=metric)
+            for src, (med, mad, mean, sd) in zip(model_config["source_names"], stats):
+                print("%s %s: median %.3f MAD %.3f mean %.3f SD %.3f" % (src, metric, med, mad, mean, sd))
     else:
         if "input_path" not in opts:
             raise SystemExit("predict needs input_path=<mixture.wav>")

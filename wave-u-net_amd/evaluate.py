@@ -106,7 +106,8 @@ def budget_batch_hops(separator, batch_hops, n_hops, input_frames, default_input
     return max(1, min(b, int(workspace_bytes) // per_hop))
 
 
-def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, hop_frames=None, workspace_bytes=None):
+def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, hop_frames=None, workspace_bytes=None,
+                   return_device=False):
     """Evaluate.predict (Evaluate.py:59-80) around predict_track (:82-145) for audio at any sample rate, without the
     host in the loop.  mix_audio: [n_frames, n_channels] float array or tensor at mix_sr Hz.  Returns {source_name: float32
     numpy [n_frames, channels]} at mix_sr: channels is the input's count, except that a stereo model on a mono file
@@ -131,7 +132,10 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     differ.  For same-padding models a long hop also moves the zero-padded hop edges (fewer of them, elsewhere).  Short
     tracks are zero-padded to one hop's OUTPUT (the default pads to its input, Evaluate.py:108-113).  batch_hops is
     lowered until batch_hops * workspace_floats of the long plan fits workspace_bytes (budget_batch_hops; default: the
-    workspace of the default tiling at batch_hops, from wun_plan_query); a last chunk runs on the same plan with zero rows."""
+    workspace of the default tiling at batch_hops, from wun_plan_query); a last chunk runs on the same plan with zero rows.
+
+    return_device=True: no download -- the float32 tensor [S, n_frames, channels] on the separator's device, sources in
+    source_names order (what evaluate_track scores where it lies)."""
     from . import resample as rs
     device = torch.device(getattr(separator, "device", None) or "cpu")
     x = mix_audio if torch.is_tensor(mix_audio) else torch.from_numpy(np.ascontiguousarray(np.asarray(mix_audio, dtype=np.float32)))
@@ -176,6 +180,8 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
         rs.resample_into(preds[si, :n_res], out[si], 0, n_back, down, up)        # [:n_res] drops extra_pad (:141-143)
     if c_fused != c_out:
         out = out.repeat(1, 1, c_out)
+    if return_device:
+        return out
     host = out.cpu().numpy()                                                     # the one download
     return {n: host[si] for si, n in enumerate(names)}
 
@@ -225,3 +231,111 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
     for source_name, source_audio in preds.items():
         wavfile.write(os.path.join(output_path, name) + "_" + source_name + ".wav", int(sr), np.asarray(source_audio, np.float32))
     return preds
+
+
+def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=None, name=None, hop_frames=None,
+                   window=1.0, hop=1.0, filters_len=512):
+    """Evaluate.predict with a results_dir (Evaluate.py:59-80,146-158): separate the mixture (separate_track, estimates kept
+    on the device), score them against the stems at the file's rate with bsseval.bss_eval, and write
+    <results_dir>/<name>.json in museval's layout.  mix_audio [n, c] at sr; stems {source_name: [n, c]} at sr with the
+    channel count of the estimates (a stereo model on a mono file gives two channels: mono stems are duplicated).  Signals
+    are cut to the shortest length.  Returns {metric: float64 [S, nwin]}, sources in source_names order."""
+    from . import bsseval
+    est = separate_track(model_config, separator, mix_audio, sr, hop_frames=hop_frames, return_device=True)
+    names = list(model_config["source_names"])
+    c = int(est.shape[2])
+    refs = []
+    for k in names:
+        a = stems[k]
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float32)
+        if a.ndim == 1:
+            a = a[:, None]
+        if a.shape[1] != c:
+            if a.shape[1] == 1:
+                a = np.tile(a, [1, c])
+            elif c == 1:
+                a = np.mean(a, axis=1, keepdims=True)
+            else:
+                raise ValueError("stem %r has %d channels, the estimates %d" % (k, a.shape[1], c))
+        refs.append(a)
+    n = min([int(est.shape[1])] + [r.shape[0] for r in refs])
+    ref = torch.from_numpy(np.ascontiguousarray(np.stack([r[:n] for r in refs]), dtype=np.float32))
+    scores = bsseval.bss_eval(ref.to(est.device), est[:, :n].contiguous(), sr, window=window, hop=hop, filters_len=filters_len)
+    if results_dir is not None:
+        import os
+        bsseval.write_track_json(os.path.join(results_dir, (name or "track") + ".json"), names, scores, window, hop)
+    return scores
+
+
+def compute_mean_metrics(json_folder, compute_averages=True, metric="SDR"):
+    """Evaluate.compute_mean_metrics (Evaluate.py:195-232): the per-track JSON files of a folder -> per source
+    (median, MAD, mean, SD) of `metric` over all segments, NaN segments (a silent source) ignored; compute_averages=False
+    returns the per-source vectors of segment values instead.  A path containing "test.json" is skipped, as there."""
+    import glob
+    import json
+    import os
+    files = sorted(glob.glob(os.path.join(json_folder, "*.json")))
+    inst_list = None
+    for path in files:
+        if "test.json" in path:                                                  # :213-215
+            continue
+        with open(path, "r") as f:
+            js = json.load(f)
+        if inst_list is None:
+            inst_list = [list() for _ in range(len(js["targets"]))]
+        for i in range(len(js["targets"])):
+            inst_list[i].extend([float(fr["metrics"][metric]) for fr in js["targets"][i]["frames"]])
+    inst_list = [np.array(perf, dtype=np.float64) for perf in (inst_list or [])]
+    if compute_averages:
+        return [(np.nanmedian(perf), np.nanmedian(np.abs(perf - np.nanmedian(perf))), np.nanmean(perf), np.nanstd(perf))
+                for perf in inst_list]
+    return inst_list
+
+
+def produce_dataset_estimates(model_config, load_model, data_root, output_path, partition="test", separator=None,
+                              hop_frames=None):
+    """The reference's produce_musdb_source_estimates (Evaluate.py:147-159) over the track folders of datasets.py:
+    data_root/<partition>/<track>/<source>.wav|.npy (+ optional mix.wav|.npy, default: the sum of the stems), every file at
+    one rate (an .npy: expected_sr).  Per track: the estimates as <output_path>/<partition>/<track>/<source>.wav and the
+    scores as <output_path>/<partition>/<track>.json.  Returns the folder of the JSON files (compute_mean_metrics reads it)."""
+    import os
+    from scipy.io import wavfile
+    from . import bsseval, datasets
+    from .separator import UnetAudioSeparator
+    sep = separator if separator is not None else UnetAudioSeparator(model_config)
+    if load_model is not None:
+        from .checkpoint import load_checkpoint
+        load_checkpoint(sep, load_model, with_optimizer=False)
+    names = list(model_config["source_names"])
+    base = os.path.join(data_root, partition)
+    out_dir = os.path.join(output_path, partition)
+    os.makedirs(out_dir, exist_ok=True)
+    for d in sorted(os.listdir(base)):
+        folder = os.path.join(base, d)
+        if not os.path.isdir(folder):
+            continue
+        stems, sr = {}, None
+        for k in names + ["mix"]:
+            for ext in (".wav", ".npy"):
+                f = os.path.join(folder, k + ext)
+                if os.path.exists(f):
+                    stems[k], r = datasets.read_audio(f)
+                    sr = r if r is not None else sr
+                    break
+            else:
+                if k != "mix":
+                    raise FileNotFoundError("%s: no %s.wav/.npy" % (folder, k))
+        sr = int(sr) if sr is not None else int(model_config["expected_sr"])
+        mix = stems.pop("mix") if "mix" in stems else sum(stems[k] for k in names)
+        est = separate_track(model_config, sep, mix, sr, hop_frames=hop_frames, return_device=True)
+        c = int(est.shape[2])
+        refs = [np.tile(stems[k], [1, c]) if stems[k].shape[1] == 1 and c > 1 else stems[k] for k in names]
+        n = min([int(est.shape[1])] + [r.shape[0] for r in refs])
+        ref = torch.from_numpy(np.ascontiguousarray(np.stack([r[:n] for r in refs]), dtype=np.float32)).to(est.device)
+        scores = bsseval.bss_eval(ref, est[:, :n].contiguous(), sr)
+        bsseval.write_track_json(os.path.join(out_dir, d + ".json"), names, scores)
+        host = est.cpu().numpy()
+        os.makedirs(os.path.join(out_dir, d), exist_ok=True)
+        for si, k in enumerate(names):
+            wavfile.write(os.path.join(out_dir, d, k + ".wav"), sr, host[si])
+    return out_dir
