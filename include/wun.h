@@ -430,6 +430,62 @@ int wun_bss_window_energies(const float* refs, const float* ests, int32_t S, int
                             const double* c_all, const double* c_own, const int64_t* starts, const int64_t* lengths,
                             int64_t nwin, double* energies, double* scratch, void* stream);
 
+/* ---- spectral training loss: STFT-magnitude L1 and its waveform gradient ----
+ * The reference's other objective (Training.py:55-60): the L1 distance between STFT magnitudes, frame 1024, hop 768,
+ * periodic Hann window, no padding -- here for up to 8 resolutions at once, next to the time-domain MSE.
+ *   audio      : device, float32 [S, B, T, C] channel-last, as wun_forward writes its outputs; a ROW is one (s, b, c),
+ *                R = S * B * C rows, row r = (s * B + b) * C + c; any 4-byte alignment
+ *   resolution : (n_fft, hop), n_fft a power of two in 64..2048, 1 <= hop <= n_fft;  K = n_fft / 2 + 1 bins,
+ *                F = 1 + (T - n_fft) / hop frames (integer division: tf's pad_end=False), frame f = samples [f hop, f hop + n_fft)
+ *   table      : fp32 [2][n_fft][K]: Cb[n][k] = w[n] cos(2 pi ((n k) mod n_fft) / n_fft), then Sb[n][k] = -w[n] sin(the same),
+ *                w[n] = 0.5 - 0.5 cos(2 pi n / n_fft); element (plane, n, k) at (plane * n_fft + n) * K + k
+ *   Re[r][f][k] = sum_n x_r[f hop + n] Cb[n][k],  Im with Sb,  M = sqrt(Re^2 + Im^2)
+ * No FFT: the transform is a GEMM against the table on the exact-fp32 MFMA, n ascending in one accumulator per output, so
+ * the bits of a row do not depend on the batch around it.  Every buffer is the caller's; nothing allocates or
+ * synchronises, no atomics, and every argument check runs before any GPU work.
+ * All entries: WUN_ERR_UNSUPPORTED for an n_fft outside the list, WUN_ERR_INVALID for a hop outside 1..n_fft or T < n_fft
+ * (checked in this order); the device entries also WUN_ERR_INVALID for a null pointer, S < 1, B < 1 or C not 1 or 2. */
+
+/* F of T frames of audio, and the floats of a table; negative wun_status for bad arguments. */
+int64_t wun_stft_frames(int64_t frames, int32_t n_fft, int32_t hop);
+int64_t wun_stft_table_floats(int32_t n_fft);
+/* Host: the table, designed in float64 (the angle reduced in integers first) and rounded once to fp32, into table_host[cap].
+ * WUN_ERR_INVALID for a null pointer or cap < wun_stft_table_floats. */
+int     wun_stft_design(int32_t n_fft, float* table_host, int64_t cap);
+/* mags[r][f][k] = M of x (device float32 [R][F][K]): the magnitude spectrogram.  table_dev: device copy of the table of
+ * n_fft.  The same kernel computes the magnitudes inside wun_spectral_loss: its signs are those of the differences of the
+ * floats this entry returns for the same inputs. */
+int     wun_stft_magnitude(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                           const float* table_dev, float* mags, void* stream);
+/* floats of `scratch` for wun_spectral_loss with these sizes: per resolution R F (4 K + n_fft) (both magnitudes, Re and Im
+ * of the estimates, the gradients of the frames), plus the float64 partial sums (one per 1024 elements) and 2 floats of
+ * alignment room.  Negative wun_status as wun_spectral_loss for the same arguments. */
+int64_t wun_spectral_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                    const int32_t* hop);
+/* L = mse_weight * MSE + sum_j weights[j] * L_j and dL / d outputs.
+ *   MSE  = mean of (outputs - targets)^2 over all S B Tout C floats (wun_loss_backward's loss)
+ *   L_j  = mean over rows, frames and bins of |M_est - M_tgt| at resolution j (Training.py:60,63)
+ *   d_outputs[r][t] = mse_weight * 2 (out - tgt) / (S B Tout C)
+ *                   + sum_j weights[j] / (R F_j K_j) * sum_{f: 0 <= t - f hop < n_fft} sum_k sgn(M_est - M_tgt)[f][k]
+ *                     * (Re_est Cb[n][k] + Im_est Sb[n][k]) / M_est,  n = t - f hop
+ *     with sgn(0) = 0 and the term of a bin with M_est == 0 equal to 0 (tf's gradient of a complex abs).  Samples behind
+ *     the last frame get the MSE term alone; the targets carry no gradient.
+ *   outputs, targets : device [S, B, Tout, C]
+ *   n_fft, hop, weights : HOST, nres entries (0 <= nres <= 8; nres == 0: the MSE and its gradient alone)
+ *   tables_dev       : HOST array of nres device pointers, tables_dev[j] = the table of n_fft[j]
+ *   d_outputs        : device [S, B, Tout, C], every float written once; NULL: the losses only
+ *   losses           : device float32 [2 + nres]: [0] = L, [1] = MSE, [2 + j] = L_j (unweighted)
+ *   scratch          : device, wun_spectral_scratch_floats floats; what it held does not matter
+ * The loss sums are float64 in an order fixed by the sizes (1024 elements per partial, one tree per partial, the partials
+ * strided over 64 lanes and one tree).  The gradient is destination-driven: one lane per output float adds the MSE term,
+ * then resolution after resolution the covering frames in ascending f; two calls give the same bits, whatever the grid,
+ * the scratch contents or the pointer alignment.  Both compute modes (the outputs are fp32 in both).
+ * WUN_ERR_INVALID also for nres outside 0..8, a null resolution table with nres > 0, or a negative or non-finite weight
+ * (mse_weight included). */
+int     wun_spectral_loss(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                          float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                          const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream);
+
 /* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
  * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
  * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is

@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""What the spectral loss costs, on the benchmarked plan: configs[1], M1 with context, 147443 -> 16389
+samples, S = 2, B = 16, mono, the pinned tuning table imported as bench.py does; the reference's resolution 1024 / 768.
+
+Kernel arms (HIP events on the launch stream around `iters` back-to-back calls, on the plan's own outputs):
+  magnitude     wun_stft_magnitude of the outputs [2, 16, 16389, 1] (32 rows x 21 frames x 513 bins)
+  loss_only     wun_spectral_loss, d_outputs = NULL (both signals' magnitudes, the float64 sums)
+  loss_grad     wun_spectral_loss with d_outputs (plus the transposed GEMM and the overlap-add)
+Trainer arms (one optimizer step each, same batch):
+  step_mse      Trainer(batch 16): the time-domain MSE (wun_loss_backward)
+  step_spectral Trainer(batch 16, spectral_loss = 1024 / 768, mse_weight 1): wun_spectral_loss, then wun_backward
+
+  python tools/spectral_bench.py [--rounds 9] [--iters 10] [--out profiles/spectral_bench.json]
+      the arms interleaved in ONE process for `rounds` rounds (order rotated each round); per arm the median, the minimum and
+      the maximum over the rounds of (time / iters).  One JSON line on stdout, and the same in --out.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+ARMS = ["magnitude", "loss_only", "loss_grad", "step_mse", "step_spectral"]
+RES = [(1024, 768)]
+
+
+def setup():
+    import torch
+    import wave_u_net_amd as wun
+    from wave_u_net_amd import spectral
+    from wave_u_net_amd.training import Trainer, synthetic_source
+    os.environ["WUN_NO_TUNE"] = "1"                               # (Trainer.tune: only the pinned table below)
+    cfg = wun.get_config("m1_context")
+    table = open(os.path.join(ROOT, "profiles", "round6_tune_table.txt")).read()
+    spec = {"resolutions": [list(r) for r in RES], "mse_weight": 1.0}
+    tr_mse, tr_spec = Trainer(cfg, batch_size=16), Trainer(cfg, batch_size=16, spectral_loss=spec)
+    mix, targets = synthetic_source(cfg, 16, tr_mse.t_in, tr_mse.t_out, tr_mse.device, seed=1337)()
+    for tr in (tr_mse, tr_spec):
+        tr.sep.get_output(mix, True)
+        tr.sep.tune_import(table)
+    outs = tr_mse.sep._outs[tr_mse.sep._last_key].clone()
+    tg = targets.to(torch.float32).contiguous()
+    loss = spectral.SpectralLoss(RES, mse_weight=1.0)
+    scratch = loss._scratch_for(outs)
+    losses = torch.empty(3, dtype=torch.float32, device=outs.device)
+    d_outs = torch.empty_like(outs)
+
+    def step(arm):
+        if arm == "magnitude":
+            spectral.stft_magnitude(outs, *RES[0])
+        elif arm == "loss_only":
+            loss.run(outs, tg, None, losses, scratch)
+        elif arm == "loss_grad":
+            loss.run(outs, tg, d_outs, losses, scratch)
+        elif arm == "step_mse":
+            tr_mse.step(mix, targets)
+        else:
+            tr_spec.step(mix, targets)
+    return torch, step, tuple(outs.shape)
+
+
+def timed(rounds, iters, out):
+    torch, step, shape = setup()
+    for arm in ARMS:                                              # warm-up
+        for _ in range(3):
+            step(arm)
+    torch.cuda.synchronize()
+    allr = {a: [] for a in ARMS}
+    for r in range(rounds):
+        order = ARMS[r % len(ARMS):] + ARMS[:r % len(ARMS)]
+        for arm in order:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                step(arm)
+            e1.record()
+            e1.synchronize()
+            allr[arm].append(round(e0.elapsed_time(e1) / iters, 4))
+    res = {"what": "ms per call / per optimizer step; arms interleaved in one process", "outputs_shape": shape,
+           "resolutions": RES, "rounds": rounds, "iters": iters,
+           "median_ms": {a: round(statistics.median(allr[a]), 4) for a in ARMS},
+           "min_ms": {a: min(allr[a]) for a in ARMS}, "max_ms": {a: max(allr[a]) for a in ARMS}, "rounds_ms": allr}
+    line = json.dumps(res)
+    print(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    timed(a.rounds, a.iters, a.out)
+
+
+if __name__ == "__main__":
+    main()

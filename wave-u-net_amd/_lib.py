@@ -75,6 +75,14 @@ _SIGS = {
     "wun_bss_correlations": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "wun_bss_window_energies": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64), C.c_int64, _P, _P, _P]),
+    "wun_stft_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_stft_table_floats": (C.c_int64, [C.c_int32]),
+    "wun_stft_design": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.c_int64]),
+    "wun_stft_magnitude": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "wun_spectral_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32)]),
+    "wun_spectral_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_void_p), _P, _P, _P, _P]),
     "wun_separate_positions": (C.c_int64, [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64]),
     "wun_forward_windows": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, _P, _P, C.c_int, _P]),
     "wun_scatter_windows": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, _P, C.c_int64, _P]),

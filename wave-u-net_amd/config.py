@@ -31,6 +31,18 @@ BASE_MODEL_CONFIG = {            # Config.py:9-39
     "worse_epochs": 20,
 }
 
+# Keys the reference does not have, with the value a model_config without them means (read with .get(); BASE_MODEL_CONFIG
+# stays the reference's dict, key by key).
+EXTENSION_DEFAULTS = {
+    "grad_accum_steps": 1,            # training.Trainer: micro-batches per optimizer step
+    "clip_grad_norm": None,           # training.Trainer: tf.clip_by_global_norm threshold
+    "skip_nonfinite_steps": False,    # training.Trainer: skip an update whose gradient norm is not finite
+    "checkpoint_format": "npz",       # training.train: "npz" or "tf"
+    # training.Trainer / spectral.SpectralLoss: None = the reference's MSE; else {"resolutions": [[n_fft, hop], ...],
+    # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60)
+    "spectral_loss": None,
+}
+
 NAMED_CONFIGS = {                # Config.py:52-161 (the Wave-U-Net ones)
     "baseline": {},
     "baseline_diff": {"output_type": "difference"},

@@ -121,6 +121,8 @@ class UnetAudioSeparator(object):
         self._ws = {}
         self._ws_gen = {}            # (batch, frames) -> forward passes run on that workspace (autograd's stale-workspace guard)
         self._outs = {}
+        self._d_outs = {}            # (batch, frames) -> dL / d outputs of loss_and_gradients(loss=...) (allocated on first use)
+        self.last_losses = None      # [total, MSE, L_0, ...] of the last loss_and_gradients(loss=...)
         self._last_mix = None
 
     # ------------------------------------------------------------------ shapes
@@ -356,7 +358,7 @@ class UnetAudioSeparator(object):
             return None, 0
         return mask.ctypes.data_as(C.POINTER(C.c_uint8)), int(mask.size)
 
-    def loss_and_gradients(self, targets, bucket_starts=None, bucket_events=None, variables=None, accumulate=False):
+    def loss_and_gradients(self, targets, bucket_starts=None, bucket_events=None, variables=None, accumulate=False, loss=None):
         """MSE loss averaged over sources (Training.py:50-63) and its gradient w.r.t. every
         separator variable.  targets: dict source_name -> [B, Tout, C] or a stacked
         [S, B, Tout, C] tensor.  Must follow get_output(training=True).  Returns the loss as
@@ -370,11 +372,28 @@ class UnetAudioSeparator(object):
         written, and launches no selected gradient needs are skipped (wun_loss_backward_select).
 
         accumulate: ADD the gradients to what self.grads holds (wun_loss_backward_accumulate: one fp32 add per float, the
-        loss is still written) -- k micro-batches per optimizer step."""
+        loss is still written) -- k micro-batches per optimizer step.
+
+        loss: a spectral.SpectralLoss replaces the MSE by mse_weight * MSE + sum_j weight_j * (STFT-magnitude L1 at
+        resolution j) (Training.py:55-60): wun_spectral_loss writes the loss and dL / d outputs, then the backward pass runs
+        from that gradient (wun_backward_ex / _select / _accumulate), so variables, accumulate and the bucket events mean
+        what they mean above.  Returns the total; self.last_losses holds [total, MSE, L_0, ...] (device tensor, L_j
+        unweighted).  None: exactly the calls above."""
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
         tg = self._stacked(targets, "targets")
+        if loss is not None:
+            outs = self._outs[self._last_key]
+            if self._last_key not in self._d_outs:
+                self._d_outs[self._last_key] = torch.empty_like(outs)
+            dout = self._d_outs[self._last_key]
+            losses = torch.empty(2 + len(loss.resolutions), dtype=torch.float32, device=self._dev())
+            loss.run(outs, tg, dout, losses, loss._scratch_for(outs))
+            self._run_backward(self._ws[self._last_key], outs, dout, self.grads, None, bucket_starts, bucket_events, mask,
+                               accumulate)
+            self.last_losses = losses
+            return losses[0]
         loss = torch.empty((), dtype=torch.float32, device=self._dev())
         fn, sel = self._backward_entry("wun_loss_backward", mask, accumulate)
         _lib.check(fn(self._active.handle, self.params.data_ptr(), self._last_mix.data_ptr(),

@@ -1,0 +1,173 @@
+"""The spectral training loss of libwun.so (include/wun.h: wun_stft_*, wun_spectral_*): the L1 distance
+between STFT magnitudes the reference builds from tf.contrib.signal.stft (Training.py:55-60 -- frame 1024, hop 768, periodic
+Hann window, no padding), for any number of resolutions up to 8, next to the time-domain MSE.
+
+    stft_magnitude(x, 1024, 768)                       # the magnitude spectrogram [S, B, C, F, K] of audio [S, B, T, C]
+    loss = SpectralLoss([(1024, 768), (256, 64)], mse_weight=1.0)
+    losses, d_outputs = loss.loss_and_grad(outputs, targets)      # [total, MSE, L_0, L_1], dL / d outputs
+    sep.loss_and_gradients(targets, loss=loss)         # the training step's loss (UnetAudioSeparator, Trainer)
+    stft_l1(net(mix), targets, loss)                   # under torch.autograd, for users of sep.module()
+
+Audio is float32 [S, B, T, C] channel-last on the GPU, as get_output stacks its outputs.  There is no CPU path.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+
+MAX_RESOLUTIONS = 8
+_TABLES = {}     # (n_fft, device) -> device tensor holding the windowed cos / sin table [2, n_fft, K]
+
+
+def frames(n, n_fft, hop):
+    """Frames of n samples: 1 + (n - n_fft) // hop, no padding (wun_stft_frames)."""
+    f = int(_lib.load().wun_stft_frames(int(n), int(n_fft), int(hop)))
+    if f < 0:
+        _lib.check(f)
+    return f
+
+
+def design(n_fft):
+    """The fp32 table [2, n_fft, K] as a numpy array: w[n] cos and -w[n] sin of 2 pi n k / n_fft (wun_stft_design)."""
+    lib = _lib.load()
+    n = int(lib.wun_stft_table_floats(int(n_fft)))
+    if n < 0:
+        _lib.check(n)
+    table = np.zeros(n, np.float32)
+    _lib.check(lib.wun_stft_design(int(n_fft), table.ctypes.data_as(C.POINTER(C.c_float)), n))
+    return table.reshape(2, int(n_fft), int(n_fft) // 2 + 1)
+
+
+def _table(n_fft, device):
+    key = (int(n_fft), str(device))
+    if key not in _TABLES:
+        _TABLES[key] = torch.from_numpy(design(n_fft)).to(device)
+    return _TABLES[key]
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _audio(x, what):
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise ValueError("%s must be a tensor on the GPU (there is no CPU path)" % what)
+    if x.dim() != 4:
+        raise ValueError("%s must be [S, B, T, C], got %s" % (what, tuple(x.shape)))
+    return x.to(torch.float32).contiguous()
+
+
+def stft_magnitude(x, n_fft, hop):
+    """|STFT| of audio x [S, B, T, C]: float32 [S, B, C, F, K], K = n_fft // 2 + 1 bins, F = frames(T, n_fft, hop) frames of
+    the periodic-Hann-windowed signal without padding (wun_stft_magnitude).  One launch on the current stream, no sync."""
+    x = _audio(x, "x")
+    S, B, T, Cn = (int(v) for v in x.shape)
+    F = frames(T, n_fft, hop)
+    mags = torch.empty((S, B, Cn, F, int(n_fft) // 2 + 1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().wun_stft_magnitude(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop),
+                                                  _table(n_fft, x.device).data_ptr(), mags.data_ptr(), _stream(x.device)))
+    return mags
+
+
+class SpectralLoss(object):
+    """L = mse_weight * MSE + sum_j weights[j] * L_j, L_j = mean |M_est - M_tgt| at resolutions[j] = (n_fft, hop).
+    weights=None: 1 for every resolution.  resolutions=[] is the MSE alone.  ValueError / NotImplementedError for what
+    wun_spectral_loss refuses, at the first call (the checks need the audio's length)."""
+
+    def __init__(self, resolutions=((1024, 768),), weights=None, mse_weight=0.0):
+        self.resolutions = [(int(n), int(h)) for n, h in resolutions]
+        if len(self.resolutions) > MAX_RESOLUTIONS:
+            raise ValueError("at most %d resolutions, got %d" % (MAX_RESOLUTIONS, len(self.resolutions)))
+        self.weights = [1.0] * len(self.resolutions) if weights is None else [float(w) for w in weights]
+        if len(self.weights) != len(self.resolutions):
+            raise ValueError("%d weights for %d resolutions" % (len(self.weights), len(self.resolutions)))
+        self.mse_weight = float(mse_weight)
+        for w in self.weights + [self.mse_weight]:
+            if not (w >= 0.0 and np.isfinite(w)):
+                raise ValueError("weights must be finite and >= 0, got %r" % (w,))
+        n = max(len(self.resolutions), 1)
+        self._n_fft = (C.c_int32 * n)(*[r[0] for r in self.resolutions])
+        self._hop = (C.c_int32 * n)(*[r[1] for r in self.resolutions])
+        self._w = (C.c_float * n)(*self.weights)
+        self._scratch = {}       # (shape, device) -> float32 scratch of wun_spectral_scratch_floats
+
+    @classmethod
+    def from_config(cls, spec):
+        """model_config["spectral_loss"]: None, a SpectralLoss, or a dict with `resolutions`, `weights`, `mse_weight`."""
+        if spec is None or isinstance(spec, cls):
+            return spec
+        unknown = set(spec) - {"resolutions", "weights", "mse_weight"}
+        if unknown:
+            raise ValueError("spectral_loss: unknown keys %s" % sorted(unknown))
+        return cls(spec.get("resolutions", ((1024, 768),)), spec.get("weights"), spec.get("mse_weight", 0.0))
+
+    def scratch_floats(self, shape):
+        S, B, T, Cn = (int(v) for v in shape)
+        n = int(_lib.load().wun_spectral_scratch_floats(S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop))
+        if n < 0:
+            _lib.check(n)
+        return n
+
+    def _scratch_for(self, x):
+        key = (tuple(x.shape), str(x.device))
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(self.scratch_floats(x.shape), dtype=torch.float32, device=x.device)
+        return self._scratch[key]
+
+    def run(self, outputs, targets, d_outputs, losses, scratch):
+        """wun_spectral_loss on the caller's buffers (contiguous float32 device tensors; d_outputs may be None)."""
+        S, B, T, Cn = (int(v) for v in outputs.shape)
+        dev = outputs.device
+        nres = len(self.resolutions)
+        tabs = (C.c_void_p * max(nres, 1))(*[_table(n, dev).data_ptr() for n, _ in self.resolutions])
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wun_spectral_loss(
+                outputs.data_ptr(), targets.data_ptr(), S, B, T, Cn, self.mse_weight, nres, self._n_fft, self._hop, self._w,
+                tabs, d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(),
+                _stream(dev)))
+
+    def loss_and_grad(self, outputs, targets, grad=True):
+        """(losses, d_outputs): losses float32 [2 + nres] on the device = [total, MSE, L_0, ...] (L_j unweighted), d_outputs
+        = d total / d outputs with the outputs' shape (None with grad=False).  No host sync."""
+        outputs, targets = _audio(outputs, "outputs"), _audio(targets, "targets")
+        if outputs.shape != targets.shape or outputs.device != targets.device:
+            raise ValueError("outputs %s and targets %s differ in shape or device" % (tuple(outputs.shape), tuple(targets.shape)))
+        scratch = self._scratch_for(outputs)
+        losses = torch.empty(2 + len(self.resolutions), dtype=torch.float32, device=outputs.device)
+        d_outputs = torch.empty_like(outputs) if grad else None
+        self.run(outputs, targets, d_outputs, losses, scratch)
+        return losses, d_outputs
+
+    def __call__(self, outputs, targets):
+        """The total loss as a 0-dim tensor, differentiable with respect to `outputs` (stft_l1)."""
+        return stft_l1(outputs, targets, self)
+
+
+class _StftL1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, outputs, targets, loss):
+        losses, d_outputs = loss.loss_and_grad(outputs.detach(), targets.detach(), grad=ctx.needs_input_grad[0])
+        if d_outputs is not None:
+            ctx.save_for_backward(d_outputs)
+        ctx.dtype = outputs.dtype
+        return losses[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        (d_outputs,) = ctx.saved_tensors
+        return (d_outputs * g).to(ctx.dtype), None, None       # (the targets carry no gradient)
+
+
+def stft_l1(outputs, targets, loss=None, resolutions=((1024, 768),), weights=None, mse_weight=0.0):
+    """The total of a SpectralLoss (`loss`, or one built from the other arguments) as a 0-dim tensor under torch.autograd:
+    backward gives d total / d outputs as wun_spectral_loss computes it; the targets get no gradient."""
+    if loss is None:
+        loss = SpectralLoss(resolutions, weights, mse_weight)
+    return _StftL1.apply(outputs, targets, loss)

@@ -19,6 +19,7 @@ import torch.distributed as dist
 from .parallel import GradAllReducer, OverlappedGradAllReducer, broadcast_parameters, init_distributed
 from .checkpoint import load_checkpoint, save_checkpoint
 from .separator import UnetAudioSeparator, check_clip_norm
+from .spectral import SpectralLoss
 
 
 def synthetic_source(model_config, batch, t_in, t_out, device, seed=1337):
@@ -54,10 +55,16 @@ class Trainer(object):
     clip_grad_norm / skip_nonfinite (or model_config["clip_grad_norm"] / ["skip_nonfinite_steps"], default off): each Adam
     update clips by the global norm of the gradient it applies -- after the all-reduce, times the all-reduce's scale / k, so
     every rank sees the same bits -- and skips the update when that norm is not finite (wun_adam_step_clip).  Off: exactly
-    the old calls."""
+    the old calls.
+
+    spectral_loss (or model_config["spectral_loss"], default None): a dict with `resolutions` [[n_fft, hop], ...], `weights`
+    and `mse_weight`, or a spectral.SpectralLoss -- the step then minimises mse_weight * MSE + sum_j weight_j * (STFT-magnitude
+    L1 at resolution j) (Training.py:55-60; wun_spectral_loss, then the backward pass from its gradient).  step() returns the
+    total; last_losses holds [total, MSE, L_0, ...] of the step (device tensor, the mean over the micro-batches).  None:
+    exactly the old calls.  Validation and early stopping stay the reference's MSE."""
 
     def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0, grad_accum_steps=None,
-                 clip_grad_norm=None, skip_nonfinite=None):
+                 clip_grad_norm=None, skip_nonfinite=None, spectral_loss=None):
         self.rank, self.local_rank, self.world = init_distributed()
         # Scheduling hint of the plan (include/wun.h): low-priority side streams only when no collective shares the
         # device -- with a process group initialised (multi-GPU, or bench.py --force-allreduce) they must stay normal.
@@ -77,6 +84,10 @@ class Trainer(object):
             raise ValueError("grad_accum_steps = %r must be >= 1 and divide the batch (%d)" % (k, self.batch))
         self.micro = self.batch // self.accum
         self.clip_norm, self.skip_nonfinite = clip_settings(model_config, clip_grad_norm, skip_nonfinite)
+        self.spectral = SpectralLoss.from_config(spectral_loss if spectral_loss is not None
+                                                 else model_config.get("spectral_loss"))
+        self._loss_kw = {"loss": self.spectral} if self.spectral is not None else {}
+        self.last_losses = None
         self.grad_norm = None                  # global norm of the last clipped / checked update (0-dim GPU tensor)
         in_shape, out_shape = self.sep.get_padding(np.array([self.batch, model_config["num_frames"], 0]))
         self.t_in, self.t_out = int(in_shape[1]), int(out_shape[1])
@@ -152,13 +163,15 @@ class Trainer(object):
         self.sep.get_output(mix, True)
         if self.overlap:
             # bucket events are recorded by the backward pass; the all-reduces wait on them
-            loss = self.sep.loss_and_gradients(targets, *self.reducer.begin())
+            loss = self.sep.loss_and_gradients(targets, *self.reducer.begin(), **self._loss_kw)
             self.reducer.launch(self.sep.grads)
             self.reducer.finish()
         else:
-            loss = self.sep.loss_and_gradients(targets)
+            loss = self.sep.loss_and_gradients(targets, **self._loss_kw)
             self.reducer.all_reduce(self.sep.grads)
         self._adam(self.reducer.grad_scale)
+        if self.spectral is not None:
+            self.last_losses = self.sep.last_losses
         return loss
 
     @property
@@ -179,21 +192,30 @@ class Trainer(object):
         if mix.shape[0] != self.batch:
             raise ValueError("step takes the whole batch: %d excerpts, got %d" % (self.batch, mix.shape[0]))
         k = self.accum
-        losses = []
+        losses, parts = [], []
         for i in range(k):
             m, t = self._micro_batch(mix, targets, i)
             self.sep.get_output(m, True)
             if self.overlap and i == k - 1:
-                losses.append(self.sep.loss_and_gradients(t, *self.reducer.begin(), accumulate=i > 0))
+                losses.append(self.sep.loss_and_gradients(t, *self.reducer.begin(), accumulate=i > 0, **self._loss_kw))
             else:
-                losses.append(self.sep.loss_and_gradients(t, accumulate=i > 0))
+                losses.append(self.sep.loss_and_gradients(t, accumulate=i > 0, **self._loss_kw))
+            if self.spectral is not None:
+                parts.append(self.sep.last_losses)
         if self.overlap:
             self.reducer.launch(self.sep.grads)
             self.reducer.finish()
         else:
             self.reducer.all_reduce(self.sep.grads)
         self._adam(self.reducer.grad_scale / k)
+        if self.spectral is not None:
+            self.last_losses = torch.stack(parts).mean(0)
         return torch.stack(losses).mean()
+
+    def loss_parts(self):
+        """(MSE, weighted sum of the spectral L1 terms) of the last step with a spectral loss, as floats (host sync)."""
+        l = self.last_losses.tolist()
+        return l[1], sum(w * x for w, x in zip(self.spectral.weights, l[2:]))
 
 
 def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
@@ -246,6 +268,8 @@ def train(model_config, experiment_id, load_model=None, batch_source=None, log_e
         loss = tr.step(mix, targets)
         if log is not None and (it % log_every == 0 or it == model_config["epoch_it"] - 1):
             line = {"global_step": tr.sep.global_step, "sep_loss": float(loss.item()), "elapsed_s": time.time() - t0}
+            if tr.spectral is not None:
+                line["mse_loss"], line["spectral_loss"] = tr.loss_parts()
             if tr.clipping:
                 line["grad_norm"] = float(tr.grad_norm.item())
                 line["skipped_steps"] = tr.sep.skipped_steps
