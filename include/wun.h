@@ -486,6 +486,58 @@ int     wun_spectral_loss(const float* outputs, const float* targets, int32_t S,
                           float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
                           const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream);
 
+/* ---- inverse STFT and soft-mask post-filter ----
+ * The synthesis half of the spectral section, on the same table, and the post-filter built on the pair: the estimates of a
+ * track are masked against the mixture's own STFT, so they share its phase and sum back to it.
+ *   audio, rows, the table [2][n_fft][K] (Cb = w cos, Sb = -w sin), the periodic Hann window w and K = n_fft / 2 + 1 are
+ *   those of the spectral section above.
+ *   Centred framing : lead = n_fft - hop, F = ceil((T + lead) / hop) (wun_stft_centered_frames); frame f holds
+ *                x[f hop - lead + n], 0 <= n < n_fft, and is zero outside [0, T).  When hop divides n_fft every sample of
+ *                [0, T) lies in exactly n_fft / hop frames.  A track shorter than n_fft is legal.
+ *   Complex STFT : Re[r][f][k] = sum_n frame_f[n] Cb[n][k], Im likewise with Sb.  lead and F are given by the caller;
+ *                lead = 0 with F = wun_stft_frames(...) is the framing of the loss.  The accumulation order is the existing
+ *                one: n ascending in one accumulator per output.
+ *   Inverse STFT : frame_f[n] = (1 / n_fft) sum_k c_k (Re[f][k] Cb[n][k] + Im[f][k] Sb[n][k]), c_0 = c_{n_fft/2} = 1, every
+ *                other c_k = 2; k ascending, a bin's real part before its imaginary part.
+ *                y[t] = (sum_f frame_f[t + lead - f hop]) / (sum_f w^2[t + lead - f hop]), both sums over the covering frames
+ *                (0 <= f < F, 0 <= t + lead - f hop < n_fft) in ascending f.  Where the denominator is below 1e-8, y[t] = 0
+ *                (librosa's rule).  The denominator is computed from the window (float64), not from the table.  The
+ *                overlap-add is destination-driven: one writer per output float, no atomics.
+ *   Soft-mask filter, for one track with mix [n, C] and estimates [S, n, C], per channel:
+ *                X = STFT(mix) and E_s = STFT(est_s) in the centred framing;  A_s = |E_s|^p, p in {1, 2} (p = 2 takes no
+ *                square root);  mask_s = (A_s + eps / S) / (sum_j A_j + eps), j ascending -- the masks sum to 1 by
+ *                construction;  out_s = ISTFT(mask_s X) over [0, n).  Requires hop a power of two and hop <= n_fft / 2, so
+ *                every sample's window-square sum is at least 0.5.  Defaults of the callers: p = 2, eps = 1e-10.
+ * Every buffer is the caller's; nothing allocates or synchronises; every argument check runs before any GPU work.  Results
+ * do not depend on what `scratch` held, on pointer alignment beyond 4 bytes, or on how the frames are blocked internally
+ * (blocks of 256 frames bound the scratch).  Both compute modes.
+ * All entries, in this order: WUN_ERR_INVALID for a null pointer (device entries), S < 1, B < 1, C not 1 or 2 or T < 1;
+ * WUN_ERR_UNSUPPORTED for an n_fft outside the spectral section's list; WUN_ERR_INVALID for a hop outside 1..n_fft, then
+ * for lead outside [0, n_fft) or F < 1 (WUN_ERR_UNSUPPORTED for more than 2^30 frames in all). */
+
+/* F of the centred framing: ceil((T + n_fft - hop) / hop).  Host only; negative wun_status for bad arguments. */
+int64_t wun_stft_centered_frames(int64_t T, int32_t n_fft, int32_t hop);
+/* re, im (device float32 [R][F][K]) = the complex STFT of x [S, B, T, C] with the caller's lead and F.  WUN_ERR_INVALID
+ * also when re or im overlap x or each other. */
+int     wun_stft_complex(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                         int32_t lead, int64_t F, const float* table_dev, float* re, float* im, void* stream);
+/* floats of `scratch` for wun_istft: R min(F, 256 + ceil(n_fft / hop) - 1) n_fft (the frames of one block), n_fft float64
+ * window squares and 2 floats of alignment room.  Negative wun_status as wun_istft for the same arguments. */
+int64_t wun_istft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
+                                 int64_t F);
+/* y (device [S, B, T, C], every float written once) = the inverse STFT of re, im [R][F][K].  Samples no frame covers are 0.
+ * WUN_ERR_INVALID also when y overlaps re or im. */
+int     wun_istft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                  int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream);
+/* floats of `scratch` for wun_mask_filter: with nb = min(F, 256 + n_fft / hop - 1) frames per block, 2 (S + 1) C nb K
+ * (the spectra) + S C nb n_fft (the frames) + 2 n_fft + 2.  Negative wun_status as wun_mask_filter. */
+int64_t wun_mask_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop);
+/* out (device [S, n, C], every float written once) = the soft-mask filter of ests [S, n, C] against mix_tc [n, C].
+ * WUN_ERR_INVALID also for a hop that is no power of two or above n_fft / 2, a power other than 1 or 2, an eps that is not
+ * finite and positive, or `out` overlapping an input; WUN_ERR_UNSUPPORTED for S > 8 (after the hop checks). */
+int     wun_mask_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                        int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream);
+
 /* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
  * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
  * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is

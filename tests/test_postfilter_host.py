@@ -1,0 +1,343 @@
+"""CPU-only checks of the inverse STFT and the soft-mask filter (include/wun.h: wun_stft_centered_frames, wun_stft_complex,
+wun_istft*, wun_mask_filter*; wave_u_net_amd.postfilter): the frame rule, every argument error before any GPU
+work and the order of the errors, the float64 oracle (tests/_postfilter_np.py) against torch.stft / torch.istft and its bounds
+on an fp32 numpy stand-in, the CPU SoftMaskFilter against that oracle, separate_track(postfilter=...) on a numpy stand-in
+separator, and the config / command-line spec.  The device path is checked in tests/test_gpu_postfilter.py."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _postfilter_np as ora  # noqa: E402
+import _spectral_np as sp  # noqa: E402
+from _observed import record  # noqa: E402
+
+import wave_u_net_amd as wun  # noqa: E402
+from wave_u_net_amd import _lib, config, postfilter, spectral  # noqa: E402
+from wave_u_net_amd.evaluate import separate_track  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("wun_stft_centered_frames", "wun_stft_complex", "wun_istft_scratch_floats", "wun_istft", "wun_mask_filter_scratch_floats",
+         "wun_mask_filter")
+INVALID, UNSUPPORTED = -1, -2
+P, Q, R3, R4 = 0x100000, 0x40000000, 0x80000000, 0xC0000000      # non-null "device pointers" far apart: never read
+RES = [(64, 32), (64, 16), (64, 8), (128, 64), (256, 64), (2048, 512)]
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return _lib.load()
+
+
+def test_declared_exported_and_documented(lib):
+    hdr = open(os.path.join(ROOT, "include", "wun.h")).read()
+    declared = set(re.findall(r"\b(wun_[a-z0-9_]+)\s*\(", hdr))
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in NAMES:
+        assert name in declared and name in _lib.EXPORTED_SYMBOLS and hasattr(lib, name), name
+        assert name in doc, name
+    # the tests quote the header's definitions
+    for line in ("lead = n_fft - hop, F = ceil((T + lead) / hop)", "c_0 = c_{n_fft/2} = 1", "mask_s = (A_s + eps / S) / (sum_j A_j + eps)",
+                 "below 1e-8, y[t] = 0"):
+        assert line in hdr, line
+
+
+# ---- the frame rule ------------------------------------------------------------------------
+@pytest.mark.parametrize("n_fft, hop", RES + [(64, 64), (64, 37), (2048, 1)])
+def test_centered_frames_rule(lib, n_fft, hop):
+    lead = n_fft - hop
+    for T in (1, 5, hop, n_fft - 1, n_fft, n_fft + 1, 1000, 5000, 7 * hop + 3):
+        want = -(-(T + lead) // hop)
+        assert lib.wun_stft_centered_frames(T, n_fft, hop) == want == spectral.centered_frames(T, n_fft, hop) \
+            == ora.centered_frames(T, n_fft, hop)
+        assert (want - 1) * hop - lead < T <= want * hop - lead          # the last frame starts inside the track, F frames cover it
+    if n_fft % hop == 0:                                                 # every sample lies in exactly n_fft / hop frames
+        T = 3 * n_fft + 5
+        F = ora.centered_frames(T, n_fft, hop)
+        t = np.arange(T)[:, None]
+        n = t + lead - np.arange(F)[None, :] * hop
+        assert np.all(((n >= 0) & (n < n_fft)).sum(1) == n_fft // hop)
+
+
+def test_centered_frames_errors(lib):
+    assert lib.wun_stft_centered_frames(0, 64, 16) == INVALID
+    assert lib.wun_stft_centered_frames(100, 64, 0) == INVALID and lib.wun_stft_centered_frames(100, 64, 65) == INVALID
+    for bad in (0, 32, 96, 4096):
+        assert lib.wun_stft_centered_frames(100, bad, 0) == UNSUPPORTED          # n_fft is judged before the hop
+    with pytest.raises(NotImplementedError):
+        spectral.centered_frames(100, 100, 10)
+
+
+@pytest.mark.parametrize("n_fft, hop", [(64, 32), (64, 16), (64, 8), (128, 64), (256, 64)])
+def test_window_square_sum_is_at_least_half(n_fft, hop):
+    """hop a power of two, hop <= n_fft / 2: every sample of the centred framing sees a window-square sum >= 0.5."""
+    for T in (5, 1000):
+        lead, F = ora.framing(T, n_fft, hop, True)
+        assert ora.window_sums(T, F, n_fft, hop, lead).min() >= 0.5 - 1e-12
+
+
+# ---- argument checks, before any GPU work ----------------------------------------------------
+def _complex(lib, x=P, S=2, B=3, T=200, Cn=2, n_fft=64, hop=16, lead=48, F=16, table=Q, re=R3, im=R4):
+    return lib.wun_stft_complex(x, S, B, T, Cn, n_fft, hop, lead, F, table, re, im, None)
+
+
+def _istft(lib, re=R3, im=R4, S=2, B=3, T=200, Cn=2, n_fft=64, hop=16, lead=48, F=16, table=Q, y=P, scratch=0x10000):
+    return lib.wun_istft(re, im, S, B, T, Cn, n_fft, hop, lead, F, table, y, scratch, None)
+
+
+def _filter(lib, mix=P, ests=Q, S=2, n=200, Cn=2, n_fft=64, hop=16, power=2, eps=1e-10, table=0x10000, out=R3, scratch=R4):
+    return lib.wun_mask_filter(mix, ests, S, n, Cn, n_fft, hop, power, eps, table, out, scratch, None)
+
+
+def test_transform_argument_errors_and_their_order(lib):
+    """No device is touched: the pointers are not device memory and there may be no device at all (so no call here is
+    valid: every one must return from its checks)."""
+    for call, ptrs in ((_complex, ("x", "table", "re", "im")), (_istft, ("re", "im", "table", "y", "scratch"))):
+        for name in ptrs:
+            assert call(lib, **{name: None}) == INVALID, name
+        for kw in ({"S": 0}, {"B": 0}, {"Cn": 0}, {"Cn": 3}, {"T": 0}, {"hop": 0}, {"hop": 65}, {"lead": -1}, {"lead": 64},
+                   {"F": 0}, {"F": -3}):
+            assert call(lib, **kw) == INVALID, kw
+        for bad in (0, 32, 96, 4096):
+            assert call(lib, n_fft=bad) == UNSUPPORTED, bad
+        # the order: a null pointer, then the audio's shape, then n_fft (UNSUPPORTED), then the hop, then lead and F
+        assert call(lib, **{ptrs[0]: None, "n_fft": 100}) == INVALID
+        assert call(lib, S=0, n_fft=100) == INVALID
+        assert call(lib, n_fft=100, hop=0, lead=-1) == UNSUPPORTED
+        assert call(lib, hop=0, lead=-1) == INVALID and b"hop" in lib.wun_last_error()
+        assert call(lib, lead=64, F=0) == INVALID and b"lead" in lib.wun_last_error()
+        assert call(lib, F=1 << 29) == UNSUPPORTED                          # more than 2^30 frames in all
+    # outputs overlapping inputs
+    assert _complex(lib, re=P + 16) == INVALID and _complex(lib, im=P) == INVALID and _complex(lib, re=R3, im=R3 + 4) == INVALID
+    assert _istft(lib, y=R3 + 64) == INVALID and _istft(lib, y=R4) == INVALID
+
+    def scratch(S=2, B=3, T=200, Cn=2, n_fft=64, hop=16, lead=48, F=16):
+        return lib.wun_istft_scratch_floats(S, B, T, Cn, n_fft, hop, lead, F)
+    assert scratch(S=0) == INVALID and scratch(hop=0) == INVALID and scratch(lead=64) == INVALID and scratch(F=0) == INVALID
+    assert scratch(n_fft=100) == UNSUPPORTED
+    # the documented size: R min(F, 256 + ceil(n_fft / hop) - 1) n_fft, n_fft float64, 2 floats of room
+    assert scratch() == 12 * 16 * 64 + 2 * 64 + 2
+    assert scratch(T=100000, F=6253) == 12 * (256 + 3) * 64 + 2 * 64 + 2
+    assert scratch(T=100000, F=6253, hop=37, lead=0) == 12 * (256 + 1) * 64 + 2 * 64 + 2
+
+
+def test_filter_argument_errors_and_their_order(lib):
+    for name in ("mix", "ests", "table", "out", "scratch"):
+        assert _filter(lib, **{name: None}) == INVALID, name
+    for kw in ({"S": 0}, {"Cn": 0}, {"Cn": 3}, {"n": 0}, {"hop": 0}, {"hop": 65}, {"hop": 24}, {"hop": 64}, {"power": 0},
+               {"power": 3}, {"eps": 0.0}, {"eps": -1e-10}, {"eps": float("nan")}, {"eps": float("inf")}):
+        assert _filter(lib, **kw) == INVALID, kw
+    for bad in (0, 32, 96, 4096):
+        assert _filter(lib, n_fft=bad) == UNSUPPORTED, bad
+    assert _filter(lib, S=9) == UNSUPPORTED
+    assert _filter(lib, mix=None, n_fft=100) == INVALID and _filter(lib, S=0, n_fft=100) == INVALID
+    assert _filter(lib, n_fft=100, hop=24, power=3) == UNSUPPORTED
+    assert _filter(lib, hop=24, power=3) == INVALID and b"hop" in lib.wun_last_error()
+    assert _filter(lib, power=3, eps=0.0) == INVALID and b"power" in lib.wun_last_error()
+    assert _filter(lib, out=P + 4) == INVALID and b"overlap" in lib.wun_last_error()         # out over the mix
+    assert _filter(lib, out=Q + 4 * (2 * 200 * 2 - 1)) == INVALID                             # out over the last estimate float
+
+    def scratch(S=2, n=200, Cn=2, n_fft=64, hop=16):
+        return lib.wun_mask_filter_scratch_floats(S, n, Cn, n_fft, hop)
+    assert scratch(S=0) == INVALID and scratch(hop=24) == INVALID and scratch(n_fft=100) == UNSUPPORTED and scratch(S=9) == UNSUPPORTED
+    F = ora.centered_frames(200, 64, 16)                                                      # 16 frames: one block
+    assert scratch() == 2 * 3 * 2 * F * 33 + 2 * 2 * F * 64 + 2 * 64 + 2
+    nb = 256 + 3                                                                              # a long track: blocks of 256 + 3
+    assert scratch(n=3 * 60 * 22050, n_fft=2048, hop=512) == 2 * 3 * 2 * nb * 1025 + 2 * 2 * nb * 2048 + 2 * 2048 + 2
+
+
+# ---- the oracle ------------------------------------------------------------------------------
+def test_oracle_against_torch_stft_and_istft():
+    """Where the framings coincide.  lead = 0 with whole frames is torch.stft(center=False).  At hop = n_fft / 2 and T a
+    multiple of the hop the centred framing is torch's center=True with constant padding (lead = n_fft / 2, F = 1 + T / hop),
+    and torch.istft is the same window-square-normalised overlap-add."""
+    rng = np.random.RandomState(3)
+    n_fft, hop, T = 64, 16, 64 + 16 * 9
+    x = 0.3 * rng.randn(3, T)
+    F = sp.num_frames(T, n_fft, hop)
+    re, im = ora.stft(x, n_fft, hop, 0, F)
+    tre, tim = sp.stft(x, n_fft, hop)
+    assert max(np.abs(re - tre).max(), np.abs(im - tim).max()) < 1e-12
+    assert ora.istft(re, im, T, n_fft, hop, 0)[:, 0].tolist() == [0.0] * 3    # w[0] = 0: the window-square sum is 0 there
+    n_fft, hop, T = 64, 32, 32 * 30
+    x = 0.3 * rng.randn(3, T)
+    lead, F = ora.framing(T, n_fft, hop, True)
+    assert lead == n_fft // 2 and F == 1 + T // hop
+    win = torch.hann_window(n_fft, periodic=True, dtype=torch.float64)
+    z = torch.stft(torch.from_numpy(x), n_fft, hop_length=hop, win_length=n_fft, window=win, center=True, pad_mode="constant",
+                   onesided=True, return_complex=True)                         # [R, K, F]
+    re, im = ora.stft(x, n_fft, hop, lead, F)
+    assert max(np.abs(re - z.real.transpose(1, 2).numpy()).max(), np.abs(im - z.imag.transpose(1, 2).numpy()).max()) < 1e-12
+    g = torch.complex(torch.from_numpy(rng.randn(*re.shape)), torch.from_numpy(rng.randn(*re.shape)))
+    g.imag[:, :, 0] = 0                                                        # (torch's inverse ignores Im of the real bins,
+    g.imag[:, :, -1] = 0                                                       #  the definition's Sb is zero there)
+    want = torch.istft(g.transpose(1, 2), n_fft, hop_length=hop, win_length=n_fft, window=win, center=True, length=T).numpy()
+    got = ora.istft(g.real.numpy(), g.imag.numpy(), T, n_fft, hop, lead)
+    err = np.abs(got - want).max()
+    record("test_oracle_against_torch_stft_and_istft", "max |oracle - torch.istft|", err, 1e-12)
+    assert err < 1e-12
+    # centred framing: the inverse of the transform is the signal
+    for T in (5, 1000):
+        x = 0.3 * rng.randn(2, T)
+        lead, F = ora.framing(T, n_fft, hop, True)
+        assert np.abs(ora.istft(*ora.stft(x, n_fft, hop, lead, F), T, n_fft, hop, lead) - x).max() < 1e-14
+
+
+@pytest.mark.parametrize("T", [5, 1000, 5000])
+@pytest.mark.parametrize("n_fft, hop", [(64, 32), (64, 16), (2048, 512)])
+def test_bounds_hold_for_an_fp32_stand_in(n_fft, hop, T):
+    """The bounds the device tests use, tried on float32 numpy first: Re / Im within beta, the inverse of given spectra within
+    istft_bound, the round trip within istft_bound at the float64 spectra plus the propagated beta."""
+    rng = np.random.RandomState(T + n_fft + hop)
+    x = (0.3 * rng.randn(3, T)).astype(np.float32)
+    lead, F = ora.framing(T, n_fft, hop, True)
+    re, im = ora.stft(x, n_fft, hop, lead, F)
+    b = ora.beta(x, n_fft, hop, lead, F)
+    r32, i32 = ora.stft_fp32(x, n_fft, hop, lead, F)
+    assert (np.abs(r32 - re) <= b[:, :, None]).all() and (np.abs(i32 - im) <= b[:, :, None]).all()
+    gre, gim = rng.randn(*re.shape).astype(np.float32), rng.randn(*re.shape).astype(np.float32)
+    y = ora.istft(gre.astype(np.float64), gim.astype(np.float64), T, n_fft, hop, lead)
+    e = np.abs(ora.istft_fp32(gre, gim, T, n_fft, hop, lead) - y)
+    assert (e <= ora.istft_bound(gre, gim, y, T, n_fft, hop, lead)).all()
+    y = ora.istft(re, im, T, n_fft, hop, lead)
+    rt = ora.istft_fp32(r32, i32, T, n_fft, hop, lead)
+    bound = ora.istft_bound(re, im, y, T, n_fft, hop, lead, fwd_beta=b)
+    record("test_bounds_hold_for_an_fp32_stand_in[%d-%d-%d]" % (n_fft, hop, T), "fp32 round trip max |y - x|", np.abs(rt - x).max(), 1e-6)
+    assert (np.abs(rt - y) <= bound).all() and np.abs(y - x).max() < 1e-14
+    assert np.abs(rt - x).max() < 1e-6                                       # 1e-7 .. 4e-7 at amplitude 0.3
+
+
+# ---- the CPU filter ---------------------------------------------------------------------------
+def _cpu_tol(n_fft, mix):
+    """n_fft 2^-24 max |mix|: the worst-case error of one n_fft-term fp32 dot product at the mix's amplitude.  The masks lie in
+    [0, 1] and are well conditioned (the fixture's energy floor), the window-square sums are >= 0.5 and the inverse transform
+    averages (sum_k c_k / n_fft = 1), so neither amplifies it."""
+    return n_fft * 2.0 ** -24 * float(np.abs(mix).max())
+
+
+@pytest.mark.parametrize("power", [2, 1])
+@pytest.mark.parametrize("S, n, C, n_fft, hop", [(2, 1000, 2, 64, 32), (3, 1000, 1, 64, 16), (2, 5000, 2, 2048, 512)])
+def test_cpu_filter_against_float64(S, n, C, n_fft, hop, power):
+    mix, est, want = ora.filter_fixture(7, S, n, C, n_fft, hop, power)
+    f = postfilter.SoftMaskFilter(n_fft, hop, power)
+    got = f.apply(torch.from_numpy(mix), torch.from_numpy(est))
+    assert got.dtype == torch.float32 and tuple(got.shape) == (S, n, C) and not got.is_cuda
+    err = np.abs(got.numpy() - want).max()
+    record("test_cpu_filter_against_float64[%d-%d-%d-p%d]" % (n_fft, hop, n, power), "max err", err, _cpu_tol(n_fft, mix))
+    assert err <= _cpu_tol(n_fft, mix)
+    assert np.abs(got.numpy().astype(np.float64).sum(0) - mix).max() <= _cpu_tol(n_fft, mix)      # the estimates sum to the mix
+    assert np.array_equal(f.apply(mix, est).numpy(), got.numpy())                                 # arrays are taken too
+
+
+def test_cpu_filter_exact_cases():
+    rng = np.random.RandomState(2)
+    mix = torch.from_numpy((0.3 * rng.randn(300, 2)).astype(np.float32))
+    f = postfilter.SoftMaskFilter(64, 16)
+    out = f.apply(mix, torch.zeros(2, 300, 2))
+    assert torch.equal(out[0], out[1])                                       # mask = 0.5 exactly
+    assert np.abs(out.numpy().sum(0) - mix.numpy()).max() <= _cpu_tol(64, mix.numpy())
+    assert bool((f.apply(torch.zeros(300, 2), torch.from_numpy(rng.randn(2, 300, 2).astype(np.float32))) == 0).all())
+
+
+def test_front_end_refuses_bad_settings():
+    F = postfilter.SoftMaskFilter
+    for kw in ({"hop": 24}, {"hop": 0}, {"n_fft": 64, "hop": 64}, {"power": 3}, {"power": 0}, {"eps": 0.0}, {"eps": -1.0},
+               {"eps": float("nan")}, {"eps": 1e-60}, {"n_fft": 64.5}):
+        with pytest.raises(ValueError):
+            F(**kw)
+    for bad in (32, 100, 4096):
+        with pytest.raises(NotImplementedError):
+            F(n_fft=bad, hop=16)
+    f = F()
+    assert f.spec() == {"n_fft": 2048, "hop": 512, "power": 2, "eps": 1e-10}                # the defaults
+    with pytest.raises(ValueError):
+        f.apply(torch.zeros(10, 2), torch.zeros(2, 11, 2))
+    with pytest.raises(ValueError):
+        f.apply(torch.zeros(10, 3), torch.zeros(2, 10, 3))
+
+
+# ---- separate_track -----------------------------------------------------------------------------
+class FakeSeparator(object):
+    """Deterministic numpy stand-in with the separator surface: output = centre crop * per-source gain + an offset."""
+
+    def __init__(self, cfg, t_in, t_out):
+        self.cfg, self.t_in, self.t_out = cfg, t_in, t_out
+
+    def get_padding(self, shape):
+        c = 1 if self.cfg["mono_downmix"] else 2
+        return np.array([shape[0], self.t_in, c]), np.array([shape[0], self.t_out, c])
+
+    def get_output(self, batch, training):
+        assert training is False
+        pad = (self.t_in - self.t_out) // 2
+        core = np.asarray(batch)[:, pad:pad + self.t_out, :]
+        return {n: core * (0.3 + 0.5 * i) + 0.01 * i for i, n in enumerate(self.cfg["source_names"])}
+
+
+@pytest.mark.parametrize("mono, chan, n", [(False, 2, 4099), (True, 2, 1033), (False, 1, 50)])
+def test_separate_track_with_the_filter(mono, chan, n):
+    """At the model's rate the filtered estimates sum to the (channel-mapped) mix; the filter is SoftMaskFilter.apply on the
+    unfiltered estimates and that mix; postfilter=None is the call without the keyword, bit for bit."""
+    cfg = wun.get_config("baseline", mono_downmix=mono, task="multi_instrument")
+    sr = cfg["expected_sr"]
+    audio = np.random.default_rng(n).uniform(-1, 1, (n, chan)).astype(np.float32)
+    plain = separate_track(cfg, FakeSeparator(cfg, 1324, 300), audio, sr, batch_hops=4)
+    none = separate_track(cfg, FakeSeparator(cfg, 1324, 300), audio, sr, batch_hops=4, postfilter=None)
+    assert all(np.array_equal(plain[k], none[k]) for k in cfg["source_names"])
+    spec = {"n_fft": 64, "hop": 16}
+    got = separate_track(cfg, FakeSeparator(cfg, 1324, 300), audio, sr, batch_hops=4, postfilter=spec)
+    mapped = audio.mean(1, keepdims=True) if mono else (np.tile(audio, [1, 2]) if chan == 1 else audio)
+    est = np.stack([plain[k][:, :mapped.shape[1]] for k in cfg["source_names"]])
+    want = postfilter.SoftMaskFilter.from_config(spec).apply(mapped, est).numpy()
+    total = np.zeros_like(mapped, dtype=np.float64)
+    for i, k in enumerate(cfg["source_names"]):
+        assert got[k].dtype == np.float32 and got[k].shape == plain[k].shape
+        assert np.array_equal(got[k][:, :mapped.shape[1]], want[i])
+        assert not np.array_equal(got[k], plain[k])
+        total += got[k][:, :mapped.shape[1]]
+    assert np.abs(total - mapped).max() <= _cpu_tol(64, mapped)
+    same = separate_track(cfg, FakeSeparator(cfg, 1324, 300), audio, sr, batch_hops=4, postfilter=postfilter.SoftMaskFilter(64, 16))
+    assert all(np.array_equal(same[k], got[k]) for k in cfg["source_names"])
+
+
+def test_separate_track_filters_at_the_models_rate():
+    """A 44 100 Hz file on a 22 050 Hz model: the filter runs between the two resamplings, so the estimates still sum to the
+    mix that went through both (resampling is linear: within fp32 rounding of the sum of S signals)."""
+    from wave_u_net_amd import resample as rs
+    cfg = wun.get_config("baseline", mono_downmix=False)
+    n = 4099
+    audio = np.random.default_rng(4).uniform(-1, 1, (n, 2)).astype(np.float32)
+    got = separate_track(cfg, FakeSeparator(cfg, 1324, 300), audio, 44100, batch_hops=4, postfilter={"n_fft": 256, "hop": 64})
+    mid = rs.resample(audio, 44100, 22050)
+    back = rs.resample(mid, 22050, 44100)[:n]
+    total = sum(got[k].astype(np.float64) for k in cfg["source_names"])
+    assert np.abs(total - back).max() <= 2 * _cpu_tol(256, mid)
+
+
+# ---- config and command line --------------------------------------------------------------------
+def test_config_and_cli_spec():
+    assert config.EXTENSION_DEFAULTS["postfilter"] is None and "postfilter" not in config.BASE_MODEL_CONFIG
+    F = postfilter.SoftMaskFilter
+    assert F.from_config(None) is None
+    f = F.from_config({"n_fft": 1024, "hop": 256, "power": 1, "eps": 1e-8})
+    assert f.spec() == {"n_fft": 1024, "hop": 256, "power": 1, "eps": 1e-8} and F.from_config(f) is f
+    assert F.from_config({"hop": 256}).spec() == {"n_fft": 2048, "hop": 256, "power": 2, "eps": 1e-10}
+    assert F.from_config(True).spec() == F().spec()
+    with pytest.raises(ValueError):
+        F.from_config({"n_fft": 1024, "window": "hann"})
+    with pytest.raises(ValueError):
+        F.from_config("wiener")
+    from wave_u_net_amd.__main__ import _parse, _postfilter
+    _, name, over, opts = _parse(["predict", "with", "cfg.full", "input_path=/x.wav", 'postfilter={"n_fft":1024,"hop":256}'])
+    assert opts["postfilter"] == {"n_fft": 1024, "hop": 256}
+    assert _postfilter(opts, wun.get_config(name, **over)).spec()["hop"] == 256
+    _, name, over, opts = _parse(["evaluate", "with", "cfg.full", 'model_config.postfilter={"power":1}', "data_root=/d"])
+    cfg = wun.get_config(name, **over)
+    assert cfg["postfilter"] == {"power": 1} and _postfilter(opts, cfg).power == 1
+    assert _postfilter({}, wun.get_config("full")) is None
+    with pytest.raises(SystemExit):
+        _postfilter({"postfilter": {"hop": 24}}, cfg)

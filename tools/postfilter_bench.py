@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""What the soft-mask post-filter costs, on a synthetic 3-minute stereo two-source track at 22 050 Hz,
+n_fft 2048, hop 512, power 2.
+
+Kernel arm (HIP events on the launch stream around `iters` back-to-back calls, on buffers resident in HBM):
+  mask_filter       wun_mask_filter: mix [n, 2], estimates [2, n, 2] -> [2, n, 2]   (n = 180 * 22050; 7 755 frames in blocks of 256)
+Track arms (a host clock around work that ends in the download of the estimates; same separator, same samples):
+  separate_track            evaluate.separate_track at the model's rate, no filter   (the comparison; there is no target)
+  separate_track_filtered   the same with postfilter = the filter above
+
+  python tools/postfilter_bench.py [--config baseline_stereo] [--rounds 7] [--iters 5] [--out profiles/postfilter_bench.json]
+      the arms interleaved in ONE process for `rounds` rounds (order rotated each round); per arm the median, the minimum and
+      the maximum over the rounds.  One JSON line on stdout, and the same in --out.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+ARMS = ["mask_filter", "separate_track", "separate_track_filtered"]
+SECONDS, N_FFT, HOP = 180, 2048, 512
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="baseline_stereo")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    import wave_u_net_amd as wun
+    from wave_u_net_amd.evaluate import separate_track
+    from wave_u_net_amd.postfilter import SoftMaskFilter
+
+    cfg = wun.get_config(args.config)
+    sep = wun.UnetAudioSeparator(cfg, device="cuda:0")
+    sr = int(cfg["expected_sr"])
+    C = 1 if cfg["mono_downmix"] else 2
+    S = len(cfg["source_names"])
+    n = SECONDS * sr
+    rng = np.random.default_rng(0)
+    audio = rng.uniform(-0.5, 0.5, (n, C)).astype(np.float32)
+    filt = SoftMaskFilter(N_FFT, HOP)
+    mix = torch.from_numpy(audio).cuda()
+    est = torch.from_numpy(rng.uniform(-0.5, 0.5, (S, n, C)).astype(np.float32)).cuda()
+    out = torch.empty_like(est)
+    scratch = torch.empty(filt.scratch_floats(S, n, C), dtype=torch.float32, device="cuda")
+
+    def run(arm):
+        """One measurement of the arm in ms."""
+        if arm == "mask_filter":
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.iters):
+                filt.run(mix, est, out, scratch)
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / args.iters
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        separate_track(cfg, sep, audio, sr, batch_hops=16, postfilter=filt if arm == "separate_track_filtered" else None)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for arm in ARMS:                                              # warm-up: every plan, table and kernel
+        run(arm)
+    times = {a: [] for a in ARMS}
+    for r in range(args.rounds):
+        for arm in ARMS[r % len(ARMS):] + ARMS[:r % len(ARMS)]:
+            times[arm].append(run(arm))
+
+    F = -(-(n + N_FFT - HOP) // HOP)
+    K = N_FFT // 2 + 1
+    flop_fwd = 2.0 * (S + 1) * C * F * N_FFT * 2 * K              # Re and Im of the estimates and the mix
+    flop_inv = 2.0 * S * C * F * N_FFT * 2 * K
+    res = {"tool": "postfilter_bench", "config": args.config, "seconds_of_audio": SECONDS, "expected_sr": sr, "channels": C,
+           "sources": S, "n_fft": N_FFT, "hop": HOP, "power": 2, "frames": F, "rounds": args.rounds, "iters": args.iters,
+           "scratch_MB": round(4 * scratch.numel() / 1e6, 1), "dense_TFLOP": {"forward": round(flop_fwd / 1e12, 3), "inverse": round(flop_inv / 1e12, 3)},
+           "ms": {a: {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)} for a, v in times.items()}}
+    m = res["ms"]
+    res["filter_TFLOPs_at_median"] = round((flop_fwd + flop_inv) / (m["mask_filter"]["median"] * 1e-3) / 1e12, 1)
+    res["separate_track_added_ms_at_median"] = round(m["separate_track_filtered"]["median"] - m["separate_track"]["median"], 3)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -14,6 +14,8 @@ overrides, and the command's own options as `<name>=<value>`.  data_root holds
 train|valid|test/<track>/<source>.wav|.npy (+ optional mix.wav) at expected_sr, or at any rate with the option
 `resample=1` (train, test).  `predict` takes a WAV at any rate and writes the estimates at that rate;
 `hop_frames=<N|track>` makes its hops N output frames long / one hop over the whole track (default: num_frames).
+`postfilter={"n_fft":2048,"hop":512,"power":2,"eps":1e-10}` (predict, evaluate; any subset of the keys, or model_config.postfilter=...)
+masks the estimates against the mix's STFT before they are written / scored (postfilter.SoftMaskFilter).
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
 1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
 source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.
@@ -49,6 +51,15 @@ def _parse(argv):
     return cmd, name, overrides, opts
 
 
+def _postfilter(opts, model_config):
+    """The postfilter= option, else model_config["postfilter"]: checked here, so that a bad spec ends the command at once."""
+    from wave_u_net_amd.postfilter import SoftMaskFilter
+    try:
+        return SoftMaskFilter.from_config(opts.get("postfilter", model_config.get("postfilter")))
+    except (ValueError, NotImplementedError, TypeError) as e:
+        raise SystemExit("postfilter: %s" % e)
+
+
 def main(argv=None):
     cmd, name, overrides, opts = _parse(sys.argv[1:] if argv is None else argv)
     import wave_u_net_amd as wun
@@ -79,7 +90,8 @@ def main(argv=None):
             if need not in opts:
                 raise SystemExit("evaluate needs %s=<dir>" % need)
         folder = evaluate.produce_dataset_estimates(model_config, opts.get("model_path"), opts["data_root"],
-                                                    opts["estimates_path"], partition=opts.get("partition", "test"))
+                                                    opts["estimates_path"], partition=opts.get("partition", "test"),
+                                                    postfilter=_postfilter(opts, model_config))
         for metric in ("SDR", "ISR", "SIR", "SAR"):
             stats = evaluate.compute_mean_metrics(folder, metric=metric)
             for src, (med, mad, mean, sd) in zip(model_config["source_names"], stats):
@@ -91,7 +103,7 @@ def main(argv=None):
         if hop is not None and hop != "track" and (isinstance(hop, bool) or not isinstance(hop, int) or hop < 1):
             raise SystemExit("hop_frames must be a positive frame count or 'track', got %r" % (hop,))
         evaluate.produce_source_estimates(model_config, opts.get("model_path"), opts["input_path"], opts.get("output_path"),
-                                          hop_frames=hop)
+                                          hop_frames=hop, postfilter=_postfilter(opts, model_config))
 
 
 if __name__ == "__main__":

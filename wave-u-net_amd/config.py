@@ -41,6 +41,9 @@ EXTENSION_DEFAULTS = {
     # training.Trainer / spectral.SpectralLoss: None = the reference's MSE; else {"resolutions": [[n_fft, hop], ...],
     # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60)
     "spectral_loss": None,
+    # evaluate.separate_track / postfilter.SoftMaskFilter: None = the estimates as the network gives them; else
+    # {"n_fft": 2048, "hop": 512, "power": 2, "eps": 1e-10} (any subset): the soft-mask filter against the mix's STFT
+    "postfilter": None,
 }
 
 NAMED_CONFIGS = {                # Config.py:52-161 (the Wave-U-Net ones)

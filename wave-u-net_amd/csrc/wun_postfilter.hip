@@ -1,0 +1,496 @@
+// gfx950 (MI355X / CDNA4): the complex STFT, its inverse and the soft-mask post-filter (include/wun.h: wun_stft_complex,
+// wun_istft, wun_mask_filter) -- the synthesis half of wun_spectral.hip's analysis, on the same table.
+//
+//   forward    Re / Im[r][f][k] = sum_n frame_f[n] * Cb / Sb[n][k], frame_f[n] = x[f hop - lead + n], zero outside [0, T):
+//              stft_fwd_kernel's GEMM (wun_spectral.hip) with a bounds-checked gather, n ascending in one accumulator
+//   mask       mask_s = (A_s + eps / S) / (sum_j A_j + eps), A = |E|^p: one lane per bin reads the S estimate spectra and
+//              the mix spectrum once and writes mask_s X over E_s
+//   inverse    frame[m][n] = sum_k (c_k / n_fft) (Re[m][k] Cb[n][k] + Im[m][k] Sb[n][k]): stft_bwd_kernel's transposed GEMM;
+//              the factor c_k / n_fft is a power of two, applied while the spectra are staged (exact)
+//   overlap    y[t] = sum_f frame_f[t + lead - f hop] / sum_f w^2[t + lead - f hop]: one lane per output float, the covering
+//              frames in ascending f, the window squares in float64 from a table the call computes first
+//
+// Frames are processed in blocks of WUN_PF_FRAMES (plus the ceil(n_fft / hop) - 1 frames before a block that its samples also
+// lie in), so scratch does not grow with the track.  A frame's floats do not depend on the block or tile it is computed in (one
+// accumulation order per output), and every output sample belongs to exactly one block (that of its last covering frame):
+// the bits do not depend on the blocking, the grid, the scratch contents or pointer alignment.  No atomics.
+//
+// Built WITHOUT the packed fp32 VALU instructions (csrc/Makefile NO_PK_FP32): the filter runs beside inference of
+// either compute mode.  Every argument check runs before any GPU work; nothing allocates or synchronises.
+#include "wun_device.h"
+#include "../../include/wun.h"
+
+#include <cmath>
+#include <string>
+
+using namespace wun;
+int fail(int code, const std::string& msg);      // wun_plan.hip: sets wun_last_error(), returns code
+
+#define WUN_PF_BLOCK 256             // threads per workgroup of every kernel here (4 waves)
+#define WUN_PF_BM 64                 // frames per GEMM workgroup: 2 x 2 waves, each 32 frames x 16 columns
+#define WUN_PF_BN 32                 // columns per GEMM workgroup (forward: bins, re and im each; inverse: samples of a frame)
+#define WUN_PF_KC 32                 // reduction indices staged per step
+#define WUN_PF_PA 36                 // LDS pitch of a tile read as [row = lane & 15][k = lane >> 4] (wun_spectral.hip)
+#define WUN_PF_PB 48                 // LDS pitch of a tile read as [k = lane >> 4][col = lane & 15]
+#define WUN_PF_FRAMES 256            // new frames per block of wun_istft / wun_mask_filter
+#define WUN_PF_MAX_SOURCES 8
+
+namespace wun {      // the kernels carry the library's wun:: prefix in profiler output
+
+__device__ __forceinline__ f32x4 pf_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// Frame rows of one launch: m = r * nb + fl is frame f0 + fl of row r; its spectrum lies at row r * fstride + foff + fl of
+// re / im [.][K] (a whole transform: nb = fstride = F, f0 = foff = 0; a block of the filter: fstride = nb, foff = 0).
+struct StftCfwdArgs {
+    const float* x[2];               // [SB, T, C]; blockIdx.z picks one (the estimates, the mix)
+    float* re[2]; float* im[2];
+    long long M[2];                  // frame rows of the signal: rows * nb
+    const float* table;              // Cb [n_fft][K], then Sb [n_fft][K]
+    long long T, nb, f0, fstride, foff;
+    int C, n_fft, hop, lead, K;
+};
+
+// grid: x = tile of 64 frame rows, y = tile of 32 bins, z = signal.  stft_fwd_kernel with frames that may reach outside
+// [0, T): every gathered sample is bounds-checked.  Lane layout of the MFMA as there.
+__global__ __launch_bounds__(WUN_PF_BLOCK) void stft_cfwd_kernel(StftCfwdArgs p) {
+    __shared__ float As[WUN_PF_BM * WUN_PF_PA];
+    __shared__ float Bc[WUN_PF_KC * WUN_PF_PB];
+    __shared__ float Bs[WUN_PF_KC * WUN_PF_PB];
+    const int z = blockIdx.z;
+    const long long M = p.M[z];
+    const long long m0 = (long long)blockIdx.x * WUN_PF_BM;
+    if (m0 >= M) return;                                     // (the grid is sized by the larger signal)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int lr = lane & 15, lq = lane >> 4;
+    const int sc = tid & 31, sr = tid >> 5;                  // staging: column and first row of this lane
+    const float* __restrict__ x = p.x[z];
+    const int k0 = (int)blockIdx.y * WUN_PF_BN;
+    const int wm = (w & 1) * 32, wk = (w >> 1) * 16;
+
+    long long rbase[WUN_PF_BM / 8], t0[WUN_PF_BM / 8];       // offset of the row's sample 0 (-1: behind the last frame row)
+#pragma unroll                                               // and the sample index of the frame's n = 0 (may be negative)
+    for (int it = 0; it < WUN_PF_BM / 8; ++it) {
+        const long long m = m0 + sr + 8 * it;
+        rbase[it] = -1; t0[it] = 0;
+        if (m < M) {
+            const long long r = m / p.nb, fl = m - r * p.nb;
+            const long long sb = r / p.C, c = r - sb * p.C;
+            rbase[it] = sb * p.T * p.C + c;
+            t0[it] = (p.f0 + fl) * p.hop - p.lead;
+        }
+    }
+    const bool kin = k0 + sc < p.K;
+    const float* __restrict__ tc = p.table + k0 + sc;
+    const float* __restrict__ ts = tc + (long long)p.n_fft * p.K;
+
+    f32x4 are[2], aim[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { are[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; aim[i] = are[i]; }
+
+    for (int n0 = 0; n0 < p.n_fft; n0 += WUN_PF_KC) {        // ascending n: the one accumulation order
+        __syncthreads();                                     // the previous step is read
+#pragma unroll
+        for (int it = 0; it < WUN_PF_BM / 8; ++it) {
+            const long long t = t0[it] + n0 + sc;
+            const bool in = rbase[it] >= 0 && t >= 0 && t < p.T;
+            As[(sr + 8 * it) * WUN_PF_PA + sc] = in ? x[rbase[it] + t * p.C] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < WUN_PF_KC / 8; ++it) {
+            const int nl = sr + 8 * it;
+            const long long idx = (long long)(n0 + nl) * p.K;
+            Bc[nl * WUN_PF_PB + sc] = kin ? tc[idx] : 0.f;
+            Bs[nl * WUN_PF_PB + sc] = kin ? ts[idx] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < WUN_PF_KC / 4; ++s) {
+            const int kq = 4 * s + lq;
+            const float a0 = As[(wm + lr) * WUN_PF_PA + kq], a1 = As[(wm + 16 + lr) * WUN_PF_PA + kq];
+            const float bc = Bc[kq * WUN_PF_PB + wk + lr], bs = Bs[kq * WUN_PF_PB + wk + lr];
+            are[0] = pf_mfma(a0, bc, are[0]);
+            aim[0] = pf_mfma(a0, bs, aim[0]);
+            are[1] = pf_mfma(a1, bc, are[1]);
+            aim[1] = pf_mfma(a1, bs, aim[1]);
+        }
+    }
+    const int k = k0 + wk + lr;
+    if (k >= p.K) return;
+    float* __restrict__ re = p.re[z];
+    float* __restrict__ im = p.im[z];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+            const long long m = m0 + wm + 16 * i + 4 * lq + r4;
+            if (m >= M) continue;
+            const long long r = m / p.nb, fl = m - r * p.nb;
+            const long long o = (r * p.fstride + p.foff + fl) * p.K + k;
+            re[o] = are[i][r4];
+            im[o] = aim[i][r4];
+        }
+}
+
+// One lane per bin (c, frame, k) of a block: xre / xim [C][nb][K] is the mix spectrum, ere / eim [S][C][nb][K] the estimates',
+// which mask_s * X replaces.  E = C * nb * K bins.  POWER 2: A = Re^2 + Im^2, no square root; POWER 1: its root.
+template <int POWER>
+__global__ __launch_bounds__(WUN_PF_BLOCK) void mask_kernel(const float* __restrict__ xre, const float* __restrict__ xim, float* ere,
+                                                            float* eim, long long E, int S, float eps, float eps_s) {
+    const long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    if (e >= E) return;
+    float A[WUN_PF_MAX_SOURCES];
+    float sum = 0.f;
+#pragma unroll
+    for (int s = 0; s < WUN_PF_MAX_SOURCES; ++s) {           // j ascending
+        A[s] = 0.f;
+        if (s < S) {
+            const float re = ere[s * E + e], im = eim[s * E + e];
+            const float a = re * re + im * im;
+            A[s] = POWER == 2 ? a : sqrtf(a);
+            sum += A[s];
+        }
+    }
+    const float den = sum + eps;
+    const float xr = xre[e], xi = xim[e];
+#pragma unroll
+    for (int s = 0; s < WUN_PF_MAX_SOURCES; ++s)
+        if (s < S) {
+            const float mask = (A[s] + eps_s) / den;
+            ere[s * E + e] = mask * xr;
+            eim[s * E + e] = mask * xi;
+        }
+}
+
+struct IstftGemmArgs {
+    const float* re; const float* im;        // the spectrum of frame row m = r * nb + fl at row r * fstride + foff + fl
+    const float* table;
+    float* frames;                           // [M][n_fft]
+    long long M, nb, fstride, foff;
+    int n_fft, K;
+    float c_edge, c_mid;                     // 1 / n_fft for k = 0 and k = n_fft / 2, 2 / n_fft between
+};
+
+// grid: x = tile of 64 frame rows, y = tile of 32 samples of the frame.  stft_bwd_kernel with the spectra scaled by
+// c_k / n_fft while staged: the reduction runs over the bins in ascending order, a bin's real part before its imaginary part;
+// bins behind K are staged as zeros.
+__global__ __launch_bounds__(WUN_PF_BLOCK) void istft_gemm_kernel(IstftGemmArgs p) {
+    __shared__ float Ar[WUN_PF_BM * WUN_PF_PA];
+    __shared__ float Ai[WUN_PF_BM * WUN_PF_PA];
+    __shared__ float Bc[WUN_PF_BN * WUN_PF_PA];
+    __shared__ float Bs[WUN_PF_BN * WUN_PF_PA];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int lr = lane & 15, lq = lane >> 4;
+    const int sc = tid & 31, sr = tid >> 5;
+    const long long m0 = (long long)blockIdx.x * WUN_PF_BM;
+    const int n0 = (int)blockIdx.y * WUN_PF_BN;
+    const int wm = (w & 1) * 32, wn = (w >> 1) * 16;
+    const float* __restrict__ tc = p.table;
+    const float* __restrict__ ts = p.table + (long long)p.n_fft * p.K;
+
+    long long srow[WUN_PF_BM / 8];                           // first float of this lane's spectrum rows (-1: behind the last)
+#pragma unroll
+    for (int it = 0; it < WUN_PF_BM / 8; ++it) {
+        const long long m = m0 + sr + 8 * it;
+        srow[it] = -1;
+        if (m < p.M) {
+            const long long r = m / p.nb, fl = m - r * p.nb;
+            srow[it] = (r * p.fstride + p.foff + fl) * p.K;
+        }
+    }
+
+    f32x4 acc[2];
+    acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = acc[0];
+    for (int k0 = 0; k0 < p.K; k0 += WUN_PF_KC) {            // ascending k
+        __syncthreads();
+        const int k = k0 + sc;
+        const bool kin = k < p.K;
+        const float ck = (k == 0 || k == p.K - 1) ? p.c_edge : p.c_mid;
+#pragma unroll
+        for (int it = 0; it < WUN_PF_BM / 8; ++it) {
+            const bool in = kin && srow[it] >= 0;
+            Ar[(sr + 8 * it) * WUN_PF_PA + sc] = in ? ck * p.re[srow[it] + k] : 0.f;
+            Ai[(sr + 8 * it) * WUN_PF_PA + sc] = in ? ck * p.im[srow[it] + k] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < WUN_PF_BN / 8; ++it) {
+            const int nl = sr + 8 * it;
+            const long long idx = (long long)(n0 + nl) * p.K + k;
+            Bc[nl * WUN_PF_PA + sc] = kin ? tc[idx] : 0.f;
+            Bs[nl * WUN_PF_PA + sc] = kin ? ts[idx] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < WUN_PF_KC / 4; ++s) {
+            const int kq = 4 * s + lq;
+            const float bc = Bc[(wn + lr) * WUN_PF_PA + kq], bs = Bs[(wn + lr) * WUN_PF_PA + kq];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                acc[i] = pf_mfma(Ar[(wm + 16 * i + lr) * WUN_PF_PA + kq], bc, acc[i]);
+                acc[i] = pf_mfma(Ai[(wm + 16 * i + lr) * WUN_PF_PA + kq], bs, acc[i]);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const long long m = m0 + wm + 16 * i + 4 * lq + r;
+            if (m < p.M) p.frames[m * p.n_fft + n0 + wn + lr] = acc[i][r];
+        }
+}
+
+// wsq[n] = w[n]^2 in float64, w the periodic Hann window (cospi: the argument n / n_fft is exact, no range reduction)
+__global__ __launch_bounds__(WUN_PF_BLOCK) void window_sq_kernel(double* __restrict__ wsq, int n_fft) {
+    const int n = blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    if (n >= n_fft) return;
+    const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)n_fft);
+    wsq[n] = w * w;
+}
+
+struct OlaArgs {
+    const float* frames;                     // [R][nb][n_fft]: frames fb0 .. fb0 + nb - 1 of every row
+    const double* wsq;                       // [n_fft]
+    float* y;                                // [SB, T, C]
+    long long T, F, nb, fb0, t_lo, t_hi, N;  // this launch writes the samples [t_lo, t_hi) of every row: N floats
+    int C, n_fft, hop, lead;
+};
+
+// one lane per output float: the frames that cover the sample in ascending f, over the window squares of the same frames;
+// 0 where those sum to less than 1e-8 (librosa's rule).  Grid-stride: the grid is capped, one writer per float all the same.
+__global__ __launch_bounds__(WUN_PF_BLOCK) void istft_ola_kernel(OlaArgs p) {
+    const long long span = (p.t_hi - p.t_lo) * p.C;
+    for (long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x; e < p.N; e += (long long)gridDim.x * WUN_PF_BLOCK) {
+        const long long sb = e / span, rest = e - sb * span;
+        const long long tl = rest / p.C, c = rest - tl * p.C;
+        const long long t = p.t_lo + tl, u = t + p.lead;     // u - f hop is the sample's place in frame f
+        const long long f_lo = u >= p.n_fft ? (u - p.n_fft) / p.hop + 1 : 0;
+        long long f_hi = u / p.hop;
+        if (f_hi > p.F - 1) f_hi = p.F - 1;
+        const float* __restrict__ fr = p.frames + (sb * p.C + c) * p.nb * p.n_fft;
+        float a = 0.f;
+        double ws = 0.0;
+        for (long long f = f_lo; f <= f_hi; ++f) {
+            const long long n = u - f * p.hop;
+            a += fr[(f - p.fb0) * p.n_fft + n];
+            ws += p.wsq[n];
+        }
+        p.y[(sb * p.T + t) * p.C + c] = ws < 1e-8 ? 0.f : a / (float)ws;
+    }
+}
+
+}  // namespace wun
+
+namespace {
+
+int check_audio(const char* who, int32_t S, int32_t B, int64_t T, int32_t C) {
+    if (S < 1 || B < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": S < 1 or B < 1");
+    if (C != 1 && C != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": C must be 1 or 2");
+    if (T < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": no frames");
+    if ((int64_t)S * B > ((int64_t)1 << 24) || T > ((int64_t)1 << 40) / ((int64_t)S * B * C))
+        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^24 rows or 2^40 floats");
+    return WUN_OK;
+}
+
+// the spectral section's order: n_fft (UNSUPPORTED), then hop (INVALID); a track shorter than a frame is legal here
+int check_res(const char* who, int32_t n_fft, int32_t hop) {
+    if (n_fft < 64 || n_fft > 2048 || (n_fft & (n_fft - 1)))
+        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": n_fft must be a power of two in 64..2048");
+    if (hop < 1 || hop > n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": hop outside 1..n_fft");
+    return WUN_OK;
+}
+
+int check_framing(const char* who, int32_t S, int32_t B, int32_t C, int32_t n_fft, int32_t lead, int64_t F) {
+    if (lead < 0 || lead >= n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": lead outside [0, n_fft)");
+    if (F < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": F < 1");
+    if (F > ((int64_t)1 << 30) / ((int64_t)S * B * C))
+        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^30 frames in all");
+    return WUN_OK;
+}
+
+bool overlaps(const void* a, long long na, const void* b, long long nb) {      // float counts
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + 4 * (uintptr_t)na, b0 = (uintptr_t)b, b1 = b0 + 4 * (uintptr_t)nb;
+    return a0 < b1 && b0 < a1;
+}
+
+long long centered_frames(int64_t T, int32_t n_fft, int32_t hop) { return (T + (n_fft - hop) + hop - 1) / hop; }
+int overlap_frames(int32_t n_fft, int32_t hop) { return (n_fft + hop - 1) / hop - 1; }
+// frames a block holds at most: its own and the overlap before them (or the whole transform, when that is shorter)
+long long block_frames(int64_t F, int32_t n_fft, int32_t hop) {
+    const long long nb = WUN_PF_FRAMES + overlap_frames(n_fft, hop);
+    return F < nb ? F : nb;
+}
+
+// the block of frames [f0, f1): the frames computed for it start at fb0, and its samples are [t_lo, t_hi) -- those whose last
+// covering frame lies in the block (the last block also takes the samples behind the last frame)
+struct Blk { long long fb0, nb, t_lo, t_hi; };
+Blk block_of(long long f0, int64_t F, int64_t T, int32_t n_fft, int32_t hop, int32_t lead) {
+    Blk b;
+    const long long f1 = f0 + WUN_PF_FRAMES < F ? f0 + WUN_PF_FRAMES : F;
+    b.fb0 = f0 - overlap_frames(n_fft, hop);
+    if (b.fb0 < 0) b.fb0 = 0;
+    b.nb = f1 - b.fb0;
+    auto clampT = [T](long long t) { return t < 0 ? 0 : (t > T ? (long long)T : t); };
+    b.t_lo = f0 == 0 ? 0 : clampT(f0 * hop - lead);
+    b.t_hi = f1 == F ? (long long)T : clampT(f1 * hop - lead);
+    return b;
+}
+
+void launch_cfwd(const float* x0, long long rows0, float* re0, float* im0, const float* x1, long long rows1, float* re1,
+                 float* im1, const float* table, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead, long long nb,
+                 long long f0, long long fstride, long long foff, hipStream_t s) {
+    StftCfwdArgs a;
+    a.x[0] = x0; a.re[0] = re0; a.im[0] = im0; a.M[0] = rows0 * nb;
+    a.x[1] = x1; a.re[1] = re1; a.im[1] = im1; a.M[1] = rows1 * nb;
+    a.table = table; a.T = T; a.nb = nb; a.f0 = f0; a.fstride = fstride; a.foff = foff;
+    a.C = C; a.n_fft = n_fft; a.hop = hop; a.lead = lead; a.K = n_fft / 2 + 1;
+    const long long M = a.M[0] > a.M[1] ? a.M[0] : a.M[1];
+    const dim3 grid((unsigned)((M + WUN_PF_BM - 1) / WUN_PF_BM), (unsigned)((a.K + WUN_PF_BN - 1) / WUN_PF_BN), x1 ? 2u : 1u);
+    hipLaunchKernelGGL(stft_cfwd_kernel, grid, dim3(WUN_PF_BLOCK), 0, s, a);
+}
+
+void launch_gemm(const float* re, const float* im, const float* table, float* frames, long long rows, long long nb,
+                 long long fstride, long long foff, int32_t n_fft, hipStream_t s) {
+    IstftGemmArgs g;
+    g.re = re; g.im = im; g.table = table; g.frames = frames; g.M = rows * nb; g.nb = nb; g.fstride = fstride; g.foff = foff;
+    g.n_fft = n_fft; g.K = n_fft / 2 + 1; g.c_edge = 1.f / (float)n_fft; g.c_mid = 2.f / (float)n_fft;
+    hipLaunchKernelGGL(istft_gemm_kernel, dim3((unsigned)((g.M + WUN_PF_BM - 1) / WUN_PF_BM), (unsigned)(n_fft / WUN_PF_BN)),
+                       dim3(WUN_PF_BLOCK), 0, s, g);
+}
+
+void launch_ola(const float* frames, const double* wsq, float* y, long long SB, int64_t T, int32_t C, int64_t F, const Blk& b,
+                int32_t n_fft, int32_t hop, int32_t lead, hipStream_t s) {
+    OlaArgs o;
+    o.frames = frames; o.wsq = wsq; o.y = y; o.T = T; o.F = F; o.nb = b.nb; o.fb0 = b.fb0; o.t_lo = b.t_lo; o.t_hi = b.t_hi;
+    o.N = SB * (b.t_hi - b.t_lo) * C; o.C = C; o.n_fft = n_fft; o.hop = hop; o.lead = lead;
+    long long grid = (o.N + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK;
+    if (grid > (1 << 20)) grid = 1 << 20;
+    hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)grid), dim3(WUN_PF_BLOCK), 0, s, o);
+}
+
+// the float64 window squares sit behind `floats` floats of scratch, on an 8-byte boundary
+double* wsq_of(float* scratch, long long floats) {
+    uintptr_t pa = (uintptr_t)(scratch + floats);
+    pa = (pa + 7) & ~(uintptr_t)7;
+    return (double*)pa;
+}
+
+void launch_window(double* wsq, int32_t n_fft, hipStream_t s) {
+    hipLaunchKernelGGL(window_sq_kernel, dim3((unsigned)((n_fft + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), dim3(WUN_PF_BLOCK), 0, s, wsq,
+                       n_fft);
+}
+
+int check_filter(const char* who, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
+    int rc;
+    if ((rc = check_audio(who, S, 1, n, C))) return rc;
+    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((hop & (hop - 1)) || hop > n_fft / 2)
+        return fail(WUN_ERR_INVALID, std::string(who) + ": hop must be a power of two, at most n_fft / 2");
+    if (S > WUN_PF_MAX_SOURCES) return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": more than 8 sources");
+    return check_framing(who, S + 1, 1, C, n_fft, n_fft - hop, centered_frames(n, n_fft, hop));
+}
+
+}  // namespace
+
+extern "C" int64_t wun_stft_centered_frames(int64_t T, int32_t n_fft, int32_t hop) {
+    int rc;
+    if ((rc = check_res("wun_stft_centered_frames", n_fft, hop))) return rc;
+    if (T < 1 || T > ((int64_t)1 << 40)) return fail(WUN_ERR_INVALID, "wun_stft_centered_frames: T outside 1..2^40");
+    return centered_frames(T, n_fft, hop);
+}
+
+extern "C" int wun_stft_complex(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                                int32_t lead, int64_t F, const float* table_dev, float* re, float* im, void* stream) {
+    const char* who = "wun_stft_complex";
+    if (!x || !table_dev || !re || !im) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    int rc;
+    if ((rc = check_audio(who, S, B, T, C))) return rc;
+    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((rc = check_framing(who, S, B, C, n_fft, lead, F))) return rc;
+    const long long R = (long long)S * B * C, E = R * F * (n_fft / 2 + 1);
+    if (overlaps(re, E, x, R * T) || overlaps(im, E, x, R * T) || overlaps(re, E, im, E))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": re / im overlap the audio or each other");
+    launch_cfwd(x, R, re, im, nullptr, 0, nullptr, nullptr, table_dev, T, C, n_fft, hop, lead, F, 0, F, 0, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
+    return WUN_OK;
+}
+
+extern "C" int64_t wun_istft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
+                                            int64_t F) {
+    const char* who = "wun_istft_scratch_floats";
+    int rc;
+    if ((rc = check_audio(who, S, B, T, C))) return rc;
+    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((rc = check_framing(who, S, B, C, n_fft, lead, F))) return rc;
+    return (int64_t)S * B * C * block_frames(F, n_fft, hop) * n_fft + 2 * (int64_t)n_fft + 2;
+}
+
+extern "C" int wun_istft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                         int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
+    const char* who = "wun_istft";
+    if (!re || !im || !table_dev || !y || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    int rc;
+    if ((rc = check_audio(who, S, B, T, C))) return rc;
+    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((rc = check_framing(who, S, B, C, n_fft, lead, F))) return rc;
+    const long long R = (long long)S * B * C, E = R * F * (n_fft / 2 + 1);
+    if (overlaps(y, R * T, re, E) || overlaps(y, R * T, im, E))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": y overlaps re or im");
+
+    hipStream_t s = (hipStream_t)stream;
+    float* frames = scratch;
+    double* wsq = wsq_of(scratch, R * block_frames(F, n_fft, hop) * n_fft);
+    launch_window(wsq, n_fft, s);
+    for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
+        const Blk b = block_of(f0, F, T, n_fft, hop, lead);
+        if (b.t_lo >= b.t_hi) continue;                      // no sample ends in this block
+        launch_gemm(re, im, table_dev, frames, R, b.nb, F, b.fb0, n_fft, s);
+        launch_ola(frames, wsq, y, (long long)S * B, T, C, F, b, n_fft, hop, lead, s);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
+    return WUN_OK;
+}
+
+extern "C" int64_t wun_mask_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
+    int rc;
+    if ((rc = check_filter("wun_mask_filter_scratch_floats", S, n, C, n_fft, hop))) return rc;
+    const long long nb = block_frames(centered_frames(n, n_fft, hop), n_fft, hop);
+    // spectra of the S estimates and the mix (Re and Im), the frames of the S outputs, the window squares, alignment room
+    return 2 * (int64_t)(S + 1) * C * nb * (n_fft / 2 + 1) + (int64_t)S * C * nb * n_fft + 2 * (int64_t)n_fft + 2;
+}
+
+extern "C" int wun_mask_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                               int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream) {
+    const char* who = "wun_mask_filter";
+    if (!mix_tc || !ests || !table_dev || !out || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    int rc;
+    if ((rc = check_filter(who, S, n, C, n_fft, hop))) return rc;
+    if (power != 1 && power != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": power must be 1 or 2");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(WUN_ERR_INVALID, std::string(who) + ": eps not positive or not finite");
+    const long long N = (long long)S * n * C;
+    if (overlaps(out, N, mix_tc, n * C) || overlaps(out, N, ests, N))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": out overlaps an input");
+
+    hipStream_t s = (hipStream_t)stream;
+    const int K = n_fft / 2 + 1, lead = n_fft - hop;
+    const long long F = centered_frames(n, n_fft, hop), nbmax = block_frames(F, n_fft, hop);
+    const long long Ee = (long long)S * C * nbmax * K, Ex = (long long)C * nbmax * K;
+    float* ere = scratch; float* eim = ere + Ee; float* xre = eim + Ee; float* xim = xre + Ex; float* frames = xim + Ex;
+    double* wsq = wsq_of(frames, (long long)S * C * nbmax * n_fft);
+    launch_window(wsq, n_fft, s);
+    for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
+        const Blk b = block_of(f0, F, n, n_fft, hop, lead);
+        if (b.t_lo >= b.t_hi) continue;
+        launch_cfwd(ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s);
+        const long long E = (long long)C * b.nb * K;         // (a short last block packs its spectra: the source stride is E)
+        const dim3 grid((unsigned)((E + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), blk(WUN_PF_BLOCK);
+        if (power == 2) hipLaunchKernelGGL(mask_kernel<2>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
+        else hipLaunchKernelGGL(mask_kernel<1>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
+        launch_gemm(ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s);
+        launch_ola(frames, wsq, out, S, n, C, F, b, n_fft, hop, lead, s);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
+    return WUN_OK;
+}

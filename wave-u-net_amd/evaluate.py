@@ -107,7 +107,7 @@ def budget_batch_hops(separator, batch_hops, n_hops, input_frames, default_input
 
 
 def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, hop_frames=None, workspace_bytes=None,
-                   return_device=False):
+                   return_device=False, postfilter=None):
     """Evaluate.predict (Evaluate.py:59-80) around predict_track (:82-145) for audio at any sample rate, without the
     host in the loop.  mix_audio: [n_frames, n_channels] float array or tensor at mix_sr Hz.  Returns {source_name: float32
     numpy [n_frames, channels]} at mix_sr: channels is the input's count, except that a stereo model on a mono file
@@ -135,8 +135,15 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     workspace of the default tiling at batch_hops, from wun_plan_query); a last chunk runs on the same plan with zero rows.
 
     return_device=True: no download -- the float32 tensor [S, n_frames, channels] on the separator's device, sources in
-    source_names order (what evaluate_track scores where it lies)."""
+    source_names order (what evaluate_track scores where it lies).
+
+    postfilter (a postfilter.SoftMaskFilter, or the spec its from_config takes; default None: no filter, today's path):
+    the soft-mask filter, applied at the model's rate to the estimates and the resampled mix before the resampling back
+    -- the estimates then share the mix's phase and sum to it."""
     from . import resample as rs
+    if postfilter is not None:
+        from .postfilter import SoftMaskFilter
+        postfilter = SoftMaskFilter.from_config(postfilter)
     device = torch.device(getattr(separator, "device", None) or "cpu")
     x = mix_audio if torch.is_tensor(mix_audio) else torch.from_numpy(np.ascontiguousarray(np.asarray(mix_audio, dtype=np.float32)))
     assert x.dim() == 2                                                          # Evaluate.py:97
@@ -170,6 +177,9 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
                 separator.scatter_windows(chunk, preds, frames=input_frames)
     else:
         preds = _separate_cpu(separator, padded, positions, batch_hops, input_frames, output_frames, names, n_frames, C)
+
+    if postfilter is not None:                                                   # at the model's rate, without extra_pad
+        preds = postfilter.apply(padded[pad:pad + n_res], preds[:, :n_res])
 
     # back to mix_sr, cut to the input's length, mono estimates duplicated to the input's channels (:64-67)
     c_out = ch if (C == 1 and ch > 1) else C
@@ -207,11 +217,12 @@ def _separate_cpu(separator, padded, positions, batch_hops, input_frames, output
     return preds
 
 
-def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None, hop_frames=None):
+def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None, hop_frames=None,
+                             postfilter=None):
     """Evaluate.produce_source_estimates (Evaluate.py:160-194): separate one mixture file with a
     checkpoint and write <input file name>_<source>.wav next to it (or into output_path), at the input file's sample rate
     and length.  WAV/NPY input at any rate (an .npy is taken to be at expected_sr; no MP3 decoding here): the separation runs
-    through separate_track (hop_frames: its option of that name).  Returns {source: [T, C]}."""
+    through separate_track (hop_frames, postfilter: its options of those names).  Returns {source: [T, C]}."""
     import os
     from scipy.io import wavfile
     from . import datasets
@@ -223,7 +234,7 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
-    preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames)
+    preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames, postfilter=postfilter)
     folder, name = os.path.split(input_path)
     if output_path is None:
         output_path = folder
@@ -234,14 +245,15 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
 
 
 def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=None, name=None, hop_frames=None,
-                   window=1.0, hop=1.0, filters_len=512):
+                   window=1.0, hop=1.0, filters_len=512, postfilter=None):
     """Evaluate.predict with a results_dir (Evaluate.py:59-80,146-158): separate the mixture (separate_track, estimates kept
     on the device), score them against the stems at the file's rate with bsseval.bss_eval, and write
     <results_dir>/<name>.json in museval's layout.  mix_audio [n, c] at sr; stems {source_name: [n, c]} at sr with the
     channel count of the estimates (a stereo model on a mono file gives two channels: mono stems are duplicated).  Signals
     are cut to the shortest length.  Returns {metric: float64 [S, nwin]}, sources in source_names order."""
     from . import bsseval
-    est = separate_track(model_config, separator, mix_audio, sr, hop_frames=hop_frames, return_device=True)
+    est = separate_track(model_config, separator, mix_audio, sr, hop_frames=hop_frames, return_device=True,
+                         postfilter=postfilter)
     names = list(model_config["source_names"])
     c = int(est.shape[2])
     refs = []
@@ -293,7 +305,7 @@ def compute_mean_metrics(json_folder, compute_averages=True, metric="SDR"):
 
 
 def produce_dataset_estimates(model_config, load_model, data_root, output_path, partition="test", separator=None,
-                              hop_frames=None):
+                              hop_frames=None, postfilter=None):
     """The reference's produce_musdb_source_estimates (Evaluate.py:147-159) over the track folders of datasets.py:
     data_root/<partition>/<track>/<source>.wav|.npy (+ optional mix.wav|.npy, default: the sum of the stems), every file at
     one rate (an .npy: expected_sr).  Per track: the estimates as <output_path>/<partition>/<track>/<source>.wav and the
@@ -327,7 +339,7 @@ def produce_dataset_estimates(model_config, load_model, data_root, output_path, 
                     raise FileNotFoundError("%s: no %s.wav/.npy" % (folder, k))
         sr = int(sr) if sr is not None else int(model_config["expected_sr"])
         mix = stems.pop("mix") if "mix" in stems else sum(stems[k] for k in names)
-        est = separate_track(model_config, sep, mix, sr, hop_frames=hop_frames, return_device=True)
+        est = separate_track(model_config, sep, mix, sr, hop_frames=hop_frames, return_device=True, postfilter=postfilter)
         c = int(est.shape[2])
         refs = [np.tile(stems[k], [1, c]) if stems[k].shape[1] == 1 and c > 1 else stems[k] for k in names]
         n = min([int(est.shape[1])] + [r.shape[0] for r in refs])

@@ -1,0 +1,142 @@
+"""The soft-mask post-filter of libwun.so (include/wun.h: wun_mask_filter): the estimates of a track are
+masked against the mixture's own STFT, so they share the mixture's phase and sum back to the mixture.
+
+    f = SoftMaskFilter(n_fft=2048, hop=512, power=2, eps=1e-10)
+    out = f.apply(mix, estimates)                      # mix [n, C], estimates [S, n, C] -> [S, n, C]
+    evaluate.separate_track(cfg, sep, audio, sr, postfilter=f)      # or model_config["postfilter"] = {"n_fft": 2048, ...}
+
+Per channel, in the centred framing (frame f starts at f hop - (n_fft - hop), zeros outside the track):
+X = STFT(mix), E_s = STFT(est_s), A_s = |E_s|^power, mask_s = (A_s + eps / S) / (sum_j A_j + eps), out_s = ISTFT(mask_s X).
+Tensors on the GPU go through wun_mask_filter (no host sync; scratch cached per shape, tables shared with spectral.py); CPU
+tensors through a plain torch float32 implementation of the same definition (numpy stand-in separators, host tests).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, spectral
+
+MAX_SOURCES = 8
+_KEYS = ("n_fft", "hop", "power", "eps")
+
+
+class SoftMaskFilter(object):
+    """ValueError / NotImplementedError at construction for what wun_mask_filter refuses: n_fft must be a power of two in
+    64..2048, hop a power of two of at most n_fft / 2 (every sample's window-square sum is then at least 0.5), power 1
+    (magnitude ratio mask) or 2 (power ratio mask, single-channel Wiener), eps finite and positive."""
+
+    def __init__(self, n_fft=2048, hop=512, power=2, eps=1e-10):
+        for what, v in (("n_fft", n_fft), ("hop", hop), ("power", power)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("%s must be an integer, got %r" % (what, v))
+        self.n_fft, self.hop, self.power, self.eps = int(n_fft), int(hop), int(power), float(eps)
+        if self.n_fft < 64 or self.n_fft > 2048 or self.n_fft & (self.n_fft - 1):
+            raise NotImplementedError("n_fft must be a power of two in 64..2048, got %d" % self.n_fft)
+        if self.hop < 1 or self.hop & (self.hop - 1) or self.hop > self.n_fft // 2:
+            raise ValueError("hop must be a power of two, at most n_fft / 2, got %d" % self.hop)
+        if self.power not in (1, 2):
+            raise ValueError("power must be 1 or 2, got %d" % self.power)
+        if not (self.eps > 0.0 and np.isfinite(self.eps) and np.float32(self.eps) > 0):
+            raise ValueError("eps must be finite and positive in float32, got %r" % (eps,))
+        self._scratch = {}       # (S, n, C, device) -> float32 scratch of wun_mask_filter_scratch_floats
+
+    @classmethod
+    def from_config(cls, spec):
+        """model_config["postfilter"]: None, a SoftMaskFilter, True (the defaults) or a dict with any of `n_fft`, `hop`,
+        `power`, `eps`."""
+        if spec is None or isinstance(spec, cls):
+            return spec
+        if spec is True:
+            return cls()
+        if not isinstance(spec, dict):
+            raise ValueError("postfilter must be None, True or a dict with %s, got %r" % (", ".join(_KEYS), spec))
+        unknown = set(spec) - set(_KEYS)
+        if unknown:
+            raise ValueError("postfilter: unknown keys %s" % sorted(unknown))
+        return cls(**spec)
+
+    def spec(self):
+        return {"n_fft": self.n_fft, "hop": self.hop, "power": self.power, "eps": self.eps}
+
+    def scratch_floats(self, S, n, Cn):
+        k = int(_lib.load().wun_mask_filter_scratch_floats(int(S), int(n), int(Cn), self.n_fft, self.hop))
+        if k < 0:
+            _lib.check(k)
+        return k
+
+    def run(self, mix, estimates, out, scratch):
+        """wun_mask_filter on the caller's buffers (contiguous float32 device tensors)."""
+        S, n, Cn = (int(v) for v in estimates.shape)
+        dev = estimates.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wun_mask_filter(
+                mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps,
+                spectral._table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def apply(self, mix, estimates):
+        """mix [n, C], estimates [S, n, C] (tensors of one device, or arrays) -> the filtered estimates, float32 [S, n, C] on
+        that device."""
+        mix = mix if torch.is_tensor(mix) else torch.from_numpy(np.ascontiguousarray(np.asarray(mix, dtype=np.float32)))
+        estimates = estimates if torch.is_tensor(estimates) else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(estimates, dtype=np.float32)))
+        if mix.dim() != 2 or estimates.dim() != 3 or tuple(estimates.shape[1:]) != tuple(mix.shape):
+            raise ValueError("mix must be [n, C] and estimates [S, n, C], got %s and %s" % (tuple(mix.shape), tuple(estimates.shape)))
+        if mix.device != estimates.device:
+            raise ValueError("mix on %s, estimates on %s" % (mix.device, estimates.device))
+        mix, estimates = mix.to(torch.float32).contiguous(), estimates.to(torch.float32).contiguous()
+        if not estimates.is_cuda:
+            return self._apply_cpu(mix, estimates)
+        S, n, Cn = (int(v) for v in estimates.shape)
+        key = (S, n, Cn, str(estimates.device))
+        if key not in self._scratch:
+            self._scratch[key] = torch.empty(self.scratch_floats(S, n, Cn), dtype=torch.float32, device=estimates.device)
+        out = torch.empty_like(estimates)
+        self.run(mix, estimates, out, self._scratch[key])
+        return out
+
+    def _apply_cpu(self, mix, estimates):
+        """The definition in torch float32 on the CPU: framed matmuls against the library's fp32 table, the window-square
+        sums in float64."""
+        S, n, Cn = (int(v) for v in estimates.shape)
+        if S < 1 or n < 1 or Cn not in (1, 2):
+            raise ValueError("S < 1, n < 1 or C not 1 or 2")
+        if S > MAX_SOURCES:
+            raise NotImplementedError("more than %d sources" % MAX_SOURCES)
+        n_fft, hop = self.n_fft, self.hop
+        lead = n_fft - hop
+        F = -(-(n + lead) // hop)
+        total = (F - 1) * hop + n_fft
+        tab = torch.from_numpy(spectral.design(n_fft))
+        cb, sb = tab[0], tab[1]                                                  # [n_fft, K]
+
+        def transform(x):                                                        # [..., n, C] -> Re, Im [..., C, F, K]
+            xp = torch.zeros(x.shape[:-2] + (Cn, total), dtype=torch.float32)
+            xp[..., lead:lead + n] = x.transpose(-1, -2)
+            fr = xp.unfold(-1, n_fft, hop)
+            return fr @ cb, fr @ sb
+
+        xre, xim = transform(mix)
+        ere, eim = transform(estimates)
+        a = ere * ere + eim * eim
+        if self.power == 1:
+            a = torch.sqrt(a)
+        eps = torch.tensor(self.eps, dtype=torch.float32)
+        den = a[0]
+        for s in range(1, S):                                                    # j ascending
+            den = den + a[s]
+        den = den + eps
+        mask = (a + eps / torch.tensor(float(S), dtype=torch.float32)) / den
+        ck = torch.full((n_fft // 2 + 1,), 2.0 / n_fft, dtype=torch.float32)
+        ck[0] = ck[-1] = 1.0 / n_fft
+        frames = (mask * xre * ck) @ cb.t() + (mask * xim * ck) @ sb.t()         # [S, C, F, n_fft]
+        y = torch.zeros((S, Cn, total), dtype=torch.float32)
+        w = 0.5 - 0.5 * torch.cos(2.0 * np.pi * torch.arange(n_fft, dtype=torch.float64) / n_fft)
+        ws = torch.zeros(total, dtype=torch.float64)
+        for f in range(F):                                                       # ascending f
+            y[..., f * hop:f * hop + n_fft] += frames[..., f, :]
+            ws[f * hop:f * hop + n_fft] += w * w
+        live = ws >= 1e-8
+        y = torch.where(live, y / torch.where(live, ws, torch.ones_like(ws)).to(torch.float32), torch.zeros_like(y))
+        return y[..., lead:lead + n].transpose(-1, -2).contiguous()

@@ -7,6 +7,8 @@ Hann window, no padding), for any number of resolutions up to 8, next to the tim
     losses, d_outputs = loss.loss_and_grad(outputs, targets)      # [total, MSE, L_0, L_1], dL / d outputs
     sep.loss_and_gradients(targets, loss=loss)         # the training step's loss (UnetAudioSeparator, Trainer)
     stft_l1(net(mix), targets, loss)                   # under torch.autograd, for users of sep.module()
+    re, im = stft(x, 2048, 512, centered=True)         # the complex STFT [S, B, C, F, K]
+    x2 = istft(re, im, x.shape[2], 2048, 512, centered=True)      # and its inverse: x again, to fp32 rounding
 
 Audio is float32 [S, B, T, C] channel-last on the GPU, as get_output stacks its outputs.  There is no CPU path.
 """
@@ -71,6 +73,63 @@ def stft_magnitude(x, n_fft, hop):
         _lib.check(_lib.load().wun_stft_magnitude(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop),
                                                   _table(n_fft, x.device).data_ptr(), mags.data_ptr(), _stream(x.device)))
     return mags
+
+
+def centered_frames(n, n_fft, hop):
+    """Frames of n samples in the centred framing: ceil((n + n_fft - hop) / hop) (wun_stft_centered_frames)."""
+    f = int(_lib.load().wun_stft_centered_frames(int(n), int(n_fft), int(hop)))
+    if f < 0:
+        _lib.check(f)
+    return f
+
+
+def _framing(T, n_fft, hop, centered):
+    """(lead, F): centered: lead = n_fft - hop samples of zeros before the track, frames until the track is covered;
+    else the framing of the loss, lead = 0 and frames(T, n_fft, hop) whole frames."""
+    if centered:
+        return int(n_fft) - int(hop), centered_frames(T, n_fft, hop)
+    return 0, frames(T, n_fft, hop)
+
+
+def stft(x, n_fft, hop, centered=False):
+    """(re, im) of audio x [S, B, T, C]: float32 [S, B, C, F, K] each (wun_stft_complex).  centered=False: the loss's
+    framing (no padding, T >= n_fft); centered=True: frame f starts at f hop - (n_fft - hop), zeros outside the track,
+    F = centered_frames(T, n_fft, hop), any T >= 1.  One launch on the current stream, no sync."""
+    x = _audio(x, "x")
+    S, B, T, Cn = (int(v) for v in x.shape)
+    lead, F = _framing(T, n_fft, hop, centered)
+    re = torch.empty((S, B, Cn, F, int(n_fft) // 2 + 1), dtype=torch.float32, device=x.device)
+    im = torch.empty_like(re)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().wun_stft_complex(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), lead, F,
+                                                _table(n_fft, x.device).data_ptr(), re.data_ptr(), im.data_ptr(),
+                                                _stream(x.device)))
+    return re, im
+
+
+def istft(re, im, length, n_fft, hop, centered=False):
+    """Audio [S, B, length, C] from re, im [S, B, C, F, K] (wun_istft): the windowed overlap-add of the inverse transforms
+    of the frames over the overlap-add of the squared window, 0 where that is below 1e-8.  F must be the frame count of
+    `length` in the chosen framing.  No sync; not differentiable."""
+    if not (torch.is_tensor(re) and torch.is_tensor(im) and re.is_cuda and im.is_cuda):
+        raise ValueError("re and im must be tensors on the GPU (there is no CPU path)")
+    if re.dim() != 5 or re.shape != im.shape or re.device != im.device:
+        raise ValueError("re and im must be [S, B, C, F, K] of one shape and device, got %s and %s" % (tuple(re.shape), tuple(im.shape)))
+    re, im = re.to(torch.float32).contiguous(), im.to(torch.float32).contiguous()
+    S, B, Cn, F, K = (int(v) for v in re.shape)
+    lead, want = _framing(int(length), n_fft, hop, centered)
+    if F != want or K != int(n_fft) // 2 + 1:
+        raise ValueError("spectra of %d frames x %d bins, expected %d x %d for length %d" % (F, K, want, int(n_fft) // 2 + 1, length))
+    lib = _lib.load()
+    n = int(lib.wun_istft_scratch_floats(S, B, int(length), Cn, int(n_fft), int(hop), lead, F))
+    if n < 0:
+        _lib.check(n)
+    scratch = torch.empty(n, dtype=torch.float32, device=re.device)
+    y = torch.empty((S, B, int(length), Cn), dtype=torch.float32, device=re.device)
+    with torch.cuda.device(re.device):
+        _lib.check(lib.wun_istft(re.data_ptr(), im.data_ptr(), S, B, int(length), Cn, int(n_fft), int(hop), lead, F,
+                                 _table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
+    return y
 
 
 class SpectralLoss(object):
