@@ -538,6 +538,37 @@ int64_t wun_mask_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t 
 int     wun_mask_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
                         int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream);
 
+/* ---- multichannel Wiener post-filter: EM iterations of a local Gaussian model ----
+ * What the soft mask cannot use is where a source sits between the channels.  For one track with mix [n, C] and estimates
+ * [S, n, C], in the centred framing above, with X = STFT(mix), E_s = STFT(est_s) and vectors over the C channels:
+ *   y_s(0) = mask_s X, the soft-mask filter exactly as defined above (power p in {1, 2}; mask_eps is its eps).
+ *   For it = 1 .. I, every sum in ascending index order:
+ *     v_s[f,k]  = (1 / C) sum_c |y_s[f,k,c]|^2
+ *     R_s[k]    = (sum_f y_s[f,k] y_s[f,k]^H) / (eps + sum_f v_s[f,k])     C x C Hermitian, over ALL F frames of the track
+ *     Cxx[f,k]  = sum_s v_s[f,k] R_s[k] + sqrt(eps) I
+ *     y_s[f,k] <- v_s[f,k] R_s[k] Cxx[f,k]^-1 X[f,k]
+ *   out_s = ISTFT(y_s(I)) over [0, n), through the inverse above.
+ * The statistics (v, both sums, R) and the per-bin algebra (Cxx, its closed-form inverse, the gain, the product with X) are
+ * computed in float64; spectra are stored as float32, so each y_s(it) is rounded to float32 once.  There is no global
+ * rescaling of the mix (norbert's max_abs): with float64 algebra it is not needed.  Parity with norbert is not claimed.
+ * C in {1, 2}, S <= 8, I in 0..4; defaults of the callers: p = 2, mask_eps = 1e-10, I = 1, eps = 1e-10.
+ * I = 0 is wun_mask_filter, bit for bit.  The y_s sum to (Cxx - sqrt(eps) I) Cxx^-1 X: the mix up to the regulariser.
+ * R_s needs the whole track and scratch must not grow with it, so the call makes I + 1 passes over the blocks of 256 frames:
+ * pass i < I recomputes a block's spectra and mask, applies R(1) .. R(i) to reach y(i) (a frame's y(i) depends on that frame
+ * and the R's alone) and adds the block's statistics of R(i+1); the last pass applies all I filters and inverts.  The
+ * statistics are partial sums over chunks of 16 frames aligned to absolute frame numbers, added in ascending chunk order: no
+ * atomics, the same bits from run to run, whatever `scratch` held.  Contract, checks and their order as wun_mask_filter; then
+ * WUN_ERR_INVALID for `iterations` outside 0..4 or an `eps` that is not finite and positive.  Both compute modes. */
+
+/* floats of `scratch` for wun_wiener_filter: wun_mask_filter_scratch_floats(S, n, C, n_fft, hop), plus, for iterations > 0,
+ * 2 (iterations + 16) S (C^2 + 1) K -- per (source, bin) the C^2 real numbers of the Hermitian R and sum_f v, as float64, for
+ * every iteration, and the 16 chunks' partial sums of one block.  Negative wun_status as wun_wiener_filter. */
+int64_t wun_wiener_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations);
+/* out (device [S, n, C], every float written once) = the Wiener filter of ests [S, n, C] against mix_tc [n, C]. */
+int     wun_wiener_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                          int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev,
+                          float* out, float* scratch, void* stream);
+
 /* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
  * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
  * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is

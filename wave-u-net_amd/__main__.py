@@ -15,7 +15,9 @@ train|valid|test/<track>/<source>.wav|.npy (+ optional mix.wav) at expected_sr, 
 `resample=1` (train, test).  `predict` takes a WAV at any rate and writes the estimates at that rate;
 `hop_frames=<N|track>` makes its hops N output frames long / one hop over the whole track (default: num_frames).
 `postfilter={"n_fft":2048,"hop":512,"power":2,"eps":1e-10}` (predict, evaluate; any subset of the keys, or model_config.postfilter=...)
-masks the estimates against the mix's STFT before they are written / scored (postfilter.SoftMaskFilter).
+masks the estimates against the mix's STFT before they are written / scored (postfilter.SoftMaskFilter);
+`postfilter={"kind":"wiener","iterations":1,"em_eps":1e-10}` (with any of the keys above) is the multichannel Wiener filter instead
+(postfilter.WienerFilter: EM iterations over the channels together; "kind":"softmask" is the default).
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
 1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
 source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.
@@ -53,9 +55,9 @@ def _parse(argv):
 
 def _postfilter(opts, model_config):
     """The postfilter= option, else model_config["postfilter"]: checked here, so that a bad spec ends the command at once."""
-    from wave_u_net_amd.postfilter import SoftMaskFilter
+    from wave_u_net_amd.postfilter import from_config
     try:
-        return SoftMaskFilter.from_config(opts.get("postfilter", model_config.get("postfilter")))
+        return from_config(opts.get("postfilter", model_config.get("postfilter")))
     except (ValueError, NotImplementedError, TypeError) as e:
         raise SystemExit("postfilter: %s" % e)
 

@@ -42,7 +42,8 @@ EXTENSION_DEFAULTS = {
     # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60)
     "spectral_loss": None,
     # evaluate.separate_track / postfilter.SoftMaskFilter: None = the estimates as the network gives them; else
-    # {"n_fft": 2048, "hop": 512, "power": 2, "eps": 1e-10} (any subset): the soft-mask filter against the mix's STFT
+    # {"n_fft": 2048, "hop": 512, "power": 2, "eps": 1e-10} (any subset): the soft-mask filter against the mix's STFT; with
+    # "kind": "wiener" (and "iterations": 1, "em_eps": 1e-10) postfilter.WienerFilter, the multichannel Wiener filter
     "postfilter": None,
 }
 

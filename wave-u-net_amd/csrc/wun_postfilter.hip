@@ -1,5 +1,6 @@
-// gfx950 (MI355X / CDNA4): the complex STFT, its inverse and the soft-mask post-filter (include/wun.h: wun_stft_complex,
-// wun_istft, wun_mask_filter) -- the synthesis half of wun_spectral.hip's analysis, on the same table.
+// gfx950 (MI355X / CDNA4): the complex STFT, its inverse, the soft-mask post-filter and the multichannel Wiener (EM) filter
+// (include/wun.h: wun_stft_complex, wun_istft, wun_mask_filter, wun_wiener_filter) -- the synthesis half
+// of wun_spectral.hip's analysis, on the same table.
 //
 //   forward    Re / Im[r][f][k] = sum_n frame_f[n] * Cb / Sb[n][k], frame_f[n] = x[f hop - lead + n], zero outside [0, T):
 //              stft_fwd_kernel's GEMM (wun_spectral.hip) with a bounds-checked gather, n ascending in one accumulator
@@ -9,6 +10,9 @@
 //              the factor c_k / n_fft is a power of two, applied while the spectra are staged (exact)
 //   overlap    y[t] = sum_f frame_f[t + lead - f hop] / sum_f w^2[t + lead - f hop]: one lane per output float, the covering
 //              frames in ascending f, the window squares in float64 from a table the call computes first
+//   EM         (wun_wiener_filter) per iteration: statistics sum_f y y^H and sum_f v per (source, bin) in float64 -- partial sums
+//              over chunks of WUN_WF_CHUNK frames aligned to absolute frame numbers, then one reduction in ascending chunk order
+//              -- and the per-bin C x C complex algebra v_s R_s Cxx^-1 X in float64 registers, one lane per (frame, bin)
 //
 // Frames are processed in blocks of WUN_PF_FRAMES (plus the ceil(n_fft / hop) - 1 frames before a block that its samples also
 // lie in), so scratch does not grow with the track.  A frame's floats do not depend on the block or tile it is computed in (one
@@ -34,6 +38,8 @@ int fail(int code, const std::string& msg);      // wun_plan.hip: sets wun_last_
 #define WUN_PF_PB 48                 // LDS pitch of a tile read as [k = lane >> 4][col = lane & 15]
 #define WUN_PF_FRAMES 256            // new frames per block of wun_istft / wun_mask_filter
 #define WUN_PF_MAX_SOURCES 8
+#define WUN_WF_CHUNK 16              // frames per partial sum of the EM statistics; divides WUN_PF_FRAMES
+#define WUN_WF_MAX_ITERS 4
 
 namespace wun {      // the kernels carry the library's wun:: prefix in profiler output
 
@@ -278,6 +284,156 @@ __global__ __launch_bounds__(WUN_PF_BLOCK) void istft_ola_kernel(OlaArgs p) {
     }
 }
 
+// ---- the multichannel Wiener filter's EM iterations ----
+// Statistics of one (source, bin): Q = CH^2 + 1 doubles, stored [S][Q][K].  CH = 2: sum |y_0|^2, sum |y_1|^2, Re and Im of
+// sum y_0 conj(y_1), sum v;  CH = 1: sum |y|^2, sum v.  Divided by eps + sum v they are R_s[k] (Hermitian: its CH^2 real
+// numbers); the last entry keeps sum v.
+
+// One lane per (source, chunk of WUN_WF_CHUNK frames, bin), the bin fastest: walks its frames in ascending order and writes the
+// chunk's partial sums to part [nch][S][Q][K].  yre / yim [S][CH][nf][K] are the block's spectra; the block starts at a
+// multiple of WUN_PF_FRAMES, so chunk c holds the absolute frames [f0 + 16 c, f0 + 16 c + 16) whatever the track's length.
+template <int CH>
+__global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_stats_kernel(const float* __restrict__ yre, const float* __restrict__ yim,
+                                                                    double* __restrict__ part, int S, int nf, int K) {
+    constexpr int Q = CH * CH + 1;
+    const int nch = (nf + WUN_WF_CHUNK - 1) / WUN_WF_CHUNK;
+    const long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    if (e >= (long long)S * nch * K) return;
+    const int k = (int)(e % K);
+    const int t = (int)(e / K), ch = t % nch, s = t / nch;
+    const long long NK = (long long)nf * K;
+    double acc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = 0.0;
+    const int fl1 = (ch + 1) * WUN_WF_CHUNK < nf ? (ch + 1) * WUN_WF_CHUNK : nf;
+    for (int fl = ch * WUN_WF_CHUNK; fl < fl1; ++fl) {       // ascending f
+        const long long i0 = (long long)s * CH * NK + (long long)fl * K + k;
+        const double ar = yre[i0], ai = yim[i0];
+        const double p0 = ar * ar + ai * ai;
+        if constexpr (CH == 1) {
+            acc[0] += p0;
+            acc[1] += p0;
+        } else {
+            const double br = yre[i0 + NK], bi = yim[i0 + NK];
+            const double p1 = br * br + bi * bi;
+            acc[0] += p0;
+            acc[1] += p1;
+            acc[2] += ar * br + ai * bi;                     // y_0 conj(y_1)
+            acc[3] += ai * br - ar * bi;
+            acc[CH * CH] += 0.5 * (p0 + p1);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) part[(((long long)ch * S + s) * Q + q) * K + k] = acc[q];
+}
+
+// One lane per (source, bin): adds the block's nch partial sums, in ascending chunk order, to the running sums (`first`: the
+// track's first block starts them from 0, so nothing is read that this call did not write).  `last`: the track's last block
+// then divides by eps + sum v, leaving R_s[k] and sum v.
+template <int Q>
+__global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_reduce_kernel(const double* __restrict__ part, double* __restrict__ stat, int S,
+                                                                     int K, int nch, int first, int last, double eps) {
+    const int e = blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    if (e >= S * K) return;
+    const int s = e / K, k = e - s * K;
+    double a[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const long long o = ((long long)s * Q + q) * K + k;
+        a[q] = first ? 0.0 : stat[o];
+        for (int c = 0; c < nch; ++c) a[q] += part[(long long)c * S * Q * K + o];
+    }
+    if (last) {
+        const double den = eps + a[Q - 1];
+#pragma unroll
+        for (int q = 0; q < Q - 1; ++q) a[q] /= den;
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) stat[((long long)s * Q + q) * K + k] = a[q];
+}
+
+// One lane per (frame, bin) of a block, mask_kernel's access pattern: reads X (xre / xim [CH][nb][K]) and the S masked spectra
+// (yre / yim [S][CH][nb][K]) once, applies the `niter` filters R [niter][S][Q][K] one after the other -- v_s, Cxx = sum_s v_s
+// R_s + sq I, its closed-form inverse and y_s = v_s R_s Cxx^-1 X in float64, each y rounded to float32 (a stored spectrum) --
+// and writes the last y over the masked spectra.  NK = nb * K.
+template <int CH>
+__global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_apply_kernel(const float* __restrict__ xre, const float* __restrict__ xim,
+                                                                    float* yre, float* yim, const double* __restrict__ R, long long NK,
+                                                                    int S, int K, int niter, double sq) {
+    constexpr int Q = CH * CH + 1;
+    const long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    if (e >= NK) return;
+    const int k = (int)(e % K);
+    float yr[WUN_PF_MAX_SOURCES][CH], yi[WUN_PF_MAX_SOURCES][CH];
+    double xr[CH], xi[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) { xr[c] = xre[c * NK + e]; xi[c] = xim[c * NK + e]; }
+#pragma unroll
+    for (int s = 0; s < WUN_PF_MAX_SOURCES; ++s)
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            yr[s][c] = 0.f; yi[s][c] = 0.f;
+            if (s < S) { yr[s][c] = yre[(s * CH + c) * NK + e]; yi[s][c] = yim[(s * CH + c) * NK + e]; }
+        }
+    for (int it = 0; it < niter; ++it) {
+        const double* __restrict__ Rt = R + (long long)it * S * Q * K + k;
+        double v[WUN_PF_MAX_SOURCES];
+        double a = 0.0, d = 0.0, br = 0.0, bi = 0.0;         // Cxx = [a, b; conj(b), d]  (CH = 1: a alone)
+#pragma unroll
+        for (int s = 0; s < WUN_PF_MAX_SOURCES; ++s) {       // s ascending
+            v[s] = 0.0;
+            if (s < S) {
+                const double p0 = (double)yr[s][0] * yr[s][0] + (double)yi[s][0] * yi[s][0];
+                if constexpr (CH == 1) {
+                    v[s] = p0;
+                    a += v[s] * Rt[(long long)s * Q * K];
+                } else {
+                    const double p1 = (double)yr[s][CH - 1] * yr[s][CH - 1] + (double)yi[s][CH - 1] * yi[s][CH - 1];
+                    v[s] = 0.5 * (p0 + p1);
+                    a += v[s] * Rt[((long long)s * Q + 0) * K];
+                    d += v[s] * Rt[((long long)s * Q + 1) * K];
+                    br += v[s] * Rt[((long long)s * Q + 2) * K];
+                    bi += v[s] * Rt[((long long)s * Q + 3) * K];
+                }
+            }
+        }
+        a += sq; d += sq;
+        double zr[CH], zi[CH];                               // z = Cxx^-1 X
+        if constexpr (CH == 1) {
+            zr[0] = xr[0] / a; zi[0] = xi[0] / a;
+        } else {
+            const double det = a * d - (br * br + bi * bi);
+            zr[0] = (d * xr[0] - (br * xr[CH - 1] - bi * xi[CH - 1])) / det;       // d X_0 - b X_1
+            zi[0] = (d * xi[0] - (br * xi[CH - 1] + bi * xr[CH - 1])) / det;
+            zr[CH - 1] = (a * xr[CH - 1] - (br * xr[0] + bi * xi[0])) / det;       // a X_1 - conj(b) X_0
+            zi[CH - 1] = (a * xi[CH - 1] - (br * xi[0] - bi * xr[0])) / det;
+        }
+#pragma unroll
+        for (int s = 0; s < WUN_PF_MAX_SOURCES; ++s)
+            if (s < S) {
+                if constexpr (CH == 1) {
+                    const double g = v[s] * Rt[(long long)s * Q * K];
+                    yr[s][0] = (float)(g * zr[0]); yi[s][0] = (float)(g * zi[0]);
+                } else {
+                    const double r00 = Rt[((long long)s * Q + 0) * K], r11 = Rt[((long long)s * Q + 1) * K];
+                    const double r01r = Rt[((long long)s * Q + 2) * K], r01i = Rt[((long long)s * Q + 3) * K];
+                    // R z: [r00 z_0 + r01 z_1; conj(r01) z_0 + r11 z_1]
+                    const double g0r = r00 * zr[0] + (r01r * zr[CH - 1] - r01i * zi[CH - 1]);
+                    const double g0i = r00 * zi[0] + (r01r * zi[CH - 1] + r01i * zr[CH - 1]);
+                    const double g1r = (r01r * zr[0] + r01i * zi[0]) + r11 * zr[CH - 1];
+                    const double g1i = (r01r * zi[0] - r01i * zr[0]) + r11 * zi[CH - 1];
+                    yr[s][0] = (float)(v[s] * g0r); yi[s][0] = (float)(v[s] * g0i);
+                    yr[s][CH - 1] = (float)(v[s] * g1r); yi[s][CH - 1] = (float)(v[s] * g1i);
+                }
+            }
+    }
+#pragma unroll
+    for (int s = 0; s < WUN_PF_MAX_SOURCES; ++s)
+        if (s < S)
+#pragma unroll
+            for (int c = 0; c < CH; ++c) { yre[(s * CH + c) * NK + e] = yr[s][c]; yim[(s * CH + c) * NK + e] = yi[s][c]; }
+}
+
 }  // namespace wun
 
 namespace {
@@ -377,6 +533,14 @@ double* wsq_of(float* scratch, long long floats) {
 void launch_window(double* wsq, int32_t n_fft, hipStream_t s) {
     hipLaunchKernelGGL(window_sq_kernel, dim3((unsigned)((n_fft + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), dim3(WUN_PF_BLOCK), 0, s, wsq,
                        n_fft);
+}
+
+// mask_s X over the estimates' spectra of one block: E = C nb K bins per source
+void launch_mask(const float* xre, const float* xim, float* ere, float* eim, long long E, int32_t S, int32_t power, float eps,
+                 hipStream_t s) {
+    const dim3 grid((unsigned)((E + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), blk(WUN_PF_BLOCK);
+    if (power == 2) hipLaunchKernelGGL(mask_kernel<2>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
+    else hipLaunchKernelGGL(mask_kernel<1>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
 }
 
 int check_filter(const char* who, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
@@ -483,10 +647,104 @@ extern "C" int wun_mask_filter(const float* mix_tc, const float* ests, int32_t S
         const Blk b = block_of(f0, F, n, n_fft, hop, lead);
         if (b.t_lo >= b.t_hi) continue;
         launch_cfwd(ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s);
-        const long long E = (long long)C * b.nb * K;         // (a short last block packs its spectra: the source stride is E)
-        const dim3 grid((unsigned)((E + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), blk(WUN_PF_BLOCK);
-        if (power == 2) hipLaunchKernelGGL(mask_kernel<2>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
-        else hipLaunchKernelGGL(mask_kernel<1>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
+        // (a short last block packs its spectra: the source stride is C nb K)
+        launch_mask(xre, xim, ere, eim, (long long)C * b.nb * K, S, power, eps, s);
+        launch_gemm(ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s);
+        launch_ola(frames, wsq, out, S, n, C, F, b, n_fft, hop, lead, s);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
+    return WUN_OK;
+}
+
+namespace {
+
+// doubles of the EM statistics: R of every iteration, and the partial sums of one block
+long long wiener_doubles(int32_t S, int32_t C, int32_t n_fft, int32_t iterations) {
+    const long long SQK = (long long)S * (C * C + 1) * (n_fft / 2 + 1);
+    return iterations ? (iterations + WUN_PF_FRAMES / WUN_WF_CHUNK) * SQK : 0;
+}
+
+template <int CH>
+void launch_apply(const float* xre, const float* xim, float* yre, float* yim, const double* R, long long NK, int32_t S, int K,
+                  int niter, double sq, hipStream_t s) {
+    hipLaunchKernelGGL(wiener_apply_kernel<CH>, dim3((unsigned)((NK + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), dim3(WUN_PF_BLOCK), 0, s, xre,
+                       xim, yre, yim, R, NK, S, K, niter, sq);
+}
+
+template <int CH>
+void launch_stats(const float* yre, const float* yim, double* part, double* stat, int32_t S, int nf, int K, bool first, bool last,
+                  double eps, hipStream_t s) {
+    const int nch = (nf + WUN_WF_CHUNK - 1) / WUN_WF_CHUNK;
+    const long long lanes = (long long)S * nch * K;
+    hipLaunchKernelGGL(wiener_stats_kernel<CH>, dim3((unsigned)((lanes + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), dim3(WUN_PF_BLOCK), 0, s,
+                       yre, yim, part, S, nf, K);
+    hipLaunchKernelGGL(wiener_reduce_kernel<CH * CH + 1>, dim3((unsigned)((S * K + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)),
+                       dim3(WUN_PF_BLOCK), 0, s, part, stat, S, K, nch, first ? 1 : 0, last ? 1 : 0, eps);
+}
+
+}  // namespace
+
+extern "C" int64_t wun_wiener_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations) {
+    const char* who = "wun_wiener_filter_scratch_floats";
+    int rc;
+    if ((rc = check_filter(who, S, n, C, n_fft, hop))) return rc;
+    if (iterations < 0 || iterations > WUN_WF_MAX_ITERS) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations outside 0..4");
+    return wun_mask_filter_scratch_floats(S, n, C, n_fft, hop) + 2 * wiener_doubles(S, C, n_fft, iterations);
+}
+
+extern "C" int wun_wiener_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                                 int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev, float* out,
+                                 float* scratch, void* stream) {
+    const char* who = "wun_wiener_filter";
+    if (!mix_tc || !ests || !table_dev || !out || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    int rc;
+    if ((rc = check_filter(who, S, n, C, n_fft, hop))) return rc;
+    if (power != 1 && power != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": power must be 1 or 2");
+    if (!(mask_eps > 0.f) || !std::isfinite(mask_eps))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": mask_eps not positive or not finite");
+    const long long N = (long long)S * n * C;
+    if (overlaps(out, N, mix_tc, n * C) || overlaps(out, N, ests, N))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": out overlaps an input");
+    if (iterations < 0 || iterations > WUN_WF_MAX_ITERS) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations outside 0..4");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(WUN_ERR_INVALID, std::string(who) + ": eps not positive or not finite");
+
+    hipStream_t s = (hipStream_t)stream;
+    const int K = n_fft / 2 + 1, lead = n_fft - hop;
+    const long long F = centered_frames(n, n_fft, hop), nbmax = block_frames(F, n_fft, hop);
+    const long long Ee = (long long)S * C * nbmax * K, Ex = (long long)C * nbmax * K;
+    float* ere = scratch; float* eim = ere + Ee; float* xre = eim + Ee; float* xim = xre + Ex; float* frames = xim + Ex;
+    double* wsq = wsq_of(frames, (long long)S * C * nbmax * n_fft);
+    const long long SQK = (long long)S * (C * C + 1) * K;
+    double* R = wsq + n_fft;                                  // [iterations][S][Q][K]
+    double* part = R + iterations * SQK;                      // [WUN_PF_FRAMES / WUN_WF_CHUNK][S][Q][K]
+    const double eps_d = (double)eps, sq = std::sqrt(eps_d);
+    launch_window(wsq, n_fft, s);
+    // pass i < iterations: y^(i) of every frame, block by block (no overlap frames: each frame counts once), into the
+    // statistics of R^(i+1); a frame's y^(i) depends on that frame and the R's alone, so nothing track-long is kept
+    for (int it = 0; it < iterations; ++it)
+        for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
+            const long long f1 = f0 + WUN_PF_FRAMES < F ? f0 + WUN_PF_FRAMES : F, nb = f1 - f0;
+            launch_cfwd(ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, nb, f0, nb, 0, s);
+            launch_mask(xre, xim, ere, eim, (long long)C * nb * K, S, power, mask_eps, s);
+            if (C == 2) {
+                if (it) launch_apply<2>(xre, xim, ere, eim, R, nb * K, S, K, it, sq, s);
+                launch_stats<2>(ere, eim, part, R + it * SQK, S, (int)nb, K, f0 == 0, f1 == F, eps_d, s);
+            } else {
+                if (it) launch_apply<1>(xre, xim, ere, eim, R, nb * K, S, K, it, sq, s);
+                launch_stats<1>(ere, eim, part, R + it * SQK, S, (int)nb, K, f0 == 0, f1 == F, eps_d, s);
+            }
+        }
+    // the last pass is wun_mask_filter's loop with all the filters applied between the mask and the inverse
+    for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
+        const Blk b = block_of(f0, F, n, n_fft, hop, lead);
+        if (b.t_lo >= b.t_hi) continue;
+        launch_cfwd(ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s);
+        launch_mask(xre, xim, ere, eim, (long long)C * b.nb * K, S, power, mask_eps, s);
+        if (iterations) {
+            if (C == 2) launch_apply<2>(xre, xim, ere, eim, R, b.nb * K, S, K, iterations, sq, s);
+            else launch_apply<1>(xre, xim, ere, eim, R, b.nb * K, S, K, iterations, sq, s);
+        }
         launch_gemm(ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s);
         launch_ola(frames, wsq, out, S, n, C, F, b, n_fft, hop, lead, s);
     }

@@ -137,13 +137,14 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     return_device=True: no download -- the float32 tensor [S, n_frames, channels] on the separator's device, sources in
     source_names order (what evaluate_track scores where it lies).
 
-    postfilter (a postfilter.SoftMaskFilter, or the spec its from_config takes; default None: no filter, today's path):
-    the soft-mask filter, applied at the model's rate to the estimates and the resampled mix before the resampling back
-    -- the estimates then share the mix's phase and sum to it."""
+    postfilter (a postfilter.SoftMaskFilter or WienerFilter, or the spec postfilter.from_config takes; default None: no
+    filter, today's path): the soft-mask filter, or with {"kind": "wiener", ...} the multichannel Wiener filter, applied at
+    the model's rate to the estimates and the resampled mix before the resampling back -- the estimates then share the
+    mix's phase and sum to it."""
     from . import resample as rs
     if postfilter is not None:
-        from .postfilter import SoftMaskFilter
-        postfilter = SoftMaskFilter.from_config(postfilter)
+        from .postfilter import from_config
+        postfilter = from_config(postfilter)
     device = torch.device(getattr(separator, "device", None) or "cpu")
     x = mix_audio if torch.is_tensor(mix_audio) else torch.from_numpy(np.ascontiguousarray(np.asarray(mix_audio, dtype=np.float32)))
     assert x.dim() == 2                                                          # Evaluate.py:97

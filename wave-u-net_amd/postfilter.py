@@ -1,14 +1,20 @@
-"""The soft-mask post-filter of libwun.so (include/wun.h: wun_mask_filter): the estimates of a track are
-masked against the mixture's own STFT, so they share the mixture's phase and sum back to the mixture.
+"""The post-filters of libwun.so (include/wun.h: wun_mask_filter, wun_wiener_filter): the estimates of
+a track are masked against the mixture's own STFT, so they share the mixture's phase and sum back to the mixture.
 
     f = SoftMaskFilter(n_fft=2048, hop=512, power=2, eps=1e-10)
     out = f.apply(mix, estimates)                      # mix [n, C], estimates [S, n, C] -> [S, n, C]
     evaluate.separate_track(cfg, sep, audio, sr, postfilter=f)      # or model_config["postfilter"] = {"n_fft": 2048, ...}
+    w = WienerFilter(n_fft=2048, hop=512, iterations=1)             # or postfilter={"kind": "wiener", "iterations": 1}
 
 Per channel, in the centred framing (frame f starts at f hop - (n_fft - hop), zeros outside the track):
 X = STFT(mix), E_s = STFT(est_s), A_s = |E_s|^power, mask_s = (A_s + eps / S) / (sum_j A_j + eps), out_s = ISTFT(mask_s X).
 Tensors on the GPU go through wun_mask_filter (no host sync; scratch cached per shape, tables shared with spectral.py); CPU
 tensors through a plain torch float32 implementation of the same definition (numpy stand-in separators, host tests).
+
+WienerFilter starts from those masked spectra y_s and runs `iterations` EM steps of a local Gaussian model over the C channels
+together (the header's definition): v_s = mean_c |y_s|^2, R_s[k] = sum_f y_s y_s^H / (em_eps + sum_f v_s) over the whole track,
+Cxx = sum_s v_s R_s + sqrt(em_eps) I, y_s <- v_s R_s Cxx^-1 X, in float64 with the spectra kept in float32.  There is no global
+rescaling of the mix (norbert's max_abs): the float64 algebra does not need it.  iterations = 0 is the soft mask, bit for bit.
 """
 import ctypes as C
 
@@ -18,6 +24,7 @@ import torch
 from . import _lib, spectral
 
 MAX_SOURCES = 8
+MAX_ITERATIONS = 4
 _KEYS = ("n_fft", "hop", "power", "eps")
 
 
@@ -130,7 +137,8 @@ class SoftMaskFilter(object):
         mask = (a + eps / torch.tensor(float(S), dtype=torch.float32)) / den
         ck = torch.full((n_fft // 2 + 1,), 2.0 / n_fft, dtype=torch.float32)
         ck[0] = ck[-1] = 1.0 / n_fft
-        frames = (mask * xre * ck) @ cb.t() + (mask * xim * ck) @ sb.t()         # [S, C, F, n_fft]
+        yre, yim = self._refine_cpu(mask * xre, mask * xim, xre, xim)
+        frames = (yre * ck) @ cb.t() + (yim * ck) @ sb.t()                       # [S, C, F, n_fft]
         y = torch.zeros((S, Cn, total), dtype=torch.float32)
         w = 0.5 - 0.5 * torch.cos(2.0 * np.pi * torch.arange(n_fft, dtype=torch.float64) / n_fft)
         ws = torch.zeros(total, dtype=torch.float64)
@@ -140,3 +148,99 @@ class SoftMaskFilter(object):
         live = ws >= 1e-8
         y = torch.where(live, y / torch.where(live, ws, torch.ones_like(ws)).to(torch.float32), torch.zeros_like(y))
         return y[..., lead:lead + n].transpose(-1, -2).contiguous()
+
+    def _refine_cpu(self, yre, yim, xre, xim):
+        """What lies between the mask and the inverse: nothing here."""
+        return yre, yim
+
+
+class WienerFilter(SoftMaskFilter):
+    """The multichannel Wiener filter (wun_wiener_filter): SoftMaskFilter's settings, `iterations` in 0..4 EM steps and their
+    regulariser `em_eps` (finite and positive in float32)."""
+    _KEYS = _KEYS + ("iterations", "em_eps")
+
+    def __init__(self, n_fft=2048, hop=512, power=2, eps=1e-10, iterations=1, em_eps=1e-10):
+        SoftMaskFilter.__init__(self, n_fft, hop, power, eps)
+        if isinstance(iterations, bool) or int(iterations) != iterations:
+            raise ValueError("iterations must be an integer, got %r" % (iterations,))
+        self.iterations, self.em_eps = int(iterations), float(em_eps)
+        if not 0 <= self.iterations <= MAX_ITERATIONS:
+            raise ValueError("iterations must lie in 0..%d, got %d" % (MAX_ITERATIONS, self.iterations))
+        if not (self.em_eps > 0.0 and np.isfinite(self.em_eps) and np.float32(self.em_eps) > 0 and np.isfinite(np.float32(self.em_eps))):
+            raise ValueError("em_eps must be finite and positive in float32, got %r" % (em_eps,))
+
+    @classmethod
+    def from_config(cls, spec):
+        """None, a WienerFilter, True (the defaults) or a dict with any of `n_fft`, `hop`, `power`, `eps`, `iterations`,
+        `em_eps`."""
+        if spec is None or isinstance(spec, cls):
+            return spec
+        if spec is True:
+            return cls()
+        if not isinstance(spec, dict):
+            raise ValueError("postfilter must be None, True or a dict with %s, got %r" % (", ".join(cls._KEYS), spec))
+        unknown = set(spec) - set(cls._KEYS)
+        if unknown:
+            raise ValueError("postfilter: unknown keys %s" % sorted(unknown))
+        return cls(**spec)
+
+    def spec(self):
+        return dict(SoftMaskFilter.spec(self), kind="wiener", iterations=self.iterations, em_eps=self.em_eps)
+
+    def scratch_floats(self, S, n, Cn):
+        k = int(_lib.load().wun_wiener_filter_scratch_floats(int(S), int(n), int(Cn), self.n_fft, self.hop, self.iterations))
+        if k < 0:
+            _lib.check(k)
+        return k
+
+    def run(self, mix, estimates, out, scratch):
+        """wun_wiener_filter on the caller's buffers (contiguous float32 device tensors)."""
+        S, n, Cn = (int(v) for v in estimates.shape)
+        dev = estimates.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wun_wiener_filter(
+                mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps, self.iterations,
+                self.em_eps, spectral._table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def _refine_cpu(self, yre, yim, xre, xim):
+        """The EM steps in float64 on float32 spectra: y [S, C, F, K], X [C, F, K]; closed forms for C = 1 and 2."""
+        S, Cn = int(yre.shape[0]), int(yre.shape[1])
+        eps = float(np.float32(self.em_eps))
+        sq = float(np.sqrt(eps))
+        x = torch.complex(xre.double(), xim.double())
+        y = torch.complex(yre.double(), yim.double())
+        for _ in range(self.iterations):
+            p = y.real * y.real + y.imag * y.imag                                # [S, C, F, K]
+            v = p[:, 0] if Cn == 1 else 0.5 * (p[:, 0] + p[:, 1])                # [S, F, K]
+            den = (eps + v.sum(1))[:, None, :]                                   # [S, 1, K]
+            r00 = p[:, 0].sum(1, keepdim=True) / den
+            if Cn == 1:
+                g = v * r00
+                y = (g / (g.sum(0) + sq))[:, None] * x
+            else:
+                r11 = p[:, 1].sum(1, keepdim=True) / den
+                r01 = (y[:, 0] * y[:, 1].conj()).sum(1, keepdim=True) / den
+                a, d, b = (v * r00).sum(0) + sq, (v * r11).sum(0) + sq, (v * r01).sum(0)
+                det = a * d - (b.real * b.real + b.imag * b.imag)
+                z0, z1 = (d * x[0] - b * x[1]) / det, (a * x[1] - b.conj() * x[0]) / det
+                y = torch.stack([v * (r00 * z0 + r01 * z1), v * (r01.conj() * z0 + r11 * z1)], 1)
+            y = y.to(torch.complex64).to(torch.complex128)                       # spectra are stored as float32
+        return y.real.to(torch.float32), y.imag.to(torch.float32)
+
+
+KINDS = {"softmask": SoftMaskFilter, "wiener": WienerFilter}
+
+
+def from_config(spec):
+    """model_config["postfilter"] / the postfilter= option: None or an instance of either class passes through; True is the
+    soft mask's defaults; a dict goes to the class its `kind` names ("softmask", the default, or "wiener") without that key."""
+    if spec is None or isinstance(spec, SoftMaskFilter):
+        return spec
+    if not isinstance(spec, dict):
+        return SoftMaskFilter.from_config(spec)
+    spec = dict(spec)
+    kind = spec.pop("kind", "softmask")
+    if not isinstance(kind, str) or kind not in KINDS:
+        raise ValueError("postfilter: kind must be one of %s, got %r" % (", ".join(sorted(KINDS)), kind))
+    return KINDS[kind].from_config(spec)
