@@ -569,6 +569,59 @@ int     wun_wiener_filter(const float* mix_tc, const float* ests, int32_t S, int
                           int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev,
                           float* out, float* scratch, void* stream);
 
+/* ---- the FFT path of the complex STFT, its inverse and the post-filters ----
+ * The three sections above run every frame transform as a GEMM against a [2][n_fft][K] table: n_fft^2 + n_fft floats and
+ * about 2 n_fft^2 flops per frame, which is why they stop at n_fft = 2048.  The entries below compute the SAME definitions --
+ * framing, periodic Hann window, Re / Im layout [R][F][K], inverse, overlap-add, mask, EM -- with a fast Fourier transform,
+ * for n_fft a power of two in 64..8192.  Only the summation order inside a frame transform differs, so the results agree with
+ * the GEMM entries to float32 rounding, not bit for bit.
+ *   table      : fp32 [3][n_fft], element (plane, t) at plane * n_fft + t:
+ *                plane 0 = cos(2 pi t / n_fft), plane 1 = -sin(2 pi t / n_fft), plane 2 = w[t] = 0.5 - 0.5 cos(2 pi t / n_fft).
+ *                Designed on the host in float64 -- t reduced in integers to a quarter turn, the quadrant applied exactly, so
+ *                the entries at the multiples of pi / 2 are exactly 0 and +-1 -- and rounded once to fp32.  3 n_fft floats.
+ *   forward    : y[n] = w[n] frame_f[n] (one fp32 product);  z[m] = y[2m] + i y[2m+1], Z = DFT of n_fft / 2 points (Stockham
+ *                radix 4, one radix-2 stage last for an odd log2), then with M = n_fft / 2, for k = 0..M:
+ *                E = (Z[k] + conj Z[M-k]) / 2,  O = (Z[k] - conj Z[M-k]) / 2i,  Re + i Im = E + exp(-2 pi i k / n_fft) O
+ *                (Z[M] = Z[0]).  Im of the bins 0 and n_fft / 2 is written as exactly 0.
+ *   inverse    : frame_f[n] = w[n] (1 / n_fft) sum_k c_k (Re[f][k] cos(2 pi n k / n_fft) - Im[f][k] sin(2 pi n k / n_fft)), c_k as
+ *                above: w times the inverse real transform.  Im of the bins 0 and n_fft / 2 is not read (the GEMM definition
+ *                multiplies it by Sb = 0).  The scale 1 / n_fft, a power of two, is applied once, then the window.  The
+ *                overlap-add, the window-square sums and the 1e-8 rule are the inverse section's, by the same kernel.
+ * A frame's floats depend on that frame's samples (or bins) and the table alone: not on the block, the grid, the frames that
+ * share its workgroup, what `scratch` held or pointer alignment beyond 4 bytes.  No atomics; nothing allocates or
+ * synchronises; every argument check runs before any GPU work.  Both compute modes.
+ * Every entry takes the arguments of the entry it is named after, with table_dev = a device copy of THIS section's table,
+ * and has its contract, scratch formula, checks and check order: null pointers, the audio shape, then WUN_ERR_UNSUPPORTED for
+ * an n_fft that is no power of two in 64..8192, then the hop, lead and F (the filters: hop a power of two of at most
+ * n_fft / 2, S <= 8, C in {1, 2}, power, eps, iterations).
+ * The Wiener filter above 2048: see DESIGN.md 5.13 for why the float64 algebra needs no rescaling of the mix up to 8192. */
+
+/* Floats of the table (3 n_fft), and the table itself into table_host[cap] (host).  WUN_ERR_UNSUPPORTED for an n_fft outside
+ * the list; WUN_ERR_INVALID for a null pointer or cap < wun_fft_table_floats. */
+int64_t wun_fft_table_floats(int32_t n_fft);
+int     wun_fft_design(int32_t n_fft, float* table_host, int64_t cap);
+/* wun_stft_frames (the framing without padding: 1 + (T - n_fft) / hop, WUN_ERR_INVALID for T < n_fft after the n_fft and hop
+ * checks) and wun_stft_centered_frames for this section's n_fft list. */
+int64_t wun_fft_frames(int64_t T, int32_t n_fft, int32_t hop);
+int64_t wun_fft_centered_frames(int64_t T, int32_t n_fft, int32_t hop);
+/* wun_stft_complex: one launch. */
+int     wun_stft_complex_fft(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                             int32_t lead, int64_t F, const float* table_dev, float* re, float* im, void* stream);
+/* wun_istft_scratch_floats / wun_istft. */
+int64_t wun_istft_fft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
+                                     int64_t F);
+int     wun_istft_fft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                      int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream);
+/* wun_mask_filter_scratch_floats / wun_mask_filter. */
+int64_t wun_mask_filter_fft_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop);
+int     wun_mask_filter_fft(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                            int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream);
+/* wun_wiener_filter_scratch_floats / wun_wiener_filter.  iterations = 0 is wun_mask_filter_fft, bit for bit. */
+int64_t wun_wiener_filter_fft_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations);
+int     wun_wiener_filter_fft(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                              int32_t hop, int32_t power, float mask_eps, int32_t iterations, float eps,
+                              const float* table_dev, float* out, float* scratch, void* stream);
+
 /* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
  * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
  * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is

@@ -18,6 +18,8 @@ train|valid|test/<track>/<source>.wav|.npy (+ optional mix.wav) at expected_sr, 
 masks the estimates against the mix's STFT before they are written / scored (postfilter.SoftMaskFilter);
 `postfilter={"kind":"wiener","iterations":1,"em_eps":1e-10}` (with any of the keys above) is the multichannel Wiener filter instead
 (postfilter.WienerFilter: EM iterations over the channels together; "kind":"softmask" is the default).
+`"transform":"fft"` in either spec computes the transforms with an FFT and lifts n_fft's limit from 2048 to 8192
+(`postfilter={"n_fft":4096,"hop":1024,"transform":"fft"}`).
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
 1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
 source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.

@@ -96,6 +96,22 @@ _SIGS = {
     "wun_wiener_filter_scratch_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "wun_wiener_filter": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                     C.c_int32, C.c_float, _P, _P, _P, _P]),
+    "wun_fft_table_floats": (C.c_int64, [C.c_int32]),
+    "wun_fft_design": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.c_int64]),
+    "wun_fft_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_fft_centered_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_stft_complex_fft": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                       _P, _P, _P, _P]),
+    "wun_istft_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_int64]),
+    "wun_istft_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                _P, _P, _P, _P]),
+    "wun_mask_filter_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "wun_mask_filter_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                      _P, _P, _P, _P]),
+    "wun_wiener_filter_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "wun_wiener_filter_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                        C.c_int32, C.c_float, _P, _P, _P, _P]),
     "wun_separate_positions": (C.c_int64, [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64]),
     "wun_forward_windows": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, _P, _P, C.c_int, _P]),
     "wun_scatter_windows": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, _P, C.c_int64, _P]),

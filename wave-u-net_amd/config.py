@@ -44,6 +44,7 @@ EXTENSION_DEFAULTS = {
     # evaluate.separate_track / postfilter.SoftMaskFilter: None = the estimates as the network gives them; else
     # {"n_fft": 2048, "hop": 512, "power": 2, "eps": 1e-10} (any subset): the soft-mask filter against the mix's STFT; with
     # "kind": "wiener" (and "iterations": 1, "em_eps": 1e-10) postfilter.WienerFilter, the multichannel Wiener filter
+    # "transform": "fft" computes the transforms with an FFT: n_fft up to 8192 instead of 2048
     "postfilter": None,
 }
 

@@ -1,0 +1,36 @@
+// What wun_postfilter.hip (the host orchestration of the transforms and filters) and wun_fft.hip (the FFT kernels) share: the
+// argument blocks of a forward and an inverse frame transform, and the launchers of the FFT path.  Both transforms of one
+// direction take the same block, so the orchestration picks one by a selector and nothing else changes.
+#pragma once
+#include "wun_device.h"
+
+namespace wun {
+
+enum { WUN_TR_GEMM = 0, WUN_TR_FFT = 1 };
+
+// Frame rows of one launch: m = r * nb + fl is frame f0 + fl of row r; its spectrum lies at row r * fstride + foff + fl of
+// re / im [.][K] (a whole transform: nb = fstride = F, f0 = foff = 0; a block of the filter: fstride = nb, foff = 0).
+struct StftCfwdArgs {
+    const float* x[2];               // [SB, T, C]; blockIdx.z picks one (the estimates, the mix)
+    float* re[2]; float* im[2];
+    long long M[2];                  // frame rows of the signal: rows * nb
+    const float* table;              // GEMM: Cb [n_fft][K], then Sb [n_fft][K];  FFT: wun_fft_design's table
+    long long T, nb, f0, fstride, foff;
+    int C, n_fft, hop, lead, K;
+};
+
+struct IstftGemmArgs {
+    const float* re; const float* im;        // the spectrum of frame row m = r * nb + fl at row r * fstride + foff + fl
+    const float* table;
+    float* frames;                           // [M][n_fft]
+    long long M, nb, fstride, foff;
+    int n_fft, K;
+    float c_edge, c_mid;                     // 1 / n_fft for k = 0 and k = n_fft / 2, 2 / n_fft between
+};
+
+// wun_fft.hip: stft_fft_kernel / istft_fft_kernel of a.n_fft (a power of two in 64..8192) on stream s.  WUN_OK, or
+// WUN_ERR_UNSUPPORTED (wun_last_error() set, nothing launched) for an n_fft without a kernel.
+int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s);
+int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s);
+
+}  // namespace wun

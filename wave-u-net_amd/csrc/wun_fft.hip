@@ -1,0 +1,284 @@
+// gfx950 (MI355X / CDNA4): the FFT path of the complex STFT and its inverse (include/wun.h: wun_fft_design, wun_stft_complex_fft,
+// wun_istft_fft and the *_fft filters).  Same definitions and layouts as stft_cfwd_kernel / istft_gemm_kernel of
+// wun_postfilter.hip, whose host code launches these through wun_fft.h; O(n log n) per frame instead of O(n^2).
+//
+//   real transform   a frame of n_fft real samples is one complex FFT of M = n_fft / 2 points, z[m] = y[2m] + i y[2m+1], and a
+//                    split step:  E = (Z[k] + conj Z[M-k]) / 2,  O = (Z[k] - conj Z[M-k]) / 2i,  X[k] = E + W_N^k O,  k = 0..M
+//   complex FFT      Stockham autosort, radix 4 with one radix-2 stage last when log2 M is odd.  Stage Ns (1, 4, 16, ..):
+//                    butterfly j reads in[j + r M/4], multiplies by W^(r (j mod Ns) M / 4Ns), r = 1..3, and writes
+//                    out[(j / Ns) 4 Ns + (j mod Ns) + p Ns].  The radix points live in registers, the stages ping-pong between
+//                    two LDS images: one barrier per stage.  The first stage takes its points straight from global memory.
+//   inverse          Z'[k] = (X[k] + conj X[M-k]) + i conj(W_N^k) (X[k] - conj X[M-k]) (twice the Z of the forward), the
+//                    same FFT on Z' with Re and Im swapped (that is the inverse transform with Re and Im swapped), then
+//                    frame[2m], frame[2m+1] = Im, Re of the result, times 1 / n_fft (a power of two) and the window.
+//   LDS              Re and Im planes of floats (ds_read_b32 / ds_write_b32: 32 banks, lane groups of 32).  Float a of a plane
+//                    lies at a ^ f(a >> 5), f(b) = 5 (b & 3) ^ ((b & 2) << 3): a permutation inside each aligned run of 32
+//                    floats, so the stride-1 stage reads stay conflict-free, and the scattered stage writes (stride 4 at
+//                    Ns = 1, runs of 4 at stride 16 at Ns = 4, runs of 16 at stride 64 at Ns = 16) land on 32 different banks.
+//                    No padding: 8192 points take 2 x 2 x 4096 floats = 64 KB.  (DESIGN.md 5.13 has the conflict degrees.)
+//   mapping          min(256, M / 4) lanes per frame: 32 .. 2 frames per 256-lane workgroup at n_fft 64 .. 1024, one frame
+//                    (1 .. 4 butterflies per lane and stage) above.  A frame's lanes and LDS region are its own and the
+//                    instruction sequence is one: its bits do not depend on the frames beside it, the grid or alignment.
+//
+// Twiddles and the window come from the host's table (float64, rounded once); no sincosf, no recurrence, no atomics.
+// Built WITHOUT the packed fp32 VALU instructions, as wun_postfilter.hip (csrc/Makefile NO_PK_FP32).
+#include "wun_fft.h"
+#include "../../include/wun.h"
+
+#include <cmath>
+#include <string>
+
+using namespace wun;
+int fail(int code, const std::string& msg);      // wun_plan.hip
+
+#define WUN_FFT_BLOCK 256
+
+namespace wun {
+
+template <int LOGM>
+struct FftGeom {
+    static constexpr int M = 1 << LOGM, N = 2 * M;
+    static constexpr int TPF = M / 4 < WUN_FFT_BLOCK ? M / 4 : WUN_FFT_BLOCK;      // lanes per frame
+    static constexpr int FPW = WUN_FFT_BLOCK / TPF;                                 // frames per workgroup
+    static constexpr int BPT = M / 4 / TPF;                                         // radix-4 butterflies per lane and stage
+    static constexpr int PLANE = FPW * M;                                           // floats of one LDS plane
+    static constexpr int STAGES = (LOGM + 1) / 2;
+    static constexpr int RESULT = (STAGES - 1) & 1;                                 // the image the last stage writes
+};
+
+__device__ __forceinline__ int fft_swz(int a) {
+    const int b = a >> 5;
+    return a ^ (((b & 3) * 5) ^ ((b & 2) << 3));
+}
+
+// The M-point FFT of one frame: `load(a, re, im)` gives point a (the first stage reads nothing else); the result lies in image
+// FftGeom::RESULT at fft_swz(base + k), natural order, behind a barrier.  tw: cos(2 pi t / N) at [t], -sin at [N + t].
+template <int LOGM, class Load>
+__device__ __forceinline__ void fft_run(Load load, float (*sre)[FftGeom<LOGM>::PLANE], float (*sim)[FftGeom<LOGM>::PLANE], int base,
+                                        int tl, const float* __restrict__ tw) {
+    using G = FftGeom<LOGM>;
+    constexpr int M = G::M, N = G::N, TPF = G::TPF;
+#pragma unroll
+    for (int s = 0; s < LOGM / 2; ++s) {
+        const int Ns = 1 << (2 * s);
+        const float* __restrict__ ir = sre[(s & 1) ^ 1];
+        const float* __restrict__ ii = sim[(s & 1) ^ 1];
+        float* __restrict__ outr = sre[s & 1];
+        float* __restrict__ outi = sim[s & 1];
+#pragma unroll
+        for (int i = 0; i < G::BPT; ++i) {
+            const int j = tl + i * TPF, k = j & (Ns - 1);
+            float vr[4], vi[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int a = j + r * (M / 4);
+                if (s == 0) load(a, vr[r], vi[r]);
+                else { vr[r] = ir[fft_swz(base + a)]; vi[r] = ii[fft_swz(base + a)]; }
+            }
+            if (s > 0) {
+#pragma unroll
+                for (int r = 1; r < 4; ++r) {
+                    const int t = 2 * r * k * (M / (4 * Ns));                // W_M^(..) in the table of W_N
+                    const float c = tw[t], sn = tw[N + t];
+                    const float xr = vr[r] * c - vi[r] * sn, xi = vr[r] * sn + vi[r] * c;
+                    vr[r] = xr; vi[r] = xi;
+                }
+            }
+            const float a0r = vr[0] + vr[2], a0i = vi[0] + vi[2], a1r = vr[0] - vr[2], a1i = vi[0] - vi[2];
+            const float a2r = vr[1] + vr[3], a2i = vi[1] + vi[3];
+            const float a3r = vi[1] - vi[3], a3i = vr[3] - vr[1];            // -i (v1 - v3)
+            const int j0 = ((j - k) << 2) + k + base;
+            outr[fft_swz(j0)] = a0r + a2r;           outi[fft_swz(j0)] = a0i + a2i;
+            outr[fft_swz(j0 + Ns)] = a1r + a3r;      outi[fft_swz(j0 + Ns)] = a1i + a3i;
+            outr[fft_swz(j0 + 2 * Ns)] = a0r - a2r;  outi[fft_swz(j0 + 2 * Ns)] = a0i - a2i;
+            outr[fft_swz(j0 + 3 * Ns)] = a1r - a3r;  outi[fft_swz(j0 + 3 * Ns)] = a1i - a3i;
+        }
+        __syncthreads();
+    }
+    if (LOGM & 1) {                                                          // the radix-2 stage, Ns = M / 2
+        constexpr int s = LOGM / 2;
+        const float* __restrict__ ir = sre[(s & 1) ^ 1];
+        const float* __restrict__ ii = sim[(s & 1) ^ 1];
+        float* __restrict__ outr = sre[s & 1];
+        float* __restrict__ outi = sim[s & 1];
+#pragma unroll
+        for (int i = 0; i < 2 * G::BPT; ++i) {
+            const int j = tl + i * TPF;
+            const float ar = ir[fft_swz(base + j)], ai = ii[fft_swz(base + j)];
+            const float br = ir[fft_swz(base + j + M / 2)], bi = ii[fft_swz(base + j + M / 2)];
+            const float c = tw[2 * j], sn = tw[N + 2 * j];
+            const float xr = br * c - bi * sn, xi = br * sn + bi * c;
+            outr[fft_swz(base + j)] = ar + xr;          outi[fft_swz(base + j)] = ai + xi;
+            outr[fft_swz(base + j + M / 2)] = ar - xr;  outi[fft_swz(base + j + M / 2)] = ai - xi;
+        }
+        __syncthreads();
+    }
+}
+
+// grid: x = group of FPW frame rows, z = signal.  Frame row m of StftCfwdArgs, as stft_cfwd_kernel.
+template <int LOGM>
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void stft_fft_kernel(StftCfwdArgs p) {
+    using G = FftGeom<LOGM>;
+    constexpr int M = G::M, N = G::N, TPF = G::TPF;
+    __shared__ float sre[2][G::PLANE];
+    __shared__ float sim[2][G::PLANE];
+    const int z = blockIdx.z;
+    const long long Mrows = p.M[z];
+    const long long m0 = (long long)blockIdx.x * G::FPW;
+    if (m0 >= Mrows) return;                                 // (the grid is sized by the larger signal; uniform)
+    const int g = threadIdx.x / TPF, tl = threadIdx.x - g * TPF, base = g * M;
+    const long long m = m0 + g;
+    const bool valid = m < Mrows;                            // a frame slot behind the last row runs on zeros, stores nothing
+    long long rbase = 0, t0 = 0, o = 0;
+    if (valid) {
+        const long long r = m / p.nb, fl = m - r * p.nb;
+        const long long sb = r / p.C, c = r - sb * p.C;
+        rbase = sb * p.T * p.C + c;
+        t0 = (p.f0 + fl) * p.hop - p.lead;
+        o = (r * p.fstride + p.foff + fl) * p.K;
+    }
+    const float* __restrict__ x = p.x[z];
+    const float* __restrict__ tw = p.table;
+    const float* __restrict__ win = p.table + 2 * N;
+    const long long T = p.T;
+    const int C = p.C;
+    fft_run<LOGM>([&](int a, float& re, float& im) {
+        const long long t = t0 + 2 * a;
+        re = (valid && t >= 0 && t < T) ? x[rbase + t * C] * win[2 * a] : 0.f;
+        im = (valid && t + 1 >= 0 && t + 1 < T) ? x[rbase + (t + 1) * C] * win[2 * a + 1] : 0.f;
+    }, sre, sim, base, tl, tw);
+    if (!valid) return;                                      // (no barrier follows)
+    const float* __restrict__ Zr = sre[G::RESULT];
+    const float* __restrict__ Zi = sim[G::RESULT];
+    float* __restrict__ re = p.re[z] + o;
+    float* __restrict__ im = p.im[z] + o;
+#pragma unroll
+    for (int i = 0; i <= M / TPF; ++i) {
+        const int k = tl + i * TPF;                          // 0 .. M: the last round is lane 0's k = M
+        if (k > M) break;
+        const int ka = base + (k & (M - 1)), kb = base + ((M - k) & (M - 1));
+        const float ar = Zr[fft_swz(ka)], ai = Zi[fft_swz(ka)], cr = Zr[fft_swz(kb)], ci = Zi[fft_swz(kb)];
+        const float er = 0.5f * (ar + cr), ei = 0.5f * (ai - ci), odr = 0.5f * (ai + ci), odi = 0.5f * (cr - ar);
+        const float wc = tw[k], ws = tw[N + k];
+        re[k] = er + (wc * odr - ws * odi);
+        im[k] = (k == 0 || k == M) ? 0.f : ei + (wc * odi + ws * odr);
+    }
+}
+
+// grid: x = group of FPW frame rows of IstftGemmArgs.  frames[m][n] = w[n] irfft(Re + i Im)[n]; Im of the bins 0 and M is
+// never read.
+template <int LOGM>
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void istft_fft_kernel(IstftGemmArgs p) {
+    using G = FftGeom<LOGM>;
+    constexpr int M = G::M, N = G::N, TPF = G::TPF;
+    __shared__ float sre[2][G::PLANE];
+    __shared__ float sim[2][G::PLANE];
+    const int g = threadIdx.x / TPF, tl = threadIdx.x - g * TPF, base = g * M;
+    const long long m = (long long)blockIdx.x * G::FPW + g;
+    const bool valid = m < p.M;
+    long long srow = 0;
+    if (valid) {
+        const long long r = m / p.nb, fl = m - r * p.nb;
+        srow = (r * p.fstride + p.foff + fl) * p.K;
+    }
+    const float* __restrict__ xr = p.re + srow;
+    const float* __restrict__ xi = p.im + srow;
+    const float* __restrict__ tw = p.table;
+    const float* __restrict__ win = p.table + 2 * N;
+    fft_run<LOGM>([&](int k, float& re, float& im) {         // (Re, Im) = (Im Z', Re Z'): the swap that inverts
+        if (!valid) { re = 0.f; im = 0.f; return; }
+        if (k == 0) {
+            const float x0 = xr[0], xm = xr[M];
+            re = x0 - xm; im = x0 + xm;
+            return;
+        }
+        const float ar = xr[k], ai = xi[k], cr = xr[M - k], ci = xi[M - k];
+        const float dr = ar - cr, di = ai + ci;
+        const float wc = tw[k], ws = tw[N + k];
+        const float pr = wc * dr + ws * di, pi = wc * di - ws * dr;          // conj(W_N^k) (X[k] - conj X[M-k])
+        re = (ai - ci) + pr; im = (ar + cr) - pi;
+    }, sre, sim, base, tl, tw);
+    if (!valid) return;
+    const float* __restrict__ Yr = sre[G::RESULT];
+    const float* __restrict__ Yi = sim[G::RESULT];
+    float* __restrict__ fr = p.frames + m * N;
+    const float scale = p.c_edge;                            // 1 / n_fft
+#pragma unroll
+    for (int i = 0; i < M / TPF; ++i) {
+        const int mm = tl + i * TPF;
+        fr[2 * mm] = (Yi[fft_swz(base + mm)] * scale) * win[2 * mm];
+        fr[2 * mm + 1] = (Yr[fft_swz(base + mm)] * scale) * win[2 * mm + 1];
+    }
+}
+
+template <int LOGM>
+static void fwd_launch(const StftCfwdArgs& a, int signals, hipStream_t s) {
+    const long long M = a.M[0] > a.M[1] || signals < 2 ? a.M[0] : a.M[1];
+    const dim3 grid((unsigned)((M + FftGeom<LOGM>::FPW - 1) / FftGeom<LOGM>::FPW), 1u, (unsigned)signals);
+    hipLaunchKernelGGL(stft_fft_kernel<LOGM>, grid, dim3(WUN_FFT_BLOCK), 0, s, a);
+}
+
+template <int LOGM>
+static void inv_launch(const IstftGemmArgs& g, hipStream_t s) {
+    hipLaunchKernelGGL(istft_fft_kernel<LOGM>, dim3((unsigned)((g.M + FftGeom<LOGM>::FPW - 1) / FftGeom<LOGM>::FPW)),
+                       dim3(WUN_FFT_BLOCK), 0, s, g);
+}
+
+int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s) {
+    switch (a.n_fft) {
+        case 64: fwd_launch<5>(a, signals, s); break;
+        case 128: fwd_launch<6>(a, signals, s); break;
+        case 256: fwd_launch<7>(a, signals, s); break;
+        case 512: fwd_launch<8>(a, signals, s); break;
+        case 1024: fwd_launch<9>(a, signals, s); break;
+        case 2048: fwd_launch<10>(a, signals, s); break;
+        case 4096: fwd_launch<11>(a, signals, s); break;
+        case 8192: fwd_launch<12>(a, signals, s); break;
+        default: return fail(WUN_ERR_UNSUPPORTED, "fft_launch_forward: no kernel for this n_fft");
+    }
+    return WUN_OK;
+}
+
+int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s) {
+    switch (g.n_fft) {
+        case 64: inv_launch<5>(g, s); break;
+        case 128: inv_launch<6>(g, s); break;
+        case 256: inv_launch<7>(g, s); break;
+        case 512: inv_launch<8>(g, s); break;
+        case 1024: inv_launch<9>(g, s); break;
+        case 2048: inv_launch<10>(g, s); break;
+        case 4096: inv_launch<11>(g, s); break;
+        case 8192: inv_launch<12>(g, s); break;
+        default: return fail(WUN_ERR_UNSUPPORTED, "fft_launch_inverse: no kernel for this n_fft");
+    }
+    return WUN_OK;
+}
+
+}  // namespace wun
+
+extern "C" int64_t wun_fft_table_floats(int32_t n_fft) {
+    if (n_fft < 64 || n_fft > 8192 || (n_fft & (n_fft - 1)))
+        return fail(WUN_ERR_UNSUPPORTED, "wun_fft_table_floats: n_fft must be a power of two in 64..8192");
+    return 3 * (int64_t)n_fft;
+}
+
+extern "C" int wun_fft_design(int32_t n_fft, float* table_host, int64_t cap) {
+    const int64_t need = wun_fft_table_floats(n_fft);
+    if (need < 0) return (int)need;
+    if (!table_host) return fail(WUN_ERR_INVALID, "wun_fft_design: null table");
+    if (cap < need) return fail(WUN_ERR_INVALID, "wun_fft_design: cap below wun_fft_table_floats");
+    // the angle reduced in integers to [0, pi / 2): t = q n_fft / 4 + i, then the quadrant's rotation, which is exact -- so
+    // the entries at the multiples of pi / 2 are exactly 0 and +-1
+    const int Q = n_fft / 4;
+    const double step = 2.0 * 3.14159265358979323846 / (double)n_fft;
+    for (int t = 0; t < n_fft; ++t) {
+        const int q = t / Q, i = t - q * Q;
+        const double c0 = std::cos(step * i), s0 = i ? std::sin(step * i) : 0.0;
+        const double c = q == 0 ? c0 : q == 1 ? -s0 : q == 2 ? -c0 : s0;
+        const double sn = q == 0 ? s0 : q == 1 ? c0 : q == 2 ? -s0 : -c0;
+        table_host[t] = (float)c;
+        table_host[n_fft + t] = (float)(0.0 - sn);
+        table_host[2 * n_fft + t] = (float)(0.5 - 0.5 * c);              // periodic Hann
+    }
+    return WUN_OK;
+}

@@ -19,9 +19,13 @@
 // accumulation order per output), and every output sample belongs to exactly one block (that of its last covering frame):
 // the bits do not depend on the blocking, the grid, the scratch contents or pointer alignment.  No atomics.
 //
+// Every entry exists a second time with the frame transforms computed by an FFT (wun_*_fft): the bodies below
+// take a selector `tr`, which launch_cfwd / launch_gemm turn into the GEMM kernels here or the FFT kernels of wun_fft.hip;
+// blocks, mask, EM, overlap-add and scratch are the same code.
+//
 // Built WITHOUT the packed fp32 VALU instructions (csrc/Makefile NO_PK_FP32): the filter runs beside inference of
 // either compute mode.  Every argument check runs before any GPU work; nothing allocates or synchronises.
-#include "wun_device.h"
+#include "wun_fft.h"
 #include "../../include/wun.h"
 
 #include <cmath>
@@ -45,16 +49,7 @@ namespace wun {      // the kernels carry the library's wun:: prefix in profiler
 
 __device__ __forceinline__ f32x4 pf_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
-// Frame rows of one launch: m = r * nb + fl is frame f0 + fl of row r; its spectrum lies at row r * fstride + foff + fl of
-// re / im [.][K] (a whole transform: nb = fstride = F, f0 = foff = 0; a block of the filter: fstride = nb, foff = 0).
-struct StftCfwdArgs {
-    const float* x[2];               // [SB, T, C]; blockIdx.z picks one (the estimates, the mix)
-    float* re[2]; float* im[2];
-    long long M[2];                  // frame rows of the signal: rows * nb
-    const float* table;              // Cb [n_fft][K], then Sb [n_fft][K]
-    long long T, nb, f0, fstride, foff;
-    int C, n_fft, hop, lead, K;
-};
+// (StftCfwdArgs, the frame rows of one launch: wun_fft.h)
 
 // grid: x = tile of 64 frame rows, y = tile of 32 bins, z = signal.  stft_fwd_kernel with frames that may reach outside
 // [0, T): every gathered sample is bounds-checked.  Lane layout of the MFMA as there.
@@ -166,15 +161,6 @@ __global__ __launch_bounds__(WUN_PF_BLOCK) void mask_kernel(const float* __restr
             eim[s * E + e] = mask * xi;
         }
 }
-
-struct IstftGemmArgs {
-    const float* re; const float* im;        // the spectrum of frame row m = r * nb + fl at row r * fstride + foff + fl
-    const float* table;
-    float* frames;                           // [M][n_fft]
-    long long M, nb, fstride, foff;
-    int n_fft, K;
-    float c_edge, c_mid;                     // 1 / n_fft for k = 0 and k = n_fft / 2, 2 / n_fft between
-};
 
 // grid: x = tile of 64 frame rows, y = tile of 32 samples of the frame.  stft_bwd_kernel with the spectra scaled by
 // c_k / n_fft while staged: the reduction runs over the bins in ascending order, a bin's real part before its imaginary part;
@@ -448,9 +434,11 @@ int check_audio(const char* who, int32_t S, int32_t B, int64_t T, int32_t C) {
 }
 
 // the spectral section's order: n_fft (UNSUPPORTED), then hop (INVALID); a track shorter than a frame is legal here
-int check_res(const char* who, int32_t n_fft, int32_t hop) {
-    if (n_fft < 64 || n_fft > 2048 || (n_fft & (n_fft - 1)))
-        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": n_fft must be a power of two in 64..2048");
+// (tr: the GEMM's table grows as n_fft^2 / 2 and stops at 2048; the FFT path goes on to 8192)
+int check_res(const char* who, int tr, int32_t n_fft, int32_t hop) {
+    const int32_t n_max = tr == WUN_TR_FFT ? 8192 : 2048;
+    if (n_fft < 64 || n_fft > n_max || (n_fft & (n_fft - 1)))
+        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": n_fft must be a power of two in 64.." + (tr == WUN_TR_FFT ? "8192" : "2048"));
     if (hop < 1 || hop > n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": hop outside 1..n_fft");
     return WUN_OK;
 }
@@ -491,26 +479,31 @@ Blk block_of(long long f0, int64_t F, int64_t T, int32_t n_fft, int32_t hop, int
     return b;
 }
 
-void launch_cfwd(const float* x0, long long rows0, float* re0, float* im0, const float* x1, long long rows1, float* re1,
-                 float* im1, const float* table, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead, long long nb,
-                 long long f0, long long fstride, long long foff, hipStream_t s) {
+// (both launchers: WUN_OK, or the FFT path's refusal of an n_fft it has no kernel for -- unreachable behind check_res)
+int launch_cfwd(int tr, const float* x0, long long rows0, float* re0, float* im0, const float* x1, long long rows1, float* re1,
+                float* im1, const float* table, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead, long long nb,
+                long long f0, long long fstride, long long foff, hipStream_t s) {
     StftCfwdArgs a;
     a.x[0] = x0; a.re[0] = re0; a.im[0] = im0; a.M[0] = rows0 * nb;
     a.x[1] = x1; a.re[1] = re1; a.im[1] = im1; a.M[1] = rows1 * nb;
     a.table = table; a.T = T; a.nb = nb; a.f0 = f0; a.fstride = fstride; a.foff = foff;
     a.C = C; a.n_fft = n_fft; a.hop = hop; a.lead = lead; a.K = n_fft / 2 + 1;
+    if (tr == WUN_TR_FFT) return fft_launch_forward(a, x1 ? 2 : 1, s);
     const long long M = a.M[0] > a.M[1] ? a.M[0] : a.M[1];
     const dim3 grid((unsigned)((M + WUN_PF_BM - 1) / WUN_PF_BM), (unsigned)((a.K + WUN_PF_BN - 1) / WUN_PF_BN), x1 ? 2u : 1u);
     hipLaunchKernelGGL(stft_cfwd_kernel, grid, dim3(WUN_PF_BLOCK), 0, s, a);
+    return WUN_OK;
 }
 
-void launch_gemm(const float* re, const float* im, const float* table, float* frames, long long rows, long long nb,
-                 long long fstride, long long foff, int32_t n_fft, hipStream_t s) {
+int launch_gemm(int tr, const float* re, const float* im, const float* table, float* frames, long long rows, long long nb,
+                long long fstride, long long foff, int32_t n_fft, hipStream_t s) {
     IstftGemmArgs g;
     g.re = re; g.im = im; g.table = table; g.frames = frames; g.M = rows * nb; g.nb = nb; g.fstride = fstride; g.foff = foff;
     g.n_fft = n_fft; g.K = n_fft / 2 + 1; g.c_edge = 1.f / (float)n_fft; g.c_mid = 2.f / (float)n_fft;
+    if (tr == WUN_TR_FFT) return fft_launch_inverse(g, s);
     hipLaunchKernelGGL(istft_gemm_kernel, dim3((unsigned)((g.M + WUN_PF_BM - 1) / WUN_PF_BM), (unsigned)(n_fft / WUN_PF_BN)),
                        dim3(WUN_PF_BLOCK), 0, s, g);
+    return WUN_OK;
 }
 
 void launch_ola(const float* frames, const double* wsq, float* y, long long SB, int64_t T, int32_t C, int64_t F, const Blk& b,
@@ -543,10 +536,10 @@ void launch_mask(const float* xre, const float* xim, float* ere, float* eim, lon
     else hipLaunchKernelGGL(mask_kernel<1>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
 }
 
-int check_filter(const char* who, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
+int check_filter(const char* who, int tr, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
     int rc;
     if ((rc = check_audio(who, S, 1, n, C))) return rc;
-    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((rc = check_res(who, tr, n_fft, hop))) return rc;
     if ((hop & (hop - 1)) || hop > n_fft / 2)
         return fail(WUN_ERR_INVALID, std::string(who) + ": hop must be a power of two, at most n_fft / 2");
     if (S > WUN_PF_MAX_SOURCES) return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": more than 8 sources");
@@ -555,47 +548,47 @@ int check_filter(const char* who, int32_t S, int64_t n, int32_t C, int32_t n_fft
 
 }  // namespace
 
-extern "C" int64_t wun_stft_centered_frames(int64_t T, int32_t n_fft, int32_t hop) {
+// Every entry below exists twice, on the GEMM and on the FFT (`tr`): one body, the transform picked in launch_cfwd / launch_gemm.
+namespace {
+
+int64_t centered_frames_entry(const char* who, int tr, int64_t T, int32_t n_fft, int32_t hop) {
     int rc;
-    if ((rc = check_res("wun_stft_centered_frames", n_fft, hop))) return rc;
-    if (T < 1 || T > ((int64_t)1 << 40)) return fail(WUN_ERR_INVALID, "wun_stft_centered_frames: T outside 1..2^40");
+    if ((rc = check_res(who, tr, n_fft, hop))) return rc;
+    if (T < 1 || T > ((int64_t)1 << 40)) return fail(WUN_ERR_INVALID, std::string(who) + ": T outside 1..2^40");
     return centered_frames(T, n_fft, hop);
 }
 
-extern "C" int wun_stft_complex(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
-                                int32_t lead, int64_t F, const float* table_dev, float* re, float* im, void* stream) {
-    const char* who = "wun_stft_complex";
+int stft_complex_entry(const char* who, int tr, const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                       int32_t lead, int64_t F, const float* table_dev, float* re, float* im, void* stream) {
     if (!x || !table_dev || !re || !im) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
     int rc;
     if ((rc = check_audio(who, S, B, T, C))) return rc;
-    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((rc = check_res(who, tr, n_fft, hop))) return rc;
     if ((rc = check_framing(who, S, B, C, n_fft, lead, F))) return rc;
     const long long R = (long long)S * B * C, E = R * F * (n_fft / 2 + 1);
     if (overlaps(re, E, x, R * T) || overlaps(im, E, x, R * T) || overlaps(re, E, im, E))
         return fail(WUN_ERR_INVALID, std::string(who) + ": re / im overlap the audio or each other");
-    launch_cfwd(x, R, re, im, nullptr, 0, nullptr, nullptr, table_dev, T, C, n_fft, hop, lead, F, 0, F, 0, (hipStream_t)stream);
+    if ((rc = launch_cfwd(tr, x, R, re, im, nullptr, 0, nullptr, nullptr, table_dev, T, C, n_fft, hop, lead, F, 0, F, 0, (hipStream_t)stream))) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
     return WUN_OK;
 }
 
-extern "C" int64_t wun_istft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
-                                            int64_t F) {
-    const char* who = "wun_istft_scratch_floats";
+int64_t istft_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                            int32_t lead, int64_t F) {
     int rc;
     if ((rc = check_audio(who, S, B, T, C))) return rc;
-    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((rc = check_res(who, tr, n_fft, hop))) return rc;
     if ((rc = check_framing(who, S, B, C, n_fft, lead, F))) return rc;
     return (int64_t)S * B * C * block_frames(F, n_fft, hop) * n_fft + 2 * (int64_t)n_fft + 2;
 }
 
-extern "C" int wun_istft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
-                         int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
-    const char* who = "wun_istft";
+int istft_entry(const char* who, int tr, const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft,
+                int32_t hop, int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
     if (!re || !im || !table_dev || !y || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
     int rc;
     if ((rc = check_audio(who, S, B, T, C))) return rc;
-    if ((rc = check_res(who, n_fft, hop))) return rc;
+    if ((rc = check_res(who, tr, n_fft, hop))) return rc;
     if ((rc = check_framing(who, S, B, C, n_fft, lead, F))) return rc;
     const long long R = (long long)S * B * C, E = R * F * (n_fft / 2 + 1);
     if (overlaps(y, R * T, re, E) || overlaps(y, R * T, im, E))
@@ -608,7 +601,7 @@ extern "C" int wun_istft(const float* re, const float* im, int32_t S, int32_t B,
     for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
         const Blk b = block_of(f0, F, T, n_fft, hop, lead);
         if (b.t_lo >= b.t_hi) continue;                      // no sample ends in this block
-        launch_gemm(re, im, table_dev, frames, R, b.nb, F, b.fb0, n_fft, s);
+        if ((rc = launch_gemm(tr, re, im, table_dev, frames, R, b.nb, F, b.fb0, n_fft, s))) return rc;
         launch_ola(frames, wsq, y, (long long)S * B, T, C, F, b, n_fft, hop, lead, s);
     }
     const hipError_t e = hipGetLastError();
@@ -616,20 +609,19 @@ extern "C" int wun_istft(const float* re, const float* im, int32_t S, int32_t B,
     return WUN_OK;
 }
 
-extern "C" int64_t wun_mask_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
+int64_t mask_scratch_entry(const char* who, int tr, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
     int rc;
-    if ((rc = check_filter("wun_mask_filter_scratch_floats", S, n, C, n_fft, hop))) return rc;
+    if ((rc = check_filter(who, tr, S, n, C, n_fft, hop))) return rc;
     const long long nb = block_frames(centered_frames(n, n_fft, hop), n_fft, hop);
     // spectra of the S estimates and the mix (Re and Im), the frames of the S outputs, the window squares, alignment room
     return 2 * (int64_t)(S + 1) * C * nb * (n_fft / 2 + 1) + (int64_t)S * C * nb * n_fft + 2 * (int64_t)n_fft + 2;
 }
 
-extern "C" int wun_mask_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
-                               int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream) {
-    const char* who = "wun_mask_filter";
+int mask_filter_entry(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                      int32_t hop, int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream) {
     if (!mix_tc || !ests || !table_dev || !out || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
     int rc;
-    if ((rc = check_filter(who, S, n, C, n_fft, hop))) return rc;
+    if ((rc = check_filter(who, tr, S, n, C, n_fft, hop))) return rc;
     if (power != 1 && power != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": power must be 1 or 2");
     if (!(eps > 0.f) || !std::isfinite(eps)) return fail(WUN_ERR_INVALID, std::string(who) + ": eps not positive or not finite");
     const long long N = (long long)S * n * C;
@@ -646,18 +638,16 @@ extern "C" int wun_mask_filter(const float* mix_tc, const float* ests, int32_t S
     for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
         const Blk b = block_of(f0, F, n, n_fft, hop, lead);
         if (b.t_lo >= b.t_hi) continue;
-        launch_cfwd(ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s);
+        if ((rc = launch_cfwd(tr, ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s))) return rc;
         // (a short last block packs its spectra: the source stride is C nb K)
         launch_mask(xre, xim, ere, eim, (long long)C * b.nb * K, S, power, eps, s);
-        launch_gemm(ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s);
+        if ((rc = launch_gemm(tr, ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s))) return rc;
         launch_ola(frames, wsq, out, S, n, C, F, b, n_fft, hop, lead, s);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
     return WUN_OK;
 }
-
-namespace {
 
 // doubles of the EM statistics: R of every iteration, and the partial sums of one block
 long long wiener_doubles(int32_t S, int32_t C, int32_t n_fft, int32_t iterations) {
@@ -683,23 +673,19 @@ void launch_stats(const float* yre, const float* yim, double* part, double* stat
                        dim3(WUN_PF_BLOCK), 0, s, part, stat, S, K, nch, first ? 1 : 0, last ? 1 : 0, eps);
 }
 
-}  // namespace
-
-extern "C" int64_t wun_wiener_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations) {
-    const char* who = "wun_wiener_filter_scratch_floats";
+int64_t wiener_scratch_entry(const char* who, int tr, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations) {
     int rc;
-    if ((rc = check_filter(who, S, n, C, n_fft, hop))) return rc;
+    if ((rc = check_filter(who, tr, S, n, C, n_fft, hop))) return rc;
     if (iterations < 0 || iterations > WUN_WF_MAX_ITERS) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations outside 0..4");
-    return wun_mask_filter_scratch_floats(S, n, C, n_fft, hop) + 2 * wiener_doubles(S, C, n_fft, iterations);
+    return mask_scratch_entry(who, tr, S, n, C, n_fft, hop) + 2 * wiener_doubles(S, C, n_fft, iterations);
 }
 
-extern "C" int wun_wiener_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
-                                 int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev, float* out,
-                                 float* scratch, void* stream) {
-    const char* who = "wun_wiener_filter";
+int wiener_filter_entry(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                        int32_t hop, int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev, float* out,
+                        float* scratch, void* stream) {
     if (!mix_tc || !ests || !table_dev || !out || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
     int rc;
-    if ((rc = check_filter(who, S, n, C, n_fft, hop))) return rc;
+    if ((rc = check_filter(who, tr, S, n, C, n_fft, hop))) return rc;
     if (power != 1 && power != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": power must be 1 or 2");
     if (!(mask_eps > 0.f) || !std::isfinite(mask_eps))
         return fail(WUN_ERR_INVALID, std::string(who) + ": mask_eps not positive or not finite");
@@ -725,7 +711,7 @@ extern "C" int wun_wiener_filter(const float* mix_tc, const float* ests, int32_t
     for (int it = 0; it < iterations; ++it)
         for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
             const long long f1 = f0 + WUN_PF_FRAMES < F ? f0 + WUN_PF_FRAMES : F, nb = f1 - f0;
-            launch_cfwd(ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, nb, f0, nb, 0, s);
+            if ((rc = launch_cfwd(tr, ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, nb, f0, nb, 0, s))) return rc;
             launch_mask(xre, xim, ere, eim, (long long)C * nb * K, S, power, mask_eps, s);
             if (C == 2) {
                 if (it) launch_apply<2>(xre, xim, ere, eim, R, nb * K, S, K, it, sq, s);
@@ -739,16 +725,98 @@ extern "C" int wun_wiener_filter(const float* mix_tc, const float* ests, int32_t
     for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
         const Blk b = block_of(f0, F, n, n_fft, hop, lead);
         if (b.t_lo >= b.t_hi) continue;
-        launch_cfwd(ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s);
+        if ((rc = launch_cfwd(tr, ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s))) return rc;
         launch_mask(xre, xim, ere, eim, (long long)C * b.nb * K, S, power, mask_eps, s);
         if (iterations) {
             if (C == 2) launch_apply<2>(xre, xim, ere, eim, R, b.nb * K, S, K, iterations, sq, s);
             else launch_apply<1>(xre, xim, ere, eim, R, b.nb * K, S, K, iterations, sq, s);
         }
-        launch_gemm(ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s);
+        if ((rc = launch_gemm(tr, ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s))) return rc;
         launch_ola(frames, wsq, out, S, n, C, F, b, n_fft, hop, lead, s);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
     return WUN_OK;
+}
+
+}  // namespace
+
+// ---- the C ABI: every entry on the GEMM (the table of wun_stft_design, n_fft <= 2048) and on the FFT (wun_fft_design, <= 8192) ----
+extern "C" int64_t wun_stft_centered_frames(int64_t T, int32_t n_fft, int32_t hop) {
+    return centered_frames_entry("wun_stft_centered_frames", WUN_TR_GEMM, T, n_fft, hop);
+}
+extern "C" int64_t wun_fft_frames(int64_t T, int32_t n_fft, int32_t hop) {      // wun_stft_frames for the FFT's n_fft list
+    int rc;
+    if ((rc = check_res("wun_fft_frames", WUN_TR_FFT, n_fft, hop))) return rc;
+    if (T < n_fft || T > ((int64_t)1 << 40)) return fail(WUN_ERR_INVALID, "wun_fft_frames: T below n_fft or above 2^40");
+    return 1 + (T - n_fft) / hop;
+}
+extern "C" int64_t wun_fft_centered_frames(int64_t T, int32_t n_fft, int32_t hop) {
+    return centered_frames_entry("wun_fft_centered_frames", WUN_TR_FFT, T, n_fft, hop);
+}
+
+extern "C" int wun_stft_complex(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                                int32_t lead, int64_t F, const float* table_dev, float* re, float* im, void* stream) {
+    return stft_complex_entry("wun_stft_complex", WUN_TR_GEMM, x, S, B, T, C, n_fft, hop, lead, F, table_dev, re, im, stream);
+}
+extern "C" int wun_stft_complex_fft(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                                    int32_t lead, int64_t F, const float* table_dev, float* re, float* im, void* stream) {
+    return stft_complex_entry("wun_stft_complex_fft", WUN_TR_FFT, x, S, B, T, C, n_fft, hop, lead, F, table_dev, re, im, stream);
+}
+
+extern "C" int64_t wun_istft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
+                                            int64_t F) {
+    return istft_scratch_entry("wun_istft_scratch_floats", WUN_TR_GEMM, S, B, T, C, n_fft, hop, lead, F);
+}
+extern "C" int64_t wun_istft_fft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
+                                                int64_t F) {
+    return istft_scratch_entry("wun_istft_fft_scratch_floats", WUN_TR_FFT, S, B, T, C, n_fft, hop, lead, F);
+}
+
+extern "C" int wun_istft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                         int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
+    return istft_entry("wun_istft", WUN_TR_GEMM, re, im, S, B, T, C, n_fft, hop, lead, F, table_dev, y, scratch, stream);
+}
+extern "C" int wun_istft_fft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                             int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
+    return istft_entry("wun_istft_fft", WUN_TR_FFT, re, im, S, B, T, C, n_fft, hop, lead, F, table_dev, y, scratch, stream);
+}
+
+extern "C" int64_t wun_mask_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
+    return mask_scratch_entry("wun_mask_filter_scratch_floats", WUN_TR_GEMM, S, n, C, n_fft, hop);
+}
+extern "C" int64_t wun_mask_filter_fft_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
+    return mask_scratch_entry("wun_mask_filter_fft_scratch_floats", WUN_TR_FFT, S, n, C, n_fft, hop);
+}
+
+extern "C" int wun_mask_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                               int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream) {
+    return mask_filter_entry("wun_mask_filter", WUN_TR_GEMM, mix_tc, ests, S, n, C, n_fft, hop, power, eps, table_dev, out, scratch,
+                             stream);
+}
+extern "C" int wun_mask_filter_fft(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                                   int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream) {
+    return mask_filter_entry("wun_mask_filter_fft", WUN_TR_FFT, mix_tc, ests, S, n, C, n_fft, hop, power, eps, table_dev, out, scratch,
+                             stream);
+}
+
+extern "C" int64_t wun_wiener_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations) {
+    return wiener_scratch_entry("wun_wiener_filter_scratch_floats", WUN_TR_GEMM, S, n, C, n_fft, hop, iterations);
+}
+extern "C" int64_t wun_wiener_filter_fft_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                                                        int32_t iterations) {
+    return wiener_scratch_entry("wun_wiener_filter_fft_scratch_floats", WUN_TR_FFT, S, n, C, n_fft, hop, iterations);
+}
+
+extern "C" int wun_wiener_filter(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop,
+                                 int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev, float* out,
+                                 float* scratch, void* stream) {
+    return wiener_filter_entry("wun_wiener_filter", WUN_TR_GEMM, mix_tc, ests, S, n, C, n_fft, hop, power, mask_eps, iterations, eps,
+                               table_dev, out, scratch, stream);
+}
+extern "C" int wun_wiener_filter_fft(const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                                     int32_t hop, int32_t power, float mask_eps, int32_t iterations, float eps,
+                                     const float* table_dev, float* out, float* scratch, void* stream) {
+    return wiener_filter_entry("wun_wiener_filter_fft", WUN_TR_FFT, mix_tc, ests, S, n, C, n_fft, hop, power, mask_eps, iterations, eps,
+                               table_dev, out, scratch, stream);
 }

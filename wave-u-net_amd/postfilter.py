@@ -5,11 +5,14 @@ a track are masked against the mixture's own STFT, so they share the mixture's p
     out = f.apply(mix, estimates)                      # mix [n, C], estimates [S, n, C] -> [S, n, C]
     evaluate.separate_track(cfg, sep, audio, sr, postfilter=f)      # or model_config["postfilter"] = {"n_fft": 2048, ...}
     w = WienerFilter(n_fft=2048, hop=512, iterations=1)             # or postfilter={"kind": "wiener", "iterations": 1}
+    g = SoftMaskFilter(n_fft=4096, hop=1024, transform="fft")       # the transforms through an FFT: n_fft up to 8192 (5.13)
 
 Per channel, in the centred framing (frame f starts at f hop - (n_fft - hop), zeros outside the track):
 X = STFT(mix), E_s = STFT(est_s), A_s = |E_s|^power, mask_s = (A_s + eps / S) / (sum_j A_j + eps), out_s = ISTFT(mask_s X).
 Tensors on the GPU go through wun_mask_filter (no host sync; scratch cached per shape, tables shared with spectral.py); CPU
 tensors through a plain torch float32 implementation of the same definition (numpy stand-in separators, host tests).
+transform="gemm" (the default) runs the transforms as GEMMs against the [2, n_fft, K] table and stops at n_fft = 2048;
+transform="fft" runs them as FFTs (wun_mask_filter_fft / wun_wiener_filter_fft; on the CPU torch.fft in float32) up to 8192.
 
 WienerFilter starts from those masked spectra y_s and runs `iterations` EM steps of a local Gaussian model over the C channels
 together (the header's definition): v_s = mean_c |y_s|^2, R_s[k] = sum_f y_s y_s^H / (em_eps + sum_f v_s) over the whole track,
@@ -25,21 +28,26 @@ from . import _lib, spectral
 
 MAX_SOURCES = 8
 MAX_ITERATIONS = 4
-_KEYS = ("n_fft", "hop", "power", "eps")
+_KEYS = ("n_fft", "hop", "power", "eps", "transform")
+MAX_N_FFT = {"gemm": 2048, "fft": 8192}
 
 
 class SoftMaskFilter(object):
     """ValueError / NotImplementedError at construction for what wun_mask_filter refuses: n_fft must be a power of two in
-    64..2048, hop a power of two of at most n_fft / 2 (every sample's window-square sum is then at least 0.5), power 1
+    64..2048 (64..8192 with transform="fft"), hop a power of two of at most n_fft / 2 (every sample's window-square sum is then at least 0.5), power 1
     (magnitude ratio mask) or 2 (power ratio mask, single-channel Wiener), eps finite and positive."""
 
-    def __init__(self, n_fft=2048, hop=512, power=2, eps=1e-10):
+    def __init__(self, n_fft=2048, hop=512, power=2, eps=1e-10, transform="gemm"):
+        if transform not in MAX_N_FFT:
+            raise ValueError("transform must be \"gemm\" or \"fft\", got %r" % (transform,))
+        self.transform = transform
         for what, v in (("n_fft", n_fft), ("hop", hop), ("power", power)):
             if isinstance(v, bool) or int(v) != v:
                 raise ValueError("%s must be an integer, got %r" % (what, v))
         self.n_fft, self.hop, self.power, self.eps = int(n_fft), int(hop), int(power), float(eps)
-        if self.n_fft < 64 or self.n_fft > 2048 or self.n_fft & (self.n_fft - 1):
-            raise NotImplementedError("n_fft must be a power of two in 64..2048, got %d" % self.n_fft)
+        if self.n_fft < 64 or self.n_fft > MAX_N_FFT[transform] or self.n_fft & (self.n_fft - 1):
+            raise NotImplementedError("n_fft must be a power of two in 64..%d%s, got %d" % (
+                MAX_N_FFT[transform], "" if transform == "fft" else " (up to 8192 with transform=\"fft\")", self.n_fft))
         if self.hop < 1 or self.hop & (self.hop - 1) or self.hop > self.n_fft // 2:
             raise ValueError("hop must be a power of two, at most n_fft / 2, got %d" % self.hop)
         if self.power not in (1, 2):
@@ -51,7 +59,7 @@ class SoftMaskFilter(object):
     @classmethod
     def from_config(cls, spec):
         """model_config["postfilter"]: None, a SoftMaskFilter, True (the defaults) or a dict with any of `n_fft`, `hop`,
-        `power`, `eps`."""
+        `power`, `eps`, `transform`."""
         if spec is None or isinstance(spec, cls):
             return spec
         if spec is True:
@@ -64,22 +72,34 @@ class SoftMaskFilter(object):
         return cls(**spec)
 
     def spec(self):
-        return {"n_fft": self.n_fft, "hop": self.hop, "power": self.power, "eps": self.eps}
+        d = {"n_fft": self.n_fft, "hop": self.hop, "power": self.power, "eps": self.eps}
+        if self.transform == "fft":          # (the default stays out: the spec of a default filter is what it always was)
+            d["transform"] = "fft"
+        return d
+
+    def _entry(self, name):
+        """The library's entry `name` (wun_mask_filter, wun_wiener_filter_scratch_floats, ...) or its FFT twin (wun_mask_filter_fft,
+        wun_wiener_filter_fft_scratch_floats), and the device table that goes with it."""
+        if self.transform != "fft":
+            return getattr(_lib.load(), name), spectral._table
+        stem = name[:-len("_scratch_floats")] if name.endswith("_scratch_floats") else name
+        return getattr(_lib.load(), stem + "_fft" + name[len(stem):]), spectral._fft_table
 
     def scratch_floats(self, S, n, Cn):
-        k = int(_lib.load().wun_mask_filter_scratch_floats(int(S), int(n), int(Cn), self.n_fft, self.hop))
+        k = int(self._entry("wun_mask_filter_scratch_floats")[0](int(S), int(n), int(Cn), self.n_fft, self.hop))
         if k < 0:
             _lib.check(k)
         return k
 
     def run(self, mix, estimates, out, scratch):
-        """wun_mask_filter on the caller's buffers (contiguous float32 device tensors)."""
+        """wun_mask_filter (transform="fft": wun_mask_filter_fft) on the caller's buffers (contiguous float32 device tensors)."""
         S, n, Cn = (int(v) for v in estimates.shape)
         dev = estimates.device
+        entry, table = self._entry("wun_mask_filter")
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().wun_mask_filter(
+            _lib.check(entry(
                 mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps,
-                spectral._table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
     def apply(self, mix, estimates):
@@ -104,8 +124,8 @@ class SoftMaskFilter(object):
         return out
 
     def _apply_cpu(self, mix, estimates):
-        """The definition in torch float32 on the CPU: framed matmuls against the library's fp32 table, the window-square
-        sums in float64."""
+        """The definition in torch float32 on the CPU: framed matmuls against the library's fp32 table (transform="fft":
+        torch.fft.rfft / irfft of the frames times the float32 window), the window-square sums in float64."""
         S, n, Cn = (int(v) for v in estimates.shape)
         if S < 1 or n < 1 or Cn not in (1, 2):
             raise ValueError("S < 1, n < 1 or C not 1 or 2")
@@ -115,13 +135,20 @@ class SoftMaskFilter(object):
         lead = n_fft - hop
         F = -(-(n + lead) // hop)
         total = (F - 1) * hop + n_fft
-        tab = torch.from_numpy(spectral.design(n_fft))
-        cb, sb = tab[0], tab[1]                                                  # [n_fft, K]
+        fft = self.transform == "fft"
+        if fft:
+            win = torch.from_numpy(spectral.fft_design(n_fft)[2])                # [n_fft], the table's float32 window
+        else:
+            tab = torch.from_numpy(spectral.design(n_fft))
+            cb, sb = tab[0], tab[1]                                              # [n_fft, K]
 
         def transform(x):                                                        # [..., n, C] -> Re, Im [..., C, F, K]
             xp = torch.zeros(x.shape[:-2] + (Cn, total), dtype=torch.float32)
             xp[..., lead:lead + n] = x.transpose(-1, -2)
             fr = xp.unfold(-1, n_fft, hop)
+            if fft:
+                z = torch.fft.rfft(fr * win, dim=-1)
+                return z.real.contiguous(), z.imag.contiguous()
             return fr @ cb, fr @ sb
 
         xre, xim = transform(mix)
@@ -138,7 +165,10 @@ class SoftMaskFilter(object):
         ck = torch.full((n_fft // 2 + 1,), 2.0 / n_fft, dtype=torch.float32)
         ck[0] = ck[-1] = 1.0 / n_fft
         yre, yim = self._refine_cpu(mask * xre, mask * xim, xre, xim)
-        frames = (yre * ck) @ cb.t() + (yim * ck) @ sb.t()                       # [S, C, F, n_fft]
+        if fft:                                                                  # (irfft ignores Im of the bins 0 and n_fft / 2)
+            frames = torch.fft.irfft(torch.complex(yre, yim), n=n_fft, dim=-1) * win
+        else:
+            frames = (yre * ck) @ cb.t() + (yim * ck) @ sb.t()                   # [S, C, F, n_fft]
         y = torch.zeros((S, Cn, total), dtype=torch.float32)
         w = 0.5 - 0.5 * torch.cos(2.0 * np.pi * torch.arange(n_fft, dtype=torch.float64) / n_fft)
         ws = torch.zeros(total, dtype=torch.float64)
@@ -159,8 +189,8 @@ class WienerFilter(SoftMaskFilter):
     regulariser `em_eps` (finite and positive in float32)."""
     _KEYS = _KEYS + ("iterations", "em_eps")
 
-    def __init__(self, n_fft=2048, hop=512, power=2, eps=1e-10, iterations=1, em_eps=1e-10):
-        SoftMaskFilter.__init__(self, n_fft, hop, power, eps)
+    def __init__(self, n_fft=2048, hop=512, power=2, eps=1e-10, iterations=1, em_eps=1e-10, transform="gemm"):
+        SoftMaskFilter.__init__(self, n_fft, hop, power, eps, transform)
         if isinstance(iterations, bool) or int(iterations) != iterations:
             raise ValueError("iterations must be an integer, got %r" % (iterations,))
         self.iterations, self.em_eps = int(iterations), float(em_eps)
@@ -172,7 +202,7 @@ class WienerFilter(SoftMaskFilter):
     @classmethod
     def from_config(cls, spec):
         """None, a WienerFilter, True (the defaults) or a dict with any of `n_fft`, `hop`, `power`, `eps`, `iterations`,
-        `em_eps`."""
+        `em_eps`, `transform`."""
         if spec is None or isinstance(spec, cls):
             return spec
         if spec is True:
@@ -188,19 +218,20 @@ class WienerFilter(SoftMaskFilter):
         return dict(SoftMaskFilter.spec(self), kind="wiener", iterations=self.iterations, em_eps=self.em_eps)
 
     def scratch_floats(self, S, n, Cn):
-        k = int(_lib.load().wun_wiener_filter_scratch_floats(int(S), int(n), int(Cn), self.n_fft, self.hop, self.iterations))
+        k = int(self._entry("wun_wiener_filter_scratch_floats")[0](int(S), int(n), int(Cn), self.n_fft, self.hop, self.iterations))
         if k < 0:
             _lib.check(k)
         return k
 
     def run(self, mix, estimates, out, scratch):
-        """wun_wiener_filter on the caller's buffers (contiguous float32 device tensors)."""
+        """wun_wiener_filter (transform="fft": wun_wiener_filter_fft) on the caller's buffers (contiguous float32 device tensors)."""
         S, n, Cn = (int(v) for v in estimates.shape)
         dev = estimates.device
+        entry, table = self._entry("wun_wiener_filter")
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().wun_wiener_filter(
+            _lib.check(entry(
                 mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps, self.iterations,
-                self.em_eps, spectral._table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
+                self.em_eps, table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
     def _refine_cpu(self, yre, yim, xre, xim):

@@ -9,6 +9,7 @@ Hann window, no padding), for any number of resolutions up to 8, next to the tim
     stft_l1(net(mix), targets, loss)                   # under torch.autograd, for users of sep.module()
     re, im = stft(x, 2048, 512, centered=True)         # the complex STFT [S, B, C, F, K]
     x2 = istft(re, im, x.shape[2], 2048, 512, centered=True)      # and its inverse: x again, to fp32 rounding
+    re, im = stft(x, 4096, 1024, centered=True, transform="fft")  # the same definitions through an FFT, n_fft up to 8192 (5.13)
 
 Audio is float32 [S, B, T, C] channel-last on the GPU, as get_output stacks its outputs.  There is no CPU path.
 """
@@ -22,11 +23,15 @@ from . import _lib
 
 MAX_RESOLUTIONS = 8
 _TABLES = {}     # (n_fft, device) -> device tensor holding the windowed cos / sin table [2, n_fft, K]
+_FFT_TABLES = {}  # (n_fft, device) -> device tensor holding the FFT path's table [3, n_fft]
+TRANSFORMS = ("gemm", "fft")
 
 
-def frames(n, n_fft, hop):
-    """Frames of n samples: 1 + (n - n_fft) // hop, no padding (wun_stft_frames)."""
-    f = int(_lib.load().wun_stft_frames(int(n), int(n_fft), int(hop)))
+def frames(n, n_fft, hop, transform="gemm"):
+    """Frames of n samples: 1 + (n - n_fft) // hop, no padding (wun_stft_frames; with transform="fft" wun_fft_frames, n_fft up
+    to 8192)."""
+    lib = _lib.load()
+    f = int((lib.wun_fft_frames if _transform(transform) else lib.wun_stft_frames)(int(n), int(n_fft), int(hop)))
     if f < 0:
         _lib.check(f)
     return f
@@ -48,6 +53,31 @@ def _table(n_fft, device):
     if key not in _TABLES:
         _TABLES[key] = torch.from_numpy(design(n_fft)).to(device)
     return _TABLES[key]
+
+
+def fft_design(n_fft):
+    """The FFT path's fp32 table [3, n_fft] as a numpy array: cos and -sin of 2 pi t / n_fft, then the periodic Hann window
+    (wun_fft_design); n_fft a power of two in 64..8192."""
+    lib = _lib.load()
+    n = int(lib.wun_fft_table_floats(int(n_fft)))
+    if n < 0:
+        _lib.check(n)
+    table = np.zeros(n, np.float32)
+    _lib.check(lib.wun_fft_design(int(n_fft), table.ctypes.data_as(C.POINTER(C.c_float)), n))
+    return table.reshape(3, int(n_fft))
+
+
+def _fft_table(n_fft, device):
+    key = (int(n_fft), str(device))
+    if key not in _FFT_TABLES:
+        _FFT_TABLES[key] = torch.from_numpy(fft_design(n_fft)).to(device)
+    return _FFT_TABLES[key]
+
+
+def _transform(transform):
+    if transform not in TRANSFORMS:
+        raise ValueError("transform must be one of %s, got %r" % (", ".join(TRANSFORMS), transform))
+    return transform == "fft"
 
 
 def _stream(device):
@@ -75,60 +105,68 @@ def stft_magnitude(x, n_fft, hop):
     return mags
 
 
-def centered_frames(n, n_fft, hop):
-    """Frames of n samples in the centred framing: ceil((n + n_fft - hop) / hop) (wun_stft_centered_frames)."""
-    f = int(_lib.load().wun_stft_centered_frames(int(n), int(n_fft), int(hop)))
+def centered_frames(n, n_fft, hop, transform="gemm"):
+    """Frames of n samples in the centred framing: ceil((n + n_fft - hop) / hop) (wun_stft_centered_frames; with
+    transform="fft" wun_fft_centered_frames, n_fft up to 8192)."""
+    lib = _lib.load()
+    f = int((lib.wun_fft_centered_frames if _transform(transform) else lib.wun_stft_centered_frames)(int(n), int(n_fft), int(hop)))
     if f < 0:
         _lib.check(f)
     return f
 
 
-def _framing(T, n_fft, hop, centered):
+def _framing(T, n_fft, hop, centered, transform="gemm"):
     """(lead, F): centered: lead = n_fft - hop samples of zeros before the track, frames until the track is covered;
     else the framing of the loss, lead = 0 and frames(T, n_fft, hop) whole frames."""
     if centered:
-        return int(n_fft) - int(hop), centered_frames(T, n_fft, hop)
-    return 0, frames(T, n_fft, hop)
+        return int(n_fft) - int(hop), centered_frames(T, n_fft, hop, transform)
+    return 0, frames(T, n_fft, hop, transform)
 
 
-def stft(x, n_fft, hop, centered=False):
+def stft(x, n_fft, hop, centered=False, transform="gemm"):
     """(re, im) of audio x [S, B, T, C]: float32 [S, B, C, F, K] each (wun_stft_complex).  centered=False: the loss's
     framing (no padding, T >= n_fft); centered=True: frame f starts at f hop - (n_fft - hop), zeros outside the track,
-    F = centered_frames(T, n_fft, hop), any T >= 1.  One launch on the current stream, no sync."""
+    F = centered_frames(T, n_fft, hop), any T >= 1.  transform="gemm" (n_fft up to 2048) or "fft" (wun_stft_complex_fft, up to
+    8192): one definition, two summation orders.  One launch on the current stream, no sync."""
+    fft = _transform(transform)
     x = _audio(x, "x")
     S, B, T, Cn = (int(v) for v in x.shape)
-    lead, F = _framing(T, n_fft, hop, centered)
+    lead, F = _framing(T, n_fft, hop, centered, transform)
     re = torch.empty((S, B, Cn, F, int(n_fft) // 2 + 1), dtype=torch.float32, device=x.device)
     im = torch.empty_like(re)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().wun_stft_complex(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), lead, F,
-                                                _table(n_fft, x.device).data_ptr(), re.data_ptr(), im.data_ptr(),
-                                                _stream(x.device)))
+        lib = _lib.load()
+        _lib.check((lib.wun_stft_complex_fft if fft else lib.wun_stft_complex)(
+            x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), lead, F,
+            (_fft_table if fft else _table)(n_fft, x.device).data_ptr(), re.data_ptr(), im.data_ptr(), _stream(x.device)))
     return re, im
 
 
-def istft(re, im, length, n_fft, hop, centered=False):
+def istft(re, im, length, n_fft, hop, centered=False, transform="gemm"):
     """Audio [S, B, length, C] from re, im [S, B, C, F, K] (wun_istft): the windowed overlap-add of the inverse transforms
     of the frames over the overlap-add of the squared window, 0 where that is below 1e-8.  F must be the frame count of
-    `length` in the chosen framing.  No sync; not differentiable."""
+    `length` in the chosen framing.  transform="fft": wun_istft_fft, n_fft up to 8192.  No sync; not differentiable."""
+    fft = _transform(transform)
     if not (torch.is_tensor(re) and torch.is_tensor(im) and re.is_cuda and im.is_cuda):
         raise ValueError("re and im must be tensors on the GPU (there is no CPU path)")
     if re.dim() != 5 or re.shape != im.shape or re.device != im.device:
         raise ValueError("re and im must be [S, B, C, F, K] of one shape and device, got %s and %s" % (tuple(re.shape), tuple(im.shape)))
     re, im = re.to(torch.float32).contiguous(), im.to(torch.float32).contiguous()
     S, B, Cn, F, K = (int(v) for v in re.shape)
-    lead, want = _framing(int(length), n_fft, hop, centered)
+    lead, want = _framing(int(length), n_fft, hop, centered, transform)
     if F != want or K != int(n_fft) // 2 + 1:
         raise ValueError("spectra of %d frames x %d bins, expected %d x %d for length %d" % (F, K, want, int(n_fft) // 2 + 1, length))
     lib = _lib.load()
-    n = int(lib.wun_istft_scratch_floats(S, B, int(length), Cn, int(n_fft), int(hop), lead, F))
+    n = int((lib.wun_istft_fft_scratch_floats if fft else lib.wun_istft_scratch_floats)(S, B, int(length), Cn, int(n_fft), int(hop),
+                                                                                    lead, F))
     if n < 0:
         _lib.check(n)
     scratch = torch.empty(n, dtype=torch.float32, device=re.device)
     y = torch.empty((S, B, int(length), Cn), dtype=torch.float32, device=re.device)
     with torch.cuda.device(re.device):
-        _lib.check(lib.wun_istft(re.data_ptr(), im.data_ptr(), S, B, int(length), Cn, int(n_fft), int(hop), lead, F,
-                                 _table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
+        _lib.check((lib.wun_istft_fft if fft else lib.wun_istft)(
+            re.data_ptr(), im.data_ptr(), S, B, int(length), Cn, int(n_fft), int(hop), lead, F,
+            (_fft_table if fft else _table)(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
     return y
 
 
