@@ -27,6 +27,7 @@ _lib.load().wun_stft_complex_fft                     # the feature: an Attribute
 import _fft_np as fo  # noqa: E402
 import _spectral_np as sp  # noqa: E402
 from _observed import record  # noqa: E402
+from _unaligned import _offset_copy  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -42,15 +43,6 @@ _CACHE = {}
 def lib():
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     return _lib.load()
-
-
-def _offset_copy(x):
-    """A copy of x whose base pointer lies one float behind an allocation's start."""
-    buf = torch.empty(x.numel() + 1, dtype=x.dtype, device=x.device)
-    v = buf[1:].view(x.shape)
-    v.copy_(x)
-    assert v.data_ptr() % 8 == 4 and v.is_contiguous()
-    return v
 
 
 def _signal(n_fft, hop, T, shape):

@@ -18,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _spectral_np as ora  # noqa: E402
 from _observed import record  # noqa: E402
+from _unaligned import _offset_copy  # noqa: E402
 
 import wave_u_net_amd as wun  # noqa: E402
 from wave_u_net_amd import _lib, spectral, training  # noqa: E402
@@ -44,15 +45,6 @@ _CACHE = {}
 def lib():
     assert torch.cuda.is_available(), "GPU tests need an MI355X"
     return _lib.load()
-
-
-def _offset_copy(x):
-    """A copy of x whose base pointer lies one float behind an allocation's start."""
-    buf = torch.empty(x.numel() + 1, dtype=x.dtype, device=x.device)
-    v = buf[1:].view(x.shape)
-    v.copy_(x)
-    assert v.data_ptr() % 8 == 4 and v.is_contiguous()
-    return v
 
 
 def _case(name):

@@ -3,11 +3,11 @@
 // of wun_spectral.hip's analysis, on the same table.
 //
 //   forward    Re / Im[r][f][k] = sum_n frame_f[n] * Cb / Sb[n][k], frame_f[n] = x[f hop - lead + n], zero outside [0, T):
-//              stft_fwd_kernel's GEMM (wun_spectral.hip) with a bounds-checked gather, n ascending in one accumulator
+//              the forward tile of wun_stft.h (stft_fwd_kernel's, wun_spectral.hip) with a bounds-checked gather
 //   mask       mask_s = (A_s + eps / S) / (sum_j A_j + eps), A = |E|^p: one lane per bin reads the S estimate spectra and
 //              the mix spectrum once and writes mask_s X over E_s
-//   inverse    frame[m][n] = sum_k (c_k / n_fft) (Re[m][k] Cb[n][k] + Im[m][k] Sb[n][k]): stft_bwd_kernel's transposed GEMM;
-//              the factor c_k / n_fft is a power of two, applied while the spectra are staged (exact)
+//   inverse    frame[m][n] = sum_k (c_k / n_fft) (Re[m][k] Cb[n][k] + Im[m][k] Sb[n][k]): the inverse tile of wun_stft.h
+//              (stft_bwd_kernel's); the factor c_k / n_fft is a power of two, applied while the spectra are staged (exact)
 //   overlap    y[t] = sum_f frame_f[t + lead - f hop] / sum_f w^2[t + lead - f hop]: one lane per output float, the covering
 //              frames in ascending f, the window squares in float64 from a table the call computes first
 //   EM         (wun_wiener_filter) per iteration: statistics sum_f y y^H and sum_f v per (source, bin) in float64 -- partial sums
@@ -25,21 +25,12 @@
 //
 // Built WITHOUT the packed fp32 VALU instructions (csrc/Makefile NO_PK_FP32): the filter runs beside inference of
 // either compute mode.  Every argument check runs before any GPU work; nothing allocates or synchronises.
-#include "wun_fft.h"
-#include "../../include/wun.h"
+#include "wun_stft.h"
 
 #include <cmath>
-#include <string>
 
 using namespace wun;
-int fail(int code, const std::string& msg);      // wun_plan.hip: sets wun_last_error(), returns code
 
-#define WUN_PF_BLOCK 256             // threads per workgroup of every kernel here (4 waves)
-#define WUN_PF_BM 64                 // frames per GEMM workgroup: 2 x 2 waves, each 32 frames x 16 columns
-#define WUN_PF_BN 32                 // columns per GEMM workgroup (forward: bins, re and im each; inverse: samples of a frame)
-#define WUN_PF_KC 32                 // reduction indices staged per step
-#define WUN_PF_PA 36                 // LDS pitch of a tile read as [row = lane & 15][k = lane >> 4] (wun_spectral.hip)
-#define WUN_PF_PB 48                 // LDS pitch of a tile read as [k = lane >> 4][col = lane & 15]
 #define WUN_PF_FRAMES 256            // new frames per block of wun_istft / wun_mask_filter
 #define WUN_PF_MAX_SOURCES 8
 #define WUN_WF_CHUNK 16              // frames per partial sum of the EM statistics; divides WUN_PF_FRAMES
@@ -47,97 +38,38 @@ int fail(int code, const std::string& msg);      // wun_plan.hip: sets wun_last_
 
 namespace wun {      // the kernels carry the library's wun:: prefix in profiler output
 
-__device__ __forceinline__ f32x4 pf_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // (StftCfwdArgs, the frame rows of one launch: wun_fft.h)
 
-// grid: x = tile of 64 frame rows, y = tile of 32 bins, z = signal.  stft_fwd_kernel with frames that may reach outside
-// [0, T): every gathered sample is bounds-checked.  Lane layout of the MFMA as there.
-__global__ __launch_bounds__(WUN_PF_BLOCK) void stft_cfwd_kernel(StftCfwdArgs p) {
-    __shared__ float As[WUN_PF_BM * WUN_PF_PA];
-    __shared__ float Bc[WUN_PF_KC * WUN_PF_PB];
-    __shared__ float Bs[WUN_PF_KC * WUN_PF_PB];
+// grid: x = tile of 64 frame rows, y = tile of 32 bins, z = signal.  stft_fwd_tile (wun_stft.h) with the bounds check -- a frame
+// may reach outside [0, T) -- storing Re / Im at the frame's row of the spectra.
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void stft_cfwd_kernel(StftCfwdArgs p) {
     const int z = blockIdx.z;
     const long long M = p.M[z];
-    const long long m0 = (long long)blockIdx.x * WUN_PF_BM;
-    if (m0 >= M) return;                                     // (the grid is sized by the larger signal)
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lr = lane & 15, lq = lane >> 4;
-    const int sc = tid & 31, sr = tid >> 5;                  // staging: column and first row of this lane
-    const float* __restrict__ x = p.x[z];
-    const int k0 = (int)blockIdx.y * WUN_PF_BN;
-    const int wm = (w & 1) * 32, wk = (w >> 1) * 16;
-
-    long long rbase[WUN_PF_BM / 8], t0[WUN_PF_BM / 8];       // offset of the row's sample 0 (-1: behind the last frame row)
-#pragma unroll                                               // and the sample index of the frame's n = 0 (may be negative)
-    for (int it = 0; it < WUN_PF_BM / 8; ++it) {
-        const long long m = m0 + sr + 8 * it;
-        rbase[it] = -1; t0[it] = 0;
-        if (m < M) {
-            const long long r = m / p.nb, fl = m - r * p.nb;
-            const long long sb = r / p.C, c = r - sb * p.C;
-            rbase[it] = sb * p.T * p.C + c;
-            t0[it] = (p.f0 + fl) * p.hop - p.lead;
-        }
-    }
-    const bool kin = k0 + sc < p.K;
-    const float* __restrict__ tc = p.table + k0 + sc;
-    const float* __restrict__ ts = tc + (long long)p.n_fft * p.K;
-
-    f32x4 are[2], aim[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { are[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; aim[i] = are[i]; }
-
-    for (int n0 = 0; n0 < p.n_fft; n0 += WUN_PF_KC) {        // ascending n: the one accumulation order
-        __syncthreads();                                     // the previous step is read
-#pragma unroll
-        for (int it = 0; it < WUN_PF_BM / 8; ++it) {
-            const long long t = t0[it] + n0 + sc;
-            const bool in = rbase[it] >= 0 && t >= 0 && t < p.T;
-            As[(sr + 8 * it) * WUN_PF_PA + sc] = in ? x[rbase[it] + t * p.C] : 0.f;
-        }
-#pragma unroll
-        for (int it = 0; it < WUN_PF_KC / 8; ++it) {
-            const int nl = sr + 8 * it;
-            const long long idx = (long long)(n0 + nl) * p.K;
-            Bc[nl * WUN_PF_PB + sc] = kin ? tc[idx] : 0.f;
-            Bs[nl * WUN_PF_PB + sc] = kin ? ts[idx] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < WUN_PF_KC / 4; ++s) {
-            const int kq = 4 * s + lq;
-            const float a0 = As[(wm + lr) * WUN_PF_PA + kq], a1 = As[(wm + 16 + lr) * WUN_PF_PA + kq];
-            const float bc = Bc[kq * WUN_PF_PB + wk + lr], bs = Bs[kq * WUN_PF_PB + wk + lr];
-            are[0] = pf_mfma(a0, bc, are[0]);
-            aim[0] = pf_mfma(a0, bs, aim[0]);
-            are[1] = pf_mfma(a1, bc, are[1]);
-            aim[1] = pf_mfma(a1, bs, aim[1]);
-        }
-    }
-    const int k = k0 + wk + lr;
-    if (k >= p.K) return;
+    if ((long long)blockIdx.x * WUN_STFT_BM >= M) return;    // (the grid is sized by the larger signal)
     float* __restrict__ re = p.re[z];
     float* __restrict__ im = p.im[z];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            const long long m = m0 + wm + 16 * i + 4 * lq + r4;
-            if (m >= M) continue;
+    stft_fwd_tile<true>(
+        p.x[z], p.table, M, p.T, p.C, p.n_fft, p.K,
+        [&](long long m, long long& base, long long& t0) {
+            const long long r = m / p.nb, fl = m - r * p.nb;
+            const long long sb = r / p.C, c = r - sb * p.C;
+            base = sb * p.T * p.C + c;
+            t0 = (p.f0 + fl) * p.hop - p.lead;
+        },
+        [&](long long m, int k, float vre, float vim) {
             const long long r = m / p.nb, fl = m - r * p.nb;
             const long long o = (r * p.fstride + p.foff + fl) * p.K + k;
-            re[o] = are[i][r4];
-            im[o] = aim[i][r4];
-        }
+            re[o] = vre;
+            im[o] = vim;
+        });
 }
 
 // One lane per bin (c, frame, k) of a block: xre / xim [C][nb][K] is the mix spectrum, ere / eim [S][C][nb][K] the estimates',
 // which mask_s * X replaces.  E = C * nb * K bins.  POWER 2: A = Re^2 + Im^2, no square root; POWER 1: its root.
 template <int POWER>
-__global__ __launch_bounds__(WUN_PF_BLOCK) void mask_kernel(const float* __restrict__ xre, const float* __restrict__ xim, float* ere,
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void mask_kernel(const float* __restrict__ xre, const float* __restrict__ xim, float* ere,
                                                             float* eim, long long E, int S, float eps, float eps_s) {
-    const long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * WUN_STFT_BLOCK + threadIdx.x;
     if (e >= E) return;
     float A[WUN_PF_MAX_SOURCES];
     float sum = 0.f;
@@ -162,78 +94,18 @@ __global__ __launch_bounds__(WUN_PF_BLOCK) void mask_kernel(const float* __restr
         }
 }
 
-// grid: x = tile of 64 frame rows, y = tile of 32 samples of the frame.  stft_bwd_kernel with the spectra scaled by
-// c_k / n_fft while staged: the reduction runs over the bins in ascending order, a bin's real part before its imaginary part;
-// bins behind K are staged as zeros.
-__global__ __launch_bounds__(WUN_PF_BLOCK) void istft_gemm_kernel(IstftGemmArgs p) {
-    __shared__ float Ar[WUN_PF_BM * WUN_PF_PA];
-    __shared__ float Ai[WUN_PF_BM * WUN_PF_PA];
-    __shared__ float Bc[WUN_PF_BN * WUN_PF_PA];
-    __shared__ float Bs[WUN_PF_BN * WUN_PF_PA];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lr = lane & 15, lq = lane >> 4;
-    const int sc = tid & 31, sr = tid >> 5;
-    const long long m0 = (long long)blockIdx.x * WUN_PF_BM;
-    const int n0 = (int)blockIdx.y * WUN_PF_BN;
-    const int wm = (w & 1) * 32, wn = (w >> 1) * 16;
-    const float* __restrict__ tc = p.table;
-    const float* __restrict__ ts = p.table + (long long)p.n_fft * p.K;
-
-    long long srow[WUN_PF_BM / 8];                           // first float of this lane's spectrum rows (-1: behind the last)
-#pragma unroll
-    for (int it = 0; it < WUN_PF_BM / 8; ++it) {
-        const long long m = m0 + sr + 8 * it;
-        srow[it] = -1;
-        if (m < p.M) {
-            const long long r = m / p.nb, fl = m - r * p.nb;
-            srow[it] = (r * p.fstride + p.foff + fl) * p.K;
-        }
-    }
-
-    f32x4 acc[2];
-    acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = acc[0];
-    for (int k0 = 0; k0 < p.K; k0 += WUN_PF_KC) {            // ascending k
-        __syncthreads();
-        const int k = k0 + sc;
-        const bool kin = k < p.K;
-        const float ck = (k == 0 || k == p.K - 1) ? p.c_edge : p.c_mid;
-#pragma unroll
-        for (int it = 0; it < WUN_PF_BM / 8; ++it) {
-            const bool in = kin && srow[it] >= 0;
-            Ar[(sr + 8 * it) * WUN_PF_PA + sc] = in ? ck * p.re[srow[it] + k] : 0.f;
-            Ai[(sr + 8 * it) * WUN_PF_PA + sc] = in ? ck * p.im[srow[it] + k] : 0.f;
-        }
-#pragma unroll
-        for (int it = 0; it < WUN_PF_BN / 8; ++it) {
-            const int nl = sr + 8 * it;
-            const long long idx = (long long)(n0 + nl) * p.K + k;
-            Bc[nl * WUN_PF_PA + sc] = kin ? tc[idx] : 0.f;
-            Bs[nl * WUN_PF_PA + sc] = kin ? ts[idx] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < WUN_PF_KC / 4; ++s) {
-            const int kq = 4 * s + lq;
-            const float bc = Bc[(wn + lr) * WUN_PF_PA + kq], bs = Bs[(wn + lr) * WUN_PF_PA + kq];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                acc[i] = pf_mfma(Ar[(wm + 16 * i + lr) * WUN_PF_PA + kq], bc, acc[i]);
-                acc[i] = pf_mfma(Ai[(wm + 16 * i + lr) * WUN_PF_PA + kq], bs, acc[i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const long long m = m0 + wm + 16 * i + 4 * lq + r;
-            if (m < p.M) p.frames[m * p.n_fft + n0 + wn + lr] = acc[i][r];
-        }
+// grid: x = tile of 64 frame rows, y = tile of 32 samples of the frame.  stft_inv_tile (wun_stft.h) with the spectra scaled by
+// c_k / n_fft while staged, on the frame rows' places in the spectra.
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void istft_gemm_kernel(IstftGemmArgs p) {
+    stft_inv_tile<true>(p.re, p.im, p.table, p.frames, p.M, p.n_fft, p.K, p.c_edge, p.c_mid, [&](long long m) {
+        const long long r = m / p.nb, fl = m - r * p.nb;
+        return (r * p.fstride + p.foff + fl) * p.K;
+    });
 }
 
 // wsq[n] = w[n]^2 in float64, w the periodic Hann window (cospi: the argument n / n_fft is exact, no range reduction)
-__global__ __launch_bounds__(WUN_PF_BLOCK) void window_sq_kernel(double* __restrict__ wsq, int n_fft) {
-    const int n = blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void window_sq_kernel(double* __restrict__ wsq, int n_fft) {
+    const int n = blockIdx.x * WUN_STFT_BLOCK + threadIdx.x;
     if (n >= n_fft) return;
     const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)n_fft);
     wsq[n] = w * w;
@@ -249,9 +121,9 @@ struct OlaArgs {
 
 // one lane per output float: the frames that cover the sample in ascending f, over the window squares of the same frames;
 // 0 where those sum to less than 1e-8 (librosa's rule).  Grid-stride: the grid is capped, one writer per float all the same.
-__global__ __launch_bounds__(WUN_PF_BLOCK) void istft_ola_kernel(OlaArgs p) {
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void istft_ola_kernel(OlaArgs p) {
     const long long span = (p.t_hi - p.t_lo) * p.C;
-    for (long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x; e < p.N; e += (long long)gridDim.x * WUN_PF_BLOCK) {
+    for (long long e = (long long)blockIdx.x * WUN_STFT_BLOCK + threadIdx.x; e < p.N; e += (long long)gridDim.x * WUN_STFT_BLOCK) {
         const long long sb = e / span, rest = e - sb * span;
         const long long tl = rest / p.C, c = rest - tl * p.C;
         const long long t = p.t_lo + tl, u = t + p.lead;     // u - f hop is the sample's place in frame f
@@ -279,11 +151,11 @@ __global__ __launch_bounds__(WUN_PF_BLOCK) void istft_ola_kernel(OlaArgs p) {
 // chunk's partial sums to part [nch][S][Q][K].  yre / yim [S][CH][nf][K] are the block's spectra; the block starts at a
 // multiple of WUN_PF_FRAMES, so chunk c holds the absolute frames [f0 + 16 c, f0 + 16 c + 16) whatever the track's length.
 template <int CH>
-__global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_stats_kernel(const float* __restrict__ yre, const float* __restrict__ yim,
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void wiener_stats_kernel(const float* __restrict__ yre, const float* __restrict__ yim,
                                                                     double* __restrict__ part, int S, int nf, int K) {
     constexpr int Q = CH * CH + 1;
     const int nch = (nf + WUN_WF_CHUNK - 1) / WUN_WF_CHUNK;
-    const long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * WUN_STFT_BLOCK + threadIdx.x;
     if (e >= (long long)S * nch * K) return;
     const int k = (int)(e % K);
     const int t = (int)(e / K), ch = t % nch, s = t / nch;
@@ -317,9 +189,9 @@ __global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_stats_kernel(const float*
 // track's first block starts them from 0, so nothing is read that this call did not write).  `last`: the track's last block
 // then divides by eps + sum v, leaving R_s[k] and sum v.
 template <int Q>
-__global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_reduce_kernel(const double* __restrict__ part, double* __restrict__ stat, int S,
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void wiener_reduce_kernel(const double* __restrict__ part, double* __restrict__ stat, int S,
                                                                      int K, int nch, int first, int last, double eps) {
-    const int e = blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    const int e = blockIdx.x * WUN_STFT_BLOCK + threadIdx.x;
     if (e >= S * K) return;
     const int s = e / K, k = e - s * K;
     double a[Q];
@@ -343,11 +215,11 @@ __global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_reduce_kernel(const doubl
 // R_s + sq I, its closed-form inverse and y_s = v_s R_s Cxx^-1 X in float64, each y rounded to float32 (a stored spectrum) --
 // and writes the last y over the masked spectra.  NK = nb * K.
 template <int CH>
-__global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_apply_kernel(const float* __restrict__ xre, const float* __restrict__ xim,
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void wiener_apply_kernel(const float* __restrict__ xre, const float* __restrict__ xim,
                                                                     float* yre, float* yim, const double* __restrict__ R, long long NK,
                                                                     int S, int K, int niter, double sq) {
     constexpr int Q = CH * CH + 1;
-    const long long e = (long long)blockIdx.x * WUN_PF_BLOCK + threadIdx.x;
+    const long long e = (long long)blockIdx.x * WUN_STFT_BLOCK + threadIdx.x;
     if (e >= NK) return;
     const int k = (int)(e % K);
     float yr[WUN_PF_MAX_SOURCES][CH], yi[WUN_PF_MAX_SOURCES][CH];
@@ -424,25 +296,6 @@ __global__ __launch_bounds__(WUN_PF_BLOCK) void wiener_apply_kernel(const float*
 
 namespace {
 
-int check_audio(const char* who, int32_t S, int32_t B, int64_t T, int32_t C) {
-    if (S < 1 || B < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": S < 1 or B < 1");
-    if (C != 1 && C != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": C must be 1 or 2");
-    if (T < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": no frames");
-    if ((int64_t)S * B > ((int64_t)1 << 24) || T > ((int64_t)1 << 40) / ((int64_t)S * B * C))
-        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^24 rows or 2^40 floats");
-    return WUN_OK;
-}
-
-// the spectral section's order: n_fft (UNSUPPORTED), then hop (INVALID); a track shorter than a frame is legal here
-// (tr: the GEMM's table grows as n_fft^2 / 2 and stops at 2048; the FFT path goes on to 8192)
-int check_res(const char* who, int tr, int32_t n_fft, int32_t hop) {
-    const int32_t n_max = tr == WUN_TR_FFT ? 8192 : 2048;
-    if (n_fft < 64 || n_fft > n_max || (n_fft & (n_fft - 1)))
-        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": n_fft must be a power of two in 64.." + (tr == WUN_TR_FFT ? "8192" : "2048"));
-    if (hop < 1 || hop > n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": hop outside 1..n_fft");
-    return WUN_OK;
-}
-
 int check_framing(const char* who, int32_t S, int32_t B, int32_t C, int32_t n_fft, int32_t lead, int64_t F) {
     if (lead < 0 || lead >= n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": lead outside [0, n_fft)");
     if (F < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": F < 1");
@@ -490,8 +343,8 @@ int launch_cfwd(int tr, const float* x0, long long rows0, float* re0, float* im0
     a.C = C; a.n_fft = n_fft; a.hop = hop; a.lead = lead; a.K = n_fft / 2 + 1;
     if (tr == WUN_TR_FFT) return fft_launch_forward(a, x1 ? 2 : 1, s);
     const long long M = a.M[0] > a.M[1] ? a.M[0] : a.M[1];
-    const dim3 grid((unsigned)((M + WUN_PF_BM - 1) / WUN_PF_BM), (unsigned)((a.K + WUN_PF_BN - 1) / WUN_PF_BN), x1 ? 2u : 1u);
-    hipLaunchKernelGGL(stft_cfwd_kernel, grid, dim3(WUN_PF_BLOCK), 0, s, a);
+    const dim3 grid((unsigned)((M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)((a.K + WUN_STFT_BN - 1) / WUN_STFT_BN), x1 ? 2u : 1u);
+    hipLaunchKernelGGL(stft_cfwd_kernel, grid, dim3(WUN_STFT_BLOCK), 0, s, a);
     return WUN_OK;
 }
 
@@ -501,8 +354,8 @@ int launch_gemm(int tr, const float* re, const float* im, const float* table, fl
     g.re = re; g.im = im; g.table = table; g.frames = frames; g.M = rows * nb; g.nb = nb; g.fstride = fstride; g.foff = foff;
     g.n_fft = n_fft; g.K = n_fft / 2 + 1; g.c_edge = 1.f / (float)n_fft; g.c_mid = 2.f / (float)n_fft;
     if (tr == WUN_TR_FFT) return fft_launch_inverse(g, s);
-    hipLaunchKernelGGL(istft_gemm_kernel, dim3((unsigned)((g.M + WUN_PF_BM - 1) / WUN_PF_BM), (unsigned)(n_fft / WUN_PF_BN)),
-                       dim3(WUN_PF_BLOCK), 0, s, g);
+    hipLaunchKernelGGL(istft_gemm_kernel, dim3((unsigned)((g.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)(n_fft / WUN_STFT_BN)),
+                       dim3(WUN_STFT_BLOCK), 0, s, g);
     return WUN_OK;
 }
 
@@ -511,27 +364,20 @@ void launch_ola(const float* frames, const double* wsq, float* y, long long SB, 
     OlaArgs o;
     o.frames = frames; o.wsq = wsq; o.y = y; o.T = T; o.F = F; o.nb = b.nb; o.fb0 = b.fb0; o.t_lo = b.t_lo; o.t_hi = b.t_hi;
     o.N = SB * (b.t_hi - b.t_lo) * C; o.C = C; o.n_fft = n_fft; o.hop = hop; o.lead = lead;
-    long long grid = (o.N + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK;
+    long long grid = (o.N + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK;
     if (grid > (1 << 20)) grid = 1 << 20;
-    hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)grid), dim3(WUN_PF_BLOCK), 0, s, o);
-}
-
-// the float64 window squares sit behind `floats` floats of scratch, on an 8-byte boundary
-double* wsq_of(float* scratch, long long floats) {
-    uintptr_t pa = (uintptr_t)(scratch + floats);
-    pa = (pa + 7) & ~(uintptr_t)7;
-    return (double*)pa;
+    hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)grid), dim3(WUN_STFT_BLOCK), 0, s, o);
 }
 
 void launch_window(double* wsq, int32_t n_fft, hipStream_t s) {
-    hipLaunchKernelGGL(window_sq_kernel, dim3((unsigned)((n_fft + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), dim3(WUN_PF_BLOCK), 0, s, wsq,
+    hipLaunchKernelGGL(window_sq_kernel, dim3((unsigned)((n_fft + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK)), dim3(WUN_STFT_BLOCK), 0, s, wsq,
                        n_fft);
 }
 
 // mask_s X over the estimates' spectra of one block: E = C nb K bins per source
 void launch_mask(const float* xre, const float* xim, float* ere, float* eim, long long E, int32_t S, int32_t power, float eps,
                  hipStream_t s) {
-    const dim3 grid((unsigned)((E + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), blk(WUN_PF_BLOCK);
+    const dim3 grid((unsigned)((E + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK)), blk(WUN_STFT_BLOCK);
     if (power == 2) hipLaunchKernelGGL(mask_kernel<2>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
     else hipLaunchKernelGGL(mask_kernel<1>, grid, blk, 0, s, xre, xim, ere, eim, E, S, eps, eps / (float)S);
 }
@@ -569,9 +415,7 @@ int stft_complex_entry(const char* who, int tr, const float* x, int32_t S, int32
     if (overlaps(re, E, x, R * T) || overlaps(im, E, x, R * T) || overlaps(re, E, im, E))
         return fail(WUN_ERR_INVALID, std::string(who) + ": re / im overlap the audio or each other");
     if ((rc = launch_cfwd(tr, x, R, re, im, nullptr, 0, nullptr, nullptr, table_dev, T, C, n_fft, hop, lead, F, 0, F, 0, (hipStream_t)stream))) return rc;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
-    return WUN_OK;
+    return launch_status(who);
 }
 
 int64_t istft_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
@@ -596,7 +440,7 @@ int istft_entry(const char* who, int tr, const float* re, const float* im, int32
 
     hipStream_t s = (hipStream_t)stream;
     float* frames = scratch;
-    double* wsq = wsq_of(scratch, R * block_frames(F, n_fft, hop) * n_fft);
+    double* wsq = f64_tail(scratch, R * block_frames(F, n_fft, hop) * n_fft);
     launch_window(wsq, n_fft, s);
     for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
         const Blk b = block_of(f0, F, T, n_fft, hop, lead);
@@ -604,9 +448,7 @@ int istft_entry(const char* who, int tr, const float* re, const float* im, int32
         if ((rc = launch_gemm(tr, re, im, table_dev, frames, R, b.nb, F, b.fb0, n_fft, s))) return rc;
         launch_ola(frames, wsq, y, (long long)S * B, T, C, F, b, n_fft, hop, lead, s);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
-    return WUN_OK;
+    return launch_status(who);
 }
 
 int64_t mask_scratch_entry(const char* who, int tr, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {
@@ -617,94 +459,67 @@ int64_t mask_scratch_entry(const char* who, int tr, int32_t S, int64_t n, int32_
     return 2 * (int64_t)(S + 1) * C * nb * (n_fft / 2 + 1) + (int64_t)S * C * nb * n_fft + 2 * (int64_t)n_fft + 2;
 }
 
-int mask_filter_entry(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
-                      int32_t hop, int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream) {
-    if (!mix_tc || !ests || !table_dev || !out || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
-    int rc;
-    if ((rc = check_filter(who, tr, S, n, C, n_fft, hop))) return rc;
-    if (power != 1 && power != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": power must be 1 or 2");
-    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(WUN_ERR_INVALID, std::string(who) + ": eps not positive or not finite");
-    const long long N = (long long)S * n * C;
-    if (overlaps(out, N, mix_tc, n * C) || overlaps(out, N, ests, N))
-        return fail(WUN_ERR_INVALID, std::string(who) + ": out overlaps an input");
-
-    hipStream_t s = (hipStream_t)stream;
-    const int K = n_fft / 2 + 1, lead = n_fft - hop;
-    const long long F = centered_frames(n, n_fft, hop), nbmax = block_frames(F, n_fft, hop);
-    const long long Ee = (long long)S * C * nbmax * K, Ex = (long long)C * nbmax * K;
-    float* ere = scratch; float* eim = ere + Ee; float* xre = eim + Ee; float* xim = xre + Ex; float* frames = xim + Ex;
-    double* wsq = wsq_of(frames, (long long)S * C * nbmax * n_fft);
-    launch_window(wsq, n_fft, s);
-    for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
-        const Blk b = block_of(f0, F, n, n_fft, hop, lead);
-        if (b.t_lo >= b.t_hi) continue;
-        if ((rc = launch_cfwd(tr, ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s))) return rc;
-        // (a short last block packs its spectra: the source stride is C nb K)
-        launch_mask(xre, xim, ere, eim, (long long)C * b.nb * K, S, power, eps, s);
-        if ((rc = launch_gemm(tr, ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s))) return rc;
-        launch_ola(frames, wsq, out, S, n, C, F, b, n_fft, hop, lead, s);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
-    return WUN_OK;
-}
-
 // doubles of the EM statistics: R of every iteration, and the partial sums of one block
 long long wiener_doubles(int32_t S, int32_t C, int32_t n_fft, int32_t iterations) {
     const long long SQK = (long long)S * (C * C + 1) * (n_fft / 2 + 1);
     return iterations ? (iterations + WUN_PF_FRAMES / WUN_WF_CHUNK) * SQK : 0;
 }
 
-template <int CH>
-void launch_apply(const float* xre, const float* xim, float* yre, float* yim, const double* R, long long NK, int32_t S, int K,
-                  int niter, double sq, hipStream_t s) {
-    hipLaunchKernelGGL(wiener_apply_kernel<CH>, dim3((unsigned)((NK + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), dim3(WUN_PF_BLOCK), 0, s, xre,
-                       xim, yre, yim, R, NK, S, K, niter, sq);
+int64_t wiener_scratch_entry(const char* who, int tr, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations) {
+    const int64_t floats = mask_scratch_entry(who, tr, S, n, C, n_fft, hop);
+    if (floats < 0) return floats;
+    if (iterations < 0 || iterations > WUN_WF_MAX_ITERS) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations outside 0..4");
+    return floats + 2 * wiener_doubles(S, C, n_fft, iterations);
 }
 
-template <int CH>
-void launch_stats(const float* yre, const float* yim, double* part, double* stat, int32_t S, int nf, int K, bool first, bool last,
-                  double eps, hipStream_t s) {
+// the kernels of C channels (C is 1 or 2: check_audio)
+void launch_apply(int32_t C, const float* xre, const float* xim, float* yre, float* yim, const double* R, long long NK, int32_t S, int K,
+                  int niter, double sq, hipStream_t s) {
+    hipLaunchKernelGGL(C == 2 ? wiener_apply_kernel<2> : wiener_apply_kernel<1>, dim3((unsigned)((NK + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK)),
+                       dim3(WUN_STFT_BLOCK), 0, s, xre, xim, yre, yim, R, NK, S, K, niter, sq);
+}
+
+void launch_stats(int32_t C, const float* yre, const float* yim, double* part, double* stat, int32_t S, int nf, int K, bool first,
+                  bool last, double eps, hipStream_t s) {
     const int nch = (nf + WUN_WF_CHUNK - 1) / WUN_WF_CHUNK;
     const long long lanes = (long long)S * nch * K;
-    hipLaunchKernelGGL(wiener_stats_kernel<CH>, dim3((unsigned)((lanes + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)), dim3(WUN_PF_BLOCK), 0, s,
-                       yre, yim, part, S, nf, K);
-    hipLaunchKernelGGL(wiener_reduce_kernel<CH * CH + 1>, dim3((unsigned)((S * K + WUN_PF_BLOCK - 1) / WUN_PF_BLOCK)),
-                       dim3(WUN_PF_BLOCK), 0, s, part, stat, S, K, nch, first ? 1 : 0, last ? 1 : 0, eps);
+    hipLaunchKernelGGL(C == 2 ? wiener_stats_kernel<2> : wiener_stats_kernel<1>, dim3((unsigned)((lanes + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK)),
+                       dim3(WUN_STFT_BLOCK), 0, s, yre, yim, part, S, nf, K);
+    hipLaunchKernelGGL(C == 2 ? wiener_reduce_kernel<5> : wiener_reduce_kernel<2>, dim3((unsigned)((S * K + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK)),
+                       dim3(WUN_STFT_BLOCK), 0, s, part, stat, S, K, nch, first ? 1 : 0, last ? 1 : 0, eps);
 }
 
-int64_t wiener_scratch_entry(const char* who, int tr, int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop, int32_t iterations) {
-    int rc;
-    if ((rc = check_filter(who, tr, S, n, C, n_fft, hop))) return rc;
-    if (iterations < 0 || iterations > WUN_WF_MAX_ITERS) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations outside 0..4");
-    return mask_scratch_entry(who, tr, S, n, C, n_fft, hop) + 2 * wiener_doubles(S, C, n_fft, iterations);
-}
-
-int wiener_filter_entry(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
-                        int32_t hop, int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev, float* out,
-                        float* scratch, void* stream) {
+// what the two filters check first, in this order; `eps_name` is the entry's own name of the mask's eps
+int check_mask_args(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                    int32_t hop, int32_t power, float eps, const char* eps_name, const float* table_dev, const float* out,
+                    const float* scratch) {
     if (!mix_tc || !ests || !table_dev || !out || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
     int rc;
     if ((rc = check_filter(who, tr, S, n, C, n_fft, hop))) return rc;
     if (power != 1 && power != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": power must be 1 or 2");
-    if (!(mask_eps > 0.f) || !std::isfinite(mask_eps))
-        return fail(WUN_ERR_INVALID, std::string(who) + ": mask_eps not positive or not finite");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(WUN_ERR_INVALID, std::string(who) + ": " + eps_name + " not positive or not finite");
     const long long N = (long long)S * n * C;
     if (overlaps(out, N, mix_tc, n * C) || overlaps(out, N, ests, N))
         return fail(WUN_ERR_INVALID, std::string(who) + ": out overlaps an input");
-    if (iterations < 0 || iterations > WUN_WF_MAX_ITERS) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations outside 0..4");
-    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(WUN_ERR_INVALID, std::string(who) + ": eps not positive or not finite");
+    return WUN_OK;
+}
 
+// The one body of wun_mask_filter and wun_wiener_filter, arguments checked: `iterations` EM steps between the mask and the
+// inverse.  With none it launches the soft mask alone -- no statistics, no apply -- and never reads em_eps.
+int filter_body(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                int32_t hop, int32_t power, float mask_eps, int32_t iterations, float em_eps, const float* table_dev, float* out,
+                float* scratch, void* stream) {
+    int rc;
     hipStream_t s = (hipStream_t)stream;
     const int K = n_fft / 2 + 1, lead = n_fft - hop;
     const long long F = centered_frames(n, n_fft, hop), nbmax = block_frames(F, n_fft, hop);
     const long long Ee = (long long)S * C * nbmax * K, Ex = (long long)C * nbmax * K;
     float* ere = scratch; float* eim = ere + Ee; float* xre = eim + Ee; float* xim = xre + Ex; float* frames = xim + Ex;
-    double* wsq = wsq_of(frames, (long long)S * C * nbmax * n_fft);
+    double* wsq = f64_tail(frames, (long long)S * C * nbmax * n_fft);
     const long long SQK = (long long)S * (C * C + 1) * K;
     double* R = wsq + n_fft;                                  // [iterations][S][Q][K]
     double* part = R + iterations * SQK;                      // [WUN_PF_FRAMES / WUN_WF_CHUNK][S][Q][K]
-    const double eps_d = (double)eps, sq = std::sqrt(eps_d);
+    const double eps_d = (double)em_eps, sq = std::sqrt(eps_d);
     launch_window(wsq, n_fft, s);
     // pass i < iterations: y^(i) of every frame, block by block (no overlap frames: each frame counts once), into the
     // statistics of R^(i+1); a frame's y^(i) depends on that frame and the R's alone, so nothing track-long is kept
@@ -713,30 +528,38 @@ int wiener_filter_entry(const char* who, int tr, const float* mix_tc, const floa
             const long long f1 = f0 + WUN_PF_FRAMES < F ? f0 + WUN_PF_FRAMES : F, nb = f1 - f0;
             if ((rc = launch_cfwd(tr, ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, nb, f0, nb, 0, s))) return rc;
             launch_mask(xre, xim, ere, eim, (long long)C * nb * K, S, power, mask_eps, s);
-            if (C == 2) {
-                if (it) launch_apply<2>(xre, xim, ere, eim, R, nb * K, S, K, it, sq, s);
-                launch_stats<2>(ere, eim, part, R + it * SQK, S, (int)nb, K, f0 == 0, f1 == F, eps_d, s);
-            } else {
-                if (it) launch_apply<1>(xre, xim, ere, eim, R, nb * K, S, K, it, sq, s);
-                launch_stats<1>(ere, eim, part, R + it * SQK, S, (int)nb, K, f0 == 0, f1 == F, eps_d, s);
-            }
+            if (it) launch_apply(C, xre, xim, ere, eim, R, nb * K, S, K, it, sq, s);
+            launch_stats(C, ere, eim, part, R + it * SQK, S, (int)nb, K, f0 == 0, f1 == F, eps_d, s);
         }
-    // the last pass is wun_mask_filter's loop with all the filters applied between the mask and the inverse
+    // the last pass: forward, mask, all the filters, inverse, overlap-add of every block in which a sample ends
     for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {
         const Blk b = block_of(f0, F, n, n_fft, hop, lead);
         if (b.t_lo >= b.t_hi) continue;
         if ((rc = launch_cfwd(tr, ests, (long long)S * C, ere, eim, mix_tc, C, xre, xim, table_dev, n, C, n_fft, hop, lead, b.nb, b.fb0, b.nb, 0, s))) return rc;
+        // (a short last block packs its spectra: the source stride is C nb K)
         launch_mask(xre, xim, ere, eim, (long long)C * b.nb * K, S, power, mask_eps, s);
-        if (iterations) {
-            if (C == 2) launch_apply<2>(xre, xim, ere, eim, R, b.nb * K, S, K, iterations, sq, s);
-            else launch_apply<1>(xre, xim, ere, eim, R, b.nb * K, S, K, iterations, sq, s);
-        }
+        if (iterations) launch_apply(C, xre, xim, ere, eim, R, b.nb * K, S, K, iterations, sq, s);
         if ((rc = launch_gemm(tr, ere, eim, table_dev, frames, (long long)S * C, b.nb, b.nb, 0, n_fft, s))) return rc;
         launch_ola(frames, wsq, out, S, n, C, F, b, n_fft, hop, lead, s);
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " launch: " + hipGetErrorString(e));
-    return WUN_OK;
+    return launch_status(who);
+}
+
+int mask_filter_entry(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                      int32_t hop, int32_t power, float eps, const float* table_dev, float* out, float* scratch, void* stream) {
+    int rc;
+    if ((rc = check_mask_args(who, tr, mix_tc, ests, S, n, C, n_fft, hop, power, eps, "eps", table_dev, out, scratch))) return rc;
+    return filter_body(who, tr, mix_tc, ests, S, n, C, n_fft, hop, power, eps, 0, 0.f, table_dev, out, scratch, stream);
+}
+
+int wiener_filter_entry(const char* who, int tr, const float* mix_tc, const float* ests, int32_t S, int64_t n, int32_t C, int32_t n_fft,
+                        int32_t hop, int32_t power, float mask_eps, int32_t iterations, float eps, const float* table_dev, float* out,
+                        float* scratch, void* stream) {
+    int rc;
+    if ((rc = check_mask_args(who, tr, mix_tc, ests, S, n, C, n_fft, hop, power, mask_eps, "mask_eps", table_dev, out, scratch))) return rc;
+    if (iterations < 0 || iterations > WUN_WF_MAX_ITERS) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations outside 0..4");
+    if (!(eps > 0.f) || !std::isfinite(eps)) return fail(WUN_ERR_INVALID, std::string(who) + ": eps not positive or not finite");
+    return filter_body(who, tr, mix_tc, ests, S, n, C, n_fft, hop, power, mask_eps, iterations, eps, table_dev, out, scratch, stream);
 }
 
 }  // namespace

@@ -3,11 +3,10 @@
 // respect to the waveform, and the time-domain MSE beside it.
 //
 //   forward    Re / Im[m][k] = sum_n x_m[n] * Cb / Sb[n][k],  m = (row, frame): a GEMM of the frames against the windowed
-//              cos / sin table on the exact-fp32 MFMA (v_mfma_f32_16x16x4_f32).  The frames are gathered from the channel-last
-//              audio while the A tile is staged in LDS (stride C, scalar loads: any 4-byte alignment); no frame matrix in HBM.
+//              cos / sin table -- the forward tile of wun_stft.h, which describes the tile, its staging and its lane layout
 //   loss       |M_est - M_tgt| summed in float64 (fixed blocks of 1024 bins, one tree per block, blocks added in one order);
 //              the same pass turns Re / Im of the estimates into the coefficients sgn * Re / M, sgn * Im / M
-//   backward   dframe[m][n] = sum_k cre[m][k] * Cb[n][k] + cim[m][k] * Sb[n][k]: the transposed GEMM, same MFMA
+//   backward   dframe[m][n] = sum_k cre[m][k] * Cb[n][k] + cim[m][k] * Sb[n][k]: the transposed GEMM, the inverse tile there
 //   gradient   one lane per output float: the MSE term, then per resolution the frames that cover the sample, ascending
 //
 // ONE forward kernel serves wun_stft_magnitude and wun_spectral_loss: the magnitudes the loss takes its signs from are the
@@ -17,28 +16,17 @@
 //
 // Built WITHOUT the packed fp32 VALU instructions (csrc/Makefile NO_PK_FP32): the loss runs between the forward
 // and the backward pass of either compute mode.  Every argument check runs before any GPU work; nothing allocates or synchronises.
-#include "wun_device.h"
-#include "../../include/wun.h"
+#include "wun_stft.h"
 
 #include <cmath>
-#include <string>
 #include <vector>
 
 using namespace wun;
-int fail(int code, const std::string& msg);      // wun_plan.hip: sets wun_last_error(), returns code
 
-#define WUN_STFT_BLOCK 256           // threads per workgroup of every kernel here (4 waves)
-#define WUN_STFT_BM 64               // frames per GEMM workgroup: 2 x 2 waves, each 32 frames x 16 columns
-#define WUN_STFT_BN 32               // columns per GEMM workgroup (forward: bins, re and im each; backward: samples of a frame)
-#define WUN_STFT_KC 32               // reduction indices staged per step
-#define WUN_STFT_PA 36               // LDS pitch of a tile read as [row = lane & 15][k = lane >> 4]: 36 r + k hits 64 banks once
-#define WUN_STFT_PB 48               // LDS pitch of a tile read as [k = lane >> 4][col = lane & 15]: 48 k + c hits 64 banks once
 #define WUN_STFT_ITEMS 4             // elements per lane of the loss / gradient kernels: 1024 per partial, THE summation constant
 #define WUN_SPEC_MAX_RES 8
 
 namespace wun {      // the kernels carry the library's wun:: prefix in profiler output
-
-__device__ __forceinline__ f32x4 stft_mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 struct StftFwdArgs {
     const float* x[2];               // [S, B, T, C]; blockIdx.z picks one (estimates, targets)
@@ -49,77 +37,23 @@ struct StftFwdArgs {
     int F, C, n_fft, hop, K;
 };
 
-// grid: x = tile of 64 frame rows, y = tile of 32 bins, z = signal.  Lane layout of the MFMA (wun_op_mfma_probe): A[row = lane & 15]
-// [k = lane >> 4], B[k = lane >> 4][col = lane & 15], D[row = 4 (lane >> 4) + reg][col = lane & 15].
+// grid: x = tile of 64 frame rows, y = tile of 32 bins, z = signal.  stft_fwd_tile (wun_stft.h) without the bounds check --
+// every frame lies inside its row, which keeps the kernel at 5 waves per SIMD -- and the magnitude as its epilogue.
 __global__ __launch_bounds__(WUN_STFT_BLOCK) void stft_fwd_kernel(StftFwdArgs p) {
-    __shared__ float As[WUN_STFT_BM * WUN_STFT_PA];
-    __shared__ float Bc[WUN_STFT_KC * WUN_STFT_PB];
-    __shared__ float Bs[WUN_STFT_KC * WUN_STFT_PB];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lr = lane & 15, lq = lane >> 4;
-    const int sc = tid & 31, sr = tid >> 5;                  // staging: column and first row of this lane
-    const float* __restrict__ x = p.x[blockIdx.z];
-    const long long m0 = (long long)blockIdx.x * WUN_STFT_BM;
-    const int k0 = (int)blockIdx.y * WUN_STFT_BN;
-    const int wm = (w & 1) * 32, wk = (w >> 1) * 16;
-
-    long long aoff[WUN_STFT_BM / 8];                         // first sample of this lane's frame rows (-1: behind the last)
-#pragma unroll
-    for (int it = 0; it < WUN_STFT_BM / 8; ++it) {
-        const long long m = m0 + sr + 8 * it;
-        aoff[it] = -1;
-        if (m < p.M) {
-            const long long r = m / p.F, f = m - r * p.F;
-            const long long sb = r / p.C, c = r - sb * p.C;
-            aoff[it] = (sb * p.T + f * p.hop) * p.C + c;
-        }
-    }
-    const bool kin = k0 + sc < p.K;
-    const float* __restrict__ tc = p.table + k0 + sc;
-    const float* __restrict__ ts = tc + (long long)p.n_fft * p.K;
-
-    f32x4 are[2], aim[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) { are[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; aim[i] = are[i]; }
-
-    for (int n0 = 0; n0 < p.n_fft; n0 += WUN_STFT_KC) {      // ascending n: the one accumulation order
-        __syncthreads();                                     // the previous step is read
-#pragma unroll
-        for (int it = 0; it < WUN_STFT_BM / 8; ++it)
-            As[(sr + 8 * it) * WUN_STFT_PA + sc] = aoff[it] >= 0 ? x[aoff[it] + (long long)(n0 + sc) * p.C] : 0.f;
-#pragma unroll
-        for (int it = 0; it < WUN_STFT_KC / 8; ++it) {
-            const int nl = sr + 8 * it;
-            const long long idx = (long long)(n0 + nl) * p.K;
-            Bc[nl * WUN_STFT_PB + sc] = kin ? tc[idx] : 0.f;
-            Bs[nl * WUN_STFT_PB + sc] = kin ? ts[idx] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < WUN_STFT_KC / 4; ++s) {
-            const int kq = 4 * s + lq;
-            const float a0 = As[(wm + lr) * WUN_STFT_PA + kq], a1 = As[(wm + 16 + lr) * WUN_STFT_PA + kq];
-            const float bc = Bc[kq * WUN_STFT_PB + wk + lr], bs = Bs[kq * WUN_STFT_PB + wk + lr];
-            are[0] = stft_mfma(a0, bc, are[0]);
-            aim[0] = stft_mfma(a0, bs, aim[0]);
-            are[1] = stft_mfma(a1, bc, are[1]);
-            aim[1] = stft_mfma(a1, bs, aim[1]);
-        }
-    }
-    const int k = k0 + wk + lr;
-    if (k >= p.K) return;
     float* __restrict__ mag = p.mag[blockIdx.z];
     const bool parts = blockIdx.z == 0 && p.re != nullptr;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const long long m = m0 + wm + 16 * i + 4 * lq + r;
-            if (m >= p.M) continue;
-            const float re = are[i][r], im = aim[i][r];
-            mag[m * p.K + k] = sqrtf(re * re + im * im);
+    stft_fwd_tile<false>(
+        p.x[blockIdx.z], p.table, p.M, p.T, p.C, p.n_fft, p.K,
+        [&](long long m, long long& base, long long& t0) {
+            const long long r = m / p.F, f = m - r * p.F;
+            const long long sb = r / p.C, c = r - sb * p.C;
+            base = sb * p.T * p.C + c;
+            t0 = f * p.hop;
+        },
+        [&](long long m, int k, float re, float im) {
+            mag[m * p.K + k] = sqrtf(fmaf(re, re, im * im));     // (spelled out: which product is fused decides the bits)
             if (parts) { p.re[m * p.K + k] = re; p.im[m * p.K + k] = im; }
-        }
+        });
 }
 
 // the fixed tree over the 256 lanes of a block; red[0] holds the sum afterwards
@@ -166,61 +100,10 @@ struct StftBwdArgs {
     int n_fft, K;
 };
 
-// grid: x = tile of 64 frame rows, y = tile of 32 samples of the frame.  The reduction runs over the bins in ascending order, a
-// bin's real part before its imaginary part; bins behind K are staged as zeros.
+// grid: x = tile of 64 frame rows, y = tile of 32 samples of the frame.  stft_inv_tile (wun_stft.h), unscaled, on the dense
+// coefficient rows.
 __global__ __launch_bounds__(WUN_STFT_BLOCK) void stft_bwd_kernel(StftBwdArgs p) {
-    __shared__ float Ar[WUN_STFT_BM * WUN_STFT_PA];
-    __shared__ float Ai[WUN_STFT_BM * WUN_STFT_PA];
-    __shared__ float Bc[WUN_STFT_BN * WUN_STFT_PA];
-    __shared__ float Bs[WUN_STFT_BN * WUN_STFT_PA];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int lr = lane & 15, lq = lane >> 4;
-    const int sc = tid & 31, sr = tid >> 5;
-    const long long m0 = (long long)blockIdx.x * WUN_STFT_BM;
-    const int n0 = (int)blockIdx.y * WUN_STFT_BN;
-    const int wm = (w & 1) * 32, wn = (w >> 1) * 16;
-    const float* __restrict__ tc = p.table;
-    const float* __restrict__ ts = p.table + (long long)p.n_fft * p.K;
-
-    f32x4 acc[2];
-    acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = acc[0];
-    for (int k0 = 0; k0 < p.K; k0 += WUN_STFT_KC) {          // ascending k
-        __syncthreads();
-        const int k = k0 + sc;
-        const bool kin = k < p.K;
-#pragma unroll
-        for (int it = 0; it < WUN_STFT_BM / 8; ++it) {
-            const long long m = m0 + sr + 8 * it;
-            const bool in = kin && m < p.M;
-            Ar[(sr + 8 * it) * WUN_STFT_PA + sc] = in ? p.cre[m * p.K + k] : 0.f;
-            Ai[(sr + 8 * it) * WUN_STFT_PA + sc] = in ? p.cim[m * p.K + k] : 0.f;
-        }
-#pragma unroll
-        for (int it = 0; it < WUN_STFT_BN / 8; ++it) {
-            const int nl = sr + 8 * it;
-            const long long idx = (long long)(n0 + nl) * p.K + k;
-            Bc[nl * WUN_STFT_PA + sc] = kin ? tc[idx] : 0.f;
-            Bs[nl * WUN_STFT_PA + sc] = kin ? ts[idx] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < WUN_STFT_KC / 4; ++s) {
-            const int kq = 4 * s + lq;
-            const float bc = Bc[(wn + lr) * WUN_STFT_PA + kq], bs = Bs[(wn + lr) * WUN_STFT_PA + kq];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                acc[i] = stft_mfma(Ar[(wm + 16 * i + lr) * WUN_STFT_PA + kq], bc, acc[i]);
-                acc[i] = stft_mfma(Ai[(wm + 16 * i + lr) * WUN_STFT_PA + kq], bs, acc[i]);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const long long m = m0 + wm + 16 * i + 4 * lq + r;
-            if (m < p.M) p.dframe[m * p.n_fft + n0 + wn + lr] = acc[i][r];
-        }
+    stft_inv_tile<false>(p.cre, p.cim, p.table, p.dframe, p.M, p.n_fft, p.K, 1.f, 1.f, [&](long long m) { return m * p.K; });
 }
 
 struct SpecGradArgs {
@@ -310,26 +193,9 @@ namespace {
 
 struct Res { int n_fft, hop, K; long long F, M; };
 
-int check_audio(const char* who, int32_t S, int32_t B, int64_t T, int32_t C) {
-    if (S < 1 || B < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": S < 1 or B < 1");
-    if (C != 1 && C != 2) return fail(WUN_ERR_INVALID, std::string(who) + ": C must be 1 or 2");
-    if (T < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": no frames");
-    if ((int64_t)S * B > ((int64_t)1 << 24) || T > ((int64_t)1 << 40) / ((int64_t)S * B * C))
-        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^24 rows or 2^40 floats");
-    return WUN_OK;
-}
-
-int check_res(const char* who, int64_t T, int32_t n_fft, int32_t hop) {
-    if (n_fft < 64 || n_fft > 2048 || (n_fft & (n_fft - 1)))
-        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": n_fft must be a power of two in 64..2048");
-    if (hop < 1 || hop > n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": hop outside 1..n_fft");
-    if (T < n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": fewer frames than n_fft (no padding)");
-    return WUN_OK;
-}
-
 int make_res(const char* who, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, Res* r) {
     int rc;
-    if ((rc = check_res(who, T, n_fft, hop))) return rc;
+    if ((rc = check_res(who, WUN_TR_GEMM, n_fft, hop, T))) return rc;
     r->n_fft = n_fft; r->hop = hop; r->K = n_fft / 2 + 1;
     r->F = 1 + (T - n_fft) / hop;
     r->M = (long long)S * B * C * r->F;
@@ -354,13 +220,13 @@ void launch_fwd(const float* x0, const float* x1, float* mag0, float* mag1, floa
 
 extern "C" int64_t wun_stft_frames(int64_t frames, int32_t n_fft, int32_t hop) {
     int rc;
-    if ((rc = check_res("wun_stft_frames", frames, n_fft, hop))) return rc;
+    if ((rc = check_res("wun_stft_frames", WUN_TR_GEMM, n_fft, hop, frames))) return rc;
     return 1 + (frames - n_fft) / hop;
 }
 
 extern "C" int64_t wun_stft_table_floats(int32_t n_fft) {
     int rc;
-    if ((rc = check_res("wun_stft_table_floats", n_fft, n_fft, 1))) return rc;
+    if ((rc = check_res("wun_stft_table_floats", WUN_TR_GEMM, n_fft, 1))) return rc;
     return 2 * (int64_t)n_fft * (n_fft / 2 + 1);
 }
 
@@ -394,9 +260,7 @@ extern "C" int wun_stft_magnitude(const float* x, int32_t S, int32_t B, int64_t 
     if ((rc = check_audio("wun_stft_magnitude", S, B, T, C))) return rc;
     if ((rc = make_res("wun_stft_magnitude", S, B, T, C, n_fft, hop, &r))) return rc;
     launch_fwd(x, nullptr, mags, nullptr, nullptr, nullptr, table_dev, T, C, r, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string("wun_stft_magnitude launch: ") + hipGetErrorString(e));
-    return WUN_OK;
+    return launch_status("wun_stft_magnitude");
 }
 
 extern "C" int64_t wun_spectral_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
@@ -438,9 +302,7 @@ extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int
     // scratch: per resolution [M_est | M_tgt | Re -> cre | Im -> cim | dframe], then the float64 partials on an 8-byte boundary
     long long floats = 0;
     for (int j = 0; j < nres; ++j) floats += res_floats(res[j]);
-    uintptr_t pa = (uintptr_t)(scratch + floats);
-    pa = (pa + 7) & ~(uintptr_t)7;
-    double* part = (double*)pa;
+    double* part = f64_tail(scratch, floats);
 
     SpecGradArgs g;
     SpecFinishArgs fin;
@@ -477,7 +339,5 @@ extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int
     if (grad) hipLaunchKernelGGL(spec_grad_kernel<true>, ggrid, blk, 0, s, g);
     else hipLaunchKernelGGL(spec_grad_kernel<false>, ggrid, blk, 0, s, g);
     hipLaunchKernelGGL(spec_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string("wun_spectral_loss launch: ") + hipGetErrorString(e));
-    return WUN_OK;
+    return launch_status("wun_spectral_loss");
 }

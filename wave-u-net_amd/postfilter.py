@@ -36,6 +36,7 @@ class SoftMaskFilter(object):
     """ValueError / NotImplementedError at construction for what wun_mask_filter refuses: n_fft must be a power of two in
     64..2048 (64..8192 with transform="fft"), hop a power of two of at most n_fft / 2 (every sample's window-square sum is then at least 0.5), power 1
     (magnitude ratio mask) or 2 (power ratio mask, single-channel Wiener), eps finite and positive."""
+    _KEYS = _KEYS            # what from_config accepts; a subclass adds its own
 
     def __init__(self, n_fft=2048, hop=512, power=2, eps=1e-10, transform="gemm"):
         if transform not in MAX_N_FFT:
@@ -58,15 +59,15 @@ class SoftMaskFilter(object):
 
     @classmethod
     def from_config(cls, spec):
-        """model_config["postfilter"]: None, a SoftMaskFilter, True (the defaults) or a dict with any of `n_fft`, `hop`,
-        `power`, `eps`, `transform`."""
+        """model_config["postfilter"]: None, an instance of the class, True (the defaults) or a dict with any of the class's
+        _KEYS: `n_fft`, `hop`, `power`, `eps`, `transform`, and for WienerFilter `iterations`, `em_eps`."""
         if spec is None or isinstance(spec, cls):
             return spec
         if spec is True:
             return cls()
         if not isinstance(spec, dict):
-            raise ValueError("postfilter must be None, True or a dict with %s, got %r" % (", ".join(_KEYS), spec))
-        unknown = set(spec) - set(_KEYS)
+            raise ValueError("postfilter must be None, True or a dict with %s, got %r" % (", ".join(cls._KEYS), spec))
+        unknown = set(spec) - set(cls._KEYS)
         if unknown:
             raise ValueError("postfilter: unknown keys %s" % sorted(unknown))
         return cls(**spec)
@@ -77,25 +78,14 @@ class SoftMaskFilter(object):
             d["transform"] = "fft"
         return d
 
-    def _entry(self, name):
-        """The library's entry `name` (wun_mask_filter, wun_wiener_filter_scratch_floats, ...) or its FFT twin (wun_mask_filter_fft,
-        wun_wiener_filter_fft_scratch_floats), and the device table that goes with it."""
-        if self.transform != "fft":
-            return getattr(_lib.load(), name), spectral._table
-        stem = name[:-len("_scratch_floats")] if name.endswith("_scratch_floats") else name
-        return getattr(_lib.load(), stem + "_fft" + name[len(stem):]), spectral._fft_table
-
     def scratch_floats(self, S, n, Cn):
-        k = int(self._entry("wun_mask_filter_scratch_floats")[0](int(S), int(n), int(Cn), self.n_fft, self.hop))
-        if k < 0:
-            _lib.check(k)
-        return k
+        return spectral.count(self.transform, "mask_filter_scratch", int(S), int(n), int(Cn), self.n_fft, self.hop)
 
     def run(self, mix, estimates, out, scratch):
         """wun_mask_filter (transform="fft": wun_mask_filter_fft) on the caller's buffers (contiguous float32 device tensors)."""
         S, n, Cn = (int(v) for v in estimates.shape)
         dev = estimates.device
-        entry, table = self._entry("wun_mask_filter")
+        entry, table = spectral.entry(self.transform, "mask_filter")
         with torch.cuda.device(dev):
             _lib.check(entry(
                 mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps,
@@ -199,35 +189,17 @@ class WienerFilter(SoftMaskFilter):
         if not (self.em_eps > 0.0 and np.isfinite(self.em_eps) and np.float32(self.em_eps) > 0 and np.isfinite(np.float32(self.em_eps))):
             raise ValueError("em_eps must be finite and positive in float32, got %r" % (em_eps,))
 
-    @classmethod
-    def from_config(cls, spec):
-        """None, a WienerFilter, True (the defaults) or a dict with any of `n_fft`, `hop`, `power`, `eps`, `iterations`,
-        `em_eps`, `transform`."""
-        if spec is None or isinstance(spec, cls):
-            return spec
-        if spec is True:
-            return cls()
-        if not isinstance(spec, dict):
-            raise ValueError("postfilter must be None, True or a dict with %s, got %r" % (", ".join(cls._KEYS), spec))
-        unknown = set(spec) - set(cls._KEYS)
-        if unknown:
-            raise ValueError("postfilter: unknown keys %s" % sorted(unknown))
-        return cls(**spec)
-
     def spec(self):
         return dict(SoftMaskFilter.spec(self), kind="wiener", iterations=self.iterations, em_eps=self.em_eps)
 
     def scratch_floats(self, S, n, Cn):
-        k = int(self._entry("wun_wiener_filter_scratch_floats")[0](int(S), int(n), int(Cn), self.n_fft, self.hop, self.iterations))
-        if k < 0:
-            _lib.check(k)
-        return k
+        return spectral.count(self.transform, "wiener_filter_scratch", int(S), int(n), int(Cn), self.n_fft, self.hop, self.iterations)
 
     def run(self, mix, estimates, out, scratch):
         """wun_wiener_filter (transform="fft": wun_wiener_filter_fft) on the caller's buffers (contiguous float32 device tensors)."""
         S, n, Cn = (int(v) for v in estimates.shape)
         dev = estimates.device
-        entry, table = self._entry("wun_wiener_filter")
+        entry, table = spectral.entry(self.transform, "wiener_filter")
         with torch.cuda.device(dev):
             _lib.check(entry(
                 mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps, self.iterations,

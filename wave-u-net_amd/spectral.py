@@ -22,62 +22,79 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 MAX_RESOLUTIONS = 8
-_TABLES = {}     # (n_fft, device) -> device tensor holding the windowed cos / sin table [2, n_fft, K]
-_FFT_TABLES = {}  # (n_fft, device) -> device tensor holding the FFT path's table [3, n_fft]
 TRANSFORMS = ("gemm", "fft")
+# (transform, operation) -> the library's entry.  "table": wun_*_table_floats, wun_*_design and the table's leading dimension.
+_ENTRIES = {
+    "gemm": {"table": ("wun_stft_table_floats", "wun_stft_design", 2), "frames": "wun_stft_frames",
+             "centered_frames": "wun_stft_centered_frames", "stft": "wun_stft_complex", "istft": "wun_istft",
+             "istft_scratch": "wun_istft_scratch_floats", "mask_filter": "wun_mask_filter",
+             "mask_filter_scratch": "wun_mask_filter_scratch_floats", "wiener_filter": "wun_wiener_filter",
+             "wiener_filter_scratch": "wun_wiener_filter_scratch_floats"},
+    "fft": {"table": ("wun_fft_table_floats", "wun_fft_design", 3), "frames": "wun_fft_frames",
+            "centered_frames": "wun_fft_centered_frames", "stft": "wun_stft_complex_fft", "istft": "wun_istft_fft",
+            "istft_scratch": "wun_istft_fft_scratch_floats", "mask_filter": "wun_mask_filter_fft",
+            "mask_filter_scratch": "wun_mask_filter_fft_scratch_floats", "wiener_filter": "wun_wiener_filter_fft",
+            "wiener_filter_scratch": "wun_wiener_filter_fft_scratch_floats"},
+}
+_TABLES = {}     # (transform, n_fft, device) -> device tensor holding the transform's table
 
 
-def frames(n, n_fft, hop, transform="gemm"):
-    """Frames of n samples: 1 + (n - n_fft) // hop, no padding (wun_stft_frames; with transform="fft" wun_fft_frames, n_fft up
-    to 8192)."""
+def entry(transform, op):
+    """(the library's entry of operation `op` on `transform`, the function (n_fft, device) -> that transform's device table)."""
+    if transform not in _ENTRIES:
+        raise ValueError("transform must be one of %s, got %r" % (", ".join(TRANSFORMS), transform))
+    return getattr(_lib.load(), _ENTRIES[transform][op]), (_fft_table if transform == "fft" else _table)
+
+
+def _design(transform, n_fft):
+    floats, fill, lead = _ENTRIES[transform]["table"]
     lib = _lib.load()
-    f = int((lib.wun_fft_frames if _transform(transform) else lib.wun_stft_frames)(int(n), int(n_fft), int(hop)))
-    if f < 0:
-        _lib.check(f)
-    return f
+    n = int(getattr(lib, floats)(int(n_fft)))
+    if n < 0:
+        _lib.check(n)
+    table = np.zeros(n, np.float32)
+    _lib.check(getattr(lib, fill)(int(n_fft), table.ctypes.data_as(C.POINTER(C.c_float)), n))
+    return table.reshape(lead, int(n_fft), -1) if transform == "gemm" else table.reshape(lead, int(n_fft))
+
+
+def _device_table(transform, n_fft, device):
+    key = (transform, int(n_fft), str(device))
+    if key not in _TABLES:
+        _TABLES[key] = torch.from_numpy(_design(transform, n_fft)).to(device)
+    return _TABLES[key]
 
 
 def design(n_fft):
     """The fp32 table [2, n_fft, K] as a numpy array: w[n] cos and -w[n] sin of 2 pi n k / n_fft (wun_stft_design)."""
-    lib = _lib.load()
-    n = int(lib.wun_stft_table_floats(int(n_fft)))
-    if n < 0:
-        _lib.check(n)
-    table = np.zeros(n, np.float32)
-    _lib.check(lib.wun_stft_design(int(n_fft), table.ctypes.data_as(C.POINTER(C.c_float)), n))
-    return table.reshape(2, int(n_fft), int(n_fft) // 2 + 1)
-
-
-def _table(n_fft, device):
-    key = (int(n_fft), str(device))
-    if key not in _TABLES:
-        _TABLES[key] = torch.from_numpy(design(n_fft)).to(device)
-    return _TABLES[key]
+    return _design("gemm", n_fft)
 
 
 def fft_design(n_fft):
     """The FFT path's fp32 table [3, n_fft] as a numpy array: cos and -sin of 2 pi t / n_fft, then the periodic Hann window
     (wun_fft_design); n_fft a power of two in 64..8192."""
-    lib = _lib.load()
-    n = int(lib.wun_fft_table_floats(int(n_fft)))
-    if n < 0:
-        _lib.check(n)
-    table = np.zeros(n, np.float32)
-    _lib.check(lib.wun_fft_design(int(n_fft), table.ctypes.data_as(C.POINTER(C.c_float)), n))
-    return table.reshape(3, int(n_fft))
+    return _design("fft", n_fft)
+
+
+def _table(n_fft, device):
+    return _device_table("gemm", n_fft, device)
 
 
 def _fft_table(n_fft, device):
-    key = (int(n_fft), str(device))
-    if key not in _FFT_TABLES:
-        _FFT_TABLES[key] = torch.from_numpy(fft_design(n_fft)).to(device)
-    return _FFT_TABLES[key]
+    return _device_table("fft", n_fft, device)
 
 
-def _transform(transform):
-    if transform not in TRANSFORMS:
-        raise ValueError("transform must be one of %s, got %r" % (", ".join(TRANSFORMS), transform))
-    return transform == "fft"
+def count(transform, op, *args):
+    """A frame or float count of the library; its negative values are error codes."""
+    n = int(entry(transform, op)[0](*args))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
+def frames(n, n_fft, hop, transform="gemm"):
+    """Frames of n samples: 1 + (n - n_fft) // hop, no padding (wun_stft_frames; with transform="fft" wun_fft_frames, n_fft up
+    to 8192)."""
+    return count(transform, "frames", int(n), int(n_fft), int(hop))
 
 
 def _stream(device):
@@ -108,11 +125,7 @@ def stft_magnitude(x, n_fft, hop):
 def centered_frames(n, n_fft, hop, transform="gemm"):
     """Frames of n samples in the centred framing: ceil((n + n_fft - hop) / hop) (wun_stft_centered_frames; with
     transform="fft" wun_fft_centered_frames, n_fft up to 8192)."""
-    lib = _lib.load()
-    f = int((lib.wun_fft_centered_frames if _transform(transform) else lib.wun_stft_centered_frames)(int(n), int(n_fft), int(hop)))
-    if f < 0:
-        _lib.check(f)
-    return f
+    return count(transform, "centered_frames", int(n), int(n_fft), int(hop))
 
 
 def _framing(T, n_fft, hop, centered, transform="gemm"):
@@ -128,17 +141,15 @@ def stft(x, n_fft, hop, centered=False, transform="gemm"):
     framing (no padding, T >= n_fft); centered=True: frame f starts at f hop - (n_fft - hop), zeros outside the track,
     F = centered_frames(T, n_fft, hop), any T >= 1.  transform="gemm" (n_fft up to 2048) or "fft" (wun_stft_complex_fft, up to
     8192): one definition, two summation orders.  One launch on the current stream, no sync."""
-    fft = _transform(transform)
+    fn, table = entry(transform, "stft")
     x = _audio(x, "x")
     S, B, T, Cn = (int(v) for v in x.shape)
     lead, F = _framing(T, n_fft, hop, centered, transform)
     re = torch.empty((S, B, Cn, F, int(n_fft) // 2 + 1), dtype=torch.float32, device=x.device)
     im = torch.empty_like(re)
     with torch.cuda.device(x.device):
-        lib = _lib.load()
-        _lib.check((lib.wun_stft_complex_fft if fft else lib.wun_stft_complex)(
-            x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), lead, F,
-            (_fft_table if fft else _table)(n_fft, x.device).data_ptr(), re.data_ptr(), im.data_ptr(), _stream(x.device)))
+        _lib.check(fn(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), lead, F, table(n_fft, x.device).data_ptr(), re.data_ptr(),
+                      im.data_ptr(), _stream(x.device)))
     return re, im
 
 
@@ -146,7 +157,7 @@ def istft(re, im, length, n_fft, hop, centered=False, transform="gemm"):
     """Audio [S, B, length, C] from re, im [S, B, C, F, K] (wun_istft): the windowed overlap-add of the inverse transforms
     of the frames over the overlap-add of the squared window, 0 where that is below 1e-8.  F must be the frame count of
     `length` in the chosen framing.  transform="fft": wun_istft_fft, n_fft up to 8192.  No sync; not differentiable."""
-    fft = _transform(transform)
+    fn, table = entry(transform, "istft")
     if not (torch.is_tensor(re) and torch.is_tensor(im) and re.is_cuda and im.is_cuda):
         raise ValueError("re and im must be tensors on the GPU (there is no CPU path)")
     if re.dim() != 5 or re.shape != im.shape or re.device != im.device:
@@ -156,17 +167,12 @@ def istft(re, im, length, n_fft, hop, centered=False, transform="gemm"):
     lead, want = _framing(int(length), n_fft, hop, centered, transform)
     if F != want or K != int(n_fft) // 2 + 1:
         raise ValueError("spectra of %d frames x %d bins, expected %d x %d for length %d" % (F, K, want, int(n_fft) // 2 + 1, length))
-    lib = _lib.load()
-    n = int((lib.wun_istft_fft_scratch_floats if fft else lib.wun_istft_scratch_floats)(S, B, int(length), Cn, int(n_fft), int(hop),
-                                                                                    lead, F))
-    if n < 0:
-        _lib.check(n)
+    n = count(transform, "istft_scratch", S, B, int(length), Cn, int(n_fft), int(hop), lead, F)
     scratch = torch.empty(n, dtype=torch.float32, device=re.device)
     y = torch.empty((S, B, int(length), Cn), dtype=torch.float32, device=re.device)
     with torch.cuda.device(re.device):
-        _lib.check((lib.wun_istft_fft if fft else lib.wun_istft)(
-            re.data_ptr(), im.data_ptr(), S, B, int(length), Cn, int(n_fft), int(hop), lead, F,
-            (_fft_table if fft else _table)(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
+        _lib.check(fn(re.data_ptr(), im.data_ptr(), S, B, int(length), Cn, int(n_fft), int(hop), lead, F,
+                      table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
     return y
 
 
