@@ -486,6 +486,51 @@ int     wun_spectral_loss(const float* outputs, const float* targets, int32_t S,
                           float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
                           const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream);
 
+/* ---- the multi-resolution STFT loss: four terms per resolution ----
+ * wun_spectral_loss with L_j = sum_t termweight_t * term_t(j) in place of its one term.  Per resolution j, with the framing,
+ * window, table, row order and [R][F][K] layout above:  E = Re_e + i Im_e the STFT of the estimates, T that of the targets,
+ * Me = |E| and Mt = |T| THE FLOATS wun_stft_magnitude RETURNS, d = Me - Mt in fp32, sg = sgn(d) with sgn(0) = 0.
+ *   mag_l1     : the mean over all R F K bins of |d| -- wun_spectral_loss's L_j.
+ *                coefficient of (Re_e, Im_e) in the gradient: sg * (Re_e, Im_e) / Me, 0 where Me == 0
+ *   log_mag_l1 : the mean over all bins of |log(Me + log_eps) - log(Mt + log_eps)| (fp32 logf); its sign is sg, log being monotone.
+ *                coefficient: sg / (Me + log_eps) * (Re_e, Im_e) / Me, 0 where Me == 0
+ *   sc         : spectral convergence PER SOURCE s, so that a quiet source is not swamped by a loud one:
+ *                D_s = sum d^2 and N_s = sum Mt^2 over the source's B C F K bins, each square formed and summed in float64 from
+ *                the fp32 d and Mt;  SC_s = sqrt(D_s / (N_s + sc_eps));  the term is the mean of SC_s over s.
+ *                coefficient: d / (sqrt(D_s) sqrt(N_s + sc_eps)) / S * (Re_e, Im_e) / Me, 0 where D_s == 0 or Me == 0
+ *   complex_l1 : phase-aware, the mean over all bins of |E - T| = sqrt(fmaf(a, a, b * b)), a = Re_e - Re_t, b = Im_e - Im_t.
+ *                coefficient: (a, b) / |E - T|, 0 where the modulus is 0
+ *   total = mse_weight * MSE + sum_j weights[j] * L_j;  d_outputs is the exact gradient of that total, signs and zero cases
+ *   treated as constants (as wun_spectral_loss treats them).
+ * The term weights must be finite and >= 0, log_eps and sc_eps finite and > 0; one set serves all resolutions.  A term whose
+ * weight is 0 is not computed.  The usual log_eps = 1e-3 and sc_eps = 1.0 are choices, not measurements: log_eps sits above the
+ * fp32 transform's own error on unit-scale audio (about 2e-4 at n_fft 64; it grows with n_fft, so long frames want a larger
+ * one), so that the log of a silent bin is not the log of rounding noise; sc_eps keeps a source that is silent in the whole
+ * batch (N_s == 0) finite: its SC_s is then sqrt(D_s / sc_eps). */
+typedef struct { float mag_l1, log_mag_l1, sc, complex_l1, log_eps, sc_eps; } wun_spectral_terms;
+/* floats of `scratch` for wun_spectral_loss_terms with these sizes and terms: wun_spectral_scratch_floats' per-resolution slice
+ * R F (4 K + n_fft), plus 2 R F K (Re and Im of the targets) when complex_l1 > 0; then as float64 (2 floats each) one partial
+ * per 1024 elements for the MSE and per resolution one per 1024 bins for each of mag_l1, log_mag_l1, complex_l1 in use, and
+ * when sc > 0 per resolution 2 S ceil(B C F K / 1024) partials and 3 S per-source scalars; 2 floats of alignment room.
+ * Negative wun_status as wun_spectral_loss_terms for the same arguments. */
+int64_t wun_spectral_terms_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                          const int32_t* hop, const wun_spectral_terms* terms);
+/* wun_spectral_loss's arguments and contract (the caller's buffers, no allocation, no sync, no atomics, every check before any
+ * GPU work, d_outputs may be NULL, any 4-byte alignment, both compute modes, bits independent of the grid, the scratch
+ * contents, the alignment and repetition), plus `terms` (HOST).  The checks of wun_spectral_loss come first, in its order; then
+ * WUN_ERR_INVALID for a null `terms`, a negative or non-finite term weight, or an eps that is not finite and > 0.
+ *   losses : device float32 [2 + 5 nres]: [0] = total, [1] = MSE, [2 + j] = L_j, [2 + nres + 4 j + t] = the unweighted term t
+ *            of resolution j, t in the order mag_l1, log_mag_l1, sc, complex_l1 (0 for a term whose weight is 0)
+ *   scratch: wun_spectral_terms_scratch_floats floats for the same terms
+ * The means of mag_l1, log_mag_l1 and complex_l1 are summed as wun_spectral_loss sums (1024 consecutive bins per float64
+ * partial, one tree, the partials strided over 64 lanes); the sums of sc run over 1024-bin blocks of each source's own bins, so
+ * a source's D_s and N_s do not depend on the other sources.  With terms = {1, 0, 0, 0, ..} the first 2 + nres losses and
+ * d_outputs are wun_spectral_loss's, bit for bit. */
+int     wun_spectral_loss_terms(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                                const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs, float* losses,
+                                float* scratch, void* stream);
+
 /* ---- inverse STFT and soft-mask post-filter ----
  * The synthesis half of the spectral section, on the same table, and the post-filter built on the pair: the estimates of a
  * track are masked against the mixture's own STFT, so they share its phase and sum back to it.

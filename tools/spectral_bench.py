@@ -6,11 +6,15 @@ Kernel arms (HIP events on the launch stream around `iters` back-to-back calls, 
   magnitude     wun_stft_magnitude of the outputs [2, 16, 16389, 1] (32 rows x 21 frames x 513 bins)
   loss_only     wun_spectral_loss, d_outputs = NULL (both signals' magnitudes, the float64 sums)
   loss_grad     wun_spectral_loss with d_outputs (plus the transposed GEMM and the overlap-add)
+  terms_mag     wun_spectral_loss_terms with d_outputs, mag_l1 alone: loss_grad's work through the four-term entry
+  terms_sc_log  ... sc + log_mag_l1 (the per-source sums pass and its one-block reduction before the coefficient pass)
+  terms_all     ... all four terms (the forward also stores Re / Im of the targets)
 Trainer arms (one optimizer step each, same batch):
   step_mse      Trainer(batch 16): the time-domain MSE (wun_loss_backward)
   step_spectral Trainer(batch 16, spectral_loss = 1024 / 768, mse_weight 1): wun_spectral_loss, then wun_backward
 
-  python tools/spectral_bench.py [--rounds 9] [--iters 10] [--out profiles/spectral_bench.json]
+  python tools/spectral_bench.py [--rounds 9] [--iters 10] [--out profiles/spectral_bench.json] [--arms a,b,...]
+      --arms loss_grad,terms_mag,terms_sc_log,terms_all --out profiles/spectral_terms_bench.json: the four-term entry beside the old
       the arms interleaved in ONE process for `rounds` rounds (order rotated each round); per arm the median, the minimum and
       the maximum over the rounds of (time / iters).  One JSON line on stdout, and the same in --out.
 """
@@ -24,7 +28,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-ARMS = ["magnitude", "loss_only", "loss_grad", "step_mse", "step_spectral"]
+ARMS = ["magnitude", "loss_only", "loss_grad", "terms_mag", "terms_sc_log", "terms_all", "step_mse", "step_spectral"]
+TERMS = {"terms_mag": {"mag_l1": 1.0}, "terms_sc_log": {"sc": 1.0, "log_mag_l1": 1.0},
+         "terms_all": {"mag_l1": 1.0, "log_mag_l1": 1.0, "sc": 1.0, "complex_l1": 1.0}}
 RES = [(1024, 768)]
 
 
@@ -48,6 +54,8 @@ def setup():
     scratch = loss._scratch_for(outs)
     losses = torch.empty(3, dtype=torch.float32, device=outs.device)
     d_outs = torch.empty_like(outs)
+    tloss = {a: spectral.SpectralLoss(RES, mse_weight=1.0, terms=t, log_eps=1.0) for a, t in TERMS.items()}   # (n_fft 1024: 5.14)
+    tbuf = {a: (torch.empty(l.num_losses, dtype=torch.float32, device=outs.device), l._scratch_for(outs)) for a, l in tloss.items()}
 
     def step(arm):
         if arm == "magnitude":
@@ -56,6 +64,8 @@ def setup():
             loss.run(outs, tg, None, losses, scratch)
         elif arm == "loss_grad":
             loss.run(outs, tg, d_outs, losses, scratch)
+        elif arm in tloss:
+            tloss[arm].run(outs, tg, d_outs, *tbuf[arm])
         elif arm == "step_mse":
             tr_mse.step(mix, targets)
         else:
@@ -63,15 +73,15 @@ def setup():
     return torch, step, tuple(outs.shape)
 
 
-def timed(rounds, iters, out):
+def timed(rounds, iters, out, arms):
     torch, step, shape = setup()
-    for arm in ARMS:                                              # warm-up
+    for arm in arms:                                              # warm-up
         for _ in range(3):
             step(arm)
     torch.cuda.synchronize()
-    allr = {a: [] for a in ARMS}
+    allr = {a: [] for a in arms}
     for r in range(rounds):
-        order = ARMS[r % len(ARMS):] + ARMS[:r % len(ARMS)]
+        order = arms[r % len(arms):] + arms[:r % len(arms)]
         for arm in order:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -82,8 +92,8 @@ def timed(rounds, iters, out):
             allr[arm].append(round(e0.elapsed_time(e1) / iters, 4))
     res = {"what": "ms per call / per optimizer step; arms interleaved in one process", "outputs_shape": shape,
            "resolutions": RES, "rounds": rounds, "iters": iters,
-           "median_ms": {a: round(statistics.median(allr[a]), 4) for a in ARMS},
-           "min_ms": {a: min(allr[a]) for a in ARMS}, "max_ms": {a: max(allr[a]) for a in ARMS}, "rounds_ms": allr}
+           "median_ms": {a: round(statistics.median(allr[a]), 4) for a in arms},
+           "min_ms": {a: min(allr[a]) for a in arms}, "max_ms": {a: max(allr[a]) for a in arms}, "rounds_ms": allr}
     line = json.dumps(res)
     print(line)
     if out:
@@ -97,8 +107,12 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--arms", default=",".join(ARMS), help="comma-separated subset of %s" % ", ".join(ARMS))
     a = ap.parse_args()
-    timed(a.rounds, a.iters, a.out)
+    arms = a.arms.split(",")
+    if not arms or any(x not in ARMS for x in arms):
+        ap.error("--arms must name some of %s" % ", ".join(ARMS))
+    timed(a.rounds, a.iters, a.out, arms)
 
 
 if __name__ == "__main__":

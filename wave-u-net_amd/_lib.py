@@ -32,6 +32,10 @@ class WunTensorInfo(C.Structure):
                 ("shape", C.c_int64 * 4)]
 
 
+class WunSpectralTerms(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("mag_l1", "log_mag_l1", "sc", "complex_l1", "log_eps", "sc_eps")]
+
+
 _P = C.c_void_p
 _SIGS = {
     "wun_get_padding": (C.c_int, [C.POINTER(WunConfig), C.c_int64, C.POINTER(C.c_int64),
@@ -83,6 +87,11 @@ _SIGS = {
                                                 C.POINTER(C.c_int32)]),
     "wun_spectral_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_void_p), _P, _P, _P, _P]),
+    "wun_spectral_terms_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                      C.POINTER(C.c_int32), C.POINTER(WunSpectralTerms)]),
+    "wun_spectral_loss_terms": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                          C.POINTER(WunSpectralTerms), C.POINTER(C.c_void_p), _P, _P, _P, _P]),
     "wun_stft_centered_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "wun_stft_complex": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                    _P, _P, _P, _P]),

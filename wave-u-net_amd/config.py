@@ -39,7 +39,8 @@ EXTENSION_DEFAULTS = {
     "skip_nonfinite_steps": False,    # training.Trainer: skip an update whose gradient norm is not finite
     "checkpoint_format": "npz",       # training.train: "npz" or "tf"
     # training.Trainer / spectral.SpectralLoss: None = the reference's MSE; else {"resolutions": [[n_fft, hop], ...],
-    # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60)
+    # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60);
+    # with "terms": {"mag_l1" | "log_mag_l1" | "sc" | "complex_l1": weight} (and "log_eps", "sc_eps") the multi-resolution STFT loss
     "spectral_loss": None,
     # evaluate.separate_track / postfilter.SoftMaskFilter: None = the estimates as the network gives them; else
     # {"n_fft": 2048, "hop": 512, "power": 2, "eps": 1e-10} (any subset): the soft-mask filter against the mix's STFT; with

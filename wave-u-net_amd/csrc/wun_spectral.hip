@@ -9,6 +9,19 @@
 //   backward   dframe[m][n] = sum_k cre[m][k] * Cb[n][k] + cim[m][k] * Sb[n][k]: the transposed GEMM, the inverse tile there
 //   gradient   one lane per output float: the MSE term, then per resolution the frames that cover the sample, ascending
 //
+//   terms      wun_spectral_loss_terms puts four terms where the loss pass has one: per bin of resolution j, with
+//              E = Re_e + i Im_e and T the STFTs of estimates and targets, Me = |E|, Mt = |T| (the floats of wun_stft_magnitude),
+//              d = Me - Mt in fp32, sg = sgn(d), sgn(0) = 0:
+//                mag_l1      mean |d|                                            coefficient sg (Re_e, Im_e) / Me
+//                log_mag_l1  mean |log(Me + log_eps) - log(Mt + log_eps)|        sg / (Me + log_eps) (Re_e, Im_e) / Me
+//                sc          mean over the sources s of sqrt(D_s / (N_s + sc_eps)), D_s = sum d^2, N_s = sum Mt^2 over the
+//                            source's B C F K bins, in float64        d / (sqrt(D_s) sqrt(N_s + sc_eps)) / S (Re_e, Im_e) / Me
+//                complex_l1  mean |E - T| = sqrt(fmaf(a, a, b b)), a = Re_e - Re_t, b = Im_e - Im_t        (a, b) / |E - T|
+//              every coefficient 0 where its denominator is (Me == 0, D_s == 0, |E - T| == 0); signs and zero cases are
+//              constants of the gradient.  L_j = sum_t termweight_t term_t(j).  The three means keep the loss pass's partition
+//              (1024 consecutive bins per partial); the per-source sums run over 1024-bin blocks of EACH SOURCE's own range
+//              first, one block then adds them source by source, and only then the coefficients are formed.
+//
 // ONE forward kernel serves wun_stft_magnitude and wun_spectral_loss: the magnitudes the loss takes its signs from are the
 // floats wun_stft_magnitude returns.  Every reduction index runs in ascending order inside one lane's accumulator, whatever the
 // tile a frame falls in: the bits of a row do not depend on the batch around it, the grid, the scratch contents or pointer
@@ -187,6 +200,182 @@ __global__ __launch_bounds__(64 * (1 + WUN_SPEC_MAX_RES)) void spec_finish_kerne
     }
 }
 
+// ---- wun_spectral_loss_terms: the loss pass with four terms (the definitions are in the header comment) ----
+
+struct StftFwdPartsArgs {            // StftFwdArgs with Re and Im of BOTH signals (complex_l1 needs the targets')
+    const float* x[2];
+    float* mag[2]; float* re[2]; float* im[2];
+    const float* table;
+    long long T, M;
+    int F, C, n_fft, hop, K;
+};
+
+// stft_fwd_kernel's grid, tile and epilogue -- the magnitudes are the same floats -- storing Re and Im of either signal
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void stft_fwd_parts_kernel(StftFwdPartsArgs p) {
+    float* __restrict__ mag = p.mag[blockIdx.z];
+    float* __restrict__ pre = p.re[blockIdx.z];
+    float* __restrict__ pim = p.im[blockIdx.z];
+    stft_fwd_tile<false>(
+        p.x[blockIdx.z], p.table, p.M, p.T, p.C, p.n_fft, p.K,
+        [&](long long m, long long& base, long long& t0) {
+            const long long r = m / p.F, f = m - r * p.F;
+            const long long sb = r / p.C, c = r - sb * p.C;
+            base = sb * p.T * p.C + c;
+            t0 = f * p.hop;
+        },
+        [&](long long m, int k, float re, float im) {
+            mag[m * p.K + k] = sqrtf(fmaf(re, re, im * im));
+            pre[m * p.K + k] = re; pim[m * p.K + k] = im;
+        });
+}
+
+// sc, first pass: block b = (source s = b / ps, 1024-bin block b - s ps of THAT source's Es bins) -> part[2 b] = sum d^2,
+// part[2 b + 1] = sum Mt^2, every square formed and added in float64.  No block crosses a source boundary.
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_sc_sums_kernel(const float* __restrict__ me, const float* __restrict__ mt,
+                                                                      double* __restrict__ part, long long Es, long long ps) {
+    __shared__ double red[2][WUN_STFT_BLOCK];
+    const int tid = threadIdx.x;
+    const long long s = (long long)blockIdx.x / ps, pb = (long long)blockIdx.x - s * ps;
+    double D = 0.0, N = 0.0;
+#pragma unroll
+    for (int it = 0; it < WUN_STFT_ITEMS; ++it) {
+        const long long el = (pb * WUN_STFT_ITEMS + it) * WUN_STFT_BLOCK + tid;
+        if (el >= Es) continue;
+        const float t = mt[s * Es + el];
+        const float d = me[s * Es + el] - t;
+        D += (double)d * (double)d;
+        N += (double)t * (double)t;
+    }
+    D = stft_block_sum(red[0], D, tid);
+    N = stft_block_sum(red[1], N, tid);
+    if (tid == 0) { part[2 * (long long)blockIdx.x] = D; part[2 * (long long)blockIdx.x + 1] = N; }
+}
+
+// sc, second pass, ONE block: source after source, lane l adds the source's partials l, l + 256, ... in ascending order and one
+// tree adds the lanes.  src[3 s] = D_s, [3 s + 1] = N_s, [3 s + 2] = Es / (sqrt(D_s) sqrt(N_s + sc_eps)), 0 where D_s == 0: the
+// coefficient's factor, pre-scaled by R F K / S so that spec_grad_kernel's scale of the resolution stays weight / (R F K).
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_sc_reduce_kernel(const double* __restrict__ part, double* __restrict__ src,
+                                                                        int S, long long ps, double es, float sc_eps) {
+    __shared__ double red[2][WUN_STFT_BLOCK];
+    const int tid = threadIdx.x;
+    for (int s = 0; s < S; ++s) {
+        double D = 0.0, N = 0.0;
+        for (long long i = tid; i < ps; i += WUN_STFT_BLOCK) { D += part[2 * (s * ps + i)]; N += part[2 * (s * ps + i) + 1]; }
+        D = stft_block_sum(red[0], D, tid);
+        N = stft_block_sum(red[1], N, tid);
+        if (tid == 0) {
+            src[3 * s] = D; src[3 * s + 1] = N;
+            src[3 * s + 2] = D > 0.0 ? es / (sqrt(D) * sqrt(N + (double)sc_eps)) : 0.0;
+        }
+        __syncthreads();                                     // red[0] is read by every lane before the next source writes it
+    }
+}
+
+struct SpecTermsArgs {
+    const float* me; const float* mt;        // [M][K]
+    float* re; float* im;                    // Re, Im of the estimates; with grad the coefficients replace them in place
+    const float* ret; const float* imt;      // Re, Im of the targets (complex_l1 only)
+    double* part[3];                         // [ceil(E / 1024)] each: mag_l1, log_mag_l1, complex_l1 (unused without the term)
+    const double* src;                       // [S][3] of spec_sc_reduce_kernel (sc only)
+    long long E, Es;                         // bins in all, bins per source
+    float w_mag, w_log, w_sc, w_cx, log_eps;
+    int grad;
+};
+
+// spec_l1_kernel with the four terms: 1024 bins per block, the same partition and tree for each of the three means, and the
+// coefficient of (Re_e, Im_e) / Me summed over the terms before the one division -- with mag_l1 = 1 alone, spec_l1_kernel's bits.
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_terms_kernel(SpecTermsArgs p) {
+    __shared__ double red[3][WUN_STFT_BLOCK];
+    const int tid = threadIdx.x;
+    const bool mag = p.w_mag > 0.f, lg = p.w_log > 0.f, sc = p.w_sc > 0.f, cx = p.w_cx > 0.f;
+    double am = 0.0, al = 0.0, ac = 0.0;
+#pragma unroll
+    for (int it = 0; it < WUN_STFT_ITEMS; ++it) {
+        const long long e = ((long long)blockIdx.x * WUN_STFT_ITEMS + it) * WUN_STFT_BLOCK + tid;
+        if (e >= p.E) continue;
+        const float a = p.me[e], t = p.mt[e];
+        const float d = a - t;
+        const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        float q = 0.f;                                       // the coefficient of (Re_e, Im_e) / Me
+        if (mag) { am += (double)fabsf(d); q = p.w_mag * sg; }
+        if (lg) {
+            const float ea = a + p.log_eps, et = t + p.log_eps;
+            al += (double)fabsf(logf(ea) - logf(et));
+            q += p.w_log * (sg / ea);
+        }
+        if (sc) q += p.w_sc * (d * (float)p.src[3 * (e / p.Es) + 2]);
+        float cr = 0.f, ci = 0.f;
+        if (p.grad && q != 0.f && a > 0.f) { cr = q * p.re[e] / a; ci = q * p.im[e] / a; }
+        if (cx) {
+            const float x = p.re[e] - p.ret[e], y = p.im[e] - p.imt[e];
+            const float m = sqrtf(fmaf(x, x, y * y));        // (spelled out, as the forward epilogue)
+            ac += (double)m;
+            if (p.grad && m > 0.f) { cr += p.w_cx * (x / m); ci += p.w_cx * (y / m); }
+        }
+        if (p.grad) { p.re[e] = cr; p.im[e] = ci; }
+    }
+    if (mag) { const double s = stft_block_sum(red[0], am, tid); if (tid == 0) p.part[0][blockIdx.x] = s; }
+    if (lg) { const double s = stft_block_sum(red[1], al, tid); if (tid == 0) p.part[1][blockIdx.x] = s; }
+    if (cx) { const double s = stft_block_sum(red[2], ac, tid); if (tid == 0) p.part[2][blockIdx.x] = s; }
+}
+
+struct SpecTermsFinishArgs {
+    const double* part[1 + WUN_SPEC_MAX_RES][3]; // slot 0: MSE (sum 0 only); slot 1 + j: mag_l1, log_mag_l1, complex_l1 of resolution j
+    long long nparts[1 + WUN_SPEC_MAX_RES][3];   // 0: the sum is not taken
+    double count[1 + WUN_SPEC_MAX_RES];
+    float weight[1 + WUN_SPEC_MAX_RES];
+    const double* src[WUN_SPEC_MAX_RES];         // [S][3] per resolution (sc only)
+    float w[4], sc_eps;                          // term weights in the order of the losses: mag_l1, log_mag_l1, sc, complex_l1
+    int S, nres;
+    float* losses;                               // [2 + 5 nres]
+};
+
+// spec_finish_kernel over the new slots: one wave per slot takes its (up to) three sums one after the other, each as there --
+// lane l adds the partials l, l + 64, ... in ascending order, one tree over the 64 lanes -- and thread 0 forms the terms, L_j
+// and the total in slot order.
+__global__ __launch_bounds__(64 * (1 + WUN_SPEC_MAX_RES)) void spec_terms_finish_kernel(SpecTermsFinishArgs p) {
+    __shared__ double red[1 + WUN_SPEC_MAX_RES][64];
+    __shared__ double sums[1 + WUN_SPEC_MAX_RES][3];
+    const int slot = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int t = 0; t < 3; ++t) {
+        double s = 0.0;
+        if (slot <= p.nres)
+            for (long long i = lane; i < p.nparts[slot][t]; i += 64) s += p.part[slot][t][i];
+        red[slot][lane] = s;
+        __syncthreads();
+        for (int h = 32; h > 0; h >>= 1) {
+            if (lane < h) red[slot][lane] += red[slot][lane + h];
+            __syncthreads();
+        }
+        if (lane == 0) sums[slot][t] = red[slot][0];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double mse = sums[0][0] / p.count[0];
+        p.losses[1] = (float)mse;
+        double total = (double)p.weight[0] * mse;
+        for (int j = 0; j < p.nres; ++j) {
+            double term[4] = {0.0, 0.0, 0.0, 0.0};
+            if (p.w[0] > 0.f) term[0] = sums[1 + j][0] / p.count[1 + j];
+            if (p.w[1] > 0.f) term[1] = sums[1 + j][1] / p.count[1 + j];
+            if (p.w[2] > 0.f) {
+                double a = 0.0;
+                for (int s = 0; s < p.S; ++s) a += sqrt(p.src[j][3 * s] / (p.src[j][3 * s + 1] + (double)p.sc_eps));
+                term[2] = a / (double)p.S;
+            }
+            if (p.w[3] > 0.f) term[3] = sums[1 + j][2] / p.count[1 + j];
+            double L = 0.0;
+            for (int t = 0; t < 4; ++t) {
+                p.losses[2 + p.nres + 4 * j + t] = (float)term[t];
+                if (p.w[t] > 0.f) L += (double)p.w[t] * term[t];
+            }
+            p.losses[2 + j] = (float)L;
+            total += (double)p.weight[1 + j] * L;
+        }
+        p.losses[0] = (float)total;
+    }
+}
+
 }  // namespace wun
 
 namespace {
@@ -206,6 +395,44 @@ int make_res(const char* who, int32_t S, int32_t B, int64_t T, int32_t C, int32_
 long long parts_of(long long n) { return (n + WUN_STFT_BLOCK * WUN_STFT_ITEMS - 1) / (WUN_STFT_BLOCK * WUN_STFT_ITEMS); }
 // floats of one resolution's slice of the scratch: magnitudes of both signals, Re and Im of the estimates, the frame gradients
 long long res_floats(const Res& r) { return 4 * r.M * r.K + r.M * r.n_fft; }
+
+// the argument checks of the two loss entries, in one order; fills res[0 .. nres)
+int check_loss(const char* who, const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+               float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+               const float* const* tables_dev, const float* losses, const float* scratch, Res* res) {
+    const std::string w(who);
+    if (!outputs || !targets || !losses || !scratch) return fail(WUN_ERR_INVALID, w + ": null argument");
+    int rc;
+    if ((rc = check_audio(who, S, B, Tout, C))) return rc;
+    if (nres < 0 || nres > WUN_SPEC_MAX_RES) return fail(WUN_ERR_INVALID, w + ": nres outside 0..8");
+    if (nres > 0 && (!n_fft || !hop || !weights || !tables_dev)) return fail(WUN_ERR_INVALID, w + ": null resolution table");
+    if (!(mse_weight >= 0.f) || !std::isfinite(mse_weight)) return fail(WUN_ERR_INVALID, w + ": mse_weight negative or not finite");
+    for (int j = 0; j < nres; ++j) {
+        if ((rc = make_res(who, S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
+        if (!(weights[j] >= 0.f) || !std::isfinite(weights[j])) return fail(WUN_ERR_INVALID, w + ": a weight negative or not finite");
+        if (!tables_dev[j]) return fail(WUN_ERR_INVALID, w + ": null table");
+    }
+    return WUN_OK;
+}
+
+int check_terms(const char* who, const wun_spectral_terms* t) {
+    const std::string w(who);
+    if (!t) return fail(WUN_ERR_INVALID, w + ": null terms");
+    for (float x : {t->mag_l1, t->log_mag_l1, t->sc, t->complex_l1})
+        if (!(x >= 0.f) || !std::isfinite(x)) return fail(WUN_ERR_INVALID, w + ": a term weight negative or not finite");
+    if (!(t->log_eps > 0.f) || !std::isfinite(t->log_eps)) return fail(WUN_ERR_INVALID, w + ": log_eps must be finite and > 0");
+    if (!(t->sc_eps > 0.f) || !std::isfinite(t->sc_eps)) return fail(WUN_ERR_INVALID, w + ": sc_eps must be finite and > 0");
+    return WUN_OK;
+}
+
+// what wun_spectral_loss_terms adds to a resolution: floats behind its slice (Re and Im of the targets), and float64s behind the
+// partials of the MSE -- one run of partials per mean term in use, then for sc [S][ps][2] partials and [S][3] scalars
+long long terms_floats(const Res& r, const wun_spectral_terms& t) { return t.complex_l1 > 0.f ? 2 * r.M * r.K : 0; }
+long long terms_doubles(const Res& r, int32_t S, const wun_spectral_terms& t) {
+    const long long E = r.M * r.K;
+    const int means = (t.mag_l1 > 0.f) + (t.log_mag_l1 > 0.f) + (t.complex_l1 > 0.f);
+    return means * parts_of(E) + (t.sc > 0.f ? 2 * S * parts_of(E / S) + 3 * (long long)S : 0);
+}
 
 void launch_fwd(const float* x0, const float* x1, float* mag0, float* mag1, float* re, float* im, const float* table, int64_t T,
                 int32_t C, const Res& r, hipStream_t s) {
@@ -282,18 +509,11 @@ extern "C" int64_t wun_spectral_scratch_floats(int32_t S, int32_t B, int64_t Tou
 extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
                                  float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
                                  const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream) {
-    if (!outputs || !targets || !losses || !scratch) return fail(WUN_ERR_INVALID, "wun_spectral_loss: null argument");
     int rc;
-    if ((rc = check_audio("wun_spectral_loss", S, B, Tout, C))) return rc;
-    if (nres < 0 || nres > WUN_SPEC_MAX_RES) return fail(WUN_ERR_INVALID, "wun_spectral_loss: nres outside 0..8");
-    if (nres > 0 && (!n_fft || !hop || !weights || !tables_dev)) return fail(WUN_ERR_INVALID, "wun_spectral_loss: null resolution table");
-    if (!(mse_weight >= 0.f) || !std::isfinite(mse_weight)) return fail(WUN_ERR_INVALID, "wun_spectral_loss: mse_weight negative or not finite");
     Res res[WUN_SPEC_MAX_RES];
-    for (int j = 0; j < nres; ++j) {
-        if ((rc = make_res("wun_spectral_loss", S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
-        if (!(weights[j] >= 0.f) || !std::isfinite(weights[j])) return fail(WUN_ERR_INVALID, "wun_spectral_loss: a weight negative or not finite");
-        if (!tables_dev[j]) return fail(WUN_ERR_INVALID, "wun_spectral_loss: null table");
-    }
+    if ((rc = check_loss("wun_spectral_loss", outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights, tables_dev, losses,
+                         scratch, res)))
+        return rc;
 
     hipStream_t s = (hipStream_t)stream;
     const dim3 blk(WUN_STFT_BLOCK);
@@ -340,4 +560,116 @@ extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int
     else hipLaunchKernelGGL(spec_grad_kernel<false>, ggrid, blk, 0, s, g);
     hipLaunchKernelGGL(spec_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin);
     return launch_status("wun_spectral_loss");
+}
+
+extern "C" int64_t wun_spectral_terms_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                                     const int32_t* hop, const wun_spectral_terms* terms) {
+    const char* who = "wun_spectral_terms_scratch_floats";
+    int rc;
+    if ((rc = check_audio(who, S, B, Tout, C))) return rc;
+    if (nres < 0 || nres > WUN_SPEC_MAX_RES) return fail(WUN_ERR_INVALID, std::string(who) + ": nres outside 0..8");
+    if (nres > 0 && (!n_fft || !hop)) return fail(WUN_ERR_INVALID, std::string(who) + ": null resolution table");
+    Res res[WUN_SPEC_MAX_RES];
+    for (int j = 0; j < nres; ++j)
+        if ((rc = make_res(who, S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
+    if ((rc = check_terms(who, terms))) return rc;
+    long long floats = 0, doubles = parts_of((long long)S * B * Tout * C);
+    for (int j = 0; j < nres; ++j) {
+        floats += res_floats(res[j]) + terms_floats(res[j], *terms);
+        doubles += terms_doubles(res[j], S, *terms);
+    }
+    return floats + 2 * doubles + 2;
+}
+
+extern "C" int wun_spectral_loss_terms(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                       float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop,
+                                       const float* weights, const wun_spectral_terms* terms, const float* const* tables_dev,
+                                       float* d_outputs, float* losses, float* scratch, void* stream) {
+    const char* who = "wun_spectral_loss_terms";
+    int rc;
+    Res res[WUN_SPEC_MAX_RES];
+    if ((rc = check_loss(who, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights, tables_dev, losses, scratch, res)))
+        return rc;
+    if ((rc = check_terms(who, terms))) return rc;
+    const wun_spectral_terms tw = *terms;
+
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 blk(WUN_STFT_BLOCK);
+    const long long R = (long long)S * B * C, N = R * Tout;
+    const bool grad = d_outputs != nullptr, cx = tw.complex_l1 > 0.f, sc = tw.sc > 0.f;
+    // scratch: per resolution [M_est | M_tgt | Re -> cre | Im -> cim | dframe | Re_tgt | Im_tgt (complex_l1 only)], then on an
+    // 8-byte boundary the float64s: the MSE's partials, then per resolution those of terms_doubles
+    long long floats = 0;
+    for (int j = 0; j < nres; ++j) floats += res_floats(res[j]) + terms_floats(res[j], tw);
+    double* part = f64_tail(scratch, floats);
+
+    SpecGradArgs g;
+    SpecTermsFinishArgs fin;
+    g.out = outputs; g.tgt = targets; g.dout = d_outputs; g.T = Tout; g.N = N; g.C = C; g.nres = nres;
+    g.cm = (float)((double)mse_weight * 2.0 / (double)N);
+    fin.nres = nres; fin.losses = losses; fin.S = S; fin.sc_eps = tw.sc_eps;
+    fin.w[0] = tw.mag_l1; fin.w[1] = tw.log_mag_l1; fin.w[2] = tw.sc; fin.w[3] = tw.complex_l1;
+    for (int k = 0; k <= WUN_SPEC_MAX_RES; ++k) {
+        for (int t = 0; t < 3; ++t) { fin.part[k][t] = part; fin.nparts[k][t] = 0; }
+        fin.count[k] = 1.0; fin.weight[k] = 0.f;
+    }
+    for (int j = 0; j < WUN_SPEC_MAX_RES; ++j) {
+        g.n_fft[j] = 64; g.hop[j] = 64; g.F[j] = 0; g.scale[j] = 0.f; g.dframe[j] = nullptr; fin.src[j] = part;
+    }
+    g.part = part;
+    fin.nparts[0][0] = parts_of(N); fin.count[0] = (double)N; fin.weight[0] = mse_weight;
+    double* pnext = part + parts_of(N);
+
+    float* base = scratch;
+    for (int j = 0; j < nres; ++j) {
+        const Res& r = res[j];
+        const long long E = r.M * r.K, Es = E / S, np = parts_of(E);
+        float* me = base; float* mt = base + E; float* re = base + 2 * E; float* im = base + 3 * E; float* df = base + 4 * E;
+        float* ret = base + res_floats(r); float* imt = ret + E;
+        base += res_floats(r) + terms_floats(r, tw);
+        if (cx) {
+            StftFwdPartsArgs a;
+            a.x[0] = outputs; a.x[1] = targets; a.mag[0] = me; a.mag[1] = mt; a.re[0] = re; a.re[1] = ret; a.im[0] = im; a.im[1] = imt;
+            a.table = tables_dev[j]; a.T = Tout; a.M = r.M; a.F = (int)r.F; a.C = C; a.n_fft = r.n_fft; a.hop = r.hop; a.K = r.K;
+            hipLaunchKernelGGL(stft_fwd_parts_kernel,
+                               dim3((unsigned)((r.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)((r.K + WUN_STFT_BN - 1) / WUN_STFT_BN), 2u),
+                               blk, 0, s, a);
+        } else {
+            launch_fwd(outputs, targets, me, mt, grad ? re : nullptr, grad ? im : nullptr, tables_dev[j], Tout, C, r, s);
+        }
+        SpecTermsArgs t;
+        t.me = me; t.mt = mt; t.re = re; t.im = im; t.ret = ret; t.imt = imt; t.src = part; t.E = E; t.Es = Es;
+        t.w_mag = tw.mag_l1; t.w_log = tw.log_mag_l1; t.w_sc = tw.sc; t.w_cx = tw.complex_l1; t.log_eps = tw.log_eps;
+        t.grad = grad ? 1 : 0;
+        const bool on[3] = {tw.mag_l1 > 0.f, tw.log_mag_l1 > 0.f, cx};
+        for (int k = 0; k < 3; ++k) {
+            t.part[k] = pnext;
+            if (!on[k]) continue;
+            fin.part[1 + j][k] = pnext; fin.nparts[1 + j][k] = np;
+            pnext += np;
+        }
+        if (sc) {
+            const long long ps = parts_of(Es);
+            double* scpart = pnext; double* src = pnext + 2 * S * ps;
+            pnext = src + 3 * (long long)S;
+            hipLaunchKernelGGL(spec_sc_sums_kernel, dim3((unsigned)(S * ps)), blk, 0, s, me, mt, scpart, Es, ps);
+            hipLaunchKernelGGL(spec_sc_reduce_kernel, dim3(1), blk, 0, s, scpart, src, S, ps, (double)Es, tw.sc_eps);
+            t.src = src; fin.src[j] = src;
+        }
+        hipLaunchKernelGGL(spec_terms_kernel, dim3((unsigned)np), blk, 0, s, t);
+        if (grad) {
+            StftBwdArgs b;
+            b.cre = re; b.cim = im; b.table = tables_dev[j]; b.dframe = df; b.M = r.M; b.n_fft = r.n_fft; b.K = r.K;
+            hipLaunchKernelGGL(stft_bwd_kernel, dim3((unsigned)((r.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)(r.n_fft / WUN_STFT_BN)),
+                               blk, 0, s, b);
+        }
+        g.n_fft[j] = r.n_fft; g.hop[j] = r.hop; g.F[j] = (int)r.F; g.dframe[j] = df;
+        g.scale[j] = (float)((double)weights[j] / ((double)r.M * (double)r.K));
+        fin.count[1 + j] = (double)E; fin.weight[1 + j] = weights[j];
+    }
+    const dim3 ggrid((unsigned)parts_of(N));
+    if (grad) hipLaunchKernelGGL(spec_grad_kernel<true>, ggrid, blk, 0, s, g);
+    else hipLaunchKernelGGL(spec_grad_kernel<false>, ggrid, blk, 0, s, g);
+    hipLaunchKernelGGL(spec_terms_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin);
+    return launch_status(who);
 }

@@ -378,7 +378,7 @@ class UnetAudioSeparator(object):
         resolution j) (Training.py:55-60): wun_spectral_loss writes the loss and dL / d outputs, then the backward pass runs
         from that gradient (wun_backward_ex / _select / _accumulate), so variables, accumulate and the bucket events mean
         what they mean above.  Returns the total; self.last_losses holds [total, MSE, L_0, ...] (device tensor, L_j
-        unweighted).  None: exactly the calls above."""
+        unweighted; a loss built with terms= adds its per-term slots, SpectralLoss.term_losses).  None: exactly the calls above."""
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
@@ -388,7 +388,7 @@ class UnetAudioSeparator(object):
             if self._last_key not in self._d_outs:
                 self._d_outs[self._last_key] = torch.empty_like(outs)
             dout = self._d_outs[self._last_key]
-            losses = torch.empty(2 + len(loss.resolutions), dtype=torch.float32, device=self._dev())
+            losses = torch.empty(loss.num_losses, dtype=torch.float32, device=self._dev())
             loss.run(outs, tg, dout, losses, loss._scratch_for(outs))
             self._run_backward(self._ws[self._last_key], outs, dout, self.grads, None, bucket_starts, bucket_events, mask,
                                accumulate)

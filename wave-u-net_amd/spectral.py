@@ -7,6 +7,9 @@ Hann window, no padding), for any number of resolutions up to 8, next to the tim
     losses, d_outputs = loss.loss_and_grad(outputs, targets)      # [total, MSE, L_0, L_1], dL / d outputs
     sep.loss_and_gradients(targets, loss=loss)         # the training step's loss (UnetAudioSeparator, Trainer)
     stft_l1(net(mix), targets, loss)                   # under torch.autograd, for users of sep.module()
+    loss = SpectralLoss.multi_resolution()             # spectral convergence + log-magnitude L1 at three resolutions (5.14)
+    loss = SpectralLoss([(1024, 256)], terms={"mag_l1": 1, "log_mag_l1": 1, "sc": 1, "complex_l1": 0.5})
+    loss.term_losses(losses)["sc"]                     # the unweighted term of every resolution, a view of `losses`
     re, im = stft(x, 2048, 512, centered=True)         # the complex STFT [S, B, C, F, K]
     x2 = istft(re, im, x.shape[2], 2048, 512, centered=True)      # and its inverse: x again, to fp32 rounding
     re, im = stft(x, 4096, 1024, centered=True, transform="fft")  # the same definitions through an FFT, n_fft up to 8192 (5.13)
@@ -22,6 +25,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 MAX_RESOLUTIONS = 8
+TERMS = ("mag_l1", "log_mag_l1", "sc", "complex_l1")       # the order of the term slots of wun_spectral_loss_terms' losses
 TRANSFORMS = ("gemm", "fft")
 # (transform, operation) -> the library's entry.  "table": wun_*_table_floats, wun_*_design and the table's leading dimension.
 _ENTRIES = {
@@ -177,11 +181,19 @@ def istft(re, im, length, n_fft, hop, centered=False, transform="gemm"):
 
 
 class SpectralLoss(object):
-    """L = mse_weight * MSE + sum_j weights[j] * L_j, L_j = mean |M_est - M_tgt| at resolutions[j] = (n_fft, hop).
-    weights=None: 1 for every resolution.  resolutions=[] is the MSE alone.  ValueError / NotImplementedError for what
-    wun_spectral_loss refuses, at the first call (the checks need the audio's length)."""
+    """L = mse_weight * MSE + sum_j weights[j] * L_j at resolutions[j] = (n_fft, hop).  weights=None: 1 for every resolution.
+    resolutions=[] is the MSE alone.  ValueError / NotImplementedError for what the library's entry refuses, at the first call
+    (the checks need the audio's length).
 
-    def __init__(self, resolutions=((1024, 768),), weights=None, mse_weight=0.0):
+    terms=None: L_j = mean |M_est - M_tgt| (wun_spectral_loss; losses [2 + nres]).
+    terms={name: weight}: L_j = sum_t weight_t * term_t(j) over TERMS (wun_spectral_loss_terms, include/wun.h; a missing name
+    is weight 0 and is not computed): "mag_l1" the term above, "log_mag_l1" mean |log(M_est + log_eps) - log(M_tgt + log_eps)|,
+    "sc" the spectral convergence sqrt(sum d^2 / (sum M_tgt^2 + sc_eps)) per source, averaged over the sources, "complex_l1"
+    mean |STFT_est - STFT_tgt|.  losses is then [2 + 5 nres]: [total, MSE, L_0 .., then mag_l1, log_mag_l1, sc, complex_l1 of
+    resolution 0, of resolution 1, ..] (term_losses).  log_eps and sc_eps are choices, not measurements: 1e-3 sits above the
+    fp32 transform's error on unit-scale audio at short frames (raise it with n_fft), 1.0 keeps a silent source finite."""
+
+    def __init__(self, resolutions=((1024, 768),), weights=None, mse_weight=0.0, terms=None, log_eps=1e-3, sc_eps=1.0):
         self.resolutions = [(int(n), int(h)) for n, h in resolutions]
         if len(self.resolutions) > MAX_RESOLUTIONS:
             raise ValueError("at most %d resolutions, got %d" % (MAX_RESOLUTIONS, len(self.resolutions)))
@@ -192,25 +204,64 @@ class SpectralLoss(object):
         for w in self.weights + [self.mse_weight]:
             if not (w >= 0.0 and np.isfinite(w)):
                 raise ValueError("weights must be finite and >= 0, got %r" % (w,))
+        self.terms, self.log_eps, self.sc_eps = None, float(log_eps), float(sc_eps)
+        self._terms = None       # the entry's wun_spectral_terms (None: wun_spectral_loss)
+        if terms is not None:
+            unknown = set(terms) - set(TERMS)
+            if unknown:
+                raise ValueError("terms: unknown names %s (known: %s)" % (sorted(unknown), ", ".join(TERMS)))
+            self.terms = {t: float(terms.get(t, 0.0)) for t in TERMS}
+            for w in self.terms.values():
+                if not (w >= 0.0 and np.isfinite(w)):
+                    raise ValueError("term weights must be finite and >= 0, got %r" % (w,))
+            for name, eps in (("log_eps", self.log_eps), ("sc_eps", self.sc_eps)):
+                if not (eps > 0.0 and np.isfinite(eps)):
+                    raise ValueError("%s must be finite and > 0, got %r" % (name, eps))
+            self._terms = _lib.WunSpectralTerms(*([self.terms[t] for t in TERMS] + [self.log_eps, self.sc_eps]))
         n = max(len(self.resolutions), 1)
         self._n_fft = (C.c_int32 * n)(*[r[0] for r in self.resolutions])
         self._hop = (C.c_int32 * n)(*[r[1] for r in self.resolutions])
         self._w = (C.c_float * n)(*self.weights)
-        self._scratch = {}       # (shape, device) -> float32 scratch of wun_spectral_scratch_floats
+        self._scratch = {}       # (shape, device) -> float32 scratch of the entry's *_scratch_floats
 
     @classmethod
     def from_config(cls, spec):
-        """model_config["spectral_loss"]: None, a SpectralLoss, or a dict with `resolutions`, `weights`, `mse_weight`."""
+        """model_config["spectral_loss"]: None, a SpectralLoss, or a dict with `resolutions`, `weights`, `mse_weight`, `terms`,
+        `log_eps`, `sc_eps`."""
         if spec is None or isinstance(spec, cls):
             return spec
-        unknown = set(spec) - {"resolutions", "weights", "mse_weight"}
+        unknown = set(spec) - {"resolutions", "weights", "mse_weight", "terms", "log_eps", "sc_eps"}
         if unknown:
             raise ValueError("spectral_loss: unknown keys %s" % sorted(unknown))
-        return cls(spec.get("resolutions", ((1024, 768),)), spec.get("weights"), spec.get("mse_weight", 0.0))
+        return cls(spec.get("resolutions", ((1024, 768),)), spec.get("weights"), spec.get("mse_weight", 0.0), spec.get("terms"),
+                   spec.get("log_eps", 1e-3), spec.get("sc_eps", 1.0))
+
+    @classmethod
+    def multi_resolution(cls):
+        """The usual multi-resolution STFT loss: spectral convergence + log-magnitude L1 at 512 / 128, 1024 / 256, 2048 / 512."""
+        return cls([(512, 128), (1024, 256), (2048, 512)], terms={"sc": 1.0, "log_mag_l1": 1.0})
+
+    @property
+    def num_losses(self):
+        """Floats of `losses`: 2 + nres, with terms 2 + 5 nres."""
+        return 2 + (1 if self._terms is None else 5) * len(self.resolutions)
+
+    def term_losses(self, losses):
+        """{name: [nres] view of `losses`}: the unweighted terms per resolution (terms= only)."""
+        if self._terms is None:
+            raise ValueError("term_losses needs a SpectralLoss built with terms=")
+        nres = len(self.resolutions)
+        per = losses[2 + nres:2 + 5 * nres].view(nres, 4)
+        return {t: per[:, i] for i, t in enumerate(TERMS)}
 
     def scratch_floats(self, shape):
         S, B, T, Cn = (int(v) for v in shape)
-        n = int(_lib.load().wun_spectral_scratch_floats(S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop))
+        lib = _lib.load()
+        if self._terms is None:
+            n = int(lib.wun_spectral_scratch_floats(S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop))
+        else:
+            n = int(lib.wun_spectral_terms_scratch_floats(S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop,
+                                                          C.byref(self._terms)))
         if n < 0:
             _lib.check(n)
         return n
@@ -222,25 +273,30 @@ class SpectralLoss(object):
         return self._scratch[key]
 
     def run(self, outputs, targets, d_outputs, losses, scratch):
-        """wun_spectral_loss on the caller's buffers (contiguous float32 device tensors; d_outputs may be None)."""
+        """wun_spectral_loss (with terms: wun_spectral_loss_terms) on the caller's buffers (contiguous float32 device tensors;
+        losses of num_losses floats; d_outputs may be None)."""
         S, B, T, Cn = (int(v) for v in outputs.shape)
         dev = outputs.device
         nres = len(self.resolutions)
         tabs = (C.c_void_p * max(nres, 1))(*[_table(n, dev).data_ptr() for n, _ in self.resolutions])
+        head = (outputs.data_ptr(), targets.data_ptr(), S, B, T, Cn, self.mse_weight, nres, self._n_fft, self._hop, self._w)
+        tail = (tabs, d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(), _stream(dev))
+        lib = _lib.load()
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().wun_spectral_loss(
-                outputs.data_ptr(), targets.data_ptr(), S, B, T, Cn, self.mse_weight, nres, self._n_fft, self._hop, self._w,
-                tabs, d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(),
-                _stream(dev)))
+            if self._terms is None:
+                _lib.check(lib.wun_spectral_loss(*(head + tail)))
+            else:
+                _lib.check(lib.wun_spectral_loss_terms(*(head + (C.byref(self._terms),) + tail)))
 
     def loss_and_grad(self, outputs, targets, grad=True):
-        """(losses, d_outputs): losses float32 [2 + nres] on the device = [total, MSE, L_0, ...] (L_j unweighted), d_outputs
-        = d total / d outputs with the outputs' shape (None with grad=False).  No host sync."""
+        """(losses, d_outputs): losses float32 [num_losses] on the device = [total, MSE, L_0, ...] (L_j unweighted; with terms
+        the per-term slots follow, term_losses), d_outputs = d total / d outputs with the outputs' shape (None with grad=False).
+        No host sync."""
         outputs, targets = _audio(outputs, "outputs"), _audio(targets, "targets")
         if outputs.shape != targets.shape or outputs.device != targets.device:
             raise ValueError("outputs %s and targets %s differ in shape or device" % (tuple(outputs.shape), tuple(targets.shape)))
         scratch = self._scratch_for(outputs)
-        losses = torch.empty(2 + len(self.resolutions), dtype=torch.float32, device=outputs.device)
+        losses = torch.empty(self.num_losses, dtype=torch.float32, device=outputs.device)
         d_outputs = torch.empty_like(outputs) if grad else None
         self.run(outputs, targets, d_outputs, losses, scratch)
         return losses, d_outputs

@@ -60,7 +60,9 @@ class Trainer(object):
     spectral_loss (or model_config["spectral_loss"], default None): a dict with `resolutions` [[n_fft, hop], ...], `weights`
     and `mse_weight`, or a spectral.SpectralLoss -- the step then minimises mse_weight * MSE + sum_j weight_j * (STFT-magnitude
     L1 at resolution j) (Training.py:55-60; wun_spectral_loss, then the backward pass from its gradient).  step() returns the
-    total; last_losses holds [total, MSE, L_0, ...] of the step (device tensor, the mean over the micro-batches).  None:
+    total; last_losses holds [total, MSE, L_0, ...] of the step (device tensor, the mean over the micro-batches).  With
+    `terms` (and `log_eps`, `sc_eps`) L_j is the weighted sum of mag_l1, log_mag_l1, sc and complex_l1 (wun_spectral_loss_terms,
+    DESIGN.md 5.14), last_losses carries the per-term slots and train.jsonl a `spectral_terms` entry (term_parts).  None:
     exactly the old calls.  Validation and early stopping stay the reference's MSE."""
 
     def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0, grad_accum_steps=None,
@@ -217,6 +219,13 @@ class Trainer(object):
         l = self.last_losses.tolist()
         return l[1], sum(w * x for w, x in zip(self.spectral.weights, l[2:]))
 
+    def term_parts(self):
+        """{term: sum_j weights[j] * termweight * term(j)} of the last step with a spectral loss built with terms= (host sync):
+        the parts of loss_parts()' second value."""
+        sp = self.spectral
+        per = {t: v.tolist() for t, v in sp.term_losses(self.last_losses).items()}
+        return {t: sp.terms[t] * sum(w * x for w, x in zip(sp.weights, per[t])) for t in per}
+
 
 def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
     """(clip_norm or None, skip_nonfinite) of a Trainer: the arguments, else model_config["clip_grad_norm"] /
@@ -270,6 +279,8 @@ def train(model_config, experiment_id, load_model=None, batch_source=None, log_e
             line = {"global_step": tr.sep.global_step, "sep_loss": float(loss.item()), "elapsed_s": time.time() - t0}
             if tr.spectral is not None:
                 line["mse_loss"], line["spectral_loss"] = tr.loss_parts()
+                if tr.spectral.terms is not None:
+                    line["spectral_terms"] = tr.term_parts()
             if tr.clipping:
                 line["grad_norm"] = float(tr.grad_norm.item())
                 line["skipped_steps"] = tr.sep.skipped_steps
