@@ -531,6 +531,60 @@ int     wun_spectral_loss_terms(const float* outputs, const float* targets, int3
                                 const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs, float* losses,
                                 float* scratch, void* stream);
 
+/* ---- waveform losses: MSE, L1, scale-invariant SDR and SNR ----
+ * The time-domain objectives beside the spectral ones: total = sum_t weight_t * term_t over the four terms below, and
+ * d total / d outputs.  outputs (the estimates e) and targets (t) are device float32 [S, B, Tout, C] as above.
+ *   N = S B Tout C floats.  A ROW is one (s, b): R = S B rows, r = s B + b, the n = Tout C contiguous floats of that excerpt,
+ *   all channels together -- one scale per excerpt, as BSS Eval has one per track.
+ * Flat terms (d = e - t formed in fp32):
+ *   mse    : the mean over all N floats of d^2.   gradient cm * d, cm = (float)(mse * 2.0 / N) -- what wun_spectral_loss forms
+ *   l1     : the mean of |d|.                     gradient (float)(l1 / N) * sgn(d), sgn(0) = 0
+ * Row quantities, in float64 from the fp32 samples: sum e, sum t, sum e e, sum t t, sum e t, sum d d per row, every product
+ * formed in float64 (exact), for sum d d the difference too.  With zero_mean: mu_e = sum e / n, mu_t = sum t / n and
+ *   See = max(sum ee - sum e mu_e, 0)   Stt = max(sum tt - sum t mu_t, 0)   Set = sum et - sum e mu_t
+ *   Dd  = max(sum dd - (sum e - sum t)^2 / n, 0)
+ * without it mu_e = mu_t = 0 and See, Stt, Set, Dd are the raw sums.  e' = e - mu_e, t' = t - mu_t, d' = e' - t'.
+ * Row terms, k = 10 / ln 10, w the term's weight:
+ *   si_sdr : P = Set^2 / (Stt + eps), Nn = max(See - P, 0), SI_r = 10 log10((P + eps) / (Nn + eps)); the term is -(1 / R) sum_r SI_r.
+ *            gradient of the weighted term: A_r e'_i + B_r t'_i,  A_r = 2 k w / (R (Nn + eps)),
+ *            B_r = -(w k / R) (2 Set / (Stt + eps)) (1 / (P + eps) + 1 / (Nn + eps))
+ *   snr    : SNR_r = 10 log10((Stt + eps) / (Dd + eps)); the term is -(1 / R) sum_r SNR_r.
+ *            gradient: G_r d'_i,  G_r = 2 k w / (R (Dd + eps))
+ *   The clamps are constants of the gradient: the closed forms are evaluated at the clamped values and max() itself is not
+ *   differentiated.  A term whose weight is 0 is not computed, is reported as 0 and adds nothing to the gradient.
+ * Consequences: a row of zero estimates gets an si_sdr gradient of exactly 0 (Set = 0 and e' = 0: the term cannot leave silence
+ * on its own; combine it with l1 or mse).  A silent target row stays finite: SI_r = 10 log10(eps / (See + eps)).  Estimates
+ * bit-equal to the targets give SI_r ~ 10 log10(Stt / (2 eps)), not infinity.  eps = 1e-8 (the Python default) is a choice, not
+ * a measurement: it lies 80 dB below a row of unit energy and far above the float64 sums' own error.
+ *   losses : device float32 [5 + 2 S]: [0] the total, [1..4] the UNWEIGHTED mse, l1, si_sdr, snr terms, [5 + s] the mean of SI_r
+ *            over source s's B rows (dB, higher is better), [5 + S + s] the mean of SNR_r, same convention
+ *   d_outputs : device [S, B, Tout, C], every float written once; NULL: the losses only.  The targets carry no gradient.
+ *   accumulate: 1: d_outputs += the gradient (one fp32 add of the old value, last) -- how this loss composes with the
+ *            spectral one: wun_spectral_loss* writes d_outputs, this entry adds to it
+ *   scratch: wun_waveform_scratch_floats floats: as float64 on an 8-byte boundary inside the buffer 2 ceil(N / 1024) flat
+ *            partials, 6 R ceil(n / 1024) row partials and 8 R row scalars, plus 2 floats of alignment room
+ * Summation: the flat sums keep wun_spectral_loss's partition and trees (1024 consecutive floats per float64 partial, lane tid
+ * takes the items tid + 256 it ascending, one tree per block; the partials strided over 64 lanes ascending, one tree), so with
+ * terms {mse: w} alone and accumulate = 0, losses[0], losses[1] and d_outputs are those of wun_spectral_loss(mse_weight = w,
+ * nres = 0), bit for bit.  The row sums run over 1024-float chunks of each row's own floats (no block crosses a row), the
+ * chunk partials strided over 256 lanes ascending and one tree: a row's scalars do not depend on the other rows.  The row
+ * scalars stay on the device as float64; no host sync.
+ * Gradient, per float: v = (A_r e' + B_r t') + G_r d' in float64 from the fp32 samples, every operation rounded on its own
+ * (nothing fused), rounded once to fp32; then in fp32, unfused, in this order: cm * d, plus the l1 part, plus (float)v, and with
+ * accumulate one final add of the old d_outputs[i].  Parts whose weights are 0 are left out, not added as zeros.
+ * Contract: every buffer is the caller's; no allocation, no synchronisation, no atomics; every argument check runs before any
+ * GPU work; any 4-byte alignment; runs beside plans of both compute modes; the bits do not depend on the grid, on what scratch
+ * held, on pointer alignment or on repetition.  2 launches with mse / l1 alone, 4 with a row term.
+ * WUN_ERR_INVALID for a null pointer (d_outputs excepted), S < 1, B < 1, Tout < 1, C not 1 or 2, a negative or non-finite term
+ * weight, an eps that is not finite and > 0, accumulate not 0 or 1, or accumulate == 1 with d_outputs NULL. */
+typedef struct { float mse, l1, si_sdr, snr, eps; int32_t zero_mean; } wun_waveform_terms;
+/* floats of `scratch` for wun_waveform_loss with these sizes (the same for every set of terms):
+ * 2 * (2 ceil(N / 1024) + 6 R ceil(n / 1024) + 8 R) + 2.  Negative wun_status as wun_waveform_loss for the same arguments. */
+int64_t wun_waveform_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, const wun_waveform_terms* terms);
+int     wun_waveform_loss(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                          const wun_waveform_terms* terms, int32_t accumulate, float* d_outputs, float* losses, float* scratch,
+                          void* stream);
+
 /* ---- inverse STFT and soft-mask post-filter ----
  * The synthesis half of the spectral section, on the same table, and the post-filter built on the pair: the estimates of a
  * track are masked against the mixture's own STFT, so they share its phase and sum back to it.

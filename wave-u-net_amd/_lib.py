@@ -36,6 +36,10 @@ class WunSpectralTerms(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("mag_l1", "log_mag_l1", "sc", "complex_l1", "log_eps", "sc_eps")]
 
 
+class WunWaveformTerms(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("mse", "l1", "si_sdr", "snr", "eps")] + [("zero_mean", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "wun_get_padding": (C.c_int, [C.POINTER(WunConfig), C.c_int64, C.POINTER(C.c_int64),
@@ -92,6 +96,9 @@ _SIGS = {
     "wun_spectral_loss_terms": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
                                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                           C.POINTER(WunSpectralTerms), C.POINTER(C.c_void_p), _P, _P, _P, _P]),
+    "wun_waveform_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(WunWaveformTerms)]),
+    "wun_waveform_loss": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(WunWaveformTerms), C.c_int32,
+                                    _P, _P, _P, _P]),
     "wun_stft_centered_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "wun_stft_complex": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                    _P, _P, _P, _P]),

@@ -42,6 +42,12 @@ EXTENSION_DEFAULTS = {
     # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60);
     # with "terms": {"mag_l1" | "log_mag_l1" | "sc" | "complex_l1": weight} (and "log_eps", "sc_eps") the multi-resolution STFT loss
     "spectral_loss": None,
+    # training.Trainer / waveform.WaveformLoss: None, or {"terms": {"mse" | "l1" | "si_sdr" | "snr": weight}, "eps": 1e-8,
+    # "zero_mean": True}: the step minimises the weighted sum of those terms (nothing adds an MSE implicitly); with
+    # "spectral_loss" too, the sum of the two totals (waveform.CombinedLoss)
+    "waveform_loss": None,
+    # validation.test: "mse" (the reference's) or "si_sdr": minus the mean SI-SDR in dB, so that lower is still better
+    "validation_metric": "mse",
     # evaluate.separate_track / postfilter.SoftMaskFilter: None = the estimates as the network gives them; else
     # {"n_fft": 2048, "hop": 512, "power": 2, "eps": 1e-10} (any subset): the soft-mask filter against the mix's STFT; with
     # "kind": "wiener" (and "iterations": 1, "em_eps": 1e-10) postfilter.WienerFilter, the multichannel Wiener filter

@@ -36,7 +36,7 @@
 
 using namespace wun;
 
-#define WUN_STFT_ITEMS 4             // elements per lane of the loss / gradient kernels: 1024 per partial, THE summation constant
+// (WUN_STFT_ITEMS, stft_block_sum, parts_of -- 1024 elements per partial, THE summation constant: wun_sum.h)
 #define WUN_SPEC_MAX_RES 8
 
 namespace wun {      // the kernels carry the library's wun:: prefix in profiler output
@@ -67,17 +67,6 @@ __global__ __launch_bounds__(WUN_STFT_BLOCK) void stft_fwd_kernel(StftFwdArgs p)
             mag[m * p.K + k] = sqrtf(fmaf(re, re, im * im));     // (spelled out: which product is fused decides the bits)
             if (parts) { p.re[m * p.K + k] = re; p.im[m * p.K + k] = im; }
         });
-}
-
-// the fixed tree over the 256 lanes of a block; red[0] holds the sum afterwards
-__device__ __forceinline__ double stft_block_sum(double* red, double v, int tid) {
-    red[tid] = v;
-    __syncthreads();
-    for (int s = WUN_STFT_BLOCK / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 // 1024 bins per block: part[block] = sum |M_est - M_tgt|; with re / im the coefficients of the gradient replace them in place:
@@ -392,7 +381,6 @@ int make_res(const char* who, int32_t S, int32_t B, int64_t T, int32_t C, int32_
     return WUN_OK;
 }
 
-long long parts_of(long long n) { return (n + WUN_STFT_BLOCK * WUN_STFT_ITEMS - 1) / (WUN_STFT_BLOCK * WUN_STFT_ITEMS); }
 // floats of one resolution's slice of the scratch: magnitudes of both signals, Re and Im of the estimates, the frame gradients
 long long res_floats(const Res& r) { return 4 * r.M * r.K + r.M * r.n_fft; }
 

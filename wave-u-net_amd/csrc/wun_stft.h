@@ -12,6 +12,7 @@
 // falls in: the bits of a frame do not depend on the rows around it, the grid, or pointer alignment.
 #pragma once
 #include "wun_fft.h"
+#include "wun_sum.h"
 #include "../../include/wun.h"
 
 #include <cstdint>
@@ -19,7 +20,7 @@
 
 int fail(int code, const std::string& msg);      // wun_plan.hip: sets wun_last_error(), returns code
 
-#define WUN_STFT_BLOCK 256           // threads per workgroup of every kernel of the family (4 waves)
+// (WUN_STFT_BLOCK, the 256 threads per workgroup of every kernel of the family: wun_sum.h)
 #define WUN_STFT_BM 64               // frames per GEMM workgroup
 #define WUN_STFT_BN 32               // columns per GEMM workgroup (forward: bins, re and im each; inverse: samples of a frame)
 #define WUN_STFT_KC 32               // reduction indices staged per step

@@ -378,7 +378,13 @@ class UnetAudioSeparator(object):
         resolution j) (Training.py:55-60): wun_spectral_loss writes the loss and dL / d outputs, then the backward pass runs
         from that gradient (wun_backward_ex / _select / _accumulate), so variables, accumulate and the bucket events mean
         what they mean above.  Returns the total; self.last_losses holds [total, MSE, L_0, ...] (device tensor, L_j
-        unweighted; a loss built with terms= adds its per-term slots, SpectralLoss.term_losses).  None: exactly the calls above."""
+        unweighted; a loss built with terms= adds its per-term slots, SpectralLoss.term_losses).  None: exactly the calls above.
+
+        `loss` is ANY object of this protocol: `_scratch_for(outputs)` -> the scratch it wants (called first), `num_losses` ->
+        the floats of its losses, `run(outputs, targets, d_outputs, losses, scratch)` -> writes losses (losses[0] the total)
+        and d total / d outputs on the current stream without a host sync.  spectral.SpectralLoss, waveform.WaveformLoss
+        (MSE, L1, SI-SDR, SNR; last_losses is then [total, mse, l1, si_sdr, snr, dB per source ...]) and
+        waveform.CombinedLoss (the sum of the two) are the package's own."""
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
@@ -388,8 +394,9 @@ class UnetAudioSeparator(object):
             if self._last_key not in self._d_outs:
                 self._d_outs[self._last_key] = torch.empty_like(outs)
             dout = self._d_outs[self._last_key]
+            scratch = loss._scratch_for(outs)              # (first: a loss's num_losses may depend on the shape)
             losses = torch.empty(loss.num_losses, dtype=torch.float32, device=self._dev())
-            loss.run(outs, tg, dout, losses, loss._scratch_for(outs))
+            loss.run(outs, tg, dout, losses, scratch)
             self._run_backward(self._ws[self._last_key], outs, dout, self.grads, None, bucket_starts, bucket_events, mask,
                                accumulate)
             self.last_losses = losses

@@ -20,6 +20,7 @@ from .parallel import GradAllReducer, OverlappedGradAllReducer, broadcast_parame
 from .checkpoint import load_checkpoint, save_checkpoint
 from .separator import UnetAudioSeparator, check_clip_norm
 from .spectral import SpectralLoss
+from .waveform import CombinedLoss, WaveformLoss, TERMS as WAVEFORM_TERMS
 
 
 def synthetic_source(model_config, batch, t_in, t_out, device, seed=1337):
@@ -63,10 +64,19 @@ class Trainer(object):
     total; last_losses holds [total, MSE, L_0, ...] of the step (device tensor, the mean over the micro-batches).  With
     `terms` (and `log_eps`, `sc_eps`) L_j is the weighted sum of mag_l1, log_mag_l1, sc and complex_l1 (wun_spectral_loss_terms,
     DESIGN.md 5.14), last_losses carries the per-term slots and train.jsonl a `spectral_terms` entry (term_parts).  None:
-    exactly the old calls.  Validation and early stopping stay the reference's MSE."""
+    exactly the old calls.
+
+    waveform_loss (or model_config["waveform_loss"], default None): a dict with `terms` {"mse" | "l1" | "si_sdr" | "snr": weight},
+    `eps` and `zero_mean`, or a waveform.WaveformLoss (wun_waveform_loss).  Alone, the step minimises the
+    waveform total -- nothing adds an MSE implicitly, ask for "mse"; with spectral_loss too, the sum of the two totals
+    (waveform.CombinedLoss: the spectral entry writes d_outputs, the waveform entry adds to it).  last_waveform_losses holds
+    [total, mse, l1, si_sdr, snr, SI-SDR dB per source, SNR dB per source] of the step (the mean over the micro-batches),
+    waveform_parts() the weighted terms, train.jsonl a `waveform_terms` entry; last_losses, loss_parts() and term_parts() keep
+    their spectral layout and meaning whenever a spectral loss is set.  Validation and early stopping stay the reference's MSE
+    unless model_config["validation_metric"] says "si_sdr" (validation.test)."""
 
     def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0, grad_accum_steps=None,
-                 clip_grad_norm=None, skip_nonfinite=None, spectral_loss=None):
+                 clip_grad_norm=None, skip_nonfinite=None, spectral_loss=None, waveform_loss=None):
         self.rank, self.local_rank, self.world = init_distributed()
         # Scheduling hint of the plan (include/wun.h): low-priority side streams only when no collective shares the
         # device -- with a process group initialised (multi-GPU, or bench.py --force-allreduce) they must stay normal.
@@ -88,8 +98,16 @@ class Trainer(object):
         self.clip_norm, self.skip_nonfinite = clip_settings(model_config, clip_grad_norm, skip_nonfinite)
         self.spectral = SpectralLoss.from_config(spectral_loss if spectral_loss is not None
                                                  else model_config.get("spectral_loss"))
-        self._loss_kw = {"loss": self.spectral} if self.spectral is not None else {}
+        self.waveform = WaveformLoss.from_config(waveform_loss if waveform_loss is not None
+                                                 else model_config.get("waveform_loss"))
+        if self.spectral is not None and self.waveform is not None:
+            self._loss_kw = {"loss": CombinedLoss(self.spectral, self.waveform)}
+        elif self.waveform is not None:
+            self._loss_kw = {"loss": self.waveform}
+        else:
+            self._loss_kw = {"loss": self.spectral} if self.spectral is not None else {}
         self.last_losses = None
+        self.last_waveform_losses = None
         self.grad_norm = None                  # global norm of the last clipped / checked update (0-dim GPU tensor)
         in_shape, out_shape = self.sep.get_padding(np.array([self.batch, model_config["num_frames"], 0]))
         self.t_in, self.t_out = int(in_shape[1]), int(out_shape[1])
@@ -172,9 +190,18 @@ class Trainer(object):
             loss = self.sep.loss_and_gradients(targets, **self._loss_kw)
             self.reducer.all_reduce(self.sep.grads)
         self._adam(self.reducer.grad_scale)
-        if self.spectral is not None:
-            self.last_losses = self.sep.last_losses
+        if self._loss_kw:
+            self._keep_losses(self.sep.last_losses)
         return loss
+
+    def _keep_losses(self, losses):
+        """losses of the step's loss object -> last_losses (the spectral loss's own layout) and last_waveform_losses."""
+        if self.spectral is not None and self.waveform is not None:
+            self.last_losses, self.last_waveform_losses = self._loss_kw["loss"].parts(losses)
+        elif self.waveform is not None:
+            self.last_waveform_losses = losses
+        else:
+            self.last_losses = losses
 
     @property
     def clipping(self):
@@ -202,7 +229,7 @@ class Trainer(object):
                 losses.append(self.sep.loss_and_gradients(t, *self.reducer.begin(), accumulate=i > 0, **self._loss_kw))
             else:
                 losses.append(self.sep.loss_and_gradients(t, accumulate=i > 0, **self._loss_kw))
-            if self.spectral is not None:
+            if self._loss_kw:
                 parts.append(self.sep.last_losses)
         if self.overlap:
             self.reducer.launch(self.sep.grads)
@@ -210,8 +237,8 @@ class Trainer(object):
         else:
             self.reducer.all_reduce(self.sep.grads)
         self._adam(self.reducer.grad_scale / k)
-        if self.spectral is not None:
-            self.last_losses = torch.stack(parts).mean(0)
+        if self._loss_kw:
+            self._keep_losses(torch.stack(parts).mean(0))
         return torch.stack(losses).mean()
 
     def loss_parts(self):
@@ -225,6 +252,17 @@ class Trainer(object):
         sp = self.spectral
         per = {t: v.tolist() for t, v in sp.term_losses(self.last_losses).items()}
         return {t: sp.terms[t] * sum(w * x for w, x in zip(sp.weights, per[t])) for t in per}
+
+
+    def waveform_parts(self):
+        """{term: weight * term} of the last step with a waveform loss -- they sum to its total -- plus "si_sdr_db" and "snr_db":
+        the per-source means in dB, higher is better (host sync)."""
+        wv = self.waveform
+        l = self.last_waveform_losses
+        per = {t: v.item() for t, v in wv.term_losses(l).items()}
+        parts = {t: wv.terms[t] * per[t] for t in WAVEFORM_TERMS}
+        parts.update({k + "_db": v.tolist() for k, v in wv.source_metrics(l).items()})
+        return parts
 
 
 def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
@@ -281,6 +319,8 @@ def train(model_config, experiment_id, load_model=None, batch_source=None, log_e
                 line["mse_loss"], line["spectral_loss"] = tr.loss_parts()
                 if tr.spectral.terms is not None:
                     line["spectral_terms"] = tr.term_parts()
+            if tr.waveform is not None:
+                line["waveform_terms"] = tr.waveform_parts()
             if tr.clipping:
                 line["grad_norm"] = float(tr.grad_norm.item())
                 line["skipped_steps"] = tr.sep.skipped_steps

@@ -6,6 +6,10 @@ separator run in inference mode (training=False, so the "linear" head clips, Tes
 mean over batches (Test.py:77-84).  optimise() = epochs of train() until the validation loss has
 not improved for `worse_epochs` epochs, then a fine-tuning round with batch_size doubled and
 init_sup_sep_lr = 1e-5, then the test-partition loss of the best checkpoint.
+
+model_config["validation_metric"] = "si_sdr" (default "mse") scores every batch with the scale-invariant SDR of
+waveform.WaveformLoss (wun_waveform_loss) instead: test() then returns MINUS the mean SI-SDR in dB, so lower
+is still better and optimise() needs no other change.
 """
 import json
 import os
@@ -17,6 +21,7 @@ from . import datasets
 from .separator import UnetAudioSeparator
 from .training import train
 from .checkpoint import load_checkpoint
+from . import waveform
 
 
 def _load_checkpoint(separator, load_model):
@@ -28,7 +33,12 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     """Test.test(model_config, partition, model_folder, load_model) -> mean MSE.  The partition's
     tracks come from `tracks` (list of track dicts) or data_root/<partition>/<track>/.
     return_sums: (sum of the per-batch losses, number of batches) instead, nothing logged.
-    resample: files of data_root at another rate are converted to expected_sr (datasets.load_audio) instead of refused."""
+    resample: files of data_root at another rate are converted to expected_sr (datasets.load_audio) instead of refused.
+    model_config["validation_metric"] = "si_sdr": the per-batch loss is minus the mean SI-SDR (dB) over the batch's sources
+    and excerpts, of the same inference-mode outputs (WaveformLoss({"si_sdr": 1}) with the eps and zero_mean of
+    model_config["waveform_loss"], grad=False); the same running mean, and test.jsonl gains "metric" and the per-source dB.
+    ValueError for any other value but "mse"."""
+    metric = waveform.validation_metric(model_config)
     if model_config["network"] != "unet":
         raise NotImplementedError(model_config["network"])                        # Test.py:14-19
     if tracks is None:
@@ -43,13 +53,22 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
 
     total_loss, batch_num, loss_sum = 0.0, 1, 0.0
     names = list(model_config["source_names"])
+    si_loss = waveform.validation_loss(model_config) if metric == "si_sdr" else None
+    source_db = np.zeros(len(names))                                              # running means of the per-source dB
     for batch in datasets.get_dataset(model_config, in_shape, out_shape, partition, tracks):
         outs = sep.get_output(batch["mix"], False)                                # Test.py:34
-        loss = 0.0
-        for key in names:                                                         # Test.py:61-74
-            real = torch.as_tensor(batch[key], device=outs[key].device)
-            loss = loss + torch.mean((real - outs[key]) ** 2)
-        curr = float(loss.item()) / float(model_config["num_sources"])
+        if si_loss is not None:
+            est = torch.stack([outs[key] for key in names])
+            real = torch.stack([torch.as_tensor(batch[key], device=est.device) for key in names])
+            losses, _ = si_loss.loss_and_grad(est, real, grad=False)
+            curr = float(losses[0].item())                                        # -(mean SI-SDR in dB)
+            source_db += (1.0 / float(batch_num)) * (si_loss.source_metrics(losses)["si_sdr"].cpu().numpy() - source_db)
+        else:
+            loss = 0.0
+            for key in names:                                                     # Test.py:61-74
+                real = torch.as_tensor(batch[key], device=outs[key].device)
+                loss = loss + torch.mean((real - outs[key]) ** 2)
+            curr = float(loss.item()) / float(model_config["num_sources"])
         total_loss = total_loss + (1.0 / float(batch_num)) * (curr - total_loss)  # Test.py:80
         loss_sum += curr
         batch_num += 1
@@ -58,8 +77,12 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
 
     log_dir = os.path.join(model_config["log_dir"], str(model_folder))            # Test.py:41,86-87
     os.makedirs(log_dir, exist_ok=True)
+    line = {"global_step": global_step, "partition": partition, "test_loss": total_loss}
+    if si_loss is not None:
+        line["metric"] = "si_sdr"
+        line["si_sdr_db"] = {key: float(v) for key, v in zip(names, source_db)}
     with open(os.path.join(log_dir, "test.jsonl"), "a") as f:
-        f.write(json.dumps({"global_step": global_step, "partition": partition, "test_loss": total_loss}) + "\n")
+        f.write(json.dumps(line) + "\n")
     return total_loss
 
 
