@@ -721,6 +721,43 @@ int     wun_wiener_filter_fft(const float* mix_tc, const float* ests, int32_t S,
                               int32_t hop, int32_t power, float mask_eps, int32_t iterations, float eps,
                               const float* table_dev, float* out, float* scratch, void* stream);
 
+/* ---- the FFT path of the spectral loss and its gradient ----
+ * wun_stft_magnitude, wun_spectral_loss and wun_spectral_loss_terms with both frame transforms of a resolution computed by the
+ * FFT of the section above instead of a GEMM, for n_fft a power of two in 64..8192: the loss at the resolutions the filters
+ * above run at (4096 / 1024), and about 0.1 MFLOP instead of 8.4 per 2048-point frame.  Every entry takes the arguments of the
+ * entry it is named after, in its order, with table_dev / tables_dev[j] = a device copy of wun_fft_design's table of n_fft[j]
+ * (3 n_fft floats), and has its contract: the framing without padding (F = 1 + (T - n_fft) / hop, wun_fft_frames), the [R][F][K]
+ * layout, the definitions of L_j, of the four terms and of d_outputs, the `losses` slots, the float64 partition and summation
+ * order, the caller's buffers, no allocation, no sync, no atomics, any 4-byte alignment, both compute modes.  The checks are the
+ * sibling's in its order and with its codes, WUN_ERR_UNSUPPORTED now for an n_fft that is no power of two in 64..8192 (nothing
+ * is launched); T < n_fft is WUN_ERR_INVALID as there.
+ *   forward  : the section above's forward transform (lead 0); M = sqrtf(fmaf(Re, Re, Im * Im)) as in the GEMM entries, Im of the
+ *              bins 0 and n_fft / 2 exactly 0.  One kernel serves the magnitude entry and both losses: the loss's signs are those
+ *              of the floats wun_stft_magnitude_fft returns.
+ *   gradient : dframe[n] = w[n] sum_{k = 0..n_fft/2} (cre[k] cos(2 pi n k / n_fft) - cim[k] sin(2 pi n k / n_fft)), every bin once:
+ *              the inverse transform above on the coefficients with the bins 0 and n_fft / 2 doubled and the scale 1 / 2 in place
+ *              of 1 / n_fft (powers of two: exact), the window applied once at the store.  The imaginary coefficients of the bins 0
+ *              and n_fft / 2 are not read.  The overlap-add over the frames is wun_spectral_loss's kernel, unchanged.
+ * Only the summation order inside a frame transform differs from the GEMM entries: losses and gradients agree with them to
+ * float32 rounding, not bit for bit.  A frame's magnitudes and its gradient frame depend on that frame and the table alone --
+ * not on the frames sharing its workgroup, the grid, the batch around the row, what `scratch` held or pointer alignment.
+ * The scratch formulas are IDENTICAL to the siblings' (the same slices hold the same arrays); the entries differ in the n_fft
+ * they accept.  With terms = {1, 0, 0, 0, ..} wun_spectral_loss_terms_fft gives wun_spectral_loss_fft's first 2 + nres losses and
+ * d_outputs bit for bit. */
+int     wun_stft_magnitude_fft(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                               const float* table_dev, float* mags, void* stream);
+int64_t wun_spectral_fft_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                        const int32_t* hop);
+int     wun_spectral_loss_fft(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                              float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                              const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream);
+int64_t wun_spectral_terms_fft_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                              const int32_t* hop, const wun_spectral_terms* terms);
+int     wun_spectral_loss_terms_fft(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                    float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                                    const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs,
+                                    float* losses, float* scratch, void* stream);
+
 /* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
  * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
  * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is

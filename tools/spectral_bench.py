@@ -12,8 +12,13 @@ Kernel arms (HIP events on the launch stream around `iters` back-to-back calls, 
 Trainer arms (one optimizer step each, same batch):
   step_mse      Trainer(batch 16): the time-domain MSE (wun_loss_backward)
   step_spectral Trainer(batch 16, spectral_loss = 1024 / 768, mse_weight 1): wun_spectral_loss, then wun_backward
+FFT arms, interleaved with the arms above in the same process -- the GEMM arm beside an FFT arm is its yardstick:
+  magnitude_fft, loss_grad_fft, terms_sc_log_fft   the arm of that name through the _fft entries (SpectralLoss(transform="fft"))
+  step_spectral_fft                                step_spectral with "transform": "fft"
+  magnitude_4096, loss_grad_4096, terms_sc_log_4096   the three FFT arms at 4096 / 1024, whatever --res says: no GEMM twin exists
 
-  python tools/spectral_bench.py [--rounds 9] [--iters 10] [--out profiles/spectral_bench.json] [--arms a,b,...]
+  python tools/spectral_bench.py [--rounds 9] [--iters 10] [--out profiles/spectral_bench.json] [--arms a,b,...] [--res 1024,768]
+      --res n_fft,hop: the resolution of every arm but the _4096 ones (default: the reference's)
       --arms loss_grad,terms_mag,terms_sc_log,terms_all --out profiles/spectral_terms_bench.json: the four-term entry beside the old
       the arms interleaved in ONE process for `rounds` rounds (order rotated each round); per arm the median, the minimum and
       the maximum over the rounds of (time / iters).  One JSON line on stdout, and the same in --out.
@@ -28,13 +33,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-ARMS = ["magnitude", "loss_only", "loss_grad", "terms_mag", "terms_sc_log", "terms_all", "step_mse", "step_spectral"]
+ARMS = ["magnitude", "loss_only", "loss_grad", "terms_mag", "terms_sc_log", "terms_all", "step_mse", "step_spectral",
+        "magnitude_fft", "loss_grad_fft", "terms_sc_log_fft", "step_spectral_fft", "magnitude_4096", "loss_grad_4096",
+        "terms_sc_log_4096"]
 TERMS = {"terms_mag": {"mag_l1": 1.0}, "terms_sc_log": {"sc": 1.0, "log_mag_l1": 1.0},
          "terms_all": {"mag_l1": 1.0, "log_mag_l1": 1.0, "sc": 1.0, "complex_l1": 1.0}}
 RES = [(1024, 768)]
+RES_4096 = [(4096, 1024)]
 
 
-def setup():
+def setup(arms):
     import torch
     import wave_u_net_amd as wun
     from wave_u_net_amd import spectral
@@ -44,8 +52,11 @@ def setup():
     table = open(os.path.join(ROOT, "profiles", "round6_tune_table.txt")).read()
     spec = {"resolutions": [list(r) for r in RES], "mse_weight": 1.0}
     tr_mse, tr_spec = Trainer(cfg, batch_size=16), Trainer(cfg, batch_size=16, spectral_loss=spec)
+    tr_fft = Trainer(cfg, batch_size=16, spectral_loss=dict(spec, transform="fft")) if "step_spectral_fft" in arms else None
     mix, targets = synthetic_source(cfg, 16, tr_mse.t_in, tr_mse.t_out, tr_mse.device, seed=1337)()
-    for tr in (tr_mse, tr_spec):
+    for tr in (tr_mse, tr_spec, tr_fft):
+        if tr is None:
+            continue
         tr.sep.get_output(mix, True)
         tr.sep.tune_import(table)
     outs = tr_mse.sep._outs[tr_mse.sep._last_key].clone()
@@ -55,6 +66,13 @@ def setup():
     losses = torch.empty(3, dtype=torch.float32, device=outs.device)
     d_outs = torch.empty_like(outs)
     tloss = {a: spectral.SpectralLoss(RES, mse_weight=1.0, terms=t, log_eps=1.0) for a, t in TERMS.items()}   # (n_fft 1024: 5.14)
+    # the FFT twins, and the 4096 / 1024 arms: (loss, its resolution list) by arm; log_eps does not change the work
+    floss = {"loss_grad_fft": spectral.SpectralLoss(RES, mse_weight=1.0, transform="fft"),
+             "terms_sc_log_fft": spectral.SpectralLoss(RES, mse_weight=1.0, terms=TERMS["terms_sc_log"], log_eps=1.0, transform="fft"),
+             "loss_grad_4096": spectral.SpectralLoss(RES_4096, mse_weight=1.0, transform="fft"),
+             "terms_sc_log_4096": spectral.SpectralLoss(RES_4096, mse_weight=1.0, terms=TERMS["terms_sc_log"], log_eps=4.0,
+                                                        transform="fft")}
+    tloss.update({a: l for a, l in floss.items() if a in arms})
     tbuf = {a: (torch.empty(l.num_losses, dtype=torch.float32, device=outs.device), l._scratch_for(outs)) for a, l in tloss.items()}
 
     def step(arm):
@@ -64,17 +82,23 @@ def setup():
             loss.run(outs, tg, None, losses, scratch)
         elif arm == "loss_grad":
             loss.run(outs, tg, d_outs, losses, scratch)
+        elif arm == "magnitude_fft":
+            spectral.stft_magnitude(outs, *RES[0], transform="fft")
+        elif arm == "magnitude_4096":
+            spectral.stft_magnitude(outs, *RES_4096[0], transform="fft")
         elif arm in tloss:
             tloss[arm].run(outs, tg, d_outs, *tbuf[arm])
         elif arm == "step_mse":
             tr_mse.step(mix, targets)
+        elif arm == "step_spectral_fft":
+            tr_fft.step(mix, targets)
         else:
             tr_spec.step(mix, targets)
     return torch, step, tuple(outs.shape)
 
 
 def timed(rounds, iters, out, arms):
-    torch, step, shape = setup()
+    torch, step, shape = setup(arms)
     for arm in arms:                                              # warm-up
         for _ in range(3):
             step(arm)
@@ -108,7 +132,9 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
     ap.add_argument("--arms", default=",".join(ARMS), help="comma-separated subset of %s" % ", ".join(ARMS))
+    ap.add_argument("--res", default="1024,768", help="n_fft,hop of every arm but the _4096 ones")
     a = ap.parse_args()
+    RES[0] = tuple(int(v) for v in a.res.split(","))
     arms = a.arms.split(",")
     if not arms or any(x not in ARMS for x in arms):
         ap.error("--arms must name some of %s" % ", ".join(ARMS))

@@ -12,6 +12,9 @@ through the library that WUN_LIB names (default libwun.so).  Two libraries that 
   filters     wun_mask_filter and wun_wiener_filter (iterations 0, 1, 2), and the _fft twins: S 2, C 1 and 2, n 200 and 5000
               at 64 / 16 (315 frames: more than one block of 256), n 5000 at 2048 / 512, power 1 and 2; one _fft case at
               4096 / 1024
+  fft loss    wun_stft_magnitude_fft on the transforms' unpadded cases and at 4096 / 1024 and 8192 / 2048; wun_spectral_loss_fft and
+              wun_spectral_loss_terms_fft (all four terms) on the loss's cases and at (64, 48) + (4096, 1024), T 6149
+              (DESIGN.md 5.16).  These lines come last: the lines above them are those of a library without the entries
 Inputs come from fixed seeds; the whole run takes a few seconds on the GPU.
 """
 import hashlib
@@ -102,8 +105,32 @@ def filters():
             show("wiener_filter_%d %s" % (it, tag), WienerFilter(n_fft, hop, power, iterations=it, transform=tr).apply(mix, est))
 
 
+def fft_loss():
+    for (n_fft, hop, T) in [(n, h, t) for (n, h) in RES for t in LENGTHS if t >= n] + [(4096, 1024, 9000), (8192, 2048, 12293)]:
+        for (S, B, Cn) in SHAPES:
+            x = audio(n_fft + T + S, (S, B, T, Cn))
+            for off in (False, True):
+                tag = "%d/%d T%d S%dB%dC%d%s" % (n_fft, hop, T, S, B, Cn, " +4" if off else "")
+                show("magnitude_fft " + tag, spectral.stft_magnitude(offset_copy(x) if off else x, n_fft, hop, transform="fft"))
+    S, B = 2, 3
+    terms = {"mag_l1": 0.7, "log_mag_l1": 0.4, "sc": 1.3, "complex_l1": 0.6}
+    for (res, T, log_eps) in ((LOSS_RES, 1000, 1e-2), ([(64, 48), (4096, 1024)], 6149, 4.0)):
+        for tname, tw in (("loss_fft", None), ("loss_terms_fft", terms)):
+            f = spectral.SpectralLoss(res, weights=[1.0, 0.5], mse_weight=0.5, terms=tw, log_eps=log_eps, transform="fft")
+            for Cn in (1, 2):
+                out, tgt = audio(10 + Cn, (S, B, T, Cn)), audio(20 + Cn, (S, B, T, Cn))
+                for grad in (False, True):
+                    losses, d_out = f.loss_and_grad(out, tgt, grad=grad)
+                    name = "%s %d/%d C%d %s" % (tname, res[-1][0], res[-1][1], Cn, "grad" if grad else "only")
+                    show(name + " losses", losses)
+                    if grad:
+                        show(name + " d_outputs", d_out)
+
+
 if __name__ == "__main__":
     transforms()
     loss()
     filters()
+    if hasattr(spectral.SpectralLoss([]), "transform"):      # (a tree from before DESIGN.md 5.16 has no such entries)
+        fft_loss()
     torch.cuda.synchronize()

@@ -20,6 +20,8 @@ masks the estimates against the mix's STFT before they are written / scored (pos
 (postfilter.WienerFilter: EM iterations over the channels together; "kind":"softmask" is the default).
 `"transform":"fft"` in either spec computes the transforms with an FFT and lifts n_fft's limit from 2048 to 8192
 (`postfilter={"n_fft":4096,"hop":1024,"transform":"fft"}`).
+`train` takes the spectral objective as `model_config.spectral_loss={"resolutions":[[4096,1024]],"transform":"fft","terms":{"sc":1,
+"log_mag_l1":1},"log_eps":4.0}`: `"transform":"fft"` lifts the loss's n_fft limit from 2048 to 8192 in the same way ("gemm" is the default).
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
 1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
 source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.

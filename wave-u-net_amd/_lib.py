@@ -128,6 +128,17 @@ _SIGS = {
     "wun_wiener_filter_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "wun_wiener_filter_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                         C.c_int32, C.c_float, _P, _P, _P, _P]),
+    "wun_stft_magnitude_fft": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "wun_spectral_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_int32)]),
+    "wun_spectral_loss_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_void_p),
+                                        _P, _P, _P, _P]),
+    "wun_spectral_terms_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(WunSpectralTerms)]),
+    "wun_spectral_loss_terms_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                              C.POINTER(WunSpectralTerms), C.POINTER(C.c_void_p), _P, _P, _P, _P]),
     "wun_separate_positions": (C.c_int64, [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64]),
     "wun_forward_windows": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, _P, _P, C.c_int, _P]),
     "wun_scatter_windows": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, _P, C.c_int64, _P]),

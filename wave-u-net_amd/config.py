@@ -40,7 +40,8 @@ EXTENSION_DEFAULTS = {
     "checkpoint_format": "npz",       # training.train: "npz" or "tf"
     # training.Trainer / spectral.SpectralLoss: None = the reference's MSE; else {"resolutions": [[n_fft, hop], ...],
     # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60);
-    # with "terms": {"mag_l1" | "log_mag_l1" | "sc" | "complex_l1": weight} (and "log_eps", "sc_eps") the multi-resolution STFT loss
+    # with "terms": {"mag_l1" | "log_mag_l1" | "sc" | "complex_l1": weight} (and "log_eps", "sc_eps") the multi-resolution STFT loss;
+    # "transform": "gemm" (default, n_fft up to 2048) or "fft" (up to 8192: {"resolutions": [[4096, 1024]], "transform": "fft"})
     "spectral_loss": None,
     # training.Trainer / waveform.WaveformLoss: None, or {"terms": {"mse" | "l1" | "si_sdr" | "snr": weight}, "eps": 1e-8,
     # "zero_mean": True}: the step minimises the weighted sum of those terms (nothing adds an MSE implicitly); with

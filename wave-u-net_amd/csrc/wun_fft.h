@@ -1,6 +1,7 @@
 // What wun_postfilter.hip (the host orchestration of the transforms and filters) and wun_fft.hip (the FFT kernels) share: the
 // argument blocks of a forward and an inverse frame transform, and the launchers of the FFT path.  Both transforms of one
-// direction take the same block, so the orchestration picks one by a selector and nothing else changes.
+// direction take the same block, so the orchestration picks one by a selector and nothing else changes.  wun_spectral.hip (the
+// spectral loss) launches the forward body with its magnitude epilogue and the inverse body as an adjoint the same way.
 #pragma once
 #include "wun_device.h"
 
@@ -28,9 +29,21 @@ struct IstftGemmArgs {
     float c_edge, c_mid;                     // 1 / n_fft for k = 0 and k = n_fft / 2, 2 / n_fft between
 };
 
+// The forward transform with the spectral loss's epilogue: mag[z][e] = sqrt(re^2 + im^2) of every bin of signal z, and Re / Im
+// into a.re[z] / a.im[z] where those are not null.
+struct StftMagArgs {
+    StftCfwdArgs a;
+    float* mag[2];
+};
+
 // wun_fft.hip: stft_fft_kernel / istft_fft_kernel of a.n_fft (a power of two in 64..8192) on stream s.  WUN_OK, or
 // WUN_ERR_UNSUPPORTED (wun_last_error() set, nothing launched) for an n_fft without a kernel.
+//   magnitude   the forward body with StftMagArgs' epilogue (the spectral loss and wun_stft_magnitude_fft)
+//   adjoint     the inverse body as the UNSCALED adjoint of the forward transform, every bin counted once (stft_bwd_kernel's
+//               definition): g.c_edge must be 1 / 2, g.c_mid is not read
 int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s);
+int fft_launch_magnitude(const StftMagArgs& a, int signals, hipStream_t s);
 int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s);
+int fft_launch_adjoint(const IstftGemmArgs& g, hipStream_t s);
 
 }  // namespace wun

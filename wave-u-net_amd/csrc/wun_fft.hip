@@ -1,6 +1,8 @@
 // gfx950 (MI355X / CDNA4): the FFT path of the complex STFT and its inverse (include/wun.h: wun_fft_design, wun_stft_complex_fft,
 // wun_istft_fft and the *_fft filters).  Same definitions and layouts as stft_cfwd_kernel / istft_gemm_kernel of
-// wun_postfilter.hip, whose host code launches these through wun_fft.h; O(n log n) per frame instead of O(n^2).
+// wun_postfilter.hip, whose host code launches these through wun_fft.h; O(n log n) per frame instead of O(n^2).  The spectral
+// loss's two frame transforms (wun_spectral_loss_fft and its kin) are the same two bodies: the forward one with
+// the magnitude as its epilogue, the inverse one as the unscaled adjoint.
 //
 //   real transform   a frame of n_fft real samples is one complex FFT of M = n_fft / 2 points, z[m] = y[2m] + i y[2m+1], and a
 //                    split step:  E = (Z[k] + conj Z[M-k]) / 2,  O = (Z[k] - conj Z[M-k]) / 2i,  X[k] = E + W_N^k O,  k = 0..M
@@ -27,6 +29,7 @@
 
 #include <cmath>
 #include <string>
+#include <type_traits>
 
 using namespace wun;
 int fail(int code, const std::string& msg);      // wun_plan.hip
@@ -115,9 +118,12 @@ __device__ __forceinline__ void fft_run(Load load, float (*sre)[FftGeom<LOGM>::P
     }
 }
 
-// grid: x = group of FPW frame rows, z = signal.  Frame row m of StftCfwdArgs, as stft_cfwd_kernel.
-template <int LOGM>
-__global__ __launch_bounds__(WUN_FFT_BLOCK) void stft_fft_kernel(StftCfwdArgs p) {
+// The forward transform of workgroup blockIdx.x's FPW frame rows of signal z = blockIdx.z (frame row m of StftCfwdArgs, as
+// stft_cfwd_kernel): store(z, e, re, im) is called once for every frame row m < M[z] and bin k = 0..n_fft / 2, e = the float
+// index of that bin in the [.][K] arrays; im of the bins 0 and n_fft / 2 is exactly 0.  The whole kernel body: it returns for
+// the workgroups and frame slots behind the last row.
+template <int LOGM, class Store>
+__device__ __forceinline__ void fft_fwd_frames(const StftCfwdArgs& p, Store store) {
     using G = FftGeom<LOGM>;
     constexpr int M = G::M, N = G::N, TPF = G::TPF;
     __shared__ float sre[2][G::PLANE];
@@ -150,8 +156,6 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void stft_fft_kernel(StftCfwdArgs p)
     if (!valid) return;                                      // (no barrier follows)
     const float* __restrict__ Zr = sre[G::RESULT];
     const float* __restrict__ Zi = sim[G::RESULT];
-    float* __restrict__ re = p.re[z] + o;
-    float* __restrict__ im = p.im[z] + o;
 #pragma unroll
     for (int i = 0; i <= M / TPF; ++i) {
         const int k = tl + i * TPF;                          // 0 .. M: the last round is lane 0's k = M
@@ -160,14 +164,34 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void stft_fft_kernel(StftCfwdArgs p)
         const float ar = Zr[fft_swz(ka)], ai = Zi[fft_swz(ka)], cr = Zr[fft_swz(kb)], ci = Zi[fft_swz(kb)];
         const float er = 0.5f * (ar + cr), ei = 0.5f * (ai - ci), odr = 0.5f * (ai + ci), odi = 0.5f * (cr - ar);
         const float wc = tw[k], ws = tw[N + k];
-        re[k] = er + (wc * odr - ws * odi);
-        im[k] = (k == 0 || k == M) ? 0.f : ei + (wc * odi + ws * odr);
+        const float xr = er + (wc * odr - ws * odi);
+        const float xi = (k == 0 || k == M) ? 0.f : ei + (wc * odi + ws * odr);
+        store(z, o + k, xr, xi);
     }
 }
 
-// grid: x = group of FPW frame rows of IstftGemmArgs.  frames[m][n] = w[n] irfft(Re + i Im)[n]; Im of the bins 0 and M is
-// never read.
+// grid: x = group of FPW frame rows, z = signal.  Re and Im of every bin: wun_stft_complex_fft and the filters' analysis.
 template <int LOGM>
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void stft_fft_kernel(StftCfwdArgs p) {
+    fft_fwd_frames<LOGM>(p, [&](int z, long long e, float re, float im) { p.re[z][e] = re; p.im[z][e] = im; });
+}
+
+// The same grid and body with the loss's epilogue (stft_fwd_kernel / stft_fwd_parts_kernel of wun_spectral.hip): the magnitude
+// of every bin, and Re / Im of the signals whose p.a.re[z] is not null.  The framing is p.a's (the loss: lead 0, whole frames).
+template <int LOGM>
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void stft_fft_mag_kernel(StftMagArgs p) {
+    fft_fwd_frames<LOGM>(p.a, [&](int z, long long e, float re, float im) {
+        p.mag[z][e] = sqrtf(fmaf(re, re, im * im));          // (spelled out as in wun_spectral.hip: which product is fused decides the bits)
+        if (p.a.re[z] != nullptr) { p.a.re[z][e] = re; p.a.im[z][e] = im; }
+    });
+}
+
+// grid: x = group of FPW frame rows of IstftGemmArgs.  frames[m][n] = w[n] irfft(Re + i Im)[n]; Im of the bins 0 and M is
+// never read.  ADJ: the unscaled adjoint of the forward transform instead (stft_bwd_kernel's definition, every bin k = 0..M
+// counted ONCE): frames[m][n] = w[n] sum_k re[k] cos(2 pi n k / N) - im[k] sin(2 pi n k / N).  That is the inverse of the spectrum
+// whose bins 0 and M are doubled, times N / 2: the k = 0 point takes 2 re[0] and 2 re[M], and the host passes c_edge = 1 / 2
+// in place of 1 / N -- powers of two, so exact.
+template <int LOGM, bool ADJ>
 __global__ __launch_bounds__(WUN_FFT_BLOCK) void istft_fft_kernel(IstftGemmArgs p) {
     using G = FftGeom<LOGM>;
     constexpr int M = G::M, N = G::N, TPF = G::TPF;
@@ -188,7 +212,7 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void istft_fft_kernel(IstftGemmArgs 
     fft_run<LOGM>([&](int k, float& re, float& im) {         // (Re, Im) = (Im Z', Re Z'): the swap that inverts
         if (!valid) { re = 0.f; im = 0.f; return; }
         if (k == 0) {
-            const float x0 = xr[0], xm = xr[M];
+            const float x0 = ADJ ? 2.f * xr[0] : xr[0], xm = ADJ ? 2.f * xr[M] : xr[M];
             re = x0 - xm; im = x0 + xm;
             return;
         }
@@ -202,7 +226,7 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void istft_fft_kernel(IstftGemmArgs 
     const float* __restrict__ Yr = sre[G::RESULT];
     const float* __restrict__ Yi = sim[G::RESULT];
     float* __restrict__ fr = p.frames + m * N;
-    const float scale = p.c_edge;                            // 1 / n_fft
+    const float scale = p.c_edge;                            // 1 / n_fft (ADJ: 1 / 2)
 #pragma unroll
     for (int i = 0; i < M / TPF; ++i) {
         const int mm = tl + i * TPF;
@@ -211,47 +235,58 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void istft_fft_kernel(IstftGemmArgs 
     }
 }
 
-template <int LOGM>
-static void fwd_launch(const StftCfwdArgs& a, int signals, hipStream_t s) {
-    const long long M = a.M[0] > a.M[1] || signals < 2 ? a.M[0] : a.M[1];
-    const dim3 grid((unsigned)((M + FftGeom<LOGM>::FPW - 1) / FftGeom<LOGM>::FPW), 1u, (unsigned)signals);
-    hipLaunchKernelGGL(stft_fft_kernel<LOGM>, grid, dim3(WUN_FFT_BLOCK), 0, s, a);
-}
-
-template <int LOGM>
-static void inv_launch(const IstftGemmArgs& g, hipStream_t s) {
-    hipLaunchKernelGGL(istft_fft_kernel<LOGM>, dim3((unsigned)((g.M + FftGeom<LOGM>::FPW - 1) / FftGeom<LOGM>::FPW)),
-                       dim3(WUN_FFT_BLOCK), 0, s, g);
-}
-
-int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s) {
-    switch (a.n_fft) {
-        case 64: fwd_launch<5>(a, signals, s); break;
-        case 128: fwd_launch<6>(a, signals, s); break;
-        case 256: fwd_launch<7>(a, signals, s); break;
-        case 512: fwd_launch<8>(a, signals, s); break;
-        case 1024: fwd_launch<9>(a, signals, s); break;
-        case 2048: fwd_launch<10>(a, signals, s); break;
-        case 4096: fwd_launch<11>(a, signals, s); break;
-        case 8192: fwd_launch<12>(a, signals, s); break;
-        default: return fail(WUN_ERR_UNSUPPORTED, "fft_launch_forward: no kernel for this n_fft");
+// f(std::integral_constant<int, log2(n_fft / 2)>) for an n_fft with a kernel; else WUN_ERR_UNSUPPORTED, nothing launched
+template <class F>
+static int fft_dispatch(const char* who, int n_fft, F f) {
+    switch (n_fft) {
+        case 64: f(std::integral_constant<int, 5>()); break;
+        case 128: f(std::integral_constant<int, 6>()); break;
+        case 256: f(std::integral_constant<int, 7>()); break;
+        case 512: f(std::integral_constant<int, 8>()); break;
+        case 1024: f(std::integral_constant<int, 9>()); break;
+        case 2048: f(std::integral_constant<int, 10>()); break;
+        case 4096: f(std::integral_constant<int, 11>()); break;
+        case 8192: f(std::integral_constant<int, 12>()); break;
+        default: return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": no kernel for this n_fft");
     }
     return WUN_OK;
+}
+
+template <int LOGM>
+static dim3 fwd_grid(const StftCfwdArgs& a, int signals) {
+    const long long M = a.M[0] > a.M[1] || signals < 2 ? a.M[0] : a.M[1];
+    return dim3((unsigned)((M + FftGeom<LOGM>::FPW - 1) / FftGeom<LOGM>::FPW), 1u, (unsigned)signals);
+}
+
+template <int LOGM>
+static dim3 inv_grid(const IstftGemmArgs& g) { return dim3((unsigned)((g.M + FftGeom<LOGM>::FPW - 1) / FftGeom<LOGM>::FPW)); }
+
+int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s) {
+    return fft_dispatch("fft_launch_forward", a.n_fft, [&](auto L) {
+        constexpr int LM = decltype(L)::value;
+        hipLaunchKernelGGL(stft_fft_kernel<LM>, fwd_grid<LM>(a, signals), dim3(WUN_FFT_BLOCK), 0, s, a);
+    });
+}
+
+int fft_launch_magnitude(const StftMagArgs& a, int signals, hipStream_t s) {
+    return fft_dispatch("fft_launch_magnitude", a.a.n_fft, [&](auto L) {
+        constexpr int LM = decltype(L)::value;
+        hipLaunchKernelGGL(stft_fft_mag_kernel<LM>, fwd_grid<LM>(a.a, signals), dim3(WUN_FFT_BLOCK), 0, s, a);
+    });
 }
 
 int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s) {
-    switch (g.n_fft) {
-        case 64: inv_launch<5>(g, s); break;
-        case 128: inv_launch<6>(g, s); break;
-        case 256: inv_launch<7>(g, s); break;
-        case 512: inv_launch<8>(g, s); break;
-        case 1024: inv_launch<9>(g, s); break;
-        case 2048: inv_launch<10>(g, s); break;
-        case 4096: inv_launch<11>(g, s); break;
-        case 8192: inv_launch<12>(g, s); break;
-        default: return fail(WUN_ERR_UNSUPPORTED, "fft_launch_inverse: no kernel for this n_fft");
-    }
-    return WUN_OK;
+    return fft_dispatch("fft_launch_inverse", g.n_fft, [&](auto L) {
+        constexpr int LM = decltype(L)::value;
+        hipLaunchKernelGGL((istft_fft_kernel<LM, false>), inv_grid<LM>(g), dim3(WUN_FFT_BLOCK), 0, s, g);
+    });
+}
+
+int fft_launch_adjoint(const IstftGemmArgs& g, hipStream_t s) {
+    return fft_dispatch("fft_launch_adjoint", g.n_fft, [&](auto L) {
+        constexpr int LM = decltype(L)::value;
+        hipLaunchKernelGGL((istft_fft_kernel<LM, true>), inv_grid<LM>(g), dim3(WUN_FFT_BLOCK), 0, s, g);
+    });
 }
 
 }  // namespace wun

@@ -22,8 +22,13 @@
 //              (1024 consecutive bins per partial); the per-source sums run over 1024-bin blocks of EACH SOURCE's own range
 //              first, one block then adds them source by source, and only then the coefficients are formed.
 //
-// ONE forward kernel serves wun_stft_magnitude and wun_spectral_loss: the magnitudes the loss takes its signs from are the
-// floats wun_stft_magnitude returns.  Every reduction index runs in ascending order inside one lane's accumulator, whatever the
+//   transforms the two frame transforms of a resolution are GEMMs (the kernels below) or, in the *_fft entries, FFTs (wun_fft.hip,
+//              launched through wun_fft.h: the forward body with this loss's magnitude epilogue, the inverse body as the unscaled
+//              adjoint).  The host code is ONE body per entry with a transform selector: checks, scratch layout,
+//              the point-wise kernels, the float64 partition and the finish kernels do not know who filled the arrays.
+//
+// ONE forward kernel per transform serves the magnitude entry and the losses: the magnitudes the loss takes its signs from are
+// the floats wun_stft_magnitude (wun_stft_magnitude_fft) returns.  Every reduction index runs in ascending order inside one lane's accumulator, whatever the
 // tile a frame falls in: the bits of a row do not depend on the batch around it, the grid, the scratch contents or pointer
 // alignment.  No atomics.
 //
@@ -371,9 +376,9 @@ namespace {
 
 struct Res { int n_fft, hop, K; long long F, M; };
 
-int make_res(const char* who, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, Res* r) {
+int make_res(const char* who, int tr, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, Res* r) {
     int rc;
-    if ((rc = check_res(who, WUN_TR_GEMM, n_fft, hop, T))) return rc;
+    if ((rc = check_res(who, tr, n_fft, hop, T))) return rc;
     r->n_fft = n_fft; r->hop = hop; r->K = n_fft / 2 + 1;
     r->F = 1 + (T - n_fft) / hop;
     r->M = (long long)S * B * C * r->F;
@@ -385,7 +390,7 @@ int make_res(const char* who, int32_t S, int32_t B, int64_t T, int32_t C, int32_
 long long res_floats(const Res& r) { return 4 * r.M * r.K + r.M * r.n_fft; }
 
 // the argument checks of the two loss entries, in one order; fills res[0 .. nres)
-int check_loss(const char* who, const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+int check_loss(const char* who, int tr, const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
                float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
                const float* const* tables_dev, const float* losses, const float* scratch, Res* res) {
     const std::string w(who);
@@ -396,7 +401,7 @@ int check_loss(const char* who, const float* outputs, const float* targets, int3
     if (nres > 0 && (!n_fft || !hop || !weights || !tables_dev)) return fail(WUN_ERR_INVALID, w + ": null resolution table");
     if (!(mse_weight >= 0.f) || !std::isfinite(mse_weight)) return fail(WUN_ERR_INVALID, w + ": mse_weight negative or not finite");
     for (int j = 0; j < nres; ++j) {
-        if ((rc = make_res(who, S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
+        if ((rc = make_res(who, tr, S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
         if (!(weights[j] >= 0.f) || !std::isfinite(weights[j])) return fail(WUN_ERR_INVALID, w + ": a weight negative or not finite");
         if (!tables_dev[j]) return fail(WUN_ERR_INVALID, w + ": null table");
     }
@@ -422,13 +427,50 @@ long long terms_doubles(const Res& r, int32_t S, const wun_spectral_terms& t) {
     return means * parts_of(E) + (t.sc > 0.f ? 2 * S * parts_of(E / S) + 3 * (long long)S : 0);
 }
 
-void launch_fwd(const float* x0, const float* x1, float* mag0, float* mag1, float* re, float* im, const float* table, int64_t T,
-                int32_t C, const Res& r, hipStream_t s) {
-    StftFwdArgs a;
-    a.x[0] = x0; a.x[1] = x1; a.mag[0] = mag0; a.mag[1] = mag1; a.re = re; a.im = im; a.table = table;
-    a.T = T; a.M = r.M; a.F = (int)r.F; a.C = C; a.n_fft = r.n_fft; a.hop = r.hop; a.K = r.K;
+// The forward transform of one resolution on transform tr (the GEMM tile or the FFT body, one epilogue): the magnitudes of x0
+// (and of x1 unless null), Re / Im of x0 into re0 / im0 and of x1 into re1 / im1 where those are not null.  The GEMM has two
+// kernels: stft_fwd_parts_kernel where the targets' Re / Im are wanted, stft_fwd_kernel otherwise.
+int launch_fwd(int tr, const float* x0, const float* x1, float* mag0, float* mag1, float* re0, float* im0, float* re1, float* im1,
+               const float* table, int64_t T, int32_t C, const Res& r, hipStream_t s) {
+    if (tr == WUN_TR_FFT) {
+        StftMagArgs a;
+        a.a.x[0] = x0; a.a.x[1] = x1; a.a.re[0] = re0; a.a.re[1] = re1; a.a.im[0] = im0; a.a.im[1] = im1;
+        a.a.M[0] = r.M; a.a.M[1] = x1 ? r.M : 0; a.a.table = table;
+        a.a.T = T; a.a.nb = r.F; a.a.f0 = 0; a.a.fstride = r.F; a.a.foff = 0;      // the loss's framing: lead 0, whole frames
+        a.a.C = C; a.a.n_fft = r.n_fft; a.a.hop = r.hop; a.a.lead = 0; a.a.K = r.K;
+        a.mag[0] = mag0; a.mag[1] = mag1;
+        return fft_launch_magnitude(a, x1 ? 2 : 1, s);
+    }
     const dim3 grid((unsigned)((r.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)((r.K + WUN_STFT_BN - 1) / WUN_STFT_BN), x1 ? 2u : 1u);
+    if (re1) {
+        StftFwdPartsArgs a;
+        a.x[0] = x0; a.x[1] = x1; a.mag[0] = mag0; a.mag[1] = mag1; a.re[0] = re0; a.re[1] = re1; a.im[0] = im0; a.im[1] = im1;
+        a.table = table; a.T = T; a.M = r.M; a.F = (int)r.F; a.C = C; a.n_fft = r.n_fft; a.hop = r.hop; a.K = r.K;
+        hipLaunchKernelGGL(stft_fwd_parts_kernel, grid, dim3(WUN_STFT_BLOCK), 0, s, a);
+        return WUN_OK;
+    }
+    StftFwdArgs a;
+    a.x[0] = x0; a.x[1] = x1; a.mag[0] = mag0; a.mag[1] = mag1; a.re = re0; a.im = im0; a.table = table;
+    a.T = T; a.M = r.M; a.F = (int)r.F; a.C = C; a.n_fft = r.n_fft; a.hop = r.hop; a.K = r.K;
     hipLaunchKernelGGL(stft_fwd_kernel, grid, dim3(WUN_STFT_BLOCK), 0, s, a);
+    return WUN_OK;
+}
+
+// dframe[m][n] = sum_k cre[m][k] Cb[n][k] + cim[m][k] Sb[n][k] on transform tr: the transposed GEMM, or the FFT's inverse body
+// as the unscaled adjoint (every bin once, final scale 1 / 2)
+int launch_bwd(int tr, const float* cre, const float* cim, const float* table, float* dframe, const Res& r, hipStream_t s) {
+    if (tr == WUN_TR_FFT) {
+        IstftGemmArgs g;
+        g.re = cre; g.im = cim; g.table = table; g.frames = dframe;
+        g.M = r.M; g.nb = r.M; g.fstride = 0; g.foff = 0;                          // dense rows: the spectrum of row m at m K
+        g.n_fft = r.n_fft; g.K = r.K; g.c_edge = 0.5f; g.c_mid = 0.5f;
+        return fft_launch_adjoint(g, s);
+    }
+    StftBwdArgs b;
+    b.cre = cre; b.cim = cim; b.table = table; b.dframe = dframe; b.M = r.M; b.n_fft = r.n_fft; b.K = r.K;
+    hipLaunchKernelGGL(stft_bwd_kernel, dim3((unsigned)((r.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)(r.n_fft / WUN_STFT_BN)),
+                       dim3(WUN_STFT_BLOCK), 0, s, b);
+    return WUN_OK;
 }
 
 }  // namespace
@@ -467,40 +509,45 @@ extern "C" int wun_stft_design(int32_t n_fft, float* table_host, int64_t cap) {
     return WUN_OK;
 }
 
-extern "C" int wun_stft_magnitude(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
-                                  const float* table_dev, float* mags, void* stream) {
-    if (!x || !table_dev || !mags) return fail(WUN_ERR_INVALID, "wun_stft_magnitude: null argument");
+// ---- the entries: one body each, `who` and the transform tr (WUN_TR_GEMM / WUN_TR_FFT: the n_fft list, the table and the two
+// frame transforms; every check, the scratch layout, the point-wise kernels and the summation order are shared) ----
+namespace {
+
+int magnitude_entry(const char* who, int tr, const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                    const float* table_dev, float* mags, void* stream) {
+    if (!x || !table_dev || !mags) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
     int rc;
     Res r;
-    if ((rc = check_audio("wun_stft_magnitude", S, B, T, C))) return rc;
-    if ((rc = make_res("wun_stft_magnitude", S, B, T, C, n_fft, hop, &r))) return rc;
-    launch_fwd(x, nullptr, mags, nullptr, nullptr, nullptr, table_dev, T, C, r, (hipStream_t)stream);
-    return launch_status("wun_stft_magnitude");
+    if ((rc = check_audio(who, S, B, T, C))) return rc;
+    if ((rc = make_res(who, tr, S, B, T, C, n_fft, hop, &r))) return rc;
+    if ((rc = launch_fwd(tr, x, nullptr, mags, nullptr, nullptr, nullptr, nullptr, nullptr, table_dev, T, C, r, (hipStream_t)stream)))
+        return rc;
+    return launch_status(who);
 }
 
-extern "C" int64_t wun_spectral_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
-                                               const int32_t* hop) {
+int64_t scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                      const int32_t* hop) {
     int rc;
-    if ((rc = check_audio("wun_spectral_scratch_floats", S, B, Tout, C))) return rc;
-    if (nres < 0 || nres > WUN_SPEC_MAX_RES) return fail(WUN_ERR_INVALID, "wun_spectral_scratch_floats: nres outside 0..8");
-    if (nres > 0 && (!n_fft || !hop)) return fail(WUN_ERR_INVALID, "wun_spectral_scratch_floats: null resolution table");
+    if ((rc = check_audio(who, S, B, Tout, C))) return rc;
+    if (nres < 0 || nres > WUN_SPEC_MAX_RES) return fail(WUN_ERR_INVALID, std::string(who) + ": nres outside 0..8");
+    if (nres > 0 && (!n_fft || !hop)) return fail(WUN_ERR_INVALID, std::string(who) + ": null resolution table");
     long long floats = 0, parts = parts_of((long long)S * B * Tout * C);
     for (int j = 0; j < nres; ++j) {
         Res r;
-        if ((rc = make_res("wun_spectral_scratch_floats", S, B, Tout, C, n_fft[j], hop[j], &r))) return rc;
+        if ((rc = make_res(who, tr, S, B, Tout, C, n_fft[j], hop[j], &r))) return rc;
         floats += res_floats(r);
         parts += parts_of(r.M * r.K);
     }
     return floats + 2 * parts + 2;                           // float64 partials, and room to align them to 8 bytes
 }
 
-extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
-                                 float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
-                                 const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream) {
+int loss_entry(const char* who, int tr, const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+               float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+               const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream) {
     int rc;
     Res res[WUN_SPEC_MAX_RES];
-    if ((rc = check_loss("wun_spectral_loss", outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights, tables_dev, losses,
-                         scratch, res)))
+    if ((rc = check_loss(who, tr, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights, tables_dev, losses, scratch,
+                         res)))
         return rc;
 
     hipStream_t s = (hipStream_t)stream;
@@ -529,15 +576,12 @@ extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int
         const long long E = r.M * r.K;
         float* me = base; float* mt = base + E; float* re = base + 2 * E; float* im = base + 3 * E; float* df = base + 4 * E;
         base += res_floats(r);
-        launch_fwd(outputs, targets, me, mt, grad ? re : nullptr, grad ? im : nullptr, tables_dev[j], Tout, C, r, s);
+        if ((rc = launch_fwd(tr, outputs, targets, me, mt, grad ? re : nullptr, grad ? im : nullptr, nullptr, nullptr, tables_dev[j],
+                             Tout, C, r, s)))
+            return rc;
         hipLaunchKernelGGL(spec_l1_kernel, dim3((unsigned)parts_of(E)), blk, 0, s, me, mt, grad ? re : nullptr, grad ? im : nullptr,
                            pnext, E);
-        if (grad) {
-            StftBwdArgs b;
-            b.cre = re; b.cim = im; b.table = tables_dev[j]; b.dframe = df; b.M = r.M; b.n_fft = r.n_fft; b.K = r.K;
-            hipLaunchKernelGGL(stft_bwd_kernel, dim3((unsigned)((r.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)(r.n_fft / WUN_STFT_BN)),
-                               blk, 0, s, b);
-        }
+        if (grad && (rc = launch_bwd(tr, re, im, tables_dev[j], df, r, s))) return rc;
         g.n_fft[j] = r.n_fft; g.hop[j] = r.hop; g.F[j] = (int)r.F; g.dframe[j] = df;
         g.scale[j] = (float)((double)weights[j] / ((double)r.M * (double)r.K));
         fin.part[1 + j] = pnext; fin.nparts[1 + j] = parts_of(E); fin.count[1 + j] = (double)E; fin.weight[1 + j] = weights[j];
@@ -547,19 +591,18 @@ extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int
     if (grad) hipLaunchKernelGGL(spec_grad_kernel<true>, ggrid, blk, 0, s, g);
     else hipLaunchKernelGGL(spec_grad_kernel<false>, ggrid, blk, 0, s, g);
     hipLaunchKernelGGL(spec_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin);
-    return launch_status("wun_spectral_loss");
+    return launch_status(who);
 }
 
-extern "C" int64_t wun_spectral_terms_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
-                                                     const int32_t* hop, const wun_spectral_terms* terms) {
-    const char* who = "wun_spectral_terms_scratch_floats";
+int64_t terms_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                            const int32_t* hop, const wun_spectral_terms* terms) {
     int rc;
     if ((rc = check_audio(who, S, B, Tout, C))) return rc;
     if (nres < 0 || nres > WUN_SPEC_MAX_RES) return fail(WUN_ERR_INVALID, std::string(who) + ": nres outside 0..8");
     if (nres > 0 && (!n_fft || !hop)) return fail(WUN_ERR_INVALID, std::string(who) + ": null resolution table");
     Res res[WUN_SPEC_MAX_RES];
     for (int j = 0; j < nres; ++j)
-        if ((rc = make_res(who, S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
+        if ((rc = make_res(who, tr, S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
     if ((rc = check_terms(who, terms))) return rc;
     long long floats = 0, doubles = parts_of((long long)S * B * Tout * C);
     for (int j = 0; j < nres; ++j) {
@@ -569,14 +612,13 @@ extern "C" int64_t wun_spectral_terms_scratch_floats(int32_t S, int32_t B, int64
     return floats + 2 * doubles + 2;
 }
 
-extern "C" int wun_spectral_loss_terms(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
-                                       float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop,
-                                       const float* weights, const wun_spectral_terms* terms, const float* const* tables_dev,
-                                       float* d_outputs, float* losses, float* scratch, void* stream) {
-    const char* who = "wun_spectral_loss_terms";
+int terms_entry(const char* who, int tr, const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs, float* losses, float* scratch,
+                void* stream) {
     int rc;
     Res res[WUN_SPEC_MAX_RES];
-    if ((rc = check_loss(who, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights, tables_dev, losses, scratch, res)))
+    if ((rc = check_loss(who, tr, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights, tables_dev, losses, scratch, res)))
         return rc;
     if ((rc = check_terms(who, terms))) return rc;
     const wun_spectral_terms tw = *terms;
@@ -615,16 +657,11 @@ extern "C" int wun_spectral_loss_terms(const float* outputs, const float* target
         float* me = base; float* mt = base + E; float* re = base + 2 * E; float* im = base + 3 * E; float* df = base + 4 * E;
         float* ret = base + res_floats(r); float* imt = ret + E;
         base += res_floats(r) + terms_floats(r, tw);
-        if (cx) {
-            StftFwdPartsArgs a;
-            a.x[0] = outputs; a.x[1] = targets; a.mag[0] = me; a.mag[1] = mt; a.re[0] = re; a.re[1] = ret; a.im[0] = im; a.im[1] = imt;
-            a.table = tables_dev[j]; a.T = Tout; a.M = r.M; a.F = (int)r.F; a.C = C; a.n_fft = r.n_fft; a.hop = r.hop; a.K = r.K;
-            hipLaunchKernelGGL(stft_fwd_parts_kernel,
-                               dim3((unsigned)((r.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)((r.K + WUN_STFT_BN - 1) / WUN_STFT_BN), 2u),
-                               blk, 0, s, a);
-        } else {
-            launch_fwd(outputs, targets, me, mt, grad ? re : nullptr, grad ? im : nullptr, tables_dev[j], Tout, C, r, s);
-        }
+        // complex_l1 reads Re / Im of both signals, with or without a gradient; the other terms those of the estimates for the gradient
+        const bool parts = cx || grad;
+        if ((rc = launch_fwd(tr, outputs, targets, me, mt, parts ? re : nullptr, parts ? im : nullptr, cx ? ret : nullptr,
+                             cx ? imt : nullptr, tables_dev[j], Tout, C, r, s)))
+            return rc;
         SpecTermsArgs t;
         t.me = me; t.mt = mt; t.re = re; t.im = im; t.ret = ret; t.imt = imt; t.src = part; t.E = E; t.Es = Es;
         t.w_mag = tw.mag_l1; t.w_log = tw.log_mag_l1; t.w_sc = tw.sc; t.w_cx = tw.complex_l1; t.log_eps = tw.log_eps;
@@ -645,12 +682,7 @@ extern "C" int wun_spectral_loss_terms(const float* outputs, const float* target
             t.src = src; fin.src[j] = src;
         }
         hipLaunchKernelGGL(spec_terms_kernel, dim3((unsigned)np), blk, 0, s, t);
-        if (grad) {
-            StftBwdArgs b;
-            b.cre = re; b.cim = im; b.table = tables_dev[j]; b.dframe = df; b.M = r.M; b.n_fft = r.n_fft; b.K = r.K;
-            hipLaunchKernelGGL(stft_bwd_kernel, dim3((unsigned)((r.M + WUN_STFT_BM - 1) / WUN_STFT_BM), (unsigned)(r.n_fft / WUN_STFT_BN)),
-                               blk, 0, s, b);
-        }
+        if (grad && (rc = launch_bwd(tr, re, im, tables_dev[j], df, r, s))) return rc;
         g.n_fft[j] = r.n_fft; g.hop[j] = r.hop; g.F[j] = (int)r.F; g.dframe[j] = df;
         g.scale[j] = (float)((double)weights[j] / ((double)r.M * (double)r.K));
         fin.count[1 + j] = (double)E; fin.weight[1 + j] = weights[j];
@@ -660,4 +692,61 @@ extern "C" int wun_spectral_loss_terms(const float* outputs, const float* target
     else hipLaunchKernelGGL(spec_grad_kernel<false>, ggrid, blk, 0, s, g);
     hipLaunchKernelGGL(spec_terms_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin);
     return launch_status(who);
+}
+
+}  // namespace
+
+extern "C" int wun_stft_magnitude(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                                  const float* table_dev, float* mags, void* stream) {
+    return magnitude_entry("wun_stft_magnitude", WUN_TR_GEMM, x, S, B, T, C, n_fft, hop, table_dev, mags, stream);
+}
+extern "C" int wun_stft_magnitude_fft(const float* x, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                                      const float* table_dev, float* mags, void* stream) {
+    return magnitude_entry("wun_stft_magnitude_fft", WUN_TR_FFT, x, S, B, T, C, n_fft, hop, table_dev, mags, stream);
+}
+
+extern "C" int64_t wun_spectral_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                               const int32_t* hop) {
+    return scratch_entry("wun_spectral_scratch_floats", WUN_TR_GEMM, S, B, Tout, C, nres, n_fft, hop);
+}
+extern "C" int64_t wun_spectral_fft_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                                   const int32_t* hop) {
+    return scratch_entry("wun_spectral_fft_scratch_floats", WUN_TR_FFT, S, B, Tout, C, nres, n_fft, hop);
+}
+
+extern "C" int wun_spectral_loss(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                 float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                                 const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream) {
+    return loss_entry("wun_spectral_loss", WUN_TR_GEMM, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights,
+                      tables_dev, d_outputs, losses, scratch, stream);
+}
+extern "C" int wun_spectral_loss_fft(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                     float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                                     const float* const* tables_dev, float* d_outputs, float* losses, float* scratch, void* stream) {
+    return loss_entry("wun_spectral_loss_fft", WUN_TR_FFT, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights,
+                      tables_dev, d_outputs, losses, scratch, stream);
+}
+
+extern "C" int64_t wun_spectral_terms_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                                     const int32_t* hop, const wun_spectral_terms* terms) {
+    return terms_scratch_entry("wun_spectral_terms_scratch_floats", WUN_TR_GEMM, S, B, Tout, C, nres, n_fft, hop, terms);
+}
+extern "C" int64_t wun_spectral_terms_fft_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres,
+                                                         const int32_t* n_fft, const int32_t* hop, const wun_spectral_terms* terms) {
+    return terms_scratch_entry("wun_spectral_terms_fft_scratch_floats", WUN_TR_FFT, S, B, Tout, C, nres, n_fft, hop, terms);
+}
+
+extern "C" int wun_spectral_loss_terms(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                       float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop,
+                                       const float* weights, const wun_spectral_terms* terms, const float* const* tables_dev,
+                                       float* d_outputs, float* losses, float* scratch, void* stream) {
+    return terms_entry("wun_spectral_loss_terms", WUN_TR_GEMM, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights,
+                       terms, tables_dev, d_outputs, losses, scratch, stream);
+}
+extern "C" int wun_spectral_loss_terms_fft(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                           float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop,
+                                           const float* weights, const wun_spectral_terms* terms, const float* const* tables_dev,
+                                           float* d_outputs, float* losses, float* scratch, void* stream) {
+    return terms_entry("wun_spectral_loss_terms_fft", WUN_TR_FFT, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop,
+                       weights, terms, tables_dev, d_outputs, losses, scratch, stream);
 }

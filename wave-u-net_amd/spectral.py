@@ -13,6 +13,8 @@ Hann window, no padding), for any number of resolutions up to 8, next to the tim
     re, im = stft(x, 2048, 512, centered=True)         # the complex STFT [S, B, C, F, K]
     x2 = istft(re, im, x.shape[2], 2048, 512, centered=True)      # and its inverse: x again, to fp32 rounding
     re, im = stft(x, 4096, 1024, centered=True, transform="fft")  # the same definitions through an FFT, n_fft up to 8192 (5.13)
+    loss = SpectralLoss([(4096, 1024)], terms={"sc": 1, "log_mag_l1": 1}, log_eps=4.0, transform="fft")    # the loss too (5.16)
+    loss = SpectralLoss.multi_resolution(transform="fft")         # the same three resolutions, both frame transforms as FFTs
 
 Audio is float32 [S, B, T, C] channel-last on the GPU, as get_output stacks its outputs.  There is no CPU path.
 """
@@ -33,12 +35,16 @@ _ENTRIES = {
              "centered_frames": "wun_stft_centered_frames", "stft": "wun_stft_complex", "istft": "wun_istft",
              "istft_scratch": "wun_istft_scratch_floats", "mask_filter": "wun_mask_filter",
              "mask_filter_scratch": "wun_mask_filter_scratch_floats", "wiener_filter": "wun_wiener_filter",
-             "wiener_filter_scratch": "wun_wiener_filter_scratch_floats"},
+             "wiener_filter_scratch": "wun_wiener_filter_scratch_floats", "magnitude": "wun_stft_magnitude",
+             "loss": "wun_spectral_loss", "loss_scratch": "wun_spectral_scratch_floats", "loss_terms": "wun_spectral_loss_terms",
+             "loss_terms_scratch": "wun_spectral_terms_scratch_floats"},
     "fft": {"table": ("wun_fft_table_floats", "wun_fft_design", 3), "frames": "wun_fft_frames",
             "centered_frames": "wun_fft_centered_frames", "stft": "wun_stft_complex_fft", "istft": "wun_istft_fft",
             "istft_scratch": "wun_istft_fft_scratch_floats", "mask_filter": "wun_mask_filter_fft",
             "mask_filter_scratch": "wun_mask_filter_fft_scratch_floats", "wiener_filter": "wun_wiener_filter_fft",
-            "wiener_filter_scratch": "wun_wiener_filter_fft_scratch_floats"},
+            "wiener_filter_scratch": "wun_wiener_filter_fft_scratch_floats", "magnitude": "wun_stft_magnitude_fft",
+            "loss": "wun_spectral_loss_fft", "loss_scratch": "wun_spectral_fft_scratch_floats",
+            "loss_terms": "wun_spectral_loss_terms_fft", "loss_terms_scratch": "wun_spectral_terms_fft_scratch_floats"},
 }
 _TABLES = {}     # (transform, n_fft, device) -> device tensor holding the transform's table
 
@@ -113,16 +119,18 @@ def _audio(x, what):
     return x.to(torch.float32).contiguous()
 
 
-def stft_magnitude(x, n_fft, hop):
+def stft_magnitude(x, n_fft, hop, transform="gemm"):
     """|STFT| of audio x [S, B, T, C]: float32 [S, B, C, F, K], K = n_fft // 2 + 1 bins, F = frames(T, n_fft, hop) frames of
-    the periodic-Hann-windowed signal without padding (wun_stft_magnitude).  One launch on the current stream, no sync."""
+    the periodic-Hann-windowed signal without padding (wun_stft_magnitude; transform="fft": wun_stft_magnitude_fft, n_fft up
+    to 8192).  The floats a SpectralLoss of the same transform takes its signs from.  One launch on the current stream, no sync."""
+    fn, table = entry(transform, "magnitude")
     x = _audio(x, "x")
     S, B, T, Cn = (int(v) for v in x.shape)
-    F = frames(T, n_fft, hop)
+    F = frames(T, n_fft, hop, transform)
     mags = torch.empty((S, B, Cn, F, int(n_fft) // 2 + 1), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(_lib.load().wun_stft_magnitude(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop),
-                                                  _table(n_fft, x.device).data_ptr(), mags.data_ptr(), _stream(x.device)))
+        _lib.check(fn(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), table(n_fft, x.device).data_ptr(), mags.data_ptr(),
+                      _stream(x.device)))
     return mags
 
 
@@ -191,9 +199,17 @@ class SpectralLoss(object):
     "sc" the spectral convergence sqrt(sum d^2 / (sum M_tgt^2 + sc_eps)) per source, averaged over the sources, "complex_l1"
     mean |STFT_est - STFT_tgt|.  losses is then [2 + 5 nres]: [total, MSE, L_0 .., then mag_l1, log_mag_l1, sc, complex_l1 of
     resolution 0, of resolution 1, ..] (term_losses).  log_eps and sc_eps are choices, not measurements: 1e-3 sits above the
-    fp32 transform's error on unit-scale audio at short frames (raise it with n_fft), 1.0 keeps a silent source finite."""
+    fp32 transform's error on unit-scale audio at short frames (raise it with n_fft), 1.0 keeps a silent source finite.
 
-    def __init__(self, resolutions=((1024, 768),), weights=None, mse_weight=0.0, terms=None, log_eps=1e-3, sc_eps=1.0):
+    transform="gemm": both frame transforms of a resolution as GEMMs against an n_fft^2 table, n_fft up to 2048.  "fft": as
+    FFTs (the *_fft entries), n_fft up to 8192 -- the same definitions, slots and summation order, results
+    equal to float32 rounding.  ValueError for any other name."""
+
+    def __init__(self, resolutions=((1024, 768),), weights=None, mse_weight=0.0, terms=None, log_eps=1e-3, sc_eps=1.0,
+                 transform="gemm"):
+        if transform not in _ENTRIES:
+            raise ValueError("transform must be one of %s, got %r" % (", ".join(TRANSFORMS), transform))
+        self.transform = transform
         self.resolutions = [(int(n), int(h)) for n, h in resolutions]
         if len(self.resolutions) > MAX_RESOLUTIONS:
             raise ValueError("at most %d resolutions, got %d" % (MAX_RESOLUTIONS, len(self.resolutions)))
@@ -227,19 +243,22 @@ class SpectralLoss(object):
     @classmethod
     def from_config(cls, spec):
         """model_config["spectral_loss"]: None, a SpectralLoss, or a dict with `resolutions`, `weights`, `mse_weight`, `terms`,
-        `log_eps`, `sc_eps`."""
+        `log_eps`, `sc_eps`, `transform`."""
         if spec is None or isinstance(spec, cls):
             return spec
-        unknown = set(spec) - {"resolutions", "weights", "mse_weight", "terms", "log_eps", "sc_eps"}
+        unknown = set(spec) - {"resolutions", "weights", "mse_weight", "terms", "log_eps", "sc_eps", "transform"}
         if unknown:
             raise ValueError("spectral_loss: unknown keys %s" % sorted(unknown))
         return cls(spec.get("resolutions", ((1024, 768),)), spec.get("weights"), spec.get("mse_weight", 0.0), spec.get("terms"),
-                   spec.get("log_eps", 1e-3), spec.get("sc_eps", 1.0))
+                   spec.get("log_eps", 1e-3), spec.get("sc_eps", 1.0), spec.get("transform", "gemm"))
 
     @classmethod
-    def multi_resolution(cls):
-        """The usual multi-resolution STFT loss: spectral convergence + log-magnitude L1 at 512 / 128, 1024 / 256, 2048 / 512."""
-        return cls([(512, 128), (1024, 256), (2048, 512)], terms={"sc": 1.0, "log_mag_l1": 1.0})
+    def multi_resolution(cls, transform="gemm", resolutions=None):
+        """The usual multi-resolution STFT loss: spectral convergence + log-magnitude L1 at 512 / 128, 1024 / 256, 2048 / 512
+        (or at `resolutions`; transform="fft" admits n_fft up to 8192)."""
+        if resolutions is None:
+            resolutions = [(512, 128), (1024, 256), (2048, 512)]
+        return cls(resolutions, terms={"sc": 1.0, "log_mag_l1": 1.0}, transform=transform)
 
     @property
     def num_losses(self):
@@ -256,15 +275,10 @@ class SpectralLoss(object):
 
     def scratch_floats(self, shape):
         S, B, T, Cn = (int(v) for v in shape)
-        lib = _lib.load()
+        args = (S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop)
         if self._terms is None:
-            n = int(lib.wun_spectral_scratch_floats(S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop))
-        else:
-            n = int(lib.wun_spectral_terms_scratch_floats(S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop,
-                                                          C.byref(self._terms)))
-        if n < 0:
-            _lib.check(n)
-        return n
+            return count(self.transform, "loss_scratch", *args)
+        return count(self.transform, "loss_terms_scratch", *(args + (C.byref(self._terms),)))
 
     def _scratch_for(self, x):
         key = (tuple(x.shape), str(x.device))
@@ -273,20 +287,20 @@ class SpectralLoss(object):
         return self._scratch[key]
 
     def run(self, outputs, targets, d_outputs, losses, scratch):
-        """wun_spectral_loss (with terms: wun_spectral_loss_terms) on the caller's buffers (contiguous float32 device tensors;
-        losses of num_losses floats; d_outputs may be None)."""
+        """wun_spectral_loss (with terms: wun_spectral_loss_terms; transform="fft": their _fft twins) on the caller's buffers
+        (contiguous float32 device tensors; losses of num_losses floats; d_outputs may be None)."""
         S, B, T, Cn = (int(v) for v in outputs.shape)
         dev = outputs.device
         nres = len(self.resolutions)
-        tabs = (C.c_void_p * max(nres, 1))(*[_table(n, dev).data_ptr() for n, _ in self.resolutions])
+        fn, table = entry(self.transform, "loss" if self._terms is None else "loss_terms")
+        tabs = (C.c_void_p * max(nres, 1))(*[table(n, dev).data_ptr() for n, _ in self.resolutions])
         head = (outputs.data_ptr(), targets.data_ptr(), S, B, T, Cn, self.mse_weight, nres, self._n_fft, self._hop, self._w)
         tail = (tabs, d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(), _stream(dev))
-        lib = _lib.load()
         with torch.cuda.device(dev):
             if self._terms is None:
-                _lib.check(lib.wun_spectral_loss(*(head + tail)))
+                _lib.check(fn(*(head + tail)))
             else:
-                _lib.check(lib.wun_spectral_loss_terms(*(head + (C.byref(self._terms),) + tail)))
+                _lib.check(fn(*(head + (C.byref(self._terms),) + tail)))
 
     def loss_and_grad(self, outputs, targets, grad=True):
         """(losses, d_outputs): losses float32 [num_losses] on the device = [total, MSE, L_0, ...] (L_j unweighted; with terms
@@ -324,9 +338,9 @@ class _StftL1(torch.autograd.Function):
         return (d_outputs * g).to(ctx.dtype), None, None       # (the targets carry no gradient)
 
 
-def stft_l1(outputs, targets, loss=None, resolutions=((1024, 768),), weights=None, mse_weight=0.0):
+def stft_l1(outputs, targets, loss=None, resolutions=((1024, 768),), weights=None, mse_weight=0.0, transform="gemm"):
     """The total of a SpectralLoss (`loss`, or one built from the other arguments) as a 0-dim tensor under torch.autograd:
     backward gives d total / d outputs as wun_spectral_loss computes it; the targets get no gradient."""
     if loss is None:
-        loss = SpectralLoss(resolutions, weights, mse_weight)
+        loss = SpectralLoss(resolutions, weights, mse_weight, transform=transform)
     return _StftL1.apply(outputs, targets, loss)

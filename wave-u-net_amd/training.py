@@ -63,8 +63,9 @@ class Trainer(object):
     L1 at resolution j) (Training.py:55-60; wun_spectral_loss, then the backward pass from its gradient).  step() returns the
     total; last_losses holds [total, MSE, L_0, ...] of the step (device tensor, the mean over the micro-batches).  With
     `terms` (and `log_eps`, `sc_eps`) L_j is the weighted sum of mag_l1, log_mag_l1, sc and complex_l1 (wun_spectral_loss_terms,
-    DESIGN.md 5.14), last_losses carries the per-term slots and train.jsonl a `spectral_terms` entry (term_parts).  None:
-    exactly the old calls.
+    DESIGN.md 5.14), last_losses carries the per-term slots and train.jsonl a `spectral_terms` entry (term_parts).  With
+    `"transform": "fft"` the loss's frame transforms are FFTs and n_fft may reach 8192 (`{"resolutions": [[4096, 1024]],
+    "transform": "fft", ...}`); "gemm" is the default.  None: exactly the old calls.
 
     waveform_loss (or model_config["waveform_loss"], default None): a dict with `terms` {"mse" | "l1" | "si_sdr" | "snr": weight},
     `eps` and `zero_mean`, or a waveform.WaveformLoss (wun_waveform_loss).  Alone, the step minimises the
