@@ -805,7 +805,87 @@ int wun_scatter_windows(const wun_plan* plan, const float* outputs, const int64_
 int wun_separate_track(const wun_plan* plan, const float* params, const float* track_tc, int64_t n_frames,
                        float* workspace, float* outputs, float* preds, void* stream);
 
+/* ---- the spectrogram U-Net baseline, inference only ------------------------
+ * The reference's other separator (Models/UnetSpectrogramSeparator.py:40-108, configs unet_spectrogram / unet_spectrogram_l1)
+ * at training = False: per source one U-Net of 5 x 5 stride-2 convolutions over log1p of the mixture's STFT magnitude, whose
+ * sigmoid mask multiplies the mixture's spectrogram.  Mono, channel-last: activations are [B, F, n_fft / 2, C] (TF's NHWC).
+ *   X = STFT(mix[b, :, 0]) in the spectral section's framing without padding (F = 1 + (T - n_fft) / hop frames, K = n_fft / 2 + 1
+ *   bins, periodic Hann; computed by the FFT of wun_stft_complex_fft);  M = |X|;  A0[b][f][k] = log1p(M[b][f][k]) for k < K - 1.
+ *   down i = 0..L-1 : conv 5 x 5 stride 2, "same" = 1 before and 2 after (out[y][x] = sum A[2y + ky - 1][2x + kx - 1][ci]
+ *                     W[ky][kx][ci][co], zeros outside) to nif 2^i channels, + bias, batch norm, LeakyReLU(0.2); levels i < L - 1
+ *                     are kept as skips
+ *   up i = 0..L-2   : transposed conv 5 x 5 stride 2 "same" (the gradient of the conv above: out[t] = sum over 2 j + k - 1 == t of
+ *                     A[j] W[k] per axis, t in [0, 2 N)) to nif 2^(L-i-2) channels, + bias, batch norm, ReLU; then the channel
+ *                     concatenation [skip_{L-2-i}, that], skip first
+ *   mask            : sigmoid(transposed conv to 1 channel + bias); the dropped bin K - 1 gets 0.5
+ *   batch norm      : (z - moving_mean) / sqrt(moving_variance + 1e-3) + beta -- no gamma
+ *   mags[s] = M mask_s, [S][B][F][K];  audio[s] = ISTFT_tf(mask_s X), [S][B][T][1] (wun_istft_tf_fft below)
+ * Shape conditions (else WUN_ERR_INVALID, before any GPU work): T == (F - 1) hop + n_fft, F and n_fft / 2 multiples of 2^L.
+ * The convolutions run on the exact-fp32 MFMA (the first down layer and the mask layer, thin GEMMs, on the VALU with the same
+ * bits), the reduction in ascending (ky, kx, ci) order in one accumulator per output, no atomics: an excerpt's bits do not depend
+ * on the batch around it, the grid, what the workspace held or pointer alignment beyond 4 bytes.  Every buffer is the caller's;
+ * nothing allocates or synchronises; every argument check runs before any GPU work.  Training this model (batch statistics,
+ * dropout, the 2-D backward), stereo and a bf16 mode are not built. */
+typedef struct wun_spec_config {
+    int32_t num_layers;          /* L in 1..10 */
+    int32_t num_initial_filters; /* nif; nif 2^(L-1) <= 65536 */
+    int32_t num_sources;         /* 1..8 (the reference asserts 2, UnetSpectrogramSeparator.py:24) */
+    int32_t n_fft;               /* a power of two in 64..8192 (the reference: 1024) */
+    int32_t hop;                 /* 1..n_fft (the reference: 768) */
+} wun_spec_config;
+/* sizeof(wun_spec_config) as the library was compiled (wun_abi_sizes keeps its three entries). */
+int64_t wun_spec_abi_size(void);
+/* The variable table: tf.layers / tf.contrib.layers names in graph-construction order inside scope "separator", an index 0
+ * without suffix; for source s: conv2d_{s L + i}/kernel [5, 5, Cin, Cout] and /bias, BatchNorm_{s (2L - 1) + j}/beta,
+ * /moving_mean, /moving_variance (j = i on the down path, L + i on the up path), conv2d_transpose_{s L + i}/kernel
+ * [5, 5, Cout, Cin] and /bias (i = L - 1: the mask layer).  Offsets are floats into one flat params buffer of
+ * wun_spec_param_floats floats, packed in table order.  Negative wun_status for a bad config or index. */
+int64_t wun_spec_num_tensors(const wun_spec_config* cfg);
+int64_t wun_spec_param_floats(const wun_spec_config* cfg);
+int     wun_spec_tensor(const wun_spec_config* cfg, int64_t index, wun_tensor_info* info);
+/* F for T samples, or WUN_ERR_INVALID where the shape conditions fail; host only. */
+int64_t wun_spec_frames(const wun_spec_config* cfg, int64_t T);
+/* floats of `workspace` for wun_spec_forward: X, M, A0, the activations of one source's network, the mask, the masked spectra of
+ * all sources and wun_istft_tf_fft's scratch.  Negative wun_status as wun_spec_forward for the same arguments. */
+int64_t wun_spec_workspace_floats(const wun_spec_config* cfg, int32_t B, int64_t T);
+/*   params    : device, wun_spec_param_floats floats
+ *   mix       : device, [B, T, 1]
+ *   table_dev : device copy of wun_fft_design's table of n_fft (3 n_fft floats)
+ *   audio     : device [S, B, T, 1] or NULL;  mags : device [S, B, F, K] or NULL (return_spectrogram); at least one
+ * WUN_ERR_INVALID for a null pointer, both outputs null, the shape conditions, B < 1 or a workspace that overlaps another
+ * buffer; WUN_ERR_UNSUPPORTED for an n_fft outside the list, sizes beyond the limits above, or a resolution wun_istft_tf_fft refuses. */
+int     wun_spec_forward(const wun_spec_config* cfg, const float* params, const float* mix, int32_t B, int64_t T,
+                         const float* table_dev, float* audio, float* mags, float* workspace, void* stream);
+
+/* tf.contrib.signal.inverse_stft with inverse_stft_window_fn(hop): wun_istft in the framing without padding (lead 0), except for
+ * the normaliser:  y[t] = (sum_f frame_f[t - f hop]) / D[t mod hop],  D[p] = sum_i w^2[p + i hop] over 0 <= p + i hop < n_fft
+ * (i ascending, float64) -- the steady-state window-square sum, at the track's edges too, where wun_istft divides by the sum
+ * over the covering frames only.  Frames, table, scratch formula, contract, checks and their order are wun_istft's (lead = 0);
+ * then WUN_ERR_UNSUPPORTED for a resolution where some D[p] is below 1e-8 (1024 / 768: min D = 2 sin^4(pi / 8) = 0.0429).  Samples no frame covers
+ * are 0.  wun_istft_tf_fft: the same on wun_istft_fft (the table of wun_fft_design, n_fft up to 8192). */
+int64_t wun_istft_tf_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int64_t F);
+int     wun_istft_tf(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                     int64_t F, const float* table_dev, float* y, float* scratch, void* stream);
+int64_t wun_istft_tf_fft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int64_t F);
+int     wun_istft_tf_fft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                         int64_t F, const float* table_dev, float* y, float* scratch, void* stream);
+
 /* ---- single operators (used by the parity tests and for per-kernel profiling) ---------- */
+
+/* One layer of the spectrogram U-Net, channel-last float32.  y = act(bn(conv + bias)):
+ *   x [B][H][W][cin], w [5][5][cin][cout] (TF layout), y [B][H / 2][W / 2][cout]; H and W even
+ *   bias [cout] or NULL;  bn_mean, bn_var, bn_beta [cout], all three or none: (z - mean) / sqrt(var + 1e-3) + beta
+ *   act : 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 sigmoid
+ * cin == 1 runs on the VALU, everything else on the exact-fp32 MFMA; same accumulation order, same bits.
+ * WUN_ERR_INVALID before any GPU work for a null x / w / y, a size below 1, odd H or W, an unknown act or a partial batch norm. */
+int wun_op_conv2d_s2(const float* x, const float* w, const float* bias, const float* bn_mean, const float* bn_var,
+                     const float* bn_beta, float* y, int B, int H, int W, int cin, int cout, int act, void* stream);
+/* The transposed layer: the input is the virtual channel concatenation of x0 [B][H][W][c0] and (optionally) x1 [B][H][W][c1],
+ * w [5][5][cout][c0 + c1] (TF layout), y [B][2 H][2 W][cout], every float written once; epilogue as above.  cout == 1 runs on
+ * the VALU.  WUN_ERR_INVALID also for c0 < 1, c1 < 0, or x1 given without c1 (and the reverse). */
+int wun_op_conv2d_transpose_s2(const float* x0, int c0, const float* x1, int c1, const float* w, const float* bias,
+                               const float* bn_mean, const float* bn_var, const float* bn_beta, float* y, int B, int H, int W,
+                               int cout, int act, void* stream);
 
 /* y[b][co][q] = act(bias[co] + sum_{k,ci} w[k][ci][co] * x[b][ci][q*stride + k - pad_left]),
  * x zero outside [0, t_in).  NCW float32, w in TF layout [K, Cin, Cout].

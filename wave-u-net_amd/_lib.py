@@ -40,6 +40,10 @@ class WunWaveformTerms(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("mse", "l1", "si_sdr", "snr", "eps")] + [("zero_mean", C.c_int32)]
 
 
+class WunSpecConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_layers", "num_initial_filters", "num_sources", "n_fft", "hop")]
+
+
 _P = C.c_void_p
 _SIGS = {
     "wun_get_padding": (C.c_int, [C.POINTER(WunConfig), C.c_int64, C.POINTER(C.c_int64),
@@ -139,6 +143,21 @@ _SIGS = {
     "wun_spectral_loss_terms_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                               C.POINTER(WunSpectralTerms), C.POINTER(C.c_void_p), _P, _P, _P, _P]),
+    "wun_spec_abi_size": (C.c_int64, []),
+    "wun_spec_num_tensors": (C.c_int64, [C.POINTER(WunSpecConfig)]),
+    "wun_spec_param_floats": (C.c_int64, [C.POINTER(WunSpecConfig)]),
+    "wun_spec_tensor": (C.c_int, [C.POINTER(WunSpecConfig), C.c_int64, C.POINTER(WunTensorInfo)]),
+    "wun_spec_frames": (C.c_int64, [C.POINTER(WunSpecConfig), C.c_int64]),
+    "wun_spec_workspace_floats": (C.c_int64, [C.POINTER(WunSpecConfig), C.c_int32, C.c_int64]),
+    "wun_spec_forward": (C.c_int, [C.POINTER(WunSpecConfig), _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
+    "wun_istft_tf_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "wun_istft_tf": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                               _P, _P, _P, _P]),
+    "wun_istft_tf_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "wun_istft_tf_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                   _P, _P, _P, _P]),
+    "wun_op_conv2d_s2": (C.c_int, [_P] * 7 + [C.c_int] * 6 + [_P]),
+    "wun_op_conv2d_transpose_s2": (C.c_int, [_P, C.c_int, _P, C.c_int] + [_P] * 6 + [C.c_int] * 5 + [_P]),
     "wun_separate_positions": (C.c_int64, [C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64]),
     "wun_forward_windows": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, _P, _P, C.c_int, _P]),
     "wun_scatter_windows": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, _P, C.c_int64, _P]),
@@ -200,6 +219,9 @@ def load():
     mine = (C.sizeof(WunConfig), C.sizeof(WunPlanInfo), C.sizeof(WunTensorInfo))
     if tuple(sizes) != mine:
         raise RuntimeError("libwun.so struct sizes %s != this binding's %s (stale library or binding)" % (tuple(sizes), mine))
+    if lib.wun_spec_abi_size() != C.sizeof(WunSpecConfig):
+        raise RuntimeError("libwun.so wun_spec_config size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_spec_abi_size(), C.sizeof(WunSpecConfig)))
     _lib = lib
     return lib
 

@@ -54,9 +54,13 @@ EXTENSION_DEFAULTS = {
     # "kind": "wiener" (and "iterations": 1, "em_eps": 1e-10) postfilter.WienerFilter, the multichannel Wiener filter
     # "transform": "fft" computes the transforms with an FFT: n_fft up to 8192 instead of 2048
     "postfilter": None,
+    # spectrogram.UnetSpectrogramSeparator: the STFT framing of the spectrogram U-Net (UnetSpectrogramSeparator.py:28-29 fixes
+    # 1024 / 768); other values exist so that tests can run small geometries
+    "spec_frame_len": 1024,
+    "spec_hop": 768,
 }
 
-NAMED_CONFIGS = {                # Config.py:52-161 (the Wave-U-Net ones)
+NAMED_CONFIGS = {                # Config.py:52-161
     "baseline": {},
     "baseline_diff": {"output_type": "difference"},
     "baseline_context": {"output_type": "difference", "context": True},
@@ -74,6 +78,12 @@ NAMED_CONFIGS = {                # Config.py:52-161 (the Wave-U-Net ones)
     "baseline_comparison": {"batch_size": 4, "output_type": "difference", "context": True,
                             "num_frames": 768 * 127 + 1024, "duration": 13,
                             "expected_sr": 8192, "num_initial_filters": 34},   # Config.py:123-134
+    # the spectrogram U-Net baseline (spectrogram.UnetSpectrogramSeparator: inference only)
+    "unet_spectrogram": {"batch_size": 4, "network": "unet_spectrogram", "num_layers": 6, "expected_sr": 8192,
+                         "num_frames": 768 * 127 + 1024, "duration": 13, "num_initial_filters": 16},     # Config.py:136-147
+    "unet_spectrogram_l1": {"batch_size": 4, "network": "unet_spectrogram", "num_layers": 6, "expected_sr": 8192,
+                            "num_frames": 768 * 127 + 1024, "duration": 13, "num_initial_filters": 16,
+                            "raw_audio_loss": False},                                                    # Config.py:149-161
     # BASELINE.json configs[1]: the M1 architecture run with input context (~147k samples in)
     "m1_context": {"context": True},
     # BASELINE.json configs[4]: 16 levels / 48 base channels, stereo, 4 sources, same padding,

@@ -121,6 +121,9 @@ struct OlaArgs {
 
 // one lane per output float: the frames that cover the sample in ascending f, over the window squares of the same frames;
 // 0 where those sum to less than 1e-8 (librosa's rule).  Grid-stride: the grid is capped, one writer per float all the same.
+// STEADY (wun_istft_tf): the denominator is the steady-state window-square sum D[u mod hop] = sum_i w^2[u mod hop + i hop] over
+// the places inside the frame, i ascending -- what tf.contrib.signal.inverse_stft_window_fn divides by, at the track's edges too.
+template <bool STEADY>
 __global__ __launch_bounds__(WUN_STFT_BLOCK) void istft_ola_kernel(OlaArgs p) {
     const long long span = (p.t_hi - p.t_lo) * p.C;
     for (long long e = (long long)blockIdx.x * WUN_STFT_BLOCK + threadIdx.x; e < p.N; e += (long long)gridDim.x * WUN_STFT_BLOCK) {
@@ -136,8 +139,10 @@ __global__ __launch_bounds__(WUN_STFT_BLOCK) void istft_ola_kernel(OlaArgs p) {
         for (long long f = f_lo; f <= f_hi; ++f) {
             const long long n = u - f * p.hop;
             a += fr[(f - p.fb0) * p.n_fft + n];
-            ws += p.wsq[n];
+            if (!STEADY) ws += p.wsq[n];
         }
+        if (STEADY)
+            for (long long n = u % p.hop; n < p.n_fft; n += p.hop) ws += p.wsq[n];
         p.y[(sb * p.T + t) * p.C + c] = ws < 1e-8 ? 0.f : a / (float)ws;
     }
 }
@@ -360,13 +365,13 @@ int launch_gemm(int tr, const float* re, const float* im, const float* table, fl
 }
 
 void launch_ola(const float* frames, const double* wsq, float* y, long long SB, int64_t T, int32_t C, int64_t F, const Blk& b,
-                int32_t n_fft, int32_t hop, int32_t lead, hipStream_t s) {
+                int32_t n_fft, int32_t hop, int32_t lead, hipStream_t s, bool steady = false) {
     OlaArgs o;
     o.frames = frames; o.wsq = wsq; o.y = y; o.T = T; o.F = F; o.nb = b.nb; o.fb0 = b.fb0; o.t_lo = b.t_lo; o.t_hi = b.t_hi;
     o.N = SB * (b.t_hi - b.t_lo) * C; o.C = C; o.n_fft = n_fft; o.hop = hop; o.lead = lead;
     long long grid = (o.N + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK;
     if (grid > (1 << 20)) grid = 1 << 20;
-    hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)grid), dim3(WUN_STFT_BLOCK), 0, s, o);
+    hipLaunchKernelGGL(steady ? istft_ola_kernel<true> : istft_ola_kernel<false>, dim3((unsigned)grid), dim3(WUN_STFT_BLOCK), 0, s, o);
 }
 
 void launch_window(double* wsq, int32_t n_fft, hipStream_t s) {
@@ -427,13 +432,37 @@ int64_t istft_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64
     return (int64_t)S * B * C * block_frames(F, n_fft, hop) * n_fft + 2 * (int64_t)n_fft + 2;
 }
 
+// the smallest steady-state window-square sum D[p] = sum_i w^2[p + i hop] of a resolution (float64, host): wun_istft_tf divides
+// by D and refuses a resolution where some D[p] is below 1e-8
+double steady_min(int32_t n_fft, int32_t hop) {
+    double dmin = INFINITY;
+    for (int p = 0; p < hop; ++p) {
+        double d = 0.0;
+        for (int n = p; n < n_fft; n += hop) {
+            const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)n / (double)n_fft);
+            d += w * w;
+        }
+        if (d < dmin) dmin = d;
+    }
+    return dmin;
+}
+
+int check_steady(const char* who, int32_t n_fft, int32_t hop) {
+    if (steady_min(n_fft, hop) < 1e-8)
+        return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": a steady-state window-square sum of this n_fft / hop is below 1e-8");
+    return WUN_OK;
+}
+
+// steady: wun_istft_tf's normaliser (istft_ola_kernel<true>) in place of the sum over the covering frames
 int istft_entry(const char* who, int tr, const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft,
-                int32_t hop, int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
+                int32_t hop, int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream,
+                bool steady = false) {
     if (!re || !im || !table_dev || !y || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
     int rc;
     if ((rc = check_audio(who, S, B, T, C))) return rc;
     if ((rc = check_res(who, tr, n_fft, hop))) return rc;
     if ((rc = check_framing(who, S, B, C, n_fft, lead, F))) return rc;
+    if (steady && (rc = check_steady(who, n_fft, hop))) return rc;
     const long long R = (long long)S * B * C, E = R * F * (n_fft / 2 + 1);
     if (overlaps(y, R * T, re, E) || overlaps(y, R * T, im, E))
         return fail(WUN_ERR_INVALID, std::string(who) + ": y overlaps re or im");
@@ -446,7 +475,7 @@ int istft_entry(const char* who, int tr, const float* re, const float* im, int32
         const Blk b = block_of(f0, F, T, n_fft, hop, lead);
         if (b.t_lo >= b.t_hi) continue;                      // no sample ends in this block
         if ((rc = launch_gemm(tr, re, im, table_dev, frames, R, b.nb, F, b.fb0, n_fft, s))) return rc;
-        launch_ola(frames, wsq, y, (long long)S * B, T, C, F, b, n_fft, hop, lead, s);
+        launch_ola(frames, wsq, y, (long long)S * B, T, C, F, b, n_fft, hop, lead, s, steady);
     }
     return launch_status(who);
 }
@@ -603,6 +632,31 @@ extern "C" int wun_istft(const float* re, const float* im, int32_t S, int32_t B,
 extern "C" int wun_istft_fft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
                              int32_t lead, int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
     return istft_entry("wun_istft_fft", WUN_TR_FFT, re, im, S, B, T, C, n_fft, hop, lead, F, table_dev, y, scratch, stream);
+}
+
+// tf.contrib.signal.inverse_stft with inverse_stft_window_fn(hop): wun_istft in the loss's framing (lead 0) with the
+// steady-state normaliser; the scratch is wun_istft's
+namespace {
+int64_t istft_tf_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int64_t F) {
+    const int64_t n = istft_scratch_entry(who, tr, S, B, T, C, n_fft, hop, 0, F);
+    if (n < 0) return n;
+    const int rc = check_steady(who, n_fft, hop);
+    return rc ? rc : n;
+}
+}  // namespace
+extern "C" int64_t wun_istft_tf_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int64_t F) {
+    return istft_tf_scratch_entry("wun_istft_tf_scratch_floats", WUN_TR_GEMM, S, B, T, C, n_fft, hop, F);
+}
+extern "C" int64_t wun_istft_tf_fft_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int64_t F) {
+    return istft_tf_scratch_entry("wun_istft_tf_fft_scratch_floats", WUN_TR_FFT, S, B, T, C, n_fft, hop, F);
+}
+extern "C" int wun_istft_tf(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                            int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
+    return istft_entry("wun_istft_tf", WUN_TR_GEMM, re, im, S, B, T, C, n_fft, hop, 0, F, table_dev, y, scratch, stream, true);
+}
+extern "C" int wun_istft_tf_fft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
+                                int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
+    return istft_entry("wun_istft_tf_fft", WUN_TR_FFT, re, im, S, B, T, C, n_fft, hop, 0, F, table_dev, y, scratch, stream, true);
 }
 
 extern "C" int64_t wun_mask_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {

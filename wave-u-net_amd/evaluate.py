@@ -142,6 +142,9 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     the model's rate to the estimates and the resampled mix before the resampling back -- the estimates then share the
     mix's phase and sum to it."""
     from . import resample as rs
+    if model_config.get("network") == "unet_spectrogram" and hop_frames is not None:
+        raise NotImplementedError("hop_frames: the spectrogram U-Net separates in hops of num_frames only (its frame count is "
+                                  "tied to num_layers); the plan-based long hops are Wave-U-Net only")
     if postfilter is not None:
         from .postfilter import from_config
         postfilter = from_config(postfilter)
@@ -227,11 +230,11 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
     import os
     from scipy.io import wavfile
     from . import datasets
-    from .separator import UnetAudioSeparator
+    from .spectrogram import make_separator
     audio, sr = datasets.read_audio(input_path)                    # Utils.load(input_path, sr=None, mono=False), :172
     if sr is None:
         sr = model_config["expected_sr"]
-    sep = separator if separator is not None else UnetAudioSeparator(model_config)
+    sep = separator if separator is not None else make_separator(model_config)
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
@@ -314,8 +317,8 @@ def produce_dataset_estimates(model_config, load_model, data_root, output_path, 
     import os
     from scipy.io import wavfile
     from . import bsseval, datasets
-    from .separator import UnetAudioSeparator
-    sep = separator if separator is not None else UnetAudioSeparator(model_config)
+    from .spectrogram import make_separator
+    sep = separator if separator is not None else make_separator(model_config)
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)

@@ -33,14 +33,16 @@ TRANSFORMS = ("gemm", "fft")
 _ENTRIES = {
     "gemm": {"table": ("wun_stft_table_floats", "wun_stft_design", 2), "frames": "wun_stft_frames",
              "centered_frames": "wun_stft_centered_frames", "stft": "wun_stft_complex", "istft": "wun_istft",
-             "istft_scratch": "wun_istft_scratch_floats", "mask_filter": "wun_mask_filter",
+             "istft_scratch": "wun_istft_scratch_floats", "istft_tf": "wun_istft_tf",
+             "istft_tf_scratch": "wun_istft_tf_scratch_floats", "mask_filter": "wun_mask_filter",
              "mask_filter_scratch": "wun_mask_filter_scratch_floats", "wiener_filter": "wun_wiener_filter",
              "wiener_filter_scratch": "wun_wiener_filter_scratch_floats", "magnitude": "wun_stft_magnitude",
              "loss": "wun_spectral_loss", "loss_scratch": "wun_spectral_scratch_floats", "loss_terms": "wun_spectral_loss_terms",
              "loss_terms_scratch": "wun_spectral_terms_scratch_floats"},
     "fft": {"table": ("wun_fft_table_floats", "wun_fft_design", 3), "frames": "wun_fft_frames",
             "centered_frames": "wun_fft_centered_frames", "stft": "wun_stft_complex_fft", "istft": "wun_istft_fft",
-            "istft_scratch": "wun_istft_fft_scratch_floats", "mask_filter": "wun_mask_filter_fft",
+            "istft_scratch": "wun_istft_fft_scratch_floats", "istft_tf": "wun_istft_tf_fft",
+            "istft_tf_scratch": "wun_istft_tf_fft_scratch_floats", "mask_filter": "wun_mask_filter_fft",
             "mask_filter_scratch": "wun_mask_filter_fft_scratch_floats", "wiener_filter": "wun_wiener_filter_fft",
             "wiener_filter_scratch": "wun_wiener_filter_fft_scratch_floats", "magnitude": "wun_stft_magnitude_fft",
             "loss": "wun_spectral_loss_fft", "loss_scratch": "wun_spectral_fft_scratch_floats",
@@ -184,6 +186,29 @@ def istft(re, im, length, n_fft, hop, centered=False, transform="gemm"):
     y = torch.empty((S, B, int(length), Cn), dtype=torch.float32, device=re.device)
     with torch.cuda.device(re.device):
         _lib.check(fn(re.data_ptr(), im.data_ptr(), S, B, int(length), Cn, int(n_fft), int(hop), lead, F,
+                      table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
+    return y
+
+
+def istft_tf(re, im, n_fft, hop, transform="gemm"):
+    """Audio [S, B, (F - 1) hop + n_fft, C] from re, im [S, B, C, F, K] in the loss's framing, as
+    tf.contrib.signal.inverse_stft with inverse_stft_window_fn(hop) gives it (wun_istft_tf): istft's frames over the steady-state
+    window-square sum D[t mod hop], at the track's edges too.  NotImplementedError where some D is below 1e-8.
+    transform="fft": wun_istft_tf_fft, n_fft up to 8192.  No sync."""
+    if not (torch.is_tensor(re) and torch.is_tensor(im) and re.is_cuda and im.is_cuda):
+        raise ValueError("re and im must be tensors on the GPU (there is no CPU path)")
+    if re.dim() != 5 or re.shape != im.shape or re.device != im.device or int(re.shape[4]) != int(n_fft) // 2 + 1:
+        raise ValueError("re and im must be [S, B, C, F, n_fft / 2 + 1] of one shape and device, got %s and %s" % (
+            tuple(re.shape), tuple(im.shape)))
+    re, im = re.to(torch.float32).contiguous(), im.to(torch.float32).contiguous()
+    S, B, Cn, F, _ = (int(v) for v in re.shape)
+    T = (F - 1) * int(hop) + int(n_fft)
+    fn, table = entry(transform, "istft_tf")
+    n = count(transform, "istft_tf_scratch", S, B, T, Cn, int(n_fft), int(hop), F)
+    scratch = torch.empty(n, dtype=torch.float32, device=re.device)
+    y = torch.empty((S, B, T, Cn), dtype=torch.float32, device=re.device)
+    with torch.cuda.device(re.device):
+        _lib.check(fn(re.data_ptr(), im.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), F,
                       table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
     return y
 

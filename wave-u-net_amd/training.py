@@ -282,6 +282,9 @@ def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
 def train(model_config, experiment_id, load_model=None, batch_source=None, log_every=None):
     """Training.train(model_config, experiment_id, load_model=None) -> save_path
     (Training.py:24-25,121)."""
+    if model_config["network"] == "unet_spectrogram":
+        raise NotImplementedError("unet_spectrogram: the spectrogram U-Net is built for inference only (predict, test, "
+                                  "evaluate); training it is out of scope")
     if model_config["network"] != "unet":
         raise NotImplementedError(model_config["network"])         # Training.py:28-33
     if log_every is None:

@@ -19,6 +19,8 @@ import torch
 
 from . import datasets
 from .separator import UnetAudioSeparator
+from .spectrogram import make_separator
+from . import spectral
 from .training import train
 from .checkpoint import load_checkpoint
 from . import waveform
@@ -39,13 +41,18 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     model_config["waveform_loss"], grad=False); the same running mean, and test.jsonl gains "metric" and the per-source dB.
     ValueError for any other value but "mse"."""
     metric = waveform.validation_metric(model_config)
-    if model_config["network"] != "unet":
+    if model_config["network"] not in ("unet", "unet_spectrogram"):
         raise NotImplementedError(model_config["network"])                        # Test.py:14-19
+    # Test.py:34,63-68: the spectrogram U-Net with raw_audio_loss=False returns magnitudes, scored by their L1 distance to the
+    # targets' STFT magnitudes (the same objective as Training.py:55-60)
+    spec_l1 = model_config["network"] == "unet_spectrogram" and not model_config["raw_audio_loss"]
+    if spec_l1 and metric != "mse":
+        raise ValueError("validation_metric=%r needs audio; the spectrogram U-Net with raw_audio_loss=False returns magnitudes" % metric)
     if tracks is None:
         if data_root is None:
             raise ValueError("test() needs `tracks` or `data_root`")
         tracks = datasets.load_partition(data_root, partition, model_config, resample)
-    sep = separator if separator is not None else UnetAudioSeparator(model_config)
+    sep = separator if separator is not None else make_separator(model_config)
     disc_input_shape = [model_config["batch_size"], model_config["num_frames"], 0]
     in_shape, out_shape = sep.get_padding(np.array(disc_input_shape))            # Test.py:21
     assert (in_shape[1] - out_shape[1]) % 2 == 0                                  # Test.py:25
@@ -56,13 +63,20 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     si_loss = waveform.validation_loss(model_config) if metric == "si_sdr" else None
     source_db = np.zeros(len(names))                                              # running means of the per-source dB
     for batch in datasets.get_dataset(model_config, in_shape, out_shape, partition, tracks):
-        outs = sep.get_output(batch["mix"], False)                                # Test.py:34
+        outs = sep.get_output(batch["mix"], False, spec_l1)                       # Test.py:34
         if si_loss is not None:
             est = torch.stack([outs[key] for key in names])
             real = torch.stack([torch.as_tensor(batch[key], device=est.device) for key in names])
             losses, _ = si_loss.loss_and_grad(est, real, grad=False)
             curr = float(losses[0].item())                                        # -(mean SI-SDR in dB)
             source_db += (1.0 / float(batch_num)) * (si_loss.source_metrics(losses)["si_sdr"].cpu().numpy() - source_db)
+        elif spec_l1:                                                             # Test.py:63-68
+            loss = 0.0
+            for key in names:
+                real = torch.as_tensor(batch[key], dtype=torch.float32, device=outs[key].device)      # [B, T, 1]
+                real_mag = spectral.stft_magnitude(real[None], sep.frame_len, sep.hop)[0, :, 0]       # [B, F, K]
+                loss = loss + torch.mean(torch.abs(real_mag - outs[key]))
+            curr = float(loss.item()) / float(model_config["num_sources"])
         else:
             loss = 0.0
             for key in names:                                                     # Test.py:61-74
