@@ -876,6 +876,7 @@ int     wun_istft_tf_fft(const float* re, const float* im, int32_t S, int32_t B,
  *   x [B][H][W][cin], w [5][5][cin][cout] (TF layout), y [B][H / 2][W / 2][cout]; H and W even
  *   bias [cout] or NULL;  bn_mean, bn_var, bn_beta [cout], all three or none: (z - mean) / sqrt(var + 1e-3) + beta
  *   act : 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 sigmoid
+ *         a NaN before the activation comes out as NaN from all four (ReLU is z > 0 ? z : (z != z ? z : 0), as torch.relu and TF's)
  * cin == 1 runs on the VALU, everything else on the exact-fp32 MFMA; same accumulation order, same bits.
  * WUN_ERR_INVALID before any GPU work for a null x / w / y, a size below 1, odd H or W, an unknown act or a partial batch norm. */
 int wun_op_conv2d_s2(const float* x, const float* w, const float* bias, const float* bn_mean, const float* bn_var,

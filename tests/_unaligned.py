@@ -10,3 +10,14 @@ def _offset_copy(x):
     v.copy_(x)
     assert v.data_ptr() % 8 == 4 and v.is_contiguous()
     return v
+
+
+def _offset_full(shape, value, dtype=torch.float32, device="cuda"):
+    """An output view at such a pointer, every element `value` (NaN: an element the kernel leaves unwritten shows)."""
+    n = 1
+    for s in shape:
+        n *= int(s)
+    buf = torch.full((n + 1,), value, dtype=dtype, device=device)
+    v = buf[1:].view(*shape)
+    assert v.data_ptr() % 8 == 4 and v.is_contiguous()
+    return v

@@ -22,7 +22,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _specunet_np as ora  # noqa: E402
 from _observed import record  # noqa: E402
-from _unaligned import _offset_copy  # noqa: E402
+from _fma_chain_np import chain, conv_weights, gather_conv, gather_transpose, transpose_weights  # noqa: E402
+from _unaligned import _offset_copy, _offset_full  # noqa: E402
 
 from wave_u_net_amd import _lib  # noqa: E402
 
@@ -37,6 +38,12 @@ CONV_CASES = [
     (1, 8, 16, 3, 17),      # both off the 16 tile
     (3, 6, 10, 16, 32),
     (1, 2, 34, 33, 16),     # reduction off any chunk; a row tile crossing image rows
+    (2, 10, 14, 3, 40),     # M = 70: two row tiles (the second of 6 rows), an excerpt boundary inside the first; two column
+                            # tiles (the second of 8 columns); a reduction of 75 = three chunks, the last of 11
+    (1, 18, 16, 5, 70),     # M = 72; three column tiles, 6 columns in the last
+    (1, 4, 6, 5, 1),        # Cout == 1 with Cin > 1: one live column on the MFMA
+    (1, 2, 2, 4, 3),        # a map smaller than the filter, on the MFMA
+    (1, 16, 18, 1, 33),     # the VALU kernel over several workgroups (2376 outputs)
 ]
 # (B, H, W, c0, c1, Cout): the input is [c0 + c1] channels, given as two ranges when c1 > 0
 TRANSPOSE_CASES = [
@@ -46,6 +53,12 @@ TRANSPOSE_CASES = [
     (2, 3, 5, 3, 5, 7),     # two ranges
     (1, 4, 6, 16, 16, 16),
     (1, 4, 8, 3, 5, 1),     # two ranges into the mask layer
+    (2, 5, 7, 3, 2, 40),    # M = 70 per class: two row tiles, two column tiles, two ranges
+    (1, 9, 8, 5, 0, 70),    # M = 72; three column tiles
+    (1, 3, 4, 1, 0, 5),     # Cin == 1 on the MFMA: a reduction of 4 to 9, less than one staged chunk
+    (1, 1, 5, 4, 0, 3),     # a one-row map on the MFMA
+    (1, 5, 1, 4, 0, 3),     # a one-column map on the MFMA
+    (1, 16, 18, 2, 3, 1),   # the VALU kernel over several workgroups per class (288 outputs each)
 ]
 
 
@@ -67,28 +80,38 @@ def _dev(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
 
 
-def run_conv(lib, x, w, bias=None, bn=None, act=None, xdev=None):
-    """numpy in, numpy out; xdev: a device tensor to read x from instead."""
+def _place(name, a, off):
+    """A device copy of a numpy operand; one float behind an allocation's start if `off` names it."""
+    d = _dev(a)
+    return _offset_copy(d) if d is not None and name in off else d
+
+
+def run_conv(lib, x, w, bias=None, bn=None, act=None, xdev=None, off=()):
+    """numpy in, numpy out; xdev: a device tensor to read x from instead; off: the operands (of x, w, bias, mean, var, beta, y) to
+    place at a pointer that is 4-byte but not 8-byte aligned."""
     B, H, W, ci = x.shape
     co = w.shape[3]
-    xd = xdev if xdev is not None else _dev(x)
-    wd, bd = _dev(w), _dev(bias)
-    bnd = [_dev(a) for a in bn] if bn is not None else [None] * 3
-    y = torch.full((B, H // 2, W // 2, co), float("nan"), dtype=torch.float32, device="cuda")
+    xd = xdev if xdev is not None else _place("x", x, off)
+    wd, bd = _place("w", w, off), _place("bias", bias, off)
+    bnd = [_place(n, a, off) for n, a in zip(("mean", "var", "beta"), bn)] if bn is not None else [None] * 3
+    shape = (B, H // 2, W // 2, co)
+    y = _offset_full(shape, float("nan")) if "y" in off else torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")
     _lib.check(lib.wun_op_conv2d_s2(xd.data_ptr(), wd.data_ptr(), _ptr(bd), _ptr(bnd[0]), _ptr(bnd[1]), _ptr(bnd[2]), y.data_ptr(),
                                     B, H, W, ci, co, ACTS[act], _stream()))
     torch.cuda.synchronize()
     return y.cpu().numpy()
 
 
-def run_transpose(lib, x0, x1, w, bias=None, bn=None, act=None, x0dev=None):
+def run_transpose(lib, x0, x1, w, bias=None, bn=None, act=None, x0dev=None, off=()):
+    """off: as run_conv, of x0, x1, w, bias, mean, var, beta, y."""
     B, H, W, c0 = x0.shape
     c1 = 0 if x1 is None else x1.shape[3]
     co = w.shape[2]
-    x0d = x0dev if x0dev is not None else _dev(x0)
-    x1d, wd, bd = _dev(x1), _dev(w), _dev(bias)
-    bnd = [_dev(a) for a in bn] if bn is not None else [None] * 3
-    y = torch.full((B, 2 * H, 2 * W, co), float("nan"), dtype=torch.float32, device="cuda")
+    x0d = x0dev if x0dev is not None else _place("x0", x0, off)
+    x1d, wd, bd = _place("x1", x1, off), _place("w", w, off), _place("bias", bias, off)
+    bnd = [_place(n, a, off) for n, a in zip(("mean", "var", "beta"), bn)] if bn is not None else [None] * 3
+    shape = (B, 2 * H, 2 * W, co)
+    y = _offset_full(shape, float("nan")) if "y" in off else torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")
     _lib.check(lib.wun_op_conv2d_transpose_s2(x0d.data_ptr(), c0, _ptr(x1d), c1, wd.data_ptr(), _ptr(bd), _ptr(bnd[0]), _ptr(bnd[1]),
                                               _ptr(bnd[2]), y.data_ptr(), B, H, W, co, ACTS[act], _stream()))
     torch.cuda.synchronize()
@@ -235,6 +258,187 @@ def test_valu_and_mfma_kernels_agree_bit_for_bit(lib):
     w2 = np.concatenate([w, 0.5 * w], axis=2)
     wide = run_transpose(lib, x, None, w2, np.concatenate([bias, bias]))
     assert np.array_equal(thin[..., 0].view(np.uint32), wide[..., 0].view(np.uint32))
+
+
+# ---------------------------------------------------------------------------------------------------- the promised order
+def _id(case):
+    return "x".join(map(str, case))
+
+
+def _assert_bits(name, got, want):
+    assert got.shape == want.shape and np.isfinite(got).all()
+    differ = int((got.view(np.uint32) != want.view(np.uint32)).sum())
+    record(name, "outputs with other bits", differ, 0.0)
+    assert differ == 0
+
+
+@pytest.mark.parametrize("case", CONV_CASES, ids=_id)
+def test_conv2d_is_the_ascending_fmaf_chain(lib, case):
+    """include/wun.h: "reduction in ascending (ky, kx, ci) order in one accumulator per output", VALU and MFMA "same bits" --
+    against tests/_fma_chain_np.py, which states that order in exact arithmetic and shares nothing with the kernels."""
+    x, w, _ = _conv_fixture(case, seed=4)
+    got = run_conv(lib, x, w)
+    want = chain(gather_conv(x), conv_weights(w)).reshape(got.shape)
+    _assert_bits("test_conv2d_is_the_ascending_fmaf_chain[%s]" % _id(case), got, want)
+
+
+@pytest.mark.parametrize("case", TRANSPOSE_CASES, ids=_id)
+def test_conv2d_transpose_is_the_ascending_fmaf_chain(lib, case):
+    x, w, _ = _transpose_fixture(case, seed=4)
+    c0, c1 = case[3], case[4]
+    got = run_transpose(lib, np.ascontiguousarray(x[..., :c0]), np.ascontiguousarray(x[..., c0:]) if c1 else None, w)
+    want = chain(gather_transpose(x), transpose_weights(w)).reshape(got.shape)
+    _assert_bits("test_conv2d_transpose_is_the_ascending_fmaf_chain[%s]" % _id(case), got, want)
+
+
+# ---------------------------------------------------------------------------------------------------- the receptive field
+def _probe_pixels(H, W):
+    """The four corners, one element on each edge, one interior element."""
+    return [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (0, W // 2), (H - 1, 1), (H // 2, 0), (1, W - 1), (H // 2, W // 2 - 1)]
+
+
+def _assert_footprint(got, clean, mask, what):
+    """NaN exactly on mask [B, H, W] (every channel), the clean run's bits everywhere else."""
+    nan = np.isnan(got)
+    assert np.array_equal(nan, np.broadcast_to(mask[..., None], got.shape)), what
+    assert np.array_equal(got.view(np.uint32)[~nan], clean.view(np.uint32)[~nan]), what
+
+
+@pytest.mark.parametrize("case", [(2, 10, 14, 3, 40), (2, 4, 6, 1, 5)], ids=["mfma", "valu"])
+def test_conv2d_footprint(lib, case):
+    """Output (b, y, x, any co) depends on input (b, iy, ix, any ci) exactly when 2y - 1 <= iy <= 2y + 3 and 2x - 1 <= ix <= 2x + 3:
+    one NaN in the input must come out there and nowhere else, and all other outputs keep their bits."""
+    B, H, W, ci, co = case
+    x, w, bias = _conv_fixture(case, seed=6)
+    clean = run_conv(lib, x, w, bias)
+    assert np.isfinite(clean).all()
+    y, xx = np.arange(H // 2), np.arange(W // 2)
+    for b in range(B):
+        for k, (iy, ix) in enumerate(_probe_pixels(H, W)):
+            xp = x.copy()
+            xp[b, iy, ix, k % ci] = np.nan
+            mask = np.zeros((B, H // 2, W // 2), bool)
+            mask[b] = ((2 * y - 1 <= iy) & (iy <= 2 * y + 3))[:, None] & ((2 * xx - 1 <= ix) & (ix <= 2 * xx + 3))[None, :]
+            assert mask.any()
+            _assert_footprint(run_conv(lib, xp, w, bias), clean, mask, (b, iy, ix))
+    # one NaN in the weights of one output channel (in the second column tile where there is one): that channel alone
+    wp = w.copy()
+    wp[2, 3, ci - 1, co - 2] = np.nan
+    got = run_conv(lib, x, wp, bias)
+    keep = np.arange(co) != co - 2
+    assert np.isnan(got[..., co - 2]).all()                  # (a tap outside the map enters as 0 x NaN)
+    assert np.array_equal(got[..., keep].view(np.uint32), clean[..., keep].view(np.uint32))
+
+
+@pytest.mark.parametrize("case", [(2, 5, 7, 3, 2, 40), (1, 16, 18, 2, 3, 1)], ids=["mfma", "valu"])
+def test_conv2d_transpose_footprint(lib, case):
+    """Output (b, ty, tx) depends on input (b, iy, ix) of either range exactly when ty = 2 iy + ky - 1 and tx = 2 ix + kx - 1 for
+    some ky, kx in 0..4."""
+    B, H, W, c0, c1, co = case
+    x, w, bias = _transpose_fixture(case, seed=6)
+    split = lambda a: (np.ascontiguousarray(a[..., :c0]), np.ascontiguousarray(a[..., c0:]))   # noqa: E731
+    clean = run_transpose(lib, *split(x), w, bias)
+    assert np.isfinite(clean).all()
+    ty, tx = np.arange(2 * H), np.arange(2 * W)
+    for b in range(B):
+        for k, (iy, ix) in enumerate(_probe_pixels(H, W)):
+            my = np.zeros(2 * H, bool)
+            mx = np.zeros(2 * W, bool)
+            for kk in range(5):
+                my |= ty == 2 * iy + kk - 1
+                mx |= tx == 2 * ix + kk - 1
+            mask = np.zeros((B, 2 * H, 2 * W), bool)
+            mask[b] = my[:, None] & mx[None, :]
+            for ch in (k % c0, c0 + k % c1):                 # an element of x0, an element of x1
+                xp = x.copy()
+                xp[b, iy, ix, ch] = np.nan
+                _assert_footprint(run_transpose(lib, *split(xp), w, bias), clean, mask, (b, iy, ix, ch))
+    wp = w.copy()
+    n = max(co - 2, 0)
+    wp[2, 3, n, c0 + c1 - 1] = np.nan
+    got = run_transpose(lib, *split(x), wp, bias)
+    keep = np.arange(co) != n
+    assert np.isnan(got[..., n]).any()
+    assert np.array_equal(got[..., keep].view(np.uint32), clean[..., keep].view(np.uint32))
+    # the tap (2, 3) is one of the class (odd ty, even tx) only
+    assert np.isnan(got[:, 1::2, 0::2, n]).all() and not np.isnan(got[:, 0::2, :, n]).any() and not np.isnan(got[:, :, 1::2, n]).any()
+
+
+# ---------------------------------------------------------------------------------------------------- every operand's alignment
+EVERY_CONV_OPERAND = ("x", "w", "bias", "mean", "var", "beta", "y")
+EVERY_TRANSPOSE_OPERAND = ("x0", "x1", "w", "bias", "mean", "var", "beta", "y")
+
+
+@pytest.mark.parametrize("off", [EVERY_CONV_OPERAND, ("w",), ("y",)], ids=["all", "w", "y"])
+@pytest.mark.parametrize("case", [(2, 4, 6, 1, 5), (2, 10, 14, 3, 40)], ids=["valu", "mfma"])
+def test_conv2d_bits_do_not_depend_on_any_operands_alignment(lib, case, off):
+    x, w, bias = _conv_fixture(case, seed=7)
+    bn = _bn(case[4], 8)
+    aligned = run_conv(lib, x, w, bias, bn, "lrelu")
+    moved = run_conv(lib, x, w, bias, bn, "lrelu", off=off)
+    assert np.isfinite(aligned).all() and np.array_equal(aligned.view(np.uint32), moved.view(np.uint32))
+
+
+@pytest.mark.parametrize("off", [EVERY_TRANSPOSE_OPERAND, ("w",), ("y",)], ids=["all", "w", "y"])
+@pytest.mark.parametrize("case", [(1, 4, 8, 3, 5, 1), (2, 5, 7, 3, 2, 40)], ids=["valu", "mfma"])
+def test_conv2d_transpose_bits_do_not_depend_on_any_operands_alignment(lib, case, off):
+    x, w, bias = _transpose_fixture(case, seed=7)
+    c0 = case[3]
+    bn = _bn(case[5], 8)
+    x0, x1 = np.ascontiguousarray(x[..., :c0]), np.ascontiguousarray(x[..., c0:])
+    aligned = run_transpose(lib, x0, x1, w, bias, bn, "relu")
+    moved = run_transpose(lib, x0, x1, w, bias, bn, "relu", off=off)
+    assert np.isfinite(aligned).all() and np.array_equal(aligned.view(np.uint32), moved.view(np.uint32))
+
+
+# ---------------------------------------------------------------------------------------------------- non-finite values
+SPECIALS = np.array([np.nan, np.inf, -np.inf, 1.0, -1.0, -0.0], dtype=np.float32)
+
+
+def _run_specials(lib, kind, bn, act):
+    """Zero weights on a 2 x 2 map, the bias SPECIALS: every output pixel of channel n is the epilogue of SPECIALS[n].
+    -> [pixels, 6]"""
+    rng = np.random.RandomState(11)
+    if kind == "conv-valu" or kind == "conv-mfma":
+        ci = 1 if kind == "conv-valu" else 2
+        x = rng.randn(1, 2, 2, ci).astype(np.float32)
+        return run_conv(lib, x, np.zeros((5, 5, ci, 6), np.float32), SPECIALS, bn, act).reshape(-1, 6)
+    x = rng.randn(1, 2, 2, 2).astype(np.float32)
+    if kind == "transpose-mfma":
+        return run_transpose(lib, x, None, np.zeros((5, 5, 6, 2), np.float32), SPECIALS, bn, act).reshape(-1, 6)
+    cols = []                                                # Cout == 1 is what sends the transposed conv to the VALU: a call per value
+    for n in range(6):
+        one = None if bn is None else [a[n:n + 1] for a in bn]
+        cols.append(run_transpose(lib, x, None, np.zeros((5, 5, 1, 2), np.float32), SPECIALS[n:n + 1], one, act).reshape(-1))
+    return np.stack(cols, axis=1)
+
+
+@pytest.mark.parametrize("with_bn", [False, True], ids=["plain", "bn"])
+@pytest.mark.parametrize("act", [None, "lrelu", "relu", "sigmoid"], ids=["none", "lrelu", "relu", "sigmoid"])
+@pytest.mark.parametrize("kind", ["conv-valu", "conv-mfma", "transpose-valu", "transpose-mfma"])
+def test_non_finite_values_go_through_the_epilogue(lib, kind, act, with_bn):
+    """NaN, +Inf and -Inf at the pre-activation come out as the oracle's epilogue makes them in float32 (torch.relu and TF's ReLU
+    propagate NaN; so must the kernels' -- a corrupted checkpoint must not be repaired silently).  Finite values: without batch
+    norm the epilogue of these inputs is exact or one rounding (0.2 z), so the float32 oracle's bits; with batch norm or the sigmoid
+    the kernel and the float32 oracle each lie within the module docstring's bound (e = 0: the pre-activation is exact) of the
+    exact value, so within twice that of each other."""
+    bn = _bn(6, 12) if with_bn else None
+    got = _run_specials(lib, kind, bn, act)
+    z32 = torch.zeros(6, dtype=torch.float32)
+    want = ora.epilogue(z32, torch.from_numpy(SPECIALS), None if bn is None else [torch.from_numpy(a) for a in bn], act).numpy()
+    assert want.dtype == np.float32 and np.isnan(want[0]) and not np.isnan(want[1:]).any()
+    want = np.broadcast_to(want, got.shape)
+    assert np.array_equal(np.isnan(got), np.isnan(want))
+    inf = np.isinf(want)
+    assert np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], want[inf])
+    fin = np.isfinite(want)
+    if bn is None and act != "sigmoid":
+        assert np.array_equal(got[fin].view(np.uint32), np.ascontiguousarray(want[fin]).view(np.uint32))
+    else:
+        with np.errstate(invalid="ignore", over="ignore"):
+            _, bound = _epilogue_bound(SPECIALS.astype(np.float64), np.zeros(6), bn, act)
+        bound = np.broadcast_to(bound, got.shape)
+        assert (np.abs(got[fin].astype(np.float64) - want[fin]) <= 2 * bound[fin]).all()
 
 
 # ---------------------------------------------------------------------------------------------------- refusals

@@ -13,6 +13,8 @@ strictly ascending order and the CPU's blocked order differ, and a 12-layer chai
 import os
 import sys
 
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -21,9 +23,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _specunet_np as ora  # noqa: E402
 import _postfilter_np as pf  # noqa: E402
 from _observed import record  # noqa: E402
+from _unaligned import _offset_copy, _offset_full  # noqa: E402
 
 import wave_u_net_amd as wun  # noqa: E402
-from wave_u_net_amd import checkpoint, datasets, evaluate, spectral, validation  # noqa: E402
+from wave_u_net_amd import _lib, checkpoint, datasets, evaluate, spectral, validation  # noqa: E402
 from wave_u_net_amd.spectrogram import UnetSpectrogramSeparator  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -267,3 +270,171 @@ def test_predict_track_returns_the_tracks_length():
     dev = evaluate.separate_track(cfg, sep, audio, cfg["expected_sr"])
     for k in preds:
         assert dev[k].shape == (n, 1) and np.array_equal(dev[k], preds[k])
+
+
+# ---------------------------------------------------------------------------------------------------- wun_spec_forward, directly
+# The separator class asks the entry for two sources and one output at a time, into an uninitialised workspace.  The entry
+# allows 1..8 sources and both outputs in one call and promises that its bits do not depend on what the workspace held, on
+# pointer alignment beyond 4 bytes or on the stream: these tests call it through the C ABI with buffers of their own.
+GUARD = 64                                                   # floats before and after a guarded buffer
+GUARD_BITS = 0x7FC0BEEF                                      # a NaN no arithmetic produces
+
+
+class _Direct(object):
+    """wun_spec_forward on a geometry of GEOMETRIES for S sources: the flat params buffer filled from wun_spec_tensor's table."""
+
+    def __init__(self, geo, S, seed=None):
+        self.lib = _lib.load()
+        self.n_fft, self.hop, self.L, self.nif, self.F, self.B = GEOMETRIES[geo]
+        self.S, self.K, self.T = S, self.n_fft // 2 + 1, (self.F - 1) * self.hop + self.n_fft
+        self.cfg = _lib.WunSpecConfig(self.L, self.nif, S, self.n_fft, self.hop)
+        self.vars = ora.random_variables(self.L, self.nif, seed=(31 + self.L + S) if seed is None else seed, S=S)
+        n, info = int(self.lib.wun_spec_num_tensors(C.byref(self.cfg))), _lib.WunTensorInfo()
+        host = np.full(int(self.lib.wun_spec_param_floats(C.byref(self.cfg))), np.nan, np.float32)
+        for i in range(n):
+            _lib.check(self.lib.wun_spec_tensor(C.byref(self.cfg), i, C.byref(info)))
+            v = self.vars[info.name.decode()]
+            assert v.shape == tuple(int(info.shape[d]) for d in range(info.ndim))
+            host[info.offset:info.offset + v.size] = v.reshape(-1)
+        assert n == len(self.vars) and np.isfinite(host).all()             # packed: every float of the buffer belongs to a tensor
+        self.params = torch.from_numpy(host).cuda()
+        self.mix_host = _fixture(geo)["mix"]
+        self.mix = torch.from_numpy(self.mix_host).cuda()
+        self.table = spectral._fft_table(self.n_fft, self.mix.device)
+        self.ws_floats = int(self.lib.wun_spec_workspace_floats(C.byref(self.cfg), self.B, self.T))
+        assert self.ws_floats > 0
+
+    def shapes(self):
+        return (self.S, self.B, self.T, 1), (self.S, self.B, self.F, self.K)
+
+    def buffers(self, audio=True, mags=True):
+        """Fresh NaN-filled outputs (an unwritten float shows) and workspace."""
+        sa, sm = self.shapes()
+        nan = float("nan")
+        return (torch.full(sa, nan, device="cuda") if audio else None, torch.full(sm, nan, device="cuda") if mags else None,
+                torch.full((self.ws_floats,), nan, device="cuda"))
+
+    def run(self, audio, mags, ws, mix=None, params=None):
+        """One call on the current stream; the outputs as numpy (None for an output not asked for)."""
+        mix = self.mix if mix is None else mix
+        params = self.params if params is None else params
+        stream = torch.cuda.current_stream()
+        _lib.check(self.lib.wun_spec_forward(C.byref(self.cfg), params.data_ptr(), mix.data_ptr(), self.B, self.T, self.table.data_ptr(),
+                                             None if audio is None else audio.data_ptr(), None if mags is None else mags.data_ptr(),
+                                             ws.data_ptr(), C.c_void_p(stream.cuda_stream)))
+        stream.synchronize()
+        return tuple(None if t is None else t.cpu().numpy() for t in (audio, mags))
+
+    def both(self):
+        """(audio, mags) of the plain call: both outputs at once, aligned buffers, the default stream.  Computed once."""
+        if not hasattr(self, "_both"):
+            self._both = self.run(*self.buffers())
+            assert all(np.isfinite(a).all() for a in self._both)
+        return self._both
+
+
+_DIRECT = {}
+
+
+def _direct(geo, S):
+    if (geo, S) not in _DIRECT:
+        _DIRECT[(geo, S)] = _Direct(geo, S)
+    return _DIRECT[(geo, S)]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+@pytest.mark.parametrize("S", [1, 3])
+def test_other_source_counts_against_float64(S):
+    """S = 1 and S = 3 (the table arithmetic s L + i, s (2L - 1) + j beyond S = 2), audio and magnitudes, under the bound rule of
+    this file: 8 x the float32-CPU oracle's own error, floored at 2^-20 max |output|."""
+    d = _direct("skip", S)
+    got = dict(zip((False, True), d.both()))
+    for spec in (False, True):
+        o64, _, _ = ora.forward(d.mix_host, d.vars, d.L, d.nif, d.n_fft, d.hop, S=S, return_spectrogram=spec)
+        o32, _, _ = ora.forward(d.mix_host, d.vars, d.L, d.nif, d.n_fft, d.hop, S=S, dtype=torch.float32, return_spectrogram=spec)
+        want, o32 = np.stack(o64), np.stack(o32)
+        stand_in = np.abs(o32 - want).max()
+        bound = max(8.0 * stand_in, 2.0 ** -20 * np.abs(want).max())
+        g = got[spec][..., 0] if not spec else got[spec]
+        assert g.shape == want.shape == ((S, d.B, d.F, d.K) if spec else (S, d.B, d.T))
+        err = np.abs(g - want).max()
+        name = "test_other_source_counts_against_float64[%d-%s]" % (S, "mags" if spec else "audio")
+        record(name, "stand-in (fp32 CPU) max err", stand_in, bound)
+        record(name, "max err", err, bound)
+        assert np.isfinite(g).all() and err <= bound
+        for i in range(S):
+            for j in range(i + 1, S):                        # every source has its own network: a mixed-up index would show
+                assert np.abs(want[i] - want[j]).max() > 100 * bound
+
+
+@pytest.mark.parametrize("geo, S", [("skip", 2), ("skip", 3), ("flat", 2)])
+def test_both_outputs_in_one_call_are_the_two_single_calls(geo, S):
+    d = _direct(geo, S)
+    audio, mags = d.both()
+    a, _, ws = d.buffers(mags=False)
+    alone_audio, none = d.run(a, None, ws)
+    assert none is None
+    _, m, ws = d.buffers(audio=False)
+    _, alone_mags = d.run(None, m, ws)
+    assert np.array_equal(_bits(audio), _bits(alone_audio)) and np.array_equal(_bits(mags), _bits(alone_mags))
+
+
+def _guarded(n):
+    """-> (whole, interior): n floats with GUARD floats of GUARD_BITS on either side; the interior holds the pattern too."""
+    whole = torch.full((n + 2 * GUARD,), GUARD_BITS, dtype=torch.int32, device="cuda").view(torch.float32)
+    return whole, whole[GUARD:GUARD + n]
+
+
+def _guards_intact(whole):
+    w = whole.view(torch.int32)
+    return bool((w[:GUARD] == GUARD_BITS).all()) and bool((w[-GUARD:] == GUARD_BITS).all())
+
+
+@pytest.mark.parametrize("geo", ["skip", "flat"])
+def test_workspace_contents_do_not_matter_and_nothing_is_written_outside(geo):
+    d = _direct(geo, 2)
+    sa, sm = d.shapes()
+    outs = []
+    for fill in (0.0, float("nan")):
+        wa, a = _guarded(int(np.prod(sa)))
+        wm, m = _guarded(int(np.prod(sm)))
+        ww, ws = _guarded(d.ws_floats)
+        ws.fill_(fill)
+        outs.append(d.run(a.view(*sa), m.view(*sm), ws))
+        assert _guards_intact(wa) and _guards_intact(wm) and _guards_intact(ww)
+        assert all(np.isfinite(o).all() for o in outs[-1])                   # every output float was written
+    for zeroed, poisoned, plain in zip(outs[0], outs[1], d.both()):
+        assert np.array_equal(_bits(zeroed), _bits(poisoned)) and np.array_equal(_bits(zeroed), _bits(plain))
+
+
+@pytest.mark.parametrize("which", ["mix", "params", "audio", "mags", "workspace", "all"])
+def test_forward_bits_do_not_depend_on_alignment(which):
+    """Every buffer one float behind an allocation's start, one at a time and all together.  The workspace too: its float64 tail
+    (the window squares of the inverse STFT) is aligned by the library from the pointer it is given (f64_tail, csrc/wun_stft.h),
+    and the scratch formula holds the room."""
+    d = _direct("skip", 2)
+    sa, sm = d.shapes()
+    moved = lambda name: which in (name, "all")              # noqa: E731
+    nan = float("nan")
+    a = _offset_full(sa, nan) if moved("audio") else torch.full(sa, nan, device="cuda")
+    m = _offset_full(sm, nan) if moved("mags") else torch.full(sm, nan, device="cuda")
+    ws = _offset_full((d.ws_floats,), nan) if moved("workspace") else torch.full((d.ws_floats,), nan, device="cuda")
+    got = d.run(a, m, ws, mix=_offset_copy(d.mix) if moved("mix") else None, params=_offset_copy(d.params) if moved("params") else None)
+    for g, want in zip(got, d.both()):
+        assert np.array_equal(_bits(g), _bits(want))
+
+
+def test_forward_on_a_side_stream():
+    d = _direct("skip", 2)
+    want = d.both()
+    a, m, ws = d.buffers()
+    torch.cuda.synchronize()                                 # the buffers' fills ran on the default stream
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        assert torch.cuda.current_stream().cuda_stream == side.cuda_stream != torch.cuda.default_stream().cuda_stream
+        got = d.run(a, m, ws)
+    for g, w in zip(got, want):
+        assert np.array_equal(_bits(g), _bits(w))

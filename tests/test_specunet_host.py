@@ -66,6 +66,26 @@ def test_conv_oracle_is_tf_same_padding():
     assert np.abs(got - want).max() <= 1e-12
 
 
+@pytest.mark.parametrize("B, N, M, ci, co", [(2, 3, 5, 3, 4), (1, 1, 1, 1, 1), (1, 4, 1, 2, 5), (2, 1, 6, 5, 2)])
+def test_both_conv_oracles_are_the_library_convolutions(B, N, M, ci, co):
+    """An implementation nobody here wrote: torch.nn.functional.conv2d on the (1, 2, 1, 2)-padded input, and
+    conv_transpose2d(stride=2, padding=1) cut to [2N, 2M] (its output has 2N + 1 rows: out[t] = sum over 2 j + k - 1 == t)."""
+    Fn = torch.nn.functional
+    rng = np.random.RandomState(B + 10 * N + 100 * M)
+    x = torch.tensor(rng.randn(B, 2 * N, 2 * M, ci), dtype=torch.float64)
+    w = torch.tensor(rng.randn(5, 5, ci, co), dtype=torch.float64)
+    want = Fn.conv2d(Fn.pad(x.permute(0, 3, 1, 2), (1, 2, 1, 2)), w.permute(3, 2, 0, 1), stride=2).permute(0, 2, 3, 1)
+    got = ora.conv2d_s2(x, w)
+    assert got.shape == want.shape == (B, N, M, co)
+    assert float((got - want).abs().max()) <= 1e-12
+    a = torch.tensor(rng.randn(B, N, M, ci), dtype=torch.float64)
+    wt = torch.tensor(rng.randn(5, 5, co, ci), dtype=torch.float64)
+    want = Fn.conv_transpose2d(a.permute(0, 3, 1, 2), wt.permute(3, 2, 0, 1), stride=2, padding=1)[..., :2 * N, :2 * M].permute(0, 2, 3, 1)
+    got = ora.conv2d_transpose_s2(a, wt)
+    assert got.shape == want.shape == (B, 2 * N, 2 * M, co)
+    assert float((got - want).abs().max()) <= 1e-12
+
+
 def _inverse_stft_window_literal(frame_length, frame_step):
     """tf.contrib.signal.inverse_stft_window_fn, transcribed: pad the squared window to overlaps * frame_step, reshape to
     [overlaps, frame_step], sum over the overlaps, tile back, divide the forward window by it."""
@@ -271,6 +291,31 @@ def test_shape_conditions_and_counts(lib):
     assert lib.wun_spec_tensor(C.byref(c), 34, C.byref(info)) == -1 and lib.wun_spec_tensor(C.byref(c), 0, None) == -1
     u7 = _spec(L=6, nif=16, n_fft=1024, hop=768)
     assert lib.wun_spec_frames(C.byref(u7), 98560) == 128
+
+
+@pytest.mark.parametrize("L, nif", [(2, 3), (1, 5)])
+@pytest.mark.parametrize("S", [1, 3])
+def test_table_through_the_c_abi_for_other_source_counts(lib, S, L, nif):
+    """wun_spec_tensor allows 1..8 sources; the separator class only ever asks for two.  The index arithmetic s L + i and
+    s (2L - 1) + j of the names, the packing and the two counts, against the oracle's table."""
+    c = _spec(L=L, nif=nif, S=S)
+    n = lib.wun_spec_num_tensors(C.byref(c))
+    want = ora.variable_shapes(L, nif, S)
+    assert n == len(want) == S * (5 * L + 5 * (L - 1) + 2)
+    info, off, names = _lib.WunTensorInfo(), 0, []
+    for i in range(n):
+        assert lib.wun_spec_tensor(C.byref(c), i, C.byref(info)) == 0
+        shape = tuple(int(info.shape[d]) for d in range(info.ndim))
+        assert (info.name.decode(), shape) == want[i]
+        assert info.offset == off                            # packed, in table order
+        off += int(np.prod(shape))
+        names.append(info.name.decode())
+    assert lib.wun_spec_param_floats(C.byref(c)) == off
+    assert len(set(names)) == n
+    assert lib.wun_spec_tensor(C.byref(c), n, C.byref(info)) == -1
+    last = S * L - 1
+    assert names[-1] == "separator/conv2d_transpose%s/bias" % ("_%d" % last if last else "")
+    assert lib.wun_spec_num_tensors(C.byref(_spec(S=9))) == -2 and lib.wun_spec_num_tensors(C.byref(_spec(S=0))) == -1
 
 
 def test_istft_tf_refuses_a_resolution_with_a_vanishing_denominator(lib):

@@ -11,6 +11,7 @@
 //              taps; M = B Hi Wi outputs of a class, every output float written once.  The input is the virtual channel
 //              concatenation of x0 [.., c0] and x1 [.., c1] (skip first): the concatenation is never materialised.
 //   epilogue   + bias, inference batch norm (z - mean) / sqrt(var + 1e-3) + beta (no gamma), LeakyReLU(0.2) | ReLU | sigmoid
+//              (a NaN stays NaN through each of them)
 //   thin       the first down layer (Cin = 1: a reduction of 25) and the mask layer (Cout = 1: one GEMM column in 16) are poor
 //              MFMA shapes and run on the VALU, one lane per output, the same gather, the same order, fmaf in place of the MFMA
 //
@@ -51,7 +52,7 @@ __device__ __forceinline__ float c2d_finish(const C2dEpilogue& e, float z, int n
     if (e.bias) z += e.bias[n];
     if (e.mean) z = (z - e.mean[n]) * (1.0f / sqrtf(e.var[n] + WUN_C2D_EPS)) + e.beta[n];
     if (e.act == C2D_ACT_LRELU) z = z > 0.f ? z : 0.2f * z;
-    else if (e.act == C2D_ACT_RELU) z = z > 0.f ? z : 0.f;
+    else if (e.act == C2D_ACT_RELU) z = z > 0.f ? z : (z != z ? z : 0.f);      // NaN stays NaN; -0.0 and below give +0.0
     else if (e.act == C2D_ACT_SIGMOID) z = 1.0f / (1.0f + expf(-z));
     return z;
 }
