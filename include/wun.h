@@ -824,8 +824,8 @@ int wun_separate_track(const wun_plan* plan, const float* params, const float* t
  * The convolutions run on the exact-fp32 MFMA (the first down layer and the mask layer, thin GEMMs, on the VALU with the same
  * bits), the reduction in ascending (ky, kx, ci) order in one accumulator per output, no atomics: an excerpt's bits do not depend
  * on the batch around it, the grid, what the workspace held or pointer alignment beyond 4 bytes.  Every buffer is the caller's;
- * nothing allocates or synchronises; every argument check runs before any GPU work.  Training this model (batch statistics,
- * dropout, the 2-D backward), stereo and a bf16 mode are not built. */
+ * nothing allocates or synchronises; every argument check runs before any GPU work.  Training on the magnitude objective is the
+ * next section; the raw-audio objective, stereo and a bf16 mode are not built. */
 typedef struct wun_spec_config {
     int32_t num_layers;          /* L in 1..10 */
     int32_t num_initial_filters; /* nif; nif 2^(L-1) <= 65536 */
@@ -857,6 +857,67 @@ int64_t wun_spec_workspace_floats(const wun_spec_config* cfg, int32_t B, int64_t
 int     wun_spec_forward(const wun_spec_config* cfg, const float* params, const float* mix, int32_t B, int64_t T,
                          const float* table_dev, float* audio, float* mags, float* workspace, void* stream);
 
+/* ---- training the spectrogram U-Net: the magnitude objective ------------------
+ * One step of UnetSpectrogramSeparator.py:63-92 at training = True with Jansson's L1 on magnitudes (Training.py:55-63,
+ * raw_audio_loss = False) and TF-Adam with the batch-norm UPDATE_OPS (Training.py:74-77).  float32, mono.
+ *   forward   every layer with a batch norm: z = conv + bias; per channel over the n = B H W pixels of the layer's output
+ *             mu = mean z, var = mean (z - mu)^2 (biased, two passes, float64 sums); zhat = (z - mu) / sqrt(var + 1e-3) + beta,
+ *             then the activation.  The mask layer has no batch norm.
+ *   dropout   on the concatenation [skip, up] of up levels i < 3 (the input of transposed layer i + 1): element e (the flat
+ *             index into [B][H][W][c_skip + c_up]) is multiplied by 1 / (1 - rate) if kept and by 0 otherwise.  The keep bit is
+ *             stateless and counter-based.  With uint64 arithmetic modulo 2^64 and
+ *               mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB;
+ *                       return z ^ z >> 31
+ *               key = mix(mix(mix(seed) + step) + (source << 8 | level))
+ *               u   = mix(key + e) >> 40                                  (24 bits)
+ *             element e is kept iff u 2^-24 >= rate (compared in float32).  rate = 0 disables dropout and its buffers.
+ *   loss      R_s = |STFT(target_s)| (wun_stft_magnitude_fft);  losses[1 + s] = mean over all B F K bins of |R_s - M mask_s|,
+ *             losses[0] = their mean over the sources.  The padded bin K - 1 (mask 0.5) adds to the loss and to no gradient.
+ *             1024 consecutive bins per float64 partial, as wun_spectral_loss sums.
+ *   backward  dmask = -sign(R - M mask) M / (S B F K), sign(0) = 0;  ReLU passes where zhat > 0, LeakyReLU has slope 1 where
+ *             zhat > 0 and 0.2 elsewhere;  batch norm: dbeta = sum g, dz = rstd (g - mean g - xh mean(g xh));  the conv biases
+ *             under a batch norm get sum dz (mathematically zero, computed all the same, as TF does).
+ *             Weight gradients: split reductions over chunks of 256 pixels of the small map, the partition a function of the
+ *             shapes alone, the chunks added in ascending order (see wun_op_conv2d_s2_wgrad).  No atomics.
+ *   Adam      wun_adam_step's rule on kernels, biases and betas; then moving_mean -= (1 - decay) (moving_mean - mu) and
+ *             moving_variance -= (1 - decay) (moving_variance - var n / max(n - 1, 1)) from the statistics of the last forward.
+ *             grads, m and v of the moving statistics stay 0.
+ * Contract as wun_spec_forward: the caller's buffers, no allocation, no sync, every check before any GPU work, a workspace that
+ * overlaps another buffer is refused; the bits depend on neither the grid, what the workspace held nor pointer alignment beyond
+ * 4 bytes.  The three entries of one step take the same (cfg, tcfg, B, T) and the same workspace, in this order. */
+typedef struct wun_spec_train_config {
+    float   bn_decay;            /* in [0, 1]; tf.contrib.layers.batch_norm: 0.999 */
+    float   dropout_rate;        /* in [0, 1); tf.layers.dropout: 0.5; 0 = none */
+    int64_t dropout_seed;
+} wun_spec_train_config;
+/* sizeof(wun_spec_train_config) as the library was compiled. */
+int64_t wun_spec_train_abi_size(void);
+/* floats of the training workspace: X, M, A0, R, and per source every layer's z, batch mean, batch variance and activation, the
+ * dropout masks and dropped concatenations of up levels i < 3 and the mask; the gradient buffers of the backward pass, the
+ * weight-gradient partials and the float64 partial sums.  Negative wun_status as wun_spec_train_forward. */
+int64_t wun_spec_train_workspace_floats(const wun_spec_config* cfg, int32_t B, int64_t T);
+/* Where a retained tensor of the last wun_spec_train_forward lies in the workspace: *offset floats from its base, *count floats
+ * (the role of wun_plan_activation).  layer: 0 .. L-1 the down path, L .. 2L-2 the up path; WUN_SPEC_TT_ACT also takes 2L-1, the
+ * sigmoid mask [B][F][K - 1]; WUN_SPEC_TT_DROPOUT takes the up level i in 0 .. L-2 and gives count 0 for i >= 3 (the mask holds
+ * the multipliers 0 and 1 / (1 - rate), and is not written when rate = 0).  Host only. */
+enum { WUN_SPEC_TT_Z = 0, WUN_SPEC_TT_MEAN = 1, WUN_SPEC_TT_VAR = 2, WUN_SPEC_TT_ACT = 3, WUN_SPEC_TT_DROPOUT = 4 };
+int     wun_spec_train_tensor(const wun_spec_config* cfg, int32_t B, int64_t T, int32_t kind, int32_t source, int32_t layer,
+                              int64_t* offset, int64_t* count);
+/*   step : the counter of the dropout keep bit (>= 0);  mags : device [S, B, F, K], required
+ * WUN_ERR_INVALID also for a bn_decay outside [0, 1] or a dropout_rate outside [0, 1) (NaN included). */
+int     wun_spec_train_forward(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, const float* params,
+                               const float* mix, int32_t B, int64_t T, const float* table_dev, int64_t step, float* mags,
+                               float* workspace, void* stream);
+/*   targets : device [S, B, T, 1];  grads : device, wun_spec_param_floats floats, every float written;  losses : device [1 + S]
+ * Reads what wun_spec_train_forward left in the workspace. */
+int     wun_spec_loss_backward(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, const float* params,
+                               const float* targets, int32_t B, int64_t T, const float* table_dev, float* grads, float* losses,
+                               float* workspace, void* stream);
+/* step is 1-based (lr_t = lr sqrt(1 - beta2^step) / (1 - beta1^step)); the workspace is read only (the batch statistics). */
+int     wun_spec_adam_step(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, float* params, const float* grads,
+                           float* m, float* v, const float* workspace, int32_t B, int64_t T, int64_t step, float lr, float beta1,
+                           float beta2, float eps, float grad_scale, void* stream);
+
 /* tf.contrib.signal.inverse_stft with inverse_stft_window_fn(hop): wun_istft in the framing without padding (lead 0), except for
  * the normaliser:  y[t] = (sum_f frame_f[t - f hop]) / D[t mod hop],  D[p] = sum_i w^2[p + i hop] over 0 <= p + i hop < n_fft
  * (i ascending, float64) -- the steady-state window-square sum, at the track's edges too, where wun_istft divides by the sum
@@ -887,6 +948,24 @@ int wun_op_conv2d_s2(const float* x, const float* w, const float* bias, const fl
 int wun_op_conv2d_transpose_s2(const float* x0, int c0, const float* x1, int c1, const float* w, const float* bias,
                                const float* bn_mean, const float* bn_var, const float* bn_beta, float* y, int B, int H, int W,
                                int cout, int act, void* stream);
+
+/* The weight gradients of the two layers above, one form: G[ky][kx][p][q] = sum_{b,y,x} Big[b][2y + ky - 1][2x + kx - 1][p]
+ * Small[b][y][x][q], zeros outside the big map.  The reduction over the B Hs Ws pixels of the small map is cut into chunks of 256
+ * consecutive pixels; chunk c's partial goes to scratch, a second pass adds the chunks in ascending order.  Exact-fp32 MFMA where
+ * both channel counts exceed 1, the VALU otherwise.  db = sum dz over the pixels (float64 partials per 1024 pixels) or NULL.
+ *   strided   : x [B][H][W][cin] (Big), dz [B][H / 2][W / 2][cout] (Small), dw [5][5][cin][cout], db [cout]
+ *   transposed: dz [B][2 H][2 W][cout] (Big), x0 [B][H][W][c0] and optionally x1 [..][c1] (Small), dw [5][5][cout][c0 + c1]
+ * scratch: *_scratch floats (negative wun_status for bad sizes); what it held does not matter; it may not overlap an operand. */
+int64_t wun_op_conv2d_s2_wgrad_scratch(int B, int H, int W, int cin, int cout);
+int     wun_op_conv2d_s2_wgrad(const float* x, const float* dz, float* dw, float* db, float* scratch, int B, int H, int W,
+                               int cin, int cout, void* stream);
+int64_t wun_op_conv2d_transpose_s2_wgrad_scratch(int B, int H, int W, int cin, int cout);
+int     wun_op_conv2d_transpose_s2_wgrad(const float* x0, int c0, const float* x1, int c1, const float* dz, float* dw, float* db,
+                                         float* scratch, int B, int H, int W, int cout, void* stream);
+/* mean[c] and the biased variance var[c] of z [B][H][W][C] over its n = B H W pixels: two passes, float64 partials per 1024
+ * pixels added in a fixed order, rounded to float32 once each. */
+int64_t wun_op_bn2d_stats_scratch(int B, int H, int W, int C);
+int     wun_op_bn2d_stats(const float* z, float* mean, float* var, float* scratch, int B, int H, int W, int C, void* stream);
 
 /* y[b][co][q] = act(bias[co] + sum_{k,ci} w[k][ci][co] * x[b][ci][q*stride + k - pad_left]),
  * x zero outside [0, t_in).  NCW float32, w in TF layout [K, Cin, Cout].

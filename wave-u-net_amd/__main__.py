@@ -9,7 +9,9 @@
   python -m wave_u_net_amd evaluate with cfg.full model_path=ckpt.npz data_root=DATA estimates_path=out partition=test
   python -m wave_u_net_amd predict with cfg.unet_spectrogram model_path=ckpt.npz input_path=mix.wav output_path=out
   python -m wave_u_net_amd test    with cfg.unet_spectrogram_l1 model_path=ckpt.npz data_root=DATA
-      (the spectrogram U-Net baseline: predict, test and evaluate only -- `train` refuses it, inference only; hop_frames does not apply)
+  python -m wave_u_net_amd train   with cfg.unet_spectrogram_l1 data_root=DATA
+      (the spectrogram U-Net baseline; `train` takes its magnitude objective, raw_audio_loss=False, on one GPU and refuses
+       cfg.unet_spectrogram, whose audio output is built for inference only; hop_frames does not apply)
 (model_path / load_model: a .npz of this package or a TensorFlow V2 checkpoint prefix such as checkpoints/full_44KHz/full_44KHz-236118)
 
 `with` arguments: `cfg.<named config>` (any of wave_u_net_amd.NAMED_CONFIGS), `model_config.<key>=<value>`

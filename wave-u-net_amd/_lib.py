@@ -44,6 +44,12 @@ class WunSpecConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("num_layers", "num_initial_filters", "num_sources", "n_fft", "hop")]
 
 
+class WunSpecTrainConfig(C.Structure):
+    _fields_ = [("bn_decay", C.c_float), ("dropout_rate", C.c_float), ("dropout_seed", C.c_int64)]
+
+
+SPEC_TT_Z, SPEC_TT_MEAN, SPEC_TT_VAR, SPEC_TT_ACT, SPEC_TT_DROPOUT = range(5)     # wun_spec_train_tensor kinds
+
 _P = C.c_void_p
 _SIGS = {
     "wun_get_padding": (C.c_int, [C.POINTER(WunConfig), C.c_int64, C.POINTER(C.c_int64),
@@ -150,6 +156,22 @@ _SIGS = {
     "wun_spec_frames": (C.c_int64, [C.POINTER(WunSpecConfig), C.c_int64]),
     "wun_spec_workspace_floats": (C.c_int64, [C.POINTER(WunSpecConfig), C.c_int32, C.c_int64]),
     "wun_spec_forward": (C.c_int, [C.POINTER(WunSpecConfig), _P, _P, C.c_int32, C.c_int64, _P, _P, _P, _P, _P]),
+    "wun_spec_train_abi_size": (C.c_int64, []),
+    "wun_spec_train_workspace_floats": (C.c_int64, [C.POINTER(WunSpecConfig), C.c_int32, C.c_int64]),
+    "wun_spec_train_tensor": (C.c_int, [C.POINTER(WunSpecConfig), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wun_spec_train_forward": (C.c_int, [C.POINTER(WunSpecConfig), C.POINTER(WunSpecTrainConfig), _P, _P, C.c_int32, C.c_int64, _P,
+                                         C.c_int64, _P, _P, _P]),
+    "wun_spec_loss_backward": (C.c_int, [C.POINTER(WunSpecConfig), C.POINTER(WunSpecTrainConfig), _P, _P, C.c_int32, C.c_int64, _P,
+                                         _P, _P, _P, _P]),
+    "wun_spec_adam_step": (C.c_int, [C.POINTER(WunSpecConfig), C.POINTER(WunSpecTrainConfig), _P, _P, _P, _P, _P, C.c_int32,
+                                     C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "wun_op_conv2d_s2_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
+    "wun_op_conv2d_s2_wgrad": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [_P]),
+    "wun_op_conv2d_transpose_s2_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
+    "wun_op_conv2d_transpose_s2_wgrad": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P] + [C.c_int] * 4 + [_P]),
+    "wun_op_bn2d_stats_scratch": (C.c_int64, [C.c_int] * 4),
+    "wun_op_bn2d_stats": (C.c_int, [_P] * 4 + [C.c_int] * 4 + [_P]),
     "wun_istft_tf_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "wun_istft_tf": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                _P, _P, _P, _P]),
@@ -222,6 +244,9 @@ def load():
     if lib.wun_spec_abi_size() != C.sizeof(WunSpecConfig):
         raise RuntimeError("libwun.so wun_spec_config size %d != this binding's %d (stale library or binding)" % (
             lib.wun_spec_abi_size(), C.sizeof(WunSpecConfig)))
+    if lib.wun_spec_train_abi_size() != C.sizeof(WunSpecTrainConfig):
+        raise RuntimeError("libwun.so wun_spec_train_config size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_spec_train_abi_size(), C.sizeof(WunSpecTrainConfig)))
     _lib = lib
     return lib
 

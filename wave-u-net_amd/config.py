@@ -58,6 +58,10 @@ EXTENSION_DEFAULTS = {
     # 1024 / 768); other values exist so that tests can run small geometries
     "spec_frame_len": 1024,
     "spec_hop": 768,
+    # its training step: tf.layers.dropout's rate on the three deepest concatenations (0 = none), the decay of
+    # tf.contrib.layers.batch_norm's moving averages; "spec_dropout_seed" (default: the separator's seed) keys the keep bits
+    "spec_dropout": 0.5,
+    "spec_bn_decay": 0.999,
 }
 
 NAMED_CONFIGS = {                # Config.py:52-161
@@ -78,7 +82,7 @@ NAMED_CONFIGS = {                # Config.py:52-161
     "baseline_comparison": {"batch_size": 4, "output_type": "difference", "context": True,
                             "num_frames": 768 * 127 + 1024, "duration": 13,
                             "expected_sr": 8192, "num_initial_filters": 34},   # Config.py:123-134
-    # the spectrogram U-Net baseline (spectrogram.UnetSpectrogramSeparator: inference only)
+    # the spectrogram U-Net baseline (spectrogram.UnetSpectrogramSeparator; training: the _l1 objective)
     "unet_spectrogram": {"batch_size": 4, "network": "unet_spectrogram", "num_layers": 6, "expected_sr": 8192,
                          "num_frames": 768 * 127 + 1024, "duration": 13, "num_initial_filters": 16},     # Config.py:136-147
     "unet_spectrogram_l1": {"batch_size": 4, "network": "unet_spectrogram", "num_layers": 6, "expected_sr": 8192,

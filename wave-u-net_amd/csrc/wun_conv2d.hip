@@ -23,7 +23,7 @@
 //
 // Built WITHOUT the packed fp32 VALU instructions (csrc/Makefile NO_PK_FP32): inference runs beside plans of either
 // compute mode.  Every argument check runs before any GPU work; nothing allocates or synchronises.
-#include "wun_stft.h"
+#include "wun_conv2d.h"
 
 #include <cmath>
 #include <cstdio>
@@ -32,21 +32,9 @@
 
 using namespace wun;
 
-#define WUN_C2D_EPS 1e-3f            // tf.contrib.layers.batch_norm's epsilon
-#define WUN_SPEC_MAX_LAYERS 10
-#define WUN_SPEC_MAX_SOURCES 8
-
 namespace wun {
 
-enum { C2D_ACT_NONE = 0, C2D_ACT_LRELU = 1, C2D_ACT_RELU = 2, C2D_ACT_SIGMOID = 3 };
-
-struct C2dEpilogue {
-    const float* bias;                       // [Cout] or null
-    const float* mean;                       // [Cout] each, or all three null: no batch norm
-    const float* var;
-    const float* beta;
-    int act;
-};
+// (C2dEpilogue, C2dArgs and the activation codes: wun_conv2d.h)
 
 __device__ __forceinline__ float c2d_finish(const C2dEpilogue& e, float z, int n) {
     if (e.bias) z += e.bias[n];
@@ -142,16 +130,6 @@ __device__ __forceinline__ void c2d_valu(long long M, int N, int Rd, RowOf row_o
         store(m, n, acc);
     }
 }
-
-struct C2dArgs {
-    const float* x0;                         // conv: [B][H][W][Cin];  transposed: [B][H][W][c0]
-    const float* x1;                         // transposed: [B][H][W][c1] or null
-    const float* w;                          // conv: [5][5][Cin][Cout];  transposed: [5][5][Cout][Cin]
-    float* y;                                // conv: [B][H/2][W/2][Cout];  transposed: [B][2H][2W][Cout]
-    C2dEpilogue epi;
-    long long M;                             // conv: B (H/2) (W/2);  transposed: B H W
-    int H, W, c0, c1, Cout;                  // the INPUT map (Cin = c0 + c1)
-};
 
 // conv: rows are output pixels (b, y, x) of the [H/2][W/2] map
 template <bool MFMA>
@@ -256,16 +234,7 @@ __global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_mask_kernel(const float* 
     }
 }
 
-}  // namespace wun
-
-namespace {
-
-unsigned capped_grid(long long lanes) {
-    long long g = (lanes + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK;
-    if (g > (1 << 16)) g = 1 << 16;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
+// the launchers, the variable table and the shape checks are shared with the training unit (wun_conv2d.h)
 // the first down layer (Cin == 1) and the mask layer (Cout == 1) run on the VALU
 void launch_conv(const C2dArgs& a, hipStream_t s) {
     if (a.c0 == 1) {
@@ -285,6 +254,19 @@ void launch_transpose(const C2dArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(conv2d_transpose_s2_mfma_kernel, grid, dim3(WUN_STFT_BLOCK), 0, s, a);
 }
 
+void launch_spec_prepare(const float* re, const float* im, float* mag, float* a0, long long E, int K, hipStream_t s) {
+    hipLaunchKernelGGL(spec_prepare_kernel, dim3(capped_grid(E)), dim3(WUN_STFT_BLOCK), 0, s, re, im, mag, a0, E, K);
+}
+
+void launch_spec_mask(const float* mask, const float* mag, const float* re, const float* im, float* mags, float* yre, float* yim,
+                      long long E, int K, hipStream_t s) {
+    hipLaunchKernelGGL(spec_mask_kernel, dim3(capped_grid(E)), dim3(WUN_STFT_BLOCK), 0, s, mask, mag, re, im, mags, yre, yim, E, K);
+}
+
+}  // namespace wun
+
+namespace {
+
 // sizes of one 2-D layer: B H W pixels of the input map, channels on both sides
 int check_c2d(const char* who, int B, int H, int W, int cin, int cout, int act, const float* mean, const float* var, const float* beta) {
     if (B < 1 || H < 1 || W < 1 || cin < 1 || cout < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": a size below 1");
@@ -296,12 +278,11 @@ int check_c2d(const char* who, int B, int H, int W, int cin, int cout, int act, 
     return WUN_OK;
 }
 
-bool overlap(const void* a, long long na, const void* b, long long nb) {       // float counts
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + 4 * (uintptr_t)na, b0 = (uintptr_t)b, b1 = b0 + 4 * (uintptr_t)nb;
-    return a0 < b1 && b0 < a1;
-}
+}  // namespace
 
 // ---- the model: variables and workspace ----
+namespace wun {
+
 int check_spec_config(const char* who, const wun_spec_config* c) {
     if (!c) return fail(WUN_ERR_INVALID, std::string(who) + ": null config");
     if (c->num_layers < 1 || c->num_initial_filters < 1 || c->num_sources < 1)
@@ -314,9 +295,7 @@ int check_spec_config(const char* who, const wun_spec_config* c) {
     return WUN_OK;
 }
 
-struct SpecTensor { std::string name; int64_t offset; int ndim; int64_t shape[4]; };
-
-std::string tf_name(const char* stem, int index, const char* leaf) {      // an index 0 has no suffix
+static std::string tf_name(const char* stem, int index, const char* leaf) {      // an index 0 has no suffix
     std::string s = std::string("separator/") + stem;
     if (index) s += "_" + std::to_string(index);
     return s + "/" + leaf;
@@ -361,6 +340,10 @@ std::vector<SpecTensor> spec_tensors(const wun_spec_config& c) {
     return v;
 }
 
+}  // namespace wun
+
+namespace {
+
 // F for T samples, or the refusal of a shape the network cannot halve num_layers times (UnetSpectrogramSeparator.py:69)
 int64_t spec_frames(const char* who, const wun_spec_config& c, int64_t T) {
     if (T < c.n_fft || T > ((int64_t)1 << 40)) return fail(WUN_ERR_INVALID, std::string(who) + ": T below n_fft or above 2^40");
@@ -395,6 +378,10 @@ int64_t spec_layout(const char* who, const wun_spec_config& c, int64_t B, int64_
     return off;
 }
 
+}  // namespace
+
+namespace wun {
+
 // what wun_spec_workspace_floats and wun_spec_forward check of (cfg, B, T): -> F
 int64_t check_spec_shape(const char* who, const wun_spec_config* cfg, int32_t B, int64_t T) {
     int rc;
@@ -407,7 +394,7 @@ int64_t check_spec_shape(const char* who, const wun_spec_config* cfg, int32_t B,
     return F;
 }
 
-}  // namespace
+}  // namespace wun
 
 // ---- the C ABI ----
 extern "C" int64_t wun_spec_abi_size(void) { return (int64_t)sizeof(wun_spec_config); }

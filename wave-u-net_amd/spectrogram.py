@@ -1,6 +1,7 @@
-"""The spectrogram U-Net baseline in inference mode: the reference's UnetSpectrogramSeparator
+"""The spectrogram U-Net baseline: the reference's UnetSpectrogramSeparator
 (/root/reference/Models/UnetSpectrogramSeparator.py:7-108; configs unet_spectrogram / unet_spectrogram_l1, Config.py:136-161)
-on wun_spec_forward (include/wun.h).
+on wun_spec_forward (include/wun.h) and, for training on magnitudes, wun_spec_train_forward /
+wun_spec_loss_backward / wun_spec_adam_step.
 
     sep = UnetSpectrogramSeparator(get_config("unet_spectrogram"))
     outs = sep.get_output(mix, False)                              # mix [B, T, 1] -> {source: [B, T, 1]} audio
@@ -11,9 +12,16 @@ convolutions with inference batch norm and LeakyReLU down, their transposes with
 that multiplies the mixture's spectrogram; audio through tf.contrib.signal.inverse_stft's normaliser (wun_istft_tf).  T must be
 (F - 1) hop + frame_len with F and frame_len / 2 multiples of 2 ** num_layers.
 
-Not built (NotImplementedError): training this model (training=True: batch-statistics batch norm, dropout, the backward of the
-2-D convolutions), stereo, any source count but two (the reference asserts both, :24-25) and a bf16 mode.
-model_config["spec_frame_len"] / ["spec_hop"] (extension keys, defaults 1024 / 768) let tests run small geometries.
+Training on the magnitude objective (raw_audio_loss=False: Jansson's L1, Training.py:55-63):
+
+    mags = sep.get_output(mix, True, return_spectrogram=True)      # batch statistics, dropout
+    loss = sep.loss_and_gradients(targets)                         # targets {source: [B, T, 1]} or stacked [S, B, T, 1] audio
+    sep.adam_step(lr)                                              # TF-Adam + the batch norms' moving averages
+
+Not built (NotImplementedError): the audio output at training=True (the raw-audio objective), stereo, any source count but two
+(the reference asserts both, :24-25) and a bf16 mode.
+model_config["spec_frame_len"] / ["spec_hop"] (extension keys, defaults 1024 / 768) let tests run small geometries;
+["spec_dropout"] (0.5), ["spec_bn_decay"] (0.999) and ["spec_dropout_seed"] (the separator's seed) are the training step's.
 """
 import ctypes as C
 import math
@@ -32,7 +40,7 @@ class _Table(object):
 
 
 class UnetSpectrogramSeparator(object):
-    """U-Net separator on magnitude spectrograms (UnetSpectrogramSeparator.py:7-12), inference only."""
+    """U-Net separator on magnitude spectrograms (UnetSpectrogramSeparator.py:7-12)."""
 
     def __init__(self, model_config, device=None, seed=1337):
         cfg = finalize(model_config) if "source_names" not in model_config else dict(model_config)
@@ -66,9 +74,14 @@ class UnetSpectrogramSeparator(object):
         self._seed = seed
         self._device = torch.device(device) if device is not None else None
         self.params = None               # flat float32 buffer, table order
-        self.adam_m = self.adam_v = None # zeros: checkpoints keep their layout; nothing here trains
+        self.grads = self.adam_m = self.adam_v = None
         self.global_step = 0
+        self._tcfg = _lib.WunSpecTrainConfig(float(cfg.get("spec_bn_decay", 0.999)), float(cfg.get("spec_dropout", 0.5)),
+                                             int(cfg.get("spec_dropout_seed", seed)))
+        self.last_losses = None          # [total, per source] of the last loss_and_gradients (device)
         self._ws = {}                    # (B, T) -> workspace
+        self._tws = {}                   # (B, T) -> training workspace
+        self._last_train = None          # (B, T) of the last training forward
         self._outs = {}                  # (B, T, return_spectrogram) -> output buffer
 
     # ------------------------------------------------------------------ shapes
@@ -125,6 +138,7 @@ class UnetSpectrogramSeparator(object):
         self.params = torch.from_numpy(self.initial_values()).to(dev)
         self.adam_m = torch.zeros(self.num_params, dtype=torch.float32, device=dev)
         self.adam_v = torch.zeros(self.num_params, dtype=torch.float32, device=dev)
+        self.grads = torch.zeros(self.num_params, dtype=torch.float32, device=dev)
 
     def variables(self):
         """dict tf_name -> tensor view into the flat buffer."""
@@ -142,14 +156,19 @@ class UnetSpectrogramSeparator(object):
             assert t.numel() == int(np.prod(shp)), (name, t.shape, shp)
             self.params[off:off + t.numel()].copy_(t)
 
+    def gradients(self):
+        """dict tf_name -> gradient view (after loss_and_gradients); the moving statistics' are 0."""
+        return {name: self.grads[off:off + int(np.prod(shp))].view(*shp) for name, off, shp in self._table.tensors}
+
     # ------------------------------------------------------------------ forward
     def get_output(self, input, training, return_spectrogram=False, reuse=True):
-        """UnetSpectrogramSeparator.py:40-108 at training=False.  input: [batch, num_samples, 1] float32 (a tensor, or
-        anything np.asarray accepts).  Returns source_name -> [batch, num_samples, 1] audio, or with return_spectrogram
-        [batch, F, frame_len / 2 + 1] magnitudes (views of one buffer the next call of the same shape overwrites)."""
-        if training:
-            raise NotImplementedError("the spectrogram U-Net is built for inference only: training=True (batch-statistics "
-                                      "batch norm, dropout, the 2-D backward) is out of scope")
+        """UnetSpectrogramSeparator.py:40-108.  input: [batch, num_samples, 1] float32 (a tensor, or anything np.asarray
+        accepts).  Returns source_name -> [batch, num_samples, 1] audio, or with return_spectrogram
+        [batch, F, frame_len / 2 + 1] magnitudes (views of one buffer the next call of the same shape overwrites).
+        training=True (batch statistics, dropout keyed by global_step) is built for return_spectrogram=True."""
+        if training and not return_spectrogram:
+            raise NotImplementedError("the spectrogram U-Net's audio output is built for inference only: at training=True "
+                                      "ask for return_spectrogram=True (train with raw_audio_loss=False)")
         if not torch.is_tensor(input):
             input = torch.as_tensor(np.asarray(input, dtype=np.float32))
         if input.dim() != 3 or input.shape[2] != 1:                              # :53
@@ -169,12 +188,93 @@ class UnetSpectrogramSeparator(object):
         if key not in self._outs:
             self._outs[key] = torch.empty((S, B, F, K) if return_spectrogram else (S, B, T, 1), dtype=torch.float32, device=dev)
         out = self._outs[key]
+        if training:
+            with torch.cuda.device(dev):
+                _lib.check(self._lib.wun_spec_train_forward(
+                    C.byref(self._scfg), C.byref(self._tcfg), self.params.data_ptr(), mix.data_ptr(), B, T,
+                    spectral._fft_table(self.frame_len, dev).data_ptr(), self.global_step, out.data_ptr(),
+                    self._train_workspace(B, T).data_ptr(), self._stream()))
+            self._last_train = (B, T)
+            return {name: out[i] for i, name in enumerate(self.source_names)}
         with torch.cuda.device(dev):
             _lib.check(self._lib.wun_spec_forward(
                 C.byref(self._scfg), self.params.data_ptr(), mix.data_ptr(), B, T, spectral._fft_table(self.frame_len, dev).data_ptr(),
                 None if return_spectrogram else out.data_ptr(), out.data_ptr() if return_spectrogram else None,
                 self._ws[(B, T)].data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return {name: out[i] for i, name in enumerate(self.source_names)}
+
+    # ------------------------------------------------------------------ the training step
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self._dev()).cuda_stream)
+
+    def _train_workspace(self, B, T):
+        if (B, T) not in self._tws:
+            n = int(self._lib.wun_spec_train_workspace_floats(C.byref(self._scfg), B, T))
+            if n < 0:
+                _lib.check(n)
+            self._tws[(B, T)] = torch.empty(n, dtype=torch.float32, device=self._dev())
+        return self._tws[(B, T)]
+
+    def loss_and_gradients(self, targets):
+        """Jansson's L1 on magnitudes (Training.py:55-63) of the last get_output(x, True, return_spectrogram=True) and its
+        gradients into self.grads.  targets: {source: [B, T, 1]} or stacked [S, B, T, 1] AUDIO (their STFT magnitudes are taken
+        here, in the model's framing).  Returns the loss as a 0-dim device tensor; last_losses holds [loss, per source]."""
+        if self._last_train is None:
+            raise RuntimeError("loss_and_gradients needs a get_output(x, True, return_spectrogram=True) first")
+        B, T = self._last_train
+        dev, S = self._dev(), len(self.source_names)
+        if isinstance(targets, dict):
+            targets = torch.stack([torch.as_tensor(targets[n]) for n in self.source_names])
+        tg = torch.as_tensor(targets).to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(tg.shape) != (S, B, T, 1):
+            raise ValueError("targets must be [%d, %d, %d, 1], got %s" % (S, B, T, tuple(tg.shape)))
+        losses = torch.empty(1 + S, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.wun_spec_loss_backward(
+                C.byref(self._scfg), C.byref(self._tcfg), self.params.data_ptr(), tg.data_ptr(), B, T,
+                spectral._fft_table(self.frame_len, dev).data_ptr(), self.grads.data_ptr(), losses.data_ptr(),
+                self._train_workspace(B, T).data_ptr(), self._stream()))
+        self.last_losses = losses
+        return losses[0]
+
+    def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0):
+        """tf.train.AdamOptimizer(learning_rate=lr) on kernels, biases and betas, the batch norms' moving averages from the last
+        training forward (the UPDATE_OPS, Training.py:74-77), global_step += 1."""
+        if self._last_train is None:
+            raise RuntimeError("adam_step needs a training forward and loss_and_gradients first")
+        B, T = self._last_train
+        self.global_step += 1
+        with torch.cuda.device(self._dev()):
+            _lib.check(self._lib.wun_spec_adam_step(
+                C.byref(self._scfg), C.byref(self._tcfg), self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(),
+                self.adam_v.data_ptr(), self._train_workspace(B, T).data_ptr(), B, T, self.global_step, lr, beta1, beta2, eps,
+                grad_scale, self._stream()))
+
+    def activation(self, kind, source, layer):
+        """A tensor the last training forward retained (wun_spec_train_tensor), as a view of the workspace.  kind: "z" (pre-norm),
+        "mean", "var" (batch statistics), "act" (post-activation; layer 2L-1: the mask [B, F, K-1]) or "dropout" (layer = up level;
+        the multipliers 0 and 1 / (1 - rate); None where the level has no dropout).  layer: 0..L-1 down, L..2L-2 up."""
+        kinds = {"z": _lib.SPEC_TT_Z, "mean": _lib.SPEC_TT_MEAN, "var": _lib.SPEC_TT_VAR, "act": _lib.SPEC_TT_ACT,
+                 "dropout": _lib.SPEC_TT_DROPOUT}
+        if self._last_train is None:
+            raise RuntimeError("activation needs a training forward first")
+        B, T = self._last_train
+        off, cnt = C.c_int64(), C.c_int64()
+        _lib.check(self._lib.wun_spec_train_tensor(C.byref(self._scfg), B, T, kinds[kind], int(source), int(layer),
+                                                   C.byref(off), C.byref(cnt)))
+        if cnt.value == 0 or (kind == "dropout" and self._tcfg.dropout_rate == 0.0):
+            return None
+        flat = self._tws[(B, T)][off.value:off.value + cnt.value]
+        L, F, W0 = self.num_layers, self.frames(T), self.frame_len // 2
+        if kind in ("mean", "var"):
+            return flat
+        if kind == "act" and layer == 2 * L - 1:
+            return flat.view(B, F, W0)
+        if kind == "dropout":
+            sh = L - 1 - layer                               # the input map of transposed layer `layer + 1`
+            return flat.view(B, F >> sh, W0 >> sh, -1)
+        sh = layer + 1 if layer < L else 2 * L - 1 - layer
+        return flat.view(B, F >> sh, W0 >> sh, -1)
 
 
 def make_separator(model_config, device=None):

@@ -266,6 +266,51 @@ class Trainer(object):
         return parts
 
 
+class SpectrogramTrainer(object):
+    """The Trainer of the spectrogram U-Net on the magnitude objective (network "unet_spectrogram", raw_audio_loss=False:
+    Jansson's L1, Training.py:55-63): step() = training forward on batch statistics with dropout, loss,
+    backward, TF-Adam with the batch norms' moving averages.  One GPU; the options of the waveform model's Trainer that are
+    not built for this network are refused here, by name."""
+    spectral = waveform = None
+    clipping = False
+    rank, world = 0, 1
+
+    def __init__(self, model_config, batch_size=None, device=None, seed=1337):
+        from .spectrogram import UnetSpectrogramSeparator
+        if model_config.get("raw_audio_loss", True):
+            raise NotImplementedError("unet_spectrogram with raw_audio_loss=True: the spectrogram U-Net's audio output is built "
+                                      "for inference only; train with raw_audio_loss=False (cfg.unet_spectrogram_l1)")
+        for key, off in (("spectral_loss", None), ("waveform_loss", None), ("clip_grad_norm", None), ("grad_accum_steps", 1),
+                         ("skip_nonfinite_steps", False)):
+            if model_config.get(key, off) not in (off, None):
+                raise NotImplementedError("unet_spectrogram: %s is not built for this network (its objective is the magnitude "
+                                          "L1 of Training.py:55-63, one batch per step)" % key)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+            raise NotImplementedError("unet_spectrogram: data-parallel training (world > 1) is not built for this network")
+        self.cfg = model_config
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        torch.cuda.set_device(self.device)
+        self.sep = UnetSpectrogramSeparator(model_config, device=self.device, seed=seed)
+        self.batch = batch_size or model_config["batch_size"]
+        in_shape, out_shape = self.sep.get_padding(np.array([self.batch, model_config["num_frames"], 0]))
+        self.t_in, self.t_out = int(in_shape[1]), int(out_shape[1])
+        self.sep.frames(self.t_in)                         # a length the network cannot take is refused here
+        self.sep._ensure_variables()
+        self.lr = model_config["init_sup_sep_lr"]
+        self.last_losses = None
+        self.tune_source, self.tune_table = "heuristic", None
+
+    def tune(self, mix, targets, pinned_table=None):
+        """Nothing to tune: the 2-D kernels have one tiling."""
+
+    def step(self, mix, targets):
+        self.sep.get_output(mix, True, return_spectrogram=True)
+        loss = self.sep.loss_and_gradients(targets)
+        self.sep.adam_step(self.lr)
+        self.last_losses = self.sep.last_losses
+        return loss
+
+
 def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
     """(clip_norm or None, skip_nonfinite) of a Trainer: the arguments, else model_config["clip_grad_norm"] /
     ["skip_nonfinite_steps"].  ValueError for a clip_grad_norm that is not > 0 (NaN included)."""
@@ -282,14 +327,12 @@ def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
 def train(model_config, experiment_id, load_model=None, batch_source=None, log_every=None):
     """Training.train(model_config, experiment_id, load_model=None) -> save_path
     (Training.py:24-25,121)."""
-    if model_config["network"] == "unet_spectrogram":
-        raise NotImplementedError("unet_spectrogram: the spectrogram U-Net is built for inference only (predict, test, "
-                                  "evaluate); training it is out of scope")
-    if model_config["network"] != "unet":
+    if model_config["network"] not in ("unet", "unet_spectrogram"):
         raise NotImplementedError(model_config["network"])         # Training.py:28-33
     if log_every is None:
         log_every = 100 if model_config["epoch_it"] > 100 else 1
-    tr = Trainer(model_config)
+    # the spectrogram U-Net trains on the magnitude objective only (SpectrogramTrainer refuses raw_audio_loss=True)
+    tr = SpectrogramTrainer(model_config) if model_config["network"] == "unet_spectrogram" else Trainer(model_config)
     if load_model is not None:
         # rank 0 reads the checkpoint (the only rank that is guaranteed to have the path: train()
         # hands save_path to every rank, but the file system need not be shared); parameters, both
