@@ -758,6 +758,93 @@ int     wun_spectral_loss_terms_fft(const float* outputs, const float* targets, 
                                     const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs,
                                     float* losses, float* scratch, void* stream);
 
+/* ---- mel-scale terms of the spectral loss ----
+ * Two more terms per resolution, on mel spectrograms: the magnitudes of a resolution projected onto n_mels triangular bands.
+ *
+ * Filterbank.  n_fft a power of two in 64..8192, sample_rate > 0 (Hz), n_mels in 1..512, 0 <= fmin < fmax <= sample_rate / 2
+ * (fmax == 0 means sample_rate / 2), norm 0 (none) or 1 (area).  The scale is HTK's: mel(f) = 2595 log10(1 + f / 700).
+ * c[0 .. n_mels + 1] are the frequencies of n_mels + 2 points equally spaced in mel from mel(fmin) to mel(fmax); bin k lies at
+ * f_k = k sample_rate / n_fft;
+ *     W[b][k] = max(0, min((f_k - c[b]) / (c[b+1] - c[b]), (c[b+2] - f_k) / (c[b+2] - c[b+1])))
+ * times 2 / (c[b+2] - c[b]) with norm == 1.  All of it in float64 on the host, rounded ONCE to float32.  Of those floats every
+ * bin has a positive weight in at most two bands, which are adjacent, and the bins a band weights form one contiguous run.
+ * A band whose float32 weights are all 0 (it lies between two bins) would train on nothing: wun_mel_design refuses the whole
+ * filterbank with WUN_ERR_INVALID and names the band.
+ *
+ * Table: 3 K + 2 n_mels 4-byte words, K = n_fft / 2 + 1 (wun_mel_table_floats), int32 and float32 words in one array:
+ *   b0[K] int32   bin k has weight w0[k] in band b0[k] and w1[k] in band b0[k] + 1.  b0[k] is the lowest band that weights the
+ *                 bin (0 for a bin outside every band); a band index outside 0 .. n_mels - 1 has weight 0, and so has band
+ *                 b0[k] + 1 wherever one band alone weights the bin
+ *   w0[K], w1[K]  float32
+ *   lo[n_mels], hi[n_mels] int32: band b weights exactly the bins lo[b] <= k < hi[b]
+ * The caller uploads it, as wun_fft_design's.
+ *
+ * Projection.  P[m][b] = sum_{k = lo[b]}^{hi[b] - 1} W[b][k] M[m][k]: ONE float32 accumulator started at +0 and one fmaf per
+ * bin, k ascending; no atomics.  A band's float depends on that frame's magnitudes and the table alone -- not on the grid, the
+ * frames sharing its workgroup, or pointer alignment beyond 4 bytes.  A bin outside [lo[b], hi[b]) is not read for band b.
+ * Adjoint.    q[m][k] = fmaf(w1[k], g[m][b0[k] + 1], w0[k] * g[m][b0[k]]), where a band whose weight at k is 0 (or whose index
+ * is outside 0 .. n_mels - 1) counts as g = 0 and is not read.  One writer per bin.
+ *
+ * Terms, per resolution j on Pe and Pt [R][F][n_mels_j], the projections of the floats wun_stft_magnitude[_fft] returns for
+ * the estimates and the targets; d = Pe - Pt in fp32, sg = sgn(d), sgn(0) = 0:
+ *   mel_l1     : the mean over the R F n_mels values of |d|
+ *   log_mel_l1 : the mean of |logf(Pe + log_eps) - logf(Pt + log_eps)|
+ *   g[m][b] = mel_l1 weight * sg + log_mel_l1 weight * sg / (Pe + log_eps): the gradient with respect to Pe times R F n_mels.
+ * The coefficient of (Re_e, Im_e) / Me at bin (m, k) gains (K / n_mels) q[m][k] of that g -- pre-scaled, so that the
+ * resolution's one scale stays weights[j] / (R F K) -- added to the four terms' coefficient before the one division by Me; 0
+ * where Me == 0.  L_j = the four terms' weighted sum + mel_l1 weight * mel_l1 + log_mel_l1 weight * log_mel_l1; the total and
+ * d_outputs as wun_spectral_loss_terms defines them.  The two means are summed as that entry's: 1024 consecutive elements of
+ * [R F][n_mels] per float64 partial, the same tree.  log_eps = 1e-3 is the usual value: a choice, not a measurement. */
+int64_t wun_mel_table_floats(int32_t n_fft, int32_t n_mels);
+/* Host: the table into table_host[cap] (int32 words stored in place).  WUN_ERR_UNSUPPORTED for the n_fft; then WUN_ERR_INVALID for
+ * n_mels outside 1..512, a sample_rate that is not finite and > 0, fmin / fmax outside the range above or not finite, norm not
+ * 0 or 1, a null pointer, cap < wun_mel_table_floats, or an empty band. */
+int     wun_mel_design(int32_t n_fft, double sample_rate, int32_t n_mels, double fmin, double fmax, int32_t norm,
+                       float* table_host, int64_t cap);
+/* Single operators on device arrays: out[m][b] = P of mags [M][K]; q[m][k] = the unscaled adjoint of g [M][n_mels].
+ * 1 <= M <= 2^30, K = n_fft / 2 + 1 of an n_fft above, n_mels in 1..512 (WUN_ERR_INVALID otherwise, or for a null pointer);
+ * mel_table_dev: a device copy of wun_mel_design's table for that K and n_mels.  One launch each, no sync. */
+int     wun_op_mel_project(const float* mags, int64_t M, int32_t K, int32_t n_mels, const float* mel_table_dev, float* out,
+                           void* stream);
+int     wun_op_mel_project_transpose(const float* g, int64_t M, int32_t K, int32_t n_mels, const float* mel_table_dev, float* q,
+                                     void* stream);
+/* the two term weights (finite, >= 0; a term whose weight is 0 is not computed) and log_eps (finite, > 0) */
+typedef struct wun_mel_terms { float mel_l1, log_mel_l1, log_eps; } wun_mel_terms;
+int64_t wun_mel_abi_size(void);        /* sizeof(wun_mel_terms) */
+/* wun_spectral_loss_terms[_fft] with the mel terms: its arguments in its order and its contract (the caller's buffers, no
+ * allocation, no sync, no atomics, every check before any GPU work, d_outputs may be NULL, any 4-byte alignment, bits
+ * independent of the grid, the scratch contents, the alignment and repetition), then
+ *   mel            : HOST, the weights above
+ *   n_mels         : HOST, nres band counts
+ *   mel_tables_dev : HOST array of nres device pointers, [j] = wun_mel_design's table for n_fft[j] and n_mels[j]
+ * All four weights of `terms` may be 0: the mel terms alone.  The checks are the sibling's in its order; then WUN_ERR_INVALID
+ * for a null `mel`, a negative or non-finite mel weight, a log_eps that is not finite and > 0, null n_mels / mel_tables_dev with
+ * nres > 0, an n_mels[j] outside 1..512 or a null mel table.
+ *   losses : device float32 [2 + 7 nres]: the first 2 + 5 nres as wun_spectral_loss_terms has them (L_j and the total include
+ *            the mel terms), then [2 + 5 nres + 2 j] = mel_l1 and [2 + 5 nres + 2 j + 1] = log_mel_l1 of resolution j, unweighted
+ *            (0 for a term whose weight is 0)
+ *   scratch: wun_spectral_mel[_fft]_scratch_floats floats: wun_spectral_terms[_fft]_scratch_floats' and, where a mel weight is
+ *            > 0, per resolution 2 R F n_mels floats (Pe, which g replaces in place, and Pt) and one float64 partial (2 floats)
+ *            per 1024 mel values for each mel term in use
+ * With both mel weights 0 nothing mel is launched: the first 2 + 5 nres losses and d_outputs are wun_spectral_loss_terms[_fft]'s
+ * bit for bit, and the mel slots are 0. */
+int64_t wun_spectral_mel_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                        const int32_t* hop, const wun_spectral_terms* terms, const wun_mel_terms* mel,
+                                        const int32_t* n_mels);
+int     wun_spectral_loss_mel(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                              float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                              const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs, float* losses,
+                              float* scratch, void* stream, const wun_mel_terms* mel, const int32_t* n_mels,
+                              const float* const* mel_tables_dev);
+int64_t wun_spectral_mel_fft_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                            const int32_t* hop, const wun_spectral_terms* terms, const wun_mel_terms* mel,
+                                            const int32_t* n_mels);
+int     wun_spectral_loss_mel_fft(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                  float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                                  const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs,
+                                  float* losses, float* scratch, void* stream, const wun_mel_terms* mel, const int32_t* n_mels,
+                                  const float* const* mel_tables_dev);
+
 /* ---- whole-track separation (Evaluate.predict_track, Evaluate.py:113-143) ------------------
  * The hop loop of the reference around get_output, on the device: hop windows are read straight from the zero-padded
  * track and the estimates are written straight into the track-long result.  Audio is float32 channel-last: the track is

@@ -9,6 +9,9 @@ Kernel arms (HIP events on the launch stream around `iters` back-to-back calls, 
   terms_mag     wun_spectral_loss_terms with d_outputs, mag_l1 alone: loss_grad's work through the four-term entry
   terms_sc_log  ... sc + log_mag_l1 (the per-source sums pass and its one-block reduction before the coefficient pass)
   terms_all     ... all four terms (the forward also stores Re / Im of the targets)
+  terms_mel     wun_spectral_loss_mel with d_outputs, mel_l1 + log_mel_l1 on 80 bands at 22 050 Hz and no linear-frequency term
+                (the projection of both magnitudes, the mel terms pass, the adjoint inside the coefficient pass)
+  terms_sc_log_mel  ... the same beside sc + log_mag_l1: terms_sc_log plus the mel stage
 Trainer arms (one optimizer step each, same batch):
   step_mse      Trainer(batch 16): the time-domain MSE (wun_loss_backward)
   step_spectral Trainer(batch 16, spectral_loss = 1024 / 768, mse_weight 1): wun_spectral_loss, then wun_backward
@@ -20,6 +23,7 @@ FFT arms, interleaved with the arms above in the same process -
   python tools/spectral_bench.py [--rounds 9] [--iters 10] [--out profiles/spectral_bench.json] [--arms a,b,...] [--res 1024,768]
       --res n_fft,hop: the resolution of every arm but the _4096 ones (default: the reference's)
       --arms loss_grad,terms_mag,terms_sc_log,terms_all --out profiles/spectral_terms_bench.json: the four-term entry beside the old
+      --arms loss_grad,terms_sc_log,terms_mel,terms_sc_log_mel --out profiles/spectral_mel_bench.json: the mel stage beside the entry
       the arms interleaved in ONE process for `rounds` rounds (order rotated each round); per arm the median, the minimum and
       the maximum over the rounds of (time / iters).  One JSON line on stdout, and the same in --out.
 """
@@ -35,7 +39,9 @@ if ROOT not in sys.path:
 
 ARMS = ["magnitude", "loss_only", "loss_grad", "terms_mag", "terms_sc_log", "terms_all", "step_mse", "step_spectral",
         "magnitude_fft", "loss_grad_fft", "terms_sc_log_fft", "step_spectral_fft", "magnitude_4096", "loss_grad_4096",
-        "terms_sc_log_4096"]
+        "terms_sc_log_4096", "terms_mel", "terms_sc_log_mel"]
+MEL = {"n_mels": 80, "sample_rate": 22050}                       # both mel terms at weight 1, log_eps 1e-3
+MEL_TERMS = {"terms_mel": None, "terms_sc_log_mel": {"sc": 1.0, "log_mag_l1": 1.0}}
 TERMS = {"terms_mag": {"mag_l1": 1.0}, "terms_sc_log": {"sc": 1.0, "log_mag_l1": 1.0},
          "terms_all": {"mag_l1": 1.0, "log_mag_l1": 1.0, "sc": 1.0, "complex_l1": 1.0}}
 RES = [(1024, 768)]
@@ -72,6 +78,8 @@ def setup(arms):
              "loss_grad_4096": spectral.SpectralLoss(RES_4096, mse_weight=1.0, transform="fft"),
              "terms_sc_log_4096": spectral.SpectralLoss(RES_4096, mse_weight=1.0, terms=TERMS["terms_sc_log"], log_eps=4.0,
                                                         transform="fft")}
+    floss.update({a: spectral.SpectralLoss(RES, mse_weight=1.0, terms=t, log_eps=1.0, mel=MEL) for a, t in MEL_TERMS.items()
+                  if a in arms and hasattr(spectral, "MEL_TERMS")})
     tloss.update({a: l for a, l in floss.items() if a in arms})
     tbuf = {a: (torch.empty(l.num_losses, dtype=torch.float32, device=outs.device), l._scratch_for(outs)) for a, l in tloss.items()}
 

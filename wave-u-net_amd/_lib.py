@@ -36,6 +36,10 @@ class WunSpectralTerms(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("mag_l1", "log_mag_l1", "sc", "complex_l1", "log_eps", "sc_eps")]
 
 
+class WunMelTerms(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("mel_l1", "log_mel_l1", "log_eps")]
+
+
 class WunWaveformTerms(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("mse", "l1", "si_sdr", "snr", "eps")] + [("zero_mean", C.c_int32)]
 
@@ -149,6 +153,26 @@ _SIGS = {
     "wun_spectral_loss_terms_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                               C.POINTER(WunSpectralTerms), C.POINTER(C.c_void_p), _P, _P, _P, _P]),
+    "wun_mel_table_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "wun_mel_design": (C.c_int, [C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_float),
+                                 C.c_int64]),
+    "wun_op_mel_project": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "wun_op_mel_project_transpose": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P]),
+    "wun_mel_abi_size": (C.c_int64, []),
+    "wun_spectral_mel_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                    C.POINTER(C.c_int32), C.POINTER(WunSpectralTerms), C.POINTER(WunMelTerms),
+                                                    C.POINTER(C.c_int32)]),
+    "wun_spectral_loss_mel": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                        C.POINTER(WunSpectralTerms), C.POINTER(C.c_void_p), _P, _P, _P, _P,
+                                        C.POINTER(WunMelTerms), C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]),
+    "wun_spectral_mel_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                                        C.POINTER(C.c_int32), C.POINTER(WunSpectralTerms), C.POINTER(WunMelTerms),
+                                                        C.POINTER(C.c_int32)]),
+    "wun_spectral_loss_mel_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_float, C.c_int32,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
+                                            C.POINTER(WunSpectralTerms), C.POINTER(C.c_void_p), _P, _P, _P, _P,
+                                            C.POINTER(WunMelTerms), C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]),
     "wun_spec_abi_size": (C.c_int64, []),
     "wun_spec_num_tensors": (C.c_int64, [C.POINTER(WunSpecConfig)]),
     "wun_spec_param_floats": (C.c_int64, [C.POINTER(WunSpecConfig)]),
@@ -247,6 +271,9 @@ def load():
     if lib.wun_spec_train_abi_size() != C.sizeof(WunSpecTrainConfig):
         raise RuntimeError("libwun.so wun_spec_train_config size %d != this binding's %d (stale library or binding)" % (
             lib.wun_spec_train_abi_size(), C.sizeof(WunSpecTrainConfig)))
+    if lib.wun_mel_abi_size() != C.sizeof(WunMelTerms):
+        raise RuntimeError("libwun.so wun_mel_terms size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_mel_abi_size(), C.sizeof(WunMelTerms)))
     _lib = lib
     return lib
 

@@ -276,13 +276,48 @@ struct SpecTermsArgs {
     int grad;
 };
 
+// ---- mel-scale terms (include/wun.h): the table's five arrays, the adjoint of one bin ----
+struct MelTable { const int* b0; const float* w0; const float* w1; const int* lo; const int* hi; };
+
+__host__ __device__ __forceinline__ MelTable mel_table(const float* t, int K) {
+    MelTable m;      // (hi = lo + n_mels is set by the projection, the one reader of it: the adjoint needs no n_mels here)
+    m.b0 = (const int*)t; m.w0 = t + K; m.w1 = t + 2 * K; m.lo = (const int*)(t + 3 * K); m.hi = m.lo;
+    return m;
+}
+
+// q[k] = fmaf(w1[k], g[b0[k] + 1], w0[k] * g[b0[k]]) of one frame's g [n_mels]: a band whose weight is 0 or whose index is
+// outside 0 .. n_mels - 1 is not read
+__device__ __forceinline__ float mel_adjoint(const MelTable& t, const float* __restrict__ g, int k, int n_mels) {
+    const int b = t.b0[k];
+    const float w0 = t.w0[k], w1 = t.w1[k];
+    const float g0 = (w0 != 0.f && b >= 0 && b < n_mels) ? g[b] : 0.f;
+    const float g1 = (w1 != 0.f && b + 1 >= 0 && b + 1 < n_mels) ? g[b + 1] : 0.f;
+    return fmaf(w1, g1, w0 * g0);
+}
+
+struct SpecMelAdjArgs {
+    const float* g;                          // [M][n_mels] of mel_terms_kernel
+    const float* table;                      // the mel table of this resolution
+    float kn;                                // K / n_mels: the mel means' 1 / (R F n_mels) on the resolution's 1 / (R F K)
+    int K, n_mels;
+};
+
 // spec_l1_kernel with the four terms: 1024 bins per block, the same partition and tree for each of the three means, and the
 // coefficient of (Re_e, Im_e) / Me summed over the terms before the one division -- with mag_l1 = 1 alone, spec_l1_kernel's bits.
-__global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_terms_kernel(SpecTermsArgs p) {
+// MEL: the mel terms' part of that coefficient, (K / n_mels) times the adjoint of g at this bin, added before the division.
+template <bool MEL>
+__device__ __forceinline__ void spec_terms_body(const SpecTermsArgs& p, const SpecMelAdjArgs& ma) {
     __shared__ double red[3][WUN_STFT_BLOCK];
     const int tid = threadIdx.x;
     const bool mag = p.w_mag > 0.f, lg = p.w_log > 0.f, sc = p.w_sc > 0.f, cx = p.w_cx > 0.f;
     double am = 0.0, al = 0.0, ac = 0.0;
+    long long mel_m0 = 0;
+    int mel_r0 = 0;
+    if (MEL) {
+        const long long e0 = (long long)blockIdx.x * WUN_STFT_ITEMS * WUN_STFT_BLOCK;
+        mel_m0 = e0 / ma.K;
+        mel_r0 = (int)(e0 - mel_m0 * ma.K);
+    }
 #pragma unroll
     for (int it = 0; it < WUN_STFT_ITEMS; ++it) {
         const long long e = ((long long)blockIdx.x * WUN_STFT_ITEMS + it) * WUN_STFT_BLOCK + tid;
@@ -298,6 +333,11 @@ __global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_terms_kernel(SpecTermsArg
             q += p.w_log * (sg / ea);
         }
         if (sc) q += p.w_sc * (d * (float)p.src[3 * (e / p.Es) + 2]);
+        if (MEL) {
+            // (frame, bin) of e: the block's first element divided once in 64 bits, its 1024 elements in 32
+            const unsigned r = (unsigned)(mel_r0 + it * WUN_STFT_BLOCK + tid), dm = r / (unsigned)ma.K;
+            q += ma.kn * mel_adjoint(mel_table(ma.table, ma.K), ma.g + (mel_m0 + dm) * ma.n_mels, (int)(r - dm * (unsigned)ma.K), ma.n_mels);
+        }
         float cr = 0.f, ci = 0.f;
         if (p.grad && q != 0.f && a > 0.f) { cr = q * p.re[e] / a; ci = q * p.im[e] / a; }
         if (cx) {
@@ -311,6 +351,11 @@ __global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_terms_kernel(SpecTermsArg
     if (mag) { const double s = stft_block_sum(red[0], am, tid); if (tid == 0) p.part[0][blockIdx.x] = s; }
     if (lg) { const double s = stft_block_sum(red[1], al, tid); if (tid == 0) p.part[1][blockIdx.x] = s; }
     if (cx) { const double s = stft_block_sum(red[2], ac, tid); if (tid == 0) p.part[2][blockIdx.x] = s; }
+}
+
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_terms_kernel(SpecTermsArgs p) { spec_terms_body<false>(p, SpecMelAdjArgs()); }
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_terms_mel_kernel(SpecTermsArgs p, SpecMelAdjArgs ma) {
+    spec_terms_body<true>(p, ma);
 }
 
 struct SpecTermsFinishArgs {
@@ -327,13 +372,27 @@ struct SpecTermsFinishArgs {
 // spec_finish_kernel over the new slots: one wave per slot takes its (up to) three sums one after the other, each as there --
 // lane l adds the partials l, l + 64, ... in ascending order, one tree over the 64 lanes -- and thread 0 forms the terms, L_j
 // and the total in slot order.
-__global__ __launch_bounds__(64 * (1 + WUN_SPEC_MAX_RES)) void spec_terms_finish_kernel(SpecTermsFinishArgs p) {
+// MEL: two more sums per resolution slot (mel_l1, log_mel_l1), taken the same way behind the three; L_j and the total gain the
+// two weighted terms behind the four, and the terms go to the slots behind the 2 + 5 nres.
+struct SpecMelFinishArgs {
+    const double* part[WUN_SPEC_MAX_RES][2];     // mel_l1, log_mel_l1 of resolution j
+    long long nparts[WUN_SPEC_MAX_RES][2];       // 0: the sum is not taken
+    double count[WUN_SPEC_MAX_RES];              // R F n_mels
+    float w[2];
+};
+
+template <bool MEL>
+__device__ __forceinline__ void spec_terms_finish_body(const SpecTermsFinishArgs& p, const SpecMelFinishArgs& q) {
+    constexpr int NS = MEL ? 5 : 3;
     __shared__ double red[1 + WUN_SPEC_MAX_RES][64];
-    __shared__ double sums[1 + WUN_SPEC_MAX_RES][3];
+    __shared__ double sums[1 + WUN_SPEC_MAX_RES][NS];
     const int slot = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int t = 0; t < 3; ++t) {
+    for (int t = 0; t < NS; ++t) {
         double s = 0.0;
-        if (slot <= p.nres)
+        if (MEL && t >= 3) {
+            if (slot >= 1 && slot <= p.nres)
+                for (long long i = lane; i < q.nparts[slot - 1][t - 3]; i += 64) s += q.part[slot - 1][t - 3][i];
+        } else if (slot <= p.nres)
             for (long long i = lane; i < p.nparts[slot][t]; i += 64) s += p.part[slot][t][i];
         red[slot][lane] = s;
         __syncthreads();
@@ -363,11 +422,120 @@ __global__ __launch_bounds__(64 * (1 + WUN_SPEC_MAX_RES)) void spec_terms_finish
                 p.losses[2 + p.nres + 4 * j + t] = (float)term[t];
                 if (p.w[t] > 0.f) L += (double)p.w[t] * term[t];
             }
+            if (MEL)
+                for (int t = 0; t < 2; ++t) {
+                    const double mt = q.w[t] > 0.f ? sums[1 + j][3 + t] / q.count[j] : 0.0;
+                    p.losses[2 + 5 * p.nres + 2 * j + t] = (float)mt;
+                    if (q.w[t] > 0.f) L += (double)q.w[t] * mt;
+                }
             p.losses[2 + j] = (float)L;
             total += (double)p.weight[1 + j] * L;
         }
         p.losses[0] = (float)total;
     }
+}
+
+__global__ __launch_bounds__(64 * (1 + WUN_SPEC_MAX_RES)) void spec_terms_finish_kernel(SpecTermsFinishArgs p) {
+    spec_terms_finish_body<false>(p, SpecMelFinishArgs());
+}
+__global__ __launch_bounds__(64 * (1 + WUN_SPEC_MAX_RES)) void spec_mel_finish_kernel(SpecTermsFinishArgs p, SpecMelFinishArgs q) {
+    spec_terms_finish_body<true>(p, q);
+}
+
+// ---- the mel projection and its terms (include/wun.h: the definitions) ----
+#define WUN_MEL_MAX 512              // bands
+#define WUN_MEL_TILE_FLOATS 2048     // magnitudes a workgroup stages: frames per workgroup = clamp(2048 / K, 1, 16)
+#define WUN_MEL_UNROLL 8             // bins whose loads are in flight together in the projection's chain
+
+struct MelProjArgs {
+    const float* mag[2];             // [M][K]; blockIdx.y picks one (estimates, targets)
+    float* out[2];                   // [M][n_mels]
+    const float* table;
+    long long M;
+    int K, n_mels, FR;               // FR frames per workgroup: FR * K floats of LDS
+};
+
+// grid: x = tile of FR frames, y = signal.  The tile's magnitudes are contiguous: they go to LDS with coalesced 4-byte loads;
+// then one lane per (frame, band) walks the band's bins lo .. hi - 1 in ONE accumulator, one fmaf per bin, ascending.  The
+// weight of bin k in band b is w0[k] where b0[k] == b, else w1[k] (then b0[k] + 1 == b: the table's two-bands property).
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void mel_project_kernel(MelProjArgs p) {
+    extern __shared__ float mel_rows[];
+    const int tid = threadIdx.x;
+    const long long m0 = (long long)blockIdx.x * p.FR;
+    const int nfr = p.M - m0 < p.FR ? (int)(p.M - m0) : p.FR;
+    const float* __restrict__ src = p.mag[blockIdx.y] + m0 * p.K;
+    for (int i = tid; i < nfr * p.K; i += WUN_STFT_BLOCK) mel_rows[i] = src[i];
+    __syncthreads();
+    MelTable t = mel_table(p.table, p.K);
+    t.hi = t.lo + p.n_mels;
+    float* __restrict__ out = p.out[blockIdx.y] + m0 * p.n_mels;
+    for (int o = tid; o < nfr * p.n_mels; o += WUN_STFT_BLOCK) {
+        const int fr = o / p.n_mels, b = o - fr * p.n_mels;
+        int lo = t.lo[b], hi = t.hi[b];
+        if (lo < 0) lo = 0;
+        if (hi > p.K) hi = p.K;                              // (a table of another K must not reach outside the tile)
+        const float* row = mel_rows + fr * p.K;
+        float acc = 0.f;
+        // eight bins at a time: their table words and magnitudes are loaded together (independent loads: one memory latency per
+        // eight bins, not two per bin), then the fmafs run in ascending k.  Behind the band's end the loads repeat bin hi - 1 and
+        // the fmaf is skipped: no bin outside [lo, hi) is read for this band.
+        for (int k = lo; k < hi; k += WUN_MEL_UNROLL) {
+            int bb[WUN_MEL_UNROLL];
+            float wa[WUN_MEL_UNROLL], wb[WUN_MEL_UNROLL], mv[WUN_MEL_UNROLL];
+#pragma unroll
+            for (int u = 0; u < WUN_MEL_UNROLL; ++u) {
+                const int kk = k + u < hi ? k + u : hi - 1;
+                bb[u] = t.b0[kk]; wa[u] = t.w0[kk]; wb[u] = t.w1[kk]; mv[u] = row[kk];
+            }
+#pragma unroll
+            for (int u = 0; u < WUN_MEL_UNROLL; ++u)
+                if (k + u < hi) acc = fmaf(bb[u] == b ? wa[u] : wb[u], mv[u], acc);
+        }
+        out[o] = acc;
+    }
+}
+
+struct MelTermsArgs {
+    float* pe; const float* pt;      // [M][n_mels]; with grad g replaces Pe in place
+    double* part[2];                 // mel_l1, log_mel_l1 (unused without the term)
+    long long E;                     // M n_mels
+    float w_mel, w_log, log_eps;
+    int grad;
+};
+
+// the loss pass's partition on the mel values: 1024 per block, the same tree for either mean; g = w_mel sg + w_log sg / (Pe + eps)
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void mel_terms_kernel(MelTermsArgs p) {
+    __shared__ double red[2][WUN_STFT_BLOCK];
+    const int tid = threadIdx.x;
+    const bool ml = p.w_mel > 0.f, lg = p.w_log > 0.f;
+    double am = 0.0, al = 0.0;
+#pragma unroll
+    for (int it = 0; it < WUN_STFT_ITEMS; ++it) {
+        const long long e = ((long long)blockIdx.x * WUN_STFT_ITEMS + it) * WUN_STFT_BLOCK + tid;
+        if (e >= p.E) continue;
+        const float a = p.pe[e], t = p.pt[e];
+        const float d = a - t;
+        const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+        float q = 0.f;
+        if (ml) { am += (double)fabsf(d); q = p.w_mel * sg; }
+        if (lg) {
+            const float ea = a + p.log_eps, et = t + p.log_eps;
+            al += (double)fabsf(logf(ea) - logf(et));
+            q = fmaf(p.w_log, sg / ea, q);
+        }
+        if (p.grad) p.pe[e] = q;
+    }
+    if (ml) { const double s = stft_block_sum(red[0], am, tid); if (tid == 0) p.part[0][blockIdx.x] = s; }
+    if (lg) { const double s = stft_block_sum(red[1], al, tid); if (tid == 0) p.part[1][blockIdx.x] = s; }
+}
+
+// the single operator: one lane per bin of q [M][K]
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void mel_transpose_kernel(const float* __restrict__ g, const float* table,
+                                                                       float* __restrict__ q, long long E, int K, int n_mels) {
+    const long long e = (long long)blockIdx.x * WUN_STFT_BLOCK + threadIdx.x;
+    if (e >= E) return;
+    const long long m = e / K;
+    q[e] = mel_adjoint(mel_table(table, K), g + m * n_mels, (int)(e - m * K), n_mels);
 }
 
 }  // namespace wun
@@ -425,6 +593,45 @@ long long terms_doubles(const Res& r, int32_t S, const wun_spectral_terms& t) {
     const long long E = r.M * r.K;
     const int means = (t.mag_l1 > 0.f) + (t.log_mag_l1 > 0.f) + (t.complex_l1 > 0.f);
     return means * parts_of(E) + (t.sc > 0.f ? 2 * S * parts_of(E / S) + 3 * (long long)S : 0);
+}
+
+// ---- the mel terms' arguments of the *_mel entries (null: the entries without them) ----
+struct MelCall { const wun_mel_terms* mel; const int32_t* n_mels; const float* const* tables; };
+
+int check_mel(const char* who, const MelCall& mc, int32_t nres, bool tables) {
+    const std::string w(who);
+    if (!mc.mel) return fail(WUN_ERR_INVALID, w + ": null mel terms");
+    for (float x : {mc.mel->mel_l1, mc.mel->log_mel_l1})
+        if (!(x >= 0.f) || !std::isfinite(x)) return fail(WUN_ERR_INVALID, w + ": a mel weight negative or not finite");
+    if (!(mc.mel->log_eps > 0.f) || !std::isfinite(mc.mel->log_eps)) return fail(WUN_ERR_INVALID, w + ": mel log_eps must be finite and > 0");
+    if (nres > 0 && (!mc.n_mels || (tables && !mc.tables))) return fail(WUN_ERR_INVALID, w + ": null n_mels or mel table list");
+    for (int j = 0; j < nres; ++j) {
+        if (mc.n_mels[j] < 1 || mc.n_mels[j] > WUN_MEL_MAX) return fail(WUN_ERR_INVALID, w + ": n_mels outside 1..512");
+        if (tables && !mc.tables[j]) return fail(WUN_ERR_INVALID, w + ": null mel table");
+    }
+    return WUN_OK;
+}
+
+bool mel_on(const wun_mel_terms& m) { return m.mel_l1 > 0.f || m.log_mel_l1 > 0.f; }
+// what the mel terms add to a resolution: Pe (g in place) and Pt behind its floats, one run of partials per mel term in use
+long long mel_floats(const Res& r, int n_mels, const wun_mel_terms& m) { return mel_on(m) ? 2 * r.M * n_mels : 0; }
+long long mel_doubles(const Res& r, int n_mels, const wun_mel_terms& m) {
+    return ((m.mel_l1 > 0.f) + (m.log_mel_l1 > 0.f)) * parts_of(r.M * n_mels);
+}
+
+int mel_frames_per_block(int K) {
+    const int fr = WUN_MEL_TILE_FLOATS / K;
+    return fr < 1 ? 1 : (fr > 16 ? 16 : fr);
+}
+
+// P of one or two [M][K] arrays in one launch
+void launch_mel_project(const float* mag0, const float* mag1, float* out0, float* out1, const float* table, long long M, int K,
+                        int n_mels, hipStream_t s) {
+    MelProjArgs a;
+    a.mag[0] = mag0; a.mag[1] = mag1; a.out[0] = out0; a.out[1] = out1; a.table = table; a.M = M; a.K = K; a.n_mels = n_mels;
+    a.FR = mel_frames_per_block(K);
+    hipLaunchKernelGGL(mel_project_kernel, dim3((unsigned)((M + a.FR - 1) / a.FR), mag1 ? 2u : 1u), dim3(WUN_STFT_BLOCK),
+                       (size_t)a.FR * K * sizeof(float), s, a);
 }
 
 // The forward transform of one resolution on transform tr (the GEMM tile or the FFT body, one epilogue): the magnitudes of x0
@@ -595,7 +802,7 @@ int loss_entry(const char* who, int tr, const float* outputs, const float* targe
 }
 
 int64_t terms_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
-                            const int32_t* hop, const wun_spectral_terms* terms) {
+                            const int32_t* hop, const wun_spectral_terms* terms, const MelCall* mc = nullptr) {
     int rc;
     if ((rc = check_audio(who, S, B, Tout, C))) return rc;
     if (nres < 0 || nres > WUN_SPEC_MAX_RES) return fail(WUN_ERR_INVALID, std::string(who) + ": nres outside 0..8");
@@ -604,10 +811,12 @@ int64_t terms_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64
     for (int j = 0; j < nres; ++j)
         if ((rc = make_res(who, tr, S, B, Tout, C, n_fft[j], hop[j], &res[j]))) return rc;
     if ((rc = check_terms(who, terms))) return rc;
+    if (mc && (rc = check_mel(who, *mc, nres, false))) return rc;
     long long floats = 0, doubles = parts_of((long long)S * B * Tout * C);
     for (int j = 0; j < nres; ++j) {
         floats += res_floats(res[j]) + terms_floats(res[j], *terms);
         doubles += terms_doubles(res[j], S, *terms);
+        if (mc) { floats += mel_floats(res[j], mc->n_mels[j], *mc->mel); doubles += mel_doubles(res[j], mc->n_mels[j], *mc->mel); }
     }
     return floats + 2 * doubles + 2;
 }
@@ -615,13 +824,18 @@ int64_t terms_scratch_entry(const char* who, int tr, int32_t S, int32_t B, int64
 int terms_entry(const char* who, int tr, const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
                 float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
                 const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs, float* losses, float* scratch,
-                void* stream) {
+                void* stream, const MelCall* mc = nullptr) {
     int rc;
     Res res[WUN_SPEC_MAX_RES];
     if ((rc = check_loss(who, tr, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights, tables_dev, losses, scratch, res)))
         return rc;
     if ((rc = check_terms(who, terms))) return rc;
+    if (mc && (rc = check_mel(who, *mc, nres, true))) return rc;
     const wun_spectral_terms tw = *terms;
+    // mel: the *_mel entries with a mel weight > 0 -- otherwise every launch below but the finish kernel is the old entry's
+    wun_mel_terms mw = {0.f, 0.f, 1.f};
+    if (mc) mw = *mc->mel;
+    const bool mel = mel_on(mw);
 
     hipStream_t s = (hipStream_t)stream;
     const dim3 blk(WUN_STFT_BLOCK);
@@ -630,11 +844,18 @@ int terms_entry(const char* who, int tr, const float* outputs, const float* targ
     // scratch: per resolution [M_est | M_tgt | Re -> cre | Im -> cim | dframe | Re_tgt | Im_tgt (complex_l1 only)], then on an
     // 8-byte boundary the float64s: the MSE's partials, then per resolution those of terms_doubles
     long long floats = 0;
-    for (int j = 0; j < nres; ++j) floats += res_floats(res[j]) + terms_floats(res[j], tw);
+    for (int j = 0; j < nres; ++j)
+        floats += res_floats(res[j]) + terms_floats(res[j], tw) + (mel ? mel_floats(res[j], mc->n_mels[j], mw) : 0);
     double* part = f64_tail(scratch, floats);
 
     SpecGradArgs g;
     SpecTermsFinishArgs fin;
+    SpecMelFinishArgs mfin;
+    mfin.w[0] = mw.mel_l1; mfin.w[1] = mw.log_mel_l1;
+    for (int j = 0; j < WUN_SPEC_MAX_RES; ++j) {
+        mfin.count[j] = 1.0;
+        for (int t = 0; t < 2; ++t) { mfin.part[j][t] = part; mfin.nparts[j][t] = 0; }
+    }
     g.out = outputs; g.tgt = targets; g.dout = d_outputs; g.T = Tout; g.N = N; g.C = C; g.nres = nres;
     g.cm = (float)((double)mse_weight * 2.0 / (double)N);
     fin.nres = nres; fin.losses = losses; fin.S = S; fin.sc_eps = tw.sc_eps;
@@ -656,7 +877,8 @@ int terms_entry(const char* who, int tr, const float* outputs, const float* targ
         const long long E = r.M * r.K, Es = E / S, np = parts_of(E);
         float* me = base; float* mt = base + E; float* re = base + 2 * E; float* im = base + 3 * E; float* df = base + 4 * E;
         float* ret = base + res_floats(r); float* imt = ret + E;
-        base += res_floats(r) + terms_floats(r, tw);
+        float* pe = ret + terms_floats(r, tw);                // mel: Pe (then g) and Pt [M][n_mels]
+        base += res_floats(r) + terms_floats(r, tw) + (mel ? mel_floats(r, mc->n_mels[j], mw) : 0);
         // complex_l1 reads Re / Im of both signals, with or without a gradient; the other terms those of the estimates for the gradient
         const bool parts = cx || grad;
         if ((rc = launch_fwd(tr, outputs, targets, me, mt, parts ? re : nullptr, parts ? im : nullptr, cx ? ret : nullptr,
@@ -681,7 +903,30 @@ int terms_entry(const char* who, int tr, const float* outputs, const float* targ
             hipLaunchKernelGGL(spec_sc_reduce_kernel, dim3(1), blk, 0, s, scpart, src, S, ps, (double)Es, tw.sc_eps);
             t.src = src; fin.src[j] = src;
         }
-        hipLaunchKernelGGL(spec_terms_kernel, dim3((unsigned)np), blk, 0, s, t);
+        if (mel) {
+            // the projection of both magnitudes, the two mel means and g; with a gradient the coefficient pass takes g's adjoint
+            const int nm = mc->n_mels[j];
+            const long long Em = r.M * nm, npm = parts_of(Em);
+            launch_mel_project(me, mt, pe, pe + Em, mc->tables[j], r.M, r.K, nm, s);
+            MelTermsArgs m;
+            m.pe = pe; m.pt = pe + Em; m.E = Em; m.w_mel = mw.mel_l1; m.w_log = mw.log_mel_l1; m.log_eps = mw.log_eps;
+            m.grad = grad ? 1 : 0;
+            const bool mon[2] = {mw.mel_l1 > 0.f, mw.log_mel_l1 > 0.f};
+            for (int k = 0; k < 2; ++k) {
+                m.part[k] = pnext;
+                if (!mon[k]) continue;
+                mfin.part[j][k] = pnext; mfin.nparts[j][k] = npm;
+                pnext += npm;
+            }
+            mfin.count[j] = (double)Em;
+            hipLaunchKernelGGL(mel_terms_kernel, dim3((unsigned)npm), blk, 0, s, m);
+            if (grad) {
+                SpecMelAdjArgs ma;
+                ma.g = pe; ma.table = mc->tables[j]; ma.kn = (float)((double)r.K / (double)nm); ma.K = r.K; ma.n_mels = nm;
+                hipLaunchKernelGGL(spec_terms_mel_kernel, dim3((unsigned)np), blk, 0, s, t, ma);
+            }
+        }
+        if (!mel || !grad) hipLaunchKernelGGL(spec_terms_kernel, dim3((unsigned)np), blk, 0, s, t);
         if (grad && (rc = launch_bwd(tr, re, im, tables_dev[j], df, r, s))) return rc;
         g.n_fft[j] = r.n_fft; g.hop[j] = r.hop; g.F[j] = (int)r.F; g.dframe[j] = df;
         g.scale[j] = (float)((double)weights[j] / ((double)r.M * (double)r.K));
@@ -690,7 +935,8 @@ int terms_entry(const char* who, int tr, const float* outputs, const float* targ
     const dim3 ggrid((unsigned)parts_of(N));
     if (grad) hipLaunchKernelGGL(spec_grad_kernel<true>, ggrid, blk, 0, s, g);
     else hipLaunchKernelGGL(spec_grad_kernel<false>, ggrid, blk, 0, s, g);
-    hipLaunchKernelGGL(spec_terms_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin);
+    if (mc) hipLaunchKernelGGL(spec_mel_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin, mfin);
+    else hipLaunchKernelGGL(spec_terms_finish_kernel, dim3(1), dim3(64 * (1 + WUN_SPEC_MAX_RES)), 0, s, fin);
     return launch_status(who);
 }
 
@@ -749,4 +995,129 @@ extern "C" int wun_spectral_loss_terms_fft(const float* outputs, const float* ta
                                            float* d_outputs, float* losses, float* scratch, void* stream) {
     return terms_entry("wun_spectral_loss_terms_fft", WUN_TR_FFT, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop,
                        weights, terms, tables_dev, d_outputs, losses, scratch, stream);
+}
+
+// ---- the mel-scale terms' entries (include/wun.h) ----
+extern "C" int64_t wun_mel_abi_size(void) { return (int64_t)sizeof(wun_mel_terms); }
+
+extern "C" int64_t wun_mel_table_floats(int32_t n_fft, int32_t n_mels) {
+    int rc;
+    if ((rc = check_res("wun_mel_table_floats", WUN_TR_FFT, n_fft, 1))) return rc;
+    if (n_mels < 1 || n_mels > WUN_MEL_MAX) return fail(WUN_ERR_INVALID, "wun_mel_table_floats: n_mels outside 1..512");
+    return 3 * (int64_t)(n_fft / 2 + 1) + 2 * (int64_t)n_mels;
+}
+
+extern "C" int wun_mel_design(int32_t n_fft, double sample_rate, int32_t n_mels, double fmin, double fmax, int32_t norm,
+                              float* table_host, int64_t cap) {
+    const std::string w("wun_mel_design");
+    const int64_t need = wun_mel_table_floats(n_fft, n_mels);
+    if (need < 0) return (int)need;
+    if (!(sample_rate > 0.0) || !std::isfinite(sample_rate)) return fail(WUN_ERR_INVALID, w + ": sample_rate must be finite and > 0");
+    if (fmax == 0.0) fmax = 0.5 * sample_rate;
+    if (!std::isfinite(fmin) || !std::isfinite(fmax) || fmin < 0.0 || !(fmin < fmax) || fmax > 0.5 * sample_rate)
+        return fail(WUN_ERR_INVALID, w + ": need 0 <= fmin < fmax <= sample_rate / 2");
+    if (norm != 0 && norm != 1) return fail(WUN_ERR_INVALID, w + ": norm must be 0 (none) or 1 (area)");
+    if (!table_host) return fail(WUN_ERR_INVALID, w + ": null table");
+    if (cap < need) return fail(WUN_ERR_INVALID, w + ": cap below wun_mel_table_floats");
+    const int K = n_fft / 2 + 1;
+    // the n_mels + 2 corner frequencies: equally spaced in mel, the two ends fmin and fmax themselves
+    const double m0 = 2595.0 * std::log10(1.0 + fmin / 700.0), m1 = 2595.0 * std::log10(1.0 + fmax / 700.0);
+    std::vector<double> c(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; ++i) c[i] = 700.0 * (std::pow(10.0, (m0 + (m1 - m0) * i / (n_mels + 1)) / 2595.0) - 1.0);
+    c[0] = fmin; c[n_mels + 1] = fmax;
+    std::vector<int32_t> b0(K, 0), lo(n_mels, K), hi(n_mels, 0), cnt(n_mels, 0);
+    std::vector<float> w0(K, 0.f), w1(K, 0.f);
+    for (int k = 0; k < K; ++k) {
+        const double f = (double)k * sample_rate / (double)n_fft;
+        int found = 0;
+        for (int b = 0; b < n_mels; ++b) {
+            const double up = (f - c[b]) / (c[b + 1] - c[b]), down = (c[b + 2] - f) / (c[b + 2] - c[b + 1]);
+            double v = up < down ? up : down;
+            if (!(v > 0.0)) continue;
+            if (norm == 1) v *= 2.0 / (c[b + 2] - c[b]);
+            const float v32 = (float)v;                          // the one rounding
+            if (!(v32 > 0.f)) continue;
+            if (found == 0) { b0[k] = b; w0[k] = v32; }
+            else if (found == 1 && b == b0[k] + 1) w1[k] = v32;
+            else return fail(WUN_ERR_INVALID, w + ": a bin weighted by more than two adjacent bands");
+            ++found;
+            if (k < lo[b]) lo[b] = k;
+            hi[b] = k + 1;
+            ++cnt[b];
+        }
+    }
+    for (int b = 0; b < n_mels; ++b) {
+        if (cnt[b] == 0)
+            return fail(WUN_ERR_INVALID, w + ": band " + std::to_string(b) + " of " + std::to_string(n_mels) +
+                        " weights no bin (it lies between two bins of this n_fft): fewer bands, a longer window or a higher fmin");
+        if (cnt[b] != hi[b] - lo[b]) return fail(WUN_ERR_INVALID, w + ": band " + std::to_string(b) + " is not one run of bins");
+    }
+    int32_t* ti = (int32_t*)table_host;
+    for (int k = 0; k < K; ++k) { ti[k] = b0[k]; table_host[K + k] = w0[k]; table_host[2 * K + k] = w1[k]; }
+    for (int b = 0; b < n_mels; ++b) { ti[3 * K + b] = lo[b]; ti[3 * K + n_mels + b] = hi[b]; }
+    return WUN_OK;
+}
+
+namespace {
+
+int check_mel_op(const char* who, const void* a, const void* table, const void* out, int64_t M, int32_t K, int32_t n_mels) {
+    const std::string w(who);
+    if (!a || !table || !out) return fail(WUN_ERR_INVALID, w + ": null argument");
+    if (M < 1 || M > ((int64_t)1 << 30)) return fail(WUN_ERR_INVALID, w + ": M outside 1..2^30");
+    const int32_t n_fft = 2 * (K - 1);
+    if (K < 33 || K > 4097 || (n_fft & (n_fft - 1))) return fail(WUN_ERR_INVALID, w + ": K must be n_fft / 2 + 1 of a power of two in 64..8192");
+    if (n_mels < 1 || n_mels > WUN_MEL_MAX) return fail(WUN_ERR_INVALID, w + ": n_mels outside 1..512");
+    return WUN_OK;
+}
+
+}  // namespace
+
+extern "C" int wun_op_mel_project(const float* mags, int64_t M, int32_t K, int32_t n_mels, const float* mel_table_dev, float* out,
+                                  void* stream) {
+    int rc;
+    if ((rc = check_mel_op("wun_op_mel_project", mags, mel_table_dev, out, M, K, n_mels))) return rc;
+    launch_mel_project(mags, nullptr, out, nullptr, mel_table_dev, M, K, n_mels, (hipStream_t)stream);
+    return launch_status("wun_op_mel_project");
+}
+
+extern "C" int wun_op_mel_project_transpose(const float* g, int64_t M, int32_t K, int32_t n_mels, const float* mel_table_dev,
+                                            float* q, void* stream) {
+    int rc;
+    if ((rc = check_mel_op("wun_op_mel_project_transpose", g, mel_table_dev, q, M, K, n_mels))) return rc;
+    const long long E = (long long)M * K;
+    hipLaunchKernelGGL(mel_transpose_kernel, dim3((unsigned)((E + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK)), dim3(WUN_STFT_BLOCK), 0,
+                       (hipStream_t)stream, g, mel_table_dev, q, E, K, n_mels);
+    return launch_status("wun_op_mel_project_transpose");
+}
+
+extern "C" int64_t wun_spectral_mel_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres, const int32_t* n_fft,
+                                                   const int32_t* hop, const wun_spectral_terms* terms, const wun_mel_terms* mel,
+                                                   const int32_t* n_mels) {
+    const MelCall mc = {mel, n_mels, nullptr};
+    return terms_scratch_entry("wun_spectral_mel_scratch_floats", WUN_TR_GEMM, S, B, Tout, C, nres, n_fft, hop, terms, &mc);
+}
+extern "C" int64_t wun_spectral_mel_fft_scratch_floats(int32_t S, int32_t B, int64_t Tout, int32_t C, int32_t nres,
+                                                       const int32_t* n_fft, const int32_t* hop, const wun_spectral_terms* terms,
+                                                       const wun_mel_terms* mel, const int32_t* n_mels) {
+    const MelCall mc = {mel, n_mels, nullptr};
+    return terms_scratch_entry("wun_spectral_mel_fft_scratch_floats", WUN_TR_FFT, S, B, Tout, C, nres, n_fft, hop, terms, &mc);
+}
+
+extern "C" int wun_spectral_loss_mel(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                     float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop, const float* weights,
+                                     const wun_spectral_terms* terms, const float* const* tables_dev, float* d_outputs,
+                                     float* losses, float* scratch, void* stream, const wun_mel_terms* mel, const int32_t* n_mels,
+                                     const float* const* mel_tables_dev) {
+    const MelCall mc = {mel, n_mels, mel_tables_dev};
+    return terms_entry("wun_spectral_loss_mel", WUN_TR_GEMM, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop, weights,
+                       terms, tables_dev, d_outputs, losses, scratch, stream, &mc);
+}
+extern "C" int wun_spectral_loss_mel_fft(const float* outputs, const float* targets, int32_t S, int32_t B, int64_t Tout, int32_t C,
+                                         float mse_weight, int32_t nres, const int32_t* n_fft, const int32_t* hop,
+                                         const float* weights, const wun_spectral_terms* terms, const float* const* tables_dev,
+                                         float* d_outputs, float* losses, float* scratch, void* stream, const wun_mel_terms* mel,
+                                         const int32_t* n_mels, const float* const* mel_tables_dev) {
+    const MelCall mc = {mel, n_mels, mel_tables_dev};
+    return terms_entry("wun_spectral_loss_mel_fft", WUN_TR_FFT, outputs, targets, S, B, Tout, C, mse_weight, nres, n_fft, hop,
+                       weights, terms, tables_dev, d_outputs, losses, scratch, stream, &mc);
 }

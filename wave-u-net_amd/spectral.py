@@ -15,6 +15,10 @@ Hann window, no padding), for any number of resolutions up to 8, next to the tim
     re, im = stft(x, 4096, 1024, centered=True, transform="fft")  # the same definitions through an FFT, n_fft up to 8192 (5.13)
     loss = SpectralLoss([(4096, 1024)], terms={"sc": 1, "log_mag_l1": 1}, log_eps=4.0, transform="fft")    # the loss too (5.16)
     loss = SpectralLoss.multi_resolution(transform="fft")         # the same three resolutions, both frame transforms as FFTs
+    loss = SpectralLoss.multi_scale_mel(22050)                    # mel L1 + log-mel L1 at 512 / 1024 / 2048, 40 / 80 / 160 bands (5.19)
+    loss = SpectralLoss([(1024, 256)], terms={"sc": 1}, mel={"n_mels": 80, "sample_rate": 22050, "terms": {"log_mel_l1": 1}})
+    mel_spectrogram(x, 1024, 256, 80, 22050)                      # [S, B, C, F, n_mels], the floats the mel terms are taken on
+    mel_filterbank(1024, 22050, 80)                               # the dense [n_mels, K] weights, rebuilt from the library's table
 
 Audio is float32 [S, B, T, C] channel-last on the GPU, as get_output stacks its outputs.  There is no CPU path.
 """
@@ -28,6 +32,8 @@ from . import _lib
 
 MAX_RESOLUTIONS = 8
 TERMS = ("mag_l1", "log_mag_l1", "sc", "complex_l1")       # the order of the term slots of wun_spectral_loss_terms' losses
+MEL_TERMS = ("mel_l1", "log_mel_l1")                         # the order of the mel slots behind them (wun_spectral_loss_mel)
+MAX_MELS = 512
 TRANSFORMS = ("gemm", "fft")
 # (transform, operation) -> the library's entry.  "table": wun_*_table_floats, wun_*_design and the table's leading dimension.
 _ENTRIES = {
@@ -38,7 +44,8 @@ _ENTRIES = {
              "mask_filter_scratch": "wun_mask_filter_scratch_floats", "wiener_filter": "wun_wiener_filter",
              "wiener_filter_scratch": "wun_wiener_filter_scratch_floats", "magnitude": "wun_stft_magnitude",
              "loss": "wun_spectral_loss", "loss_scratch": "wun_spectral_scratch_floats", "loss_terms": "wun_spectral_loss_terms",
-             "loss_terms_scratch": "wun_spectral_terms_scratch_floats"},
+             "loss_terms_scratch": "wun_spectral_terms_scratch_floats", "loss_mel": "wun_spectral_loss_mel",
+             "loss_mel_scratch": "wun_spectral_mel_scratch_floats"},
     "fft": {"table": ("wun_fft_table_floats", "wun_fft_design", 3), "frames": "wun_fft_frames",
             "centered_frames": "wun_fft_centered_frames", "stft": "wun_stft_complex_fft", "istft": "wun_istft_fft",
             "istft_scratch": "wun_istft_fft_scratch_floats", "istft_tf": "wun_istft_tf_fft",
@@ -46,9 +53,12 @@ _ENTRIES = {
             "mask_filter_scratch": "wun_mask_filter_fft_scratch_floats", "wiener_filter": "wun_wiener_filter_fft",
             "wiener_filter_scratch": "wun_wiener_filter_fft_scratch_floats", "magnitude": "wun_stft_magnitude_fft",
             "loss": "wun_spectral_loss_fft", "loss_scratch": "wun_spectral_fft_scratch_floats",
-            "loss_terms": "wun_spectral_loss_terms_fft", "loss_terms_scratch": "wun_spectral_terms_fft_scratch_floats"},
+            "loss_terms": "wun_spectral_loss_terms_fft", "loss_terms_scratch": "wun_spectral_terms_fft_scratch_floats",
+            "loss_mel": "wun_spectral_loss_mel_fft", "loss_mel_scratch": "wun_spectral_mel_fft_scratch_floats"},
 }
 _TABLES = {}     # (transform, n_fft, device) -> device tensor holding the transform's table
+_MEL_TABLES = {}  # (n_fft, sample_rate, n_mels, fmin, fmax, norm, device) -> device tensor holding the mel table's words
+_MEL_NORMS = {None: 0, "none": 0, 0: 0, "area": 1, 1: 1}
 
 
 def entry(transform, op):
@@ -134,6 +144,64 @@ def stft_magnitude(x, n_fft, hop, transform="gemm"):
         _lib.check(fn(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), table(n_fft, x.device).data_ptr(), mags.data_ptr(),
                       _stream(x.device)))
     return mags
+
+
+def _mel_key(n_fft, sample_rate, n_mels, fmin, fmax, norm):
+    if norm not in _MEL_NORMS:
+        raise ValueError("norm must be None or 'area', got %r" % (norm,))
+    return int(n_fft), float(sample_rate), int(n_mels), float(fmin), 0.0 if fmax is None else float(fmax), _MEL_NORMS[norm]
+
+
+def mel_design(n_fft, sample_rate, n_mels, fmin=0.0, fmax=None, norm=None):
+    """The mel table's 3 K + 2 n_mels words as an int32 numpy array (wun_mel_design, include/wun.h): b0[K], the bits of the
+    float32 w0[K] and w1[K], lo[n_mels], hi[n_mels].  ValueError for what the library refuses -- an empty band among it."""
+    key = _mel_key(n_fft, sample_rate, n_mels, fmin, fmax, norm)
+    lib = _lib.load()
+    n = int(lib.wun_mel_table_floats(key[0], key[2]))
+    if n < 0:
+        _lib.check(n)
+    table = np.zeros(n, np.float32)
+    _lib.check(lib.wun_mel_design(key[0], key[1], key[2], key[3], key[4], key[5], table.ctypes.data_as(C.POINTER(C.c_float)), n))
+    return table.view(np.int32)
+
+
+def mel_table_parts(words, n_fft, n_mels):
+    """(b0, w0, w1, lo, hi) views of mel_design's words."""
+    K = int(n_fft) // 2 + 1
+    return (words[:K], words[K:2 * K].view(np.float32), words[2 * K:3 * K].view(np.float32), words[3 * K:3 * K + n_mels],
+            words[3 * K + n_mels:3 * K + 2 * n_mels])
+
+
+def mel_filterbank(n_fft, sample_rate, n_mels, fmin=0.0, fmax=None, norm=None):
+    """The float32 weights W [n_mels, K] of the HTK-scale triangular filterbank (include/wun.h), rebuilt from the library's
+    table: fmax=None is sample_rate / 2, norm=None or "area"."""
+    b0, w0, w1, _, _ = mel_table_parts(mel_design(n_fft, sample_rate, n_mels, fmin, fmax, norm), n_fft, n_mels)
+    W = np.zeros((int(n_mels), b0.size), np.float32)
+    k = np.arange(b0.size)
+    for b, w in ((b0, w0), (b0 + 1, w1)):
+        ok = (w > 0) & (b >= 0) & (b < int(n_mels))
+        W[b[ok], k[ok]] = w[ok]
+    return W
+
+
+def _mel_table(n_fft, sample_rate, n_mels, fmin, fmax, norm, device):
+    key = _mel_key(n_fft, sample_rate, n_mels, fmin, fmax, norm) + (str(device),)
+    if key not in _MEL_TABLES:
+        _MEL_TABLES[key] = torch.from_numpy(mel_design(n_fft, sample_rate, n_mels, fmin, fmax, norm)).to(device)
+    return _MEL_TABLES[key]
+
+
+def mel_spectrogram(x, n_fft, hop, n_mels, sample_rate, fmin=0.0, fmax=None, norm=None, transform="gemm"):
+    """The mel magnitudes of audio x [S, B, T, C]: float32 [S, B, C, F, n_mels], stft_magnitude's floats projected onto the
+    filterbank (wun_op_mel_project: one ascending fmaf chain per band).  The floats the mel terms of a SpectralLoss with the
+    same arguments are taken on.  No sync."""
+    table = _mel_table(n_fft, sample_rate, n_mels, fmin, fmax, norm, x.device)       # (refusals before any launch)
+    mags = stft_magnitude(x, n_fft, hop, transform)
+    out = torch.empty(mags.shape[:4] + (int(n_mels),), dtype=torch.float32, device=mags.device)
+    with torch.cuda.device(mags.device):
+        _lib.check(_lib.load().wun_op_mel_project(mags.data_ptr(), mags.numel() // mags.shape[4], int(mags.shape[4]), int(n_mels),
+                                                  table.data_ptr(), out.data_ptr(), _stream(mags.device)))
+    return out
 
 
 def centered_frames(n, n_fft, hop, transform="gemm"):
@@ -226,12 +294,19 @@ class SpectralLoss(object):
     resolution 0, of resolution 1, ..] (term_losses).  log_eps and sc_eps are choices, not measurements: 1e-3 sits above the
     fp32 transform's error on unit-scale audio at short frames (raise it with n_fft), 1.0 keeps a silent source finite.
 
+    mel=None: nothing below.  mel={"n_mels": int or one per resolution, "sample_rate": Hz, "fmin": 0, "fmax": None, "norm": None,
+    "terms": {name: weight} over MEL_TERMS (default both 1), "log_eps": 1e-3}: L_j gains weight * "mel_l1", the mean |Pe - Pt|
+    of the mel magnitudes (mel_spectrogram's floats), and weight * "log_mel_l1", the mean |log(Pe + log_eps) - log(Pt + log_eps)|
+    (wun_spectral_loss_mel).  losses is then [2 + 7 nres]: the 2 + 5 nres slots above, then mel_l1, log_mel_l1 of
+    resolution 0, of resolution 1, ..; with terms=None no linear-frequency term is computed.  The mel log_eps of 1e-3 is a
+    choice, not a measurement.  A filterbank with a band that weights no bin is refused (ValueError) at construction.
+
     transform="gemm": both frame transforms of a resolution as GEMMs against an n_fft^2 table, n_fft up to 2048.  "fft": as
     FFTs (the *_fft entries), n_fft up to 8192 -- the same definitions, slots and summation order, results
     equal to float32 rounding.  ValueError for any other name."""
 
     def __init__(self, resolutions=((1024, 768),), weights=None, mse_weight=0.0, terms=None, log_eps=1e-3, sc_eps=1.0,
-                 transform="gemm"):
+                 transform="gemm", mel=None):
         if transform not in _ENTRIES:
             raise ValueError("transform must be one of %s, got %r" % (", ".join(TRANSFORMS), transform))
         self.transform = transform
@@ -247,6 +322,10 @@ class SpectralLoss(object):
                 raise ValueError("weights must be finite and >= 0, got %r" % (w,))
         self.terms, self.log_eps, self.sc_eps = None, float(log_eps), float(sc_eps)
         self._terms = None       # the entry's wun_spectral_terms (None: wun_spectral_loss)
+        self.mel = self._mel = None      # the mel arguments as given (defaults filled in); the entry's wun_mel_terms
+        if mel is not None:
+            self._init_mel(mel)
+            terms = {} if terms is None else terms       # no linear-frequency term unless asked for
         if terms is not None:
             unknown = set(terms) - set(TERMS)
             if unknown:
@@ -265,17 +344,61 @@ class SpectralLoss(object):
         self._w = (C.c_float * n)(*self.weights)
         self._scratch = {}       # (shape, device) -> float32 scratch of the entry's *_scratch_floats
 
+    def _init_mel(self, mel):
+        known = {"n_mels", "sample_rate", "fmin", "fmax", "norm", "terms", "log_eps"}
+        unknown = set(mel) - known
+        if unknown:
+            raise ValueError("mel: unknown keys %s (known: %s)" % (sorted(unknown), ", ".join(sorted(known))))
+        for need in ("n_mels", "sample_rate"):
+            if need not in mel:
+                raise ValueError("mel: `%s` is required" % need)
+        nres = len(self.resolutions)
+        n_mels = mel["n_mels"]
+        n_mels = [int(n_mels)] * nres if np.isscalar(n_mels) else [int(n) for n in n_mels]
+        if len(n_mels) != nres:
+            raise ValueError("mel: %d band counts for %d resolutions" % (len(n_mels), nres))
+        mterms = mel.get("terms")
+        mterms = {t: 1.0 for t in MEL_TERMS} if mterms is None else mterms
+        unknown = set(mterms) - set(MEL_TERMS)
+        if unknown:
+            raise ValueError("mel terms: unknown names %s (known: %s)" % (sorted(unknown), ", ".join(MEL_TERMS)))
+        mterms = {t: float(mterms.get(t, 0.0)) for t in MEL_TERMS}
+        for w in mterms.values():
+            if not (w >= 0.0 and np.isfinite(w)):
+                raise ValueError("mel term weights must be finite and >= 0, got %r" % (w,))
+        eps = float(mel.get("log_eps", 1e-3))
+        if not (eps > 0.0 and np.isfinite(eps)):
+            raise ValueError("mel log_eps must be finite and > 0, got %r" % (eps,))
+        self.mel = {"n_mels": n_mels, "sample_rate": float(mel["sample_rate"]), "fmin": float(mel.get("fmin", 0.0) or 0.0),
+                    "fmax": mel.get("fmax"), "norm": mel.get("norm"), "terms": mterms, "log_eps": eps}
+        for (n_fft, _), n in zip(self.resolutions, n_mels):      # the library's refusals now, not at the first step
+            mel_design(n_fft, self.mel["sample_rate"], n, self.mel["fmin"], self.mel["fmax"], self.mel["norm"])
+        self._mel = _lib.WunMelTerms(mterms["mel_l1"], mterms["log_mel_l1"], eps)
+        self._n_mels = (C.c_int32 * max(nres, 1))(*n_mels)
+
+    def _mel_tables(self, device):
+        m = self.mel
+        return [_mel_table(n_fft, m["sample_rate"], n, m["fmin"], m["fmax"], m["norm"], device)
+                for (n_fft, _), n in zip(self.resolutions, m["n_mels"])]
+
     @classmethod
     def from_config(cls, spec):
         """model_config["spectral_loss"]: None, a SpectralLoss, or a dict with `resolutions`, `weights`, `mse_weight`, `terms`,
-        `log_eps`, `sc_eps`, `transform`."""
+        `log_eps`, `sc_eps`, `transform`, `mel` (the dict of the `mel` argument)."""
         if spec is None or isinstance(spec, cls):
             return spec
-        unknown = set(spec) - {"resolutions", "weights", "mse_weight", "terms", "log_eps", "sc_eps", "transform"}
+        unknown = set(spec) - {"resolutions", "weights", "mse_weight", "terms", "log_eps", "sc_eps", "transform", "mel"}
         if unknown:
             raise ValueError("spectral_loss: unknown keys %s" % sorted(unknown))
         return cls(spec.get("resolutions", ((1024, 768),)), spec.get("weights"), spec.get("mse_weight", 0.0), spec.get("terms"),
-                   spec.get("log_eps", 1e-3), spec.get("sc_eps", 1.0), spec.get("transform", "gemm"))
+                   spec.get("log_eps", 1e-3), spec.get("sc_eps", 1.0), spec.get("transform", "gemm"), spec.get("mel"))
+
+    @classmethod
+    def multi_scale_mel(cls, sample_rate, transform="gemm"):
+        """The usual multi-scale mel loss: mel L1 + log-mel L1 at windows 512 / 1024 / 2048, hop a quarter of each, 40 / 80 / 160
+        bands from 0 to sample_rate / 2 -- every band weights a bin at 22 050 Hz; ValueError at a rate where one does not."""
+        return cls([(512, 128), (1024, 256), (2048, 512)], transform=transform,
+                   mel={"n_mels": [40, 80, 160], "sample_rate": sample_rate, "terms": {t: 1.0 for t in MEL_TERMS}})
 
     @classmethod
     def multi_resolution(cls, transform="gemm", resolutions=None):
@@ -287,23 +410,34 @@ class SpectralLoss(object):
 
     @property
     def num_losses(self):
-        """Floats of `losses`: 2 + nres, with terms 2 + 5 nres."""
-        return 2 + (1 if self._terms is None else 5) * len(self.resolutions)
+        """Floats of `losses`: 2 + nres, with terms 2 + 5 nres, with mel 2 + 7 nres."""
+        return 2 + (7 if self._mel is not None else 1 if self._terms is None else 5) * len(self.resolutions)
+
+    def term_weight(self, name):
+        """The weight of a term of term_losses."""
+        return self.mel["terms"][name] if name in MEL_TERMS else self.terms[name]
 
     def term_losses(self, losses):
-        """{name: [nres] view of `losses`}: the unweighted terms per resolution (terms= only)."""
+        """{name: [nres] view of `losses`}: the unweighted terms per resolution (terms= or mel= only; with mel= the two mel
+        terms too)."""
         if self._terms is None:
             raise ValueError("term_losses needs a SpectralLoss built with terms=")
         nres = len(self.resolutions)
         per = losses[2 + nres:2 + 5 * nres].view(nres, 4)
-        return {t: per[:, i] for i, t in enumerate(TERMS)}
+        out = {t: per[:, i] for i, t in enumerate(TERMS)}
+        if self._mel is not None:
+            mper = losses[2 + 5 * nres:2 + 7 * nres].view(nres, 2)
+            out.update({t: mper[:, i] for i, t in enumerate(MEL_TERMS)})
+        return out
 
     def scratch_floats(self, shape):
         S, B, T, Cn = (int(v) for v in shape)
         args = (S, B, T, Cn, len(self.resolutions), self._n_fft, self._hop)
         if self._terms is None:
             return count(self.transform, "loss_scratch", *args)
-        return count(self.transform, "loss_terms_scratch", *(args + (C.byref(self._terms),)))
+        if self._mel is None:
+            return count(self.transform, "loss_terms_scratch", *(args + (C.byref(self._terms),)))
+        return count(self.transform, "loss_mel_scratch", *(args + (C.byref(self._terms), C.byref(self._mel), self._n_mels)))
 
     def _scratch_for(self, x):
         key = (tuple(x.shape), str(x.device))
@@ -312,20 +446,25 @@ class SpectralLoss(object):
         return self._scratch[key]
 
     def run(self, outputs, targets, d_outputs, losses, scratch):
-        """wun_spectral_loss (with terms: wun_spectral_loss_terms; transform="fft": their _fft twins) on the caller's buffers
+        """wun_spectral_loss (with terms: wun_spectral_loss_terms, with mel: wun_spectral_loss_mel; transform="fft": their _fft
+        twins) on the caller's buffers
         (contiguous float32 device tensors; losses of num_losses floats; d_outputs may be None)."""
         S, B, T, Cn = (int(v) for v in outputs.shape)
         dev = outputs.device
         nres = len(self.resolutions)
-        fn, table = entry(self.transform, "loss" if self._terms is None else "loss_terms")
+        fn, table = entry(self.transform, "loss" if self._terms is None else "loss_terms" if self._mel is None else "loss_mel")
         tabs = (C.c_void_p * max(nres, 1))(*[table(n, dev).data_ptr() for n, _ in self.resolutions])
         head = (outputs.data_ptr(), targets.data_ptr(), S, B, T, Cn, self.mse_weight, nres, self._n_fft, self._hop, self._w)
         tail = (tabs, d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(), _stream(dev))
         with torch.cuda.device(dev):
             if self._terms is None:
                 _lib.check(fn(*(head + tail)))
-            else:
+            elif self._mel is None:
                 _lib.check(fn(*(head + (C.byref(self._terms),) + tail)))
+            else:
+                mtabs = self._mel_tables(dev)
+                mptr = (C.c_void_p * max(nres, 1))(*[t.data_ptr() for t in mtabs])
+                _lib.check(fn(*(head + (C.byref(self._terms),) + tail + (C.byref(self._mel), self._n_mels, mptr))))
 
     def loss_and_grad(self, outputs, targets, grad=True):
         """(losses, d_outputs): losses float32 [num_losses] on the device = [total, MSE, L_0, ...] (L_j unweighted; with terms

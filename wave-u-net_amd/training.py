@@ -248,11 +248,12 @@ class Trainer(object):
         return l[1], sum(w * x for w, x in zip(self.spectral.weights, l[2:]))
 
     def term_parts(self):
-        """{term: sum_j weights[j] * termweight * term(j)} of the last step with a spectral loss built with terms= (host sync):
+        """{term: sum_j weights[j] * termweight * term(j)} of the last step with a spectral loss built with terms= or mel= (the
+        mel terms only with mel=; host sync):
         the parts of loss_parts()' second value."""
         sp = self.spectral
         per = {t: v.tolist() for t, v in sp.term_losses(self.last_losses).items()}
-        return {t: sp.terms[t] * sum(w * x for w, x in zip(sp.weights, per[t])) for t in per}
+        return {t: sp.term_weight(t) * sum(w * x for w, x in zip(sp.weights, per[t])) for t in per}
 
 
     def waveform_parts(self):
