@@ -1005,6 +1005,46 @@ int     wun_spec_adam_step(const wun_spec_config* cfg, const wun_spec_train_conf
                            float* m, float* v, const float* workspace, int32_t B, int64_t T, int64_t step, float lr, float beta1,
                            float beta2, float eps, float grad_scale, void* stream);
 
+/* ---- the spectrogram U-Net: backward from any loss, on magnitudes or audio ------
+ * The training forward's two outputs are mags_s = M mask_s [S][B][F][K] and audio_s = ISTFT_tf(mask_s X) [S][B][T][1]; these entries
+ * give the second one and the backward pass from an upstream gradient on either or both, in place of the objective compiled into
+ * wun_spec_loss_backward.  All of them read what the last wun_spec_train_forward on that workspace retained (X, M, the masks, every
+ * z, activation, batch mean and variance, the dropout masks) and leave it unchanged; they take that call's (cfg, tcfg, B, T).
+ *   adjoint of ISTFT_tf   u[t] = d_audio[t] / D[t mod hop], D[p] = sum_i w^2[p + i hop] in float64 (i ascending, the squares as
+ *                         wun_istft_tf_fft forms them) ROUNDED ONCE to float32: the kernel DIVIDES by the rounded D, as the forward
+ *                         does, and does not multiply by a reciprocal.  G = STFT(u) in the forward's framing, window and FFT;
+ *                         ga[k] = c_k fmaf(Re X[k], Re G[k], Im X[k] Im G[k]), c_0 = 1 / n_fft, c_k = 2 / n_fft for 0 < k < K - 1.
+ *                         G is never stored: the gradient is the FFT kernel's epilogue.
+ *   head, k < K - 1       d_mags alone: dmask = d_mags M;  d_audio alone: dmask = ga;  both: dmask = fmaf(d_mags, M, ga);
+ *                         dz = dmask * (mask * (1 - mask)).  Bin K - 1 (mask 0.5) receives no gradient from either domain.
+ *                         With d_mags = -sign(R - M mask) / (S B F K) in float32 the gradients are wun_spec_loss_backward's bits.
+ *   body                  the backward of the previous section from dz on: same launches, order and arithmetic.  grads gets
+ *                         every float written; the moving statistics' slots are 0.
+ * The gradient with respect to the mix is not built.  Contract as the previous section: the caller's buffers, no allocation, no
+ * sync, every check before any GPU work, no atomics; the bits depend on neither the grid, what the scratch held nor pointer
+ * alignment beyond 4 bytes.  The backward entries may be called any number of times after one forward, in any order with
+ * wun_spec_loss_backward: each call gives the bits of the first.
+ * WUN_ERR_INVALID for a null pointer, both gradients null, the shape conditions, a bad tcfg, or a workspace, scratch or gradient
+ * buffer that overlaps another buffer; WUN_ERR_UNSUPPORTED for an n_fft outside the list or a resolution wun_istft_tf_fft refuses.
+ *
+ * scratch of the audio output, floats:  2 ceil4(S B F K) + wun_istft_tf_fft_scratch_floats of (S, B, T, 1, n_fft, hop, F)
+ *   (the masked spectra of all sources, Re then Im, then the inverse transform's own scratch; ceil4 rounds up to a multiple of 4)
+ *   audio : device [S, B, T, 1], every float written;  workspace : the training workspace, read only */
+int64_t wun_spec_train_audio_scratch_floats(const wun_spec_config* cfg, int32_t B, int64_t T);
+int     wun_spec_train_audio(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, int32_t B, int64_t T,
+                             const float* table_dev, float* audio, const float* workspace, float* scratch, void* stream);
+/* scratch of the backward, floats:  ceil4(hop) + B T   (D, then u of one source; the same with d_audio null)
+ *   d_mags : device [S, B, F, K] or NULL;  d_audio : device [S, B, T, 1] or NULL;  at least one
+ *   grads  : device, wun_spec_param_floats floats; wun_spec_adam_step takes them as it takes wun_spec_loss_backward's */
+int64_t wun_spec_backward_scratch_floats(const wun_spec_config* cfg, int32_t B, int64_t T);
+int     wun_spec_backward(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, const float* params, const float* d_mags,
+                          const float* d_audio, int32_t B, int64_t T, const float* table_dev, float* grads, float* workspace,
+                          float* scratch, void* stream);
+/* The UPDATE_OPS alone: the moving averages of wun_spec_adam_step from the batch statistics of the last forward, the same launch
+ * and bits, for callers whose optimizer is not wun_spec_adam_step.  The workspace is read only. */
+int     wun_spec_update_moving_averages(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, float* params,
+                                        const float* workspace, int32_t B, int64_t T, void* stream);
+
 /* tf.contrib.signal.inverse_stft with inverse_stft_window_fn(hop): wun_istft in the framing without padding (lead 0), except for
  * the normaliser:  y[t] = (sum_f frame_f[t - f hop]) / D[t mod hop],  D[p] = sum_i w^2[p + i hop] over 0 <= p + i hop < n_fft
  * (i ascending, float64) -- the steady-state window-square sum, at the track's edges too, where wun_istft divides by the sum
@@ -1053,6 +1093,15 @@ int     wun_op_conv2d_transpose_s2_wgrad(const float* x0, int c0, const float* x
  * pixels added in a fixed order, rounded to float32 once each. */
 int64_t wun_op_bn2d_stats_scratch(int B, int H, int W, int C);
 int     wun_op_bn2d_stats(const float* z, float* mean, float* var, float* scratch, int B, int H, int W, int C, void* stream);
+
+/* The head of wun_spec_backward for one source, without a network: dz [B][F][K - 1] from re, im, mag [B][F][K] (X and M of the
+ * mix), mask [B][F][K - 1], d_mags [B][F][K] or NULL and d_audio [B][T] or NULL (at least one), by the formulas of that section.
+ * T == (F - 1) hop + n_fft, n_fft a power of two in 64..8192, hop in 1..n_fft; table_dev is wun_fft_design's table.
+ * scratch, floats:  ceil4(hop) + B T;  it may overlap neither dz nor an operand, nor dz an operand. */
+int64_t wun_op_spec_head_backward_scratch(int32_t B, int64_t T, int32_t n_fft, int32_t hop);
+int     wun_op_spec_head_backward(const float* re, const float* im, const float* mag, const float* mask, const float* d_mags,
+                                  const float* d_audio, int32_t B, int64_t T, int32_t n_fft, int32_t hop, const float* table_dev,
+                                  float* dz, float* scratch, void* stream);
 
 /* y[b][co][q] = act(bias[co] + sum_{k,ci} w[k][ci][co] * x[b][ci][q*stride + k - pad_left]),
  * x zero outside [0, t_in).  NCW float32, w in TF layout [K, Cin, Cout].

@@ -190,6 +190,16 @@ _SIGS = {
                                          _P, _P, _P, _P]),
     "wun_spec_adam_step": (C.c_int, [C.POINTER(WunSpecConfig), C.POINTER(WunSpecTrainConfig), _P, _P, _P, _P, _P, C.c_int32,
                                      C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P]),
+    "wun_spec_train_audio_scratch_floats": (C.c_int64, [C.POINTER(WunSpecConfig), C.c_int32, C.c_int64]),
+    "wun_spec_train_audio": (C.c_int, [C.POINTER(WunSpecConfig), C.POINTER(WunSpecTrainConfig), C.c_int32, C.c_int64, _P, _P, _P, _P,
+                                       _P]),
+    "wun_spec_backward_scratch_floats": (C.c_int64, [C.POINTER(WunSpecConfig), C.c_int32, C.c_int64]),
+    "wun_spec_backward": (C.c_int, [C.POINTER(WunSpecConfig), C.POINTER(WunSpecTrainConfig), _P, _P, _P, C.c_int32, C.c_int64, _P,
+                                    _P, _P, _P, _P]),
+    "wun_spec_update_moving_averages": (C.c_int, [C.POINTER(WunSpecConfig), C.POINTER(WunSpecTrainConfig), _P, _P, C.c_int32,
+                                                  C.c_int64, _P]),
+    "wun_op_spec_head_backward_scratch": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
+    "wun_op_spec_head_backward": (C.c_int, [_P] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "wun_op_conv2d_s2_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
     "wun_op_conv2d_s2_wgrad": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [_P]),
     "wun_op_conv2d_transpose_s2_wgrad_scratch": (C.c_int64, [C.c_int] * 5),

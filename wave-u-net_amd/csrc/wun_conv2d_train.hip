@@ -1,6 +1,8 @@
 // gfx950 (MI355X / CDNA4): one training step of the spectrogram U-Net for the magnitude objective (include/wun.h:
 // wun_spec_train_forward, wun_spec_loss_backward, wun_spec_adam_step, wun_op_conv2d_s2_wgrad, wun_op_conv2d_transpose_s2_wgrad,
-// wun_op_bn2d_stats; Models/UnetSpectrogramSeparator.py:63-92 at training = True, Training.py:47-77).
+// wun_op_bn2d_stats; Models/UnetSpectrogramSeparator.py:63-92 at training = True, Training.py:47-77), and the same
+// backward pass from any upstream gradient on the magnitudes, the audio or both (wun_spec_backward, wun_spec_train_audio,
+// wun_spec_update_moving_averages, wun_op_spec_head_backward).
 //
 //   forward    every layer with a batch norm: z = conv + bias (wun_conv2d.hip's kernels, act 0), per channel mu = mean z and
 //              var = mean (z - mu)^2 (biased, two passes), a = act((z - mu) / sqrt(var + 1e-3) + beta).  Dropout multiplies the
@@ -14,6 +16,9 @@
 //              is cut into chunks of WUN_WG_CHUNK pixels (a function of the shapes alone), one workgroup per (tile, chunk)
 //              writes its partial tile to scratch, a second pass adds the chunks in ascending order.  Exact-fp32 MFMA on
 //              wun_stft.h's tile where both channel counts exceed 1, one lane per output on the VALU otherwise.
+//   head       wun_spec_backward's first launches per source in place of the loss's: dz of the mask layer from d_mags (one lane
+//              per bin) and / or d_audio (u = d_audio / D, then wun_fft.hip's forward FFT with the mask gradient as its epilogue);
+//              everything behind dz is network_backward, the one body of both entries
 //   sums       per-channel sums (statistics, the two means of the batch-norm backward, bias gradients) and the loss are float64
 //              partials over 1024 consecutive pixels / bins, added in ascending order by one fixed tree.  No atomics anywhere:
 //              the bits depend on neither the grid, what the workspace held nor pointer alignment beyond 4 bytes.
@@ -23,6 +28,7 @@
 // Built WITHOUT the packed fp32 VALU instructions (csrc/Makefile NO_PK_FP32).  Every argument check runs before
 // any GPU work; nothing allocates or synchronises.
 #include "wun_conv2d.h"
+#include "wun_fft.h"
 
 #include <cmath>
 #include <cstring>
@@ -335,6 +341,20 @@ __global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_loss_kernel(const float* 
     if (tid == 0) part[blockIdx.x] = s;
 }
 
+// The head of wun_spec_backward for an upstream gradient on the magnitudes alone: one lane per bin (grid-stride),
+// dz = (d_mags M) * (mask (1 - mask)) for k < K - 1.  With d_mags = -sign(R - M mask) cm it writes spec_loss_kernel's bits.
+__global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_head_mags_kernel(const float* __restrict__ dmags, const float* __restrict__ mag,
+                                                                       const float* __restrict__ mask, float* __restrict__ dz,
+                                                                       long long E, int K) {
+    for (long long e = (long long)blockIdx.x * WUN_STFT_BLOCK + threadIdx.x; e < E; e += (long long)gridDim.x * WUN_STFT_BLOCK) {
+        const long long bf = e / K;
+        const int k = (int)(e - bf * K);
+        if (k == K - 1) continue;
+        const float mk = mask[bf * (K - 1) + k];
+        dz[bf * (K - 1) + k] = (dmags[e] * mag[e]) * (mk * (1.0f - mk));
+    }
+}
+
 // one block: losses[1 + s] = mean of source s, losses[0] = their mean
 __global__ __launch_bounds__(WUN_STFT_BLOCK) void spec_loss_finish_kernel(const double* __restrict__ part, long long blocks, int S,
                                                                          double inv_e, float* __restrict__ losses) {
@@ -569,6 +589,114 @@ SrcVars source_vars(const std::vector<SpecTensor>& tab, int L, int src) {
     return v;
 }
 
+// Everything of one source's backward pass behind the head: dz of the mask layer is in dzb; the retained tensors
+// are read, gA / gB / dzb / gskip / part / stat / sums are scratch, every gradient of the source's kernels, biases and betas is written.
+void network_backward(const TrainLayout& l, const wun_spec_train_config* tcfg, const float* params, float* grads, float* ws,
+                      double* sums, int src, const SrcVars& v, hipStream_t s) {
+    const int L = l.L, nif = l.nif;
+    const long long B = l.B;
+    float* gA = ws + l.gA; float* gB = ws + l.gB; float* dzb = ws + l.dzb;
+    float* mg = ws + l.stat;
+    // dz of batch-norm layer j from the gradient(s) behind its activation; dbeta on the way
+    auto bn_backward = [&](int j, const float* g1, const float* g2, const float* beta, float* dbeta, int act) {
+        const Geo g = l.bn(j);
+        ChanArgs a;
+        memset(&a, 0, sizeof(a));
+        a.x = g1; a.g2 = g2; a.z = ws + l.z[src][j]; a.mean = ws + l.mean[src][j]; a.var = ws + l.var[src][j]; a.beta = beta;
+        a.part = sums; a.n = g.n; a.C = g.C; a.act = act;
+        launch_chan_sums(CH_BNBWD, a, s);
+        launch_chan_finish(sums, g.n, g.C, 1.0 / (double)g.n, mg, mg + g.C, dbeta, s);
+        hipLaunchKernelGGL(bn_bwd_kernel, dim3(capped_grid(g.n * g.C)), dim3(WUN_STFT_BLOCK), 0, s, g1, g2, a.z, a.mean, a.var, beta,
+                           mg, mg + g.C, dzb, g.n * g.C, g.C, act);
+    };
+    for (int i = L - 1; i >= 0; --i) {                   // the transposed layers, the mask layer first; dz is in dzb
+        int Hi, Wi, c0, c1, cout;
+        l.up_in(i, &Hi, &Wi, &c0, &c1, &cout);
+        const bool drop = dropped(*tcfg, i);
+        const float* x0 = i ? ws + l.act[src][L - 1 - i] : ws + l.act[src][L - 1];
+        const float* x1 = i ? ws + l.act[src][L + i - 1] : nullptr;
+        const long long nin = (long long)B * Hi * Wi, nout = 4 * nin;
+        WgArgs wa;
+        wa.big = dzb; wa.part = ws + l.part; wa.nred = nin; wa.Hs = Hi; wa.Ws = Wi; wa.Cb = cout;
+        if (drop) { wa.s0 = ws + l.cat[src][i - 1]; wa.s1 = nullptr; wa.c0 = c0 + c1; wa.c1 = 0; }
+        else { wa.s0 = x0; wa.s1 = x1; wa.c0 = c0; wa.c1 = c1; }
+        launch_wgrad(wa, grads + v.uw[i], s);
+        channel_sum(dzb, nout, cout, sums, grads + v.ub[i], s);
+        // the data gradient: conv2d_s2(dz, W) with W [5][5][cout][cin] read as [5][5][cin' = cout][cout' = cin]
+        C2dArgs a;
+        a.x0 = dzb; a.x1 = nullptr; a.w = params + v.uw[i]; a.y = i ? gB : gA;
+        a.epi.bias = nullptr; a.epi.beta = nullptr; a.epi.mean = nullptr; a.epi.var = nullptr; a.epi.act = C2D_ACT_NONE;
+        a.H = 2 * Hi; a.W = 2 * Wi; a.c0 = cout; a.c1 = 0; a.Cout = c0 + c1;
+        a.M = nin;
+        launch_conv(a, s);
+        if (i) {
+            const long long Ec = nin * (c0 + c1);
+            hipLaunchKernelGGL(concat_split_kernel, dim3(capped_grid(Ec)), dim3(WUN_STFT_BLOCK), 0, s, gB,
+                               drop ? ws + l.dmask[src][i - 1] : nullptr, ws + l.gskip[L - 1 - i], gA, Ec, c0, c1);
+            bn_backward(L + i - 1, gA, nullptr, params + v.ubeta[i - 1], grads + v.ubeta[i - 1], C2D_ACT_RELU);
+        }
+    }
+    for (int i = L - 1; i >= 0; --i) {                   // the down path; the gradient from below is in gA
+        const Geo g = l.bn(i);
+        const int cin = i ? nif << (i - 1) : 1;
+        bn_backward(i, gA, i < L - 1 ? ws + l.gskip[i] : nullptr, params + v.dbeta[i], grads + v.dbeta[i], C2D_ACT_LRELU);
+        WgArgs wa;
+        wa.big = i ? ws + l.act[src][i - 1] : ws + l.a0; wa.part = ws + l.part; wa.nred = g.n; wa.Hs = g.H; wa.Ws = g.W; wa.Cb = cin;
+        wa.s0 = dzb; wa.s1 = nullptr; wa.c0 = g.C; wa.c1 = 0;
+        launch_wgrad(wa, grads + v.dw[i], s);
+        channel_sum(dzb, g.n, g.C, sums, grads + v.db[i], s);
+        if (i) {                                         // conv2d_transpose_s2(dz, W): W [5][5][cin][cout] read as [5][5][cout' = cin][cin' = cout]
+            C2dArgs a;
+            a.x0 = dzb; a.x1 = nullptr; a.w = params + v.dw[i]; a.y = gA;
+            a.epi.bias = nullptr; a.epi.beta = nullptr; a.epi.mean = nullptr; a.epi.var = nullptr; a.epi.act = C2D_ACT_NONE;
+            a.H = g.H; a.W = g.W; a.c0 = g.C; a.c1 = 0; a.Cout = cin;
+            a.M = g.n;
+            launch_transpose(a, s);
+        }
+    }
+}
+
+// the UPDATE_OPS of source src from the batch statistics in the workspace
+void launch_moving_averages(const TrainLayout& l, const wun_spec_train_config* tcfg, float* params, const float* workspace, int src,
+                            const SrcVars& sv, hipStream_t s) {
+    const int L = l.L;
+    MovingArgs a;
+    memset(&a, 0, sizeof(a));
+    int cmax = 1;
+    for (int j = 0; j < 2 * L - 1; ++j) {
+        const Geo g = l.bn(j);
+        a.pmean[j] = j < L ? sv.dmean[j] : sv.umean[j - L]; a.pvar[j] = j < L ? sv.dvar[j] : sv.uvar[j - L];
+        a.wmean[j] = l.mean[src][j]; a.wvar[j] = l.var[src][j]; a.n[j] = g.n; a.C[j] = g.C;
+        cmax = std::max(cmax, g.C);
+    }
+    hipLaunchKernelGGL(moving_average_kernel, dim3((unsigned)((cmax + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK), (unsigned)(2 * L - 1)),
+                       dim3(WUN_STFT_BLOCK), 0, s, a, params, workspace, 1.0f - tcfg->bn_decay);
+}
+
+// floats of the head's scratch: D [hop] (padded to 4 floats), then u [B T]
+long long head_scratch(long long B, long long T, int hop) { return (((long long)hop + 3) & ~3LL) + B * T; }
+
+// dz of one source's mask layer from the upstream gradient(s): D is in scratch (launch_steady_den) when dau is given
+int launch_head(const float* re, const float* im, const float* mag, const float* mask, const float* dmg, const float* dau,
+                long long B, long long T, long long F, int n_fft, int hop, const float* table_dev, float* dz, float* scratch,
+                hipStream_t s) {
+    const int K = n_fft / 2 + 1;
+    if (!dau) {
+        hipLaunchKernelGGL(spec_head_mags_kernel, dim3(capped_grid(B * F * K)), dim3(WUN_STFT_BLOCK), 0, s, dmg, mag, mask, dz, B * F * K, K);
+        return WUN_OK;
+    }
+    float* u = scratch + (((long long)hop + 3) & ~3LL);
+    launch_steady_divide(dau, scratch, u, B * T, T, hop, s);
+    SpecHeadArgs h;
+    memset(&h, 0, sizeof(h));
+    h.a.x[0] = u; h.a.M[0] = B * F; h.a.table = table_dev;
+    h.a.T = T; h.a.nb = F; h.a.f0 = 0; h.a.fstride = F; h.a.foff = 0;
+    h.a.C = 1; h.a.n_fft = n_fft; h.a.hop = hop; h.a.lead = 0; h.a.K = K;
+    h.xre = re; h.xim = im; h.mag = mag; h.mask = mask; h.dmags = dmg; h.dz = dz;
+    h.c_edge = 1.0f / (float)n_fft; h.c_mid = 2.0f / (float)n_fft;
+    return fft_launch_spec_head(h, s);
+}
+
 }  // namespace
 
 // ---- the C ABI ----
@@ -708,7 +836,7 @@ extern "C" int wun_spec_loss_backward(const wun_spec_config* cfg, const wun_spec
     if (F < 0) return (int)F;
     TrainLayout l;
     const int64_t total = train_layout(*cfg, B, F, &l);
-    const int L = l.L, S = l.S, K = l.K, nif = l.nif;
+    const int L = l.L, S = l.S, K = l.K;
     const int64_t np = wun_spec_param_floats(cfg);
     if (overlap(workspace, total, targets, (int64_t)S * B * T) || overlap(workspace, total, params, np) ||
         overlap(workspace, total, grads, np) || overlap(workspace, total, losses, 1 + S) || overlap(grads, np, params, np) ||
@@ -726,70 +854,13 @@ extern "C" int wun_spec_loss_backward(const wun_spec_config* cfg, const wun_spec
     if (hipMemsetAsync(grads, 0, (size_t)np * sizeof(float), s) != hipSuccess)          // the moving statistics keep 0
         return fail(WUN_ERR_HIP, std::string(who) + ": memset failed");
     const float cm = (float)(1.0 / ((double)S * (double)E));
-    float* gA = ws + l.gA; float* gB = ws + l.gB; float* dzb = ws + l.dzb;
-    float* mg = ws + l.stat;
+    float* dzb = ws + l.dzb;
 
     for (int src = 0; src < S; ++src) {
         const SrcVars v = source_vars(tab, L, src);
         hipLaunchKernelGGL(spec_loss_kernel, dim3((unsigned)lblocks), dim3(WUN_STFT_BLOCK), 0, s, ws + l.R + (long long)src * E,
                            ws + l.mag, ws + l.mask[src], dzb, f64 + (long long)src * lblocks, E, K, cm);
-        // dz of batch-norm layer j from the gradient(s) behind its activation; dbeta on the way
-        auto bn_backward = [&](int j, const float* g1, const float* g2, const float* beta, float* dbeta, int act) {
-            const Geo g = l.bn(j);
-            ChanArgs a;
-            memset(&a, 0, sizeof(a));
-            a.x = g1; a.g2 = g2; a.z = ws + l.z[src][j]; a.mean = ws + l.mean[src][j]; a.var = ws + l.var[src][j]; a.beta = beta;
-            a.part = sums; a.n = g.n; a.C = g.C; a.act = act;
-            launch_chan_sums(CH_BNBWD, a, s);
-            launch_chan_finish(sums, g.n, g.C, 1.0 / (double)g.n, mg, mg + g.C, dbeta, s);
-            hipLaunchKernelGGL(bn_bwd_kernel, dim3(capped_grid(g.n * g.C)), dim3(WUN_STFT_BLOCK), 0, s, g1, g2, a.z, a.mean, a.var, beta,
-                               mg, mg + g.C, dzb, g.n * g.C, g.C, act);
-        };
-        for (int i = L - 1; i >= 0; --i) {                   // the transposed layers, the mask layer first; dz is in dzb
-            int Hi, Wi, c0, c1, cout;
-            l.up_in(i, &Hi, &Wi, &c0, &c1, &cout);
-            const bool drop = dropped(*tcfg, i);
-            const float* x0 = i ? ws + l.act[src][L - 1 - i] : ws + l.act[src][L - 1];
-            const float* x1 = i ? ws + l.act[src][L + i - 1] : nullptr;
-            const long long nin = (long long)B * Hi * Wi, nout = 4 * nin;
-            WgArgs wa;
-            wa.big = dzb; wa.part = ws + l.part; wa.nred = nin; wa.Hs = Hi; wa.Ws = Wi; wa.Cb = cout;
-            if (drop) { wa.s0 = ws + l.cat[src][i - 1]; wa.s1 = nullptr; wa.c0 = c0 + c1; wa.c1 = 0; }
-            else { wa.s0 = x0; wa.s1 = x1; wa.c0 = c0; wa.c1 = c1; }
-            launch_wgrad(wa, grads + v.uw[i], s);
-            channel_sum(dzb, nout, cout, sums, grads + v.ub[i], s);
-            // the data gradient: conv2d_s2(dz, W) with W [5][5][cout][cin] read as [5][5][cin' = cout][cout' = cin]
-            C2dArgs a;
-            a.x0 = dzb; a.x1 = nullptr; a.w = params + v.uw[i]; a.y = i ? gB : gA;
-            a.epi.bias = nullptr; a.epi.beta = nullptr; a.epi.mean = nullptr; a.epi.var = nullptr; a.epi.act = C2D_ACT_NONE;
-            a.H = 2 * Hi; a.W = 2 * Wi; a.c0 = cout; a.c1 = 0; a.Cout = c0 + c1;
-            a.M = nin;
-            launch_conv(a, s);
-            if (i) {
-                const long long Ec = nin * (c0 + c1);
-                hipLaunchKernelGGL(concat_split_kernel, dim3(capped_grid(Ec)), dim3(WUN_STFT_BLOCK), 0, s, gB,
-                                   drop ? ws + l.dmask[src][i - 1] : nullptr, ws + l.gskip[L - 1 - i], gA, Ec, c0, c1);
-                bn_backward(L + i - 1, gA, nullptr, params + v.ubeta[i - 1], grads + v.ubeta[i - 1], C2D_ACT_RELU);
-            }
-        }
-        for (int i = L - 1; i >= 0; --i) {                   // the down path; the gradient from below is in gA
-            const Geo g = l.bn(i);
-            const int cin = i ? nif << (i - 1) : 1;
-            bn_backward(i, gA, i < L - 1 ? ws + l.gskip[i] : nullptr, params + v.dbeta[i], grads + v.dbeta[i], C2D_ACT_LRELU);
-            WgArgs wa;
-            wa.big = i ? ws + l.act[src][i - 1] : ws + l.a0; wa.part = ws + l.part; wa.nred = g.n; wa.Hs = g.H; wa.Ws = g.W; wa.Cb = cin;
-            wa.s0 = dzb; wa.s1 = nullptr; wa.c0 = g.C; wa.c1 = 0;
-            launch_wgrad(wa, grads + v.dw[i], s);
-            channel_sum(dzb, g.n, g.C, sums, grads + v.db[i], s);
-            if (i) {                                         // conv2d_transpose_s2(dz, W): W [5][5][cin][cout] read as [5][5][cout' = cin][cin' = cout]
-                C2dArgs a;
-                a.x0 = dzb; a.x1 = nullptr; a.w = params + v.dw[i]; a.y = gA;
-                a.epi.bias = nullptr; a.epi.beta = nullptr; a.epi.mean = nullptr; a.epi.var = nullptr; a.epi.act = C2D_ACT_NONE;
-                a.H = g.H; a.W = g.W; a.c0 = g.C; a.c1 = 0; a.Cout = cin;
-                a.M = g.n;
-                launch_transpose(a, s);
-            }
-        }
+        network_backward(l, tcfg, params, grads, ws, sums, src, v, s);
     }
     hipLaunchKernelGGL(spec_loss_finish_kernel, dim3(1), dim3(WUN_STFT_BLOCK), 0, s, f64, lblocks, S, 1.0 / (double)E, losses);
     return launch_status(who);
@@ -829,22 +900,162 @@ extern "C" int wun_spec_adam_step(const wun_spec_config* cfg, const wun_spec_tra
         run(sv.uw[L - 1], sv.ub[L - 1] + 1);
         if (launch_adam_ranges(params, grads, m, v, r, lr_t, beta1, beta2, eps, grad_scale, s) != hipSuccess)
             return fail(WUN_ERR_HIP, std::string(who) + ": launch failed");
-        MovingArgs a;
-        memset(&a, 0, sizeof(a));
-        int cmax = 1;
-        for (int j = 0; j < 2 * L - 1; ++j) {
-            const Geo g = l.bn(j);
-            a.pmean[j] = j < L ? sv.dmean[j] : sv.umean[j - L]; a.pvar[j] = j < L ? sv.dvar[j] : sv.uvar[j - L];
-            a.wmean[j] = l.mean[src][j]; a.wvar[j] = l.var[src][j]; a.n[j] = g.n; a.C[j] = g.C;
-            cmax = std::max(cmax, g.C);
-        }
-        hipLaunchKernelGGL(moving_average_kernel, dim3((unsigned)((cmax + WUN_STFT_BLOCK - 1) / WUN_STFT_BLOCK), (unsigned)(2 * L - 1)),
-                           dim3(WUN_STFT_BLOCK), 0, s, a, params, workspace, 1.0f - tcfg->bn_decay);
+        launch_moving_averages(l, tcfg, params, workspace, src, sv, s);
     }
     return launch_status(who);
 }
 
+// ---- the backward pass from any upstream gradient, the audio of a training forward ----
+namespace {
+// (cfg, tcfg, B, T) of the entries below, and the resolution as wun_istft_tf_fft takes it: -> F
+int64_t check_backward_shape(const char* who, const wun_spec_config* cfg, const wun_spec_train_config* tcfg, int32_t B, int64_t T) {
+    int rc;
+    if ((rc = check_train_config(who, tcfg))) return rc;
+    const int64_t F = check_train_shape(who, cfg, B, T);
+    if (F < 0) return F;
+    const int64_t is = wun_istft_tf_fft_scratch_floats(cfg->num_sources, B, T, 1, cfg->n_fft, cfg->hop, F);
+    return is < 0 ? is : F;
+}
+}  // namespace
+
+extern "C" int64_t wun_spec_train_audio_scratch_floats(const wun_spec_config* cfg, int32_t B, int64_t T) {
+    const int64_t F = check_train_shape("wun_spec_train_audio_scratch_floats", cfg, B, T);
+    if (F < 0) return F;
+    const int64_t is = wun_istft_tf_fft_scratch_floats(cfg->num_sources, B, T, 1, cfg->n_fft, cfg->hop, F);
+    if (is < 0) return is;
+    const int64_t E = (int64_t)cfg->num_sources * B * F * (cfg->n_fft / 2 + 1);
+    return 2 * ((E + 3) & ~(int64_t)3) + is;
+}
+
+extern "C" int wun_spec_train_audio(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, int32_t B, int64_t T,
+                                    const float* table_dev, float* audio, const float* workspace, float* scratch, void* stream) {
+    const char* who = "wun_spec_train_audio";
+    if (!cfg || !tcfg || !table_dev || !audio || !workspace || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    const int64_t F = check_backward_shape(who, cfg, tcfg, B, T);
+    if (F < 0) return (int)F;
+    TrainLayout l;
+    const int64_t total = train_layout(*cfg, B, F, &l);
+    const int64_t ns = wun_spec_train_audio_scratch_floats(cfg, B, T);
+    const int S = l.S, K = l.K;
+    if (overlap(workspace, total, audio, (int64_t)S * B * T) || overlap(workspace, total, scratch, ns) ||
+        overlap(scratch, ns, audio, (int64_t)S * B * T))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": the workspace, the scratch and the audio overlap");
+    hipStream_t s = (hipStream_t)stream;
+    const long long E = (long long)B * F * K, SE = ((long long)S * E + 3) & ~3LL;
+    float* yre = scratch; float* yim = scratch + SE;
+    for (int src = 0; src < S; ++src)
+        launch_spec_mask(workspace + l.mask[src], workspace + l.mag, workspace + l.re, workspace + l.im, nullptr, yre + src * E,
+                         yim + src * E, E, K, s);
+    int rc;
+    if ((rc = wun_istft_tf_fft(yre, yim, S, B, T, 1, cfg->n_fft, cfg->hop, F, table_dev, audio, scratch + 2 * SE, stream))) return rc;
+    return launch_status(who);
+}
+
+extern "C" int64_t wun_spec_backward_scratch_floats(const wun_spec_config* cfg, int32_t B, int64_t T) {
+    const char* who = "wun_spec_backward_scratch_floats";
+    const int64_t F = check_train_shape(who, cfg, B, T);
+    if (F < 0) return F;
+    const int64_t is = wun_istft_tf_fft_scratch_floats(cfg->num_sources, B, T, 1, cfg->n_fft, cfg->hop, F);
+    if (is < 0) return is;
+    return head_scratch(B, T, cfg->hop);
+}
+
+extern "C" int wun_spec_backward(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, const float* params,
+                                 const float* d_mags, const float* d_audio, int32_t B, int64_t T, const float* table_dev,
+                                 float* grads, float* workspace, float* scratch, void* stream) {
+    const char* who = "wun_spec_backward";
+    if (!cfg || !tcfg || !params || !table_dev || !grads || !workspace || !scratch)
+        return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    if (!d_mags && !d_audio) return fail(WUN_ERR_INVALID, std::string(who) + ": d_mags and d_audio are both null");
+    const int64_t F = check_backward_shape(who, cfg, tcfg, B, T);
+    if (F < 0) return (int)F;
+    TrainLayout l;
+    const int64_t total = train_layout(*cfg, B, F, &l);
+    const int L = l.L, S = l.S, K = l.K;
+    const int64_t np = wun_spec_param_floats(cfg), ns = head_scratch(B, T, cfg->hop);
+    const int64_t nm = (int64_t)S * B * F * K, na = (int64_t)S * B * T;
+    const void* bufs[5] = {workspace, scratch, grads, params, nullptr};
+    const int64_t lens[4] = {total, ns, np, np};
+    for (int i = 0; i < 3; ++i) {                            // the workspace, the scratch and the gradients against everything else
+        for (int j = i + 1; j < 4; ++j)
+            if (overlap(bufs[i], lens[i], bufs[j], lens[j])) return fail(WUN_ERR_INVALID, std::string(who) + ": two buffers overlap");
+        if ((d_mags && overlap(bufs[i], lens[i], d_mags, nm)) || (d_audio && overlap(bufs[i], lens[i], d_audio, na)))
+            return fail(WUN_ERR_INVALID, std::string(who) + ": an upstream gradient overlaps the workspace, the scratch or the gradients");
+    }
+
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = workspace;
+    double* sums = align8(ws + l.f64) + l.f64_sums;
+    const std::vector<SpecTensor> tab = spec_tensors(*cfg);
+    const long long E = (long long)B * F * K;
+    if (hipMemsetAsync(grads, 0, (size_t)np * sizeof(float), s) != hipSuccess)          // the moving statistics keep 0
+        return fail(WUN_ERR_HIP, std::string(who) + ": memset failed");
+    if (d_audio) launch_steady_den(scratch, cfg->n_fft, cfg->hop, s);
+    int rc;
+    for (int src = 0; src < S; ++src) {
+        const SrcVars v = source_vars(tab, L, src);
+        if ((rc = launch_head(ws + l.re, ws + l.im, ws + l.mag, ws + l.mask[src], d_mags ? d_mags + (long long)src * E : nullptr,
+                              d_audio ? d_audio + (long long)src * B * T : nullptr, B, T, F, cfg->n_fft, cfg->hop, table_dev,
+                              ws + l.dzb, scratch, s)))
+            return rc;
+        network_backward(l, tcfg, params, grads, ws, sums, src, v, s);
+    }
+    return launch_status(who);
+}
+
+extern "C" int wun_spec_update_moving_averages(const wun_spec_config* cfg, const wun_spec_train_config* tcfg, float* params,
+                                               const float* workspace, int32_t B, int64_t T, void* stream) {
+    const char* who = "wun_spec_update_moving_averages";
+    if (!cfg || !tcfg || !params || !workspace) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    int rc;
+    if ((rc = check_train_config(who, tcfg))) return rc;
+    const int64_t F = check_train_shape(who, cfg, B, T);
+    if (F < 0) return (int)F;
+    TrainLayout l;
+    const int64_t total = train_layout(*cfg, B, F, &l);
+    if (overlap(workspace, total, params, wun_spec_param_floats(cfg)))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": the workspace overlaps the parameters");
+    const std::vector<SpecTensor> tab = spec_tensors(*cfg);
+    for (int src = 0; src < l.S; ++src)
+        launch_moving_averages(l, tcfg, params, workspace, src, source_vars(tab, l.L, src), (hipStream_t)stream);
+    return launch_status(who);
+}
+
 // ---- single operators ----
+extern "C" int64_t wun_op_spec_head_backward_scratch(int32_t B, int64_t T, int32_t n_fft, int32_t hop) {
+    const char* who = "wun_op_spec_head_backward_scratch";
+    if (B < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": B < 1");
+    const int64_t F = wun_fft_frames(T, n_fft, hop);          // the n_fft list, hop in 1..n_fft, T >= n_fft
+    if (F < 0) return F;
+    if (T != (F - 1) * hop + n_fft) return fail(WUN_ERR_INVALID, std::string(who) + ": T is not (F - 1) hop + n_fft");
+    if ((int64_t)B * F > ((int64_t)1 << 28) / (n_fft / 2)) return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": more than 2^28 bins in a batch");
+    const int64_t is = wun_istft_tf_fft_scratch_floats(1, B, T, 1, n_fft, hop, F);      // the resolution as wun_istft_tf_fft takes it
+    if (is < 0) return is;
+    return head_scratch(B, T, hop);
+}
+
+extern "C" int wun_op_spec_head_backward(const float* re, const float* im, const float* mag, const float* mask, const float* d_mags,
+                                         const float* d_audio, int32_t B, int64_t T, int32_t n_fft, int32_t hop,
+                                         const float* table_dev, float* dz, float* scratch, void* stream) {
+    const char* who = "wun_op_spec_head_backward";
+    if (!re || !im || !mag || !mask || !table_dev || !dz || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    if (!d_mags && !d_audio) return fail(WUN_ERR_INVALID, std::string(who) + ": d_mags and d_audio are both null");
+    const int64_t ns = wun_op_spec_head_backward_scratch(B, T, n_fft, hop);
+    if (ns < 0) return (int)ns;
+    const int64_t F = 1 + (T - n_fft) / hop, K = n_fft / 2 + 1, E = (int64_t)B * F * K, Ez = (int64_t)B * F * (K - 1);
+    const float* in[6] = {re, im, mag, mask, d_mags, d_audio};
+    const int64_t len[6] = {E, E, E, Ez, E, (int64_t)B * T};
+    for (int i = 0; i < 6; ++i)
+        if (in[i] && (overlap(scratch, ns, in[i], len[i]) || overlap(dz, Ez, in[i], len[i])))
+            return fail(WUN_ERR_INVALID, std::string(who) + ": the scratch or dz overlaps an operand");
+    if (overlap(scratch, ns, dz, Ez)) return fail(WUN_ERR_INVALID, std::string(who) + ": the scratch overlaps dz");
+    hipStream_t s = (hipStream_t)stream;
+    if (d_audio) launch_steady_den(scratch, n_fft, hop, s);
+    int rc;
+    if ((rc = launch_head(re, im, mag, mask, d_mags, d_audio, B, T, F, n_fft, hop, table_dev, dz, scratch, s))) return rc;
+    return launch_status(who);
+}
+
 extern "C" int64_t wun_op_conv2d_s2_wgrad_scratch(int B, int H, int W, int cin, int cout) {
     const char* who = "wun_op_conv2d_s2_wgrad_scratch";
     if ((H | W) & 1) return fail(WUN_ERR_INVALID, std::string(who) + ": H and W must be even");

@@ -36,6 +36,20 @@ struct StftMagArgs {
     float* mag[2];
 };
 
+// The forward transform with the spectrogram U-Net's mask-gradient epilogue: a.x[0] is u = d_audio / D, G = STFT(u)
+// stays in registers, and for every bin k < K - 1 of frame row bf
+//   ga = c_k fmaf(xre, Re G, xim Im G)  (c_k = c_edge at k = 0, c_mid elsewhere),  dmask = dmags ? fmaf(dmags, mag, ga) : ga,
+//   dz[bf (K - 1) + k] = dmask * (mask * (1 - mask)).
+// a.re / a.im are not read; bin K - 1 stores nothing.
+struct SpecHeadArgs {
+    StftCfwdArgs a;
+    const float* xre; const float* xim; const float* mag;        // [B F][K]: the mix's spectrum and its magnitude
+    const float* mask;                                           // [B F][K - 1]
+    const float* dmags;                                          // [B F][K] or null
+    float* dz;                                                   // [B F][K - 1]
+    float c_edge, c_mid;                                         // 1 / n_fft, 2 / n_fft
+};
+
 // wun_fft.hip: stft_fft_kernel / istft_fft_kernel of a.n_fft (a power of two in 64..8192) on stream s.  WUN_OK, or
 // WUN_ERR_UNSUPPORTED (wun_last_error() set, nothing launched) for an n_fft without a kernel.
 //   magnitude   the forward body with StftMagArgs' epilogue (the spectral loss and wun_stft_magnitude_fft)
@@ -45,5 +59,11 @@ int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s);
 int fft_launch_magnitude(const StftMagArgs& a, int signals, hipStream_t s);
 int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s);
 int fft_launch_adjoint(const IstftGemmArgs& g, hipStream_t s);
+//   spec_head   the forward body on a.x[0] with SpecHeadArgs' epilogue, one signal
+int fft_launch_spec_head(const SpecHeadArgs& a, hipStream_t s);
+// D[p] = (float) sum_i w^2[p + i hop] over p + i hop < n_fft (float64, i ascending: istft_ola_kernel<true>'s normaliser), p < hop
+void launch_steady_den(float* D, int n_fft, int hop, hipStream_t s);
+// u[e] = g[e] / D[(e mod T) mod hop] for the N = rows T samples of [rows][T]
+void launch_steady_divide(const float* g, const float* D, float* u, long long N, long long T, int hop, hipStream_t s);
 
 }  // namespace wun

@@ -2,7 +2,8 @@
 // wun_istft_fft and the *_fft filters).  Same definitions and layouts as stft_cfwd_kernel / istft_gemm_kernel of
 // wun_postfilter.hip, whose host code launches these through wun_fft.h; O(n log n) per frame instead of O(n^2).  The spectral
 // loss's two frame transforms (wun_spectral_loss_fft and its kin) are the same two bodies: the forward one with
-// the magnitude as its epilogue, the inverse one as the unscaled adjoint.
+// the magnitude as its epilogue, the inverse one as the unscaled adjoint.  The spectrogram U-Net's backward from an audio gradient
+// (wun_spec_backward) is the forward body once more, on d_audio / D, with the mask gradient as its epilogue.
 //
 //   real transform   a frame of n_fft real samples is one complex FFT of M = n_fft / 2 points, z[m] = y[2m] + i y[2m+1], and a
 //                    split step:  E = (Z[k] + conj Z[M-k]) / 2,  O = (Z[k] - conj Z[M-k]) / 2i,  X[k] = E + W_N^k O,  k = 0..M
@@ -186,6 +187,45 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void stft_fft_mag_kernel(StftMagArgs
     });
 }
 
+// The same grid and body on u = d_audio / D with the mask gradient of the spectrogram U-Net as its epilogue (SpecHeadArgs,
+// DESIGN.md 5.20): G = STFT(u) is consumed in registers; the epilogue adds loads of X, M, the mask and d_mags at the lane's own
+// bin, no LDS and no barrier.
+template <int LOGM>
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void spec_head_fft_kernel(SpecHeadArgs p) {
+    const int K = p.a.K;
+    fft_fwd_frames<LOGM>(p.a, [&](int, long long e, float re, float im) {
+        const long long bf = e / K;
+        const int k = (int)(e - bf * K);
+        if (k == K - 1) return;                              // the dropped bin: no gradient
+        const float ga = (k == 0 ? p.c_edge : p.c_mid) * fmaf(p.xre[e], re, p.xim[e] * im);
+        const float dm = p.dmags != nullptr ? fmaf(p.dmags[e], p.mag[e], ga) : ga;
+        const float mk = p.mask[bf * (K - 1) + k];
+        p.dz[bf * (K - 1) + k] = dm * (mk * (1.0f - mk));
+    });
+}
+
+// D[p] of wun_istft_tf: window_sq_kernel's squares (cospi, float64) summed over the places p + i hop of a frame, i ascending,
+// rounded once -- the float istft_ola_kernel<true> divides by
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void steady_den_kernel(float* __restrict__ D, int n_fft, int hop) {
+    const int p = blockIdx.x * WUN_FFT_BLOCK + threadIdx.x;
+    if (p >= hop) return;
+    double ws = 0.0;
+    for (int n = p; n < n_fft; n += hop) {
+        const double w = 0.5 - 0.5 * cospi(2.0 * (double)n / (double)n_fft);
+        ws += w * w;
+    }
+    D[p] = (float)ws;
+}
+
+// one lane per sample (grid-stride, one writer per float): u = g / D[t mod hop]
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void steady_divide_kernel(const float* __restrict__ g, const float* __restrict__ D,
+                                                                     float* __restrict__ u, long long N, long long T, int hop) {
+    for (long long e = (long long)blockIdx.x * WUN_FFT_BLOCK + threadIdx.x; e < N; e += (long long)gridDim.x * WUN_FFT_BLOCK) {
+        const long long t = e % T;
+        u[e] = g[e] / D[t % hop];
+    }
+}
+
 // grid: x = group of FPW frame rows of IstftGemmArgs.  frames[m][n] = w[n] irfft(Re + i Im)[n]; Im of the bins 0 and M is
 // never read.  ADJ: the unscaled adjoint of the forward transform instead (stft_bwd_kernel's definition, every bin k = 0..M
 // counted ONCE): frames[m][n] = w[n] sum_k re[k] cos(2 pi n k / N) - im[k] sin(2 pi n k / N).  That is the inverse of the spectrum
@@ -273,6 +313,23 @@ int fft_launch_magnitude(const StftMagArgs& a, int signals, hipStream_t s) {
         constexpr int LM = decltype(L)::value;
         hipLaunchKernelGGL(stft_fft_mag_kernel<LM>, fwd_grid<LM>(a.a, signals), dim3(WUN_FFT_BLOCK), 0, s, a);
     });
+}
+
+int fft_launch_spec_head(const SpecHeadArgs& a, hipStream_t s) {
+    return fft_dispatch("fft_launch_spec_head", a.a.n_fft, [&](auto L) {
+        constexpr int LM = decltype(L)::value;
+        hipLaunchKernelGGL(spec_head_fft_kernel<LM>, fwd_grid<LM>(a.a, 1), dim3(WUN_FFT_BLOCK), 0, s, a);
+    });
+}
+
+void launch_steady_den(float* D, int n_fft, int hop, hipStream_t s) {
+    hipLaunchKernelGGL(steady_den_kernel, dim3((unsigned)((hop + WUN_FFT_BLOCK - 1) / WUN_FFT_BLOCK)), dim3(WUN_FFT_BLOCK), 0, s, D, n_fft, hop);
+}
+
+void launch_steady_divide(const float* g, const float* D, float* u, long long N, long long T, int hop, hipStream_t s) {
+    long long grid = (N + WUN_FFT_BLOCK - 1) / WUN_FFT_BLOCK;
+    if (grid > (1 << 16)) grid = 1 << 16;
+    hipLaunchKernelGGL(steady_divide_kernel, dim3((unsigned)(grid < 1 ? 1 : grid)), dim3(WUN_FFT_BLOCK), 0, s, g, D, u, N, T, hop);
 }
 
 int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s) {

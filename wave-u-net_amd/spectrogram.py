@@ -18,8 +18,15 @@ Training on the magnitude objective (raw_audio_loss=False: Jansson's L1, Trainin
     loss = sep.loss_and_gradients(targets)                         # targets {source: [B, T, 1]} or stacked [S, B, T, 1] audio
     sep.adam_step(lr)                                              # TF-Adam + the batch norms' moving averages
 
-Not built (NotImplementedError): the audio output at training=True (the raw-audio objective), stereo, any source count but two
-(the reference asserts both, :24-25) and a bf16 mode.
+Any other loss, on magnitudes, audio or both (wun_spec_backward, wun_spec_train_audio):
+
+    audio = sep.audio_output()                                     # {source: [B, T, 1]} of that training forward
+    sep.backward(d_mags=..., d_audio=...)                          # dL/d mags [S, B, F, K] and / or dL/d audio [S, B, T, 1] -> sep.grads
+    sep.adam_step(lr)                                              # or sep.update_moving_averages() beside another optimizer
+    net = sep.module("audio")                                      # SpecUNet, a torch.nn.Module: net(mix) under torch.autograd
+
+Not built (NotImplementedError): get_output's own audio at training=True (ask audio_output() for it), the gradient with respect
+to the mix, stereo, any source count but two (the reference asserts both, :24-25) and a bf16 mode.
 model_config["spec_frame_len"] / ["spec_hop"] (extension keys, defaults 1024 / 768) let tests run small geometries;
 ["spec_dropout"] (0.5), ["spec_bn_decay"] (0.999) and ["spec_dropout_seed"] (the separator's seed) are the training step's.
 """
@@ -28,6 +35,7 @@ import math
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib, spectral
 from .config import finalize
@@ -83,6 +91,8 @@ class UnetSpectrogramSeparator(object):
         self._tws = {}                   # (B, T) -> training workspace
         self._last_train = None          # (B, T) of the last training forward
         self._outs = {}                  # (B, T, return_spectrogram) -> output buffer
+        self._tws_gen = {}               # (B, T) -> training forwards that wrote the training workspace
+        self._scr = {}                   # (kind, B, T) -> scratch of audio_output / backward
 
     # ------------------------------------------------------------------ shapes
     def get_padding(self, shape):
@@ -195,6 +205,7 @@ class UnetSpectrogramSeparator(object):
                     spectral._fft_table(self.frame_len, dev).data_ptr(), self.global_step, out.data_ptr(),
                     self._train_workspace(B, T).data_ptr(), self._stream()))
             self._last_train = (B, T)
+            self._tws_gen[(B, T)] = self._tws_gen.get((B, T), 0) + 1
             return {name: out[i] for i, name in enumerate(self.source_names)}
         with torch.cuda.device(dev):
             _lib.check(self._lib.wun_spec_forward(
@@ -250,6 +261,81 @@ class UnetSpectrogramSeparator(object):
                 self.adam_v.data_ptr(), self._train_workspace(B, T).data_ptr(), B, T, self.global_step, lr, beta1, beta2, eps,
                 grad_scale, self._stream()))
 
+    # ------------------------------------------------------------------ any loss
+    def _scratch(self, kind, B, T):
+        if (kind, B, T) not in self._scr:
+            query = self._lib.wun_spec_train_audio_scratch_floats if kind == "audio" else self._lib.wun_spec_backward_scratch_floats
+            n = int(query(C.byref(self._scfg), B, T))
+            if n < 0:
+                _lib.check(n)
+            self._scr[(kind, B, T)] = torch.empty(n, dtype=torch.float32, device=self._dev())
+        return self._scr[(kind, B, T)]
+
+    def _train_audio(self, B, T, out):
+        dev = self._dev()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.wun_spec_train_audio(
+                C.byref(self._scfg), C.byref(self._tcfg), B, T, spectral._fft_table(self.frame_len, dev).data_ptr(), out.data_ptr(),
+                self._train_workspace(B, T).data_ptr(), self._scratch("audio", B, T).data_ptr(), self._stream()))
+        return out
+
+    def audio_output(self):
+        """{source: [B, T, 1]} audio of the last get_output(x, True, return_spectrogram=True): ISTFT_tf(mask X) from what that
+        forward retained (a fresh tensor per call; the workspace and the variables are left as they are)."""
+        if self._last_train is None:
+            raise RuntimeError("audio_output needs a get_output(x, True, return_spectrogram=True) first")
+        B, T = self._last_train
+        out = self._train_audio(B, T, torch.empty((len(self.source_names), B, T, 1), dtype=torch.float32, device=self._dev()))
+        return {name: out[i] for i, name in enumerate(self.source_names)}
+
+    def _upstream(self, g, what, shape):
+        if g is None:
+            return None
+        if isinstance(g, dict):
+            g = torch.stack([torch.as_tensor(g[n]) for n in self.source_names])
+        g = torch.as_tensor(g).to(device=self._dev(), dtype=torch.float32).contiguous()
+        if tuple(g.shape) != shape:
+            raise ValueError("%s must be %s, got %s" % (what, list(shape), tuple(g.shape)))
+        return g
+
+    def _backward_into(self, params, grads, d_mags, d_audio, B, T):
+        dev = self._dev()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.wun_spec_backward(
+                C.byref(self._scfg), C.byref(self._tcfg), params.data_ptr(), None if d_mags is None else d_mags.data_ptr(),
+                None if d_audio is None else d_audio.data_ptr(), B, T, spectral._fft_table(self.frame_len, dev).data_ptr(),
+                grads.data_ptr(), self._train_workspace(B, T).data_ptr(), self._scratch("backward", B, T).data_ptr(), self._stream()))
+
+    def backward(self, d_mags=None, d_audio=None):
+        """The gradients of any loss on the last training forward's outputs into self.grads: d_mags = dL/d mags
+        ({source: [B, F, K]} or stacked [S, B, F, K]), d_audio = dL/d audio ({source: [B, T, 1]} or [S, B, T, 1]), either or both.
+        Afterwards gradients() and adam_step(lr) behave as after loss_and_gradients."""
+        if self._last_train is None:
+            raise RuntimeError("backward needs a get_output(x, True, return_spectrogram=True) first")
+        if d_mags is None and d_audio is None:
+            raise ValueError("backward needs d_mags, d_audio or both")
+        B, T = self._last_train
+        S, K = len(self.source_names), self.frame_len // 2 + 1
+        d_mags = self._upstream(d_mags, "d_mags", (S, B, self.frames(T), K))
+        d_audio = self._upstream(d_audio, "d_audio", (S, B, T, 1))
+        self._backward_into(self.params, self.grads, d_mags, d_audio, B, T)
+
+    def update_moving_averages(self):
+        """The batch norms' UPDATE_OPS alone (Training.py:74-75), from the last training forward: what adam_step does after its
+        update, for a step whose optimizer is not adam_step.  global_step is left alone."""
+        if self._last_train is None:
+            raise RuntimeError("update_moving_averages needs a training forward first")
+        B, T = self._last_train
+        with torch.cuda.device(self._dev()):
+            _lib.check(self._lib.wun_spec_update_moving_averages(
+                C.byref(self._scfg), C.byref(self._tcfg), self.params.data_ptr(), self._train_workspace(B, T).data_ptr(), B, T,
+                self._stream()))
+
+    def module(self, output="audio"):
+        """This separator as a torch.nn.Module (SpecUNet) whose forward gives "audio" [S, B, T, 1], "mags" [S, B, F, K] or
+        "both" (audio, mags)."""
+        return SpecUNet(self, output)
+
     def activation(self, kind, source, layer):
         """A tensor the last training forward retained (wun_spec_train_tensor), as a view of the workspace.  kind: "z" (pre-norm),
         "mean", "var" (batch statistics), "act" (post-activation; layer 2L-1: the mask [B, F, K-1]) or "dropout" (layer = up level;
@@ -285,3 +371,106 @@ def make_separator(model_config, device=None):
     if model_config["network"] == "unet_spectrogram":
         return UnetSpectrogramSeparator(model_config, device=device)
     raise NotImplementedError(model_config["network"])
+
+
+# ---------------------------------------------------------------------- torch.autograd
+class _TrainOutput(torch.autograd.Function):
+    """(audio [S, B, T, 1] and / or mags [S, B, F, K]) of a training forward with the parameters in `arena`; the backward pass is
+    wun_spec_backward from the gradients of whichever outputs the loss used."""
+
+    @staticmethod
+    def forward(ctx, arena, mix, sep, output, step):
+        B, T = int(mix.shape[0]), int(mix.shape[1])
+        F, S, K = sep.frames(T), len(sep.source_names), sep.frame_len // 2 + 1
+        dev = arena.device
+        mags = torch.empty((S, B, F, K), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(sep._lib.wun_spec_train_forward(
+                C.byref(sep._scfg), C.byref(sep._tcfg), arena.data_ptr(), mix.data_ptr(), B, T,
+                spectral._fft_table(sep.frame_len, dev).data_ptr(), int(step), mags.data_ptr(), sep._train_workspace(B, T).data_ptr(),
+                sep._stream()))
+        sep._last_train = (B, T)
+        sep._tws_gen[(B, T)] = sep._tws_gen.get((B, T), 0) + 1
+        ctx.sep, ctx.key, ctx.gen, ctx.output = sep, (B, T), sep._tws_gen[(B, T)], output
+        ctx.save_for_backward(arena)
+        ctx.set_materialize_grads(False)             # an output the loss did not use gives None: that head is not run
+        if output == "mags":
+            return mags
+        audio = sep._train_audio(B, T, torch.empty((S, B, T, 1), dtype=torch.float32, device=dev))
+        return audio if output == "audio" else (audio, mags)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *d_outputs):
+        (arena,) = ctx.saved_tensors                 # (torch's version check: the arena must not change before backward)
+        sep, key = ctx.sep, ctx.key
+        if sep._tws_gen.get(key) != ctx.gen:
+            raise RuntimeError("wave_u_net_amd: another training forward of shape %s ran on the shared workspace after this "
+                               "one; run backward before the next forward of the same shape" % (key,))
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        d_audio = d_outputs[0] if ctx.output != "mags" else None
+        d_mags = d_outputs[-1] if ctx.output != "audio" else None
+        d_audio, d_mags = (None if g is None else g.to(torch.float32).contiguous() for g in (d_audio, d_mags))
+        grads = torch.zeros_like(arena)              # the moving statistics' floats stay 0 for torch optimizers
+        if d_audio is not None or d_mags is not None:
+            sep._backward_into(arena, grads, d_mags, d_audio, key[0], key[1])
+        return grads, None, None, None, None
+
+
+class SpecUNet(torch.nn.Module):
+    """A UnetSpectrogramSeparator as a torch.nn.Module, on the model of autograd.WaveUNet.  forward(mix [B, T, 1]) gives
+    output="audio": [S, B, T, 1];  "mags": [S, B, F, K];  "both": (audio, mags) -- fresh tensors per call, source_names order.
+    train(): batch statistics, dropout keyed by `dropout_step` (starts at the separator's global_step, advances by one per
+    training forward, settable), differentiable w.r.t. `arena`, the ONE nn.Parameter that shares storage with sep.params (the
+    moving statistics' floats get gradient 0).  eval(): wun_spec_forward under no_grad.  The separator keeps one training
+    workspace per (batch, samples): a second training forward of the same shape before the first one's backward makes that
+    backward raise RuntimeError.  Second-order gradients are not supported."""
+
+    def __init__(self, sep, output="audio"):
+        super().__init__()
+        if output not in ("audio", "mags", "both"):
+            raise ValueError('output must be "audio", "mags" or "both", got %r' % (output,))
+        self.sep, self.output = sep, output
+        sep._ensure_variables()
+        self.arena = torch.nn.Parameter(sep.params, requires_grad=True)    # shares storage with sep.params
+        assert self.arena.data_ptr() == sep.params.data_ptr()
+        self.tensors = list(sep._table.tensors)
+        self.dropout_step = int(sep.global_step)
+
+    def forward(self, mix):
+        if torch.is_tensor(mix) and mix.requires_grad:
+            raise NotImplementedError("the spectrogram U-Net has no gradient with respect to the mix: it would pass through |X|, "
+                                      "which has a kink at 0, log1p and the phase; detach the mix")
+        if not torch.is_tensor(mix):
+            mix = torch.as_tensor(np.asarray(mix, dtype=np.float32))
+        if mix.dim() != 3 or mix.shape[2] != 1:
+            raise ValueError("input must be [batch, samples, 1] (mono), got %s" % (tuple(mix.shape),))
+        sep = self.sep
+        sep.frames(int(mix.shape[1]))                # every refusal before any GPU work
+        if not self.training:
+            with torch.no_grad():
+                outs = [torch.stack([o[n] for n in sep.source_names]) for o in
+                        (sep.get_output(mix, False, return_spectrogram=r) for r in ((False,) if self.output == "audio" else
+                                                                                     (True,) if self.output == "mags" else (False, True)))]
+            return outs[0] if len(outs) == 1 else tuple(outs)
+        mix = mix.to(device=self.arena.device, dtype=torch.float32).contiguous()
+        step = self.dropout_step
+        self.dropout_step += 1
+        return _TrainOutput.apply(self.arena, mix, sep, self.output, step)
+
+    def update_moving_averages(self):
+        """The batch norms' UPDATE_OPS from the last training forward (what a torch optimizer does not do)."""
+        with torch.no_grad():
+            self.sep.update_moving_averages()
+
+    def named_variables(self):
+        """tf_name -> view of the arena."""
+        return {name: self.arena[off:off + int(np.prod(shp))].view(*shp) for name, off, shp in self.tensors}
+
+    def variable_grads(self):
+        """tf_name -> view of arena.grad (after backward), or None."""
+        g = self.arena.grad
+        if g is None:
+            return None
+        return {name: g[off:off + int(np.prod(shp))].view(*shp) for name, off, shp in self.tensors}
