@@ -721,6 +721,58 @@ int     wun_wiener_filter_fft(const float* mix_tc, const float* ests, int32_t S,
                               int32_t hop, int32_t power, float mask_eps, int32_t iterations, float eps,
                               const float* table_dev, float* out, float* scratch, void* stream);
 
+/* ---- Griffin-Lim phase reconstruction: magnitudes to audio ----
+ * Audio whose STFT magnitude approaches a given `mag`, by alternating projections (Griffin & Lim 1984; the reference's
+ * Utils.reconPhase) with the optional acceleration of Perraudin, Balazs & Sondergaard 2013.  Rows are r = (s B + b) C + c of
+ * audio [S, B, T, C]; spectra are [R][F][K], K = n_fft / 2 + 1; the caller gives lead and F exactly as for
+ * wun_stft_complex_fft / wun_istft_fft.  STFT and ISTFT below are THAT section's, bit for bit: periodic Hann, wun_fft_design's
+ * table, the window-square-normalised overlap-add (the least-squares inverse the method's convergence argument needs), the
+ * 1e-8 rule, samples outside [0, T) read as 0.
+ *   unit(c)   : c / |c|, and unit(0) = 1 (numpy's angle(0) is 0).  In float32, with c = re + i im:
+ *                   if (re == 0 && im == 0)  u = 1 + 0 i            (either sign of zero)
+ *                   else  s = fmaxf(fabsf(re), fabsf(im));  a = re / s;  b = im / s;        (IEEE divisions: |a|, |b| <= 1, one is 1)
+ *                         n = sqrtf(fmaf(a, a, b * b));  u = a / n + i (b / n)               (n in [1, sqrt 2])
+ *               so neither re^2 + im^2 nor its reciprocal can overflow or flush to zero.  A NaN in c gives NaN; so does an
+ *               infinity.  The projected bin is S = mag * Re u + i (mag * Im u): one float32 product each.
+ *   plain     : (momentum = 0) for i = 0 .. iterations - 1:  c_i = STFT(y_{i-1}) -- for i = 0 the caller's initial spectrum
+ *               when one is given (its Im at the bins 0 and n_fft / 2 counts as 0), STFT(y_init) otherwise;
+ *               S_i = mag * unit(c_i), which at the bins 0 and n_fft / 2 is mag * sign(Re), sign(0) = 1;
+ *               y_i = ISTFT(S_i) over [0, T).  The result is y_{iterations - 1}.
+ *   fast      : (0 < momentum < 1)  t_i = c_i + momentum (c_i - c_{i-1}) as fmaf(momentum, c_i - c_{i-1}, c_i) on Re and on Im,
+ *               t_0 = c_0;  S_i = mag * unit(t_i).  c_{i-1} is one [R][F][K] complex spectrum in `scratch`; the frame kernel's
+ *               epilogue reads and rewrites it at the lane's own bin.  momentum = 0 touches no such buffer, needs no scratch
+ *               for it and gives the plain path's bits.
+ *   inconsistency : optional device float64 [iterations][2] (may be NULL).  For an iteration that runs a forward transform,
+ *               slot 0 = sum (|c_i| - mag)^2 and slot 1 = sum mag^2 over all rows, frames and bins, with
+ *               |c_i| = sqrt(Re^2 + Im^2) in float64 on the float32 Re, Im.  Per frame: every lane adds its bins
+ *               k = lane, lane + L, .. (L = min(256, n_fft / 8) lanes per frame; bin n_fft / 2 is lane 0's last) in ascending k,
+ *               the lanes are added in groups of 8 in ascending lane order, the groups in ascending order; a finishing launch adds
+ *               the frames in ascending (r, f).  No atomics, no host sync; the bits do not depend on the grid.  sqrt(slot 0 /
+ *               slot 1) is the spectral convergence a caller stops on.  An iteration that starts from a given spectrum writes
+ *               NaN into both slots.
+ * One launch per block of 256 frames takes a frame from samples to FFT, projection, inverse FFT and windowed frame inside one
+ * workgroup's LDS -- the spectrum never reaches memory -- followed by wun_istft's overlap-add kernel.  Iteration i + 1 reads the
+ * whole of y_i: the iterations alternate between y and an audio buffer in `scratch`, so no launch reads what it writes (an
+ * y_init that overlaps y is first copied into that buffer when iteration 0 would write y).  A frame's floats depend on that
+ * frame's samples, its `mag` row and the table alone: not on the frames sharing its workgroup, the block, the grid, what
+ * `scratch` held or pointer alignment beyond 4 bytes.  Caller-owned buffers; nothing allocates or synchronises; every check
+ * runs before any GPU work.  Both compute modes. */
+
+/* floats of `scratch` for wun_griffin_lim, with R = S B C and nb = min(F, 256 + ceil(n_fft / hop) - 1):
+ *   R nb n_fft (the frames of one block) + R T (the second audio buffer) + (momentum_nonzero ? 2 R F K : 0) (c_{i-1})
+ *   + 2 n_fft (the float64 window squares) + 4 R F (the frames' float64 partial sums) + 2 (alignment room).
+ * Negative wun_status as wun_griffin_lim for the same arguments. */
+int64_t wun_griffin_lim_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
+                                       int64_t F, int32_t momentum_nonzero);
+/* y (device [S, B, T, C], every float written) = y_{iterations - 1} from mag (device [R][F][K]) and exactly one start: the
+ * spectrum init_re, init_im (device [R][F][K]) or the audio y_init (device [S, B, T, C]; may be y itself).  table_dev is
+ * wun_fft_design's table.  Checks and their order as wun_istft_fft (null mag, table_dev, y or scratch; the audio shape; n_fft;
+ * hop; lead; F); then WUN_ERR_INVALID for iterations < 1, a momentum outside [0, 1) or not finite, both or neither start
+ * given (init_re without init_im, or the reverse, is refused too), y overlapping mag or the initial spectrum. */
+int     wun_griffin_lim(const float* mag, const float* init_re, const float* init_im, const float* y_init, int32_t S, int32_t B,
+                        int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead, int64_t F, int32_t iterations,
+                        float momentum, const float* table_dev, float* y, double* inconsistency, float* scratch, void* stream);
+
 /* ---- the FFT path of the spectral loss and its gradient ----
  * wun_stft_magnitude, wun_spectral_loss and wun_spectral_loss_terms with both frame transforms of a resolution computed by the
  * FFT of the section above instead of a GEMM, for n_fft a power of two in 64..8192: the loss at the resolutions the filters

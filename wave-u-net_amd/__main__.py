@@ -25,6 +25,9 @@ masks the estimates against the mix's STFT before they are written / scored (pos
 (postfilter.WienerFilter: EM iterations over the channels together; "kind":"softmask" is the default).
 `"transform":"fft"` in either spec computes the transforms with an FFT and lifts n_fft's limit from 2048 to 8192
 (`postfilter={"n_fft":4096,"hop":1024,"transform":"fft"}`).
+`phase_iterations=N` (predict, evaluate; cfg.unet_spectrogram* only) refines the phase of the network's source magnitudes with N
+Griffin-Lim iterations from the mix's phase (the reference's spectrogramToAudioFile, Utils.py:125-173) instead of keeping the mix's
+phase; the refined audio is normalised by the window-square sum over the covering frames.  Absent or 0: the default audio output.
 `train` takes the spectral objective as `model_config.spectral_loss={"resolutions":[[4096,1024]],"transform":"fft","terms":{"sc":1,
 "log_mag_l1":1},"log_eps":4.0}`: `"transform":"fft"` lifts the loss's n_fft limit from 2048 to 8192 in the same way ("gemm" is the default).
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
@@ -71,6 +74,13 @@ def _postfilter(opts, model_config):
         raise SystemExit("postfilter: %s" % e)
 
 
+def _phase_iterations(opts):
+    n = opts.get("phase_iterations", 0)
+    if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise SystemExit("phase_iterations must be an iteration count >= 0, got %r" % (n,))
+    return n
+
+
 def main(argv=None):
     cmd, name, overrides, opts = _parse(sys.argv[1:] if argv is None else argv)
     import wave_u_net_amd as wun
@@ -102,7 +112,8 @@ def main(argv=None):
                 raise SystemExit("evaluate needs %s=<dir>" % need)
         folder = evaluate.produce_dataset_estimates(model_config, opts.get("model_path"), opts["data_root"],
                                                     opts["estimates_path"], partition=opts.get("partition", "test"),
-                                                    postfilter=_postfilter(opts, model_config))
+                                                    postfilter=_postfilter(opts, model_config),
+                                                    phase_iterations=_phase_iterations(opts))
         for metric in ("SDR", "ISR", "SIR", "SAR"):
             stats = evaluate.compute_mean_metrics(folder, metric=metric)
             for src, (med, mad, mean, sd) in zip(model_config["source_names"], stats):
@@ -114,7 +125,8 @@ def main(argv=None):
         if hop is not None and hop != "track" and (isinstance(hop, bool) or not isinstance(hop, int) or hop < 1):
             raise SystemExit("hop_frames must be a positive frame count or 'track', got %r" % (hop,))
         evaluate.produce_source_estimates(model_config, opts.get("model_path"), opts["input_path"], opts.get("output_path"),
-                                          hop_frames=hop, postfilter=_postfilter(opts, model_config))
+                                          hop_frames=hop, postfilter=_postfilter(opts, model_config),
+                                          phase_iterations=_phase_iterations(opts))
 
 
 if __name__ == "__main__":

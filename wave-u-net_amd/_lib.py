@@ -142,6 +142,10 @@ _SIGS = {
     "wun_wiener_filter_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "wun_wiener_filter_fft": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                         C.c_int32, C.c_float, _P, _P, _P, _P]),
+    "wun_griffin_lim_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   C.c_int64, C.c_int32]),
+    "wun_griffin_lim": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int64, C.c_int32, C.c_float, _P, _P, _P, _P, _P]),
     "wun_stft_magnitude_fft": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "wun_spectral_fft_scratch_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                                     C.POINTER(C.c_int32)]),

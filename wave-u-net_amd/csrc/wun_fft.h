@@ -50,6 +50,24 @@ struct SpecHeadArgs {
     float c_edge, c_mid;                                         // 1 / n_fft, 2 / n_fft
 };
 
+// One Griffin-Lim iteration on the frame rows of a block (wun_griffin_lim): frame row m = r * nb + fl is frame
+// f = f0 + fl of row r; its bins lie at (r * F + f) * K of mag, cre / cim and pre / pim, its partial sums at (r * F + f) * 2.
+struct GlArgs {
+    const float* x;                          // y_{i-1} [SB, T, C] (not read when the spectrum is given)
+    const float* cre; const float* cim;      // the given spectrum c_0 (read only then)
+    const float* mag;
+    float* pre; float* pim;                  // c_{i-1}, or null: momentum 0
+    double* part;                            // [R][F][2], or null: no inconsistency asked for (never written from a given spectrum)
+    const float* table;
+    float* frames;                           // [M][n_fft]
+    long long M, nb, f0, F, T;
+    long long last_below;                    // frames f < last_below are computed for the last time in this iteration: they
+                                             // alone store c_i and their partial sums (a later block computes the others again)
+    int C, n_fft, hop, lead, K;
+    int first;                               // iteration 0: t_0 = c_0, c_{i-1} is not read
+    float momentum, scale;                   // scale = 1 / n_fft
+};
+
 // wun_fft.hip: stft_fft_kernel / istft_fft_kernel of a.n_fft (a power of two in 64..8192) on stream s.  WUN_OK, or
 // WUN_ERR_UNSUPPORTED (wun_last_error() set, nothing launched) for an n_fft without a kernel.
 //   magnitude   the forward body with StftMagArgs' epilogue (the spectral loss and wun_stft_magnitude_fft)
@@ -61,6 +79,10 @@ int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s);
 int fft_launch_adjoint(const IstftGemmArgs& g, hipStream_t s);
 //   spec_head   the forward body on a.x[0] with SpecHeadArgs' epilogue, one signal
 int fft_launch_spec_head(const SpecHeadArgs& a, hipStream_t s);
+//   griffin_lim gl_frame_kernel on the frame rows of g; given: c_0 is g.cre / g.cim and no forward transform runs
+int fft_launch_griffin_lim(const GlArgs& g, bool given, hipStream_t s);
+// out[0], out[1] = the sums of part[e][0] and part[e][1] over e = 0 .. n - 1 in ascending e (one workgroup); n < 0: NaN into both
+void launch_gl_finish(const double* part, long long n, double* out, hipStream_t s);
 // D[p] = (float) sum_i w^2[p + i hop] over p + i hop < n_fft (float64, i ascending: istft_ola_kernel<true>'s normaliser), p < hop
 void launch_steady_den(float* D, int n_fft, int hop, hipStream_t s);
 // u[e] = g[e] / D[(e mod T) mod hop] for the N = rows T samples of [rows][T]

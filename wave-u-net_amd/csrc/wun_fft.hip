@@ -4,6 +4,7 @@
 // loss's two frame transforms (wun_spectral_loss_fft and its kin) are the same two bodies: the forward one with
 // the magnitude as its epilogue, the inverse one as the unscaled adjoint.  The spectrogram U-Net's backward from an audio gradient
 // (wun_spec_backward) is the forward body once more, on d_audio / D, with the mask gradient as its epilogue.
+// Griffin-Lim (wun_griffin_lim) runs both transforms of a frame in one workgroup, the projection between them.
 //
 //   real transform   a frame of n_fft real samples is one complex FFT of M = n_fft / 2 points, z[m] = y[2m] + i y[2m+1], and a
 //                    split step:  E = (Z[k] + conj Z[M-k]) / 2,  O = (Z[k] - conj Z[M-k]) / 2i,  X[k] = E + W_N^k O,  k = 0..M
@@ -57,7 +58,9 @@ __device__ __forceinline__ int fft_swz(int a) {
 
 // The M-point FFT of one frame: `load(a, re, im)` gives point a (the first stage reads nothing else); the result lies in image
 // FftGeom::RESULT at fft_swz(base + k), natural order, behind a barrier.  tw: cos(2 pi t / N) at [t], -sin at [N + t].
-template <int LOGM, class Load>
+// FLIP = 1 swaps the roles of the two images (the first stage writes image 1, the result lies in RESULT ^ 1): the same
+// instructions on the same values.
+template <int LOGM, int FLIP = 0, class Load>
 __device__ __forceinline__ void fft_run(Load load, float (*sre)[FftGeom<LOGM>::PLANE], float (*sim)[FftGeom<LOGM>::PLANE], int base,
                                         int tl, const float* __restrict__ tw) {
     using G = FftGeom<LOGM>;
@@ -65,10 +68,10 @@ __device__ __forceinline__ void fft_run(Load load, float (*sre)[FftGeom<LOGM>::P
 #pragma unroll
     for (int s = 0; s < LOGM / 2; ++s) {
         const int Ns = 1 << (2 * s);
-        const float* __restrict__ ir = sre[(s & 1) ^ 1];
-        const float* __restrict__ ii = sim[(s & 1) ^ 1];
-        float* __restrict__ outr = sre[s & 1];
-        float* __restrict__ outi = sim[s & 1];
+        const float* __restrict__ ir = sre[(s & 1) ^ 1 ^ FLIP];
+        const float* __restrict__ ii = sim[(s & 1) ^ 1 ^ FLIP];
+        float* __restrict__ outr = sre[(s & 1) ^ FLIP];
+        float* __restrict__ outi = sim[(s & 1) ^ FLIP];
 #pragma unroll
         for (int i = 0; i < G::BPT; ++i) {
             const int j = tl + i * TPF, k = j & (Ns - 1);
@@ -101,10 +104,10 @@ __device__ __forceinline__ void fft_run(Load load, float (*sre)[FftGeom<LOGM>::P
     }
     if (LOGM & 1) {                                                          // the radix-2 stage, Ns = M / 2
         constexpr int s = LOGM / 2;
-        const float* __restrict__ ir = sre[(s & 1) ^ 1];
-        const float* __restrict__ ii = sim[(s & 1) ^ 1];
-        float* __restrict__ outr = sre[s & 1];
-        float* __restrict__ outi = sim[s & 1];
+        const float* __restrict__ ir = sre[(s & 1) ^ 1 ^ FLIP];
+        const float* __restrict__ ii = sim[(s & 1) ^ 1 ^ FLIP];
+        float* __restrict__ outr = sre[(s & 1) ^ FLIP];
+        float* __restrict__ outi = sim[(s & 1) ^ FLIP];
 #pragma unroll
         for (int i = 0; i < 2 * G::BPT; ++i) {
             const int j = tl + i * TPF;
@@ -275,6 +278,177 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void istft_fft_kernel(IstftGemmArgs 
     }
 }
 
+// unit(c) of wun_griffin_lim (include/wun.h), spelled out: which operation is fused decides the bits.  Scaled by the larger
+// of |re| and |im|, so nothing overflows or flushes; a NaN (fmaxf drops it, the division brings it back) stays NaN.
+__device__ __forceinline__ void gl_unit(float re, float im, float& ur, float& ui) {
+    if (re == 0.f && im == 0.f) { ur = 1.f; ui = 0.f; return; }
+    const float s = fmaxf(fabsf(re), fabsf(im));
+    const float a = re / s, b = im / s;
+    const float n = sqrtf(fmaf(a, a, b * b));
+    ur = a / n;
+    ui = b / n;
+}
+
+// One Griffin-Lim iteration of the workgroup's FPW frame rows (GlArgs, wun_fft.h): fft_fwd_frames' transform of
+// the windowed samples of y_{i-1}, the split step per bin in registers, the momentum epilogue and the projection
+// S = mag unit(t), then istft_fft_kernel's inverse of S -- the spectrum never leaves the workgroup.  S goes to the LDS image the
+// forward transform's last stage left free (RESULT ^ 1; bin M is real and takes the imaginary slot of bin 0, so 8192 points
+// still take 64 KB); behind ONE barrier the inverse pre-step reads S[k] and S[M-k] from there while its first stage writes the
+// image the forward result lay in (fft_run<.., FLIP = RESULT>): the inverse's result is image 0 for every LOGM.  The reads of
+// S run along k and against it, both a permutation inside each aligned run of 32 floats under fft_swz: conflict-free but for
+// the one lane across a run's edge, as the forward split step.
+// GIVEN: c_0 comes from p.cre / p.cim, no forward transform and no partial sums.
+// With p.part the frame's two float64 sums leave through image 1, free behind the inverse's last barrier (two more barriers).
+template <int LOGM, bool GIVEN>
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void gl_frame_kernel(GlArgs p) {
+    using G = FftGeom<LOGM>;
+    constexpr int M = G::M, N = G::N, TPF = G::TPF, SI = G::RESULT ^ 1;
+    __shared__ __attribute__((aligned(16))) float sre[2][G::PLANE];
+    __shared__ __attribute__((aligned(16))) float sim[2][G::PLANE];
+    const int g = threadIdx.x / TPF, tl = threadIdx.x - g * TPF, base = g * M;
+    const long long m = (long long)blockIdx.x * G::FPW + g;
+    const bool valid = m < p.M;                              // a frame slot behind the last row runs on zeros, stores nothing
+    long long rbase = 0, t0 = 0, row = 0;
+    bool last = false;
+    if (valid) {
+        const long long r = m / p.nb, f = p.f0 + (m - r * p.nb);
+        const long long sb = r / p.C, c = r - sb * p.C;
+        rbase = sb * p.T * p.C + c;
+        t0 = f * p.hop - p.lead;
+        row = r * p.F + f;
+        last = f < p.last_below;
+    }
+    const long long o = row * p.K;
+    const float* __restrict__ tw = p.table;
+    const float* __restrict__ win = p.table + 2 * N;
+    if (!GIVEN) {
+        const float* __restrict__ x = p.x;
+        const long long T = p.T;
+        const int C = p.C;
+        fft_run<LOGM>([&](int a, float& re, float& im) {     // (fft_fwd_frames' load)
+            const long long t = t0 + 2 * a;
+            re = (valid && t >= 0 && t < T) ? x[rbase + t * C] * win[2 * a] : 0.f;
+            im = (valid && t + 1 >= 0 && t + 1 < T) ? x[rbase + (t + 1) * C] * win[2 * a + 1] : 0.f;
+        }, sre, sim, base, tl, tw);
+    }
+    const float* __restrict__ Zr = sre[G::RESULT];
+    const float* __restrict__ Zi = sim[G::RESULT];
+    float* Sr = sre[SI];
+    float* Si = sim[SI];
+    const bool mom = p.pre != nullptr && valid;
+    const bool sums = !GIVEN && p.part != nullptr;           // (uniform)
+    double d0 = 0.0, d1 = 0.0;
+#pragma unroll
+    for (int i = 0; i <= M / TPF; ++i) {
+        const int k = tl + i * TPF;                          // 0 .. M: the last round is lane 0's k = M
+        if (k > M) break;
+        float cr, ci;
+        if (GIVEN) {
+            cr = valid ? p.cre[o + k] : 0.f;
+            ci = (valid && k != 0 && k != M) ? p.cim[o + k] : 0.f;
+        } else {                                             // (fft_fwd_frames' split step)
+            const int ka = base + (k & (M - 1)), kb = base + ((M - k) & (M - 1));
+            const float ar = Zr[fft_swz(ka)], ai = Zi[fft_swz(ka)], br = Zr[fft_swz(kb)], bi = Zi[fft_swz(kb)];
+            const float er = 0.5f * (ar + br), ei = 0.5f * (ai - bi), odr = 0.5f * (ai + bi), odi = 0.5f * (br - ar);
+            const float wc = tw[k], ws = tw[N + k];
+            cr = er + (wc * odr - ws * odi);
+            ci = (k == 0 || k == M) ? 0.f : ei + (wc * odi + ws * odr);
+        }
+        const float mg = valid ? p.mag[o + k] : 0.f;
+        float tr = cr, ti = ci;
+        if (mom) {
+            if (!p.first) {
+                tr = fmaf(p.momentum, cr - p.pre[o + k], cr);
+                ti = fmaf(p.momentum, ci - p.pim[o + k], ci);
+            }
+            if (last) { p.pre[o + k] = cr; p.pim[o + k] = ci; }
+        }
+        if (sums) {
+            const double a = (double)cr, b = (double)ci, mm = (double)mg;
+            const double d = sqrt(a * a + b * b) - mm;
+            d0 += d * d;
+            d1 += mm * mm;
+        }
+        float ur, ui;
+        gl_unit(tr, ti, ur, ui);
+        const float sr = mg * ur, si = mg * ui;
+        if (k == M) Si[fft_swz(base)] = sr;
+        else {
+            Sr[fft_swz(base + k)] = sr;
+            if (k != 0) Si[fft_swz(base + k)] = si;
+        }
+    }
+    __syncthreads();
+    fft_run<LOGM, G::RESULT>([&](int k, float& re, float& im) {      // (istft_fft_kernel's pre-step, S from LDS)
+        if (k == 0) {
+            const float x0 = Sr[fft_swz(base)], xm = Si[fft_swz(base)];
+            re = x0 - xm; im = x0 + xm;
+            return;
+        }
+        const float ar = Sr[fft_swz(base + k)], ai = Si[fft_swz(base + k)];
+        const float cr = Sr[fft_swz(base + M - k)], ci = Si[fft_swz(base + M - k)];
+        const float dr = ar - cr, di = ai + ci;
+        const float wc = tw[k], ws = tw[N + k];
+        const float pr = wc * dr + ws * di, pi = wc * di - ws * dr;
+        re = (ai - ci) + pr; im = (ar + cr) - pi;
+    }, sre, sim, base, tl, tw);
+    if (valid) {
+        const float* __restrict__ Yr = sre[0];
+        const float* __restrict__ Yi = sim[0];
+        float* __restrict__ fr = p.frames + m * N;
+        const float scale = p.scale;
+#pragma unroll
+        for (int i = 0; i < M / TPF; ++i) {
+            const int mm = tl + i * TPF;
+            fr[2 * mm] = (Yi[fft_swz(base + mm)] * scale) * win[2 * mm];
+            fr[2 * mm + 1] = (Yr[fft_swz(base + mm)] * scale) * win[2 * mm + 1];
+        }
+    }
+    if (sums) {                                              // lanes in groups of 8, then the groups, ascending
+        double* dp = reinterpret_cast<double*>(&sre[1][0]);  // 2 x 256 doubles <= PLANE floats
+        dp[2 * threadIdx.x] = d0;
+        dp[2 * threadIdx.x + 1] = d1;
+        __syncthreads();
+        if ((tl & 7) == 0) {
+            double a0 = dp[2 * threadIdx.x], a1 = dp[2 * threadIdx.x + 1];
+#pragma unroll
+            for (int j = 1; j < 8; ++j) { a0 += dp[2 * (threadIdx.x + j)]; a1 += dp[2 * (threadIdx.x + j) + 1]; }
+            dp[2 * threadIdx.x] = a0;
+            dp[2 * threadIdx.x + 1] = a1;
+        }
+        __syncthreads();
+        if (tl == 0 && valid && last) {
+            double a0 = dp[2 * threadIdx.x], a1 = dp[2 * threadIdx.x + 1];
+            for (int j = 8; j < TPF; j += 8) { a0 += dp[2 * (threadIdx.x + j)]; a1 += dp[2 * (threadIdx.x + j) + 1]; }
+            p.part[2 * row] = a0;
+            p.part[2 * row + 1] = a1;
+        }
+    }
+}
+
+// one workgroup: chunks of 256 frames through LDS, lane 0 adds slot 0 and lane 64 slot 1 in ascending frame order
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void gl_finish_kernel(const double* __restrict__ part, long long n, double* __restrict__ out) {
+    __shared__ double buf[2][WUN_FFT_BLOCK];
+    const int tid = threadIdx.x;
+    if (n < 0) {
+        if (tid < 2) out[tid] = __builtin_nan("");
+        return;
+    }
+    const int slot = tid == 64 ? 1 : 0;
+    double acc = 0.0;
+    for (long long e0 = 0; e0 < n; e0 += WUN_FFT_BLOCK) {
+        const long long e = e0 + tid;
+        if (e < n) { buf[0][tid] = part[2 * e]; buf[1][tid] = part[2 * e + 1]; }
+        __syncthreads();
+        if (tid == 0 || tid == 64) {
+            const int cnt = n - e0 < WUN_FFT_BLOCK ? (int)(n - e0) : WUN_FFT_BLOCK;
+            for (int j = 0; j < cnt; ++j) acc += buf[slot][j];
+        }
+        __syncthreads();
+    }
+    if (tid == 0 || tid == 64) out[slot] = acc;
+}
+
 // f(std::integral_constant<int, log2(n_fft / 2)>) for an n_fft with a kernel; else WUN_ERR_UNSUPPORTED, nothing launched
 template <class F>
 static int fft_dispatch(const char* who, int n_fft, F f) {
@@ -337,6 +511,19 @@ int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s) {
         constexpr int LM = decltype(L)::value;
         hipLaunchKernelGGL((istft_fft_kernel<LM, false>), inv_grid<LM>(g), dim3(WUN_FFT_BLOCK), 0, s, g);
     });
+}
+
+int fft_launch_griffin_lim(const GlArgs& g, bool given, hipStream_t s) {
+    return fft_dispatch("fft_launch_griffin_lim", g.n_fft, [&](auto L) {
+        constexpr int LM = decltype(L)::value;
+        const dim3 grid((unsigned)((g.M + FftGeom<LM>::FPW - 1) / FftGeom<LM>::FPW));
+        if (given) hipLaunchKernelGGL((gl_frame_kernel<LM, true>), grid, dim3(WUN_FFT_BLOCK), 0, s, g);
+        else hipLaunchKernelGGL((gl_frame_kernel<LM, false>), grid, dim3(WUN_FFT_BLOCK), 0, s, g);
+    });
+}
+
+void launch_gl_finish(const double* part, long long n, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(gl_finish_kernel, dim3(1), dim3(WUN_FFT_BLOCK), 0, s, part, n, out);
 }
 
 int fft_launch_adjoint(const IstftGemmArgs& g, hipStream_t s) {

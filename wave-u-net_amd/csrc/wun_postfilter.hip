@@ -21,7 +21,8 @@
 //
 // Every entry exists a second time with the frame transforms computed by an FFT (wun_*_fft): the bodies below
 // take a selector `tr`, which launch_cfwd / launch_gemm turn into the GEMM kernels here or the FFT kernels of wun_fft.hip;
-// blocks, mask, EM, overlap-add and scratch are the same code.
+// blocks, mask, EM, overlap-add and scratch are the same code.  wun_griffin_lim iterates on the same blocks and
+// overlap-add around gl_frame_kernel of wun_fft.hip.
 //
 // Built WITHOUT the packed fp32 VALU instructions (csrc/Makefile NO_PK_FP32): the filter runs beside inference of
 // either compute mode.  Every argument check runs before any GPU work; nothing allocates or synchronises.
@@ -657,6 +658,80 @@ extern "C" int wun_istft_tf(const float* re, const float* im, int32_t S, int32_t
 extern "C" int wun_istft_tf_fft(const float* re, const float* im, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop,
                                 int64_t F, const float* table_dev, float* y, float* scratch, void* stream) {
     return istft_entry("wun_istft_tf_fft", WUN_TR_FFT, re, im, S, B, T, C, n_fft, hop, 0, F, table_dev, y, scratch, stream, true);
+}
+
+// ---- Griffin-Lim (include/wun.h): istft_entry's blocks, window squares and overlap-add around gl_frame_kernel ----
+// scratch: the frames of one block, the second audio buffer, c_{i-1} (Re, Im) with momentum; float64 tail: the window squares,
+// then the frames' partial sums [R][F][2]
+namespace {
+int check_griffin_lim(const char* who, int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead, int64_t F) {
+    int rc;
+    if ((rc = check_audio(who, S, B, T, C))) return rc;
+    if ((rc = check_res(who, WUN_TR_FFT, n_fft, hop))) return rc;
+    return check_framing(who, S, B, C, n_fft, lead, F);
+}
+}  // namespace
+
+extern "C" int64_t wun_griffin_lim_scratch_floats(int32_t S, int32_t B, int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead,
+                                                  int64_t F, int32_t momentum_nonzero) {
+    const int rc = check_griffin_lim("wun_griffin_lim_scratch_floats", S, B, T, C, n_fft, hop, lead, F);
+    if (rc) return rc;
+    const int64_t R = (int64_t)S * B * C, K = n_fft / 2 + 1;
+    return R * block_frames(F, n_fft, hop) * n_fft + R * T + (momentum_nonzero ? 2 * R * F * K : 0) + 2 * (int64_t)n_fft + 4 * R * F + 2;
+}
+
+extern "C" int wun_griffin_lim(const float* mag, const float* init_re, const float* init_im, const float* y_init, int32_t S, int32_t B,
+                               int64_t T, int32_t C, int32_t n_fft, int32_t hop, int32_t lead, int64_t F, int32_t iterations,
+                               float momentum, const float* table_dev, float* y, double* inconsistency, float* scratch, void* stream) {
+    const char* who = "wun_griffin_lim";
+    if (!mag || !table_dev || !y || !scratch) return fail(WUN_ERR_INVALID, std::string(who) + ": null argument");
+    int rc;
+    if ((rc = check_griffin_lim(who, S, B, T, C, n_fft, hop, lead, F))) return rc;
+    if (iterations < 1) return fail(WUN_ERR_INVALID, std::string(who) + ": iterations < 1");
+    if (!(momentum >= 0.f && momentum < 1.f)) return fail(WUN_ERR_INVALID, std::string(who) + ": momentum outside [0, 1)");
+    const bool given = init_re && init_im;
+    if ((init_re != nullptr) != (init_im != nullptr) || given == (y_init != nullptr))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": exactly one of (init_re and init_im) and y_init must be given");
+    const long long R = (long long)S * B * C, K = n_fft / 2 + 1, E = R * F * K, NT = R * T;
+    if (overlaps(y, NT, mag, E) || (given && (overlaps(y, NT, init_re, E) || overlaps(y, NT, init_im, E))))
+        return fail(WUN_ERR_INVALID, std::string(who) + ": y overlaps mag or the initial spectrum");
+
+    hipStream_t s = (hipStream_t)stream;
+    const long long fr_floats = R * block_frames(F, n_fft, hop) * n_fft;
+    float* frames = scratch;
+    float* alt = scratch + fr_floats;
+    float* pre = momentum != 0.f ? alt + NT : nullptr;
+    float* pim = pre ? pre + E : nullptr;
+    double* wsq = f64_tail(scratch, fr_floats + NT + (pre ? 2 * E : 0));
+    double* part = wsq + n_fft;
+    launch_window(wsq, n_fft, s);
+    // iteration i writes y when an even number of iterations follows it, the second buffer otherwise
+    const float* src = y_init;
+    if (!given && (iterations & 1) && overlaps(y_init, NT, y, NT)) {         // iteration 0 would write what it reads
+        const hipError_t e = hipMemcpyAsync(alt, y_init, 4 * (size_t)NT, hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string(who) + " copy: " + hipGetErrorString(e));
+        src = alt;
+    }
+    const int ov = overlap_frames(n_fft, hop);
+    for (int it = 0; it < iterations; ++it) {
+        float* dst = ((iterations - 1 - it) & 1) ? alt : y;
+        const bool giv = given && it == 0;
+        for (long long f0 = 0; f0 < F; f0 += WUN_PF_FRAMES) {                // (every block: its frames' c_i and sums are needed
+            const Blk b = block_of(f0, F, T, n_fft, hop, lead);              //  even where no sample ends in it)
+            GlArgs a;
+            a.x = giv ? nullptr : src; a.cre = giv ? init_re : nullptr; a.cim = giv ? init_im : nullptr; a.mag = mag;
+            a.pre = pre; a.pim = pim; a.part = inconsistency && !giv ? part : nullptr; a.table = table_dev; a.frames = frames;
+            a.M = R * b.nb; a.nb = b.nb; a.f0 = b.fb0; a.F = F; a.T = T;
+            a.last_below = f0 + WUN_PF_FRAMES < F ? f0 + WUN_PF_FRAMES - ov : (long long)F;
+            a.C = C; a.n_fft = n_fft; a.hop = hop; a.lead = lead; a.K = (int)K; a.first = it == 0;
+            a.momentum = momentum; a.scale = 1.f / (float)n_fft;
+            if ((rc = fft_launch_griffin_lim(a, giv, s))) return rc;
+            if (b.t_lo < b.t_hi) launch_ola(frames, wsq, dst, (long long)S * B, T, C, F, b, n_fft, hop, lead, s);
+        }
+        if (inconsistency) launch_gl_finish(part, giv ? -1 : R * F, inconsistency + 2 * it, s);
+        src = dst;
+    }
+    return launch_status(who);
 }
 
 extern "C" int64_t wun_mask_filter_scratch_floats(int32_t S, int64_t n, int32_t C, int32_t n_fft, int32_t hop) {

@@ -107,7 +107,7 @@ def budget_batch_hops(separator, batch_hops, n_hops, input_frames, default_input
 
 
 def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, hop_frames=None, workspace_bytes=None,
-                   return_device=False, postfilter=None):
+                   return_device=False, postfilter=None, phase_iterations=0):
     """Evaluate.predict (Evaluate.py:59-80) around predict_track (:82-145) for audio at any sample rate, without the
     host in the loop.  mix_audio: [n_frames, n_channels] float array or tensor at mix_sr Hz.  Returns {source_name: float32
     numpy [n_frames, channels]} at mix_sr: channels is the input's count, except that a stereo model on a mono file
@@ -140,8 +140,21 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     postfilter (a postfilter.SoftMaskFilter or WienerFilter, or the spec postfilter.from_config takes; default None: no
     filter, today's path): the soft-mask filter, or with {"kind": "wiener", ...} the multichannel Wiener filter, applied at
     the model's rate to the estimates and the resampled mix before the resampling back -- the estimates then share the
-    mix's phase and sum to it."""
+    mix's phase and sum to it.
+
+    phase_iterations=N > 0 (network "unet_spectrogram" only; NotImplementedError on the waveform network, whose own magnitudes
+    with its own phase are already consistent): every hop's source magnitudes (get_output(.., return_spectrogram=True)) go
+    through N Griffin-Lim iterations from the mix's phase (separator.reconstruct, the reference's spectrogramToAudioFile with
+    phase=mix_phase) instead of keeping the mix's phase as it is.  The refined audio is normalised by
+    wun_istft's window-square sum over the covering frames, not by inverse_stft_window_fn: it differs from the default audio
+    output at a hop's edges even before the phase moves.  0 (default) is exactly the path and the bits without the option."""
     from . import resample as rs
+    phase_iterations = int(phase_iterations)
+    if phase_iterations < 0:
+        raise ValueError("phase_iterations must be >= 0, got %d" % phase_iterations)
+    if phase_iterations and model_config.get("network") != "unet_spectrogram":
+        raise NotImplementedError("phase_iterations: Griffin-Lim refines the magnitudes of the spectrogram U-Net "
+                                  "(network 'unet_spectrogram'); the waveform network has no magnitude output")
     if model_config.get("network") == "unet_spectrogram" and hop_frames is not None:
         raise NotImplementedError("hop_frames: the spectrogram U-Net separates in hops of num_frames only (its frame count is "
                                   "tied to num_layers); the plan-based long hops are Wave-U-Net only")
@@ -180,7 +193,8 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
                 separator.get_output_windows(padded, chunk, False, frames=input_frames)
                 separator.scatter_windows(chunk, preds, frames=input_frames)
     else:
-        preds = _separate_cpu(separator, padded, positions, batch_hops, input_frames, output_frames, names, n_frames, C)
+        preds = _separate_cpu(separator, padded, positions, batch_hops, input_frames, output_frames, names, n_frames, C,
+                              phase_iterations)
 
     if postfilter is not None:                                                   # at the model's rate, without extra_pad
         preds = postfilter.apply(padded[pad:pad + n_res], preds[:, :n_res])
@@ -200,14 +214,19 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     return {n: host[si] for si, n in enumerate(names)}
 
 
-def _separate_cpu(separator, padded, positions, batch_hops, input_frames, output_frames, names, n_frames, C):
-    """The hop loop on CPU tensors through separator.get_output (numpy stand-ins)."""
+def _separate_cpu(separator, padded, positions, batch_hops, input_frames, output_frames, names, n_frames, C, phase_iterations=0):
+    """The hop loop on CPU tensors through separator.get_output (numpy stand-ins).  phase_iterations > 0: the hop's magnitudes
+    through separator.reconstruct instead of its audio output."""
     device = padded.device
     preds = torch.zeros((len(names), n_frames, C), dtype=torch.float32, device=device)   # :117
     for k in range(0, len(positions), batch_hops):
         chunk = positions[k:k + batch_hops]
         batch = torch.stack([padded[p:p + input_frames] for p in chunk])         # strided views -> [B, Tin, C]
-        outs = separator.get_output(batch if device.type != "cpu" else batch.numpy(), False)
+        if phase_iterations:
+            mags = separator.get_output(batch, False, return_spectrogram=True)
+            outs = separator.reconstruct(mags, batch, phase_iterations)
+        else:
+            outs = separator.get_output(batch if device.type != "cpu" else batch.numpy(), False)
         run = 1                                                                  # leading hops at consecutive multiples
         while run < len(chunk) and chunk[run] == chunk[0] + run * output_frames:
             run += 1
@@ -222,11 +241,11 @@ def _separate_cpu(separator, padded, positions, batch_hops, input_frames, output
 
 
 def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None, hop_frames=None,
-                             postfilter=None):
+                             postfilter=None, phase_iterations=0):
     """Evaluate.produce_source_estimates (Evaluate.py:160-194): separate one mixture file with a
     checkpoint and write <input file name>_<source>.wav next to it (or into output_path), at the input file's sample rate
     and length.  WAV/NPY input at any rate (an .npy is taken to be at expected_sr; no MP3 decoding here): the separation runs
-    through separate_track (hop_frames, postfilter: its options of those names).  Returns {source: [T, C]}."""
+    through separate_track (hop_frames, postfilter, phase_iterations: its options of those names).  Returns {source: [T, C]}."""
     import os
     from scipy.io import wavfile
     from . import datasets
@@ -238,7 +257,8 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
-    preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames, postfilter=postfilter)
+    preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames, postfilter=postfilter,
+                           phase_iterations=phase_iterations)
     folder, name = os.path.split(input_path)
     if output_path is None:
         output_path = folder
@@ -249,7 +269,7 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
 
 
 def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=None, name=None, hop_frames=None,
-                   window=1.0, hop=1.0, filters_len=512, postfilter=None):
+                   window=1.0, hop=1.0, filters_len=512, postfilter=None, phase_iterations=0):
     """Evaluate.predict with a results_dir (Evaluate.py:59-80,146-158): separate the mixture (separate_track, estimates kept
     on the device), score them against the stems at the file's rate with bsseval.bss_eval, and write
     <results_dir>/<name>.json in museval's layout.  mix_audio [n, c] at sr; stems {source_name: [n, c]} at sr with the
@@ -257,7 +277,7 @@ def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=No
     are cut to the shortest length.  Returns {metric: float64 [S, nwin]}, sources in source_names order."""
     from . import bsseval
     est = separate_track(model_config, separator, mix_audio, sr, hop_frames=hop_frames, return_device=True,
-                         postfilter=postfilter)
+                         postfilter=postfilter, phase_iterations=phase_iterations)
     names = list(model_config["source_names"])
     c = int(est.shape[2])
     refs = []
@@ -309,7 +329,7 @@ def compute_mean_metrics(json_folder, compute_averages=True, metric="SDR"):
 
 
 def produce_dataset_estimates(model_config, load_model, data_root, output_path, partition="test", separator=None,
-                              hop_frames=None, postfilter=None):
+                              hop_frames=None, postfilter=None, phase_iterations=0):
     """The reference's produce_musdb_source_estimates (Evaluate.py:147-159) over the track folders of datasets.py:
     data_root/<partition>/<track>/<source>.wav|.npy (+ optional mix.wav|.npy, default: the sum of the stems), every file at
     one rate (an .npy: expected_sr).  Per track: the estimates as <output_path>/<partition>/<track>/<source>.wav and the
@@ -343,7 +363,8 @@ def produce_dataset_estimates(model_config, load_model, data_root, output_path, 
                     raise FileNotFoundError("%s: no %s.wav/.npy" % (folder, k))
         sr = int(sr) if sr is not None else int(model_config["expected_sr"])
         mix = stems.pop("mix") if "mix" in stems else sum(stems[k] for k in names)
-        est = separate_track(model_config, sep, mix, sr, hop_frames=hop_frames, return_device=True, postfilter=postfilter)
+        est = separate_track(model_config, sep, mix, sr, hop_frames=hop_frames, return_device=True, postfilter=postfilter,
+                             phase_iterations=phase_iterations)
         c = int(est.shape[2])
         refs = [np.tile(stems[k], [1, c]) if stems[k].shape[1] == 1 and c > 1 else stems[k] for k in names]
         n = min([int(est.shape[1])] + [r.shape[0] for r in refs])

@@ -19,8 +19,10 @@ Hann window, no padding), for any number of resolutions up to 8, next to the tim
     loss = SpectralLoss([(1024, 256)], terms={"sc": 1}, mel={"n_mels": 80, "sample_rate": 22050, "terms": {"log_mel_l1": 1}})
     mel_spectrogram(x, 1024, 256, 80, 22050)                      # [S, B, C, F, n_mels], the floats the mel terms are taken on
     mel_filterbank(1024, 22050, 80)                               # the dense [n_mels, K] weights, rebuilt from the library's table
+    y = griffin_lim(mag, 2048, 512, iterations=32, momentum=0.99) # audio [..., T] from magnitudes [..., F, K] (5.21)
 
-Audio is float32 [S, B, T, C] channel-last on the GPU, as get_output stacks its outputs.  There is no CPU path.
+Audio is float32 [S, B, T, C] channel-last on the GPU, as get_output stacks its outputs.  There is no CPU path, except for
+griffin_lim, whose definition also runs in plain torch on CPU tensors (the tests' stand-in, as postfilter.py's).
 """
 import ctypes as C
 
@@ -508,3 +510,168 @@ def stft_l1(outputs, targets, loss=None, resolutions=((1024, 768),), weights=Non
     if loss is None:
         loss = SpectralLoss(resolutions, weights, mse_weight, transform=transform)
     return _StftL1.apply(outputs, targets, loss)
+
+
+# ---------------------------------------------------------------------------------------------------- Griffin-Lim
+def _gl_window(n_fft, dtype, device):
+    n = torch.arange(int(n_fft), dtype=torch.float64, device=device)
+    return (0.5 - 0.5 * torch.cos(2.0 * np.pi * n / int(n_fft))).to(dtype)
+
+
+def _gl_window_sums(T, n_fft, hop, lead, F, device):
+    """float64 [T]: the sum of w^2 over the frames that cover each sample."""
+    w2 = _gl_window(n_fft, torch.float64, device) ** 2
+    total = max((F - 1) * hop + n_fft, lead + T)
+    cols = w2[None, :, None].expand(1, n_fft, F)
+    ws = torch.nn.functional.fold(cols, (1, (F - 1) * hop + n_fft), (1, n_fft), stride=(1, hop)).reshape(-1)
+    ws = torch.nn.functional.pad(ws, (0, total - ws.numel()))
+    return ws[lead:lead + T]
+
+
+def _gl_stft(y, n_fft, hop, lead, F, w):
+    """complex [R, F, K] of y [R, T]: zeros outside [0, T), Im of the bins 0 and n_fft / 2 exactly 0."""
+    total = (F - 1) * hop + n_fft
+    keep = min(int(y.shape[1]), total - lead)
+    pad = torch.zeros((y.shape[0], total), dtype=y.dtype, device=y.device)
+    pad[:, lead:lead + keep] = y[:, :keep]
+    c = torch.fft.rfft(pad.unfold(1, n_fft, hop)[:, :F] * w, dim=-1)
+    c.imag[..., 0] = 0
+    c.imag[..., -1] = 0
+    return c
+
+
+def _gl_istft(spec, T, n_fft, hop, lead, w, ws):
+    """[R, T] of complex [R, F, K]: the windowed inverse frames overlap-added over the window-square sums, the 1e-8 rule."""
+    spec = spec.clone()
+    spec.imag[..., 0] = 0
+    spec.imag[..., -1] = 0
+    R, F = int(spec.shape[0]), int(spec.shape[1])
+    fr = torch.fft.irfft(spec, n=n_fft, dim=-1) * w
+    y = torch.nn.functional.fold(fr.transpose(1, 2), (1, (F - 1) * hop + n_fft), (1, n_fft), stride=(1, hop)).reshape(R, -1)
+    y = torch.nn.functional.pad(y, (0, max(0, lead + T - y.shape[1])))[:, lead:lead + T]
+    live = ws >= 1e-8
+    return torch.where(live, y / torch.where(live, ws, torch.ones_like(ws)).to(y.dtype), torch.zeros_like(y))
+
+
+def _gl_unit(t):
+    """unit(t) of include/wun.h in t's precision: scaled by max(|Re|, |Im|), unit(0) = 1, NaN stays NaN."""
+    re, im = t.real, t.imag
+    zero = (re == 0) & (im == 0)
+    s = torch.where(zero, torch.ones_like(re), torch.maximum(re.abs(), im.abs()))
+    s = torch.where(torch.isnan(re) | torch.isnan(im), torch.full_like(s, float("nan")), s)
+    a, b = re / s, im / s
+    n = torch.sqrt(a * a + b * b)
+    return torch.complex(torch.where(zero, torch.ones_like(a), a / n), torch.where(zero, torch.zeros_like(b), b / n))
+
+
+def griffin_lim_torch(mag, c0, y0, T, n_fft, hop, lead, iterations, momentum=0.0, dtype=torch.float32):
+    """The definition of wun_griffin_lim (include/wun.h) in plain torch, in `dtype`: mag [R, F, K], exactly one of c0 (complex
+    [R, F, K]) and y0 ([R, T]).  Returns (y [R, T], inconsistency float64 [iterations, 2]).  What griffin_lim runs on CPU
+    tensors, and the tests' float32 stand-in."""
+    cdtype = torch.complex64 if dtype == torch.float32 else torch.complex128
+    mag = mag.to(dtype)
+    R, F, K = (int(v) for v in mag.shape)
+    w = _gl_window(n_fft, dtype, mag.device)
+    ws = _gl_window_sums(T, n_fft, hop, lead, F, mag.device)
+    inc = torch.full((iterations, 2), float("nan"), dtype=torch.float64)
+    y = None if y0 is None else y0.to(dtype)
+    prev = None
+    for i in range(iterations):
+        if i == 0 and c0 is not None:
+            c = c0.to(cdtype).clone()
+            c.imag[..., 0] = 0
+            c.imag[..., -1] = 0
+        else:
+            c = _gl_stft(y, n_fft, hop, lead, F, w)
+            m64 = mag.to(torch.float64)
+            inc[i, 0] = ((c.to(torch.complex128).abs() - m64) ** 2).sum()
+            inc[i, 1] = (m64 * m64).sum()
+        t = c if (momentum == 0.0 or prev is None) else c + float(momentum) * (c - prev)
+        prev = c
+        u = _gl_unit(t)
+        y = _gl_istft(torch.complex(mag * u.real, mag * u.imag), T, n_fft, hop, lead, w, ws)
+    return y, inc
+
+
+def griffin_lim_call(mag, init_re, init_im, y_init, T, n_fft, hop, lead, iterations, momentum=0.0, y=None, inconsistency=None,
+                     scratch=None):
+    """wun_griffin_lim on device tensors: mag (and init_re / init_im) float32 [R, F, K], y_init [R, T]; rows as S = R, B = C = 1.
+    y, inconsistency (float64 [iterations, 2] or None) and scratch are the caller's or allocated here.  Returns y [R, T]."""
+    lib = _lib.load()
+    R, F, K = (int(v) for v in mag.shape)
+    dev = mag.device
+    if scratch is None:
+        n = int(lib.wun_griffin_lim_scratch_floats(R, 1, int(T), 1, int(n_fft), int(hop), int(lead), F, int(momentum != 0.0)))
+        if n < 0:
+            _lib.check(n)
+        scratch = torch.empty(n, dtype=torch.float32, device=dev)
+    if y is None:
+        y = torch.empty((R, int(T)), dtype=torch.float32, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.wun_griffin_lim(ptr(mag), ptr(init_re), ptr(init_im), ptr(y_init), R, 1, int(T), 1, int(n_fft), int(hop),
+                                       int(lead), F, int(iterations), float(momentum), _fft_table(n_fft, dev).data_ptr(), ptr(y),
+                                       ptr(inconsistency), ptr(scratch), _stream(dev)))
+    return y
+
+
+def griffin_lim_default_length(F, n_fft, hop, centered=True):
+    """The longest track whose framing has F frames: F hop - (n_fft - hop) centred, (F - 1) hop + n_fft otherwise."""
+    return int(F) * int(hop) - (int(n_fft) - int(hop)) if centered else (int(F) - 1) * int(hop) + int(n_fft)
+
+
+def griffin_lim(mag, n_fft, hop, iterations=10, init=None, length=None, centered=True, momentum=0.0, generator=None,
+                return_inconsistency=False):
+    """Audio [..., length] whose STFT magnitude approaches mag [..., F, K]: Griffin-Lim's alternating projections
+    (wun_griffin_lim, include/wun.h; the reference's Utils.reconPhase), n_fft a power of two in 64..8192.
+
+    init: an (re, im) pair of mag's shape -- the initial spectrum, e.g. a mix's (its phase is what counts) --, an audio tensor
+    [..., length], or None: the reference's random start, the spectrum U[0, 1) + i U[-pi, pi) (Utils.py:163 takes its angle),
+    drawn with torch on mag's device from `generator`.  length=None: the longest track with F frames in the chosen framing
+    (centered as spectral.stft).  momentum in [0, 1): 0 is the plain iteration, 0.99 the usual accelerated one (Perraudin et al.).
+    return_inconsistency: also a float64 [iterations, 2] tensor of sum (|STFT(y_{i-1})| - mag)^2 and sum mag^2 per iteration
+    (NaN for an iteration that started from a given spectrum); sqrt of their ratio is the spectral convergence.
+
+    On the GPU one library call, no host sync.  On CPU tensors the same definition in plain float32 torch (griffin_lim_torch).
+    The inverse is wun_istft's (window-square-normalised).  Not differentiable."""
+    if not torch.is_tensor(mag) or mag.dim() < 2:
+        raise ValueError("mag must be a tensor [..., F, K]")
+    n_fft, hop, iterations, momentum = int(n_fft), int(hop), int(iterations), float(momentum)
+    F, K = int(mag.shape[-2]), int(mag.shape[-1])
+    if K != n_fft // 2 + 1:
+        raise ValueError("mag has %d bins, expected n_fft / 2 + 1 = %d" % (K, n_fft // 2 + 1))
+    if iterations < 1:
+        raise ValueError("iterations must be at least 1, got %d" % iterations)
+    if not (0.0 <= momentum < 1.0):
+        raise ValueError("momentum must lie in [0, 1), got %r" % (momentum,))
+    T = griffin_lim_default_length(F, n_fft, hop, centered) if length is None else int(length)
+    if T < 1:
+        raise ValueError("no sample is covered: %d frames of %d / %d" % (F, n_fft, hop))
+    lead, want = _framing(T, n_fft, hop, centered, "fft")
+    if want != F:
+        raise ValueError("mag has %d frames, length %d has %d in this framing" % (F, T, want))
+    batch = tuple(mag.shape[:-2])
+    dev = mag.device
+    m = mag.to(torch.float32).reshape(-1, F, K).contiguous()
+    init_re = init_im = y_init = None
+    if init is None:
+        init_re = torch.rand(m.shape, generator=generator, dtype=torch.float32, device=dev)
+        init_im = (torch.rand(m.shape, generator=generator, dtype=torch.float32, device=dev) * 2.0 - 1.0) * float(np.pi)
+    elif isinstance(init, (tuple, list)):
+        if len(init) != 2 or any((not torch.is_tensor(t)) or t.shape != mag.shape or t.device != dev for t in init):
+            raise ValueError("init must be an (re, im) pair of mag's shape and device")
+        init_re, init_im = (t.to(torch.float32).reshape(-1, F, K).contiguous() for t in init)
+    elif torch.is_tensor(init):
+        if tuple(init.shape) != batch + (T,) or init.device != dev:
+            raise ValueError("an audio init must be %s on mag's device, got %s" % (list(batch + (T,)), tuple(init.shape)))
+        y_init = init.to(torch.float32).reshape(-1, T).contiguous()
+    else:
+        raise ValueError("init must be None, an (re, im) pair or an audio tensor")
+    if m.is_cuda:
+        inc = torch.empty((iterations, 2), dtype=torch.float64, device=dev) if return_inconsistency else None
+        y = griffin_lim_call(m, init_re, init_im, y_init, T, n_fft, hop, lead, iterations, momentum, inconsistency=inc)
+    else:
+        c0 = None if init_re is None else torch.complex(init_re, init_im)
+        y, inc = griffin_lim_torch(m, c0, y_init, T, n_fft, hop, lead, iterations, momentum)
+    y = y.reshape(batch + (T,))
+    return (y, inc) if return_inconsistency else y

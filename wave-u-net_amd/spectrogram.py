@@ -25,6 +25,10 @@ Any other loss, on magnitudes, audio or both (wun_spec_backward,
     sep.adam_step(lr)                                              # or sep.update_moving_averages() beside another optimizer
     net = sep.module("audio")                                      # SpecUNet, a torch.nn.Module: net(mix) under torch.autograd
 
+Audio from the magnitudes with a refined phase (wun_griffin_lim):
+
+    audio = sep.reconstruct(mags, mix, iterations=10)              # Griffin-Lim from the mix's phase, {source: [B, T, 1]}
+
 Not built (NotImplementedError): get_output's own audio at training=True (ask audio_output() for it), the gradient with respect
 to the mix, stereo, any source count but two (the reference asserts both, :24-25) and a bf16 mode.
 model_config["spec_frame_len"] / ["spec_hop"] (extension keys, defaults 1024 / 768) let tests run small geometries;
@@ -287,6 +291,34 @@ class UnetSpectrogramSeparator(object):
         B, T = self._last_train
         out = self._train_audio(B, T, torch.empty((len(self.source_names), B, T, 1), dtype=torch.float32, device=self._dev()))
         return {name: out[i] for i, name in enumerate(self.source_names)}
+
+    def reconstruct(self, mags, mix, iterations, momentum=0.0):
+        """{source: [B, T, 1]} audio from source magnitudes `mags` ({source: [B, F, K]} or stacked [S, B, F, K], e.g. what
+        get_output(mix, False, return_spectrogram=True) returned) by `iterations` Griffin-Lim iterations in the network's framing
+        (lead 0) from the spectrum of `mix` [B, T, 1] -- the reference's spectrogramToAudioFile(.., phase=mix_phase,
+        phaseIterations=N), Utils.py:125-173; spectral.griffin_lim, DESIGN.md 5.21.  mask X with the mix's phase is not the STFT
+        of any signal; the iterations move the phase until magnitude and phase agree better.  The mix's spectrum is taken again
+        here (one launch of the transform the network ran: the same bits).  The inverse is wun_istft's, normalised by the
+        window-square sum over the covering frames -- not inverse_stft_window_fn's steady-state sum, so the audio differs from
+        get_output's at the clip's edges even before the phase moves."""
+        if isinstance(mags, dict):
+            mags = torch.stack([torch.as_tensor(mags[n]) for n in self.source_names])
+        if not torch.is_tensor(mix):
+            mix = torch.as_tensor(np.asarray(mix, dtype=np.float32))
+        if mix.dim() != 3 or mix.shape[2] != 1:
+            raise ValueError("mix must be [batch, samples, 1] (mono), got %s" % (tuple(mix.shape),))
+        B, T = int(mix.shape[0]), int(mix.shape[1])
+        S, K = len(self.source_names), self.frame_len // 2 + 1
+        F = self.frames(T)
+        dev = self._dev()
+        mags = torch.as_tensor(mags).to(device=dev, dtype=torch.float32)
+        if tuple(mags.shape) != (S, B, F, K):
+            raise ValueError("mags must be [%d, %d, %d, %d], got %s" % (S, B, F, K, tuple(mags.shape)))
+        x = mix.to(device=dev, dtype=torch.float32).reshape(1, B, T, 1).contiguous()
+        re, im = spectral.stft(x, self.frame_len, self.hop, centered=False, transform="fft")           # [1, B, 1, F, K]
+        init = tuple(t.reshape(1, B, F, K).expand(S, B, F, K).contiguous() for t in (re, im))
+        y = spectral.griffin_lim(mags, self.frame_len, self.hop, iterations, init=init, length=T, centered=False, momentum=momentum)
+        return {name: y[i].unsqueeze(-1) for i, name in enumerate(self.source_names)}
 
     def _upstream(self, g, what, shape):
         if g is None:
