@@ -944,6 +944,43 @@ int wun_scatter_windows(const wun_plan* plan, const float* outputs, const int64_
 int wun_separate_track(const wun_plan* plan, const float* params, const float* track_tc, int64_t n_frames,
                        float* workspace, float* outputs, float* preds, void* stream);
 
+/* ---- training batches from resident tracks (Datasets.py:29-34, Utils.py:26-42) --------------
+ * One batch of the reference's snippet pipeline, and the source-level augmentations around it, in one kernel: the sources of
+ * a data set live on the device as S planes [plane_frames, C] (the zero-padded tracks one behind the other) and, with
+ * mix_mode 0, a mix plane of the same shape.  Row b of the batch reads the window of Tin frames at desc[b][s].start of
+ * plane s:
+ *   a_s[t][c]        = gain_s * x_s[start_s + t][c']     c' = the other channel with flag bit 0, sign flipped with bit 1
+ *   targets[s][b]    = a_s[pad .. pad + Tout),           pad = (Tin - Tout) / 2 (Utils.crop_sample)
+ *   mix[b]           = ((a_0 + a_1) + a_2) + ...         mix_mode 1 (Utils.random_amplify's re-summed mix)
+ *                    = mix_plane[start_0 .. start_0 + Tin)   mix_mode 0 (the targets still get their gains and flags)
+ * The product is one float32 multiplication rounded on its own and every addition is rounded (no fused multiply-add), so the
+ * batch is bit-identical to the host pipeline's; with gain == 1.0f a source's bits pass through unchanged (negative zero,
+ * denormals and NaN payloads included).  Sources of one row may start at different frames (independent remix).
+ * Every buffer is the caller's; nothing allocates device memory, copies from the host or synchronises: the descriptor
+ * table travels by value in the kernel arguments, WUN_SNIPPET_ROWS rows per launch (a larger batch is several launches on
+ * `stream`).  Every argument check runs before any GPU work.  Nothing outside a window is read; a window may start at any
+ * frame (no alignment beyond a float's). */
+typedef struct wun_snippet_source {   /* one source of one batch row; 16 bytes */
+    int64_t  start;   /* first frame of the window inside that source's plane */
+    float    gain;    /* multiplies every sample */
+    uint32_t flags;   /* bit 0: swap the two channels (C == 2 only); bit 1: negate */
+} wun_snippet_source;
+#define WUN_SNIPPET_SWAP 1u
+#define WUN_SNIPPET_NEGATE 2u
+#define WUN_SNIPPET_ROWS 24           /* batch rows per launch: 24 rows x 8 sources x 16 bytes = 3 KB of kernel arguments */
+int32_t wun_snippet_abi_size(void);   /* sizeof(wun_snippet_source) */
+
+/*   planes      : HOST array of S device pointers, each [plane_frames, C]
+ *   mix_plane   : device [plane_frames, C], or NULL with mix_mode 1
+ *   desc        : HOST, [B][S] (copied into the launches; free to reuse after the call returns)
+ *   mix_out     : device [B, Tin, C];  targets_out : device [S, B, Tout, C]
+ * WUN_ERR_INVALID for a null required pointer (mix_plane with mix_mode 0 included), mix_mode outside {0, 1}, C outside
+ * {1, 2}, the swap flag with C == 1, S outside 1..8, B < 1, Tout > Tin, an odd Tin - Tout, Tout < 1, a window outside
+ * [0, plane_frames], unknown flag bits, a plane or an output that is not 4-byte aligned. */
+int wun_gather_snippets(const float* const* planes, const float* mix_plane, int64_t plane_frames, int32_t C, int32_t S,
+                        int32_t B, int64_t Tin, int64_t Tout, const wun_snippet_source* desc, int32_t mix_mode,
+                        float* mix_out, float* targets_out, void* stream);
+
 /* ---- the spectrogram U-Net baseline, inference only ------------------------
  * The reference's other separator (Models/UnetSpectrogramSeparator.py:40-108, configs unet_spectrogram / unet_spectrogram_l1)
  * at training = False: per source one U-Net of 5 x 5 stride-2 convolutions over log1p of the mixture's STFT magnitude, whose

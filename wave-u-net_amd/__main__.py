@@ -30,6 +30,10 @@ Griffin-Lim iterations from the mix's phase (the reference's spectrogramToAudioF
 phase; the refined audio is normalised by the window-square sum over the covering frames.  Absent or 0: the default audio output.
 `train` takes the spectral objective as `model_config.spectral_loss={"resolutions":[[4096,1024]],"transform":"fft","terms":{"sc":1,
 "log_mag_l1":1},"log_eps":4.0}`: `"transform":"fft"` lifts the loss's n_fft limit from 2048 to 8192 in the same way ("gemm" is the default).
+`train` and `test` take `model_config.data_producer=fused` to produce their batches with one HIP kernel out of tracks resident in
+HBM (datasets.FusedSnippetSource; the default "torch" keeps the torch-operator / host producers -- the batches are the same), and
+`train` then takes `model_config.augment={"remix":0.5,"channel_swap":0.5,"polarity":0.5}` (any subset; probabilities) for the
+source-level augmentations: stems remixed across songs, channels swapped, polarity inverted, per source.
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
 1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
 source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.

@@ -52,6 +52,13 @@ class WunSpecTrainConfig(C.Structure):
     _fields_ = [("bn_decay", C.c_float), ("dropout_rate", C.c_float), ("dropout_seed", C.c_int64)]
 
 
+class WunSnippetSource(C.Structure):
+    _fields_ = [("start", C.c_int64), ("gain", C.c_float), ("flags", C.c_uint32)]
+
+
+SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2                 # wun_snippet_source.flags
+SNIPPET_ROWS = 24                                   # WUN_SNIPPET_ROWS: batch rows per launch of wun_gather_snippets
+
 SPEC_TT_Z, SPEC_TT_MEAN, SPEC_TT_VAR, SPEC_TT_ACT, SPEC_TT_DROPOUT = range(5)     # wun_spec_train_tensor kinds
 
 _P = C.c_void_p
@@ -222,6 +229,9 @@ _SIGS = {
     "wun_forward_windows": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, _P, _P, C.c_int, _P]),
     "wun_scatter_windows": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, _P, C.c_int64, _P]),
     "wun_separate_track": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "wun_snippet_abi_size": (C.c_int32, []),
+    "wun_gather_snippets": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int32,
+                                      _P, _P, _P]),
     "wun_op_conv1d": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     "wun_op_conv1d_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
     "wun_op_conv1d_wgrad": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
@@ -288,6 +298,9 @@ def load():
     if lib.wun_mel_abi_size() != C.sizeof(WunMelTerms):
         raise RuntimeError("libwun.so wun_mel_terms size %d != this binding's %d (stale library or binding)" % (
             lib.wun_mel_abi_size(), C.sizeof(WunMelTerms)))
+    if lib.wun_snippet_abi_size() != C.sizeof(WunSnippetSource):
+        raise RuntimeError("libwun.so wun_snippet_source size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_snippet_abi_size(), C.sizeof(WunSnippetSource)))
     _lib = lib
     return lib
 

@@ -1,5 +1,5 @@
 // Internal: device helpers shared by the kernel units (wun_kernels, wun_elementwise, wun_bf16, wun_wgrad_bf16,
-// wun_wgrad_win, wun_narrow).  Host units include wun_internal.h only.  gfx950 only.
+// wun_wgrad_win, wun_narrow, wun_track, wun_dataset).  Host units include wun_internal.h only.  gfx950 only.
 #pragma once
 #include "wun_internal.h"
 
@@ -50,6 +50,35 @@ template <typename ET> __device__ __forceinline__ void st4(ET* p, long long i, f
 template <> __device__ __forceinline__ void st4<float>(float* p, long long i, f32x4 v) { *reinterpret_cast<f32x4*>(p + i) = v; }
 template <> __device__ __forceinline__ void st4<bf16_t>(bf16_t* p, long long i, f32x4 v) {
     *reinterpret_cast<u32x2*>(p + i) = (u32x2){bf_pack2(v[0], v[1]), bf_pack2(v[2], v[3])};
+}
+
+// ---- windows that start at any float of a plane (wun_track.hip, wun_dataset.hip) ----
+// p[i .. i + 3] where p + i - M is 16-byte aligned (0 <= M < 4); floats outside [lo, hi) read as 0 and are not touched
+template <int M>
+__device__ __forceinline__ f32x4 ld4_window(const float* __restrict__ p, long long i, long long lo, long long hi) {
+    constexpr int NG = M ? 2 : 1;
+    float f[4 * NG];
+#pragma unroll
+    for (int j = 0; j < NG; ++j) {
+        const long long a = i - M + 4 * j;
+        if (a >= lo && a + 4 <= hi) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(p + a);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) f[4 * j + r] = v[r];
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long k = a + r;
+                const bool need = 4 * j + r >= M && 4 * j + r < M + 4;
+                f[4 * j + r] = (need && k >= lo && k < hi) ? p[k] : 0.f;
+            }
+        }
+    }
+    return (f32x4){f[M], f[M + 1], f[M + 2], f[M + 3]};
+}
+
+__device__ __forceinline__ int granule_offset(const float* p, long long i) {
+    return (int)(((long long)(reinterpret_cast<uintptr_t>(p) >> 2) + i) & 3);
 }
 
 // ---- gradient accumulation (wun_*backward_accumulate) ----

@@ -26,34 +26,7 @@
 
 namespace wun {      // the kernels carry the library's wun:: prefix in profiler output
 
-// p[i .. i + 3] where p + i - M is 16-byte aligned (0 <= M < 4); floats outside [lo, hi) read as 0 and are not touched
-template <int M>
-__device__ __forceinline__ f32x4 ld4_window(const float* __restrict__ p, long long i, long long lo, long long hi) {
-    constexpr int NG = M ? 2 : 1;
-    float f[4 * NG];
-#pragma unroll
-    for (int j = 0; j < NG; ++j) {
-        const long long a = i - M + 4 * j;
-        if (a >= lo && a + 4 <= hi) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(p + a);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) f[4 * j + r] = v[r];
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long long k = a + r;
-                const bool need = 4 * j + r >= M && 4 * j + r < M + 4;
-                f[4 * j + r] = (need && k >= lo && k < hi) ? p[k] : 0.f;
-            }
-        }
-    }
-    return (f32x4){f[M], f[M + 1], f[M + 2], f[M + 3]};
-}
-
-__device__ __forceinline__ int granule_offset(const float* p, long long i) {
-    return (int)(((long long)(reinterpret_cast<uintptr_t>(p) >> 2) + i) & 3);
-}
-
+// (ld4_window / granule_offset, the reads of a window that starts at any float: wun_device.h)
 struct GatherArgs {
     const float* track; float* dst;          // dst: NCW row 0 of the launch's first batch row
     long long pos[WUN_TRACK_ROWS];           // first frame of the row's window; < 0: a row of zeros

@@ -12,7 +12,9 @@ stores per song, :57-90).  get_dataset() reproduces the reference's stream of ba
   batches of batch_size, remainder dropped                                     (:215)
 on the host in numpy.  DeviceSnippetSource is the MI355X-first producer for training: every padded
 track lives in HBM (a full MUSDB train set at 22 kHz mono fp32 is ~4 GB of 288 GB), and a batch
-is one gather + gain + sum + crop on the GPU, so the input side keeps up with a ~10 ms step.
+is one gather + gain + sum + crop on the GPU, so the input side keeps up with a ~10 ms step.  FusedSnippetSource is
+the same producer as ONE HIP kernel per batch (wun_gather_snippets), which also carries the source-level augmentations
+the reference lacks: independent remix, channel swap, polarity (augmented_descriptors).
 
 Decoding MUSDB stems (musdb, soundfile in the reference, Datasets.py:119-186) is out of scope: tracks come from WAV
 (scipy) or .npy files, at model_config["expected_sr"] or -- with resample=True -- at any rate (resample.py).
@@ -309,3 +311,175 @@ class DeviceSnippetSource(object):
             mix = self.data["mix"][idx]
         targets = srcs[:, :, self.pad:self.t_in - self.pad, :] if self.pad > 0 else srcs
         return mix.contiguous(), targets.contiguous()
+
+
+# --------------------------------------------------------------------------------------
+# the fused producer: descriptors with source-level augmentations, one gather kernel per batch
+# --------------------------------------------------------------------------------------
+# one source of one batch row: wun_snippet_source of include/wun.h (start in frames of the source's plane)
+SNIPPET_DTYPE = np.dtype([("start", np.int64), ("gain", np.float32), ("flags", np.uint32)])
+SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2
+AUGMENT_KEYS = ("remix", "channel_swap", "polarity")
+
+
+def check_augment(model_config, augment):
+    """{key: probability} of the active augmentations (probability > 0).  ValueError for an unknown key, a probability
+    outside [0, 1] (NaN included) and channel_swap on a mono config."""
+    if augment is None:
+        return {}
+    if not isinstance(augment, dict):
+        raise ValueError("augment must be a dict with the optional keys %s, got %r" % (", ".join(AUGMENT_KEYS), augment))
+    active = {}
+    for key, p in augment.items():
+        if key not in AUGMENT_KEYS:
+            raise ValueError("unknown augmentation %r (have: %s)" % (key, ", ".join(AUGMENT_KEYS)))
+        if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("augment[%r] must be a probability in [0, 1], got %r" % (key, p))
+        if float(p) > 0.0:
+            active[key] = float(p)
+    if "channel_swap" in active and model_config["mono_downmix"]:
+        raise ValueError("augment['channel_swap'] needs two channels; this config is mono (mono_downmix=True)")
+    return active
+
+
+def augmented_descriptors(model_config, lengths, input_frames, output_frames, rng, augment=None, aug_rng=None):
+    """snippet_descriptors(..., "train", rng) -- the unchanged stream, shuffle buffer included -- as the tables of
+    wun_gather_snippets, with the source-level augmentations drawn on top.  Yields (rec, mix_mode) per snippet: rec is a
+    SNIPPET_DTYPE array [S] of (plane offset of the track + start, gain, flags), the planes being the padded tracks one behind
+    the other (`lengths` in order); mix_mode 1 = the mix is the sum of the delivered sources, 0 = the track's own mix.
+      augment empty : exactly the base stream -- every source at the base (track, start), the base gains (else 1.0), flags 0,
+                      mix_mode 1 iff the base stream carried gains (model_config["augmentation"])
+      augment       : {"remix": p, "channel_swap": p, "polarity": p}, each optional.  remix -- with probability p every source
+                      s >= 1 comes from a track and a start of its own (source 0 keeps the base position): the stems of different
+                      songs mixed; channel_swap / polarity -- per source, with probability p the two channels change places / the
+                      sign flips.  Next to the reference's per-source gain (Utils.py:26-36).  Any active one makes mix_mode 1.
+    The draws come from aug_rng (default np.random.default_rng([1337, 1]); FusedSnippetSource passes [seed, 1]), never from
+    rng, so the base stream does not shift.  Only keys with a probability > 0 draw, in this order per snippet: one uniform for
+    remix; if taken, per source s >= 1 a track (integers(0, n_tracks)) then a start (integers(0, len - Tin)); one uniform per
+    source for the swap; one uniform per source for the polarity."""
+    active = check_augment(model_config, augment)
+    S = len(model_config["source_names"])
+    n_tracks = len(lengths)
+    offset = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))[:-1]]).astype(np.int64)
+    if active and aug_rng is None:
+        aug_rng = np.random.default_rng([1337, 1])
+    for ti, pos, gains in snippet_descriptors(model_config, lengths, input_frames, output_frames, "train", rng):
+        rec = np.zeros(S, dtype=SNIPPET_DTYPE)
+        rec["start"] = offset[ti] + pos
+        rec["gain"] = gains if gains is not None else 1.0
+        if "remix" in active and aug_rng.random() < active["remix"]:
+            for s in range(1, S):
+                tj = int(aug_rng.integers(0, n_tracks))
+                rec["start"][s] = offset[tj] + int(random_positions(lengths[tj], input_frames, None, aug_rng))
+        if "channel_swap" in active:
+            for s in range(S):
+                if aug_rng.random() < active["channel_swap"]:
+                    rec["flags"][s] |= SNIPPET_SWAP
+        if "polarity" in active:
+            for s in range(S):
+                if aug_rng.random() < active["polarity"]:
+                    rec["flags"][s] |= SNIPPET_NEGATE
+        yield rec, int(gains is not None or bool(active))
+
+
+class FusedSnippetSource(object):
+    """DeviceSnippetSource's batches from ONE kernel (wun_gather_snippets, csrc/wun_dataset.hip): the same residency -- the
+    padded tracks one behind the other, one plane per key, in HBM -- and per batch a table of B x S descriptors (16 bytes
+    each) that travels in the kernel arguments: no index tensor, no host-to-device copy, no intermediate.  Calling the object
+    returns (mix [B,Tin,C], targets [S,B,Tout,C]) as fresh tensors, written on the current stream.
+
+    partition "train": endless; augmented_descriptors' stream -- without `augment` bit-identical to get_dataset(..., "train",
+    ...) and DeviceSnippetSource for equal seeds; with it the remix / channel-swap / polarity augmentations on top (draws from
+    np.random.default_rng([seed, 1])).  Any other partition: a finite iterator over every hop of every track in order, the
+    remainder dropped -- the batches of get_dataset(..., partition, ...); a call behind the last batch raises StopIteration.
+    descriptors() shows the next batch's table without touching the GPU."""
+
+    def __init__(self, model_config, tracks, input_frames, output_frames, batch_size, device, seed=1337, rng=None,
+                 augment=None, partition="train"):
+        import torch
+        self.cfg = model_config
+        self.names = list(model_config["source_names"])
+        self.t_in, self.t_out = int(input_frames), int(output_frames)
+        if self.t_out > self.t_in or (self.t_in - self.t_out) % 2 != 0:
+            raise ValueError("input_frames - output_frames must be even and >= 0")
+        self.pad = (self.t_in - self.t_out) // 2
+        self.batch = int(batch_size)
+        self.device = torch.device(device)
+        self.partition = partition
+        active = check_augment(model_config, augment)
+        if active and partition != "train":
+            raise ValueError("augment applies to the train partition only")
+        if self.device.type != "cuda":
+            raise RuntimeError("FusedSnippetSource gathers its batches with a HIP kernel; there is no CPU fallback "
+                               "(got device %s)" % self.device)
+        from . import _lib
+        self._lib_mod, self._lib = _lib, _lib.load()
+        lens, cat = [], {k: [] for k in self.names + ["mix"]}
+        for t in tracks:
+            p = pad_track(t, self.pad)
+            n = p["mix"].shape[0]
+            if n <= self.t_in:
+                raise ValueError("track shorter than the network input")
+            lens.append(n)
+            for k in cat:
+                cat[k].append(p[k])
+        self.channels = int(cat["mix"][0].shape[1])
+        self.plane_frames = int(sum(lens))
+        self.data = {k: torch.from_numpy(np.concatenate(v)).to(self.device) for k, v in cat.items()}
+        self._planes = (_lib.C.c_void_p * len(self.names))(*[self.data[k].data_ptr() for k in self.names])
+        rng = rng if rng is not None else np.random.default_rng(seed)
+        if partition == "train":
+            self.mix_mode = int(bool(model_config["augmentation"]) or bool(active))
+            self.stream = augmented_descriptors(model_config, lens, self.t_in, self.t_out, rng, augment,
+                                                np.random.default_rng([seed, 1]))
+        else:
+            self.mix_mode = 0
+            self.stream = self._ordered(snippet_descriptors(model_config, lens, self.t_in, self.t_out, partition, rng), lens)
+        self._next = None
+
+    def _ordered(self, stream, lens):
+        offset = np.concatenate([[0], np.cumsum(np.asarray(lens, dtype=np.int64))[:-1]])
+        for ti, pos, _ in stream:
+            rec = np.zeros(len(self.names), dtype=SNIPPET_DTYPE)
+            rec["start"] = offset[ti] + pos
+            rec["gain"] = 1.0
+            yield rec, 0
+
+    def descriptors(self):
+        """The next batch's table, SNIPPET_DTYPE [B, S] (host only: nothing is launched).  StopIteration behind the last
+        whole batch of a finite partition."""
+        if self._next is None:
+            rows = []
+            for rec, _ in self.stream:
+                rows.append(rec)
+                if len(rows) == self.batch:
+                    break
+            if len(rows) < self.batch:                   # remainder dropped (batch_and_drop_remainder, Datasets.py:215)
+                raise StopIteration
+            self._next = np.ascontiguousarray(np.stack(rows))
+        return self._next
+
+    def gather(self, table, mix_mode):
+        """(mix, targets) of a SNIPPET_DTYPE table [B, S] through wun_gather_snippets, on the current stream."""
+        import torch
+        table = np.ascontiguousarray(table, dtype=SNIPPET_DTYPE)
+        B, S, C = int(table.shape[0]), len(self.names), self.channels
+        with torch.cuda.device(self.device):
+            mix = torch.empty((B, self.t_in, C), dtype=torch.float32, device=self.device)
+            targets = torch.empty((S, B, self.t_out, C), dtype=torch.float32, device=self.device)
+            self._lib_mod.check(self._lib.wun_gather_snippets(
+                self._planes, self.data["mix"].data_ptr(), self.plane_frames, C, S, B, self.t_in, self.t_out,
+                table.ctypes.data, int(mix_mode), mix.data_ptr(), targets.data_ptr(),
+                torch.cuda.current_stream(self.device).cuda_stream))
+        return mix, targets
+
+    def __call__(self):
+        table = self.descriptors()
+        self._next = None
+        return self.gather(table, self.mix_mode)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return self()

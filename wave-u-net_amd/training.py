@@ -5,8 +5,10 @@
 The reference feeds the step from a tf.data pipeline over MUSDB (Datasets.py); here
 `batch_source` is any callable returning (mix [B,Tin,C], targets [S,B,Tout,C]) GPU tensors
 honouring that pipeline's output contract (float32, mix = sum of sources, targets
-centre-cropped): datasets.DeviceSnippetSource for real tracks, `synthetic_source` for the
-benchmark.
+centre-cropped): datasets.DeviceSnippetSource for real tracks -- or datasets.FusedSnippetSource, the
+same batches from one HIP kernel plus the remix / channel-swap / polarity augmentations, selected
+by model_config["data_producer"] = "fused" and model_config["augment"] (validation._train_source)
+-- and `synthetic_source` for the benchmark.
 """
 import json
 import os

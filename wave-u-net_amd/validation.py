@@ -10,6 +10,12 @@ init_sup_sep_lr = 1e-5, then the test-partition loss of the best checkpoint.
 model_config["validation_metric"] = "si_sdr" (default "mse") scores every batch with the scale-invariant SDR of
 waveform.WaveformLoss (wun_waveform_loss) instead: test() then returns MINUS the mean SI-SDR in dB, so lower
 is still better and optimise() needs no other change.
+
+model_config["data_producer"] = "fused" (default "torch") takes the batches of train() and test() from
+datasets.FusedSnippetSource -- one HIP kernel per batch out of tracks resident in HBM (wun_gather_snippets)
+-- instead of DeviceSnippetSource's torch operators / the host pipeline of get_dataset: the same batches, bit for bit.
+model_config["augment"] = {"remix": p, "channel_swap": p, "polarity": p} (fused producer only; datasets.augmented_descriptors)
+adds the source-level augmentations to the training batches.
 """
 import json
 import os
@@ -30,6 +36,40 @@ def _load_checkpoint(separator, load_model):
     return load_checkpoint(separator, load_model, with_optimizer=False)
 
 
+PRODUCERS = ("torch", "fused")
+
+
+def data_producer(model_config):
+    """model_config.get("data_producer", "torch"), checked together with model_config.get("augment"): ValueError for an unknown
+    producer, for `augment` with the torch producer (it has no augmentations beyond the reference's gain) and for a bad
+    `augment` (datasets.check_augment)."""
+    producer = model_config.get("data_producer", "torch")
+    if producer not in PRODUCERS:
+        raise ValueError("data_producer must be one of %s, got %r" % (", ".join(PRODUCERS), producer))
+    augment = model_config.get("augment")
+    if augment is not None and producer != "fused":
+        raise ValueError("model_config['augment'] needs data_producer='fused' (the torch producer has no source-level augmentations)")
+    datasets.check_augment(model_config, augment)
+    return producer
+
+
+def _batches(model_config, producer, sep, in_shape, out_shape, partition, tracks):
+    """The partition's batches {source..., "mix"}: get_dataset's on the host, or -- "fused" -- the same batches gathered on the
+    separator's device from the tracks uploaded once."""
+    if producer != "fused":
+        return datasets.get_dataset(model_config, in_shape, out_shape, partition, tracks)
+    names = list(model_config["source_names"])
+    src = datasets.FusedSnippetSource(model_config, tracks, int(in_shape[1]), int(out_shape[1]), int(model_config["batch_size"]),
+                                      sep.device, partition=partition)
+
+    def gen():
+        for mix, targets in src:
+            batch = {key: targets[i] for i, key in enumerate(names)}
+            batch["mix"] = mix
+            yield batch
+    return gen()
+
+
 def test(model_config, partition, model_folder, load_model, tracks=None, data_root=None, separator=None,
          return_sums=False, resample=False):
     """Test.test(model_config, partition, model_folder, load_model) -> mean MSE.  The partition's
@@ -39,8 +79,11 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     model_config["validation_metric"] = "si_sdr": the per-batch loss is minus the mean SI-SDR (dB) over the batch's sources
     and excerpts, of the same inference-mode outputs (WaveformLoss({"si_sdr": 1}) with the eps and zero_mean of
     model_config["waveform_loss"], grad=False); the same running mean, and test.jsonl gains "metric" and the per-source dB.
-    ValueError for any other value but "mse"."""
+    ValueError for any other value but "mse".
+    model_config["data_producer"] = "fused": the batches come from a datasets.FusedSnippetSource(partition=...) on the separator's
+    device (the tracks are uploaded once per call) instead of the host pipeline; the same batches, the same loss."""
     metric = waveform.validation_metric(model_config)
+    producer = data_producer(model_config)
     if model_config["network"] not in ("unet", "unet_spectrogram"):
         raise NotImplementedError(model_config["network"])                        # Test.py:14-19
     # Test.py:34,63-68: the spectrogram U-Net with raw_audio_loss=False returns magnitudes, scored by their L1 distance to the
@@ -62,7 +105,7 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     names = list(model_config["source_names"])
     si_loss = waveform.validation_loss(model_config) if metric == "si_sdr" else None
     source_db = np.zeros(len(names))                                              # running means of the per-source dB
-    for batch in datasets.get_dataset(model_config, in_shape, out_shape, partition, tracks):
+    for batch in _batches(model_config, producer, sep, in_shape, out_shape, partition, tracks):
         outs = sep.get_output(batch["mix"], False, spec_l1)                       # Test.py:34
         if si_loss is not None:
             est = torch.stack([outs[key] for key in names])
@@ -228,8 +271,14 @@ def _rank0_test(model_config, partition, model_folder, load_model, tracks):
 
 def _train_source(model_config, tracks, seed):
     """Deferred constructor: train() builds the Trainer first (it fixes device and shapes), then
-    asks for the batch source."""
+    asks for the batch source: DeviceSnippetSource, or FusedSnippetSource with model_config["data_producer"] = "fused"
+    (and its model_config["augment"])."""
+    producer = data_producer(model_config)
+
     def make(trainer):
+        if producer == "fused":
+            return datasets.FusedSnippetSource(model_config, tracks, trainer.t_in, trainer.t_out, trainer.batch, trainer.device,
+                                               seed=seed + trainer.rank, augment=model_config.get("augment"))
         return datasets.DeviceSnippetSource(model_config, tracks, trainer.t_in, trainer.t_out, trainer.batch,
                                             trainer.device, seed=seed + trainer.rank)
     make.needs_trainer = True
