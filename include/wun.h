@@ -981,6 +981,41 @@ int wun_gather_snippets(const float* const* planes, const float* mix_plane, int6
                         int32_t B, int64_t Tin, int64_t Tout, const wun_snippet_source* desc, int32_t mix_mode,
                         float* mix_out, float* targets_out, void* stream);
 
+/* Speed perturbation (pitch and tempo together) inside the gather: a source of a row may be played at speed
+ * down / up, its window of Tin frames resampled while it is read from n_src = wun_speed_source_frames(Tin, up, down) frames
+ * of its plane.  The ratios come from a bank of up to WUN_SPEED_RATES entries, each with a device copy of
+ * wun_resample_design(up, down)'s phase-major table (K = ceil((2 half + 1) / up), half = 10 max(up, down)).  rate[b][s] = 0 is
+ * the unit rate, exactly wun_gather_snippets' path and bits; i >= 1 selects bank entry i - 1:
+ *   v[m][c]   = x_s[start_s + m][c']   for 0 <= m < n_src, +0 outside   (c' = the other channel with flag bit 0)
+ *   u = t down + half;  q = u / up;  p = u % up
+ *   r_s[t][c] = acc after  acc = fmaf(table[p K + k], v[q - k][c], acc)  for k = 0, 1, .., K - 1;  acc starts at +0
+ *   a_s[t][c] = gain_s * r_s[t][c]     (one rounded product, skipped when gain == 1.0f), sign flipped with flag bit 1
+ * which is bit for bit wun_resample(plane_s + start_s C, n_src, C, .., y_offset 0, n_out Tin, C, table, up, down) followed by the
+ * gain, swap and sign above.  Targets and mix as for wun_gather_snippets; nothing outside [start_s, start_s + n_src) is read.
+ * A rated source needs mix_mode 1 (with mix_mode 0 the mix plane would have to be resampled too). */
+#define WUN_SPEED_RATES 8             /* entries of a rate bank */
+#define WUN_SPEED_MAX_RATIO 64        /* ceiling on max(up, down) of an entry; and 1/2 <= down / up <= 2 */
+typedef struct wun_speed_bank {
+    int32_t      n;                        /* entries in use, 0..WUN_SPEED_RATES */
+    int32_t      up[WUN_SPEED_RATES];      /* positive, coprime with down, not 1/1 */
+    int32_t      down[WUN_SPEED_RATES];
+    const float* table[WUN_SPEED_RATES];   /* device: wun_resample_design(up, down)'s table, wun_resample_table_floats floats */
+} wun_speed_bank;
+int32_t wun_speed_abi_size(void);     /* sizeof(wun_speed_bank) */
+/* ((Tin - 1) down) / up + 1: the smallest n with wun_resample_frames(n, up, down) >= Tin.  Host only.  WUN_ERR_INVALID for
+ * Tin < 1 (or above 2^40) or a ratio that is not positive and coprime or is 1/1; WUN_ERR_UNSUPPORTED above the ceiling or
+ * outside [1/2, 2]. */
+int64_t wun_speed_source_frames(int64_t Tin, int32_t up, int32_t down);
+/*   rate : HOST uint8 [B][S], NULL = all unit;  bank : HOST, may be NULL when rate is NULL or all zero
+ * With all rates unit: wun_gather_snippets' bits in both mix modes.  WUN_ERR_INVALID for everything wun_gather_snippets refuses,
+ * a rate index above bank->n, a non-zero rate with a null bank or with mix_mode 0, bank->n outside 0..8, a ratio that is not
+ * positive and coprime or is 1/1, a table that is null or not 4-byte aligned, a rated window with start < 0 or start + n_src >
+ * plane_frames (unit windows keep the rule with Tin); WUN_ERR_UNSUPPORTED for a ratio above the ceiling or outside [1/2, 2].
+ * Every check runs before any GPU work.  WUN_SNIPPET_ROWS rows per launch, no intermediate, no atomics, no copy. */
+int wun_gather_snippets_speed(const float* const* planes, const float* mix_plane, int64_t plane_frames, int32_t C, int32_t S,
+                              int32_t B, int64_t Tin, int64_t Tout, const wun_snippet_source* desc, const uint8_t* rate,
+                              const wun_speed_bank* bank, int32_t mix_mode, float* mix_out, float* targets_out, void* stream);
+
 /* ---- the spectrogram U-Net baseline, inference only ------------------------
  * The reference's other separator (Models/UnetSpectrogramSeparator.py:40-108, configs unet_spectrogram / unet_spectrogram_l1)
  * at training = False: per source one U-Net of 5 x 5 stride-2 convolutions over log1p of the mixture's STFT magnitude, whose

@@ -56,7 +56,12 @@ class WunSnippetSource(C.Structure):
     _fields_ = [("start", C.c_int64), ("gain", C.c_float), ("flags", C.c_uint32)]
 
 
+class WunSpeedBank(C.Structure):
+    _fields_ = [("n", C.c_int32), ("up", C.c_int32 * 8), ("down", C.c_int32 * 8), ("table", C.c_void_p * 8)]
+
+
 SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2                 # wun_snippet_source.flags
+SPEED_RATES, SPEED_MAX_RATIO = 8, 64                # WUN_SPEED_RATES, WUN_SPEED_MAX_RATIO: the rate bank of wun_gather_snippets_speed
 SNIPPET_ROWS = 24                                   # WUN_SNIPPET_ROWS: batch rows per launch of wun_gather_snippets
 
 SPEC_TT_Z, SPEC_TT_MEAN, SPEC_TT_VAR, SPEC_TT_ACT, SPEC_TT_DROPOUT = range(5)     # wun_spec_train_tensor kinds
@@ -232,6 +237,10 @@ _SIGS = {
     "wun_snippet_abi_size": (C.c_int32, []),
     "wun_gather_snippets": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int32,
                                       _P, _P, _P]),
+    "wun_speed_abi_size": (C.c_int32, []),
+    "wun_speed_source_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_gather_snippets_speed": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P,
+                                            _P, C.c_int32, _P, _P, _P]),
     "wun_op_conv1d": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     "wun_op_conv1d_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
     "wun_op_conv1d_wgrad": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
@@ -301,6 +310,9 @@ def load():
     if lib.wun_snippet_abi_size() != C.sizeof(WunSnippetSource):
         raise RuntimeError("libwun.so wun_snippet_source size %d != this binding's %d (stale library or binding)" % (
             lib.wun_snippet_abi_size(), C.sizeof(WunSnippetSource)))
+    if lib.wun_speed_abi_size() != C.sizeof(WunSpeedBank):
+        raise RuntimeError("libwun.so wun_speed_bank size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_speed_abi_size(), C.sizeof(WunSpeedBank)))
     _lib = lib
     return lib
 

@@ -19,6 +19,7 @@ the reference lacks: independent remix, channel swap, polarity (augmented_descri
 Decoding MUSDB stems (musdb, soundfile in the reference, Datasets.py:119-186) is out of scope: tracks come from WAV
 (scipy) or .npy files, at model_config["expected_sr"] or -- with resample=True -- at any rate (resample.py).
 """
+import math
 import os
 
 import numpy as np
@@ -319,18 +320,56 @@ class DeviceSnippetSource(object):
 # one source of one batch row: wun_snippet_source of include/wun.h (start in frames of the source's plane)
 SNIPPET_DTYPE = np.dtype([("start", np.int64), ("gain", np.float32), ("flags", np.uint32)])
 SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2
-AUGMENT_KEYS = ("remix", "channel_swap", "polarity")
+AUGMENT_KEYS = ("remix", "channel_swap", "polarity", "speed")
+# the rate bank of wun_gather_snippets_speed (include/wun.h): (up, down) pairs, speed = down / up
+SPEED_RATES_DEFAULT = ((10, 9), (20, 19), (20, 21), (10, 11))      # speeds 0.9, 0.95, 1.05, 1.1
+SPEED_MAX_RATES, SPEED_MAX_RATIO = 8, 64                           # WUN_SPEED_RATES, WUN_SPEED_MAX_RATIO
+
+
+def speed_source_frames(input_frames, up, down):
+    """Source frames behind a window of input_frames played at speed down / up (wun_speed_source_frames): the smallest n
+    with resample.frames(n, up, down) >= input_frames."""
+    return ((int(input_frames) - 1) * int(down)) // int(up) + 1
+
+
+def _check_speed_rates(rates):
+    """The bank as a tuple of (up, down) reduced by their gcd; ValueError for what wun_gather_snippets_speed refuses."""
+    if isinstance(rates, (str, bytes, dict)) or not hasattr(rates, "__len__"):
+        raise ValueError("augment['speed_rates'] must be a list of [up, down] pairs, got %r" % (rates,))
+    if not 1 <= len(rates) <= SPEED_MAX_RATES:
+        raise ValueError("augment['speed_rates'] holds 1 to %d pairs, got %d" % (SPEED_MAX_RATES, len(rates)))
+    out = []
+    for pair in rates:
+        ok = not isinstance(pair, (str, bytes, dict)) and hasattr(pair, "__len__") and len(pair) == 2 and all(
+            isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v > 0 for v in pair)
+        if not ok:
+            raise ValueError("augment['speed_rates']: every pair is [up, down] of positive integers, got %r" % (pair,))
+        g = math.gcd(int(pair[0]), int(pair[1]))
+        up, down = int(pair[0]) // g, int(pair[1]) // g
+        if up == down:
+            raise ValueError("augment['speed_rates']: %r is the unit rate 1/1" % (pair,))
+        if max(up, down) > SPEED_MAX_RATIO or down > 2 * up or up > 2 * down:
+            raise ValueError("augment['speed_rates']: %r needs max(up, down) <= %d after reduction and a speed down / up in "
+                             "[1/2, 2]" % (pair, SPEED_MAX_RATIO))
+        if (up, down) in out:
+            raise ValueError("augment['speed_rates']: %r occurs twice (after reduction)" % (pair,))
+        out.append((up, down))
+    return tuple(out)
 
 
 def check_augment(model_config, augment):
-    """{key: probability} of the active augmentations (probability > 0).  ValueError for an unknown key, a probability
-    outside [0, 1] (NaN included) and channel_swap on a mono config."""
+    """{key: probability} of the active augmentations (probability > 0); with an active "speed" also "speed_rates": the bank
+    as a tuple of reduced (up, down) pairs (augment["speed_rates"], default SPEED_RATES_DEFAULT).  ValueError for an unknown
+    key, a probability outside [0, 1] (NaN included), channel_swap on a mono config, speed_rates without an active speed and
+    a bank the library would refuse (1/1, duplicates after reduction, more than 8 pairs, a ratio above 64 or outside [1/2, 2])."""
     if augment is None:
         return {}
     if not isinstance(augment, dict):
         raise ValueError("augment must be a dict with the optional keys %s, got %r" % (", ".join(AUGMENT_KEYS), augment))
     active = {}
     for key, p in augment.items():
+        if key == "speed_rates":
+            continue
         if key not in AUGMENT_KEYS:
             raise ValueError("unknown augmentation %r (have: %s)" % (key, ", ".join(AUGMENT_KEYS)))
         if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
@@ -339,6 +378,10 @@ def check_augment(model_config, augment):
             active[key] = float(p)
     if "channel_swap" in active and model_config["mono_downmix"]:
         raise ValueError("augment['channel_swap'] needs two channels; this config is mono (mono_downmix=True)")
+    if "speed" in active:
+        active["speed_rates"] = _check_speed_rates(augment.get("speed_rates", SPEED_RATES_DEFAULT))
+    elif "speed_rates" in augment:
+        raise ValueError("augment['speed_rates'] needs an active augment['speed'] (a probability > 0)")
     return active
 
 
@@ -356,21 +399,52 @@ def augmented_descriptors(model_config, lengths, input_frames, output_frames, rn
     The draws come from aug_rng (default np.random.default_rng([1337, 1]); FusedSnippetSource passes [seed, 1]), never from
     rng, so the base stream does not shift.  Only keys with a probability > 0 draw, in this order per snippet: one uniform for
     remix; if taken, per source s >= 1 a track (integers(0, n_tracks)) then a start (integers(0, len - Tin)); one uniform per
-    source for the swap; one uniform per source for the polarity."""
+    source for the swap; one uniform per source for the polarity.  An active "speed" is refused with a ValueError: its stream
+    carries a rate per source (speed_descriptors)."""
+    if "speed" in check_augment(model_config, augment):
+        raise ValueError("augment['speed'] needs the rate stream: use datasets.speed_descriptors, which yields (rec, mix_mode, rate)")
+    for rec, mix_mode, _ in _descriptors(model_config, lengths, input_frames, output_frames, rng, augment, aug_rng):
+        yield rec, mix_mode
+
+
+def speed_descriptors(model_config, lengths, input_frames, output_frames, rng, augment=None, aug_rng=None):
+    """augmented_descriptors with speed perturbation: yields (rec, mix_mode, rate) per snippet, rate a uint8 [S] of rate indices
+    for wun_gather_snippets_speed (0 = unit rate, i >= 1 = entry i - 1 of the bank check_augment returns as "speed_rates").
+    Without an active "speed" (rec, mix_mode) are exactly augmented_descriptors' and rate is zero.
+      augment["speed"] = p, augment["speed_rates"] = [[up, down], ...] (optional): with probability p the snippet is played at
+      a speed down / up of the bank -- pitch and tempo together.  A remixed snippet draws a rate per source; otherwise all
+      sources share one, so the stems of one song stay aligned.  An active speed makes mix_mode 1.
+    Draws (aug_rng only, after remix, swap and polarity): one random(); if taken, integers(0, R) per source s = 0..S-1 for a
+    remixed snippet, else one integers(0, R) for all.  Placement takes no draws: a rated source reads n_src =
+    speed_source_frames(Tin, up, down) frames of its padded track j (length len_j) around the centre of its unit window at
+    pos -- it starts at clip(pos + (Tin - n_src) // 2, 0, len_j - n_src) -- and a track shorter than n_src keeps the unit rate."""
+    return _descriptors(model_config, lengths, input_frames, output_frames, rng, augment, aug_rng)
+
+
+def _descriptors(model_config, lengths, input_frames, output_frames, rng, augment, aug_rng):
     active = check_augment(model_config, augment)
     S = len(model_config["source_names"])
     n_tracks = len(lengths)
     offset = np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))[:-1]]).astype(np.int64)
     if active and aug_rng is None:
         aug_rng = np.random.default_rng([1337, 1])
+    bank = active.get("speed_rates", ())
+    unit = np.zeros(S, dtype=np.uint8)                    # shared by every snippet at the unit rate (read-only)
+    unit.setflags(write=False)
     for ti, pos, gains in snippet_descriptors(model_config, lengths, input_frames, output_frames, "train", rng):
         rec = np.zeros(S, dtype=SNIPPET_DTYPE)
+        rate = unit
         rec["start"] = offset[ti] + pos
         rec["gain"] = gains if gains is not None else 1.0
-        if "remix" in active and aug_rng.random() < active["remix"]:
+        where = [(int(ti), int(pos))] * S if bank else None      # (track, start inside it) of every source: speed places by it
+        remixed = "remix" in active and aug_rng.random() < active["remix"]
+        if remixed:
             for s in range(1, S):
                 tj = int(aug_rng.integers(0, n_tracks))
-                rec["start"][s] = offset[tj] + int(random_positions(lengths[tj], input_frames, None, aug_rng))
+                p = int(random_positions(lengths[tj], input_frames, None, aug_rng))
+                rec["start"][s] = offset[tj] + p
+                if bank:
+                    where[s] = (tj, p)
         if "channel_swap" in active:
             for s in range(S):
                 if aug_rng.random() < active["channel_swap"]:
@@ -379,7 +453,20 @@ def augmented_descriptors(model_config, lengths, input_frames, output_frames, rn
             for s in range(S):
                 if aug_rng.random() < active["polarity"]:
                     rec["flags"][s] |= SNIPPET_NEGATE
-        yield rec, int(gains is not None or bool(active))
+        if "speed" in active and aug_rng.random() < active["speed"]:
+            if remixed:
+                picks = [int(aug_rng.integers(0, len(bank))) for _ in range(S)]
+            else:
+                picks = [int(aug_rng.integers(0, len(bank)))] * S
+            rate = np.zeros(S, dtype=np.uint8)
+            for s in range(S):
+                tj, p = where[s]
+                n_src = speed_source_frames(input_frames, *bank[picks[s]])
+                if lengths[tj] < n_src:
+                    continue                              # the track cannot fill the window at this speed: unit rate
+                rate[s] = picks[s] + 1
+                rec["start"][s] = offset[tj] + min(max(p + (input_frames - n_src) // 2, 0), lengths[tj] - n_src)
+        yield rec, int(gains is not None or bool(active)), rate
 
 
 class FusedSnippetSource(object):
@@ -389,8 +476,9 @@ class FusedSnippetSource(object):
     returns (mix [B,Tin,C], targets [S,B,Tout,C]) as fresh tensors, written on the current stream.
 
     partition "train": endless; augmented_descriptors' stream -- without `augment` bit-identical to get_dataset(..., "train",
-    ...) and DeviceSnippetSource for equal seeds; with it the remix / channel-swap / polarity augmentations on top (draws from
-    np.random.default_rng([seed, 1])).  Any other partition: a finite iterator over every hop of every track in order, the
+    ...) and DeviceSnippetSource for equal seeds; with it the remix / channel-swap / polarity / speed augmentations on top
+    (draws from np.random.default_rng([seed, 1])); with "speed" the batch comes from wun_gather_snippets_speed, which resamples
+    the rated sources inside the same launch (speed_descriptors; rates() shows the next batch's rate indices).  Any other partition: a finite iterator over every hop of every track in order, the
     remainder dropped -- the batches of get_dataset(..., partition, ...); a call behind the last batch raises StopIteration.
     descriptors() shows the next batch's table without touching the GPU."""
 
@@ -430,12 +518,24 @@ class FusedSnippetSource(object):
         rng = rng if rng is not None else np.random.default_rng(seed)
         if partition == "train":
             self.mix_mode = int(bool(model_config["augmentation"]) or bool(active))
-            self.stream = augmented_descriptors(model_config, lens, self.t_in, self.t_out, rng, augment,
-                                                np.random.default_rng([seed, 1]))
+            self.stream = speed_descriptors(model_config, lens, self.t_in, self.t_out, rng, augment,
+                                            np.random.default_rng([seed, 1]))
         else:
             self.mix_mode = 0
             self.stream = self._ordered(snippet_descriptors(model_config, lens, self.t_in, self.t_out, partition, rng), lens)
-        self._next = None
+        self._next = self._next_rates = None
+        # the rate bank of wun_gather_snippets_speed: one table per ratio, designed and uploaded once
+        self.speed_rates = active.get("speed_rates", ())
+        self._bank = None
+        self._unit_rates = np.zeros((self.batch, len(self.names)), dtype=np.uint8)
+        self._unit_rates.setflags(write=False)
+        if self.speed_rates:
+            from . import resample
+            self._tables = [torch.from_numpy(resample.design(up, down)).to(self.device) for up, down in self.speed_rates]
+            self._bank = _lib.WunSpeedBank()
+            self._bank.n = len(self.speed_rates)
+            for i, ((up, down), tab) in enumerate(zip(self.speed_rates, self._tables)):
+                self._bank.up[i], self._bank.down[i], self._bank.table[i] = up, down, tab.data_ptr()
 
     def _ordered(self, stream, lens):
         offset = np.concatenate([[0], np.cumsum(np.asarray(lens, dtype=np.int64))[:-1]])
@@ -443,40 +543,65 @@ class FusedSnippetSource(object):
             rec = np.zeros(len(self.names), dtype=SNIPPET_DTYPE)
             rec["start"] = offset[ti] + pos
             rec["gain"] = 1.0
-            yield rec, 0
+            yield rec, 0, np.zeros(len(self.names), dtype=np.uint8)
 
     def descriptors(self):
         """The next batch's table, SNIPPET_DTYPE [B, S] (host only: nothing is launched).  StopIteration behind the last
         whole batch of a finite partition."""
         if self._next is None:
-            rows = []
-            for rec, _ in self.stream:
+            rows, rates = [], []
+            for rec, _, rate in self.stream:
                 rows.append(rec)
+                rates.append(rate)
                 if len(rows) == self.batch:
                     break
             if len(rows) < self.batch:                   # remainder dropped (batch_and_drop_remainder, Datasets.py:215)
                 raise StopIteration
             self._next = np.ascontiguousarray(np.stack(rows))
+            # (without a bank every rate is the shared zero row: one table for all batches, nothing stacked)
+            self._next_rates = np.ascontiguousarray(np.stack(rates)) if self._bank is not None else self._unit_rates
         return self._next
 
-    def gather(self, table, mix_mode):
-        """(mix, targets) of a SNIPPET_DTYPE table [B, S] through wun_gather_snippets, on the current stream."""
+    def rates(self):
+        """The next batch's rate indices, uint8 [B, S] (0 = unit rate, i = speed_rates[i - 1]); all zero without an active
+        augment["speed"].  Host only, like descriptors(), and about the same batch."""
+        self.descriptors()
+        return self._next_rates
+
+    def gather(self, table, mix_mode, rates=None):
+        """(mix, targets) of a SNIPPET_DTYPE table [B, S] through wun_gather_snippets, on the current stream; with `rates`
+        (uint8 [B, S]) that hold a non-zero, through wun_gather_snippets_speed and this source's rate bank."""
         import torch
         table = np.ascontiguousarray(table, dtype=SNIPPET_DTYPE)
         B, S, C = int(table.shape[0]), len(self.names), self.channels
+        if rates is not None:
+            rates = np.ascontiguousarray(rates, dtype=np.uint8)
+            if rates.shape != (B, S):
+                raise ValueError("rates must be uint8 [B, S] = %r, got %r" % ((B, S), rates.shape))
+            if not rates.any():
+                rates = None
+            elif self._bank is None:
+                raise ValueError("a non-zero rate needs a source built with augment['speed']")
         with torch.cuda.device(self.device):
             mix = torch.empty((B, self.t_in, C), dtype=torch.float32, device=self.device)
             targets = torch.empty((S, B, self.t_out, C), dtype=torch.float32, device=self.device)
-            self._lib_mod.check(self._lib.wun_gather_snippets(
-                self._planes, self.data["mix"].data_ptr(), self.plane_frames, C, S, B, self.t_in, self.t_out,
-                table.ctypes.data, int(mix_mode), mix.data_ptr(), targets.data_ptr(),
-                torch.cuda.current_stream(self.device).cuda_stream))
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if rates is None:
+                self._lib_mod.check(self._lib.wun_gather_snippets(
+                    self._planes, self.data["mix"].data_ptr(), self.plane_frames, C, S, B, self.t_in, self.t_out,
+                    table.ctypes.data, int(mix_mode), mix.data_ptr(), targets.data_ptr(), stream))
+            else:
+                self._lib_mod.check(self._lib.wun_gather_snippets_speed(
+                    self._planes, self.data["mix"].data_ptr(), self.plane_frames, C, S, B, self.t_in, self.t_out,
+                    table.ctypes.data, rates.ctypes.data, self._lib_mod.C.addressof(self._bank), int(mix_mode), mix.data_ptr(),
+                    targets.data_ptr(), stream))
         return mix, targets
 
     def __call__(self):
         table = self.descriptors()
-        self._next = None
-        return self.gather(table, self.mix_mode)
+        rates = self._next_rates if self._bank is not None else None
+        self._next = self._next_rates = None
+        return self.gather(table, self.mix_mode, rates)
 
     def __iter__(self):
         return self

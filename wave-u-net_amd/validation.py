@@ -14,8 +14,8 @@ is still better and optimise() needs no other change.
 model_config["data_producer"] = "fused" (default "torch") takes the batches of train() and test() from
 datasets.FusedSnippetSource -- one HIP kernel per batch out of tracks resident in HBM (wun_gather_snippets)
 -- instead of DeviceSnippetSource's torch operators / the host pipeline of get_dataset: the same batches, bit for bit.
-model_config["augment"] = {"remix": p, "channel_swap": p, "polarity": p} (fused producer only; datasets.augmented_descriptors)
-adds the source-level augmentations to the training batches.
+model_config["augment"] = {"remix": p, "channel_swap": p, "polarity": p, "speed": p, "speed_rates": [[up, down], ...]} (fused
+producer only; datasets.speed_descriptors) adds the source-level augmentations to the training batches.
 """
 import json
 import os
