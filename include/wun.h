@@ -1303,6 +1303,94 @@ int wun_op_set_wgrad_win(int on);
  * shapes fail with WUN_ERR_UNSUPPORTED. */
 int wun_op_set_wgrad_narrow(int on);
 
+/* Test hook: what the plan asks of the last conv of a level (DESIGN.md "fused upsampling").  Every following stride-1
+ * wun_op_conv1d_ex launch also produces ups_y[b][c][0 .. ups_tup) = the 2x upsampling of its output y[b][c][0 .. t_out)
+ * (rows ups_pitch floats apart, batch stride cout * ups_pitch; ups_tup = 2 t_out - 1 or 2 t_out; ups_w = the learned
+ * per-channel weights before the sigmoid, or NULL = linear; ups_y 16-byte aligned).  A launch that ends in the split-K
+ * epilogue writes it there; any other launch is followed by the stand-alone kernel, as in the plan.
+ * wun_op_last_path(WUN_OP_CONV_EPILOGUE) tells which.  wun_op_set_conv_upsample(NULL, 0, 0, NULL) resets. */
+int wun_op_set_conv_upsample(float* ups_y, int ups_pitch, int ups_tup, const float* ups_w);
+
+/* Input gradient of an up conv over concat(skip, 2x LINEAR upsampling of x_prev), as the plan launches it: the bias-free,
+ * activation-free stride-1 conv  g[b][m][q] = sum_{j, c} wt[j][c][m] dz[b][c][q + j - pad_left]  (wt [k][cin][n_skip + n_cur],
+ * dz [batch][cin][t_in], 0 <= q < tup, zero outside [0, t_in)).  Columns m < n_skip go to d_skip [batch][n_skip][tup]; the
+ * others are d(upsampled tensor) and go through the adjoint of the upsampling into
+ *   dz_prev[b][c][i] = LeakyReLU'(x_prev[b][c][i]) * (g[2i] + wa g[2i+1] + 1/2 g[2i-1]),  0 <= i < n,  tup in {2n - 1, 2n}
+ * (wa = 1 at i = n - 1 with tup = 2n, else 1/2; rows of dz_prev / x_prev prev_pitch floats apart).  A launch that ends in the
+ * split-K epilogue (wun_op_force_conv_variant(v, ksplit >= 2)) does this there and leaves d_up [batch][n_cur][tup] untouched;
+ * any other launch stores d_up and runs the stand-alone adjoint.  wun_op_last_path(WUN_OP_CONV_EPILOGUE) tells which. */
+int wun_op_conv1d_upsample_adjoint(const float* dz, const float* wt, float* d_skip, float* d_up, float* dz_prev,
+                                   const float* x_prev, int batch, int cin, int n_skip, int n_cur, int k, int t_in, int tup,
+                                   int pad_left, int n, int prev_pitch, void* stream);
+
+/* ---- The elementwise family as single operators (upsampling, head, layout change) ---------------------------------------
+ * Thin wrappers over the launchers the plan uses.  Rows may sit anywhere: no alignment is asked of pointers or pitches, a
+ * tensor that is not 16-byte aligned with padded pitches is served by the scalar forms.  Pitches are in ELEMENTS, the batch
+ * stride of a tensor is channels * pitch.  bf16 != 0: the rows hold bfloat16 elements (arithmetic in fp32, one rounding to
+ * nearest even on the store).  FOOTPRINT: exactly the elements [0, length) of every output row are written; row padding
+ * between length and pitch and everything before / behind the tensor is never touched.
+ * WUN_ERR_INVALID (before any GPU work) for a null required pointer, a shape below 1, a pitch below its row length, tup
+ * outside {2n - 1, 2n}, more than 4 head sources or 2 channels. */
+
+/* y[b][c][2i] = x[b][c][i];  y[b][c][2i+1] = s x[i] + (1 - s) x[i+1], s = sigmoid(w[c]), x[n] = 0   (w != NULL, learned)
+ *                                           = 0.5 (x[i] + x[i+1]), x[n] = x[n-1]                     (w == NULL, linear)
+ * for 0 <= t < tup; tup = 2n - 1 (context) or 2n. */
+int wun_op_upsample(const void* x, void* y, const float* w, int B, int C, int n, int tup, int xpitch, int ypitch, int bf16,
+                    void* stream);
+/* The adjoint, times the LeakyReLU derivative of the level's stored activation x (1 for x > 0, else 0.2):
+ *   dz[b][c][i] = LeakyReLU'(x[i]) (dy[2i] + wa dy[2i+1] + wb dy[2i-1])     (terms outside [0, tup) dropped)
+ * learned: wa = s, wb = 1 - s; linear: wa = wb = 1/2, wa = 1 at i = n - 1 when tup = 2n.  dz has x's geometry.
+ * With w and dw: dw[c] (=, or += with accumulate) s (1 - s) sum_{b, i} dy[2i+1] (x[i] - x[i+1]); dw_partial = B * C floats of
+ * scratch selects the two-stage form where the rows allow it, NULL the one-stage form. */
+int wun_op_upsample_backward(const void* dy, const void* x, void* dz, const float* w, float* dw, float* dw_partial, int B,
+                             int C, int n, int tup, int ypitch, int xpitch, int bf16, int accumulate, void* stream);
+
+/* The output head (OutputLayer.py): S estimates [S][B][Tout][C] from the mix rows [B][C][mix_pitch] and the feature map
+ * [B][F][feat_pitch] (Tfeat valid).  Sh = S - difference sources have a conv of Ko taps over concat(mix, features):
+ *   pre_s[b][t][c] = bias_s[c] + sum_{k, ci} W_s[k][ci][c] in[b][ci][t + k - padl]     (zero outside [0, Tfeat))
+ * with in = mix[mix_off_feat + .] for ci < C and feat for ci >= C; out_s = tanh(pre_s) (tanh != 0), or pre_s clipped to
+ * [-1, 1] unless training.  difference: out[S-1] = mix[mix_off_diff + t] - sum_s out_s (clipped unless training).
+ * Source s' parameters {W [Ko][C+F][C], bias [C]} start at params + hoff[s]: any order, gaps allowed. */
+typedef struct wun_op_head_desc {
+    int32_t C, F, S, difference, Ko, padl, Tfeat, Tout, B, tanh, training, feat_bf16;
+    int32_t mix_pitch, feat_pitch, dpre_pitch;      /* elements; dpre is [Sh][B][C][dpre_pitch] */
+    int32_t mix_off_feat, mix_off_diff;             /* crop offsets into a mix row */
+} wun_op_head_desc;
+int32_t wun_op_head_abi_size(void);   /* sizeof(wun_op_head_desc) */
+int wun_op_head_forward(const wun_op_head_desc* desc, const float* mix, const void* feat, const float* params,
+                        const int64_t* hoff, float* out, void* stream);
+/* MSE over all S estimates: *loss = mean (out - targets)^2; dpre = dL/d pre_s; dzfeat (feat's geometry and type) =
+ * LeakyReLU'(feat) * dL/d feat.  out: what wun_op_head_forward wrote with training != 0 -- the gradient is the training graph's
+ * (clipping happens at inference only), the backward entries do not read desc->training. */
+int wun_op_head_loss_backward(const wun_op_head_desc* desc, const void* feat, const float* params, const int64_t* hoff,
+                              const float* out, const float* targets, float* dpre, void* dzfeat, float* loss, void* stream);
+/* The same from an upstream gradient d_outputs [S][B][Tout][C] instead of the MSE. */
+int wun_op_head_backward(const wun_op_head_desc* desc, const void* feat, const float* params, const int64_t* hoff,
+                         const float* out, const float* d_outputs, float* dpre, void* dzfeat, void* stream);
+
+/* dst[b][c][t] = src[b][t][c]  ([B][T][C] -> [B][C][pitch]), any C >= 1. */
+int wun_op_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pitch, void* stream);
+
+/* Which form the last launch of an operator took on the calling thread (the forms share one profiler name): */
+#define WUN_OP_UPSAMPLE          0   /* scalar / vec4 / vec8-bf16 */
+#define WUN_OP_UPSAMPLE_BACKWARD 1   /* scalar / vec4 */
+#define WUN_OP_INTERP_GRAD       2   /* one-stage / two-stage */
+#define WUN_OP_HEAD_FORWARD      3   /* generic / four-position */
+#define WUN_OP_HEAD_DFEAT        4   /* generic / four-position (d feature map of both head backward entries) */
+#define WUN_OP_CONV_EPILOGUE     5   /* fused / not fused (wun_op_set_conv_upsample, wun_op_conv1d_upsample_adjoint) */
+#define WUN_OP_BTC_TO_NCW        6   /* scalar / vec4 */
+#define WUN_PATH_NONE          0     /* no launch yet */
+#define WUN_PATH_SCALAR        1
+#define WUN_PATH_VEC4          2
+#define WUN_PATH_VEC8_BF16     3
+#define WUN_PATH_ONE_STAGE     4
+#define WUN_PATH_TWO_STAGE     5
+#define WUN_PATH_GENERIC       6
+#define WUN_PATH_FOUR_POSITION 7
+#define WUN_PATH_NOT_FUSED     8
+#define WUN_PATH_FUSED         9
+int wun_op_last_path(int op);
+
 /* The bf16 mode's conv as a single operator (wun_op_conv1d semantics, Cin >= 8, K <= 15): x and w
  * are rounded to bf16 (nearest-even; x into a temporary bf16 copy -- the kernel reads bf16 rows), products accumulate
  * in fp32, y is stored as fp32.  scratch: device floats, at least

@@ -60,6 +60,17 @@ class WunSpeedBank(C.Structure):
     _fields_ = [("n", C.c_int32), ("up", C.c_int32 * 8), ("down", C.c_int32 * 8), ("table", C.c_void_p * 8)]
 
 
+class WunOpHeadDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "C", "F", "S", "difference", "Ko", "padl", "Tfeat", "Tout", "B", "tanh", "training", "feat_bf16",
+        "mix_pitch", "feat_pitch", "dpre_pitch", "mix_off_feat", "mix_off_diff")]
+
+
+# wun_op_last_path: operators and forms (WUN_OP_*, WUN_PATH_* of include/wun.h)
+(OP_UPSAMPLE, OP_UPSAMPLE_BACKWARD, OP_INTERP_GRAD, OP_HEAD_FORWARD, OP_HEAD_DFEAT, OP_CONV_EPILOGUE, OP_BTC_TO_NCW) = range(7)
+(PATH_NONE, PATH_SCALAR, PATH_VEC4, PATH_VEC8_BF16, PATH_ONE_STAGE, PATH_TWO_STAGE, PATH_GENERIC, PATH_FOUR_POSITION,
+ PATH_NOT_FUSED, PATH_FUSED) = range(10)
+
 SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2                 # wun_snippet_source.flags
 SPEED_RATES, SPEED_MAX_RATIO = 8, 64                # WUN_SPEED_RATES, WUN_SPEED_MAX_RATIO: the rate bank of wun_gather_snippets_speed
 SNIPPET_ROWS = 24                                   # WUN_SNIPPET_ROWS: batch rows per launch of wun_gather_snippets
@@ -259,6 +270,16 @@ _SIGS = {
     "wun_op_set_wgrad_narrow": (C.c_int, [C.c_int]),
     "wun_op_conv1d_ex": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P, _P, _P] + [C.c_int] * 12 + [_P]),
     "wun_op_set_conv_copies": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
+    "wun_op_set_conv_upsample": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "wun_op_conv1d_upsample_adjoint": (C.c_int, [_P] * 6 + [C.c_int] * 10 + [_P]),
+    "wun_op_upsample": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [_P]),
+    "wun_op_upsample_backward": (C.c_int, [_P] * 6 + [C.c_int] * 8 + [_P]),
+    "wun_op_head_abi_size": (C.c_int32, []),
+    "wun_op_head_forward": (C.c_int, [C.POINTER(WunOpHeadDesc), _P, _P, _P, C.POINTER(C.c_int64), _P, _P]),
+    "wun_op_head_loss_backward": (C.c_int, [C.POINTER(WunOpHeadDesc), _P, _P, C.POINTER(C.c_int64), _P, _P, _P, _P, _P, _P]),
+    "wun_op_head_backward": (C.c_int, [C.POINTER(WunOpHeadDesc), _P, _P, C.POINTER(C.c_int64), _P, _P, _P, _P, _P]),
+    "wun_op_btc_to_ncw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "wun_op_last_path": (C.c_int, [C.c_int]),
     "wun_profile_begin": (C.c_int, []),
     "wun_profile_end": (C.c_int, [C.c_char_p, C.c_int64]),
     "wun_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
@@ -310,6 +331,9 @@ def load():
     if lib.wun_snippet_abi_size() != C.sizeof(WunSnippetSource):
         raise RuntimeError("libwun.so wun_snippet_source size %d != this binding's %d (stale library or binding)" % (
             lib.wun_snippet_abi_size(), C.sizeof(WunSnippetSource)))
+    if lib.wun_op_head_abi_size() != C.sizeof(WunOpHeadDesc):
+        raise RuntimeError("libwun.so wun_op_head_desc size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_op_head_abi_size(), C.sizeof(WunOpHeadDesc)))
     if lib.wun_speed_abi_size() != C.sizeof(WunSpeedBank):
         raise RuntimeError("libwun.so wun_speed_bank size %d != this binding's %d (stale library or binding)" % (
             lib.wun_speed_abi_size(), C.sizeof(WunSpeedBank)))

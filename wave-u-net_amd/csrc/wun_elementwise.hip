@@ -24,7 +24,10 @@ struct ProfScope {
     }
     ~ProfScope() { prof_scope_end(s); }
 };
+thread_local int t_last_path[EW_NUM_OPS];      // elementwise_last_path()
 }  // namespace
+
+int elementwise_last_path(int op) { return (op >= 0 && op < EW_NUM_OPS) ? t_last_path[op] : EW_PATH_NONE; }
 
 // =====================================================================================
 // upsampling (linear / learned), forward and backward
@@ -32,6 +35,10 @@ struct ProfScope {
 // =====================================================================================
 // (ET: element type of x and y -- float, or bf16_t in the bf16 mode whose activations live in HBM as bf16; the arithmetic
 //  is fp32 either way, ET = float compiles to the plain accesses)
+// The learned mid-point s a + (1 - s) b in the rounding order the vector forms compile to (the second product rounded, the
+// first fused), written out for the scalar form: left to -ffp-contract it fused the OTHER product, fma(1 - s, b, s a), and
+// differed from the vector forms by an ulp (tests/test_gpu_elementwise.py, "forms differ").
+__device__ __forceinline__ float interp_mid(float s, float a, float b) { return fmaf(s, a, (1.f - s) * b); }
 template <typename ET>
 __global__ void upsample_kernel(UpsampleArgs a) {
     const long long total = (long long)a.B * a.C * a.tup;
@@ -48,7 +55,7 @@ __global__ void upsample_kernel(UpsampleArgs a) {
         } else if (a.w != nullptr) {
             const float s = 1.f / (1.f + __expf(-a.w[c]));
             const float x1 = (j + 1 < a.n) ? ld1<ET>(x, j + 1) : 0.f;      // SAME: one zero on the right
-            v = s * ld1<ET>(x, j) + (1.f - s) * x1;
+            v = interp_mid(s, ld1<ET>(x, j), x1);
         } else {
             const float x1 = (j + 1 < a.n) ? ld1<ET>(x, j + 1) : ld1<ET>(x, j);     // legacy bilinear clamps
             v = 0.5f * (ld1<ET>(x, j) + x1);
@@ -136,9 +143,11 @@ hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s) {
     ProfScope ps("upsample_kernel", 0.0, s, "", (a.bf ? 2.0 : 4.0) * (double)a.B * a.C * ((double)a.n + a.tup));
     if ((a.ypitch & 3) == 0 && (a.ybs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & 15) == 0 && (long long)a.B * a.C <= 4 * 65535ll) {
         const int nvec = (a.tup + 3) / 4;
+        t_last_path[EW_UPSAMPLE] = EW_PATH_VEC4;
         const dim3 grid((unsigned)((nvec + 63) / 64), (unsigned)((a.B * a.C + 3) / 4));
         if (a.bf && (a.xpitch & 3) == 0 && (a.xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 && (a.ypitch & 7) == 0 && (a.ybs & 7) == 0) {
             const dim3 grid8((unsigned)(((a.tup + 7) / 8 + 63) / 64), (unsigned)((a.B * a.C + 3) / 4));
+            t_last_path[EW_UPSAMPLE] = EW_PATH_VEC8_BF16;
             hipLaunchKernelGGL(upsample_vec8_bf16_kernel, grid8, dim3(256), 0, s, a);
         } else if (a.bf) hipLaunchKernelGGL(upsample_vec_kernel<bf16_t>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(upsample_vec_kernel<float>, grid, dim3(256), 0, s, a);
@@ -147,6 +156,7 @@ hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s) {
     const long long total = (long long)a.B * a.C * a.tup;
     long long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
+    t_last_path[EW_UPSAMPLE] = EW_PATH_SCALAR;
     if (a.bf) hipLaunchKernelGGL(upsample_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(upsample_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, a);
     return hipGetLastError();
@@ -317,6 +327,7 @@ hipError_t launch_upsample_bwd(const UpsampleBwdArgs& a, hipStream_t s) {
     const bool vecok = (a.ypitch & 3) == 0 && (a.ybs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.dy) & 15) == 0 &&
                        (a.xpitch & 3) == 0 && (a.xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0 &&
                        (reinterpret_cast<uintptr_t>(a.dz) & 15) == 0 && (long long)a.B * a.C <= 4 * 65535ll;
+    t_last_path[EW_UPSAMPLE_BWD] = vecok ? EW_PATH_VEC4 : EW_PATH_SCALAR;
     if (vecok) {
         const int nvec = (a.n + 3) / 4;
         const dim3 grid((unsigned)((nvec + 63) / 64), (unsigned)((a.B * a.C + 3) / 4));
@@ -338,7 +349,9 @@ hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s, bool accu
     if (a.w != nullptr && a.dw != nullptr) {
         ProfScope ps("interp_grad_kernel", 0.0, s, "", (a.bf ? 2.0 : 4.0) * (double)a.B * a.C * (a.n + a.tup));
         // rows 16-byte aligned (the plan's buffers) and a scratch vector given: the two-stage form
-        if (a.dw_partial != nullptr && vecok && a.B <= 65535) {
+        const bool two_stage = a.dw_partial != nullptr && vecok && a.B <= 65535;
+        t_last_path[EW_INTERP_GRAD] = two_stage ? EW_PATH_TWO_STAGE : EW_PATH_ONE_STAGE;
+        if (two_stage) {
             const dim3 grid((unsigned)a.C, (unsigned)a.B);
             if (a.bf) hipLaunchKernelGGL(interp_grad_rows_kernel<bf16_t>, grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL(interp_grad_rows_kernel<float>, grid, dim3(256), 0, s, a);
@@ -836,7 +849,9 @@ __global__ __launch_bounds__(256) void btc_to_ncw_vec_kernel(const float* __rest
 hipError_t launch_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pitch,
                              hipStream_t s) {
     const long long total = (long long)B * T * C;
-    if ((C == 1 || C == 2) && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && B <= 65535) {
+    const bool vec = (C == 1 || C == 2) && (pitch & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 && B <= 65535;
+    t_last_path[EW_BTC_TO_NCW] = vec ? EW_PATH_VEC4 : EW_PATH_SCALAR;
+    if (vec) {
         ProfScope ps("btc_to_ncw_kernel", 0.0, s, "", 8.0 * (double)total);
         const dim3 grid((unsigned)((T + 1023) / 1024), (unsigned)B);
         if (C == 1) hipLaunchKernelGGL(btc_to_ncw_vec_kernel<1>, grid, dim3(256), 0, s, src, dst, T, pitch);
@@ -1165,6 +1180,7 @@ hipError_t launch_head_fwd_off(const HeadArgs& a, const long long* hoff, hipStre
     // feature map + mix window read once, all sources written
     const double fb = a.featbf ? 2.0 : 4.0;
     ProfScope ps("head_fwd_kernel", 0.0, s, "", (double)a.B * ((double)a.Tfeat * (fb * a.F + 4.0 * a.C) + 4.0 * (double)a.Tout * a.S * a.C));
+    t_last_path[EW_HEAD_FWD] = head_vec4_ok(a) ? EW_PATH_FOUR_POSITION : EW_PATH_GENERIC;
     if (head_vec4_ok(a)) {
         long long b4 = ((long long)a.B * (a.Tout >> 2) + 255) / 256;
         if (b4 > 4096) b4 = 4096;
@@ -1215,8 +1231,10 @@ static hipError_t launch_head_dfeat(const HeadArgs& a, const long long* hoff, hi
     const long long total = (long long)a.B * a.Tfeat;
     long long blocks = (total + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    if (head_vec4_ok(a) && (a.dppitch & 3) == 0 && (a.dpbs & 3) == 0 && (a.dps & 3) == 0 && (reinterpret_cast<uintptr_t>(a.dpre) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(a.dzfeat) & 15) == 0) {
+    const bool vec4 = head_vec4_ok(a) && (a.dppitch & 3) == 0 && (a.dpbs & 3) == 0 && (a.dps & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(a.dpre) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.dzfeat) & 15) == 0;
+    t_last_path[EW_HEAD_DFEAT] = vec4 ? EW_PATH_FOUR_POSITION : EW_PATH_GENERIC;
+    if (vec4) {
         long long b4 = ((long long)a.B * (a.Tfeat >> 2) + 255) / 256;
         if (b4 > 4096) b4 = 4096;
         if (b4 < 1) b4 = 1;

@@ -294,6 +294,13 @@ void wgrad_resolved_geom(const WgradArgs& a, int& mtw, int& nw);
 long long wgrad_partial_floats(const WgradArgs& a, const WunSwitches& sw);
 hipError_t launch_wgrad_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
                                hipStream_t s, const WunSwitches& sw);
+// Which form the last launch of an elementwise operator took on this thread (wun_op_last_path): the host launchers of
+// wun_elementwise.hip record it, because one ProfScope name covers every form of an operator.  Values = the WUN_PATH_* of
+// include/wun.h; 0 before the first launch.
+enum { EW_UPSAMPLE = 0, EW_UPSAMPLE_BWD, EW_INTERP_GRAD, EW_HEAD_FWD, EW_HEAD_DFEAT, EW_BTC_TO_NCW, EW_NUM_OPS };
+enum { EW_PATH_NONE = 0, EW_PATH_SCALAR, EW_PATH_VEC4, EW_PATH_VEC8_BF16, EW_PATH_ONE_STAGE, EW_PATH_TWO_STAGE,
+       EW_PATH_GENERIC, EW_PATH_FOUR_POSITION };
+int elementwise_last_path(int op);
 hipError_t launch_upsample(const UpsampleArgs& a, hipStream_t s);
 hipError_t launch_upsample_bwd(const UpsampleBwdArgs& a, hipStream_t s);
 hipError_t launch_interp_grad(const UpsampleBwdArgs& a, hipStream_t s, bool accum = false);   // dw of the learned interpolation weights

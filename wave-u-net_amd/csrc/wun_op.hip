@@ -23,6 +23,9 @@ static int g_op_wg_narrow = 0;                                     // wun_op_set
 static int g_op_wg_win = 0;                                        // wun_op_set_wgrad_win (test hook)
 static float* g_op_copy0 = nullptr; static float* g_op_copy1 = nullptr;   // wun_op_set_conv_copies (test hook)
 static int g_op_copy_t0 = 0, g_op_copy_t1 = 0, g_op_copy_exp = 0, g_op_copy_lo = 0, g_op_copy_len = 0, g_op_acc_lo = 0, g_op_acc_len = 0;
+static float* g_op_ups_y = nullptr; static const float* g_op_ups_w = nullptr;   // wun_op_set_conv_upsample (test hook)
+static int g_op_ups_pitch = 0, g_op_ups_tup = 0;
+static thread_local int t_op_epilogue_path = WUN_PATH_NONE;                     // wun_op_last_path(WUN_OP_CONV_EPILOGUE)
 static float* op_scratch() {
     static float* buf = nullptr;
     if (!buf && hipMalloc((void**)&buf, kOpScratchFloats * sizeof(float)) != hipSuccess) {
@@ -290,9 +293,205 @@ extern "C" int wun_op_conv1d_ex(const float* x0, int c0, const float* x1, int c1
     }
     if (g_op_copy1 != nullptr) { a.dec1 = g_op_copy1; a.dec1pitch = g_op_copy_t1; a.dec1bs = (long long)cout * g_op_copy_t1; }
     if (accumulate && g_op_acc_len > 0) { a.acc_lo = g_op_acc_lo; a.acc_len = (unsigned)g_op_acc_len; }
+    if (g_op_ups_y != nullptr) {
+        // wun_op_set_conv_upsample: what the plan asks of a level's last conv (wun_forward.hip) -- the split-K epilogue also
+        // writes the 2x upsampled copy; a launch that does not end there is followed by the stand-alone kernel, as in the plan
+        if (g_op_ups_tup != 2 * t_out - 1 && g_op_ups_tup != 2 * t_out) return fail(WUN_ERR_INVALID, "ups_tup must be 2 t_out - 1 or 2 t_out");
+        if (stride != 1 || ostride != 1 || ooff != 0 || accumulate || mask) return fail(WUN_ERR_INVALID, "fused upsampling: plain forward launches only");
+        if ((reinterpret_cast<uintptr_t>(g_op_ups_y) & 15) != 0) return fail(WUN_ERR_INVALID, "fused upsampling: ups_y must be 16-byte aligned");
+        a.ups_y = g_op_ups_y; a.ups_pitch = g_op_ups_pitch; a.ups_bs = (long long)cout * g_op_ups_pitch;
+        a.ups_tup = g_op_ups_tup; a.ups_w = g_op_ups_w;
+    }
     HIP_TRY(op_launch_conv(a, (hipStream_t)stream));
+    if (a.ups_y != nullptr) {
+        t_op_epilogue_path = conv_last_fused_ups() ? WUN_PATH_FUSED : WUN_PATH_NOT_FUSED;
+        if (!conv_last_fused_ups()) {
+            UpsampleArgs u;
+            memset(&u, 0, sizeof(u));
+            u.x = y; u.xpitch = t_y; u.xbs = (long long)cout * t_y; u.n = t_out;
+            u.y = a.ups_y; u.ypitch = a.ups_pitch; u.ybs = a.ups_bs; u.tup = a.ups_tup; u.w = a.ups_w;
+            u.C = cout; u.B = batch; u.context = (a.ups_tup & 1);
+            HIP_TRY(launch_upsample(u, (hipStream_t)stream));
+        }
+    }
     return WUN_OK;
 }
+
+extern "C" int wun_op_set_conv_upsample(float* ups_y, int ups_pitch, int ups_tup, const float* ups_w) {
+    if (ups_y && (ups_tup < 1 || ups_pitch < ups_tup)) return fail(WUN_ERR_INVALID, "bad upsampled-copy geometry");
+    g_op_ups_y = ups_y; g_op_ups_pitch = ups_pitch; g_op_ups_tup = ups_tup; g_op_ups_w = ups_y ? ups_w : nullptr;
+    return WUN_OK;
+}
+
+// Input gradient of an up conv whose input is concat(skip, upsampled) with LINEAR upsampling, as the plan launches it
+// (wun_backward.hip): a bias-free, activation-free stride-1 conv over dz with the transposed weights wt [k][cin][n_skip + n_cur];
+// output columns < n_skip go to d_skip, the others are d(upsampled tensor).  A launch that ends in the split-K epilogue applies
+// the adjoint of the upsampling there (ConvArgs.ubw_*) and never stores d_up; any other launch stores d_up and is followed by
+// the stand-alone adjoint kernel.  Either way dz_prev[b][c][0 .. n) is written.
+extern "C" int wun_op_conv1d_upsample_adjoint(const float* dz, const float* wt, float* d_skip, float* d_up, float* dz_prev,
+                                              const float* x_prev, int batch, int cin, int n_skip, int n_cur, int k, int t_in,
+                                              int tup, int pad_left, int n, int prev_pitch, void* stream) {
+    if (!dz || !wt || !d_skip || !d_up || !dz_prev || !x_prev) return fail(WUN_ERR_INVALID, "null argument");
+    if (batch < 1 || cin < 1 || n_skip < 1 || n_cur < 1 || k < 1 || t_in < 1 || n < 1) return fail(WUN_ERR_INVALID, "bad shape");
+    if (tup != 2 * n - 1 && tup != 2 * n) return fail(WUN_ERR_INVALID, "tup must be 2n - 1 or 2n");
+    if (prev_pitch < n) return fail(WUN_ERR_INVALID, "pitch below length");
+    hipStream_t s = (hipStream_t)stream;
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = batch; a.ostride = 1;
+    op_src(a, dz, cin, t_in);
+    a.loader = LOADER_DIRECT;
+    a.Tin = t_in; a.shift = pad_left; a.W = wt; a.KW = k; a.N = n_skip + n_cur; a.N0 = n_skip; a.Tout = tup;
+    a.dst0 = d_skip; a.obs0 = (long long)n_skip * tup; a.opitch0 = tup;
+    a.dst1 = d_up; a.obs1 = (long long)n_cur * tup; a.opitch1 = tup;
+    a.ubw_dz = dz_prev; a.ubw_x = x_prev; a.ubw_pitch = prev_pitch; a.ubw_bs = (long long)n_cur * prev_pitch; a.ubw_n = n;
+    HIP_TRY(op_launch_conv(a, s));
+    t_op_epilogue_path = conv_last_fused_ups() ? WUN_PATH_FUSED : WUN_PATH_NOT_FUSED;
+    if (!conv_last_fused_ups()) {
+        UpsampleBwdArgs ub;
+        memset(&ub, 0, sizeof(ub));
+        ub.dy = d_up; ub.ypitch = tup; ub.ybs = (long long)n_cur * tup; ub.tup = tup;
+        ub.x = x_prev; ub.xpitch = prev_pitch; ub.xbs = (long long)n_cur * prev_pitch; ub.n = n;
+        ub.dz = dz_prev; ub.C = n_cur; ub.B = batch; ub.context = (tup & 1);
+        HIP_TRY(launch_upsample_bwd(ub, s));
+    }
+    return WUN_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// the elementwise family (wun_elementwise.hip) as single operators: thin wrappers that fill the launchers' argument structs.
+// Every check runs before any GPU work; no alignment is asked of pointers or pitches (the scalar forms serve those).
+// ---------------------------------------------------------------------------------------
+static const char* op_updown_check(const void* a, const void* b, int B, int C, int n, int tup, int xpitch, int ypitch) {
+    if (!a || !b) return "null argument";
+    if (B < 1 || C < 1 || n < 1) return "bad shape";
+    if (tup != 2 * n - 1 && tup != 2 * n) return "tup must be 2n - 1 or 2n";
+    if (tup < 1) return "bad shape";
+    if (xpitch < n || ypitch < tup) return "pitch below length";
+    return nullptr;
+}
+
+extern "C" int wun_op_upsample(const void* x, void* y, const float* w, int B, int C, int n, int tup, int xpitch, int ypitch,
+                               int bf16, void* stream) {
+    if (const char* why = op_updown_check(x, y, B, C, n, tup, xpitch, ypitch)) return fail(WUN_ERR_INVALID, why);
+    UpsampleArgs u;
+    memset(&u, 0, sizeof(u));
+    u.x = reinterpret_cast<const float*>(x); u.xpitch = xpitch; u.xbs = (long long)C * xpitch; u.n = n;
+    u.y = reinterpret_cast<float*>(y); u.ypitch = ypitch; u.ybs = (long long)C * ypitch; u.tup = tup;
+    u.w = w; u.C = C; u.B = B; u.context = (tup & 1); u.bf = bf16 ? 1 : 0;
+    HIP_TRY(launch_upsample(u, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_upsample_backward(const void* dy, const void* x, void* dz, const float* w, float* dw, float* dw_partial,
+                                        int B, int C, int n, int tup, int ypitch, int xpitch, int bf16, int accumulate,
+                                        void* stream) {
+    if (const char* why = op_updown_check(dy, x, B, C, n, tup, xpitch, ypitch)) return fail(WUN_ERR_INVALID, why);
+    if (!dz) return fail(WUN_ERR_INVALID, "null argument");
+    if (dw && !w) return fail(WUN_ERR_INVALID, "dw without w");
+    UpsampleBwdArgs ub;
+    memset(&ub, 0, sizeof(ub));
+    ub.dy = reinterpret_cast<const float*>(dy); ub.ypitch = ypitch; ub.ybs = (long long)C * ypitch; ub.tup = tup;
+    ub.x = reinterpret_cast<const float*>(x); ub.xpitch = xpitch; ub.xbs = (long long)C * xpitch; ub.n = n;
+    ub.dz = reinterpret_cast<float*>(dz); ub.w = w; ub.dw = dw; ub.dw_partial = dw ? dw_partial : nullptr;
+    ub.C = C; ub.B = B; ub.context = (tup & 1); ub.bf = bf16 ? 1 : 0;
+    HIP_TRY(launch_upsample_bwd(ub, (hipStream_t)stream));
+    if (w && dw) HIP_TRY(launch_interp_grad(ub, (hipStream_t)stream, accumulate != 0));
+    return WUN_OK;
+}
+
+extern "C" int32_t wun_op_head_abi_size(void) { return (int32_t)sizeof(wun_op_head_desc); }
+
+// fills HeadArgs from the descriptor; null = fine, else why not
+static const char* op_head_args(const wun_op_head_desc* d, const float* mix, const void* feat, const float* params,
+                                const int64_t* hoff, HeadArgs& h, long long* off) {
+    if (!d || !feat || !params || !hoff) return "null argument";
+    if (d->difference != 0 && d->difference != 1) return "difference must be 0 or 1";
+    const int Sh = d->S - d->difference;
+    if (d->C < 1 || d->C > 2 || Sh < 1 || Sh > 4 || Sh * d->C > 8) return "C must be 1 or 2, 1..4 head sources, Sh * C <= 8";
+    if (d->F < 1 || d->Ko < 1 || d->padl < 0 || d->padl >= d->Ko || d->Tfeat < 1 || d->Tout < 1 || d->B < 1) return "bad shape";
+    if (d->feat_pitch < d->Tfeat || d->dpre_pitch < d->Tout) return "pitch below length";
+    if (mix && (d->mix_off_feat < 0 || d->mix_off_diff < 0 || d->mix_pitch < d->mix_off_feat + d->Tfeat ||
+                (d->difference && d->mix_pitch < d->mix_off_diff + d->Tout))) return "pitch below length";
+    if ((long long)Sh * ((long long)d->Ko * (d->C + d->F) * d->C + d->C) * 4 > 64 * 1024) return "head parameters exceed the LDS";
+    for (int i = 0; i < Sh; ++i)
+        if (hoff[i] < 0) return "negative parameter offset";
+    memset(&h, 0, sizeof(h));
+    h.mix_ncw = mix; h.mpitch = d->mix_pitch; h.mbs = (long long)d->C * d->mix_pitch;
+    h.moff_feat = d->mix_off_feat; h.moff_diff = d->mix_off_diff;
+    h.feat = reinterpret_cast<const float*>(feat); h.fpitch = d->feat_pitch; h.fbs = (long long)d->F * d->feat_pitch;
+    h.Wh = params;
+    h.C = d->C; h.F = d->F; h.S = d->S; h.Sh = Sh; h.Ko = d->Ko; h.padl = d->padl;
+    h.Tfeat = d->Tfeat; h.Tout = d->Tout; h.B = d->B;
+    h.tanh_act = d->tanh ? 1 : 0; h.difference = d->difference; h.training = d->training ? 1 : 0;
+    h.dppitch = d->dpre_pitch; h.dpbs = (long long)d->C * d->dpre_pitch; h.dps = (long long)d->B * h.dpbs;
+    h.gscale = 2.0f / ((float)d->S * (float)d->B * (float)d->Tout * (float)d->C);
+    h.featbf = d->feat_bf16 ? 1 : 0;
+    for (int i = 0; i < 4; ++i) off[i] = i < Sh ? (long long)hoff[i] : 0;
+    return nullptr;
+}
+
+extern "C" int wun_op_head_forward(const wun_op_head_desc* desc, const float* mix, const void* feat, const float* params,
+                                   const int64_t* hoff, float* out, void* stream) {
+    HeadArgs h;
+    long long off[4];
+    if (!mix || !out) return fail(WUN_ERR_INVALID, "null argument");
+    if (const char* why = op_head_args(desc, mix, feat, params, hoff, h, off)) return fail(WUN_ERR_INVALID, why);
+    h.out = out;
+    HIP_TRY(launch_head_fwd_off(h, off, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_head_loss_backward(const wun_op_head_desc* desc, const void* feat, const float* params, const int64_t* hoff,
+                                         const float* out, const float* targets, float* dpre, void* dzfeat, float* loss,
+                                         void* stream) {
+    HeadArgs h;
+    long long off[4];
+    if (!out || !targets || !dpre || !dzfeat || !loss) return fail(WUN_ERR_INVALID, "null argument");
+    if (const char* why = op_head_args(desc, nullptr, feat, params, hoff, h, off)) return fail(WUN_ERR_INVALID, why);
+    h.out = const_cast<float*>(out); h.tgt = targets; h.dpre = dpre; h.dzfeat = reinterpret_cast<float*>(dzfeat);
+    h.loss_partial = op_scratch();
+    if (!h.loss_partial) return fail(WUN_ERR_NOMEM, "operator scratch");
+    HIP_TRY(launch_head_bwd_off(h, off, (hipStream_t)stream));
+    HIP_TRY(launch_loss_finish(h.loss_partial, head_bwd_blocks(h),
+                               1.0f / ((float)h.S * (float)h.B * (float)h.Tout * (float)h.C), loss, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_head_backward(const wun_op_head_desc* desc, const void* feat, const float* params, const int64_t* hoff,
+                                    const float* out, const float* d_outputs, float* dpre, void* dzfeat, void* stream) {
+    HeadArgs h;
+    long long off[4];
+    if (!out || !d_outputs || !dpre || !dzfeat) return fail(WUN_ERR_INVALID, "null argument");
+    if (const char* why = op_head_args(desc, nullptr, feat, params, hoff, h, off)) return fail(WUN_ERR_INVALID, why);
+    h.out = const_cast<float*>(out); h.dout = d_outputs; h.dpre = dpre; h.dzfeat = reinterpret_cast<float*>(dzfeat);
+    HIP_TRY(launch_head_grad_off(h, off, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pitch, void* stream) {
+    if (!src || !dst) return fail(WUN_ERR_INVALID, "null argument");
+    if (B < 1 || T < 1 || C < 1) return fail(WUN_ERR_INVALID, "bad shape");
+    if (pitch < T) return fail(WUN_ERR_INVALID, "pitch below length");
+    HIP_TRY(launch_btc_to_ncw(src, dst, B, T, C, pitch, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_op_last_path(int op) {
+    switch (op) {
+        case WUN_OP_UPSAMPLE: return elementwise_last_path(EW_UPSAMPLE);
+        case WUN_OP_UPSAMPLE_BACKWARD: return elementwise_last_path(EW_UPSAMPLE_BWD);
+        case WUN_OP_INTERP_GRAD: return elementwise_last_path(EW_INTERP_GRAD);
+        case WUN_OP_HEAD_FORWARD: return elementwise_last_path(EW_HEAD_FWD);
+        case WUN_OP_HEAD_DFEAT: return elementwise_last_path(EW_HEAD_DFEAT);
+        case WUN_OP_BTC_TO_NCW: return elementwise_last_path(EW_BTC_TO_NCW);
+        case WUN_OP_CONV_EPILOGUE: return t_op_epilogue_path;
+        default: return fail(WUN_ERR_INVALID, "unknown operator");
+    }
+}
+static_assert(EW_PATH_SCALAR == WUN_PATH_SCALAR && EW_PATH_VEC4 == WUN_PATH_VEC4 && EW_PATH_VEC8_BF16 == WUN_PATH_VEC8_BF16 &&
+              EW_PATH_ONE_STAGE == WUN_PATH_ONE_STAGE && EW_PATH_TWO_STAGE == WUN_PATH_TWO_STAGE &&
+              EW_PATH_GENERIC == WUN_PATH_GENERIC && EW_PATH_FOUR_POSITION == WUN_PATH_FOUR_POSITION, "wun.h path values");
 
 extern "C" int wun_op_set_conv_copies(float* copy0, int t0, int expand, int exp_lo, int exp_len, float* copy1, int t1,
                                       int acc_lo, int acc_len) {
