@@ -1016,6 +1016,52 @@ int wun_gather_snippets_speed(const float* const* planes, const float* mix_plane
                               int32_t B, int64_t Tin, int64_t Tout, const wun_snippet_source* desc, const uint8_t* rate,
                               const wun_speed_bank* bank, int32_t mix_mode, float* mix_out, float* targets_out, void* stream);
 
+/* ---- phase vocoder: time stretch at constant pitch --------------------------
+ * A job stretches one span of interleaved audio x[n_in][C] into y[n_out][C] at the tempo ratio num / den (above 1 plays faster:
+ * the output is shorter).  With pitch_shift = a stretch followed by wun_resample at the same ratio, the two augmentations that
+ * wun_gather_snippets_speed does not have: tempo without pitch and pitch without tempo.  Jobs are independent and batched: the
+ * table travels by value in the kernel arguments, WUN_STRETCH_JOBS jobs per launch set of four launches (a longer table is
+ * several sets on `stream`).
+ *
+ * With N = n_fft, h = hop, K = N / 2 + 1, w the periodic Hann window of wun_fft_design, lead = N - h, every channel on its own and
+ * F = wun_fft_centered_frames(n_out, N, h), for f = 0 .. F - 1:
+ *   a_f      = (f h num) / den                                   (64-bit integers, floor)
+ *   X_f      = the forward FFT of wun_stft_complex_fft, bit for bit, of w[n] x[a_f - lead + n];  P_f the same at a_f - h - lead;
+ *              samples outside [0, n_in) read as +0 and nothing outside the span is read
+ *   M_f[k]   = sqrtf(fmaf(Re, Re, Im Im)) of X_f[k]
+ *   q        = X_f[k] conj(P_f[k]) in float64 (the four products are exact, each sum is rounded once)
+ *   ang      = atan2(q_im, q_re) / 2 pi, 0 where q_re == 0 and q_im == 0 (either sign of zero);  adv = ((k h) mod N) / N
+ *   D_f[k]   = (float)(d - rint(d)),  d = ang - adv;     D_0[k] = (float)(atan2(Im X_0, Re X_0) / 2 pi), the same zero rule
+ *   Phi_0    = D_0;   Phi_f = Phi_{f-1} + (adv + D_f)             (float64, ascending f per channel and bin)
+ *   Y_f[k]   = (M_f (float)cos(2 pi Phi_f), M_f (float)sin(2 pi Phi_f)), one float32 product each; Im of the bins 0 and N / 2 is 0
+ *   y        = wun_istft_fft's inverse transform of Y_f, windowed, overlap-added at f h - lead and divided by the float64
+ *              window squares of the covering frames (0 where those sum to less than 1e-8), over [0, n_out)
+ * Every float of y[0 .. n_out C) is written and nothing else.  At 1/1, P_f is X_{f-1} bit for bit and the entry is STFT -> ISTFT up
+ * to the float32 rounding of D.  A job's floats depend on its span, its ratio, N, h and the table -- not on the other jobs, its
+ * place in the table, the launch set, the grid, what `scratch` held or pointer alignment. */
+#define WUN_STRETCH_JOBS 64            /* jobs per launch set; more jobs = more launch sets on the same stream */
+typedef struct wun_stretch_job {       /* 32 bytes */
+    const float* x;                    /* device, [n_in][C]; any 4-byte alignment */
+    float*       y;                    /* device, [n_out][C]; any 4-byte alignment */
+    int32_t      n_in, n_out, num, den;
+} wun_stretch_job;
+int32_t wun_stretch_abi_size(void);    /* sizeof(wun_stretch_job) */
+/* ceil(n_in den / num): the longest n_out of a job.  Host only.  WUN_ERR_INVALID for n_in < 1 (or above 2^40) or a ratio that is
+ * not positive and coprime; WUN_ERR_UNSUPPORTED for max(num, den) > 64 or a ratio outside [1/2, 2].  1/1 is legal. */
+int64_t wun_time_stretch_frames(int64_t n_in, int32_t num, int32_t den);
+/* Floats of `scratch` for this table: rows (2 K + N) of the largest launch set, rows = C times the sum of its jobs' F (only n_out
+ * of a job is read).  Errors as wun_time_stretch's for jobs, J, C, n_fft, hop and n_out < 1. */
+int64_t wun_time_stretch_scratch_floats(const wun_stretch_job* jobs, int32_t J, int32_t C, int32_t n_fft, int32_t hop);
+/*   jobs      : HOST, [J] (copied into the launches; free to reuse after the call returns)
+ *   table_dev : device, wun_fft_design(n_fft)'s table;  scratch : device, wun_time_stretch_scratch_floats floats
+ * WUN_ERR_INVALID for a null pointer, J < 1, C outside {1, 2}, a hop that is not a power of two or is above n_fft / 4, and per job
+ * n_in < 1, n_out < 1 or above wun_time_stretch_frames, a ratio that is not positive and coprime, a pointer that is not 4-byte
+ * aligned, a y that overlaps the x of any job;  WUN_ERR_UNSUPPORTED for an n_fft that is not a power of two in 64..8192, a ratio
+ * above the ceiling of 64 or outside [1/2, 2], more than 2^31 - 1 frame rows in a launch set.  Every check runs before any GPU
+ * work.  No allocation, no synchronisation, no atomics; both compute modes. */
+int wun_time_stretch(const wun_stretch_job* jobs, int32_t J, int32_t C, int32_t n_fft, int32_t hop, const float* table_dev,
+                     float* scratch, void* stream);
+
 /* ---- the spectrogram U-Net baseline, inference only ------------------------
  * The reference's other separator (Models/UnetSpectrogramSeparator.py:40-108, configs unet_spectrogram / unet_spectrogram_l1)
  * at training = False: per source one U-Net of 5 x 5 stride-2 convolutions over log1p of the mixture's STFT magnitude, whose

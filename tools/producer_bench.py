@@ -8,6 +8,11 @@ Arms (the same snippet stream, seed and residency):
   fused_aug    the same with augment = {"remix": 1, "channel_swap": .5, "polarity": .5} (channel_swap on stereo shapes only)
   fused_speed  the same with augment = {"speed": 1} and the default rates: every source resampled inside the one launch
                (wun_gather_snippets_speed)
+  fused_pitch / fused_stretch   the same with augment = {"pitch_shift": 1} / {"time_stretch": 1} and the default ratios and
+               resolution (n_fft 2048, hop 512): every source of every row is one job of the phase vocoder (wun_time_stretch,
+               DESIGN.md 5.24: four launches per 64 jobs) into a slot behind its plane, then the one gather, which resamples
+               the slots for fused_pitch.  kernel_ms is both entries called directly on one batch; `vocoder_split_ms` splits
+               one such call by kernel (the library's event brackets, wun_profile_begin / wun_profile_end).
   composed     the same batch without the fused resampling: B x S wun_resample launches of the spans into temporary planes, then
                one wun_gather_snippets over them, the C entries called directly (device and kernel columns only).  As a
                producer (device column) it draws its table and rates from fused_speed's stream and allocates its outputs per
@@ -71,7 +76,7 @@ def main():
     import numpy as np
     import torch
     import wave_u_net_amd as wun
-    from wave_u_net_amd import _lib, datasets, resample
+    from wave_u_net_amd import _lib, datasets, resample, vocoder
     from wave_u_net_amd.training import Trainer
 
     assert torch.cuda.is_available(), "this benchmark needs an MI355X"
@@ -95,6 +100,8 @@ def main():
             "fused": datasets.FusedSnippetSource(cfg, tracks, tr.t_in, tr.t_out, B, dev, seed=1),
             "fused_aug": datasets.FusedSnippetSource(cfg, tracks, tr.t_in, tr.t_out, B, dev, seed=1, augment=augment),
             "fused_speed": datasets.FusedSnippetSource(cfg, tracks, tr.t_in, tr.t_out, B, dev, seed=1, augment={"speed": 1}),
+            "fused_pitch": datasets.FusedSnippetSource(cfg, tracks, tr.t_in, tr.t_out, B, dev, seed=1, augment={"pitch_shift": 1}),
+            "fused_stretch": datasets.FusedSnippetSource(cfg, tracks, tr.t_in, tr.t_out, B, dev, seed=1, augment={"time_stretch": 1}),
         }
         del tracks
         # what the fused kernel moves (mix_mode 1): every source window read, the mix and the cropped targets written
@@ -194,7 +201,23 @@ def main():
                 _lib.check(lib.wun_gather_snippets_speed(sp._planes, None, sp.plane_frames, C, S, B, tr.t_in, tr.t_out,
                                                          sp_table.ctypes.data, sp_rates.ctypes.data, _lib.C.addressof(sp._bank), 1,
                                                          outs[0].data_ptr(), outs[1].data_ptr(), stream))
+            # the vocoder arms: wun_time_stretch on the job table of one batch, then the gather on its descriptors
+            voc = {}
+            for k in ("fused_pitch", "fused_stretch"):
+                p = producers[k]
+                vt, vr, vj = p.descriptors().copy(), p.rates().copy(), p.jobs().copy()
+                assert (vj[:, :, 1] > 0).all()                          # every source of every row is a job
+                voc[k] = (p, vt, vr, p.job_table(vj, vr))
+
+            def launch_vocoder(k):
+                p, vt, vr, jt = voc[k]
+                vocoder.run(jt, C, p.vocoder_fft[0], p.vocoder_fft[1], p._scratch, dev)
+                _lib.check(lib.wun_gather_snippets_speed(p._planes, None, p.gather_frames, C, S, B, tr.t_in, tr.t_out,
+                                                         vt.ctypes.data, vr.ctypes.data,
+                                                         _lib.C.addressof(p._bank) if p._bank is not None else None, 1,
+                                                         outs[0].data_ptr(), outs[1].data_ptr(), stream))
             kernels = {"fused": lambda: launch("fused"), "fused_aug": lambda: launch("fused_aug"), "fused_speed": launch_speed,
+                       "fused_pitch": lambda: launch_vocoder("fused_pitch"), "fused_stretch": lambda: launch_vocoder("fused_stretch"),
                        "composed": composed, "d2d_copy": arms["d2d_copy"]}
             knames, reps = list(kernels), 50
             kernel_ms = {k: [] for k in knames}
@@ -207,6 +230,22 @@ def main():
                     e1.record()
                     e1.synchronize()
                     kernel_ms[k].append(e0.elapsed_time(e1) / reps)
+
+            # one call of each vocoder arm split by kernel (ms per call; the brackets' overhead, once per launch, beside it)
+            split = {}
+            for k in voc:
+                launch_vocoder(k)
+                torch.cuda.synchronize()
+                lib.wun_profile_begin()
+                for _ in range(5):
+                    launch_vocoder(k)
+                torch.cuda.synchronize()
+                buf = _lib.C.create_string_buffer(1 << 20)
+                _lib.check(lib.wun_profile_end(buf, len(buf)))
+                prof = json.loads(buf.value.decode())
+                split[k] = {"bracket_overhead_ms": prof.get("bracket_overhead_ms"), "jobs": int(len(voc[k][3])),
+                            "kernels": {e["name"]: {"launches_per_call": e["launches"] / 5.0, "ms_per_call": e["ms"] / 5.0}
+                                        for e in prof["kernels"]}}
 
             wall_ms = {k: [] for k in producers}
             pnames = list(producers)
@@ -248,6 +287,8 @@ def main():
             "d2d_copy_gb_per_s": kernel_bytes / (copy_med * 1e-3) / 1e9,
             "copy_rate_fraction": copy_med / fused_med,
             "speed_over_plain_kernel": speed_med / fused_med,
+            "vocoder_fft": list(voc["fused_pitch"][0].vocoder_fft), "vocoder_split_ms": split,
+            "vocoder_over_plain_kernel": {k: statistics.median(kernel_ms[k]) / fused_med for k in voc},
             "speed_taps": int(speed_taps), "speed_gfma_per_s": speed_taps / (speed_med * 1e-3) / 1e9,
             "fused_speed_below_composed": {"kernel": speed_med < min(kernel_ms["composed"]),
                                            "device": statistics.median(dev_ms["fused_speed"]) < min(dev_ms["composed"]),
@@ -256,7 +297,7 @@ def main():
             "fused_not_slower": {"device": fused_dev <= statistics.median(dev_ms["torch"]),
                                  "wall": statistics.median(wall_ms["fused"]) <= statistics.median(wall_ms["torch"])},
         }
-        del producers, arms, loops, kernels, lib_src, outs, tr, a, b, mix, targets, ttx, sp, tmp, c_outs, spans, draw
+        del producers, arms, loops, kernels, lib_src, outs, voc, tr, a, b, mix, targets, ttx, sp, tmp, c_outs, spans, draw
         torch.cuda.empty_cache()
 
     line = json.dumps(result, sort_keys=True)

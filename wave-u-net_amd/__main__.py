@@ -33,7 +33,9 @@ phase; the refined audio is normalised by the window-square sum over the coverin
 `train` and `test` take `model_config.data_producer=fused` to produce their batches with one HIP kernel out of tracks resident in
 HBM (datasets.FusedSnippetSource; the default "torch" keeps the torch-operator / host producers -- the batches are the same), and
 `train` then takes `model_config.augment={"remix":0.5,"channel_swap":0.5,"polarity":0.5}` (any subset; probabilities) for the
-source-level augmentations: stems remixed across songs, channels swapped, polarity inverted, per source.
+source-level augmentations: stems remixed across songs, channels swapped, polarity inverted, per source; `"speed":p` plays a
+snippet faster or slower, `"pitch_shift":p` transposes it at its tempo and `"time_stretch":p` changes its tempo in its key (a
+phase vocoder on the GPU in front of the same kernel).
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
 1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
 source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.

@@ -60,6 +60,11 @@ class WunSpeedBank(C.Structure):
     _fields_ = [("n", C.c_int32), ("up", C.c_int32 * 8), ("down", C.c_int32 * 8), ("table", C.c_void_p * 8)]
 
 
+class WunStretchJob(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("n_in", C.c_int32), ("n_out", C.c_int32), ("num", C.c_int32),
+                ("den", C.c_int32)]
+
+
 class WunOpHeadDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "C", "F", "S", "difference", "Ko", "padl", "Tfeat", "Tout", "B", "tanh", "training", "feat_bf16",
@@ -73,6 +78,7 @@ class WunOpHeadDesc(C.Structure):
 
 SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2                 # wun_snippet_source.flags
 SPEED_RATES, SPEED_MAX_RATIO = 8, 64                # WUN_SPEED_RATES, WUN_SPEED_MAX_RATIO: the rate bank of wun_gather_snippets_speed
+STRETCH_JOBS = 64                                   # WUN_STRETCH_JOBS: jobs per launch set of wun_time_stretch
 SNIPPET_ROWS = 24                                   # WUN_SNIPPET_ROWS: batch rows per launch of wun_gather_snippets
 
 SPEC_TT_Z, SPEC_TT_MEAN, SPEC_TT_VAR, SPEC_TT_ACT, SPEC_TT_DROPOUT = range(5)     # wun_spec_train_tensor kinds
@@ -252,6 +258,10 @@ _SIGS = {
     "wun_speed_source_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "wun_gather_snippets_speed": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, _P,
                                             _P, C.c_int32, _P, _P, _P]),
+    "wun_stretch_abi_size": (C.c_int32, []),
+    "wun_time_stretch_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_time_stretch_scratch_floats": (C.c_int64, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "wun_time_stretch": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "wun_op_conv1d": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
     "wun_op_conv1d_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
     "wun_op_conv1d_wgrad": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
@@ -337,6 +347,9 @@ def load():
     if lib.wun_speed_abi_size() != C.sizeof(WunSpeedBank):
         raise RuntimeError("libwun.so wun_speed_bank size %d != this binding's %d (stale library or binding)" % (
             lib.wun_speed_abi_size(), C.sizeof(WunSpeedBank)))
+    if lib.wun_stretch_abi_size() != C.sizeof(WunStretchJob):
+        raise RuntimeError("libwun.so wun_stretch_job size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_stretch_abi_size(), C.sizeof(WunStretchJob)))
     _lib = lib
     return lib
 

@@ -4,6 +4,7 @@
 // spectral loss) launches the forward body with its magnitude epilogue and the inverse body as an adjoint the same way.
 #pragma once
 #include "wun_device.h"
+#include "../../include/wun.h"
 
 namespace wun {
 
@@ -68,6 +69,19 @@ struct GlArgs {
     float momentum, scale;                   // scale = 1 / n_fft
 };
 
+// One launch set of the phase vocoder (wun_time_stretch): up to WUN_STRETCH_JOBS jobs by value.  Job j owns the
+// frames [fp[j], fp[j + 1]) of each of its C rows: frame f of (j, c) is frame row C fp[j] + c F_j + f of mag / dlt [rows][K] and
+// of the synthesis frames; the analysis workgroups [gp[j], gp[j + 1]) are its C ceil(F_j / FPW) groups of FPW frames, c-major.
+struct VocArgs {
+    wun_stretch_job job[WUN_STRETCH_JOBS];
+    long long fp[WUN_STRETCH_JOBS + 1];
+    long long gp[WUN_STRETCH_JOBS + 1];
+    const float* table;                      // wun_fft_design's
+    float* mag; float* dlt;                  // [rows][K]: |X_f| and the phase increment in turns; the phase kernel leaves Re Y, Im Y
+    int J, C, n_fft, hop, K;
+};
+static_assert(sizeof(VocArgs) <= 4096, "the argument block must fit HIP's kernel-argument limit");
+
 // wun_fft.hip: stft_fft_kernel / istft_fft_kernel of a.n_fft (a power of two in 64..8192) on stream s.  WUN_OK, or
 // WUN_ERR_UNSUPPORTED (wun_last_error() set, nothing launched) for an n_fft without a kernel.
 //   magnitude   the forward body with StftMagArgs' epilogue (the spectral loss and wun_stft_magnitude_fft)
@@ -81,6 +95,10 @@ int fft_launch_adjoint(const IstftGemmArgs& g, hipStream_t s);
 int fft_launch_spec_head(const SpecHeadArgs& a, hipStream_t s);
 //   griffin_lim gl_frame_kernel on the frame rows of g; given: c_0 is g.cre / g.cim and no forward transform runs
 int fft_launch_griffin_lim(const GlArgs& g, bool given, hipStream_t s);
+//   voc_analysis voc_analysis_kernel on the jobs of v: |X_f| and the phase increment of every frame row of v.fp, on v.gp[v.J]
+//               workgroups of fft_frames_per_workgroup(n_fft) frames (0 for an n_fft without a kernel)
+int fft_frames_per_workgroup(int n_fft);
+int fft_launch_voc_analysis(const VocArgs& v, hipStream_t s);
 // out[0], out[1] = the sums of part[e][0] and part[e][1] over e = 0 .. n - 1 in ascending e (one workgroup); n < 0: NaN into both
 void launch_gl_finish(const double* part, long long n, double* out, hipStream_t s);
 // D[p] = (float) sum_i w^2[p + i hop] over p + i hop < n_fft (float64, i ascending: istft_ola_kernel<true>'s normaliser), p < hop

@@ -5,6 +5,7 @@
 // the magnitude as its epilogue, the inverse one as the unscaled adjoint.  The spectrogram U-Net's backward from an audio gradient
 // (wun_spec_backward) is the forward body once more, on d_audio / D, with the mask gradient as its epilogue.
 // Griffin-Lim (wun_griffin_lim) runs both transforms of a frame in one workgroup, the projection between them.
+// The phase vocoder's analysis (wun_time_stretch) is the forward body twice per frame, one hop apart.
 //
 //   real transform   a frame of n_fft real samples is one complex FFT of M = n_fft / 2 points, z[m] = y[2m] + i y[2m+1], and a
 //                    split step:  E = (Z[k] + conj Z[M-k]) / 2,  O = (Z[k] - conj Z[M-k]) / 2i,  X[k] = E + W_N^k O,  k = 0..M
@@ -426,6 +427,78 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void gl_frame_kernel(GlArgs p) {
     }
 }
 
+// The analysis of the phase vocoder (wun_time_stretch; VocArgs, wun_fft.h): the workgroup owns FPW synthesis
+// frames of one (job, channel), found from the workgroup prefix in the arguments (uniform: scalar loads).  Frame f is analysed at
+// a_f = (f hop num) / den and one hop before it: P_f first, fft_fwd_frames' transform and split step with the bins kept in
+// registers, then X_f through the same LDS behind one barrier, and per bin the magnitude, the product X conj(P) in float64 (the
+// four products of float32 values are exact there, each sum is rounded once whether it is fused or not), its angle in turns less
+// the hop's advance, wrapped to [-1/2, 1/2] and rounded to float32.  Only |X_f| and that increment are stored: the spectra
+// never reach memory.  A frame slot behind the job's last frame runs on zeros and stores nothing; no lane leaves before the
+// last barrier.  Nothing outside [0, n_in) of the job's span is read.
+template <int LOGM>
+__global__ __launch_bounds__(WUN_FFT_BLOCK) void voc_analysis_kernel(VocArgs p) {
+    using G = FftGeom<LOGM>;
+    constexpr int M = G::M, N = G::N, TPF = G::TPF, NB = M / TPF + 1;
+    __shared__ float sre[2][G::PLANE];
+    __shared__ float sim[2][G::PLANE];
+    const long long wg = blockIdx.x;
+    int j = 0;
+    while (j + 1 < p.J && wg >= p.gp[j + 1]) ++j;
+    const wun_stretch_job jb = p.job[j];
+    const long long F = p.fp[j + 1] - p.fp[j];
+    const long long groups = (F + G::FPW - 1) / G::FPW, local = wg - p.gp[j];
+    const long long c = local / groups;                      // < C: the host sized gp
+    const int g = threadIdx.x / TPF, tl = threadIdx.x - g * TPF, base = g * M;
+    const long long f = (local - c * groups) * G::FPW + g;
+    const bool valid = f < F;
+    const long long t0 = valid ? (f * p.hop * jb.num) / jb.den - (N - p.hop) : 0;
+    const long long o = valid ? (p.C * p.fp[j] + c * F + f) * p.K : 0;
+    const float* __restrict__ x = jb.x + c;
+    const float* __restrict__ tw = p.table;
+    const float* __restrict__ win = p.table + 2 * N;
+    const long long T = jb.n_in;
+    const int C = p.C;
+    float pr[NB], pi[NB];
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long ts = pass ? t0 : t0 - p.hop;
+        fft_run<LOGM>([&](int a, float& re, float& im) {     // (fft_fwd_frames' load at the frame's own start)
+            const long long t = ts + 2 * a;
+            re = (valid && t >= 0 && t < T) ? x[t * C] * win[2 * a] : 0.f;
+            im = (valid && t + 1 >= 0 && t + 1 < T) ? x[(t + 1) * C] * win[2 * a + 1] : 0.f;
+        }, sre, sim, base, tl, tw);
+        const float* __restrict__ Zr = sre[G::RESULT];
+        const float* __restrict__ Zi = sim[G::RESULT];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int k = tl + i * TPF;                      // 0 .. M: the last round is lane 0's k = M
+            if (k <= M) {                                    // (fft_fwd_frames' split step)
+                const int ka = base + (k & (M - 1)), kb = base + ((M - k) & (M - 1));
+                const float ar = Zr[fft_swz(ka)], ai = Zi[fft_swz(ka)], cr = Zr[fft_swz(kb)], ci = Zi[fft_swz(kb)];
+                const float er = 0.5f * (ar + cr), ei = 0.5f * (ai - ci), odr = 0.5f * (ai + ci), odi = 0.5f * (cr - ar);
+                const float wc = tw[k], ws = tw[N + k];
+                const float xr = er + (wc * odr - ws * odi);
+                const float xi = (k == 0 || k == M) ? 0.f : ei + (wc * odi + ws * odr);
+                if (pass == 0) { pr[i] = xr; pi[i] = xi; }
+                else if (valid) {
+                    double qr = (double)xr, qi = (double)xi, adv = 0.0;
+                    if (f > 0) {
+                        const double a = (double)xr, b = (double)xi, u = (double)pr[i], v = (double)pi[i];
+                        qr = a * u + b * v;
+                        qi = b * u - a * v;
+                        adv = (double)((k * p.hop) & (N - 1)) / (double)N;
+                    }
+                    const double ang = (qr == 0.0 && qi == 0.0) ? 0.0 : atan2(qi, qr) / 6.283185307179586476925286766559;
+                    const double d = ang - adv;
+                    p.mag[o + k] = sqrtf(fmaf(xr, xr, xi * xi));
+                    p.dlt[o + k] = f > 0 ? (float)(d - rint(d)) : (float)ang;
+                }
+            }
+        }
+        if (pass == 0) __syncthreads();                      // every lane has read P_f: the next first stage may write that image
+    }
+}
+
 // one workgroup: chunks of 256 frames through LDS, lane 0 adds slot 0 and lane 64 slot 1 in ascending frame order
 __global__ __launch_bounds__(WUN_FFT_BLOCK) void gl_finish_kernel(const double* __restrict__ part, long long n, double* __restrict__ out) {
     __shared__ double buf[2][WUN_FFT_BLOCK];
@@ -519,6 +592,20 @@ int fft_launch_griffin_lim(const GlArgs& g, bool given, hipStream_t s) {
         const dim3 grid((unsigned)((g.M + FftGeom<LM>::FPW - 1) / FftGeom<LM>::FPW));
         if (given) hipLaunchKernelGGL((gl_frame_kernel<LM, true>), grid, dim3(WUN_FFT_BLOCK), 0, s, g);
         else hipLaunchKernelGGL((gl_frame_kernel<LM, false>), grid, dim3(WUN_FFT_BLOCK), 0, s, g);
+    });
+}
+
+int fft_frames_per_workgroup(int n_fft) {
+    int fpw = 0;
+    if (n_fft >= 64 && n_fft <= 8192 && !(n_fft & (n_fft - 1))) fpw = n_fft / 8 < WUN_FFT_BLOCK ? WUN_FFT_BLOCK / (n_fft / 8) : 1;
+    return fpw;
+}
+
+int fft_launch_voc_analysis(const VocArgs& v, hipStream_t s) {
+    return fft_dispatch("fft_launch_voc_analysis", v.n_fft, [&](auto L) {
+        constexpr int LM = decltype(L)::value;
+        static_assert(FftGeom<LM>::FPW == (FftGeom<LM>::N / 8 < WUN_FFT_BLOCK ? WUN_FFT_BLOCK / (FftGeom<LM>::N / 8) : 1), "fft_frames_per_workgroup");
+        hipLaunchKernelGGL(voc_analysis_kernel<LM>, dim3((unsigned)v.gp[v.J]), dim3(WUN_FFT_BLOCK), 0, s, v);
     });
 }
 

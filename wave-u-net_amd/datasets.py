@@ -324,6 +324,12 @@ AUGMENT_KEYS = ("remix", "channel_swap", "polarity", "speed")
 # the rate bank of wun_gather_snippets_speed (include/wun.h): (up, down) pairs, speed = down / up
 SPEED_RATES_DEFAULT = ((10, 9), (20, 19), (20, 21), (10, 11))      # speeds 0.9, 0.95, 1.05, 1.1
 SPEED_MAX_RATES, SPEED_MAX_RATIO = 8, 64                           # WUN_SPEED_RATES, WUN_SPEED_MAX_RATIO
+# the phase vocoder's augmentations (wun_time_stretch): probabilities, next to AUGMENT_KEYS
+VOCODER_KEYS = ("pitch_shift", "time_stretch")
+PITCH_SHIFT_RATES_DEFAULT = ((18, 17), (9, 8), (17, 18), (8, 9))   # (up, down): pitch times down / up, about -1, -2, +1, +2 semitones
+TIME_STRETCH_RATES_DEFAULT = ((10, 9), (20, 19), (20, 21), (10, 11))   # (num, den): tempo num / den
+VOCODER_FFT_DEFAULT = (2048, 512)
+_RATE_KEYS = {"speed_rates": "speed", "pitch_shift_rates": "pitch_shift", "time_stretch_rates": "time_stretch"}
 
 
 def speed_source_frames(input_frames, up, down):
@@ -332,57 +338,95 @@ def speed_source_frames(input_frames, up, down):
     return ((int(input_frames) - 1) * int(down)) // int(up) + 1
 
 
-def _check_speed_rates(rates):
-    """The bank as a tuple of (up, down) reduced by their gcd; ValueError for what wun_gather_snippets_speed refuses."""
+def _check_speed_rates(rates, key="speed_rates"):
+    """The bank as a tuple of (up, down) reduced by their gcd; ValueError for what wun_gather_snippets_speed refuses.  The
+    ratios of the vocoder's keys obey the same rules (wun_time_stretch has the same ceilings)."""
     if isinstance(rates, (str, bytes, dict)) or not hasattr(rates, "__len__"):
-        raise ValueError("augment['speed_rates'] must be a list of [up, down] pairs, got %r" % (rates,))
+        raise ValueError("augment[%r] must be a list of [up, down] pairs, got %r" % (key, rates))
     if not 1 <= len(rates) <= SPEED_MAX_RATES:
-        raise ValueError("augment['speed_rates'] holds 1 to %d pairs, got %d" % (SPEED_MAX_RATES, len(rates)))
+        raise ValueError("augment[%r] holds 1 to %d pairs, got %d" % (key, SPEED_MAX_RATES, len(rates)))
     out = []
     for pair in rates:
         ok = not isinstance(pair, (str, bytes, dict)) and hasattr(pair, "__len__") and len(pair) == 2 and all(
             isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v > 0 for v in pair)
         if not ok:
-            raise ValueError("augment['speed_rates']: every pair is [up, down] of positive integers, got %r" % (pair,))
+            raise ValueError("augment[%r]: every pair is [up, down] of positive integers, got %r" % (key, pair))
         g = math.gcd(int(pair[0]), int(pair[1]))
         up, down = int(pair[0]) // g, int(pair[1]) // g
         if up == down:
-            raise ValueError("augment['speed_rates']: %r is the unit rate 1/1" % (pair,))
+            raise ValueError("augment[%r]: %r is the unit rate 1/1" % (key, pair))
         if max(up, down) > SPEED_MAX_RATIO or down > 2 * up or up > 2 * down:
-            raise ValueError("augment['speed_rates']: %r needs max(up, down) <= %d after reduction and a speed down / up in "
-                             "[1/2, 2]" % (pair, SPEED_MAX_RATIO))
+            raise ValueError("augment[%r]: %r needs max(up, down) <= %d after reduction and a speed down / up in "
+                             "[1/2, 2]" % (key, pair, SPEED_MAX_RATIO))
         if (up, down) in out:
-            raise ValueError("augment['speed_rates']: %r occurs twice (after reduction)" % (pair,))
+            raise ValueError("augment[%r]: %r occurs twice (after reduction)" % (key, pair))
         out.append((up, down))
     return tuple(out)
+
+
+def _check_vocoder_fft(res):
+    ok = not isinstance(res, (str, bytes, dict)) and hasattr(res, "__len__") and len(res) == 2 and all(
+        isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v > 0 for v in res)
+    if ok:
+        n_fft, hop = int(res[0]), int(res[1])
+        ok = 64 <= n_fft <= 8192 and n_fft & (n_fft - 1) == 0 and hop & (hop - 1) == 0 and hop <= n_fft // 4
+    if not ok:
+        raise ValueError("augment['vocoder_fft'] must be [n_fft, hop]: n_fft a power of two in 64..8192, hop a power of two at "
+                         "most n_fft / 4 (wun_time_stretch), got %r" % (res,))
+    return n_fft, hop
 
 
 def check_augment(model_config, augment):
     """{key: probability} of the active augmentations (probability > 0); with an active "speed" also "speed_rates": the bank
     as a tuple of reduced (up, down) pairs (augment["speed_rates"], default SPEED_RATES_DEFAULT).  ValueError for an unknown
     key, a probability outside [0, 1] (NaN included), channel_swap on a mono config, speed_rates without an active speed and
-    a bank the library would refuse (1/1, duplicates after reduction, more than 8 pairs, a ratio above 64 or outside [1/2, 2])."""
+    a bank the library would refuse (1/1, duplicates after reduction, more than 8 pairs, a ratio above 64 or outside [1/2, 2]).
+    The vocoder's keys (VOCODER_KEYS) follow the same rules: an active "pitch_shift" / "time_stretch" brings its
+    "pitch_shift_rates" / "time_stretch_rates" (defaults PITCH_SHIFT_RATES_DEFAULT / TIME_STRETCH_RATES_DEFAULT), either one
+    "vocoder_fft": (n_fft, hop) (default VOCODER_FFT_DEFAULT), and an active pitch_shift "bank_rates": speed_rates followed
+    by the pitch_shift_rates not among them -- the resampler's bank, ValueError when it exceeds 8 entries."""
     if augment is None:
         return {}
     if not isinstance(augment, dict):
         raise ValueError("augment must be a dict with the optional keys %s, got %r" % (", ".join(AUGMENT_KEYS), augment))
     active = {}
     for key, p in augment.items():
-        if key == "speed_rates":
+        if key in _RATE_KEYS or key == "vocoder_fft":
             continue
-        if key not in AUGMENT_KEYS:
-            raise ValueError("unknown augmentation %r (have: %s)" % (key, ", ".join(AUGMENT_KEYS)))
+        if key not in AUGMENT_KEYS and key not in VOCODER_KEYS:
+            raise ValueError("unknown augmentation %r (have: %s)" % (key, ", ".join(AUGMENT_KEYS + VOCODER_KEYS)))
         if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:
             raise ValueError("augment[%r] must be a probability in [0, 1], got %r" % (key, p))
         if float(p) > 0.0:
             active[key] = float(p)
     if "channel_swap" in active and model_config["mono_downmix"]:
         raise ValueError("augment['channel_swap'] needs two channels; this config is mono (mono_downmix=True)")
-    if "speed" in active:
-        active["speed_rates"] = _check_speed_rates(augment.get("speed_rates", SPEED_RATES_DEFAULT))
-    elif "speed_rates" in augment:
-        raise ValueError("augment['speed_rates'] needs an active augment['speed'] (a probability > 0)")
+    defaults = {"speed_rates": SPEED_RATES_DEFAULT, "pitch_shift_rates": PITCH_SHIFT_RATES_DEFAULT,
+                "time_stretch_rates": TIME_STRETCH_RATES_DEFAULT}
+    for rkey, key in _RATE_KEYS.items():
+        if key in active:
+            active[rkey] = _check_speed_rates(augment.get(rkey, defaults[rkey]), rkey)
+        elif rkey in augment:
+            raise ValueError("augment[%r] needs an active augment[%r] (a probability > 0)" % (rkey, key))
+    if any(k in active for k in VOCODER_KEYS):
+        active["vocoder_fft"] = _check_vocoder_fft(augment.get("vocoder_fft", VOCODER_FFT_DEFAULT))
+    elif "vocoder_fft" in augment:
+        raise ValueError("augment['vocoder_fft'] needs an active augment['pitch_shift'] or augment['time_stretch']")
+    if "pitch_shift" in active:
+        bank = tuple(active.get("speed_rates", ()))
+        bank += tuple(r for r in active["pitch_shift_rates"] if r not in bank)
+        if len(bank) > SPEED_MAX_RATES:
+            raise ValueError("augment: speed_rates and pitch_shift_rates together need %d entries of the resampler's bank of %d"
+                             % (len(bank), SPEED_MAX_RATES))
+        active["bank_rates"] = bank
     return active
+
+
+def _refuse_vocoder(active, who):
+    for key in VOCODER_KEYS:
+        if key in active:
+            raise ValueError("augment[%r] needs the job stream: use datasets.vocoder_descriptors, which yields (rec, mix_mode, "
+                             "rate, jobs) -- %s does not carry jobs" % (key, who))
 
 
 def augmented_descriptors(model_config, lengths, input_frames, output_frames, rng, augment=None, aug_rng=None):
@@ -400,10 +444,12 @@ def augmented_descriptors(model_config, lengths, input_frames, output_frames, rn
     rng, so the base stream does not shift.  Only keys with a probability > 0 draw, in this order per snippet: one uniform for
     remix; if taken, per source s >= 1 a track (integers(0, n_tracks)) then a start (integers(0, len - Tin)); one uniform per
     source for the swap; one uniform per source for the polarity.  An active "speed" is refused with a ValueError: its stream
-    carries a rate per source (speed_descriptors)."""
-    if "speed" in check_augment(model_config, augment):
+    carries a rate per source (speed_descriptors); so are the vocoder's keys, whose stream carries jobs (vocoder_descriptors)."""
+    active = check_augment(model_config, augment)
+    if "speed" in active:
         raise ValueError("augment['speed'] needs the rate stream: use datasets.speed_descriptors, which yields (rec, mix_mode, rate)")
-    for rec, mix_mode, _ in _descriptors(model_config, lengths, input_frames, output_frames, rng, augment, aug_rng):
+    _refuse_vocoder(active, "augmented_descriptors")
+    for rec, mix_mode, _, _ in _descriptors(model_config, lengths, input_frames, output_frames, rng, augment, aug_rng):
         yield rec, mix_mode
 
 
@@ -417,7 +463,34 @@ def speed_descriptors(model_config, lengths, input_frames, output_frames, rng, a
     Draws (aug_rng only, after remix, swap and polarity): one random(); if taken, integers(0, R) per source s = 0..S-1 for a
     remixed snippet, else one integers(0, R) for all.  Placement takes no draws: a rated source reads n_src =
     speed_source_frames(Tin, up, down) frames of its padded track j (length len_j) around the centre of its unit window at
-    pos -- it starts at clip(pos + (Tin - n_src) // 2, 0, len_j - n_src) -- and a track shorter than n_src keeps the unit rate."""
+    pos -- it starts at clip(pos + (Tin - n_src) // 2, 0, len_j - n_src) -- and a track shorter than n_src keeps the unit rate.
+    The vocoder's keys are refused with a ValueError: their stream carries jobs (vocoder_descriptors)."""
+    _refuse_vocoder(check_augment(model_config, augment), "speed_descriptors")
+    return _strip_jobs(_descriptors(model_config, lengths, input_frames, output_frames, rng, augment, aug_rng))
+
+
+def _strip_jobs(stream):
+    for rec, mix_mode, rate, _ in stream:
+        yield rec, mix_mode, rate
+
+
+def vocoder_descriptors(model_config, lengths, input_frames, output_frames, rng, augment=None, aug_rng=None):
+    """speed_descriptors with the phase vocoder's augmentations (wun_time_stretch): yields (rec, mix_mode, rate,
+    jobs) per snippet, jobs an int64 [S, 4] of (span_start, n_span, num, den) -- the span of the source's plane that a job
+    stretches at the tempo num / den before the gather reads its output -- with n_span = 0 for a source without a job.  Without
+    the vocoder's keys (rec, mix_mode, rate) are exactly speed_descriptors' and jobs is zero.
+      augment["pitch_shift"] = p, augment["pitch_shift_rates"] = [[up, down], ...] (optional): with probability p the snippet is
+      transposed to the pitch down / up at its own tempo: a job stretches n_span = ceil(n_src up / down) frames to n_src =
+      speed_source_frames(Tin, up, down) at num / den = up / down, and the gather resamples those to Tin through the bank entry
+      (up, down) of check_augment's "bank_rates" (rate = its index + 1).
+      augment["time_stretch"] = p, augment["time_stretch_rates"] = [[num, den], ...] (optional): with probability p the snippet
+      is played at the tempo num / den in its own key: a job stretches n_span = ceil(Tin num / den) frames to Tin; rate 0.
+    A snippet takes at most one of speed, pitch_shift and time_stretch.  Draws (aug_rng only, after speed's; a snippet that took
+    an earlier one draws nothing for the later ones), for pitch_shift then time_stretch: one random(); if taken, integers(0, R)
+    per source s = 0..S-1 for a remixed snippet, else one for all, so the stems of one song share the ratio.  Placement takes no
+    draws: the span starts at clip(pos + (Tin - n_span) // 2, 0, len_j - n_span) of the source's padded track j, and a track
+    shorter than n_span keeps the plain window (no job, rate 0).  rec["start"] of a source with a job is the span's start; the
+    consumer points it at the job's output (FusedSnippetSource: a slot behind the planes).  An active key makes mix_mode 1."""
     return _descriptors(model_config, lengths, input_frames, output_frames, rng, augment, aug_rng)
 
 
@@ -429,21 +502,26 @@ def _descriptors(model_config, lengths, input_frames, output_frames, rng, augmen
     if active and aug_rng is None:
         aug_rng = np.random.default_rng([1337, 1])
     bank = active.get("speed_rates", ())
+    bank_all = active.get("bank_rates", bank)
+    vocoder = [k for k in VOCODER_KEYS if k in active]
     unit = np.zeros(S, dtype=np.uint8)                    # shared by every snippet at the unit rate (read-only)
     unit.setflags(write=False)
+    no_jobs = np.zeros((S, 4), dtype=np.int64)            # shared by every snippet without a job (read-only)
+    no_jobs.setflags(write=False)
     for ti, pos, gains in snippet_descriptors(model_config, lengths, input_frames, output_frames, "train", rng):
         rec = np.zeros(S, dtype=SNIPPET_DTYPE)
-        rate = unit
+        rate, jobs = unit, no_jobs
         rec["start"] = offset[ti] + pos
         rec["gain"] = gains if gains is not None else 1.0
-        where = [(int(ti), int(pos))] * S if bank else None      # (track, start inside it) of every source: speed places by it
+        # (track, start inside it) of every source: speed and the vocoder place by it
+        where = [(int(ti), int(pos))] * S if bank or vocoder else None
         remixed = "remix" in active and aug_rng.random() < active["remix"]
         if remixed:
             for s in range(1, S):
                 tj = int(aug_rng.integers(0, n_tracks))
                 p = int(random_positions(lengths[tj], input_frames, None, aug_rng))
                 rec["start"][s] = offset[tj] + p
-                if bank:
+                if where is not None:
                     where[s] = (tj, p)
         if "channel_swap" in active:
             for s in range(S):
@@ -453,7 +531,8 @@ def _descriptors(model_config, lengths, input_frames, output_frames, rng, augmen
             for s in range(S):
                 if aug_rng.random() < active["polarity"]:
                     rec["flags"][s] |= SNIPPET_NEGATE
-        if "speed" in active and aug_rng.random() < active["speed"]:
+        taken = "speed" in active and aug_rng.random() < active["speed"]
+        if taken:
             if remixed:
                 picks = [int(aug_rng.integers(0, len(bank))) for _ in range(S)]
             else:
@@ -466,7 +545,29 @@ def _descriptors(model_config, lengths, input_frames, output_frames, rng, augmen
                     continue                              # the track cannot fill the window at this speed: unit rate
                 rate[s] = picks[s] + 1
                 rec["start"][s] = offset[tj] + min(max(p + (input_frames - n_src) // 2, 0), lengths[tj] - n_src)
-        yield rec, int(gains is not None or bool(active)), rate
+        for key in vocoder:
+            if taken or not aug_rng.random() < active[key]:
+                continue
+            taken = True
+            ratios = active[key + "_rates"]
+            if remixed:
+                picks = [int(aug_rng.integers(0, len(ratios))) for _ in range(S)]
+            else:
+                picks = [int(aug_rng.integers(0, len(ratios)))] * S
+            rate, jobs = np.zeros(S, dtype=np.uint8), np.zeros((S, 4), dtype=np.int64)
+            for s in range(S):
+                tj, p = where[s]
+                num, den = ratios[picks[s]]
+                n_out = speed_source_frames(input_frames, num, den) if key == "pitch_shift" else input_frames
+                n_span = -((-n_out * num) // den)
+                if lengths[tj] < n_span:
+                    continue                              # the track cannot fill the span: the plain window
+                if key == "pitch_shift":
+                    rate[s] = bank_all.index((num, den)) + 1
+                start = offset[tj] + min(max(p + (input_frames - n_span) // 2, 0), lengths[tj] - n_span)
+                rec["start"][s] = start
+                jobs[s] = (start, n_span, num, den)
+        yield rec, int(gains is not None or bool(active)), rate, jobs
 
 
 class FusedSnippetSource(object):
@@ -478,7 +579,10 @@ class FusedSnippetSource(object):
     partition "train": endless; augmented_descriptors' stream -- without `augment` bit-identical to get_dataset(..., "train",
     ...) and DeviceSnippetSource for equal seeds; with it the remix / channel-swap / polarity / speed augmentations on top
     (draws from np.random.default_rng([seed, 1])); with "speed" the batch comes from wun_gather_snippets_speed, which resamples
-    the rated sources inside the same launch (speed_descriptors; rates() shows the next batch's rate indices).  Any other partition: a finite iterator over every hop of every track in order, the
+    the rated sources inside the same launch (speed_descriptors; rates() shows the next batch's rate indices); with "pitch_shift"
+    or "time_stretch" (vocoder_descriptors; jobs() shows the next batch's jobs) every source plane carries a tail of B slots, one
+    wun_time_stretch call per batch stretches the jobs' spans into the slots of their rows, and the same gather reads them
+    there -- resampling them for pitch_shift.  Any other partition: a finite iterator over every hop of every track in order, the
     remainder dropped -- the batches of get_dataset(..., partition, ...); a call behind the last batch raises StopIteration.
     descriptors() shows the next batch's table without touching the GPU."""
 
@@ -513,28 +617,51 @@ class FusedSnippetSource(object):
                 cat[k].append(p[k])
         self.channels = int(cat["mix"][0].shape[1])
         self.plane_frames = int(sum(lens))
-        self.data = {k: torch.from_numpy(np.concatenate(v)).to(self.device) for k, v in cat.items()}
+        # the vocoder's slots: B per source plane behind the tracks, each as long as the longest job output (only with its keys)
+        self.vocoder_fft = active.get("vocoder_fft")
+        self.bank_rates = active.get("bank_rates", active.get("speed_rates", ()))
+        self.slot_frames = 0
+        if self.vocoder_fft is not None:
+            outs = [speed_source_frames(self.t_in, up, down) for up, down in active.get("pitch_shift_rates", ())]
+            self.slot_frames = max(outs + [self.t_in] if "time_stretch" in active else outs)
+        self.gather_frames = self.plane_frames + self.batch * self.slot_frames      # what the gather may address
+        tail = self.batch * self.slot_frames
+
+        def plane(k, parts):
+            if tail and k != "mix":
+                parts = parts + [np.zeros((tail, self.channels), np.float32)]
+            return torch.from_numpy(np.concatenate(parts)).to(self.device)
+        self.data = {k: plane(k, v) for k, v in cat.items()}
         self._planes = (_lib.C.c_void_p * len(self.names))(*[self.data[k].data_ptr() for k in self.names])
         rng = rng if rng is not None else np.random.default_rng(seed)
         if partition == "train":
             self.mix_mode = int(bool(model_config["augmentation"]) or bool(active))
-            self.stream = speed_descriptors(model_config, lens, self.t_in, self.t_out, rng, augment,
-                                            np.random.default_rng([seed, 1]))
+            self.stream = vocoder_descriptors(model_config, lens, self.t_in, self.t_out, rng, augment,
+                                              np.random.default_rng([seed, 1]))
         else:
             self.mix_mode = 0
             self.stream = self._ordered(snippet_descriptors(model_config, lens, self.t_in, self.t_out, partition, rng), lens)
-        self._next = self._next_rates = None
+        self._next = self._next_rates = self._next_jobs = None
+        self._no_jobs = np.zeros((self.batch, len(self.names), 4), dtype=np.int64)
+        self._no_jobs.setflags(write=False)
+        self._scratch = None
+        if self.vocoder_fft is not None:                 # allocated once: every source of every row a job of the longest output
+            from . import vocoder
+            worst = np.zeros(self.batch * len(self.names), vocoder.JOB_DTYPE)
+            worst["n_out"], worst["num"], worst["den"] = self.slot_frames, 1, 1
+            self._scratch = torch.empty(vocoder.scratch_floats(worst, self.channels, *self.vocoder_fft), dtype=torch.float32,
+                                        device=self.device)
         # the rate bank of wun_gather_snippets_speed: one table per ratio, designed and uploaded once
-        self.speed_rates = active.get("speed_rates", ())
+        self.speed_rates = active.get("speed_rates", ())     # (bank_rates: these, then pitch_shift's)
         self._bank = None
         self._unit_rates = np.zeros((self.batch, len(self.names)), dtype=np.uint8)
         self._unit_rates.setflags(write=False)
-        if self.speed_rates:
+        if self.bank_rates:
             from . import resample
-            self._tables = [torch.from_numpy(resample.design(up, down)).to(self.device) for up, down in self.speed_rates]
+            self._tables = [torch.from_numpy(resample.design(up, down)).to(self.device) for up, down in self.bank_rates]
             self._bank = _lib.WunSpeedBank()
-            self._bank.n = len(self.speed_rates)
-            for i, ((up, down), tab) in enumerate(zip(self.speed_rates, self._tables)):
+            self._bank.n = len(self.bank_rates)
+            for i, ((up, down), tab) in enumerate(zip(self.bank_rates, self._tables)):
                 self._bank.up[i], self._bank.down[i], self._bank.table[i] = up, down, tab.data_ptr()
 
     def _ordered(self, stream, lens):
@@ -543,16 +670,18 @@ class FusedSnippetSource(object):
             rec = np.zeros(len(self.names), dtype=SNIPPET_DTYPE)
             rec["start"] = offset[ti] + pos
             rec["gain"] = 1.0
-            yield rec, 0, np.zeros(len(self.names), dtype=np.uint8)
+            yield rec, 0, np.zeros(len(self.names), dtype=np.uint8), self._no_jobs[0]
 
     def descriptors(self):
         """The next batch's table, SNIPPET_DTYPE [B, S] (host only: nothing is launched).  StopIteration behind the last
-        whole batch of a finite partition."""
+        whole batch of a finite partition.  A source with a job (jobs()) starts at its slot: frame plane_frames + b slot_frames
+        of its plane, where the job's output lies when the gather runs."""
         if self._next is None:
-            rows, rates = [], []
-            for rec, _, rate in self.stream:
+            rows, rates, jobs = [], [], []
+            for rec, _, rate, job in self.stream:
                 rows.append(rec)
                 rates.append(rate)
+                jobs.append(job)
                 if len(rows) == self.batch:
                     break
             if len(rows) < self.batch:                   # remainder dropped (batch_and_drop_remainder, Datasets.py:215)
@@ -560,6 +689,10 @@ class FusedSnippetSource(object):
             self._next = np.ascontiguousarray(np.stack(rows))
             # (without a bank every rate is the shared zero row: one table for all batches, nothing stacked)
             self._next_rates = np.ascontiguousarray(np.stack(rates)) if self._bank is not None else self._unit_rates
+            self._next_jobs = np.ascontiguousarray(np.stack(jobs)) if self.vocoder_fft is not None else self._no_jobs
+            if self.vocoder_fft is not None:
+                slot = self.plane_frames + self.slot_frames * np.arange(self.batch, dtype=np.int64)
+                self._next["start"] = np.where(self._next_jobs[:, :, 1] > 0, slot[:, None], self._next["start"])
         return self._next
 
     def rates(self):
@@ -568,12 +701,51 @@ class FusedSnippetSource(object):
         self.descriptors()
         return self._next_rates
 
-    def gather(self, table, mix_mode, rates=None):
+    def jobs(self):
+        """The next batch's vocoder jobs, int64 [B, S, 4] of (span_start, n_span, num, den) in frames of the source's plane
+        (n_span = 0: no job); all zero without an active "pitch_shift" / "time_stretch".  Host only, like descriptors(), and
+        about the same batch: the job of (b, s) is stretched into slot b of plane s, n_src frames of it for a rated source
+        (rates()), Tin otherwise."""
+        self.descriptors()
+        return self._next_jobs
+
+    def job_table(self, jobs, rates=None):
+        """The host table of wun_time_stretch (vocoder.JOB_DTYPE) for an int64 [B, S, 4] table of jobs (jobs()): the span of
+        (b, s) in plane s into slot b of that plane, n_src frames of it for a rated source (`rates`, uint8 [B, S]), else Tin."""
+        from . import vocoder
+        jobs = np.asarray(jobs, dtype=np.int64)
+        B, S, C = int(jobs.shape[0]), len(self.names), self.channels
+        if jobs.shape != (B, S, 4) or B > self.batch:
+            raise ValueError("jobs must be int64 [B <= %d, %d, 4], got %r" % (self.batch, S, jobs.shape))
+        bs = np.argwhere(jobs[:, :, 1] > 0)
+        if len(bs) and self.vocoder_fft is None:
+            raise ValueError("a job needs a source built with augment['pitch_shift'] or augment['time_stretch']")
+        table = np.zeros(len(bs), vocoder.JOB_DTYPE)
+        for i, (b, s) in enumerate(bs):
+            start, n_span, num, den = (int(v) for v in jobs[b, s])
+            r = int(rates[b, s]) if rates is not None else 0
+            n_out = speed_source_frames(self.t_in, *self.bank_rates[r - 1]) if r else self.t_in
+            base = self.data[self.names[s]].data_ptr()
+            table[i] = (base + 4 * C * start, base + 4 * C * (self.plane_frames + b * self.slot_frames), n_span, n_out, num, den)
+        return table
+
+    def stretch(self, jobs, rates=None):
+        """One wun_time_stretch call on the current stream: the jobs of an int64 [B, S, 4] table (jobs()) into the slots of
+        their rows.  Nothing is launched for a table without jobs."""
+        from . import vocoder
+        table = self.job_table(jobs, rates)
+        if len(table):
+            vocoder.run(table, self.channels, self.vocoder_fft[0], self.vocoder_fft[1], self._scratch, self.device)
+
+    def gather(self, table, mix_mode, rates=None, jobs=None):
         """(mix, targets) of a SNIPPET_DTYPE table [B, S] through wun_gather_snippets, on the current stream; with `rates`
-        (uint8 [B, S]) that hold a non-zero, through wun_gather_snippets_speed and this source's rate bank."""
+        (uint8 [B, S]) that hold a non-zero, through wun_gather_snippets_speed and this source's rate bank; with `jobs`
+        (stretch) the vocoder's call first, on the same stream."""
         import torch
         table = np.ascontiguousarray(table, dtype=SNIPPET_DTYPE)
         B, S, C = int(table.shape[0]), len(self.names), self.channels
+        if jobs is not None:
+            self.stretch(jobs, rates)
         if rates is not None:
             rates = np.ascontiguousarray(rates, dtype=np.uint8)
             if rates.shape != (B, S):
@@ -588,11 +760,11 @@ class FusedSnippetSource(object):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             if rates is None:
                 self._lib_mod.check(self._lib.wun_gather_snippets(
-                    self._planes, self.data["mix"].data_ptr(), self.plane_frames, C, S, B, self.t_in, self.t_out,
+                    self._planes, self.data["mix"].data_ptr(), self.gather_frames, C, S, B, self.t_in, self.t_out,
                     table.ctypes.data, int(mix_mode), mix.data_ptr(), targets.data_ptr(), stream))
             else:
                 self._lib_mod.check(self._lib.wun_gather_snippets_speed(
-                    self._planes, self.data["mix"].data_ptr(), self.plane_frames, C, S, B, self.t_in, self.t_out,
+                    self._planes, self.data["mix"].data_ptr(), self.gather_frames, C, S, B, self.t_in, self.t_out,
                     table.ctypes.data, rates.ctypes.data, self._lib_mod.C.addressof(self._bank), int(mix_mode), mix.data_ptr(),
                     targets.data_ptr(), stream))
         return mix, targets
@@ -600,8 +772,9 @@ class FusedSnippetSource(object):
     def __call__(self):
         table = self.descriptors()
         rates = self._next_rates if self._bank is not None else None
-        self._next = self._next_rates = None
-        return self.gather(table, self.mix_mode, rates)
+        jobs = self._next_jobs if self.vocoder_fft is not None else None
+        self._next = self._next_rates = self._next_jobs = None
+        return self.gather(table, self.mix_mode, rates, jobs)
 
     def __iter__(self):
         return self

@@ -15,7 +15,9 @@ model_config["data_producer"] = "fused" (default "torch") takes the batches of t
 datasets.FusedSnippetSource -- one HIP kernel per batch out of tracks resident in HBM (wun_gather_snippets)
 -- instead of DeviceSnippetSource's torch operators / the host pipeline of get_dataset: the same batches, bit for bit.
 model_config["augment"] = {"remix": p, "channel_swap": p, "polarity": p, "speed": p, "speed_rates": [[up, down], ...]} (fused
-producer only; datasets.speed_descriptors) adds the source-level augmentations to the training batches.
+producer only; datasets.speed_descriptors) adds the source-level augmentations to the training batches; "pitch_shift": p and
+"time_stretch": p (with "pitch_shift_rates", "time_stretch_rates", "vocoder_fft"; datasets.vocoder_descriptors)
+add the phase vocoder's two.
 """
 import json
 import os
