@@ -944,6 +944,64 @@ int wun_scatter_windows(const wun_plan* plan, const float* outputs, const int64_
 int wun_separate_track(const wun_plan* plan, const float* params, const float* track_tc, int64_t n_frames,
                        float* workspace, float* outputs, float* preds, void* stream);
 
+/* ---- blended separation: overlapping hops and shifted passes ---------------
+ * Every frame of the result is a weighted mean over every window that covers it, taken in one fixed order.
+ * Geometry: Tout = the hop's output frames, V = overlap_frames (0 <= V <= Tout - 1), H = Tout - V the stride.  A pass with
+ * shift s >= 0 has windows at p_k = k H - s, k = 0 .. K - 1, K = 1 + ceil(max(0, n_frames + s - Tout) / H): the last window
+ * is not re-aligned, it hangs over the end of the track.  The window list of a separation is its passes one behind the other
+ * in the order of the shifts, windows inside a pass in order of k; g is the index in that list.
+ * Weight of frame t of a window, a float32 trapezoid:  w[t] = (float)min(t + 1, Tout - t, V + 1) / (float)(V + 1), one
+ * correctly rounded division, without the t + 1 term for a window flagged WUN_BLEND_NO_RISE (the first of a pass) and without
+ * the Tout - t term for one flagged WUN_BLEND_NO_FALL (the last): the weight is 1 there.
+ * Result, for every frame f, source s and channel c:  acc = den = +0 (float32);  for g ascending over the windows covering f:
+ * acc = fmaf(w_g, x_g, acc), den = den + w_g;  pred = acc / den (correctly rounded), +0 where nothing covers f.
+ * acc and den live in `preds` and `den` as float32 between calls, so a frame's chain is the same numbers however the window
+ * list is cut into calls, batches or launches: the result's bits do not depend on it.  Averaging over shifts is this mean over
+ * the union of the passes' windows, not a mean of per-pass results.  (A frame that a single weight-1 window covers keeps that
+ * window's value: fmaf(1, x, +0) / 1 == x, with -0 becoming +0.) */
+typedef struct wun_blend_window {     /* 16 bytes */
+    int64_t pos;     /* first frame of the window in preds; may be negative or beyond pred_frames (clipped) */
+    int32_t row;     /* row of `outputs` that holds the window's Tout frames */
+    int32_t flags;   /* WUN_BLEND_NO_RISE | WUN_BLEND_NO_FALL */
+} wun_blend_window;
+#define WUN_BLEND_NO_RISE 1
+#define WUN_BLEND_NO_FALL 2
+int32_t wun_blend_abi_size(void);     /* sizeof(wun_blend_window) */
+
+/* One pass's table: windows[k] = {k H - shift, row = k, NO_RISE for k == 0 | NO_FALL for k == K - 1} (the caller renumbers the
+ * rows per chunk).  Returns K and writes windows[cap] (NULL: count only).  Host only.  WUN_ERR_INVALID for output_frames < 1,
+ * n_frames < 1, overlap_frames outside [0, output_frames - 1], shift < 0 or a cap below K. */
+int64_t wun_blend_positions(int64_t output_frames, int64_t n_frames, int64_t overlap_frames, int64_t shift,
+                            wun_blend_window* windows, int64_t cap);
+
+/* The accumulation above for the windows of one table, in table order (the caller's ascending g), into preds (acc) and den,
+ * which the caller zeroed before the first call of a separation.  Independent of any plan.  Destination-driven: the host cuts
+ * the windows, clipped to [0, pred_frames), into runs of frames whose covering set is constant; one lane owns one 16-byte
+ * granule of preds and walks the run's covering rows -- one writer per float per launch, no atomics.  A covering set larger
+ * than 4 rows continues in the next launch on `stream`.
+ *   outputs : device, [S, B, Tout, C];  windows : HOST, nwin entries (copied into the launches);  C is 1 or 2
+ *   preds   : device, [S, pred_frames, C];  den : device, [pred_frames]
+ * WUN_ERR_INVALID for a null pointer, a size out of range, a row outside [0, B), unknown flag bits, overlap_frames outside
+ * [0, Tout - 1] or a pointer that is not 4-byte aligned. */
+int wun_blend_windows(const float* outputs, int64_t S, int64_t B, int64_t Tout, int64_t C, const wun_blend_window* windows,
+                      int64_t nwin, int64_t overlap_frames, float* preds, float* den, int64_t pred_frames, void* stream);
+
+/* preds[s][f][c] = den[f] != 0 ? preds[s][f][c] / den[f] : +0, in place. */
+int wun_blend_finish(float* preds, const float* den, int64_t S, int64_t pred_frames, int64_t C, void* stream);
+
+/* The whole loop: preds and den zeroed (hipMemsetAsync), the window list of `shifts` walked in chunks of the plan's batch
+ * (chunks run across pass boundaries, a short last chunk runs as zero rows), per chunk the forward pass on windows read from
+ * the track (training = 0) then wun_blend_windows, at the end wun_blend_finish; all on `stream`.
+ *   track_tc : device, [track_frames, C]: lead + pad zero frames, the track, zeros; pad = (Tin - Tout) / 2.  The window at
+ *              pred position p reads track_tc[lead + p .. lead + p + Tin)
+ *   shifts   : HOST, nshifts frame offsets >= 0
+ *   preds    : device, [S, n_frames, C]; den : device, [n_frames]; every frame is covered
+ * WUN_ERR_INVALID for a null pointer, an odd Tin - Tout, a bad size, a misaligned pointer, or a window of a pass outside
+ * [0, track_frames] (lead >= every shift, and enough zeros behind for the overhanging last hop); the message names it. */
+int wun_separate_track_blend(const wun_plan* plan, const float* params, const float* track_tc, int64_t track_frames,
+                             int64_t lead, int64_t n_frames, int64_t overlap_frames, const int64_t* shifts, int64_t nshifts,
+                             float* workspace, float* outputs, float* preds, float* den, void* stream);
+
 /* ---- training batches from resident tracks (Datasets.py:29-34, Utils.py:26-42) --------------
  * One batch of the reference's snippet pipeline, and the source-level augmentations around it, in one kernel: the sources of
  * a data set live on the device as S planes [plane_frames, C] (the zero-padded tracks one behind the other) and, with

@@ -28,6 +28,9 @@ masks the estimates against the mix's STFT before they are written / scored (pos
 `phase_iterations=N` (predict, evaluate; cfg.unet_spectrogram* only) refines the phase of the network's source magnitudes with N
 Griffin-Lim iterations from the mix's phase (the reference's spectrogramToAudioFile, Utils.py:125-173) instead of keeping the mix's
 phase; the refined audio is normalised by the window-square sum over the covering frames.  Absent or 0: the default audio output.
+`overlap=0.25 shifts=4` (predict, evaluate; or model_config.separation={"overlap":0.25,"shifts":4}) lets neighbouring hops share a
+quarter of a hop, cross-faded, and averages 4 passes whose hop grids are shifted by 0 .. max_shift frames (max_shift=<frames>,
+default expected_sr // 2; shifts=[0,3,700] names the offsets): about shifts / (1 - overlap) times the forward passes.
 `train` takes the spectral objective as `model_config.spectral_loss={"resolutions":[[4096,1024]],"transform":"fft","terms":{"sc":1,
 "log_mag_l1":1},"log_eps":4.0}`: `"transform":"fft"` lifts the loss's n_fft limit from 2048 to 8192 in the same way ("gemm" is the default).
 `train` and `test` take `model_config.data_producer=fused` to produce their batches with one HIP kernel out of tracks resident in
@@ -87,6 +90,17 @@ def _phase_iterations(opts):
     return n
 
 
+def _separation(opts, model_config):
+    """overlap= / shifts= / max_shift=, else model_config["separation"]: checked here, so that a bad value ends the command at once."""
+    from wave_u_net_amd.evaluate import blend_options, separation_options
+    try:
+        kw = separation_options(model_config, opts.get("overlap"), opts.get("shifts"), opts.get("max_shift"))
+        blend_options(kw["overlap"], kw["shifts"], kw["max_shift"], model_config["expected_sr"])
+    except (ValueError, TypeError) as e:
+        raise SystemExit("overlap / shifts / max_shift: %s" % e)
+    return kw
+
+
 def main(argv=None):
     cmd, name, overrides, opts = _parse(sys.argv[1:] if argv is None else argv)
     import wave_u_net_amd as wun
@@ -119,7 +133,7 @@ def main(argv=None):
         folder = evaluate.produce_dataset_estimates(model_config, opts.get("model_path"), opts["data_root"],
                                                     opts["estimates_path"], partition=opts.get("partition", "test"),
                                                     postfilter=_postfilter(opts, model_config),
-                                                    phase_iterations=_phase_iterations(opts))
+                                                    phase_iterations=_phase_iterations(opts), **_separation(opts, model_config))
         for metric in ("SDR", "ISR", "SIR", "SAR"):
             stats = evaluate.compute_mean_metrics(folder, metric=metric)
             for src, (med, mad, mean, sd) in zip(model_config["source_names"], stats):
@@ -132,7 +146,7 @@ def main(argv=None):
             raise SystemExit("hop_frames must be a positive frame count or 'track', got %r" % (hop,))
         evaluate.produce_source_estimates(model_config, opts.get("model_path"), opts["input_path"], opts.get("output_path"),
                                           hop_frames=hop, postfilter=_postfilter(opts, model_config),
-                                          phase_iterations=_phase_iterations(opts))
+                                          phase_iterations=_phase_iterations(opts), **_separation(opts, model_config))
 
 
 if __name__ == "__main__":

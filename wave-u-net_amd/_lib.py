@@ -65,6 +65,10 @@ class WunStretchJob(C.Structure):
                 ("den", C.c_int32)]
 
 
+class WunBlendWindow(C.Structure):
+    _fields_ = [("pos", C.c_int64), ("row", C.c_int32), ("flags", C.c_int32)]
+
+
 class WunOpHeadDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "C", "F", "S", "difference", "Ko", "padl", "Tfeat", "Tout", "B", "tanh", "training", "feat_bf16",
@@ -76,6 +80,7 @@ class WunOpHeadDesc(C.Structure):
 (PATH_NONE, PATH_SCALAR, PATH_VEC4, PATH_VEC8_BF16, PATH_ONE_STAGE, PATH_TWO_STAGE, PATH_GENERIC, PATH_FOUR_POSITION,
  PATH_NOT_FUSED, PATH_FUSED) = range(10)
 
+BLEND_NO_RISE, BLEND_NO_FALL = 1, 2                 # wun_blend_window.flags
 SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2                 # wun_snippet_source.flags
 SPEED_RATES, SPEED_MAX_RATIO = 8, 64                # WUN_SPEED_RATES, WUN_SPEED_MAX_RATIO: the rate bank of wun_gather_snippets_speed
 STRETCH_JOBS = 64                                   # WUN_STRETCH_JOBS: jobs per launch set of wun_time_stretch
@@ -251,6 +256,13 @@ _SIGS = {
     "wun_forward_windows": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, _P, _P, C.c_int, _P]),
     "wun_scatter_windows": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.c_int64, _P, C.c_int64, _P]),
     "wun_separate_track": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "wun_blend_abi_size": (C.c_int32, []),
+    "wun_blend_positions": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(WunBlendWindow), C.c_int64]),
+    "wun_blend_windows": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(WunBlendWindow), C.c_int64,
+                                    C.c_int64, _P, _P, C.c_int64, _P]),
+    "wun_blend_finish": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "wun_separate_track_blend": (C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64),
+                                           C.c_int64, _P, _P, _P, _P, _P]),
     "wun_snippet_abi_size": (C.c_int32, []),
     "wun_gather_snippets": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _P, C.c_int32,
                                       _P, _P, _P]),
@@ -350,6 +362,9 @@ def load():
     if lib.wun_stretch_abi_size() != C.sizeof(WunStretchJob):
         raise RuntimeError("libwun.so wun_stretch_job size %d != this binding's %d (stale library or binding)" % (
             lib.wun_stretch_abi_size(), C.sizeof(WunStretchJob)))
+    if lib.wun_blend_abi_size() != C.sizeof(WunBlendWindow):
+        raise RuntimeError("libwun.so wun_blend_window size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_blend_abi_size(), C.sizeof(WunBlendWindow)))
     _lib = lib
     return lib
 

@@ -54,6 +54,10 @@ EXTENSION_DEFAULTS = {
     # "kind": "wiener" (and "iterations": 1, "em_eps": 1e-10) postfilter.WienerFilter, the multichannel Wiener filter
     # "transform": "fft" computes the transforms with an FFT: n_fft up to 8192 instead of 2048
     "postfilter": None,
+    # evaluate.separate_track (through produce_source_estimates / evaluate_track / produce_dataset_estimates): None = disjoint
+    # hops, one pass; else {"overlap": 0.25, "shifts": 4, "max_shift": 11025} (any subset): neighbouring hops share that
+    # fraction of a hop and are cross-faded, and the hop grid is run at that many shifted offsets and averaged
+    "separation": None,
     # spectrogram.UnetSpectrogramSeparator: the STFT framing of the spectrogram U-Net (UnetSpectrogramSeparator.py:28-29 fixes
     # 1024 / 768); other values exist so that tests can run small geometries
     "spec_frame_len": 1024,

@@ -323,6 +323,17 @@ hipError_t launch_gather_windows(const MixWindows& w, float* dst, int B, int T, 
 struct ScatterSeg { long long dst; int row, src, len; };
 hipError_t launch_scatter_segments(const float* outputs, float* preds, const ScatterSeg* segs, int nsegs, int S, int B,
                                    int Tout, int C, long long pred_frames, hipStream_t s);
+// One run of frames with a constant covering set, and up to WUN_BLEND_COVER of its covering rows in ascending window order:
+// for every frame f of [dst, dst + len), source s and channel c, j = 0 .. n - 1 in turn
+//   preds[s][f][c] = fmaf(w_j(t0[j] + f - dst), outputs[s][row[j]][t0[j] + f - dst][c], preds[s][f][c]);  den[f] += w_j(..)
+// meta: bits 0-2 = n, bits 4 + 2j / 5 + 2j = WUN_BLEND_NO_RISE / WUN_BLEND_NO_FALL of cover j.  A covering set larger than the
+// cap is cut into successive pieces of the same run, launched one after the other on the stream.
+#define WUN_BLEND_COVER 4
+struct BlendRun { long long dst; int len; unsigned meta; int row[WUN_BLEND_COVER]; int t0[WUN_BLEND_COVER]; };
+hipError_t launch_blend_runs(const float* outputs, float* preds, float* den, const BlendRun* runs, int nruns, int S, int B,
+                             int Tout, int C, int overlap, long long pred_frames, hipStream_t s);
+// preds[s][f][c] = den[f] != 0 ? preds[s][f][c] / den[f] : +0
+hipError_t launch_blend_finish(float* preds, const float* den, int S, long long pred_frames, int C, hipStream_t s);
 hipError_t launch_make_wt(const float* params, float* ws, const WtDesc* dev_descs, int ndesc,
                           int max_elems, hipStream_t s);
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr_t,

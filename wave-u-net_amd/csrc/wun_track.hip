@@ -102,6 +102,102 @@ __global__ __launch_bounds__(WUN_TRACK_BLOCK) void scatter_windows_kernel(Scatte
     }
 }
 
+struct BlendArgs {
+    const float* outputs; float* preds; float* den;
+    BlendRun run[WUN_TRACK_ROWS];
+    long long out_plane, row_floats, pred_plane;     // floats: B * Tout * C, Tout * C, pred_frames * C
+    int C, Tout, V;                                  // C is 1 or 2
+};
+
+// the trapezoid of include/wun.h at frame t of a window: one correctly rounded division of two exact integers
+__device__ __forceinline__ float blend_weight(int t, int Tout, int V, unsigned flags) {
+    int m = V + 1;
+    if (!(flags & WUN_BLEND_NO_RISE)) m = min(m, t + 1);
+    if (!(flags & WUN_BLEND_NO_FALL)) m = min(m, Tout - t);
+    return __fdiv_rn((float)m, (float)(V + 1));
+}
+
+// grid (granules of the longest run / 256, runs, sources): a lane owns one 16-byte granule of preds (the accumulator) and
+// walks the run's covering rows in table order; the lanes of source 0 that hold a frame's first channel own its den element
+__global__ __launch_bounds__(WUN_TRACK_BLOCK) void blend_windows_kernel(BlendArgs a) {
+    const BlendRun& rn = a.run[blockIdx.y];          // uniform: read from the kernel arguments where it is used
+    float* dst = a.preds + (long long)blockIdx.z * a.pred_plane;
+    const float* plane = a.outputs + (long long)blockIdx.z * a.out_plane;
+    const long long d0 = rn.dst * a.C, d1 = d0 + (long long)rn.len * a.C;
+    const long long d = d0 - granule_offset(dst, d0) + 4LL * ((long long)blockIdx.x * WUN_TRACK_BLOCK + threadIdx.x);
+    if (d >= d1) return;
+    const bool whole = d >= d0 && d + 4 <= d1;       // the run's first and last granule belong to it in part only
+    float acc[4], dn[4];
+    int tq[4];                                       // frame of float r, counted from the run's first
+    bool in[4], own[4];
+    if (whole) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(dst + d);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = v[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long long q = d + r - d0;
+        in[r] = q >= 0 && d + r < d1;
+        if (!whole) acc[r] = in[r] ? dst[d + r] : 0.f;
+        tq[r] = (int)(a.C == 2 ? q >> 1 : q);
+        own[r] = in[r] && blockIdx.z == 0 && (q & (a.C - 1)) == 0;
+        dn[r] = own[r] ? a.den[rn.dst + tq[r]] : 0.f;
+    }
+    const int n = (int)(rn.meta & 7u);
+#pragma unroll
+    for (int j = 0; j < WUN_BLEND_COVER; ++j) {
+        if (j >= n) break;
+        const float* src = plane + (long long)rn.row[j] * a.row_floats;
+        const long long delta = (long long)rn.t0[j] * a.C - d0;      // source float of destination float d: d + delta
+        const unsigned flags = (rn.meta >> (4 + 2 * j)) & 3u;
+        f32x4 x;
+        switch (granule_offset(src, d + delta)) {     // uniform over the workgroup
+            case 0: x = ld4_window<0>(src, d + delta, d0 + delta, d1 + delta); break;
+            case 1: x = ld4_window<1>(src, d + delta, d0 + delta, d1 + delta); break;
+            case 2: x = ld4_window<2>(src, d + delta, d0 + delta, d1 + delta); break;
+            default: x = ld4_window<3>(src, d + delta, d0 + delta, d1 + delta); break;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float w = blend_weight(rn.t0[j] + tq[r], a.Tout, a.V, flags);
+            acc[r] = __fmaf_rn(w, x[r], acc[r]);
+            dn[r] = dn[r] + w;
+        }
+    }
+    if (whole) {
+        *reinterpret_cast<f32x4*>(dst + d) = (f32x4){acc[0], acc[1], acc[2], acc[3]};
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (in[r]) dst[d + r] = acc[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (own[r]) a.den[rn.dst + tq[r]] = dn[r];
+}
+
+struct FinishArgs { float* preds; const float* den; long long plane; int C; };
+
+__device__ __forceinline__ float blend_quotient(float acc, float den) { return den != 0.f ? __fdiv_rn(acc, den) : 0.f; }
+
+// grid (granules of a source's plane / 256, sources): a lane owns one 16-byte granule of preds
+__global__ __launch_bounds__(WUN_TRACK_BLOCK) void blend_finish_kernel(FinishArgs a) {
+    float* dst = a.preds + (long long)blockIdx.y * a.plane;
+    const long long d = 4LL * ((long long)blockIdx.x * WUN_TRACK_BLOCK + threadIdx.x) - granule_offset(dst, 0);
+    if (d >= a.plane) return;
+    if (d >= 0 && d + 4 <= a.plane) {
+        f32x4 v = *reinterpret_cast<const f32x4*>(dst + d);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = blend_quotient(v[r], a.den[a.C == 2 ? (d + r) >> 1 : d + r]);
+        *reinterpret_cast<f32x4*>(dst + d) = v;
+    } else {                                          // a plane's first and last granule belong to it in part only
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (d + r >= 0 && d + r < a.plane) dst[d + r] = blend_quotient(dst[d + r], a.den[a.C == 2 ? (d + r) >> 1 : d + r]);
+    }
+}
+
 // (C is 1 or 2 for every plan: wun_plan_create refuses other num_channels, so launch_btc_to_ncw's general form has no
 // counterpart here; pitch and the alignments are the plan's own and the entries' argument checks)
 hipError_t launch_gather_windows(const MixWindows& w, float* dst, int B, int T, int C, int pitch, hipStream_t s) {
@@ -148,6 +244,45 @@ hipError_t launch_scatter_segments(const float* outputs, float* preds, const Sca
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// (runs of one call are disjoint: one writer per preds float and per den element in every launch)
+hipError_t launch_blend_runs(const float* outputs, float* preds, float* den, const BlendRun* runs, int nruns, int S, int B,
+                             int Tout, int C, int overlap, long long pred_frames, hipStream_t s) {
+    if (C != 1 && C != 2) return hipErrorInvalidValue;
+    for (int k0 = 0; k0 < nruns; k0 += WUN_TRACK_ROWS) {
+        const int n = std::min(nruns - k0, WUN_TRACK_ROWS);
+        BlendArgs a;
+        a.outputs = outputs; a.preds = preds; a.den = den; a.C = C; a.Tout = Tout; a.V = overlap;
+        a.out_plane = (long long)B * Tout * C; a.row_floats = (long long)Tout * C; a.pred_plane = pred_frames * C;
+        int longest = 0;
+        double floats = 0.0;                          // moved per source: accumulator in and out, and every covering row
+        for (int r = 0; r < WUN_TRACK_ROWS; ++r) {
+            a.run[r] = r < n ? runs[k0 + r] : BlendRun{0, 0, 0u, {0, 0, 0, 0}, {0, 0, 0, 0}};
+            longest = std::max(longest, a.run[r].len);
+            floats += (double)a.run[r].len * C * (2.0 + (a.run[r].meta & 7u));
+        }
+        const long long granules = ((long long)longest * C + 3) / 4 + 1;
+        const dim3 grid((unsigned)((granules + WUN_TRACK_BLOCK - 1) / WUN_TRACK_BLOCK), (unsigned)n, (unsigned)S);
+        prof_scope_begin("blend_windows_kernel", 0.0, s, "", 4.0 * floats * S);
+        hipLaunchKernelGGL(blend_windows_kernel, grid, dim3(WUN_TRACK_BLOCK), 0, s, a);
+        prof_scope_end(s);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_blend_finish(float* preds, const float* den, int S, long long pred_frames, int C, hipStream_t s) {
+    if (C != 1 && C != 2) return hipErrorInvalidValue;
+    if (pred_frames < 1) return hipSuccess;
+    const FinishArgs a = {preds, den, pred_frames * C, C};
+    const long long granules = (a.plane + 3) / 4 + 1;
+    const dim3 grid((unsigned)((granules + WUN_TRACK_BLOCK - 1) / WUN_TRACK_BLOCK), (unsigned)S);
+    prof_scope_begin("blend_finish_kernel", 0.0, s, "", (8.0 * (double)a.plane + 4.0 * (double)pred_frames) * S);
+    hipLaunchKernelGGL(blend_finish_kernel, grid, dim3(WUN_TRACK_BLOCK), 0, s, a);
+    prof_scope_end(s);
+    return hipGetLastError();
 }
 
 }  // namespace wun
@@ -223,7 +358,176 @@ int scatter_checked(const wun_plan* p, const float* outputs, const int64_t* posi
     return WUN_OK;
 }
 
+// The windows of a call, clipped to [0, pred_frames), cut at every window edge into runs of frames whose covering set is
+// constant; each run carries its covering windows in table order (the caller's ascending g).  levels[k] holds covers
+// WUN_BLEND_COVER k .. WUN_BLEND_COVER k + 3 of every run that has that many: level k + 1 is launched behind level k, and
+// the chain of a frame passes through preds and den in memory, so where it is cut does not change its bits.  Frames no
+// window covers make no run.  O(edges x windows) on the windows of one call (a plan's batch in wun_separate_track_blend).
+std::vector<std::vector<BlendRun>> blend_runs(const wun_blend_window* w, int64_t nwin, int Tout, int64_t pred_frames) {
+    std::vector<long long> cuts;
+    for (int64_t g = 0; g < nwin; ++g) {
+        const long long lo = std::max<long long>(w[g].pos, 0), hi = std::min<long long>(w[g].pos + Tout, pred_frames);
+        if (lo < hi) { cuts.push_back(lo); cuts.push_back(hi); }
+    }
+    std::sort(cuts.begin(), cuts.end());
+    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
+    std::vector<std::vector<BlendRun>> levels;
+    for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+        const long long f0 = cuts[c], f1 = cuts[c + 1];
+        int covers = 0;
+        for (int64_t g = 0; g < nwin; ++g) {
+            if (w[g].pos > f0 || w[g].pos + Tout < f1) continue;       // an edge never lies inside [f0, f1): all or nothing
+            const size_t level = (size_t)(covers / WUN_BLEND_COVER);
+            const int j = covers % WUN_BLEND_COVER;
+            if (levels.size() <= level) levels.emplace_back();
+            if (j == 0) levels[level].push_back(BlendRun{f0, (int)(f1 - f0), 0u, {0, 0, 0, 0}, {0, 0, 0, 0}});
+            BlendRun& r = levels[level].back();
+            r.row[j] = w[g].row;
+            r.t0[j] = (int)(f0 - w[g].pos);
+            r.meta = (r.meta & ~7u) + (unsigned)(j + 1);
+            r.meta |= ((unsigned)w[g].flags & 3u) << (4 + 2 * j);
+            ++covers;
+        }
+    }
+    return levels;
+}
+
+int check_blend(const char* who, int64_t S, int64_t B, int64_t Tout, int64_t C, const wun_blend_window* w, int64_t nwin,
+                int64_t overlap, int64_t pred_frames) {
+    const std::string me(who);
+    if (S < 1 || S > 65535 || B < 1 || B > ((int64_t)1 << 30) || Tout < 1 || Tout > ((int64_t)1 << 30))
+        return fail(WUN_ERR_INVALID, me + ": need 1 <= S <= 65535 and 1 <= B, Tout <= 2^30");
+    if (C != 1 && C != 2) return fail(WUN_ERR_INVALID, me + ": C must be 1 or 2");
+    if (overlap < 0 || overlap > Tout - 1) return fail(WUN_ERR_INVALID, me + ": overlap_frames must be in [0, Tout - 1]");
+    if (pred_frames < 0 || pred_frames > ((int64_t)1 << 46)) return fail(WUN_ERR_INVALID, me + ": bad pred_frames");
+    if (nwin < 1 || nwin > ((int64_t)1 << 24)) return fail(WUN_ERR_INVALID, me + ": nwin must be in [1, 2^24]");
+    for (int64_t g = 0; g < nwin; ++g) {
+        if (w[g].row < 0 || w[g].row >= B)
+            return fail(WUN_ERR_INVALID, me + ": window " + std::to_string(g) + " names a row outside [0, B)");
+        if (w[g].pos < -((int64_t)1 << 46) || w[g].pos > ((int64_t)1 << 46))
+            return fail(WUN_ERR_INVALID, me + ": window " + std::to_string(g) + " has a position beyond 2^46");
+        if ((w[g].flags & ~(WUN_BLEND_NO_RISE | WUN_BLEND_NO_FALL)) != 0)
+            return fail(WUN_ERR_INVALID, me + ": window " + std::to_string(g) + " has unknown flag bits");
+    }
+    return WUN_OK;
+}
+
+int blend_checked(const float* outputs, int S, int B, int Tout, int C, const wun_blend_window* w, int64_t nwin, int overlap,
+                  float* preds, float* den, int64_t pred_frames, hipStream_t s) {
+    const std::vector<std::vector<BlendRun>> levels = blend_runs(w, nwin, Tout, pred_frames);
+    for (const auto& runs : levels)
+        HIP_TRY(launch_blend_runs(outputs, preds, den, runs.data(), (int)runs.size(), S, B, Tout, C, overlap, pred_frames, s));
+    return WUN_OK;
+}
+
+// one pass of wun_blend_positions: K, or a negative status
+int64_t blend_pass(const char* who, int64_t Tout, int64_t n_frames, int64_t overlap, int64_t shift) {
+    const std::string me(who);
+    if (Tout < 1 || Tout > ((int64_t)1 << 30) || n_frames < 1 || n_frames > ((int64_t)1 << 46))
+        return fail(WUN_ERR_INVALID, me + ": need 1 <= output_frames <= 2^30 and 1 <= n_frames <= 2^46");
+    if (overlap < 0 || overlap > Tout - 1) return fail(WUN_ERR_INVALID, me + ": overlap_frames must be in [0, output_frames - 1]");
+    if (shift < 0 || shift > ((int64_t)1 << 46)) return fail(WUN_ERR_INVALID, me + ": a shift must be in [0, 2^46]");
+    const int64_t H = Tout - overlap, over = std::max<int64_t>(0, n_frames + shift - Tout), K = 1 + (over + H - 1) / H;
+    if (K > ((int64_t)1 << 30)) return fail(WUN_ERR_INVALID, me + ": more than 2^30 windows in a pass");
+    return K;
+}
+
 }  // namespace
+
+extern "C" int32_t wun_blend_abi_size(void) { return (int32_t)sizeof(wun_blend_window); }
+
+extern "C" int64_t wun_blend_positions(int64_t output_frames, int64_t n_frames, int64_t overlap_frames, int64_t shift,
+                                       wun_blend_window* windows, int64_t cap) {
+    const int64_t K = blend_pass("wun_blend_positions", output_frames, n_frames, overlap_frames, shift);
+    if (K < 0 || !windows) return K;
+    if (cap < K) return fail(WUN_ERR_INVALID, "wun_blend_positions: cap below the number of windows");
+    const int64_t H = output_frames - overlap_frames;
+    for (int64_t k = 0; k < K; ++k)
+        windows[k] = wun_blend_window{k * H - shift, (int32_t)k,
+                                      (k == 0 ? WUN_BLEND_NO_RISE : 0) | (k == K - 1 ? WUN_BLEND_NO_FALL : 0)};
+    return K;
+}
+
+extern "C" int wun_blend_windows(const float* outputs, int64_t S, int64_t B, int64_t Tout, int64_t C,
+                                 const wun_blend_window* windows, int64_t nwin, int64_t overlap_frames, float* preds,
+                                 float* den, int64_t pred_frames, void* stream) {
+    if (!outputs || !windows || !preds || !den) return fail(WUN_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = check_blend("wun_blend_windows", S, B, Tout, C, windows, nwin, overlap_frames, pred_frames))) return rc;
+    if (((reinterpret_cast<uintptr_t>(outputs) | reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(den)) & 3) != 0)
+        return fail(WUN_ERR_INVALID, "wun_blend_windows: outputs, preds and den must be 4-byte aligned");
+    return no_throw("wun_blend_windows", [&] {
+        return blend_checked(outputs, (int)S, (int)B, (int)Tout, (int)C, windows, nwin, (int)overlap_frames, preds, den,
+                             pred_frames, (hipStream_t)stream);
+    });
+}
+
+extern "C" int wun_blend_finish(float* preds, const float* den, int64_t S, int64_t pred_frames, int64_t C, void* stream) {
+    if (!preds || !den) return fail(WUN_ERR_INVALID, "null argument");
+    if (S < 1 || S > 65535 || (C != 1 && C != 2) || pred_frames < 0 || pred_frames > ((int64_t)1 << 46))
+        return fail(WUN_ERR_INVALID, "wun_blend_finish: need 1 <= S <= 65535, C of 1 or 2 and 0 <= pred_frames <= 2^46");
+    if (((reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(den)) & 3) != 0)
+        return fail(WUN_ERR_INVALID, "wun_blend_finish: preds and den must be 4-byte aligned");
+    HIP_TRY(launch_blend_finish(preds, den, (int)S, pred_frames, (int)C, (hipStream_t)stream));
+    return WUN_OK;
+}
+
+extern "C" int wun_separate_track_blend(const wun_plan* p, const float* params, const float* track_tc, int64_t track_frames,
+                                        int64_t lead, int64_t n_frames, int64_t overlap_frames, const int64_t* shifts,
+                                        int64_t nshifts, float* ws, float* outputs, float* preds, float* den, void* stream) {
+    if (!p || !params || !track_tc || !shifts || !ws || !outputs || !preds || !den) return fail(WUN_ERR_INVALID, "null argument");
+    const char* me = "wun_separate_track_blend";
+    if (nshifts < 1 || nshifts > 4096) return fail(WUN_ERR_INVALID, std::string(me) + ": nshifts must be in [1, 4096]");
+    if ((p->Tin - p->Tout) % 2 != 0)
+        return fail(WUN_ERR_INVALID, std::string(me) + ": input_frames - output_frames must be even (symmetric context padding)");
+    if (lead < 0 || track_frames < 0 || track_frames > ((int64_t)1 << 47))
+        return fail(WUN_ERR_INVALID, std::string(me) + ": bad lead or track_frames");
+    const int64_t H = p->Tout - overlap_frames;
+    int64_t total = 0;
+    for (int64_t i = 0; i < nshifts; ++i) {           // a pass's windows ascend: its first and its last bound the rest
+        const int64_t K = blend_pass(me, p->Tout, n_frames, overlap_frames, shifts[i]);
+        if (K < 0) return (int)K;
+        const int64_t first = lead - shifts[i], last = lead + (K - 1) * H - shifts[i];
+        if (first < 0 || last + p->Tin > track_frames)
+            return fail(WUN_ERR_INVALID, std::string(me) + ": window " + std::to_string(first < 0 ? 0 : K - 1) + " of pass " +
+                        std::to_string(i) + " lies outside [0, track_frames] (lead >= every shift, and zeros behind the track for "
+                        "the overhanging last hop)");
+        total += K;
+    }
+    if (total > ((int64_t)1 << 30)) return fail(WUN_ERR_INVALID, std::string(me) + ": more than 2^30 windows");
+    int rc;
+    if ((rc = check_track_alignment(me, track_tc, ws))) return rc;
+    if (((reinterpret_cast<uintptr_t>(outputs) | reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(den)) & 3) != 0)
+        return fail(WUN_ERR_INVALID, std::string(me) + ": outputs, preds and den must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // The window list is the passes one behind the other; chunks of the plan's batch run across pass boundaries.  Chunk
+    // k + 1 overwrites `outputs` behind the blend of chunk k: stream order, as in wun_separate_track.
+    return no_throw(me, [&] {
+        std::vector<wun_blend_window> win((size_t)total);
+        int64_t g = 0;
+        for (int64_t i = 0; i < nshifts; ++i)
+            g += wun_blend_positions(p->Tout, n_frames, overlap_frames, shifts[i], win.data() + g, total - g);
+        HIP_TRY(hipMemsetAsync(preds, 0, sizeof(float) * (size_t)p->S * (size_t)n_frames * (size_t)p->C, s));
+        HIP_TRY(hipMemsetAsync(den, 0, sizeof(float) * (size_t)n_frames, s));
+        std::vector<int64_t> pos((size_t)p->B);
+        std::vector<wun_blend_window> chunk((size_t)p->B);
+        for (int64_t k = 0; k < total; k += p->B) {
+            const int n = (int)std::min<int64_t>(total - k, p->B);
+            for (int b = 0; b < n; ++b) {
+                chunk[(size_t)b] = win[(size_t)(k + b)];
+                chunk[(size_t)b].row = b;
+                pos[(size_t)b] = lead + chunk[(size_t)b].pos;
+            }
+            const MixWindows w = {track_tc, pos.data(), n};
+            int r;
+            if ((r = forward_pass(p, params, nullptr, &w, ws, outputs, 0, s))) return r;
+            if ((r = blend_checked(outputs, p->S, p->B, p->Tout, p->C, chunk.data(), n, (int)overlap_frames, preds, den,
+                                   n_frames, s))) return r;
+        }
+        HIP_TRY(launch_blend_finish(preds, den, p->S, n_frames, p->C, s));
+        return (int)WUN_OK;
+    });
+}
 
 extern "C" int wun_forward_windows(const wun_plan* p, const float* params, const float* track_tc, int64_t track_frames,
                                    const int64_t* positions, int64_t npos, float* ws, float* outputs, int training,

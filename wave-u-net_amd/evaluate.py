@@ -11,7 +11,8 @@ separate_track is the whole of Evaluate.predict (:59-80) for a file at ANY rate,
 downmix + resampling + context padding in one kernel (resample.py, wun_resample), the hop loop in one C call
 (wun_separate_track: windows gathered from the track by the forward's first kernel, estimates scattered by one kernel
 per chunk), resampling back + trim + channel duplication in one kernel per source, one upload and one download per track.
-hop_frames lets a hop be longer than the reference's num_frames, up to the whole track.
+hop_frames lets a hop be longer than the reference's num_frames, up to the whole track.  overlap / shifts blend overlapping hops
+and several shifted passes into one weighted mean per output frame (blend.py, wun_separate_track_blend).
 """
 import numpy as np
 import torch
@@ -106,8 +107,35 @@ def budget_batch_hops(separator, batch_hops, n_hops, input_frames, default_input
     return max(1, min(b, int(workspace_bytes) // per_hop))
 
 
+def blend_options(overlap, shifts, max_shift, expected_sr):
+    """separate_track's overlap / shifts / max_shift checked and resolved: (overlap as a float, the list of shift offsets).
+    shifts None, 0 or 1: [0]; an int N: blend.shift_offsets(N, max_shift), max_shift defaulting to expected_sr // 2; a list:
+    its non-negative frame offsets.  ValueError for anything out of range."""
+    from . import blend
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, float)) or not 0.0 <= float(overlap) < 1.0:
+        raise ValueError("overlap = %r must be a fraction of the hop in [0, 1)" % (overlap,))
+    if shifts is None:
+        offsets = [0]
+    elif isinstance(shifts, bool):
+        raise ValueError("shifts = %r must be a count or a list of frame offsets" % (shifts,))
+    elif isinstance(shifts, (int, np.integer)):
+        if shifts < 0:
+            raise ValueError("shifts = %d must be >= 0" % shifts)
+        if max_shift is None:
+            max_shift = int(expected_sr) // 2
+        if isinstance(max_shift, bool) or not isinstance(max_shift, (int, np.integer)) or max_shift < 0:
+            raise ValueError("max_shift = %r must be a frame count >= 0" % (max_shift,))
+        offsets = blend.shift_offsets(shifts, max_shift) if shifts > 1 else [0]
+    else:
+        offsets = list(shifts)
+        if not offsets or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 for v in offsets):
+            raise ValueError("shifts = %r must be a non-empty list of frame offsets >= 0" % (shifts,))
+        offsets = [int(v) for v in offsets]
+    return float(overlap), offsets
+
+
 def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, hop_frames=None, workspace_bytes=None,
-                   return_device=False, postfilter=None, phase_iterations=0):
+                   return_device=False, postfilter=None, phase_iterations=0, overlap=0.0, shifts=None, max_shift=None):
     """Evaluate.predict (Evaluate.py:59-80) around predict_track (:82-145) for audio at any sample rate, without the
     host in the loop.  mix_audio: [n_frames, n_channels] float array or tensor at mix_sr Hz.  Returns {source_name: float32
     numpy [n_frames, channels]} at mix_sr: channels is the input's count, except that a stereo model on a mono file
@@ -147,8 +175,21 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     through N Griffin-Lim iterations from the mix's phase (separator.reconstruct, the reference's spectrogramToAudioFile with
     phase=mix_phase) instead of keeping the mix's phase as it is.  The refined audio is normalised by
     wun_istft's window-square sum over the covering frames, not by inverse_stft_window_fn: it differs from the default audio
-    output at a hop's edges even before the phase moves.  0 (default) is exactly the path and the bits without the option."""
+    output at a hop's edges even before the phase moves.  0 (default) is exactly the path and the bits without the option.
+
+    overlap (a fraction of the hop's output, 0 <= overlap < 1) and shifts (a count N of passes at blend.shift_offsets(N,
+    max_shift), max_shift defaulting to expected_sr // 2, or a list of frame offsets at the model's rate): neighbouring
+    hops share V = round(overlap * output_frames) frames and are cross-faded over them with a trapezoid, and the hop grid
+    is run once per shift, each pass moved back by its offset; every output frame is ONE weighted mean over every window of
+    every pass that covers it (blend.py).  The last hop of a pass is not re-aligned: it hangs over the
+    track's end and reads zeros there.  The waveform network runs the whole loop in one wun_separate_track_blend call on
+    one plan with batch min(batch_hops, windows); any other separator goes chunk by chunk through get_output and
+    blend.blend_windows (the same kernel on a device, its restatement on CPU tensors).  About nshifts / (1 - overlap) times
+    the forward passes of the plain path; no quality gain is measured or claimed.  overlap == 0 with shifts None, 0, 1 or
+    [0] is exactly the path and the bits without the options."""
     from . import resample as rs
+    overlap, offsets = blend_options(overlap, shifts, max_shift, model_config["expected_sr"])
+    blended = overlap != 0.0 or offsets != [0]
     phase_iterations = int(phase_iterations)
     if phase_iterations < 0:
         raise ValueError("phase_iterations must be >= 0, got %d" % phase_iterations)
@@ -174,15 +215,31 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     # :108-113 (short inputs: zeros behind)
     n_frames = max(n_res, input_frames if hop_frames is None else output_frames)
     pad = (input_frames - output_frames) // 2                                    # :121-122
-    padded = torch.zeros((n_frames + 2 * pad, C), dtype=torch.float32, device=device)
-    rs.resample_into(x, padded, pad, n_res, up, down)                            # downmix / duplicate, resample, pad
+    lead, table = 0, None
+    track_frames = n_frames + 2 * pad
+    if blended:
+        from . import blend
+        v_frames = min(int(round(overlap * output_frames)), output_frames - 1)
+        table = blend.window_table(output_frames, n_frames, v_frames, offsets)
+        lead = max(offsets)                                                      # the first window of a pass starts at -shift
+        track_frames = max(track_frames + lead, lead + int(table[:, 0].max()) + input_frames)   # ... its last one overhangs
+    padded = torch.zeros((track_frames, C), dtype=torch.float32, device=device)
+    rs.resample_into(x, padded, lead + pad, n_res, up, down)                     # downmix / duplicate, resample, pad
 
     names = list(model_config["source_names"])
-    positions = _hop_positions(n_frames, output_frames)
+    positions = _hop_positions(n_frames, output_frames) if table is None else table[:, 0].tolist()
     if hop_frames is not None:
         batch_hops = budget_batch_hops(separator, batch_hops, len(positions), input_frames,
                                        hop_geometry(model_config, separator, n_res)[0], workspace_bytes)
-    if device.type != "cpu" and hasattr(separator, "separate_padded"):
+    if table is not None:
+        if device.type != "cpu" and hasattr(separator, "separate_padded_blend"):
+            preds = torch.empty((len(names), n_frames, C), dtype=torch.float32, device=device)
+            separator.separate_padded_blend(padded, n_frames, min(batch_hops, len(positions)), v_frames, offsets, lead,
+                                            frames=input_frames, out=preds)
+        else:
+            preds = _separate_blend_chunks(separator, padded, table, lead, v_frames, batch_hops, input_frames, names,
+                                           n_frames, C, phase_iterations)
+    elif device.type != "cpu" and hasattr(separator, "separate_padded"):
         preds = torch.empty((len(names), n_frames, C), dtype=torch.float32, device=device)   # every frame is written
         batch = min(batch_hops, len(positions))
         if hop_frames is not None or len(positions) % batch == 0:
@@ -197,7 +254,7 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
                               phase_iterations)
 
     if postfilter is not None:                                                   # at the model's rate, without extra_pad
-        preds = postfilter.apply(padded[pad:pad + n_res], preds[:, :n_res])
+        preds = postfilter.apply(padded[lead + pad:lead + pad + n_res], preds[:, :n_res])
 
     # back to mix_sr, cut to the input's length, mono estimates duplicated to the input's channels (:64-67)
     c_out = ch if (C == 1 and ch > 1) else C
@@ -240,12 +297,40 @@ def _separate_cpu(separator, padded, positions, batch_hops, input_frames, output
     return preds
 
 
+def _separate_blend_chunks(separator, padded, table, lead, v_frames, batch_hops, input_frames, names, n_frames, C,
+                           phase_iterations=0):
+    """The blended hop loop through separator.get_output, for separators without a plan (the spectrogram U-Net, numpy
+    stand-ins): the window at pred position p is padded[lead + p : lead + p + input_frames]; every chunk's estimates are
+    accumulated by blend.blend_windows where `padded` lives."""
+    from . import blend
+    device = padded.device
+    preds = torch.zeros((len(names), n_frames, C), dtype=torch.float32, device=device)
+    den = torch.zeros(n_frames, dtype=torch.float32, device=device)
+    for k in range(0, table.shape[0], batch_hops):
+        chunk = table[k:k + batch_hops].copy()
+        chunk[:, 1] = np.arange(chunk.shape[0])                                  # rows of this chunk's batch
+        batch = torch.stack([padded[lead + p:lead + p + input_frames] for p in chunk[:, 0].tolist()])
+        if phase_iterations:
+            mags = separator.get_output(batch, False, return_spectrogram=True)
+            outs = separator.reconstruct(mags, batch, phase_iterations)
+        else:
+            outs = separator.get_output(batch if device.type != "cpu" else batch.numpy(), False)
+        rows = []
+        for n in names:
+            o = outs[n]
+            o = o if torch.is_tensor(o) else torch.from_numpy(np.ascontiguousarray(np.asarray(o, dtype=np.float32)))
+            rows.append(o.to(device=device, dtype=torch.float32))
+        blend.blend_windows(torch.stack(rows).contiguous(), chunk, v_frames, preds, den)
+    return blend.blend_finish(preds, den)
+
+
 def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None, hop_frames=None,
-                             postfilter=None, phase_iterations=0):
+                             postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None):
     """Evaluate.produce_source_estimates (Evaluate.py:160-194): separate one mixture file with a
     checkpoint and write <input file name>_<source>.wav next to it (or into output_path), at the input file's sample rate
     and length.  WAV/NPY input at any rate (an .npy is taken to be at expected_sr; no MP3 decoding here): the separation runs
-    through separate_track (hop_frames, postfilter, phase_iterations: its options of those names).  Returns {source: [T, C]}."""
+    through separate_track (hop_frames, postfilter, phase_iterations, overlap, shifts, max_shift: its options of those
+    names; overlap / shifts / max_shift None: model_config["separation"]'s, else none).  Returns {source: [T, C]}."""
     import os
     from scipy.io import wavfile
     from . import datasets
@@ -258,7 +343,7 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
     preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames, postfilter=postfilter,
-                           phase_iterations=phase_iterations)
+                           phase_iterations=phase_iterations, **separation_options(model_config, overlap, shifts, max_shift))
     folder, name = os.path.split(input_path)
     if output_path is None:
         output_path = folder
@@ -268,8 +353,21 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
     return preds
 
 
+def separation_options(model_config, overlap=None, shifts=None, max_shift=None):
+    """The overlap / shifts / max_shift keywords of separate_track: each argument that is None falls back to
+    model_config["separation"] = {"overlap": .., "shifts": .., "max_shift": ..} (config.EXTENSION_DEFAULTS: None, no
+    blending)."""
+    spec = model_config.get("separation") or {}
+    if not isinstance(spec, dict) or set(spec) - {"overlap", "shifts", "max_shift"}:
+        raise ValueError("model_config['separation'] = %r: a dict with the keys overlap, shifts, max_shift expected" % (spec,))
+    return {"overlap": overlap if overlap is not None else spec.get("overlap", 0.0),
+            "shifts": shifts if shifts is not None else spec.get("shifts"),
+            "max_shift": max_shift if max_shift is not None else spec.get("max_shift")}
+
+
 def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=None, name=None, hop_frames=None,
-                   window=1.0, hop=1.0, filters_len=512, postfilter=None, phase_iterations=0):
+                   window=1.0, hop=1.0, filters_len=512, postfilter=None, phase_iterations=0, overlap=None, shifts=None,
+                   max_shift=None):
     """Evaluate.predict with a results_dir (Evaluate.py:59-80,146-158): separate the mixture (separate_track, estimates kept
     on the device), score them against the stems at the file's rate with bsseval.bss_eval, and write
     <results_dir>/<name>.json in museval's layout.  mix_audio [n, c] at sr; stems {source_name: [n, c]} at sr with the
@@ -277,7 +375,8 @@ def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=No
     are cut to the shortest length.  Returns {metric: float64 [S, nwin]}, sources in source_names order."""
     from . import bsseval
     est = separate_track(model_config, separator, mix_audio, sr, hop_frames=hop_frames, return_device=True,
-                         postfilter=postfilter, phase_iterations=phase_iterations)
+                         postfilter=postfilter, phase_iterations=phase_iterations,
+                         **separation_options(model_config, overlap, shifts, max_shift))
     names = list(model_config["source_names"])
     c = int(est.shape[2])
     refs = []
@@ -329,7 +428,7 @@ def compute_mean_metrics(json_folder, compute_averages=True, metric="SDR"):
 
 
 def produce_dataset_estimates(model_config, load_model, data_root, output_path, partition="test", separator=None,
-                              hop_frames=None, postfilter=None, phase_iterations=0):
+                              hop_frames=None, postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None):
     """The reference's produce_musdb_source_estimates (Evaluate.py:147-159) over the track folders of datasets.py:
     data_root/<partition>/<track>/<source>.wav|.npy (+ optional mix.wav|.npy, default: the sum of the stems), every file at
     one rate (an .npy: expected_sr).  Per track: the estimates as <output_path>/<partition>/<track>/<source>.wav and the
@@ -343,6 +442,7 @@ def produce_dataset_estimates(model_config, load_model, data_root, output_path, 
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)
     names = list(model_config["source_names"])
+    blend_kw = separation_options(model_config, overlap, shifts, max_shift)
     base = os.path.join(data_root, partition)
     out_dir = os.path.join(output_path, partition)
     os.makedirs(out_dir, exist_ok=True)
@@ -364,7 +464,7 @@ def produce_dataset_estimates(model_config, load_model, data_root, output_path, 
         sr = int(sr) if sr is not None else int(model_config["expected_sr"])
         mix = stems.pop("mix") if "mix" in stems else sum(stems[k] for k in names)
         est = separate_track(model_config, sep, mix, sr, hop_frames=hop_frames, return_device=True, postfilter=postfilter,
-                             phase_iterations=phase_iterations)
+                             phase_iterations=phase_iterations, **blend_kw)
         c = int(est.shape[2])
         refs = [np.tile(stems[k], [1, c]) if stems[k].shape[1] == 1 and c > 1 else stems[k] for k in names]
         n = min([int(est.shape[1])] + [r.shape[0] for r in refs])

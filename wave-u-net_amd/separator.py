@@ -337,6 +337,45 @@ class UnetAudioSeparator(object):
         self._last_mix, self._last_training = None, False
         return out
 
+    def blend_windows(self, windows, preds, den, overlap_frames, frames=None, batch=None):
+        """scatter_windows' blending counterpart (blend.blend_windows, wun_blend_windows): the estimates of the last
+        get_output_windows / get_output with the same (batch, frames) are accumulated into preds [S, pred_frames,
+        num_channels] and den [pred_frames] with the trapezoid weights of `overlap_frames`; windows: [nwin, 3] rows of
+        (pos, row of the batch, flags) in the order of the separation's window list.  blend.blend_finish ends it."""
+        from . import blend
+        tab = np.asarray(windows, dtype=np.int64).reshape(-1, 3)
+        key = (int(batch) if batch is not None else int(tab.shape[0]), int(frames) if frames is not None else self._default_frames())
+        if key not in self._outs:
+            raise RuntimeError("no outputs for batch %d, %d frames: run get_output_windows first" % key)
+        return blend.blend_windows(self._outs[key], tab, overlap_frames, preds, den)
+
+    def separate_padded_blend(self, track, n_frames, batch_hops, overlap_frames, shifts, lead, frames=None, out=None):
+        """separate_padded with overlapping hops and shifted passes blended (wun_separate_track_blend).
+        track: [track_frames, num_channels]: lead + pad zero frames, the track, then zeros for the overhanging last hop of
+        every pass (pad = (input - output frames) // 2, lead >= max(shifts)); overlap_frames: frames two neighbouring hops
+        share; shifts: the passes' frame offsets.  Returns the estimates [S, n_frames, num_channels] on the device (`out`
+        when given).  No host synchronisation."""
+        track = self._track(track)
+        key = (int(batch_hops), int(frames) if frames is not None else self._default_frames())
+        plan = self._plan(*key)
+        self._ensure_variables(plan)
+        ws, outs = self._buffers(plan, key)
+        n_frames = int(n_frames)
+        sh = np.ascontiguousarray(np.asarray(list(shifts), dtype=np.int64).reshape(-1))
+        if out is None:
+            out = torch.empty((len(self.source_names), max(n_frames, 0), self.num_channels), dtype=torch.float32, device=self._dev())
+        assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (len(self.source_names), n_frames,
+                                                                                             self.num_channels)
+        den = torch.empty(max(n_frames, 1), dtype=torch.float32, device=self._dev())
+        _lib.check(self._lib.wun_separate_track_blend(plan.handle, self.params.data_ptr(), track.data_ptr(), int(track.shape[0]),
+                                                      int(lead), n_frames, int(overlap_frames),
+                                                      sh.ctypes.data_as(C.POINTER(C.c_int64)), int(sh.size), ws.data_ptr(),
+                                                      outs.data_ptr(), out.data_ptr(), den.data_ptr(), self._stream()))
+        self._ws_gen[key] = self._ws_gen.get(key, 0) + 1
+        self._active, self._last_key = plan, key
+        self._last_mix, self._last_training = None, False
+        return out
+
     # ------------------------------------------------------------------ training step pieces
     def select_mask(self, variables):
         """TF variable names -> the selection of wun_*_select (include/wun.h): a uint8 array with one byte per tensor in
