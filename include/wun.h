@@ -346,6 +346,58 @@ int wun_adam_step_clip(const wun_plan* plan, float* params, const float* grads, 
                        float clip_norm, int32_t flags, float* norm_ws, int64_t* skipped,
                        void* stream, const uint8_t* select, int64_t nselect);
 
+/* ---- the extended optimizer: decoupled weight decay (AdamW) and an EMA of the weights ---------
+ * flags: WUN_CLIP_SKIP_NONFINITE as for wun_adam_step_clip, and WUN_OPTIM_EMA_WARMUP. */
+#define WUN_OPTIM_EMA_WARMUP 2
+typedef struct wun_optim_config {
+    float beta1, beta2, eps;       /* TF-Adam's, as wun_adam_step takes them */
+    float weight_decay;            /* >= 0; 0 = none */
+    float ema_decay;               /* in [0, 1); read only when ema is given */
+    float clip_norm;               /* > 0; +INFINITY = no clipping */
+    int32_t flags;
+} wun_optim_config;
+/* sizeof(wun_optim_config) as the library was compiled (wun_abi_sizes keeps its three entries). */
+int64_t wun_optim_abi_size(void);
+
+/* wun_adam_step_clip with two more steps fused into the same pass over the arenas.  For every float of a selected tensor, in
+ * this order, each product rounded as written (no fused multiply-add where the formula has none):
+ *   g, the clip scale, m, v      exactly as wun_adam_step_clip (grad_scale, clip_norm / N, WUN_CLIP_SKIP_NONFINITE, skipped)
+ *   theta = theta * (1 - lr * weight_decay)          only for a tensor in decay_select -- torch.optim.AdamW's decoupled decay:
+ *                                                    lr, not lr_t; the factor is formed once on the host in float64 and rounded
+ *                                                    to fp32, so weight_decay = 0 gives exactly 1 and leaves the bits alone
+ *   theta -= lr_t * m / (sqrt(v) + eps)              wun_adam_step's expression
+ *   ema -= (1 - d_t) * (ema - theta)                 only when ema is non-NULL, on the NEW theta: the form of
+ *                                                    tf.train.ExponentialMovingAverage / assign_moving_average;
+ *                                                    d_t = ema_decay, or min(ema_decay, (1 + step) / (10 + step)) with
+ *                                                    WUN_OPTIM_EMA_WARMUP (TF's num_updates rule); 1 - d_t is formed once on
+ *                                                    the host in float64 from the fp32 ema_decay and rounded once
+ * PINNED: with weight_decay = 0 and ema = NULL, params, m and v are BIT-EQUAL to wun_adam_step / _select / _clip for the same
+ * arguments; with ema given and no decay they still are, and ema is the formula applied to those bits (wun_ema_update's bits).
+ * decay_select / ndecay: a second byte table with select's conventions (NULL = every tensor decays); a tensor decays when it
+ * is selected and in decay_select.  ema is an arena like params (the caller initialises it, e.g. as a copy of params: TF's
+ * shadow variables start at the variable's value).
+ * A skipped step writes none of theta, m, v, ema and increments *skipped once.  Unselected tensors and the padding floats
+ * between tensors are not touched in any of the four arenas (NULL select = every tensor, still not the padding).  No atomics;
+ * the bits do not depend on the grid, the stream, the arenas' alignment beyond 4 bytes (16-byte accesses run only where all
+ * arenas share one alignment, through the same expressions) or on how tensors merge into ranges.
+ * clip_norm = +INFINITY without WUN_CLIP_SKIP_NONFINITE: the norm is not launched and norm_ws may be NULL; otherwise norm_ws
+ * as for wun_adam_step_clip.  step: as wun_adam_step_clip (1-based, counted per call).
+ * WUN_ERR_INVALID before any GPU work for a null plan / params / grads / m / v / cfg, a null or misaligned norm_ws when the
+ * norm is needed, step < 1, weight_decay < 0 or NaN, ema_decay outside [0, 1) with a non-null ema, clip_norm <= 0 or NaN,
+ * unknown flags, a bad nselect or ndecay, or a null skipped with WUN_CLIP_SKIP_NONFINITE.
+ * Both compute modes (the arenas are fp32 in both).  No host synchronisation, no allocation. */
+int wun_optim_step(const wun_plan* plan, float* params, const float* grads, float* m, float* v, float* ema,
+                   int64_t step, float lr, float grad_scale, const wun_optim_config* cfg, float* norm_ws,
+                   int64_t* skipped, void* stream, const uint8_t* select, int64_t nselect,
+                   const uint8_t* decay_select, int64_t ndecay);
+
+/* The EMA line of wun_optim_step alone, for callers whose optimizer is not this library's (torch.optim on the autograd
+ * module): ema -= (1 - d_t) * (ema - params) on the selected tensors, the same bits as the fused path given the same params,
+ * ema_decay, step and flag.  flags: 0 or WUN_OPTIM_EMA_WARMUP.  WUN_ERR_INVALID before any GPU work for a null plan / ema /
+ * params, ema_decay outside [0, 1), step < 0, unknown flags or a bad nselect.  No host synchronisation, no allocation. */
+int wun_ema_update(const wun_plan* plan, float* ema, const float* params, float ema_decay, int64_t step, int32_t flags,
+                   void* stream, const uint8_t* select, int64_t nselect);
+
 /* ---- sample-rate conversion of the audio boundary ---------------------------------------
  * Rational polyphase resampler: what the reference does with librosa on the way into and out of Evaluate.predict
  * (Evaluate.py:59-67,104; Utils.py:94-95), fused with the channel mapping and the context padding around it.

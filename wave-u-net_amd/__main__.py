@@ -39,6 +39,10 @@ HBM (datasets.FusedSnippetSource; the default "torch" keeps the torch-operator /
 source-level augmentations: stems remixed across songs, channels swapped, polarity inverted, per source; `"speed":p` plays a
 snippet faster or slower, `"pitch_shift":p` transposes it at its tempo and `"time_stretch":p` changes its tempo in its key (a
 phase vocoder on the GPU in front of the same kernel).
+`train` takes `model_config.optimizer={"weight_decay":0.01,"ema_decay":0.999,"ema_warmup":True,"eval_with_ema":True}` (any subset:
+decoupled weight decay on the conv kernels, an EMA of the weights kept in the checkpoint and scored by validation) and
+`model_config.lr_schedule={"warmup_steps":1000,"kind":"cosine","total_steps":200000}`; `weights=ema` (predict, evaluate) then
+separates with the checkpoint's EMA weights instead of the trained ones.
 `evaluate` separates every track folder of data_root/<partition>, scores it on the GPU (BSS Eval v4: SDR / ISR / SIR / SAR per
 1 s segment, bsseval.py), writes estimates and museval-style JSON under estimates_path and prints the median / MAD / mean / SD per
 source.  Multi-GPU: launch `train` with `python -m torch.distributed.run --nproc-per-node N -m wave_u_net_amd train with ...`.
@@ -90,6 +94,15 @@ def _phase_iterations(opts):
     return n
 
 
+def _weights(opts):
+    """weights=trained|ema (predict, evaluate): checked here, so that a bad value ends the command at once."""
+    from wave_u_net_amd.evaluate import WEIGHTS
+    w = opts.get("weights")
+    if w is not None and w not in WEIGHTS:
+        raise SystemExit("weights must be one of %s, got %r" % (", ".join(WEIGHTS), w))
+    return w
+
+
 def _separation(opts, model_config):
     """overlap= / shifts= / max_shift=, else model_config["separation"]: checked here, so that a bad value ends the command at once."""
     from wave_u_net_amd.evaluate import blend_options, separation_options
@@ -133,7 +146,8 @@ def main(argv=None):
         folder = evaluate.produce_dataset_estimates(model_config, opts.get("model_path"), opts["data_root"],
                                                     opts["estimates_path"], partition=opts.get("partition", "test"),
                                                     postfilter=_postfilter(opts, model_config),
-                                                    phase_iterations=_phase_iterations(opts), **_separation(opts, model_config))
+                                                    phase_iterations=_phase_iterations(opts), weights=_weights(opts),
+                                                    **_separation(opts, model_config))
         for metric in ("SDR", "ISR", "SIR", "SAR"):
             stats = evaluate.compute_mean_metrics(folder, metric=metric)
             for src, (med, mad, mean, sd) in zip(model_config["source_names"], stats):
@@ -146,7 +160,8 @@ def main(argv=None):
             raise SystemExit("hop_frames must be a positive frame count or 'track', got %r" % (hop,))
         evaluate.produce_source_estimates(model_config, opts.get("model_path"), opts["input_path"], opts.get("output_path"),
                                           hop_frames=hop, postfilter=_postfilter(opts, model_config),
-                                          phase_iterations=_phase_iterations(opts), **_separation(opts, model_config))
+                                          phase_iterations=_phase_iterations(opts), weights=_weights(opts),
+                                          **_separation(opts, model_config))
 
 
 if __name__ == "__main__":

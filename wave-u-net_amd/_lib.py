@@ -52,6 +52,10 @@ class WunSpecTrainConfig(C.Structure):
     _fields_ = [("bn_decay", C.c_float), ("dropout_rate", C.c_float), ("dropout_seed", C.c_int64)]
 
 
+class WunOptimConfig(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("beta1", "beta2", "eps", "weight_decay", "ema_decay", "clip_norm")] + [("flags", C.c_int32)]
+
+
 class WunSnippetSource(C.Structure):
     _fields_ = [("start", C.c_int64), ("gain", C.c_float), ("flags", C.c_uint32)]
 
@@ -121,6 +125,10 @@ _SIGS = {
     "wun_grad_norm": (C.c_int, [_P, _P, C.c_float, _P, _P, C.POINTER(C.c_uint8), C.c_int64]),
     "wun_adam_step_clip": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                      C.c_float, C.c_int32, _P, _P, _P, C.POINTER(C.c_uint8), C.c_int64]),
+    "wun_optim_abi_size": (C.c_int64, []),
+    "wun_optim_step": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_float, C.c_float, C.POINTER(WunOptimConfig), _P, _P, _P,
+                                 C.POINTER(C.c_uint8), C.c_int64, C.POINTER(C.c_uint8), C.c_int64]),
+    "wun_ema_update": (C.c_int, [_P, _P, _P, C.c_float, C.c_int64, C.c_int32, _P, C.POINTER(C.c_uint8), C.c_int64]),
     "wun_resample_ratio": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "wun_resample_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "wun_resample_table_floats": (C.c_int64, [C.c_int32, C.c_int32]),
@@ -311,6 +319,7 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGS))
 WUN_CLIP_SKIP_NONFINITE = 1      # wun_adam_step_clip flags
+WUN_OPTIM_EMA_WARMUP = 2         # wun_optim_step / wun_ema_update flags
 _lib = None
 
 # Process-wide record of the scheduling hint wun_config.exclusive_streams (include/wun.h): plans created with it run
@@ -362,6 +371,9 @@ def load():
     if lib.wun_stretch_abi_size() != C.sizeof(WunStretchJob):
         raise RuntimeError("libwun.so wun_stretch_job size %d != this binding's %d (stale library or binding)" % (
             lib.wun_stretch_abi_size(), C.sizeof(WunStretchJob)))
+    if lib.wun_optim_abi_size() != C.sizeof(WunOptimConfig):
+        raise RuntimeError("libwun.so wun_optim_config size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_optim_abi_size(), C.sizeof(WunOptimConfig)))
     if lib.wun_blend_abi_size() != C.sizeof(WunBlendWindow):
         raise RuntimeError("libwun.so wun_blend_window size %d != this binding's %d (stale library or binding)" % (
             lib.wun_blend_abi_size(), C.sizeof(WunBlendWindow)))

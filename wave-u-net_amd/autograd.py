@@ -130,6 +130,7 @@ class WaveUNet(torch.nn.Module):
         return [n for n in self.variable_names() if n in self._frozen]
 
     def forward(self, mix):
+        self.sep._refuse_in_ema("the autograd module's forward (it runs on its own arena, the trained weights)")
         dev = self.arena.device
         if not torch.is_tensor(mix):
             mix = torch.as_tensor(np.asarray(mix, dtype=np.float32))
@@ -141,6 +142,18 @@ class WaveUNet(torch.nn.Module):
         if self._frozen:
             mask = np.array([0 if n in self._frozen else 1 for n in self.variable_names()], dtype=np.uint8)
         return GetOutput.apply(mix, self.arena, self.sep, mask)
+
+    def ema_update(self, decay, warmup=False, variables=None, step=None):
+        """After the user's optimizer.step(): the separator's EMA of the weights moves towards the arena (sep.ema_update,
+        wun_ema_update; the EMA arena starts as a copy of the weights at the first call).  step: TF's num_updates, needed for
+        warmup=True -- the caller's own count of optimizer steps, which it keeps (and checkpoints) with its torch optimizer;
+        the module keeps no counter.  sep.ema_variables() reads the EMA.  sep.ema_weights() serves the SEPARATOR's own calls
+        (get_output, separate_track, validation): this module's forward takes `arena`, the trained Parameter, so it is
+        refused inside that block rather than run quietly on the trained weights."""
+        if warmup and step is None:
+            raise ValueError("ema_update(warmup=True) needs step = the number of optimizer steps made so far")
+        with torch.no_grad():
+            self.sep.ema_update(decay, warmup=warmup, variables=variables, step=0 if step is None else step)
 
     def named_variables(self):
         """tf_name -> view of the arena (the TF variables, UnetAudioSeparator.py)."""

@@ -19,6 +19,11 @@ import torch
 from . import tf_checkpoint
 
 SOLVER_SCOPE = "separator_solver"
+# The EMA of the weights (UnetAudioSeparator.ema), written only when the separator has one: `.npz` entries
+# "ema/<variable>"; in the TF format "<variable>/ExponentialMovingAverage", the name tf.train.ExponentialMovingAverage.apply
+# gives a variable's shadow (the reference builds no EMA, so no TF-written file with these names exists to check against).
+EMA_PREFIX = "ema/"
+EMA_SUFFIX = "/ExponentialMovingAverage"
 
 
 def _tensors(separator):
@@ -54,6 +59,7 @@ def load_checkpoint(separator, path, with_optimizer=True):
                 _fill(separator.adam_m, off, shp, ck["%s/%s/Adam" % (SOLVER_SCOPE, name)], name + "/Adam")
                 _fill(separator.adam_v, off, shp, ck["%s/%s/Adam_1" % (SOLVER_SCOPE, name)], name + "/Adam_1")
         step = int(ck["global_step"]) if "global_step" in ck else 0
+        ema = {n: ck[n + EMA_SUFFIX] for n, _, _ in tensors if (n + EMA_SUFFIX) in ck}
     else:
         state = np.load(path)
         separator.load_variables({k: state[k] for k in state.files if k.startswith("separator/")})
@@ -61,6 +67,17 @@ def load_checkpoint(separator, path, with_optimizer=True):
             separator.adam_m.copy_(torch.from_numpy(state["adam_m"]))
             separator.adam_v.copy_(torch.from_numpy(state["adam_v"]))
         step = int(state["global_step"]) if "global_step" in state.files else 0
+        ema = {n: state[EMA_PREFIX + n] for n, _, _ in tensors if (EMA_PREFIX + n) in state.files}
+    # the EMA of the weights (separator.ema) is weights, not optimizer state: restored whenever the file has it; a
+    # separator that keeps an EMA and loads a file without one starts it from the restored variables
+    if ema and len(ema) != len(tensors):
+        raise KeyError("checkpoint %s has EMA entries for %d of this model's %d variables" % (path, len(ema), len(tensors)))
+    if ema:
+        arena = separator._ensure_ema()
+        for name, off, shp in tensors:
+            _fill(arena, off, shp, ema[name], name + " (EMA)")
+    elif getattr(separator, "ema", None) is not None:
+        separator.ema.copy_(separator.params)
     separator.global_step = step
     return step
 
@@ -73,11 +90,14 @@ def save_checkpoint(separator, path, fmt=None, beta1=0.9, beta2=0.999):
         fmt = "npz" if path.endswith(".npz") else "tf"
     variables = {n: v.detach().cpu().numpy() for n, v in separator.variables().items()}
     step = int(separator.global_step)
+    ema = separator.ema_variables() if getattr(separator, "ema", None) is not None else None
     if fmt == "npz":
         arrays = dict(variables)
         arrays["adam_m"] = separator.adam_m.cpu().numpy()
         arrays["adam_v"] = separator.adam_v.cpu().numpy()
         arrays["global_step"] = np.int64(step)
+        if ema is not None:
+            arrays.update({EMA_PREFIX + n: a for n, a in ema.items()})
         np.savez(path, **arrays)
         return path if path.endswith(".npz") else path + ".npz"
     if fmt != "tf":
@@ -89,6 +109,8 @@ def save_checkpoint(separator, path, fmt=None, beta1=0.9, beta2=0.999):
         n = int(np.prod(shp)) if len(shp) else 1
         out["%s/%s/Adam" % (SOLVER_SCOPE, name)] = m[off:off + n].reshape(shp)
         out["%s/%s/Adam_1" % (SOLVER_SCOPE, name)] = v[off:off + n].reshape(shp)
+    if ema is not None:
+        out.update({n + EMA_SUFFIX: a for n, a in ema.items()})
     # TF's Adam keeps beta ** (number of updates + 1) in two accumulator variables
     out["%s/beta1_power" % SOLVER_SCOPE] = np.asarray(beta1 ** (step + 1), dtype=np.float32)
     out["%s/beta2_power" % SOLVER_SCOPE] = np.asarray(beta2 ** (step + 1), dtype=np.float32)

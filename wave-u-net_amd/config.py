@@ -38,6 +38,13 @@ EXTENSION_DEFAULTS = {
     "clip_grad_norm": None,           # training.Trainer: tf.clip_by_global_norm threshold
     "skip_nonfinite_steps": False,    # training.Trainer: skip an update whose gradient norm is not finite
     "checkpoint_format": "npz",       # training.train: "npz" or "tf"
+    # training.Trainer: None = the reference's TF-Adam; else {"weight_decay": w, "decay_variables": [...] | None,
+    # "ema_decay": d, "ema_warmup": bool, "eval_with_ema": bool} (any subset): decoupled weight decay (AdamW; None = every conv
+    # kernel, no bias), an EMA of the weights kept in the checkpoints, and validation / early stopping on the EMA values
+    "optimizer": None,
+    # training.Trainer / training.lr_factor: None = constant init_sup_sep_lr; else {"warmup_steps": n, "kind": "constant" |
+    # "cosine" | "step" | "exponential", "total_steps", "min_factor", "step_size", "gamma"}: the factor on the lr per global_step
+    "lr_schedule": None,
     # training.Trainer / spectral.SpectralLoss: None = the reference's MSE; else {"resolutions": [[n_fft, hop], ...],
     # "weights": [...], "mse_weight": w}: the objective becomes w * MSE + sum_j weight_j * STFT-magnitude L1 (Training.py:55-60);
     # with "terms": {"mag_l1" | "log_mag_l1" | "sc" | "complex_l1": weight} (and "log_eps", "sc_eps") the multi-resolution STFT loss;

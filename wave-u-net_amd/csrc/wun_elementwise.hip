@@ -1148,6 +1148,147 @@ hipError_t launch_adam_clip_ranges(float* p, const float* g, float* m, float* v,
     return hipGetLastError();
 }
 
+// ---- the extended optimizer (wun_optim_step, wun_ema_update): decoupled weight decay and an EMA of the weights, fused --------
+// One kernel over the selected runs: a float's g, clip scale, m and v are adam_update's / adam_clipped's expressions in their
+// order, theta is decayed first when its run decays (one product, rounded), then takes wun_adam_step's step, and the EMA moves
+// towards the NEW theta (tf assign_moving_average: ema -= (1 - d) (ema - theta), difference, product and difference each
+// rounded -- no fused multiply-add anywhere the formula has none).  20 bytes read and 16 written per float with all five arrays:
+// 16-byte loads and stores from each piece's first 16-byte aligned float when the arenas share one alignment (a.vec), the head and
+// the tail -- or the whole piece -- by single floats through the same optim_one, so the bits do not depend on the alignment.
+__device__ __forceinline__ void optim_one(float gi, float& pi, float& mi, float& vi, float& ei, const OptimArgs& a, bool decay,
+                                          bool ema) {
+#pragma clang fp contract(off)
+    mi = fmaf(a.b1, mi, (1.f - a.b1) * gi);
+    vi = fmaf(a.b2, vi, (1.f - a.b2) * gi * gi);
+    if (decay) pi = pi * a.wdf;
+    pi = pi - a.lr_t * mi / (sqrtf(vi) + a.eps);
+    if (ema) ei = ei - a.emaw * (ei - pi);
+}
+
+__device__ __forceinline__ void ema_one(float pi, float& ei, float emaw) {
+#pragma clang fp contract(off)
+    ei = ei - emaw * (ei - pi);
+}
+
+// The walk: the launch's runs laid end to end and cut into chunks of WUN_OPTIM_CHUNK floats, one workgroup per chunk (grid-
+// strided), so every workgroup has the same amount of work whatever the runs' sizes -- a launch of 32 small and large runs is
+// one pass, not 32.  A chunk's pieces (it spans a run boundary wherever one falls inside it) go to f(run k, first arena float,
+// length): the pieces' floats are exactly the runs' floats, each visited once.
+#define WUN_OPTIM_CHUNK 1024
+template <class F>
+__device__ __forceinline__ void for_each_piece(const AdamRanges& r, long long chunk, F f) {
+    const long long total = r.cum[r.n], t0 = chunk * WUN_OPTIM_CHUNK;
+    const long long t1 = t0 + WUN_OPTIM_CHUNK < total ? t0 + WUN_OPTIM_CHUNK : total;
+    int k = 0;
+    while (k + 1 < r.n && t0 >= r.cum[k + 1]) ++k;
+    for (; k < r.n && r.cum[k] < t1; ++k) {
+        const long long lo = t0 > r.cum[k] ? t0 : r.cum[k], hi = t1 < r.cum[k + 1] ? t1 : r.cum[k + 1];
+        f(k, r.off[k] + (lo - r.cum[k]), (int)(hi - lo));
+    }
+}
+
+// a piece cut for the vector loop: [0, head) and [tail0, len) by single floats, nv groups of four between them (vec == 0: all
+// of it by single floats)
+struct OptimCut { int head, nv, tail0, nsc; };
+__device__ __forceinline__ OptimCut optim_cut(const float* first, int len, int vec) {
+    OptimCut c;
+    const int h = (int)(((16 - (reinterpret_cast<uintptr_t>(first) & 15)) & 15) >> 2);
+    c.head = vec ? (h < len ? h : len) : len;
+    c.nv = (len - c.head) >> 2;
+    c.tail0 = c.head + 4 * c.nv;
+    c.nsc = c.head + (len - c.tail0);
+    return c;
+}
+
+__global__ __launch_bounds__(256) void optim_ranges_kernel(OptimArgs a, AdamRanges r) {
+    AdamClip c;
+    c.clipping = false; c.cs = 1.f;
+    if (a.gnorm && !adam_clip_prologue(a.gnorm, a.clip, a.skip, a.skipped, c)) return;
+    const bool ema = a.ema != nullptr;
+    const int t = threadIdx.x;
+    const long long nchunks = (r.cum[r.n] + WUN_OPTIM_CHUNK - 1) / WUN_OPTIM_CHUNK;
+    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        for_each_piece(r, chunk, [&](int k, long long lo, int len) {
+            const OptimCut u = optim_cut(a.p + lo, len, a.vec);
+            const bool decay = (a.decay >> k) & 1u;
+            for (int j = t; j < u.nsc; j += 256) {
+                const long long i = lo + (j < u.head ? j : u.tail0 + (j - u.head));
+                float pi = a.p[i], mi = a.m[i], vi = a.v[i], ei = ema ? a.ema[i] : 0.f;
+                optim_one(adam_clipped(a.g[i] * a.gscale, c), pi, mi, vi, ei, a, decay, ema);
+                a.m[i] = mi; a.v[i] = vi; a.p[i] = pi;
+                if (ema) a.ema[i] = ei;
+            }
+            for (int j = t; j < u.nv; j += 256) {
+                const long long i = lo + u.head + 4 * j;
+                const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.g + i);
+                f32x4 p4 = *reinterpret_cast<const f32x4*>(a.p + i);
+                f32x4 m4 = *reinterpret_cast<const f32x4*>(a.m + i);
+                f32x4 v4 = *reinterpret_cast<const f32x4*>(a.v + i);
+                f32x4 e4 = {0.f, 0.f, 0.f, 0.f};
+                if (ema) e4 = *reinterpret_cast<const f32x4*>(a.ema + i);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float pi = p4[q], mi = m4[q], vi = v4[q], ei = e4[q];
+                    optim_one(adam_clipped(g4[q] * a.gscale, c), pi, mi, vi, ei, a, decay, ema);
+                    p4[q] = pi; m4[q] = mi; v4[q] = vi; e4[q] = ei;
+                }
+                *reinterpret_cast<f32x4*>(a.m + i) = m4;
+                *reinterpret_cast<f32x4*>(a.v + i) = v4;
+                *reinterpret_cast<f32x4*>(a.p + i) = p4;
+                if (ema) *reinterpret_cast<f32x4*>(a.ema + i) = e4;
+            }
+        });
+    }
+}
+
+// the EMA line alone (wun_ema_update): ema_one is optim_one's last line, so the bits are the fused path's for the same theta
+__global__ __launch_bounds__(256) void ema_ranges_kernel(float* ema, const float* p, float emaw, int vec, AdamRanges r) {
+    const int t = threadIdx.x;
+    const long long nchunks = (r.cum[r.n] + WUN_OPTIM_CHUNK - 1) / WUN_OPTIM_CHUNK;
+    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        for_each_piece(r, chunk, [&](int, long long lo, int len) {
+            const OptimCut u = optim_cut(p + lo, len, vec);
+            for (int j = t; j < u.nsc; j += 256) {
+                const long long i = lo + (j < u.head ? j : u.tail0 + (j - u.head));
+                float ei = ema[i];
+                ema_one(p[i], ei, emaw);
+                ema[i] = ei;
+            }
+            for (int j = t; j < u.nv; j += 256) {
+                const long long i = lo + u.head + 4 * j;
+                const f32x4 p4 = *reinterpret_cast<const f32x4*>(p + i);
+                f32x4 e4 = *reinterpret_cast<const f32x4*>(ema + i);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float ei = e4[q];
+                    ema_one(p4[q], ei, emaw);
+                    e4[q] = ei;
+                }
+                *reinterpret_cast<f32x4*>(ema + i) = e4;
+            }
+        });
+    }
+}
+
+// one workgroup per chunk of WUN_OPTIM_CHUNK floats (four per thread), at most 2048 workgroups (eight per CU), grid-strided beyond
+static unsigned optim_grid(long long n) { return (unsigned)std::min(std::max((n + WUN_OPTIM_CHUNK - 1) / WUN_OPTIM_CHUNK, 1LL), 2048LL); }
+
+hipError_t launch_optim_ranges(const OptimArgs& a, const AdamRanges& r, hipStream_t s) {
+    const long long n = r.n > 0 ? r.cum[r.n] : 0;
+    if (n <= 0) return hipSuccess;
+    ProfScope ps("optim_ranges_kernel", 0.0, s, "", (a.ema ? 36.0 : 28.0) * (double)n);
+    hipLaunchKernelGGL(optim_ranges_kernel, dim3(optim_grid(n)), dim3(256), 0, s, a, r);
+    return hipGetLastError();
+}
+
+hipError_t launch_ema_ranges(float* ema, const float* p, float emaw, int vec, const AdamRanges& r, hipStream_t s) {
+    const long long n = r.n > 0 ? r.cum[r.n] : 0;
+    if (n <= 0) return hipSuccess;
+    ProfScope ps("ema_ranges_kernel", 0.0, s, "", 12.0 * (double)n);
+    hipLaunchKernelGGL(ema_ranges_kernel, dim3(optim_grid(n)), dim3(256), 0, s, ema, p, emaw, vec, r);
+    return hipGetLastError();
+}
+
 __global__ void fill_kernel(float* p, long long n, float val) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) p[i] = val;

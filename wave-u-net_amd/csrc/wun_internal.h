@@ -362,6 +362,19 @@ hipError_t launch_adam_clip(float* p, const float* g, float* m, float* v, long l
 hipError_t launch_adam_clip_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t, float b1,
                                    float b2, float eps, float gscale, const float* gnorm, float clip, int skip,
                                    long long* skipped, hipStream_t s);
+// The extended optimizer over selected runs (wun_optim_step): adam_clip_ranges_kernel's gradient, m and v; theta times wdf
+// first in the runs whose bit of `decay` is set, then wun_adam_step's step; ema (may be null) -= emaw * (ema - new theta).
+// gnorm null: no clip prologue (nothing clips, nothing skips).  vec: the arenas share one alignment modulo 16 bytes, so the
+// 16-byte path may run; the bits are the scalar path's.
+struct OptimArgs {
+    float* p; const float* g; float* m; float* v; float* ema;
+    float lr_t, b1, b2, eps, gscale, wdf, emaw;
+    const float* gnorm; float clip; int skip; long long* skipped;
+    unsigned decay; int vec;
+};
+hipError_t launch_optim_ranges(const OptimArgs& a, const AdamRanges& r, hipStream_t s);
+// the EMA line alone over selected runs (wun_ema_update)
+hipError_t launch_ema_ranges(float* ema, const float* p, float emaw, int vec, const AdamRanges& r, hipStream_t s);
 hipError_t launch_fill(float* p, long long n, float val, hipStream_t s);
 hipError_t launch_mfma_probe(const float* a, const float* b, float* d, hipStream_t s);
 void prof_begin(bool detail);                 // detail: per-launch list in the JSON (WUN_PROFILE_DETAIL)

@@ -1,5 +1,6 @@
 // Host side of libwun.so: the optimizer of the training step -- TF-Adam over the whole arena or a selection of its tensors,
-// the global gradient norm, and the clipped / skipping Adam step built on it.
+// the global gradient norm, the clipped / skipping Adam step built on it, and that step extended by decoupled weight decay and
+// an EMA of the weights (wun_optim_step, wun_ema_update).
 #include "wun_plan_impl.h"
 
 #include <cmath>
@@ -141,6 +142,126 @@ extern "C" int wun_adam_step_clip(const wun_plan* p, float* params, const float*
     return for_each_range_batch(p, select, [&](const AdamRanges& r, bool first) -> int {
         HIP_TRY(launch_adam_clip_ranges(params, grads, m, v, r, lr_t, beta1, beta2, eps, grad_scale, gnorm, clip_norm, skip,
                                         first ? cnt : nullptr, s));
+        return WUN_OK;
+    });
+}
+
+// ---------------------------------------------------------------------------------------
+// the extended optimizer: decoupled weight decay (AdamW) and an EMA of the weights, fused into the clipped Adam step
+// ---------------------------------------------------------------------------------------
+extern "C" int64_t wun_optim_abi_size(void) { return (int64_t)sizeof(wun_optim_config); }
+
+// for_each_range_batch with a per-run decay bit: tensors merge into a run only when they agree on it.  select NULL = every
+// tensor (the padding floats between tensors belong to no run: unlike wun_adam_step's whole-arena kernel, nothing visits them).
+// launch(const AdamRanges&, unsigned decay_bits, bool first) -> int
+template <class Launch>
+static int for_each_optim_batch(const wun_plan* p, const uint8_t* select, const uint8_t* decay, bool decay_all, Launch launch) {
+    AdamRanges r;
+    memset(&r, 0, sizeof(r));
+    unsigned bits = 0;
+    bool first = true;
+    int rc;
+    for (size_t k = 0; k < p->tensors.size(); ++k) {
+        if (select && !select[k]) continue;
+        const wun_tensor_info& t = p->tensors[k];
+        const bool dk = decay_all || (decay && decay[k]);
+        long long n = 1;
+        for (int d = 0; d < t.ndim; ++d) n *= t.shape[d];
+        if (r.n > 0 && r.off[r.n - 1] + (r.cum[r.n] - r.cum[r.n - 1]) == t.offset && (((bits >> (r.n - 1)) & 1u) != 0) == dk) {
+            r.cum[r.n] += n;
+            continue;
+        }
+        if (r.n == WUN_ADAM_RANGES) {
+            if ((rc = launch(r, bits, first))) return rc;
+            first = false;
+            memset(&r, 0, sizeof(r));
+            bits = 0;
+        }
+        r.off[r.n] = t.offset; r.cum[r.n + 1] = r.cum[r.n] + n;
+        if (dk) bits |= 1u << r.n;
+        ++r.n;
+    }
+    return r.n > 0 ? launch(r, bits, first) : WUN_OK;
+}
+
+// 1 - d_t of the EMA, formed in float64 and rounded once: d_t = decay, or min(decay, (1 + step) / (10 + step)) with warm-up
+static float ema_weight(float ema_decay, int64_t step, bool warmup) {
+    double d = (double)ema_decay;
+    if (warmup) d = std::min(d, (1.0 + (double)step) / (10.0 + (double)step));
+    return (float)(1.0 - d);
+}
+
+static bool same_alignment(std::initializer_list<const void*> ptrs) {
+    uintptr_t a = 0;
+    bool have = false;
+    for (const void* q : ptrs) {
+        if (!q) continue;
+        const uintptr_t x = reinterpret_cast<uintptr_t>(q) & 15;
+        if (have && x != a) return false;
+        a = x; have = true;
+    }
+    return true;
+}
+
+extern "C" int wun_optim_step(const wun_plan* p, float* params, const float* grads, float* m, float* v, float* ema,
+                              int64_t step, float lr, float grad_scale, const wun_optim_config* cfg, float* norm_ws,
+                              int64_t* skipped, void* stream, const uint8_t* select, int64_t nselect,
+                              const uint8_t* decay_select, int64_t ndecay) {
+    int rc;
+    if ((rc = adam_args(p, params, grads, m, v, step))) return rc;
+    if (!cfg) return fail(WUN_ERR_INVALID, "null argument");
+    if (!(cfg->weight_decay >= 0.f)) return fail(WUN_ERR_INVALID, "weight_decay must be >= 0");
+    if (ema && !(cfg->ema_decay >= 0.f && cfg->ema_decay < 1.f)) return fail(WUN_ERR_INVALID, "ema_decay must be in [0, 1)");
+    if (!(cfg->clip_norm > 0.f)) return fail(WUN_ERR_INVALID, "clip_norm must be > 0 (+INFINITY = no clipping)");
+    if (cfg->flags & ~(WUN_CLIP_SKIP_NONFINITE | WUN_OPTIM_EMA_WARMUP)) return fail(WUN_ERR_INVALID, "unknown flags");
+    const int skip = (cfg->flags & WUN_CLIP_SKIP_NONFINITE) ? 1 : 0;
+    if (skip && !skipped) return fail(WUN_ERR_INVALID, "skipped is required with WUN_CLIP_SKIP_NONFINITE");
+    if ((rc = check_nselect(p, select, nselect))) return rc;
+    if ((rc = check_nselect(p, decay_select, ndecay))) return rc;
+    // the norm is needed to clip or to decide a skip: with neither it is not launched and norm_ws may be NULL
+    const bool need_norm = skip || !std::isinf(cfg->clip_norm);
+    hipStream_t s = (hipStream_t)stream;
+    NormSelect sel;
+    long long nfloats;
+    if (need_norm) {
+        if ((rc = norm_args(p, grads, norm_ws, select, nselect, sel, nfloats))) return rc;
+        if ((rc = grad_norm_launch(p, grads, grad_scale, norm_ws, sel, nfloats, s))) return rc;
+    }
+    OptimArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p = params; a.g = grads; a.m = m; a.v = v; a.ema = ema;
+    a.lr_t = adam_lr_t(step, lr, cfg->beta1, cfg->beta2);
+    a.b1 = cfg->beta1; a.b2 = cfg->beta2; a.eps = cfg->eps; a.gscale = grad_scale;
+    a.wdf = (float)(1.0 - (double)lr * (double)cfg->weight_decay);
+    a.emaw = ema ? ema_weight(cfg->ema_decay, step, (cfg->flags & WUN_OPTIM_EMA_WARMUP) != 0) : 0.f;
+    a.gnorm = need_norm ? norm_ws + p->tensors.size() : nullptr;
+    a.clip = cfg->clip_norm; a.skip = skip;
+    a.vec = same_alignment({params, grads, m, v, ema}) ? 1 : 0;
+    const bool decaying = cfg->weight_decay > 0.f;
+    long long* cnt = skip ? reinterpret_cast<long long*>(skipped) : nullptr;
+    return for_each_optim_batch(p, select, decaying ? decay_select : nullptr, decaying && !decay_select,
+                                [&](const AdamRanges& r, unsigned bits, bool first) -> int {
+        OptimArgs b = a;
+        b.decay = bits;
+        b.skipped = first ? cnt : nullptr;            // every launch of a skipped step returns at once; the first counts it
+        HIP_TRY(launch_optim_ranges(b, r, s));
+        return WUN_OK;
+    });
+}
+
+extern "C" int wun_ema_update(const wun_plan* p, float* ema, const float* params, float ema_decay, int64_t step, int32_t flags,
+                              void* stream, const uint8_t* select, int64_t nselect) {
+    if (!p || !ema || !params) return fail(WUN_ERR_INVALID, "null argument");
+    if (!(ema_decay >= 0.f && ema_decay < 1.f)) return fail(WUN_ERR_INVALID, "ema_decay must be in [0, 1)");
+    if (step < 0) return fail(WUN_ERR_INVALID, "step must be >= 0");
+    if (flags & ~WUN_OPTIM_EMA_WARMUP) return fail(WUN_ERR_INVALID, "unknown flags");
+    int rc;
+    if ((rc = check_nselect(p, select, nselect))) return rc;
+    const float w = ema_weight(ema_decay, step, (flags & WUN_OPTIM_EMA_WARMUP) != 0);
+    const int vec = same_alignment({ema, params}) ? 1 : 0;
+    hipStream_t s = (hipStream_t)stream;
+    return for_each_optim_batch(p, select, nullptr, false, [&](const AdamRanges& r, unsigned, bool) -> int {
+        HIP_TRY(launch_ema_ranges(ema, params, w, vec, r, s));
         return WUN_OK;
     });
 }

@@ -324,13 +324,32 @@ def _separate_blend_chunks(separator, padded, table, lead, v_frames, batch_hops,
     return blend.blend_finish(preds, den)
 
 
+WEIGHTS = ("trained", "ema")
+
+
+def weights_context(separator, weights):
+    """The context predict / evaluate separate under: weights None or "trained" = the separator as it is; "ema" =
+    separator.ema_weights(), the EMA of the weights its checkpoint carries.  ValueError for another value,
+    RuntimeError when the separator (its checkpoint) has no EMA."""
+    import contextlib
+    if weights not in (None,) + WEIGHTS:
+        raise ValueError("weights = %r, expected one of %s" % (weights, ", ".join(WEIGHTS)))
+    if weights != "ema":
+        return contextlib.nullcontext()
+    if getattr(separator, "ema", None) is None:
+        raise RuntimeError("weights='ema': the checkpoint (or the separator given) has no EMA of the weights -- it was "
+                           "trained without model_config['optimizer']['ema_decay']")
+    return separator.ema_weights()
+
+
 def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None, hop_frames=None,
-                             postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None):
+                             postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None, *, weights=None):
     """Evaluate.produce_source_estimates (Evaluate.py:160-194): separate one mixture file with a
     checkpoint and write <input file name>_<source>.wav next to it (or into output_path), at the input file's sample rate
     and length.  WAV/NPY input at any rate (an .npy is taken to be at expected_sr; no MP3 decoding here): the separation runs
     through separate_track (hop_frames, postfilter, phase_iterations, overlap, shifts, max_shift: its options of those
-    names; overlap / shifts / max_shift None: model_config["separation"]'s, else none).  Returns {source: [T, C]}."""
+    names; overlap / shifts / max_shift None: model_config["separation"]'s, else none).  weights="ema": separate with the EMA
+    of the weights that the checkpoint carries (weights_context; RuntimeError when it has none).  Returns {source: [T, C]}."""
     import os
     from scipy.io import wavfile
     from . import datasets
@@ -342,8 +361,9 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
-    preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames, postfilter=postfilter,
-                           phase_iterations=phase_iterations, **separation_options(model_config, overlap, shifts, max_shift))
+    with weights_context(sep, weights):
+        preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames, postfilter=postfilter,
+                               phase_iterations=phase_iterations, **separation_options(model_config, overlap, shifts, max_shift))
     folder, name = os.path.split(input_path)
     if output_path is None:
         output_path = folder
@@ -428,21 +448,29 @@ def compute_mean_metrics(json_folder, compute_averages=True, metric="SDR"):
 
 
 def produce_dataset_estimates(model_config, load_model, data_root, output_path, partition="test", separator=None,
-                              hop_frames=None, postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None):
+                              hop_frames=None, postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None,
+                              *, weights=None):
     """The reference's produce_musdb_source_estimates (Evaluate.py:147-159) over the track folders of datasets.py:
     data_root/<partition>/<track>/<source>.wav|.npy (+ optional mix.wav|.npy, default: the sum of the stems), every file at
     one rate (an .npy: expected_sr).  Per track: the estimates as <output_path>/<partition>/<track>/<source>.wav and the
-    scores as <output_path>/<partition>/<track>.json.  Returns the folder of the JSON files (compute_mean_metrics reads it)."""
-    import os
-    from scipy.io import wavfile
-    from . import bsseval, datasets
+    scores as <output_path>/<partition>/<track>.json.  Returns the folder of the JSON files (compute_mean_metrics reads it).
+    weights="ema": separate with the EMA of the weights (weights_context)."""
     from .spectrogram import make_separator
     sep = separator if separator is not None else make_separator(model_config)
     if load_model is not None:
         from .checkpoint import load_checkpoint
         load_checkpoint(sep, load_model, with_optimizer=False)
+    with weights_context(sep, weights):
+        return _dataset_estimates(model_config, sep, data_root, output_path, partition, hop_frames, postfilter, phase_iterations,
+                                  separation_options(model_config, overlap, shifts, max_shift))
+
+
+def _dataset_estimates(model_config, sep, data_root, output_path, partition, hop_frames, postfilter, phase_iterations, blend_kw):
+    """produce_dataset_estimates on a loaded separator."""
+    import os
+    from scipy.io import wavfile
+    from . import bsseval, datasets
     names = list(model_config["source_names"])
-    blend_kw = separation_options(model_config, overlap, shifts, max_shift)
     base = os.path.join(data_root, partition)
     out_dir = os.path.join(output_path, partition)
     os.makedirs(out_dir, exist_ok=True)

@@ -9,6 +9,7 @@ include/wun.h.  Because there is no tf.gradients here, the object additionally e
 
 torch is used for device memory, streams and torch.distributed only.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -50,6 +51,28 @@ def check_clip_norm(clip_norm):
     if isinstance(clip_norm, bool) or not c > 0:
         raise ValueError("clip_norm = %r must be > 0 (None or inf = no clipping)" % (clip_norm,))
     return c
+
+
+def check_weight_decay(weight_decay):
+    """weight_decay of adam_step / the optimizer dict -> float; ValueError unless a number >= 0 (NaN is refused)."""
+    try:
+        w = float(weight_decay)
+    except (TypeError, ValueError):
+        raise ValueError("weight_decay = %r must be a number >= 0" % (weight_decay,))
+    if isinstance(weight_decay, bool) or not w >= 0 or math.isinf(w):
+        raise ValueError("weight_decay = %r must be a finite number >= 0" % (weight_decay,))
+    return w
+
+
+def check_ema_decay(ema_decay):
+    """ema_decay -> float; ValueError unless a number in [0, 1)."""
+    try:
+        d = float(ema_decay)
+    except (TypeError, ValueError):
+        raise ValueError("ema_decay = %r must be a number in [0, 1)" % (ema_decay,))
+    if isinstance(ema_decay, bool) or not 0 <= d < 1:
+        raise ValueError("ema_decay = %r must be in [0, 1)" % (ema_decay,))
+    return d
 
 
 class _Plan(object):
@@ -117,6 +140,9 @@ class UnetAudioSeparator(object):
         self.params = None           # flat float32 arena (TF creation order)
         self.grads = self.adam_m = self.adam_v = None
         self.global_step = 0
+        self.ema = None              # EMA of params, an arena like adam_m (created on first use: _ensure_ema)
+        self._in_ema = False         # inside ema_weights(): params and ema are exchanged
+        self._step_phase = 0         # 1: a training forward is open, 2: gradients are pending (until adam_step)
         self._norm_ws = self._skipped = None     # wun_grad_norm workspace, skipped-step counter (allocated on first use)
         self._ws = {}
         self._ws_gen = {}            # (batch, frames) -> forward passes run on that workspace (autograd's stale-workspace guard)
@@ -226,6 +252,8 @@ class UnetAudioSeparator(object):
         (torch tensor on the GPU, or anything np.asarray accepts).  Returns a dict
         source_name -> [batch, num_out_samples, num_channels] torch tensor (views of one
         buffer that is overwritten by the next call with the same shape)."""
+        if training:
+            self._refuse_in_ema("get_output(training=True)")
         dev = self._dev()
         if not torch.is_tensor(input):
             input = torch.as_tensor(np.asarray(input, dtype=np.float32))
@@ -242,6 +270,10 @@ class UnetAudioSeparator(object):
         self._ws_gen[key] = self._ws_gen.get(key, 0) + 1
         self._active, self._last_mix, self._last_key = plan, mix, key
         self._last_training = bool(training)
+        if training:
+            self._step_phase = max(self._step_phase, 1)
+        elif self._step_phase == 1:
+            self._step_phase = 0
         return {name: outs[i] for i, name in enumerate(self.source_names)}
 
     # ------------------------------------------------------------------ whole tracks (wun_forward_windows / wun_separate_track)
@@ -424,10 +456,12 @@ class UnetAudioSeparator(object):
         and d total / d outputs on the current stream without a host sync.  spectral.SpectralLoss, waveform.WaveformLoss
         (MSE, L1, SI-SDR, SNR; last_losses is then [total, mse, l1, si_sdr, snr, dB per source ...]) and
         waveform.CombinedLoss (the sum of the two) are the package's own."""
+        self._refuse_in_ema("loss_and_gradients")
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
         tg = self._stacked(targets, "targets")
+        self._step_phase = 2
         if loss is not None:
             outs = self._outs[self._last_key]
             if self._last_key not in self._d_outs:
@@ -486,10 +520,13 @@ class UnetAudioSeparator(object):
         are wanted (None = all; the others' floats in self.grads are not written); variables=[] with input_grad=True is the
         input-only gradient (wun_backward_select).  accumulate: ADD the parameter gradients to self.grads
         (wun_backward_accumulate); dL/d mix is still written."""
+        self._refuse_in_ema("backward")
         mask = self.select_mask(variables)
         if self._active is None or not self._last_training:
             raise RuntimeError("call get_output(..., training=True) first")
         dout = self._stacked(d_outputs, "d_outputs")
+        if mask is None or mask.any():
+            self._step_phase = 2
         d_mix = torch.empty(tuple(self._last_mix.shape), dtype=torch.float32, device=self._dev()) if input_grad else None
         self._run_backward(self._ws[self._last_key], self._outs[self._last_key], dout, self.grads, d_mix,
                            bucket_starts, bucket_events, mask, accumulate)
@@ -533,8 +570,80 @@ class UnetAudioSeparator(object):
         """Reuse choices exported by a plan of the same config / batch / length (ValueError otherwise)."""
         _lib.check(self._lib.wun_plan_tune_import(self._active.handle, text.encode()))
 
+    # ------------------------------------------------------------------ EMA of the weights (wun_optim_step, wun_ema_update)
+    def _ensure_ema(self):
+        """The EMA arena, created on first use as a copy of params (TF's shadow variables start at the variable's value)."""
+        if self.ema is None:
+            self._ensure_variables(self._active if self._active is not None else self._any_plan())
+            self.ema = self.params.clone()
+        return self.ema
+
+    def ema_variables(self):
+        """dict tf_name -> numpy array of the EMA values (RuntimeError when no EMA exists)."""
+        if self.ema is None:
+            raise RuntimeError("this separator has no EMA of its weights (adam_step(ema_decay=...) / ema_update create one)")
+        plan = self._any_plan()
+        host = self.ema.cpu().numpy()
+        return {name: host[off:off + int(np.prod(shp))].reshape(shp).copy() for name, off, shp in plan.tensors}
+
+    def ema_update(self, decay, warmup=False, variables=None, step=None):
+        """ema -= (1 - d_t) * (ema - params) on `variables` (None = all), d_t = decay or, with warmup, min(decay, (1 + step) /
+        (10 + step)) -- tf.train.ExponentialMovingAverage.apply; wun_ema_update, the bits of adam_step(ema_decay=...) for the
+        same params.  step: default global_step.  For weights updated by another optimizer (torch.optim on module())."""
+        self._refuse_in_ema("ema_update")
+        decay = check_ema_decay(decay)
+        mask = self.select_mask(variables)
+        plan = self._active if self._active is not None else self._any_plan()
+        ema = self._ensure_ema()
+        _lib.check(self._lib.wun_ema_update(plan.handle, ema.data_ptr(), self.params.data_ptr(), decay,
+                                            int(self.global_step if step is None else step),
+                                            _lib.WUN_OPTIM_EMA_WARMUP if warmup else 0, self._stream(), *self._mask_arg(mask)))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run get_output / separate_padded / validation ... on the EMA values: inside the block the library is handed the EMA
+        arena where it takes the parameters (the arenas are exchanged, nothing is copied; whatever a plan derives from the
+        weights -- the bf16 mode's packed images, the transposed copies -- is rebuilt from the arena it is handed by every
+        forward pass, so it follows).  The trained weights are back on exit, also after an exception.  Refused between a
+        training forward and the optimizer step that consumes its gradients (adam_step, or discard_gradients() for gradients
+        that were only inspected).  Inside the block the separator infers only: get_output(training=True), loss_and_gradients,
+        backward, adam_step and ema_update are refused, so no gradient of the EMA values can reach the trained weights.  The
+        autograd module (module()) holds the trained arena itself, so its forward is refused inside the block too."""
+        if self.ema is None:
+            raise RuntimeError("this separator has no EMA of its weights (adam_step(ema_decay=...) / ema_update create one)")
+        if self._step_phase:
+            raise RuntimeError("ema_weights() between a training forward pass and its adam_step: %s (adam_step applies, "
+                               "discard_gradients() abandons them)" %
+                               ("gradients are pending" if self._step_phase == 2 else "a training forward is open"))
+        self._refuse_in_ema("ema_weights")
+        self.params, self.ema = self.ema, self.params
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self.params, self.ema = self.ema, self.params
+            self._in_ema = False
+
+    def _refuse_in_ema(self, what):
+        if self._in_ema:
+            raise RuntimeError("%s inside ema_weights(): params and ema are exchanged there, the block is for inference" % what)
+
+    def discard_gradients(self):
+        """Abandon an open training forward / pending gradients (computed to read grad_norm, to inspect, ...) without an
+        optimizer step: self.grads keeps its floats, but loss_and_gradients / backward need a new get_output(training=True),
+        and ema_weights() may be entered again."""
+        self._step_phase, self._last_training = 0, False
+
+    def decay_mask(self, decay_variables):
+        """decay_variables of adam_step -> wun_optim_step's decay_select: None = every conv kernel (tensors of rank > 1) and no
+        bias; else the named variables (validated like variables=)."""
+        if decay_variables is None:
+            plan = self._active if self._active is not None else self._any_plan()
+            return np.array([1 if len(shp) > 1 else 0 for _, _, shp in plan.tensors], dtype=np.uint8)
+        return self.select_mask(decay_variables)
+
     def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, variables=None, clip_norm=None,
-                  skip_nonfinite=False):
+                  skip_nonfinite=False, weight_decay=0.0, decay_variables=None, ema_decay=None, ema_warmup=False):
         """tf.train.AdamOptimizer(learning_rate=lr) update (Training.py:77) + global_step += 1.  variables: TF variable names
         to update, as minimize(loss, var_list=...) does (None = all); params, m and v of every other tensor stay as they are
         (wun_adam_step_select).
@@ -542,8 +651,26 @@ class UnetAudioSeparator(object):
         clip_norm: tf.clip_by_global_norm(grads, clip_norm) first, the global norm taken over the updated variables' gradients
         (times grad_scale).  skip_nonfinite: when that norm is not finite, params, m and v are left as they are and
         skipped_steps grows by one (global_step still advances, as TF's does per sess.run).  With either set the update is
-        wun_adam_step_clip and the global norm is returned (0-dim GPU tensor, no host sync); otherwise None."""
+        wun_adam_step_clip and the global norm is returned (0-dim GPU tensor, no host sync); otherwise None.
+
+        weight_decay: torch.optim.AdamW's decoupled decay, theta *= 1 - lr * weight_decay before the Adam step, on
+        decay_variables (None = every conv kernel -- tensors of rank > 1 -- and no bias) among the updated variables.
+        ema_decay: self.ema -= (1 - d_t) (self.ema - new theta) in the same pass (tf.train.ExponentialMovingAverage; the EMA
+        arena starts as a copy of params); ema_warmup: d_t = min(ema_decay, (1 + step) / (10 + step)).  A skipped step
+        leaves the EMA alone too.  With any of the four set the update is wun_optim_step; params, m and v
+        are bit-equal to the calls above when weight_decay is 0.  With all four at their defaults: exactly the calls above."""
+        self._refuse_in_ema("adam_step")
+        norm = self._adam_step(lr, beta1, beta2, eps, grad_scale, variables, clip_norm, skip_nonfinite, weight_decay,
+                               decay_variables, ema_decay, ema_warmup)
+        self._step_phase = 0                    # (only once the update was accepted: a refused call leaves the gradients pending)
+        return norm
+
+    def _adam_step(self, lr, beta1, beta2, eps, grad_scale, variables, clip_norm, skip_nonfinite, weight_decay, decay_variables,
+                   ema_decay, ema_warmup):
         mask = self.select_mask(variables)
+        if weight_decay or decay_variables is not None or ema_decay is not None or ema_warmup:
+            return self._optim_step(lr, beta1, beta2, eps, grad_scale, mask, clip_norm, skip_nonfinite, weight_decay,
+                                    decay_variables, ema_decay, ema_warmup)
         if clip_norm is not None or skip_nonfinite:
             clip = check_clip_norm(clip_norm)
             ws, skipped = self._norm_buffers()
@@ -565,6 +692,31 @@ class UnetAudioSeparator(object):
             self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
             self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
             grad_scale, self._stream(), *self._mask_arg(mask)))
+
+    def _optim_step(self, lr, beta1, beta2, eps, grad_scale, mask, clip_norm, skip_nonfinite, weight_decay, decay_variables,
+                    ema_decay, ema_warmup):
+        """adam_step's extended form: one wun_optim_step call."""
+        wd = check_weight_decay(weight_decay)
+        if ema_warmup and ema_decay is None:
+            raise ValueError("ema_warmup needs ema_decay")
+        dmask = self.decay_mask(decay_variables)
+        ema = None
+        if ema_decay is not None:
+            ema_decay = check_ema_decay(ema_decay)
+            ema = self._ensure_ema()
+        need_norm = clip_norm is not None or skip_nonfinite
+        ws, skipped = self._norm_buffers() if need_norm else (None, None)
+        cfg = _lib.WunOptimConfig(beta1, beta2, eps, wd, ema_decay if ema_decay is not None else 0.0,
+                                  check_clip_norm(clip_norm),
+                                  (_lib.WUN_CLIP_SKIP_NONFINITE if skip_nonfinite else 0) |
+                                  (_lib.WUN_OPTIM_EMA_WARMUP if ema_warmup else 0))
+        self.global_step += 1
+        _lib.check(self._lib.wun_optim_step(
+            self._active.handle, self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(),
+            self.adam_v.data_ptr(), ema.data_ptr() if ema is not None else None, self.global_step, lr, grad_scale,
+            C.byref(cfg), ws.data_ptr() if ws is not None else None, skipped.data_ptr() if skipped is not None else None,
+            self._stream(), *self._mask_arg(mask), *self._mask_arg(dmask)))
+        return ws[len(self._active.tensors)].clone() if need_norm else None
 
     def _norm_buffers(self):
         """(norm workspace, int64 skip counter) of wun_grad_norm / wun_adam_step_clip, allocated on first use."""

@@ -11,6 +11,7 @@ by model_config["data_producer"] = "fused" and model_config["augment"] (validati
 -- and `synthetic_source` for the benchmark.
 """
 import json
+import math
 import os
 import time
 
@@ -20,7 +21,7 @@ import torch.distributed as dist
 
 from .parallel import GradAllReducer, OverlappedGradAllReducer, broadcast_parameters, init_distributed
 from .checkpoint import load_checkpoint, save_checkpoint
-from .separator import UnetAudioSeparator, check_clip_norm
+from .separator import UnetAudioSeparator, check_clip_norm, check_ema_decay, check_weight_decay
 from .spectral import SpectralLoss
 from .waveform import CombinedLoss, WaveformLoss, TERMS as WAVEFORM_TERMS
 
@@ -76,10 +77,23 @@ class Trainer(object):
     [total, mse, l1, si_sdr, snr, SI-SDR dB per source, SNR dB per source] of the step (the mean over the micro-batches),
     waveform_parts() the weighted terms, train.jsonl a `waveform_terms` entry; last_losses, loss_parts() and term_parts() keep
     their spectral layout and meaning whenever a spectral loss is set.  Validation and early stopping stay the reference's MSE
-    unless model_config["validation_metric"] says "si_sdr" (validation.test)."""
+    unless model_config["validation_metric"] says "si_sdr" (validation.test).
+
+    optimizer (or model_config["optimizer"], default None): {"weight_decay": w, "decay_variables": [...] | None, "ema_decay": d,
+    "ema_warmup": bool, "eval_with_ema": bool}, any subset -- decoupled weight decay (torch.optim.AdamW; None = every conv
+    kernel, no bias), an EMA of the weights (sep.ema, tf.train.ExponentialMovingAverage; saved in the checkpoints) and
+    validation on the EMA values, all in the one update kernel that clips and steps (wun_optim_step).
+    lr_schedule (or model_config["lr_schedule"], default None): {"warmup_steps": n, "kind": "constant" | "cosine" | "step" |
+    "exponential", "total_steps", "min_factor", "step_size", "gamma"}: each update's lr is float32(init_sup_sep_lr *
+    lr_factor(schedule, sep.global_step)); last_lr holds it, train.jsonl gains `lr`.  Unknown keys and inconsistent values raise
+    ValueError here.  Both None: exactly the old calls."""
 
     def __init__(self, model_config, batch_size=None, device=None, seed=1337, bucket_mib=16.0, grad_accum_steps=None,
-                 clip_grad_norm=None, skip_nonfinite=None, spectral_loss=None, waveform_loss=None):
+                 clip_grad_norm=None, skip_nonfinite=None, spectral_loss=None, waveform_loss=None, optimizer=None,
+                 lr_schedule=None):
+        # (checked before anything touches the device: unknown keys and inconsistent values raise ValueError here)
+        self.optimizer = optimizer_settings(optimizer if optimizer is not None else model_config.get("optimizer"))
+        self.lr_schedule = schedule_settings(lr_schedule if lr_schedule is not None else model_config.get("lr_schedule"))
         self.rank, self.local_rank, self.world = init_distributed()
         # Scheduling hint of the plan (include/wun.h): low-priority side streams only when no collective shares the
         # device -- with a process group initialised (multi-GPU, or bench.py --force-allreduce) they must stay normal.
@@ -125,6 +139,11 @@ class Trainer(object):
         else:
             self.reducer = GradAllReducer(plan.tensors, plan.info.arena_floats, bucket_mib)
         self.lr = model_config["init_sup_sep_lr"]
+        self.last_lr = self.lr                 # the lr of the last optimizer step (the schedule's value when one is set)
+        if self.optimizer is not None:
+            self.sep.decay_mask(self.optimizer["decay_variables"])        # KeyError: not a variable of this separator
+            if self.optimizer["ema_decay"] is not None:
+                self.sep._ensure_ema()
 
     def tune(self, mix, targets, pinned_table=None):
         """One-off kernel autotuning on a real batch (skipped with WUN_NO_TUNE=1).  Rank 0 decides
@@ -210,12 +229,25 @@ class Trainer(object):
     def clipping(self):
         return self.clip_norm is not None or self.skip_nonfinite
 
+    @property
+    def logs_lr(self):
+        """train.jsonl carries `lr` when a schedule or an optimizer dict is set, and only then."""
+        return self.optimizer is not None or self.lr_schedule is not None
+
     def _adam(self, grad_scale):
+        lr = self.lr
+        if self.lr_schedule is not None:
+            # keyed on the separator's global_step: carries across train() epochs and resumes from a checkpoint
+            lr = scheduled_lr(self.lr, self.lr_schedule, self.sep.global_step)
+        self.last_lr = lr
+        kw = {}
+        if self.optimizer is not None:
+            kw = {k: self.optimizer[k] for k in ("weight_decay", "decay_variables", "ema_decay", "ema_warmup")}
         if self.clipping:
-            self.grad_norm = self.sep.adam_step(self.lr, grad_scale=grad_scale, clip_norm=self.clip_norm,
-                                                skip_nonfinite=self.skip_nonfinite)
+            self.grad_norm = self.sep.adam_step(lr, grad_scale=grad_scale, clip_norm=self.clip_norm,
+                                                skip_nonfinite=self.skip_nonfinite, **kw)
         else:
-            self.sep.adam_step(self.lr, grad_scale=grad_scale)
+            self.sep.adam_step(lr, grad_scale=grad_scale, **kw)
 
     def _accumulated_step(self, mix, targets):
         """k micro-batches, one optimizer step.  Only the last backward pass records the bucket events: an event then means
@@ -284,7 +316,7 @@ class SpectrogramTrainer(object):
             raise NotImplementedError("unet_spectrogram with raw_audio_loss=True: the spectrogram U-Net's audio output is built "
                                       "for inference only; train with raw_audio_loss=False (cfg.unet_spectrogram_l1)")
         for key, off in (("spectral_loss", None), ("waveform_loss", None), ("clip_grad_norm", None), ("grad_accum_steps", 1),
-                         ("skip_nonfinite_steps", False)):
+                         ("skip_nonfinite_steps", False), ("optimizer", None), ("lr_schedule", None)):
             if model_config.get(key, off) not in (off, None):
                 raise NotImplementedError("unet_spectrogram: %s is not built for this network (its objective is the magnitude "
                                           "L1 of Training.py:55-63, one batch per step)" % key)
@@ -314,6 +346,130 @@ class SpectrogramTrainer(object):
         return loss
 
 
+OPTIMIZER_KEYS = ("weight_decay", "decay_variables", "ema_decay", "ema_warmup", "eval_with_ema")
+SCHEDULE_KEYS = ("warmup_steps", "kind", "total_steps", "min_factor", "step_size", "gamma")
+SCHEDULE_KINDS = ("constant", "cosine", "step", "exponential")
+
+
+def optimizer_settings(optimizer):
+    """model_config["optimizer"] / Trainer(optimizer=...) -> a checked copy with every key present, or None for None: the
+    keyword arguments of UnetAudioSeparator.adam_step plus eval_with_ema (validation.test).  ValueError for an unknown key or
+    an inconsistent value."""
+    if optimizer is None:
+        return None
+    if not isinstance(optimizer, dict):
+        raise ValueError("optimizer must be a dict or None, got %r" % (optimizer,))
+    unknown = sorted(set(optimizer) - set(OPTIMIZER_KEYS))
+    if unknown:
+        raise ValueError("optimizer: unknown keys %s (known: %s)" % (unknown, list(OPTIMIZER_KEYS)))
+    out = {"weight_decay": check_weight_decay(optimizer.get("weight_decay", 0.0)),
+           "decay_variables": optimizer.get("decay_variables"),
+           "ema_decay": optimizer.get("ema_decay"),
+           "ema_warmup": optimizer.get("ema_warmup", False),
+           "eval_with_ema": optimizer.get("eval_with_ema", False)}
+    if out["ema_decay"] is not None:
+        out["ema_decay"] = check_ema_decay(out["ema_decay"])
+    for key in ("ema_warmup", "eval_with_ema"):
+        if not isinstance(out[key], bool):
+            raise ValueError("optimizer: %s = %r must be a bool" % (key, out[key]))
+        if out[key] and out["ema_decay"] is None:
+            raise ValueError("optimizer: %s needs ema_decay" % key)
+    dv = out["decay_variables"]
+    if dv is not None:
+        if isinstance(dv, str) or not all(isinstance(n, str) for n in dv):
+            raise ValueError("optimizer: decay_variables = %r must be a list of variable names or None" % (dv,))
+        out["decay_variables"] = list(dv)
+    return out
+
+
+def schedule_settings(schedule):
+    """model_config["lr_schedule"] -> a checked copy with every key present, or None for None (constant lr).  ValueError for
+    an unknown key or an inconsistent value."""
+    if schedule is None:
+        return None
+    if not isinstance(schedule, dict):
+        raise ValueError("lr_schedule must be a dict or None, got %r" % (schedule,))
+    unknown = sorted(set(schedule) - set(SCHEDULE_KEYS))
+    if unknown:
+        raise ValueError("lr_schedule: unknown keys %s (known: %s)" % (unknown, list(SCHEDULE_KEYS)))
+    s = {"warmup_steps": schedule.get("warmup_steps", 0), "kind": schedule.get("kind", "constant"),
+         "total_steps": schedule.get("total_steps"), "min_factor": schedule.get("min_factor", 0.0),
+         "step_size": schedule.get("step_size"), "gamma": schedule.get("gamma")}
+    if s["kind"] not in SCHEDULE_KINDS:
+        raise ValueError("lr_schedule: kind = %r, expected one of %s" % (s["kind"], list(SCHEDULE_KINDS)))
+
+    def integer(key, least):
+        v = s[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+            raise ValueError("lr_schedule: %s = %r must be an integer >= %d" % (key, v, least))
+        s[key] = int(v)
+
+    def number(key, lo, hi, lo_open):
+        v = s[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (lo <= v <= hi) or (lo_open and v == lo):
+            raise ValueError("lr_schedule: %s = %r must be a number in %s%g, %g]" % (key, v, "(" if lo_open else "[", lo, hi))
+        s[key] = float(v)
+
+    integer("warmup_steps", 0)
+    needs = {"constant": (), "cosine": ("total_steps",), "step": ("step_size", "gamma"), "exponential": ("gamma",)}[s["kind"]]
+    for key in ("total_steps", "step_size", "gamma"):
+        if key not in needs and s[key] is not None:
+            raise ValueError("lr_schedule: %s does not apply to kind %r" % (key, s["kind"]))
+        if key in needs and s[key] is None:
+            raise ValueError("lr_schedule: kind %r needs %s" % (s["kind"], key))
+    if s["min_factor"] is None:
+        s["min_factor"] = 0.0
+    number("min_factor", 0.0, 1.0, False)
+    if s["kind"] != "cosine" and s["min_factor"] != 0.0:           # (0: what a checked copy carries, so checking one again passes)
+        raise ValueError("lr_schedule: min_factor does not apply to kind %r" % (s["kind"],))
+    if s["kind"] == "cosine":
+        integer("total_steps", 1)
+        if s["total_steps"] <= s["warmup_steps"]:
+            raise ValueError("lr_schedule: total_steps = %d must exceed warmup_steps = %d" % (s["total_steps"], s["warmup_steps"]))
+    if s["kind"] == "step":
+        integer("step_size", 1)
+    if s["kind"] in ("step", "exponential"):
+        number("gamma", 0.0, 1.0, True)
+    return s
+
+
+def lr_factor(schedule, global_step):
+    """The factor on init_sup_sep_lr of the optimizer step taken at `global_step` (the separator's count BEFORE the step: 0 for
+    the first one), in float64; a pure function of its arguments.  schedule: model_config["lr_schedule"] (None = 1).
+      warm-up      steps 0 .. warmup_steps - 1: (step + 1) / warmup_steps, linear from 1 / warmup_steps to 1; it multiplies
+                   nothing else: the kind starts at t = step - warmup_steps = 0 with factor 1
+      constant     1
+      cosine       min_factor + (1 - min_factor) (1 + cos(pi t / T)) / 2, T = total_steps - warmup_steps; min_factor from
+                   step total_steps on
+      step         gamma ** (t // step_size)
+      exponential  gamma ** t"""
+    s = schedule_settings(schedule)
+    if s is None:
+        return 1.0
+    step = int(global_step)
+    if step < 0:
+        raise ValueError("global_step = %r must be >= 0" % (global_step,))
+    w = s["warmup_steps"]
+    if step < w:
+        return (step + 1.0) / w
+    t = step - w
+    if s["kind"] == "cosine":
+        T = s["total_steps"] - w
+        if t >= T:
+            return s["min_factor"]
+        return s["min_factor"] + (1.0 - s["min_factor"]) * 0.5 * (1.0 + math.cos(math.pi * t / T))
+    if s["kind"] == "step":
+        return s["gamma"] ** (t // s["step_size"])
+    if s["kind"] == "exponential":
+        return s["gamma"] ** t
+    return 1.0
+
+
+def scheduled_lr(base_lr, schedule, global_step):
+    """The lr of the step taken at global_step: float32(base_lr * lr_factor), the product in float64, as a Python float."""
+    return float(np.float32(float(base_lr) * lr_factor(schedule, global_step)))
+
+
 def clip_settings(model_config, clip_grad_norm=None, skip_nonfinite=None):
     """(clip_norm or None, skip_nonfinite) of a Trainer: the arguments, else model_config["clip_grad_norm"] /
     ["skip_nonfinite_steps"].  ValueError for a clip_grad_norm that is not > 0 (NaN included)."""
@@ -341,10 +497,19 @@ def train(model_config, experiment_id, load_model=None, batch_source=None, log_e
         # hands save_path to every rank, but the file system need not be shared); parameters, both
         # Adam slots and global_step are then broadcast so every replica resumes the SAME state
         # (`.npz` of this package, or a TensorFlow V2 checkpoint prefix as the reference's Saver writes: checkpoint.py)
+        # Whether an EMA is kept is the CONFIGURATION's word (the Trainer made the arena on every rank when it is), never the
+        # file's: every rank then issues the same broadcasts.  A checkpoint's EMA that this run would not update is dropped,
+        # with a warning, instead of being carried along stale into the next checkpoint.
+        keeps_ema = bool(getattr(tr, "optimizer", None)) and tr.optimizer["ema_decay"] is not None
         if tr.rank == 0:
             load_checkpoint(tr.sep, load_model)
+            if not keeps_ema and getattr(tr.sep, "ema", None) is not None:
+                import warnings
+                warnings.warn("wun: %s carries an EMA of the weights, but this run keeps none (no optimizer['ema_decay']): the "
+                              "EMA is dropped and the checkpoints of this run will not contain one" % load_model, RuntimeWarning)
+                tr.sep.ema = None
         if tr.world > 1:
-            for t in (tr.sep.params, tr.sep.adam_m, tr.sep.adam_v):
+            for t in (tr.sep.params, tr.sep.adam_m, tr.sep.adam_v) + ((tr.sep.ema,) if keeps_ema else ()):
                 broadcast_parameters(t)
             box = [tr.sep.global_step]
             dist.broadcast_object_list(box, src=0)
@@ -374,6 +539,8 @@ def train(model_config, experiment_id, load_model=None, batch_source=None, log_e
             if tr.clipping:
                 line["grad_norm"] = float(tr.grad_norm.item())
                 line["skipped_steps"] = tr.sep.skipped_steps
+            if getattr(tr, "logs_lr", False):
+                line["lr"] = tr.last_lr
             log.write(json.dumps(line) + "\n")
             log.flush()
     torch.cuda.synchronize()

@@ -19,6 +19,7 @@ producer only; datasets.speed_descriptors) adds the source-level augmentations t
 "time_stretch": p (with "pitch_shift_rates", "time_stretch_rates", "vocoder_fft"; datasets.vocoder_descriptors)
 add the phase vocoder's two.
 """
+import contextlib
 import json
 import os
 
@@ -72,6 +73,23 @@ def _batches(model_config, producer, sep, in_shape, out_shape, partition, tracks
     return gen()
 
 
+def eval_with_ema(model_config):
+    """model_config["optimizer"]["eval_with_ema"] (default False), the optimizer dict checked as the Trainer checks it."""
+    from .training import optimizer_settings
+    opt = optimizer_settings(model_config.get("optimizer"))
+    return bool(opt and opt["eval_with_ema"])
+
+
+def _eval_weights(model_config, sep):
+    """The context test() scores under: sep.ema_weights() with eval_with_ema, else nothing.  RuntimeError when the separator
+    (the checkpoint it was loaded from) has no EMA."""
+    if not eval_with_ema(model_config):
+        return contextlib.nullcontext()
+    if getattr(sep, "ema", None) is None:
+        raise RuntimeError("optimizer['eval_with_ema'] is set but the separator / its checkpoint has no EMA of the weights")
+    return sep.ema_weights()
+
+
 def test(model_config, partition, model_folder, load_model, tracks=None, data_root=None, separator=None,
          return_sums=False, resample=False):
     """Test.test(model_config, partition, model_folder, load_model) -> mean MSE.  The partition's
@@ -83,7 +101,10 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     model_config["waveform_loss"], grad=False); the same running mean, and test.jsonl gains "metric" and the per-source dB.
     ValueError for any other value but "mse".
     model_config["data_producer"] = "fused": the batches come from a datasets.FusedSnippetSource(partition=...) on the separator's
-    device (the tracks are uploaded once per call) instead of the host pipeline; the same batches, the same loss."""
+    device (the tracks are uploaded once per call) instead of the host pipeline; the same batches, the same loss.
+    model_config["optimizer"]["eval_with_ema"]: the loss is that of the EMA weights (the checkpoint's ema/ entries, or the
+    given separator's EMA; separator.ema_weights()) -- what optimise()'s early stopping then compares.  RuntimeError when
+    there is no EMA."""
     metric = waveform.validation_metric(model_config)
     producer = data_producer(model_config)
     if model_config["network"] not in ("unet", "unet_spectrogram"):
@@ -107,31 +128,32 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
     names = list(model_config["source_names"])
     si_loss = waveform.validation_loss(model_config) if metric == "si_sdr" else None
     source_db = np.zeros(len(names))                                              # running means of the per-source dB
-    for batch in _batches(model_config, producer, sep, in_shape, out_shape, partition, tracks):
-        outs = sep.get_output(batch["mix"], False, spec_l1)                       # Test.py:34
-        if si_loss is not None:
-            est = torch.stack([outs[key] for key in names])
-            real = torch.stack([torch.as_tensor(batch[key], device=est.device) for key in names])
-            losses, _ = si_loss.loss_and_grad(est, real, grad=False)
-            curr = float(losses[0].item())                                        # -(mean SI-SDR in dB)
-            source_db += (1.0 / float(batch_num)) * (si_loss.source_metrics(losses)["si_sdr"].cpu().numpy() - source_db)
-        elif spec_l1:                                                             # Test.py:63-68
-            loss = 0.0
-            for key in names:
-                real = torch.as_tensor(batch[key], dtype=torch.float32, device=outs[key].device)      # [B, T, 1]
-                real_mag = spectral.stft_magnitude(real[None], sep.frame_len, sep.hop)[0, :, 0]       # [B, F, K]
-                loss = loss + torch.mean(torch.abs(real_mag - outs[key]))
-            curr = float(loss.item()) / float(model_config["num_sources"])
-        else:
-            loss = 0.0
-            for key in names:                                                     # Test.py:61-74
-                real = torch.as_tensor(batch[key], device=outs[key].device)
-                loss = loss + torch.mean((real - outs[key]) ** 2)
-            curr = float(loss.item()) / float(model_config["num_sources"])
-        total_loss = total_loss + (1.0 / float(batch_num)) * (curr - total_loss)  # Test.py:80
-        loss_sum += curr
-        batch_num += 1
-    if return_sums:                                                               # a shard of the partition (_sharded_test)
+    with _eval_weights(model_config, sep):
+        for batch in _batches(model_config, producer, sep, in_shape, out_shape, partition, tracks):
+            outs = sep.get_output(batch["mix"], False, spec_l1)                       # Test.py:34
+            if si_loss is not None:
+                est = torch.stack([outs[key] for key in names])
+                real = torch.stack([torch.as_tensor(batch[key], device=est.device) for key in names])
+                losses, _ = si_loss.loss_and_grad(est, real, grad=False)
+                curr = float(losses[0].item())                                        # -(mean SI-SDR in dB)
+                source_db += (1.0 / float(batch_num)) * (si_loss.source_metrics(losses)["si_sdr"].cpu().numpy() - source_db)
+            elif spec_l1:                                                             # Test.py:63-68
+                loss = 0.0
+                for key in names:
+                    real = torch.as_tensor(batch[key], dtype=torch.float32, device=outs[key].device)      # [B, T, 1]
+                    real_mag = spectral.stft_magnitude(real[None], sep.frame_len, sep.hop)[0, :, 0]       # [B, F, K]
+                    loss = loss + torch.mean(torch.abs(real_mag - outs[key]))
+                curr = float(loss.item()) / float(model_config["num_sources"])
+            else:
+                loss = 0.0
+                for key in names:                                                     # Test.py:61-74
+                    real = torch.as_tensor(batch[key], device=outs[key].device)
+                    loss = loss + torch.mean((real - outs[key]) ** 2)
+                curr = float(loss.item()) / float(model_config["num_sources"])
+            total_loss = total_loss + (1.0 / float(batch_num)) * (curr - total_loss)  # Test.py:80
+            loss_sum += curr
+            batch_num += 1
+    if return_sums:                                                              # a shard of the partition (_sharded_test)
         return loss_sum, batch_num - 1
 
     log_dir = os.path.join(model_config["log_dir"], str(model_folder))            # Test.py:41,86-87
@@ -196,6 +218,11 @@ def _load_on_rank0_and_broadcast(model_config, load_model, make_separator=None):
     dist.broadcast_object_list(box, src=0)
     if box[0] is None:
         broadcast_parameters(sep.params)
+        if eval_with_ema(model_config):
+            has = [getattr(sep, "ema", None) is not None]
+            dist.broadcast_object_list(has, src=0)
+            if has[0]:                               # (absent: test() raises the same error on every rank)
+                broadcast_parameters(sep._ensure_ema())
     return sep, box[0]
 
 
