@@ -482,6 +482,70 @@ int wun_bss_window_energies(const float* refs, const float* ests, int32_t S, int
                             const double* c_all, const double* c_own, const int64_t* starts, const int64_t* lengths,
                             int64_t nwin, double* energies, double* scratch, void* stream);
 
+/* ---- recursive filtering along time and the BS.1770-4 loudness meter -----------
+ * Audio is device float32 [n, C] interleaved, C in {1, 2}, any 4-byte alignment; arithmetic is float64.  Every buffer is
+ * the caller's; nothing allocates or synchronises, no atomics, every sum has one order fixed by the sizes, and every
+ * argument check runs before any GPU work.  All entries: WUN_ERR_INVALID for a null pointer, n < 1, C not 1 or 2, a
+ * scratch / float64 pointer off 8 bytes; WUN_ERR_UNSUPPORTED above 2^40 frames.
+ *
+ * The parallel schedule of a recurrence is part of its definition here (the bits do not depend on the grid, the stream or
+ * where buffers lie): time is cut into chunks of wun_sos_chunk() frames.  (1) every chunk runs the cascade with the true
+ * input history and ZERO recursive state and keeps its end state; (2) a carry pass turns the end states into every chunk's
+ * true start state, v[k+1] = M v[k] + e[k], with M the 2 nsec x 2 nsec zero-input transition of a whole chunk (formed on
+ * the host in float64 by repeated squaring) -- in two levels: the wun_sos_tile() chunks of a group are walked from zero, the
+ * group ends are walked with M^tile, the groups are walked again from their true starts; a step computes row r as
+ * acc = e[r], acc = fma(M[r][q], v[q], acc) for q ascending; (3) every chunk runs again from its true state and writes.  The state of section s is (y_s[t-1], y_s[t-2]).  A short last chunk needs no power of
+ * its own: its end state has no reader. */
+int32_t wun_sos_chunk(void);                      /* frames per chunk (256) */
+int32_t wun_sos_tile(void);                       /* chunks per workgroup and per carry group (64) */
+
+/* float64 elements of `scratch` for wun_sosfilt: 2 nsec C (chunks + groups).  Negative wun_status for bad arguments. */
+int64_t wun_sosfilt_scratch_doubles(int64_t n, int32_t C, int32_t nsec);
+
+/* y = sosfilt(sos, x) per channel from zero initial state (scipy.signal.sosfilt): sos is HOST float64 [nsec][6] =
+ * b0 b1 b2 a0 a1 a2 with a0 == 1, 1 <= nsec <= 8.  Per section, direct form I,
+ *   y[t] = b0 x[t] + b1 x[t-1] + b2 x[t-2] - a1 y[t-1] - a2 y[t-2]
+ * in float64 (the five products added in that order by FMA), the last section's output rounded once to float32.
+ * WUN_ERR_INVALID also for nsec outside 1..8, a coefficient that is not finite, a0 != 1, or x and y overlapping. */
+int wun_sosfilt(const float* x, int64_t n, int32_t C, const double* sos, int32_t nsec, float* y, double* scratch,
+                void* stream);
+
+/* Host: the K-weighting of ITU-R BS.1770-4 at sample rate sr as two sections sos[2][6] (the high shelf, then the
+ * high-pass with b = 1, -2, 1), from the analogue prototype by the bilinear transform -- at 48000 Hz the standard's
+ * table.  WUN_ERR_INVALID for sr outside 4000..384000. */
+int wun_kweight_design(int32_t sr, double* sos);
+
+/* Host: complete gating blocks of n frames at sr: Nb = round(0.4 sr) frames at a step of round(0.1 sr) (halves up);
+ * (n - Nb) / step + 1 for n >= Nb, else 0.  Negative wun_status for n < 1 or sr outside 4000..384000. */
+int64_t wun_loudness_blocks(int64_t n, int32_t sr);
+
+/* float64 elements of `scratch` for wun_loudness.  Negative wun_status for bad arguments. */
+int64_t wun_loudness_scratch_doubles(int64_t n, int32_t C, int32_t sr);
+
+/* Integrated loudness of x (BS.1770-4 / EBU R 128, every channel weighted 1), all of it on the device:
+ *   the signal is K-weighted by the schedule above; its third pass accumulates squares, the filtered signal is never written
+ *   z_j = sum_c (sum_t y_c[t]^2) / Nb over block j (channels ascending; within a channel ascending time, in pieces cut at
+ *         chunk and block boundaries);  l_j = -0.691 + 10 log10 z_j
+ *   absolute gate l_j > -70;  relative gate l_j > (-0.691 + 10 log10 mean of the absolute-gated z) - 10
+ *   L = -0.691 + 10 log10 mean of z over the blocks passing both (means: 256 strided partial sums, then a fixed tree)
+ *   meter  : device float64 [4]: L (-inf when no block passes, NaN when a block is NaN), blocks kept, blocks nb, max |x|
+ *            (NaN when x holds one)
+ *   blocks : device float64 [nb] momentary values l_j, or NULL
+ * WUN_ERR_INVALID also for sr outside 4000..384000. */
+int wun_loudness(const float* x, int64_t n, int32_t C, int32_t sr, double* meter, double* blocks, double* scratch,
+                 void* stream);
+
+/* gain[0] = (float) g and gain[1] = (float)(1.0 / (double) gain[0]), device float32 [2], from a meter of wun_loudness:
+ * in float64 g = 10^((target_lufs - L) / 20), capped at 10^(max_gain_db / 20) and, when peak_limit > 0, at
+ * peak_limit / peak; a non-finite L gives exactly 1.  WUN_ERR_INVALID for a target that is not finite, max_gain_db < 0
+ * or peak_limit < 0 (0: no limit). */
+int wun_loudness_gain(const double* meter, double target_lufs, double max_gain_db, double peak_limit, float* gain,
+                      void* stream);
+
+/* x[i] *= *gain for i < count, in place, one fp32 rounding; the factor is read on the device.  WUN_ERR_INVALID for
+ * count < 1. */
+int wun_scale_by(float* x, int64_t count, const float* gain, void* stream);
+
 /* ---- spectral training loss: STFT-magnitude L1 and its waveform gradient ----
  * The reference's other objective (Training.py:55-60): the L1 distance between STFT magnitudes, frame 1024, hop 768,
  * periodic Hann window, no padding -- here for up to 8 resolutions at once, next to the time-domain MSE.

@@ -8,7 +8,7 @@
 R=$(cd $(dirname $0)/.. && pwd)
 T=$(mktemp -d)
 rc=0
-for u in wun_narrow wun_bf16 wun_wgrad_bf16 wun_elementwise wun_resample wun_bsseval wun_spectral wun_waveform wun_postfilter wun_fft wun_conv2d wun_conv2d_train wun_track wun_dataset wun_vocoder; do
+for u in wun_narrow wun_bf16 wun_wgrad_bf16 wun_elementwise wun_resample wun_bsseval wun_spectral wun_waveform wun_postfilter wun_fft wun_conv2d wun_conv2d_train wun_track wun_dataset wun_vocoder wun_loudness; do
     o=$R/wave-u-net_amd/csrc/$u.o
     [ -f $o ] || { echo "$u.o: not built"; rc=1; continue; }
     # the device code object is a fat binary embedded in the host object's .hip_fatbin section

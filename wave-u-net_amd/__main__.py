@@ -31,6 +31,10 @@ phase; the refined audio is normalised by the window-square sum over the coverin
 `overlap=0.25 shifts=4` (predict, evaluate; or model_config.separation={"overlap":0.25,"shifts":4}) lets neighbouring hops share a
 quarter of a hop, cross-faded, and averages 4 passes whose hop grids are shifted by 0 .. max_shift frames (max_shift=<frames>,
 default expected_sr // 2; shifts=[0,3,700] names the offsets): about shifts / (1 - overlap) times the forward passes.
+`loudness=-23` (predict, evaluate; or `loudness={"target":-23,"max_gain_db":30,"peak_limit":0.99,"restore":True}`, or
+model_config.loudness=...) meters the mix at the model's rate (BS.1770-4 integrated loudness, on the GPU), scales it to that
+many LUFS before the network and scales the estimates back; `model_config.loudness={"target":-23,"data":True}` makes `train` and
+`test` scale every track's mix and stems by the gain of its mix when the tracks are loaded.
 `train` takes the spectral objective as `model_config.spectral_loss={"resolutions":[[4096,1024]],"transform":"fft","terms":{"sc":1,
 "log_mag_l1":1},"log_eps":4.0}`: `"transform":"fft"` lifts the loss's n_fft limit from 2048 to 8192 in the same way ("gemm" is the default).
 `train` and `test` take `model_config.data_producer=fused` to produce their batches with one HIP kernel out of tracks resident in
@@ -85,6 +89,15 @@ def _postfilter(opts, model_config):
         return from_config(opts.get("postfilter", model_config.get("postfilter")))
     except (ValueError, NotImplementedError, TypeError) as e:
         raise SystemExit("postfilter: %s" % e)
+
+
+def _loudness(opts, model_config):
+    """The loudness= option, else model_config["loudness"]: checked here, so that a bad spec ends the command at once."""
+    from wave_u_net_amd.loudness import from_config
+    try:
+        return from_config(opts.get("loudness", model_config.get("loudness")))
+    except (ValueError, TypeError) as e:
+        raise SystemExit("loudness: %s" % e)
 
 
 def _phase_iterations(opts):
@@ -147,7 +160,7 @@ def main(argv=None):
                                                     opts["estimates_path"], partition=opts.get("partition", "test"),
                                                     postfilter=_postfilter(opts, model_config),
                                                     phase_iterations=_phase_iterations(opts), weights=_weights(opts),
-                                                    **_separation(opts, model_config))
+                                                    loudness=_loudness(opts, model_config), **_separation(opts, model_config))
         for metric in ("SDR", "ISR", "SIR", "SAR"):
             stats = evaluate.compute_mean_metrics(folder, metric=metric)
             for src, (med, mad, mean, sd) in zip(model_config["source_names"], stats):
@@ -161,7 +174,7 @@ def main(argv=None):
         evaluate.produce_source_estimates(model_config, opts.get("model_path"), opts["input_path"], opts.get("output_path"),
                                           hop_frames=hop, postfilter=_postfilter(opts, model_config),
                                           phase_iterations=_phase_iterations(opts), weights=_weights(opts),
-                                          **_separation(opts, model_config))
+                                          loudness=_loudness(opts, model_config), **_separation(opts, model_config))
 
 
 if __name__ == "__main__":

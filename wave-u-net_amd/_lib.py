@@ -139,6 +139,16 @@ _SIGS = {
     "wun_bss_correlations": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "wun_bss_window_energies": (C.c_int, [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64), C.c_int64, _P, _P, _P]),
+    "wun_sos_chunk": (C.c_int32, []),
+    "wun_sos_tile": (C.c_int32, []),
+    "wun_sosfilt_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_sosfilt": (C.c_int, [_P, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_int32, _P, _P, _P]),
+    "wun_kweight_design": (C.c_int, [C.c_int32, C.POINTER(C.c_double)]),
+    "wun_loudness_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
+    "wun_loudness_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_loudness": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "wun_loudness_gain": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
+    "wun_scale_by": (C.c_int, [_P, C.c_int64, _P, _P]),
     "wun_stft_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "wun_stft_table_floats": (C.c_int64, [C.c_int32]),
     "wun_stft_design": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.c_int64]),

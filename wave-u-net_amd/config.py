@@ -65,6 +65,12 @@ EXTENSION_DEFAULTS = {
     # hops, one pass; else {"overlap": 0.25, "shifts": 4, "max_shift": 11025} (any subset): neighbouring hops share that
     # fraction of a hop and are cross-faded, and the hop grid is run at that many shifted offsets and averaged
     "separation": None,
+    # evaluate.separate_track (through the same callers) / loudness.from_config: None = the mix at the level it
+    # arrives; else a target in LUFS or {"target": -23.0, "max_gain_db": 30.0, "peak_limit": None, "restore": True,
+    # "data": False} (any subset): the resampled mix is metered (BS.1770-4 integrated loudness) and scaled to the target before
+    # the network, the estimates scaled back unless "restore" is False; "data": True makes train / test scale every track's mix
+    # and stems by the gain of its mix at load (datasets.normalize_tracks)
+    "loudness": None,
     # spectrogram.UnetSpectrogramSeparator: the STFT framing of the spectrogram U-Net (UnetSpectrogramSeparator.py:28-29 fixes
     # 1024 / 768); other values exist so that tests can run small geometries
     "spec_frame_len": 1024,

@@ -125,6 +125,37 @@ def load_partition(root, partition, model_config, resample=False):
             for d in sorted(os.listdir(base)) if os.path.isdir(os.path.join(base, d))]
 
 
+def normalize_tracks(tracks, model_config, device, spec):
+    """Loudness-normalised training data: every track's MIX is metered once on `device` at expected_sr
+    (loudness.integrated, BS.1770-4), the gain to spec's target is computed there (loudness.gain) and read back -- the one host
+    synchronisation per track, at load time -- and that one float32 factor multiplies the mix and every stem (one fp32 product
+    per sample, so the stems still sum to the mix as before up to that rounding).  spec: what loudness.from_config takes.
+    Returns (new track dicts, float32 gains [len(tracks)]); the given tracks are left as they are.  GPU only."""
+    import torch
+    from . import loudness as ld
+    spec = ld.from_config(spec)
+    if spec is None:
+        raise ValueError("normalize_tracks needs a loudness spec, got None")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("normalize_tracks meters on a GPU; there is no CPU fallback (got device %s)" % device)
+    sr = int(model_config["expected_sr"])
+    out, gains = [], np.zeros(len(tracks), np.float32)
+    for i, track in enumerate(tracks):
+        mix = torch.from_numpy(np.ascontiguousarray(track["mix"], np.float32)).to(device)
+        g = ld.gain(ld.integrated(mix, sr), spec["target"], spec["max_gain_db"], spec["peak_limit"])
+        gains[i] = g[0:1].cpu().numpy()[0]                                      # the one sync of this track
+        out.append({k: np.ascontiguousarray(np.asarray(v, np.float32) * gains[i]) for k, v in track.items()})
+    return out, gains
+
+
+def loudness_data_spec(model_config):
+    """model_config["loudness"] when it asks for normalised training data ("data": True), else None."""
+    from . import loudness as ld
+    spec = ld.from_config(model_config.get("loudness"))
+    return spec if spec is not None and spec["data"] else None
+
+
 def pad_track(track, pad_frames):
     """Zero padding at both ends (Datasets.py:76)."""
     if pad_frames <= 0:

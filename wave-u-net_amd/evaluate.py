@@ -135,7 +135,8 @@ def blend_options(overlap, shifts, max_shift, expected_sr):
 
 
 def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, hop_frames=None, workspace_bytes=None,
-                   return_device=False, postfilter=None, phase_iterations=0, overlap=0.0, shifts=None, max_shift=None):
+                   return_device=False, postfilter=None, phase_iterations=0, overlap=0.0, shifts=None, max_shift=None,
+                   loudness=None, loudness_probe=None):
     """Evaluate.predict (Evaluate.py:59-80) around predict_track (:82-145) for audio at any sample rate, without the
     host in the loop.  mix_audio: [n_frames, n_channels] float array or tensor at mix_sr Hz.  Returns {source_name: float32
     numpy [n_frames, channels]} at mix_sr: channels is the input's count, except that a stereo model on a mono file
@@ -186,8 +187,20 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     one plan with batch min(batch_hops, windows); any other separator goes chunk by chunk through get_output and
     blend.blend_windows (the same kernel on a device, its restatement on CPU tensors).  About nshifts / (1 - overlap) times
     the forward passes of the plain path; no quality gain is measured or claimed.  overlap == 0 with shifts None, 0, 1 or
-    [0] is exactly the path and the bits without the options."""
+    [0] is exactly the path and the bits without the options.
+
+    loudness (a target in LUFS or the spec loudness.from_config takes; default None: the mix at the level it arrives, today's
+    path and bits): the n_res frames the network will see are metered at expected_sr with the model's channel count (BS.1770-4
+    integrated loudness, loudness.integrated), the gain to the target is computed on the device (loudness.gain) and those
+    frames are scaled in place; after the resampling back the estimates are scaled by the reciprocal factor in one launch
+    unless the spec's "restore" is False.  A post-filter sees the scaled mix and the scaled estimates.  No value is read on
+    the host.  GPU separators only.  loudness_probe (a dict, for tests and tools) receives "meter" and "gain" (the device
+    tensors) and "padded" (the scaled track the network read, with its context padding)."""
     from . import resample as rs
+    loud = None
+    if loudness is not None:
+        from . import loudness as ld
+        loud = ld.from_config(loudness)
     overlap, offsets = blend_options(overlap, shifts, max_shift, model_config["expected_sr"])
     blended = overlap != 0.0 or offsets != [0]
     phase_iterations = int(phase_iterations)
@@ -203,6 +216,8 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
         from .postfilter import from_config
         postfilter = from_config(postfilter)
     device = torch.device(getattr(separator, "device", None) or "cpu")
+    if loud is not None and device.type != "cuda":
+        raise RuntimeError("loudness: the meter runs on a GPU; there is no CPU fallback (separator on %s)" % device)
     x = mix_audio if torch.is_tensor(mix_audio) else torch.from_numpy(np.ascontiguousarray(np.asarray(mix_audio, dtype=np.float32)))
     assert x.dim() == 2                                                          # Evaluate.py:97
     x = x.to(device=device, dtype=torch.float32).contiguous()                    # the one upload
@@ -225,6 +240,14 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
         track_frames = max(track_frames + lead, lead + int(table[:, 0].max()) + input_frames)   # ... its last one overhangs
     padded = torch.zeros((track_frames, C), dtype=torch.float32, device=device)
     rs.resample_into(x, padded, lead + pad, n_res, up, down)                     # downmix / duplicate, resample, pad
+    gain = None
+    if loud is not None:
+        seen = padded[lead + pad:lead + pad + n_res]                             # what the network will see of the file
+        meter = ld.integrated(seen, int(model_config["expected_sr"]))
+        gain = ld.gain(meter, loud["target"], loud["max_gain_db"], loud["peak_limit"])
+        ld.scale_(seen, gain[0:1])
+        if loudness_probe is not None:
+            loudness_probe.update(meter=meter, gain=gain, padded=padded, offset=lead + pad, frames=n_res)
 
     names = list(model_config["source_names"])
     positions = _hop_positions(n_frames, output_frames) if table is None else table[:, 0].tolist()
@@ -263,6 +286,8 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     out = torch.empty((len(names), n_back, c_fused), dtype=torch.float32, device=device)
     for si in range(len(names)):
         rs.resample_into(preds[si, :n_res], out[si], 0, n_back, down, up)        # [:n_res] drops extra_pad (:141-143)
+    if gain is not None and loud["restore"]:
+        ld.scale_(out, gain[1:2])                                                # back to the file's level
     if c_fused != c_out:
         out = out.repeat(1, 1, c_out)
     if return_device:
@@ -343,12 +368,14 @@ def weights_context(separator, weights):
 
 
 def produce_source_estimates(model_config, load_model, input_path, output_path=None, separator=None, hop_frames=None,
-                             postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None, *, weights=None):
+                             postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None, *, weights=None,
+                             loudness=None):
     """Evaluate.produce_source_estimates (Evaluate.py:160-194): separate one mixture file with a
     checkpoint and write <input file name>_<source>.wav next to it (or into output_path), at the input file's sample rate
     and length.  WAV/NPY input at any rate (an .npy is taken to be at expected_sr; no MP3 decoding here): the separation runs
     through separate_track (hop_frames, postfilter, phase_iterations, overlap, shifts, max_shift: its options of those
-    names; overlap / shifts / max_shift None: model_config["separation"]'s, else none).  weights="ema": separate with the EMA
+    names; overlap / shifts / max_shift None: model_config["separation"]'s, else none; loudness None:
+    model_config["loudness"]'s, else none).  weights="ema": separate with the EMA
     of the weights that the checkpoint carries (weights_context; RuntimeError when it has none).  Returns {source: [T, C]}."""
     import os
     from scipy.io import wavfile
@@ -363,7 +390,8 @@ def produce_source_estimates(model_config, load_model, input_path, output_path=N
         load_checkpoint(sep, load_model, with_optimizer=False)     # .npz or a TensorFlow V2 checkpoint prefix
     with weights_context(sep, weights):
         preds = separate_track(model_config, sep, audio, sr, hop_frames=hop_frames, postfilter=postfilter,
-                               phase_iterations=phase_iterations, **separation_options(model_config, overlap, shifts, max_shift))
+                               phase_iterations=phase_iterations, loudness=loudness_option(model_config, loudness),
+                               **separation_options(model_config, overlap, shifts, max_shift))
     folder, name = os.path.split(input_path)
     if output_path is None:
         output_path = folder
@@ -385,9 +413,15 @@ def separation_options(model_config, overlap=None, shifts=None, max_shift=None):
             "max_shift": max_shift if max_shift is not None else spec.get("max_shift")}
 
 
+def loudness_option(model_config, loudness=None):
+    """The loudness keyword of separate_track: the argument, or when it is None model_config["loudness"]
+    (config.EXTENSION_DEFAULTS: None, no normalisation)."""
+    return loudness if loudness is not None else model_config.get("loudness")
+
+
 def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=None, name=None, hop_frames=None,
                    window=1.0, hop=1.0, filters_len=512, postfilter=None, phase_iterations=0, overlap=None, shifts=None,
-                   max_shift=None):
+                   max_shift=None, *, loudness=None):
     """Evaluate.predict with a results_dir (Evaluate.py:59-80,146-158): separate the mixture (separate_track, estimates kept
     on the device), score them against the stems at the file's rate with bsseval.bss_eval, and write
     <results_dir>/<name>.json in museval's layout.  mix_audio [n, c] at sr; stems {source_name: [n, c]} at sr with the
@@ -396,6 +430,7 @@ def evaluate_track(model_config, separator, mix_audio, stems, sr, results_dir=No
     from . import bsseval
     est = separate_track(model_config, separator, mix_audio, sr, hop_frames=hop_frames, return_device=True,
                          postfilter=postfilter, phase_iterations=phase_iterations,
+                         loudness=loudness_option(model_config, loudness),
                          **separation_options(model_config, overlap, shifts, max_shift))
     names = list(model_config["source_names"])
     c = int(est.shape[2])
@@ -449,7 +484,7 @@ def compute_mean_metrics(json_folder, compute_averages=True, metric="SDR"):
 
 def produce_dataset_estimates(model_config, load_model, data_root, output_path, partition="test", separator=None,
                               hop_frames=None, postfilter=None, phase_iterations=0, overlap=None, shifts=None, max_shift=None,
-                              *, weights=None):
+                              *, weights=None, loudness=None):
     """The reference's produce_musdb_source_estimates (Evaluate.py:147-159) over the track folders of datasets.py:
     data_root/<partition>/<track>/<source>.wav|.npy (+ optional mix.wav|.npy, default: the sum of the stems), every file at
     one rate (an .npy: expected_sr).  Per track: the estimates as <output_path>/<partition>/<track>/<source>.wav and the
@@ -462,7 +497,8 @@ def produce_dataset_estimates(model_config, load_model, data_root, output_path, 
         load_checkpoint(sep, load_model, with_optimizer=False)
     with weights_context(sep, weights):
         return _dataset_estimates(model_config, sep, data_root, output_path, partition, hop_frames, postfilter, phase_iterations,
-                                  separation_options(model_config, overlap, shifts, max_shift))
+                                  dict(separation_options(model_config, overlap, shifts, max_shift),
+                                       loudness=loudness_option(model_config, loudness)))
 
 
 def _dataset_estimates(model_config, sep, data_root, output_path, partition, hop_frames, postfilter, phase_iterations, blend_kw):

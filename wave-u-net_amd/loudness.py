@@ -1,0 +1,174 @@
+"""Integrated loudness (ITU-R BS.1770-4 / EBU R 128) and loudness normalisation on the device, and the recursive filter
+underneath it.  DESIGN.md 5.27 holds the definition; the kernels are libwun.so's (include/wun.h: wun_sosfilt, wun_loudness,
+wun_loudness_gain, wun_scale_by).  The reference has no counterpart: it feeds a file at whatever level it arrives.
+
+Nothing here reads a device value on the host: the meter, the gain and the scaling are launches on the current stream, and the
+factor travels as a device tensor.  There is no CPU fallback: tensors are filtered and metered on a GPU.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+KEYS = ("target", "max_gain_db", "peak_limit", "restore", "data")
+DEFAULTS = {"target": -23.0, "max_gain_db": 30.0, "peak_limit": None, "restore": True, "data": False}
+
+
+def chunk():
+    """Frames per chunk of the filter's parallel schedule (wun_sos_chunk)."""
+    return int(_lib.load().wun_sos_chunk())
+
+
+def tile():
+    """Chunks per workgroup and per carry group (wun_sos_tile)."""
+    return int(_lib.load().wun_sos_tile())
+
+
+def kweight_sos(sr):
+    """The K-weighting at sr Hz as float64 numpy [2, 6] in scipy's sos layout (wun_kweight_design)."""
+    sos = (C.c_double * 12)()
+    _lib.check(_lib.load().wun_kweight_design(int(sr), sos))
+    return np.array(sos, dtype=np.float64).reshape(2, 6)
+
+
+def blocks(n, sr):
+    """Complete 0.4 s gating blocks of n frames at sr (wun_loudness_blocks)."""
+    v = int(_lib.load().wun_loudness_blocks(int(n), int(sr)))
+    if v < 0:
+        _lib.check(v)
+    return v
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _audio(x, who):
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError("%s runs its kernels on a GPU; there is no CPU fallback (got %s)" % (
+            who, "a tensor on %s" % x.device if torch.is_tensor(x) else type(x).__name__))
+    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
+        raise ValueError("%s: audio must be a contiguous float32 tensor [n, C], got %s %s" % (who, x.dtype, tuple(x.shape)))
+    return int(x.shape[0]), int(x.shape[1])
+
+
+def sosfilt(x, sos, out=None, scratch=None):
+    """scipy.signal.sosfilt(sos, x, axis=0) from zero state for a float32 device tensor x [n, C]: float64 arithmetic, one rounding
+    to float32 (wun_sosfilt).  sos: [nsec, 6] host floats, a0 == 1, nsec in 1..8."""
+    n, Cc = _audio(x, "sosfilt")
+    sos = np.ascontiguousarray(np.asarray(sos, dtype=np.float64))
+    if sos.ndim != 2 or sos.shape[1] != 6:
+        raise ValueError("sos must be [nsec, 6], got %s" % (sos.shape,))
+    lib = _lib.load()
+    nsec = int(sos.shape[0])
+    dev = x.device
+    if scratch is None:
+        need = int(lib.wun_sosfilt_scratch_doubles(n, Cc, nsec))
+        if need < 0:
+            _lib.check(need)
+        scratch = torch.empty(need, dtype=torch.float64, device=dev)
+    y = torch.empty_like(x) if out is None else out
+    with torch.cuda.device(dev):
+        _lib.check(lib.wun_sosfilt(x.data_ptr(), n, Cc, sos.ctypes.data_as(C.POINTER(C.c_double)), nsec, y.data_ptr(),
+                                   scratch.data_ptr(), _stream(dev)))
+    return y
+
+
+def k_weight(x, sr):
+    """x through the K-weighting at sr Hz."""
+    return sosfilt(x, kweight_sos(sr))
+
+
+def scratch_doubles(n, Cc, sr):
+    v = int(_lib.load().wun_loudness_scratch_doubles(int(n), int(Cc), int(sr)))
+    if v < 0:
+        _lib.check(v)
+    return v
+
+
+def integrated(x, sr, return_blocks=False, scratch=None):
+    """The meter of a float32 device tensor x [n, C] at sr Hz: a float64 device tensor [4] = integrated loudness in LUFS (-inf
+    when no block passes the gates, NaN when x holds one), blocks kept, complete blocks, sample peak max |x| (wun_loudness).
+    return_blocks: also the momentary loudness of every block, float64 [nb].  No host synchronisation."""
+    n, Cc = _audio(x, "integrated")
+    dev = x.device
+    if scratch is None:
+        scratch = torch.empty(scratch_doubles(n, Cc, sr), dtype=torch.float64, device=dev)
+    meter = torch.empty(4, dtype=torch.float64, device=dev)
+    blk = torch.empty(blocks(n, sr), dtype=torch.float64, device=dev) if return_blocks else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().wun_loudness(x.data_ptr(), n, Cc, int(sr), meter.data_ptr(),
+                                            blk.data_ptr() if blk is not None and blk.numel() else None,
+                                            scratch.data_ptr(), _stream(dev)))
+    return (meter, blk) if return_blocks else meter
+
+
+def gain(meter, target=-23.0, max_gain_db=30.0, peak_limit=None):
+    """float32 device tensor [2] = (g, 1 / g) from a meter of integrated(): g = 10^((target - L) / 20) capped at max_gain_db and,
+    with peak_limit, at peak_limit / peak; exactly 1 when L is not finite (wun_loudness_gain)."""
+    if not torch.is_tensor(meter) or not meter.is_cuda:
+        raise RuntimeError("gain reads the meter on a GPU; there is no CPU fallback")
+    if meter.dtype != torch.float64 or meter.numel() != 4 or not meter.is_contiguous():
+        raise ValueError("meter must be the float64 [4] tensor of integrated()")
+    dev = meter.device
+    g = torch.empty(2, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().wun_loudness_gain(meter.data_ptr(), float(target), float(max_gain_db),
+                                                 0.0 if peak_limit is None else float(peak_limit), g.data_ptr(), _stream(dev)))
+    return g
+
+
+def scale_(x, factor):
+    """x *= factor[0] in place: x a contiguous float32 device tensor of any shape, factor a float32 device tensor (a view of
+    gain()'s result: g[0:1] scales, g[1:2] restores).  One launch (wun_scale_by)."""
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError("scale_ runs on a GPU; there is no CPU fallback")
+    if x.dtype != torch.float32 or not x.is_contiguous() or factor.dtype != torch.float32 or factor.device != x.device:
+        raise ValueError("scale_: a contiguous float32 tensor and a float32 factor on its device expected")
+    if x.numel():
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().wun_scale_by(x.data_ptr(), x.numel(), factor.data_ptr(), _stream(x.device)))
+    return x
+
+
+def normalize(x, sr, target=-23.0, max_gain_db=30.0, peak_limit=None, inplace=False):
+    """(y, gain): x [n, C] scaled to `target` LUFS, and the float32 [2] factor pair of gain()."""
+    g = gain(integrated(x, sr), target, max_gain_db, peak_limit)
+    y = x if inplace else x.clone()
+    return scale_(y, g[0:1]), g
+
+
+def from_config(spec):
+    """model_config["loudness"] / separate_track's keyword checked and completed: None stays None; a number is the target; a
+    dict may hold target, max_gain_db, peak_limit, restore, data.  ValueError for anything else."""
+    if spec is None:
+        return None
+    if isinstance(spec, bool):
+        raise ValueError("loudness = %r: a target in LUFS or a dict expected" % (spec,))
+    if isinstance(spec, (int, float, np.integer, np.floating)):
+        spec = {"target": float(spec)}
+    if not isinstance(spec, dict):
+        raise ValueError("loudness = %r: a target in LUFS or a dict expected" % (spec,))
+    unknown = set(spec) - set(KEYS)
+    if unknown:
+        raise ValueError("loudness: unknown keys %s (have %s)" % (sorted(unknown), ", ".join(KEYS)))
+    out = dict(DEFAULTS, **spec)
+    for k in ("target", "max_gain_db"):
+        if isinstance(out[k], bool) or not isinstance(out[k], (int, float, np.integer, np.floating)) or not math.isfinite(out[k]):
+            raise ValueError("loudness[%r] = %r must be a finite number" % (k, out[k]))
+        out[k] = float(out[k])
+    if out["max_gain_db"] < 0:
+        raise ValueError("loudness['max_gain_db'] = %r must be >= 0" % out["max_gain_db"])
+    pl = out["peak_limit"]
+    if pl is not None:
+        if isinstance(pl, bool) or not isinstance(pl, (int, float, np.integer, np.floating)) or not math.isfinite(pl) or pl <= 0:
+            raise ValueError("loudness['peak_limit'] = %r must be a number > 0 or None" % (pl,))
+        out["peak_limit"] = float(pl)
+    for k in ("restore", "data"):
+        if not isinstance(out[k], (bool, np.bool_)):
+            raise ValueError("loudness[%r] = %r must be a bool" % (k, out[k]))
+        out[k] = bool(out[k])
+    return out

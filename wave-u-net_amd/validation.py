@@ -90,6 +90,16 @@ def _eval_weights(model_config, sep):
     return sep.ema_weights()
 
 
+def _loudness_data(model_config, tracks):
+    """model_config["loudness"]["data"]: the tracks scaled to the target loudness of their mixes once, where they are loaded
+    (datasets.normalize_tracks on the current GPU); otherwise the tracks as they are.  optimise() does it for its three
+    partitions, test() for the tracks it loads itself -- tracks handed to test() are taken at the level they have."""
+    spec = datasets.loudness_data_spec(model_config)
+    if spec is None:
+        return tracks
+    return datasets.normalize_tracks(tracks, model_config, torch.device("cuda", torch.cuda.current_device()), spec)[0]
+
+
 def test(model_config, partition, model_folder, load_model, tracks=None, data_root=None, separator=None,
          return_sums=False, resample=False):
     """Test.test(model_config, partition, model_folder, load_model) -> mean MSE.  The partition's
@@ -118,6 +128,7 @@ def test(model_config, partition, model_folder, load_model, tracks=None, data_ro
         if data_root is None:
             raise ValueError("test() needs `tracks` or `data_root`")
         tracks = datasets.load_partition(data_root, partition, model_config, resample)
+        tracks = _loudness_data(model_config, tracks)
     sep = separator if separator is not None else make_separator(model_config)
     disc_input_shape = [model_config["batch_size"], model_config["num_frames"], 0]
     in_shape, out_shape = sep.get_padding(np.array(disc_input_shape))            # Test.py:21
@@ -175,6 +186,7 @@ def optimise(model_config, experiment_id, data=None, data_root=None, max_epochs=
         if data_root is None:
             raise ValueError("optimise() needs `data` or `data_root`")
         data = {part: datasets.load_partition(data_root, part, model_config, resample) for part in ("train", "valid", "test")}
+    data = {part: _loudness_data(model_config, tracks) for part, tracks in data.items()}
     model_config = dict(model_config)
     epoch = 0
     best_loss = 10000
