@@ -1,9 +1,11 @@
 """The extended optimizer step of include/wun.h (wun_optim_step, wun_ema_update) in numpy: the formulas in
-float64, a float32 restatement with the library's roundings, and the learning-rate factor of training.lr_factor written out
-a second time.  Everything works on flat arrays; `decay` is a boolean array (which floats decay)."""
+float64, a bit-exact float32 restatement with the library's roundings, and the learning-rate factor of training.lr_factor
+written out a second time.  Everything works on flat arrays; `decay` is a boolean array (which floats decay)."""
 import math
 
 import numpy as np
+
+from _fma_chain_np import fmaf_np
 
 
 def lr_t(step, lr, b1=0.9, b2=0.999):
@@ -66,24 +68,18 @@ def ema32(ema, theta, ema_decay, step, warmup=False):
     return (ema - (w * (ema - theta)).astype(f)).astype(f)
 
 
-def _fma32(a, b, c):
-    """fmaf on fp32 inputs through float64: a * b is exact there; the sum is rounded to float64 and then to fp32 (a double
-    rounding that can differ from fmaf in the last bit in rare ties -- this restatement is for orientation, the bit pins of
-    the tests compare library calls with library calls)."""
-    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
-
-
 def step32(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8, grad_scale=1.0, norm=None, clip=math.inf, weight_decay=0.0,
            decay=None):
-    """(theta, m, v) with the library's roundings: g * grad_scale, times fp32(clip / N) when N > clip; m = fma(b1, m, (1 - b1)
-    g); v = fma(b2, v, ((1 - b2) g) g); theta * fp32(1 - lr wd) where it decays; theta - (lr_t m) / (sqrt(v) + eps)."""
+    """(theta, m, v) with the library's roundings, bit-exact: g * grad_scale, times fp32(clip / N) when N > clip; m = fma(b1, m,
+    (1 - b1) g); v = fma(b2, v, ((1 - b2) g) g), the fused multiply-adds exact (fmaf_np); theta * fp32(1 - lr wd) where it
+    decays; theta - (lr_t m) / (sqrt(v) + eps), every other operation rounded once to fp32.  norm: the fp32 global norm N."""
     f = np.float32
     p, g, m, v = (np.asarray(a, f) for a in (p, g, m, v))
     gi = g * f(grad_scale)
     if norm is not None and f(norm) > f(clip):
         gi = gi * (f(clip) / f(norm))
-    m = _fma32(f(b1), m, (f(1) - f(b1)) * gi)
-    v = _fma32(f(b2), v, ((f(1) - f(b2)) * gi) * gi)
+    m = fmaf_np(f(b1), m, (f(1) - f(b1)) * gi)
+    v = fmaf_np(f(b2), v, ((f(1) - f(b2)) * gi) * gi)
     if decay is not None and weight_decay:
         wdf = f(1.0 - float(f(lr)) * float(f(weight_decay)))
         p = np.where(decay, p * wdf, p)

@@ -7,7 +7,7 @@ Plans (the smallest that can still go wrong):
   odd         the odd-filter geometry of the golden case odd_filters_small: tensor sizes and offsets are no multiples of 4
   many        7 layers, learned upsampling, four sources: 45 tensors, one above 8192 floats -- the norm has more than one
               chunk, and with the kernels decaying and the biases not, the walk has over 32 runs: more than one range batch
-The float64 oracle and the float32 restatement of the EMA line live in tests/_optim_np.py."""
+The float64 oracle and the bit-exact float32 restatements of the step and of the EMA line live in tests/_optim_np.py."""
 import ctypes as C
 import json
 import math
@@ -220,6 +220,59 @@ def test_bit_equal_to_the_adam_entries(lib, kind, select):
             assert not torch.equal(_bits(bare.p), _bits(a0.p))
 
 
+@pytest.mark.parametrize("kind", ["small", "small_bf16", "odd", "many"])
+@pytest.mark.parametrize("select", ["all", "every_other"])
+def test_bits_of_every_entry_against_the_float32_restatement(lib, kind, select):
+    """params, m and v of wun_adam_step / _select, of wun_adam_step_clip (clip active at 0.1 N, inactive at 2 N, +inf with the
+    skip flag) and of wun_optim_step with the rank > 1 tensors decaying and no EMA, bit for bit against _optim_np.step32 -- numpy
+    with an exact fmaf, no library call -- on the selected floats; every other float keeps its bits.  N is the fp32 global norm
+    the call leaves in norm_ws (tests/test_gpu_grad_clip.py checks its accuracy)."""
+    sep, _ = _separator(kind)
+    a0 = Arenas(sep)
+    sel = None if select == "all" else _every_other(sep)
+    nt = len(sep._active.tensors)
+    chosen = _floats(sep, sel if sel is not None else np.ones(nt, dtype=np.uint8))
+    dec = _kernels(sep)
+    ws, cnt = _ws(lib, sep)
+    h, s = sep._active.handle, sep._stream()
+    step, lr, gs, wd = 4, 1e-3, 0.5, 0.1
+    p0, g0, m0, v0 = (t.cpu().numpy() for t in (a0.p, a0.g, a0.m, a0.v))
+
+    def check(got, tag, **kw):
+        torch.cuda.synchronize()
+        want = onp.step32(p0, g0, m0, v0, step, lr, B1, B2, EPS, gs, **kw)
+        for x, w, o, what in zip((got.p, got.m, got.v), want, (a0.p, a0.m, a0.v), ("params", "m", "v")):
+            w = torch.where(chosen, torch.from_numpy(w).cuda(), o)
+            assert torch.equal(_bits(x), _bits(w)), (tag, what, int((_bits(x) != _bits(w)).sum().item()))
+        assert not torch.equal(_bits(got.p), _bits(a0.p))
+        assert torch.equal(_bits(got.g), _bits(a0.g)) and torch.equal(_bits(got.ema), _bits(a0.ema))
+
+    got = a0.clone()
+    if sel is None:
+        _lib.check(lib.wun_adam_step(h, got.p.data_ptr(), got.g.data_ptr(), got.m.data_ptr(), got.v.data_ptr(), step, lr, B1, B2,
+                                     EPS, gs, s))
+    else:
+        _lib.check(lib.wun_adam_step_select(h, got.p.data_ptr(), got.g.data_ptr(), got.m.data_ptr(), got.v.data_ptr(), step, lr,
+                                            B1, B2, EPS, gs, s, *_mask_arg(sel)))
+    check(got, "adam")
+
+    def clipped(clip, flag):
+        got = a0.clone()
+        _lib.check(lib.wun_adam_step_clip(h, got.p.data_ptr(), got.g.data_ptr(), got.m.data_ptr(), got.v.data_ptr(), step, lr, B1,
+                                          B2, EPS, gs, clip, flag, ws.data_ptr(), cnt.data_ptr(), s, *_mask_arg(sel)))
+        return got, float(ws[nt].item())
+
+    norm = clipped(math.inf, 0)[1]                     # the norm does not depend on the clip: every call below leaves this value
+    assert math.isfinite(norm) and norm > 0
+    for factor, flag in ((0.1, 0), (2.0, 0), (math.inf, _lib.WUN_CLIP_SKIP_NONFINITE)):
+        got, n = clipped(factor * norm, flag)
+        assert n == norm and int(cnt.item()) == 0
+        check(got, ("clip", factor, flag), norm=norm, clip=factor * norm)
+    got = a0.clone()
+    _optim(lib, sep, got, step, lr, gs, wd=wd, sel=sel, dec=dec)
+    check(got, "decay", weight_decay=wd, decay=_floats(sep, dec).cpu().numpy())
+
+
 # ------------------------------------------------------------------------------------------------ 2. against float64
 def _ulps(got, want64, *operands):
     """|got - want| in float32 ulps of the largest of |want| and the |operands| the value was formed from (the rule of
@@ -353,40 +406,90 @@ def test_skip_is_counted_once_over_several_launches(lib, with_ema):
 
 
 # ------------------------------------------------------------------------------------------------ 4. independence
+def _entry(lib, sep, entry, ws, cnt):
+    """call(arenas, stream=None): one step through `entry`, with everything on that the entry has."""
+    skip = _lib.WUN_CLIP_SKIP_NONFINITE
+    if entry == "optim":
+        kw = dict(wd=0.05, ema_decay=0.99, clip=1e-3, flags=_lib.WUN_OPTIM_EMA_WARMUP | skip, dec=_kernels(sep), ws=ws, skipped=cnt)
+        return lambda a, stream=None: _optim(lib, sep, a, stream=stream, **kw)
+
+    def call(a, stream=None):
+        args = (sep._active.handle, a.p.data_ptr(), a.g.data_ptr(), a.m.data_ptr(), a.v.data_ptr(), 4, 1e-3, B1, B2, EPS, 1.0)
+        s = stream if stream is not None else sep._stream()
+        if entry == "adam":
+            _lib.check(lib.wun_adam_step(*args, s))
+        else:
+            _lib.check(lib.wun_adam_step_clip(*args, 1e-3, skip, ws.data_ptr(), cnt.data_ptr(), s, None, 0))
+    return call
+
+
 @pytest.mark.parametrize("kind", ["odd", "many"])
-def test_bits_do_not_depend_on_stream_repetition_or_alignment(lib, kind):
+@pytest.mark.parametrize("entry", ["optim", "adam", "adam_clip"])
+def test_bits_do_not_depend_on_stream_repetition_or_alignment(lib, kind, entry):
     sep, _ = _separator(kind)
     a0 = Arenas(sep)
-    dec = _kernels(sep)
     ws, cnt = _ws(lib, sep)
-    kw = dict(wd=0.05, ema_decay=0.99, clip=1e-3, flags=_lib.WUN_OPTIM_EMA_WARMUP | _lib.WUN_CLIP_SKIP_NONFINITE, dec=dec, ws=ws,
-              skipped=cnt)
+    call = _entry(lib, sep, entry, ws, cnt)
     ref = a0.clone()
-    _optim(lib, sep, ref, **kw)
+    call(ref)
     torch.cuda.synchronize()
+    assert not torch.equal(_bits(ref.p), _bits(a0.p)) and int(cnt.item()) == 0
     again = a0.clone()
-    _optim(lib, sep, again, **kw)
+    call(again)
     _equal(again.four(), ref.four(), "repetition")
     side = torch.cuda.Stream()
     other = a0.clone()
     torch.cuda.synchronize()
     with torch.cuda.stream(side):
-        _optim(lib, sep, other, stream=C.c_void_p(side.cuda_stream), **kw)
+        call(other, stream=C.c_void_p(side.cuda_stream))
     side.synchronize()
     _equal(other.four(), ref.four(), "stream")
-    shifted = a0.clone(shift=True)                                   # every arena one float behind an allocation's start
-    _optim(lib, sep, shifted, **kw)
+    shifted = a0.clone(shift=True)                                   # every arena one float behind an allocation's start:
+    call(shifted)                                                    # the 16-byte path with a scalar head
     _equal(shifted.four(), ref.four(), "one-float shift of every arena")
     mixed = a0.clone()                                               # arenas that do not share an alignment: the scalar path
-    mixed.ema = _offset_copy(mixed.ema)
-    mixed.v = _offset_copy(mixed.v)
-    _optim(lib, sep, mixed, **kw)
+    if entry == "optim":
+        mixed.ema = _offset_copy(mixed.ema)
+        mixed.v = _offset_copy(mixed.v)
+    else:
+        mixed.g = _offset_copy(mixed.g)
+    call(mixed)
     torch.cuda.synchronize()
     _equal(mixed.four(), ref.four(), "mixed alignment")
-    alone_a, alone_b = a0.ema.clone(), _offset_copy(a0.ema)
-    for e in (alone_a, alone_b):
-        _lib.check(lib.wun_ema_update(sep._active.handle, e.data_ptr(), a0.p.data_ptr(), 0.99, 3, 0, sep._stream(), None, 0))
-    assert torch.equal(_bits(alone_a), _bits(alone_b))
+    if entry == "optim":
+        alone_a, alone_b = a0.ema.clone(), _offset_copy(a0.ema)
+        for e in (alone_a, alone_b):
+            _lib.check(lib.wun_ema_update(sep._active.handle, e.data_ptr(), a0.p.data_ptr(), 0.99, 3, 0, sep._stream(), None, 0))
+        assert torch.equal(_bits(alone_a), _bits(alone_b))
+
+
+def test_adam_step_footprint_without_a_selection(lib):
+    """wun_adam_step with a NULL selection on 'odd', the four arenas embedded in larger buffers with sentinels before and
+    behind: exactly the arena's floats are written -- the ends of the 16-byte loop, with the arena (a multiple of 4 floats) at a
+    16-byte boundary (front of 4 floats: neither head nor tail), one float past it (5: a head of 3, a tail of 1) and three
+    past it (7: a head of 1, a tail of 3) -- and the bits are those of the call on plain buffers."""
+    sep, _ = _separator("odd")
+    a0 = Arenas(sep)
+    n = int(sep._active.info.arena_floats)
+    assert n % 4 == 0 and n > 1024
+    call = _entry(lib, sep, "adam", None, None)
+    ref = a0.clone()
+    call(ref)
+    torch.cuda.synchronize()
+    back = 7
+    for front in (4, 5, 7):
+        bufs, inner = {}, object.__new__(Arenas)
+        for k in ("p", "g", "m", "v", "ema"):
+            bufs[k] = torch.full((front + n + back,), SENTINEL, dtype=torch.int32, device="cuda").view(torch.float32)
+            setattr(inner, k, bufs[k][front:front + n])
+            getattr(inner, k).copy_(getattr(a0, k))
+            assert getattr(inner, k).data_ptr() % 16 == 4 * (front % 4)
+        call(inner)
+        torch.cuda.synchronize()
+        _equal(inner.four(), ref.four(), ("embedded", front))
+        assert torch.equal(_bits(inner.g), _bits(a0.g))
+        for k, b in bufs.items():
+            assert (_bits(b)[:front] == SENTINEL).all() and (_bits(b)[front + n:] == SENTINEL).all(), (front, k)
 
 
 # ------------------------------------------------------------------------------------------------ 5. ema_weights()

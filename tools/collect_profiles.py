@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Copy the artefacts of `tools/profile_round.sh <tag>` from gpurun_out/ (scratch) into profiles/ (tracked), putting a
 header line on the two rocprofv3 kernel-stats CSVs that says which command they profile and how many training steps
-they contain (counted from the adam_kernel calls).   usage: python tools/collect_profiles.py round5"""
+they contain (counted from the optimizer's calls: optim_ranges_kernel, adam_kernel in older traces).   usage: python tools/collect_profiles.py round5"""
 import csv
 import glob
 import json
@@ -16,7 +16,7 @@ src, dst = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
 
 def steps_of(path):
     rows = list(csv.DictReader(open(path)))
-    return sum(int(r["Calls"]) for r in rows if "adam_kernel" in r["Name"])
+    return sum(int(r["Calls"]) for r in rows if "optim_ranges_kernel" in r["Name"] or "adam_kernel" in r["Name"])
 
 
 def settle_of(path):

@@ -3,6 +3,7 @@
 context, B = 16) and of deep_l16_f48 (the arenas do not depend on the batch: that plan is built for one excerpt).
 
 Arms (one optimizer step each; the gradient arena holds N(0, 1e-3) floats, clip_norm = 0.1 x its norm clips every call):
+  a0 adam             wun_adam_step: no norm                                  28 B / float
   a  adam_clip        wun_adam_step_clip                                      32 B / float (norm 4 + Adam 28)
   b  optim_off        wun_optim_step, weight_decay 0, no EMA                  32 B / float
   c  optim_on         wun_optim_step, weight decay on every tensor + EMA      40 B / float (norm 4 + the fused pass 36)
@@ -27,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-ARMS = ["adam_clip", "optim_off", "optim_on", "optim_kernels", "unfused", "grad_norm"]
+ARMS = ["adam", "adam_clip", "optim_off", "optim_on", "optim_kernels", "unfused", "grad_norm"]
 HBM_TBS = 6.29
 LR, WD, EMA_D = 1e-4, 0.01, 0.999
 
@@ -60,7 +61,9 @@ def setup(name, batch):
 
     def call(arm):
         st = sep._stream()
-        if arm in ("adam_clip", "unfused"):
+        if arm == "adam":
+            _lib.check(lib.wun_adam_step(h, p, g, m, v, 1, LR, 0.9, 0.999, 1e-8, 1.0, st))
+        elif arm in ("adam_clip", "unfused"):
             _lib.check(lib.wun_adam_step_clip(h, p, g, m, v, 1, LR, 0.9, 0.999, 1e-8, 1.0, clip, 1, ws.data_ptr(),
                                               skipped.data_ptr(), st, None, 0))
             if arm == "unfused":

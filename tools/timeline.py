@@ -3,7 +3,7 @@
 
 usage: tools/timeline.py <kernel_trace.csv> [step_index_from_end=2] [out.txt]
 
-A step is delimited by consecutive adam_kernel launches.  Prints, for the chosen step: wall time, the time with
+A step is delimited by consecutive launches of the optimizer (optim_ranges_kernel; adam_kernel in the traces under profiles/).  Prints, for the chosen step: wall time, the time with
 0 / 1 / 2 / >=3 kernels in flight, per-queue busy time, the largest gaps with nothing running, and a coarse
 phase table (forward / backward split at head_bwd_kernel) with the kernel families active in each.
 """
@@ -27,7 +27,7 @@ def main():
     for r in csv.DictReader(open(path)):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", "0")))
     rows.sort()
-    adam = [i for i, r in enumerate(rows) if "adam_kernel" in r[2]]
+    adam = [i for i, r in enumerate(rows) if "optim_ranges_kernel" in r[2] or "adam_kernel" in r[2]]
     if len(adam) < back + 1:
         print("not enough steps in the trace", file=out)
         return

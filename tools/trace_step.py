@@ -10,7 +10,8 @@ rows.sort()
 back = int(sys.argv[2]) if len(sys.argv) > 2 else 2
 lo_us = float(sys.argv[3]) if len(sys.argv) > 3 else -1e30
 hi_us = float(sys.argv[4]) if len(sys.argv) > 4 else 1e30
-adam = [i for i, r in enumerate(rows) if "adam_kernel" in r[2]]
+# the optimizer ends a step: optim_ranges_kernel (adam_kernel in the traces under profiles/)
+adam = [i for i, r in enumerate(rows) if "optim_ranges_kernel" in r[2] or "adam_kernel" in r[2]]
 lo, hi = adam[-back - 1] + 1, adam[-back] + 1
 t0 = rows[adam[-back - 1]][1]
 def short(name):

@@ -20,7 +20,7 @@ Frozen variables (fine-tuning part of the network) and input-only gradients (a f
 The backward pass then runs wun_backward_select: launches no wanted gradient needs are skipped, and the frozen ranges of
 arena.grad are 0, as the padding floats are.  A torch optimizer still steps every float of the one arena Parameter: with
 weight decay (AdamW, Adam(weight_decay=...)) or momentum left over from earlier steps it moves frozen variables too.  The
-separator's own adam_step(variables=...) (wun_adam_step_select) leaves them bit-unchanged.
+separator's own adam_step(variables=...) leaves them bit-unchanged.
 """
 import numpy as np
 import torch

@@ -884,21 +884,26 @@ extern "C" int wun_spec_adam_step(const wun_spec_config* cfg, const wun_spec_tra
         overlap(m, np, v, np) || overlap(m, np, grads, np) || overlap(v, np, grads, np))
         return fail(WUN_ERR_INVALID, std::string(who) + ": two buffers overlap");
     hipStream_t s = (hipStream_t)stream;
-    // TF-Adam's step size (Training.py:77), as wun_adam_step forms it
-    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)step)) / (1.0 - std::pow((double)beta1, (double)step)));
+    // wun_adam_step's update: the optimizer's kernel with no clip prologue, no decay and no EMA
+    OptimArgs a;
+    memset(&a, 0, sizeof(a));
+    a.p = params; a.g = grads; a.m = m; a.v = v;
+    a.lr_t = adam_lr_t(step, lr, beta1, beta2);
+    a.b1 = beta1; a.b2 = beta2; a.eps = eps; a.gscale = grad_scale;
+    a.vec = same_alignment({params, grads, m, v}) ? 1 : 0;
     const std::vector<SpecTensor> tab = spec_tensors(*cfg);
     const int L = l.L;
     for (int src = 0; src < l.S; ++src) {
         const SrcVars sv = source_vars(tab, L, src);
-        // kernels, biases and betas: per layer one run of consecutive floats (kernel, bias, beta), wun_adam_step_select's kernel;
-        // the moving statistics between the runs are not touched, nor are their slots
+        // kernels, biases and betas: per layer one run of consecutive floats (kernel, bias, beta); the moving statistics
+        // between the runs are not touched, nor are their slots
         AdamRanges r;
         memset(&r, 0, sizeof(r));
         auto run = [&](int64_t first, int64_t end) { r.off[r.n] = first; r.cum[r.n + 1] = r.cum[r.n] + (end - first); ++r.n; };
         for (int i = 0; i < L; ++i) run(sv.dw[i], sv.dmean[i]);
         for (int i = 0; i < L - 1; ++i) run(sv.uw[i], sv.umean[i]);
         run(sv.uw[L - 1], sv.ub[L - 1] + 1);
-        if (launch_adam_ranges(params, grads, m, v, r, lr_t, beta1, beta2, eps, grad_scale, s) != hipSuccess)
+        if (launch_optim_ranges(a, r, s) != hipSuccess)
             return fail(WUN_ERR_HIP, std::string(who) + ": launch failed");
         launch_moving_averages(l, tcfg, params, workspace, src, sv, s);
     }

@@ -953,65 +953,7 @@ hipError_t launch_make_wt_one(const float* src, float* dst, WtDesc d, hipStream_
     return hipGetLastError();
 }
 
-// ---- TF-Adam (wun_adam_step, _select, _clip): four thin kernels over ONE update, ONE run lookup, ONE clip prologue --------
-// The kernels differ in which floats they visit (the whole arena / the selected runs) and in what they do to the gradient first
-// (nothing / clip by the global norm); a float's update is the same expressions in the same order in all of them, which is what
-// makes a selected float bit-equal to the full step's and an inactive clip bit-equal to the plain step.
-// The fused multiply-adds of mi and vi (decayed term fused, gradient term rounded first) are written out: left to
-// -ffp-contract, which of a sum's two products is fused is the compiler's choice per call site, and that choice is a rounding.
-__device__ __forceinline__ void adam_update(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, long long i,
-                                            float gi, float lr_t, float b1, float b2, float eps) {
-    const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
-    const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
-    m[i] = mi;
-    v[i] = vi;
-    p[i] = p[i] - lr_t * mi / (sqrtf(vi) + eps);
-}
-
-// position t of the concatenated runs -> arena index: a scan of the (at most WUN_ADAM_RANGES) prefix sums
-__device__ __forceinline__ long long adam_range_index(const AdamRanges& r, long long t) {
-    int k = 0;
-    while (k + 1 < r.n && t >= r.cum[k + 1]) ++k;
-    return r.off[k] + (t - r.cum[k]);
-}
-
-static unsigned adam_grid(long long n) { return (unsigned)std::min(std::max((n + 255) / 256, 1LL), 4096LL); }
-
-__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long long n, float lr_t, float b1, float b2,
-                            float eps, float gscale) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        adam_update(p, m, v, i, g[i] * gscale, lr_t, b1, b2, eps);
-}
-
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr_t,
-                       float b1, float b2, float eps, float gscale, hipStream_t s) {
-    ProfScope ps("adam_kernel", 0.0, s, "", 28.0 * (double)n);       // p, m, v read + written, g read
-    hipLaunchKernelGGL(adam_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, gscale);
-    return hipGetLastError();
-}
-
-// adam_kernel over the selected runs only: thread-strided over the concatenated runs
-__global__ void adam_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                   float* __restrict__ v, AdamRanges r, float lr_t, float b1, float b2,
-                                   float eps, float gscale) {
-    const long long total = r.cum[r.n];
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const long long i = adam_range_index(r, t);
-        adam_update(p, m, v, i, g[i] * gscale, lr_t, b1, b2, eps);
-    }
-}
-
-hipError_t launch_adam_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t,
-                              float b1, float b2, float eps, float gscale, hipStream_t s) {
-    const long long n = r.n > 0 ? r.cum[r.n] : 0;
-    if (n <= 0) return hipSuccess;
-    ProfScope ps("adam_ranges_kernel", 0.0, s, "", 28.0 * (double)n);
-    hipLaunchKernelGGL(adam_ranges_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2, eps, gscale);
-    return hipGetLastError();
-}
-
-// ---- global gradient norm (wun_grad_norm) and the clipped TF-Adam (wun_adam_step_clip) --------------------------------
+// ---- global gradient norm (wun_grad_norm; the clipping entries read it) --------------------------------
 // Sums of squares in float64: double(g) * double(g) is exact, so the only rounding is in the float64 adds, whose order is
 // fixed by the chunk table and the block shape alone -- no atomics, bitwise reproducible, independent of the grid size.
 __device__ __forceinline__ double wave_sum_f64(double x) {
@@ -1091,8 +1033,15 @@ hipError_t launch_grad_norm(const float* g, const NormChunk* chunks, const int* 
     return hipGetLastError();
 }
 
-// The clipped kernels: gi = g * gscale, times clip / N only when N > clip -- with no clipping every float is bit-equal to
-// adam_kernel's.  A skipped step (skip != 0, N not finite) returns before any p / m / v access; block 0's first lane counts it.
+// ---- the optimizer (wun_adam_step, _select, _clip, wun_optim_step, wun_ema_update): ONE kernel steps the weights ------------
+// Every entry that steps weights launches optim_ranges_kernel over runs of consecutive arena floats; the entries differ only in
+// what they leave empty (gnorm: no clip prologue; decay bits; ema).  A float's update is the same expressions in the same order
+// whichever entry, selection or alignment reaches it, which is what makes a selected float bit-equal to the full step's, an
+// inactive clip bit-equal to the plain step and the extended step with nothing set bit-equal to TF-Adam (DESIGN.md 5.5, 5.7,
+// 5.26).  The whole arena is the one run of all its tensors (they are packed end to end): no float outside it is touched.
+//
+// The clip: gi = g * gscale, times clip / N only when N > clip.  A skipped step (skip != 0, N not finite) returns before any
+// p / m / v access; block 0's first lane counts it.
 struct AdamClip { bool clipping; float cs; };
 // false: the step is skipped
 __device__ __forceinline__ bool adam_clip_prologue(const float* __restrict__ gnorm, float clip, int skip, long long* skipped,
@@ -1106,55 +1055,11 @@ __device__ __forceinline__ bool adam_clip_prologue(const float* __restrict__ gno
 }
 __device__ __forceinline__ float adam_clipped(float gi, const AdamClip& c) { return c.clipping ? gi * c.cs : gi; }
 
-__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, long long n, float lr_t, float b1, float b2, float eps, float gscale,
-                                 const float* __restrict__ gnorm, float clip, int skip, long long* skipped) {
-    AdamClip c;
-    if (!adam_clip_prologue(gnorm, clip, skip, skipped, c)) return;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        adam_update(p, m, v, i, adam_clipped(g[i] * gscale, c), lr_t, b1, b2, eps);
-}
-
-hipError_t launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr_t, float b1, float b2,
-                            float eps, float gscale, const float* gnorm, float clip, int skip, long long* skipped,
-                            hipStream_t s) {
-    ProfScope ps("adam_clip_kernel", 0.0, s, "", 28.0 * (double)n);
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, n, lr_t, b1, b2, eps, gscale,
-                       gnorm, clip, skip, skipped);
-    return hipGetLastError();
-}
-
-__global__ void adam_clip_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                        float* __restrict__ v, AdamRanges r, float lr_t, float b1, float b2, float eps,
-                                        float gscale, const float* __restrict__ gnorm, float clip, int skip,
-                                        long long* skipped) {
-    AdamClip c;
-    if (!adam_clip_prologue(gnorm, clip, skip, skipped, c)) return;
-    const long long total = r.cum[r.n];
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const long long i = adam_range_index(r, t);
-        adam_update(p, m, v, i, adam_clipped(g[i] * gscale, c), lr_t, b1, b2, eps);
-    }
-}
-
-hipError_t launch_adam_clip_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t, float b1,
-                                   float b2, float eps, float gscale, const float* gnorm, float clip, int skip,
-                                   long long* skipped, hipStream_t s) {
-    const long long n = r.n > 0 ? r.cum[r.n] : 0;
-    if (n <= 0) return hipSuccess;
-    ProfScope ps("adam_clip_ranges_kernel", 0.0, s, "", 28.0 * (double)n);
-    hipLaunchKernelGGL(adam_clip_ranges_kernel, dim3(adam_grid(n)), dim3(256), 0, s, p, g, m, v, r, lr_t, b1, b2, eps,
-                       gscale, gnorm, clip, skip, skipped);
-    return hipGetLastError();
-}
-
-// ---- the extended optimizer (wun_optim_step, wun_ema_update): decoupled weight decay and an EMA of the weights, fused --------
-// One kernel over the selected runs: a float's g, clip scale, m and v are adam_update's / adam_clipped's expressions in their
-// order, theta is decayed first when its run decays (one product, rounded), then takes wun_adam_step's step, and the EMA moves
-// towards the NEW theta (tf assign_moving_average: ema -= (1 - d) (ema - theta), difference, product and difference each
-// rounded -- no fused multiply-add anywhere the formula has none).  20 bytes read and 16 written per float with all five arrays:
-// 16-byte loads and stores from each piece's first 16-byte aligned float when the arenas share one alignment (a.vec), the head and
-// the tail -- or the whole piece -- by single floats through the same optim_one, so the bits do not depend on the alignment.
+// One float's step.  The fused multiply-adds of mi and vi (decayed term fused, gradient term rounded first) are written out and
+// contraction is off: left to -ffp-contract, which of a sum's two products is fused is the compiler's choice per call site, and
+// that choice is a rounding.  theta is decayed first when its run decays (one product, rounded), then takes the TF-Adam step,
+// and the EMA moves towards the NEW theta (tf assign_moving_average: ema -= (1 - d) (ema - theta), difference, product and
+// difference each rounded -- no fused multiply-add anywhere the formula has none).
 __device__ __forceinline__ void optim_one(float gi, float& pi, float& mi, float& vi, float& ei, const OptimArgs& a, bool decay,
                                           bool ema) {
 #pragma clang fp contract(off)
@@ -1200,74 +1105,77 @@ __device__ __forceinline__ OptimCut optim_cut(const float* first, int len, int v
     return c;
 }
 
+// The workgroup's share of the runs: one(k, i) for every float i of a piece's head and tail (lane t takes the t-th of them, head
+// first), quad(k, i) for every 16-byte group between them (lane t the t-th group), k the piece's run.  base: an arena whose
+// alignment the others share when vec is set.  Both kernels below go through it, so they visit the same floats the same way.
+template <class One, class Quad>
+__device__ __forceinline__ void for_each_float(const AdamRanges& r, const float* base, int vec, One one, Quad quad) {
+    const int t = threadIdx.x;
+    const long long nchunks = (r.cum[r.n] + WUN_OPTIM_CHUNK - 1) / WUN_OPTIM_CHUNK;
+    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+        for_each_piece(r, chunk, [&](int k, long long lo, int len) {
+            const OptimCut u = optim_cut(base + lo, len, vec);
+            for (int j = t; j < u.nsc; j += 256) one(k, lo + (j < u.head ? j : u.tail0 + (j - u.head)));
+            for (int j = t; j < u.nv; j += 256) quad(k, lo + u.head + 4 * j);
+        });
+    }
+}
+
+// 16 bytes read per float and 12 written, 20 and 16 with an EMA: 16-byte loads and stores from each piece's first 16-byte aligned
+// float when the arenas share one alignment (a.vec), the head and the tail -- or the whole piece -- by single floats through the
+// same optim_one, so the bits do not depend on the alignment.
 __global__ __launch_bounds__(256) void optim_ranges_kernel(OptimArgs a, AdamRanges r) {
     AdamClip c;
     c.clipping = false; c.cs = 1.f;
     if (a.gnorm && !adam_clip_prologue(a.gnorm, a.clip, a.skip, a.skipped, c)) return;
     const bool ema = a.ema != nullptr;
-    const int t = threadIdx.x;
-    const long long nchunks = (r.cum[r.n] + WUN_OPTIM_CHUNK - 1) / WUN_OPTIM_CHUNK;
-    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        for_each_piece(r, chunk, [&](int k, long long lo, int len) {
-            const OptimCut u = optim_cut(a.p + lo, len, a.vec);
+    for_each_float(r, a.p, a.vec,
+        [&](int k, long long i) {
+            float pi = a.p[i], mi = a.m[i], vi = a.v[i], ei = ema ? a.ema[i] : 0.f;
+            optim_one(adam_clipped(a.g[i] * a.gscale, c), pi, mi, vi, ei, a, (a.decay >> k) & 1u, ema);
+            a.m[i] = mi; a.v[i] = vi; a.p[i] = pi;
+            if (ema) a.ema[i] = ei;
+        },
+        [&](int k, long long i) {
             const bool decay = (a.decay >> k) & 1u;
-            for (int j = t; j < u.nsc; j += 256) {
-                const long long i = lo + (j < u.head ? j : u.tail0 + (j - u.head));
-                float pi = a.p[i], mi = a.m[i], vi = a.v[i], ei = ema ? a.ema[i] : 0.f;
-                optim_one(adam_clipped(a.g[i] * a.gscale, c), pi, mi, vi, ei, a, decay, ema);
-                a.m[i] = mi; a.v[i] = vi; a.p[i] = pi;
-                if (ema) a.ema[i] = ei;
-            }
-            for (int j = t; j < u.nv; j += 256) {
-                const long long i = lo + u.head + 4 * j;
-                const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.g + i);
-                f32x4 p4 = *reinterpret_cast<const f32x4*>(a.p + i);
-                f32x4 m4 = *reinterpret_cast<const f32x4*>(a.m + i);
-                f32x4 v4 = *reinterpret_cast<const f32x4*>(a.v + i);
-                f32x4 e4 = {0.f, 0.f, 0.f, 0.f};
-                if (ema) e4 = *reinterpret_cast<const f32x4*>(a.ema + i);
+            const f32x4 g4 = *reinterpret_cast<const f32x4*>(a.g + i);
+            f32x4 p4 = *reinterpret_cast<const f32x4*>(a.p + i);
+            f32x4 m4 = *reinterpret_cast<const f32x4*>(a.m + i);
+            f32x4 v4 = *reinterpret_cast<const f32x4*>(a.v + i);
+            f32x4 e4 = {0.f, 0.f, 0.f, 0.f};
+            if (ema) e4 = *reinterpret_cast<const f32x4*>(a.ema + i);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float pi = p4[q], mi = m4[q], vi = v4[q], ei = e4[q];
-                    optim_one(adam_clipped(g4[q] * a.gscale, c), pi, mi, vi, ei, a, decay, ema);
-                    p4[q] = pi; m4[q] = mi; v4[q] = vi; e4[q] = ei;
-                }
-                *reinterpret_cast<f32x4*>(a.m + i) = m4;
-                *reinterpret_cast<f32x4*>(a.v + i) = v4;
-                *reinterpret_cast<f32x4*>(a.p + i) = p4;
-                if (ema) *reinterpret_cast<f32x4*>(a.ema + i) = e4;
+            for (int q = 0; q < 4; ++q) {
+                float pi = p4[q], mi = m4[q], vi = v4[q], ei = e4[q];
+                optim_one(adam_clipped(g4[q] * a.gscale, c), pi, mi, vi, ei, a, decay, ema);
+                p4[q] = pi; m4[q] = mi; v4[q] = vi; e4[q] = ei;
             }
+            *reinterpret_cast<f32x4*>(a.m + i) = m4;
+            *reinterpret_cast<f32x4*>(a.v + i) = v4;
+            *reinterpret_cast<f32x4*>(a.p + i) = p4;
+            if (ema) *reinterpret_cast<f32x4*>(a.ema + i) = e4;
         });
-    }
 }
 
 // the EMA line alone (wun_ema_update): ema_one is optim_one's last line, so the bits are the fused path's for the same theta
 __global__ __launch_bounds__(256) void ema_ranges_kernel(float* ema, const float* p, float emaw, int vec, AdamRanges r) {
-    const int t = threadIdx.x;
-    const long long nchunks = (r.cum[r.n] + WUN_OPTIM_CHUNK - 1) / WUN_OPTIM_CHUNK;
-    for (long long chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        for_each_piece(r, chunk, [&](int, long long lo, int len) {
-            const OptimCut u = optim_cut(p + lo, len, vec);
-            for (int j = t; j < u.nsc; j += 256) {
-                const long long i = lo + (j < u.head ? j : u.tail0 + (j - u.head));
-                float ei = ema[i];
-                ema_one(p[i], ei, emaw);
-                ema[i] = ei;
-            }
-            for (int j = t; j < u.nv; j += 256) {
-                const long long i = lo + u.head + 4 * j;
-                const f32x4 p4 = *reinterpret_cast<const f32x4*>(p + i);
-                f32x4 e4 = *reinterpret_cast<const f32x4*>(ema + i);
+    for_each_float(r, p, vec,
+        [&](int, long long i) {
+            float ei = ema[i];
+            ema_one(p[i], ei, emaw);
+            ema[i] = ei;
+        },
+        [&](int, long long i) {
+            const f32x4 p4 = *reinterpret_cast<const f32x4*>(p + i);
+            f32x4 e4 = *reinterpret_cast<const f32x4*>(ema + i);
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float ei = e4[q];
-                    ema_one(p4[q], ei, emaw);
-                    e4[q] = ei;
-                }
-                *reinterpret_cast<f32x4*>(ema + i) = e4;
+            for (int q = 0; q < 4; ++q) {
+                float ei = e4[q];
+                ema_one(p4[q], ei, emaw);
+                e4[q] = ei;
             }
+            *reinterpret_cast<f32x4*>(ema + i) = e4;
         });
-    }
 }
 
 // one workgroup per chunk of WUN_OPTIM_CHUNK floats (four per thread), at most 2048 workgroups (eight per CU), grid-strided beyond

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <initializer_list>
 #include <string>
 
 namespace wun {
@@ -336,14 +337,9 @@ hipError_t launch_blend_runs(const float* outputs, float* preds, float* den, con
 hipError_t launch_blend_finish(float* preds, const float* den, int S, long long pred_frames, int C, hipStream_t s);
 hipError_t launch_make_wt(const float* params, float* ws, const WtDesc* dev_descs, int ndesc,
                           int max_elems, hipStream_t s);
-hipError_t launch_adam(float* p, const float* g, float* m, float* v, long long n, float lr_t,
-                       float b1, float b2, float eps, float gscale, hipStream_t s);
-// TF-Adam over selected runs of the arena (wun_adam_step_select): run k = floats [off[k], off[k] + cum[k+1] - cum[k]),
-// passed by value; the per-element arithmetic of adam_kernel
+// Runs of consecutive arena floats, passed by value to the optimizer's kernels: run k = floats [off[k], off[k] + cum[k+1] - cum[k])
 #define WUN_ADAM_RANGES 32
 struct AdamRanges { long long off[WUN_ADAM_RANGES]; long long cum[WUN_ADAM_RANGES + 1]; int n; };
-hipError_t launch_adam_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t,
-                              float b1, float b2, float eps, float gscale, hipStream_t s);
 // Gradient norm (wun_grad_norm): the arena cut into chunks of at most WUN_NORM_CHUNK floats that never cross a tensor
 // boundary (plan-owned device table, chunks of tensor k = [first[k], first[k+1])); one float64 sum of squares per chunk,
 // then per tensor and over the selected tensors, in a fixed order (no atomics: bitwise reproducible, grid-independent).
@@ -354,18 +350,23 @@ struct NormSelect { unsigned bits[WUN_NORM_MAX_TENSORS / 32]; };       // by val
 hipError_t launch_grad_norm(const float* g, const NormChunk* chunks, const int* first, int nchunks, int ntensors,
                             const NormSelect& sel, long long nfloats, float gscale, float* norms, double* partial,
                             hipStream_t s);
-// adam_kernel / adam_ranges_kernel on the gradient clipped by the global norm *gnorm (device): gi *= clip / N when N > clip;
-// skip != 0 and N not finite: nothing written, *skipped += 1 (when non-null) by one lane
-hipError_t launch_adam_clip(float* p, const float* g, float* m, float* v, long long n, float lr_t, float b1, float b2,
-                            float eps, float gscale, const float* gnorm, float clip, int skip, long long* skipped,
-                            hipStream_t s);
-hipError_t launch_adam_clip_ranges(float* p, const float* g, float* m, float* v, const AdamRanges& r, float lr_t, float b1,
-                                   float b2, float eps, float gscale, const float* gnorm, float clip, int skip,
-                                   long long* skipped, hipStream_t s);
-// The extended optimizer over selected runs (wun_optim_step): adam_clip_ranges_kernel's gradient, m and v; theta times wdf
-// first in the runs whose bit of `decay` is set, then wun_adam_step's step; ema (may be null) -= emaw * (ema - new theta).
-// gnorm null: no clip prologue (nothing clips, nothing skips).  vec: the arenas share one alignment modulo 16 bytes, so the
-// 16-byte path may run; the bits are the scalar path's.
+// The optimizer step over runs (every Adam entry, wun_optim_step, wun_spec_adam_step): gi = g * gscale, times clip / N when the
+// global norm N = *gnorm (device) > clip; m and v by TF-Adam; theta times wdf first in the runs whose bit of `decay` is set,
+// then the step of size lr_t; ema (may be null) -= emaw * (ema - new theta).  skip != 0 and N not finite: nothing written,
+// *skipped += 1 (when non-null) by one lane.  gnorm null: no clip prologue (nothing clips, nothing skips).  vec: the arenas
+// share one alignment modulo 16 bytes (same_alignment), so the 16-byte path may run; the bits are the scalar path's.
+float adam_lr_t(int64_t step, float lr, float beta1, float beta2);      // TF-Adam's step size (wun_optim.hip)
+static inline bool same_alignment(std::initializer_list<const void*> ptrs) {       // null pointers do not count
+    uintptr_t a = 0;
+    bool have = false;
+    for (const void* q : ptrs) {
+        if (!q) continue;
+        const uintptr_t x = reinterpret_cast<uintptr_t>(q) & 15;
+        if (have && x != a) return false;
+        a = x; have = true;
+    }
+    return true;
+}
 struct OptimArgs {
     float* p; const float* g; float* m; float* v; float* ema;
     float lr_t, b1, b2, eps, gscale, wdf, emaw;

@@ -645,61 +645,27 @@ class UnetAudioSeparator(object):
     def adam_step(self, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, variables=None, clip_norm=None,
                   skip_nonfinite=False, weight_decay=0.0, decay_variables=None, ema_decay=None, ema_warmup=False):
         """tf.train.AdamOptimizer(learning_rate=lr) update (Training.py:77) + global_step += 1.  variables: TF variable names
-        to update, as minimize(loss, var_list=...) does (None = all); params, m and v of every other tensor stay as they are
-        (wun_adam_step_select).
+        to update, as minimize(loss, var_list=...) does (None = all); params, m and v of every other tensor stay as they are.
 
         clip_norm: tf.clip_by_global_norm(grads, clip_norm) first, the global norm taken over the updated variables' gradients
         (times grad_scale).  skip_nonfinite: when that norm is not finite, params, m and v are left as they are and
-        skipped_steps grows by one (global_step still advances, as TF's does per sess.run).  With either set the update is
-        wun_adam_step_clip and the global norm is returned (0-dim GPU tensor, no host sync); otherwise None.
+        skipped_steps grows by one (global_step still advances, as TF's does per sess.run).  With either set the global
+        norm is returned (0-dim GPU tensor, no host sync); otherwise None.
 
         weight_decay: torch.optim.AdamW's decoupled decay, theta *= 1 - lr * weight_decay before the Adam step, on
         decay_variables (None = every conv kernel -- tensors of rank > 1 -- and no bias) among the updated variables.
         ema_decay: self.ema -= (1 - d_t) (self.ema - new theta) in the same pass (tf.train.ExponentialMovingAverage; the EMA
         arena starts as a copy of params); ema_warmup: d_t = min(ema_decay, (1 + step) / (10 + step)).  A skipped step
-        leaves the EMA alone too.  With any of the four set the update is wun_optim_step; params, m and v
-        are bit-equal to the calls above when weight_decay is 0.  With all four at their defaults: exactly the calls above."""
+        leaves the EMA alone too.
+
+        Every combination is one wun_optim_step call.  With the last four at their defaults params, m and v
+        have the same bits as wun_adam_step / wun_adam_step_select / wun_adam_step_clip give: all of them run one kernel."""
         self._refuse_in_ema("adam_step")
-        norm = self._adam_step(lr, beta1, beta2, eps, grad_scale, variables, clip_norm, skip_nonfinite, weight_decay,
-                               decay_variables, ema_decay, ema_warmup)
-        self._step_phase = 0                    # (only once the update was accepted: a refused call leaves the gradients pending)
-        return norm
-
-    def _adam_step(self, lr, beta1, beta2, eps, grad_scale, variables, clip_norm, skip_nonfinite, weight_decay, decay_variables,
-                   ema_decay, ema_warmup):
         mask = self.select_mask(variables)
-        if weight_decay or decay_variables is not None or ema_decay is not None or ema_warmup:
-            return self._optim_step(lr, beta1, beta2, eps, grad_scale, mask, clip_norm, skip_nonfinite, weight_decay,
-                                    decay_variables, ema_decay, ema_warmup)
-        if clip_norm is not None or skip_nonfinite:
-            clip = check_clip_norm(clip_norm)
-            ws, skipped = self._norm_buffers()
-            self.global_step += 1
-            _lib.check(self._lib.wun_adam_step_clip(
-                self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
-                self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
-                grad_scale, clip, _lib.WUN_CLIP_SKIP_NONFINITE if skip_nonfinite else 0, ws.data_ptr(),
-                skipped.data_ptr(), self._stream(), *self._mask_arg(mask)))
-            return ws[len(self._active.tensors)].clone()
-        self.global_step += 1
-        if mask is None:
-            _lib.check(self._lib.wun_adam_step(
-                self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
-                self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
-                grad_scale, self._stream()))
-            return
-        _lib.check(self._lib.wun_adam_step_select(
-            self._active.handle, self.params.data_ptr(), self.grads.data_ptr(),
-            self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.global_step, lr, beta1, beta2, eps,
-            grad_scale, self._stream(), *self._mask_arg(mask)))
-
-    def _optim_step(self, lr, beta1, beta2, eps, grad_scale, mask, clip_norm, skip_nonfinite, weight_decay, decay_variables,
-                    ema_decay, ema_warmup):
-        """adam_step's extended form: one wun_optim_step call."""
-        wd = check_weight_decay(weight_decay)
+        wd = check_weight_decay(weight_decay) if weight_decay else 0.0
         if ema_warmup and ema_decay is None:
             raise ValueError("ema_warmup needs ema_decay")
-        dmask = self.decay_mask(decay_variables)
+        dmask = self.decay_mask(decay_variables) if wd or decay_variables is not None else None      # (no decay: no table)
         ema = None
         if ema_decay is not None:
             ema_decay = check_ema_decay(ema_decay)
@@ -716,6 +682,7 @@ class UnetAudioSeparator(object):
             self.adam_v.data_ptr(), ema.data_ptr() if ema is not None else None, self.global_step, lr, grad_scale,
             C.byref(cfg), ws.data_ptr() if ws is not None else None, skipped.data_ptr() if skipped is not None else None,
             self._stream(), *self._mask_arg(mask), *self._mask_arg(dmask)))
+        self._step_phase = 0                    # (only once the update was accepted: a refused call leaves the gradients pending)
         return ws[len(self._active.tensors)].clone() if need_norm else None
 
     def _norm_buffers(self):

@@ -58,8 +58,8 @@ class Trainer(object):
 
     clip_grad_norm / skip_nonfinite (or model_config["clip_grad_norm"] / ["skip_nonfinite_steps"], default off): each Adam
     update clips by the global norm of the gradient it applies -- after the all-reduce, times the all-reduce's scale / k, so
-    every rank sees the same bits -- and skips the update when that norm is not finite (wun_adam_step_clip).  Off: exactly
-    the old calls.
+    every rank sees the same bits -- and skips the update when that norm is not finite (adam_step's clip_norm /
+    skip_nonfinite).  Off: the plain update's bits.
 
     spectral_loss (or model_config["spectral_loss"], default None): a dict with `resolutions` [[n_fft, hop], ...], `weights`
     and `mse_weight`, or a spectral.SpectralLoss -- the step then minimises mse_weight * MSE + sum_j weight_j * (STFT-magnitude
