@@ -546,6 +546,54 @@ int wun_loudness_gain(const double* meter, double target_lufs, double max_gain_d
  * count < 1. */
 int wun_scale_by(float* x, int64_t count, const float* gain, void* stream);
 
+/* ---- the rest of an EBU R 128 meter: true peak, short-term loudness, loudness range ----
+ * The contract of the section above holds: the caller's buffers, scratch sized by a *_scratch_doubles query, no
+ * allocation, no host synchronisation, no atomics, every argument check before any GPU work.
+ *
+ * Oversampling factor: the smallest power of two L in 1..32 with L * sr >= 176400 (192 k: 1, 96 k: 2, 48 k and
+ * 44.1 k: 4, 22.05 k: 8, 8 k: 32).  Negative wun_status for sr outside 4000..384000. */
+int32_t wun_true_peak_factor(int32_t sr);
+
+/* float64 elements of `scratch` for wun_true_peak: one partial per channel and workgroup of 1024 frames. */
+int64_t wun_true_peak_scratch_doubles(int64_t n, int32_t C);
+
+/* True peak: max over t, c of |r_c[t]|, r being BIT FOR BIT what wun_resample writes for up = L, down = 1 per channel
+ * (no channel mapping), all n L outputs: with the table of wun_resample_design(L, 1) on the device (K = 21 taps per
+ * phase), u = t + 10 L, q = u / L, p = u % L, acc = fmaf(table[p K + k], x[q - k], acc) for k ascending from +0, x = +0
+ * outside the input.  r is never written.  L == 1: r = x, the sample peak; table_dev may be NULL then.
+ *   out : device float64 [1 + C]: the overall maximum, then one per channel, each holding a float32 value exactly.  A NaN
+ *         SAMPLE in a channel makes that channel's and the overall value NaN; the NaNs an infinite sample makes of r are
+ *         dropped by the maximum, which is then +inf.
+ * The interpolator is this project's resampler -- scipy.signal.resample_poly's default Kaiser design -- NOT the 48-tap
+ * table of BS.1770-4 Annex 2; no bound on the under-read is claimed.  WUN_ERR_INVALID also for an L that is not a power
+ * of two in 1..32 or a null table with L > 1. */
+int wun_true_peak(const float* x, int64_t n, int32_t C, int32_t L, const float* table_dev, double* out, double* scratch,
+                  void* stream);
+
+/* Host: complete short-term blocks of n frames at sr: N3 = round(3 sr) frames at the meter's step round(0.1 sr) (halves
+ * up, in integers); (n - N3) / step + 1 for n >= N3, else 0.  Negative wun_status for n < 1 or sr out of range. */
+int64_t wun_loudness_short_term_blocks(int64_t n, int32_t sr);
+
+/* float64 elements of `scratch` for wun_loudness_r128.  Negative wun_status for bad arguments. */
+int64_t wun_loudness_r128_scratch_doubles(int64_t n, int32_t C, int32_t sr);
+
+/* The R 128 readings of x in one call.  The K-weighting schedule runs ONCE; its third pass adds every y[t]^2 into the
+ * 0.4 s pieces exactly as wun_loudness does and into a second set of pieces cut at the 3 s blocks' starts and ends.
+ *   z3_j = sum_c (sum_t y_c[t]^2) / N3 over short-term block j (the order of z_j above);  s_j = -0.691 + 10 log10 z3_j
+ *   range: absolute gate s_j > -70, relative gate s_j > (-0.691 + 10 log10 mean of the absolute-gated z3) - 20; the m
+ *          values that pass sorted ascending (ties by block index) as v:
+ *          LRA = v[((m - 1) 95 + 50) / 100] - v[((m - 1) 10 + 50) / 100] (integer division), 0 for m == 0, NaN with a
+ *          NaN block.  The two ranks are selected on the device by counting, m^2 comparisons, without sorting.
+ *   report     : device float64 [8]: integrated loudness, loudness range, largest momentary value l_j, largest short-term
+ *                value s_j (both -inf with no complete block), true peak (L = wun_true_peak_factor(sr)), sample peak,
+ *                gating blocks kept, short-term blocks kept (m).  Integrated loudness, sample peak and gating blocks
+ *                kept are wun_loudness's bits for the same input.
+ *   short_term : device float64 [wun_loudness_short_term_blocks] the s_j, or NULL
+ *   table_dev  : wun_resample_design(L, 1) on the device; may be NULL when L == 1
+ * WUN_ERR_INVALID also for sr outside 4000..384000; WUN_ERR_UNSUPPORTED above 2^20 short-term blocks (29 hours). */
+int wun_loudness_r128(const float* x, int64_t n, int32_t C, int32_t sr, const float* table_dev, double* report,
+                      double* short_term, double* scratch, void* stream);
+
 /* ---- spectral training loss: STFT-magnitude L1 and its waveform gradient ----
  * The reference's other objective (Training.py:55-60): the L1 distance between STFT magnitudes, frame 1024, hop 768,
  * periodic Hann window, no padding -- here for up to 8 resolutions at once, next to the time-domain MSE.

@@ -31,7 +31,8 @@ phase; the refined audio is normalised by the window-square sum over the coverin
 `overlap=0.25 shifts=4` (predict, evaluate; or model_config.separation={"overlap":0.25,"shifts":4}) lets neighbouring hops share a
 quarter of a hop, cross-faded, and averages 4 passes whose hop grids are shifted by 0 .. max_shift frames (max_shift=<frames>,
 default expected_sr // 2; shifts=[0,3,700] names the offsets): about shifts / (1 - overlap) times the forward passes.
-`loudness=-23` (predict, evaluate; or `loudness={"target":-23,"max_gain_db":30,"peak_limit":0.99,"restore":True}`, or
+`loudness=-23` (predict, evaluate; or `loudness={"target":-23,"max_gain_db":30,"peak_limit":0.99,"restore":True}`, with
+`"true_peak_limit":-1` instead of peak_limit for a ceiling in dBTP on the oversampled peak, or
 model_config.loudness=...) meters the mix at the model's rate (BS.1770-4 integrated loudness, on the GPU), scales it to that
 many LUFS before the network and scales the estimates back; `model_config.loudness={"target":-23,"data":True}` makes `train` and
 `test` scale every track's mix and stems by the gain of its mix when the tracks are loaded.

@@ -149,6 +149,12 @@ _SIGS = {
     "wun_loudness": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "wun_loudness_gain": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _P, _P]),
     "wun_scale_by": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "wun_true_peak_factor": (C.c_int32, [C.c_int32]),
+    "wun_true_peak_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32]),
+    "wun_true_peak": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "wun_loudness_short_term_blocks": (C.c_int64, [C.c_int64, C.c_int32]),
+    "wun_loudness_r128_scratch_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "wun_loudness_r128": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     "wun_stft_frames": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "wun_stft_table_floats": (C.c_int64, [C.c_int32]),
     "wun_stft_design": (C.c_int, [C.c_int32, C.POINTER(C.c_float), C.c_int64]),

@@ -69,7 +69,8 @@ EXTENSION_DEFAULTS = {
     # arrives; else a target in LUFS or {"target": -23.0, "max_gain_db": 30.0, "peak_limit": None, "restore": True,
     # "data": False} (any subset): the resampled mix is metered (BS.1770-4 integrated loudness) and scaled to the target before
     # the network, the estimates scaled back unless "restore" is False; "data": True makes train / test scale every track's mix
-    # and stems by the gain of its mix at load (datasets.normalize_tracks)
+    # and stems by the gain of its mix at load (datasets.normalize_tracks); one more key, "true_peak_limit" (dBTP, e.g. -1.0,
+    # instead of "peak_limit"), meters with loudness.r128 and keeps the TRUE peak of the scaled mix under it
     "loudness": None,
     # spectrogram.UnetSpectrogramSeparator: the STFT framing of the spectrogram U-Net (UnetSpectrogramSeparator.py:28-29 fixes
     # 1024 / 768); other values exist so that tests can run small geometries

@@ -5,6 +5,9 @@
 //                      y[t] = b0 x[t] + b1 x[t-1] + b2 x[t-2] - a1 y[t-1] - a2 y[t-2]      (float64, rounded once to float32)
 //   loudness           K-weighting (two sections), mean squares over blocks of 0.4 s at a step of 0.1 s, absolute gate at
 //                      -70 LUFS, relative gate 10 LU under the absolute-gated mean; the filtered signal is never written
+//   R 128              the other figures of that meter (wun_true_peak, wun_loudness_r128): the true peak as the
+//                      maximum of the resampler's oversampled output, never written; 3 s short-term blocks from the same walk
+//                      of the recurrence; the loudness range, its two ranks selected by counting
 //
 // A recurrence is serial in time, so the SCHEDULE is part of the definition (the bits must not depend on the grid): time is
 // cut into chunks of WUN_SOS_CHUNK frames, one lane per (chunk, channel).
@@ -86,7 +89,7 @@ __host__ __device__ __forceinline__ void loud_cuts(long long t0, long long t1, l
 
 __device__ __forceinline__ double nan_max(double a, double b) { return (a != a || b != b) ? (a + b) : (a > b ? a : b); }
 
-enum { SOS_END_STATE = 0, SOS_WRITE = 1, SOS_SQUARES = 2 };
+enum { SOS_END_STATE = 0, SOS_WRITE = 1, SOS_SQUARES = 2, SOS_SQUARES2 = 3 };    // SQUARES2: the 0.4 s and the 3 s pieces in one walk
 
 struct SosChunkArgs {
     const float* x; float* y;        // [n, C]; y: SOS_WRITE only
@@ -94,7 +97,8 @@ struct SosChunkArgs {
     double* grp;                     // [2 nsec][C][ngroups]: SOS_END_STATE writes the group ends, the other modes read the group starts
     double* pieces;                  // SOS_SQUARES: [3][C][nchunks] sums of squares of the chunk's pieces
     double* peak;                    // SOS_SQUARES: [C][nchunks] max |x| of the chunk (NaN if it holds one)
-    long long n, nchunks, ngroups, Nb, step;
+    double* pieces3;                 // SOS_SQUARES2: [3][C][nchunks] the same squares cut at the 3 s blocks' starts and ends
+    long long n, nchunks, ngroups, Nb, step, N3;
     SosCoef k;
     SosMat M;                        // the chunk transition
 };
@@ -174,11 +178,13 @@ __global__ __launch_bounds__(WUN_SOS_TILE * CH) void sos_chunk_kernel(SosChunkAr
                 }
         }
     }
-    long long c1 = 0, c2 = 0;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, pk = 0.0;
-    if (MODE == SOS_SQUARES) {
+    constexpr bool SQ = MODE == SOS_SQUARES || MODE == SOS_SQUARES2;
+    long long c1 = 0, c2 = 0, d1 = 0, d2 = 0;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, pk = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    if (SQ) {
         const long long t1 = t0 + WUN_SOS_CHUNK < p.n ? t0 + WUN_SOS_CHUNK : p.n;
         loud_cuts(t0, t1, p.Nb, p.step, c1, c2);
+        if (MODE == SOS_SQUARES2) loud_cuts(t0, t1, p.N3, p.step, d1, d2);
     }
 
     for (int sub = 0; sub < WUN_SOS_CHUNK / WUN_SOS_SUB; ++sub) {
@@ -198,11 +204,16 @@ __global__ __launch_bounds__(WUN_SOS_TILE * CH) void sos_chunk_kernel(SosChunkAr
                 const float xf = row[j * CH];
                 const double yv = sos_step(p.k, s, (double)xf);
                 if (MODE == SOS_WRITE) row[j * CH] = (float)yv;
-                if (MODE == SOS_SQUARES) {
+                if (SQ) {
                     if (t < c1) a0 = fma(yv, yv, a0);
                     else if (t < c2) a1 = fma(yv, yv, a1);
                     else a2 = fma(yv, yv, a2);
                     pk = nan_max(pk, fabs((double)xf));
+                }
+                if (MODE == SOS_SQUARES2) {                  // the same sample into the 3 s pieces: own sums, own cuts
+                    if (t < d1) s0 = fma(yv, yv, s0);
+                    else if (t < d2) s1 = fma(yv, yv, s1);
+                    else s2 = fma(yv, yv, s2);
                 }
             }
         }
@@ -233,11 +244,16 @@ __global__ __launch_bounds__(WUN_SOS_TILE * CH) void sos_chunk_kernel(SosChunkAr
             if (walk_ok) p.grp[((long long)wr * CH + wc) * p.ngroups + blockIdx.x] = v;
         }
     }
-    if (MODE == SOS_SQUARES && live) {
+    if (SQ && live) {
         p.pieces[((long long)0 * CH + c) * p.nchunks + kc] = a0;
         p.pieces[((long long)1 * CH + c) * p.nchunks + kc] = a1;
         p.pieces[((long long)2 * CH + c) * p.nchunks + kc] = a2;
         p.peak[(long long)c * p.nchunks + kc] = pk;
+    }
+    if (MODE == SOS_SQUARES2 && live) {
+        p.pieces3[((long long)0 * CH + c) * p.nchunks + kc] = s0;
+        p.pieces3[((long long)1 * CH + c) * p.nchunks + kc] = s1;
+        p.pieces3[((long long)2 * CH + c) * p.nchunks + kc] = s2;
     }
 }
 
@@ -271,10 +287,9 @@ __global__ __launch_bounds__(64) void sos_group_kernel(SosMat MG, int D, double*
 }
 
 // z_j of block j = sum over channels (ascending) of [sum of the block's pieces in ascending (chunk, piece) order] / Nb
-__global__ __launch_bounds__(WUN_LOUD_BLOCK) void loud_block_kernel(const double* __restrict__ pieces, double* __restrict__ z,
-                                                                    long long n, long long nchunks, long long nb, long long Nb,
-                                                                    long long step, int C) {
-    const long long j = (long long)blockIdx.x * WUN_LOUD_BLOCK + threadIdx.x;
+__device__ __forceinline__ void loud_block_body(const double* __restrict__ pieces, double* __restrict__ z, long long n,
+                                                long long nchunks, long long nb, long long Nb, long long step, int C,
+                                                long long j) {
     if (j >= nb) return;
     const long long s = j * step, e = s + Nb;
     double zj = 0.0;
@@ -294,6 +309,21 @@ __global__ __launch_bounds__(WUN_LOUD_BLOCK) void loud_block_kernel(const double
     z[j] = zj;
 }
 
+__global__ __launch_bounds__(WUN_LOUD_BLOCK) void loud_block_kernel(const double* __restrict__ pieces, double* __restrict__ z,
+                                                                    long long n, long long nchunks, long long nb, long long Nb,
+                                                                    long long step, int C) {
+    loud_block_body(pieces, z, n, nchunks, nb, Nb, step, C, (long long)blockIdx.x * WUN_LOUD_BLOCK + threadIdx.x);
+}
+
+// both window lengths in one launch: the first g workgroups sum the 0.4 s blocks, the others the 3 s blocks, one lane per block
+__global__ __launch_bounds__(WUN_LOUD_BLOCK) void loud_block2_kernel(const double* __restrict__ pieces, double* __restrict__ z,
+                                                                     long long nb, long long Nb, const double* __restrict__ pieces3,
+                                                                     double* __restrict__ z3, long long nb3, long long N3, long long n,
+                                                                     long long nchunks, long long step, int C, unsigned g) {
+    if (blockIdx.x < g) loud_block_body(pieces, z, n, nchunks, nb, Nb, step, C, (long long)blockIdx.x * WUN_LOUD_BLOCK + threadIdx.x);
+    else loud_block_body(pieces3, z3, n, nchunks, nb3, N3, step, C, (long long)(blockIdx.x - g) * WUN_LOUD_BLOCK + threadIdx.x);
+}
+
 // the fixed tree over the lanes of the one gating workgroup; every lane gets the total
 __device__ __forceinline__ double loud_tree(double* red, double v, int tid, bool is_max) {
     __syncthreads();
@@ -310,17 +340,23 @@ __device__ __forceinline__ double loud_lufs(double z) { return -0.691 + 10.0 * l
 
 // ONE workgroup: momentary values, both gates, the result and the peak.  Lane i adds the blocks i, i + 256, ... in ascending
 // order, then the tree adds the lanes.  A NaN block (a NaN or an infinity in x) makes L NaN: the gates alone would drop it.
-__global__ __launch_bounds__(WUN_LOUD_BLOCK) void loud_gate_kernel(const double* __restrict__ z, long long nb,
-                                                                   const double* __restrict__ peak, long long npeak,
-                                                                   double* __restrict__ meter, double* __restrict__ blocks) {
-    __shared__ double red[WUN_LOUD_BLOCK];
+// MOM: also the largest momentary value (-inf with no block, NaN with a NaN block) into *mom
+template <bool MOM>
+__device__ __forceinline__ void loud_gate_body(double* red, const double* __restrict__ z, long long nb,
+                                               const double* __restrict__ peak, long long npeak, double* __restrict__ meter,
+                                               double* __restrict__ blocks, double* __restrict__ mom) {
     const int tid = threadIdx.x;
-    double sum = 0.0, cnt = 0.0, bad = 0.0;
+    double sum = 0.0, cnt = 0.0, bad = 0.0, top = -HUGE_VAL;
     for (long long j = tid; j < nb; j += WUN_LOUD_BLOCK) {
         const double l = loud_lufs(z[j]);
         if (blocks) blocks[j] = l;
         if (l != l) bad = 1.0;
+        if (MOM) top = nan_max(top, l);
         if (l > -70.0) { sum += z[j]; cnt += 1.0; }
+    }
+    if (MOM) {
+        top = loud_tree(red, top, tid, true);
+        if (tid == 0) *mom = top;
     }
     sum = loud_tree(red, sum, tid, false);
     cnt = loud_tree(red, cnt, tid, false);
@@ -343,6 +379,220 @@ __global__ __launch_bounds__(WUN_LOUD_BLOCK) void loud_gate_kernel(const double*
         double L = cnt2 > 0.0 ? loud_lufs(sum2 / cnt2) : -HUGE_VAL;
         if (bad > 0.0) L = nan("");
         meter[0] = L; meter[1] = cnt2; meter[2] = (double)nb; meter[3] = pk;
+    }
+}
+
+__global__ __launch_bounds__(WUN_LOUD_BLOCK) void loud_gate_kernel(const double* __restrict__ z, long long nb,
+                                                                   const double* __restrict__ peak, long long npeak,
+                                                                   double* __restrict__ meter, double* __restrict__ blocks) {
+    __shared__ double red[WUN_LOUD_BLOCK];
+    loud_gate_body<false>(red, z, nb, peak, npeak, meter, blocks, nullptr);
+}
+
+// ---- EBU R 128: short-term gating, loudness range, true peak ----------------------------------------------
+#define WUN_TP_TILE 1024             // input frames per workgroup of the peak kernel
+#define WUN_TP_BLOCK 256
+#define WUN_TP_K 21                  // taps per phase of wun_resample_design(L, 1) for every L >= 2: ceil((20 L + 1) / L)
+#define WUN_TP_MAXL 32
+#define WUN_LRA_TILE 1024            // keys staged in LDS at a time by the selection kernel
+#define WUN_LRA_MAX_BLOCKS (1 << 20) // short-term blocks the quadratic selection accepts (29 hours)
+
+// st[0] = m, the short-term blocks past both gates; st[1] > 0: a NaN block; st[2] = the largest s_j.  key[j] = s_j for a
+// block that passes, +inf otherwise: what lra_select_kernel orders.  The gating sums as in loud_gate_body.
+__device__ __forceinline__ void st_gate_body(double* red, const double* __restrict__ z3, long long nb3, double* __restrict__ key,
+                                             double* __restrict__ short_term, double* __restrict__ st) {
+    const int tid = threadIdx.x;
+    double sum = 0.0, cnt = 0.0, bad = 0.0, top = -HUGE_VAL;
+    for (long long j = tid; j < nb3; j += WUN_LOUD_BLOCK) {
+        const double s = loud_lufs(z3[j]);
+        if (short_term) short_term[j] = s;
+        if (s != s) bad = 1.0;
+        top = nan_max(top, s);
+        if (s > -70.0) { sum += z3[j]; cnt += 1.0; }
+    }
+    top = loud_tree(red, top, tid, true);
+    sum = loud_tree(red, sum, tid, false);
+    cnt = loud_tree(red, cnt, tid, false);
+    bad = loud_tree(red, bad, tid, false);
+    const double gate = cnt > 0.0 ? loud_lufs(sum / cnt) - 20.0 : 0.0;
+    double m = 0.0;
+    for (long long j = tid; j < nb3; j += WUN_LOUD_BLOCK) {
+        const double s = loud_lufs(z3[j]);
+        const bool keep = cnt > 0.0 && s > -70.0 && s > gate;
+        key[j] = keep ? s : HUGE_VAL;
+        if (keep) m += 1.0;
+    }
+    m = loud_tree(red, m, tid, false);
+    if (tid == 0) { st[0] = m; st[1] = bad; st[2] = top; }
+}
+
+// workgroup 0: the meter of wun_loudness (+ the largest momentary value); workgroup 1: the short-term gating
+__global__ __launch_bounds__(WUN_LOUD_BLOCK) void r128_gate_kernel(const double* __restrict__ z, long long nb,
+                                                                   const double* __restrict__ peak, long long npeak,
+                                                                   double* __restrict__ meter, double* __restrict__ mom,
+                                                                   const double* __restrict__ z3, long long nb3,
+                                                                   double* __restrict__ key, double* __restrict__ short_term,
+                                                                   double* __restrict__ st) {
+    __shared__ double red[WUN_LOUD_BLOCK];
+    if (blockIdx.x == 0) loud_gate_body<true>(red, z, nb, peak, npeak, meter, nullptr, mom);
+    else st_gate_body(red, z3, nb3, key, short_term, st);
+}
+
+// The two ranks of the loudness range, without sorting: lane j counts the keys that order before its own by (value, index);
+// the counts of the m blocks that pass are a permutation of 0 .. m - 1, so exactly one lane holds each wanted rank and writes
+// its value.  No atomics, no host value; nb3^2 comparisons over the grid, the keys passing through LDS.
+__global__ __launch_bounds__(WUN_LOUD_BLOCK) void lra_select_kernel(const double* __restrict__ key, long long nb3,
+                                                                    const double* __restrict__ st, double* __restrict__ sel) {
+    __shared__ double tile[WUN_LRA_TILE];
+    const int tid = threadIdx.x;
+    const long long j = (long long)blockIdx.x * WUN_LOUD_BLOCK + tid;
+    const double kj = j < nb3 ? key[j] : HUGE_VAL;
+    long long before = 0;
+    for (long long i0 = 0; i0 < nb3; i0 += WUN_LRA_TILE) {
+        const int cnt = nb3 - i0 < WUN_LRA_TILE ? (int)(nb3 - i0) : WUN_LRA_TILE;
+        __syncthreads();
+        for (int i = tid; i < cnt; i += WUN_LOUD_BLOCK) tile[i] = key[i0 + i];
+        __syncthreads();
+        for (int i = 0; i < cnt; ++i) {
+            const double ki = tile[i];
+            before += (ki < kj || (ki == kj && i0 + i < j)) ? 1 : 0;
+        }
+    }
+    if (kj < HUGE_VAL) {
+        const long long m = (long long)st[0];
+        if (before == ((m - 1) * 10 + 50) / 100) sel[0] = kj;
+        if (before == ((m - 1) * 95 + 50) / 100) sel[1] = kj;
+    }
+}
+
+struct PeakArgs { const float* x; const float* taps; double* part; long long n; int L; };
+
+// max |r| of the signal oversampled by L, r never written: r[t] is wun_resample's output for up = L, down = 1 bit for bit --
+// u = t + 10 L, q = u / L = t / L + 10, p = u % L = t % L, acc = fmaf(taps[p K + k], v[q - k], acc) for k ascending, +0
+// outside the input.  A workgroup stages WUN_TP_TILE frames with their 10-frame halo on both sides and the table in LDS; a
+// lane takes a frame f, keeps the 21 samples v[f + 10 - k] in registers and walks the L phases of that frame.  A maximum
+// does not depend on the order: wave shuffles, then LDS, one partial per workgroup and channel (NaN when the channel holds a
+// NaN SAMPLE in the tile: the comparison drops the NaNs an infinity makes of r).  L == 1: r = x.
+template <int CL>
+__global__ __launch_bounds__(WUN_TP_BLOCK) void true_peak_kernel(PeakArgs a) {
+    constexpr int W = WUN_TP_TILE + WUN_TP_K - 1, H = (WUN_TP_K - 1) / 2;
+    __shared__ __attribute__((aligned(16))) float win[W * CL];
+    __shared__ float tab[WUN_TP_MAXL * WUN_TP_K];
+    __shared__ float red[(WUN_TP_BLOCK / 64) * CL];
+    __shared__ int redbad[(WUN_TP_BLOCK / 64) * CL];
+    const int tid = threadIdx.x;
+    const long long F0 = (long long)blockIdx.x * WUN_TP_TILE;
+    for (int i = tid; i < W * CL; i += WUN_TP_BLOCK) {
+        const long long m = F0 - H + i / CL;
+        win[i] = (m >= 0 && m < a.n) ? a.x[m * CL + i % CL] : 0.f;
+    }
+    if (a.L > 1)
+        for (int i = tid; i < a.L * WUN_TP_K; i += WUN_TP_BLOCK) tab[i] = a.taps[i];
+    __syncthreads();
+
+    float mx[CL];
+    bool bad[CL];
+#pragma unroll
+    for (int c = 0; c < CL; ++c) { mx[c] = 0.f; bad[c] = false; }
+    for (int fl = tid; fl < WUN_TP_TILE && F0 + fl < a.n; fl += WUN_TP_BLOCK) {
+        float v[WUN_TP_K][CL];
+#pragma unroll
+        for (int k = 0; k < WUN_TP_K; ++k) {
+            const int j = fl + WUN_TP_K - 1 - k;                 // window index of v[q - k]
+            if (CL == 2) {
+                const f32x2 w = *reinterpret_cast<const f32x2*>(win + 2 * j);
+                v[k][0] = w[0]; v[k][CL - 1] = w[1];
+            } else {
+                v[k][0] = win[j];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < CL; ++c)
+            if (v[H][c] != v[H][c]) bad[c] = true;               // v[H] is the frame's own sample
+        if (a.L == 1) {
+#pragma unroll
+            for (int c = 0; c < CL; ++c) {
+                const float r = fabsf(v[H][c]);
+                if (r > mx[c]) mx[c] = r;
+            }
+        } else {
+            for (int p = 0; p < a.L; ++p) {
+                const float* row = tab + p * WUN_TP_K;
+                float acc[CL];
+#pragma unroll
+                for (int c = 0; c < CL; ++c) acc[c] = 0.f;
+#pragma unroll
+                for (int k = 0; k < WUN_TP_K; ++k) {             // k ascending: the resampler's one accumulation order
+                    const float h = row[k];
+#pragma unroll
+                    for (int c = 0; c < CL; ++c) acc[c] = fmaf(h, v[k][c], acc[c]);
+                }
+#pragma unroll
+                for (int c = 0; c < CL; ++c) {
+                    const float r = fabsf(acc[c]);
+                    if (r > mx[c]) mx[c] = r;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < CL; ++c) {
+        for (int off = 32; off > 0; off >>= 1) {
+            const float o = __shfl_xor(mx[c], off);
+            if (o > mx[c]) mx[c] = o;
+        }
+        const int anybad = __any(bad[c] ? 1 : 0);
+        if ((tid & 63) == 0) { red[(tid >> 6) * CL + c] = mx[c]; redbad[(tid >> 6) * CL + c] = anybad; }
+    }
+    __syncthreads();
+    if (tid < CL) {
+        float m = red[tid];
+        int b = redbad[tid];
+        for (int w = 1; w < WUN_TP_BLOCK / 64; ++w) {
+            const float o = red[w * CL + tid];
+            if (o > m) m = o;
+            b |= redbad[w * CL + tid];
+        }
+        a.part[(long long)blockIdx.x * CL + tid] = b ? nan("") : (double)m;
+    }
+}
+
+// the partials [nwg][C] of true_peak_kernel into per-channel maxima (tid 0: per_channel[c], when given) and the overall one
+__device__ __forceinline__ double tp_combine(double* red, const double* __restrict__ part, long long nwg, int C,
+                                             double* __restrict__ per_channel) {
+    const int tid = threadIdx.x;
+    double all = 0.0;
+    for (int c = 0; c < C; ++c) {
+        double pk = 0.0;
+        for (long long i = tid; i < nwg; i += WUN_LOUD_BLOCK) pk = nan_max(pk, part[i * C + c]);
+        pk = loud_tree(red, pk, tid, true);
+        if (per_channel && tid == 0) per_channel[c] = pk;
+        all = nan_max(all, pk);
+    }
+    return all;
+}
+
+__global__ __launch_bounds__(WUN_LOUD_BLOCK) void true_peak_finish_kernel(const double* __restrict__ part, long long nwg, int C,
+                                                                         double* __restrict__ out) {
+    __shared__ double red[WUN_LOUD_BLOCK];
+    const double all = tp_combine(red, part, nwg, C, out + 1);
+    if (threadIdx.x == 0) out[0] = all;
+}
+
+// ONE workgroup: the true peak from its partials, the range from the two selected values, the rest copied
+__global__ __launch_bounds__(WUN_LOUD_BLOCK) void r128_report_kernel(const double* __restrict__ meter, const double* __restrict__ mom,
+                                                                    const double* __restrict__ st, const double* __restrict__ sel,
+                                                                    const double* __restrict__ part, long long nwg, int C,
+                                                                    double* __restrict__ report) {
+    __shared__ double red[WUN_LOUD_BLOCK];
+    const double tp = tp_combine(red, part, nwg, C, nullptr);
+    if (threadIdx.x == 0) {
+        const double m = st[0];
+        double lra = 0.0;
+        if (m > 0.0) lra = sel[1] - sel[0];
+        if (st[1] > 0.0) lra = nan("");
+        report[0] = meter[0]; report[1] = lra; report[2] = mom[0]; report[3] = st[2];
+        report[4] = tp; report[5] = meter[3]; report[6] = meter[1]; report[7] = m;
     }
 }
 
@@ -563,6 +813,160 @@ extern "C" int wun_loudness(const float* x, int64_t n, int32_t C, int32_t sr, do
                        blocks);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string("wun_loudness launch: ") + hipGetErrorString(e));
+    return WUN_OK;
+}
+
+// ---- EBU R 128 ------------------------------------------------------------------------------------------
+namespace {
+
+int check_rate(const char* who, int32_t sr) {
+    if (sr < 4000 || sr > 384000) return fail(WUN_ERR_INVALID, std::string(who) + ": sample rate outside 4000..384000 Hz");
+    return WUN_OK;
+}
+
+int32_t peak_factor(int32_t sr) {
+    int32_t L = 1;
+    while (L < WUN_TP_MAXL && (int64_t)L * sr < 176400) L *= 2;
+    return L;
+}
+
+bool peak_factor_ok(int32_t L) { return L >= 1 && L <= WUN_TP_MAXL && (L & (L - 1)) == 0; }
+
+int64_t peak_groups(int64_t n) { return (n + WUN_TP_TILE - 1) / WUN_TP_TILE; }
+
+void short_term_geometry(int32_t sr, int64_t n, int64_t* N3, int64_t* nb3) {
+    *N3 = ((int64_t)30 * sr + 5) / 10;                     // round(3 sr), halves up, as Nb is formed
+    const int64_t step = ((int64_t)sr + 5) / 10;
+    *nb3 = n >= *N3 ? (n - *N3) / step + 1 : 0;
+}
+
+void launch_peak(const float* x, int64_t n, int32_t C, int32_t L, const float* table_dev, double* part, hipStream_t s) {
+    PeakArgs a;
+    a.x = x; a.taps = table_dev; a.part = part; a.n = n; a.L = L;
+    const dim3 grid((unsigned)peak_groups(n)), blk(WUN_TP_BLOCK);
+    if (C == 2) hipLaunchKernelGGL(true_peak_kernel<2>, grid, blk, 0, s, a);
+    else hipLaunchKernelGGL(true_peak_kernel<1>, grid, blk, 0, s, a);
+}
+
+// the parts of wun_loudness_r128's scratch behind wun_loudness's own layout
+struct R128Layout { int64_t pieces3, z3, key, small, part, total; };      // small: meter [4], mom [1], st [3], sel [2]
+
+R128Layout r128_layout(int64_t n, int32_t C, int32_t sr) {
+    int64_t Nb, step, nb, N3, nb3;
+    block_geometry(sr, n, &Nb, &step, &nb);
+    short_term_geometry(sr, n, &N3, &nb3);
+    R128Layout l;
+    l.pieces3 = state_doubles(n, C, 2) + (int64_t)4 * C * n_chunks(n) + nb;
+    l.z3 = l.pieces3 + (int64_t)3 * C * n_chunks(n);
+    l.key = l.z3 + nb3;
+    l.small = l.key + nb3;
+    l.part = l.small + 10;
+    l.total = l.part + (int64_t)C * peak_groups(n);
+    return l;
+}
+
+}  // namespace
+
+extern "C" int32_t wun_true_peak_factor(int32_t sr) {
+    int rc;
+    if ((rc = check_rate("wun_true_peak_factor", sr))) return rc;
+    return peak_factor(sr);
+}
+
+extern "C" int64_t wun_true_peak_scratch_doubles(int64_t n, int32_t C) {
+    int rc;
+    if ((rc = check_audio("wun_true_peak_scratch_doubles", n, C))) return rc;
+    return (int64_t)C * peak_groups(n);
+}
+
+extern "C" int wun_true_peak(const float* x, int64_t n, int32_t C, int32_t L, const float* table_dev, double* out, double* scratch,
+                             void* stream) {
+    if (!x || !out) return fail(WUN_ERR_INVALID, "wun_true_peak: null argument");
+    int rc;
+    if ((rc = check_scratch("wun_true_peak", scratch))) return rc;
+    if (reinterpret_cast<uintptr_t>(out) % 8) return fail(WUN_ERR_INVALID, "wun_true_peak: out is not 8-byte aligned");
+    if ((rc = check_audio("wun_true_peak", n, C))) return rc;
+    if (!peak_factor_ok(L)) return fail(WUN_ERR_INVALID, "wun_true_peak: L is not a power of two in 1..32 (wun_true_peak_factor)");
+    if (L > 1 && !table_dev) return fail(WUN_ERR_INVALID, "wun_true_peak: null table (wun_resample_design(L, 1) on the device)");
+    if (L > 1 && wun_resample_table_floats(L, 1) != (int64_t)L * WUN_TP_K)
+        return fail(WUN_ERR_UNSUPPORTED, "wun_true_peak: the resampler's table no longer has 21 taps per phase");
+
+    hipStream_t s = (hipStream_t)stream;
+    launch_peak(x, n, C, L, table_dev, scratch, s);
+    hipLaunchKernelGGL(true_peak_finish_kernel, dim3(1), dim3(WUN_LOUD_BLOCK), 0, s, scratch, (long long)peak_groups(n), (int)C, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string("wun_true_peak launch: ") + hipGetErrorString(e));
+    return WUN_OK;
+}
+
+extern "C" int64_t wun_loudness_short_term_blocks(int64_t n, int32_t sr) {
+    if (n < 1) return fail(WUN_ERR_INVALID, "wun_loudness_short_term_blocks: n < 1");
+    int rc;
+    if ((rc = check_rate("wun_loudness_short_term_blocks", sr))) return rc;
+    int64_t N3, nb3;
+    short_term_geometry(sr, n, &N3, &nb3);
+    return nb3;
+}
+
+extern "C" int64_t wun_loudness_r128_scratch_doubles(int64_t n, int32_t C, int32_t sr) {
+    int rc;
+    if ((rc = check_audio("wun_loudness_r128_scratch_doubles", n, C))) return rc;
+    if ((rc = check_rate("wun_loudness_r128_scratch_doubles", sr))) return rc;
+    return r128_layout(n, C, sr).total;
+}
+
+extern "C" int wun_loudness_r128(const float* x, int64_t n, int32_t C, int32_t sr, const float* table_dev, double* report,
+                                 double* short_term, double* scratch, void* stream) {
+    if (!x || !report) return fail(WUN_ERR_INVALID, "wun_loudness_r128: null argument");
+    int rc;
+    if ((rc = check_scratch("wun_loudness_r128", scratch))) return rc;
+    if (reinterpret_cast<uintptr_t>(report) % 8 || reinterpret_cast<uintptr_t>(short_term) % 8)
+        return fail(WUN_ERR_INVALID, "wun_loudness_r128: report / short_term are not 8-byte aligned");
+    if ((rc = check_audio("wun_loudness_r128", n, C))) return rc;
+    double sos[12];
+    if ((rc = wun_kweight_design(sr, sos))) return rc;
+    const int32_t L = peak_factor(sr);
+    if (L > 1 && !table_dev) return fail(WUN_ERR_INVALID, "wun_loudness_r128: null table (wun_resample_design(L, 1) on the device)");
+    if (L > 1 && wun_resample_table_floats(L, 1) != (int64_t)L * WUN_TP_K)
+        return fail(WUN_ERR_UNSUPPORTED, "wun_loudness_r128: the resampler's table no longer has 21 taps per phase");
+    SosPlan p;
+    if ((rc = sos_plan("wun_loudness_r128", sos, 2, &p))) return rc;
+    int64_t Nb, step, nb, N3, nb3;
+    block_geometry(sr, n, &Nb, &step, &nb);
+    short_term_geometry(sr, n, &N3, &nb3);
+    if (nb3 > WUN_LRA_MAX_BLOCKS) return fail(WUN_ERR_UNSUPPORTED, "wun_loudness_r128: more than 2^20 short-term blocks");
+
+    hipStream_t s = (hipStream_t)stream;
+    const long long nch = n_chunks(n);
+    const R128Layout l = r128_layout(n, C, sr);
+    double* pieces = scratch + state_doubles(n, C, 2);                      // wun_loudness's layout, then the new parts
+    double* peak = pieces + (long long)3 * C * nch;
+    double* z = peak + (long long)C * nch;
+    double* pieces3 = scratch + l.pieces3;
+    double* z3 = scratch + l.z3;
+    double* key = scratch + l.key;
+    double* meter = scratch + l.small;
+    double* mom = meter + 4;
+    double* st = meter + 5;
+    double* sel = meter + 8;
+    double* part = scratch + l.part;
+    SosChunkArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.x = x; a.pieces = pieces; a.peak = peak; a.pieces3 = pieces3; a.Nb = Nb; a.step = step; a.N3 = N3;
+    if (C == 2) launch_schedule<2, SOS_SQUARES2>(p, a, n, scratch, s);
+    else launch_schedule<1, SOS_SQUARES2>(p, a, n, scratch, s);
+    const unsigned g = (unsigned)((nb + WUN_LOUD_BLOCK - 1) / WUN_LOUD_BLOCK), g3 = (unsigned)((nb3 + WUN_LOUD_BLOCK - 1) / WUN_LOUD_BLOCK);
+    if (g + g3 > 0)
+        hipLaunchKernelGGL(loud_block2_kernel, dim3(g + g3), dim3(WUN_LOUD_BLOCK), 0, s, pieces, z, (long long)nb, (long long)Nb,
+                           pieces3, z3, (long long)nb3, (long long)N3, (long long)n, nch, (long long)step, (int)C, g);
+    hipLaunchKernelGGL(r128_gate_kernel, dim3(2), dim3(WUN_LOUD_BLOCK), 0, s, z, (long long)nb, peak, (long long)C * nch, meter, mom,
+                       z3, (long long)nb3, key, short_term, st);
+    launch_peak(x, n, C, L, table_dev, part, s);
+    if (g3 > 0) hipLaunchKernelGGL(lra_select_kernel, dim3(g3), dim3(WUN_LOUD_BLOCK), 0, s, key, (long long)nb3, st, sel);
+    hipLaunchKernelGGL(r128_report_kernel, dim3(1), dim3(WUN_LOUD_BLOCK), 0, s, meter, mom, st, sel, part, (long long)peak_groups(n),
+                       (int)C, report);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(WUN_ERR_HIP, std::string("wun_loudness_r128 launch: ") + hipGetErrorString(e));
     return WUN_OK;
 }
 

@@ -129,7 +129,8 @@ def normalize_tracks(tracks, model_config, device, spec):
     """Loudness-normalised training data: every track's MIX is metered once on `device` at expected_sr
     (loudness.integrated, BS.1770-4), the gain to spec's target is computed there (loudness.gain) and read back -- the one host
     synchronisation per track, at load time -- and that one float32 factor multiplies the mix and every stem (one fp32 product
-    per sample, so the stems still sum to the mix as before up to that rounding).  spec: what loudness.from_config takes.
+    per sample, so the stems still sum to the mix as before up to that rounding).  spec: what loudness.from_config takes; with
+    its "true_peak_limit" the mix is metered by loudness.r128 and the gain keeps its true peak under the limit (5.28).
     Returns (new track dicts, float32 gains [len(tracks)]); the given tracks are left as they are.  GPU only."""
     import torch
     from . import loudness as ld
@@ -143,7 +144,8 @@ def normalize_tracks(tracks, model_config, device, spec):
     out, gains = [], np.zeros(len(tracks), np.float32)
     for i, track in enumerate(tracks):
         mix = torch.from_numpy(np.ascontiguousarray(track["mix"], np.float32)).to(device)
-        g = ld.gain(ld.integrated(mix, sr), spec["target"], spec["max_gain_db"], spec["peak_limit"])
+        meter, limit = ld.meter_for(mix, sr, spec)                              # true_peak_limit: r128, else integrated
+        g = ld.gain(meter, spec["target"], spec["max_gain_db"], limit)
         gains[i] = g[0:1].cpu().numpy()[0]                                      # the one sync of this track
         out.append({k: np.ascontiguousarray(np.asarray(v, np.float32) * gains[i]) for k, v in track.items()})
     return out, gains

@@ -194,7 +194,8 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     integrated loudness, loudness.integrated), the gain to the target is computed on the device (loudness.gain) and those
     frames are scaled in place; after the resampling back the estimates are scaled by the reciprocal factor in one launch
     unless the spec's "restore" is False.  A post-filter sees the scaled mix and the scaled estimates.  No value is read on
-    the host.  GPU separators only.  loudness_probe (a dict, for tests and tools) receives "meter" and "gain" (the device
+    the host.  With the spec's "true_peak_limit" (dBTP) the meter is loudness.r128 and the gain is capped so that the TRUE peak
+    of the scaled frames stays under it; without the key nothing new is called.  GPU separators only.  loudness_probe (a dict, for tests and tools) receives "meter" and "gain" (the device
     tensors) and "padded" (the scaled track the network read, with its context padding)."""
     from . import resample as rs
     loud = None
@@ -243,8 +244,8 @@ def separate_track(model_config, separator, mix_audio, mix_sr, batch_hops=16, ho
     gain = None
     if loud is not None:
         seen = padded[lead + pad:lead + pad + n_res]                             # what the network will see of the file
-        meter = ld.integrated(seen, int(model_config["expected_sr"]))
-        gain = ld.gain(meter, loud["target"], loud["max_gain_db"], loud["peak_limit"])
+        meter, limit = ld.meter_for(seen, int(model_config["expected_sr"]), loud)     # true_peak_limit: r128, else integrated
+        gain = ld.gain(meter, loud["target"], loud["max_gain_db"], limit)
         ld.scale_(seen, gain[0:1])
         if loudness_probe is not None:
             loudness_probe.update(meter=meter, gain=gain, padded=padded, offset=lead + pad, frames=n_res)

@@ -14,6 +14,8 @@ import torch
 from . import _lib
 
 KEYS = ("target", "max_gain_db", "peak_limit", "restore", "data")
+OPTIONAL_KEYS = ("true_peak_limit",)     # in the checked copy only when the caller gave them
+REPORT = ("integrated", "range", "max_momentary", "max_short_term", "true_peak", "sample_peak", "blocks_kept", "short_term_kept")
 DEFAULTS = {"target": -23.0, "max_gain_db": 30.0, "peak_limit": None, "restore": True, "data": False}
 
 
@@ -106,6 +108,88 @@ def integrated(x, sr, return_blocks=False, scratch=None):
     return (meter, blk) if return_blocks else meter
 
 
+def oversampling(sr):
+    """The true-peak oversampling factor at sr Hz: the smallest power of two L in 1..32 with L sr >= 176400
+    (wun_true_peak_factor)."""
+    v = int(_lib.load().wun_true_peak_factor(int(sr)))
+    if v < 0:
+        _lib.check(v)
+    return v
+
+
+def short_term_blocks(n, sr):
+    """Complete 3 s short-term blocks of n frames at sr, at the meter's 0.1 s step (wun_loudness_short_term_blocks)."""
+    v = int(_lib.load().wun_loudness_short_term_blocks(int(n), int(sr)))
+    if v < 0:
+        _lib.check(v)
+    return v
+
+
+def _peak_table(L, device):
+    from . import resample as rs
+    return rs._table(L, 1, device) if L > 1 else None
+
+
+def true_peak(x, sr, scratch=None):
+    """float64 device tensor [1 + C]: max |r| over all channels, then per channel, r being bit for bit the resampler's output
+    for up = oversampling(sr), down = 1 -- computed without writing r (wun_true_peak).  NaN where x holds one.  This project's
+    Kaiser interpolator, not the 48-tap table of BS.1770-4 Annex 2."""
+    n, Cc = _audio(x, "true_peak")
+    dev = x.device
+    L = oversampling(sr)
+    lib = _lib.load()
+    if scratch is None:
+        scratch = torch.empty(int(lib.wun_true_peak_scratch_doubles(n, Cc)), dtype=torch.float64, device=dev)
+    tab = _peak_table(L, dev)
+    out = torch.empty(1 + Cc, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.wun_true_peak(x.data_ptr(), n, Cc, L, tab.data_ptr() if tab is not None else None, out.data_ptr(),
+                                     scratch.data_ptr(), _stream(dev)))
+    return out
+
+
+def r128_scratch_doubles(n, Cc, sr):
+    v = int(_lib.load().wun_loudness_r128_scratch_doubles(int(n), int(Cc), int(sr)))
+    if v < 0:
+        _lib.check(v)
+    return v
+
+
+def r128(x, sr, return_short_term=False, scratch=None):
+    """The EBU R 128 readings of a float32 device tensor x [n, C] at sr Hz: a float64 device tensor [8] in the order of REPORT
+    -- integrated loudness, loudness range (LU), largest momentary and short-term loudness, true peak, sample peak, gating
+    blocks kept, short-term blocks kept (wun_loudness_r128; the first, sixth and seventh are integrated()'s bits).
+    return_short_term: also the short-term loudness of every 3 s block, float64 [short_term_blocks(n, sr)].  No host
+    synchronisation."""
+    n, Cc = _audio(x, "r128")
+    dev = x.device
+    if scratch is None:
+        scratch = torch.empty(r128_scratch_doubles(n, Cc, sr), dtype=torch.float64, device=dev)
+    tab = _peak_table(oversampling(sr), dev)
+    report = torch.empty(8, dtype=torch.float64, device=dev)
+    st = torch.empty(short_term_blocks(n, sr), dtype=torch.float64, device=dev) if return_short_term else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().wun_loudness_r128(x.data_ptr(), n, Cc, int(sr), tab.data_ptr() if tab is not None else None,
+                                                 report.data_ptr(), st.data_ptr() if st is not None and st.numel() else None,
+                                                 scratch.data_ptr(), _stream(dev)))
+    return (report, st) if return_short_term else report
+
+
+def meter_from_r128(report, n, sr):
+    """The [L, kept, nb, peak] tensor gain() reads, built on the device from r128()'s report with the TRUE peak in the peak
+    slot: gain(.., peak_limit=p) then holds the true peak of the scaled signal under p.  No value reaches the host."""
+    nb = torch.full((1,), float(blocks(n, sr)), dtype=torch.float64, device=report.device)
+    return torch.cat([report[0:1], report[6:7], nb, report[4:5]])
+
+
+def meter_for(x, sr, spec):
+    """(meter, peak_limit) for gain() under a checked spec: integrated() and the sample-peak limit, or -- with true_peak_limit
+    (dBTP) -- r128() with the true peak in the peak slot and the limit 10^(true_peak_limit / 20)."""
+    if spec.get("true_peak_limit") is None:
+        return integrated(x, sr), spec["peak_limit"]
+    return meter_from_r128(r128(x, sr), int(x.shape[0]), sr), 10.0 ** (spec["true_peak_limit"] / 20.0)
+
+
 def gain(meter, target=-23.0, max_gain_db=30.0, peak_limit=None):
     """float32 device tensor [2] = (g, 1 / g) from a meter of integrated(): g = 10^((target - L) / 20) capped at max_gain_db and,
     with peak_limit, at peak_limit / peak; exactly 1 when L is not finite (wun_loudness_gain)."""
@@ -134,16 +218,22 @@ def scale_(x, factor):
     return x
 
 
-def normalize(x, sr, target=-23.0, max_gain_db=30.0, peak_limit=None, inplace=False):
-    """(y, gain): x [n, C] scaled to `target` LUFS, and the float32 [2] factor pair of gain()."""
-    g = gain(integrated(x, sr), target, max_gain_db, peak_limit)
+def normalize(x, sr, target=-23.0, max_gain_db=30.0, peak_limit=None, inplace=False, true_peak_limit=None):
+    """(y, gain): x [n, C] scaled to `target` LUFS, and the float32 [2] factor pair of gain().  true_peak_limit (dBTP, instead
+    of peak_limit): the ceiling is on the true peak."""
+    if true_peak_limit is not None and peak_limit is not None:
+        raise ValueError("normalize: peak_limit and true_peak_limit are exclusive")
+    meter, limit = meter_for(x, sr, {"peak_limit": peak_limit, "true_peak_limit": true_peak_limit})
+    g = gain(meter, target, max_gain_db, limit)
     y = x if inplace else x.clone()
     return scale_(y, g[0:1]), g
 
 
 def from_config(spec):
     """model_config["loudness"] / separate_track's keyword checked and completed: None stays None; a number is the target; a
-    dict may hold target, max_gain_db, peak_limit, restore, data.  ValueError for anything else."""
+    dict may hold target, max_gain_db, peak_limit, restore, data and true_peak_limit (dBTP, a finite number such as -1.0: the
+    ceiling is then on the true peak, metered by r128(); not together with peak_limit; the key appears in the result only when
+    it was given).  ValueError for anything else."""
     if spec is None:
         return None
     if isinstance(spec, bool):
@@ -152,9 +242,9 @@ def from_config(spec):
         spec = {"target": float(spec)}
     if not isinstance(spec, dict):
         raise ValueError("loudness = %r: a target in LUFS or a dict expected" % (spec,))
-    unknown = set(spec) - set(KEYS)
+    unknown = set(spec) - set(KEYS) - set(OPTIONAL_KEYS)
     if unknown:
-        raise ValueError("loudness: unknown keys %s (have %s)" % (sorted(unknown), ", ".join(KEYS)))
+        raise ValueError("loudness: unknown keys %s (have %s)" % (sorted(unknown), ", ".join(KEYS + OPTIONAL_KEYS)))
     out = dict(DEFAULTS, **spec)
     for k in ("target", "max_gain_db"):
         if isinstance(out[k], bool) or not isinstance(out[k], (int, float, np.integer, np.floating)) or not math.isfinite(out[k]):
@@ -167,6 +257,13 @@ def from_config(spec):
         if isinstance(pl, bool) or not isinstance(pl, (int, float, np.integer, np.floating)) or not math.isfinite(pl) or pl <= 0:
             raise ValueError("loudness['peak_limit'] = %r must be a number > 0 or None" % (pl,))
         out["peak_limit"] = float(pl)
+    if "true_peak_limit" in out:
+        tp = out["true_peak_limit"]
+        if isinstance(tp, bool) or not isinstance(tp, (int, float, np.integer, np.floating)) or not math.isfinite(tp):
+            raise ValueError("loudness['true_peak_limit'] = %r must be a finite number of dBTP" % (tp,))
+        if pl is not None:
+            raise ValueError("loudness: peak_limit and true_peak_limit are exclusive (one ceiling, on the sample or the true peak)")
+        out["true_peak_limit"] = float(tp)
     for k in ("restore", "data"):
         if not isinstance(out[k], (bool, np.bool_)):
             raise ValueError("loudness[%r] = %r must be a bool" % (k, out[k]))
