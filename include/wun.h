@@ -1647,6 +1647,7 @@ int wun_op_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pit
 #define WUN_OP_HEAD_DFEAT        4   /* generic / four-position (d feature map of both head backward entries) */
 #define WUN_OP_CONV_EPILOGUE     5   /* fused / not fused (wun_op_set_conv_upsample, wun_op_conv1d_upsample_adjoint) */
 #define WUN_OP_BTC_TO_NCW        6   /* scalar / vec4 */
+#define WUN_OP_FIRST_CONV        7   /* WUN_PATH_FIRST_CONV once wun_op_first_conv has launched first_conv_kernel */
 #define WUN_PATH_NONE          0     /* no launch yet */
 #define WUN_PATH_SCALAR        1
 #define WUN_PATH_VEC4          2
@@ -1657,6 +1658,7 @@ int wun_op_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pit
 #define WUN_PATH_FOUR_POSITION 7
 #define WUN_PATH_NOT_FUSED     8
 #define WUN_PATH_FUSED         9
+#define WUN_PATH_FIRST_CONV    10
 int wun_op_last_path(int op);
 
 /* The bf16 mode's conv as a single operator (wun_op_conv1d semantics, Cin >= 8, K <= 15): x and w
@@ -1674,6 +1676,55 @@ int wun_op_conv1d_bf16(const float* x, const float* w, const float* bias, float*
 int64_t wun_op_conv1d_dgrad_bf16_scratch(int cin, int cout, int k);
 int wun_op_conv1d_dgrad_bf16(const float* dz, const float* w, float* dx, float* scratch, int batch, int cin,
                              int cout, int k, int t_in, int t_out, int stride, int pad_left, void* stream);
+
+/* Tile codes of the bf16 conv: wun_op_force_conv_variant(WUN_BF16_VARIANT_BASE + code, 0), code = (log2 MT) * 9 + (NW - 2) * 3 +
+ * (NCK - 1) in 0..26 (MT in {1, 2, 4} tiles of 16 positions per wave, NW in {2, 3, 4} column tiles, NCK in {1, 2, 3} chunks of
+ * 32 channels per stage), forces that tile on every following launch of the bf16 conv entries (wun_op_conv1d_bf16,
+ * wun_op_conv1d_dgrad_bf16, wun_op_conv_bf16_ex).  A code the launcher would refuse for the launch returns
+ * WUN_ERR_UNSUPPORTED before any GPU work.  The bf16 entries ignore forced variants below the base, the fp32 entries those at
+ * or above it. */
+#define WUN_BF16_VARIANT_BASE 1000
+
+/* The bf16 conv launch of the plan as a single operator, on bf16 rows THE CALLER made.  mode 0 / 1: the stride-1 / stride-2 conv
+ *   v[b][n][q] = bias[n] + sum_{k, c} w[k][c][n] x[b][c][q * stride + k - shift]      (zero outside [0, Tin), 0 <= q < Tout)
+ * over the virtual channel-concat of x0 [B][C0][x0_pitch] and x1 [B][C1][x1_pitch] (C1 = 0: x1 unused); w is fp32 [K][C0 + C1][N]
+ * (rounded to bf16 when it is packed).  mode 2: the input gradient of a valid stride-2 conv of K taps as the plan's fused
+ * two-phase launch (shift 0, C1 = 0, N0 = N, N % 4 == 0, no bias / lrelu / dec):
+ *   v[b][n][t] = sum_{k, m} w[k][n][m] x[b][m][(t - k) / 2]   (t - k even and inside [0, 2 Tin)),  w fp32 [K][N][C0], 0 <= t < Tout.
+ * The first element of every input row is x_off elements (even or odd) behind the row's start; the rest of the row, to its
+ * pitch, is never used (it is READ: dword pairs -- it must be addressable, its content is dropped).  x0 / x1: 16-byte aligned,
+ * even pitches.  Then lrelu (max(0.2 v, v)), mask (v *= mask > 0 ? 1 : 0.2; mask0 / mask1 have the geometry and type of y0 / y1,
+ * or NULL), accumulate (v += what the destination holds, at the row positions y_off + q inside [acc_lo, acc_lo + acc_len);
+ * acc_len = 0: everywhere), store: columns n < N0 to y0 [B][N0][y0_pitch] at y0_off + q, the others to y1 [B][N - N0][y1_pitch]
+ * at y1_off + q; dec (or NULL): dec[b][n][q >> 1] = the stored value at even q, n < N0, [B][N0][dec_pitch].  out_bf16: y0, y1,
+ * the masks and dec hold bf16 (one rounding to nearest even on the store), else fp32.  scratch: device floats, at least
+ * wun_op_conv_bf16_ex_scratch(desc).  Every check runs before any GPU work: WUN_ERR_INVALID for a null required pointer, a bad
+ * shape, a row that does not fit its pitch or a misaligned input; WUN_ERR_UNSUPPORTED for what the bf16 kernel does not serve
+ * (fewer than 8 channels, K > 15, odd pitches, C0 % 8 != 0 with two sources) and for a forced tile code the launcher refuses.
+ * Synchronises the stream. */
+typedef struct wun_op_conv_bf16_desc {
+    int32_t mode, B, C0, C1, N, N0, K, Tin, Tout, shift;
+    int32_t lrelu, out_bf16, accumulate, acc_lo, acc_len;
+    int32_t x0_pitch, x1_pitch, x_off;                           /* bf16 elements */
+    int32_t y0_pitch, y0_off, y1_pitch, y1_off, dec_pitch;       /* elements of the output type */
+} wun_op_conv_bf16_desc;
+int32_t wun_op_conv_bf16_abi_size(void);   /* sizeof(wun_op_conv_bf16_desc) */
+int64_t wun_op_conv_bf16_ex_scratch(const wun_op_conv_bf16_desc* desc);
+int wun_op_conv_bf16_ex(const wun_op_conv_bf16_desc* desc, const void* x0, const void* x1, const float* w, const float* bias,
+                        void* y0, void* y1, const void* mask0, const void* mask1, void* dec, float* scratch, void* stream);
+/* Host only, no GPU work: 1 when the launcher accepts tile `code` (0..26) for the launch `desc` describes, 0 when it refuses
+ * it (or the shape); negative for a null or malformed descriptor.  Pointers play no part (rows are taken as aligned). */
+int wun_op_conv_bf16_choice_ok(const wun_op_conv_bf16_desc* desc, int code);
+
+/* The audio-input conv of the bf16 mode (first_conv_kernel) as a single operator: fp32 x [B][cin][x_pitch] (cin 1 or 2), fp32 w
+ * [k][cin][cout], wun_op_conv1d semantics with stride 1 / 2, output y [B][cout][y_pitch] and the optional compact copy of the even
+ * positions dec [B][cout][dec_pitch] (dec[q >> 1] = y[q], even q < t_out) as bf16 (out_bf16) or fp32.  Refuses what the plan's
+ * launcher refuses (WUN_ERR_UNSUPPORTED: cin outside {1, 2}, k outside 1..15, y not 16-byte aligned, y_pitch % 4 != 0);
+ * WUN_ERR_INVALID for a null pointer, a shape below 1 or a pitch below its row.  Every check runs before any GPU work.
+ * wun_op_last_path(WUN_OP_FIRST_CONV) = WUN_PATH_FIRST_CONV afterwards. */
+int wun_op_first_conv(const float* x, const float* w, const float* bias, void* y, void* dec, int batch, int cin, int cout, int k,
+                      int t_in, int t_out, int stride, int pad_left, int lrelu, int out_bf16, int x_pitch, int y_pitch,
+                      int dec_pitch, void* stream);
 
 /* Lane layout probe of v_mfma_f32_16x16x32_bf16: d[16][16] = bf16(a[16][32]) * bf16(b[32][16]) (row-major). */
 int wun_op_mfma_bf16_probe(const float* a, const float* b, float* d, void* stream);

@@ -221,6 +221,22 @@ def test_integration_doc_stub_matches_the_binding(lib):
     assert len(init.split(",")) == len(fields)
 
 
+def test_op_descriptors_match_the_header(lib):
+    """The single-operator descriptors are passed by pointer: the binding's field lists are the header's, in its order, and
+    their sizes the ones the library was compiled with (wun_op_head_abi_size, wun_op_conv_bf16_abi_size)."""
+    hdr = open(os.path.join(ROOT, "include", "wun.h")).read()
+    for cname, cls, size in (("wun_op_head_desc", _lib.WunOpHeadDesc, lib.wun_op_head_abi_size()),
+                             ("wun_op_conv_bf16_desc", _lib.WunOpConvBf16Desc, lib.wun_op_conv_bf16_abi_size())):
+        body = hdr[hdr.index("typedef struct %s {" % cname):hdr.index("} %s;" % cname)]
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        names = []
+        for decl in re.findall(r"int32_t\s+([^;]+);", body):
+            names += [n.strip() for n in decl.split(",")]
+        assert names == [n for n, _ in cls._fields_], cname
+        assert all(t is C.c_int32 for _, t in cls._fields_)
+        assert size == 4 * len(names) == C.sizeof(cls), cname
+
+
 def test_c_caller_links_and_runs(tmp_path):
     """tests/abi_smoke.c: a plain C program against include/wun.h + libwun.so (no ctypes, no torch)."""
     import shutil

@@ -79,10 +79,19 @@ class WunOpHeadDesc(C.Structure):
         "mix_pitch", "feat_pitch", "dpre_pitch", "mix_off_feat", "mix_off_diff")]
 
 
+class WunOpConvBf16Desc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "mode", "B", "C0", "C1", "N", "N0", "K", "Tin", "Tout", "shift", "lrelu", "out_bf16", "accumulate", "acc_lo", "acc_len",
+        "x0_pitch", "x1_pitch", "x_off", "y0_pitch", "y0_off", "y1_pitch", "y1_off", "dec_pitch")]
+
+
+BF16_VARIANT_BASE = 1000                            # WUN_BF16_VARIANT_BASE: wun_op_force_conv_variant(base + tile code, 0)
+
 # wun_op_last_path: operators and forms (WUN_OP_*, WUN_PATH_* of include/wun.h)
 (OP_UPSAMPLE, OP_UPSAMPLE_BACKWARD, OP_INTERP_GRAD, OP_HEAD_FORWARD, OP_HEAD_DFEAT, OP_CONV_EPILOGUE, OP_BTC_TO_NCW) = range(7)
+OP_FIRST_CONV = 7
 (PATH_NONE, PATH_SCALAR, PATH_VEC4, PATH_VEC8_BF16, PATH_ONE_STAGE, PATH_TWO_STAGE, PATH_GENERIC, PATH_FOUR_POSITION,
- PATH_NOT_FUSED, PATH_FUSED) = range(10)
+ PATH_NOT_FUSED, PATH_FUSED, PATH_FIRST_CONV) = range(11)
 
 BLEND_NO_RISE, BLEND_NO_FALL = 1, 2                 # wun_blend_window.flags
 SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2                 # wun_snippet_source.flags
@@ -326,6 +335,11 @@ _SIGS = {
     "wun_op_head_backward": (C.c_int, [C.POINTER(WunOpHeadDesc), _P, _P, C.POINTER(C.c_int64), _P, _P, _P, _P, _P]),
     "wun_op_btc_to_ncw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "wun_op_last_path": (C.c_int, [C.c_int]),
+    "wun_op_conv_bf16_abi_size": (C.c_int32, []),
+    "wun_op_conv_bf16_ex_scratch": (C.c_int64, [C.POINTER(WunOpConvBf16Desc)]),
+    "wun_op_conv_bf16_ex": (C.c_int, [C.POINTER(WunOpConvBf16Desc)] + [_P] * 11),
+    "wun_op_conv_bf16_choice_ok": (C.c_int, [C.POINTER(WunOpConvBf16Desc), C.c_int]),
+    "wun_op_first_conv": (C.c_int, [_P] * 5 + [C.c_int] * 13 + [_P]),
     "wun_profile_begin": (C.c_int, []),
     "wun_profile_end": (C.c_int, [C.c_char_p, C.c_int64]),
     "wun_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
@@ -381,6 +395,9 @@ def load():
     if lib.wun_op_head_abi_size() != C.sizeof(WunOpHeadDesc):
         raise RuntimeError("libwun.so wun_op_head_desc size %d != this binding's %d (stale library or binding)" % (
             lib.wun_op_head_abi_size(), C.sizeof(WunOpHeadDesc)))
+    if lib.wun_op_conv_bf16_abi_size() != C.sizeof(WunOpConvBf16Desc):
+        raise RuntimeError("libwun.so wun_op_conv_bf16_desc size %d != this binding's %d (stale library or binding)" % (
+            lib.wun_op_conv_bf16_abi_size(), C.sizeof(WunOpConvBf16Desc)))
     if lib.wun_speed_abi_size() != C.sizeof(WunSpeedBank):
         raise RuntimeError("libwun.so wun_speed_bank size %d != this binding's %d (stale library or binding)" % (
             lib.wun_speed_abi_size(), C.sizeof(WunSpeedBank)))

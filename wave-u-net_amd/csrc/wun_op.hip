@@ -26,6 +26,7 @@ static int g_op_copy_t0 = 0, g_op_copy_t1 = 0, g_op_copy_exp = 0, g_op_copy_lo =
 static float* g_op_ups_y = nullptr; static const float* g_op_ups_w = nullptr;   // wun_op_set_conv_upsample (test hook)
 static int g_op_ups_pitch = 0, g_op_ups_tup = 0;
 static thread_local int t_op_epilogue_path = WUN_PATH_NONE;                     // wun_op_last_path(WUN_OP_CONV_EPILOGUE)
+static thread_local int t_op_first_conv_path = WUN_PATH_NONE;                   // wun_op_last_path(WUN_OP_FIRST_CONV)
 static float* op_scratch() {
     static float* buf = nullptr;
     if (!buf && hipMalloc((void**)&buf, kOpScratchFloats * sizeof(float)) != hipSuccess) {
@@ -61,9 +62,22 @@ static const float* op_to_bf16(int slot, const float* src, long long rows, int T
 }
 
 static hipError_t op_launch_conv(ConvArgs a, hipStream_t s) {
-    if (g_op_variant >= 0) { a.force_variant = g_op_variant + 1; a.force_ksplit = (a.flags & F_PHASE2) ? 0 : g_op_ksplit; }
+    // (a forced bf16 tile code, >= kBf16VariantBase, is for the bf16 entries: op_force_bf16)
+    if (g_op_variant >= 0 && g_op_variant < kBf16VariantBase) {
+        a.force_variant = g_op_variant + 1; a.force_ksplit = (a.flags & F_PHASE2) ? 0 : g_op_ksplit;
+    }
     return launch_conv(a, op_scratch(), kOpScratchFloats, s, wun_switches_from_env());
 }
+
+// the bf16 entries under wun_op_force_conv_variant: a forced tile code goes into the launch; false = the launcher would refuse it
+// (the caller returns WUN_ERR_UNSUPPORTED before any GPU work).  Forced fp32 variants are not for these entries.
+static bool op_force_bf16(ConvArgs& a) {
+    if (g_op_variant < kBf16VariantBase) return true;
+    if (!conv_bf16_choice_ok(a, g_op_variant)) return false;
+    a.force_variant = g_op_variant + 1;
+    return true;
+}
+static_assert(WUN_BF16_VARIANT_BASE == kBf16VariantBase, "wun.h tile code base");
 
 static void op_src(ConvArgs& a, const float* x, int C, int T) {
     const int pitch = T;
@@ -486,6 +500,7 @@ extern "C" int wun_op_last_path(int op) {
         case WUN_OP_HEAD_DFEAT: return elementwise_last_path(EW_HEAD_DFEAT);
         case WUN_OP_BTC_TO_NCW: return elementwise_last_path(EW_BTC_TO_NCW);
         case WUN_OP_CONV_EPILOGUE: return t_op_epilogue_path;
+        case WUN_OP_FIRST_CONV: return t_op_first_conv_path;
         default: return fail(WUN_ERR_INVALID, "unknown operator");
     }
 }
@@ -522,10 +537,11 @@ extern "C" int wun_op_conv1d_bf16(const float* x, const float* w, const float* b
     a.flags = lrelu ? F_LRELU : 0;
     a.dst0 = y; a.obs0 = (long long)cout * t_out; a.opitch0 = t_out;
     // the kernel reads bf16 rows: convert x (fp32 output, obf = 0, keeps the comparison with float64 sharp)
-    a.src0 = op_to_bf16(0, x, (long long)batch * cin, t_in, t_in, s);
-    if (!a.src0) return fail(WUN_ERR_NOMEM, "bf16 temporary");
     a.pitch0 = pad8(t_in); a.bs0 = (long long)cin * a.pitch0; a.xbf = 1; a.obf = 0;
     if (!conv_bf16_supported(a)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the bf16 kernel (cin < 8 or k > 15)");
+    if (!op_force_bf16(a)) return fail(WUN_ERR_UNSUPPORTED, "forced bf16 tile code refused for this launch");
+    a.src0 = op_to_bf16(0, x, (long long)batch * cin, t_in, t_in, s);
+    if (!a.src0) return fail(WUN_ERR_NOMEM, "bf16 temporary");
     float* img = (float*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
     PackDesc d;
     d.src_off = 0; d.src_in_ws = 0; d.dst_off = 0; d.KW = k; d.C = cin; d.N = cout;
@@ -578,10 +594,11 @@ extern "C" int wun_op_conv1d_dgrad_bf16(const float* dz, const float* w, float* 
         pd.KW = J0; pd.N = 2 * cin; pd.Npad = (2 * cin + 32 + 63) / 64 * 64;
     }
     pd.C8p = bf16_image_groups(cout);
-    a.src0 = op_to_bf16(0, dz, (long long)batch * cout, t_out, t_out, s);
-    if (!a.src0) return fail(WUN_ERR_NOMEM, "bf16 temporary");
     a.pitch0 = pad8(t_out); a.bs0 = (long long)cout * a.pitch0; a.xbf = 1; a.obf = 0;
     if (!conv_bf16_supported(a)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the bf16 kernel");
+    if (!op_force_bf16(a)) return fail(WUN_ERR_UNSUPPORTED, "forced bf16 tile code refused for this launch");
+    a.src0 = op_to_bf16(0, dz, (long long)batch * cout, t_out, t_out, s);
+    if (!a.src0) return fail(WUN_ERR_NOMEM, "bf16 temporary");
     HIP_TRY(launch_make_wt_one(w, wt, d, s));
     PackDesc* dd = nullptr;
     HIP_TRY(hipMalloc((void**)&dd, sizeof(PackDesc)));
@@ -592,6 +609,136 @@ extern "C" int wun_op_conv1d_dgrad_bf16(const float* dz, const float* w, float* 
     (void)hipStreamSynchronize(s);
     (void)hipFree(dd);
     HIP_TRY(e);
+    return WUN_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// The plan's bf16 conv launch as a single operator on rows the caller made (wun.h: wun_op_conv_bf16_desc), and the
+// audio-input conv.  Test hooks: what the plan runs -- bf16 stores, masks, ranged accumulate, the column split, the compact
+// copy, crop windows at any first-element offset -- reachable tile by tile.
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t wun_op_conv_bf16_abi_size(void) { return (int32_t)sizeof(wun_op_conv_bf16_desc); }
+
+// fills the shape side of ConvArgs (no pointers) from the descriptor; null = fine, else why not (WUN_ERR_INVALID)
+static const char* op_conv_bf16_shape(const wun_op_conv_bf16_desc* d, ConvArgs& a) {
+    if (!d) return "null argument";
+    if (d->mode < 0 || d->mode > 2) return "mode must be 0, 1 or 2";
+    if (d->B < 1 || d->C0 < 1 || d->C1 < 0 || d->N < 1 || d->K < 1 || d->Tin < 1 || d->Tout < 1) return "bad shape";
+    if (d->N0 < 1 || d->N0 > d->N) return "N0 must be in 1..N";
+    if (d->x_off < 0 || d->y0_off < 0 || d->y1_off < 0 || d->acc_len < 0) return "negative offset or length";
+    if ((long long)d->x_off + d->Tin > d->x0_pitch || (d->C1 > 0 && (long long)d->x_off + d->Tin > d->x1_pitch)) return "input row does not fit its pitch";
+    if ((long long)d->y0_off + d->Tout > d->y0_pitch || (d->N0 < d->N && (long long)d->y1_off + d->Tout > d->y1_pitch)) return "output row does not fit its pitch";
+    if (d->dec_pitch != 0 && d->dec_pitch < (d->Tout + 1) / 2) return "dec_pitch below the copy's length";
+    if (d->mode == 2 && (d->shift != 0 || d->C1 != 0 || d->N0 != d->N || (d->N & 3) != 0 || d->lrelu || d->dec_pitch != 0))
+        return "two-phase form: shift 0, one source, one destination, N % 4 == 0, no lrelu, no dec";
+    if (d->mode == 2 && d->Tout > 2ll * d->Tin + d->K) return "Tout larger than the transposed conv produces";
+    memset(&a, 0, sizeof(a));
+    a.B = d->B; a.ostride = 1;
+    a.C0 = d->C0; a.pitch0 = d->x0_pitch; a.bs0 = (long long)d->C0 * d->x0_pitch; a.off0 = d->x_off;
+    if (d->C1 > 0) { a.C1 = d->C1; a.pitch1 = d->x1_pitch; a.bs1 = (long long)d->C1 * d->x1_pitch; a.off1 = d->x_off; }
+    a.loader = d->mode == 1 ? LOADER_DEINT : LOADER_DIRECT;
+    a.Tin = d->Tin; a.N = d->N; a.N0 = d->N0;
+    if (d->mode == 2) {          // as wun_op_conv1d_dgrad_bf16 sets it up
+        const int J0 = (d->K + 1) / 2;
+        a.KW = J0; a.kw_full = d->K; a.shift = J0 - 1; a.Tout = (d->Tout + 1) / 2; a.Tlim = d->Tout; a.flags = F_PHASE2;
+    } else {
+        a.KW = d->K; a.shift = d->shift; a.Tout = d->Tout;
+        a.flags = d->lrelu ? F_LRELU : 0;
+    }
+    if (d->accumulate) { a.flags |= F_ACCUM; a.acc_lo = d->acc_lo; a.acc_len = (unsigned)d->acc_len; }
+    a.opitch0 = d->y0_pitch; a.obs0 = (long long)d->N0 * d->y0_pitch; a.ooff0 = d->y0_off;
+    if (d->N0 < d->N) { a.opitch1 = d->y1_pitch; a.obs1 = (long long)(d->N - d->N0) * d->y1_pitch; a.ooff1 = d->y1_off; }
+    if (d->dec_pitch != 0) { a.decpitch = d->dec_pitch; a.decbs = (long long)d->N0 * d->dec_pitch; }
+    a.xbf = 1; a.obf = d->out_bf16 ? 1 : 0;
+    return nullptr;
+}
+
+extern "C" int wun_op_conv_bf16_choice_ok(const wun_op_conv_bf16_desc* desc, int code) {
+    ConvArgs a;
+    if (const char* why = op_conv_bf16_shape(desc, a)) return fail(WUN_ERR_INVALID, why);
+    if (code < 0 || code >= 27) return 0;
+    return conv_bf16_choice_ok(a, kBf16VariantBase + code) ? 1 : 0;
+}
+
+extern "C" int64_t wun_op_conv_bf16_ex_scratch(const wun_op_conv_bf16_desc* d) {
+    if (!d) return fail(WUN_ERR_INVALID, "null argument");
+    return d->mode == 2 ? wun_op_conv1d_dgrad_bf16_scratch(d->N, d->C0, d->K) : wun_op_conv1d_bf16_scratch(d->C0 + d->C1, d->N, d->K);
+}
+
+extern "C" int wun_op_conv_bf16_ex(const wun_op_conv_bf16_desc* d, const void* x0, const void* x1, const float* w, const float* bias,
+                                   void* y0, void* y1, const void* mask0, const void* mask1, void* dec, float* scratch,
+                                   void* stream) {
+    ConvArgs a;
+    if (const char* why = op_conv_bf16_shape(d, a)) return fail(WUN_ERR_INVALID, why);
+    if (!x0 || !w || !y0 || !scratch || (d->C1 > 0 && !x1) || (d->N0 < d->N && !y1)) return fail(WUN_ERR_INVALID, "null argument");
+    if ((dec != nullptr) != (d->dec_pitch != 0)) return fail(WUN_ERR_INVALID, "dec and dec_pitch go together");
+    if (d->mode == 2 && bias) return fail(WUN_ERR_INVALID, "two-phase form: no bias");
+    if (mask1 && !(d->N0 < d->N)) return fail(WUN_ERR_INVALID, "mask1 without a second destination");
+    if (!aligned16(x0) || (d->C1 > 0 && !aligned16(x1))) return fail(WUN_ERR_INVALID, "input rows must be 16-byte aligned");
+    const int esz = d->out_bf16 ? 2 : 4;
+    if ((reinterpret_cast<uintptr_t>(y0) % esz) || (y1 && reinterpret_cast<uintptr_t>(y1) % esz) ||
+        (dec && reinterpret_cast<uintptr_t>(dec) % esz)) return fail(WUN_ERR_INVALID, "output not aligned to its element");
+    a.src0 = reinterpret_cast<const float*>(x0);
+    if (d->C1 > 0) a.src1 = reinterpret_cast<const float*>(x1);
+    a.bias = bias;
+    a.dst0 = reinterpret_cast<float*>(y0); a.msk0 = reinterpret_cast<const float*>(mask0);
+    if (d->N0 < d->N) { a.dst1 = reinterpret_cast<float*>(y1); a.msk1 = reinterpret_cast<const float*>(mask1); }
+    a.dec = reinterpret_cast<float*>(dec);
+    if (!conv_bf16_supported(a)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the bf16 kernel");
+    if (!op_force_bf16(a)) return fail(WUN_ERR_UNSUPPORTED, "forced bf16 tile code refused for this launch");
+    hipStream_t s = (hipStream_t)stream;
+    const int Ctot = d->C0 + d->C1;
+    PackDesc pd; pd.src_off = 0; pd.src_in_ws = 0; pd.dst_off = 0;
+    const float* wsrc = w;
+    float* img;
+    if (d->mode == 2) {
+        // forward weights [K][cin = N][cout = C0] -> the two-phase transposed copy -> its packed image (wun_op_conv1d_dgrad_bf16)
+        const int cin = d->N, cout = d->C0, k = d->K;
+        float* wt = (float*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+        img = (float*)(((uintptr_t)(wt + 2ll * (k + 1) * cin * cout) + 255) & ~(uintptr_t)255);
+        WtDesc wd; wd.src_off = 0; wd.dst_off = 0; wd.C = cin; wd.N = cout;
+        wd.J = a.KW; wd.k_last = 2 * (a.KW - 1); wd.k_step = k; wd.mode = 1;
+        HIP_TRY(launch_make_wt_one(w, wt, wd, s));
+        wsrc = wt;
+        pd.C = cout; pd.KW = a.KW; pd.N = 2 * cin; pd.Npad = (2 * cin + 32 + 63) / 64 * 64;
+    } else {
+        img = (float*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+        pd.C = Ctot; pd.KW = d->K; pd.N = d->N; pd.Npad = (d->N + 63) / 64 * 64;
+    }
+    pd.C8p = bf16_image_groups(pd.C);
+    PackDesc* dd = nullptr;
+    HIP_TRY(hipMalloc((void**)&dd, sizeof(PackDesc)));
+    hipError_t e = hipMemcpyAsync(dd, &pd, sizeof(pd), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch_pack_bf16(wsrc, img, dd, 1, (long long)pd.KW * pd.C8p * pd.Npad, s);
+    a.W = img; a.wb_c8p = pd.C8p; a.wb_npad = pd.Npad;
+    if (e == hipSuccess) e = launch_conv_bf16(a, s, wun_switches_from_env());
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(dd);
+    HIP_TRY(e);
+    return WUN_OK;
+}
+
+extern "C" int wun_op_first_conv(const float* x, const float* w, const float* bias, void* y, void* dec, int batch, int cin,
+                                 int cout, int k, int t_in, int t_out, int stride, int pad_left, int lrelu, int out_bf16,
+                                 int x_pitch, int y_pitch, int dec_pitch, void* stream) {
+    if (!x || !w || !y) return fail(WUN_ERR_INVALID, "null argument");
+    if (batch < 1 || cin < 1 || cout < 1 || k < 1 || t_in < 1 || t_out < 1 || pad_left < 0) return fail(WUN_ERR_INVALID, "bad shape");
+    if (stride != 1 && stride != 2) return fail(WUN_ERR_UNSUPPORTED, "stride must be 1 or 2");
+    if (x_pitch < t_in || y_pitch < t_out || (dec && dec_pitch < (t_out + 1) / 2)) return fail(WUN_ERR_INVALID, "pitch below length");
+    if (dec && (reinterpret_cast<uintptr_t>(dec) % (out_bf16 ? 2 : 4))) return fail(WUN_ERR_INVALID, "dec not aligned to its element");
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = batch; a.ostride = 1;
+    a.src0 = x; a.bs0 = (long long)cin * x_pitch; a.pitch0 = x_pitch; a.C0 = cin;
+    a.loader = stride == 2 ? LOADER_DEINT : LOADER_DIRECT;
+    a.Tin = t_in; a.shift = pad_left; a.W = w; a.bias = bias; a.KW = k; a.N = a.N0 = cout; a.Tout = t_out;
+    a.flags = lrelu ? F_LRELU : 0;
+    a.dst0 = reinterpret_cast<float*>(y); a.obs0 = (long long)cout * y_pitch; a.opitch0 = y_pitch;
+    if (dec) { a.dec = reinterpret_cast<float*>(dec); a.decpitch = dec_pitch; a.decbs = (long long)cout * dec_pitch; }
+    a.obf = out_bf16 ? 1 : 0;
+    if (!first_conv_supported(a)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the audio-input conv kernel");
+    HIP_TRY(launch_first_conv(a, (hipStream_t)stream));
+    t_op_first_conv_path = WUN_PATH_FIRST_CONV;
     return WUN_OK;
 }
 
