@@ -16,6 +16,8 @@ import wave_u_net_amd as wun
 from wave_u_net_amd import _lib
 from wave_u_net_amd.separator import UnetAudioSeparator, _wun_config
 
+import _abi  # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -32,6 +34,106 @@ def test_exports_every_declared_symbol(lib):
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.wun_version().decode().startswith("wun")
+
+
+# ---- the whole binding against the whole header (tests/_abi.py) ----
+@pytest.fixture(scope="module")
+def header():
+    return _abi.parse(os.path.join(ROOT, "include", "wun.h"))
+
+
+_BOUND_STRUCTS = [v for v in vars(_lib).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure]
+
+
+def test_every_prototype_matches_its_binding(header):
+    """Arity, return type, and per argument scalar-or-pointer, width, kind and pointee of all of _lib._SIGS; the names agree in
+    both directions."""
+    assert len(header["functions"]) == len(_lib._SIGS) > 100
+    assert _abi.compare_functions(header["functions"], _lib._SIGS) == []
+
+
+def test_every_struct_matches_its_binding(header):
+    """Field names, order, types and array lengths of every ctypes Structure; every header struct but the opaque plan is bound."""
+    assert header["opaque"] == {"wun_plan"}
+    assert _abi.compare_structs(header["structs"], _BOUND_STRUCTS) == []
+    for entry, cls in _lib._ABI_SIZES:                       # load()'s size table names entries and structs of the header
+        assert entry in header["functions"] and _lib.c_name(cls) in header["structs"]
+    assert len(set(cls for _, cls in _lib._ABI_SIZES)) == len(_lib._ABI_SIZES)
+
+
+def test_load_refuses_a_struct_of_another_size(lib, monkeypatch):
+    class WunBlendWindow(C.Structure):
+        _fields_ = _lib.WunBlendWindow._fields_ + [("more", C.c_int64)]
+    monkeypatch.setattr(_lib, "_ABI_SIZES", _lib._ABI_SIZES[:-1] + (("wun_blend_abi_size", WunBlendWindow),))
+    monkeypatch.setattr(_lib, "_lib", None)
+    with pytest.raises(RuntimeError, match=r"libwun.so wun_blend_window size 16 != this binding's 24 \(stale library or binding\)"):
+        _lib.load()
+
+
+def test_every_constant_of_the_header_is_the_bindings(header):
+    """A #define or enumerator the binding repeats (as NAME or WUN_NAME) has the header's value, and every #define is repeated."""
+    for name, value in list(header["defines"].items()) + list(header["enums"].items()):
+        mine = [getattr(_lib, n) for n in (name, name[4:]) if hasattr(_lib, n)]
+        assert mine == [value] or (not mine and name in header["enums"]), name
+
+
+def test_abi_surface_is_the_pinned_list(lib, header):
+    """tests/golden/abi_symbols.txt: the sorted names of the ABI.  Header, binding, library and list agree."""
+    pinned = open(os.path.join(ROOT, "tests", "golden", "abi_symbols.txt")).read().split()
+    assert pinned == sorted(set(pinned)) == sorted(header["functions"]) == list(_lib.EXPORTED_SYMBOLS)
+    assert all(hasattr(lib, name) for name in pinned)
+
+
+def _edit_function(header, name, edit):
+    functions = dict(header["functions"])
+    ret, args = functions[name]
+    functions[name] = (ret, edit(list(args)))
+    return _abi.compare_functions(functions, _lib._SIGS)
+
+
+def _set(i, value):
+    return lambda args: args[:i] + [value] + args[i + 1:]
+
+
+@pytest.mark.parametrize("name, edit, reason", [
+    ("wun_resample", lambda args: args[:-1], "wun_resample: arity 10 != 11"),                       # a dropped argument
+    ("wun_resample", _set(2, ("int", 8)), "wun_resample: argument 2: width 8 != 4"),                # int32_t -> int64_t
+    ("wun_adam_step", _set(6, ("float", 8)), "wun_adam_step: argument 6: width 8 != 4"),            # float -> double
+    ("wun_adam_step", _set(5, ("float", 8)), "wun_adam_step: argument 5: kind float != int"),       # int64_t -> double
+    ("wun_resample", _set(1, ("ptr", ("int", 8))),
+     "wun_resample: argument 1: pointer in the header, scalar in the binding"),                     # a scalar turned into a pointer
+    ("wun_resample", _set(0, ("float", 4)),
+     "wun_resample: argument 0: scalar in the header, pointer in the binding"),                     # and the reverse
+    ("wun_get_padding", _set(2, ("ptr", ("int", 4))), "wun_get_padding: argument 2: pointee: width 4 != 8"),
+])
+def test_the_comparison_refuses_an_edited_prototype(header, name, edit, reason):
+    """The check can fail: each edit of the PARSED table (never of the library) is reported, for the stated reason only."""
+    assert _edit_function(header, name, edit) == [reason]
+
+
+def test_the_comparison_refuses_edited_structs(header):
+    structs = dict(header["structs"])
+    f = structs["wun_blend_window"]
+    structs["wun_blend_window"] = [f[0], f[2], f[1]]                                               # a swapped struct field
+    assert _abi.compare_structs(structs, _BOUND_STRUCTS) == [
+        "wun_blend_window: fields ['pos', 'flags', 'row'] != ['pos', 'row', 'flags']"]
+    bank = [(n, t, 4 if n == "up" else k) for n, t, k in header["structs"]["wun_speed_bank"]]
+    structs = dict(header["structs"], wun_speed_bank=bank)
+    assert _abi.compare_structs(structs, _BOUND_STRUCTS) == ["wun_speed_bank.up: array length 4 != 8"]
+    structs = dict(header["structs"])
+    del structs["wun_mel_terms"]
+    assert _abi.compare_structs(structs, _BOUND_STRUCTS) == ["wun_mel_terms: bound, not declared"]
+    functions = dict(header["functions"], wun_new_entry=(("int", 4), []))
+    assert _abi.compare_functions(functions, _lib._SIGS) == ["wun_new_entry: declared, not bound"]
+
+
+def test_the_parser_refuses_what_it_does_not_understand(tmp_path):
+    for text in ("typedef union u { int a; } u;", "int wun_f(int (*cb)(int));", "int wun_f(wun_unknown* p);",
+                 "typedef struct s { int a : 3; } s;", "#define WUN_X (1 << 2)\n", "int wun_f(int a)"):
+        path = tmp_path / "h.h"
+        path.write_text(text)
+        with pytest.raises((ValueError, KeyError)):
+            _abi.parse(str(path))
 
 
 def _oracle_cfg(**kw):

@@ -3,8 +3,6 @@ declared, exported and bound; the norm workspace size; every argument error refu
 -- on a plan built without a GPU -- plus the clip_norm / clip_grad_norm checks of adam_step and the Trainer."""
 import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,9 +12,7 @@ from wave_u_net_amd import _lib
 from wave_u_net_amd.separator import UnetAudioSeparator, check_clip_norm
 from wave_u_net_amd.training import clip_settings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WUN_ERR_INVALID = -1
-CLIP = ("wun_grad_norm_workspace_floats", "wun_grad_norm", "wun_adam_step_clip")
 
 
 @pytest.fixture(scope="module")
@@ -30,20 +26,6 @@ def plan():
                                           upsampling="learned", output_type="difference", task="multi_instrument"))
     i, _ = s.get_padding(np.array([2, 300, 0]))
     return s._plan(2, int(i[1]))
-
-
-def test_clip_symbols_declared_exported_and_bound(lib):
-    hdr = open(os.path.join(ROOT, "include", "wun.h")).read()
-    declared = set(re.findall(r"\b(wun_[a-z0-9_]+)\s*\(", hdr))
-    assert "#define WUN_CLIP_SKIP_NONFINITE 1" in hdr
-    for name in CLIP:
-        assert name in declared and name in _lib.EXPORTED_SYMBOLS, name
-    assert lib.wun_grad_norm_workspace_floats.restype is C.c_int64
-    assert lib.wun_grad_norm.restype is C.c_int and len(lib.wun_grad_norm.argtypes) == 7
-    assert lib.wun_adam_step_clip.restype is C.c_int and len(lib.wun_adam_step_clip.argtypes) == 18
-    # the leading arguments are wun_adam_step's, the selection trails as in wun_adam_step_select
-    assert lib.wun_adam_step_clip.argtypes[:11] == lib.wun_adam_step.argtypes[:11]
-    assert lib.wun_adam_step_clip.argtypes[-2:] == lib.wun_adam_step_select.argtypes[-2:]
 
 
 def test_workspace_floats(lib, plan):

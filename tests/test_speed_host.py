@@ -4,8 +4,6 @@ brute force, every argument error of the entry before any GPU work (no device he
 against scipy's float64 resampler, the order and the source of the draws, the placement rule and every ValueError."""
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -16,7 +14,6 @@ from wave_u_net_amd import _lib, datasets, resample, validation
 
 import _speed_np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WUN_ERR_INVALID, WUN_ERR_UNSUPPORTED = -1, -2
 _FAKE = C.c_void_p(0x1000)          # non-null, 16-byte aligned, never dereferenced: every call below fails a check first
 T_IN, T_OUT = 90, 40
@@ -38,13 +35,7 @@ def lib():
 
 # ---------------------------------------------------------------------------------------- the C ABI
 def test_symbols_struct_and_binding(lib):
-    hdr = open(os.path.join(ROOT, "include", "wun.h")).read()
-    declared = set(re.findall(r"\b(wun_[a-z0-9_]+)\s*\(", hdr))
-    for name in ("wun_speed_abi_size", "wun_speed_source_frames", "wun_gather_snippets_speed"):
-        assert name in declared and name in _lib.EXPORTED_SYMBOLS, name
-        getattr(lib, name)
-    assert int(re.search(r"#define WUN_SPEED_RATES (\d+)", hdr).group(1)) == 8 == _lib.SPEED_RATES == datasets.SPEED_MAX_RATES
-    assert int(re.search(r"#define WUN_SPEED_MAX_RATIO (\d+)", hdr).group(1)) == 64 == _lib.SPEED_MAX_RATIO == datasets.SPEED_MAX_RATIO
+    assert 8 == _lib.SPEED_RATES == datasets.SPEED_MAX_RATES and 64 == _lib.SPEED_MAX_RATIO == datasets.SPEED_MAX_RATIO
     assert lib.wun_speed_abi_size() == C.sizeof(_lib.WunSpeedBank) == 4 + 32 + 32 + 4 + 64      # 4 bytes of padding before the pointers
     for f, (off, size) in {"n": (0, 4), "up": (4, 32), "down": (36, 32), "table": (72, 64)}.items():
         fld = getattr(_lib.WunSpeedBank, f)

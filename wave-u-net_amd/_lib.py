@@ -352,6 +352,22 @@ WUN_CLIP_SKIP_NONFINITE = 1      # wun_adam_step_clip flags
 WUN_OPTIM_EMA_WARMUP = 2         # wun_optim_step / wun_ema_update flags
 _lib = None
 
+# (size entry, struct): the structs of this binding against the sizes the library was compiled with, checked by load().
+# wun_abi_sizes reports its three in this order; every later struct has an entry of its own.
+_ABI_SIZES = (
+    ("wun_abi_sizes", WunConfig), ("wun_abi_sizes", WunPlanInfo), ("wun_abi_sizes", WunTensorInfo),
+    ("wun_spec_abi_size", WunSpecConfig), ("wun_spec_train_abi_size", WunSpecTrainConfig), ("wun_mel_abi_size", WunMelTerms),
+    ("wun_snippet_abi_size", WunSnippetSource), ("wun_op_head_abi_size", WunOpHeadDesc),
+    ("wun_op_conv_bf16_abi_size", WunOpConvBf16Desc), ("wun_speed_abi_size", WunSpeedBank),
+    ("wun_stretch_abi_size", WunStretchJob), ("wun_optim_abi_size", WunOptimConfig), ("wun_blend_abi_size", WunBlendWindow))
+_DEVICE_TABLES = {}    # device_table's cache
+
+
+def c_name(cls):
+    """The header's name of a struct of this binding: WunOpConvBf16Desc -> wun_op_conv_bf16_desc."""
+    return "".join("_" + ch.lower() if ch.isupper() else ch for ch in cls.__name__)[1:]
+
+
 # Process-wide record of the scheduling hint wun_config.exclusive_streams (include/wun.h): plans created with it run
 # their side streams on LOWEST-priority hardware queues, and a process that has ever created those queues is ~40 %
 # slower once a communication stream (RCCL) shares the device.  parallel.init_distributed() refuses to start a
@@ -374,42 +390,14 @@ def load():
         fn = getattr(lib, name)      # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args
-    # the structs of this binding against the sizes the library was compiled with (wun_abi_sizes, include/wun.h)
     sizes = (C.c_int64 * 3)()
     lib.wun_abi_sizes(sizes, 3)
-    mine = (C.sizeof(WunConfig), C.sizeof(WunPlanInfo), C.sizeof(WunTensorInfo))
-    if tuple(sizes) != mine:
-        raise RuntimeError("libwun.so struct sizes %s != this binding's %s (stale library or binding)" % (tuple(sizes), mine))
-    if lib.wun_spec_abi_size() != C.sizeof(WunSpecConfig):
-        raise RuntimeError("libwun.so wun_spec_config size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_spec_abi_size(), C.sizeof(WunSpecConfig)))
-    if lib.wun_spec_train_abi_size() != C.sizeof(WunSpecTrainConfig):
-        raise RuntimeError("libwun.so wun_spec_train_config size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_spec_train_abi_size(), C.sizeof(WunSpecTrainConfig)))
-    if lib.wun_mel_abi_size() != C.sizeof(WunMelTerms):
-        raise RuntimeError("libwun.so wun_mel_terms size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_mel_abi_size(), C.sizeof(WunMelTerms)))
-    if lib.wun_snippet_abi_size() != C.sizeof(WunSnippetSource):
-        raise RuntimeError("libwun.so wun_snippet_source size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_snippet_abi_size(), C.sizeof(WunSnippetSource)))
-    if lib.wun_op_head_abi_size() != C.sizeof(WunOpHeadDesc):
-        raise RuntimeError("libwun.so wun_op_head_desc size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_op_head_abi_size(), C.sizeof(WunOpHeadDesc)))
-    if lib.wun_op_conv_bf16_abi_size() != C.sizeof(WunOpConvBf16Desc):
-        raise RuntimeError("libwun.so wun_op_conv_bf16_desc size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_op_conv_bf16_abi_size(), C.sizeof(WunOpConvBf16Desc)))
-    if lib.wun_speed_abi_size() != C.sizeof(WunSpeedBank):
-        raise RuntimeError("libwun.so wun_speed_bank size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_speed_abi_size(), C.sizeof(WunSpeedBank)))
-    if lib.wun_stretch_abi_size() != C.sizeof(WunStretchJob):
-        raise RuntimeError("libwun.so wun_stretch_job size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_stretch_abi_size(), C.sizeof(WunStretchJob)))
-    if lib.wun_optim_abi_size() != C.sizeof(WunOptimConfig):
-        raise RuntimeError("libwun.so wun_optim_config size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_optim_abi_size(), C.sizeof(WunOptimConfig)))
-    if lib.wun_blend_abi_size() != C.sizeof(WunBlendWindow):
-        raise RuntimeError("libwun.so wun_blend_window size %d != this binding's %d (stale library or binding)" % (
-            lib.wun_blend_abi_size(), C.sizeof(WunBlendWindow)))
+    triple = iter(sizes)
+    for entry, cls in _ABI_SIZES:
+        size = next(triple) if entry == "wun_abi_sizes" else getattr(lib, entry)()
+        if size != C.sizeof(cls):
+            raise RuntimeError("libwun.so %s size %d != this binding's %d (stale library or binding)" % (
+                c_name(cls), size, C.sizeof(cls)))
     _lib = lib
     return lib
 
@@ -428,3 +416,26 @@ def check(rc):
     if rc == -1:
         raise ValueError(msg)                     # the reference's shape asserts
     raise WunError("wun status %d: %s" % (rc, msg))
+
+
+def count(v):
+    """A frame, float or window count of the library as an int; its negative values are error codes and raise as check does."""
+    v = int(v)
+    check(min(v, 0))
+    return v
+
+
+def stream(device):
+    """torch's current stream on `device` as the void* every entry takes."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def device_table(key, device, make):
+    """The device copy of a table designed on the host, uploaded once per process: `key` is (kind, the design's arguments...),
+    make() returns the numpy array.  Cached under key + (str(device),), so "cuda" and "cuda:0" hold separate copies."""
+    key = tuple(key) + (str(device),)
+    if key not in _DEVICE_TABLES:
+        import torch
+        _DEVICE_TABLES[key] = torch.from_numpy(make()).to(device)
+    return _DEVICE_TABLES[key]

@@ -11,8 +11,6 @@ that covers it, taken in the order of the window list.
 Device tensors go through the library's kernels.  CPU tensors (numpy stand-in separators) go through the restatement below, which
 gives the same bits: the chain of a frame is float32 fused multiply-adds in table order, whichever side runs it.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -32,11 +30,9 @@ def window_table(output_frames, n_frames, overlap_frames, shifts):
     lib = _lib.load()
     parts = []
     for s in shifts:
-        k = lib.wun_blend_positions(int(output_frames), int(n_frames), int(overlap_frames), int(s), None, 0)
-        if k < 0:
-            _lib.check(int(k))
+        k = _lib.count(lib.wun_blend_positions(int(output_frames), int(n_frames), int(overlap_frames), int(s), None, 0))
         buf = (_lib.WunBlendWindow * k)()
-        _lib.check(min(0, int(lib.wun_blend_positions(int(output_frames), int(n_frames), int(overlap_frames), int(s), buf, k))))
+        _lib.count(lib.wun_blend_positions(int(output_frames), int(n_frames), int(overlap_frames), int(s), buf, k))
         parts.append(np.array([(w.pos, w.row, w.flags) for w in buf], dtype=np.int64).reshape(k, 3))
     if not parts:
         raise ValueError("window_table: no shifts")
@@ -62,10 +58,6 @@ def _check_tensors(outputs, preds, den):
                                                                                 tuple(den.shape)))
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def blend_windows(outputs, windows, overlap_frames, preds, den):
     """preds (the accumulator) and den, zeroed by the caller before the first table of a separation, take the windows of
     `windows` ([nwin, 3]: pos, row of outputs, flags) in table order.  outputs [S, B, Tout, C]; returns preds."""
@@ -75,7 +67,7 @@ def blend_windows(outputs, windows, overlap_frames, preds, den):
     if preds.device.type != "cpu":
         lib = _lib.load()
         _lib.check(lib.wun_blend_windows(outputs.data_ptr(), S, B, tout, ch, buf, int(tab.shape[0]), int(overlap_frames),
-                                         preds.data_ptr(), den.data_ptr(), int(preds.shape[1]), _stream(preds.device)))
+                                         preds.data_ptr(), den.data_ptr(), int(preds.shape[1]), _lib.stream(preds.device)))
         return preds
     _blend_windows_cpu(outputs.numpy(), tab, int(overlap_frames), preds.numpy(), den.numpy())
     return preds
@@ -90,7 +82,7 @@ def blend_finish(preds, den):
     if preds.device.type != "cpu":
         lib = _lib.load()
         _lib.check(lib.wun_blend_finish(preds.data_ptr(), den.data_ptr(), int(preds.shape[0]), int(preds.shape[1]),
-                                        int(preds.shape[2]), _stream(preds.device)))
+                                        int(preds.shape[2]), _lib.stream(preds.device)))
         return preds
     p, d = preds.numpy(), den.numpy()
     live = d != 0

@@ -27,21 +27,14 @@ def window_table(n, window, hop):
     to n; window 0 / None or n < window: one window over everything."""
     lib = _lib.load()
     window, hop = int(window or 0), int(hop or 0)
-    count = int(lib.wun_bss_windows(int(n), window, hop, None, None, 0))
-    if count < 0:
-        _lib.check(count)
+    count = _lib.count(lib.wun_bss_windows(int(n), window, hop, None, None, 0))
     starts, lengths = (C.c_int64 * count)(), (C.c_int64 * count)()
-    got = int(lib.wun_bss_windows(int(n), window, hop, starts, lengths, count))
-    if got < 0:
-        _lib.check(got)
+    got = _lib.count(lib.wun_bss_windows(int(n), window, hop, starts, lengths, count))
     return list(starts), list(lengths)
 
 
 def scratch_doubles(S, n, Cc, L, nwin, max_len):
-    v = int(_lib.load().wun_bss_scratch_doubles(int(S), int(n), int(Cc), int(L), int(nwin), int(max_len)))
-    if v < 0:
-        _lib.check(v)
-    return v
+    return _lib.count(_lib.load().wun_bss_scratch_doubles(int(S), int(n), int(Cc), int(L), int(nwin), int(max_len)))
 
 
 def _as_device(x, device):
@@ -60,10 +53,6 @@ def _pick_device(references, estimates, device):
     return torch.device("cuda:0")
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def correlations(references, estimates, filters_len=512, scratch=None):
     """(R, D): float64 device tensors [A, A, L], R[a][b][l] = sum_t s_a[t] s_b[t + l], D[a][q][l] = sum_t s_a[t] est_q[t + l]
     for l in [0, L); negative lags are r_ab[-l] = R[b][a][l].  references, estimates: float32 device tensors [S, n, C]."""
@@ -76,7 +65,7 @@ def correlations(references, estimates, filters_len=512, scratch=None):
     D = torch.empty((A, A, L), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().wun_bss_correlations(references.data_ptr(), estimates.data_ptr(), S, n, Cc, L, R.data_ptr(),
-                                                    D.data_ptr(), scratch.data_ptr(), _stream(dev)))
+                                                    D.data_ptr(), scratch.data_ptr(), _lib.stream(dev)))
     LAUNCHES["correlations"] += 1
     return R, D
 
@@ -100,7 +89,7 @@ def window_energies(references, estimates, starts, lengths, c_all=None, c_own=No
         _lib.check(_lib.load().wun_bss_window_energies(
             references.data_ptr(), estimates.data_ptr(), S, n, Cc, L,
             c_all.data_ptr() if c_all is not None else None, c_own.data_ptr() if c_own is not None else None,
-            st, ln, nwin, out.data_ptr(), scratch.data_ptr(), _stream(dev)))
+            st, ln, nwin, out.data_ptr(), scratch.data_ptr(), _lib.stream(dev)))
     LAUNCHES["energies"] += 1
     return out
 

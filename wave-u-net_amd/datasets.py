@@ -691,7 +691,7 @@ class FusedSnippetSource(object):
         self._unit_rates.setflags(write=False)
         if self.bank_rates:
             from . import resample
-            self._tables = [torch.from_numpy(resample.design(up, down)).to(self.device) for up, down in self.bank_rates]
+            self._tables = [resample._table(up, down, self.device) for up, down in self.bank_rates]
             self._bank = _lib.WunSpeedBank()
             self._bank.n = len(self.bank_rates)
             for i, ((up, down), tab) in enumerate(zip(self.bank_rates, self._tables)):
@@ -790,7 +790,7 @@ class FusedSnippetSource(object):
         with torch.cuda.device(self.device):
             mix = torch.empty((B, self.t_in, C), dtype=torch.float32, device=self.device)
             targets = torch.empty((S, B, self.t_out, C), dtype=torch.float32, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
+            stream = self._lib_mod.stream(self.device)
             if rates is None:
                 self._lib_mod.check(self._lib.wun_gather_snippets(
                     self._planes, self.data["mix"].data_ptr(), self.gather_frames, C, S, B, self.t_in, self.t_out,

@@ -38,14 +38,10 @@ def kweight_sos(sr):
 
 def blocks(n, sr):
     """Complete 0.4 s gating blocks of n frames at sr (wun_loudness_blocks)."""
-    v = int(_lib.load().wun_loudness_blocks(int(n), int(sr)))
-    if v < 0:
-        _lib.check(v)
-    return v
+    return _lib.count(_lib.load().wun_loudness_blocks(int(n), int(sr)))
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+_stream = _lib.stream
 
 
 def _audio(x, who):
@@ -68,9 +64,7 @@ def sosfilt(x, sos, out=None, scratch=None):
     nsec = int(sos.shape[0])
     dev = x.device
     if scratch is None:
-        need = int(lib.wun_sosfilt_scratch_doubles(n, Cc, nsec))
-        if need < 0:
-            _lib.check(need)
+        need = _lib.count(lib.wun_sosfilt_scratch_doubles(n, Cc, nsec))
         scratch = torch.empty(need, dtype=torch.float64, device=dev)
     y = torch.empty_like(x) if out is None else out
     with torch.cuda.device(dev):
@@ -85,10 +79,7 @@ def k_weight(x, sr):
 
 
 def scratch_doubles(n, Cc, sr):
-    v = int(_lib.load().wun_loudness_scratch_doubles(int(n), int(Cc), int(sr)))
-    if v < 0:
-        _lib.check(v)
-    return v
+    return _lib.count(_lib.load().wun_loudness_scratch_doubles(int(n), int(Cc), int(sr)))
 
 
 def integrated(x, sr, return_blocks=False, scratch=None):
@@ -111,18 +102,12 @@ def integrated(x, sr, return_blocks=False, scratch=None):
 def oversampling(sr):
     """The true-peak oversampling factor at sr Hz: the smallest power of two L in 1..32 with L sr >= 176400
     (wun_true_peak_factor)."""
-    v = int(_lib.load().wun_true_peak_factor(int(sr)))
-    if v < 0:
-        _lib.check(v)
-    return v
+    return _lib.count(_lib.load().wun_true_peak_factor(int(sr)))
 
 
 def short_term_blocks(n, sr):
     """Complete 3 s short-term blocks of n frames at sr, at the meter's 0.1 s step (wun_loudness_short_term_blocks)."""
-    v = int(_lib.load().wun_loudness_short_term_blocks(int(n), int(sr)))
-    if v < 0:
-        _lib.check(v)
-    return v
+    return _lib.count(_lib.load().wun_loudness_short_term_blocks(int(n), int(sr)))
 
 
 def _peak_table(L, device):
@@ -149,10 +134,7 @@ def true_peak(x, sr, scratch=None):
 
 
 def r128_scratch_doubles(n, Cc, sr):
-    v = int(_lib.load().wun_loudness_r128_scratch_doubles(int(n), int(Cc), int(sr)))
-    if v < 0:
-        _lib.check(v)
-    return v
+    return _lib.count(_lib.load().wun_loudness_r128_scratch_doubles(int(n), int(Cc), int(sr)))
 
 
 def r128(x, sr, return_short_term=False, scratch=None):

@@ -19,8 +19,6 @@ together (the header's definition): v_s = mean_c |y_s|^2, R_s[k] = sum_f y_s y_s
 Cxx = sum_s v_s R_s + sqrt(em_eps) I, y_s <- v_s R_s Cxx^-1 X, in float64 with the spectra kept in float32.  There is no global
 rescaling of the mix (norbert's max_abs): the float64 algebra does not need it.  iterations = 0 is the soft mask, bit for bit.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -89,8 +87,7 @@ class SoftMaskFilter(object):
         with torch.cuda.device(dev):
             _lib.check(entry(
                 mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps,
-                table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(), _lib.stream(dev)))
 
     def apply(self, mix, estimates):
         """mix [n, C], estimates [S, n, C] (tensors of one device, or arrays) -> the filtered estimates, float32 [S, n, C] on
@@ -203,8 +200,7 @@ class WienerFilter(SoftMaskFilter):
         with torch.cuda.device(dev):
             _lib.check(entry(
                 mix.data_ptr(), estimates.data_ptr(), S, n, Cn, self.n_fft, self.hop, self.power, self.eps, self.iterations,
-                self.em_eps, table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                self.em_eps, table(self.n_fft, dev).data_ptr(), out.data_ptr(), scratch.data_ptr(), _lib.stream(dev)))
 
     def _refine_cpu(self, yre, yim, xre, xim):
         """The EM steps in float64 on float32 spectra: y [S, C, F, K], X [C, F, K]; closed forms for C = 1 and 2."""

@@ -12,9 +12,6 @@ import torch
 
 from . import _lib
 
-_TABLES = {}     # (up, down, device) -> device tensor holding the phase-major fp32 filter table
-
-
 def ratio(orig_sr, new_sr):
     """(up, down) = new_sr / orig_sr reduced by their gcd (wun_resample_ratio)."""
     up, down = C.c_int32(), C.c_int32()
@@ -24,28 +21,21 @@ def ratio(orig_sr, new_sr):
 
 def frames(n_in, up, down):
     """ceil(n_in * up / down): the length rule of librosa and scipy (wun_resample_frames)."""
-    n = int(_lib.load().wun_resample_frames(int(n_in), int(up), int(down)))
-    if n < 0:
-        _lib.check(n)
-    return n
+    return _lib.count(_lib.load().wun_resample_frames(int(n_in), int(up), int(down)))
 
 
 def design(up, down):
     """The phase-major fp32 filter table of (up, down) as a numpy array [up, K] (wun_resample_design)."""
     lib = _lib.load()
-    n = int(lib.wun_resample_table_floats(int(up), int(down)))
-    if n < 0:
-        _lib.check(n)
+    n = _lib.count(lib.wun_resample_table_floats(int(up), int(down)))
     table = np.zeros(n, np.float32)
     _lib.check(lib.wun_resample_design(int(up), int(down), table.ctypes.data_as(C.POINTER(C.c_float)), n))
     return table.reshape(int(up), n // int(up))
 
 
 def _table(up, down, device):
-    key = (up, down, str(device))
-    if key not in _TABLES:
-        _TABLES[key] = torch.from_numpy(design(up, down)).to(device)
-    return _TABLES[key]
+    """The device tensor holding the phase-major fp32 filter table of (up, down), uploaded once per device."""
+    return _lib.device_table(("resample", up, down), device, lambda: design(up, down))
 
 
 def _map_channels_host(x, c_out):
@@ -76,7 +66,7 @@ def resample_into(x, y, y_offset, n_out, up, down):
     if x.is_cuda:
         tab = _table(up, down, x.device) if up != down else None
         with torch.cuda.device(x.device):
-            stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            stream = _lib.stream(x.device)
             _lib.check(_lib.load().wun_resample(x.data_ptr(), n_in, int(x.shape[1]), y.data_ptr(), y_offset, n_out,
                                                 int(y.shape[1]), tab.data_ptr() if tab is not None else None,
                                                 int(up), int(down), stream))

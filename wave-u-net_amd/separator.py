@@ -245,7 +245,7 @@ class UnetAudioSeparator(object):
 
     # ------------------------------------------------------------------ forward
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._dev()).cuda_stream)
+        return _lib.stream(self._dev())
 
     def get_output(self, input, training, return_spectrogram=False, reuse=True):
         """UnetAudioSeparator.py:85-144.  input: [batch, num_samples, num_channels] float32

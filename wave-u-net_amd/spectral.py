@@ -58,8 +58,7 @@ _ENTRIES = {
             "loss_terms": "wun_spectral_loss_terms_fft", "loss_terms_scratch": "wun_spectral_terms_fft_scratch_floats",
             "loss_mel": "wun_spectral_loss_mel_fft", "loss_mel_scratch": "wun_spectral_mel_fft_scratch_floats"},
 }
-_TABLES = {}     # (transform, n_fft, device) -> device tensor holding the transform's table
-_MEL_TABLES = {}  # (n_fft, sample_rate, n_mels, fmin, fmax, norm, device) -> device tensor holding the mel table's words
+_TABLES = _lib._DEVICE_TABLES     # the shared cache: (transform, n_fft, device) -> device tensor holding the transform's table
 _MEL_NORMS = {None: 0, "none": 0, 0: 0, "area": 1, 1: 1}
 
 
@@ -73,19 +72,14 @@ def entry(transform, op):
 def _design(transform, n_fft):
     floats, fill, lead = _ENTRIES[transform]["table"]
     lib = _lib.load()
-    n = int(getattr(lib, floats)(int(n_fft)))
-    if n < 0:
-        _lib.check(n)
+    n = _lib.count(getattr(lib, floats)(int(n_fft)))
     table = np.zeros(n, np.float32)
     _lib.check(getattr(lib, fill)(int(n_fft), table.ctypes.data_as(C.POINTER(C.c_float)), n))
     return table.reshape(lead, int(n_fft), -1) if transform == "gemm" else table.reshape(lead, int(n_fft))
 
 
 def _device_table(transform, n_fft, device):
-    key = (transform, int(n_fft), str(device))
-    if key not in _TABLES:
-        _TABLES[key] = torch.from_numpy(_design(transform, n_fft)).to(device)
-    return _TABLES[key]
+    return _lib.device_table((transform, int(n_fft)), device, lambda: _design(transform, n_fft))
 
 
 def design(n_fft):
@@ -109,20 +103,13 @@ def _fft_table(n_fft, device):
 
 def count(transform, op, *args):
     """A frame or float count of the library; its negative values are error codes."""
-    n = int(entry(transform, op)[0](*args))
-    if n < 0:
-        _lib.check(n)
-    return n
+    return _lib.count(entry(transform, op)[0](*args))
 
 
 def frames(n, n_fft, hop, transform="gemm"):
     """Frames of n samples: 1 + (n - n_fft) // hop, no padding (wun_stft_frames; with transform="fft" wun_fft_frames, n_fft up
     to 8192)."""
     return count(transform, "frames", int(n), int(n_fft), int(hop))
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _audio(x, what):
@@ -144,7 +131,7 @@ def stft_magnitude(x, n_fft, hop, transform="gemm"):
     mags = torch.empty((S, B, Cn, F, int(n_fft) // 2 + 1), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(fn(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), table(n_fft, x.device).data_ptr(), mags.data_ptr(),
-                      _stream(x.device)))
+                      _lib.stream(x.device)))
     return mags
 
 
@@ -159,9 +146,7 @@ def mel_design(n_fft, sample_rate, n_mels, fmin=0.0, fmax=None, norm=None):
     float32 w0[K] and w1[K], lo[n_mels], hi[n_mels].  ValueError for what the library refuses -- an empty band among it."""
     key = _mel_key(n_fft, sample_rate, n_mels, fmin, fmax, norm)
     lib = _lib.load()
-    n = int(lib.wun_mel_table_floats(key[0], key[2]))
-    if n < 0:
-        _lib.check(n)
+    n = _lib.count(lib.wun_mel_table_floats(key[0], key[2]))
     table = np.zeros(n, np.float32)
     _lib.check(lib.wun_mel_design(key[0], key[1], key[2], key[3], key[4], key[5], table.ctypes.data_as(C.POINTER(C.c_float)), n))
     return table.view(np.int32)
@@ -187,10 +172,8 @@ def mel_filterbank(n_fft, sample_rate, n_mels, fmin=0.0, fmax=None, norm=None):
 
 
 def _mel_table(n_fft, sample_rate, n_mels, fmin, fmax, norm, device):
-    key = _mel_key(n_fft, sample_rate, n_mels, fmin, fmax, norm) + (str(device),)
-    if key not in _MEL_TABLES:
-        _MEL_TABLES[key] = torch.from_numpy(mel_design(n_fft, sample_rate, n_mels, fmin, fmax, norm)).to(device)
-    return _MEL_TABLES[key]
+    key = ("mel",) + _mel_key(n_fft, sample_rate, n_mels, fmin, fmax, norm)
+    return _lib.device_table(key, device, lambda: mel_design(n_fft, sample_rate, n_mels, fmin, fmax, norm))
 
 
 def mel_spectrogram(x, n_fft, hop, n_mels, sample_rate, fmin=0.0, fmax=None, norm=None, transform="gemm"):
@@ -202,7 +185,7 @@ def mel_spectrogram(x, n_fft, hop, n_mels, sample_rate, fmin=0.0, fmax=None, nor
     out = torch.empty(mags.shape[:4] + (int(n_mels),), dtype=torch.float32, device=mags.device)
     with torch.cuda.device(mags.device):
         _lib.check(_lib.load().wun_op_mel_project(mags.data_ptr(), mags.numel() // mags.shape[4], int(mags.shape[4]), int(n_mels),
-                                                  table.data_ptr(), out.data_ptr(), _stream(mags.device)))
+                                                  table.data_ptr(), out.data_ptr(), _lib.stream(mags.device)))
     return out
 
 
@@ -233,7 +216,7 @@ def stft(x, n_fft, hop, centered=False, transform="gemm"):
     im = torch.empty_like(re)
     with torch.cuda.device(x.device):
         _lib.check(fn(x.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), lead, F, table(n_fft, x.device).data_ptr(), re.data_ptr(),
-                      im.data_ptr(), _stream(x.device)))
+                      im.data_ptr(), _lib.stream(x.device)))
     return re, im
 
 
@@ -256,7 +239,7 @@ def istft(re, im, length, n_fft, hop, centered=False, transform="gemm"):
     y = torch.empty((S, B, int(length), Cn), dtype=torch.float32, device=re.device)
     with torch.cuda.device(re.device):
         _lib.check(fn(re.data_ptr(), im.data_ptr(), S, B, int(length), Cn, int(n_fft), int(hop), lead, F,
-                      table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
+                      table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _lib.stream(re.device)))
     return y
 
 
@@ -279,7 +262,7 @@ def istft_tf(re, im, n_fft, hop, transform="gemm"):
     y = torch.empty((S, B, T, Cn), dtype=torch.float32, device=re.device)
     with torch.cuda.device(re.device):
         _lib.check(fn(re.data_ptr(), im.data_ptr(), S, B, T, Cn, int(n_fft), int(hop), F,
-                      table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _stream(re.device)))
+                      table(n_fft, re.device).data_ptr(), y.data_ptr(), scratch.data_ptr(), _lib.stream(re.device)))
     return y
 
 
@@ -457,7 +440,7 @@ class SpectralLoss(object):
         fn, table = entry(self.transform, "loss" if self._terms is None else "loss_terms" if self._mel is None else "loss_mel")
         tabs = (C.c_void_p * max(nres, 1))(*[table(n, dev).data_ptr() for n, _ in self.resolutions])
         head = (outputs.data_ptr(), targets.data_ptr(), S, B, T, Cn, self.mse_weight, nres, self._n_fft, self._hop, self._w)
-        tail = (tabs, d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(), _stream(dev))
+        tail = (tabs, d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(), _lib.stream(dev))
         with torch.cuda.device(dev):
             if self._terms is None:
                 _lib.check(fn(*(head + tail)))
@@ -601,9 +584,7 @@ def griffin_lim_call(mag, init_re, init_im, y_init, T, n_fft, hop, lead, iterati
     R, F, K = (int(v) for v in mag.shape)
     dev = mag.device
     if scratch is None:
-        n = int(lib.wun_griffin_lim_scratch_floats(R, 1, int(T), 1, int(n_fft), int(hop), int(lead), F, int(momentum != 0.0)))
-        if n < 0:
-            _lib.check(n)
+        n = _lib.count(lib.wun_griffin_lim_scratch_floats(R, 1, int(T), 1, int(n_fft), int(hop), int(lead), F, int(momentum != 0.0)))
         scratch = torch.empty(n, dtype=torch.float32, device=dev)
     if y is None:
         y = torch.empty((R, int(T)), dtype=torch.float32, device=dev)
@@ -611,7 +592,7 @@ def griffin_lim_call(mag, init_re, init_im, y_init, T, n_fft, hop, lead, iterati
     with torch.cuda.device(dev):
         _lib.check(lib.wun_griffin_lim(ptr(mag), ptr(init_re), ptr(init_im), ptr(y_init), R, 1, int(T), 1, int(n_fft), int(hop),
                                        int(lead), F, int(iterations), float(momentum), _fft_table(n_fft, dev).data_ptr(), ptr(y),
-                                       ptr(inconsistency), ptr(scratch), _stream(dev)))
+                                       ptr(inconsistency), ptr(scratch), _lib.stream(dev)))
     return y
 
 

@@ -74,9 +74,7 @@ class UnetSpectrogramSeparator(object):
 
         self._lib = _lib.load()                                  # raises if libwun.so is missing
         self._scfg = _lib.WunSpecConfig(self.num_layers, self.num_initial_filters, len(self.source_names), self.frame_len, self.hop)
-        n = int(self._lib.wun_spec_num_tensors(C.byref(self._scfg)))
-        if n < 0:
-            _lib.check(n)
+        n = _lib.count(self._lib.wun_spec_num_tensors(C.byref(self._scfg)))
         tensors, info = [], _lib.WunTensorInfo()
         for i in range(n):
             _lib.check(self._lib.wun_spec_tensor(C.byref(self._scfg), i, C.byref(info)))
@@ -106,10 +104,7 @@ class UnetSpectrogramSeparator(object):
 
     def frames(self, num_samples):
         """F of num_samples samples; ValueError where the network cannot take the length (:69)."""
-        F = int(self._lib.wun_spec_frames(C.byref(self._scfg), int(num_samples)))
-        if F < 0:
-            _lib.check(F)
-        return F
+        return _lib.count(self._lib.wun_spec_frames(C.byref(self._scfg), int(num_samples)))
 
     # ------------------------------------------------------------------ variables
     def _dev(self):
@@ -194,9 +189,7 @@ class UnetSpectrogramSeparator(object):
         self._ensure_variables()
         S, K = len(self.source_names), self.frame_len // 2 + 1
         if (B, T) not in self._ws:
-            n = int(self._lib.wun_spec_workspace_floats(C.byref(self._scfg), B, T))
-            if n < 0:
-                _lib.check(n)
+            n = _lib.count(self._lib.wun_spec_workspace_floats(C.byref(self._scfg), B, T))
             self._ws[(B, T)] = torch.empty(n, dtype=torch.float32, device=dev)
         key = (B, T, bool(return_spectrogram))
         if key not in self._outs:
@@ -215,18 +208,16 @@ class UnetSpectrogramSeparator(object):
             _lib.check(self._lib.wun_spec_forward(
                 C.byref(self._scfg), self.params.data_ptr(), mix.data_ptr(), B, T, spectral._fft_table(self.frame_len, dev).data_ptr(),
                 None if return_spectrogram else out.data_ptr(), out.data_ptr() if return_spectrogram else None,
-                self._ws[(B, T)].data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                self._ws[(B, T)].data_ptr(), _lib.stream(dev)))
         return {name: out[i] for i, name in enumerate(self.source_names)}
 
     # ------------------------------------------------------------------ the training step
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._dev()).cuda_stream)
+        return _lib.stream(self._dev())
 
     def _train_workspace(self, B, T):
         if (B, T) not in self._tws:
-            n = int(self._lib.wun_spec_train_workspace_floats(C.byref(self._scfg), B, T))
-            if n < 0:
-                _lib.check(n)
+            n = _lib.count(self._lib.wun_spec_train_workspace_floats(C.byref(self._scfg), B, T))
             self._tws[(B, T)] = torch.empty(n, dtype=torch.float32, device=self._dev())
         return self._tws[(B, T)]
 
@@ -269,9 +260,7 @@ class UnetSpectrogramSeparator(object):
     def _scratch(self, kind, B, T):
         if (kind, B, T) not in self._scr:
             query = self._lib.wun_spec_train_audio_scratch_floats if kind == "audio" else self._lib.wun_spec_backward_scratch_floats
-            n = int(query(C.byref(self._scfg), B, T))
-            if n < 0:
-                _lib.check(n)
+            n = _lib.count(query(C.byref(self._scfg), B, T))
             self._scr[(kind, B, T)] = torch.empty(n, dtype=torch.float32, device=self._dev())
         return self._scr[(kind, B, T)]
 

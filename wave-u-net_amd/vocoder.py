@@ -15,10 +15,7 @@ assert JOB_DTYPE.itemsize == C.sizeof(_lib.WunStretchJob)
 
 def frames(n_in, num, den):
     """ceil(n_in * den / num): the longest output of a span of n_in frames at the tempo num / den (wun_time_stretch_frames)."""
-    n = int(_lib.load().wun_time_stretch_frames(int(n_in), int(num), int(den)))
-    if n < 0:
-        _lib.check(n)
-    return n
+    return _lib.count(_lib.load().wun_time_stretch_frames(int(n_in), int(num), int(den)))
 
 
 def job_table(jobs):
@@ -32,10 +29,8 @@ def job_table(jobs):
 def scratch_floats(table, channels, n_fft, hop):
     """Floats of scratch for this job table (wun_time_stretch_scratch_floats)."""
     table = np.ascontiguousarray(table, JOB_DTYPE)
-    n = int(_lib.load().wun_time_stretch_scratch_floats(table.ctypes.data, len(table), int(channels), int(n_fft), int(hop)))
-    if n < 0:
-        _lib.check(n)
-    return n
+    return _lib.count(_lib.load().wun_time_stretch_scratch_floats(table.ctypes.data, len(table), int(channels), int(n_fft),
+                                                                  int(hop)))
 
 
 def run(table, channels, n_fft, hop, scratch, device):
@@ -45,7 +40,7 @@ def run(table, channels, n_fft, hop, scratch, device):
     device = torch.device(device)
     tab = spectral._fft_table(int(n_fft), device)
     with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        stream = _lib.stream(device)
         _lib.check(_lib.load().wun_time_stretch(table.ctypes.data, len(table), int(channels), int(n_fft), int(hop), tab.data_ptr(),
                                                 scratch.data_ptr(), stream))
 
@@ -87,9 +82,7 @@ def pitch_shift(x, up, down, n_fft=2048, hop=512):
     up / down to T."""
     _check_audio("pitch_shift", x)
     T, ch = int(x.shape[-2]), int(x.shape[-1])
-    n_src = int(_lib.load().wun_speed_source_frames(T, int(up), int(down)))
-    if n_src < 0:
-        _lib.check(n_src)
+    n_src = _lib.count(_lib.load().wun_speed_source_frames(T, int(up), int(down)))
     s = time_stretch(x, up, down, n_fft, hop, length=n_src)
     y = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
     sv, yv = s.view(-1, n_src, ch), y.view(-1, T, ch)

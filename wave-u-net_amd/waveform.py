@@ -19,7 +19,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .spectral import _audio, _stream
+from .spectral import _audio
 
 TERMS = ("mse", "l1", "si_sdr", "snr")       # the order of the term slots of wun_waveform_loss's losses
 METRICS = ("mse", "si_sdr")                  # model_config["validation_metric"]
@@ -83,9 +83,7 @@ class WaveformLoss(object):
 
     def scratch_floats(self, shape):
         S, B, T, Cn = (int(v) for v in shape)
-        n = int(_lib.load().wun_waveform_scratch_floats(S, B, T, Cn, C.byref(self._terms)))
-        if n < 0:
-            _lib.check(n)
+        n = _lib.count(_lib.load().wun_waveform_scratch_floats(S, B, T, Cn, C.byref(self._terms)))
         self._S = S
         return n
 
@@ -104,7 +102,7 @@ class WaveformLoss(object):
         with torch.cuda.device(dev):
             _lib.check(_lib.load().wun_waveform_loss(
                 outputs.data_ptr(), targets.data_ptr(), S, B, T, Cn, C.byref(self._terms), 1 if accumulate else 0,
-                d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(), _stream(dev)))
+                d_outputs.data_ptr() if d_outputs is not None else None, losses.data_ptr(), scratch.data_ptr(), _lib.stream(dev)))
 
     def loss_and_grad(self, outputs, targets, grad=True):
         """(losses, d_outputs): losses float32 [5 + 2 S] on the device = [total, mse, l1, si_sdr, snr, SI-SDR dB per source, SNR
