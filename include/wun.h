@@ -1659,6 +1659,9 @@ int wun_op_btc_to_ncw(const float* src, float* dst, int B, int T, int C, int pit
 #define WUN_PATH_NOT_FUSED     8
 #define WUN_PATH_FUSED         9
 #define WUN_PATH_FIRST_CONV    10
+#define WUN_OP_WGRAD             8   /* direct epilogue / split reduction (wun_op_wgrad_ex) */
+#define WUN_PATH_WGRAD_DIRECT  11
+#define WUN_PATH_WGRAD_SPLIT   12
 int wun_op_last_path(int op);
 
 /* The bf16 mode's conv as a single operator (wun_op_conv1d semantics, Cin >= 8, K <= 15): x and w
@@ -1725,6 +1728,60 @@ int wun_op_conv_bf16_choice_ok(const wun_op_conv_bf16_desc* desc, int code);
 int wun_op_first_conv(const float* x, const float* w, const float* bias, void* y, void* dec, int batch, int cin, int cout, int k,
                       int t_in, int t_out, int stride, int pad_left, int lrelu, int out_bf16, int x_pitch, int y_pitch,
                       int dec_pitch, void* stream);
+
+/* A layer's weight / bias gradient exactly as the plan launches it (run_wgrad / run_narrow_wgrad), on rows THE CALLER made:
+ * nothing is repacked or converted, the entry fills the launchers' argument blocks and calls them.  One or two PARTS (a down
+ * level: its decimated and its window positions) over one virtual channel-concat of x0 [B][C0][x0_pitch] and x1 [B][C1][x1_pitch]
+ * (C1 = 0: x1 unused); part p reads the window [off, off + Tin[p]) of every row (off = x0_off[p] / x1_off[p]; what lies before
+ * and behind it in the row is activations of other launches: loaded perhaps, never summed) against dz_p [B][N][dz_pitch[p]]:
+ *   dW[k][c][n] = sum_p sum_{b, q < Tq[p]} win_p[b][c][S q + k - shift[p]] dz_p[b][n][q]   (win_p zero outside [0, Tin[p]))
+ *   db[n]       = sum_p sum_{b, q} dz_p[b][n][q],          S = 1 (loader 0, direct) or 2 (loader 1, de-interleaving).
+ * family: WUN_WGRAD_LDS = wgrad_mfma_kernel, WUN_WGRAD_WIN = the register-window kernel, WUN_WGRAD_BF16 = the bf16 kernel
+ * (rows_bf16 must be 1: x0, x1 and dz hold bfloat16 elements, pitches and offsets in elements), WUN_WGRAD_NARROW = the
+ * direct-reduction kernels.  grads + 0: the weights [K][C0 + C1][N] with the bias [N] directly behind them -- the plan's arena
+ * layout; `accumulate` adds to what the block holds (grad_acc_add: bit-equal to float32 old + stored).  nsplit[p]: requested
+ * reduction splits of part p, 0 = the library's choice, else min(request, the part's work units).  Total split count 1: the
+ * direct epilogue writes the block; otherwise the parts' splits lie one after the other in `scratch` (device floats, at least
+ * wun_op_wgrad_ex_scratch(desc)) and ONE reduction sums them.  Afterwards wun_op_last_path(WUN_OP_WGRAD) is
+ * WUN_PATH_WGRAD_DIRECT or WUN_PATH_WGRAD_SPLIT and wun_op_wgrad_last_splits() the total split count.
+ * force_mtw / force_nw: as wun_op_force_wgrad_variant takes them for the family (0, 0 = the plan's default; the bf16 family
+ * mtw in {4, 8}; the window family mtw = column groups per workgroup 1 / 2, nw = column tiles per wave); a geometry that does
+ * not resolve for every part is WUN_ERR_UNSUPPORTED.  Two parts share one tile geometry (LDS / bf16 family: the default is
+ * lowered until they agree, as the plan does).
+ * WUN_WGRAD_NARROW: N = planes * Nper dz rows; plane s of part p is dz_p + s * zss elements; its block {weights
+ * [K][C0 + C1][Nper], bias [Nper]} starts at grads + plane_off[s] (planes in 1..4).  et: bit 0 (value 1) = x0, bit 1 (value 2) = x1,
+ * bit 2 (value 4) = dz hold bf16 (instantiated: 0, 2, 4; the streaming form of the audio-input conv 0, 4); rows_bf16 must
+ * be 0.  No direct epilogue: always the split reduction.
+ * REFUSED, before any GPU work (nothing is computed by another kernel instead) -- WUN_ERR_INVALID: a null required pointer, a
+ * size below 1, nparts outside {1, 2}, a loader outside {0, 1}, a negative offset / shift / split request, shift >= K, a window
+ * that does not fit its pitch, Tq above dz_pitch, a pitch or zss that is not a multiple of 4 elements, x0 / x1 / dz off 16
+ * bytes, rows_bf16 that contradicts the family, planes outside 1..4 or not dividing N, unknown et bits.  WUN_ERR_UNSUPPORTED:
+ * what the family's support predicate or launcher refuses (window: K outside {15, 5}, K = 5 with loader 1, fewer than 8
+ * channels or 16 columns, K = 15 with (C0 + C1) % 8 or, with two sources, C0 % 8; bf16: K > 15, fewer than 8 channels, odd C0
+ * with two sources; LDS: a row group the staging registers cannot hold; narrow: (C0 + C1) * N > 256, K > 15, an et the
+ * kernels are not instantiated for); a forced geometry that does not resolve, or two parts whose splits would not share one
+ * partial layout; a forced geometry with the narrow family is WUN_ERR_INVALID; and the combinations the plan never builds:
+ * two parts with two sources (C1 > 0), and shift > 0 together with a nonzero window offset.
+ * Launches on `stream`, does not synchronise. */
+#define WUN_WGRAD_LDS    0
+#define WUN_WGRAD_WIN    1
+#define WUN_WGRAD_BF16   2
+#define WUN_WGRAD_NARROW 3
+typedef struct wun_op_wgrad_desc {
+    int32_t family, B, C0, C1, N, K, x0_pitch, x1_pitch, rows_bf16, nparts;
+    int32_t loader[2], x0_off[2], x1_off[2], Tin[2], shift[2], Tq[2], dz_pitch[2], nsplit[2];   /* per part */
+    int32_t accumulate, force_mtw, force_nw;
+    int32_t planes, zss, et, plane_off[4];                           /* WUN_WGRAD_NARROW */
+} wun_op_wgrad_desc;
+int32_t wun_op_wgrad_abi_size(void);   /* sizeof(wun_op_wgrad_desc) */
+int64_t wun_op_wgrad_ex_scratch(const wun_op_wgrad_desc* desc);
+int wun_op_wgrad_ex(const wun_op_wgrad_desc* desc, const void* x0, const void* x1, const void* dz_part0, const void* dz_part1,
+                    float* grads, float* scratch, void* stream);
+/* Host only: the work units of part `part` under the descriptor's family and geometry (the most splits it can be granted);
+ * negative for a descriptor wun_op_wgrad_ex would refuse on shape grounds (pointers play no part). */
+int wun_op_wgrad_max_units(const wun_op_wgrad_desc* desc, int part);
+/* Total split count of the calling thread's last wun_op_wgrad_ex launch (0 before the first). */
+int wun_op_wgrad_last_splits(void);
 
 /* Lane layout probe of v_mfma_f32_16x16x32_bf16: d[16][16] = bf16(a[16][32]) * bf16(b[32][16]) (row-major). */
 int wun_op_mfma_bf16_probe(const float* a, const float* b, float* d, void* stream);

@@ -85,13 +85,22 @@ class WunOpConvBf16Desc(C.Structure):
         "x0_pitch", "x1_pitch", "x_off", "y0_pitch", "y0_off", "y1_pitch", "y1_off", "dec_pitch")]
 
 
-BF16_VARIANT_BASE = 1000                            # WUN_BF16_VARIANT_BASE: wun_op_force_conv_variant(base + tile code, 0)
+class WunOpWgradDesc(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("family", "B", "C0", "C1", "N", "K", "x0_pitch", "x1_pitch", "rows_bf16", "nparts")] +
+                [(n, C.c_int32 * 2) for n in ("loader", "x0_off", "x1_off", "Tin", "shift", "Tq", "dz_pitch", "nsplit")] +
+                [(n, C.c_int32) for n in ("accumulate", "force_mtw", "force_nw", "planes", "zss", "et")] +
+                [("plane_off", C.c_int32 * 4)])
+
+
+WGRAD_LDS, WGRAD_WIN, WGRAD_BF16, WGRAD_NARROW = range(4)     # wun_op_wgrad_desc.family
+BF16_VARIANT_BASE = 1000                           # WUN_BF16_VARIANT_BASE: wun_op_force_conv_variant(base + tile code, 0)
 
 # wun_op_last_path: operators and forms (WUN_OP_*, WUN_PATH_* of include/wun.h)
 (OP_UPSAMPLE, OP_UPSAMPLE_BACKWARD, OP_INTERP_GRAD, OP_HEAD_FORWARD, OP_HEAD_DFEAT, OP_CONV_EPILOGUE, OP_BTC_TO_NCW) = range(7)
 OP_FIRST_CONV = 7
+OP_WGRAD = 8
 (PATH_NONE, PATH_SCALAR, PATH_VEC4, PATH_VEC8_BF16, PATH_ONE_STAGE, PATH_TWO_STAGE, PATH_GENERIC, PATH_FOUR_POSITION,
- PATH_NOT_FUSED, PATH_FUSED, PATH_FIRST_CONV) = range(11)
+ PATH_NOT_FUSED, PATH_FUSED, PATH_FIRST_CONV, PATH_WGRAD_DIRECT, PATH_WGRAD_SPLIT) = range(13)
 
 BLEND_NO_RISE, BLEND_NO_FALL = 1, 2                 # wun_blend_window.flags
 SNIPPET_SWAP, SNIPPET_NEGATE = 1, 2                 # wun_snippet_source.flags
@@ -340,6 +349,11 @@ _SIGS = {
     "wun_op_conv_bf16_ex": (C.c_int, [C.POINTER(WunOpConvBf16Desc)] + [_P] * 11),
     "wun_op_conv_bf16_choice_ok": (C.c_int, [C.POINTER(WunOpConvBf16Desc), C.c_int]),
     "wun_op_first_conv": (C.c_int, [_P] * 5 + [C.c_int] * 13 + [_P]),
+    "wun_op_wgrad_abi_size": (C.c_int32, []),
+    "wun_op_wgrad_ex_scratch": (C.c_int64, [C.POINTER(WunOpWgradDesc)]),
+    "wun_op_wgrad_ex": (C.c_int, [C.POINTER(WunOpWgradDesc)] + [_P] * 7),
+    "wun_op_wgrad_max_units": (C.c_int, [C.POINTER(WunOpWgradDesc), C.c_int]),
+    "wun_op_wgrad_last_splits": (C.c_int, []),
     "wun_profile_begin": (C.c_int, []),
     "wun_profile_end": (C.c_int, [C.c_char_p, C.c_int64]),
     "wun_abi_sizes": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
@@ -358,7 +372,7 @@ _ABI_SIZES = (
     ("wun_abi_sizes", WunConfig), ("wun_abi_sizes", WunPlanInfo), ("wun_abi_sizes", WunTensorInfo),
     ("wun_spec_abi_size", WunSpecConfig), ("wun_spec_train_abi_size", WunSpecTrainConfig), ("wun_mel_abi_size", WunMelTerms),
     ("wun_snippet_abi_size", WunSnippetSource), ("wun_op_head_abi_size", WunOpHeadDesc),
-    ("wun_op_conv_bf16_abi_size", WunOpConvBf16Desc), ("wun_speed_abi_size", WunSpeedBank),
+    ("wun_op_conv_bf16_abi_size", WunOpConvBf16Desc), ("wun_op_wgrad_abi_size", WunOpWgradDesc), ("wun_speed_abi_size", WunSpeedBank),
     ("wun_stretch_abi_size", WunStretchJob), ("wun_optim_abi_size", WunOptimConfig), ("wun_blend_abi_size", WunBlendWindow))
 _DEVICE_TABLES = {}    # device_table's cache
 

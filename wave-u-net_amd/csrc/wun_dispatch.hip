@@ -276,7 +276,7 @@ hipError_t conv_dispatch(const wun_plan* p, ConvArgs a, float* part, long long c
 // All parts of one layer's weight gradient (a down level has two: the decimated and the window
 // positions) use ONE tile geometry, so their splits land in one tile-major partial buffer that a
 // single reduction sums.  Returns false if the parts do not resolve to the same geometry.
-static bool wgrad_common_geom(WgradArgs* parts, int nparts, int mtw, int nw) {
+bool wgrad_common_geom(WgradArgs* parts, int nparts, int mtw, int nw) {
     int m0 = 0, n0 = 0;
     for (int i = 0; i < nparts; ++i) {
         parts[i].force_mtw = mtw; parts[i].force_nw = nw;

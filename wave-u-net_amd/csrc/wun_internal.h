@@ -291,6 +291,11 @@ int wgrad_max_units(const WgradArgs& a, const WunSwitches& sw);
 
 int  wgrad_pick_nsplit(const WgradArgs& a, const WunSwitches& sw);
 hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s, const WunSwitches& sw);
+// host only: would launch_wgrad accept `a` (family by a.bf16 / a.win; pointers, shape, resolved geometry)?  The launchers'
+// own refusals, asked before any GPU work (wun_op_wgrad_ex).
+bool wgrad_launch_ok(const WgradArgs& a, const WunSwitches& sw);
+bool wgrad_bf16_launch_ok(const WgradArgs& a);
+bool wgrad_win_launch_ok(const WgradArgs& a, const WunSwitches& sw);
 void wgrad_resolved_geom(const WgradArgs& a, int& mtw, int& nw);
 long long wgrad_partial_floats(const WgradArgs& a, const WunSwitches& sw);
 hipError_t launch_wgrad_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
@@ -390,6 +395,7 @@ int narrow_wgrad_units(const NarrowWgradArgs& a);
 int narrow_wgrad_pick_nsplit(const NarrowWgradArgs& a, const WunSwitches& sw);
 long long narrow_wgrad_partial_floats(const NarrowWgradArgs& a);
 hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitches& sw);
+bool narrow_wgrad_launch_ok(const NarrowWgradArgs& a, const WunSwitches& sw);      // host only: would launch_narrow_wgrad accept `a`?
 hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* partial, int nsplit, float* grads,
                                       const long long* woff, const long long* boff, hipStream_t s, bool accum = false);
 size_t mix_grad_lds_bytes(const MixGradArgs& a);

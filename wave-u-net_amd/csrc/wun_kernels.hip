@@ -1920,6 +1920,20 @@ hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s, const WunSwitches& sw
     return hipErrorInvalidValue;
 }
 
+// the refusals of launch_wgrad (and of the family launchers it forwards to) without the launch
+bool wgrad_launch_ok(const WgradArgs& a, const WunSwitches& sw) {
+    if (a.bf16) return wgrad_bf16_launch_ok(a);
+    if (a.win) return wgrad_win_launch_ok(a, sw);
+    if ((a.pitch0 & 3) || (a.bs0 & 3) || (reinterpret_cast<uintptr_t>(a.src0) & 15) || a.pitch0 < 4) return false;
+    if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || a.pitch1 < 4)) return false;
+    if ((a.dzpitch & 3) || (a.dzbs & 3) || (reinterpret_cast<uintptr_t>(a.dz) & 15) || a.dzpitch < 4) return false;
+    const WgradGeom g = wgrad_geom(a);
+    if ((long long)g.nChMax * g.XW4 > (long long)WUN_WG_XIT * 256) return false;
+    if (g.lds > 160 * 1024) return false;
+    return (g.NW <= 3 && (g.MTW == 1 || g.MTW == 2 || g.MTW == 4 || g.MTW == 6)) ||
+           ((g.NW == 4 || g.NW == 5) && (g.MTW == 1 || g.MTW == 2 || g.MTW == 4));
+}
+
 void wgrad_resolved_geom(const WgradArgs& a, int& mtw, int& nw) {
     if (a.win) { mtw = a.force_mtw; nw = a.force_nw; return; }      // (own geometry; parts need not agree)
     if (a.bf16) { const WgradBfGeom b = wgrad_bf16_geom(a); mtw = b.MTW; nw = b.NW; return; }

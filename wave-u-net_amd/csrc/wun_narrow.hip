@@ -447,6 +447,14 @@ hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitch
     return hipGetLastError();
 }
 
+// the refusals of launch_narrow_wgrad without the launch
+bool narrow_wgrad_launch_ok(const NarrowWgradArgs& a, const WunSwitches& sw) {
+    if (!narrow_wgrad_supported(a)) return false;
+    if (narrow_stream_ok(a, sw)) return (a.et & ~4) == 0;
+    if (narrow_wgrad_lds(a) > 160 * 1024) return false;
+    return a.et == 0 || a.et == 4 || a.et == 2;
+}
+
 hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* partial, int nsplit, float* grads,
                                       const long long* woff, const long long* boff, hipStream_t s, bool accum) {
     const int P = (int)narrow_wgrad_partial_floats(a);

@@ -27,6 +27,7 @@ static float* g_op_ups_y = nullptr; static const float* g_op_ups_w = nullptr;   
 static int g_op_ups_pitch = 0, g_op_ups_tup = 0;
 static thread_local int t_op_epilogue_path = WUN_PATH_NONE;                     // wun_op_last_path(WUN_OP_CONV_EPILOGUE)
 static thread_local int t_op_first_conv_path = WUN_PATH_NONE;                   // wun_op_last_path(WUN_OP_FIRST_CONV)
+static thread_local int t_op_wgrad_path = WUN_PATH_NONE, t_op_wgrad_splits = 0;  // wun_op_last_path(WUN_OP_WGRAD), wun_op_wgrad_last_splits
 static float* op_scratch() {
     static float* buf = nullptr;
     if (!buf && hipMalloc((void**)&buf, kOpScratchFloats * sizeof(float)) != hipSuccess) {
@@ -501,6 +502,7 @@ extern "C" int wun_op_last_path(int op) {
         case WUN_OP_BTC_TO_NCW: return elementwise_last_path(EW_BTC_TO_NCW);
         case WUN_OP_CONV_EPILOGUE: return t_op_epilogue_path;
         case WUN_OP_FIRST_CONV: return t_op_first_conv_path;
+        case WUN_OP_WGRAD: return t_op_wgrad_path;
         default: return fail(WUN_ERR_INVALID, "unknown operator");
     }
 }
@@ -739,6 +741,181 @@ extern "C" int wun_op_first_conv(const float* x, const float* w, const float* bi
     if (!first_conv_supported(a)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the audio-input conv kernel");
     HIP_TRY(launch_first_conv(a, (hipStream_t)stream));
     t_op_first_conv_path = WUN_PATH_FIRST_CONV;
+    return WUN_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// A layer's weight gradient as the plan launches it (run_wgrad / run_narrow_wgrad of wun_dispatch.hip) on rows the caller made
+// (wun.h: wun_op_wgrad_desc).  Test hook: two sources with crop offsets, windows inside longer rows, two-part launches into
+// one partial buffer, the direct epilogue, the accumulating instantiations, bf16 rows, the narrow kernels' plane / et forms.
+// ---------------------------------------------------------------------------------------
+extern "C" int32_t wun_op_wgrad_abi_size(void) { return (int32_t)sizeof(wun_op_wgrad_desc); }
+
+struct OpWgrad {                 // a checked descriptor as the launchers' argument blocks
+    bool narrow;
+    int nparts, total, units[2];
+    WgradArgs w[2];
+    NarrowWgradArgs nw[2];
+    long long woff[4], boff[4];
+    long long part_floats;       // floats of one split in the partial buffer
+};
+
+// Every check of wun_op_wgrad_ex but the null pointers, then the argument blocks with geometry and split counts as run_wgrad /
+// run_narrow_wgrad settle them.  Null row pointers count as aligned (the host-only callers pass none).  0 = fine.
+static int op_wgrad_build(const wun_op_wgrad_desc* d, const void* x0, const void* x1, const void* dz0, const void* dz1,
+                          const WunSwitches& sw, OpWgrad& o) {
+    if (!d) return fail(WUN_ERR_INVALID, "null argument");
+    if (d->family < WUN_WGRAD_LDS || d->family > WUN_WGRAD_NARROW) return fail(WUN_ERR_INVALID, "unknown kernel family");
+    if (d->B < 1 || d->C0 < 1 || d->C1 < 0 || d->N < 1 || d->K < 1) return fail(WUN_ERR_INVALID, "bad shape");
+    if (d->nparts != 1 && d->nparts != 2) return fail(WUN_ERR_INVALID, "nparts must be 1 or 2");
+    const bool narrow = d->family == WUN_WGRAD_NARROW;
+    if ((d->rows_bf16 != 0) != (d->family == WUN_WGRAD_BF16)) return fail(WUN_ERR_INVALID, "rows_bf16 goes with the bf16 family and no other");
+    if ((d->x0_pitch & 3) || (d->C1 > 0 && (d->x1_pitch & 3))) return fail(WUN_ERR_INVALID, "row pitches must be multiples of 4 elements");
+    if (!aligned16(x0) || (d->C1 > 0 && !aligned16(x1)) || !aligned16(dz0) || (d->nparts == 2 && !aligned16(dz1)))
+        return fail(WUN_ERR_INVALID, "x0 / x1 / dz must be 16-byte aligned");
+    for (int i = 0; i < d->nparts; ++i) {
+        if (d->loader[i] != LOADER_DIRECT && d->loader[i] != LOADER_DEINT) return fail(WUN_ERR_INVALID, "loader must be 0 or 1");
+        if (d->x0_off[i] < 0 || d->x1_off[i] < 0 || d->shift[i] < 0 || d->nsplit[i] < 0) return fail(WUN_ERR_INVALID, "negative offset, shift or split request");
+        if (d->Tin[i] < 1 || d->Tq[i] < 1) return fail(WUN_ERR_INVALID, "bad shape");
+        if (d->shift[i] >= d->K) return fail(WUN_ERR_INVALID, "shift must be below K");
+        if ((long long)d->x0_off[i] + d->Tin[i] > d->x0_pitch || (d->C1 > 0 && (long long)d->x1_off[i] + d->Tin[i] > d->x1_pitch))
+            return fail(WUN_ERR_INVALID, "window does not fit its pitch");
+        if (d->Tq[i] > d->dz_pitch[i] || (d->dz_pitch[i] & 3)) return fail(WUN_ERR_INVALID, "dz_pitch must hold Tq and be a multiple of 4 elements");
+    }
+    int Nper = d->N;
+    if (narrow) {
+        if (d->planes < 1 || d->planes > 4 || d->N % d->planes != 0) return fail(WUN_ERR_INVALID, "planes must be in 1..4 and divide N");
+        if (d->et & ~7) return fail(WUN_ERR_INVALID, "unknown et bits");
+        if (d->zss < 0 || (d->zss & 3)) return fail(WUN_ERR_INVALID, "zss must be a non-negative multiple of 4 elements");
+        if (d->force_mtw != 0 || d->force_nw != 0) return fail(WUN_ERR_INVALID, "the narrow family has no geometry to force");
+        for (int s = 0; s < d->planes; ++s)
+            if (d->plane_off[s] < 0) return fail(WUN_ERR_INVALID, "negative plane offset");
+        Nper = d->N / d->planes;
+    }
+    // ---- what the plan never builds ----
+    if (d->nparts == 2 && d->C1 > 0) return fail(WUN_ERR_UNSUPPORTED, "two parts with two sources: no layer of the plan launches this");
+    for (int i = 0; i < d->nparts; ++i)
+        if (d->shift[i] > 0 && (d->x0_off[i] != 0 || (d->C1 > 0 && d->x1_off[i] != 0)))
+            return fail(WUN_ERR_UNSUPPORTED, "shift > 0 with a nonzero window offset: no layer of the plan launches this");
+    memset(&o, 0, sizeof(o));
+    o.narrow = narrow; o.nparts = d->nparts;
+    const int Ctot = d->C0 + d->C1;
+    if (narrow) {
+        for (int i = 0; i < d->nparts; ++i) {
+            NarrowWgradArgs& n = o.nw[i];
+            n.src0 = reinterpret_cast<const float*>(x0); n.bs0 = (long long)d->C0 * d->x0_pitch; n.pitch0 = d->x0_pitch; n.off0 = d->x0_off[i]; n.C0 = d->C0;
+            if (d->C1 > 0) { n.src1 = reinterpret_cast<const float*>(x1); n.bs1 = (long long)d->C1 * d->x1_pitch; n.pitch1 = d->x1_pitch; n.off1 = d->x1_off[i]; n.C1 = d->C1; }
+            n.Tin = d->Tin[i]; n.shift = d->shift[i]; n.KW = d->K; n.stride = d->loader[i] == LOADER_DEINT ? 2 : 1;
+            n.dz = reinterpret_cast<const float*>(i == 0 ? dz0 : dz1); n.zss = d->zss; n.dzbs = (long long)Nper * d->dz_pitch[i]; n.dzpitch = d->dz_pitch[i];
+            n.N = d->N; n.Nper = Nper; n.Tq = d->Tq[i]; n.B = d->B; n.et = d->et;
+            if (!narrow_wgrad_launch_ok(n, sw)) return fail(WUN_ERR_UNSUPPORTED, "shape or element types not served by the narrow weight-gradient kernels");
+            o.units[i] = narrow_wgrad_units(n);
+            n.nsplit = d->nsplit[i] > 0 ? std::min(d->nsplit[i], o.units[i]) : narrow_wgrad_pick_nsplit(n, sw);
+            o.total += n.nsplit;
+        }
+        for (int s = 0; s < d->planes; ++s) { o.woff[s] = d->plane_off[s]; o.boff[s] = d->plane_off[s] + (long long)d->K * Ctot * Nper; }
+        o.part_floats = narrow_wgrad_partial_floats(o.nw[0]);
+        return WUN_OK;
+    }
+    for (int i = 0; i < d->nparts; ++i) {
+        WgradArgs& w = o.w[i];
+        w.B = d->B; w.loader = d->loader[i];
+        w.src0 = reinterpret_cast<const float*>(x0); w.bs0 = (long long)d->C0 * d->x0_pitch; w.pitch0 = d->x0_pitch; w.off0 = d->x0_off[i]; w.C0 = d->C0;
+        if (d->C1 > 0) { w.src1 = reinterpret_cast<const float*>(x1); w.bs1 = (long long)d->C1 * d->x1_pitch; w.pitch1 = d->x1_pitch; w.off1 = d->x1_off[i]; w.C1 = d->C1; }
+        w.Tin = d->Tin[i]; w.shift = d->shift[i]; w.KW = d->K;
+        w.dz = reinterpret_cast<const float*>(i == 0 ? dz0 : dz1); w.dzbs = (long long)d->N * d->dz_pitch[i]; w.dzpitch = d->dz_pitch[i]; w.N = d->N; w.Tq = d->Tq[i];
+        w.bf16 = w.sbf = d->family == WUN_WGRAD_BF16 ? 1 : 0;
+        w.win = d->family == WUN_WGRAD_WIN ? 1 : 0;
+        w.accum = d->accumulate ? 1 : 0;
+        if (w.bf16 && !wgrad_bf16_supported(w)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the bf16 weight-gradient kernel");
+        if (w.win && !wgrad_win_supported(w)) return fail(WUN_ERR_UNSUPPORTED, "shape not served by the register-window weight-gradient kernel");
+    }
+    if (d->force_mtw < 0 || d->force_nw < 0) return fail(WUN_ERR_INVALID, "negative forced geometry");
+    if (d->family == WUN_WGRAD_WIN) {
+        // own geometry per part (split partials are in the final layout): column groups per workgroup, column tiles per wave
+        if (d->force_mtw > 2 || d->force_nw > (d->K == 15 ? 5 : 6))
+            return fail(WUN_ERR_UNSUPPORTED, "forced weight-gradient tile geometry is not available for this shape");
+        for (int i = 0; i < d->nparts; ++i) { o.w[i].force_mtw = d->force_mtw; o.w[i].force_nw = d->force_nw; }
+    } else if (d->force_mtw > 0 || d->force_nw > 0) {
+        int m, n;
+        if (!wgrad_common_geom(o.w, d->nparts, d->force_mtw, d->force_nw)) return fail(WUN_ERR_UNSUPPORTED, "the parts do not resolve to one forced tile geometry");
+        wgrad_resolved_geom(o.w[0], m, n);
+        if (m != d->force_mtw || n != d->force_nw) return fail(WUN_ERR_UNSUPPORTED, "forced weight-gradient tile geometry is not available for this shape");
+    } else {
+        // the plan's default: the heuristic geometry of the first part, lowered until every part agrees
+        int m, n;
+        wgrad_resolved_geom(o.w[0], m, n);
+        while (!wgrad_common_geom(o.w, d->nparts, m, n) && m > 1) m = m == 6 ? 4 : m / 2;
+        if (!wgrad_common_geom(o.w, d->nparts, m, n)) return fail(WUN_ERR_UNSUPPORTED, "the parts do not resolve to one tile geometry");
+    }
+    for (int i = 0; i < d->nparts; ++i) {
+        WgradArgs& w = o.w[i];
+        if (!wgrad_launch_ok(w, sw)) return fail(WUN_ERR_UNSUPPORTED, "the weight-gradient launcher refuses this shape under the resolved geometry");
+        o.units[i] = wgrad_max_units(w, sw);
+        w.nsplit = d->nsplit[i] > 0 ? std::min(d->nsplit[i], o.units[i]) : wgrad_pick_nsplit(w, sw);
+        o.total += w.nsplit;
+    }
+    o.part_floats = wgrad_partial_floats(o.w[0], sw);
+    // (one reduction reads every part's splits through the first part's layout)
+    for (int i = 1; i < d->nparts; ++i)
+        if (wgrad_partial_floats(o.w[i], sw) != o.part_floats) return fail(WUN_ERR_UNSUPPORTED, "the parts do not share one partial layout");
+    return WUN_OK;
+}
+
+extern "C" int64_t wun_op_wgrad_ex_scratch(const wun_op_wgrad_desc* d) {
+    OpWgrad o;
+    if (int rc = op_wgrad_build(d, nullptr, nullptr, nullptr, nullptr, wun_switches_from_env(), o)) return rc;
+    return (int64_t)o.total * o.part_floats + 128;
+}
+
+extern "C" int wun_op_wgrad_max_units(const wun_op_wgrad_desc* d, int part) {
+    OpWgrad o;
+    if (int rc = op_wgrad_build(d, nullptr, nullptr, nullptr, nullptr, wun_switches_from_env(), o)) return rc;
+    if (part < 0 || part >= o.nparts) return fail(WUN_ERR_INVALID, "no such part");
+    return o.units[part];
+}
+
+extern "C" int wun_op_wgrad_last_splits(void) { return t_op_wgrad_splits; }
+
+extern "C" int wun_op_wgrad_ex(const wun_op_wgrad_desc* d, const void* x0, const void* x1, const void* dz_part0,
+                               const void* dz_part1, float* grads, float* scratch, void* stream) {
+    if (!d || !x0 || !dz_part0 || !grads || !scratch || (d->C1 > 0 && !x1) || (d->nparts == 2 && !dz_part1))
+        return fail(WUN_ERR_INVALID, "null argument");
+    if (reinterpret_cast<uintptr_t>(grads) & 3) return fail(WUN_ERR_INVALID, "grads not aligned to a float");
+    const WunSwitches sw = wun_switches_from_env();
+    OpWgrad o;
+    if (int rc = op_wgrad_build(d, x0, x1, dz_part0, dz_part1, sw, o)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float* partial = (float*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
+    if (o.narrow) {
+        // run_narrow_wgrad: consecutive splits of one partial list, one reduction (no direct form)
+        int done = 0;
+        for (int i = 0; i < o.nparts; ++i) {
+            o.nw[i].partial = partial; o.nw[i].split_base = done;
+            HIP_TRY(launch_narrow_wgrad(o.nw[i], s, sw));
+            done += o.nw[i].nsplit;
+        }
+        HIP_TRY(launch_narrow_wgrad_reduce(o.nw[0], partial, o.total, grads, o.woff, o.boff, s, d->accumulate != 0));
+        t_op_wgrad_path = WUN_PATH_WGRAD_SPLIT; t_op_wgrad_splits = o.total;
+        return WUN_OK;
+    }
+    float* out_w = grads;
+    float* out_b = out_w + (long long)d->K * (d->C0 + d->C1) * d->N;
+    if (o.total == 1) {
+        // run_wgrad: one split in all -- the direct epilogue writes the final block
+        o.w[0].out = out_w; o.w[0].direct = 1; o.w[0].split_base = 0;
+        HIP_TRY(launch_wgrad(o.w[0], s, sw));
+        t_op_wgrad_path = WUN_PATH_WGRAD_DIRECT; t_op_wgrad_splits = 1;
+        return WUN_OK;
+    }
+    int done = 0;
+    for (int i = 0; i < o.nparts; ++i) {
+        o.w[i].out = partial; o.w[i].direct = 0; o.w[i].split_base = done;
+        HIP_TRY(launch_wgrad(o.w[i], s, sw));
+        done += o.w[i].nsplit;
+    }
+    HIP_TRY(launch_wgrad_reduce(o.w[0], partial, o.total, out_w, out_b, s, sw));
+    t_op_wgrad_path = WUN_PATH_WGRAD_SPLIT; t_op_wgrad_splits = o.total;
     return WUN_OK;
 }
 

@@ -180,6 +180,8 @@ unsigned event_flags(const wun_plan* p);
 int side_init(const wun_plan* p);
 int stream_dep(const wun_plan* p, hipStream_t from, hipStream_t to);
 hipError_t conv_dispatch(const wun_plan* p, ConvArgs a, float* part, long long cap, hipStream_t s, long long at = -1);
+// forces (mtw, nw) on every part; false if the parts do not resolve to one tile geometry (run_wgrad, wun_op_wgrad_ex)
+bool wgrad_common_geom(WgradArgs* parts, int nparts, int mtw, int nw);
 // accum: the final stores add to `grads` (wun_*backward_accumulate); same launches, tilings and split counts
 int run_wgrad(const wun_plan* p, WgradArgs* parts, int nparts, const ConvLayer& cl, float* ws, float* grads,
               hipStream_t main, hipStream_t s, bool dep = true, bool accum = false);

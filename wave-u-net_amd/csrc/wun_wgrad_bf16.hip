@@ -502,6 +502,19 @@ hipError_t launch_wgrad_bf16(const WgradArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
+// the refusals of launch_wgrad_bf16 / wgrad_bf16_launch_t without the launch
+bool wgrad_bf16_launch_ok(const WgradArgs& a) {
+    if (!wgrad_bf16_supported(a) || !a.sbf) return false;
+    if ((a.pitch0 & 3) || (a.bs0 & 3) || (reinterpret_cast<uintptr_t>(a.src0) & 15) || a.pitch0 < 4) return false;
+    if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || a.pitch1 < 4)) return false;
+    if ((a.dzpitch & 3) || (a.dzbs & 3) || (reinterpret_cast<uintptr_t>(a.dz) & 15) || a.dzpitch < 4) return false;
+    const WgradBfGeom g = wgrad_bf16_geom(a);
+    if (!((g.MTW == 4 && g.NW >= 1 && g.NW <= 5) || (g.MTW == 8 && g.NW >= 1 && g.NW <= 3))) return false;
+    if (g.lds > 160 * 1024 || (size_t)(g.NW * 16) * g.ZPe > 65535 || g.XW4 >= (1 << 20)) return false;
+    if ((size_t)g.NCB * (a.loader == LOADER_DEINT ? 2 : 1) * g.XROWS * 16 + 80 > 65535) return false;
+    return (long long)8 * g.NCB * g.XW4 <= (long long)WUN_WGB_XITP * 256;
+}
+
 hipError_t launch_wgrad_bf16_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
                                     hipStream_t s) {
     const WgradBfGeom g = wgrad_bf16_geom(a);

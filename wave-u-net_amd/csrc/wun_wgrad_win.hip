@@ -687,6 +687,16 @@ hipError_t launch_wgrad_win(const WgradArgs& a, hipStream_t s, const WunSwitches
     return hipErrorInvalidValue;
 }
 
+// the refusals of launch_wgrad_win without the launch
+bool wgrad_win_launch_ok(const WgradArgs& a, const WunSwitches& sw) {
+    if (!wgrad_win_supported(a)) return false;
+    const WinGeom g = wgrad_win_geom(a, sw);
+    if (g.lds > 160 * 1024) return false;
+    const long long xs = g.p.zoff / 4, zs = (g.p.bufFloats - g.p.zoff) / 4;
+    if (xs > (long long)WUN_WIN_XIT * g.threads || zs > (long long)WUN_WIN_ZIT * g.threads) return false;
+    return g.S == 2 ? (g.K15 == 1 && g.NW >= 1 && g.NW <= 5) : (g.NW >= 1 && g.NW <= (g.K15 ? 5 : 6));
+}
+
 hipError_t launch_wgrad_win_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
                                    hipStream_t s, const WunSwitches& sw) {
     const WinGeom g = wgrad_win_geom(a, sw);
