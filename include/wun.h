@@ -1495,6 +1495,26 @@ int     wun_op_spec_head_backward(const float* re, const float* im, const float*
                                   const float* d_audio, int32_t B, int64_t T, int32_t n_fft, int32_t hop, const float* table_dev,
                                   float* dz, float* scratch, void* stream);
 
+/* The launch ledger of the FFT path (test entries; host only, nothing on a hot path reads it).  The eight kernel bodies of the
+ * FFT path are built for each of the eight sizes n_fft = 64 << j, j = 0 .. WUN_FFT_SIZE_COUNT - 1; every launch of one that the
+ * runtime accepted adds 1 to the process-wide counter [family][j].  A refused n_fft (WUN_ERR_UNSUPPORTED) adds nothing.
+ *   FORWARD            Re / Im of every bin     wun_stft_complex_fft and the *_fft filters' analysis
+ *   MAGNITUDE          the loss's forward       wun_stft_magnitude_fft, wun_spectral_loss*_fft
+ *   SPEC_HEAD          the mask-gradient head   wun_spec_backward, wun_op_spec_head_backward (with d_audio)
+ *   INVERSE            frames of a spectrum     wun_istft_fft, wun_istft_tf_fft, the *_fft filters, wun_time_stretch's synthesis
+ *   ADJOINT            the loss's gradient      wun_spectral_loss*_fft with d_outputs
+ *   GRIFFIN_LIM        a step from audio        wun_griffin_lim
+ *   GRIFFIN_LIM_GIVEN  a step from a spectrum   wun_griffin_lim with re0 / im0, its first step
+ *   VOC_ANALYSIS       the vocoder's analysis   wun_time_stretch
+ * wun_fft_launch_counts copies the table to counts[family * WUN_FFT_SIZE_COUNT + j]; WUN_ERR_INVALID for a null pointer or
+ * cap < WUN_FFT_FAMILY_COUNT * WUN_FFT_SIZE_COUNT.  wun_fft_launch_counts_reset sets every counter to 0. */
+enum { WUN_FFT_FAMILY_FORWARD = 0, WUN_FFT_FAMILY_MAGNITUDE = 1, WUN_FFT_FAMILY_SPEC_HEAD = 2, WUN_FFT_FAMILY_INVERSE = 3,
+       WUN_FFT_FAMILY_ADJOINT = 4, WUN_FFT_FAMILY_GRIFFIN_LIM = 5, WUN_FFT_FAMILY_GRIFFIN_LIM_GIVEN = 6,
+       WUN_FFT_FAMILY_VOC_ANALYSIS = 7, WUN_FFT_FAMILY_COUNT = 8 };
+enum { WUN_FFT_SIZE_COUNT = 8 };
+int  wun_fft_launch_counts(int64_t* counts, int32_t cap);
+void wun_fft_launch_counts_reset(void);
+
 /* y[b][co][q] = act(bias[co] + sum_{k,ci} w[k][ci][co] * x[b][ci][q*stride + k - pad_left]),
  * x zero outside [0, t_in).  NCW float32, w in TF layout [K, Cin, Cout].
  * stride in {1, 2}; t_out is given by the caller.  lrelu: 0/1 (alpha = 0.2). */

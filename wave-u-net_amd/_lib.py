@@ -110,6 +110,11 @@ SNIPPET_ROWS = 24                                   # WUN_SNIPPET_ROWS: batch ro
 
 SPEC_TT_Z, SPEC_TT_MEAN, SPEC_TT_VAR, SPEC_TT_ACT, SPEC_TT_DROPOUT = range(5)     # wun_spec_train_tensor kinds
 
+# wun_fft_launch_counts: the kernel bodies of the FFT path (WUN_FFT_FAMILY_*) and its sizes n_fft = 64 << j, j < FFT_SIZE_COUNT
+(FFT_FAMILY_FORWARD, FFT_FAMILY_MAGNITUDE, FFT_FAMILY_SPEC_HEAD, FFT_FAMILY_INVERSE, FFT_FAMILY_ADJOINT, FFT_FAMILY_GRIFFIN_LIM,
+ FFT_FAMILY_GRIFFIN_LIM_GIVEN, FFT_FAMILY_VOC_ANALYSIS, FFT_FAMILY_COUNT) = range(9)
+FFT_SIZE_COUNT = 8
+
 _P = C.c_void_p
 _SIGS = {
     "wun_get_padding": (C.c_int, [C.POINTER(WunConfig), C.c_int64, C.POINTER(C.c_int64),
@@ -280,6 +285,8 @@ _SIGS = {
                                                   C.c_int64, _P]),
     "wun_op_spec_head_backward_scratch": (C.c_int64, [C.c_int32, C.c_int64, C.c_int32, C.c_int32]),
     "wun_op_spec_head_backward": (C.c_int, [_P] * 6 + [C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "wun_fft_launch_counts": (C.c_int, [C.POINTER(C.c_int64), C.c_int32]),
+    "wun_fft_launch_counts_reset": (None, []),
     "wun_op_conv2d_s2_wgrad_scratch": (C.c_int64, [C.c_int] * 5),
     "wun_op_conv2d_s2_wgrad": (C.c_int, [_P] * 5 + [C.c_int] * 5 + [_P]),
     "wun_op_conv2d_transpose_s2_wgrad_scratch": (C.c_int64, [C.c_int] * 5),

@@ -87,6 +87,8 @@ static_assert(sizeof(VocArgs) <= 4096, "the argument block must fit HIP's kernel
 //   magnitude   the forward body with StftMagArgs' epilogue (the spectral loss and wun_stft_magnitude_fft)
 //   adjoint     the inverse body as the UNSCALED adjoint of the forward transform, every bin counted once (stft_bwd_kernel's
 //               definition): g.c_edge must be 1 / 2, g.c_mid is not read
+// Each launcher below adds 1 to the host-side ledger [WUN_FFT_FAMILY_*][log2(n_fft) - 6] once the runtime has taken its launch
+// (wun_fft_launch_counts, include/wun.h: test entries; nothing else reads it).
 int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s);
 int fft_launch_magnitude(const StftMagArgs& a, int signals, hipStream_t s);
 int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s);

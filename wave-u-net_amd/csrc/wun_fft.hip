@@ -30,6 +30,7 @@
 #include "wun_fft.h"
 #include "../../include/wun.h"
 
+#include <atomic>
 #include <cmath>
 #include <string>
 #include <type_traits>
@@ -522,20 +523,28 @@ __global__ __launch_bounds__(WUN_FFT_BLOCK) void gl_finish_kernel(const double* 
     if (tid == 0 || tid == 64) out[slot] = acc;
 }
 
-// f(std::integral_constant<int, log2(n_fft / 2)>) for an n_fft with a kernel; else WUN_ERR_UNSUPPORTED, nothing launched
+// The launch ledger of the test entries wun_fft_launch_counts / wun_fft_launch_counts_reset (include/wun.h): launches per kernel
+// body (WUN_FFT_FAMILY_*) and size (log2(n_fft / 2) - 5).  Host code only, written by fft_dispatch and read by nothing else here.
+static std::atomic<long long> g_fft_launches[WUN_FFT_FAMILY_COUNT][WUN_FFT_SIZE_COUNT];
+
+// f(std::integral_constant<int, log2(n_fft / 2)>) for an n_fft with a kernel, then one more launch of `family` in the ledger if
+// the runtime took it; else WUN_ERR_UNSUPPORTED, nothing launched and nothing counted
 template <class F>
-static int fft_dispatch(const char* who, int n_fft, F f) {
+static int fft_dispatch(const char* who, int family, int n_fft, F f) {
+    int logm = 0;
     switch (n_fft) {
-        case 64: f(std::integral_constant<int, 5>()); break;
-        case 128: f(std::integral_constant<int, 6>()); break;
-        case 256: f(std::integral_constant<int, 7>()); break;
-        case 512: f(std::integral_constant<int, 8>()); break;
-        case 1024: f(std::integral_constant<int, 9>()); break;
-        case 2048: f(std::integral_constant<int, 10>()); break;
-        case 4096: f(std::integral_constant<int, 11>()); break;
-        case 8192: f(std::integral_constant<int, 12>()); break;
+        case 64: f(std::integral_constant<int, 5>()); logm = 5; break;
+        case 128: f(std::integral_constant<int, 6>()); logm = 6; break;
+        case 256: f(std::integral_constant<int, 7>()); logm = 7; break;
+        case 512: f(std::integral_constant<int, 8>()); logm = 8; break;
+        case 1024: f(std::integral_constant<int, 9>()); logm = 9; break;
+        case 2048: f(std::integral_constant<int, 10>()); logm = 10; break;
+        case 4096: f(std::integral_constant<int, 11>()); logm = 11; break;
+        case 8192: f(std::integral_constant<int, 12>()); logm = 12; break;
         default: return fail(WUN_ERR_UNSUPPORTED, std::string(who) + ": no kernel for this n_fft");
     }
+    static_assert(WUN_FFT_SIZE_COUNT == 12 - 5 + 1, "one ledger column per case above");
+    if (hipPeekAtLastError() == hipSuccess) g_fft_launches[family][logm - 5].fetch_add(1, std::memory_order_relaxed);
     return WUN_OK;
 }
 
@@ -549,21 +558,21 @@ template <int LOGM>
 static dim3 inv_grid(const IstftGemmArgs& g) { return dim3((unsigned)((g.M + FftGeom<LOGM>::FPW - 1) / FftGeom<LOGM>::FPW)); }
 
 int fft_launch_forward(const StftCfwdArgs& a, int signals, hipStream_t s) {
-    return fft_dispatch("fft_launch_forward", a.n_fft, [&](auto L) {
+    return fft_dispatch("fft_launch_forward", WUN_FFT_FAMILY_FORWARD, a.n_fft, [&](auto L) {
         constexpr int LM = decltype(L)::value;
         hipLaunchKernelGGL(stft_fft_kernel<LM>, fwd_grid<LM>(a, signals), dim3(WUN_FFT_BLOCK), 0, s, a);
     });
 }
 
 int fft_launch_magnitude(const StftMagArgs& a, int signals, hipStream_t s) {
-    return fft_dispatch("fft_launch_magnitude", a.a.n_fft, [&](auto L) {
+    return fft_dispatch("fft_launch_magnitude", WUN_FFT_FAMILY_MAGNITUDE, a.a.n_fft, [&](auto L) {
         constexpr int LM = decltype(L)::value;
         hipLaunchKernelGGL(stft_fft_mag_kernel<LM>, fwd_grid<LM>(a.a, signals), dim3(WUN_FFT_BLOCK), 0, s, a);
     });
 }
 
 int fft_launch_spec_head(const SpecHeadArgs& a, hipStream_t s) {
-    return fft_dispatch("fft_launch_spec_head", a.a.n_fft, [&](auto L) {
+    return fft_dispatch("fft_launch_spec_head", WUN_FFT_FAMILY_SPEC_HEAD, a.a.n_fft, [&](auto L) {
         constexpr int LM = decltype(L)::value;
         hipLaunchKernelGGL(spec_head_fft_kernel<LM>, fwd_grid<LM>(a.a, 1), dim3(WUN_FFT_BLOCK), 0, s, a);
     });
@@ -580,14 +589,14 @@ void launch_steady_divide(const float* g, const float* D, float* u, long long N,
 }
 
 int fft_launch_inverse(const IstftGemmArgs& g, hipStream_t s) {
-    return fft_dispatch("fft_launch_inverse", g.n_fft, [&](auto L) {
+    return fft_dispatch("fft_launch_inverse", WUN_FFT_FAMILY_INVERSE, g.n_fft, [&](auto L) {
         constexpr int LM = decltype(L)::value;
         hipLaunchKernelGGL((istft_fft_kernel<LM, false>), inv_grid<LM>(g), dim3(WUN_FFT_BLOCK), 0, s, g);
     });
 }
 
 int fft_launch_griffin_lim(const GlArgs& g, bool given, hipStream_t s) {
-    return fft_dispatch("fft_launch_griffin_lim", g.n_fft, [&](auto L) {
+    return fft_dispatch("fft_launch_griffin_lim", given ? WUN_FFT_FAMILY_GRIFFIN_LIM_GIVEN : WUN_FFT_FAMILY_GRIFFIN_LIM, g.n_fft, [&](auto L) {
         constexpr int LM = decltype(L)::value;
         const dim3 grid((unsigned)((g.M + FftGeom<LM>::FPW - 1) / FftGeom<LM>::FPW));
         if (given) hipLaunchKernelGGL((gl_frame_kernel<LM, true>), grid, dim3(WUN_FFT_BLOCK), 0, s, g);
@@ -602,7 +611,7 @@ int fft_frames_per_workgroup(int n_fft) {
 }
 
 int fft_launch_voc_analysis(const VocArgs& v, hipStream_t s) {
-    return fft_dispatch("fft_launch_voc_analysis", v.n_fft, [&](auto L) {
+    return fft_dispatch("fft_launch_voc_analysis", WUN_FFT_FAMILY_VOC_ANALYSIS, v.n_fft, [&](auto L) {
         constexpr int LM = decltype(L)::value;
         static_assert(FftGeom<LM>::FPW == (FftGeom<LM>::N / 8 < WUN_FFT_BLOCK ? WUN_FFT_BLOCK / (FftGeom<LM>::N / 8) : 1), "fft_frames_per_workgroup");
         hipLaunchKernelGGL(voc_analysis_kernel<LM>, dim3((unsigned)v.gp[v.J]), dim3(WUN_FFT_BLOCK), 0, s, v);
@@ -614,13 +623,28 @@ void launch_gl_finish(const double* part, long long n, double* out, hipStream_t 
 }
 
 int fft_launch_adjoint(const IstftGemmArgs& g, hipStream_t s) {
-    return fft_dispatch("fft_launch_adjoint", g.n_fft, [&](auto L) {
+    return fft_dispatch("fft_launch_adjoint", WUN_FFT_FAMILY_ADJOINT, g.n_fft, [&](auto L) {
         constexpr int LM = decltype(L)::value;
         hipLaunchKernelGGL((istft_fft_kernel<LM, true>), inv_grid<LM>(g), dim3(WUN_FFT_BLOCK), 0, s, g);
     });
 }
 
 }  // namespace wun
+
+extern "C" int wun_fft_launch_counts(int64_t* counts, int32_t cap) {
+    if (!counts) return fail(WUN_ERR_INVALID, "wun_fft_launch_counts: null counts");
+    if (cap < WUN_FFT_FAMILY_COUNT * WUN_FFT_SIZE_COUNT)
+        return fail(WUN_ERR_INVALID, "wun_fft_launch_counts: cap below WUN_FFT_FAMILY_COUNT * WUN_FFT_SIZE_COUNT");
+    for (int f = 0; f < WUN_FFT_FAMILY_COUNT; ++f)
+        for (int j = 0; j < WUN_FFT_SIZE_COUNT; ++j)
+            counts[f * WUN_FFT_SIZE_COUNT + j] = (int64_t)g_fft_launches[f][j].load(std::memory_order_relaxed);
+    return WUN_OK;
+}
+
+extern "C" void wun_fft_launch_counts_reset(void) {
+    for (int f = 0; f < WUN_FFT_FAMILY_COUNT; ++f)
+        for (int j = 0; j < WUN_FFT_SIZE_COUNT; ++j) g_fft_launches[f][j].store(0, std::memory_order_relaxed);
+}
 
 extern "C" int64_t wun_fft_table_floats(int32_t n_fft) {
     if (n_fft < 64 || n_fft > 8192 || (n_fft & (n_fft - 1)))
