@@ -434,110 +434,20 @@ static int bf16_pick_nck(const ConvArgs& a, int TT, int NT, int xit) {
     return nck;
 }
 
-template <int MT, int NW, int MODE, int NCK, int KT>
-static hipError_t conv_bf16_launch_k(const ConvArgs& a, int nTT, int nNT, int ROWS, size_t lds, long long grid, hipStream_t s) {
-    auto kern = conv_bf16_kernel<MT, NW, MODE, NCK, KT>;
-    static size_t lds_allowed = 64 * 1024;
-    if (lds > lds_allowed) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_allowed = lds;
-    }
-    char nm[64], tag[160];
-    snprintf(nm, sizeof(nm), "conv_bf16_kernel<%d, %d>", MT, NW);
-    snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nck=%d ph2=%d grid=%lld", a.C0 + a.C1, a.N, a.Tout, a.KW, a.loader,
-             a.B, NCK, MODE == 2 ? 1 : 0, grid);
-    prof_scope_begin(nm, conv_flops(a), s, tag);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, a, nTT, nNT, ROWS);
-    prof_scope_end(s);
-    return hipGetLastError();
-}
-
-template <int MT, int NW, int MODE>
-static hipError_t conv_bf16_launch_m(const ConvArgs& a, int NCK, int nTT, int nNT, int ROWS, size_t lds, long long grid, hipStream_t s) {
-    // the shipped filter sizes get their own instantiation: stride-1 loader 15 / 5 taps, stride-2 loader 15 taps, the
-    // fused two-phase conv 8 taps per phase (of 15); anything else takes the run-time-tap kernel
-    constexpr int K1 = MODE == 2 ? 8 : 15, K2 = MODE == 0 ? 5 : 0;
-#define WUN_BF_K(N) \
-    if (NCK == N) { \
-        if (a.KW == K1) return conv_bf16_launch_k<MT, NW, MODE, N, K1>(a, nTT, nNT, ROWS, lds, grid, s); \
-        if (K2 > 0 && a.KW == K2) return conv_bf16_launch_k<MT, NW, MODE, N, K2>(a, nTT, nNT, ROWS, lds, grid, s); \
-        return conv_bf16_launch_k<MT, NW, MODE, N, 0>(a, nTT, nNT, ROWS, lds, grid, s); \
-    }
-    WUN_BF_K(1) WUN_BF_K(2) WUN_BF_K(3)
-#undef WUN_BF_K
-    return hipErrorInvalidValue;
-}
-
-template <int MT, int NW>
-static hipError_t conv_bf16_launch_t(ConvArgs a, hipStream_t s, int nck_force = 0) {
-    constexpr int TT = 4 * MT * 16, NT = NW * 16;
-    const int NCK = nck_force > 0 ? nck_force : bf16_pick_nck(a, TT, NT, BfXit<MT>::v);
-    const int ROWS = bf16_rows(a, TT);
-    const bool deint = a.loader == LOADER_DEINT;
-    const int planes = deint ? 2 : 1;
-    const size_t lds = bf16_lds(a, TT, NT, NCK);
-    if (lds > 160 * 1024 || bf16_pairs64(planes * ROWS) * 4 * NCK > BfXit<MT>::v * 256) return hipErrorInvalidValue;
-    const bool phase2 = (a.flags & F_PHASE2) != 0;
-    if (phase2 && ((NW % 2) != 0 || deint)) return hipErrorInvalidValue;
-    const int nTT = (a.Tout + TT - 1) / TT, nNT = phase2 ? (a.N + NT / 2 - 1) / (NT / 2) : (a.N + NT - 1) / NT;
-    const long long grid = (long long)nTT * a.B * nNT;
-    if (grid <= 0) return hipSuccess;
-    if constexpr ((NW % 2) == 0) {
-        if (phase2) return conv_bf16_launch_m<MT, NW, 2>(a, NCK, nTT, nNT, ROWS, lds, grid, s);
-    }
-    return deint ? conv_bf16_launch_m<MT, NW, 1>(a, NCK, nTT, nNT, ROWS, lds, grid, s)
-                 : conv_bf16_launch_m<MT, NW, 0>(a, NCK, nTT, nNT, ROWS, lds, grid, s);
-}
+// the instantiated (MT, NW) of conv_bf16_kernel, stated once
+#define WUN_BF_TILES(WUN_BF) \
+    WUN_BF(4, 4) WUN_BF(4, 3) WUN_BF(4, 2) \
+    WUN_BF(2, 4) WUN_BF(2, 3) WUN_BF(2, 2) \
+    WUN_BF(1, 4) WUN_BF(1, 3) WUN_BF(1, 2)
 
 // Tile choices of the autotuner: code = (log2 MT) * 9 + (NW - 2) * 3 + (NCK - 1), MT in {1, 2, 4} tiles of 16
 // positions per wave, NW in {2, 3, 4} column tiles, NCK in {1, 2, 3} channel chunks per stage.
-bool conv_bf16_choice_ok(const ConvArgs& a, int variant) {
-    const int code = variant - kBf16VariantBase;
-    if (code < 0 || code >= 27 || !conv_bf16_supported(a)) return false;
-    const int mt = 1 << (code / 9), nw = 2 + (code / 3) % 3, nck = 1 + code % 3;
-    const bool phase2 = (a.flags & F_PHASE2) != 0;
-    if (phase2 && (nw & 1)) return false;
-    const int TT = 64 * mt, NT = 16 * nw;
-    const int chan = phase2 ? NT / 2 : NT;
-    const int padded = (a.N + chan - 1) / chan * chan;
-    if (padded * 3 > a.N * 4 + 48) return false;                       // > ~33 % padded columns
-    // the packed weight image is padded to a multiple of 64 columns: a tile whose last column group runs past that
-    // would DMA the next channel group's rows (results land in discarded columns, but it is an out-of-image read)
-    if (!phase2 && padded > (a.N + 63) / 64 * 64) return false;
-    if (TT > 64 && TT >= 2 * a.Tout) return false;                     // mostly padding in time
-    if (nck > (a.C0 + a.C1 + 31) / 32) return false;
-    const int planes = a.loader == LOADER_DEINT ? 2 : 1;
-    if (bf16_pairs64(planes * bf16_rows(a, TT)) * 4 * nck > bf16_xit(mt) * 256) return false;
-    return bf16_lds(a, TT, NT, nck) <= 160 * 1024;
-}
-int conv_bf16_list_candidates(const ConvArgs& a, ConvChoice* out, int maxn) {
-    int n = 0;
-    for (int code = 0; code < 27 && n < maxn; ++code)
-        if (conv_bf16_choice_ok(a, kBf16VariantBase + code)) { out[n].variant = kBf16VariantBase + code; out[n].ksplit = 1; ++n; }
-    return n;
-}
+static const int kNumBfCodes = 27;
+struct BfTile { int mt, nw, nck; };
+static inline BfTile bf16_decode(int code) { return {1 << (code / 9), 2 + (code / 3) % 3, 1 + code % 3}; }
 
-// a.W must point at the packed bf16 image of the layer's weights (pack_bf16_kernel), a.wb_c8p / a.wb_npad set
-hipError_t launch_conv_bf16(const ConvArgs& a_in, hipStream_t s, const WunSwitches& sw) {
-    ConvArgs a = a_in;
-    if (!a.xbf || !conv_bf16_supported(a) || a.wb_c8p <= 0 || a.wb_npad <= 0 || !aligned16(a.W)) return hipErrorInvalidValue;
-    if (!aligned16(a.src0) || (a.src1 != nullptr && !aligned16(a.src1))) return hipErrorInvalidValue;      // dword pairs at even row elements
-    conv_output_setup(a);
-    if (a.dec != nullptr && !aligned16(a.dec)) a.flags &= ~F_VEC4;      // (the bf16 copy stores its pairs as dwords)
-    // autotuned choice (ConvChoice.variant = kBf16VariantBase + tile code; checked by conv_bf16_choice_ok)
-    if (a.force_variant > kBf16VariantBase) {
-        const int code = a.force_variant - 1 - kBf16VariantBase;
-        if (!conv_bf16_choice_ok(a, a.force_variant - 1)) return hipErrorInvalidValue;
-        const int mt = 1 << (code / 9), nw = 2 + (code / 3) % 3, nck = 1 + code % 3;
-#define WUN_BF(M, N) if (mt == M && nw == N) return conv_bf16_launch_t<M, N>(a, s, nck);
-        WUN_BF(4, 4) WUN_BF(4, 3) WUN_BF(4, 2)
-        WUN_BF(2, 4) WUN_BF(2, 3) WUN_BF(2, 2)
-        WUN_BF(1, 4) WUN_BF(1, 3) WUN_BF(1, 2)
-#undef WUN_BF
-        return hipErrorInvalidValue;
-    }
-    // tile: fewest padded columns among 64/48/32; rows by how many tiles the launch has
+// the heuristic (MT, NW): fewest padded columns among 64/48/32; rows by how many tiles the launch has
+static BfTile bf16_pick_tile(const ConvArgs& a, int lds_cap_kib) {
     const bool phase2 = (a.flags & F_PHASE2) != 0;
     int bestnw = 4, bestpad = 1 << 30;
     const int cands[3] = {4, 3, 2};
@@ -554,19 +464,121 @@ hipError_t launch_conv_bf16(const ConvArgs& a_in, hipStream_t s, const WunSwitch
                       bf16_lds(a, 64 * mt, bestnw * 16, 1) > 160 * 1024)) mt >>= 1;
     // A workgroup runs its phases (fetch, MFMA, store) back to back, so the CU needs a second resident workgroup to
     // overlap them: take the tallest tile whose LDS footprint still lets two workgroups share a CU
-    const int lds_cap = sw.bf16_lds_cap;
-    {
-        int m2 = mt;
-        while (m2 > 1 && bf16_lds(a, 64 * m2, bestnw * 16, bf16_pick_nck(a, 64 * m2, bestnw * 16, bf16_xit(m2))) >
-                             (size_t)lds_cap * 1024) m2 >>= 1;
-        if (bf16_lds(a, 64 * m2, bestnw * 16, bf16_pick_nck(a, 64 * m2, bestnw * 16, bf16_xit(m2))) <= (size_t)lds_cap * 1024)
-            mt = m2;
+    auto lds_of = [&](int m) { return bf16_lds(a, 64 * m, bestnw * 16, bf16_pick_nck(a, 64 * m, bestnw * 16, bf16_xit(m))); };
+    int m2 = mt;
+    while (m2 > 1 && lds_of(m2) > (size_t)lds_cap_kib * 1024) m2 >>= 1;
+    if (lds_of(m2) <= (size_t)lds_cap_kib * 1024) mt = m2;
+    return {mt, bestnw, bf16_pick_nck(a, 64 * mt, bestnw * 16, bf16_xit(mt))};
+}
+
+// One launch of the bf16 conv from the shape side of `a`, or a refusal (conv_bf16_resolve): launch_conv_bf16 launches it,
+// conv_bf16_choice_ok asks.  code: the tuner's tile code, or < 0 for the heuristic (lds_cap_kib: WunSwitches.bf16_lds_cap).
+struct ConvBfLaunch { hipError_t err; BfTile t; int mode, kt, TT, NT, nTT, nNT, ROWS; size_t lds; long long grid; };
+static ConvBfLaunch conv_bf16_resolve(const ConvArgs& a, int code, int lds_cap_kib) {
+    ConvBfLaunch r = {};
+    r.err = hipErrorInvalidValue;
+    if (code >= kNumBfCodes || !conv_bf16_supported(a)) return r;
+    const bool phase2 = (a.flags & F_PHASE2) != 0, deint = a.loader == LOADER_DEINT;
+    const BfTile& t = r.t = code >= 0 ? bf16_decode(code) : bf16_pick_tile(a, lds_cap_kib);
+#define WUN_BF_IS(M, N) || (t.mt == M && t.nw == N)
+    if (!(false WUN_BF_TILES(WUN_BF_IS))) return r;
+#undef WUN_BF_IS
+    if (phase2 && (t.nw & 1)) return r;
+    if (t.nck < 1 || t.nck > 3 || (code >= 0 && t.nck > (a.C0 + a.C1 + 31) / 32)) return r;
+    r.TT = 64 * t.mt; r.NT = 16 * t.nw;
+    r.ROWS = bf16_rows(a, r.TT);
+    r.lds = bf16_lds(a, r.TT, r.NT, t.nck);
+    if (r.lds > 160 * 1024 || bf16_pairs64((deint ? 2 : 1) * r.ROWS) * 4 * t.nck > bf16_xit(t.mt) * 256) return r;
+    const int chan = phase2 ? r.NT / 2 : r.NT;                         // output channels per workgroup
+    r.nTT = (a.Tout + r.TT - 1) / r.TT;
+    r.nNT = (a.N + chan - 1) / chan;
+    // the packed weight image is padded to a multiple of 64 columns: a tile whose last column group runs past that
+    // would DMA the next channel group's rows (results land in discarded columns, but it is an out-of-image read)
+    if (!phase2 && r.nNT * chan > (a.N + 63) / 64 * 64) return r;
+    // the shipped filter sizes get their own instantiation: stride-1 loader 15 / 5 taps, stride-2 loader 15 taps, the
+    // fused two-phase conv 8 taps per phase (of 15); anything else takes the run-time-tap kernel
+    r.mode = phase2 ? 2 : (deint ? 1 : 0);
+    const int K1 = r.mode == 2 ? 8 : 15, K2 = r.mode == 0 ? 5 : 0;
+    r.kt = a.KW == K1 ? K1 : (K2 > 0 && a.KW == K2 ? K2 : 0);
+    r.grid = (long long)r.nTT * a.B * r.nNT;
+    r.err = hipSuccess;
+    return r;
+}
+
+template <int MT, int NW, int MODE, int NCK, int KT>
+static hipError_t conv_bf16_launch_k(const ConvArgs& a, const ConvBfLaunch& r, hipStream_t s) {
+    auto kern = conv_bf16_kernel<MT, NW, MODE, NCK, KT>;
+    static size_t lds_allowed = 64 * 1024;
+    hipError_t e = raise_lds_limit((const void*)kern, r.lds, lds_allowed);
+    if (e != hipSuccess) return e;
+    char nm[64], tag[160];
+    snprintf(nm, sizeof(nm), "conv_bf16_kernel<%d, %d>", MT, NW);
+    snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nck=%d ph2=%d grid=%lld", a.C0 + a.C1, a.N, a.Tout, a.KW, a.loader,
+             a.B, NCK, MODE == 2 ? 1 : 0, r.grid);
+    prof_scope_begin(nm, conv_flops(a), s, tag);
+    hipLaunchKernelGGL(kern, dim3((unsigned)r.grid), dim3(256), r.lds, s, a, r.nTT, r.nNT, r.ROWS);
+    prof_scope_end(s);
+    return hipGetLastError();
+}
+
+// the (NCK, KT) instantiations of one (MT, NW, MODE): KT = the mode's shipped tap counts, or 0 for run-time taps
+template <int MT, int NW, int MODE>
+static hipError_t conv_bf16_launch_m(const ConvArgs& a, const ConvBfLaunch& r, hipStream_t s) {
+    constexpr int K1 = MODE == 2 ? 8 : 15, K2 = MODE == 0 ? 5 : 0;
+#define WUN_BF_K(N) \
+    if (r.t.nck == N) { \
+        if (r.kt == K1) return conv_bf16_launch_k<MT, NW, MODE, N, K1>(a, r, s); \
+        if (K2 > 0 && r.kt == K2) return conv_bf16_launch_k<MT, NW, MODE, N, K2>(a, r, s); \
+        return conv_bf16_launch_k<MT, NW, MODE, N, 0>(a, r, s); \
     }
-#define WUN_BF(M, N) if (mt == M && bestnw == N) return conv_bf16_launch_t<M, N>(a, s);
-    WUN_BF(4, 4) WUN_BF(4, 3) WUN_BF(4, 2)
-    WUN_BF(2, 4) WUN_BF(2, 3) WUN_BF(2, 2)
-    WUN_BF(1, 4) WUN_BF(1, 3) WUN_BF(1, 2)
-#undef WUN_BF
+    WUN_BF_K(1) WUN_BF_K(2) WUN_BF_K(3)
+#undef WUN_BF_K
+    return hipErrorInvalidValue;
+}
+
+template <int MT, int NW>
+static hipError_t conv_bf16_launch_t(const ConvArgs& a, const ConvBfLaunch& r, hipStream_t s) {
+    if constexpr ((NW % 2) == 0) {
+        if (r.mode == 2) return conv_bf16_launch_m<MT, NW, 2>(a, r, s);
+    }
+    return r.mode == 1 ? conv_bf16_launch_m<MT, NW, 1>(a, r, s) : conv_bf16_launch_m<MT, NW, 0>(a, r, s);
+}
+
+// the tuner's limits on a resolved launch with a forced tile code -- what it may pick, narrower than what would run
+static bool conv_bf16_policy_ok(const ConvArgs& a, const ConvBfLaunch& r) {
+    const int chan = (a.flags & F_PHASE2) ? r.NT / 2 : r.NT;
+    if (r.nNT * chan * 3 > a.N * 4 + 48) return false;                 // > ~33 % padded columns
+    return !(r.TT > 64 && r.TT >= 2 * a.Tout);                         // mostly padding in time
+}
+// = the launch resolves, within the tuner's limits (ConvChoice.variant = kBf16VariantBase + tile code)
+bool conv_bf16_choice_ok(const ConvArgs& a, int variant) {
+    if (variant < kBf16VariantBase) return false;
+    const ConvBfLaunch r = conv_bf16_resolve(a, variant - kBf16VariantBase, 0);
+    return r.err == hipSuccess && conv_bf16_policy_ok(a, r);
+}
+int conv_bf16_list_candidates(const ConvArgs& a, ConvChoice* out, int maxn) {
+    int n = 0;
+    for (int code = 0; code < kNumBfCodes && n < maxn; ++code)
+        if (conv_bf16_choice_ok(a, kBf16VariantBase + code)) { out[n].variant = kBf16VariantBase + code; out[n].ksplit = 1; ++n; }
+    return n;
+}
+
+// a.W must point at the packed bf16 image of the layer's weights (pack_bf16_kernel), a.wb_c8p / a.wb_npad set
+hipError_t launch_conv_bf16(const ConvArgs& a_in, hipStream_t s, const WunSwitches& sw) {
+    ConvArgs a = a_in;
+    if (!a.xbf || a.wb_c8p <= 0 || a.wb_npad <= 0 || !aligned16(a.W)) return hipErrorInvalidValue;
+    if (!aligned16(a.src0) || (a.src1 != nullptr && !aligned16(a.src1))) return hipErrorInvalidValue;      // dword pairs at even row elements
+    conv_output_setup(a);
+    if (a.dec != nullptr && !aligned16(a.dec)) a.flags &= ~F_VEC4;      // (the bf16 copy stores its pairs as dwords)
+    // autotuned choice: a forced tile code is held to the tuner's limits too
+    const bool forced = a.force_variant > kBf16VariantBase;
+    const ConvBfLaunch r = conv_bf16_resolve(a, forced ? a.force_variant - 1 - kBf16VariantBase : -1, sw.bf16_lds_cap);
+    if (r.err != hipSuccess) return r.err;
+    if (forced && !conv_bf16_policy_ok(a, r)) return hipErrorInvalidValue;
+    if (r.grid <= 0) return hipSuccess;
+#define WUN_BF_GO(M, N) if (r.t.mt == M && r.t.nw == N) return conv_bf16_launch_t<M, N>(a, r, s);
+    WUN_BF_TILES(WUN_BF_GO)
+#undef WUN_BF_GO
     return hipErrorInvalidValue;
 }
 

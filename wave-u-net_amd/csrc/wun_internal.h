@@ -135,6 +135,14 @@ struct ConvArgs {
 // did the last launch_conv() on this thread write the fused upsampled copy?  (only split-K launches do)
 int conv_last_fused_ups();
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// A kernel may take more than 64 KiB of dynamic LDS only once its attribute is raised.  `allowed` is the caller's high-water
+// mark for `kernel` (a function-local static starting at 64 KiB): one runtime call per kernel and size.  Every launcher's.
+static inline hipError_t raise_lds_limit(const void* kernel, size_t lds, size_t& allowed) {
+    if (lds <= allowed) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) allowed = lds;
+    return e;
+}
 // output side of a conv launch, shared by launch_conv and launch_conv_bf16: normalises acc_len == 0 to the whole row and
 // sets F_VEC4 when every destination / mask row allows the 16-byte vector epilogue
 void conv_output_setup(ConvArgs& a);
@@ -164,6 +172,25 @@ struct WgradArgs {
     int accum;       // final stores ADD to what the gradient arena holds (wun_*backward_accumulate): the launchers pick the
                      // accumulating instantiations (direct epilogue and split reduction); the kernels never read this field
 };
+// canonical layout the LDS-tiled and bf16 weight-gradient kernels stage from: 16-byte aligned rows of >= 4 elements
+static inline bool wgrad_rows_aligned(const WgradArgs& a) {
+    if ((a.pitch0 & 3) || (a.bs0 & 3) || !aligned16(a.src0) || a.pitch0 < 4) return false;
+    if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || !aligned16(a.src1) || a.pitch1 < 4)) return false;
+    return !((a.dzpitch & 3) || (a.dzbs & 3) || !aligned16(a.dz) || a.dzpitch < 4);
+}
+// What the three MFMA weight-gradient launchers derive from the caller's split count: units of TK positions per split, the
+// accumulating instantiation (only a single-split launch stores final values; split launches write partials with the plain
+// kernel), the grid.  nsplit 0 = not picked yet -- the *_launch_ok questions come before the pick -- and is not divided by.
+struct WgradSplit { int nQT, units_per_split; bool acc; long long grid; };
+static inline WgradSplit wgrad_split(const WgradArgs& a, int TK, long long tiles) {
+    WgradSplit sp;
+    sp.nQT = (a.Tq + TK - 1) / TK;
+    const int ns = a.nsplit > 0 ? a.nsplit : 1;
+    sp.units_per_split = (int)(((long long)a.B * sp.nQT + ns - 1) / ns);
+    sp.acc = a.accum && a.direct;
+    sp.grid = tiles * a.nsplit;
+    return sp;
+}
 
 // tile geometry of an exact-fp32 weight-gradient launch
 struct WgradGeom { int MTW, NW, nMG, nNG, TK, XP, ZP, nChMax, ONESP, XW4; size_t lds; };
@@ -279,7 +306,10 @@ struct WtDesc {      // mode 0: dst[j][n][c] = src[k_last - j*k_step][c][n]
 };
 
 // ---- launchers (wun_kernels.hip) ---------------------------------------------------
-size_t conv_lds_bytes(const ConvArgs& a, int variant, const WunSwitches& sw);
+// Every launcher family below resolves a launch in ONE host function of its unit (conv_resolve, conv_bf16_resolve,
+// wgrad_resolve, wgrad_win_resolve, wgrad_bf16_resolve, narrow_wgrad_resolve): args -> instantiation, geometry, split, LDS
+// bytes and grid, or a refusal.  launch_* launches the result; the host-only *_ok questions are "it resolved" (for the convs:
+// within the tuner's limits), so neither can accept what the other computes differently.
 int  conv_pick_variant(const ConvArgs& a);
 hipError_t launch_conv(const ConvArgs& a, float* part, long long part_cap, hipStream_t s, const WunSwitches& sw);
 double conv_flops(const ConvArgs& a);        // useful FLOPs (2*MACs) of the launch
@@ -291,8 +321,8 @@ int wgrad_max_units(const WgradArgs& a, const WunSwitches& sw);
 
 int  wgrad_pick_nsplit(const WgradArgs& a, const WunSwitches& sw);
 hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s, const WunSwitches& sw);
-// host only: would launch_wgrad accept `a` (family by a.bf16 / a.win; pointers, shape, resolved geometry)?  The launchers'
-// own refusals, asked before any GPU work (wun_op_wgrad_ex).
+// host only: would launch_wgrad accept `a` (family by a.bf16 / a.win; pointers, shape, resolved geometry)?  The family's
+// resolve step without the launch, asked before any GPU work (wun_op_wgrad_ex); a.nsplit need not be set yet.
 bool wgrad_launch_ok(const WgradArgs& a, const WunSwitches& sw);
 bool wgrad_bf16_launch_ok(const WgradArgs& a);
 bool wgrad_win_launch_ok(const WgradArgs& a, const WunSwitches& sw);

@@ -992,48 +992,80 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(ConvArgs a, i
 static thread_local int t_last_fused_ups = 0;       // conv_last_fused_ups()
 
 // variant table -------------------------------------------------------------------------
+// The tiles of conv_mfma_kernel, each stated once: X(index, MT, NW, WT, WN, CK, FOLD).  The rows make kConvVariants[] and the
+// dispatch switch of launch_conv; the further instantiations of a row (DMA staging, scalar weight loads, in-workgroup
+// split-K) follow from the row and the two index lists below (conv_launch_tile).
+#define WUN_CONV_TILES(X) \
+    X( 0, 4, 2, 4, 1, 8, 0) X( 1, 4, 3, 4, 1, 8, 0) X( 2, 4, 4, 4, 1, 8, 0) X( 3, 4, 5, 4, 1, 8, 0)   /*  0..3 : 256 x 32/48/64/80 */ \
+    X( 4, 2, 2, 4, 1, 8, 0) X( 5, 2, 3, 4, 1, 8, 0) X( 6, 2, 4, 4, 1, 8, 0) X( 7, 2, 5, 4, 1, 8, 0)   /*  4..7 : 128 x 32/48/64/80 */ \
+    X( 8, 1, 2, 4, 1, 8, 0) X( 9, 1, 3, 4, 1, 8, 0)                                                   /*  8..9 :  64 x 32/48 */ \
+    X(10, 1, 2, 2, 2, 8, 0) X(11, 1, 3, 2, 2, 8, 0)                                                   /* 10..11:  32 x 64/96 */ \
+    X(12, 1, 2, 1, 4, 8, 0)                                                                           /* 12    :  16 x 128 */ \
+    X(13, 4, 2, 4, 1, 4, 0) X(14, 1, 2, 4, 1, 4, 0)                                                   /* 13..14: 1-/2-channel audio input */ \
+    X(15, 2, 6, 4, 1, 8, 0) X(16, 4, 6, 4, 1, 8, 0)                                                   /* 15..16: 128/256 x 96 (fused two-phase dgrad) */ \
+    /* non-power-of-two tile heights: let the autotuner land the workgroup count on a multiple of */ \
+    /* the 256 CUs (e.g. T = 9203: 96 tiles of 192 rows x 16 excerpts = 6 workgroups per CU) */ \
+    X(17, 3, 2, 4, 1, 8, 0) X(18, 3, 3, 4, 1, 8, 0) X(19, 3, 4, 4, 1, 8, 0) X(20, 3, 5, 4, 1, 8, 0)   /* 17..20: 192 x 32/48/64/80 */ \
+    X(21, 3, 6, 4, 1, 8, 0)                                                                           /* 21    : 192 x 96 */ \
+    X(22, 5, 2, 4, 1, 8, 0) X(23, 5, 3, 4, 1, 8, 0)                                                   /* 22..23: 320 x 32/48 */ \
+    X(24, 6, 2, 4, 1, 8, 0) X(25, 6, 3, 4, 1, 8, 0)                                                   /* 24..25: 384 x 32/48 */ \
+    /* 4-channel chunks for stride-1 launches: half the LDS weight slab -> 3+ workgroups per CU */ \
+    X(26, 4, 3, 4, 1, 4, 0) X(27, 2, 3, 4, 1, 4, 0) X(28, 3, 3, 4, 1, 4, 0) X(29, 2, 2, 4, 1, 4, 0) X(30, 3, 2, 4, 1, 4, 0) \
+    X(31, 4, 5, 4, 1, 4, 0) X(32, 3, 5, 4, 1, 4, 0) X(33, 2, 5, 4, 1, 4, 0) \
+    /* FOLD tiles for the deep levels: M = flattened (excerpt, position) */ \
+    X(34, 1, 2, 4, 1, 8, 1) X(35, 1, 3, 4, 1, 8, 1)                                                   /* 34..35:  64 x 32/48 */ \
+    X(36, 2, 2, 4, 1, 8, 1) X(37, 2, 3, 4, 1, 8, 1)                                                   /* 36..37: 128 x 32/48 */ \
+    X(38, 2, 3, 2, 2, 8, 1) X(39, 4, 3, 2, 2, 8, 1)                                                   /* 38..39:  64/128 x 96 */ \
+    X(40, 2, 2, 2, 2, 8, 1) X(41, 4, 2, 2, 2, 8, 1)                                                   /* 40..41:  64/128 x 64 */
 struct ConvVariant { int MT, NW, WT, WN, CK, fold; };
-static const ConvVariant kConvVariants[] = {
-    {4, 2, 4, 1, 8}, {4, 3, 4, 1, 8}, {4, 4, 4, 1, 8}, {4, 5, 4, 1, 8},   //  0..3 : 256 x 32/48/64/80
-    {2, 2, 4, 1, 8}, {2, 3, 4, 1, 8}, {2, 4, 4, 1, 8}, {2, 5, 4, 1, 8},   //  4..7 : 128 x 32/48/64/80
-    {1, 2, 4, 1, 8}, {1, 3, 4, 1, 8},                                     //  8..9 :  64 x 32/48
-    {1, 2, 2, 2, 8}, {1, 3, 2, 2, 8},                                     // 10..11:  32 x 64/96
-    {1, 2, 1, 4, 8},                                                      // 12    :  16 x 128
-    {4, 2, 4, 1, 4}, {1, 2, 4, 1, 4},                                     // 13..14: 1-/2-channel audio input
-    {2, 6, 4, 1, 8}, {4, 6, 4, 1, 8},                                     // 15..16: 128/256 x 96 (fused two-phase dgrad)
-    // non-power-of-two tile heights: let the autotuner land the workgroup count on a multiple of
-    // the 256 CUs (e.g. T = 9203: 96 tiles of 192 rows x 16 excerpts = 6 workgroups per CU)
-    {3, 2, 4, 1, 8}, {3, 3, 4, 1, 8}, {3, 4, 4, 1, 8}, {3, 5, 4, 1, 8},   // 17..20: 192 x 32/48/64/80
-    {3, 6, 4, 1, 8},                                                      // 21    : 192 x 96
-    {5, 2, 4, 1, 8}, {5, 3, 4, 1, 8},                                     // 22..23: 320 x 32/48
-    {6, 2, 4, 1, 8}, {6, 3, 4, 1, 8},                                     // 24..25: 384 x 32/48
-    // 4-channel chunks for stride-1 launches: half the LDS weight slab -> 3+ workgroups per CU
-    {4, 3, 4, 1, 4}, {2, 3, 4, 1, 4}, {3, 3, 4, 1, 4}, {2, 2, 4, 1, 4}, {3, 2, 4, 1, 4},   // 26..30
-    {4, 5, 4, 1, 4}, {3, 5, 4, 1, 4}, {2, 5, 4, 1, 4},                                    // 31..33
-    // FOLD tiles for the deep levels: M = flattened (excerpt, position)
-    {1, 2, 4, 1, 8, 1}, {1, 3, 4, 1, 8, 1},                               // 34..35:  64 x 32/48
-    {2, 2, 4, 1, 8, 1}, {2, 3, 4, 1, 8, 1},                               // 36..37: 128 x 32/48
-    {2, 3, 2, 2, 8, 1}, {4, 3, 2, 2, 8, 1},                               // 38..39:  64/128 x 96
-    {2, 2, 2, 2, 8, 1}, {4, 2, 2, 2, 8, 1},                               // 40..41:  64/128 x 64
-};
-#define WUN_FIRST_FOLD_VARIANT 34
+#define WUN_ROW(i, MT, NW, WT, WN, CK, F) {MT, NW, WT, WN, CK, F},
+static constexpr ConvVariant kConvVariants[] = {WUN_CONV_TILES(WUN_ROW)};
+#undef WUN_ROW
+#define WUN_ROW(i, MT, NW, WT, WN, CK, F) i,
+static constexpr int kConvRowIndex[] = {WUN_CONV_TILES(WUN_ROW)};
+#undef WUN_ROW
+static constexpr int kNumConvTiles = (int)(sizeof(kConvVariants) / sizeof(kConvVariants[0]));
+static constexpr bool conv_rows_in_order() {
+    for (int i = 0; i < kNumConvTiles; ++i)
+        if (kConvRowIndex[i] != i) return false;
+    return true;
+}
+static_assert(conv_rows_in_order(), "row i of WUN_CONV_TILES is variant i (tuning tables store the index)");
+static_assert(kNumConvTiles == WUN_FIRST_RETIRED_VARIANT, "the retired index range follows the tile table");
 
-// In-workgroup split-K variants (conv_mfma_kernel<..., KG = 3>): variant WUN_FIRST_K3_VARIANT + i runs the tile of
+template <int N>
+static constexpr bool in_list(const int (&list)[N], int i) {
+    for (int k = 0; k < N; ++k)
+        if (list[k] == i) return true;
+    return false;
+}
+
+// In-workgroup split-K variants (conv_mfma_kernel<..., KG = 3>): variant kFirstK3 + i runs the tile of
 // kK3Base[i] with three 256-thread groups per workgroup.  3 divides the chunk count of every layer of this network
 // (channel counts are multiples of 24 = 3 chunks of 8), 4 does not.
 #define WUN_KG 3
-static const int kK3Base[] = {8, 9, 10, 11, 4, 5, 34, 35, 36, 37, 40};
-static const int kNumK3 = (int)(sizeof(kK3Base) / sizeof(kK3Base[0]));
-static int first_k3_variant();
-static inline bool is_k3(int v) { return v >= first_k3_variant() && v < first_k3_variant() + kNumK3; }
-static inline int conv_tile_variant(int v) { return is_k3(v) ? kK3Base[v - first_k3_variant()] : v; }   // index into kConvVariants
+static constexpr int kK3Base[] = {8, 9, 10, 11, 4, 5, 34, 35, 36, 37, 40};
+static constexpr int kNumK3 = (int)(sizeof(kK3Base) / sizeof(kK3Base[0]));
+static constexpr int kFirstK3 = WUN_FIRST_RETIRED_VARIANT + WUN_NUM_RETIRED_VARIANTS;
+static inline bool is_k3(int v) { return v >= kFirstK3 && v < kFirstK3 + kNumK3; }
+int conv_num_variants() { return kFirstK3 + kNumK3; }
+
+// Channel counts that are not multiples of 4, or unaligned weights (non-shipped configs): scalar weight loads on this fixed
+// menu.  The audio-input pair also serves every launch of <= 4 input channels.
+static constexpr int kScalarTiles[] = {13, 14, 12, 9, 1};
+static int conv_scalar_menu(const ConvArgs& a) {
+    if (a.C0 + a.C1 <= 4) return kScalarTiles[a.Tout > 64 ? 0 : 1];
+    return kScalarTiles[a.Tout <= 16 ? 2 : (a.Tout <= 64 ? 3 : 4)];
+}
+
+static inline int conv_J(const ConvArgs& a) { return a.loader == LOADER_DEINT ? (a.KW + 1) / 2 : a.KW; }
 
 // can this launch use FOLD variant `v`?  (segments of every excerpt a tile touches must fit the LDS row)
 static bool conv_fold_ok(const ConvArgs& a, int v) {
     const ConvVariant& cv = kConvVariants[v];
     if (!cv.fold || (a.flags & F_PHASE2)) return false;
     const int TT = cv.WT * cv.MT * 16;
-    const int J = a.loader == LOADER_DEINT ? (a.KW + 1) / 2 : a.KW;
+    const int J = conv_J(a);
     long long nb = (TT - 1) / a.Tout + 2;
     if (nb > a.B) nb = a.B;
     if (nb * (a.Tout + J - 1) > WUN_FOLD_XCAP(TT)) return false;
@@ -1041,8 +1073,6 @@ static bool conv_fold_ok(const ConvArgs& a, int v) {
     const long long span0 = a.bs0 * (long long)a.B, span1 = a.src1 ? a.bs1 * (long long)a.B : 0;
     return span0 < (1ll << 31) && span1 < (1ll << 31);
 }
-
-static inline int conv_J(const ConvArgs& a) { return a.loader == LOADER_DEINT ? (a.KW + 1) / 2 : a.KW; }
 
 static int pick_nw(int N, const int* cands, int ncand) {
     // fewest padded columns; ties resolved by the order of `cands`
@@ -1057,7 +1087,7 @@ static int pick_nw(int N, const int* cands, int ncand) {
 
 int conv_pick_variant(const ConvArgs& a) {
     const int Ctot = a.C0 + a.C1;
-    if (Ctot <= 4) return a.Tout > 64 ? 13 : 14;
+    if (Ctot <= 4) return conv_scalar_menu(a);
     if (a.Tout <= 96 && a.B > 1 && (a.N & 3) == 0) {
         // deep levels: fold the batch into M; 128-row tiles when there are enough rows to fill the chip
         const int c[2] = {3, 2};
@@ -1099,7 +1129,6 @@ long long conv_natural_wgs_phase2(const ConvArgs& a) {
     return (long long)((a.Tout + TT - 1) / TT) * ((a.N + half - 1) / half) * a.B;
 }
 
-static inline int conv_J(const ConvArgs& a);
 // Vector (16-byte) paths need aligned bases / pitches; everything the plan allocates is.
 void conv_output_setup(ConvArgs& a) {
     if (a.acc_len == 0) { a.acc_lo = 0; a.acc_len = 0x7FFFFFFFu; }          // F_ACCUM over the whole row (default)
@@ -1130,189 +1159,165 @@ static bool conv_xvec_ok(const ConvArgs& a, int variant, const WunSwitches& sw) 
     return true;
 }
 
-static void conv_geom(const ConvArgs& a, int variant, const WunSwitches& sw, int& TT, int& NT, int& J, int& XP, int& WP) {
-    const ConvVariant& v = kConvVariants[variant];
-    TT = v.WT * v.MT * 16;
-    NT = v.WN * v.NW * 16;
-    J = conv_J(a);
-    XP = fit_pitch(v.fold ? WUN_FOLD_XCAP(TT) : TT + J - 1, 16);
-    if (conv_xvec_ok(a, variant, sw)) XP = conv_dma_pitch(TT + J - 1 + 3);       // whole 16-byte granules incl. the sub-vector shift
-    WP = fit_pitch(NT, 16);
-}
-
-// workgroup tiles along M (per excerpt, or over the flattened batch for FOLD) and the excerpt factor of the grid
-static inline long long conv_mtiles(const ConvArgs& a, int variant, int TT, int& bfac) {
-    if (kConvVariants[variant].fold) { bfac = 1; return ((long long)a.B * a.Tout + TT - 1) / TT; }
-    bfac = a.B;
-    return (a.Tout + TT - 1) / TT;
-}
-
-size_t conv_lds_bytes(const ConvArgs& a, int variant, const WunSwitches& sw) {
-    if (is_k3(variant)) {
-        const int bv = conv_tile_variant(variant);
-        const size_t stage = WUN_KG * conv_lds_bytes(a, bv, sw);
-        const size_t red = (size_t)(WUN_KG - 1) * kConvVariants[bv].MT * kConvVariants[bv].NW * 256 * 16;   // accumulator hand-over
-        return stage > red ? stage : red;
-    }
-    if (variant >= WUN_FIRST_RETIRED_VARIANT) return (size_t)1 << 30;             // retired index range: never launched
-    int TT, NT, J, XP, WP;
-    conv_geom(a, variant, sw, TT, NT, J, XP, WP);
-    const int CK = kConvVariants[variant].CK;
-    return 2 * sizeof(float) * ((size_t)CK * XP + (size_t)J * CK * WP);     // double buffered
-}
-
 double conv_flops(const ConvArgs& a) {
     if (a.flags & F_PHASE2)   // useful work of the transposed conv: every forward tap once per forward output
         return 2.0 * a.kw_full * (double)(a.C0 + a.C1) * a.N * (double)a.Tin * a.B;
     return 2.0 * a.KW * (double)(a.C0 + a.C1) * a.N * (double)a.Tout * a.B;
 }
 
-// split-K decision: (ksplit, chunks per split) from shapes only (deterministic)
-void conv_splitk(const ConvArgs& a, int variant, const WunSwitches& sw, long long part_cap_floats, int& ksplit, int& cps) {
-    int TT, NT, J, XP, WP;
-    conv_geom(a, variant, sw, TT, NT, J, XP, WP);
-    const int CK = kConvVariants[variant].CK;
-    const int CKC = a.loader == LOADER_DEINT ? CK / 2 : CK;
-    const int nchunks = (a.C0 + a.C1 + CKC - 1) / CKC;
-    int bfac;
-    const long long natural = conv_mtiles(a, variant, TT, bfac) * ((a.N + NT - 1) / NT) * bfac;
-    ksplit = 1; cps = nchunks;
-    if (natural >= 512 || nchunks < 2 || part_cap_floats <= 0) return;
-    long long want = (1024 + natural - 1) / natural;
-    if (want > nchunks) want = nchunks;
-    const long long per = (long long)a.B * a.N * ((a.Tout + 3) & ~3);
-    if (want * per > part_cap_floats) want = part_cap_floats / per;
-    if (want < 2) return;
-    cps = (int)((nchunks + want - 1) / want);
-    ksplit = (nchunks + cps - 1) / cps;
-    if (ksplit < 2) { ksplit = 1; cps = nchunks; }
+// Everything launch_conv needs to know about one launch, or a refusal: the one place where a conv launch's instantiation,
+// geometry, split and LDS size are decided (conv_resolve).  launch_conv launches it; conv_choice_ok asks whether it exists.
+struct ConvLaunch {
+    hipError_t err;                 // != hipSuccess: refused, nothing below holds
+    int tile;                       // row of kConvVariants
+    bool vecw, xvec; int kg;        // instantiation of that row: 16-byte weight loads, DMA staging, 256-thread groups
+    int TT, NT, J, XP, WP, nTT, nNT, bfac;
+    int nchunks, ksplit, cps;
+    size_t tile_lds, lds;           // one group's double-buffered stage; the workgroup's dynamic LDS
+    long long grid;
+};
+
+// v: tile variant, or < 0 for the heuristic; ks: split-K factor, or <= 0 for the heuristic (F_PHASE2 launches never split).
+// have_part: a partial buffer of part_cap floats exists -- without one a forced split degrades to 1.
+static ConvLaunch conv_resolve(const ConvArgs& a, int v, int ks, bool have_part, long long part_cap, const WunSwitches& sw) {
+    ConvLaunch r = {};
+    r.err = hipErrorInvalidValue;
+    const bool phase2 = (a.flags & F_PHASE2) != 0;
+    const int Ctot = a.C0 + a.C1;
+    r.J = conv_J(a);
+    if (r.J > WUN_JMAX) return r;                                        // rejected at plan creation
+    r.vecw = (a.N & 3) == 0 && aligned16(a.W);
+    if (phase2 && !(a.ostride == 1 && a.dst1 == nullptr && r.vecw)) return r;
+    r.kg = 1;
+    if (v < 0) r.tile = !r.vecw ? conv_scalar_menu(a) : (phase2 ? conv_pick_variant_phase2(a) : conv_pick_variant(a));
+    else if (is_k3(v)) { r.tile = kK3Base[v - kFirstK3]; r.kg = WUN_KG; }
+    else if (v >= WUN_FIRST_RETIRED_VARIANT) return r;                   // retired index range (wun_internal.h) and beyond
+    else r.tile = v;
+    const ConvVariant& cv = kConvVariants[r.tile];
+    if (v >= 0) {                                                        // tiles the launch's channels / loader cannot run on
+        if (Ctot <= 4 && cv.CK != 4) return r;
+        if (Ctot > 4 && cv.CK == 4 && (a.loader == LOADER_DEINT || phase2 || r.tile < 26)) return r;
+        if (phase2 && !(cv.WN == 1 && ((cv.NW % 2) == 0 || cv.NW == 3))) return r;
+    }
+    if (cv.fold && !conv_fold_ok(a, r.tile)) return r;
+    r.xvec = conv_xvec_ok(a, r.tile, sw);
+    r.TT = cv.WT * cv.MT * 16;
+    r.NT = cv.WN * cv.NW * 16;
+    r.XP = r.xvec ? conv_dma_pitch(r.TT + r.J - 1 + 3)                   // whole 16-byte granules incl. the sub-vector shift
+                  : fit_pitch(cv.fold ? WUN_FOLD_XCAP(r.TT) : r.TT + r.J - 1, 16);
+    r.WP = fit_pitch(r.NT, 16);
+    r.tile_lds = r.lds = 2 * sizeof(float) * ((size_t)cv.CK * r.XP + (size_t)r.J * cv.CK * r.WP);     // double buffered
+    if (r.kg > 1) {
+        // the three staging regions, or the accumulator hand-over, inside the CU's LDS
+        const size_t red = (size_t)(r.kg - 1) * cv.MT * cv.NW * 256 * 16;
+        r.lds = r.kg * r.tile_lds > red ? r.kg * r.tile_lds : red;
+        if (phase2 || r.lds > 160 * 1024) return r;
+    }
+    // workgroup tiles along M (per excerpt, or over the flattened batch for FOLD) and the excerpt factor of the grid
+    r.bfac = cv.fold ? 1 : a.B;
+    r.nTT = cv.fold ? (int)(((long long)a.B * a.Tout + r.TT - 1) / r.TT) : (a.Tout + r.TT - 1) / r.TT;
+    const int chan = phase2 ? r.NT / 2 : r.NT;                           // output channels per workgroup
+    r.nNT = (a.N + chan - 1) / chan;
+    const long long natural = (long long)r.nTT * r.nNT * r.bfac;
+    const int CKC = a.loader == LOADER_DEINT ? cv.CK / 2 : cv.CK;
+    r.nchunks = (Ctot + CKC - 1) / CKC;
+    const long long per = (long long)a.B * a.N * ((a.Tout + 3) & ~3);    // floats of one split's partial sums
+    r.ksplit = 1; r.cps = r.nchunks;
+    if (r.kg > 1) {
+        // every 256-thread group of every split gets the same whole number of chunks (uniform barriers)
+        const int want = (ks > 0 && have_part) ? ks : 1;
+        if (Ctot % CKC != 0 || r.nchunks % (r.kg * want) != 0) return r;
+        if (want > 1 && (long long)want * per > part_cap) return r;
+        r.ksplit = want;
+        r.cps = r.nchunks / (r.kg * want);
+    } else if (ks > 0 && !phase2) {                                      // autotuned choice
+        int want = ks > r.nchunks ? r.nchunks : ks;
+        if (!have_part) want = 1;
+        if (want > 1 && (long long)want * per > part_cap) return r;     // would overrun the scratch
+        r.cps = (r.nchunks + want - 1) / want;
+        r.ksplit = (r.nchunks + r.cps - 1) / r.cps;
+    } else if (natural < 512 && r.nchunks >= 2 && have_part && !phase2 && part_cap > 0) {
+        // from shapes only (deterministic): aim at 1024 workgroups
+        long long want = (1024 + natural - 1) / natural;
+        if (want > r.nchunks) want = r.nchunks;
+        if (want * per > part_cap) want = part_cap / per;
+        if (want >= 2) {
+            r.cps = (int)((r.nchunks + want - 1) / want);
+            r.ksplit = (r.nchunks + r.cps - 1) / r.cps;
+            if (r.ksplit < 2) { r.ksplit = 1; r.cps = r.nchunks; }
+        }
+    }
+    r.grid = natural * r.ksplit;
+    r.err = hipSuccess;
+    return r;
 }
 
+// kernel pointer, LDS attribute, profiler name and tag of one instantiation; every number comes from `r`
 template <int MT, int NW, int WT, int WN, int CK, bool VECW, bool FOLD = false, bool XVEC = false, int KG = 1>
-static hipError_t conv_launch_t(ConvArgs a, int variant, float* part, long long part_cap, hipStream_t s, const WunSwitches& sw) {
-    int TT, NT, J, XP, WP;
-    conv_geom(a, variant, sw, TT, NT, J, XP, WP);
-    const bool phase2 = (a.flags & F_PHASE2) != 0;
-    int bfac;
-    const int nTT = (int)conv_mtiles(a, variant, TT, bfac);
-    const int nNT = phase2 ? (a.N + NT / 2 - 1) / (NT / 2) : (a.N + NT - 1) / NT;
-    size_t lds = conv_lds_bytes(a, variant, sw);
-    if (KG > 1) {
-        const size_t red = (size_t)(KG - 1) * MT * NW * 256 * 16;
-        lds = KG * lds > red ? KG * lds : red;
-        if (phase2 || lds > 160 * 1024) return hipErrorInvalidValue;
-    }
-    if (FOLD && !conv_fold_ok(a, variant)) return hipErrorInvalidValue;
+static hipError_t conv_launch_t(const ConvArgs& a, const ConvLaunch& r, hipStream_t s) {
     auto kern = conv_mfma_kernel<MT, NW, WT, WN, CK, VECW, FOLD, XVEC, KG>;
     static size_t lds_allowed = 64 * 1024;
-    if (lds > lds_allowed) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        lds_allowed = lds;
-    }
-    const size_t lds_launch = lds;
-    int ksplit, cps;
-    conv_splitk(a, variant, sw, (part != nullptr && !phase2) ? part_cap : 0, ksplit, cps);
-    if (a.force_ksplit > 0 && !phase2) {                         // autotuned choice
-        const int CKC = a.loader == LOADER_DEINT ? CK / 2 : CK;
-        const int nchunks = (a.C0 + a.C1 + CKC - 1) / CKC;
-        int want = a.force_ksplit > nchunks ? nchunks : a.force_ksplit;
-        if (part == nullptr) want = 1;
-        const long long per = (long long)a.B * a.N * ((a.Tout + 3) & ~3);
-        if (want > 1 && (long long)want * per > part_cap) return hipErrorInvalidValue;   // would overrun the scratch
-        cps = (nchunks + want - 1) / want;
-        ksplit = (nchunks + cps - 1) / cps;
-    }
-    if (KG > 1) {
-        // every 256-thread group of every split gets the same whole number of chunks (uniform barriers)
-        const int CKC = a.loader == LOADER_DEINT ? CK / 2 : CK;
-        const int nchunks = (a.C0 + a.C1) / CKC;
-        const int want = (a.force_ksplit > 0 && part != nullptr) ? a.force_ksplit : 1;
-        if ((a.C0 + a.C1) % CKC != 0 || nchunks % (KG * want) != 0) return hipErrorInvalidValue;
-        const long long per = (long long)a.B * a.N * ((a.Tout + 3) & ~3);
-        if (want > 1 && (long long)want * per > part_cap) return hipErrorInvalidValue;
-        ksplit = want;
-        cps = nchunks / (KG * want);
-    }
-    a.cps = cps;
-    a.part = ksplit > 1 ? part : nullptr;
-    const long long grid = (long long)nTT * nNT * bfac * ksplit;
-    if (grid <= 0) return hipSuccess;
-    char nm[64];
+    hipError_t e = raise_lds_limit((const void*)kern, r.lds, lds_allowed);
+    if (e != hipSuccess) return e;
+    char nm[64], tag[160];
     snprintf(nm, sizeof(nm), "conv_mfma_kernel<%d, %d, %d, %d, %d, %s%s%s%s>", MT, NW, WT, WN, CK, VECW ? "true" : "false",
              FOLD ? ", fold" : "", XVEC ? ", dma" : "", KG > 1 ? ", k3" : "");
-    {
-        char tag[160];
-        snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d ks=%d ph2=%d acc=%d os=%d grid=%lld", a.C0 + a.C1, a.N,
-                 a.Tout, a.KW, a.loader, a.B, ksplit, (a.flags & F_PHASE2) ? 1 : 0, (a.flags & F_ACCUM) ? 1 : 0,
-                 a.ostride, grid);
-        ProfScope ps(nm, conv_flops(a), s, tag);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256 * KG), lds_launch, s, a, nTT, nNT, J, XP, WP);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || ksplit == 1) return e;
-    const long long total = (long long)a.B * a.N * (((a.Tout + 3) & ~3) >> 2);
-    long long blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    {
-        const double elems = (double)a.B * a.N * a.Tout;
-        double by = 4.0 * elems * (ksplit + 1 + (a.msk0 != nullptr ? 1 : 0) + ((a.flags & F_ACCUM) ? 1 : 0));
-        if (a.ups_y != nullptr) by += 4.0 * (double)a.B * a.N * a.ups_tup;
-        ProfScope ps("conv_splitk_epilogue_kernel", 0.0, s, "", by);
-        hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, ksplit);
-    }
-    t_last_fused_ups = (a.ups_y != nullptr || a.ubw_dz != nullptr) ? 1 : 0;
+    snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d ks=%d ph2=%d acc=%d os=%d grid=%lld", a.C0 + a.C1, a.N,
+             a.Tout, a.KW, a.loader, a.B, r.ksplit, (a.flags & F_PHASE2) ? 1 : 0, (a.flags & F_ACCUM) ? 1 : 0,
+             a.ostride, r.grid);
+    prof_scope_begin(nm, conv_flops(a), s, tag);
+    hipLaunchKernelGGL(kern, dim3((unsigned)r.grid), dim3(256 * KG), r.lds, s, a, r.nTT, r.nNT, r.J, r.XP, r.WP);
+    prof_scope_end(s);
     return hipGetLastError();
+}
+
+// The instantiations of tile row I.  Every row has the 16-byte-weight kernel; rows with 8-channel chunks and no FOLD also the
+// DMA-staging one; the rows of kScalarTiles the scalar-weight one; the rows of kK3Base the three-group ones.
+template <int I, int MT, int NW, int WT, int WN, int CK, bool FOLD>
+static hipError_t conv_launch_tile(const ConvArgs& a, const ConvLaunch& r, hipStream_t s) {
+    constexpr bool DMA = !FOLD && CK == 8;
+    if (r.kg > 1) {
+        if constexpr (in_list(kK3Base, I)) {
+            if constexpr (DMA) {
+                if (r.xvec) return conv_launch_t<MT, NW, WT, WN, CK, true, FOLD, true, WUN_KG>(a, r, s);
+            }
+            return conv_launch_t<MT, NW, WT, WN, CK, true, FOLD, false, WUN_KG>(a, r, s);
+        }
+        return hipErrorInvalidValue;
+    }
+    if (!r.vecw) {
+        if constexpr (in_list(kScalarTiles, I)) return conv_launch_t<MT, NW, WT, WN, CK, false>(a, r, s);
+        return hipErrorInvalidValue;
+    }
+    if constexpr (DMA) {
+        if (r.xvec) return conv_launch_t<MT, NW, WT, WN, CK, true, false, true>(a, r, s);
+    }
+    return conv_launch_t<MT, NW, WT, WN, CK, true, FOLD>(a, r, s);
+}
+
+// The tuner's limits on a resolved launch with forced (tile, split) -- what it may pick, narrower than what would run.
+static bool conv_policy_ok(const ConvArgs& a, const ConvLaunch& r, int ks, const WunSwitches& sw) {
+    const ConvVariant& cv = kConvVariants[r.tile];
+    const bool phase2 = (a.flags & F_PHASE2) != 0;
+    if ((a.N & 3) != 0) return false;                                // scalar-weight fallback: fixed menu
+    if (!cv.fold && r.TT > 16 && r.TT >= 2 * a.Tout) return false;   // mostly padding in time
+    if (cv.fold && (long long)r.TT >= 2ll * a.B * a.Tout) return false;
+    const int chan = phase2 ? r.NT / 2 : r.NT;
+    if (r.nNT * chan * 3 > a.N * 4 + 48) return false;               // > ~33 % padded columns
+    if (r.tile_lds > 150 * 1024) return false;
+    const long long natural = (long long)r.nTT * r.nNT * r.bfac;
+    if (r.kg > 1) return !sw.no_k3 && natural * ks <= 2048;         // (a launch that fills the chip needs no help)
+    return ks == 1 || !(phase2 || ks > r.nchunks || natural * ks > 6144);
 }
 
 // Is (tile variant, split-K factor) a choice the dispatcher may use for this launch?  The single
 // rule set behind the autotuner's candidate list, the test hook's forced choices and imported
 // tuning tables: a choice that fails here is never launched (a stale table cannot push a split
-// past the partial scratch or select a tile the loader does not support).
+// past the partial scratch or select a tile the loader does not support).  = the launch resolves, within the tuner's limits.
 bool conv_choice_ok(const ConvArgs& a, long long part_cap, int v, int ks, const WunSwitches& sw) {
-    const int nvar = (int)(sizeof(kConvVariants) / sizeof(kConvVariants[0]));
-    if (is_k3(v)) {
-        // the tile's own rules, whole chunks for every group of every split, the three staging regions inside the CU's LDS
-        const int bv = conv_tile_variant(v);
-        if (sw.no_k3 || (a.flags & F_PHASE2) || ks < 1 || !conv_choice_ok(a, part_cap, bv, 1, sw)) return false;
-        const ConvVariant& cv = kConvVariants[bv];
-        const int CKC = a.loader == LOADER_DEINT ? cv.CK / 2 : cv.CK;
-        const int Ctot = a.C0 + a.C1;
-        if (Ctot % CKC) return false;
-        const int nchunks = Ctot / CKC;
-        if (nchunks % (WUN_KG * ks) != 0) return false;
-        if (conv_lds_bytes(a, v, sw) > 160 * 1024) return false;
-        const int TT = cv.WT * cv.MT * 16, NT = cv.WN * cv.NW * 16;
-        int bfac;
-        const long long natural = conv_mtiles(a, bv, TT, bfac) * ((a.N + NT - 1) / NT) * bfac;
-        if (natural * ks > 2048) return false;                         // (a launch that fills the chip needs no help)
-        const long long per = (long long)a.B * a.N * ((a.Tout + 3) & ~3);
-        return ks == 1 || (long long)ks * per <= part_cap;
-    }
-    if (v >= WUN_FIRST_RETIRED_VARIANT) return false;                // retired index range (wun_internal.h)
-    if (v < 0 || v >= nvar || ks < 1) return false;
-    const int Ctot = a.C0 + a.C1;
-    const bool phase2 = (a.flags & F_PHASE2) != 0;
-    if ((a.N & 3) != 0) return false;                                // scalar-weight fallback: fixed menu
-    const ConvVariant& cv = kConvVariants[v];
-    if (Ctot <= 4 && cv.CK != 4) return false;
-    if (Ctot > 4 && cv.CK == 4 && (a.loader == LOADER_DEINT || phase2 || v < 26)) return false;
-    if (phase2 && !(cv.WN == 1 && ((cv.NW % 2) == 0 || cv.NW == 3))) return false;
-    if (cv.fold && !conv_fold_ok(a, v)) return false;
-    const int TT = cv.WT * cv.MT * 16;
-    const int NT = phase2 ? cv.WN * cv.NW * 8 : cv.WN * cv.NW * 16;   // channels per workgroup
-    if (!cv.fold && TT > 16 && TT >= 2 * a.Tout) return false;       // mostly padding in time
-    if (cv.fold && (long long)TT >= 2ll * a.B * a.Tout) return false;
-    const int padded = ((a.N + NT - 1) / NT) * NT;
-    if (padded * 3 > a.N * 4 + 48) return false;                      // > ~33 % padded columns
-    if (conv_lds_bytes(a, v, sw) > 150 * 1024) return false;
-    if (ks == 1) return true;
-    const int CKC = a.loader == LOADER_DEINT ? cv.CK / 2 : cv.CK;
-    const int nchunks = (Ctot + CKC - 1) / CKC;
-    int bfac;
-    const long long natural = conv_mtiles(a, v, TT, bfac) * ((a.N + NT - 1) / NT) * bfac;
-    const long long per = (long long)a.B * a.N * ((a.Tout + 3) & ~3);
-    return !(phase2 || ks > nchunks || natural * ks > 6144 || (long long)ks * per > part_cap);
+    if (v < 0 || ks < 1) return false;
+    const ConvLaunch r = conv_resolve(a, v, ks, true, part_cap, sw);
+    return r.err == hipSuccess && conv_policy_ok(a, r, ks, sw);
 }
 
 // Candidate (tile variant, split-K) choices for the autotuner.  Returns the number written.
@@ -1331,12 +1336,24 @@ int conv_list_candidates(const ConvArgs& a, long long part_cap, ConvChoice* out,
     return n;
 }
 
-static_assert(sizeof(kConvVariants) / sizeof(kConvVariants[0]) == WUN_FIRST_RETIRED_VARIANT, "the retired index range follows the tile table");
-static int first_k3_variant() { return WUN_FIRST_RETIRED_VARIANT + WUN_NUM_RETIRED_VARIANTS; }
-int conv_num_variants() { return first_k3_variant() + kNumK3; }
-
-
 int conv_last_fused_ups() { return t_last_fused_ups; }
+
+// bias / activation / mask / accumulate over the sum of `ksplit` partials (0: of nothing), four outputs per thread
+static hipError_t launch_conv_epilogue(const ConvArgs& a, int ksplit, hipStream_t s) {
+    const long long total = (long long)a.B * a.N * (((a.Tout + 3) & ~3) >> 2);
+    if (total <= 0) return hipSuccess;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (ksplit > 0) {
+        const double elems = (double)a.B * a.N * a.Tout;
+        double by = 4.0 * elems * (ksplit + 1 + (a.msk0 != nullptr ? 1 : 0) + ((a.flags & F_ACCUM) ? 1 : 0));
+        if (a.ups_y != nullptr) by += 4.0 * (double)a.B * a.N * a.ups_tup;
+        prof_scope_begin("conv_splitk_epilogue_kernel", 0.0, s, "", by);
+    }
+    hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, ksplit);
+    if (ksplit > 0) prof_scope_end(s);
+    return hipGetLastError();
+}
 
 hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hipStream_t s, const WunSwitches& sw) {
     ConvArgs a = a_in;
@@ -1350,83 +1367,29 @@ hipError_t launch_conv(const ConvArgs& a_in, float* part, long long part_cap, hi
                                 (a.flags & (F_ACCUM | F_PHASE2 | F_LRELU)) != 0 || a.N0 >= a.N || a.ubw_x == nullptr))
         return hipErrorInvalidValue;
     conv_output_setup(a);
-    if (conv_J(a) > WUN_JMAX) return hipErrorInvalidValue;       // rejected at plan creation
-    if (a.KW <= 0) {
-        // no taps (odd output phase of a transposed stride-2 conv with filter_size 1): the conv is the
-        // epilogue of an empty sum -- bias / activation / mask / accumulate through the split-K epilogue
-        const long long total = (long long)a.B * a.N * (((a.Tout + 3) & ~3) >> 2);
-        if (total <= 0) return hipSuccess;
-        long long blocks = (total + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, 0);
-        return hipGetLastError();
+    // no taps (odd output phase of a transposed stride-2 conv with filter_size 1): the conv is the
+    // epilogue of an empty sum -- bias / activation / mask / accumulate through the split-K epilogue
+    if (a.KW <= 0) return launch_conv_epilogue(a, 0, s);
+    // a forced tile needs 16-byte weight loads (ignored otherwise; force_ksplit still holds) and is taken whole or refused:
+    // its split is not dropped for want of a partial buffer
+    const bool forced = a.force_variant > 0 && (a.N & 3) == 0 && aligned16(a.W);
+    const ConvLaunch r = conv_resolve(a, forced ? a.force_variant - 1 : -1, a.force_ksplit, forced || part != nullptr,
+                                      part != nullptr ? part_cap : 0, sw);
+    if (r.err != hipSuccess) return r.err;
+    if (forced && !conv_policy_ok(a, r, a.force_ksplit > 0 ? a.force_ksplit : 1, sw)) return hipErrorInvalidValue;
+    if (r.grid <= 0) return hipSuccess;
+    a.cps = r.cps;
+    a.part = r.ksplit > 1 ? part : nullptr;
+    hipError_t e = hipErrorInvalidValue;
+    switch (r.tile) {
+#define WUN_ROW(i, MT, NW, WT, WN, CK, F) case i: e = conv_launch_tile<i, MT, NW, WT, WN, CK, F != 0>(a, r, s); break;
+        WUN_CONV_TILES(WUN_ROW)
+#undef WUN_ROW
     }
-    const bool vecw = (a.N & 3) == 0 && aligned16(a.W);
-    if ((a.flags & F_PHASE2) && !(a.ostride == 1 && a.dst1 == nullptr && vecw)) return hipErrorInvalidValue;
-    int v = (a.flags & F_PHASE2) ? conv_pick_variant_phase2(a) : conv_pick_variant(a);
-    if (a.force_variant > 0 && vecw) {
-        v = a.force_variant - 1;
-        if (!conv_choice_ok(a, part != nullptr ? part_cap : 0, v, a.force_ksplit > 0 ? a.force_ksplit : 1, sw)) return hipErrorInvalidValue;
-    }
-    if (is_k3(v)) {
-        const int bv = conv_tile_variant(v);
-        const bool xv3 = conv_xvec_ok(a, bv, sw);
-#define WUN_K3(i, MT, NW, WT, WN) case i: \
-        if (xv3) return conv_launch_t<MT, NW, WT, WN, 8, true, false, true, WUN_KG>(a, bv, part, part_cap, s, sw); \
-        return conv_launch_t<MT, NW, WT, WN, 8, true, false, false, WUN_KG>(a, bv, part, part_cap, s, sw);
-#define WUN_K3F(i, MT, NW, WT, WN) case i: return conv_launch_t<MT, NW, WT, WN, 8, true, true, false, WUN_KG>(a, bv, part, part_cap, s, sw);
-        switch (bv) {
-            WUN_K3(8, 1, 2, 4, 1) WUN_K3(9, 1, 3, 4, 1) WUN_K3(10, 1, 2, 2, 2) WUN_K3(11, 1, 3, 2, 2)
-            WUN_K3(4, 2, 2, 4, 1) WUN_K3(5, 2, 3, 4, 1)
-            WUN_K3F(34, 1, 2, 4, 1) WUN_K3F(35, 1, 3, 4, 1) WUN_K3F(36, 2, 2, 4, 1) WUN_K3F(37, 2, 3, 4, 1)
-            WUN_K3F(40, 2, 2, 2, 2)
-            default: return hipErrorInvalidValue;
-        }
-#undef WUN_K3
-#undef WUN_K3F
-    }
-    if (v >= WUN_FIRST_RETIRED_VARIANT) return hipErrorInvalidValue;
-    if (!vecw) {
-        // channel counts that are not multiples of 4 (non-shipped configs): scalar weight loads,
-        // restricted tile menu
-        const int Ctot = a.C0 + a.C1;
-        if (Ctot <= 4) v = a.Tout > 64 ? 13 : 14;
-        else v = a.Tout <= 16 ? 12 : (a.Tout <= 64 ? 9 : 1);
-        switch (v) {
-            case 1: return conv_launch_t<4, 3, 4, 1, 8, false>(a, v, part, part_cap, s, sw);
-            case 9: return conv_launch_t<1, 3, 4, 1, 8, false>(a, v, part, part_cap, s, sw);
-            case 12: return conv_launch_t<1, 2, 1, 4, 8, false>(a, v, part, part_cap, s, sw);
-            case 13: return conv_launch_t<4, 2, 4, 1, 4, false>(a, v, part, part_cap, s, sw);
-            default: return conv_launch_t<1, 2, 4, 1, 4, false>(a, v, part, part_cap, s, sw);
-        }
-    }
-    const bool xv = conv_xvec_ok(a, v, sw);
-#define WUN_CV(i, MT, NW, WT, WN, CK) case i: \
-        if (xv) return conv_launch_t<MT, NW, WT, WN, CK, true, false, true>(a, v, part, part_cap, s, sw); \
-        return conv_launch_t<MT, NW, WT, WN, CK, true>(a, v, part, part_cap, s, sw);
-#define WUN_CV4(i, MT, NW, WT, WN, CK) case i: return conv_launch_t<MT, NW, WT, WN, CK, true>(a, v, part, part_cap, s, sw);
-    switch (v) {
-        WUN_CV(0, 4, 2, 4, 1, 8) WUN_CV(1, 4, 3, 4, 1, 8) WUN_CV(2, 4, 4, 4, 1, 8) WUN_CV(3, 4, 5, 4, 1, 8)
-        WUN_CV(4, 2, 2, 4, 1, 8) WUN_CV(5, 2, 3, 4, 1, 8) WUN_CV(6, 2, 4, 4, 1, 8) WUN_CV(7, 2, 5, 4, 1, 8)
-        WUN_CV(8, 1, 2, 4, 1, 8) WUN_CV(9, 1, 3, 4, 1, 8)
-        WUN_CV(10, 1, 2, 2, 2, 8) WUN_CV(11, 1, 3, 2, 2, 8)
-        WUN_CV(12, 1, 2, 1, 4, 8)
-        WUN_CV4(13, 4, 2, 4, 1, 4) WUN_CV4(14, 1, 2, 4, 1, 4)
-        WUN_CV(15, 2, 6, 4, 1, 8) WUN_CV(16, 4, 6, 4, 1, 8)
-        WUN_CV(17, 3, 2, 4, 1, 8) WUN_CV(18, 3, 3, 4, 1, 8) WUN_CV(19, 3, 4, 4, 1, 8) WUN_CV(20, 3, 5, 4, 1, 8)
-        WUN_CV(21, 3, 6, 4, 1, 8)
-        WUN_CV(22, 5, 2, 4, 1, 8) WUN_CV(23, 5, 3, 4, 1, 8)
-        WUN_CV(24, 6, 2, 4, 1, 8) WUN_CV(25, 6, 3, 4, 1, 8)
-        WUN_CV4(26, 4, 3, 4, 1, 4) WUN_CV4(27, 2, 3, 4, 1, 4) WUN_CV4(28, 3, 3, 4, 1, 4) WUN_CV4(29, 2, 2, 4, 1, 4)
-        WUN_CV4(30, 3, 2, 4, 1, 4) WUN_CV4(31, 4, 5, 4, 1, 4) WUN_CV4(32, 3, 5, 4, 1, 4) WUN_CV4(33, 2, 5, 4, 1, 4)
-#define WUN_CF(i, MT, NW, WT, WN, CK) case i: return conv_launch_t<MT, NW, WT, WN, CK, true, true>(a, v, part, part_cap, s, sw);
-        WUN_CF(34, 1, 2, 4, 1, 8) WUN_CF(35, 1, 3, 4, 1, 8) WUN_CF(36, 2, 2, 4, 1, 8) WUN_CF(37, 2, 3, 4, 1, 8)
-        WUN_CF(38, 2, 3, 2, 2, 8) WUN_CF(39, 4, 3, 2, 2, 8) WUN_CF(40, 2, 2, 2, 2, 8) WUN_CF(41, 4, 2, 2, 2, 8)
-#undef WUN_CF
-        default: return hipErrorInvalidValue;
-    }
-#undef WUN_CV
-#undef WUN_CV4
+    if (e != hipSuccess || r.ksplit == 1) return e;
+    e = launch_conv_epilogue(a, r.ksplit, s);
+    t_last_fused_ups = (a.ups_y != nullptr || a.ubw_dz != nullptr) ? 1 : 0;
+    return e;
 }
 
 // =====================================================================================
@@ -1874,28 +1837,49 @@ int wgrad_pick_nsplit(const WgradArgs& a, const WunSwitches& sw) {
     return (int)ns;
 }
 
+// the instantiated (MTW, NW) of wgrad_mfma_kernel, stated once
+#define WUN_WG_TILES(WUN_WG) \
+    WUN_WG(1, 1) WUN_WG(1, 2) WUN_WG(1, 3) \
+    WUN_WG(2, 1) WUN_WG(2, 2) WUN_WG(2, 3) \
+    WUN_WG(4, 1) WUN_WG(4, 2) WUN_WG(4, 3) \
+    WUN_WG(6, 1) WUN_WG(6, 2) WUN_WG(6, 3) \
+    WUN_WG(1, 4) WUN_WG(2, 4) WUN_WG(4, 4) \
+    WUN_WG(1, 5) WUN_WG(2, 5) WUN_WG(4, 5)
+
+// one launch of the LDS-tiled weight gradient, or a refusal (wgrad_resolve): launch_wgrad launches it, wgrad_launch_ok asks
+struct WgradLaunch { hipError_t err; WgradGeom g; WgradSplit sp; };
+static WgradLaunch wgrad_resolve(const WgradArgs& a) {
+    WgradLaunch r = {};
+    r.err = hipErrorInvalidValue;
+    if (!wgrad_rows_aligned(a)) return r;           // (the plan's buffers are; the single-op entry points repack)
+    const WgradGeom& g = r.g = wgrad_geom(a);
+    if ((long long)g.nChMax * g.XW4 > (long long)WUN_WG_XIT * 256) return r;
+    if (g.lds > 160 * 1024) return r;               // the CU's LDS
+#define WUN_WG_IS(M, N) || (g.MTW == M && g.NW == N)
+    if (!(false WUN_WG_TILES(WUN_WG_IS))) return r;
+#undef WUN_WG_IS
+    r.sp = wgrad_split(a, g.TK, (long long)g.nMG * g.nNG);
+    r.err = hipSuccess;
+    return r;
+}
+
 template <int MTW, int NW>
-static hipError_t wgrad_launch_t(WgradArgs a, const WgradGeom& g, hipStream_t s) {
-    a.nQT = (a.Tq + g.TK - 1) / g.TK;
-    const long long units = (long long)a.B * a.nQT;
-    a.units_per_split = (int)((units + a.nsplit - 1) / a.nsplit);
-    const bool acc = a.accum && a.direct;           // (split launches write partials: the plain kernel)
+static hipError_t wgrad_launch_t(WgradArgs a, const WgradLaunch& r, hipStream_t s) {
+    const WgradGeom& g = r.g;
+    const bool acc = r.sp.acc;
+    a.nQT = r.sp.nQT;
+    a.units_per_split = r.sp.units_per_split;
     auto kern = acc ? wgrad_mfma_kernel<MTW, NW, true> : wgrad_mfma_kernel<MTW, NW>;
     static size_t lds_allowed[2] = {64 * 1024, 64 * 1024};
-    size_t& allowed = lds_allowed[acc ? 1 : 0];
-    if (g.lds > allowed) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
-        if (e != hipSuccess) return e;
-        allowed = g.lds;
-    }
-    const long long grid = (long long)g.nMG * g.nNG * a.nsplit;
+    hipError_t e = raise_lds_limit((const void*)kern, g.lds, lds_allowed[acc ? 1 : 0]);
+    if (e != hipSuccess) return e;
     char nm[64];
     snprintf(nm, sizeof(nm), acc ? "wgrad_mfma_acc_kernel<%d, %d>" : "wgrad_mfma_kernel<%d, %d>", MTW, NW);
     char tag[160];
     snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nsplit=%d grid=%lld", a.C0 + a.C1, a.N, a.Tq, a.KW,
-             a.loader, a.B, a.nsplit, grid);
+             a.loader, a.B, a.nsplit, r.sp.grid);
     ProfScope ps(nm, 2.0 * a.KW * (double)(a.C0 + a.C1) * a.N * (double)a.Tq * a.B, s, tag);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), g.lds, s, a, g.nMG, g.nNG, g.TK, g.XP,
+    hipLaunchKernelGGL(kern, dim3((unsigned)r.sp.grid), dim3(256), g.lds, s, a, g.nMG, g.nNG, g.TK, g.XP,
                        g.ZP, g.nChMax, g.ONESP, g.XW4);
     return hipGetLastError();
 }
@@ -1903,35 +1887,18 @@ static hipError_t wgrad_launch_t(WgradArgs a, const WgradGeom& g, hipStream_t s)
 hipError_t launch_wgrad(const WgradArgs& a, hipStream_t s, const WunSwitches& sw) {
     if (a.bf16) return launch_wgrad_bf16(a, s);
     if (a.win) return launch_wgrad_win(a, s, sw);
-    // canonical layout required (the plan's buffers are; the single-op entry points repack)
-    if ((a.pitch0 & 3) || (a.bs0 & 3) || (reinterpret_cast<uintptr_t>(a.src0) & 15) || a.pitch0 < 4) return hipErrorInvalidValue;
-    if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || a.pitch1 < 4)) return hipErrorInvalidValue;
-    if ((a.dzpitch & 3) || (a.dzbs & 3) || (reinterpret_cast<uintptr_t>(a.dz) & 15) || a.dzpitch < 4) return hipErrorInvalidValue;
-    const WgradGeom g = wgrad_geom(a);
-    if ((long long)g.nChMax * g.XW4 > (long long)WUN_WG_XIT * 256) return hipErrorInvalidValue;
-#define WUN_WG(M, N) if (g.MTW == M && g.NW == N) return wgrad_launch_t<M, N>(a, g, s);
-    WUN_WG(1, 1) WUN_WG(1, 2) WUN_WG(1, 3)
-    WUN_WG(2, 1) WUN_WG(2, 2) WUN_WG(2, 3)
-    WUN_WG(4, 1) WUN_WG(4, 2) WUN_WG(4, 3)
-    WUN_WG(6, 1) WUN_WG(6, 2) WUN_WG(6, 3)
-    WUN_WG(1, 4) WUN_WG(2, 4) WUN_WG(4, 4)
-    WUN_WG(1, 5) WUN_WG(2, 5) WUN_WG(4, 5)
-#undef WUN_WG
+    const WgradLaunch r = wgrad_resolve(a);
+    if (r.err != hipSuccess) return r.err;
+#define WUN_WG_GO(M, N) if (r.g.MTW == M && r.g.NW == N) return wgrad_launch_t<M, N>(a, r, s);
+    WUN_WG_TILES(WUN_WG_GO)
+#undef WUN_WG_GO
     return hipErrorInvalidValue;
 }
 
-// the refusals of launch_wgrad (and of the family launchers it forwards to) without the launch
 bool wgrad_launch_ok(const WgradArgs& a, const WunSwitches& sw) {
     if (a.bf16) return wgrad_bf16_launch_ok(a);
     if (a.win) return wgrad_win_launch_ok(a, sw);
-    if ((a.pitch0 & 3) || (a.bs0 & 3) || (reinterpret_cast<uintptr_t>(a.src0) & 15) || a.pitch0 < 4) return false;
-    if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || a.pitch1 < 4)) return false;
-    if ((a.dzpitch & 3) || (a.dzbs & 3) || (reinterpret_cast<uintptr_t>(a.dz) & 15) || a.dzpitch < 4) return false;
-    const WgradGeom g = wgrad_geom(a);
-    if ((long long)g.nChMax * g.XW4 > (long long)WUN_WG_XIT * 256) return false;
-    if (g.lds > 160 * 1024) return false;
-    return (g.NW <= 3 && (g.MTW == 1 || g.MTW == 2 || g.MTW == 4 || g.MTW == 6)) ||
-           ((g.NW == 4 || g.NW == 5) && (g.MTW == 1 || g.MTW == 2 || g.MTW == 4));
+    return wgrad_resolve(a).err == hipSuccess;
 }
 
 void wgrad_resolved_geom(const WgradArgs& a, int& mtw, int& nw) {

@@ -388,72 +388,82 @@ int narrow_wgrad_pick_nsplit(const NarrowWgradArgs& a, const WunSwitches& sw) {
     return ns < 1 ? 1 : ns;
 }
 
+// The instantiations, stated once.  Streaming form: (stride, dz element type, its `et`, input channels) -- the audio itself is
+// always fp32.  LDS-staged form: (tap capacity, stride, et) with the element-type combinations the plan produces: all fp32;
+// the bf16 mode's audio-input conv (fp32 audio, bf16 dz); the bf16 mode's head (fp32 audio + bf16 feature map, fp32
+// d(pre-activation)).
+#define WUN_NS_TILES(WUN_NSK) \
+    WUN_NSK(1, float, 0, 1) WUN_NSK(2, float, 0, 1) WUN_NSK(1, bf16_t, 4, 1) WUN_NSK(2, bf16_t, 4, 1) \
+    WUN_NSK(1, float, 0, 2) WUN_NSK(2, float, 0, 2) WUN_NSK(1, bf16_t, 4, 2) WUN_NSK(2, bf16_t, 4, 2)
+#define WUN_NW_ETS(WUN_NWE, K, S) WUN_NWE(K, S, 0) WUN_NWE(K, S, 4) WUN_NWE(K, S, 2)
+#define WUN_NW_TILES(WUN_NWE) WUN_NW_ETS(WUN_NWE, 3, 1) WUN_NW_ETS(WUN_NWE, 3, 2) WUN_NW_ETS(WUN_NWE, 15, 1) WUN_NW_ETS(WUN_NWE, 15, 2)
+
+// one narrow weight-gradient launch, or a refusal (narrow_wgrad_resolve): launch_narrow_wgrad launches it,
+// narrow_wgrad_launch_ok asks
+struct NarrowLaunch { hipError_t err; bool stream; int KT; size_t lds; int nQT, units_per_split; };
+static NarrowLaunch narrow_wgrad_resolve(const NarrowWgradArgs& a, const WunSwitches& sw) {
+    NarrowLaunch r = {};
+    r.err = hipErrorInvalidValue;
+    if (!narrow_wgrad_supported(a)) return r;
+    r.stream = narrow_stream_ok(a, sw);
+    r.KT = r.stream ? 15 : narrow_kt(a.KW);
+    r.lds = r.stream ? 0 : narrow_wgrad_lds(a);
+    if (r.lds > 160 * 1024) return r;
+#define WUN_NS_IS(SI, ZT, E, CI) || (a.stride == SI && a.et == E && a.C0 == CI)
+#define WUN_NW_IS(K, S, E) || (r.KT == K && a.stride == S && a.et == E)
+    if (!(r.stream ? (false WUN_NS_TILES(WUN_NS_IS)) : (false WUN_NW_TILES(WUN_NW_IS)))) return r;
+#undef WUN_NS_IS
+#undef WUN_NW_IS
+    r.nQT = (a.Tq + WUN_NW_TQ - 1) / WUN_NW_TQ;
+    const int ns = a.nsplit > 0 ? a.nsplit : 1;       // (narrow_wgrad_launch_ok asks before the caller has picked a split count)
+    r.units_per_split = (a.B * r.nQT + ns - 1) / ns;
+    r.err = hipSuccess;
+    return r;
+}
+
 // a.nsplit / a.split_base / a.partial set by the caller
 hipError_t launch_narrow_wgrad(NarrowWgradArgs a, hipStream_t s, const WunSwitches& sw) {
-    if (!narrow_wgrad_supported(a)) return hipErrorInvalidValue;
-    a.nQT = (a.Tq + WUN_NW_TQ - 1) / WUN_NW_TQ;
-    const int units = a.B * a.nQT;
-    a.units_per_split = (units + a.nsplit - 1) / a.nsplit;
-    if (narrow_stream_ok(a, sw)) {
-        char tag[160];
+    const NarrowLaunch r = narrow_wgrad_resolve(a, sw);
+    if (r.err != hipSuccess) return r.err;
+    a.nQT = r.nQT;
+    a.units_per_split = r.units_per_split;
+    char tag[160];
+    if (r.stream) {
         snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d stride=%d B=%d nsplit=%d stream", a.C0, a.N, a.Tq, a.KW, a.stride, a.B, a.nsplit);
         prof_scope_begin("narrow_wgrad_kernel", 2.0 * a.KW * (double)a.C0 * a.N * (double)a.Tq * a.B, s, tag,
                          (double)a.B * a.Tq * (((a.et & 4) ? 2.0 : 4.0) * a.N + 4.0 * a.C0 * a.stride));
-        if (a.et & ~4) { prof_scope_end(s); return hipErrorInvalidValue; }      // (the audio itself is always fp32)
         const dim3 blk(64 * (24 / WUN_NS_NPW));
         // 24 dz rows per launch (the second launch of a 48-row layer writes the other rows of the same partial vectors)
         for (int r0 = 0; r0 < a.N; r0 += 24) {
             a.nrow0 = r0;
-#define WUN_NSK(SI, ZT, CI) hipLaunchKernelGGL((narrow_stream_kernel<15, SI, WUN_NS_NPW, WUN_NS_PF, ZT, CI>), dim3((unsigned)a.nsplit), blk, 0, s, a)
-            if (a.C0 == 1) {
-                if (a.et & 4) { if (a.stride == 2) WUN_NSK(2, bf16_t, 1); else WUN_NSK(1, bf16_t, 1); }
-                else { if (a.stride == 2) WUN_NSK(2, float, 1); else WUN_NSK(1, float, 1); }
-            } else {
-                if (a.et & 4) { if (a.stride == 2) WUN_NSK(2, bf16_t, 2); else WUN_NSK(1, bf16_t, 2); }
-                else { if (a.stride == 2) WUN_NSK(2, float, 2); else WUN_NSK(1, float, 2); }
-            }
-#undef WUN_NSK
+#define WUN_NS_GO(SI, ZT, E, CI) \
+            if (a.stride == SI && a.et == E && a.C0 == CI) \
+                hipLaunchKernelGGL((narrow_stream_kernel<15, SI, WUN_NS_NPW, WUN_NS_PF, ZT, CI>), dim3((unsigned)a.nsplit), blk, 0, s, a);
+            WUN_NS_TILES(WUN_NS_GO)
+#undef WUN_NS_GO
         }
         prof_scope_end(s);
         return hipGetLastError();
     }
-    const size_t lds = narrow_wgrad_lds(a);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const int KT = narrow_kt(a.KW);
-    char tag[160];
     snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d stride=%d B=%d nsplit=%d", a.C0 + a.C1, a.N, a.Tq, a.KW, a.stride, a.B, a.nsplit);
     // (bandwidth-bound: dz rows + the input rows they touch streamed once)
     prof_scope_begin("narrow_wgrad_kernel", 2.0 * a.KW * (double)(a.C0 + a.C1) * a.N * (double)a.Tq * a.B, s, tag,
                      (double)a.B * a.Tq * (((a.et & 4) ? 2.0 : 4.0) * a.N + (((a.et & 1) ? 2.0 : 4.0) * a.C0 + ((a.et & 2) ? 2.0 : 4.0) * a.C1) * a.stride));
-    // element-type combinations the plan produces: all fp32; the bf16 mode's audio-input conv (fp32 audio, bf16 dz);
-    // the bf16 mode's head (fp32 audio + bf16 feature map, fp32 d(pre-activation))
-    if (a.et != 0 && a.et != 4 && a.et != 2) { prof_scope_end(s); return hipErrorInvalidValue; }
-#define WUN_NWL(K, S) WUN_NWE(K, S, 0) WUN_NWE(K, S, 4) WUN_NWE(K, S, 2)
-#define WUN_NWE(K, S, E) \
-    if (KT == K && a.stride == S && a.et == E) { \
+    hipError_t e = hipSuccess;
+#define WUN_NW_GO(K, S, E) \
+    if (r.KT == K && a.stride == S && a.et == E) { \
         auto kern = narrow_wgrad_kernel<K, S, E>; \
         static size_t allowed = 64 * 1024; \
-        if (lds > allowed) { \
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            if (e != hipSuccess) return e; \
-            allowed = lds; \
-        } \
-        hipLaunchKernelGGL(kern, dim3((unsigned)a.nsplit), dim3(256), lds, s, a); \
+        e = raise_lds_limit((const void*)kern, r.lds, allowed); \
+        if (e == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)a.nsplit), dim3(256), r.lds, s, a); \
     }
-    WUN_NWL(3, 1) WUN_NWL(3, 2) WUN_NWL(15, 1) WUN_NWL(15, 2)
-#undef WUN_NWL
-#undef WUN_NWE
+    WUN_NW_TILES(WUN_NW_GO)
+#undef WUN_NW_GO
     prof_scope_end(s);
-    return hipGetLastError();
+    return e != hipSuccess ? e : hipGetLastError();
 }
 
-// the refusals of launch_narrow_wgrad without the launch
-bool narrow_wgrad_launch_ok(const NarrowWgradArgs& a, const WunSwitches& sw) {
-    if (!narrow_wgrad_supported(a)) return false;
-    if (narrow_stream_ok(a, sw)) return (a.et & ~4) == 0;
-    if (narrow_wgrad_lds(a) > 160 * 1024) return false;
-    return a.et == 0 || a.et == 4 || a.et == 2;
-}
+bool narrow_wgrad_launch_ok(const NarrowWgradArgs& a, const WunSwitches& sw) { return narrow_wgrad_resolve(a, sw).err == hipSuccess; }
 
 hipError_t launch_narrow_wgrad_reduce(const NarrowWgradArgs& a, const float* partial, int nsplit, float* grads,
                                       const long long* woff, const long long* boff, hipStream_t s, bool accum) {

@@ -459,61 +459,63 @@ WgradBfGeom wgrad_bf16_geom(const WgradArgs& a) {
     return g;
 }
 
+// the instantiated (MTW, NW) of wgrad_bf16_kernel, stated once
+#define WUN_WGB_TILES(WUN_WGB) \
+    WUN_WGB(4, 1) WUN_WGB(4, 2) WUN_WGB(4, 3) WUN_WGB(4, 4) WUN_WGB(4, 5) \
+    WUN_WGB(8, 1) WUN_WGB(8, 2) WUN_WGB(8, 3)
+
+// one launch of the bf16 weight gradient, or a refusal (wgrad_bf16_resolve): launch_wgrad_bf16 launches it,
+// wgrad_bf16_launch_ok asks
+struct WgradBfLaunch { hipError_t err; WgradBfGeom g; WgradSplit sp; };
+static WgradBfLaunch wgrad_bf16_resolve(const WgradArgs& a) {
+    WgradBfLaunch r = {};
+    r.err = hipErrorInvalidValue;
+    if (!wgrad_bf16_supported(a) || !a.sbf) return r;     // bf16 rows in HBM (the operator entry point converts first)
+    if (!wgrad_rows_aligned(a)) return r;
+    const WgradBfGeom& g = r.g = wgrad_bf16_geom(a);
+#define WUN_WGB_IS(M, N) || (g.MTW == M && g.NW == N)
+    if (!(false WUN_WGB_TILES(WUN_WGB_IS))) return r;
+#undef WUN_WGB_IS
+    if (g.lds > 160 * 1024 || (size_t)(g.NW * 16) * g.ZPe > 65535 || g.XW4 >= (1 << 20)) return r;
+    if ((size_t)g.NCB * (a.loader == LOADER_DEINT ? 2 : 1) * g.XROWS * 16 + 80 > 65535) return r;   // 16-bit LDS destinations
+    if ((long long)8 * g.NCB * g.XW4 > (long long)WUN_WGB_XITP * 256) return r;
+    r.sp = wgrad_split(a, g.TK, (long long)g.nMG * g.nNG);
+    r.err = hipSuccess;
+    return r;
+}
+
 template <int MTW, int NW>
-static hipError_t wgrad_bf16_launch_t(WgradArgs a, const WgradBfGeom& g, hipStream_t s) {
-    a.nQT = (a.Tq + g.TK - 1) / g.TK;
-    const long long units = (long long)a.B * a.nQT;
-    a.units_per_split = (int)((units + a.nsplit - 1) / a.nsplit);
-    if (g.lds > 160 * 1024 || (size_t)(NW * 16) * g.ZPe > 65535 || g.XW4 >= (1 << 20)) return hipErrorInvalidValue;
-    if ((size_t)g.NCB * (a.loader == LOADER_DEINT ? 2 : 1) * g.XROWS * 16 + 80 > 65535) return hipErrorInvalidValue;   // 16-bit LDS destinations
-    if ((long long)8 * g.NCB * g.XW4 > (long long)WUN_WGB_XITP * 256) return hipErrorInvalidValue;
-    const bool acc = a.accum && a.direct;           // (split launches write partials: the plain kernel)
+static hipError_t wgrad_bf16_launch_t(WgradArgs a, const WgradBfLaunch& r, hipStream_t s) {
+    const WgradBfGeom& g = r.g;
+    const bool acc = r.sp.acc;
+    a.nQT = r.sp.nQT;
+    a.units_per_split = r.sp.units_per_split;
     auto kern = acc ? wgrad_bf16_kernel<MTW, NW, true> : wgrad_bf16_kernel<MTW, NW>;
     static size_t lds_allowed[2] = {64 * 1024, 64 * 1024};
-    size_t& allowed = lds_allowed[acc ? 1 : 0];
-    if (g.lds > allowed) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
-        if (e != hipSuccess) return e;
-        allowed = g.lds;
-    }
-    const long long grid = (long long)g.nMG * g.nNG * a.nsplit;
+    hipError_t e = raise_lds_limit((const void*)kern, g.lds, lds_allowed[acc ? 1 : 0]);
+    if (e != hipSuccess) return e;
     char nm[64], tag[160];
     snprintf(nm, sizeof(nm), acc ? "wgrad_bf16_acc_kernel<%d, %d>" : "wgrad_bf16_kernel<%d, %d>", MTW, NW);
     snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nsplit=%d grid=%lld", a.C0 + a.C1, a.N, a.Tq, a.KW, a.loader, a.B,
-             a.nsplit, grid);
+             a.nsplit, r.sp.grid);
     prof_scope_begin(nm, 2.0 * a.KW * (double)(a.C0 + a.C1) * a.N * (double)a.Tq * a.B, s, tag);
     WgBfK k;
     k.NCB = g.NCB; k.nCB = g.nCB; k.nMG = g.nMG; k.nNG = g.nNG; k.TK = g.TK; k.XW4 = g.XW4; k.XROWS = g.XROWS; k.ZPe = g.ZPe;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), g.lds, s, a, k);
+    hipLaunchKernelGGL(kern, dim3((unsigned)r.sp.grid), dim3(256), g.lds, s, a, k);
     prof_scope_end(s);
     return hipGetLastError();
 }
 
 hipError_t launch_wgrad_bf16(const WgradArgs& a, hipStream_t s) {
-    if (!wgrad_bf16_supported(a) || !a.sbf) return hipErrorInvalidValue;     // bf16 rows in HBM (the operator entry point converts first)
-    if ((a.pitch0 & 3) || (a.bs0 & 3) || (reinterpret_cast<uintptr_t>(a.src0) & 15) || a.pitch0 < 4) return hipErrorInvalidValue;
-    if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || a.pitch1 < 4)) return hipErrorInvalidValue;
-    if ((a.dzpitch & 3) || (a.dzbs & 3) || (reinterpret_cast<uintptr_t>(a.dz) & 15) || a.dzpitch < 4) return hipErrorInvalidValue;
-    const WgradBfGeom g = wgrad_bf16_geom(a);
-#define WUN_WGB(M, N) if (g.MTW == M && g.NW == N) return wgrad_bf16_launch_t<M, N>(a, g, s);
-    WUN_WGB(4, 1) WUN_WGB(4, 2) WUN_WGB(4, 3) WUN_WGB(4, 4) WUN_WGB(4, 5)
-    WUN_WGB(8, 1) WUN_WGB(8, 2) WUN_WGB(8, 3)
-#undef WUN_WGB
+    const WgradBfLaunch r = wgrad_bf16_resolve(a);
+    if (r.err != hipSuccess) return r.err;
+#define WUN_WGB_GO(M, N) if (r.g.MTW == M && r.g.NW == N) return wgrad_bf16_launch_t<M, N>(a, r, s);
+    WUN_WGB_TILES(WUN_WGB_GO)
+#undef WUN_WGB_GO
     return hipErrorInvalidValue;
 }
 
-// the refusals of launch_wgrad_bf16 / wgrad_bf16_launch_t without the launch
-bool wgrad_bf16_launch_ok(const WgradArgs& a) {
-    if (!wgrad_bf16_supported(a) || !a.sbf) return false;
-    if ((a.pitch0 & 3) || (a.bs0 & 3) || (reinterpret_cast<uintptr_t>(a.src0) & 15) || a.pitch0 < 4) return false;
-    if (a.C1 > 0 && ((a.pitch1 & 3) || (a.bs1 & 3) || (reinterpret_cast<uintptr_t>(a.src1) & 15) || a.pitch1 < 4)) return false;
-    if ((a.dzpitch & 3) || (a.dzbs & 3) || (reinterpret_cast<uintptr_t>(a.dz) & 15) || a.dzpitch < 4) return false;
-    const WgradBfGeom g = wgrad_bf16_geom(a);
-    if (!((g.MTW == 4 && g.NW >= 1 && g.NW <= 5) || (g.MTW == 8 && g.NW >= 1 && g.NW <= 3))) return false;
-    if (g.lds > 160 * 1024 || (size_t)(g.NW * 16) * g.ZPe > 65535 || g.XW4 >= (1 << 20)) return false;
-    if ((size_t)g.NCB * (a.loader == LOADER_DEINT ? 2 : 1) * g.XROWS * 16 + 80 > 65535) return false;
-    return (long long)8 * g.NCB * g.XW4 <= (long long)WUN_WGB_XITP * 256;
-}
+bool wgrad_bf16_launch_ok(const WgradArgs& a) { return wgrad_bf16_resolve(a).err == hipSuccess; }
 
 hipError_t launch_wgrad_bf16_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
                                     hipStream_t s) {

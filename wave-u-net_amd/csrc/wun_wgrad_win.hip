@@ -641,61 +641,65 @@ long long wgrad_win_partial_floats(const WgradArgs& a, const WunSwitches& sw) { 
 int wgrad_win_units(const WgradArgs& a, const WunSwitches& sw) { const WinGeom g = wgrad_win_geom(a, sw); return a.B * ((a.Tq + g.p.TK - 1) / g.p.TK); }
 int wgrad_win_tiles(const WgradArgs& a, const WunSwitches& sw) { const WinGeom g = wgrad_win_geom(a, sw); return g.p.nMG * g.p.nNG; }
 
+// the instantiated (K = 15?, NW, S) of wgrad_win_kernel, stated once
+#define WUN_WIN_TILES(WUN_WIN) \
+    WUN_WIN(1, 1, 1) WUN_WIN(1, 2, 1) WUN_WIN(1, 3, 1) WUN_WIN(1, 4, 1) WUN_WIN(1, 5, 1) \
+    WUN_WIN(1, 1, 2) WUN_WIN(1, 2, 2) WUN_WIN(1, 3, 2) WUN_WIN(1, 4, 2) WUN_WIN(1, 5, 2) \
+    WUN_WIN(0, 1, 1) WUN_WIN(0, 2, 1) WUN_WIN(0, 3, 1) WUN_WIN(0, 4, 1) WUN_WIN(0, 5, 1) WUN_WIN(0, 6, 1)
+
+// one launch of the register-window weight gradient, or a refusal (wgrad_win_resolve): launch_wgrad_win launches it,
+// wgrad_win_launch_ok asks
+struct WinLaunch { hipError_t err; WinGeom g; WgradSplit sp; };
+static WinLaunch wgrad_win_resolve(const WgradArgs& a, const WunSwitches& sw) {
+    WinLaunch r = {};
+    r.err = hipErrorInvalidValue;
+    if (!wgrad_win_supported(a)) return r;
+    const WinGeom& g = r.g = wgrad_win_geom(a, sw);
+    if (g.lds > 160 * 1024) return r;
+    const long long xs = g.p.zoff / 4, zs = (g.p.bufFloats - g.p.zoff) / 4;
+    if (xs > (long long)WUN_WIN_XIT * g.threads || zs > (long long)WUN_WIN_ZIT * g.threads) return r;
+#define WUN_WIN_IS(k15, nw, ss) || (g.K15 == k15 && g.NW == nw && g.S == ss)
+    if (!(false WUN_WIN_TILES(WUN_WIN_IS))) return r;
+#undef WUN_WIN_IS
+    r.sp = wgrad_split(a, g.p.TK, (long long)g.p.nMG * g.p.nNG);
+    r.err = hipSuccess;
+    return r;
+}
+
 template <bool K15, int NW, int S>
-static hipError_t win_launch_t(WgradArgs a, const WinGeom& g, hipStream_t s, bool occ_log) {
-    a.nQT = (a.Tq + g.p.TK - 1) / g.p.TK;
-    const long long units = (long long)a.B * a.nQT;
-    a.units_per_split = (int)((units + a.nsplit - 1) / a.nsplit);
-    // (only a single-split launch stores the final values: a split launch of an accumulating call is the plain kernel)
-    const bool acc = a.accum && a.direct;
+static hipError_t win_launch_t(WgradArgs a, const WinLaunch& r, hipStream_t s, bool occ_log) {
+    const WinGeom& g = r.g;
+    const bool acc = r.sp.acc;
+    a.nQT = r.sp.nQT;
+    a.units_per_split = r.sp.units_per_split;
     auto kern = acc ? wgrad_win_kernel<K15, NW, S, true> : wgrad_win_kernel<K15, NW, S>;
     static size_t lds_allowed[2] = {64 * 1024, 64 * 1024};
-    size_t& allowed = lds_allowed[acc ? 1 : 0];
-    if (g.lds > allowed) {
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
-        if (e != hipSuccess) return e;
-        allowed = g.lds;
-    }
-    const long long grid = (long long)g.p.nMG * g.p.nNG * a.nsplit;
+    hipError_t e = raise_lds_limit((const void*)kern, g.lds, lds_allowed[acc ? 1 : 0]);
+    if (e != hipSuccess) return e;
     char nm[64];
     snprintf(nm, sizeof(nm), acc ? "wgrad_win_acc_kernel<%d, %d, %d>" : "wgrad_win_kernel<%d, %d, %d>", K15 ? 15 : 5, NW, S);
     char tag[200];
     int occ = -1;
     if (occ_log) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, g.threads, g.lds);
     snprintf(tag, sizeof(tag), "C=%d N=%d T=%d K=%d ld=%d B=%d nsplit=%d grid=%lld w=%dx%d tk=%d lds=%zu occ=%d", a.C0 + a.C1, a.N, a.Tq,
-             a.KW, a.loader, a.B, a.nsplit, grid, 4, g.p.CGW, g.p.TK, g.lds, occ);
+             a.KW, a.loader, a.B, a.nsplit, r.sp.grid, 4, g.p.CGW, g.p.TK, g.lds, occ);
     if (occ_log) fprintf(stderr, "[win] %s %s\n", nm, tag);
     prof_scope_begin(nm, 2.0 * a.KW * (double)(a.C0 + a.C1) * a.N * (double)a.Tq * a.B, s, tag);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(g.threads), g.lds, s, a, g.p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)r.sp.grid), dim3(g.threads), g.lds, s, a, g.p);
     prof_scope_end(s);
     return hipGetLastError();
 }
 
 hipError_t launch_wgrad_win(const WgradArgs& a, hipStream_t s, const WunSwitches& sw) {
-    if (!wgrad_win_supported(a)) return hipErrorInvalidValue;
-    const WinGeom g = wgrad_win_geom(a, sw);
-    if (g.lds > 160 * 1024) return hipErrorInvalidValue;
-    {
-        const long long xs = g.p.zoff / 4, zs = (g.p.bufFloats - g.p.zoff) / 4;
-        if (xs > (long long)WUN_WIN_XIT * g.threads || zs > (long long)WUN_WIN_ZIT * g.threads) return hipErrorInvalidValue;
-    }
-#define WUN_WIN(k15, nw, ss) if (g.K15 == k15 && g.NW == nw && g.S == ss) return win_launch_t<k15 != 0, nw, ss>(a, g, s, sw.win_occ);
-    WUN_WIN(1, 1, 1) WUN_WIN(1, 2, 1) WUN_WIN(1, 3, 1) WUN_WIN(1, 4, 1) WUN_WIN(1, 5, 1)
-    WUN_WIN(1, 1, 2) WUN_WIN(1, 2, 2) WUN_WIN(1, 3, 2) WUN_WIN(1, 4, 2) WUN_WIN(1, 5, 2)
-    WUN_WIN(0, 1, 1) WUN_WIN(0, 2, 1) WUN_WIN(0, 3, 1) WUN_WIN(0, 4, 1) WUN_WIN(0, 5, 1) WUN_WIN(0, 6, 1)
-#undef WUN_WIN
+    const WinLaunch r = wgrad_win_resolve(a, sw);
+    if (r.err != hipSuccess) return r.err;
+#define WUN_WIN_GO(k15, nw, ss) if (r.g.K15 == k15 && r.g.NW == nw && r.g.S == ss) return win_launch_t<k15 != 0, nw, ss>(a, r, s, sw.win_occ);
+    WUN_WIN_TILES(WUN_WIN_GO)
+#undef WUN_WIN_GO
     return hipErrorInvalidValue;
 }
 
-// the refusals of launch_wgrad_win without the launch
-bool wgrad_win_launch_ok(const WgradArgs& a, const WunSwitches& sw) {
-    if (!wgrad_win_supported(a)) return false;
-    const WinGeom g = wgrad_win_geom(a, sw);
-    if (g.lds > 160 * 1024) return false;
-    const long long xs = g.p.zoff / 4, zs = (g.p.bufFloats - g.p.zoff) / 4;
-    if (xs > (long long)WUN_WIN_XIT * g.threads || zs > (long long)WUN_WIN_ZIT * g.threads) return false;
-    return g.S == 2 ? (g.K15 == 1 && g.NW >= 1 && g.NW <= 5) : (g.NW >= 1 && g.NW <= (g.K15 ? 5 : 6));
-}
+bool wgrad_win_launch_ok(const WgradArgs& a, const WunSwitches& sw) { return wgrad_win_resolve(a, sw).err == hipSuccess; }
 
 hipError_t launch_wgrad_win_reduce(const WgradArgs& a, const float* partial, int nsplit, float* out_w, float* out_b,
                                    hipStream_t s, const WunSwitches& sw) {
