@@ -283,10 +283,13 @@ def _step(cfg_over, ocfg, params, B, frames, seed, tag, tune=False):
     return sep
 
 
-def _compare_with_emulation(sep, ocfg, params, mix, targets, gpu_loss, g, tag):
+def _compare_with_emulation(sep, ocfg, params, mix, targets, gpu_loss, g, tag, flip_pool=None):
     """The same step, layer by layer, against oracle/bf16_emul.py: every stored tensor (wun_plan_activation kinds 0 - 9)
     is handed to the emulation as the input of whatever reads it, and compared with what the emulation computes for it
-    from ITS producer's (given) inputs; the loss and every gradient tensor likewise."""
+    from ITS producer's (given) inputs; the loss and every gradient tensor likewise.
+    flip_pool: a list that receives (differing elements, elements) of every stored tensor INSTEAD of the per-tensor
+    EMUL_FLIP_TOL assertion -- for plans whose tensors have a few dozen elements, where one legitimate flip exceeds a per-tensor
+    fraction; the caller asserts the pooled fraction (tests/test_gpu_geometry.py).  Every other assertion stays."""
     L, same = ocfg["num_layers"], not ocfg["context"]
     forced = {}
 
@@ -309,6 +312,8 @@ def _compare_with_emulation(sep, ocfg, params, mix, targets, gpu_loss, g, tag):
         mag = torch.maximum(ref.abs(), inter["_scale"][name]) if name in inter["_scale"] else ref.abs()
         unit = torch.clamp(mag, min=1e-2 * rms + 1e-30) * 2.0 ** -8           # (near-zero elements: fp32 noise, not flips)
         frac = (diff > 0).double().mean().item()
+        if flip_pool is not None:
+            flip_pool.append((int((diff > 0).sum()), diff.numel()))
         mx = (diff / unit).max().item()
         if frac > worst_flip[0]:
             worst_flip = (frac, name)
@@ -329,7 +334,7 @@ def _compare_with_emulation(sep, ocfg, params, mix, targets, gpu_loss, g, tag):
             wv = (l2, n)
     record("bf16_kernel_gradients_rel_l2_vs_layerwise_emulation", "%s (worst: %s)" % (tag, wk[1]), wk[0], EMUL_KERNEL_GRAD_L2_TOL)
     record("bf16_vector_gradients_rel_l2_vs_layerwise_emulation", "%s (worst: %s)" % (tag, wv[1]), wv[0], EMUL_VECTOR_GRAD_L2_TOL)
-    assert worst_flip[0] <= EMUL_FLIP_TOL and worst_ulps[0] <= EMUL_MAX_ULPS, (worst_flip, worst_ulps)
+    assert (flip_pool is not None or worst_flip[0] <= EMUL_FLIP_TOL) and worst_ulps[0] <= EMUL_MAX_ULPS, (worst_flip, worst_ulps)
     assert el <= EMUL_LOSS_TOL, el
     assert wk[0] <= EMUL_KERNEL_GRAD_L2_TOL and wv[0] <= EMUL_VECTOR_GRAD_L2_TOL, (wk, wv)
 

@@ -10,7 +10,11 @@ conv AND a full-rate conv over the skip window (rounds 1 - 5: the even window po
   0 (none early: the non-nested fall-back path, window part after the row-wide part)), both fuse floors and both forms of the
   fused odd-window launch (aligned start with the shifted filter / odd start, `WUN_NO_ODD_ALIGN`) give the same gradients to fp32
   summation order (a + b + c in another order);
-* odd and even crop starts, levels whose window has a single position, stereo / difference / learned-upsampling heads.
+* stereo / difference / learned-upsampling heads.
+
+Every case takes its length from get_padding, whose crops are symmetric and whose bottleneck has at least two positions: all
+of them have even crop starts and windows of three or more positions.  Odd crop starts, windows with a single position and
+levels whose window gradient cannot start early are tests/test_gpu_geometry.py's (tests/_geometry.py: the signature).
 """
 import numpy as np
 import pytest
